@@ -10,6 +10,12 @@ seeded random weights (no checkpoint or HG002 data offline).  Inputs are residen
 timed region.  For N > 1 the driver launches one rank per GPU with torch.distributed.run; sites shard
 with no data-path collective -- RCCL is used only for the barrier and the
 max-over-ranks of the elapsed time.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (with the per-kernel HIP-event times and the roofline
+figures taken inside the timed steps).  --full adds everything else the benchmark measures or checks, each in a pass of its own
+after the timed steps: the oracle comparison and tiling check of the timed outputs, the CPU baseline, the host-buffer pass and
+the skip_empty_rows pass (their --no-* options still turn them off one by one).  --dump-outputs DIR writes what rank 0's last
+timed step computed as DIR/<name>.npy (float32; inputs and weights are seeded, so two builds can be compared output for output).
 """
 from __future__ import annotations
 
@@ -185,6 +191,26 @@ def parity_check(outs, want, period, precision):
     return res
 
 
+DUMP_BYTES_MAX = 60 << 20            # array bytes: with the .npy headers the files stay below 64 MB (10^6 or 2^20)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: array} of the last timed step -> out_dir/<name>.npy, float32 (float64 where the array is).  Above
+    DUMP_BYTES_MAX in all, a fixed sample of rows (seed 0, sorted; every array has one row per site) is written instead, with
+    its row numbers as row_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        rows = max(v.shape[0] for v in arrays.values() if v.ndim)
+        keep = min(rows, DUMP_BYTES_MAX // (total // rows + 8))          # + 8 bytes per row: its float64 row number
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        arrays = {k: (v[idx] if v.ndim and v.shape[0] == rows else v) for k, v in arrays.items()}
+        arrays["row_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+
+
 def bench_train(args):
     """--mode train: BASELINE config 4's unit of work -- one optimisation step of the DAN network (train-mode forward with
     BatchNorm batch statistics and dropout, loss mix, backward, gradient clipping, Adam; dl4vc/trainer.py:109-439) on a
@@ -255,7 +281,7 @@ def bench_train(args):
             ex_ms["normalisers"] += (t_b - t_a) * 1e3; ex_ms["exposed"] += (t_d - t_c) * 1e3; ex_ms["steps"] += 1
         else:
             out = tr.backward(planes, tg, seed=i)
-        tr.apply()
+        out["grad_norm"] = tr.apply()
         return out
 
     def fence():
@@ -278,6 +304,10 @@ def bench_train(args):
         t = torch.tensor([elapsed], device=torch.device("cuda", local_rank) if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        from dl4vc_amd.train import LOSS_NAMES
+        dump_outputs(args.dump_outputs, {"losses": np.array([last[k] for k in LOSS_NAMES], np.float32), "grad_norm": np.array([last["grad_norm"]], np.float32),
+                                         "bin_close": last["bin_close"], "vt_close": last["vt_close"]})
     if rank == 0:
         # algorithmic FLOPs of one step: every GEMM of the forward once more for its data gradient and once for its weight
         # gradient (the layer-1 data gradient IS needed: the embeddings train)
@@ -310,7 +340,7 @@ def bench_train(args):
                     "normalisers_ms_per_step": round(ex_ms["normalisers"] / max(ex_ms["steps"], 1), 3),
                     "note": "rank 0's host clock: exposed = end of the backward pass to the end of the last bucket's exchange"},
                 "last_step": {k: round(float(last[k]), 6) for k in ("loss", "bin", "vt", "af", "cov", "vb", "vr")}}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle.dan_train_oracle import train_step_oracle, TrainHyper as OH
             cores = min(os.cpu_count() or 1, 16)
             torch.set_num_threads(cores)
@@ -346,20 +376,27 @@ def main():
     ap.add_argument("--reads", type=int, default=64)
     ap.add_argument("--chunk-sites", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the oracle's timing passes (its one pass used as the parity check of the timed outputs still runs "
+                    help="--full: skip the oracle's timing passes (its one pass used as the parity check of the timed outputs still runs "
                          "unless --no-oracle-check)")
-    ap.add_argument("--no-oracle-check", action="store_true", help="skip the oracle comparison of the timed outputs")
+    ap.add_argument("--no-oracle-check", action="store_true", help="--full: skip the oracle comparison of the timed outputs")
     ap.add_argument("--no-host-path", action="store_true",
-                    help="omit the informational host-buffer pass (first H2D to last D2H through dan_forward_async/dan_wait)")
+                    help="--full: omit the informational host-buffer pass (first H2D to last D2H through dan_forward_async/dan_wait)")
     ap.add_argument("--precision", type=int, default=0, help="0 fp32 MFMA (headline), 1 bf16x3 split, 2 bf16")
     ap.add_argument("--window", type=int, default=201)
     ap.add_argument("--conv-algo", type=int, default=0, help="fp32 conv form: 0 auto (Winograd F(2,3) on the dilation-2 "
                                                               "layers), 1 direct, 2 winograd")
-    ap.add_argument("--no-skip-pass", action="store_true", help="omit the informational second pass with skip_empty_rows")
+    ap.add_argument("--no-skip-pass", action="store_true", help="--full: omit the informational second pass with skip_empty_rows")
     ap.add_argument("--skip-empty-rows", action="store_true",
                     help="compute the all-padding rows of each pileup once per site (bit-identical outputs; off for the headline, "
                          "which computes every row like the reference)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the passes beyond the headline: oracle comparison and tiling check of the timed outputs, CPU "
+                         "baseline, host-buffer pass, skip_empty_rows pass (off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what rank 0's last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     args.ranks = resolve_ranks(args, sys.argv[1:])           # may start the ranks as a child job and exit with its code
     if args.mode == "train":
         return bench_train(args)
@@ -438,19 +475,22 @@ def main():
         t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: t.cpu().numpy() for k, t in zip(("bin_logits", "vt_logits", "vt_prob", "bp"), outs)})
 
-    # The outputs of the last timed step, checked: against the oracle on rank 0 (the pass that also sizes the cpu_baseline
+    # --full: the outputs of the last timed step, checked: against the oracle on rank 0 (the pass that also sizes the cpu_baseline
     # sample) and through the tiling property on every rank.
-    cpu_line, want = None, None
-    if rank == 0 and not args.no_oracle_check:
-        cpu_line, want = cpu_baseline(cfg, sd, base, timing=(world == 1 and not args.no_cpu_baseline))
-    parity = parity_check(outs, want, 256, cfg.precision)
+    cpu_line, want, parity = None, None, None
+    if args.full:
+        if rank == 0 and not args.no_oracle_check:
+            cpu_line, want = cpu_baseline(cfg, sd, base, timing=(world == 1 and not args.no_cpu_baseline))
+        parity = parity_check(outs, want, 256, cfg.precision)
 
     # Informational (never `value`): SURVEY.md section 8d defines the metric from the first H2D to the last D2H.  One pass
     # of the same batch from PAGEABLE host buffers through the double-buffered asynchronous ABI (pinned staging, H2D /
     # forward / D2H on three streams), outputs checked bit-identical against the device-resident pass.
     host_path = None
-    if world == 1 and not args.no_host_path:
+    if args.full and world == 1 and not args.no_host_path:
         host = [t.cpu().numpy() for t in planes]
         mb = net.handle.query("max_batch")
         got = {k: [] for k in ("bin_logits", "vt_logits", "vt_prob", "bp")}
@@ -484,7 +524,7 @@ def main():
     # Informational second pass (never `value`): the same K steps with the all-padding pileup rows computed once per site
     # (dan_config.skip_empty_rows; outputs bit-identical).  The headline above computes every row, as the reference does.
     skip_value = None
-    if not cfg.skip_empty_rows and not args.no_skip_pass:
+    if args.full and not cfg.skip_empty_rows and not args.no_skip_pass:
         import dataclasses
         net2 = DanNet(dataclasses.replace(cfg, skip_empty_rows=True), device_id=local_rank,
                       chunk_sites=args.chunk_sites).load_state_dict(sd)
@@ -560,7 +600,8 @@ def main():
                                             "note": "informational: empty pileup rows computed once per site; not the headline"}
         if cpu_line is not None:
             line["cpu_baseline"] = cpu_line
-        line["parity"] = parity
+        if parity is not None:
+            line["parity"] = parity
         # whole-forward rate against the direct-convolution MFMA ceiling of the precision, for both definitions of the metric
         ceil_sites = peak * 1e12 / cfg.flops_per_site()
         line["roofline"]["whole_forward_frac"] = round(value / world / ceil_sites, 4)
@@ -575,7 +616,7 @@ def main():
     net.close()
     if dist is not None:
         dist.destroy_process_group()
-    if not parity["ok"]:
+    if parity is not None and not parity["ok"]:
         raise SystemExit("bench.py: outputs of the timed region failed the parity check: %s" % parity)
     if host_path is not None and not host_path["outputs_bit_identical_to_device_resident_pass"]:
         raise SystemExit("bench.py: the host-buffer pass disagrees with the device-resident pass")

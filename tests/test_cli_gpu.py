@@ -141,7 +141,7 @@ def test_bench_two_rank_launch_path(how):
     barrier and the max of the elapsed times (RCCL refuses two ranks on one device).  Sites shard with no data-path
     collective: main.py:117 / SURVEY.md section 8e."""
     import json
-    r = _bench_launch(how, ["--gpus", "2", "--sites", "512", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-skip-pass"])
+    r = _bench_launch(how, ["--gpus", "2", "--sites", "512", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-skip-pass"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout

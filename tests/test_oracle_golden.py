@@ -91,8 +91,8 @@ def test_fp64_oracle_close_to_fp32():
 
 @pytest.mark.parametrize("case", ["bf16_operands_small", "bf16_operands_l301", "bf16_operands_r128_l301"])
 def test_bf16_operands_mode_matches_the_reference_run_with_bf16_rounded_gemm_operands(case):
-    """The pin of the oracle's bf16 = "operands" mode that TRAVELS (tests/test_vs_live_reference.py fuzzes the same comparison,
-    but only where /root/reference exists): oracle/gen_golden.py::gen_bf16_fixtures ran the reference itself with the weights of
+    """The pin of the oracle's bf16 = "operands" mode at fixed shapes (tests/test_vs_live_reference.py fuzzes the same comparison
+    on random structures): oracle/gen_golden.py::gen_bf16_fixtures ran the reference itself with the weights of
     its conv / residual 1x1 / bottleneck modules rounded to bf16 and forward-pre-hooks rounding those modules' inputs -- fp32
     sums, compression / FC / heads untouched -- at 201 and at 301 columns.  Same torch kernels on both sides: the fp32-vs-fp32
     bar.  The fp32 oracle is far from these outputs (the mode IS different), the "storage" mode (the kernel's bf16 activation

@@ -11,16 +11,16 @@ out=gpurun_out/lines_$tag
 mkdir -p "$out"
 if [ "$part" = a ] || [ "$part" = all ]; then
 timeout -k 10 900 tools/profile_round.sh "$tag"
-timeout -k 10 300 python bench.py --reads 100 --sites 32768 --steps 3 --warmup 1 --no-cpu-baseline > "$out/fp32_100x201.json" 2> "$out/fp32_100x201.err"
-timeout -k 10 300 python bench.py --skip-empty-rows --steps 3 --warmup 1 --no-cpu-baseline > "$out/skip_empty_rows.json" 2> "$out/skip.err"
-timeout -k 10 300 python bench.py --precision 1 --steps 3 --warmup 1 --no-cpu-baseline > "$out/bf16x3.json" 2> "$out/bf16x3.err"
-timeout -k 10 300 python bench.py --precision 2 --reads 128 --window 301 --sites 16384 --steps 3 --warmup 1 --no-cpu-baseline > "$out/bf16_128x301.json" 2> "$out/bf16.err"
-timeout -k 10 300 python bench.py --precision 2 --steps 3 --warmup 1 --no-cpu-baseline > "$out/bf16_64x201.json" 2> "$out/bf16b.err"
-timeout -k 10 300 python bench.py --mode train --steps 10 --warmup 2 > "$out/train.json" 2> "$out/train.err"
-timeout -k 10 300 python bench.py --mode train --train-batch 10 --steps 20 --warmup 3 --no-cpu-baseline > "$out/train_b10.json" 2> "$out/train_b10.err"
+timeout -k 10 300 python bench.py --full --reads 100 --sites 32768 --steps 3 --warmup 1 --no-cpu-baseline > "$out/fp32_100x201.json" 2> "$out/fp32_100x201.err"
+timeout -k 10 300 python bench.py --full --skip-empty-rows --steps 3 --warmup 1 --no-cpu-baseline > "$out/skip_empty_rows.json" 2> "$out/skip.err"
+timeout -k 10 300 python bench.py --full --precision 1 --steps 3 --warmup 1 --no-cpu-baseline > "$out/bf16x3.json" 2> "$out/bf16x3.err"
+timeout -k 10 300 python bench.py --full --precision 2 --reads 128 --window 301 --sites 16384 --steps 3 --warmup 1 --no-cpu-baseline > "$out/bf16_128x301.json" 2> "$out/bf16.err"
+timeout -k 10 300 python bench.py --full --precision 2 --steps 3 --warmup 1 --no-cpu-baseline > "$out/bf16_64x201.json" 2> "$out/bf16b.err"
+timeout -k 10 300 python bench.py --full --mode train --steps 10 --warmup 2 > "$out/train.json" 2> "$out/train.err"
+timeout -k 10 300 python bench.py --full --mode train --train-batch 10 --steps 20 --warmup 3 --no-cpu-baseline > "$out/train_b10.json" 2> "$out/train_b10.err"
 # windows of 301 columns on the two parity-grade precisions (two units per read; round 5)
-timeout -k 10 300 python bench.py --reads 128 --window 301 --sites 8192 --steps 2 --warmup 1 --no-cpu-baseline --no-skip-pass > "$out/fp32_128x301.json" 2> "$out/fp32_128x301.err"
-timeout -k 10 300 python bench.py --precision 1 --reads 128 --window 301 --sites 16384 --steps 3 --warmup 1 --no-cpu-baseline --no-skip-pass > "$out/bf16x3_128x301.json" 2> "$out/bf16x3_128x301.err"
+timeout -k 10 300 python bench.py --full --reads 128 --window 301 --sites 8192 --steps 2 --warmup 1 --no-cpu-baseline --no-skip-pass > "$out/fp32_128x301.json" 2> "$out/fp32_128x301.err"
+timeout -k 10 300 python bench.py --full --precision 1 --reads 128 --window 301 --sites 16384 --steps 3 --warmup 1 --no-cpu-baseline --no-skip-pass > "$out/bf16x3_128x301.json" 2> "$out/bf16x3_128x301.err"
 fi
 if [ "$part" = c ]; then
     timeout -k 10 400 tools/profile_pmc.sh "pmc_train_b10_$tag" --mode train --train-batch 10 --steps 2 --warmup 1 --no-cpu-baseline

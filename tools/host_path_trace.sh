@@ -9,6 +9,6 @@ out=$root/gpurun_out/trace_$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$out/t" -- python3 "$root/bench.py" --precision 2 --reads 128 --window 301 --sites 16384 --steps 1 --warmup 1 --no-cpu-baseline --no-skip-pass --no-oracle-check > "$out/bench.json" 2> "$out/bench.err"
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$out/t" -- python3 "$root/bench.py" --full --precision 2 --reads 128 --window 301 --sites 16384 --steps 1 --warmup 1 --no-cpu-baseline --no-skip-pass --no-oracle-check > "$out/bench.json" 2> "$out/bench.err"
 cd "$root"
 python tools/host_path_gaps.py "$out/t" | tee "$out/gaps.txt"

@@ -5,6 +5,7 @@ set -e
 ARGS="${1:---precision 1 --sites 32768}"
 N=${2:-2}
 TAG=$(echo "$ARGS" | tr -c "a-zA-Z0-9" "_")
+ARGS="--full $ARGS"          # the parity of the timed outputs printed below is checked under --full
 shift 2 || true
 BUILDS="${@:-base tree}"
 for i in $(seq 1 $N); do
