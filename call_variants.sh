@@ -3,10 +3,12 @@
 # candidates.hdf (tools/convert_bam_single_reads.py here: own BAM / FASTA readers, no pysam), scoring with the MI355X-native DAN
 # forward, then sort, genotype thresholds, multi-allele join and bgzip/tabix (with bcftools/htslib when installed, else in
 # process: dl4vc_amd/vcfpost.py).  The first stage -- BAM -> candidates.vcf (tools/candidate_generator.py, reference
-# call_variants.sh:76-83) -- is CPU pre-processing outside this implementation: OUTDIR must already hold candidates.vcf.
-# With an OUTDIR that also holds candidates.hdf, -i / -r are not needed and the conversion is skipped.
+# call_variants.sh:76-83) -- runs when OUTDIR holds neither candidates.hdf nor candidates.vcf and -i is given: per-read allele
+# detection and per-locus counting on the GPU (libdl4vc_cand.so), with the reference's flags; -b restricts it to a BED file
+# (the reference requires -b; here it is optional and its absence means the whole BAM).  An existing candidates.vcf is used
+# as it is.  With an OUTDIR that also holds candidates.hdf, -i / -r are not needed and the conversion is skipped.
 set -e
-usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-g GPUS] [-p PROCESSES]   (OUTDIR must hold candidates.vcf)"; exit 1; }
+usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES]"; exit 1; }
 GPUS=1
 PROCS=16
 while getopts "m:o:g:i:r:b:p:h" opt; do
@@ -16,13 +18,20 @@ while getopts "m:o:g:i:r:b:p:h" opt; do
     g) GPUS=$OPTARG ;;
     i) BAM=$OPTARG ;;
     r) REFERENCE=$OPTARG ;;
-    b) BED=$OPTARG ;;       # (accepted for compatibility with the reference's flag line; only candidate generation uses it)
+    b) BED=$OPTARG ;;       # candidate generation only
     p) PROCS=$OPTARG ;;
     *) usage ;;
   esac
 done
 [ -z "$MODEL" ] || [ -z "$OUTDIR" ] && usage
 SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
+if [ ! -f "$OUTDIR/candidates.hdf" ] && [ ! -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ]; then
+  mkdir -p "$OUTDIR"
+  printf "Generate candidate VCF...\n"
+  python "$SCRIPTDIR/tools/candidate_generator.py" --input "$BAM" --output "$OUTDIR/candidates.vcf" \
+      --snp_min_freq 0.075 --indel_min_freq 0.02 ${BED:+--bedfile "$BED"} --keep_multialleles \
+      > "$OUTDIR/candidate_generator.log" 2>&1
+fi
 if [ ! -f "$OUTDIR/candidates.hdf" ]; then
   [ -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ] && [ -n "$REFERENCE" ] || { echo "missing $OUTDIR/candidates.hdf (or candidates.vcf with -i BAM -r REFERENCE to make it)"; exit 1; }
   printf "Convert candidates to HDF...\n"

@@ -414,7 +414,9 @@ def build_bai(bam_path: str, out_path: Optional[str] = None) -> BaiIndex:
 # BAM writer (tests, tools/make_test_bam.py): the inverse of parse_record, kept independent of it
 # ------------------------------------------------------------------------------------------------------
 def pack_record(tid: int, pos: int, name: str, flag: int, mapq: int, cigar: Sequence[Tuple[int, int]], seq: str,
-                qual: Optional[Sequence[int]] = None, next_tid: int = -1, next_pos: int = -1, tlen: int = 0) -> bytes:
+                qual: Optional[Sequence[int]] = None, next_tid: int = -1, next_pos: int = -1, tlen: int = 0,
+                aux: bytes = b"") -> bytes:
+    """One length-prefixed record; ``aux`` is the raw tag area (e.g. ``b"MDZ" + md + b"\\0"``), appended as given."""
     l_seq = len(seq)
     end = pos + (sum(l for op, l in cigar if _CONSUMES_REF[op]) or 1)
     nm = name.encode("ascii") + b"\x00"
@@ -428,6 +430,7 @@ def pack_record(tid: int, pos: int, name: str, flag: int, mapq: int, cigar: Sequ
         codes.append(0)
     out += bytes((codes[i] << 4) | codes[i + 1] for i in range(0, len(codes), 2))
     out += bytes(qual) if qual is not None else b"\xff" * l_seq
+    out += aux
     return struct.pack("<i", len(out)) + bytes(out)
 
 

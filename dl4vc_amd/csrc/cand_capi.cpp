@@ -1,0 +1,319 @@
+// Host side of libdl4vc_cand.so (C ABI: include/dl4vc_candgen.h).  Worker threads, each with its own BAM handle, fetch the
+// records of a batch of subregions (BAI linear index, htslib's overlap rule: pos < end and bam_endpos > start, no flag
+// filter), frame and validate every record (bam_native.h::frame_record) and gather them into one pinned buffer; the device
+// does the rest (cand_kernels.hip).  A read overlapping two subregions is listed once for each, as the reference's per
+// subregion fetch counts it.  Every extern "C" body catches what it throws: a corrupt file is an error code, never an abort.
+#include "../../include/dl4vc_candgen.h"
+#include "bam_native.h"
+#include "cand_device.h"
+
+#include <atomic>
+#include <chrono>
+#include <cstdarg>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+namespace {
+
+thread_local std::string g_err;
+
+int fail(int code, const char* fmt, ...) {
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+const char BASES[] = "=ACMGRSVTWYHKDBN";
+constexpr int64_t BATCH_BASES = 4000000;     // subregion length gathered per device batch
+constexpr uint32_t MAX_BATCH_SUBS = 1u << 20;
+
+// htslib's bam_endpos: an unmapped read, or one without reference-consuming operations, covers one position
+int64_t endpos(const uint8_t* b, const bamn::RecordFrame& fr) {
+    if (fr.flag & 0x4) return (int64_t)fr.pos + 1;
+    int64_t rlen = 0;
+    for (int i = 0; i < fr.n_cig; ++i) {
+        uint32_t v;
+        memcpy(&v, b + fr.cigar_off + 4 * i, 4);
+        const int op = v & 0xf;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += v >> 4;
+    }
+    return (int64_t)fr.pos + (rlen > 0 ? rlen : 1);
+}
+
+struct Gathered {
+    std::vector<uint8_t> bytes;
+    std::vector<cand::ReadMeta> meta;   // off relative to bytes
+    std::string err;
+};
+
+}  // namespace
+
+struct cg_handle {
+    std::string bam_path;
+    bamn::BamFile header;
+    bamn::Bai bai;
+    bool have_bai = false;
+    cg_options opt{};
+    hipStream_t stream = nullptr;
+    cand::Workspace* ws = nullptr;
+    uint8_t* pinned = nullptr;
+    size_t pinned_cap = 0;
+    std::vector<cg_candidate> out;
+    ~cg_handle() {
+        if (pinned) (void)hipHostFree(pinned);
+        cand::workspace_destroy(ws);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+
+// the records of subregion s (one BAM handle per worker)
+bool fetch_sub(cg_handle* h, bamn::BamFile& bam, std::vector<uint8_t>& blk, const cg_region& rg, uint32_t s, Gathered& g) {
+    int64_t at = bam.first_record;
+    if (h->have_bai) {
+        const uint64_t off = h->bai.linear_offset(rg.tid, rg.start);
+        if (off == 0) return true;
+        at = (int64_t)off;
+    }
+    if (!bam.r.seek(at)) { g.err = "BGZF: " + bam.r.err; return false; }
+    for (;;) {
+        const int64_t voff = bam.r.tell();
+        const int got = bam.next_block(blk);
+        if (got == 0) return true;
+        if (got < 0) { g.err = bam.err + " (record at virtual offset " + std::to_string(voff) + ")"; return false; }
+        bamn::RecordFrame fr;
+        const char* why = bamn::frame_record(blk.data(), blk.size(), fr);
+        if (why) { g.err = std::string(why) + " (record at virtual offset " + std::to_string(voff) + ")"; return false; }
+        if (fr.tid != rg.tid) {
+            if (fr.tid < 0 || fr.tid > rg.tid) return true;
+            continue;
+        }
+        if (fr.pos >= rg.end) return true;
+        if (endpos(blk.data(), fr) <= rg.start) continue;
+        cand::ReadMeta m;
+        m.off = g.bytes.size();
+        m.len = (uint32_t)blk.size();
+        m.sub = s;
+        m.md_off = fr.md_off;
+        m.md_len = fr.md_len;
+        g.bytes.insert(g.bytes.end(), blk.begin(), blk.end());
+        g.bytes.resize((g.bytes.size() + 3) & ~(size_t)3);
+        g.meta.push_back(m);
+    }
+}
+
+void decode(const cand::DevCand& c, cg_candidate& o) {
+    auto base = [&](int i) { return BASES[(c.w[i >> 4] >> (60 - 4 * (i & 15))) & 0xf]; };
+    memset(o.ref, 0, sizeof o.ref);
+    memset(o.alt, 0, sizeof o.alt);
+    if (c.kind == 0) {
+        o.ref[0] = BASES[(c.w[0] >> 60) & 0xf];
+        o.alt[0] = BASES[(c.w[0] >> 56) & 0xf];
+        return;
+    }
+    const int n = (int)std::min<uint32_t>(c.len, CG_MAX_ALLELE_LEN);
+    char* seq = c.kind == cand::KIND_INS ? o.alt : o.ref;
+    char* one = c.kind == cand::KIND_INS ? o.ref : o.alt;
+    for (int i = 0; i < n; ++i) seq[i] = base(i);
+    one[0] = seq[0];
+}
+
+int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg_stats& st) {
+    const uint32_t n_subs = (uint32_t)(b1 - b0);
+    const int nt = std::max(1, std::min<int>(h->opt.threads, (int)n_subs));
+    std::vector<Gathered> per(n_subs);
+    std::atomic<uint32_t> next{0};
+    std::mutex open_mu;
+    std::string open_err;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto worker = [&]() {
+        bamn::BamFile bam;
+        std::vector<uint8_t> blk;
+        if (!bam.open(h->bam_path)) {
+            std::lock_guard<std::mutex> lk(open_mu);
+            open_err = bam.err;
+            return;
+        }
+        for (;;) {
+            const uint32_t s = next.fetch_add(1);
+            if (s >= n_subs) return;
+            try {
+                fetch_sub(h, bam, blk, regions[b0 + s], s, per[s]);
+            } catch (const std::exception& e) {
+                per[s].err = std::string("host framing: ") + e.what();
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int i = 1; i < nt; ++i) pool.emplace_back(worker);
+    worker();
+    for (auto& t : pool) t.join();
+    if (!open_err.empty()) return fail(-3, "%s", open_err.c_str());
+    for (uint32_t s = 0; s < n_subs; ++s)
+        if (!per[s].err.empty()) return fail(-3, "%s", per[s].err.c_str());
+    // the device is set up only now, after the first batch framed cleanly (framing errors need no GPU)
+    if (hipSetDevice(h->opt.device) != hipSuccess) return fail(-2, "hipSetDevice(%d) failed", h->opt.device);
+    if (!h->stream && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(-2, "hipStreamCreate failed");
+    if (!h->ws && !(h->ws = cand::workspace_create())) return fail(-2, "cannot create the device workspace");
+    // gather into the pinned buffer, subregion by subregion
+    uint64_t bytes = 0, n_reads = 0;
+    for (auto& g : per) { bytes += g.bytes.size(); n_reads += g.meta.size(); }
+    if (bytes + 1 > h->pinned_cap) {
+        if (h->pinned) (void)hipHostFree(h->pinned);
+        h->pinned = nullptr; h->pinned_cap = 0;
+        const size_t want = bytes + bytes / 4 + 4096;
+        if (hipHostMalloc((void**)&h->pinned, want, hipHostMallocDefault) != hipSuccess) return fail(-2, "hipHostMalloc(%zu) failed", want);
+        h->pinned_cap = want;
+    }
+    std::vector<cand::ReadMeta> meta;
+    meta.reserve(n_reads);
+    std::vector<cand::SubDesc> subs(n_subs);
+    uint64_t at = 0;
+    int64_t cov = 0;
+    for (uint32_t s = 0; s < n_subs; ++s) {
+        const cg_region& rg = regions[b0 + s];
+        subs[s].start = rg.start;
+        subs[s].end = rg.end;
+        subs[s].cov_base = cov;
+        cov += (int64_t)rg.end - rg.start + 2;
+        Gathered& g = per[s];
+        if (!g.bytes.empty()) memcpy(h->pinned + at, g.bytes.data(), g.bytes.size());
+        for (auto m : g.meta) { m.off += at; meta.push_back(m); }
+        at += g.bytes.size();
+        std::vector<uint8_t>().swap(g.bytes);
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    st.host_frame_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    const char* msg = nullptr;
+    if (cand::upload(h->ws, h->pinned, bytes, meta.data(), n_reads, subs.data(), n_subs, cov, h->stream, &msg))
+        return fail(-2, "device upload: %s", msg);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(-2, "device upload failed");
+    const auto t2 = std::chrono::steady_clock::now();
+    st.upload_ms += std::chrono::duration<double, std::milli>(t2 - t1).count();
+    const cand::DevCand* dc = nullptr;
+    const uint8_t* status = nullptr;
+    uint64_t n_out = 0, n_events = 0, n_unique = 0;
+    cand::BatchTimes bt{};
+    if (cand::run_batch(h->ws, n_reads, n_subs, cov, h->opt.max_len_indel_allele, h->opt.snp_min_freq, h->opt.indel_min_freq,
+                        h->stream, &dc, &n_out, &status, &n_events, &n_unique, &bt, &msg))
+        return fail(-2, "device: %s", msg);
+    st.device_ms += bt.device_ms;
+    st.reads += (int64_t)n_reads;
+    for (uint64_t r = 0; r < n_reads; ++r) {
+        const uint8_t v = status[r];
+        switch (v & 0xf) {
+            case cand::ST_NO_MD: ++st.reads_no_md; break;
+            case cand::ST_NO_PAIRS: ++st.reads_no_pairs; break;
+            case cand::ST_UNSUPPORTED: ++st.reads_unsupported; break;
+            case cand::ST_MALFORMED: ++st.reads_malformed; break;
+            default: break;
+        }
+        if (v & cand::ST_DEL_DROPPED) ++st.reads_deletions_dropped;
+    }
+    st.allele_events += (int64_t)n_events;
+    st.alleles += (int64_t)n_unique;
+    st.candidates += (int64_t)n_out;
+    ++st.batches;
+    const size_t o = h->out.size();
+    h->out.resize(o + n_out);
+    for (uint64_t i = 0; i < n_out; ++i) {
+        cg_candidate& c = h->out[o + i];
+        c.region = (int32_t)(b0 + dc[i].sub);
+        c.tid = regions[c.region].tid;
+        c.pos0 = dc[i].pos;
+        c.depth = dc[i].depth;
+        c.count = dc[i].count;
+        decode(dc[i], c);
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* cg_last_error(void) { return g_err.c_str(); }
+
+int cg_open(const char* bam_path, const char* bai_path, const cg_options* opt, cg_handle_t** out) {
+    try {
+        if (!out || !bam_path || !opt) return fail(-1, "cg_open: null argument");
+        *out = nullptr;
+        if (opt->max_len_indel_allele > CG_MAX_ALLELE_LEN)
+            return fail(-1, "max_len_indel_allele %d exceeds the allele key's limit of %d bases", opt->max_len_indel_allele,
+                        CG_MAX_ALLELE_LEN);
+        std::unique_ptr<cg_handle> h(new cg_handle());
+        h->bam_path = bam_path;
+        h->opt = *opt;
+        if (h->opt.threads <= 0) h->opt.threads = 1;
+        if (!h->header.open(bam_path)) return fail(-3, "%s", h->header.err.c_str());
+        if (bai_path && *bai_path) {
+            if (!h->bai.load(bai_path)) return fail(-3, "cannot read the BAI index %s", bai_path);
+            h->have_bai = true;
+        }
+        *out = h.release();
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(-4, "cg_open: %s", e.what());
+    } catch (...) {
+        return fail(-4, "cg_open: unknown exception");
+    }
+}
+
+int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg_candidate** out, int64_t* n_out, cg_stats* stats) {
+    try {
+        if (!h || !out || !n_out || (n_regions > 0 && !regions)) return fail(-1, "cg_run: null argument");
+        const auto t0 = std::chrono::steady_clock::now();
+        cg_stats st{};
+        h->out.clear();
+        for (int64_t i = 0; i < n_regions; ++i) {
+            const cg_region& r = regions[i];
+            if (r.tid < 0 || r.tid >= (int)h->header.refs.size()) return fail(-1, "region %lld: tid %d not in the BAM header", (long long)i, r.tid);
+            if (r.start < 0 || r.end < r.start) return fail(-1, "region %lld: bad interval [%d, %d)", (long long)i, r.start, r.end);
+        }
+        int64_t b0 = 0;
+        while (b0 < n_regions) {
+            int64_t b1 = b0, len = 0;
+            while (b1 < n_regions && (b1 == b0 || (len + regions[b1].end - regions[b1].start <= BATCH_BASES && b1 - b0 < MAX_BATCH_SUBS))) {
+                len += (int64_t)regions[b1].end - regions[b1].start;
+                ++b1;
+            }
+            const int rc = run_batch(h, regions, b0, b1, st);
+            if (rc) return rc;
+            b0 = b1;
+        }
+        st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (stats) *stats = st;
+        *out = h->out.data();
+        *n_out = (int64_t)h->out.size();
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(-4, "cg_run: %s", e.what());
+    } catch (...) {
+        return fail(-4, "cg_run: unknown exception");
+    }
+}
+
+int32_t cg_n_refs(const cg_handle_t* h) { return h ? (int32_t)h->header.refs.size() : 0; }
+const char* cg_ref_name(const cg_handle_t* h, int32_t tid) {
+    return (h && tid >= 0 && tid < (int32_t)h->header.refs.size()) ? h->header.refs[tid].c_str() : nullptr;
+}
+int64_t cg_ref_length(const cg_handle_t* h, int32_t tid) {
+    return (h && tid >= 0 && tid < (int32_t)h->header.lengths.size()) ? h->header.lengths[tid] : -1;
+}
+
+void cg_close(cg_handle_t* h) {
+    try {
+        delete h;
+    } catch (...) {
+    }
+}
+
+}  // extern "C"

@@ -1,0 +1,62 @@
+// Types shared by the candidate generator's kernels (cand_kernels.hip) and its host side (cand_capi.cpp).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace cand {
+
+// one framed record of one subregion: its bytes are buf[off, off + len) (the bytes behind block_size)
+struct ReadMeta {
+    uint64_t off;
+    uint32_t len;
+    uint32_t sub;        // subregion index within the batch
+    int32_t md_off;      // MD:Z value within the record, -1 when absent
+    int32_t md_len;
+};
+
+struct SubDesc {
+    int32_t start, end;  // fetch [start, end), alleles at start <= pos <= end
+    int64_t cov_base;    // first element of this subregion's coverage slot (end - start + 2 ints)
+};
+
+// per-read status (the low bits) and flag
+enum : uint8_t { ST_OK = 0, ST_NO_MD = 1, ST_NO_PAIRS = 2, ST_UNSUPPORTED = 3, ST_MALFORMED = 4 };
+constexpr uint8_t ST_DEL_DROPPED = 0x10;
+
+// Allele keys.  SNP: sub(24) | pos(32) | ref(4) | alt(4).  Indel: w[0] = sub(24) | pos(32) | kind(2) | len(6), then the bases
+// (anchor first: ALT of an insertion, REF of a deletion) as BAM nibble codes, 16 per word from the top.
+constexpr int KIND_INS = 1, KIND_DEL = 2;
+constexpr int KEY_BASES = 64;
+struct IndelKey {
+    uint64_t w[5];
+};
+__host__ __device__ inline bool operator==(const IndelKey& a, const IndelKey& b) {
+    return a.w[0] == b.w[0] && a.w[1] == b.w[1] && a.w[2] == b.w[2] && a.w[3] == b.w[3] && a.w[4] == b.w[4];
+}
+__host__ __device__ inline bool operator!=(const IndelKey& a, const IndelKey& b) { return !(a == b); }
+
+struct DevCand {
+    int32_t sub, pos, depth, count;
+    uint32_t kind, len;  // kind 0 = SNP (w[0] top byte = ref << 4 | alt)
+    uint64_t w[4];
+};
+
+struct Workspace;     // device buffers, grown on demand (cand_kernels.hip)
+
+struct BatchTimes {
+    float device_ms;
+};
+
+Workspace* workspace_create();
+void workspace_destroy(Workspace* ws);
+// Runs one batch whose framed records are already on the device (ws buffers from upload()).  Returns 0 or a negative code
+// with msg set.  out / n_out: survivors in a host array owned by the workspace; status: one byte per read, host.
+int upload(Workspace* ws, const uint8_t* recs, uint64_t rec_bytes, const ReadMeta* meta, uint64_t n_reads,
+           const SubDesc* subs, uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg);
+int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len, int max_len, double snp_min, double indel_min,
+              hipStream_t stream, const DevCand** out, uint64_t* n_out, const uint8_t** status, uint64_t* n_events,
+              uint64_t* n_unique, BatchTimes* t, const char** msg);
+
+}  // namespace cand

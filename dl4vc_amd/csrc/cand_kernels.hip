@@ -1,0 +1,549 @@
+// Candidate generation on the GPU (reference tools/candidate_generator.py::build_allele_stats + filter_alleles_by_frequency):
+// one thread per framed read walks its CIGAR and MD, adds two coverage difference events per aligned M/=/X run, and emits one
+// fixed-width key per allele; the keys are radix sorted and run-length encoded (rocPRIM), the coverage events scanned into
+// depth, and each distinct allele kept when min(count, depth) / depth > the minimum frequency (double precision).  Counting
+// by sort + run-length encoding is exact and independent of the order the reads run in; the only atomics are integer adds,
+// two per aligned run (not per base), and one per survivor.
+//
+// Per read, the semantics of the reference's detect_variants on pysam's get_aligned_pairs(with_seq=True):
+//   * the pairs before the first and after the last reference-consuming operation are trimmed (which drops insertions next to
+//     a clip); a soft clip between them reads as an insertion, as its pairs do;
+//   * SNP: an MD mismatch letter in ACGT at an aligned base in ACGT;
+//   * insertion: a run of query-only pairs, anchored on the pair before it (a deleted position anchors at that position);
+//   * deletion: a run of reference-only pairs, REF = anchor + deleted bases, ALT = anchor; a run at the first pair takes the
+//     LAST pair as its anchor (Python's aligned_pairs[-1]); a run anchored on an inserted base raises TypeError in the
+//     reference, which drops every deletion of that read;
+//   * an allele whose REF or ALT is longer than max_len is dropped; only alleles at start <= pos <= end count.
+// A read whose MD does not agree with its CIGAR (runs past it, ends short, a '^' run of the wrong length, a letter outside the
+// BAM alphabet) is marked malformed and gives no alleles.  Every byte read is bounded by the read's framed length.
+#include "cand_device.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_run_length_encode.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <vector>
+
+namespace cand {
+namespace {
+
+__device__ inline uint32_t ld16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+__device__ inline uint32_t ld32(const uint8_t* p) {
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+// an MD letter as a BAM nibble code ("=ACMGRSVTWYHKDBN"), -1 outside the alphabet (lower case included)
+__device__ inline int letter_code(uint8_t c) {
+    switch (c) {
+        case 'A': return 1; case 'C': return 2; case 'M': return 3; case 'G': return 4; case 'R': return 5; case 'S': return 6;
+        case 'V': return 7; case 'T': return 8; case 'W': return 9; case 'Y': return 10; case 'H': return 11; case 'K': return 12;
+        case 'D': return 13; case 'B': return 14; case 'N': return 15; default: return -1;
+    }
+}
+__device__ inline bool is_acgt(int code) { return code == 1 || code == 2 || code == 4 || code == 8; }
+__device__ inline bool is_upper(uint8_t c) { return c >= 'A' && c <= 'Z'; }
+
+enum { OP_M = 0, OP_I = 1, OP_D = 2, OP_N = 3, OP_S = 4, OP_H = 5, OP_P = 6, OP_EQ = 7, OP_X = 8 };
+__device__ inline bool aligned_op(int op) { return op == OP_M || op == OP_EQ || op == OP_X; }
+
+// The MD string as pysam's build_alignment_sequence reads it, held to a strict grammar: matches are decimal counts, a
+// mismatch is one upper-case letter, a deletion '^' plus exactly the deleted letters (ended by a digit or the end).
+struct Md {
+    const uint8_t* p;
+    int n, i;
+    uint32_t rem;
+    bool in_del, bad;
+
+    // the reference base of an aligned pair whose read base is rc
+    __device__ int match(int rc, bool& mism) {
+        end_del();
+        while (rem == 0) {
+            if (bad || i >= n) { bad = true; return 0; }
+            const uint8_t c = p[i];
+            if (c >= '0' && c <= '9') {
+                uint32_t v = 0;
+                int digits = 0;
+                while (i < n && p[i] >= '0' && p[i] <= '9') {
+                    v = v * 10 + (p[i] - '0');
+                    ++i;
+                    if (++digits > 9) { bad = true; return 0; }
+                }
+                rem = v;
+                continue;
+            }
+            const int code = letter_code(c);
+            if (code < 0) { bad = true; return 0; }    // '^' where a base is aligned, or a letter outside the alphabet
+            ++i;
+            mism = true;
+            return code;
+        }
+        --rem;
+        mism = false;
+        return rc;
+    }
+    // the deleted reference base of a reference-only pair
+    __device__ int del() {
+        if (rem != 0) { bad = true; return 0; }
+        if (!in_del) {
+            while (i < n && p[i] == '0') ++i;
+            if (i >= n || p[i] != '^') { bad = true; return 0; }
+            ++i;
+            in_del = true;
+        }
+        const int code = i < n ? letter_code(p[i]) : -1;
+        if (code < 0) { bad = true; return 0; }
+        ++i;
+        return code;
+    }
+    // a '^' run ends at a pair that is not a deletion: a letter still waiting means the run was longer than the deletion
+    __device__ void end_del() {
+        if (in_del) {
+            if (i < n && is_upper(p[i])) bad = true;
+            in_del = false;
+        }
+    }
+    __device__ void finish() {
+        end_del();
+        while (i < n && p[i] == '0') ++i;
+        if (rem != 0 || i != n) bad = true;
+    }
+};
+
+struct Sink {
+    // count mode (keys == nullptr) or emit mode
+    uint64_t* snp;
+    IndelKey* indel;
+    uint32_t n_snp, n_indel;
+};
+
+struct Pair {
+    int kind;      // -1 none, OP_M, OP_D, OP_I
+    int32_t pos;
+    int code;
+};
+
+struct Walk {
+    const uint8_t* cig;
+    const uint8_t* seq;
+    int n_cig, k0, k1;
+    int32_t pos, lo, hi;
+    uint32_t sub;
+    int max_len;
+    bool del_dropped;
+
+    __device__ int read_code(int q) const { return (q & 1) ? (seq[q >> 1] & 0xf) : (seq[q >> 1] >> 4); }
+
+    // dry = true: only the MD walk, returning the last pair (the anchor of a deletion run at the first pair)
+    __device__ bool run(bool dry, Pair last_pair, Sink& out, Pair* last_out) const {
+        Md md{nullptr, 0, 0, 0, false, false};
+        md.p = md_p; md.n = md_n;
+        int32_t rp = pos;
+        int qp = 0;
+        Pair prev{-1, 0, 0};
+        int run_kind = -1, run_len = 0;
+        int32_t run_pos = 0;
+        uint64_t run_w[4] = {0, 0, 0, 0};
+        bool first = true;
+        auto close_run = [&]() {
+            if (run_kind < 0) return;
+            const bool keep = run_len <= max_len && run_pos >= lo && run_pos <= hi && !(run_kind == OP_D && del_dropped);
+            if (keep) {
+                if (out.indel) {
+                    IndelKey k;
+                    k.w[0] = ((uint64_t)sub << 40) | ((uint64_t)(uint32_t)run_pos << 8) |
+                             ((uint64_t)(run_kind == OP_I ? KIND_INS : KIND_DEL) << 6) | (uint64_t)run_len;
+                    for (int j = 0; j < 4; ++j) k.w[j + 1] = run_w[j];
+                    out.indel[out.n_indel] = k;
+                }
+                ++out.n_indel;
+            }
+            run_kind = -1;
+        };
+        auto push_base = [&](int code) {
+            if (run_len < KEY_BASES) run_w[run_len >> 4] |= (uint64_t)code << (60 - 4 * (run_len & 15));
+            ++run_len;
+        };
+        auto start_run = [&](int kind, const Pair& anchor) {
+            run_kind = kind;
+            run_pos = anchor.pos;
+            run_len = 0;
+            run_w[0] = run_w[1] = run_w[2] = run_w[3] = 0;
+            push_base(anchor.code);
+        };
+        for (int k = 0; k < n_cig; ++k) {
+            const uint32_t c = ld32(cig + 4 * k);
+            const int op = c & 0xf;
+            const int l = (int)(c >> 4);
+            const bool q = aligned_op(op) || op == OP_I || op == OP_S;
+            if (k < k0 || k > k1) { if (q) qp += l; continue; }
+            if (aligned_op(op)) {
+                for (int i = 0; i < l; ++i) {
+                    if (!dry && run_kind >= 0) close_run();
+                    const int rc = read_code(qp + i);
+                    bool mism = false;
+                    const int code = md.match(rc, mism);
+                    if (md.bad) return false;
+                    const int32_t p = rp + i;
+                    if (!dry && mism && is_acgt(code) && is_acgt(rc) && p >= lo && p <= hi) {
+                        if (out.snp) out.snp[out.n_snp] = ((uint64_t)sub << 40) | ((uint64_t)(uint32_t)p << 8) | ((uint64_t)code << 4) | rc;
+                        ++out.n_snp;
+                    }
+                    prev = Pair{OP_M, p, code};
+                    first = false;
+                }
+                rp += l; qp += l;
+            } else if (op == OP_D) {
+                for (int i = 0; i < l; ++i) {
+                    if (!dry && run_kind == OP_I) close_run();
+                    const int code = md.del();
+                    if (md.bad) return false;
+                    if (!dry && run_kind != OP_D) start_run(OP_D, first ? last_pair : prev);
+                    if (!dry) push_base(code);
+                    prev = Pair{OP_D, rp + i, code};
+                    first = false;
+                }
+                rp += l;
+            } else if (op == OP_I || op == OP_S) {
+                for (int i = 0; i < l; ++i) {
+                    md.end_del();
+                    if (md.bad) return false;
+                    if (!dry && run_kind == OP_D) close_run();
+                    if (!dry && run_kind != OP_I) start_run(OP_I, prev);
+                    if (!dry) push_base(read_code(qp + i));
+                    prev = Pair{OP_I, 0, 0};
+                }
+                qp += l;
+            }
+            // H: no pairs
+        }
+        if (!dry) close_run();
+        md.finish();
+        if (md.bad) return false;
+        if (last_out) *last_out = prev;
+        return true;
+    }
+    const uint8_t* md_p;
+    int md_n;
+};
+
+// Shared by both passes: frames the read (again, on the device), adds its coverage events (count pass), and walks it.
+template <bool EMIT>
+__device__ void process_read(const uint8_t* __restrict__ buf, const ReadMeta& m, const SubDesc* __restrict__ subs, int max_len,
+                             int* __restrict__ cov, Sink& out, uint8_t& status) {
+    const uint8_t* b = buf + m.off;
+    const uint32_t len = m.len;
+    status = ST_MALFORMED;
+    if (len < 32) return;
+    const int32_t pos = (int32_t)ld32(b + 4);
+    const uint32_t l_name = b[8];
+    const int n_cig = (int)ld16(b + 12);
+    const int32_t l_seq = (int32_t)ld32(b + 16);
+    if (l_seq < 0) return;
+    const uint64_t cig_off = 32 + (uint64_t)l_name, seq_off = cig_off + 4 * (uint64_t)n_cig;
+    if (seq_off + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq > len) return;
+    const uint8_t* cig = b + cig_off;
+    const SubDesc sd = subs[m.sub];
+    // coverage: every fetched read, whatever else is wrong with it (get_reference_positions runs first in the reference)
+    if (!EMIT) {
+        int32_t rp = pos;
+        for (int k = 0; k < n_cig; ++k) {
+            const uint32_t c = ld32(cig + 4 * k);
+            const int op = c & 0xf;
+            const int32_t l = (int32_t)(c >> 4);
+            if (aligned_op(op)) {
+                const int64_t a = max((int64_t)rp, (int64_t)sd.start), e = min((int64_t)rp + l, (int64_t)sd.end + 1);
+                if (a < e) {
+                    atomicAdd(cov + sd.cov_base + (a - sd.start), 1);
+                    atomicAdd(cov + sd.cov_base + (e - sd.start), -1);
+                }
+            }
+            if (aligned_op(op) || op == OP_D || op == OP_N) rp += l;
+        }
+    }
+    if (m.md_off < 0) { status = ST_NO_MD; return; }
+    if ((uint64_t)m.md_off + (uint64_t)(m.md_len < 0 ? 0 : m.md_len) > len) return;
+    int k0 = -1, k1 = -1;
+    int64_t qlen = 0;
+    bool unsupported = l_seq == 0, bad_op = false, dd = false;
+    int prev_kind = -1;
+    for (int k = 0; k < n_cig; ++k) {
+        const uint32_t c = ld32(cig + 4 * k);
+        const int op = c & 0xf;
+        if (op > OP_X) bad_op = true;
+        if (op == OP_N || op == OP_P) unsupported = true;
+        if (aligned_op(op) || op == OP_I || op == OP_S) qlen += c >> 4;
+        if ((aligned_op(op) || op == OP_D) && (c >> 4) > 0) { if (k0 < 0) k0 = k; k1 = k; }
+    }
+    if (bad_op) return;
+    if (k0 < 0) { status = ST_NO_PAIRS; return; }
+    if (unsupported) { status = ST_UNSUPPORTED; return; }
+    if (qlen != l_seq) return;
+    for (int k = k0; k <= k1; ++k) {
+        const uint32_t c = ld32(cig + 4 * k);
+        const int op = c & 0xf;
+        if ((c >> 4) == 0) continue;
+        if (op == OP_D && prev_kind == OP_I) dd = true;
+        if (aligned_op(op)) prev_kind = OP_M;
+        else if (op == OP_D) prev_kind = OP_D;
+        else if (op == OP_I || op == OP_S) prev_kind = OP_I;
+    }
+    Walk w;
+    w.cig = cig; w.seq = b + seq_off; w.n_cig = n_cig; w.k0 = k0; w.k1 = k1; w.pos = pos;
+    w.lo = sd.start; w.hi = sd.end; w.sub = m.sub; w.max_len = max_len; w.del_dropped = dd;
+    w.md_p = b + m.md_off; w.md_n = m.md_len;
+    Pair last{-1, 0, 0};
+    Sink dry{nullptr, nullptr, 0, 0};
+    if ((ld32(cig + 4 * k0) & 0xf) == OP_D) {
+        if (!w.run(true, last, dry, &last)) return;
+    }
+    if (!w.run(false, last, out, nullptr)) { out.n_snp = out.n_indel = 0; return; }
+    status = dd ? (uint8_t)(ST_OK | ST_DEL_DROPPED) : ST_OK;
+}
+
+__global__ void count_kernel(const uint8_t* __restrict__ buf, const ReadMeta* __restrict__ meta, uint64_t n,
+                             const SubDesc* __restrict__ subs, int max_len, int* __restrict__ cov, uint32_t* __restrict__ n_snp,
+                             uint32_t* __restrict__ n_indel, uint8_t* __restrict__ status) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    Sink s{nullptr, nullptr, 0, 0};
+    uint8_t st;
+    process_read<false>(buf, meta[r], subs, max_len, cov, s, st);
+    n_snp[r] = s.n_snp;
+    n_indel[r] = s.n_indel;
+    status[r] = st;
+}
+
+__global__ void emit_kernel(const uint8_t* __restrict__ buf, const ReadMeta* __restrict__ meta, uint64_t n,
+                            const SubDesc* __restrict__ subs, int max_len, const uint32_t* __restrict__ snp_off,
+                            const uint32_t* __restrict__ indel_off, const uint32_t* __restrict__ n_snp,
+                            const uint32_t* __restrict__ n_indel, uint64_t* __restrict__ snp_keys, IndelKey* __restrict__ indel_keys) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n || (n_snp[r] == 0 && n_indel[r] == 0)) return;
+    Sink s{snp_keys + snp_off[r], indel_keys + indel_off[r], 0, 0};
+    uint8_t st;
+    process_read<true>(buf, meta[r], subs, max_len, nullptr, s, st);
+}
+
+__device__ inline void keep_if(const SubDesc* subs, const int* depth, uint32_t sub, int32_t pos, uint32_t count, bool snp,
+                               double snp_min, double indel_min, DevCand& c, bool& keep) {
+    const SubDesc sd = subs[sub];
+    const int d = depth[sd.cov_base + (pos - sd.start)];
+    keep = false;
+    if (d <= 0) return;
+    const double af = (double)min((int64_t)count, (int64_t)d) / (double)d;
+    keep = af > (snp ? snp_min : indel_min);
+    c.sub = (int32_t)sub; c.pos = pos; c.depth = d; c.count = (int32_t)count;
+}
+
+__global__ void filter_snp_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ n_runs,
+                                  const SubDesc* __restrict__ subs, const int* __restrict__ depth, double snp_min,
+                                  DevCand* __restrict__ out, uint32_t* __restrict__ n_out) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= *n_runs) return;
+    const uint64_t k = keys[r];
+    DevCand c;
+    bool keep;
+    keep_if(subs, depth, (uint32_t)(k >> 40), (int32_t)(uint32_t)(k >> 8), counts[r], true, snp_min, 0.0, c, keep);
+    if (!keep) return;
+    c.kind = 0; c.len = 1;
+    c.w[0] = (k & 0xff) << 56; c.w[1] = c.w[2] = c.w[3] = 0;
+    out[atomicAdd(n_out, 1u)] = c;
+}
+
+__global__ void filter_indel_kernel(const IndelKey* __restrict__ keys, const uint32_t* __restrict__ counts,
+                                    const uint32_t* __restrict__ n_runs, const SubDesc* __restrict__ subs,
+                                    const int* __restrict__ depth, double indel_min, DevCand* __restrict__ out,
+                                    uint32_t* __restrict__ n_out) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= *n_runs) return;
+    const IndelKey k = keys[r];
+    DevCand c;
+    bool keep;
+    keep_if(subs, depth, (uint32_t)(k.w[0] >> 40), (int32_t)(uint32_t)(k.w[0] >> 8), counts[r], false, 0.0, indel_min, c, keep);
+    if (!keep) return;
+    c.kind = (uint32_t)((k.w[0] >> 6) & 3); c.len = (uint32_t)(k.w[0] & 63);
+    for (int j = 0; j < 4; ++j) c.w[j] = k.w[j + 1];
+    out[atomicAdd(n_out, 1u)] = c;
+}
+
+struct IndelDecomposer {
+    __host__ __device__ ::rocprim::tuple<uint64_t&, uint64_t&, uint64_t&, uint64_t&, uint64_t&> operator()(IndelKey& k) const {
+        return ::rocprim::tuple<uint64_t&, uint64_t&, uint64_t&, uint64_t&, uint64_t&>(k.w[0], k.w[1], k.w[2], k.w[3], k.w[4]);
+    }
+};
+
+}  // namespace
+
+struct Buf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+        const size_t want = bytes + bytes / 4 + 256;
+        const hipError_t e = hipMalloc(&p, want);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    template <class T> T* as() const { return (T*)p; }
+    ~Buf() { if (p) (void)hipFree(p); }
+};
+
+struct Workspace {
+    Buf recs, meta, subs, cov, depth, n_snp, n_indel, snp_off, indel_off, status, snp_keys, snp_sorted, indel_keys, indel_sorted,
+        snp_unique, snp_counts, indel_unique, indel_counts, scalars, cands, temp;
+    std::vector<uint8_t> h_status;
+    std::vector<DevCand> h_cands;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+Workspace* workspace_create() {
+    Workspace* ws = new Workspace();
+    if (hipEventCreate(&ws->ev0) != hipSuccess || hipEventCreate(&ws->ev1) != hipSuccess) { delete ws; return nullptr; }
+    return ws;
+}
+void workspace_destroy(Workspace* ws) {
+    if (!ws) return;
+    if (ws->ev0) (void)hipEventDestroy(ws->ev0);
+    if (ws->ev1) (void)hipEventDestroy(ws->ev1);
+    delete ws;
+}
+
+#define CG_CHECK(x)                                                        \
+    do {                                                                   \
+        const hipError_t e_ = (x);                                         \
+        if (e_ != hipSuccess) { *msg = hipGetErrorString(e_); return -2; } \
+    } while (0)
+
+int upload(Workspace* ws, const uint8_t* recs, uint64_t rec_bytes, const ReadMeta* meta, uint64_t n_reads, const SubDesc* subs,
+           uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg) {
+    CG_CHECK(ws->recs.ensure(rec_bytes + 1));
+    CG_CHECK(ws->meta.ensure((n_reads + 1) * sizeof(ReadMeta)));
+    CG_CHECK(ws->subs.ensure((n_subs + 1) * sizeof(SubDesc)));
+    CG_CHECK(ws->cov.ensure((size_t)(cov_len + 1) * sizeof(int)));
+    if (rec_bytes) CG_CHECK(hipMemcpyAsync(ws->recs.p, recs, rec_bytes, hipMemcpyHostToDevice, stream));
+    if (n_reads) CG_CHECK(hipMemcpyAsync(ws->meta.p, meta, n_reads * sizeof(ReadMeta), hipMemcpyHostToDevice, stream));
+    CG_CHECK(hipMemcpyAsync(ws->subs.p, subs, n_subs * sizeof(SubDesc), hipMemcpyHostToDevice, stream));
+    CG_CHECK(hipMemsetAsync(ws->cov.p, 0, (size_t)cov_len * sizeof(int), stream));
+    return 0;
+}
+
+int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len, int max_len, double snp_min, double indel_min,
+              hipStream_t stream, const DevCand** out, uint64_t* n_out, const uint8_t** status, uint64_t* n_events,
+              uint64_t* n_unique, BatchTimes* t, const char** msg) {
+    (void)n_subs;
+    *n_out = 0; *n_events = 0; *n_unique = 0;
+    ws->h_status.assign(n_reads, 0);
+    *status = ws->h_status.data();
+    CG_CHECK(hipEventRecord(ws->ev0, stream));
+    const uint64_t nr1 = n_reads + 1;
+    CG_CHECK(ws->n_snp.ensure(nr1 * 4));
+    CG_CHECK(ws->n_indel.ensure(nr1 * 4));
+    CG_CHECK(ws->snp_off.ensure(nr1 * 4));
+    CG_CHECK(ws->indel_off.ensure(nr1 * 4));
+    CG_CHECK(ws->status.ensure(nr1));
+    CG_CHECK(ws->depth.ensure((size_t)(cov_len + 1) * sizeof(int)));
+    CG_CHECK(ws->scalars.ensure(16 * sizeof(uint32_t)));
+    uint32_t* sc = ws->scalars.as<uint32_t>();     // [0] snp runs, [1] indel runs, [2] survivors
+    CG_CHECK(hipMemsetAsync(sc, 0, 16 * sizeof(uint32_t), stream));
+    const int TB = 256;
+    const unsigned grid = (unsigned)((n_reads + TB - 1) / TB);
+    if (n_reads) {
+        hipLaunchKernelGGL(count_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs.as<const uint8_t>(), ws->meta.as<const ReadMeta>(),
+                           n_reads, ws->subs.as<const SubDesc>(), max_len, ws->cov.as<int>(), ws->n_snp.as<uint32_t>(),
+                           ws->n_indel.as<uint32_t>(), ws->status.as<uint8_t>());
+        CG_CHECK(hipGetLastError());
+    }
+    // per-read output offsets (exclusive scans; the element past the last read carries the total)
+    CG_CHECK(hipMemsetAsync(ws->n_snp.as<uint32_t>() + n_reads, 0, 4, stream));
+    CG_CHECK(hipMemsetAsync(ws->n_indel.as<uint32_t>() + n_reads, 0, 4, stream));
+    size_t tb = 0, tb2 = 0;
+    CG_CHECK(rocprim::exclusive_scan(nullptr, tb, ws->n_snp.as<uint32_t>(), ws->snp_off.as<uint32_t>(), 0u, nr1,
+                                     rocprim::plus<uint32_t>(), stream));
+    CG_CHECK(rocprim::inclusive_scan(nullptr, tb2, ws->cov.as<int>(), ws->depth.as<int>(), (size_t)cov_len, rocprim::plus<int>(), stream));
+    tb = std::max(tb, tb2);
+    CG_CHECK(ws->temp.ensure(tb));
+    tb = ws->temp.cap;
+    CG_CHECK(rocprim::exclusive_scan(ws->temp.p, tb, ws->n_snp.as<uint32_t>(), ws->snp_off.as<uint32_t>(), 0u, nr1,
+                                     rocprim::plus<uint32_t>(), stream));
+    tb = ws->temp.cap;
+    CG_CHECK(rocprim::exclusive_scan(ws->temp.p, tb, ws->n_indel.as<uint32_t>(), ws->indel_off.as<uint32_t>(), 0u, nr1,
+                                     rocprim::plus<uint32_t>(), stream));
+    tb = ws->temp.cap;
+    if (cov_len > 0)
+        CG_CHECK(rocprim::inclusive_scan(ws->temp.p, tb, ws->cov.as<int>(), ws->depth.as<int>(), (size_t)cov_len, rocprim::plus<int>(), stream));
+    uint32_t tot[2];
+    CG_CHECK(hipMemcpyAsync(&tot[0], ws->snp_off.as<uint32_t>() + n_reads, 4, hipMemcpyDeviceToHost, stream));
+    CG_CHECK(hipMemcpyAsync(&tot[1], ws->indel_off.as<uint32_t>() + n_reads, 4, hipMemcpyDeviceToHost, stream));
+    CG_CHECK(hipStreamSynchronize(stream));
+    const uint64_t ns = tot[0], ni = tot[1];
+    *n_events = ns + ni;
+    CG_CHECK(ws->snp_keys.ensure((ns + 1) * 8));
+    CG_CHECK(ws->snp_sorted.ensure((ns + 1) * 8));
+    CG_CHECK(ws->snp_unique.ensure((ns + 1) * 8));
+    CG_CHECK(ws->snp_counts.ensure((ns + 1) * 4));
+    CG_CHECK(ws->indel_keys.ensure((ni + 1) * sizeof(IndelKey)));
+    CG_CHECK(ws->indel_sorted.ensure((ni + 1) * sizeof(IndelKey)));
+    CG_CHECK(ws->indel_unique.ensure((ni + 1) * sizeof(IndelKey)));
+    CG_CHECK(ws->indel_counts.ensure((ni + 1) * 4));
+    CG_CHECK(ws->cands.ensure((ns + ni + 1) * sizeof(DevCand)));
+    if (ns + ni > 0) {
+        hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs.as<const uint8_t>(), ws->meta.as<const ReadMeta>(),
+                           n_reads, ws->subs.as<const SubDesc>(), max_len, ws->snp_off.as<const uint32_t>(),
+                           ws->indel_off.as<const uint32_t>(), ws->n_snp.as<const uint32_t>(), ws->n_indel.as<const uint32_t>(),
+                           ws->snp_keys.as<uint64_t>(), ws->indel_keys.as<IndelKey>());
+        CG_CHECK(hipGetLastError());
+    }
+    if (ns > 0) {
+        size_t a = 0, b = 0;
+        CG_CHECK(rocprim::radix_sort_keys(nullptr, a, ws->snp_keys.as<uint64_t>(), ws->snp_sorted.as<uint64_t>(), (size_t)ns, 0u, 64u, stream));
+        CG_CHECK(rocprim::run_length_encode(nullptr, b, ws->snp_sorted.as<uint64_t>(), (unsigned)ns, ws->snp_unique.as<uint64_t>(),
+                                            ws->snp_counts.as<uint32_t>(), sc + 0, stream));
+        CG_CHECK(ws->temp.ensure(std::max(a, b)));
+        a = b = ws->temp.cap;
+        CG_CHECK(rocprim::radix_sort_keys(ws->temp.p, a, ws->snp_keys.as<uint64_t>(), ws->snp_sorted.as<uint64_t>(), (size_t)ns, 0u, 64u, stream));
+        CG_CHECK(rocprim::run_length_encode(ws->temp.p, b, ws->snp_sorted.as<uint64_t>(), (unsigned)ns, ws->snp_unique.as<uint64_t>(),
+                                            ws->snp_counts.as<uint32_t>(), sc + 0, stream));
+        hipLaunchKernelGGL(filter_snp_kernel, dim3((unsigned)((ns + TB - 1) / TB)), dim3(TB), 0, stream, ws->snp_unique.as<const uint64_t>(),
+                           ws->snp_counts.as<const uint32_t>(), sc + 0, ws->subs.as<const SubDesc>(), ws->depth.as<const int>(), snp_min,
+                           ws->cands.as<DevCand>(), sc + 2);
+        CG_CHECK(hipGetLastError());
+    }
+    if (ni > 0) {
+        size_t a = 0, b = 0;
+        CG_CHECK(rocprim::radix_sort_keys(nullptr, a, ws->indel_keys.as<IndelKey>(), ws->indel_sorted.as<IndelKey>(), (size_t)ni,
+                                          IndelDecomposer(), stream));
+        CG_CHECK(rocprim::run_length_encode(nullptr, b, ws->indel_sorted.as<IndelKey>(), (unsigned)ni, ws->indel_unique.as<IndelKey>(),
+                                            ws->indel_counts.as<uint32_t>(), sc + 1, stream));
+        CG_CHECK(ws->temp.ensure(std::max(a, b)));
+        a = b = ws->temp.cap;
+        CG_CHECK(rocprim::radix_sort_keys(ws->temp.p, a, ws->indel_keys.as<IndelKey>(), ws->indel_sorted.as<IndelKey>(), (size_t)ni,
+                                          IndelDecomposer(), stream));
+        CG_CHECK(rocprim::run_length_encode(ws->temp.p, b, ws->indel_sorted.as<IndelKey>(), (unsigned)ni, ws->indel_unique.as<IndelKey>(),
+                                            ws->indel_counts.as<uint32_t>(), sc + 1, stream));
+        hipLaunchKernelGGL(filter_indel_kernel, dim3((unsigned)((ni + TB - 1) / TB)), dim3(TB), 0, stream, ws->indel_unique.as<const IndelKey>(),
+                           ws->indel_counts.as<const uint32_t>(), sc + 1, ws->subs.as<const SubDesc>(), ws->depth.as<const int>(), indel_min,
+                           ws->cands.as<DevCand>(), sc + 2);
+        CG_CHECK(hipGetLastError());
+    }
+    CG_CHECK(hipEventRecord(ws->ev1, stream));
+    uint32_t hs[3];
+    CG_CHECK(hipMemcpyAsync(hs, sc, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (n_reads) CG_CHECK(hipMemcpyAsync(ws->h_status.data(), ws->status.p, n_reads, hipMemcpyDeviceToHost, stream));
+    CG_CHECK(hipStreamSynchronize(stream));
+    *n_unique = (uint64_t)hs[0] + hs[1];
+    ws->h_cands.resize(hs[2]);
+    if (hs[2]) {
+        CG_CHECK(hipMemcpyAsync(ws->h_cands.data(), ws->cands.p, hs[2] * sizeof(DevCand), hipMemcpyDeviceToHost, stream));
+        CG_CHECK(hipStreamSynchronize(stream));
+    }
+    *out = ws->h_cands.data();
+    *n_out = hs[2];
+    float ms = 0.f;
+    CG_CHECK(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
+    t->device_ms = ms;
+    return 0;
+}
+
+}  // namespace cand

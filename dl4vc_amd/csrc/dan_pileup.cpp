@@ -12,6 +12,7 @@
 // module by construction (tests/test_pileup_native.py).  Worker threads take contiguous runs of locations, each with its
 // own file handles and window.
 #include "../../include/dl4vc_loader.h"
+#include "bam_native.h"
 
 #include <zlib.h>
 
@@ -51,79 +52,8 @@ inline bool is_refop(int op) { return is_aligned(op) || op == CDEL || op == CREF
 constexpr int FLAG_MASK = 0x4 | 0x100 | 0x200 | 0x400;          // unmapped, secondary, QC fail, duplicate (BAM_DEF_MASK)
 constexpr int FREVERSE = 0x10;
 
-// ---- BGZF -------------------------------------------------------------------------------------------------------------------------
-struct Bgzf {
-    FILE* f = nullptr;                                           // owned: closed with the reader (also when an exception unwinds past it)
-    Bgzf() = default;
-    Bgzf(const Bgzf&) = delete;
-    Bgzf& operator=(const Bgzf&) = delete;
-    ~Bgzf() { if (f) fclose(f); }
-    int64_t block_start = 0, next_block = 0;
-    std::vector<uint8_t> data, raw;
-    size_t off = 0;
-    std::string err;
-
-    bool load(int64_t file_off) {
-        if (fseeko(f, file_off, SEEK_SET) != 0) { err = "seek failed"; return false; }
-        uint8_t head[18];
-        const size_t got = fread(head, 1, 18, f);
-        if (got == 0) { block_start = next_block = file_off; data.clear(); off = 0; return false; }
-        if (got < 18 || head[0] != 0x1f || head[1] != 0x8b || head[2] != 8 || head[3] != 4) { err = "not a BGZF block"; return false; }
-        const int xlen = head[10] | (head[11] << 8);
-        std::vector<uint8_t> extra(xlen);
-        memcpy(extra.data(), head + 12, std::min(6, xlen));
-        if (xlen > 6 && fread(extra.data() + 6, 1, xlen - 6, f) != (size_t)(xlen - 6)) { err = "truncated BGZF header"; return false; }
-        int bsize = -1;
-        for (int i = 0; i + 4 <= xlen;) {
-            const int slen = extra[i + 2] | (extra[i + 3] << 8);
-            if (extra[i] == 'B' && extra[i + 1] == 'C' && i + 6 <= xlen) bsize = extra[i + 4] | (extra[i + 5] << 8);
-            i += 4 + slen;
-        }
-        if (bsize < 0) { err = "BGZF block without a BC field"; return false; }
-        const int body = bsize + 1 - 12 - xlen;
-        if (body < 8) { err = "truncated BGZF block"; return false; }
-        raw.resize(body);
-        if (fread(raw.data(), 1, body, f) != (size_t)body) { err = "truncated BGZF block"; return false; }
-        uint32_t crc, isize;
-        memcpy(&crc, raw.data() + body - 8, 4);
-        memcpy(&isize, raw.data() + body - 4, 4);
-        if (isize > 65536) { err = "BGZF block claims more than 64 KiB of data"; return false; }   // (the format's limit; not a size to trust)
-        data.resize(isize);
-        uint8_t scratch[8];
-        z_stream zs{};
-        if (inflateInit2(&zs, -15) != Z_OK) { err = "inflateInit2 failed"; return false; }
-        zs.next_in = raw.data(); zs.avail_in = body - 8;
-        zs.next_out = isize ? data.data() : scratch; zs.avail_out = isize ? isize : (unsigned)sizeof scratch;   // (the empty end-of-file block)
-        const int rc = inflate(&zs, Z_FINISH);
-        const bool ok = rc == Z_STREAM_END && zs.total_out == isize;
-        inflateEnd(&zs);
-        if (!ok || (uint32_t)crc32(0L, isize ? data.data() : scratch, isize) != crc) { err = "BGZF block fails its CRC / size check"; return false; }
-        block_start = file_off; next_block = file_off + bsize + 1; off = 0;
-        return true;
-    }
-    int64_t tell() const { return (block_start << 16) | (int64_t)off; }
-    bool seek(int64_t voff) {
-        const int64_t blk = voff >> 16;
-        if (blk != block_start || data.empty()) { err.clear(); load(blk); if (!err.empty()) return false; }
-        off = (size_t)(voff & 0xffff);
-        return true;
-    }
-    // reads up to n bytes; returns the count (short at end of file); err set on a corrupt block
-    size_t read(void* dst, size_t n) {
-        size_t done = 0;
-        while (n > 0) {
-            if (off >= data.size()) {
-                err.clear();
-                if (!load(next_block)) { if (!err.empty()) return done; break; }
-                continue;
-            }
-            const size_t take = std::min(n, data.size() - off);
-            memcpy((uint8_t*)dst + done, data.data() + off, take);
-            off += take; done += take; n -= take;
-        }
-        return done;
-    }
-};
+using bamn::Bgzf;
+using bamn::Bai;
 
 struct Rec {
     int32_t tid = -1, pos = 0, ref_end = 0;
@@ -264,36 +194,8 @@ struct Fasta {
     ~Fasta() { if (f) fclose(f); }
 };
 
-struct Bam {
-    Bgzf r;
-    std::vector<std::string> refs;
-    std::map<std::string, int> tid_of;
-    int64_t first_record = 0;
-    std::string err;
-
-    bool open(const std::string& path) {
-        r.f = fopen(path.c_str(), "rb");
-        if (!r.f) { err = "cannot open " + path; return false; }
-        char magic[4];
-        if (r.read(magic, 4) != 4 || memcmp(magic, "BAM\1", 4) != 0) { err = path + " is not a BAM file"; return false; }
-        int32_t l_text = 0, n_ref = 0;
-        if (r.read(&l_text, 4) != 4) { err = "truncated BAM header"; return false; }
-        if (l_text < 0 || l_text > (1 << 30)) { err = "corrupt BAM header (text length)"; return false; }
-        std::vector<char> text((size_t)l_text);
-        if (r.read(text.data(), text.size()) != text.size() || r.read(&n_ref, 4) != 4) { err = "truncated BAM header"; return false; }
-        if (n_ref < 0) { err = "corrupt BAM header (reference count)"; return false; }
-        for (int i = 0; i < n_ref; ++i) {
-            int32_t ln = 0, len = 0;
-            if (r.read(&ln, 4) != 4) { err = "truncated BAM header"; return false; }
-            if (ln < 1 || ln > 65536) { err = "corrupt BAM header (reference name length)"; return false; }
-            std::vector<char> nm((size_t)ln);
-            if (r.read(nm.data(), nm.size()) != nm.size() || r.read(&len, 4) != 4) { err = "truncated BAM header"; return false; }
-            refs.emplace_back(nm.data(), ln > 0 ? (size_t)ln - 1 : 0);
-            tid_of[refs.back()] = i;
-        }
-        first_record = r.tell();
-        return true;
-    }
+struct Bam : bamn::BamFile {
+    std::vector<uint8_t> b;
     int get_tid(const std::string& name) const {
         auto it = tid_of.find(name);
         if (it != tid_of.end()) return it->second;
@@ -303,13 +205,9 @@ struct Bam {
     }
     // next record; 0 = end of file, 1 = ok, -1 = error
     int next(std::shared_ptr<Rec>& out) {
-        int32_t size = 0;
-        const size_t g = r.read(&size, 4);
-        if (g < 4) { if (!r.err.empty()) err = r.err; return r.err.empty() ? 0 : -1; }
-        // every length below comes from the file: checked against the record before anything is sized or indexed by it
-        if (size < 32 || size > (1 << 28)) { err = "corrupt BAM record (block_size)"; return -1; }
-        std::vector<uint8_t> b((size_t)size);
-        if (r.read(b.data(), b.size()) != b.size()) { err = r.err.empty() ? "truncated BAM record" : r.err; return -1; }
+        const int g = next_block(b);
+        if (g <= 0) return g;
+        const int32_t size = (int32_t)b.size();
         auto rec = std::make_shared<Rec>();
         int32_t tid, pos, l_seq;
         uint8_t l_name;
@@ -345,46 +243,6 @@ struct Bam {
         rec->qual.assign(b.begin() + o, b.begin() + o + l_seq);
         out = rec;
         return 1;
-    }
-};
-
-struct Bai {
-    std::vector<std::vector<uint64_t>> linear;
-    bool load(const std::string& path) {
-        FILE* f = fopen(path.c_str(), "rb");
-        if (!f) return false;
-        std::vector<uint8_t> raw;
-        uint8_t buf[65536];
-        size_t g;
-        while ((g = fread(buf, 1, sizeof buf, f)) > 0) raw.insert(raw.end(), buf, buf + g);
-        fclose(f);
-        if (raw.size() < 8 || memcmp(raw.data(), "BAI\1", 4) != 0) return false;
-        size_t o = 4;
-        int32_t n_ref;
-        memcpy(&n_ref, &raw[o], 4); o += 4;
-        for (int r = 0; r < n_ref; ++r) {
-            int32_t n_bin;
-            memcpy(&n_bin, &raw[o], 4); o += 4;
-            for (int b = 0; b < n_bin; ++b) {
-                int32_t n_chunk;
-                memcpy(&n_chunk, &raw[o + 4], 4);
-                o += 8 + 16 * (size_t)n_chunk;
-            }
-            int32_t n_intv;
-            memcpy(&n_intv, &raw[o], 4); o += 4;
-            std::vector<uint64_t> lin((size_t)n_intv);
-            if (n_intv > 0) memcpy(lin.data(), &raw[o], 8 * (size_t)n_intv);
-            o += 8 * (size_t)n_intv;
-            linear.push_back(std::move(lin));
-        }
-        return true;
-    }
-    // 0 = "no alignment at or after the window" (BaiIndex.linear_offset returning None)
-    uint64_t linear_offset(int tid, int64_t start) const {
-        if (tid < 0 || tid >= (int)linear.size()) return 0;
-        const auto& lin = linear[tid];
-        for (size_t w = (size_t)(std::max<int64_t>(start, 0) >> 14); w < lin.size(); ++w) if (lin[w]) return lin[w];
-        return 0;
     }
 };
 

@@ -1,0 +1,82 @@
+/* C ABI of libdl4vc_cand.so: candidate generation from a BAM (the first stage of call_variants.sh; reference
+ * tools/candidate_generator.py).  Host threads inflate and frame the records of each subregion; the per-read work (CIGAR + MD
+ * walk, allele keys, coverage) and the per-locus counting (radix sort + run-length encode of the keys, depth by a scan of
+ * coverage difference events, the allele-frequency filter in double precision) run on the GPU.  Bindings:
+ * dl4vc_amd/candgen.py.
+ *
+ * Every call returns 0 on success and a negative code on failure; cg_last_error() then says why.  No call aborts the process
+ * on bad input: a corrupt BAM is an error code. */
+#ifndef DL4VC_CANDGEN_H
+#define DL4VC_CANDGEN_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The longest REF or ALT an allele key holds (bases, anchor included): --max_len_indel_allele may not exceed it. */
+#define CG_MAX_ALLELE_LEN 63
+
+typedef struct cg_handle cg_handle_t;
+
+typedef struct {
+    int32_t threads;               /* host threads that inflate and frame records (<= 0: 1) */
+    int32_t max_len_indel_allele;  /* indels whose REF or ALT is longer are dropped (reference CLI default 60) */
+    double snp_min_freq;           /* a SNP is kept when min(count, depth) / depth > snp_min_freq */
+    double indel_min_freq;         /* the same for an insertion or deletion */
+    int32_t device;                /* HIP device ordinal */
+} cg_options;
+
+/* One subregion: reads are fetched over [start, end) (htslib's overlap rule), alleles counted at start <= pos <= end. */
+typedef struct {
+    int32_t tid;
+    int32_t start;
+    int32_t end;
+} cg_region;
+
+/* One surviving allele of one subregion.  ref / alt are NUL-terminated upper-case bases. */
+typedef struct {
+    int32_t region;                /* index into the cg_run regions array */
+    int32_t tid;
+    int32_t pos0;                  /* 0-based position (the anchor base of an indel) */
+    int32_t depth;                 /* reads whose M/=/X operations cover pos0, in this subregion's fetch */
+    int32_t count;                 /* reads of this subregion carrying the allele */
+    char ref[CG_MAX_ALLELE_LEN + 1];
+    char alt[CG_MAX_ALLELE_LEN + 1];
+} cg_candidate;
+
+typedef struct {
+    int64_t reads;                 /* records fetched, summed over subregions (a read in two subregions counts twice) */
+    int64_t reads_no_md;           /* coverage counted, no alleles (the reference's "MD tag not present") */
+    int64_t reads_no_pairs;        /* no CIGAR or no reference-consuming operation: no alleles */
+    int64_t reads_unsupported;     /* N or P CIGAR operation, or SEQ '*': coverage counted, alleles skipped */
+    int64_t reads_malformed;       /* MD inconsistent with CIGAR / SEQ, or a letter outside the BAM alphabet: alleles skipped */
+    int64_t reads_deletions_dropped; /* a deletion anchored on an inserted base: the read's deletions dropped */
+    int64_t allele_events;         /* alleles emitted by reads, before counting */
+    int64_t alleles;               /* distinct (subregion, allele) after counting */
+    int64_t candidates;            /* survivors of the frequency filter */
+    int64_t batches;
+    double host_frame_ms;          /* inflate + frame (wall time of the host threads) */
+    double upload_ms;              /* host -> device copy of the framed records */
+    double device_ms;              /* count, scan, emit, sort, encode, depth, filter (device events) */
+    double total_ms;
+} cg_stats;
+
+int cg_open(const char* bam_path, const char* bai_path /* NULL or "": linear scan */, const cg_options* opt,
+            cg_handle_t** out);
+/* Runs every region (internally in batches).  On success *out points at n_out candidates owned by the handle, valid until the
+ * next cg_run or cg_close; their order is unspecified. */
+int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg_candidate** out, int64_t* n_out,
+           cg_stats* stats);
+/* Reference names and lengths of the BAM header. */
+int32_t cg_n_refs(const cg_handle_t* h);
+const char* cg_ref_name(const cg_handle_t* h, int32_t tid);
+int64_t cg_ref_length(const cg_handle_t* h, int32_t tid);
+const char* cg_last_error(void);
+void cg_close(cg_handle_t* h);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

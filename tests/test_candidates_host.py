@@ -1,0 +1,160 @@
+"""Candidate generation, host side (no GPU): regions, BED, subregions, groups, filter, multi-allele rule and VCF order against
+the reference's own functions (tests/golden/candidates_*.json.gz, tools/gen_golden_candidates.py), the CLI's flag table
+against the reference's parser, and corrupt input reported as an error by libdl4vc_cand.so's host framing."""
+import gzip
+import os
+import struct
+import subprocess
+import sys
+import zlib
+
+import pytest
+
+from dl4vc_amd import candidates as C
+from tests.candidates_fixture import NAMES, load, write_bam
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _runs():
+    for name in NAMES:
+        fx = load(name)
+        for run in fx["runs"]:
+            yield pytest.param(fx, run, id="%s-%s" % (name, run["name"]))
+
+
+@pytest.mark.parametrize("fx,run", list(_runs()))
+def test_regions_subregions_groups_match_reference(fx, run, tmp_path):
+    p = run["params"]
+    bed = None
+    if run["bed"] is not None:
+        bed = str(tmp_path / "r.bed")
+        open(bed, "w").write(run["bed"])
+    refs = [r[0] for r in fx["references"]]
+    lens = [r[1] for r in fx["references"]]
+    regions = C.contig_regions(refs, lens, p["contigs"], bed, p["keep_contig_chr"])
+    assert [list(r) for r in regions] == run["regions"]
+    subs = C.split_subregions(regions, p["chunk_size"] * 1000)
+    assert [list(s) for s in subs] == run["subregions"]
+    groups = C.group_subregions(subs, p["chunk_size"] * 1000)
+    assert [[list(s) for s in g] for g in groups] == run["groups"]
+
+
+@pytest.mark.parametrize("fx,run", list(_runs()))
+def test_filter_multiallele_and_vcf_order_match_reference(fx, run):
+    """The reference's final tuples, fed back as counts, survive this module's filter / multi-allele rule / order unchanged."""
+    p = run["params"]
+    tuples = [tuple(t) for t in run["tuples"]]
+    for chrom, pos, ref, alt, depth, af in tuples:
+        assert af > (p["snp_min_freq"] if len(ref) == len(alt) == 1 else p["indel_min_freq"])
+    lines = C.sort_lines([C.record_line(*t) for t in reversed(tuples)])
+    assert lines == run["lines"]
+
+
+def test_multiallele_rule_first_highest_af():
+    al = [("c", 5, "A", "T", 10, 0.2), ("c", 5, "A", "G", 10, 0.4), ("c", 5, "A", "C", 10, 0.4), ("c", 6, "G", "T", 9, 0.1)]
+    assert C.keep_one_per_position(al) == [("c", 5, "A", "C", 10, 0.4), ("c", 6, "G", "T", 9, 0.1)]
+
+
+def test_af_filter_is_strict_and_double():
+    assert not C.passes("A", "T", 1, 100, 0.01, 0.5)           # 0.01 > 0.01 is false
+    assert C.passes("A", "T", 2, 100, 0.01, 0.5)
+    assert not C.passes("A", "AT", 2, 100, 0.01, 0.5)
+    assert C.passes("AT", "A", 5, 3, 0.5, 0.5)                   # min(count, depth) / depth = 1
+    assert not C.passes("A", "T", 1, 0, 0.0, 0.0)
+
+
+def test_vcf_text():
+    assert C.record_line("chr1", 99, "A", "T", 40, 0.075) == "chr1\t100\t.\tA\tT\t50\t.\tDP=40;AF=0.075\tGT:GQ\t1:50"
+    assert C.format_af(1 / 3) == "0.333333"
+    h = C.header_lines(["chr1", "2"], [100, 50])
+    assert h[0] == "##fileformat=VCFv4.2" and h[-1].startswith("#CHROM\tPOS") and h[-1].endswith("FORMAT\tCALLED")
+    assert h[-3:-1] == ["##contig=<ID=chr1,length=100>", "##contig=<ID=2,length=50>"]
+    # sort -k1,1 -k2,2n: chrom bytes, POS numerically, then the line
+    lines = ["chr2\t5\tx", "chr10\t7\tx", "chr1\t10\tb", "chr1\t9\tz", "chr1\t10\ta"]
+    assert C.sort_lines(lines) == ["chr1\t9\tz", "chr1\t10\ta", "chr1\t10\tb", "chr10\t7\tx", "chr2\t5\tx"]
+
+
+def test_cli_flags_match_reference_parser():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import candidate_generator as cli
+    want = load("edge")["flag_table"]
+    got = []
+    for a in cli.build_parser()._actions:
+        if a.dest == "help":
+            continue
+        got.append({"flags": list(a.option_strings), "dest": a.dest, "default": a.default,
+                    "type": a.type.__name__ if a.type else None, "action": type(a).__name__})
+    assert got == want
+
+
+def test_max_len_beyond_key_is_refused(tmp_path):
+    bam = write_bam(load("nochr"), str(tmp_path / "x.bam"))
+    with pytest.raises(ValueError, match="limit of 63"):
+        C.generate(bam, str(tmp_path / "o.vcf"), max_len_indel_allele=64)
+
+
+# ---- corrupt input: host framing reports it, the process survives ----------------------------------------------------------------
+def _blocks(path):
+    raw = open(path, "rb").read()
+    out, o = [], 0
+    while o < len(raw):
+        bsize = struct.unpack_from("<H", raw, o + 16)[0] + 1
+        out.append(raw[o:o + bsize])
+        o += bsize
+    return out
+
+
+def _bgzf(data):
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    body = c.compress(data) + c.flush()
+    return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", len(body) + 25) + body +
+            struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data)))
+
+
+def _damaged(tmp_path, kind):
+    fx = load("nochr")
+    good = write_bam(fx, str(tmp_path / "good.bam"), index=False)
+    raw = b"".join(zlib.decompress(b[18:-8], -15) for b in _blocks(good))
+    l_text = struct.unpack_from("<i", raw, 4)[0]
+    o = 8 + l_text
+    n_ref = struct.unpack_from("<i", raw, o)[0]
+    o += 4
+    for _ in range(n_ref):
+        o += 8 + struct.unpack_from("<i", raw, o)[0]
+    first = o
+    rec = bytearray(raw[first:first + 4 + struct.unpack_from("<i", raw, first)[0]])
+    rest = raw[first + len(rec):]
+    if kind == "block_size_past_eof":
+        rec[0:4] = struct.pack("<i", 1 << 20)
+    elif kind == "l_seq_past_record":
+        rec[20:24] = struct.pack("<i", 5000)
+    elif kind == "n_cigar_past_record":
+        rec[16:18] = struct.pack("<H", 4000)
+    data = raw[:first] + bytes(rec) + rest
+    p = str(tmp_path / (kind + ".bam"))
+    blob = b"".join(_bgzf(data[i:i + 60000]) for i in range(0, len(data), 60000)) + _bgzf(b"")
+    if kind == "truncated_bgzf":
+        blocks = [_bgzf(data[i:i + 30000]) for i in range(0, len(data), 30000)]
+        blob = blocks[0] + blocks[1][:len(blocks[1]) // 2] if len(blocks) > 1 else blocks[0][:len(blocks[0]) - 40]
+        if len(blocks) == 1:
+            blob = _bgzf(data[:first]) + _bgzf(data[first:])[:60]
+    open(p, "wb").write(blob)
+    return p
+
+
+@pytest.mark.parametrize("kind", ["truncated_bgzf", "block_size_past_eof", "l_seq_past_record", "n_cigar_past_record"])
+def test_corrupt_bam_is_an_error_not_a_crash(tmp_path, kind):
+    """Run in a child process so that an abort would show as a signal, not take the test run down."""
+    bam = _damaged(tmp_path, kind)
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from dl4vc_amd.candgen import CandidateCounter\n"
+            "try:\n"
+            "    cc = CandidateCounter(%r, threads=2)\n"
+            "    cc.run([(0, 0, 3200)])\n"
+            "except RuntimeError as e:\n"
+            "    print('ERR', e); sys.exit(3)\n"
+            "print('OK')\n") % (ROOT, bam)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 3, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    assert "corrupt BAM record" in r.stdout or "truncated" in r.stdout or "BGZF" in r.stdout, r.stdout

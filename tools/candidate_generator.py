@@ -1,0 +1,62 @@
+#!/usr/bin/env python
+"""BAM -> candidates.vcf: the first stage of call_variants.sh, with the reference tool's flags, types and defaults
+(reference tools/candidate_generator.py).  The per-read work and the per-locus counts run on the GPU
+(libdl4vc_cand.so); see dl4vc_amd/candidates.py for the host logic and DESIGN.md section 9 for the divergences.
+
+    candidate_generator.py --input in.bam --output out.vcf --contigs 20:1000:2000,17:0:50000,8
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import logging
+import os
+import sys
+from argparse import RawTextHelpFormatter
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def build_parser() -> argparse.ArgumentParser:
+    from dl4vc_amd.candgen import default_threads
+    p = argparse.ArgumentParser(description="Generate a VCF from a BAM file with candidate variants.\n\n"
+                                "Example usage:\n    candidate_generator.py --input in.bam --output out.vcf --contigs "
+                                "20:1000:2000,17:0:50000", formatter_class=RawTextHelpFormatter)
+    p.add_argument("--input", help="input BAM file (indexed by INPUT.bai when that file exists)")
+    p.add_argument("--output", default="out.vcf", help="output VCF file")
+    p.add_argument("--contigs", default=None, help="Comma delimited list of contigs to use in format contig:start:end")
+    p.add_argument("--keep_contig_chr", action="store_true", default=False,
+                   help='Set true if BAM file lists contigs as "chrC" instead of "X"')
+    p.add_argument("--chunk_size", default=1000, type=int,
+                   help="Size of region for each process to calculate variants on, in kb (kilobases)")
+    p.add_argument("--threads", default=None, type=int,
+                   help="Host threads that inflate and frame records. Defaults to min(16, usable cores) = %d here"
+                   % default_threads())
+    p.add_argument("--snp_min_freq", default=0.01, type=float,
+                   help="The minimum fraction of SNP alleles at a locus to be included as a candidate")
+    p.add_argument("--indel_min_freq", default=0.01, type=float,
+                   help="The minimum fraction of indel alleles at a locus to be included as a candidate")
+    p.add_argument("--keep_multialleles", action="store_true", default=False,
+                   help="Do not remove multiple alleles for same genomic location")
+    p.add_argument("--max_len_indel_allele", default=60, type=int, help="In case of bad mapping, ignore long alleles.")
+    p.add_argument("--bedfile", default=None, help="BED file with intervals to use for candidate generation")
+    p.add_argument("--debug", action="store_true", help="Print debug information")
+    return p
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    print(args)
+    logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.DEBUG if args.debug else logging.INFO)
+    from dl4vc_amd.candidates import generate
+    stats = generate(args.input, args.output, contigs=args.contigs, bedfile=args.bedfile, keep_contig_chr=args.keep_contig_chr,
+                     chunk_size=args.chunk_size, threads=args.threads, snp_min_freq=args.snp_min_freq,
+                     indel_min_freq=args.indel_min_freq, keep_multialleles=args.keep_multialleles,
+                     max_len_indel_allele=args.max_len_indel_allele)
+    logging.info("Generated final VCF file at %s.", args.output)
+    print("summary " + json.dumps(stats, sort_keys=True))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
