@@ -1,0 +1,43 @@
+#!/bin/bash
+# Steps 1-2 of the training recipe (reference docs/Step-by-step.md:40-96) as one command: BAM -> candidates.vcf
+# (tools/candidate_generator.py, allele counting on the GPU, with the docs' flags) -> true / false positives against a truth
+# VCF (tools/vcf_isec.py, bcftools isec -p's pairing: same CHROM, POS, REF and ALT set) -> OUTDIR/train.hdf
+# (tools/convert_bam_single_reads.py: isec/0003.vcf as --tp_vcf with label 0, isec/0002.vcf as --tp_full_vcf for the truth's
+# GT, isec/0001.vcf as --fp_vcf with label 2).  A multi-allelic truth record (1/2) pairs only with a candidate of the same
+# ALT set, so its split candidates are labelled false positives; split such truth records beforehand if that is not wanted.
+# Stages whose output already exists in OUTDIR are skipped.
+set -e
+usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES]"; exit 1; }
+PROCS=16
+while getopts "i:r:t:o:b:p:h" opt; do
+  case $opt in
+    i) BAM=$OPTARG ;;
+    r) REFERENCE=$OPTARG ;;
+    t) TRUTH=$OPTARG ;;
+    o) OUTDIR=$OPTARG ;;
+    b) BED=$OPTARG ;;       # candidate generation only
+    p) PROCS=$OPTARG ;;
+    *) usage ;;
+  esac
+done
+[ -z "$BAM" ] || [ -z "$REFERENCE" ] || [ -z "$TRUTH" ] || [ -z "$OUTDIR" ] && usage
+SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
+mkdir -p "$OUTDIR"
+if [ ! -f "$OUTDIR/candidates.vcf" ]; then
+  printf "Generate candidate VCF...\n"
+  python "$SCRIPTDIR/tools/candidate_generator.py" --input "$BAM" --output "$OUTDIR/candidates.vcf" \
+      --snp_min_freq 0.075 --indel_min_freq 0.02 ${BED:+--bedfile "$BED"} --keep_multialleles \
+      > "$OUTDIR/candidate_generator.log" 2>&1
+fi
+if [ ! -f "$OUTDIR/isec/0003.vcf" ]; then
+  printf "Intersect candidates with the truth set...\n"
+  python "$SCRIPTDIR/tools/vcf_isec.py" -p "$OUTDIR/isec" "$TRUTH" "$OUTDIR/candidates.vcf" > "$OUTDIR/isec.log" 2>&1
+fi
+if [ ! -f "$OUTDIR/train.hdf" ]; then
+  printf "Convert candidates to HDF...\n"
+  python "$SCRIPTDIR/tools/convert_bam_single_reads.py" --input "$BAM" --tp_vcf "$OUTDIR/isec/0003.vcf" \
+      --tp_full_vcf "$OUTDIR/isec/0002.vcf" --fp_vcf "$OUTDIR/isec/0001.vcf" --fasta-input "$REFERENCE" \
+      --output "$OUTDIR/train.hdf" --max-reads 200 --num-processes "$PROCS" --locations-process-step 100000 \
+      --max-insert-length 10 --max-insert-length-variant 50 --save-q-scores --save-strand > "$OUTDIR/training_data.log" 2>&1
+fi
+echo "Training data in $OUTDIR/train.hdf"
