@@ -1,0 +1,523 @@
+// Host side of libdl4vc_pileup.so (C ABI: include/dl4vc_pileup_gpu.h).  Locations are sorted by (tid, position) and cut
+// into runs; worker threads, each with its own BAM and FASTA handles, fetch every run's records once (BAI linear index; a
+// BAM without one gets the same index built by one scan), frame and validate them (bam_native.h::frame_record), and read
+// the run's reference slice as tokens.  The records of a batch of locations go to the device in one pinned buffer; the
+// kernels (pileup_kernels.hip) do the rest.  Every extern "C" body catches what it throws: a corrupt file is an error code,
+// never an abort.
+#include "../../include/dl4vc_pileup_gpu.h"
+#include "bam_native.h"
+#include "fasta_native.h"
+#include "pileup_device.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cstdarg>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+namespace {
+
+std::string g_err;
+
+constexpr int FLAG_MASK = 0x4 | 0x100 | 0x200 | 0x400;   // unmapped, secondary, QC fail, duplicate (dan_pileup.cpp)
+constexpr int FREVERSE = 0x10;
+constexpr int BATCH_LOCS = 512;                          // locations per device batch
+constexpr int64_t RUN_GAP = 4096, RUN_SPAN = 1 << 20;    // a run: locations closer than RUN_GAP, at most RUN_SPAN bases
+constexpr int MAX_THREADS = 8;
+constexpr int64_t MAX_NREF = 1 << 29;                     // a longer reference span is a corrupt record (no contig is longer)
+
+// the converter's token table (dan_pileup.cpp::Tables); REF_UNKNOWN for a character outside it
+struct RefTokens {
+    uint8_t tok[256];
+    RefTokens() {
+        memset(tok, pg::REF_UNKNOWN, sizeof tok);
+        auto set = [&](const char* cs, uint8_t v) { for (; *cs; ++cs) tok[(uint8_t)*cs] = v; };
+        set("Aa", 1); set("TtUu", 2); set("Gg", 3); set("Cc", 4); set("-*NnXx.,", 5); set("e", 7);
+        set("?MmKkRrYySsWwBbVvHhDd", 9);
+    }
+};
+const RefTokens RT;
+
+struct Entry {
+    int32_t tid, pos1;
+    int64_t idx;          // position in the caller's arrays
+    int32_t pre;          // -1: encode on the device; 0 / 2: decided here
+};
+
+struct Run {
+    int64_t e0, e1;       // entries [e0, e1) of the sorted list
+    int32_t tid;
+    int64_t s0, stop;     // union of the locations' fetch windows
+    const char* contig;
+    // filled by a worker
+    std::vector<uint8_t> bytes;
+    std::vector<pg::Rec> recs;   // off relative to bytes, res relative to the run
+    std::vector<uint8_t> ref;    // tokens of [s0, stop)
+    int64_t max_nref = 0;
+    int64_t nres = 0;
+    bool sorted = true;
+    std::string err;
+};
+
+// One host framing thread's file handles, kept for the encoder's life (a FASTA without .fai is scanned once, at pg_open).
+struct Worker {
+    bamn::BamFile bam;
+    fastan::Fasta fasta;
+    std::vector<uint8_t> blk;
+};
+
+template <class T>
+bool grow(T*& p, size_t& cap, size_t n) {
+    if (n <= cap) return true;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    const size_t want = n + n / 4 + 64;
+    if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) return false;
+    cap = want;
+    return true;
+}
+
+}  // namespace
+
+struct pg_encoder {
+    std::string bam_path, fasta_path, err;
+    pe_options opt{};
+    int32_t device = 0;
+    bamn::BamFile header;
+    fastan::Fasta fasta;
+    bamn::Bai bai;
+    bool have_bai = false, scanned = false;
+    std::vector<std::unique_ptr<Worker>> workers;
+    hipStream_t stream = nullptr;
+    uint8_t* d_buf = nullptr; size_t c_buf = 0;
+    pg::Rec* d_recs = nullptr; size_t c_recs = 0;
+    pg::Loc* d_locs = nullptr; size_t c_locs = 0;
+    uint8_t* d_ref = nullptr; size_t c_ref = 0;
+    int32_t* d_qpos = nullptr; size_t c_qpos = 0;
+    int32_t* d_indel = nullptr; size_t c_indel = 0;
+    uint8_t* d_isdel = nullptr; size_t c_isdel = 0;
+    uint8_t* d_small = nullptr; size_t c_small = 0;   // ref [B][W] | num [B] i32 | status [B] i8
+    uint8_t* d_planes = nullptr; size_t c_planes = 0; // pg_encode: [3][B][max_reads][W]
+    uint8_t* h_buf = nullptr; size_t hc_buf = 0;      // pinned
+    uint8_t* h_planes = nullptr; size_t hc_planes = 0;
+    ~pg_encoder() {
+        for (void* p : {(void*)d_buf, (void*)d_recs, (void*)d_locs, (void*)d_ref, (void*)d_qpos, (void*)d_indel, (void*)d_isdel,
+                        (void*)d_small, (void*)d_planes})
+            if (p) (void)hipFree(p);
+        if (h_buf) (void)hipHostFree(h_buf);
+        if (h_planes) (void)hipHostFree(h_planes);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+
+int fail(pg_encoder* h, int code, const char* fmt, ...) {
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    (h ? h->err : g_err) = buf;
+    return code;
+}
+
+bool pinned_grow(uint8_t*& p, size_t& cap, size_t n) {
+    if (n <= cap) return true;
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    const size_t want = n + n / 4 + 4096;
+    if (hipHostMalloc((void**)&p, want, hipHostMallocDefault) != hipSuccess) return false;
+    cap = want;
+    return true;
+}
+
+int get_tid(const bamn::BamFile& b, const std::string& name) {
+    auto it = b.tid_of.find(name);
+    if (it != b.tid_of.end()) return it->second;
+    const std::string alt = name.rfind("chr", 0) == 0 ? name.substr(3) : "chr" + name;
+    it = b.tid_of.find(alt);
+    return it == b.tid_of.end() ? -1 : it->second;
+}
+
+struct Cigar { int64_t nref = 0; bool has_ref = false, skip = false; };
+// nullptr, or why the record's reference span cannot be trusted (it sizes the device's resolution arrays)
+const char* walk_cigar(const uint8_t* b, const bamn::RecordFrame& fr, Cigar& c) {
+    c = Cigar{};
+    for (int i = 0; i < fr.n_cig; ++i) {
+        uint32_t v;
+        memcpy(&v, b + fr.cigar_off + 4 * i, 4);
+        const int op = v & 0xf;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) { c.nref += (int64_t)(v >> 4); c.has_ref = true; }
+        if (op == 3) c.skip = true;
+    }
+    if (c.nref > MAX_NREF || (int64_t)fr.pos + c.nref > INT32_MAX) return "corrupt BAM record (CIGAR reference length)";
+    return nullptr;
+}
+
+// A BAM without a BAI: the linear index (the smallest virtual offset of a record overlapping each 16 kbp window) from one scan.
+int build_linear_index(pg_encoder* h) {
+    bamn::BamFile bam;
+    if (!bam.open(h->bam_path)) return fail(h, -3, "%s", bam.err.c_str());
+    std::vector<uint8_t> blk;
+    h->bai.linear.assign(bam.refs.size(), {});
+    for (;;) {
+        const int64_t voff = bam.r.tell();
+        const int got = bam.next_block(blk);
+        if (got == 0) break;
+        if (got < 0) return fail(h, -3, "%s (record at virtual offset %lld)", bam.err.c_str(), (long long)voff);
+        bamn::RecordFrame fr;
+        if (const char* why = bamn::frame_record(blk.data(), blk.size(), fr))
+            return fail(h, -3, "%s (record at virtual offset %lld)", why, (long long)voff);
+        if (fr.tid < 0 || fr.tid >= (int)bam.refs.size() || fr.pos < 0) continue;
+        Cigar c;
+        if (const char* why = walk_cigar(blk.data(), fr, c))
+            return fail(h, -3, "%s (record at virtual offset %lld)", why, (long long)voff);
+        const int64_t end = (int64_t)fr.pos + std::max<int64_t>(c.nref, 1);
+        auto& lin = h->bai.linear[fr.tid];
+        const size_t w1 = (size_t)((end - 1) >> 14);
+        if (lin.size() <= w1) lin.resize(w1 + 1, 0);
+        for (size_t w = (size_t)(fr.pos >> 14); w <= w1; ++w) if (!lin[w]) lin[w] = (uint64_t)voff;
+    }
+    h->have_bai = true;
+    return 0;
+}
+
+// The records of one run: tid == run.tid, pos < stop and pos + max(nref, 1) > s0 (the window reader of dan_pileup.cpp),
+// plus the run's reference tokens.
+void fetch_run(pg_encoder* h, bamn::BamFile& bam, fastan::Fasta& fasta, std::vector<uint8_t>& blk, Run& run) {
+    std::string seq;
+    fasta.fetch(run.contig, run.s0, run.stop, seq);
+    run.ref.resize((size_t)(run.stop - run.s0));
+    for (size_t i = 0; i < run.ref.size(); ++i) run.ref[i] = i < seq.size() ? RT.tok[(uint8_t)seq[i]] : 5;
+    const uint64_t at = h->bai.linear_offset(run.tid, run.s0);
+    if (at == 0) return;
+    if (!bam.r.seek((int64_t)at)) { run.err = "BGZF: " + bam.r.err; return; }
+    int32_t last_pos = -1;
+    for (;;) {
+        const int64_t voff = bam.r.tell();
+        const int got = bam.next_block(blk);
+        if (got == 0) return;
+        if (got < 0) { run.err = bam.err + " (record at virtual offset " + std::to_string(voff) + ")"; return; }
+        bamn::RecordFrame fr;
+        if (const char* why = bamn::frame_record(blk.data(), blk.size(), fr)) {
+            run.err = std::string(why) + " (record at virtual offset " + std::to_string(voff) + ")";
+            return;
+        }
+        if (fr.tid != run.tid) {
+            if (fr.tid < 0 || fr.tid > run.tid) return;
+            continue;
+        }
+        if (fr.pos >= run.stop) return;
+        Cigar c;
+        if (const char* why = walk_cigar(blk.data(), fr, c)) {
+            run.err = std::string(why) + " (record at virtual offset " + std::to_string(voff) + ")";
+            return;
+        }
+        if ((int64_t)fr.pos + std::max<int64_t>(c.nref, 1) <= run.s0) continue;
+        if (fr.pos < last_pos) run.sorted = false;
+        last_pos = fr.pos;
+        pg::Rec m{};
+        m.off = run.bytes.size();
+        m.pos = fr.pos;
+        m.end = (int32_t)(fr.pos + c.nref);
+        m.res = (int32_t)std::min<int64_t>(run.nres, INT32_MAX);   // (a batch past INT32_MAX positions is refused below)
+        m.l_seq = fr.l_seq;
+        m.cigar_off = fr.cigar_off; m.seq_off = fr.seq_off; m.qual_off = fr.qual_off;
+        m.n_cig = fr.n_cig; m.l_name = fr.l_name;
+        m.bits = ((fr.flag & FLAG_MASK) ? 0 : pg::R_FLAG_OK) | (c.has_ref ? pg::R_HAS_REF : 0) | (c.skip ? pg::R_SKIP : 0) |
+                 ((fr.flag & FREVERSE) ? pg::R_REVERSE : 0);
+        run.nres += c.nref;
+        run.max_nref = std::max(run.max_nref, c.nref);
+        run.recs.push_back(m);
+        run.bytes.insert(run.bytes.end(), blk.begin(), blk.end());
+        run.bytes.resize((run.bytes.size() + 3) & ~(size_t)3);
+    }
+}
+
+// Encodes sorted entries [b0, b1) on h->stream.  Planes go to (reads, qual, strand) at slot = entry.idx when `by_index`,
+// else at slot = position in the batch; ref / num / status of the batch are left in h->d_small.
+int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& es, int64_t b0, int64_t b1, uint8_t* reads,
+                 uint8_t* qual, uint8_t* strand, bool by_index) {
+    const pe_options& o = h->opt;
+    const int w = o.window_size, W = 2 * w + 1;
+    std::vector<Run> runs;
+    for (int64_t i = b0; i < b1; ++i) {
+        const Entry& e = es[i];
+        if (e.pre >= 0) continue;
+        const int64_t s0 = std::max<int64_t>((int64_t)e.pos1 - (w + 2), 0), stop = (int64_t)e.pos1 + w + 3;
+        if (!runs.empty()) {
+            Run& r = runs.back();
+            if (r.e1 == i && r.tid == e.tid && strcmp(r.contig, contigs[e.idx]) == 0 && s0 <= r.stop + RUN_GAP && stop - r.s0 <= RUN_SPAN) {
+                r.e1 = i + 1;
+                r.stop = std::max(r.stop, stop);
+                continue;
+            }
+        }
+        Run r;
+        r.e0 = i; r.e1 = i + 1; r.tid = e.tid; r.s0 = s0; r.stop = stop; r.contig = contigs[e.idx];
+        runs.push_back(std::move(r));
+    }
+    // host framing, one run at a time per worker; the workers' file handles are opened once per encoder
+    {
+        const int nt = std::max(1, std::min<int>({MAX_THREADS, (int)std::max(1u, std::thread::hardware_concurrency()), (int)runs.size()}));
+        while ((int)h->workers.size() < nt) {
+            auto wk = std::make_unique<Worker>();
+            if (!wk->bam.open(h->bam_path)) return fail(h, -3, "%s", wk->bam.err.c_str());
+            wk->fasta.f = fopen(h->fasta_path.c_str(), "rb");
+            if (!wk->fasta.f) return fail(h, -3, "cannot open %s", h->fasta_path.c_str());
+            wk->fasta.index = h->fasta.index;
+            h->workers.push_back(std::move(wk));
+        }
+        std::atomic<size_t> next{0};
+        std::mutex mu;
+        std::string open_err;
+        auto worker = [&](Worker* wk) {
+            try {
+                for (;;) {
+                    const size_t r = next.fetch_add(1);
+                    if (r >= runs.size()) return;
+                    fetch_run(h, wk->bam, wk->fasta, wk->blk, runs[r]);
+                }
+            } catch (const std::exception& ex) {
+                std::lock_guard<std::mutex> lk(mu);
+                open_err = std::string("host framing: ") + ex.what();
+            }
+        };
+        std::vector<std::thread> pool;
+        for (int t = 1; t < nt && !runs.empty(); ++t) pool.emplace_back(worker, h->workers[t].get());
+        if (!runs.empty()) worker(h->workers[0].get());
+        for (auto& t : pool) t.join();
+        if (!open_err.empty()) return fail(h, -3, "%s", open_err.c_str());
+        for (auto& r : runs) if (!r.err.empty()) return fail(h, -3, "%s", r.err.c_str());
+    }
+    // gather
+    size_t bytes = 0, n_recs = 0, n_ref = 0;
+    int64_t n_res = 0;
+    for (auto& r : runs) { bytes += r.bytes.size(); n_recs += r.recs.size(); n_ref += r.ref.size(); n_res += r.nres; }
+    if (n_res > INT32_MAX || n_recs > INT32_MAX) return fail(h, -1, "batch too large (%lld reference positions of records)", (long long)n_res);
+    if (!pinned_grow(h->h_buf, h->hc_buf, bytes + 4)) return fail(h, -2, "hipHostMalloc(%zu) failed", bytes);
+    std::vector<pg::Rec> recs;
+    recs.reserve(n_recs);
+    std::vector<uint8_t> ref;
+    ref.reserve(n_ref);
+    const int64_t nb = b1 - b0;
+    std::vector<pg::Loc> locs((size_t)nb);
+    for (int64_t i = 0; i < nb; ++i) {
+        const Entry& e = es[b0 + i];
+        pg::Loc& L = locs[i];
+        L = pg::Loc{};
+        L.pre = e.pre;
+        L.slot = by_index ? e.idx : i;
+    }
+    size_t at = 0;
+    int64_t res = 0;
+    for (auto& r : runs) {
+        const int32_t rec0 = (int32_t)recs.size();
+        const int64_t ref0 = (int64_t)ref.size();
+        if (!r.bytes.empty()) memcpy(h->h_buf + at, r.bytes.data(), r.bytes.size());
+        for (auto m : r.recs) { m.off += at; m.res += (int32_t)res; recs.push_back(m); }   // (res + nres <= INT32_MAX, checked above)
+        ref.insert(ref.end(), r.ref.begin(), r.ref.end());
+        for (int64_t i = r.e0; i < r.e1; ++i) {
+            const Entry& e = es[i];
+            pg::Loc& L = locs[i - b0];
+            const int64_t s0 = std::max<int64_t>((int64_t)e.pos1 - (w + 2), 0), stop = (int64_t)e.pos1 + w + 3;
+            L.s0 = (int32_t)s0; L.stop = (int32_t)stop; L.ci = (int32_t)(e.pos1 - 1 - s0);
+            L.ref = ref0 + (s0 - r.s0);
+            if (!r.sorted) { L.pre = 2; continue; }                // (the stable order by clipped start needs sorted records)
+            auto lower = std::lower_bound(r.recs.begin(), r.recs.end(), s0 - r.max_nref,
+                                          [](const pg::Rec& m, int64_t v) { return (int64_t)m.pos < v; });
+            auto upper = std::lower_bound(r.recs.begin(), r.recs.end(), stop, [](const pg::Rec& m, int64_t v) { return (int64_t)m.pos < v; });
+            L.first = rec0 + (int32_t)(lower - r.recs.begin());
+            L.last = rec0 + (int32_t)(upper - r.recs.begin());
+        }
+        at += r.bytes.size();
+        res += r.nres;
+        std::vector<uint8_t>().swap(r.bytes);
+    }
+    // device
+    hipStream_t s = h->stream;
+    const size_t small = (size_t)nb * (W + 4 + 1);
+    if (!grow(h->d_buf, h->c_buf, bytes + 4) || !grow(h->d_recs, h->c_recs, recs.size() + 1) || !grow(h->d_locs, h->c_locs, locs.size() + 1) ||
+        !grow(h->d_ref, h->c_ref, ref.size() + 1) || !grow(h->d_qpos, h->c_qpos, (size_t)res + 1) ||
+        !grow(h->d_indel, h->c_indel, (size_t)res + 1) || !grow(h->d_isdel, h->c_isdel, (size_t)res + 1) ||
+        !grow(h->d_small, h->c_small, small + 16))
+        return fail(h, -2, "hipMalloc failed (batch of %lld locations, %zu records)", (long long)nb, recs.size());
+    uint8_t* d_ref_small = h->d_small;
+    int32_t* d_num = (int32_t*)(h->d_small + (((size_t)nb * W + 3) & ~(size_t)3));
+    int8_t* d_status = (int8_t*)(d_num + nb);
+    hipError_t rc = hipSuccess;
+    auto ok = [&](hipError_t r) { if (rc == hipSuccess) rc = r; };
+    if (bytes) ok(hipMemcpyAsync(h->d_buf, h->h_buf, bytes, hipMemcpyHostToDevice, s));
+    if (!recs.empty()) ok(hipMemcpyAsync(h->d_recs, recs.data(), recs.size() * sizeof(pg::Rec), hipMemcpyHostToDevice, s));
+    ok(hipMemcpyAsync(h->d_locs, locs.data(), locs.size() * sizeof(pg::Loc), hipMemcpyHostToDevice, s));
+    if (!ref.empty()) ok(hipMemcpyAsync(h->d_ref, ref.data(), ref.size(), hipMemcpyHostToDevice, s));
+    ok(pg::launch_resolve(h->d_buf, h->d_recs, (int32_t)recs.size(), h->d_qpos, h->d_indel, h->d_isdel, s));
+    const pg::Params P{w, W, o.max_reads, o.max_insert_length, o.max_insert_length_variant};
+    ok(pg::launch_encode(h->d_buf, h->d_recs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, reads, qual,
+                         strand, d_ref_small, d_num, d_status, s));
+    // (the pageable copies above read the host vectors before this returns)
+    ok(hipStreamSynchronize(s));
+    if (rc != hipSuccess) return fail(h, -2, "device: %s", hipGetErrorString(rc));
+    return 0;
+}
+
+int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads, uint8_t* qual,
+               uint8_t* strand, uint8_t* ref_out, int32_t* num_out, int8_t* status_out, bool device_planes, void* stream) {
+    if (n < 0 || (n > 0 && (!contigs || !positions || !reads || !qual || !strand || !ref_out || !num_out || !status_out)))
+        return fail(h, -1, "null argument");
+    const pe_options& o = h->opt;
+    const int W = 2 * o.window_size + 1, MR = o.max_reads;
+    const size_t plane = (size_t)MR * W;
+    // (a BAM without a BAI is indexed by one scan here, before the device is touched: a corrupt record needs no GPU)
+    if (!h->have_bai && !h->scanned) {
+        h->scanned = true;
+        const int rc = build_linear_index(h);
+        if (rc) { h->scanned = false; return rc; }
+    }
+    // the caller's current device is restored on every return
+    struct DeviceGuard {
+        int prev = -1;
+        ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+    } guard;
+    if (hipGetDevice(&guard.prev) != hipSuccess) guard.prev = -1;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(h, -2, "hipSetDevice(%d) failed", h->device);
+    if (!h->stream && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(h, -2, "hipStreamCreate failed");
+    // the caller's stream must not run ahead of (or behind) our work on its planes
+    hipStream_t cs = (hipStream_t)stream;
+    if (device_planes) {
+        hipEvent_t ev;
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(h, -2, "hipEventCreate failed");
+        const bool good = hipEventRecord(ev, cs) == hipSuccess && hipStreamWaitEvent(h->stream, ev, 0) == hipSuccess;
+        (void)hipEventDestroy(ev);
+        if (!good) return fail(h, -2, "cannot order the encoder after the caller's stream");
+    }
+    std::vector<Entry> es((size_t)n);
+    const bool plan = o.window_size <= pg::MAX_WINDOW && o.min_base_quality <= 0;
+    std::string last_name;
+    int last_tid = -1;
+    bool last_fa = false;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!contigs[i]) return fail(h, -1, "contig %lld is NULL", (long long)i);
+        if (i == 0 || last_name != contigs[i]) {
+            last_name = contigs[i];
+            last_tid = get_tid(h->header, last_name);
+            last_fa = h->fasta.entry(last_name) != nullptr;
+        }
+        Entry& e = es[i];
+        e.tid = last_tid; e.pos1 = positions[i]; e.idx = i;
+        e.pre = last_tid < 0 ? 0 : (!last_fa || !plan) ? 2 : -1;   // (encode_one's order: no tid, no FASTA sequence, options)
+        if (e.pre < 0 && (positions[i] < 1 || (int64_t)positions[i] + o.window_size + 3 > INT32_MAX)) e.pre = 2;
+    }
+    std::stable_sort(es.begin(), es.end(), [](const Entry& a, const Entry& b) {
+        const int ka = a.pre < 0 ? 0 : 1, kb = b.pre < 0 ? 0 : 1;
+        if (ka != kb) return ka < kb;
+        return a.tid != b.tid ? a.tid < b.tid : a.pos1 < b.pos1;
+    });
+    if (!device_planes && !grow(h->d_planes, h->c_planes, 3 * plane * BATCH_LOCS))
+        return fail(h, -2, "hipMalloc of the plane buffer failed");
+    if (!device_planes && !pinned_grow(h->h_planes, h->hc_planes, 3 * plane * BATCH_LOCS))
+        return fail(h, -2, "hipHostMalloc of the plane buffer failed");
+    std::vector<uint8_t> small;
+    for (int64_t b0 = 0; b0 < n; b0 += BATCH_LOCS) {
+        const int64_t b1 = std::min<int64_t>(n, b0 + BATCH_LOCS), nb = b1 - b0;
+        uint8_t* R = device_planes ? reads : h->d_planes;
+        uint8_t* Q = device_planes ? qual : h->d_planes + plane * BATCH_LOCS;
+        uint8_t* S = device_planes ? strand : h->d_planes + 2 * plane * BATCH_LOCS;
+        int rc = encode_batch(h, contigs, es, b0, b1, R, Q, S, device_planes);
+        if (rc) return rc;
+        const size_t small_bytes = (((size_t)nb * W + 3) & ~(size_t)3) + (size_t)nb * 5;
+        small.resize(small_bytes);
+        if (hipMemcpy(small.data(), h->d_small, small_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, -2, "hipMemcpy failed");
+        const int32_t* num = (const int32_t*)(small.data() + (((size_t)nb * W + 3) & ~(size_t)3));
+        const int8_t* st = (const int8_t*)(num + nb);
+        if (!device_planes) {
+            for (int c = 0; c < 3; ++c)
+                if (hipMemcpy(h->h_planes + c * plane * BATCH_LOCS, h->d_planes + c * plane * BATCH_LOCS, plane * nb, hipMemcpyDeviceToHost) != hipSuccess)
+                    return fail(h, -2, "hipMemcpy failed");
+        }
+        for (int64_t i = 0; i < nb; ++i) {
+            const int64_t j = es[b0 + i].idx;
+            status_out[j] = st[i];
+            num_out[j] = num[i];
+            memcpy(ref_out + (size_t)j * W, small.data() + (size_t)i * W, W);
+            if (!device_planes)
+                for (int c = 0; c < 3; ++c) {
+                    uint8_t* dst = c == 0 ? reads : c == 1 ? qual : strand;
+                    memcpy(dst + (size_t)j * plane, h->h_planes + c * plane * BATCH_LOCS + (size_t)i * plane, plane);
+                }
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* pg_last_error(const pg_encoder_t* h) { return h ? h->err.c_str() : g_err.c_str(); }
+
+int pg_open(const char* bam_path, const char* bai_path, const char* fasta_path, const pe_options* opt, int32_t device, pg_encoder_t** out) {
+    try {
+        if (!bam_path || !fasta_path || !opt || !out) return fail(nullptr, -1, "pg_open: null argument");
+        *out = nullptr;
+        if (opt->window_size < 1 || opt->max_reads < 1) return fail(nullptr, -1, "pg_open: window_size and max_reads must be positive");
+        std::unique_ptr<pg_encoder> h(new pg_encoder());
+        h->bam_path = bam_path; h->fasta_path = fasta_path; h->opt = *opt; h->device = device;
+        if (!h->header.open(bam_path)) return fail(nullptr, -3, "%s", h->header.err.c_str());
+        std::string err;
+        if (!h->fasta.open(fasta_path, err)) return fail(nullptr, -3, "%s", err.c_str());
+        std::vector<std::string> cands;
+        if (bai_path && *bai_path) cands.push_back(bai_path);
+        else {
+            cands.push_back(std::string(bam_path) + ".bai");
+            const std::string p(bam_path);
+            const size_t dot = p.find_last_of('.'), slash = p.find_last_of('/');
+            if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) cands.push_back(p.substr(0, dot) + ".bai");
+        }
+        for (auto& c : cands) if (h->bai.load(c)) { h->have_bai = true; break; }
+        *out = h.release();
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(nullptr, -4, "pg_open: %s", e.what());
+    } catch (...) {
+        return fail(nullptr, -4, "pg_open: unknown exception");
+    }
+}
+
+int pg_encode(pg_encoder_t* h, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads_out, uint8_t* qual_out,
+              uint8_t* strand_out, uint8_t* ref_out, int32_t* num_reads_out, int8_t* status_out) {
+    if (!h) return fail(nullptr, -1, "pg_encode: null handle");
+    try {
+        return encode_all(h, contigs, positions, n, reads_out, qual_out, strand_out, ref_out, num_reads_out, status_out, false, nullptr);
+    } catch (const std::exception& e) {
+        return fail(h, -4, "pg_encode: %s", e.what());
+    } catch (...) {
+        return fail(h, -4, "pg_encode: unknown exception");
+    }
+}
+
+int pg_encode_device(pg_encoder_t* h, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads_dev,
+                     uint8_t* qual_dev, uint8_t* strand_dev, uint8_t* ref_out, int32_t* num_reads_out, int8_t* status_out,
+                     void* stream) {
+    if (!h) return fail(nullptr, -1, "pg_encode_device: null handle");
+    try {
+        return encode_all(h, contigs, positions, n, reads_dev, qual_dev, strand_dev, ref_out, num_reads_out, status_out, true, stream);
+    } catch (const std::exception& e) {
+        return fail(h, -4, "pg_encode_device: %s", e.what());
+    } catch (...) {
+        return fail(h, -4, "pg_encode_device: unknown exception");
+    }
+}
+
+void pg_close(pg_encoder_t* h) {
+    try {
+        delete h;
+    } catch (...) {
+    }
+}
+
+}  // extern "C"

@@ -1,0 +1,51 @@
+// Shared between the host side (pileup_capi.cpp) and the kernels (pileup_kernels.hip) of libdl4vc_pileup.so.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace pg {
+
+constexpr int BLOCK = 256;                   // threads per location workgroup (four wave64)
+constexpr int MAX_TRACKS = 1024;             // PG_MAX_TRACKS
+constexpr int MAX_WINDOW = 100;              // PG_MAX_WINDOW
+constexpr int MAX_POS = 2 * MAX_WINDOW + 5;  // reference positions of one location's fetch window [s0, stop)
+constexpr int HASH_SLOTS = 2 * MAX_TRACKS;   // LDS open-addressing table of name:sequence hashes
+constexpr uint8_t REF_UNKNOWN = 0xff;        // a reference base outside the token table
+
+enum : uint32_t { R_FLAG_OK = 1, R_HAS_REF = 2, R_SKIP = 4, R_REVERSE = 8, R_EQ = 16 };
+
+// One framed record of a batch (the host fills all but hash and R_EQ, which the resolve kernel adds).
+struct Rec {
+    uint64_t off;          // first byte of the record (after block_size) in the batch buffer
+    uint64_t hash;         // FNV-1a 64 of name ':' sequence, never 0
+    int32_t pos, end;      // end = pos + reference-consuming length (nref)
+    int32_t res;           // first of the record's nref entries in the resolution arrays
+    int32_t l_seq;
+    uint32_t cigar_off, seq_off, qual_off;
+    uint32_t n_cig, l_name;
+    uint32_t bits;
+};
+
+// One location of a batch.
+struct Loc {
+    int32_t s0, stop, ci;  // fetch window [s0, stop) and the 0-based offset of the candidate position in it
+    int32_t first, last;   // candidate records [first, last) of the batch
+    int32_t pre;           // -1: encode; 0 or 2: status decided on the host
+    int64_t ref;           // index of position s0 in the batch's reference token array
+    int64_t slot;          // plane slot the location writes (every slot is written, zeros unless status 1)
+};
+
+struct Params {
+    int32_t w, W, max_reads, max_insert_length, max_insert_length_variant;
+};
+
+hipError_t launch_resolve(const uint8_t* buf, Rec* recs, int32_t n_recs, int32_t* qpos, int32_t* indel, uint8_t* isdel,
+                          hipStream_t s);
+hipError_t launch_encode(const uint8_t* buf, const Rec* recs, const Loc* locs, int32_t n_locs, const uint8_t* reftok,
+                         const int32_t* qpos, const int32_t* indel, const uint8_t* isdel, Params p, uint8_t* reads,
+                         uint8_t* qual, uint8_t* strand, uint8_t* ref_small, int32_t* num_small, int8_t* status_small,
+                         hipStream_t s);
+
+}  // namespace pg

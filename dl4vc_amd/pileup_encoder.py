@@ -407,24 +407,44 @@ def encode_location(bam, fasta, loc: Location, opt: EncoderOptions, reader=None)
 
 
 def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Location], opt: EncoderOptions,
-                     native: Optional[bool] = None, threads: int = 1) -> Tuple[np.ndarray, int]:
+                     native: Optional[bool] = None, threads: int = 1, device: Optional[str] = None,
+                     device_id: int = 0) -> Tuple[np.ndarray, int]:
     """Records for ``locations`` in input order and the number of locations that produced none.
 
     ``native`` (default: when libdl4vc_loader.so is built): the image planes come from the C++ encoder (``pe_encode``:
     BGZF / BAM / CIGAR / image builder in ``threads`` worker threads); a location it declines (status 2: the cases
     ``process_tracks`` hands to the column-by-column builder) is encoded here, so the records are the same bytes either
-    way (tests/test_pileup_native.py)."""
+    way (tests/test_pileup_native.py).
+
+    ``device="gpu"`` (default None: the host encoders above): the planes come from the GPU encoder (libdl4vc_pileup.so on HIP device ``device_id``) first; what it
+    declines goes to ``pe_encode``, and what that declines to the Python encoder -- the same bytes and error count as
+    ``native=True`` (tests/test_pileup_gpu.py).  A missing libdl4vc_pileup.so is an error, not a fall-back."""
     from .bamio import BamFile, FastaFile, WindowReader
     from . import loader
+    if device not in (None, "gpu"):
+        raise ValueError("device must be None (host encoders) or 'gpu', not %r" % (device,))
     dtype = record_dtype(opt.max_reads, 2 * opt.window_size + 1)
     out = np.zeros(len(locations), dtype)
     n = errors = 0
     use_native = loader.available() if native is None else native
     planes = None
-    if use_native and len(locations):
+    contigs, positions = [l.contig for l in locations], [l.pos for l in locations]
+    if device == "gpu" and len(locations):
+        from . import pileup_gpu
+        with pileup_gpu.GpuPileupEncoder(bam_path, fasta_path, opt.window_size, opt.max_reads, opt.max_insert_length,
+                                         opt.max_insert_length_variant, opt.min_base_quality, device=device_id) as enc:
+            planes = enc.encode(contigs, positions)
+        declined = np.flatnonzero(planes[5] == 2)
+        if len(declined):
+            with loader.NativePileupEncoder(bam_path, fasta_path, opt.window_size, opt.max_reads, opt.max_insert_length,
+                                            opt.max_insert_length_variant, opt.min_base_quality) as enc:
+                sub = enc.encode([contigs[i] for i in declined], [positions[i] for i in declined], threads)
+            for full, part in zip(planes, sub):
+                full[declined] = part
+    elif use_native and len(locations):
         with loader.NativePileupEncoder(bam_path, fasta_path, opt.window_size, opt.max_reads, opt.max_insert_length,
                                         opt.max_insert_length_variant, opt.min_base_quality) as enc:
-            planes = enc.encode([l.contig for l in locations], [l.pos for l in locations], threads)
+            planes = enc.encode(contigs, positions, threads)
     bam = fasta = reader = None
     try:
         for i, loc in enumerate(locations):

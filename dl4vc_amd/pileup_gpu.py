@@ -1,0 +1,107 @@
+"""ctypes binding of libdl4vc_pileup.so (``include/dl4vc_pileup_gpu.h``): the pileup encoder of ``loader.NativePileupEncoder``
+(``pe_*``) with the record planes built on the GPU.
+
+Status per location: 1 = planes byte-identical to ``pe_encode``'s, 0 = no record (only where ``pe_encode`` also gives 0),
+2 = declined -- ``pileup_encoder.encode_locations(device="gpu")`` hands those to ``pe_encode`` and what that declines to the
+Python encoder."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional, Sequence
+
+import numpy as np
+
+from .loader import PileupOptions
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_pileup.so")
+SYMBOLS = ("pg_open", "pg_encode", "pg_encode_device", "pg_close", "pg_last_error")
+MAX_TRACKS = 1024            # PG_MAX_TRACKS
+MAX_WINDOW = 100             # PG_MAX_WINDOW
+_lib = None
+
+
+def available() -> bool:
+    return os.path.isfile(LIB_PATH)
+
+
+def load_library() -> C.CDLL:
+    global _lib
+    if _lib is None:
+        if not os.path.isfile(LIB_PATH):
+            raise RuntimeError("%s is not built (make -C dl4vc_amd/csrc)" % LIB_PATH)
+        lib = C.CDLL(LIB_PATH)
+        vp = C.c_void_p
+        lib.pg_open.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PileupOptions), C.c_int32, C.POINTER(vp)]
+        lib.pg_encode.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
+        lib.pg_encode_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
+        lib.pg_close.argtypes = [vp]
+        lib.pg_close.restype = None
+        lib.pg_last_error.argtypes = [vp]
+        lib.pg_last_error.restype = C.c_char_p
+        _lib = lib
+    return _lib
+
+
+class GpuPileupEncoder:
+    """Image planes of a list of locations, in input order; the same outputs as ``loader.NativePileupEncoder.encode``."""
+
+    def __init__(self, bam_path: str, fasta_path: str, window_size: int, max_reads: int, max_insert_length: int,
+                 max_insert_length_variant: int, min_base_quality: int = 0, bai_path: Optional[str] = None, device: int = 0):
+        self.lib = load_library()
+        self._h = C.c_void_p()
+        self.window, self.max_reads, self.device = 2 * window_size + 1, max_reads, device
+        opt = PileupOptions(window_size, max_reads, max_insert_length, max_insert_length_variant, min_base_quality)
+        rc = self.lib.pg_open(bam_path.encode(), bai_path.encode() if bai_path else None, fasta_path.encode(), C.byref(opt),
+                              int(device), C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            raise RuntimeError("pg_open failed: %s" % self.lib.pg_last_error(None).decode())
+
+    def _args(self, contigs: Sequence[str], positions):
+        n = len(positions)
+        names = (C.c_char_p * max(n, 1))(*[c.encode() for c in contigs])
+        pos = np.ascontiguousarray(positions, np.int32)
+        ref = np.zeros((n, self.window), np.uint8)
+        num = np.zeros(n, np.int32)
+        status = np.zeros(n, np.int8)
+        return n, names, pos, ref, num, status
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError("%s failed: %s" % (what, self.lib.pg_last_error(self._h).decode()))
+
+    def encode(self, contigs: Sequence[str], positions):
+        """-> (reads, qual, strand [n][max_reads][W] u8, ref [n][W] u8, num_reads [n] i32, status [n] i8), host arrays."""
+        n, names, pos, ref, num, status = self._args(contigs, positions)
+        reads, qual, strand = (np.zeros((n, self.max_reads, self.window), np.uint8) for _ in range(3))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self._check(self.lib.pg_encode(self._h, C.cast(names, C.c_void_p), p(pos), n, p(reads), p(qual), p(strand), p(ref),
+                                       p(num), p(status)), "pg_encode")
+        return reads, qual, strand, ref, num, status
+
+    def encode_device(self, contigs: Sequence[str], positions, stream=None):
+        """-> (reads, qual, strand: torch uint8 [n][max_reads][W] on the encoder's device, ref, num_reads, status: host).
+        ``stream``: a ``torch.cuda.Stream`` the planes are ordered after (default: the current stream)."""
+        import torch
+        n, names, pos, ref, num, status = self._args(contigs, positions)
+        dev = torch.device("cuda", self.device)
+        reads, qual, strand = (torch.empty((n, self.max_reads, self.window), dtype=torch.uint8, device=dev) for _ in range(3))
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        t = lambda x: C.c_void_p(x.data_ptr() if x.numel() else None)   # noqa: E731
+        self._check(self.lib.pg_encode_device(self._h, C.cast(names, C.c_void_p), p(pos), n, t(reads), t(qual), t(strand),
+                                              p(ref), p(num), p(status), C.c_void_p(s.cuda_stream)), "pg_encode_device")
+        return reads, qual, strand, ref, num, status
+
+    def close(self):
+        if self._h is not None:
+            self.lib.pg_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
