@@ -9,8 +9,9 @@
 // pileup rules: qpos / is_del / is_refskip / merged indel lengths) and FASTA + .fai access.  A location the read-by-read form
 // declines (two reads sharing a name:sequence key, a reference skip, a base outside the token table, > 1000 columns, > 8000
 // reads) is reported back as status 2 and takes the Python column-by-column path: results are byte-identical to the Python
-// module by construction (tests/test_pileup_native.py).  Worker threads take contiguous runs of locations, each with its
-// own file handles and window.
+// module by construction (tests/test_pileup_native.py).  Status 2 as well, with a ValueError on the Python side: a read inside
+// the window whose alignment has no reference position (0M 5I) or whose SEQ is shorter than its CIGAR's query length (SEQ '*');
+// tests/test_pileup_edges.py.  Worker threads take contiguous runs of locations, each with its own file handles and window.
 #include "../../include/dl4vc_loader.h"
 #include "bam_native.h"
 #include "fasta_native.h"
@@ -63,7 +64,7 @@ struct Rec {
     std::vector<uint32_t> cigar;                                 // (len << 4) | op
     std::vector<uint8_t> qual;
     // resolved against the reference (pileup.py::ReadTrack), filled on first use
-    bool resolved = false, has_ref = false;
+    bool resolved = false, has_ref = false, short_seq = false;     // short_seq: the CIGAR implies query bases SEQ lacks
     int32_t start = 0, end = 0;
     std::vector<int32_t> qpos, indel;
     std::vector<uint8_t> is_del, is_skip;
@@ -76,6 +77,9 @@ struct Rec {
         has_ref = false;
         for (uint32_t c : cigar) if (is_refop(c & 0xf)) has_ref = true;
         start = pos; end = pos + n;
+        int64_t nq = 0;
+        for (uint32_t c : cigar) { const int op = c & 0xf; if (is_aligned(op) || op == CINS || op == CSOFT_CLIP) nq += (int64_t)(c >> 4); }
+        short_seq = nq > (int64_t)seq.size();
         qpos.assign(n, 0); indel.assign(n, 0); is_del.assign(n, 0); is_skip.assign(n, 0);
         int x = 0, y = 0;
         const int nc = (int)cigar.size();
@@ -261,7 +265,12 @@ int encode_one(const pe_options& opt, Window& win, Bam& bam, Fasta& fasta, const
         r.resolve();
         if (!r.has_ref) continue;
         ++n_resolved;
-        if (r.end > s0 && r.start < stop) tracks.push_back(&r);
+        if (r.end > s0 && r.start < stop) {
+            // A track with no reference position (0M 5I: has_ref, end == start) has no first base to draw, and one whose SEQ
+            // is shorter than its CIGAR's query length (SEQ '*') has no bases: neither has an answer in the specification.
+            if (r.end <= r.start || r.short_seq) return 2;
+            tracks.push_back(&r);
+        }
     }
     if (n_resolved > 8000) return 2;
     {

@@ -143,7 +143,7 @@ int get_tid(const bamn::BamFile& b, const std::string& name) {
     return it == b.tid_of.end() ? -1 : it->second;
 }
 
-struct Cigar { int64_t nref = 0; bool has_ref = false, skip = false; };
+struct Cigar { int64_t nref = 0, nquery = 0; bool has_ref = false, skip = false; };
 // nullptr, or why the record's reference span cannot be trusted (it sizes the device's resolution arrays)
 const char* walk_cigar(const uint8_t* b, const bamn::RecordFrame& fr, Cigar& c) {
     c = Cigar{};
@@ -152,6 +152,7 @@ const char* walk_cigar(const uint8_t* b, const bamn::RecordFrame& fr, Cigar& c) 
         memcpy(&v, b + fr.cigar_off + 4 * i, 4);
         const int op = v & 0xf;
         if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) { c.nref += (int64_t)(v >> 4); c.has_ref = true; }
+        if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) c.nquery += (int64_t)(v >> 4);
         if (op == 3) c.skip = true;
     }
     if (c.nref > MAX_NREF || (int64_t)fr.pos + c.nref > INT32_MAX) return "corrupt BAM record (CIGAR reference length)";
@@ -229,7 +230,7 @@ void fetch_run(pg_encoder* h, bamn::BamFile& bam, fastan::Fasta& fasta, std::vec
         m.cigar_off = fr.cigar_off; m.seq_off = fr.seq_off; m.qual_off = fr.qual_off;
         m.n_cig = fr.n_cig; m.l_name = fr.l_name;
         m.bits = ((fr.flag & FLAG_MASK) ? 0 : pg::R_FLAG_OK) | (c.has_ref ? pg::R_HAS_REF : 0) | (c.skip ? pg::R_SKIP : 0) |
-                 ((fr.flag & FREVERSE) ? pg::R_REVERSE : 0);
+                 ((fr.flag & FREVERSE) ? pg::R_REVERSE : 0) | (c.nquery > (int64_t)fr.l_seq ? pg::R_SHORT_SEQ : 0);
         run.nres += c.nref;
         run.max_nref = std::max(run.max_nref, c.nref);
         run.recs.push_back(m);

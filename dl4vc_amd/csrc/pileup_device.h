@@ -14,9 +14,10 @@ constexpr int MAX_POS = 2 * MAX_WINDOW + 5;  // reference positions of one locat
 constexpr int HASH_SLOTS = 2 * MAX_TRACKS;   // LDS open-addressing table of name:sequence hashes
 constexpr uint8_t REF_UNKNOWN = 0xff;        // a reference base outside the token table
 
-enum : uint32_t { R_FLAG_OK = 1, R_HAS_REF = 2, R_SKIP = 4, R_REVERSE = 8, R_EQ = 16 };
+enum : uint32_t { R_FLAG_OK = 1, R_HAS_REF = 2, R_SKIP = 4, R_REVERSE = 8, R_EQ = 16, R_SHORT_SEQ = 32 };
 
-// One framed record of a batch (the host fills all but hash and R_EQ, which the resolve kernel adds).
+// One framed record of a batch (the host fills all but hash and R_EQ, which the resolve kernel adds;
+// R_SHORT_SEQ: SEQ holds fewer bases than the CIGAR's query length, e.g. SEQ '*').
 struct Rec {
     uint64_t off;          // first byte of the record (after block_size) in the batch buffer
     uint64_t hash;         // FNV-1a 64 of name ':' sequence, never 0

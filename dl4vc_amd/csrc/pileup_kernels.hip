@@ -191,7 +191,7 @@ __global__ void __launch_bounds__(BLOCK) encode_locations(
             if (m.bits & R_FLAG_OK) {
                 if (m.end > m.pos && m.pos < L.stop && m.end > L.s0) {
                     sel = 1;
-                    if (m.bits & (R_SKIP | R_EQ)) s_decline = 1;
+                    if (m.bits & (R_SKIP | R_EQ | R_SHORT_SEQ)) s_decline = 1;
                 } else if ((m.bits & R_HAS_REF) && m.end == m.pos && m.pos >= L.s0 && m.pos < L.stop) {
                     s_decline = 1;                                     // a zero-length alignment inside the window
                 }

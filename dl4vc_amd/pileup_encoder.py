@@ -35,6 +35,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .bamio import _CONSUMES_QUERY
 from .hdf5_schema import record_dtype
 
 # token tables (tools/convert_bam_single_reads.py:38-56)
@@ -206,10 +207,21 @@ def process_tracks(tracks, s0: int, stop: int, center_position: int, opt: Encode
     """``process_columns`` for the common case, one read at a time: same result, ~10x faster.  Returns ``NotImplemented`` when
     the location needs the column-by-column path -- two reads sharing a ``name:sequence`` key (they share and swap image
     rows in the reference), a reference skip, a base outside the token table, more than 1000 columns, a depth beyond
-    pysam's cap or ``--min-base-quality`` -- so those keep the reference's exact column order of operations."""
+    pysam's cap or ``--min-base-quality`` -- so those keep the reference's exact column order of operations.  Raises
+    ``ValueError`` (naming the read) for a track the specification has no answer for: a zero-length alignment inside the
+    window (``0M 5I``) or a SEQ shorter than the CIGAR's query length (SEQ ``*``)."""
     if opt.min_base_quality > 0 or len(tracks) > 8000:
         return NotImplemented
     tracks = [t for t in tracks if t.end > s0 and t.start < stop]
+    for t in tracks:
+        # neither has an answer in the specification (pe_encode and the GPU encoder decline them, status 2)
+        if t.end <= t.start:
+            raise ValueError("read %r at %d: zero-length alignment (CIGAR %s) inside the window of position %d"
+                             % (t.rec.name, t.start + 1, t.rec.cigar_string(), center_position))
+        n_query = sum(l for op, l in t.rec.cigar if _CONSUMES_QUERY[op])
+        if n_query > len(t.rec.seq):
+            raise ValueError("read %r at %d: SEQ holds %d bases, its CIGAR %s needs %d (SEQ '*'?)"
+                             % (t.rec.name, t.start + 1, len(t.rec.seq), t.rec.cigar_string(), n_query))
     keys = {t.key for t in tracks}
     if len(keys) != len(tracks):
         return NotImplemented
@@ -418,7 +430,11 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
 
     ``device="gpu"`` (default None: the host encoders above): the planes come from the GPU encoder (libdl4vc_pileup.so on HIP device ``device_id``) first; what it
     declines goes to ``pe_encode``, and what that declines to the Python encoder -- the same bytes and error count as
-    ``native=True`` (tests/test_pileup_gpu.py).  A missing libdl4vc_pileup.so is an error, not a fall-back."""
+    ``native=True`` (tests/test_pileup_gpu.py).  A missing libdl4vc_pileup.so is an error, not a fall-back.
+
+    Raises ``ValueError`` naming the read where a location's window holds a read the specification has no answer for (a
+    zero-length alignment such as ``0M 5I``, a SEQ shorter than the CIGAR's query length such as SEQ ``*``): the native and
+    GPU encoders decline such a location, so all three paths end here (tests/test_pileup_edges.py)."""
     from .bamio import BamFile, FastaFile, WindowReader
     from . import loader
     if device not in (None, "gpu"):

@@ -57,7 +57,9 @@ int dl_allele_masks(const char* vcfrec, const uint8_t* window /*[201]*/, uint8_t
  * text the caller already has.  status: 1 = planes written, 0 = the location yields no record (no read over the candidate's
  * column; the reference counts an error), 2 = the location needs the column-by-column form (reads sharing a name:sequence
  * key, a reference skip, a base outside the token table, > 1000 columns, > 8000 reads, min_base_quality > 0): the Python
- * module encodes those, so results are identical to dl4vc_amd/pileup_encoder.py for every location.  `threads` workers take
+ * module encodes those, so results are identical to dl4vc_amd/pileup_encoder.py for every location.  Also 2, because the
+ * specification has no answer: a read inside the window whose alignment has no reference position (0M 5I) or whose SEQ
+ * is shorter than its CIGAR's query length (SEQ '*'); the Python module raises ValueError there.  `threads` workers take
  * contiguous runs of locations (locations sorted by position keep every alignment parsed once per run). */
 typedef struct pe_encoder pe_encoder_t;
 typedef struct pe_options {

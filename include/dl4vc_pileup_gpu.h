@@ -11,8 +11,10 @@
  *   status 1: reads / qual / strand / ref / num_reads are byte-identical to what pe_encode writes;
  *   status 0: no record -- only where pe_encode also gives 0;
  *   status 2: declined -- the caller hands the location to pe_encode (and what that declines to the Python encoder).
- * Declined: two tracks with the same name:sequence hash, a reference skip or an '=' base in a track, a zero-length
- * alignment inside the window, a base of the reference outside the token table, more than PG_MAX_TRACKS tracks,
+ * Declined: two tracks with the same name:sequence hash, a reference skip or an '=' base in a track, a track whose SEQ
+ * holds fewer bases than its CIGAR's query length (SEQ '*'), a zero-length alignment inside the window (a read such as
+ * 0M 5I: a reference-consuming operation, no reference position; pe_encode declines it too, and the Python builder raises
+ * ValueError), a base of the reference outside the token table, more than PG_MAX_TRACKS tracks,
  * window_size > PG_MAX_WINDOW, min_base_quality > 0, a contig missing from the FASTA, a position below 1, a BAM that is not
  * coordinate-sorted within a run.  A record whose CIGAR spans more than 2^29 reference bases is a corrupt-BAM error.
  *

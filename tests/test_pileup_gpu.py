@@ -2,7 +2,8 @@
 
 The contract: the GPU's status is ``pe_encode``'s status or 2 (declined), never 1 or 0 where ``pe_encode`` says otherwise, and
 every status-1 record is byte-equal to ``pe_encode``'s.  ``encode_locations(device="gpu")`` (GPU, then ``pe_encode`` for what
-the GPU declines, then the Python encoder for what that declines) gives the bytes and error count of ``native=True``."""
+the GPU declines, then the Python encoder for what that declines) gives the bytes and error count of ``native=True``.  A decline
+needs a reason: every status 2 must be one ``tests/pileup_cases.py::expected_decline`` explains from the records themselves."""
 import dataclasses
 import os
 import subprocess
@@ -15,6 +16,7 @@ from dl4vc_amd import bamio, loader, pileup_gpu
 from dl4vc_amd import pileup_encoder as PE
 from oracle.gen_golden_pileup import simulate_reads
 from tests.candidates_fixture import load, write_bam
+from tests.pileup_cases import Pileup, expected_decline
 from tests.test_pileup_native import _big_case, write_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,14 +29,19 @@ def _both(bam, fa, contigs, pos, w=100, mr=200, mil=10, milv=50, mbq=0):
         want = e.encode(contigs, pos, 1)
     with pileup_gpu.GpuPileupEncoder(bam, fa, w, mr, mil, milv, mbq) as g:
         got = g.encode(contigs, pos)
-    return want, got
+    pile = Pileup.of_files(bam, fa)
+    why = [expected_decline(pile, c, int(p), w, mbq) if s == 2 else None for c, p, s in zip(contigs, pos, got[5])]
+    return want, got, why
 
 
-def _agree(want, got):
-    """The contract, location by location -> (locations the GPU encoded, locations pe_encode encoded)."""
+def _agree(want, got, why):
+    """The contract, location by location -> (locations the GPU encoded, locations pe_encode encoded).  ``why[i]``: the decline
+    reasons that hold at a location the GPU gave status 2."""
     ws, gs = want[5], got[5]
     bad = np.flatnonzero((gs != ws) & (gs != 2))
     assert len(bad) == 0, [(int(i), int(ws[i]), int(gs[i])) for i in bad[:10]]
+    unexplained = [int(i) for i in np.flatnonzero(gs == 2) if not why[i]]
+    assert not unexplained, ("declined without a reason", unexplained[:10])
     one = np.flatnonzero(gs == 1)
     for k, name in enumerate(FIELDS):
         diff = [int(i) for i in one if not np.array_equal(got[k][i], want[k][i])]
@@ -51,8 +58,8 @@ def test_simulated_pileups(tmp_path):
         dup = seed % 10 == 9
         ref, center, reads = simulate_reads(100 + seed, w, [8, 40, 90, 300][seed % 4], duplicate_ids=dup)
         bam, fa = write_inputs(tmp_path, ref, reads, tag="s%d" % seed, index=seed % 2 == 0)
-        want, got = _both(bam, fa, ["ref"], [center], w, 200, [10, 3, 0][seed % 3], [50, 5, 0][seed % 3])
-        g, c = _agree(want, got)
+        want, got, why = _both(bam, fa, ["ref"], [center], w, 200, [10, 3, 0][seed % 3], [50, 5, 0][seed % 3])
+        g, c = _agree(want, got, why)
         if not dup:
             gpu, cpu = gpu + g, cpu + c
     assert cpu >= 20 and gpu >= 0.9 * cpu, (gpu, cpu)
@@ -70,8 +77,8 @@ def test_runs_sorted_shuffled_missing_contig_and_past_the_data(tmp_path, index):
     contigs = ["chr20"] * (len(pos) - 1) + ["chrX"]
     for order in (np.arange(len(pos)), rng.permutation(len(pos))):
         c, p = [contigs[i] for i in order], [pos[i] for i in order]
-        want, got = _both(bam, fa, c, p)
-        g, n = _agree(want, got)
+        want, got, why = _both(bam, fa, c, p)
+        g, n = _agree(want, got, why)
         assert n >= 140 and g >= 0.9 * n, (g, n)
         assert got[5][int(np.flatnonzero(order == len(pos) - 1)[0])] == 0       # chrX
         assert got[5][int(np.flatnonzero(order == len(pos) - 2)[0])] == 0       # past the data
@@ -81,8 +88,8 @@ def test_runs_sorted_shuffled_missing_contig_and_past_the_data(tmp_path, index):
 def test_windows_and_depth_above_max_reads(tmp_path, w, mr):
     bam, fa, ref = _big_case(tmp_path, n_reads=2400, length=6000, seed=3)        # ~50x
     pos = list(range(200, 5800, 37))
-    want, got = _both(bam, fa, ["chr20"] * len(pos), pos, w, mr)
-    g, n = _agree(want, got)
+    want, got, why = _both(bam, fa, ["chr20"] * len(pos), pos, w, mr)
+    g, n = _agree(want, got, why)
     assert n >= 0.8 * len(pos) and g >= 0.9 * n, (g, n)
     if mr < 50:
         assert (got[4][got[5] == 1] == mr).any()                                 # deep sites keep their middle rows
@@ -95,8 +102,8 @@ def test_duplicate_secondary_unmapped_and_qc_fail_reads(tmp_path):
     reads = [dataclasses.replace(r, flag=r.flag | int(rng.choice(flags))) for r in reads]
     bam, fa = write_inputs(tmp_path, ref, reads, tag="flags")
     pos = list(range(center - 60, center + 61, 3))
-    want, got = _both(bam, fa, ["ref"] * len(pos), pos)
-    g, n = _agree(want, got)
+    want, got, why = _both(bam, fa, ["ref"] * len(pos), pos)
+    g, n = _agree(want, got, why)
     assert n >= 20 and g >= 0.9 * n, (g, n)
 
 
@@ -112,8 +119,8 @@ def test_candidates_fixture_bam(tmp_path):
             f.write(">%s\n%s\n" % (name, "\n".join(s[i:i + 60] for i in range(0, length, 60))))
     lines = [run for run in fx["runs"] if run["name"] == "cli"][0]["lines"]
     contigs, pos = [l.split("\t")[0] for l in lines], [int(l.split("\t")[1]) for l in lines]
-    want, got = _both(bam, fa, contigs, pos)
-    g, n = _agree(want, got)
+    want, got, why = _both(bam, fa, contigs, pos)
+    g, n = _agree(want, got, why)
     assert n >= 0.8 * len(pos) and g >= 0.9 * n, (g, n)
 
 
