@@ -21,6 +21,7 @@ ABI_VERSION = 6
 # every symbol include/dl4vc_dan.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = ("dan_abi_version", "dan_source_hash", "dan_create", "dan_set_tensor", "dan_finalize", "dan_destroy", "dan_last_error",
            "dan_forward", "dan_forward_aux", "dan_forward_device", "dan_forward_async", "dan_wait", "dan_set_tap", "dan_read_buffer", "dan_query",
+           "dan_set_pool_form",
            "dan_profile_enable", "dan_kernel_stats")
 
 
@@ -68,6 +69,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.dan_read_buffer.restype = C.c_int64
     lib.dan_query.argtypes = [vp, C.c_char_p]
     lib.dan_query.restype = C.c_int64
+    if hasattr(lib, "dan_set_pool_form"):        # (a library built before the entry point existed can still be loaded for A/B runs)
+        lib.dan_set_pool_form.argtypes = [vp, C.c_int32]
     lib.dan_profile_enable.argtypes = [vp, C.c_int32]
     lib.dan_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     if lib.dan_abi_version() != ABI_VERSION:
@@ -227,6 +230,10 @@ class DanHandle:
     # ---- debug taps / profiling ---------------------------------------------------------------
     def set_tap(self, layer: int) -> None:
         self._check(self.lib.dan_set_tap(self._h, layer), "dan_set_tap")
+
+    def set_pool_form(self, form: int) -> None:
+        """0 = automatic, 1 = read-axis pooling in separate kernels, 2 = inside the segment kernel (``query("pool_form")``)."""
+        self._check(self.lib.dan_set_pool_form(self._h, form), "dan_set_pool_form")
 
     def read_buffer(self, name: str, n_floats: int) -> np.ndarray:
         dst = np.empty(int(n_floats), np.float32)

@@ -69,6 +69,11 @@ struct dan_handle {
     int* d_rowsrc = nullptr;                 // empty-row map of the current chunk (skip_empty_rows)
     int *d_work = nullptr, *d_work_count = nullptr;   // ... and the list of rows to compute
     int n_cus = 0;
+    // read-axis pooling inside the segment kernel (dan_kernels.h SegmentArgs::fold; dan_set_pool_form)
+    const char* fold_why_not = nullptr;      // why the in-segment form does not apply to this handle (null: it does)
+    int pool_form = 0;                       // 0 = per chunk by its site count, 1 = separate tail kernels, 2 = in-segment
+    int last_pool_form = 1;                  // the form the last chunk ran (before the first: the one a full chunk would)
+    float* d_fold = nullptr;                 // [workgroup][2][L][CPAD] running planes of the site-owning workgroups
     float *d_wc = nullptr, *d_bc = nullptr;
     float *d_feat = nullptr, *d_hid0 = nullptr, *d_hid1 = nullptr;
     float* d_fc_ws = nullptr;                                  // split-k partial sums of FC1 [2][max_batch][fc0]
@@ -337,6 +342,11 @@ int dan_create(const dan_config* cfg, dan_t** out) {
     dan_handle* h = new dan_handle();
     h->cfg = c;
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device_id) == hipSuccess) h->n_cus = cus; }
+    h->fold_why_not = c.precision != 0 ? "the in-segment pooling form exists for precision 0 only"
+                    : c.length > MPOS ? "the in-segment pooling form needs one unit per read (windows up to 208 columns)"
+                    : c.skip_empty_rows ? "the in-segment pooling form computes every row: not with skip_empty_rows"
+                    : h->n_cus < 8 ? "the in-segment pooling form needs at least 8 compute units" : nullptr;
+    h->last_pool_form = h->fold_why_not ? 1 : 2;
     h->max_batch = c.max_batch > 0 ? c.max_batch : 4096;
     if (c.chunk_sites > 0) {
         h->chunk = c.chunk_sites;
@@ -673,6 +683,7 @@ int dan_finalize(dan_t* h) {
     if ((rc = dev_alloc(h, &h->d_y, (size_t)h->chunk * R * read_floats / act_div))) return rc;
     if (h->split && (rc = dev_alloc(h, &h->d_y2, (size_t)h->chunk * R * read_floats))) return rc;
     if ((rc = dev_alloc(h, &h->d_pool, (size_t)h->chunk * read_floats))) return rc;
+    if (!h->fold_why_not && (rc = dev_alloc(h, &h->d_fold, (size_t)(h->n_cus & ~7) * 2 * read_floats))) return rc;
     if (conv_pool && h->n_segments > 1) {
         if ((rc = dev_alloc(h, &h->d_cp, (size_t)h->chunk * read_floats))) return rc;
         if ((rc = dev_alloc(h, &h->d_cols, (size_t)h->chunk * L * 3 * CPAD))) return rc;
@@ -722,6 +733,17 @@ void dan_destroy(dan_t* h) {
 // stream of its own) and hands back the event the compute stream waits for.  The asynchronous host path uploads a macro-batch
 // chunk by chunk THROUGH this: chunk k's launches are queued before the host touches chunk k + 1, so the forward of chunk 0 starts
 // after one chunk's staging and the staging of chunk k + 1 runs under chunk k's kernels.
+// The in-segment pooling form gives a workgroup whole sites, so a chunk that does not deal evenly leaves compute units idle at
+// its end: with W workgroups in 8 XCD slices the chunk takes ceil(ceil(ns / 8) / (W / 8)) site-times where the row form takes
+// ns / W.  It is chosen when that loss is smaller than what the fold saves (FOLD_GAIN: measured, HISTORY.md).
+static constexpr double FOLD_GAIN = 0.013;
+static bool fold_deals_evenly(int ns, int n_cus) {
+    const int W = n_cus & ~7;
+    if (W < 8 || ns <= 0) return false;
+    const int per = (ns + 7) / 8, rounds = (per + W / 8 - 1) / (W / 8);
+    return (double)rounds * W / ns - 1.0 < FOLD_GAIN;
+}
+
 struct ChunkFeed {
     int (*fn)(void* ctx, int64_t first_site, int n_sites, int64_t k, hipEvent_t* ready);
     void* ctx;
@@ -766,6 +788,8 @@ static int forward_device_impl(dan_t* h, const uint8_t* reads, const uint8_t* qu
                 launch_row_map(reads + g0 * rl, qual + g0 * rl, strand + g0 * rl, h->d_rowsrc, h->d_work, h->d_work_count, ns, R, L, s);
                 rcm = prof_end(h, "row_map", s, &evm); if (rcm) return rcm;
             }
+            const bool fold = !h->fold_why_not && (h->pool_form == 2 || (h->pool_form == 0 && fold_deals_evenly(ns, h->n_cus)));
+            float* const feat = h->d_feat + (size_t)c0 * h->F_stride;
             float* y_seg = h->d_y;                           // where the segment just launched left its output
             for (int sg = 0; sg < h->n_segments; ++sg) {
                 SegmentArgs a{};
@@ -793,6 +817,11 @@ static int forward_device_impl(dan_t* h, const uint8_t* reads, const uint8_t* qu
                 a.wino = h->wino;
                 a.l0_tab = h->d_l0tab;
                 a.work = h->d_work; a.work_count = h->d_rowsrc ? h->d_work_count : nullptr;
+                if (fold) {
+                    a.fold = 1; a.fold_scratch = h->d_fold;
+                    if (sg + 1 < h->n_segments) a.fold_pool = h->d_pool;
+                    else { a.fold_feat = feat; a.fold_feat_stride = h->F_stride; a.fold_C = c.c_final; }
+                }
                 EventPair ev{};
                 int rc = prof_begin(h, "conv_segment", s, &ev); if (rc) return rc;
                 if (c.precision == 0) {
@@ -820,7 +849,9 @@ static int forward_device_impl(dan_t* h, const uint8_t* reads, const uint8_t* qu
                     launch_segmentp(b, ns, h->n_cus, s);
                 }
                 rc = prof_end(h, "conv_segment", s, &ev); if (rc) return rc;
-                if (sg + 1 < h->n_segments) {
+                if (fold) {
+                    HIPCHK(h, hipGetLastError());
+                } else if (sg + 1 < h->n_segments) {
                     rc = prof_begin(h, "pool", s, &ev); if (rc) return rc;
                     if (h->use_p || h->use_x) {
                         if (h->use_x) launch_read_meanx((const uint16_t*)y_seg, h->d_pool, ns, R, L, h->d_rowsrc, s);
@@ -833,14 +864,16 @@ static int forward_device_impl(dan_t* h, const uint8_t* reads, const uint8_t* qu
                     HIPCHK(h, hipGetLastError());            // a refused launch must not let garbage flow on to the FC
                 }
             }
-            float* feat = h->d_feat + (size_t)c0 * h->F_stride;
             EventPair ev{};
-            int rc = prof_begin(h, "pool", s, &ev); if (rc) return rc;
-            if (h->use_x) launch_final_poolx((const uint16_t*)y_seg, feat, h->F_stride, ns, R, L, c.c_final, h->d_rowsrc, s);
-            else if (h->use_p) launch_final_pool16((const uint16_t*)h->d_y, feat, h->F_stride, ns, R, L, c.c_final, h->d_rowsrc, s);
-            else launch_final_pool(y_seg, feat, h->F_stride, ns, R, L, c.c_final, h->d_rowsrc, s);
-            rc = prof_end(h, "pool", s, &ev); if (rc) return rc;
-            HIPCHK(h, hipGetLastError());
+            int rc = DAN_OK;
+            if (!fold) {                                     // (in-segment form: the last segment has written the pooled blocks)
+                rc = prof_begin(h, "pool", s, &ev); if (rc) return rc;
+                if (h->use_x) launch_final_poolx((const uint16_t*)y_seg, feat, h->F_stride, ns, R, L, c.c_final, h->d_rowsrc, s);
+                else if (h->use_p) launch_final_pool16((const uint16_t*)h->d_y, feat, h->F_stride, ns, R, L, c.c_final, h->d_rowsrc, s);
+                else launch_final_pool(y_seg, feat, h->F_stride, ns, R, L, c.c_final, h->d_rowsrc, s);
+                rc = prof_end(h, "pool", s, &ev); if (rc) return rc;
+                HIPCHK(h, hipGetLastError());
+            }
             if (H > 0) {
                 rc = prof_begin(h, "highway", s, &ev); if (rc) return rc;
                 if (h->use_p)
@@ -852,6 +885,7 @@ static int forward_device_impl(dan_t* h, const uint8_t* reads, const uint8_t* qu
                 rc = prof_end(h, "highway", s, &ev); if (rc) return rc;
             }
             h->last_chunk_sites = ns;
+            h->last_pool_form = fold ? 2 : 1;
         }
         EventPair ev{};
         int rc = prof_begin(h, "fc", s, &ev); if (rc) return rc;
@@ -1062,6 +1096,15 @@ int dan_set_tap(dan_t* h, int32_t layer) {
     return DAN_OK;
 }
 
+int dan_set_pool_form(dan_t* h, int32_t form) {
+    if (!h) return DAN_ERR_INVALID_ARG;
+    if (form < 0 || form > 2) return fail(h, DAN_ERR_INVALID_ARG, "pool form %d: 0 = automatic, 1 = separate kernels, 2 = in-segment", form);
+    if (form == 2 && h->fold_why_not) return fail(h, DAN_ERR_INVALID_ARG, "pool form 2 refused: %s", h->fold_why_not);
+    h->pool_form = form;
+    h->last_pool_form = (form == 1 || h->fold_why_not) ? 1 : 2;
+    return DAN_OK;
+}
+
 int64_t dan_query(const dan_t* h, const char* what) {
     if (!h || !what) return DAN_ERR_INVALID_ARG;
     const std::string w(what);
@@ -1076,6 +1119,7 @@ int64_t dan_query(const dan_t* h, const char* what) {
     if (w == "bf16_pingpong") return h->use_p ? 1 : 0;
     if (w == "bf16x3_split_kernel") return h->use_x ? 1 : 0;
     if (w == "hidden0_stride") return h->n0_stride;
+    if (w == "pool_form") return h->last_pool_form;
     return fail(h, DAN_ERR_INVALID_ARG, "dan_query: unknown key '%s'", what);
 }
 

@@ -81,6 +81,18 @@ struct SegmentArgs {
     int units, Lw;
     int u_off[2], u_len[2], own_lo[2], own_hi[2];
     float* y_out;
+    // ---- fold = 1: the site-owning form (segment_kernel FOLD; one unit per read, work_count null): the reductions over the read
+    // axis happen inside the segment kernel.  fold_scratch: [workgroup][2][L][CPAD] running planes (segment_fold_workgroups of
+    // them).  A segment that feeds another writes fold_pool [site][L][CPAD] (what launch_read_mean writes) and y as ever; the
+    // network's last segment has fold_feat set and writes the two pooled blocks of the feature rows (what launch_final_pool
+    // writes: fold_feat_stride floats between sites, fold_C channels) and no y.
+    int fold;
+    int n_sites, xcd_sites;      // filled by launch_segment
+    float* fold_scratch;
+    float* fold_pool;
+    float* fold_feat;
+    long long fold_feat_stride;
+    int fold_C;
 };
 
 // Windows above MPOS columns: two units per read (see SegmentArgs; SegmentXArgs carries the same fields).  halo = the segment's
@@ -125,6 +137,8 @@ inline bool plan_units(Args& a, int Lw, int halo) {
 
 // max_wgs: workgroups to launch (one per CU: they are persistent and walk the rows with the grid's stride); 0 = one per row
 void launch_segment(const SegmentArgs& a, int n_sites, int max_wgs, hipStream_t s);
+// workgroups the site-owning form launches for a chunk (<= max_wgs rounded down to whole XCD rounds; fold_scratch holds as many planes)
+int segment_fold_workgroups(int n_sites, int max_wgs);
 
 // ---- bf16 "ping-pong" kernel (dan_kernels_bf16p.hip): plain bf16, v_mfma_f32_32x32x16_bf16, two XOR-swizzled LDS images
 // (layer input / layer output), bf16 activations in HBM (y, h), persistent workgroups.  BASELINE config 5 (128 x 301).

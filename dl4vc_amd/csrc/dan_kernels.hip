@@ -87,15 +87,23 @@ __device__ __forceinline__ void gemm1x1_wino(v4f (&acc)[TW][2], const float* xro
 // CU walking the device-side list of rows to do with the grid's stride -- used with empty-row skipping, where dispatching
 // a workgroup per row only to have a quarter of them exit costs the command processor ~0.26 us each, serialised.  The row
 // loop costs registers (what is live across rows), so that form re-reads its arguments per row and does without the
-// cross-layer weight prefetch; it is ~1 % slower per computed row.
+// cross-layer weight prefetch; with every row computed at 64 x 201 it is 0.26 ms per launch of layers 3-7 slower (110.38 -> 110.64)
+// and no slower on layers 1-2 (HISTORY.md section 15).
 // SPLIT = true: windows of 209..304 columns, every read as two overlapping units (SegmentArgs::units == 2, plan_units): a work
 // item is (row, unit), `L` below is the UNIT's length and every position-indexed pointer is offset to the unit's first column;
 // what differs from the one-unit form is addressing (window stride Lw), the allele-agreement predicates (taken over the whole
 // window, not the unit) and the stores (own columns only, y out of place).  SPLIT = false compiles to the code it always was.
 // TW: Winograd tiles per lane -- MW = 7 (one unit of up to 208 columns) or, SPLIT, MW_SHORT = 6 (units of up to 190 columns: every
 // unit of a split Winograd read, e.g. 161 columns at a 301-column window; launch_segment).
-template <bool WINO, bool PERSIST, bool SPLIT, int TW = MW>
+// FOLD = true (with PERSIST, one unit per read, every row computed): the workgroup owns WHOLE SITES -- site s, rows 0 .. R-1 in
+// order, then its next site -- and forms the reductions over the read axis itself: after a row's last layer it adds the LDS
+// image to its own running planes in device memory (SegmentArgs::fold_scratch: sum, and max for the network's last segment;
+// fetched under the row's bottleneck GEMM, a thread only ever re-reads what it stored itself) and after the site's last row it
+// writes what read_mean_kernel / final_pool_kernel would have written, from the same operations in the same order.  The last
+// segment then writes no y at all.  No atomics and no hand-off between workgroups: the bits do not depend on the grid.
+template <bool WINO, bool PERSIST, bool SPLIT, int TW = MW, bool FOLD = false>
 __global__ __launch_bounds__(SEG_THREADS, NWAVE / 4) void segment_kernel(SegmentArgs a_by_value) {
+    static_assert(!FOLD || (PERSIST && !SPLIT), "the site-owning form is a persistent one-unit form");
     static_assert((!(SPLIT && WINO) && TW == MW) || (SPLIT && WINO && TW == MW_SHORT), "six tiles per lane: the split Winograd kernel, and only it");
     constexpr int TILES = TW == MW ? MT : (MPOS_SHORT + 15) / 16;           // 16-column tiles of the unit (bottleneck, table walk)
     // one allocation, so that the layout the Winograd tiles past the window rely on (constants right after the activation
@@ -107,15 +115,17 @@ __global__ __launch_bounds__(SEG_THREADS, NWAVE / 4) void segment_kernel(Segment
     // (the row body sits at function scope with an explicit back edge: wrapped in a lambda, or in a for loop left by a
     // compile-time break, the same code costs the non-persistent form 56 spilled registers)
     constexpr int UNITS = SPLIT ? 2 : 1;
-    const int n_work = (a_by_value.work_count ? *a_by_value.work_count : a_by_value.n_rows) * UNITS;
+    // (FOLD: a work item is a SITE, dealt exactly as the rows are; fold_r is the row inside it)
+    const int n_work = FOLD ? a_by_value.n_sites : (a_by_value.work_count ? *a_by_value.work_count : a_by_value.n_rows) * UNITS;
     // XCD-aware order: workgroups b and b + 8 share an XCD (round-robin dealing), so the rows are cut into 8 contiguous
     // slices of `per` rows and workgroup b takes row (b % 8) * per + b / 8 (+ a multiple of the grid's eighth when
     // persistent): the 64 reads of a site, which all read that site's pool image and the same weights, stay in one L2.
-    const int per = a_by_value.work_count ? (n_work + 7) >> 3 : a_by_value.xcd_rows * UNITS;
+    const int per = FOLD ? a_by_value.xcd_sites : a_by_value.work_count ? (n_work + 7) >> 3 : a_by_value.xcd_rows * UNITS;
     const int xcd = blockIdx.x & 7;
     int j = blockIdx.x >> 3;                                // position inside the XCD's slice
     int wk = xcd * per + j;
     if (j >= per || wk >= n_work) return;
+    [[maybe_unused]] int fold_r = 0;
 next_row:                                                   // (PERSIST only: back edge at the bottom)
     {
     // PERSIST: the arguments are re-read from the kernarg segment for every row through a pointer the compiler cannot see
@@ -138,9 +148,9 @@ next_row:                                                   // (PERSIST only: ba
     const int lane = tid & 63;                              // the row loop (it would live through every GEMM and spill)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wrow = SPLIT ? wk >> 1 : wk;
-    const int row_index = __builtin_amdgcn_readfirstlane(a.work_count ? a.work[wrow] : wrow);     // uniform: everything derived stays scalar
-    const int site = (int)((unsigned)row_index / (unsigned)a.R);
-    const int r = row_index - site * a.R;
+    const int row_index = FOLD ? wk * a.R + fold_r : __builtin_amdgcn_readfirstlane(a.work_count ? a.work[wrow] : wrow);     // uniform: everything derived stays scalar
+    const int site = FOLD ? wk : (int)((unsigned)row_index / (unsigned)a.R);
+    const int r = FOLD ? fold_r : row_index - site * a.R;
     const size_t read_idx = (size_t)site * a.R + r;
     float* yrow = a.y + (read_idx * (size_t)Lw + u_off) * CPAD;                   // this unit's first column of the segment's input
     float* yout = SPLIT ? a.y_out + (read_idx * (size_t)Lw + u_off) * CPAD : yrow;  // ... and of its output (in place unless SPLIT)
@@ -309,7 +319,8 @@ next_row:                                                   // (PERSIST only: ba
         // layer's conv stage, where the four older waves run it on the same LDS-resident input while the younger wave of
         // each SIMD is still in its conv GEMM (the arbiter serves the older wave first, so it finishes the conv early and
         // would only wait at the barrier)
-        if (a.has_hw && !(WINO && l + 1 < a.l_end))
+        // (FOLD: the segment's last bottleneck GEMM runs behind the layer loop, over the requests for the running planes)
+        if (!(FOLD && WINO) && a.has_hw && !(WINO && l + 1 < a.l_end) && !(FOLD && l + 1 == a.l_end))
             bottleneck<NWAVE, SPLIT, TILES>(xs, wbot, lc + CST_BBOT, a.h + (size_t)l * a.h_layer_stride + (read_idx * (size_t)Lw + u_off) * HPAD,
                                      own_hi, wave, lane, own_lo);
         STAMP(sb + 7);
@@ -658,15 +669,134 @@ next_row:                                                   // (PERSIST only: ba
         for (; l < a.l_end; ++l) direct_layer(l);
     }
     STAMP(62);
-    copy_out(xs, yout, own_lo, own_hi, tid);
+    if constexpr (FOLD) {
+        const bool fin = a.fold_feat != nullptr;             // the network's last segment: max and mean into the feature row, no y
+        if (!fin) copy_out(xs, yout, own_lo, own_hi, tid);
+        // this thread's elements i = tid + k * SEG_THREADS of the workgroup's running planes [L][CPAD] (sum | max): requested
+        // here, so that they arrive under the last layer's bottleneck GEMM.  Row 0 of a site starts them afresh.
+        constexpr int NF = MT * 16 * (CPAD / 4) / SEG_THREADS;
+        const int n4 = L * (CPAD / 4);
+        v4f* sp = (v4f*)(a.fold_scratch + (size_t)blockIdx.x * (2 * (size_t)n4 * 4));
+        int t = tid;
+        asm volatile("" : "+v"(t));
+        v4f fsum[NF], fmx[NF];
+        if (r > 0) {
+#pragma unroll
+            for (int k = 0; k < NF; ++k) {
+                const int i = t + k * SEG_THREADS;
+                fsum[k] = (i < n4) ? sp[i] : splat(0.f);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NF; ++k) fsum[k] = splat(0.f);
+        }
+        if (r > 0 && fin) {
+#pragma unroll
+            for (int k = 0; k < NF; ++k) {
+                const int i = t + k * SEG_THREADS;
+                fmx[k] = (i < n4) ? sp[n4 + i] : splat(0.f);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NF; ++k) fmx[k] = splat(0.f);
+        }
+        if (a.has_hw) {
+            const int ll = a.l_end - 1;
+            bottleneck<NWAVE, false, TILES>(xs, wbot, cst + (ll - a.l_begin) * CST_FLOATS + CST_BBOT,
+                                            a.h + (size_t)ll * a.h_layer_stride + read_idx * (size_t)Lw * HPAD, own_hi, wave, lane, own_lo);
+        }
+        const bool last_row = r + 1 == a.R;
+        // read_mean_kernel: sum = +0, then += rows 0 .. R-1.  final_pool_kernel: max = sum = row 0, then rows 1 .. R-1.
+#pragma unroll
+        for (int k = 0; k < NF; ++k) {
+            const int i = t + k * SEG_THREADS;
+            const v4f v = (i < n4) ? *(const v4f*)(xs + (HALO + (i >> 5)) * LDS_S + (i & 31) * 4) : splat(0.f);
+            v4f mx = v;
+            if (r > 0) {
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) mx[jj] = fmaxf(fmx[k][jj], v[jj]);
+            }
+            fmx[k] = mx;
+            v4f sum = fsum[k];
+            sum += v;
+            fsum[k] = (fin && r == 0) ? v : sum;
+        }
+        if (!last_row) {
+#pragma unroll
+            for (int k = 0; k < NF; ++k) {
+                const int i = t + k * SEG_THREADS;
+                if (i < n4) sp[i] = fsum[k];
+            }
+            if (fin) {
+#pragma unroll
+                for (int k = 0; k < NF; ++k) {
+                    const int i = t + k * SEG_THREADS;
+                    if (i < n4) sp[n4 + i] = fmx[k];
+                }
+            }
+        } else {
+            // the site's last row: the image is free, so the results go out through it in rolled loops (once per site: short
+            // code matters more than speed here) -- every thread puts its elements back where it read them
+            const float fR = (float)a.R;
+            __syncthreads();                                 // every wave has finished the bottleneck GEMM's reads of the image
+            auto put = [&](const v4f (&src)[NF]) {
+#pragma unroll
+                for (int k = 0; k < NF; ++k) {
+                    const int i = t + k * SEG_THREADS;
+                    if (i < n4) *(v4f*)(xs + (HALO + (i >> 5)) * LDS_S + (i & 31) * 4) = src[k];
+                }
+            };
+            if (!fin) {
+                put(fsum);                                   // (each thread re-reads its own elements: no barrier)
+                v4f* pl = (v4f*)(a.fold_pool + (size_t)site * n4 * 4);
+#pragma unroll 1
+                for (int i = t; i < n4; i += SEG_THREADS)
+                    pl[i] = *(const v4f*)(xs + (HALO + (i >> 5)) * LDS_S + (i & 31) * 4) / splat(fR);
+            } else {
+                // feat[site][c L + p] = max, feat[site][C L + c L + p] = mean: channel-major, max block first (model.py:833);
+                // the image carries the transpose (wave = channel, lane = position: 256-byte runs of the feature row)
+                float* row = a.fold_feat + (size_t)site * a.fold_feat_stride;
+                const int C = a.fold_C;
+                put(fmx);
+                __syncthreads();
+#pragma unroll 1
+                for (int c = wave; c < C; c += NWAVE)
+#pragma unroll 1
+                    for (int p = lane; p < L; p += 64) row[(unsigned)(c * L + p)] = xs[(HALO + p) * LDS_S + c];
+                __syncthreads();
+                put(fsum);
+                __syncthreads();
+                row += (size_t)C * L;
+#pragma unroll 1
+                for (int c = wave; c < C; c += NWAVE)
+#pragma unroll 1
+                    for (int p = lane; p < L; p += 64) row[(unsigned)(c * L + p)] = xs[(HALO + p) * LDS_S + c] / fR;
+            }
+        }
+    } else {
+        copy_out(xs, yout, own_lo, own_hi, tid);
+    }
     STAMP(63);
     }
-    if constexpr (PERSIST) {
+    if constexpr (FOLD) {
+        if (++fold_r == a_by_value.R) {
+            fold_r = 0;
+            j += gridDim.x >> 3;
+            wk = xcd * per + j;
+        }
+        __syncthreads();                                    // the next row re-uses the LDS image
+        if (j < per && wk < n_work) goto next_row;
+    } else if constexpr (PERSIST) {
         j += gridDim.x >> 3;
         wk = xcd * per + j;
         __syncthreads();                                    // the next row re-uses the LDS image
         if (j < per && wk < n_work) goto next_row;
     }
+}
+
+int segment_fold_workgroups(int n_sites, int max_wgs) {
+    const int w = max_wgs & ~7, need = 8 * ((n_sites + 7) / 8);
+    return w < need ? w : need;
 }
 
 void launch_segment(const SegmentArgs& a0, int n_sites, int max_wgs, hipStream_t s) {
@@ -676,6 +806,14 @@ void launch_segment(const SegmentArgs& a0, int n_sites, int max_wgs, hipStream_t
     const bool split = a.units == 2;
     if (!split) { a.units = 1; a.Lw = a.L; a.y_out = a.y; }   // (callers that never heard of units: one unit, the whole window, in place)
     const int units = split ? 2 : 1;
+    if (a.fold) {                                           // (callers ask for it only where it applies: dan_capi.cpp)
+        a.n_sites = n_sites;
+        a.xcd_sites = (n_sites + 7) / 8;                    // the same XCD slices of whole sites as the row forms
+        const dim3 grid((unsigned)segment_fold_workgroups(n_sites, max_wgs)), blk(SEG_THREADS);
+        if (a.wino) hipLaunchKernelGGL((segment_kernel<true, true, false, MW, true>), grid, blk, 0, s, a);
+        else hipLaunchKernelGGL((segment_kernel<false, true, false, MW, true>), grid, blk, 0, s, a);
+        return;
+    }
     const bool persist = a.work_count != nullptr && max_wgs >= 8 && max_wgs < a.n_rows * units;
     const dim3 grid((unsigned)(persist ? (max_wgs & ~7) : 8 * a.xcd_rows * units)), blk(SEG_THREADS);
     if (split) {

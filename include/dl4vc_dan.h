@@ -141,6 +141,12 @@ int dan_wait(dan_t* h, int64_t ticket);
 int dan_set_tap(dan_t* h, int32_t layer);
 int64_t dan_read_buffer(dan_t* h, const char* name, float* dst, int64_t capacity);
 int64_t dan_query(const dan_t* h, const char* what);
+/* Where the reductions over the read axis (the read-mean behind a pool layer, the final max / mean pool) are computed:
+ * 0 = chosen per chunk by its site count (default), 1 = in separate kernels behind each segment, 2 = inside the segment
+ * kernel, whose workgroups then own whole sites.  Both forms give the same bits.  Form 2 exists for precision 0, windows up
+ * to 208 columns and skip_empty_rows = 0; elsewhere it is refused with a reason and forms 0 and 1 mean the same.
+ * dan_query("pool_form") = the form (1 or 2) the last chunk ran. */
+int dan_set_pool_form(dan_t* h, int32_t form);
 
 /* Kernel timing with HIP events on the launch stream (bench.py's roofline leg).  When enabled,
  * every launch of the conv-stack segment kernel is bracketed by events; dan_kernel_stats() returns
