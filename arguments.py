@@ -70,6 +70,9 @@ _EXTRA = [
                                    "within 1e-4, ~2.3x faster) or bf16"),
     ("--compute-empty-rows", "flag", False, "compute every all-padding pileup row separately, as the reference does (default: once "
                                             "per site -- their inputs are identical, the outputs bit-identical)"),
+    ("--test_bam", "str", None, "inference straight from a coordinate-sorted BAM (with --test_fasta and --sample_vcf, the candidate "
+                                "VCF): pileups are encoded and scored on the GPU and no candidates.hdf is written; replaces --test_file"),
+    ("--test_fasta", "str", None, "reference FASTA of --test_bam"),
     ("--conv-algo", "str", "auto", "fp32 conv form: auto (Winograd F(2,3) where every layer after the first has "
                                    "dilation 2), direct, or winograd"),
 ]
@@ -95,3 +98,16 @@ def create_arg_parser() -> argparse.ArgumentParser:
         else:
             p.add_argument(name, type=_TYPES[kind], default=default, help=text)
     return p
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    """``create_arg_parser().parse_args(argv)``, except that ``--test_file`` is not required where ``--test_bam`` stands in
+    for it (the parser itself keeps the reference's ``required=True``)."""
+    import sys
+    argv = list(sys.argv[1:] if argv is None else argv)
+    p = create_arg_parser()
+    if any(a == "--test_bam" or a.startswith("--test_bam=") for a in argv):
+        for a in p._actions:
+            if a.dest == "test_file":
+                a.required = False
+    return p.parse_args(argv)

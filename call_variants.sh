@@ -7,11 +7,14 @@
 # detection and per-locus counting on the GPU (libdl4vc_cand.so), with the reference's flags; -b restricts it to a BED file
 # (the reference requires -b; here it is optional and its absence means the whole BAM).  An existing candidates.vcf is used
 # as it is.  With an OUTDIR that also holds candidates.hdf, -i / -r are not needed and the conversion is skipped.
+# -d (direct; needs -i and -r, one GPU): no candidates.hdf at all -- main.py --test_bam encodes the pileups on the GPU, assembles
+# and scores them there.  The scored VCF is byte-identical to the two-step path's.  Without -d nothing changes.
 set -e
-usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES]"; exit 1; }
+usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d]"; exit 1; }
 GPUS=1
 PROCS=16
-while getopts "m:o:g:i:r:b:p:h" opt; do
+DIRECT=0
+while getopts "m:o:g:i:r:b:p:dh" opt; do
   case $opt in
     m) MODEL=$OPTARG ;;
     o) OUTDIR=$OPTARG ;;
@@ -20,6 +23,7 @@ while getopts "m:o:g:i:r:b:p:h" opt; do
     r) REFERENCE=$OPTARG ;;
     b) BED=$OPTARG ;;       # candidate generation only
     p) PROCS=$OPTARG ;;
+    d) DIRECT=1 ;;          # score straight from the BAM (main.py --test_bam)
     *) usage ;;
   esac
 done
@@ -32,7 +36,13 @@ if [ ! -f "$OUTDIR/candidates.hdf" ] && [ ! -f "$OUTDIR/candidates.vcf" ] && [ -
       --snp_min_freq 0.075 --indel_min_freq 0.02 ${BED:+--bedfile "$BED"} --keep_multialleles \
       > "$OUTDIR/candidate_generator.log" 2>&1
 fi
-if [ ! -f "$OUTDIR/candidates.hdf" ]; then
+if [ "$DIRECT" = 1 ]; then
+  [ -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ] && [ -n "$REFERENCE" ] || { echo "-d needs -i BAM -r REFERENCE (and $OUTDIR/candidates.vcf, made from the BAM when absent)"; exit 1; }
+  TEST_INPUT=(--test_bam "$BAM" --test_fasta "$REFERENCE")
+else
+  TEST_INPUT=(--test_file "$OUTDIR/candidates.hdf")
+fi
+if [ "$DIRECT" != 1 ] && [ ! -f "$OUTDIR/candidates.hdf" ]; then
   [ -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ] && [ -n "$REFERENCE" ] || { echo "missing $OUTDIR/candidates.hdf (or candidates.vcf with -i BAM -r REFERENCE to make it)"; exit 1; }
   printf "Convert candidates to HDF...\n"
   python "$SCRIPTDIR/tools/convert_bam_single_reads.py" --input "$BAM" --fp_vcf "$OUTDIR/candidates.vcf" \
@@ -49,7 +59,7 @@ python "$SCRIPTDIR/main.py" \
     --model_pool_combine_dimension 0 --model-bottleneck-size 32 --model_final_layer_dilation 2 \
     --model_middle_layer_dilation 2 --model_concat_hw_reads --model-highway-single-reads \
     --gpus "$GPUS" --test-batch-size 200 --save_vcf_records \
-    --save_vcf_records_file "$OUTDIR/model_test.vcf" --test_file "$OUTDIR/candidates.hdf" \
+    --save_vcf_records_file "$OUTDIR/model_test.vcf" "${TEST_INPUT[@]}" \
     --sample_vcf "$OUTDIR/candidates.vcf" --modelload "$MODEL" > "$OUTDIR/training.log" 2>&1
 
 printf "Sort output VCF...\n"

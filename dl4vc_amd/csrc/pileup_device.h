@@ -49,4 +49,24 @@ hipError_t launch_encode(const uint8_t* buf, const Rec* recs, const Loc* locs, i
                          uint8_t* qual, uint8_t* strand, uint8_t* ref_small, int32_t* num_small, int8_t* status_small,
                          hipStream_t s);
 
+// ---- site assembly (assemble_kernels.hip) ----
+constexpr int ASSEMBLE_BLOCK = 256;          // threads per (site, plane) workgroup
+
+// Where one output site comes from.
+struct SiteSrc {
+    int32_t slot;          // location slot of the stored planes
+    int32_t first_rows;    // != 0: stored rows 0..R-1, one contiguous span; 0: the site's R entries of `rows`
+};
+
+struct AssembleArgs {
+    const uint8_t* src[3];  // stored reads / qual / strand [n][S][L]
+    uint8_t* dst[3];        // assembled reads / qual / strand [m][R][L]
+    const SiteSrc* sites;   // [m], device
+    const int16_t* rows;    // [m][R], device; read only where first_rows == 0
+    int32_t S, R, L;
+    int32_t use[3];         // 0: the plane is zero-filled (a model without q-scores / strands)
+};
+
+hipError_t launch_assemble(const AssembleArgs& a, int32_t m, hipStream_t s);
+
 }  // namespace pg

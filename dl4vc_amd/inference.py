@@ -167,3 +167,256 @@ def run_shard(net, hdf_path: str, out_path: str, shard_index: int = 0, shard_cou
                 with CandidateFile(hdf_path) as src:
                     done += score_records(net, src, f.write, a, b, **kw)
     return done
+
+
+# ---- BAM in, scored records out: no candidates.hdf ----------------------------------------------------------------------
+
+ENCODER_COUNTS = ("locations", "gpu", "native", "python", "no_record")
+
+
+class _Stopped(Exception):
+    """The consumer of ``_BamBatches`` has gone: the worker thread ends."""
+
+
+class _Scored:
+    """What ``_Pipeline._emit`` reads of a batch."""
+
+    def __init__(self, vcfrec):
+        self.vcfrec = vcfrec
+
+
+class _BamBatches:
+    """Worker side of ``score_bam``: a thread that turns ``sites_per_launch`` locations at a time into assembled device
+    planes.  Per round: ``pg_encode_device`` into the stored planes (the BAM fetch and framing run in its host threads),
+    ``pe_encode`` for what it declines and the Python builder for what that declines (their planes are copied into the
+    location's slot), rows and masks on the host (``site_assembly.plan_sites``), ``pg_assemble_device`` into one of two plane
+    sets.  A forward batch holds exactly ``sites_per_launch`` RECORDS, as a batch of the candidate file does, so a round's
+    records may finish one set and start the next.
+
+    Device memory, allocated once: the stored planes 3 * B * S * L bytes and two sets of 3 * B * (R + 1) * L bytes.  At B = 4096,
+    S = 200, R = 100, L = 201 that is 494 MB + 2 * 249 MB = 0.99 GB (about 120 KB per site for the stored planes alone)."""
+
+    def __init__(self, cfg, bam, fasta, locations, opt, sites_per_launch, reads_seed, site_limit, device_id, threads, counts):
+        import queue
+        import threading
+        import torch
+        from . import pileup_gpu, loader
+        self.torch, self.cfg, self.bam, self.fasta, self.locations, self.opt = torch, cfg, bam, fasta, locations, opt
+        self.B, self.seed, self.limit, self.threads, self.counts = int(sites_per_launch), reads_seed, site_limit, threads, counts
+        self.S, self.L, self.R = opt.max_reads, 2 * opt.window_size + 1, cfg.reads
+        if self.L != cfg.length:
+            raise ValueError("the encoder's window gives %d columns, the model reads %d" % (self.L, cfg.length))
+        if self.R > self.S:
+            raise ValueError("the model reads %d rows per site but the encoder stores only %d" % (self.R, self.S))
+        self.dev = torch.device("cuda", device_id)
+        self.enc = pileup_gpu.GpuPileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
+                                               opt.max_insert_length_variant, opt.min_base_quality, device=device_id)
+        self.cpu = loader.NativePileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
+                                              opt.max_insert_length_variant, opt.min_base_quality)
+        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=self.dev)   # noqa: E731
+        self.stored = [u8(self.B, self.S, self.L) for _ in range(3)]
+        self.sets = []
+        for _ in range(2):
+            planes = [u8(self.B, self.R, self.L) for _ in range(3)] + [u8(self.B, self.L) for _ in range(3)]
+            self.sets.append({"planes": planes, "vt": torch.empty((self.B, 3), dtype=torch.float32, device=self.dev),
+                              "bp": torch.empty((self.B,), dtype=torch.float32, device=self.dev),
+                              "h_vt": torch.empty((self.B, 3), dtype=torch.float32).pin_memory(),
+                              "h_bp": torch.empty((self.B,), dtype=torch.float32).pin_memory(),
+                              "done": torch.cuda.Event(), "vcfrec": [], "filled": 0})
+        self.stream = torch.cuda.Stream(self.dev)
+        self.free, self.ready = queue.Queue(), queue.Queue(maxsize=1)
+        for s in self.sets:
+            self.free.put(s)
+        self.stop = threading.Event()
+        self.thread = threading.Thread(target=self._run, name="score_bam-encoder", daemon=True)
+
+    # -- queue plumbing that gives up when the consumer has gone
+    def _get_free(self):
+        import queue
+        while not self.stop.is_set():
+            try:
+                return self.free.get(timeout=0.2)
+            except queue.Empty:
+                pass
+        raise _Stopped()
+
+    def _put_ready(self, item):
+        import queue
+        while not self.stop.is_set():
+            try:
+                return self.ready.put(item, timeout=0.2)
+            except queue.Full:
+                pass
+        raise _Stopped()
+
+    def _encode(self, locs):
+        """One round: the stored planes of ``locs`` in device memory -> (ref, num_reads, status) with status in {0, 1}."""
+        torch = self.torch
+        from .pileup_encoder import encode_location, finish_record
+        from .hdf5_schema import record_dtype
+        contigs, positions = [l.contig for l in locs], [l.pos for l in locs]
+        _r, _q, _s, ref, num, status = self.enc.encode_device(contigs, positions, stream=self.stream, out=self.stored)
+        c = self.counts
+        c["locations"] += len(locs)
+        c["gpu"] += int((status == 1).sum())
+        declined = np.flatnonzero(status == 2)
+        if len(declined):
+            sub = self.cpu.encode([contigs[i] for i in declined], [positions[i] for i in declined], self.threads)
+            host = {}
+            for k, i in enumerate(declined):
+                st = int(sub[5][k])
+                if st == 1:
+                    host[int(i)] = (sub[0][k], sub[1][k], sub[2][k], sub[3][k], int(sub[4][k]))
+                    c["native"] += 1
+                elif st == 2:
+                    if self._py is None:
+                        from .bamio import BamFile, FastaFile, WindowReader
+                        b = BamFile(self.bam)
+                        self._py = (b, FastaFile(self.fasta), WindowReader(b))
+                    b, f, reader = self._py
+                    res = encode_location(b, f, locs[i], self.opt, reader)
+                    rec = finish_record(res, locs[i], self.opt, record_dtype(self.S, self.L)) if res is not None else None
+                    if rec is not None:
+                        host[int(i)] = (rec["single_reads"], rec["q-scores"], rec["strand"], rec["ref_bases"], int(rec["num_reads"]))
+                        c["python"] += 1
+                        st = 1
+                    else:
+                        st = 0
+                status[i] = st
+            with torch.cuda.stream(self.stream):
+                for i, (rd, ql, sd, rf, n) in host.items():
+                    for plane, src in zip(self.stored, (rd, ql, sd)):
+                        plane[i].copy_(torch.from_numpy(np.ascontiguousarray(src, np.uint8)))
+                    ref[i], num[i] = rf, n
+        c["no_record"] += int((status == 0).sum())
+        return ref, num, status
+
+    def _run(self):
+        from .site_assembly import plan_sites
+        self._py = None
+        cur = None
+        records = 0
+        try:
+            with self.torch.cuda.device(self.dev):
+                for l0 in range(0, len(self.locations), self.B):
+                    locs = self.locations[l0:l0 + self.B]
+                    ref, num, status = self._encode(locs)
+                    plan = plan_sites(status, num, ref, [l.vcf_string for l in locs], self.R, self.S, self.seed, first_record=records)
+                    if self.limit > 0:
+                        plan = plan.slice(0, max(0, self.limit - records))
+                    records += len(plan)
+                    off = 0
+                    while off < len(plan):
+                        if cur is None:
+                            cur = self._get_free()
+                            cur["vcfrec"], cur["filled"] = [], 0
+                        take = min(len(plan) - off, self.B - cur["filled"])
+                        part, at = plan.slice(off, off + take), cur["filled"]
+                        outs = [t[at:].data_ptr() for t in cur["planes"]]
+                        self.enc.assemble_device([t.data_ptr() for t in self.stored], len(locs), part, outs, self.cfg.use_q,
+                                                 self.cfg.use_strand, stream=self.stream.cuda_stream)
+                        cur["vcfrec"] += part.vcfrec
+                        cur["filled"] += take
+                        off += take
+                        if cur["filled"] == self.B:
+                            self.stream.synchronize()
+                            self._put_ready(cur)
+                            cur = None
+                    self.stream.synchronize()          # the next round overwrites the stored planes
+                    if self.limit > 0 and records >= self.limit:
+                        break
+                if cur is not None and cur["filled"]:
+                    self._put_ready(cur)
+            self._put_ready(None)
+        except _Stopped:
+            pass
+        except BaseException as e:      # noqa: BLE001 -- handed to the consumer, which raises it
+            try:
+                self._put_ready(e)
+            except _Stopped:
+                pass
+        finally:
+            if self._py is not None:
+                self._py[0].close()
+                self._py[1].close()
+
+    def close(self):
+        self.stop.set()
+        if self.thread.is_alive():
+            self.thread.join()
+        self.enc.close()
+        self.cpu.close()
+
+
+def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None], sites_per_launch: int = 4096,
+              reads_seed: int = 0, use_var_type_threshold: bool = False, log=None, stats=None, site_limit: int = 0,
+              encoder_options=None, device_id: int = 0, threads: int = 0, encoder_counts=None) -> int:
+    """Score ``locations`` (``pileup_encoder.Location``s, e.g. ``locations_from_vcf(candidates.vcf, label=2)``) straight from
+    the BAM: the same lines ``tools/convert_bam_single_reads.py`` + ``score_records`` write, without a candidate file.  The
+    pileup planes are encoded (``pg_encode_device``) and assembled (``pg_assemble_device``) in device memory and scored there
+    (``dan_forward_device``); only the rows, the allele masks and the scores cross the bus.
+
+    While batch k's forward runs on its own stream, a worker thread encodes and assembles batch k+1, and batch k-1's scores
+    are formatted.  Site i draws its read subset with ``reads_seed + i``, i counting the locations that gave a record;
+    ``site_limit`` > 0 stops after that many records.  ``encoder_options``: ``pileup_encoder.EncoderOptions`` (default: what
+    call_variants.sh passes to the converter).  ``encoder_counts`` (a dict) receives how many locations each encoder took
+    (``ENCODER_COUNTS``).  Device memory: see ``_BamBatches`` -- about 1 GB at 4096 sites per launch.  ``net`` must have been
+    created after ``import torch`` (see the error below).  Returns the number of sites scored."""
+    import os
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("score_bam: torch sees no HIP device.  It shares buffers and streams with torch, so torch has to be "
+                           "imported before libdl4vc_dan.so / libdl4vc_pileup.so are loaded (one HIP runtime per process)")
+    from .pileup_encoder import EncoderOptions
+    opt = encoder_options or EncoderOptions(window_size=100, max_reads=200, max_insert_length=10, max_insert_length_variant=50,
+                                            min_base_quality=0)
+    counts = encoder_counts if encoder_counts is not None else {}
+    for k in ENCODER_COUNTS:
+        counts.setdefault(k, 0)
+    threads = threads or max(2, min(16, (os.cpu_count() or 4)))
+    emit = _Pipeline(net, write, use_var_type_threshold, stats)._emit
+    src = _BamBatches(net.config, bam, fasta, list(locations), opt, sites_per_launch, reads_seed, site_limit, device_id, threads,
+                      counts)
+    fwd = torch.cuda.Stream(src.dev)
+    done = 0
+    total = len(src.locations)
+    t0 = time.perf_counter()
+
+    def finish(s):
+        s["done"].synchronize()
+        n = s["filled"]
+        emit(_Scored(s["vcfrec"]), {"vt_prob": s["h_vt"][:n].numpy().copy(), "bp": s["h_bp"][:n].numpy().copy()})
+        src.free.put(s)
+
+    prev = None
+    try:
+        src.thread.start()
+        while True:
+            item = src.ready.get()
+            if isinstance(item, BaseException):
+                raise item
+            if item is None:
+                break
+            n = item["filled"]
+            net.handle.forward_device([t.data_ptr() for t in item["planes"]], n, (0, 0, item["vt"].data_ptr(), item["bp"].data_ptr(), 0),
+                                      stream=fwd.cuda_stream)
+            with torch.cuda.stream(fwd):
+                item["h_vt"][:n].copy_(item["vt"][:n], non_blocking=True)
+                item["h_bp"][:n].copy_(item["bp"][:n], non_blocking=True)
+                item["done"].record(fwd)
+            if prev is not None:
+                finish(prev)
+            prev = item
+            done += n
+            if log:
+                dt = time.perf_counter() - t0
+                log("  submitted %d sites of %d locations (%.0f sites/s)" % (done, total, done / max(dt, 1e-9)))
+        if prev is not None:
+            finish(prev)
+            prev = None
+    finally:
+        if prev is not None:
+            prev["done"].synchronize()
+        fwd.synchronize()
+        src.close()
+    return done

@@ -16,7 +16,7 @@ from .loader import PileupOptions
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_pileup.so")
-SYMBOLS = ("pg_open", "pg_encode", "pg_encode_device", "pg_close", "pg_last_error")
+SYMBOLS = ("pg_open", "pg_encode", "pg_encode_device", "pg_assemble_device", "pg_close", "pg_last_error")
 MAX_TRACKS = 1024            # PG_MAX_TRACKS
 MAX_WINDOW = 100             # PG_MAX_WINDOW
 _lib = None
@@ -36,6 +36,8 @@ def load_library() -> C.CDLL:
         lib.pg_open.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PileupOptions), C.c_int32, C.POINTER(vp)]
         lib.pg_encode.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
         lib.pg_encode_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
+        lib.pg_assemble_device.argtypes = ([vp] * 4 + [C.c_int64, C.c_int32, C.c_int32] + [vp] * 3 + [C.c_int64, C.c_int32] + [vp] * 3 +
+                                           [C.c_int32, C.c_int32] + [vp] * 6 + [vp])
         lib.pg_close.argtypes = [vp]
         lib.pg_close.restype = None
         lib.pg_last_error.argtypes = [vp]
@@ -81,19 +83,49 @@ class GpuPileupEncoder:
                                        p(num), p(status)), "pg_encode")
         return reads, qual, strand, ref, num, status
 
-    def encode_device(self, contigs: Sequence[str], positions, stream=None):
+    def encode_device(self, contigs: Sequence[str], positions, stream=None, out=None):
         """-> (reads, qual, strand: torch uint8 [n][max_reads][W] on the encoder's device, ref, num_reads, status: host).
-        ``stream``: a ``torch.cuda.Stream`` the planes are ordered after (default: the current stream)."""
+        ``stream``: a ``torch.cuda.Stream`` the planes are ordered after (default: the current stream).  ``out``: three
+        contiguous uint8 tensors on the encoder's device with room for n locations, written instead of new ones (their first
+        n slots are returned)."""
         import torch
         n, names, pos, ref, num, status = self._args(contigs, positions)
         dev = torch.device("cuda", self.device)
-        reads, qual, strand = (torch.empty((n, self.max_reads, self.window), dtype=torch.uint8, device=dev) for _ in range(3))
+        if out is not None:
+            for x in out:
+                if x.dtype != torch.uint8 or not x.is_contiguous() or x.device != dev or x.numel() < n * self.max_reads * self.window:
+                    raise ValueError("out: three contiguous uint8 tensors on %s with room for %d locations" % (dev, n))
+            reads, qual, strand = (x.view(-1)[:n * self.max_reads * self.window].view(n, self.max_reads, self.window) for x in out)
+        else:
+            reads, qual, strand = (torch.empty((n, self.max_reads, self.window), dtype=torch.uint8, device=dev) for _ in range(3))
         s = stream if stream is not None else torch.cuda.current_stream(dev)
         p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
         t = lambda x: C.c_void_p(x.data_ptr() if x.numel() else None)   # noqa: E731
         self._check(self.lib.pg_encode_device(self._h, C.cast(names, C.c_void_p), p(pos), n, t(reads), t(qual), t(strand),
                                               p(ref), p(num), p(status), C.c_void_p(s.cuda_stream)), "pg_encode_device")
         return reads, qual, strand, ref, num, status
+
+    def assemble_device(self, src_ptrs, n_slots: int, plan, out_ptrs, use_q: bool = True, use_strand: bool = True,
+                        stream: int = 0, stored_rows: Optional[int] = None, window: Optional[int] = None) -> None:
+        """``pg_assemble_device``: the stored planes at the device addresses ``src_ptrs`` (reads, qual, strand:
+        ``[n_slots][stored_rows][window]``) -> the six planes of ``plan``'s sites (``site_assembly.SitePlan``) at the device
+        addresses ``out_ptrs`` (reads, qual, strand, ref, ref_mask, var_mask), enqueued on ``stream`` (a raw hipStream_t, 0 = the
+        default stream).  Asynchronous: the caller synchronises the stream."""
+        m = len(plan)
+        if m == 0:
+            return
+        R = plan.rows.shape[1]
+        slots = np.ascontiguousarray(plan.slots, np.int32)
+        first = np.ascontiguousarray(plan.first_rows, np.uint8)
+        rows = np.ascontiguousarray(plan.rows, np.int16) if not first.all() else None
+        lines = [np.ascontiguousarray(a, np.uint8) for a in (plan.ref, plan.ref_mask, plan.var_mask)]
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
+        v = lambda x: C.c_void_p(int(x)) if x else None   # noqa: E731
+        self._check(self.lib.pg_assemble_device(self._h, *[v(x) for x in src_ptrs], int(n_slots),
+                                                int(stored_rows if stored_rows is not None else self.max_reads),
+                                                int(window if window is not None else self.window), p(slots), p(rows), p(first), m, R,
+                                                *[p(a) for a in lines], int(bool(use_q)), int(bool(use_strand)),
+                                                *[v(x) for x in out_ptrs], v(stream)), "pg_assemble_device")
 
     def close(self):
         if self._h is not None:

@@ -1,0 +1,97 @@
+"""Site assembly without candidates.hdf: encoder planes of a list of locations -> the six planes of the forward.
+
+What ``dataset.assemble_batch`` / the native loader do to the records of a candidate file, restated for planes that never
+became records: locations without a record (status 0) leave no hole, site i takes R of the S stored rows -- the first R, or
+the seeded sorted subset of a pileup deeper than R, drawn by ``dl_select_rows`` with ``seed + (absolute record index)`` --
+and gets its allele masks from ``dl_allele_masks`` (both are the native loader's own functions, libdl4vc_loader.so).
+
+``plan_sites`` is the host part (rows, masks, record text); ``assemble_host`` is the numpy statement of the copy that
+``pg_assemble_device`` (csrc/assemble_kernels.hip) does on the device, and the definition that kernel is tested against."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import List, Sequence
+
+import numpy as np
+
+from .hdf5_schema import VCFREC_BYTES
+
+
+@dataclass
+class SitePlan:
+    slots: np.ndarray        # (m,) i32   location slot of each output site
+    rows: np.ndarray         # (m,R) i16  stored rows of each output site
+    first_rows: np.ndarray   # (m,) u8    1: rows 0..R-1
+    ref: np.ndarray          # (m,L) u8
+    ref_mask: np.ndarray     # (m,L) u8
+    var_mask: np.ndarray     # (m,L) u8
+    vcfrec: List[str]        # record text as the candidate file would hold it (truncated to S128)
+    num_reads: np.ndarray    # (m,) i32
+
+    def __len__(self):
+        return len(self.slots)
+
+    def slice(self, lo: int, hi: int) -> "SitePlan":
+        return SitePlan(self.slots[lo:hi], self.rows[lo:hi], self.first_rows[lo:hi], self.ref[lo:hi], self.ref_mask[lo:hi],
+                        self.var_mask[lo:hi], self.vcfrec[lo:hi], self.num_reads[lo:hi])
+
+
+def stored_vcfrec(vcf_string: str) -> str:
+    """The text ``record_dtype``'s ``vcfrec`` field keeps of a location's record: 128 bytes, read back up to the first NUL."""
+    return vcf_string.encode()[:VCFREC_BYTES].split(b"\x00", 1)[0].decode()
+
+
+def plan_sites(status, num_reads, ref, vcf_strings: Sequence[str], reads: int, stored_rows: int, seed: int,
+               first_record: int = 0) -> SitePlan:
+    """Rows and masks of the locations with ``status == 1``, in order.  Site i (counting records only) draws with
+    ``seed + first_record + i``, as ``score_records`` / ``NativeLoader`` seed record ``first_record + i`` of a file."""
+    from . import loader
+    lib = loader.load_library()
+    status = np.asarray(status)
+    slots = np.flatnonzero(status == 1).astype(np.int32)
+    m, R, S = len(slots), int(reads), int(stored_rows)
+    L = ref.shape[1] if ref.ndim == 2 else 0
+    if R > S:
+        raise ValueError("the model reads %d rows per site but the encoder stores only %d" % (R, S))
+    if m and L != 201:
+        raise ValueError("allele masks are defined on the 201-column window (window size 100), not %d columns" % L)
+    rows = np.empty((m, R), np.int16)
+    rows[:] = np.arange(R, dtype=np.int16)
+    first = np.ones(m, np.uint8)
+    out_ref = np.ascontiguousarray(ref[slots], np.uint8)
+    rmask, vmask = np.zeros((m, L), np.uint8), np.zeros((m, L), np.uint8)
+    nr = np.ascontiguousarray(np.asarray(num_reads)[slots], np.int32)
+    recs = []
+    draw = np.empty(max(R, S), np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    base = int(seed) & 0xFFFFFFFF
+    for i in range(m):
+        n = int(nr[i])
+        if n > R:
+            if n > S:
+                raise ValueError("location slot %d holds %d reads, more than the %d stored rows" % (slots[i], n, S))
+            k = lib.dl_select_rows((base + first_record + i) & 0xFFFFFFFF, n, S, R, draw.ctypes.data_as(C.POINTER(C.c_int32)))
+            if k != R:
+                raise ValueError("dl_select_rows gave %d rows, not %d" % (k, R))
+            rows[i] = draw[:R]
+            first[i] = 0
+        text = stored_vcfrec(vcf_strings[int(slots[i])])
+        recs.append(text)
+        st = lib.dl_allele_masks(text.encode(), p(out_ref[i:i + 1]), p(rmask[i:i + 1]), p(vmask[i:i + 1]))
+        if st not in (0, 1):
+            raise ValueError("record %d (%s): the allele masks cannot be built" % (first_record + i, text.split("\t", 2)[:2]))
+    return SitePlan(slots, rows, first, out_ref, rmask, vmask, recs, nr)
+
+
+def assemble_host(reads, qual, strand, plan: SitePlan, use_q: bool = True, use_strand: bool = True):
+    """numpy statement of ``pg_assemble_device``: stored planes ``[n][S][L]`` -> ``(reads, qual, strand [m][R][L], ref, ref_mask,
+    var_mask [m][L])``; row gather, compaction over the sites of ``plan``, zero-fill of an unused plane."""
+    m, R = plan.rows.shape
+    L = reads.shape[2]
+    rows = np.where(plan.first_rows[:, None] != 0, np.arange(R)[None, :], plan.rows).astype(np.int64)
+    site = plan.slots.astype(np.int64)[:, None]
+    rd = np.ascontiguousarray(reads[site, rows]) if m else np.zeros((0, R, L), np.uint8)
+    ql = np.ascontiguousarray(qual[site, rows]) if (m and use_q) else np.zeros((m, R, L), np.uint8)
+    st = np.ascontiguousarray(strand[site, rows]) if (m and use_strand) else np.zeros((m, R, L), np.uint8)
+    return rd, ql, st, plan.ref.copy(), plan.ref_mask.copy(), plan.var_mask.copy()

@@ -47,6 +47,23 @@ int pg_encode(pg_encoder_t* h, const char* const* contigs, const int32_t* positi
 int pg_encode_device(pg_encoder_t* h, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads_dev,
                      uint8_t* qual_dev, uint8_t* strand_dev, uint8_t* ref_out, int32_t* num_reads_out, int8_t* status_out,
                      void* stream);
+/* Site assembly on the device: the stored planes pg_encode_device wrote -> the six planes dan_forward_device reads
+ * (include/dl4vc_dan.h), compacted over the m locations that gave a record.
+ *   reads_src / qual_src / strand_src: DEVICE, [n_slots][stored_rows][window] (stored_rows = the encoder's max_reads);
+ *   slots [m]: HOST, the location slot each output site comes from;
+ *   rows [m][reads]: HOST int16, the stored rows of each output site in output order (NULL: every site takes rows
+ *     0..reads-1); first_rows [m]: HOST, may be NULL; != 0 marks a site that takes rows 0..reads-1 (its rows are not read);
+ *   ref / ref_mask / var_mask [m][window]: HOST;
+ *   outputs: DEVICE, reads_out / qual_out / strand_out [m][reads][window], ref_out / ref_mask_out / var_mask_out [m][window];
+ *     qual_out / strand_out are zero-filled when use_q / use_strand is 0.
+ * Slots and rows are range-checked on the host before anything is enqueued.  The host arrays are free again on return; the
+ * copies and the kernel are enqueued on `stream` (a hipStream_t, NULL = the default stream) behind the work already there, and
+ * the call returns without waiting for them: the caller synchronises, or enqueues dan_forward_device on the same stream. */
+int pg_assemble_device(pg_encoder_t* h, const uint8_t* reads_src, const uint8_t* qual_src, const uint8_t* strand_src,
+                       int64_t n_slots, int32_t stored_rows, int32_t window, const int32_t* slots, const int16_t* rows,
+                       const uint8_t* first_rows, int64_t m, int32_t reads, const uint8_t* ref, const uint8_t* ref_mask,
+                       const uint8_t* var_mask, int32_t use_q, int32_t use_strand, uint8_t* reads_out, uint8_t* qual_out,
+                       uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out, uint8_t* var_mask_out, void* stream);
 void pg_close(pg_encoder_t* h);
 const char* pg_last_error(const pg_encoder_t* h);      /* h may be NULL: error of the last failed pg_open */
 

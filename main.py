@@ -22,7 +22,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from arguments import create_arg_parser                       # noqa: E402
+from arguments import parse_args                              # noqa: E402
 
 
 def child_devices(n: int):
@@ -251,12 +251,36 @@ def train_main(args, argv) -> int:
     return 0
 
 
+GPUS_WITH_BAM = ("--test_bam runs on one GPU: a shard's read subsets are seeded with the index of its first RECORD, which needs the "
+                 "number of locations without a record in every shard before it; drop --gpus, or convert to candidates.hdf "
+                 "(tools/convert_bam_single_reads.py) and use --test_file --gpus N")
+
+
+def check_bam_arguments(args) -> None:
+    """--test_bam: what it needs and what it refuses (nothing is silently ignored)."""
+    if args.test_file:
+        raise SystemExit("--test_file and --test_bam are two sources of the same sites: give exactly one")
+    if args.train_file:
+        raise SystemExit("--test_bam is an inference input; training evaluates on a --test_file")
+    if not args.test_fasta or not args.sample_vcf:
+        raise SystemExit("--test_bam needs --test_fasta (the reference) and --sample_vcf (the candidate VCF: its records are the sites)")
+    if args.gpus > 1 or args.shard:
+        raise SystemExit(GPUS_WITH_BAM)
+    if args.test_holdout_chromosomes:
+        raise SystemExit("--test_holdout_chromosomes is not supported with --test_bam: on a candidate file the held-out records keep "
+                         "the record index (the read-subset seed) they have among ALL records, which only encoding every location "
+                         "would give; filter the candidate VCF instead")
+
+
 def main(argv=None) -> int:
-    args = create_arg_parser().parse_args(argv)
+    args = parse_args(argv)
     print(args)
+    if args.test_bam:
+        check_bam_arguments(args)
     if args.train_file:
         return train_main(args, list(argv if argv is not None else sys.argv[1:]))
-    assert args.test_file[-3:] == "hdf", "Test dataset must be in HDF format"                     # main.py:84
+    if not args.test_bam:
+        assert args.test_file[-3:] == "hdf", "Test dataset must be in HDF format"                 # main.py:84
     print("\n\nRunning in inference only mode...\n\n")
     assert args.modelload is not None, "--modelload argument is required when running in inference only mode"   # main.py:215
     from dl4vc_amd.config import DanConfig
@@ -284,7 +308,7 @@ def main(argv=None) -> int:
     shard_i, shard_n = parse_shard(args.shard)
     if args.save_vcf_records:
         assert args.save_vcf_records_file != "", "Need a valid filename for args.save_vcf_records_file to save records"
-    out_base = args.save_vcf_records_file or os.path.join(os.path.dirname(args.test_file), "model_test.vcf")
+    out_base = args.save_vcf_records_file or os.path.join(os.path.dirname(args.test_bam or args.test_file), "model_test.vcf")
     out_final = scored_vcf_path(out_base)                     # <dir>/epoch1_<basename>, dl4vc/utils.py:152
 
     if args.gpus > 1 and not args.shard:
@@ -330,6 +354,12 @@ def main(argv=None) -> int:
         print("\tTime elapsed for inference/testing {:.4f}".format(time.time() - t0))
         return 0
 
+    if args.test_bam:
+        # this path shares device buffers and streams with torch: torch's HIP runtime has to be the process's only one, so it
+        # is loaded before libdl4vc_dan.so brings in its own
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("--test_bam needs a HIP device visible to torch; there is no CPU path")
     from dl4vc_amd.model import DanNet, load_checkpoint
     from dl4vc_amd.inference import run_shard
 
@@ -342,17 +372,32 @@ def main(argv=None) -> int:
         target = out_final + ".records"
     t_loop = time.time()
     stats = None if os.environ.get("DL4VC_NO_THRESHOLD_STATS") else {}      # (the near-threshold count is a log line: opt out for raw rate)
-    n = run_shard(net, args.test_file, target, shard_i, shard_n, sites_per_launch=args.sites_per_launch,
-                  reads_seed=args.reads_seed, use_var_type_threshold=args.use_var_type_threshold,
-                  holdout_chromosomes=holdout, site_limit=site_limit, log=lambda m: print(m, end="\r"), stats=stats)
+    counts = {}
+    if args.test_bam:
+        # the encoder options are what call_variants.sh passes to the converter (score_bam's default)
+        from dl4vc_amd.inference import score_bam
+        from dl4vc_amd.pileup_encoder import locations_from_vcf
+        locations = locations_from_vcf(args.sample_vcf, label=2)
+        with open(target, "w") as f:
+            n = score_bam(net, args.test_bam, args.test_fasta, locations, f.write, sites_per_launch=args.sites_per_launch,
+                          reads_seed=args.reads_seed, use_var_type_threshold=args.use_var_type_threshold, site_limit=site_limit,
+                          log=lambda m: print(m, end="\r"), stats=stats, encoder_counts=counts)
+    else:
+        n = run_shard(net, args.test_file, target, shard_i, shard_n, sites_per_launch=args.sites_per_launch,
+                      reads_seed=args.reads_seed, use_var_type_threshold=args.use_var_type_threshold,
+                      holdout_chromosomes=holdout, site_limit=site_limit, log=lambda m: print(m, end="\r"), stats=stats)
     t_loop = time.time() - t_loop
     net.close()
+    if args.test_bam:
+        print("\npileup encoder: %d locations: %d on the GPU, %d by pe_encode, %d by the Python builder, %d without a record"
+              % tuple(counts[k] for k in ("locations", "gpu", "native", "python", "no_record")))
     if stats is not None:
         print("\n%d of %d sites lie within 1e-4 of a genotype threshold of the published pipeline (format_vcf flags of "
               "call_variants.sh:154-160; main.py has no threshold flags of its own -- tools/format_vcf.py takes them later): only "
               "there could a call differ from another correct fp32 evaluation of the same scores"
               % (stats.get("near_threshold", 0), stats.get("sites", 0)))
-    print("\nscoring loop (HDF5 read + assembly + forward + VCF text): %d sites in %.2f s = %.0f sites/s" % (n, t_loop, n / max(t_loop, 1e-9)))
+    print("\nscoring loop (%s + assembly + forward + VCF text): %d sites in %.2f s = %.0f sites/s"
+          % ("BAM fetch + pileup encoder" if args.test_bam else "HDF5 read", n, t_loop, n / max(t_loop, 1e-9)))
     if shard_n == 1:
         if args.sample_vcf:
             start_scored_vcf(args.sample_vcf, out_base)

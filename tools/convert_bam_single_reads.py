@@ -58,6 +58,9 @@ def main(argv=None):
     ap.add_argument("--max-insert-length-variant", type=int, default=50)
     ap.add_argument("--save-q-scores", action="store_true")
     ap.add_argument("--save-strand", action="store_true")
+    ap.add_argument("--pileup-device", type=str, default=None, choices=["gpu"],
+                    help="gpu: build the image planes with the GPU pileup encoder (libdl4vc_pileup.so); what it declines goes to the "
+                         "host encoders, so the file is the same bytes (default: the host encoders)")
     args = ap.parse_args(argv)
     for flag, why in (("locations", "numpy location tables"), ("restrict_locations", "location restriction files"),
                       ("non_restrict_match_random", "location restriction files")):
@@ -90,10 +93,12 @@ def main(argv=None):
     pool = None
     from dl4vc_amd import loader
     native = loader.available() and not os.environ.get("DL4VC_PILEUP_PYTHON")
-    if native:
+    if args.pileup_device == "gpu":
+        print("GPU pileup encoder; %d thread(s) for what it declines" % procs)
+    elif native:
         # the native encoder (libdl4vc_loader.so, pe_*): --num-processes becomes worker THREADS over contiguous runs of locations
         print("native pileup encoder: %d thread(s)" % procs)
-    if not native and procs > 1 and n_loc - start > 4 * procs:
+    if not native and args.pileup_device is None and procs > 1 and n_loc - start > 4 * procs:
         import multiprocessing as mp
         pool = mp.get_context("spawn").Pool(procs)
     total_errors, written, created = 0, 0, append
@@ -108,7 +113,8 @@ def main(argv=None):
                 recs = np.concatenate([p[0] for p in parts]) if parts else np.zeros(0)
                 errors = sum(p[1] for p in parts)
             else:
-                recs, errors = encode_locations(args.input, args.fasta_input, chunk, opt, native=native, threads=procs)
+                recs, errors = encode_locations(args.input, args.fasta_input, chunk, opt, native=native, threads=procs,
+                                                device=args.pileup_device)
             total_errors += errors
             if not created:
                 hdf5io.write_candidates(args.output, recs, chunk=8)
