@@ -9,12 +9,15 @@
 # as it is.  With an OUTDIR that also holds candidates.hdf, -i / -r are not needed and the conversion is skipped.
 # -d (direct; needs -i and -r, one GPU): no candidates.hdf at all -- main.py --test_bam encodes the pileups on the GPU, assembles
 # and scores them there.  The scored VCF is byte-identical to the two-step path's.  Without -d nothing changes.
+# -z: the candidate generator inflates the BAM's BGZF blocks and frames its records on the GPU (--inflate-device gpu; needs
+# BAM.bai); candidates.vcf is the same.
 set -e
-usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d]"; exit 1; }
+usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z]"; exit 1; }
 GPUS=1
 PROCS=16
 DIRECT=0
-while getopts "m:o:g:i:r:b:p:dh" opt; do
+INFLATE=""
+while getopts "m:o:g:i:r:b:p:dzh" opt; do
   case $opt in
     m) MODEL=$OPTARG ;;
     o) OUTDIR=$OPTARG ;;
@@ -24,6 +27,7 @@ while getopts "m:o:g:i:r:b:p:dh" opt; do
     b) BED=$OPTARG ;;       # candidate generation only
     p) PROCS=$OPTARG ;;
     d) DIRECT=1 ;;          # score straight from the BAM (main.py --test_bam)
+    z) INFLATE=gpu ;;       # candidate generation only: BGZF inflate and record framing on the GPU
     *) usage ;;
   esac
 done
@@ -34,6 +38,7 @@ if [ ! -f "$OUTDIR/candidates.hdf" ] && [ ! -f "$OUTDIR/candidates.vcf" ] && [ -
   printf "Generate candidate VCF...\n"
   python "$SCRIPTDIR/tools/candidate_generator.py" --input "$BAM" --output "$OUTDIR/candidates.vcf" \
       --snp_min_freq 0.075 --indel_min_freq 0.02 ${BED:+--bedfile "$BED"} --keep_multialleles \
+      ${INFLATE:+--inflate-device "$INFLATE"} \
       > "$OUTDIR/candidate_generator.log" 2>&1
 fi
 if [ "$DIRECT" = 1 ]; then

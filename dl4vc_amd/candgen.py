@@ -10,7 +10,10 @@ from typing import Dict, List, Optional, Sequence, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_cand.so")
 MAX_ALLELE_LEN = 63          # CG_MAX_ALLELE_LEN
-SYMBOLS = ("cg_open", "cg_run", "cg_last_error", "cg_close", "cg_n_refs", "cg_ref_name", "cg_ref_length")
+SYMBOLS = ("cg_open", "cg_run", "cg_last_error", "cg_close", "cg_n_refs", "cg_ref_name", "cg_ref_length",
+           "cg_set_inflate_device", "cg_get_inflate_stats", "cg_debug_ranges",
+           "bz_inflate", "bz_inflate_host", "bz_status_text", "bz_last_error")
+INFLATE_DEVICES = ("gpu",)
 
 
 class Options(C.Structure):
@@ -36,6 +39,14 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class InflateStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("blocks", "compressed_bytes", "inflated_bytes", "records")] + \
+               [(n, C.c_double) for n in ("read_ms", "inflate_ms", "walk_frame_ms")]
+
+    def as_dict(self) -> Dict[str, float]:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -55,6 +66,16 @@ def load_library() -> C.CDLL:
         lib.cg_ref_name.restype = C.c_char_p
         lib.cg_ref_length.argtypes = [C.c_void_p, C.c_int32]
         lib.cg_ref_length.restype = C.c_int64
+        lib.cg_set_inflate_device.argtypes = [C.c_void_p, C.c_int]
+        lib.cg_get_inflate_stats.argtypes = [C.c_void_p, C.POINTER(InflateStats)]
+        lib.cg_debug_ranges.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                        C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        lib.bz_inflate.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                   C.c_int]
+        lib.bz_inflate_host.argtypes = lib.bz_inflate.argtypes[:-1]
+        lib.bz_status_text.argtypes = [C.c_int]
+        lib.bz_status_text.restype = C.c_char_p
+        lib.bz_last_error.restype = C.c_char_p
         _lib = lib
     return _lib
 
@@ -63,11 +84,47 @@ def default_threads() -> int:
     return min(16, len(os.sched_getaffinity(0)))
 
 
+def status_text(status: int) -> str:
+    return load_library().bz_status_text(int(status)).decode()
+
+
+def inflate_blocks(blocks: bytes, block_off, out, out_off, device: Optional[int] = None) -> List[int]:
+    """Inflates the whole BGZF blocks that start at ``blocks[block_off[i]]`` into ``out[out_off[i]:]`` (``out``: a writable
+    uint8 numpy array, changed in place) and returns one status per block (0 = ok, else ``status_text``).  ``device`` None runs
+    the decode core on the CPU (``bz_inflate_host``), an ordinal runs the kernel on that GPU (``bz_inflate``)."""
+    import numpy as np
+    host_lib = os.environ.get("DL4VC_BGZF_HOST_LIB")     # (a sanitizer build of the decode core: tools/asan_bgzf.sh)
+    if device is None and host_lib:
+        lib = C.CDLL(host_lib)
+        lib.bz_inflate_host.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.bz_last_error.restype = C.c_char_p
+    else:
+        lib = load_library()
+    boff = np.ascontiguousarray(block_off, dtype=np.uint64)
+    ooff = np.ascontiguousarray(out_off, dtype=np.uint64)
+    if boff.shape != ooff.shape or boff.ndim != 1:
+        raise ValueError("block_off and out_off must be one-dimensional and of one length")
+    if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable):
+        raise ValueError("out must be a writable contiguous uint8 array")
+    blocks = bytes(blocks)
+    status = np.zeros(len(boff), np.int32)
+    args = [blocks, len(blocks), boff.ctypes.data, len(boff), out.ctypes.data, out.size, ooff.ctypes.data, status.ctypes.data]
+    rc = lib.bz_inflate_host(*args) if device is None else lib.bz_inflate(*args, int(device))
+    if rc != 0:
+        raise RuntimeError("bz_inflate: %s" % lib.bz_last_error().decode())
+    return [int(v) for v in status]
+
+
 class CandidateCounter:
-    """One open BAM.  ``run(subregions)`` -> ``[(region_index, tid, pos0, ref, alt, depth, count)]`` (unordered) and stats."""
+    """One open BAM.  ``run(subregions)`` -> ``[(region_index, tid, pos0, ref, alt, depth, count)]`` (unordered) and stats.
+    ``inflate_device="gpu"`` sends each batch's BGZF blocks to the device compressed (inflate, record walk and framing there;
+    needs the ``.bai``); the stats then carry ``inflate_*`` entries as well."""
 
     def __init__(self, bam_path: str, bai_path: Optional[str] = None, threads: Optional[int] = None,
-                 max_len_indel_allele: int = 60, snp_min_freq: float = 0.01, indel_min_freq: float = 0.01, device: int = 0):
+                 max_len_indel_allele: int = 60, snp_min_freq: float = 0.01, indel_min_freq: float = 0.01, device: int = 0,
+                 inflate_device: Optional[str] = None):
+        if inflate_device is not None and inflate_device not in INFLATE_DEVICES:
+            raise ValueError("inflate_device must be None or one of %s" % (INFLATE_DEVICES,))
         self.lib = load_library()
         if bai_path is None and os.path.isfile(bam_path + ".bai"):
             bai_path = bam_path + ".bai"
@@ -77,6 +134,11 @@ class CandidateCounter:
         if rc != 0:
             raise RuntimeError("cg_open: %s" % self.lib.cg_last_error().decode())
         self.h = h
+        self.inflate_device = inflate_device
+        if inflate_device is not None and self.lib.cg_set_inflate_device(h, 1) != 0:
+            msg = self.lib.cg_last_error().decode()
+            self.close()
+            raise RuntimeError("cg_set_inflate_device: %s" % msg)
         n = self.lib.cg_n_refs(h)
         self.references: List[str] = [self.lib.cg_ref_name(h, i).decode() for i in range(n)]
         self.lengths: List[int] = [int(self.lib.cg_ref_length(h, i)) for i in range(n)]
@@ -90,7 +152,24 @@ class CandidateCounter:
         if rc != 0:
             raise RuntimeError("cg_run: %s" % self.lib.cg_last_error().decode())
         res = [(c.region, c.tid, c.pos0, c.ref.decode(), c.alt.decode(), c.depth, c.count) for c in out[:n.value]]
-        return res, st.as_dict()
+        stats = st.as_dict()
+        if self.inflate_device is not None:
+            ist = InflateStats()
+            self.lib.cg_get_inflate_stats(self.h, C.byref(ist))
+            stats.update((k if k == "inflate_ms" else "inflate_" + k, v) for k, v in ist.as_dict().items())
+        return res, stats
+
+    def debug_ranges(self, tid: int, start: int, end: int):
+        """``(ranges, bounds)`` of the device inflate path for one region, as BGZF virtual offsets: merged ``[begin, end)``
+        pairs and the sorted walk boundaries (for tests; reads the index only)."""
+        import numpy as np
+        nr, nb = C.c_int64(), C.c_int64()
+        if self.lib.cg_debug_ranges(self.h, tid, start, end, None, 0, C.byref(nr), None, 0, C.byref(nb)) != 0:
+            raise RuntimeError("cg_debug_ranges: %s" % self.lib.cg_last_error().decode())
+        ranges, bounds = np.zeros(2 * max(1, nr.value), np.uint64), np.zeros(max(1, nb.value), np.uint64)
+        self.lib.cg_debug_ranges(self.h, tid, start, end, ranges.ctypes.data, nr.value, C.byref(nr), bounds.ctypes.data, nb.value,
+                                 C.byref(nb))
+        return [(int(ranges[2 * i]), int(ranges[2 * i + 1])) for i in range(nr.value)], [int(v) for v in bounds[:nb.value]]
 
     def close(self) -> None:
         if self.h:

@@ -194,14 +194,15 @@ def candidate_tuples(subregions: Sequence[Region], counted: Sequence[tuple], kee
 def generate(bam_path: str, output: str, contigs: Optional[str] = None, bedfile: Optional[str] = None,
              keep_contig_chr: bool = False, chunk_size: int = 1000, threads: Optional[int] = None, snp_min_freq: float = 0.01,
              indel_min_freq: float = 0.01, keep_multialleles: bool = False, max_len_indel_allele: int = 60,
-             device: int = 0) -> dict:
-    """Writes ``output`` and returns the run's summary (counts of reads by kind, candidates, times)."""
+             device: int = 0, inflate_device: Optional[str] = None) -> dict:
+    """Writes ``output`` and returns the run's summary (counts of reads by kind, candidates, times).  ``inflate_device="gpu"``
+    inflates and frames the BAM's records on the device (needs the ``.bai``) and adds the ``inflate_*`` figures to the summary."""
     from .candgen import CandidateCounter, MAX_ALLELE_LEN
     if max_len_indel_allele > MAX_ALLELE_LEN:
         raise ValueError("--max_len_indel_allele %d exceeds the allele key's limit of %d bases" % (max_len_indel_allele,
                                                                                                   MAX_ALLELE_LEN))
     with CandidateCounter(bam_path, threads=threads, max_len_indel_allele=max_len_indel_allele, snp_min_freq=snp_min_freq,
-                          indel_min_freq=indel_min_freq, device=device) as cc:
+                          indel_min_freq=indel_min_freq, device=device, inflate_device=inflate_device) as cc:
         regions = contig_regions(cc.references, cc.lengths, contigs, bedfile, keep_contig_chr)
         logging.info("Examining %d regions in the bamfile", len(regions))
         subregions = split_subregions(regions, chunk_size * 1000)

@@ -200,9 +200,11 @@ inline const char* frame_record(const uint8_t* b, size_t size, RecordFrame& fr) 
     return nullptr;
 }
 
-// ---- BAI: the linear index only -------------------------------------------------------------------------------------------------
+// ---- BAI: the linear index, and the chunks of every bin ------------------------------------------------------------------------
 struct Bai {
     std::vector<std::vector<uint64_t>> linear;
+    typedef std::pair<uint64_t, uint64_t> Chunk;                 // [begin, end) as virtual offsets
+    std::vector<std::map<uint32_t, std::vector<Chunk>>> bins;    // per reference: bin -> chunks (the pseudo-bin 37450 left out)
     // false when the file is absent, not a BAI or shorter than its own counts say
     bool load(const std::string& path) {
         FILE* f = fopen(path.c_str(), "rb");
@@ -220,10 +222,20 @@ struct Bai {
         for (int r = 0; r < n_ref; ++r) {
             int32_t n_bin;
             if (!take32(n_bin) || n_bin < 0) return false;
+            bins.emplace_back();
             for (int b = 0; b < n_bin; ++b) {
                 int32_t bin, n_chunk;
                 if (!take32(bin) || !take32(n_chunk) || n_chunk < 0) return false;
                 if ((uint64_t)16 * (uint64_t)n_chunk > raw.size() - o) return false;
+                if ((uint32_t)bin != 37450u) {
+                    std::vector<Chunk>& ch = bins.back()[(uint32_t)bin];
+                    for (int32_t c = 0; c < n_chunk; ++c) {
+                        Chunk k;
+                        memcpy(&k.first, &raw[o + 16 * (size_t)c], 8);
+                        memcpy(&k.second, &raw[o + 16 * (size_t)c + 8], 8);
+                        ch.push_back(k);
+                    }
+                }
                 o += 16 * (size_t)n_chunk;
             }
             int32_t n_intv;
@@ -242,6 +254,36 @@ struct Bai {
         const auto& lin = linear[tid];
         for (size_t w = (size_t)(std::max<int64_t>(start, 0) >> 14); w < lin.size(); ++w) if (lin[w]) return lin[w];
         return 0;
+    }
+    // The chunks of every bin that overlaps [start, end) (reg2bins), without those that end at or before the linear index's
+    // offset for start (htslib's pruning: no alignment that reaches start begins there); appended to out, unmerged.
+    void region_chunks(int tid, int64_t start, int64_t end, std::vector<Chunk>& out) const {
+        if (tid < 0 || tid >= (int)bins.size() || end <= start) return;
+        const uint64_t min_off = linear_offset(tid, start);
+        if (min_off == 0) return;
+        const int64_t b = std::max<int64_t>(start, 0), e = std::min<int64_t>(end, (int64_t)1 << 29) - 1;
+        if (e < b) return;
+        const auto& m = bins[tid];
+        auto take = [&](uint32_t bin) {
+            const auto it = m.find(bin);
+            if (it == m.end()) return;
+            for (const Chunk& c : it->second) if (c.second > min_off && c.second > c.first) out.push_back(c);
+        };
+        take(0);
+        const int shift[5] = {26, 23, 20, 17, 14};
+        const uint32_t base[5] = {1, 9, 73, 585, 4681};
+        for (int l = 0; l < 5; ++l)
+            for (int64_t k = b >> shift[l]; k <= (e >> shift[l]); ++k) take(base[l] + (uint32_t)k);
+    }
+    // sorted, with overlapping and adjacent chunks merged
+    static void merge_chunks(std::vector<Chunk>& v) {
+        std::sort(v.begin(), v.end());
+        size_t n = 0;
+        for (const Chunk& c : v) {
+            if (n > 0 && c.first <= v[n - 1].second) v[n - 1].second = std::max(v[n - 1].second, c.second);
+            else v[n++] = c;
+        }
+        v.resize(n);
     }
 };
 

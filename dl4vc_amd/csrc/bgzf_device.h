@@ -1,0 +1,42 @@
+// Device side of the BGZF path (bgzf_kernels.hip) as its hosts see it (bgzf_capi.cpp, cand_capi.cpp): inflate a run of BGZF
+// blocks into one contiguous buffer, walk the BAM record chain in it, frame the records and hand them to the candidate
+// kernels as cand::ReadMeta without leaving the device.
+#pragma once
+
+#include "bgzf_inflate.h"
+#include "cand_device.h"
+
+namespace bz {
+
+// a stretch of the inflated buffer whose two ends are known record boundaries; slot_base: first of its bytes / 36 + 1 slots
+struct Segment {
+    uint64_t start, stop, slot_base;
+};
+
+// why a record was refused (the texts of bamn::frame_record and BamFile::next_block, same order as reason_text())
+enum Reason : uint32_t {
+    R_NONE = 0, R_BLOCK_SIZE, R_TRUNCATED, R_OVER_STOP, R_L_NAME, R_L_SEQ, R_NAME_EXCEEDS, R_CIGAR_EXCEEDS, R_SEQ_EXCEEDS,
+    R_AUX_TAG, R_AUX_NUL, R_AUX_ARRAY, R_AUX_ARRAY_TYPE, R_AUX_TYPE, R_AUX_VALUE, R_COUNT
+};
+const char* reason_text(uint32_t r);
+
+struct SubRange {
+    int32_t tid, start, end;
+};
+
+constexpr uint64_t NO_ERROR = ~0ull;   // else (offset of the record's block_size field) << 8 | Reason, the lowest offset wins
+
+// inflates n blocks of comp (device) into out (device); status[i] per block.  Blocks whose desc.status is set are skipped.
+hipError_t launch_inflate(const uint8_t* comp, const BlockDesc* tab, int64_t n, uint8_t* out, int32_t* status, hipStream_t stream);
+
+struct Framer;   // device buffers of the walk / frame / emit passes, grown on demand
+Framer* framer_create();
+void framer_destroy(Framer* f);
+// Walks segs over infl[0, infl_bytes), frames every record and lists it once for each subregion it overlaps (same tid,
+// pos < end, endpos > start).  *meta (device, owned by the framer) then holds *n_reads entries with off into infl; *n_records
+// = records walked; *err = NO_ERROR or the first refused record.  0 or -2 with msg.
+int frame_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Segment* segs, uint64_t n_segs, uint64_t n_slots,
+                  const SubRange* subs /* host */, uint32_t n_subs, hipStream_t stream,
+                  const cand::ReadMeta** meta, uint64_t* n_reads, uint64_t* n_records, uint64_t* err, const char** msg);
+
+}  // namespace bz

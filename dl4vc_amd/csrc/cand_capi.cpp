@@ -3,9 +3,18 @@
 // filter), frame and validate every record (bam_native.h::frame_record) and gather them into one pinned buffer; the device
 // does the rest (cand_kernels.hip).  A read overlapping two subregions is listed once for each, as the reference's per
 // subregion fetch counts it.  Every extern "C" body catches what it throws: a corrupt file is an error code, never an abort.
+//
+// With cg_set_inflate_device() the host does none of that: run_batch_device() takes the batch's byte ranges from the BAI bins,
+// reads their BGZF blocks as they are into pinned memory, and the device inflates them, walks the record chain, frames the
+// records and lists them per subregion (bgzf_kernels.hip); the same count / emit / filter kernels follow.
 #include "../../include/dl4vc_candgen.h"
 #include "bam_native.h"
+#include "bgzf_device.h"
 #include "cand_device.h"
+
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include <atomic>
 #include <chrono>
@@ -66,7 +75,19 @@ struct cg_handle {
     uint8_t* pinned = nullptr;
     size_t pinned_cap = 0;
     std::vector<cg_candidate> out;
+    // the device inflate path (cg_set_inflate_device)
+    bool inflate_device = false;
+    int fd = -1;
+    bz::Framer* framer = nullptr;
+    void *d_comp = nullptr, *d_tab = nullptr, *d_infl = nullptr, *d_bstatus = nullptr;
+    size_t d_comp_cap = 0, d_tab_cap = 0, d_infl_cap = 0, d_bstatus_cap = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    cg_inflate_stats ist{};
     ~cg_handle() {
+        if (fd >= 0) close(fd);
+        bz::framer_destroy(framer);
+        for (void* p : {d_comp, d_tab, d_infl, d_bstatus}) if (p) (void)hipFree(p);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         if (pinned) (void)hipHostFree(pinned);
         cand::workspace_destroy(ws);
         if (stream) (void)hipStreamDestroy(stream);
@@ -124,6 +145,47 @@ void decode(const cand::DevCand& c, cg_candidate& o) {
     char* one = c.kind == cand::KIND_INS ? o.ref : o.alt;
     for (int i = 0; i < n; ++i) seq[i] = base(i);
     one[0] = seq[0];
+}
+
+// the counting kernels over what upload() / upload_device() left in the workspace, and the batch's results
+int finish_batch(cg_handle* h, const cg_region* regions, int64_t b0, uint64_t n_reads, uint32_t n_subs, int64_t cov, cg_stats& st) {
+    const char* msg = nullptr;
+    const cand::DevCand* dc = nullptr;
+    const uint8_t* status = nullptr;
+    uint64_t n_out = 0, n_events = 0, n_unique = 0;
+    cand::BatchTimes bt{};
+    if (cand::run_batch(h->ws, n_reads, n_subs, cov, h->opt.max_len_indel_allele, h->opt.snp_min_freq, h->opt.indel_min_freq,
+                        h->stream, &dc, &n_out, &status, &n_events, &n_unique, &bt, &msg))
+        return fail(-2, "device: %s", msg);
+    st.device_ms += bt.device_ms;
+    st.reads += (int64_t)n_reads;
+    for (uint64_t r = 0; r < n_reads; ++r) {
+        const uint8_t v = status[r];
+        switch (v & 0xf) {
+            case cand::ST_NO_MD: ++st.reads_no_md; break;
+            case cand::ST_NO_PAIRS: ++st.reads_no_pairs; break;
+            case cand::ST_UNSUPPORTED: ++st.reads_unsupported; break;
+            case cand::ST_MALFORMED: ++st.reads_malformed; break;
+            default: break;
+        }
+        if (v & cand::ST_DEL_DROPPED) ++st.reads_deletions_dropped;
+    }
+    st.allele_events += (int64_t)n_events;
+    st.alleles += (int64_t)n_unique;
+    st.candidates += (int64_t)n_out;
+    ++st.batches;
+    const size_t o = h->out.size();
+    h->out.resize(o + n_out);
+    for (uint64_t i = 0; i < n_out; ++i) {
+        cg_candidate& c = h->out[o + i];
+        c.region = (int32_t)(b0 + dc[i].sub);
+        c.tid = regions[c.region].tid;
+        c.pos0 = dc[i].pos;
+        c.depth = dc[i].depth;
+        c.count = dc[i].count;
+        decode(dc[i], c);
+    }
+    return 0;
 }
 
 int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg_stats& st) {
@@ -198,42 +260,234 @@ int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg
     if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(-2, "device upload failed");
     const auto t2 = std::chrono::steady_clock::now();
     st.upload_ms += std::chrono::duration<double, std::milli>(t2 - t1).count();
-    const cand::DevCand* dc = nullptr;
-    const uint8_t* status = nullptr;
-    uint64_t n_out = 0, n_events = 0, n_unique = 0;
-    cand::BatchTimes bt{};
-    if (cand::run_batch(h->ws, n_reads, n_subs, cov, h->opt.max_len_indel_allele, h->opt.snp_min_freq, h->opt.indel_min_freq,
-                        h->stream, &dc, &n_out, &status, &n_events, &n_unique, &bt, &msg))
-        return fail(-2, "device: %s", msg);
-    st.device_ms += bt.device_ms;
-    st.reads += (int64_t)n_reads;
-    for (uint64_t r = 0; r < n_reads; ++r) {
-        const uint8_t v = status[r];
-        switch (v & 0xf) {
-            case cand::ST_NO_MD: ++st.reads_no_md; break;
-            case cand::ST_NO_PAIRS: ++st.reads_no_pairs; break;
-            case cand::ST_UNSUPPORTED: ++st.reads_unsupported; break;
-            case cand::ST_MALFORMED: ++st.reads_malformed; break;
-            default: break;
+    return finish_batch(h, regions, b0, n_reads, n_subs, cov, st);
+}
+
+// ---- the device inflate path ---------------------------------------------------------------------------------------------
+typedef bamn::Bai::Chunk Chunk;
+
+struct Plan {
+    std::vector<Chunk> ranges;                  // merged, sorted (virtual offsets)
+    std::vector<std::vector<uint64_t>> bounds;  // per range: walk boundaries inside it (virtual offsets), ends included
+};
+
+// The batch's byte ranges (the union over its subregions of the chunks of every overlapping bin, merged) and where a walk may
+// start inside them: every chunk begin and every distinct linear-index offset of the subregions' windows.
+void plan_ranges(const bamn::Bai& bai, const cg_region* regions, int64_t b0, int64_t b1, Plan& pl) {
+    std::vector<Chunk> chunks;
+    std::vector<uint64_t> starts;
+    for (int64_t i = b0; i < b1; ++i) {
+        const cg_region& rg = regions[i];
+        const size_t before = chunks.size();
+        bai.region_chunks(rg.tid, rg.start, rg.end, chunks);
+        if (chunks.size() == before) continue;
+        const auto& lin = bai.linear[rg.tid];
+        for (int64_t w = rg.start >> 14; w <= ((int64_t)rg.end - 1) >> 14 && w < (int64_t)lin.size(); ++w)
+            if (lin[w]) starts.push_back(lin[w]);
+    }
+    for (const Chunk& c : chunks) starts.push_back(c.first);
+    std::sort(starts.begin(), starts.end());
+    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
+    pl.ranges = chunks;
+    bamn::Bai::merge_chunks(pl.ranges);
+    pl.bounds.assign(pl.ranges.size(), {});
+    for (size_t r = 0; r < pl.ranges.size(); ++r) {
+        std::vector<uint64_t>& b = pl.bounds[r];
+        b.push_back(pl.ranges[r].first);
+        for (auto it = std::upper_bound(starts.begin(), starts.end(), pl.ranges[r].first); it != starts.end() && *it < pl.ranges[r].second; ++it)
+            b.push_back(*it);
+        b.push_back(pl.ranges[r].second);
+    }
+}
+
+struct HostBlock {
+    uint64_t coff;       // file offset of the block
+    uint64_t out_off;
+    uint32_t isize;
+};
+
+bool dev_ensure(void*& p, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return true;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    const size_t want = bytes + bytes / 4 + 4096;
+    if (hipMalloc(&p, want) != hipSuccess) return false;
+    cap = want;
+    return true;
+}
+
+double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+    return std::chrono::duration<double, std::milli>(b - a).count();
+}
+
+int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg_stats& st) {
+    const uint32_t n_subs = (uint32_t)(b1 - b0);
+    const auto t0 = std::chrono::steady_clock::now();
+    Plan pl;
+    plan_ranges(h->bai, regions, b0, b1, pl);
+    struct stat sb;
+    if (fstat(h->fd, &sb) != 0) return fail(-3, "BGZF: cannot stat %s", h->bam_path.c_str());
+    const uint64_t file_size = (uint64_t)sb.st_size;
+    // the file spans: from the block a range begins in to the end of the block it ends in (read 64 KiB past that block's start,
+    // which holds it whole)
+    const size_t n_ranges = pl.ranges.size();
+    std::vector<uint64_t> span_at(n_ranges + 1, 0), span_lo(n_ranges), span_hi(n_ranges);
+    for (size_t r = 0; r < n_ranges; ++r) {
+        const uint64_t cb = pl.ranges[r].first >> 16, ce = pl.ranges[r].second >> 16, ue = pl.ranges[r].second & 0xffff;
+        if (cb >= file_size || ce > file_size || (ue > 0 && ce >= file_size))
+            return fail(-3, "BGZF: truncated file (the index points at offset %llu, past its end at %llu)", (unsigned long long)std::max(cb, ce),
+                        (unsigned long long)file_size);
+        span_lo[r] = cb;
+        span_hi[r] = ue > 0 ? std::min<uint64_t>(file_size, ce + 65536) : ce;
+        span_at[r + 1] = span_at[r] + (span_hi[r] - span_lo[r]);
+    }
+    const uint64_t comp_bytes = span_at[n_ranges];
+    if (hipSetDevice(h->opt.device) != hipSuccess) return fail(-2, "hipSetDevice(%d) failed", h->opt.device);
+    if (comp_bytes + 1 > h->pinned_cap) {
+        if (h->pinned) (void)hipHostFree(h->pinned);
+        h->pinned = nullptr; h->pinned_cap = 0;
+        const size_t want = comp_bytes + comp_bytes / 4 + 4096;
+        if (hipHostMalloc((void**)&h->pinned, want, hipHostMallocDefault) != hipSuccess) return fail(-2, "hipHostMalloc(%zu) failed", want);
+        h->pinned_cap = want;
+    }
+    std::vector<bz::BlockDesc> tab;
+    std::vector<HostBlock> blocks;                 // in out_off order
+    std::vector<size_t> first_block(n_ranges + 1, 0);
+    uint64_t infl_bytes = 0;
+    for (size_t r = 0; r < n_ranges; ++r) {
+        uint64_t got = 0;
+        const uint64_t want = span_hi[r] - span_lo[r];
+        while (got < want) {
+            const ssize_t g = pread(h->fd, h->pinned + span_at[r] + got, want - got, (off_t)(span_lo[r] + got));
+            if (g <= 0) return fail(-3, "BGZF: cannot read %s at offset %llu", h->bam_path.c_str(), (unsigned long long)(span_lo[r] + got));
+            got += (uint64_t)g;
         }
-        if (v & cand::ST_DEL_DROPPED) ++st.reads_deletions_dropped;
+        const uint64_t ce = pl.ranges[r].second >> 16, ue = pl.ranges[r].second & 0xffff;
+        uint64_t c = span_lo[r];
+        first_block[r] = blocks.size();
+        while (c < ce || (c == ce && ue > 0)) {
+            bz::BlockDesc d;
+            uint32_t bsize = 0;
+            if (bz::parse_block(h->pinned, span_at[r + 1], span_at[r] + (c - span_lo[r]), d, &bsize) != BZ_OK)
+                return fail(-3, "BGZF: not a BGZF block, or a truncated BGZF block (block at file offset %llu)", (unsigned long long)c);
+            d.out_off = infl_bytes;
+            tab.push_back(d);
+            blocks.push_back(HostBlock{c, infl_bytes, d.isize});
+            infl_bytes += d.isize;
+            c += bsize;
+        }
     }
-    st.allele_events += (int64_t)n_events;
-    st.alleles += (int64_t)n_unique;
-    st.candidates += (int64_t)n_out;
-    ++st.batches;
-    const size_t o = h->out.size();
-    h->out.resize(o + n_out);
-    for (uint64_t i = 0; i < n_out; ++i) {
-        cg_candidate& c = h->out[o + i];
-        c.region = (int32_t)(b0 + dc[i].sub);
-        c.tid = regions[c.region].tid;
-        c.pos0 = dc[i].pos;
-        c.depth = dc[i].depth;
-        c.count = dc[i].count;
-        decode(dc[i], c);
+    first_block[n_ranges] = blocks.size();
+    // virtual offset -> offset in the inflated buffer, within range r's run of blocks
+    auto locate = [&](size_t r, uint64_t voff, uint64_t& at) {
+        const uint64_t coff = voff >> 16, u = voff & 0xffff;
+        const auto lo = blocks.begin() + first_block[r], hi = blocks.begin() + first_block[r + 1];
+        const auto it = std::lower_bound(lo, hi, coff, [](const HostBlock& b, uint64_t c) { return b.coff < c; });
+        if (it != hi && it->coff == coff) {
+            if (u > it->isize) return false;
+            at = it->out_off + u;
+            return true;
+        }
+        if (it == hi && u == 0 && lo != hi) {                 // the offset just past the run's last block
+            at = (hi - 1)->out_off + (hi - 1)->isize;
+            return true;
+        }
+        return false;
+    };
+    std::vector<bz::Segment> segs;
+    uint64_t n_slots = 0;
+    for (size_t r = 0; r < n_ranges; ++r) {
+        std::vector<uint64_t> at;
+        for (const uint64_t v : pl.bounds[r]) {
+            uint64_t a;
+            if (!locate(r, v, a))
+                return fail(-3, "BGZF: the index offset %llu does not point into a block of its chunk", (unsigned long long)v);
+            at.push_back(a);
+        }
+        const uint64_t lo = at.front(), hi = at.back();
+        std::sort(at.begin(), at.end());
+        at.erase(std::unique(at.begin(), at.end()), at.end());
+        for (size_t k = 0; k + 1 < at.size(); ++k) {
+            if (at[k] < lo || at[k + 1] > hi) continue;
+            segs.push_back(bz::Segment{at[k], at[k + 1], n_slots});
+            n_slots += (at[k + 1] - at[k]) / 36 + 1;
+        }
     }
-    return 0;
+    const auto t1 = std::chrono::steady_clock::now();
+    st.host_frame_ms += ms_between(t0, t1);
+    h->ist.read_ms += ms_between(t0, t1);
+    h->ist.blocks += (int64_t)blocks.size();
+    h->ist.compressed_bytes += (int64_t)comp_bytes;
+    h->ist.inflated_bytes += (int64_t)infl_bytes;
+    // the device
+    if (!h->stream && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(-2, "hipStreamCreate failed");
+    if (!h->ws && !(h->ws = cand::workspace_create())) return fail(-2, "cannot create the device workspace");
+    if (!h->framer) h->framer = bz::framer_create();
+    for (hipEvent_t& e : h->ev)
+        if (!e && hipEventCreate(&e) != hipSuccess) return fail(-2, "hipEventCreate failed");
+    if (!dev_ensure(h->d_comp, h->d_comp_cap, comp_bytes + 16) || !dev_ensure(h->d_tab, h->d_tab_cap, (tab.size() + 1) * sizeof(bz::BlockDesc)) ||
+        !dev_ensure(h->d_infl, h->d_infl_cap, infl_bytes + 16) || !dev_ensure(h->d_bstatus, h->d_bstatus_cap, (tab.size() + 1) * sizeof(int32_t)))
+        return fail(-2, "hipMalloc failed for a batch of %llu compressed and %llu inflated bytes", (unsigned long long)comp_bytes,
+                    (unsigned long long)infl_bytes);
+#define CG_TRY(x)                                                                                 \
+    do {                                                                                          \
+        const hipError_t e_ = (x);                                                                \
+        if (e_ != hipSuccess) return fail(-2, "device inflate: %s: %s", #x, hipGetErrorString(e_)); \
+    } while (0)
+    if (comp_bytes) CG_TRY(hipMemcpyAsync(h->d_comp, h->pinned, comp_bytes, hipMemcpyHostToDevice, h->stream));
+    if (!tab.empty()) CG_TRY(hipMemcpyAsync(h->d_tab, tab.data(), tab.size() * sizeof(bz::BlockDesc), hipMemcpyHostToDevice, h->stream));
+    CG_TRY(hipStreamSynchronize(h->stream));
+    const auto t2 = std::chrono::steady_clock::now();
+    st.upload_ms += ms_between(t1, t2);
+    CG_TRY(hipEventRecord(h->ev[0], h->stream));
+    CG_TRY(bz::launch_inflate((const uint8_t*)h->d_comp, (const bz::BlockDesc*)h->d_tab, (int64_t)tab.size(), (uint8_t*)h->d_infl,
+                              (int32_t*)h->d_bstatus, h->stream));
+    CG_TRY(hipEventRecord(h->ev[1], h->stream));
+    std::vector<int32_t> bstatus(tab.size());
+    if (!tab.empty()) CG_TRY(hipMemcpyAsync(bstatus.data(), h->d_bstatus, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    CG_TRY(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < tab.size(); ++i)
+        if (bstatus[i] != BZ_OK)
+            return fail(-3, "BGZF block fails its CRC / size check (%s, block at file offset %llu)", bz_status_text(bstatus[i]),
+                        (unsigned long long)blocks[i].coff);
+    std::vector<bz::SubRange> sr(n_subs);
+    for (uint32_t s = 0; s < n_subs; ++s) sr[s] = bz::SubRange{regions[b0 + s].tid, regions[b0 + s].start, regions[b0 + s].end};
+    const cand::ReadMeta* meta_dev = nullptr;
+    uint64_t n_reads = 0, n_records = 0, err = bz::NO_ERROR;
+    const char* msg = nullptr;
+    CG_TRY(hipEventRecord(h->ev[2], h->stream));
+    if (bz::frame_records(h->framer, (const uint8_t*)h->d_infl, infl_bytes, segs.data(), segs.size(), n_slots, sr.data(), n_subs, h->stream,
+                          &meta_dev, &n_reads, &n_records, &err, &msg))
+        return fail(-2, "device framing: %s", msg);
+    if (err != bz::NO_ERROR) {
+        const uint64_t off = err >> 8;
+        auto it = std::upper_bound(blocks.begin(), blocks.end(), off, [](uint64_t o, const HostBlock& b) { return o < b.out_off; });
+        // (blocks of no bytes share an out_off: the last block at or before off holds it)
+        const HostBlock& b = *(it == blocks.begin() ? it : it - 1);
+        return fail(-3, "%s (record at virtual offset %lld)", bz::reason_text((uint32_t)(err & 0xff)),
+                    (long long)((b.coff << 16) | std::min<uint64_t>(off - b.out_off, 0xffff)));
+    }
+    CG_TRY(hipEventRecord(h->ev[3], h->stream));
+    CG_TRY(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    CG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    h->ist.inflate_ms += ms;
+    CG_TRY(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    h->ist.walk_frame_ms += ms;
+    h->ist.records += (int64_t)n_records;
+#undef CG_TRY
+    std::vector<cand::SubDesc> subs(n_subs);
+    int64_t cov = 0;
+    for (uint32_t s = 0; s < n_subs; ++s) {
+        const cg_region& rg = regions[b0 + s];
+        subs[s].start = rg.start;
+        subs[s].end = rg.end;
+        subs[s].cov_base = cov;
+        cov += (int64_t)rg.end - rg.start + 2;
+    }
+    if (cand::upload_device(h->ws, (const uint8_t*)h->d_infl, meta_dev, subs.data(), n_subs, cov, h->stream, &msg))
+        return fail(-2, "device upload: %s", msg);
+    return finish_batch(h, regions, b0, n_reads, n_subs, cov, st);
 }
 
 }  // namespace
@@ -272,6 +526,7 @@ int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg
         if (!h || !out || !n_out || (n_regions > 0 && !regions)) return fail(-1, "cg_run: null argument");
         const auto t0 = std::chrono::steady_clock::now();
         cg_stats st{};
+        h->ist = cg_inflate_stats{};
         h->out.clear();
         for (int64_t i = 0; i < n_regions; ++i) {
             const cg_region& r = regions[i];
@@ -285,7 +540,7 @@ int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg
                 len += (int64_t)regions[b1].end - regions[b1].start;
                 ++b1;
             }
-            const int rc = run_batch(h, regions, b0, b1, st);
+            const int rc = h->inflate_device ? run_batch_device(h, regions, b0, b1, st) : run_batch(h, regions, b0, b1, st);
             if (rc) return rc;
             b0 = b1;
         }
@@ -298,6 +553,51 @@ int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg
         return fail(-4, "cg_run: %s", e.what());
     } catch (...) {
         return fail(-4, "cg_run: unknown exception");
+    }
+}
+
+int cg_set_inflate_device(cg_handle_t* h, int on) {
+    try {
+        if (!h) return fail(-1, "cg_set_inflate_device: null handle");
+        if (on && !h->have_bai)
+            return fail(-1, "inflate on the device needs the BAI index of %s: its bins give the byte ranges to read", h->bam_path.c_str());
+        if (on && h->fd < 0 && (h->fd = open(h->bam_path.c_str(), O_RDONLY)) < 0) return fail(-3, "cannot open %s", h->bam_path.c_str());
+        h->inflate_device = on != 0;
+        return 0;
+    } catch (...) {
+        return fail(-4, "cg_set_inflate_device: unknown exception");
+    }
+}
+
+int cg_get_inflate_stats(const cg_handle_t* h, cg_inflate_stats* out) {
+    if (!h || !out) return fail(-1, "cg_get_inflate_stats: null argument");
+    *out = h->ist;
+    return 0;
+}
+
+int cg_debug_ranges(const cg_handle_t* h, int32_t tid, int32_t start, int32_t end, uint64_t* ranges, int64_t cap_ranges, int64_t* n_ranges,
+                    uint64_t* bounds, int64_t cap_bounds, int64_t* n_bounds) {
+    try {
+        if (!h || !n_ranges || !n_bounds) return fail(-1, "cg_debug_ranges: null argument");
+        if (!h->have_bai) return fail(-1, "cg_debug_ranges: the handle has no BAI index");
+        const cg_region rg{tid, start, end};
+        Plan pl;
+        plan_ranges(h->bai, &rg, 0, 1, pl);
+        *n_ranges = (int64_t)pl.ranges.size();
+        int64_t nb = 0;
+        for (size_t r = 0; r < pl.ranges.size(); ++r) {
+            if (ranges && (int64_t)r < cap_ranges) { ranges[2 * r] = pl.ranges[r].first; ranges[2 * r + 1] = pl.ranges[r].second; }
+            for (const uint64_t v : pl.bounds[r]) {
+                if (bounds && nb < cap_bounds) bounds[nb] = v;
+                ++nb;
+            }
+        }
+        *n_bounds = nb;
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(-4, "cg_debug_ranges: %s", e.what());
+    } catch (...) {
+        return fail(-4, "cg_debug_ranges: unknown exception");
     }
 }
 

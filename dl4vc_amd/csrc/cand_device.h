@@ -55,6 +55,10 @@ void workspace_destroy(Workspace* ws);
 // with msg set.  out / n_out: survivors in a host array owned by the workspace; status: one byte per read, host.
 int upload(Workspace* ws, const uint8_t* recs, uint64_t rec_bytes, const ReadMeta* meta, uint64_t n_reads,
            const SubDesc* subs, uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg);
+// The same for records and meta that are already on the device (the BGZF path, bgzf_device.h): they are used in place and must
+// stay valid until run_batch() returns.
+int upload_device(Workspace* ws, const uint8_t* recs_dev, const ReadMeta* meta_dev, const SubDesc* subs, uint32_t n_subs,
+                  int64_t cov_len, hipStream_t stream, const char** msg);
 int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len, int max_len, double snp_min, double indel_min,
               hipStream_t stream, const DevCand** out, uint64_t* n_out, const uint8_t** status, uint64_t* n_events,
               uint64_t* n_unique, BatchTimes* t, const char** msg);

@@ -395,6 +395,8 @@ struct Workspace {
         snp_unique, snp_counts, indel_unique, indel_counts, scalars, cands, temp;
     std::vector<uint8_t> h_status;
     std::vector<DevCand> h_cands;
+    const uint8_t* recs_p = nullptr;      // the batch's records and their meta: ws->recs / ws->meta after upload(), the
+    const ReadMeta* meta_p = nullptr;     // caller's device buffers after upload_device()
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
@@ -426,6 +428,19 @@ int upload(Workspace* ws, const uint8_t* recs, uint64_t rec_bytes, const ReadMet
     if (n_reads) CG_CHECK(hipMemcpyAsync(ws->meta.p, meta, n_reads * sizeof(ReadMeta), hipMemcpyHostToDevice, stream));
     CG_CHECK(hipMemcpyAsync(ws->subs.p, subs, n_subs * sizeof(SubDesc), hipMemcpyHostToDevice, stream));
     CG_CHECK(hipMemsetAsync(ws->cov.p, 0, (size_t)cov_len * sizeof(int), stream));
+    ws->recs_p = ws->recs.as<const uint8_t>();
+    ws->meta_p = ws->meta.as<const ReadMeta>();
+    return 0;
+}
+
+int upload_device(Workspace* ws, const uint8_t* recs_dev, const ReadMeta* meta_dev, const SubDesc* subs, uint32_t n_subs,
+                  int64_t cov_len, hipStream_t stream, const char** msg) {
+    CG_CHECK(ws->subs.ensure((n_subs + 1) * sizeof(SubDesc)));
+    CG_CHECK(ws->cov.ensure((size_t)(cov_len + 1) * sizeof(int)));
+    CG_CHECK(hipMemcpyAsync(ws->subs.p, subs, n_subs * sizeof(SubDesc), hipMemcpyHostToDevice, stream));
+    CG_CHECK(hipMemsetAsync(ws->cov.p, 0, (size_t)cov_len * sizeof(int), stream));
+    ws->recs_p = recs_dev;
+    ws->meta_p = meta_dev;
     return 0;
 }
 
@@ -450,7 +465,7 @@ int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len,
     const int TB = 256;
     const unsigned grid = (unsigned)((n_reads + TB - 1) / TB);
     if (n_reads) {
-        hipLaunchKernelGGL(count_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs.as<const uint8_t>(), ws->meta.as<const ReadMeta>(),
+        hipLaunchKernelGGL(count_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs_p, ws->meta_p,
                            n_reads, ws->subs.as<const SubDesc>(), max_len, ws->cov.as<int>(), ws->n_snp.as<uint32_t>(),
                            ws->n_indel.as<uint32_t>(), ws->status.as<uint8_t>());
         CG_CHECK(hipGetLastError());
@@ -489,7 +504,7 @@ int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len,
     CG_CHECK(ws->indel_counts.ensure((ni + 1) * 4));
     CG_CHECK(ws->cands.ensure((ns + ni + 1) * sizeof(DevCand)));
     if (ns + ni > 0) {
-        hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs.as<const uint8_t>(), ws->meta.as<const ReadMeta>(),
+        hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs_p, ws->meta_p,
                            n_reads, ws->subs.as<const SubDesc>(), max_len, ws->snp_off.as<const uint32_t>(),
                            ws->indel_off.as<const uint32_t>(), ws->n_snp.as<const uint32_t>(), ws->n_indel.as<const uint32_t>(),
                            ws->snp_keys.as<uint64_t>(), ws->indel_keys.as<IndelKey>());

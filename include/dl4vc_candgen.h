@@ -63,12 +63,35 @@ typedef struct {
     double total_ms;
 } cg_stats;
 
+/* What the device inflate path did in the last cg_run (all zero when it is off). */
+typedef struct {
+    int64_t blocks;                /* BGZF blocks inflated (a block two ranges touch counts for each) */
+    int64_t compressed_bytes;      /* read from the file and uploaded as they are */
+    int64_t inflated_bytes;
+    int64_t records;               /* BAM records walked and framed on the device */
+    double read_ms;                /* host: index ranges, file to pinned memory, header / trailer checks */
+    double inflate_ms;             /* device events around the inflate kernel */
+    double walk_frame_ms;          /* device events around the walk, frame, scan and emit passes */
+} cg_inflate_stats;
+
 int cg_open(const char* bam_path, const char* bai_path /* NULL or "": linear scan */, const cg_options* opt,
             cg_handle_t** out);
 /* Runs every region (internally in batches).  On success *out points at n_out candidates owned by the handle, valid until the
  * next cg_run or cg_close; their order is unspecified. */
 int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg_candidate** out, int64_t* n_out,
            cg_stats* stats);
+/* on != 0: the BGZF blocks of each batch go to the device compressed, and inflate, record walk and framing run there
+ * (dl4vc_bgzf.h has the decoder's statuses); the host reads the file and the index and does no per-record work.  Needs the BAI
+ * (its bins give the byte ranges): fails with a message on a handle opened without one.  Limits: ISIZE <= 65536 per block (the
+ * format's), one inflated buffer per batch sized from the block trailers.  Off by default; cg_stats.host_frame_ms keeps its
+ * meaning (host wall time in front of the device work). */
+int cg_set_inflate_device(cg_handle_t* h, int on);
+int cg_get_inflate_stats(const cg_handle_t* h, cg_inflate_stats* out);
+/* For tests: the byte ranges and walk boundaries the device path would use for one region, as BGZF virtual offsets.
+ * ranges: n_ranges pairs [begin, end), merged and sorted; bounds: every walk boundary (range ends included), sorted.  At most
+ * cap_* entries are written; the counts are always the full ones.  Reads the index only. */
+int cg_debug_ranges(const cg_handle_t* h, int32_t tid, int32_t start, int32_t end, uint64_t* ranges, int64_t cap_ranges,
+                    int64_t* n_ranges, uint64_t* bounds, int64_t cap_bounds, int64_t* n_bounds);
 /* Reference names and lengths of the BAM header. */
 int32_t cg_n_refs(const cg_handle_t* h);
 const char* cg_ref_name(const cg_handle_t* h, int32_t tid);

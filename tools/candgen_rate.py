@@ -5,6 +5,10 @@ host's inflate-and-frame time against the device time (per-stage device times co
 ``rocprofv3 --kernel-trace --stats`` run of this tool).
 
     python tools/candgen_rate.py --bam /tmp/cg_rate.bam [--reads 2000000 --length 10000000] [--out profiles/x.json]
+        [--inflate-device gpu] [--chunk_size 1000]
+
+``--inflate-device gpu`` measures the device inflate path (the line then carries its read / inflate / walk-and-frame times);
+``--chunk_size`` other than 1000 changes the subregions, and with them the candidates at their boundaries: a timing line only.
 """
 import argparse
 import json
@@ -64,6 +68,8 @@ def main():
     ap.add_argument("--threads", type=int, default=None)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--inflate-device", dest="inflate_device", choices=["gpu"], default=None)
+    ap.add_argument("--chunk_size", type=int, default=1000)
     a = ap.parse_args()
     if not os.path.isfile(a.bam + ".bai"):
         t = time.time()
@@ -73,7 +79,8 @@ def main():
     runs = []
     for k in range(a.repeats):
         t = time.perf_counter()
-        st = generate(a.bam, a.bam + ".vcf", threads=a.threads, snp_min_freq=0.075, indel_min_freq=0.02, keep_multialleles=True)
+        st = generate(a.bam, a.bam + ".vcf", threads=a.threads, snp_min_freq=0.075, indel_min_freq=0.02, keep_multialleles=True,
+                      chunk_size=a.chunk_size, inflate_device=a.inflate_device)
         st["wall_s"] = time.perf_counter() - t
         runs.append(st)
     best = min(runs, key=lambda r: r["wall_s"])
@@ -81,7 +88,14 @@ def main():
            "reads_per_s": round(best["reads"] / best["wall_s"]), "host_frame_ms": round(best["host_frame_ms"], 1),
            "upload_ms": round(best["upload_ms"], 1), "device_ms": round(best["device_ms"], 1),
            "native_total_ms": round(best["total_ms"], 1), "candidates": best["candidates"], "alleles": best["alleles"],
-           "allele_events": best["allele_events"], "batches": best["batches"], "threads": a.threads or min(16, len(os.sched_getaffinity(0)))}
+           "allele_events": best["allele_events"], "batches": best["batches"], "threads": a.threads or min(16, len(os.sched_getaffinity(0))),
+           "chunk_size": a.chunk_size, "inflate_device": a.inflate_device}
+    for k in ("inflate_blocks", "inflate_compressed_bytes", "inflate_inflated_bytes", "inflate_records", "inflate_read_ms", "inflate_ms",
+              "inflate_walk_frame_ms"):
+        if k in best:
+            res[k] = round(best[k], 1) if isinstance(best[k], float) else best[k]
+    if best.get("inflate_ms"):
+        res["inflate_MB_per_s"] = round(best["inflate_inflated_bytes"] / 1e6 / (best["inflate_ms"] / 1e3))
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -45,14 +45,18 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    p = build_parser()
+    # (added here, after build_parser(): its table of flags stays the reference tool's)
+    p.add_argument("--inflate-device", dest="inflate_device", choices=["gpu"], default=None,
+                   help="Inflate the BAM's BGZF blocks and frame its records on the GPU instead of in host threads (needs INPUT.bai)")
+    args = p.parse_args(argv)
     print(args)
     logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.DEBUG if args.debug else logging.INFO)
     from dl4vc_amd.candidates import generate
     stats = generate(args.input, args.output, contigs=args.contigs, bedfile=args.bedfile, keep_contig_chr=args.keep_contig_chr,
                      chunk_size=args.chunk_size, threads=args.threads, snp_min_freq=args.snp_min_freq,
                      indel_min_freq=args.indel_min_freq, keep_multialleles=args.keep_multialleles,
-                     max_len_indel_allele=args.max_len_indel_allele)
+                     max_len_indel_allele=args.max_len_indel_allele, inflate_device=args.inflate_device)
     logging.info("Generated final VCF file at %s.", args.output)
     print("summary " + json.dumps(stats, sort_keys=True))
     return 0
