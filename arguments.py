@@ -73,6 +73,8 @@ _EXTRA = [
     ("--test_bam", "str", None, "inference straight from a coordinate-sorted BAM (with --test_fasta and --sample_vcf, the candidate "
                                 "VCF): pileups are encoded and scored on the GPU and no candidates.hdf is written; replaces --test_file"),
     ("--test_fasta", "str", None, "reference FASTA of --test_bam"),
+    ("--inflate-device", "str", None, "gpu: with --test_bam, the pileup encoder inflates the BAM's BGZF blocks and frames its records "
+                                      "on the GPU as well (needs the .bai; same scored VCF)"),
     ("--conv-algo", "str", "auto", "fp32 conv form: auto (Winograd F(2,3) where every layer after the first has "
                                    "dilation 2), direct, or winograd"),
 ]

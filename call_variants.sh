@@ -10,7 +10,8 @@
 # -d (direct; needs -i and -r, one GPU): no candidates.hdf at all -- main.py --test_bam encodes the pileups on the GPU, assembles
 # and scores them there.  The scored VCF is byte-identical to the two-step path's.  Without -d nothing changes.
 # -z: the candidate generator inflates the BAM's BGZF blocks and frames its records on the GPU (--inflate-device gpu; needs
-# BAM.bai); candidates.vcf is the same.
+# BAM.bai); candidates.vcf is the same.  With -d, main.py --test_bam gets --inflate-device gpu as well, so no stage inflates or
+# frames a record on the host; the scored VCF is the same.
 set -e
 usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z]"; exit 1; }
 GPUS=1
@@ -27,7 +28,7 @@ while getopts "m:o:g:i:r:b:p:dzh" opt; do
     b) BED=$OPTARG ;;       # candidate generation only
     p) PROCS=$OPTARG ;;
     d) DIRECT=1 ;;          # score straight from the BAM (main.py --test_bam)
-    z) INFLATE=gpu ;;       # candidate generation only: BGZF inflate and record framing on the GPU
+    z) INFLATE=gpu ;;       # BGZF inflate and record framing on the GPU: candidate generation, and with -d the pileup encoder
     *) usage ;;
   esac
 done
@@ -43,7 +44,7 @@ if [ ! -f "$OUTDIR/candidates.hdf" ] && [ ! -f "$OUTDIR/candidates.vcf" ] && [ -
 fi
 if [ "$DIRECT" = 1 ]; then
   [ -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ] && [ -n "$REFERENCE" ] || { echo "-d needs -i BAM -r REFERENCE (and $OUTDIR/candidates.vcf, made from the BAM when absent)"; exit 1; }
-  TEST_INPUT=(--test_bam "$BAM" --test_fasta "$REFERENCE")
+  TEST_INPUT=(--test_bam "$BAM" --test_fasta "$REFERENCE" ${INFLATE:+--inflate-device "$INFLATE"})
 else
   TEST_INPUT=(--test_file "$OUTDIR/candidates.hdf")
 fi

@@ -4,14 +4,10 @@
 #pragma once
 
 #include "bgzf_inflate.h"
+#include "bgzf_plan.h"
 #include "cand_device.h"
 
 namespace bz {
-
-// a stretch of the inflated buffer whose two ends are known record boundaries; slot_base: first of its bytes / 36 + 1 slots
-struct Segment {
-    uint64_t start, stop, slot_base;
-};
 
 // why a record was refused (the texts of bamn::frame_record and BamFile::next_block, same order as reason_text())
 enum Reason : uint32_t {
@@ -32,6 +28,12 @@ hipError_t launch_inflate(const uint8_t* comp, const BlockDesc* tab, int64_t n, 
 struct Framer;   // device buffers of the walk / frame / emit passes, grown on demand
 Framer* framer_create();
 void framer_destroy(Framer* f);
+constexpr uint64_t NO_RECORD = ~0ull;   // a record slot the walk left empty
+// Walks segs (bgzf_plan.h) over infl[0, infl_bytes): *rec_off (device, owned by the framer, n_slots entries) holds the offset of
+// every record's block_size field, NO_RECORD in the slots left over; *n_records = records walked; *err = NO_ERROR or the first
+// refused record.  0 or -2 with msg.  The first pass of frame_records(), and of the pileup encoder's framing.
+int walk_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Segment* segs /* host */, uint64_t n_segs, uint64_t n_slots,
+                 hipStream_t stream, const uint64_t** rec_off, uint64_t* n_records, uint64_t* err, const char** msg);
 // Walks segs over infl[0, infl_bytes), frames every record and lists it once for each subregion it overlaps (same tid,
 // pos < end, endpos > start).  *meta (device, owned by the framer) then holds *n_reads entries with off into infl; *n_records
 // = records walked; *err = NO_ERROR or the first refused record.  0 or -2 with msg.

@@ -19,7 +19,6 @@ namespace bz {
 namespace {
 
 constexpr int WAVE = 64;
-constexpr uint64_t NO_RECORD = ~0ull;
 
 // The wave's writes into the LDS window.  All 64 lanes call each method with the same arguments (the decode is uniform).  A match
 // byte k comes from out[o - dist + k % dist], which lies before o: no lane reads what another writes in the same copy, also when
@@ -328,24 +327,16 @@ void framer_destroy(Framer* f) { delete f; }
         if (e_ != hipSuccess) { *msg = hipGetErrorString(e_); return -2; } \
     } while (0)
 
-int frame_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Segment* segs, uint64_t n_segs, uint64_t n_slots,
-                  const SubRange* subs, uint32_t n_subs, hipStream_t stream, const cand::ReadMeta** meta, uint64_t* n_reads,
-                  uint64_t* n_records, uint64_t* err, const char** msg) {
-    *meta = nullptr; *n_reads = 0; *n_records = 0; *err = NO_ERROR;
+int walk_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Segment* segs, uint64_t n_segs, uint64_t n_slots,
+                 hipStream_t stream, const uint64_t** rec_off, uint64_t* n_records, uint64_t* err, const char** msg) {
+    *rec_off = nullptr; *n_records = 0; *err = NO_ERROR;
     if (n_segs == 0 || n_slots == 0) return 0;
     if (n_slots >= (1ull << 31)) { *msg = "too many record slots in one batch"; return -2; }
-    const int TB = 256;
     BZ_CHECK(f->segs.ensure(n_segs * sizeof(Segment)));
-    BZ_CHECK(f->subs.ensure((n_subs + 1) * sizeof(SubRange)));
     BZ_CHECK(f->rec_off.ensure(n_slots * 8));
-    BZ_CHECK(f->count.ensure((n_slots + 1) * 4));
-    BZ_CHECK(f->first.ensure((n_slots + 1) * 4));
-    BZ_CHECK(f->md_off.ensure(n_slots * 4));
-    BZ_CHECK(f->md_len.ensure(n_slots * 4));
     BZ_CHECK(f->scalars.ensure(2 * 8));
     unsigned long long* sc = f->scalars.as<unsigned long long>();   // [0] records walked, [1] first refused record
     BZ_CHECK(hipMemcpyAsync(f->segs.p, segs, n_segs * sizeof(Segment), hipMemcpyHostToDevice, stream));
-    BZ_CHECK(hipMemcpyAsync(f->subs.p, subs, n_subs * sizeof(SubRange), hipMemcpyHostToDevice, stream));
     BZ_CHECK(hipMemsetAsync(f->rec_off.p, 0xff, n_slots * 8, stream));
     BZ_CHECK(hipMemsetAsync(sc, 0, 8, stream));
     BZ_CHECK(hipMemsetAsync(sc + 1, 0xff, 8, stream));
@@ -356,7 +347,28 @@ int frame_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Seg
     BZ_CHECK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, stream));
     BZ_CHECK(hipStreamSynchronize(stream));
     *n_records = h[0];
-    if (h[1] != NO_ERROR) { *err = h[1]; return 0; }     // (a refused walk leaves slots unset: nothing is framed from them)
+    *err = h[1];                                           // (a refused walk leaves slots unset: nothing is framed from them)
+    *rec_off = f->rec_off.as<const uint64_t>();
+    return 0;
+}
+
+int frame_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Segment* segs, uint64_t n_segs, uint64_t n_slots,
+                  const SubRange* subs, uint32_t n_subs, hipStream_t stream, const cand::ReadMeta** meta, uint64_t* n_reads,
+                  uint64_t* n_records, uint64_t* err, const char** msg) {
+    *meta = nullptr; *n_reads = 0; *n_records = 0; *err = NO_ERROR;
+    if (n_segs == 0 || n_slots == 0) return 0;
+    const int TB = 256;
+    const uint64_t* walked = nullptr;
+    if (const int rc = walk_records(f, infl, infl_bytes, segs, n_segs, n_slots, stream, &walked, n_records, err, msg)) return rc;
+    if (*err != NO_ERROR) return 0;
+    BZ_CHECK(f->subs.ensure((n_subs + 1) * sizeof(SubRange)));
+    BZ_CHECK(f->count.ensure((n_slots + 1) * 4));
+    BZ_CHECK(f->first.ensure((n_slots + 1) * 4));
+    BZ_CHECK(f->md_off.ensure(n_slots * 4));
+    BZ_CHECK(f->md_len.ensure(n_slots * 4));
+    unsigned long long* sc = f->scalars.as<unsigned long long>();
+    unsigned long long h[2];
+    BZ_CHECK(hipMemcpyAsync(f->subs.p, subs, n_subs * sizeof(SubRange), hipMemcpyHostToDevice, stream));
     const unsigned grid = (unsigned)((n_slots + TB - 1) / TB);
     hipLaunchKernelGGL(bam_frame_kernel, dim3(grid), dim3(TB), 0, stream, infl, f->rec_off.as<const uint64_t>(), n_slots,
                        f->subs.as<const SubRange>(), n_subs, f->count.as<uint32_t>(), f->md_off.as<int32_t>(), f->md_len.as<int32_t>(),

@@ -264,48 +264,6 @@ int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg
 }
 
 // ---- the device inflate path ---------------------------------------------------------------------------------------------
-typedef bamn::Bai::Chunk Chunk;
-
-struct Plan {
-    std::vector<Chunk> ranges;                  // merged, sorted (virtual offsets)
-    std::vector<std::vector<uint64_t>> bounds;  // per range: walk boundaries inside it (virtual offsets), ends included
-};
-
-// The batch's byte ranges (the union over its subregions of the chunks of every overlapping bin, merged) and where a walk may
-// start inside them: every chunk begin and every distinct linear-index offset of the subregions' windows.
-void plan_ranges(const bamn::Bai& bai, const cg_region* regions, int64_t b0, int64_t b1, Plan& pl) {
-    std::vector<Chunk> chunks;
-    std::vector<uint64_t> starts;
-    for (int64_t i = b0; i < b1; ++i) {
-        const cg_region& rg = regions[i];
-        const size_t before = chunks.size();
-        bai.region_chunks(rg.tid, rg.start, rg.end, chunks);
-        if (chunks.size() == before) continue;
-        const auto& lin = bai.linear[rg.tid];
-        for (int64_t w = rg.start >> 14; w <= ((int64_t)rg.end - 1) >> 14 && w < (int64_t)lin.size(); ++w)
-            if (lin[w]) starts.push_back(lin[w]);
-    }
-    for (const Chunk& c : chunks) starts.push_back(c.first);
-    std::sort(starts.begin(), starts.end());
-    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
-    pl.ranges = chunks;
-    bamn::Bai::merge_chunks(pl.ranges);
-    pl.bounds.assign(pl.ranges.size(), {});
-    for (size_t r = 0; r < pl.ranges.size(); ++r) {
-        std::vector<uint64_t>& b = pl.bounds[r];
-        b.push_back(pl.ranges[r].first);
-        for (auto it = std::upper_bound(starts.begin(), starts.end(), pl.ranges[r].first); it != starts.end() && *it < pl.ranges[r].second; ++it)
-            b.push_back(*it);
-        b.push_back(pl.ranges[r].second);
-    }
-}
-
-struct HostBlock {
-    uint64_t coff;       // file offset of the block
-    uint64_t out_off;
-    uint32_t isize;
-};
-
 bool dev_ensure(void*& p, size_t& cap, size_t bytes) {
     if (bytes <= cap) return true;
     if (p) (void)hipFree(p);
@@ -323,25 +281,13 @@ double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_c
 int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg_stats& st) {
     const uint32_t n_subs = (uint32_t)(b1 - b0);
     const auto t0 = std::chrono::steady_clock::now();
-    Plan pl;
-    plan_ranges(h->bai, regions, b0, b1, pl);
+    bz::BlockPlan pl;
+    std::string perr;
+    pl.plan(h->bai, regions + b0, b1 - b0);
     struct stat sb;
     if (fstat(h->fd, &sb) != 0) return fail(-3, "BGZF: cannot stat %s", h->bam_path.c_str());
-    const uint64_t file_size = (uint64_t)sb.st_size;
-    // the file spans: from the block a range begins in to the end of the block it ends in (read 64 KiB past that block's start,
-    // which holds it whole)
-    const size_t n_ranges = pl.ranges.size();
-    std::vector<uint64_t> span_at(n_ranges + 1, 0), span_lo(n_ranges), span_hi(n_ranges);
-    for (size_t r = 0; r < n_ranges; ++r) {
-        const uint64_t cb = pl.ranges[r].first >> 16, ce = pl.ranges[r].second >> 16, ue = pl.ranges[r].second & 0xffff;
-        if (cb >= file_size || ce > file_size || (ue > 0 && ce >= file_size))
-            return fail(-3, "BGZF: truncated file (the index points at offset %llu, past its end at %llu)", (unsigned long long)std::max(cb, ce),
-                        (unsigned long long)file_size);
-        span_lo[r] = cb;
-        span_hi[r] = ue > 0 ? std::min<uint64_t>(file_size, ce + 65536) : ce;
-        span_at[r + 1] = span_at[r] + (span_hi[r] - span_lo[r]);
-    }
-    const uint64_t comp_bytes = span_at[n_ranges];
+    if (!pl.spans((uint64_t)sb.st_size, perr)) return fail(-3, "%s", perr.c_str());
+    const uint64_t comp_bytes = pl.comp_bytes;
     if (hipSetDevice(h->opt.device) != hipSuccess) return fail(-2, "hipSetDevice(%d) failed", h->opt.device);
     if (comp_bytes + 1 > h->pinned_cap) {
         if (h->pinned) (void)hipHostFree(h->pinned);
@@ -350,69 +296,11 @@ int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t
         if (hipHostMalloc((void**)&h->pinned, want, hipHostMallocDefault) != hipSuccess) return fail(-2, "hipHostMalloc(%zu) failed", want);
         h->pinned_cap = want;
     }
-    std::vector<bz::BlockDesc> tab;
-    std::vector<HostBlock> blocks;                 // in out_off order
-    std::vector<size_t> first_block(n_ranges + 1, 0);
-    uint64_t infl_bytes = 0;
-    for (size_t r = 0; r < n_ranges; ++r) {
-        uint64_t got = 0;
-        const uint64_t want = span_hi[r] - span_lo[r];
-        while (got < want) {
-            const ssize_t g = pread(h->fd, h->pinned + span_at[r] + got, want - got, (off_t)(span_lo[r] + got));
-            if (g <= 0) return fail(-3, "BGZF: cannot read %s at offset %llu", h->bam_path.c_str(), (unsigned long long)(span_lo[r] + got));
-            got += (uint64_t)g;
-        }
-        const uint64_t ce = pl.ranges[r].second >> 16, ue = pl.ranges[r].second & 0xffff;
-        uint64_t c = span_lo[r];
-        first_block[r] = blocks.size();
-        while (c < ce || (c == ce && ue > 0)) {
-            bz::BlockDesc d;
-            uint32_t bsize = 0;
-            if (bz::parse_block(h->pinned, span_at[r + 1], span_at[r] + (c - span_lo[r]), d, &bsize) != BZ_OK)
-                return fail(-3, "BGZF: not a BGZF block, or a truncated BGZF block (block at file offset %llu)", (unsigned long long)c);
-            d.out_off = infl_bytes;
-            tab.push_back(d);
-            blocks.push_back(HostBlock{c, infl_bytes, d.isize});
-            infl_bytes += d.isize;
-            c += bsize;
-        }
-    }
-    first_block[n_ranges] = blocks.size();
-    // virtual offset -> offset in the inflated buffer, within range r's run of blocks
-    auto locate = [&](size_t r, uint64_t voff, uint64_t& at) {
-        const uint64_t coff = voff >> 16, u = voff & 0xffff;
-        const auto lo = blocks.begin() + first_block[r], hi = blocks.begin() + first_block[r + 1];
-        const auto it = std::lower_bound(lo, hi, coff, [](const HostBlock& b, uint64_t c) { return b.coff < c; });
-        if (it != hi && it->coff == coff) {
-            if (u > it->isize) return false;
-            at = it->out_off + u;
-            return true;
-        }
-        if (it == hi && u == 0 && lo != hi) {                 // the offset just past the run's last block
-            at = (hi - 1)->out_off + (hi - 1)->isize;
-            return true;
-        }
-        return false;
-    };
-    std::vector<bz::Segment> segs;
-    uint64_t n_slots = 0;
-    for (size_t r = 0; r < n_ranges; ++r) {
-        std::vector<uint64_t> at;
-        for (const uint64_t v : pl.bounds[r]) {
-            uint64_t a;
-            if (!locate(r, v, a))
-                return fail(-3, "BGZF: the index offset %llu does not point into a block of its chunk", (unsigned long long)v);
-            at.push_back(a);
-        }
-        const uint64_t lo = at.front(), hi = at.back();
-        std::sort(at.begin(), at.end());
-        at.erase(std::unique(at.begin(), at.end()), at.end());
-        for (size_t k = 0; k + 1 < at.size(); ++k) {
-            if (at[k] < lo || at[k + 1] > hi) continue;
-            segs.push_back(bz::Segment{at[k], at[k + 1], n_slots});
-            n_slots += (at[k + 1] - at[k]) / 36 + 1;
-        }
-    }
+    if (!pl.read(h->fd, h->bam_path, h->pinned, perr) || !pl.segments(perr)) return fail(-3, "%s", perr.c_str());
+    const std::vector<bz::BlockDesc>& tab = pl.tab;
+    const std::vector<bz::HostBlock>& blocks = pl.blocks;
+    const std::vector<bz::Segment>& segs = pl.segs;
+    const uint64_t infl_bytes = pl.infl_bytes, n_slots = pl.n_slots;
     const auto t1 = std::chrono::steady_clock::now();
     st.host_frame_ms += ms_between(t0, t1);
     h->ist.read_ms += ms_between(t0, t1);
@@ -460,12 +348,7 @@ int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t
                           &meta_dev, &n_reads, &n_records, &err, &msg))
         return fail(-2, "device framing: %s", msg);
     if (err != bz::NO_ERROR) {
-        const uint64_t off = err >> 8;
-        auto it = std::upper_bound(blocks.begin(), blocks.end(), off, [](uint64_t o, const HostBlock& b) { return o < b.out_off; });
-        // (blocks of no bytes share an out_off: the last block at or before off holds it)
-        const HostBlock& b = *(it == blocks.begin() ? it : it - 1);
-        return fail(-3, "%s (record at virtual offset %lld)", bz::reason_text((uint32_t)(err & 0xff)),
-                    (long long)((b.coff << 16) | std::min<uint64_t>(off - b.out_off, 0xffff)));
+        return fail(-3, "%s (record at virtual offset %lld)", bz::reason_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
     }
     CG_TRY(hipEventRecord(h->ev[3], h->stream));
     CG_TRY(hipStreamSynchronize(h->stream));
@@ -581,8 +464,8 @@ int cg_debug_ranges(const cg_handle_t* h, int32_t tid, int32_t start, int32_t en
         if (!h || !n_ranges || !n_bounds) return fail(-1, "cg_debug_ranges: null argument");
         if (!h->have_bai) return fail(-1, "cg_debug_ranges: the handle has no BAI index");
         const cg_region rg{tid, start, end};
-        Plan pl;
-        plan_ranges(h->bai, &rg, 0, 1, pl);
+        bz::BlockPlan pl;
+        pl.plan(h->bai, &rg, 1);
         *n_ranges = (int64_t)pl.ranges.size();
         int64_t nb = 0;
         for (size_t r = 0; r < pl.ranges.size(); ++r) {

@@ -4,13 +4,25 @@
 // the run's reference slice as tokens.  The records of a batch of locations go to the device in one pinned buffer; the
 // kernels (pileup_kernels.hip) do the rest.  Every extern "C" body catches what it throws: a corrupt file is an error code,
 // never an abort.
+//
+// With pg_set_inflate_device() the host does none of the per-record work: encode_all_device() takes every run's byte ranges from
+// the BAI bins (bgzf_plan.h), reads their BGZF blocks as they are into pinned memory, and the device inflates them group of runs
+// by group of runs, walks the record chain (bgzf_kernels.hip), frames the records and finds each location's records
+// (pileup_frame_kernels.hip); the same resolve / encode kernels follow, reading the records where they lie in the inflated buffer.
 #include "../../include/dl4vc_pileup_gpu.h"
 #include "bam_native.h"
+#include "bgzf_device.h"
 #include "fasta_native.h"
 #include "pileup_device.h"
+#include "pileup_fetch.h"
+
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdarg>
 #include <memory>
 #include <mutex>
@@ -20,14 +32,10 @@
 
 namespace {
 
-std::string g_err;
-
-constexpr int FLAG_MASK = 0x4 | 0x100 | 0x200 | 0x400;   // unmapped, secondary, QC fail, duplicate (dan_pileup.cpp)
-constexpr int FREVERSE = 0x10;
 constexpr int BATCH_LOCS = 512;                          // locations per device batch
 constexpr int64_t RUN_GAP = 4096, RUN_SPAN = 1 << 20;    // a run: locations closer than RUN_GAP, at most RUN_SPAN bases
 constexpr int MAX_THREADS = 8;
-constexpr int64_t MAX_NREF = 1 << 29;                     // a longer reference span is a corrupt record (no contig is longer)
+constexpr uint64_t DEFAULT_INFLATED = 256ull << 20;      // inflated bytes of one group of runs (pg_set_inflate_device)
 
 // the converter's token table (dan_pileup.cpp::Tables); REF_UNKNOWN for a character outside it
 struct RefTokens {
@@ -47,19 +55,12 @@ struct Entry {
     int32_t pre;          // -1: encode on the device; 0 / 2: decided here
 };
 
-struct Run {
+struct Run : pgh::RunRecs {  // (the records a worker fills: bytes, recs, max_nref, nres, sorted, err)
     int64_t e0, e1;       // entries [e0, e1) of the sorted list
     int32_t tid;
     int64_t s0, stop;     // union of the locations' fetch windows
     const char* contig;
-    // filled by a worker
-    std::vector<uint8_t> bytes;
-    std::vector<pg::Rec> recs;   // off relative to bytes, res relative to the run
-    std::vector<uint8_t> ref;    // tokens of [s0, stop)
-    int64_t max_nref = 0;
-    int64_t nres = 0;
-    bool sorted = true;
-    std::string err;
+    std::vector<uint8_t> ref;    // tokens of [s0, stop), filled by a worker
 };
 
 // One host framing thread's file handles, kept for the encoder's life (a FASTA without .fai is scanned once, at pg_open).
@@ -108,7 +109,24 @@ struct pg_encoder {
     uint8_t* d_meta = nullptr; size_t c_meta = 0;
     uint8_t* h_meta = nullptr; size_t hc_meta = 0;
     hipEvent_t ev_meta = nullptr; bool meta_busy = false;
+    pg_stats st{};                                    // stages of the last encode call
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // the device inflate path (pg_set_inflate_device)
+    bool inflate_device = false;
+    uint64_t max_inflated = DEFAULT_INFLATED;
+    int fd = -1;
+    bz::Framer* walker = nullptr;
+    pg::Framing* framing = nullptr;
+    uint8_t* d_comp = nullptr; size_t c_comp = 0;
+    bz::BlockDesc* d_tab = nullptr; size_t c_tab = 0;
+    uint8_t* d_infl = nullptr; size_t c_infl = 0;
+    int32_t* d_bstatus = nullptr; size_t c_bstatus = 0;
     ~pg_encoder() {
+        if (fd >= 0) close(fd);
+        bz::framer_destroy(walker);
+        pg::framing_destroy(framing);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (void* p : {(void*)d_comp, (void*)d_tab, (void*)d_infl, (void*)d_bstatus}) if (p) (void)hipFree(p);
         if (ev_meta) { if (meta_busy) (void)hipEventSynchronize(ev_meta); (void)hipEventDestroy(ev_meta); }
         for (void* p : {(void*)d_buf, (void*)d_recs, (void*)d_locs, (void*)d_ref, (void*)d_qpos, (void*)d_indel, (void*)d_isdel,
                         (void*)d_small, (void*)d_planes, (void*)d_meta})
@@ -128,7 +146,7 @@ int fail(pg_encoder* h, int code, const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
     va_end(ap);
-    (h ? h->err : g_err) = buf;
+    (h ? h->err : pgh::g_err) = buf;
     return code;
 }
 
@@ -150,20 +168,8 @@ int get_tid(const bamn::BamFile& b, const std::string& name) {
     return it == b.tid_of.end() ? -1 : it->second;
 }
 
-struct Cigar { int64_t nref = 0, nquery = 0; bool has_ref = false, skip = false; };
-// nullptr, or why the record's reference span cannot be trusted (it sizes the device's resolution arrays)
-const char* walk_cigar(const uint8_t* b, const bamn::RecordFrame& fr, Cigar& c) {
-    c = Cigar{};
-    for (int i = 0; i < fr.n_cig; ++i) {
-        uint32_t v;
-        memcpy(&v, b + fr.cigar_off + 4 * i, 4);
-        const int op = v & 0xf;
-        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) { c.nref += (int64_t)(v >> 4); c.has_ref = true; }
-        if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) c.nquery += (int64_t)(v >> 4);
-        if (op == 3) c.skip = true;
-    }
-    if (c.nref > MAX_NREF || (int64_t)fr.pos + c.nref > INT32_MAX) return "corrupt BAM record (CIGAR reference length)";
-    return nullptr;
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // A BAM without a BAI: the linear index (the smallest virtual offset of a record overlapping each 16 kbp window) from one scan.
@@ -177,14 +183,13 @@ int build_linear_index(pg_encoder* h) {
         const int got = bam.next_block(blk);
         if (got == 0) break;
         if (got < 0) return fail(h, -3, "%s (record at virtual offset %lld)", bam.err.c_str(), (long long)voff);
-        bamn::RecordFrame fr;
-        if (const char* why = bamn::frame_record(blk.data(), blk.size(), fr))
-            return fail(h, -3, "%s (record at virtual offset %lld)", why, (long long)voff);
+        pg::frame::Framed fr;
+        if (const uint32_t why = pg::frame::frame_record(blk.data(), blk.size(), fr))
+            return fail(h, -3, "%s (record at virtual offset %lld)", pg::frame::why_text(why), (long long)voff);
         if (fr.tid < 0 || fr.tid >= (int)bam.refs.size() || fr.pos < 0) continue;
-        Cigar c;
-        if (const char* why = walk_cigar(blk.data(), fr, c))
-            return fail(h, -3, "%s (record at virtual offset %lld)", why, (long long)voff);
-        const int64_t end = (int64_t)fr.pos + std::max<int64_t>(c.nref, 1);
+        if (const uint32_t why = pg::frame::walk_cigar(blk.data(), fr))
+            return fail(h, -3, "%s (record at virtual offset %lld)", pg::frame::why_text(why), (long long)voff);
+        const int64_t end = (int64_t)fr.pos + std::max<int64_t>(fr.nref, 1);
         auto& lin = h->bai.linear[fr.tid];
         const size_t w1 = (size_t)((end - 1) >> 14);
         if (lin.size() <= w1) lin.resize(w1 + 1, 0);
@@ -194,70 +199,29 @@ int build_linear_index(pg_encoder* h) {
     return 0;
 }
 
-// The records of one run: tid == run.tid, pos < stop and pos + max(nref, 1) > s0 (the window reader of dan_pileup.cpp),
-// plus the run's reference tokens.
-void fetch_run(pg_encoder* h, bamn::BamFile& bam, fastan::Fasta& fasta, std::vector<uint8_t>& blk, Run& run) {
+// the run's reference tokens
+void fetch_ref(fastan::Fasta& fasta, Run& run) {
     std::string seq;
     fasta.fetch(run.contig, run.s0, run.stop, seq);
     run.ref.resize((size_t)(run.stop - run.s0));
     for (size_t i = 0; i < run.ref.size(); ++i) run.ref[i] = i < seq.size() ? RT.tok[(uint8_t)seq[i]] : 5;
-    const uint64_t at = h->bai.linear_offset(run.tid, run.s0);
-    if (at == 0) return;
-    if (!bam.r.seek((int64_t)at)) { run.err = "BGZF: " + bam.r.err; return; }
-    int32_t last_pos = -1;
-    for (;;) {
-        const int64_t voff = bam.r.tell();
-        const int got = bam.next_block(blk);
-        if (got == 0) return;
-        if (got < 0) { run.err = bam.err + " (record at virtual offset " + std::to_string(voff) + ")"; return; }
-        bamn::RecordFrame fr;
-        if (const char* why = bamn::frame_record(blk.data(), blk.size(), fr)) {
-            run.err = std::string(why) + " (record at virtual offset " + std::to_string(voff) + ")";
-            return;
-        }
-        if (fr.tid != run.tid) {
-            if (fr.tid < 0 || fr.tid > run.tid) return;
-            continue;
-        }
-        if (fr.pos >= run.stop) return;
-        Cigar c;
-        if (const char* why = walk_cigar(blk.data(), fr, c)) {
-            run.err = std::string(why) + " (record at virtual offset " + std::to_string(voff) + ")";
-            return;
-        }
-        if ((int64_t)fr.pos + std::max<int64_t>(c.nref, 1) <= run.s0) continue;
-        if (fr.pos < last_pos) run.sorted = false;
-        last_pos = fr.pos;
-        pg::Rec m{};
-        m.off = run.bytes.size();
-        m.pos = fr.pos;
-        m.end = (int32_t)(fr.pos + c.nref);
-        m.res = (int32_t)std::min<int64_t>(run.nres, INT32_MAX);   // (a batch past INT32_MAX positions is refused below)
-        m.l_seq = fr.l_seq;
-        m.cigar_off = fr.cigar_off; m.seq_off = fr.seq_off; m.qual_off = fr.qual_off;
-        m.n_cig = fr.n_cig; m.l_name = fr.l_name;
-        m.bits = ((fr.flag & FLAG_MASK) ? 0 : pg::R_FLAG_OK) | (c.has_ref ? pg::R_HAS_REF : 0) | (c.skip ? pg::R_SKIP : 0) |
-                 ((fr.flag & FREVERSE) ? pg::R_REVERSE : 0) | (c.nquery > (int64_t)fr.l_seq ? pg::R_SHORT_SEQ : 0);
-        run.nres += c.nref;
-        run.max_nref = std::max(run.max_nref, c.nref);
-        run.recs.push_back(m);
-        run.bytes.insert(run.bytes.end(), blk.begin(), blk.end());
-        run.bytes.resize((run.bytes.size() + 3) & ~(size_t)3);
-    }
 }
 
-// Encodes sorted entries [b0, b1) on h->stream.  Planes go to (reads, qual, strand) at slot = entry.idx when `by_index`,
-// else at slot = position in the batch; ref / num / status of the batch are left in h->d_small.
-int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& es, int64_t b0, int64_t b1, uint8_t* reads,
-                 uint8_t* qual, uint8_t* strand, bool by_index) {
-    const pe_options& o = h->opt;
-    const int w = o.window_size, W = 2 * w + 1;
-    std::vector<Run> runs;
+// The records of one run (pileup_fetch.h), plus the run's reference tokens.
+void fetch_run(pg_encoder* h, bamn::BamFile& bam, fastan::Fasta& fasta, std::vector<uint8_t>& blk, Run& run) {
+    fetch_ref(fasta, run);
+    pgh::fetch_records(h->bai, bam, blk, run.tid, run.s0, run.stop, run);
+}
+
+// The runs of sorted entries [b0, b1), appended to runs: locations closer than RUN_GAP, at most RUN_SPAN bases, one contig name.
+void build_runs(const pe_options& o, const char* const* contigs, const std::vector<Entry>& es, int64_t b0, int64_t b1, std::vector<Run>& runs) {
+    const int w = o.window_size;
+    const size_t first = runs.size();
     for (int64_t i = b0; i < b1; ++i) {
         const Entry& e = es[i];
         if (e.pre >= 0) continue;
         const int64_t s0 = std::max<int64_t>((int64_t)e.pos1 - (w + 2), 0), stop = (int64_t)e.pos1 + w + 3;
-        if (!runs.empty()) {
+        if (runs.size() > first) {
             Run& r = runs.back();
             if (r.e1 == i && r.tid == e.tid && strcmp(r.contig, contigs[e.idx]) == 0 && s0 <= r.stop + RUN_GAP && stop - r.s0 <= RUN_SPAN) {
                 r.e1 = i + 1;
@@ -269,37 +233,65 @@ int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& 
         r.e0 = i; r.e1 = i + 1; r.tid = e.tid; r.s0 = s0; r.stop = stop; r.contig = contigs[e.idx];
         runs.push_back(std::move(r));
     }
+}
+
+// one worker per thread, file handles opened once per encoder; 0 or an error
+int ensure_workers(pg_encoder* h, int nt) {
+    while ((int)h->workers.size() < nt) {
+        auto wk = std::make_unique<Worker>();
+        if (!wk->bam.open(h->bam_path)) return fail(h, -3, "%s", wk->bam.err.c_str());
+        wk->fasta.f = fopen(h->fasta_path.c_str(), "rb");
+        if (!wk->fasta.f) return fail(h, -3, "cannot open %s", h->fasta_path.c_str());
+        wk->fasta.index = h->fasta.index;
+        h->workers.push_back(std::move(wk));
+    }
+    return 0;
+}
+
+// job(worker, r) for every r in [r0, r1) on the worker threads; "" or what a job threw
+template <class Job>
+std::string on_workers(pg_encoder* h, int nt, size_t r0, size_t r1, Job job) {
+    std::atomic<size_t> next{r0};
+    std::mutex mu;
+    std::string job_err;
+    auto worker = [&](Worker* wk) {
+        try {
+            for (;;) {
+                const size_t r = next.fetch_add(1);
+                if (r >= r1) return;
+                job(wk, r);
+            }
+        } catch (const std::exception& ex) {
+            std::lock_guard<std::mutex> lk(mu);
+            job_err = std::string("host framing: ") + ex.what();
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt && r1 > r0; ++t) pool.emplace_back(worker, h->workers[t].get());
+    if (r1 > r0) worker(h->workers[0].get());
+    for (auto& t : pool) t.join();
+    return job_err;
+}
+
+int thread_count(size_t jobs) {
+    return std::max(1, std::min<int>({MAX_THREADS, (int)std::max(1u, std::thread::hardware_concurrency()), (int)jobs}));
+}
+
+// Encodes sorted entries [b0, b1) on h->stream.  Planes go to (reads, qual, strand) at slot = entry.idx when `by_index`,
+// else at slot = position in the batch; ref / num / status of the batch are left in h->d_small.
+int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& es, int64_t b0, int64_t b1, uint8_t* reads,
+                 uint8_t* qual, uint8_t* strand, bool by_index) {
+    const pe_options& o = h->opt;
+    const int w = o.window_size, W = 2 * w + 1;
+    const auto t_host = std::chrono::steady_clock::now();
+    std::vector<Run> runs;
+    build_runs(o, contigs, es, b0, b1, runs);
     // host framing, one run at a time per worker; the workers' file handles are opened once per encoder
     {
-        const int nt = std::max(1, std::min<int>({MAX_THREADS, (int)std::max(1u, std::thread::hardware_concurrency()), (int)runs.size()}));
-        while ((int)h->workers.size() < nt) {
-            auto wk = std::make_unique<Worker>();
-            if (!wk->bam.open(h->bam_path)) return fail(h, -3, "%s", wk->bam.err.c_str());
-            wk->fasta.f = fopen(h->fasta_path.c_str(), "rb");
-            if (!wk->fasta.f) return fail(h, -3, "cannot open %s", h->fasta_path.c_str());
-            wk->fasta.index = h->fasta.index;
-            h->workers.push_back(std::move(wk));
-        }
-        std::atomic<size_t> next{0};
-        std::mutex mu;
-        std::string open_err;
-        auto worker = [&](Worker* wk) {
-            try {
-                for (;;) {
-                    const size_t r = next.fetch_add(1);
-                    if (r >= runs.size()) return;
-                    fetch_run(h, wk->bam, wk->fasta, wk->blk, runs[r]);
-                }
-            } catch (const std::exception& ex) {
-                std::lock_guard<std::mutex> lk(mu);
-                open_err = std::string("host framing: ") + ex.what();
-            }
-        };
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nt && !runs.empty(); ++t) pool.emplace_back(worker, h->workers[t].get());
-        if (!runs.empty()) worker(h->workers[0].get());
-        for (auto& t : pool) t.join();
-        if (!open_err.empty()) return fail(h, -3, "%s", open_err.c_str());
+        const int nt = thread_count(runs.size());
+        if (const int rc = ensure_workers(h, nt)) return rc;
+        const std::string job_err = on_workers(h, nt, 0, runs.size(), [&](Worker* wk, size_t r) { fetch_run(h, wk->bam, wk->fasta, wk->blk, runs[r]); });
+        if (!job_err.empty()) return fail(h, -3, "%s", job_err.c_str());
         for (auto& r : runs) if (!r.err.empty()) return fail(h, -3, "%s", r.err.c_str());
     }
     // gather
@@ -346,6 +338,9 @@ int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& 
         res += r.nres;
         std::vector<uint8_t>().swap(r.bytes);
     }
+    h->st.host_frame_ms += ms_since(t_host);
+    h->st.host_records += (int64_t)recs.size();
+    h->st.records += (int64_t)recs.size();
     // device
     hipStream_t s = h->stream;
     const size_t small = (size_t)nb * (W + 4 + 1);
@@ -359,19 +354,281 @@ int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& 
     int8_t* d_status = (int8_t*)(d_num + nb);
     hipError_t rc = hipSuccess;
     auto ok = [&](hipError_t r) { if (rc == hipSuccess) rc = r; };
+    ok(hipEventRecord(h->ev[0], s));
     if (bytes) ok(hipMemcpyAsync(h->d_buf, h->h_buf, bytes, hipMemcpyHostToDevice, s));
     if (!recs.empty()) ok(hipMemcpyAsync(h->d_recs, recs.data(), recs.size() * sizeof(pg::Rec), hipMemcpyHostToDevice, s));
     ok(hipMemcpyAsync(h->d_locs, locs.data(), locs.size() * sizeof(pg::Loc), hipMemcpyHostToDevice, s));
     if (!ref.empty()) ok(hipMemcpyAsync(h->d_ref, ref.data(), ref.size(), hipMemcpyHostToDevice, s));
+    ok(hipEventRecord(h->ev[1], s));
     ok(pg::launch_resolve(h->d_buf, h->d_recs, (int32_t)recs.size(), h->d_qpos, h->d_indel, h->d_isdel, s));
     const pg::Params P{w, W, o.max_reads, o.max_insert_length, o.max_insert_length_variant};
     ok(pg::launch_encode(h->d_buf, h->d_recs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, reads, qual,
                          strand, d_ref_small, d_num, d_status, s));
+    ok(hipEventRecord(h->ev[2], s));
     // (the pageable copies above read the host vectors before this returns)
     ok(hipStreamSynchronize(s));
+    float ms = 0.f;
+    if (rc == hipSuccess && hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->st.upload_ms += ms;
+    if (rc == hipSuccess && hipEventElapsedTime(&ms, h->ev[1], h->ev[2]) == hipSuccess) h->st.encode_ms += ms;
     if (rc != hipSuccess) return fail(h, -2, "device: %s", hipGetErrorString(rc));
     return 0;
 }
+
+// Copies ref / num / status (and, unless the planes are the caller's device arrays, the planes) of the piece [i0, i1) of the
+// sorted entries, which the encode kernel left at the piece's slots, to the caller's arrays.
+int copy_back(pg_encoder* h, const std::vector<Entry>& es, int64_t i0, int64_t i1, uint8_t* reads, uint8_t* qual, uint8_t* strand,
+              uint8_t* ref_out, int32_t* num_out, int8_t* status_out, bool device_planes, std::vector<uint8_t>& small) {
+    const int W = 2 * h->opt.window_size + 1;
+    const size_t plane = (size_t)h->opt.max_reads * W;
+    const int64_t nb = i1 - i0;
+    const size_t small_bytes = (((size_t)nb * W + 3) & ~(size_t)3) + (size_t)nb * 5;
+    small.resize(small_bytes);
+    if (hipMemcpy(small.data(), h->d_small, small_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, -2, "hipMemcpy failed");
+    const int32_t* num = (const int32_t*)(small.data() + (((size_t)nb * W + 3) & ~(size_t)3));
+    const int8_t* st = (const int8_t*)(num + nb);
+    if (!device_planes) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (int c = 0; c < 3; ++c)
+            if (hipMemcpy(h->h_planes + c * plane * BATCH_LOCS, h->d_planes + c * plane * BATCH_LOCS, plane * nb, hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(h, -2, "hipMemcpy failed");
+        h->st.copy_back_ms += ms_since(t0);
+    }
+    for (int64_t i = 0; i < nb; ++i) {
+        const int64_t j = es[i0 + i].idx;
+        status_out[j] = st[i];
+        num_out[j] = num[i];
+        memcpy(ref_out + (size_t)j * W, small.data() + (size_t)i * W, W);
+        if (!device_planes)
+            for (int c = 0; c < 3; ++c) {
+                uint8_t* dst = c == 0 ? reads : c == 1 ? qual : strand;
+                memcpy(dst + (size_t)j * plane, h->h_planes + c * plane * BATCH_LOCS + (size_t)i * plane, plane);
+            }
+    }
+    return 0;
+}
+
+// ---- the device inflate path (pg_set_inflate_device) ------------------------------------------------------------------------
+#define PG_TRY(x)                                                                                     \
+    do {                                                                                              \
+        const hipError_t e_ = (x);                                                                    \
+        if (e_ != hipSuccess) return fail(h, -2, "device inflate: %s: %s", #x, hipGetErrorString(e_)); \
+    } while (0)
+
+// Encodes the piece [i0, i1) of the sorted entries (at most BATCH_LOCS) from the group's records on the device; runs
+// [ra, rb) are the group's runs that lie in the piece (g0: the group's first run).
+int encode_piece(pg_encoder* h, const std::vector<Entry>& es, int64_t i0, int64_t i1, const std::vector<Run>& runs, size_t ra, size_t rb,
+                 size_t g0, size_t g1, const pg::Rec* d_grecs, const pg::RunOut* d_run_out, uint8_t* reads, uint8_t* qual, uint8_t* strand,
+                 bool by_index) {
+    const pe_options& o = h->opt;
+    const int w = o.window_size, W = 2 * w + 1;
+    const int64_t nb = i1 - i0;
+    std::vector<pg::Loc> locs((size_t)nb);
+    std::vector<int32_t> loc_run((size_t)nb, -1);
+    std::vector<uint8_t> ref;
+    for (int64_t i = 0; i < nb; ++i) {
+        const Entry& e = es[i0 + i];
+        pg::Loc& L = locs[i];
+        L = pg::Loc{};
+        L.pre = e.pre >= 0 ? e.pre : 2;                    // (an entry of no run of this piece has its status already)
+        L.slot = by_index ? e.idx : i;
+    }
+    for (size_t r = ra; r < rb; ++r) {
+        const Run& run = runs[r];
+        const int64_t ref0 = (int64_t)ref.size();
+        ref.insert(ref.end(), run.ref.begin(), run.ref.end());
+        for (int64_t i = run.e0; i < run.e1; ++i) {
+            const Entry& e = es[i];
+            pg::Loc& L = locs[i - i0];
+            const int64_t s0 = std::max<int64_t>((int64_t)e.pos1 - (w + 2), 0), stop = (int64_t)e.pos1 + w + 3;
+            L.s0 = (int32_t)s0; L.stop = (int32_t)stop; L.ci = (int32_t)(e.pos1 - 1 - s0);
+            L.ref = ref0 + (s0 - run.s0);
+            L.pre = e.pre;
+            loc_run[i - i0] = (int32_t)(r - g0);
+        }
+    }
+    hipStream_t s = h->stream;
+    const size_t small = (size_t)nb * (W + 4 + 1);
+    if (!grow(h->d_locs, h->c_locs, locs.size() + 1) || !grow(h->d_ref, h->c_ref, ref.size() + 1) || !grow(h->d_small, h->c_small, small + 16))
+        return fail(h, -2, "hipMalloc failed (piece of %lld locations)", (long long)nb);
+    uint8_t* d_ref_small = h->d_small;
+    int32_t* d_num = (int32_t*)(h->d_small + (((size_t)nb * W + 3) & ~(size_t)3));
+    int8_t* d_status = (int8_t*)(d_num + nb);
+    // device events between the stages, as on the host path: upload | location search | encode
+    PG_TRY(hipEventRecord(h->ev[0], s));
+    PG_TRY(hipMemcpyAsync(h->d_locs, locs.data(), locs.size() * sizeof(pg::Loc), hipMemcpyHostToDevice, s));
+    if (!ref.empty()) PG_TRY(hipMemcpyAsync(h->d_ref, ref.data(), ref.size(), hipMemcpyHostToDevice, s));
+    const char* msg = nullptr;
+    if (g1 > g0 && pg::locate(h->framing, d_grecs, d_run_out, (int32_t)(g1 - g0), loc_run.data(), h->d_locs, (int32_t)nb, s, &msg, h->ev[1]))
+        return fail(h, -2, "device framing: %s", msg);
+    if (g1 == g0) PG_TRY(hipEventRecord(h->ev[1], s));
+    PG_TRY(hipEventRecord(h->ev[2], s));
+    const pg::Params P{w, W, o.max_reads, o.max_insert_length, o.max_insert_length_variant};
+    PG_TRY(pg::launch_encode(h->d_infl, d_grecs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, reads, qual, strand,
+                             d_ref_small, d_num, d_status, s));
+    PG_TRY(hipEventRecord(h->ev[3], s));
+    PG_TRY(hipStreamSynchronize(s));                       // (the pageable copies above have read the host vectors)
+    float ms = 0.f;
+    PG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    h->st.upload_ms += ms;
+    PG_TRY(hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
+    h->st.frame_ms += ms;
+    PG_TRY(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    h->st.encode_ms += ms;
+    return 0;
+}
+
+struct Outs {
+    uint8_t *reads, *qual, *strand, *ref;
+    int32_t* num;
+    int8_t* status;
+    bool device_planes;
+};
+
+// the pieces of [e0, e1): cut where the BATCH_LOCS batches of the sorted list are cut
+int encode_pieces(pg_encoder* h, const std::vector<Entry>& es, int64_t e0, int64_t e1, const std::vector<Run>& runs, size_t g0, size_t g1,
+                  const pg::Rec* d_grecs, const pg::RunOut* d_run_out, const Outs& out, std::vector<uint8_t>& small) {
+    const size_t plane = (size_t)h->opt.max_reads * (2 * h->opt.window_size + 1);
+    size_t r = g0;
+    for (int64_t i0 = e0; i0 < e1;) {
+        const int64_t i1 = std::min<int64_t>(e1, (i0 / BATCH_LOCS + 1) * BATCH_LOCS);
+        const size_t ra = r;
+        while (r < g1 && runs[r].e1 <= i1) ++r;
+        uint8_t* R = out.device_planes ? out.reads : h->d_planes;
+        uint8_t* Q = out.device_planes ? out.qual : h->d_planes + plane * BATCH_LOCS;
+        uint8_t* S = out.device_planes ? out.strand : h->d_planes + 2 * plane * BATCH_LOCS;
+        int rc = encode_piece(h, es, i0, i1, runs, ra, r, g0, g1, d_grecs, d_run_out, R, Q, S, out.device_planes);
+        if (rc) return rc;
+        rc = copy_back(h, es, i0, i1, out.reads, out.qual, out.strand, out.ref, out.num, out.status, out.device_planes, small);
+        if (rc) return rc;
+        i0 = i1;
+    }
+    return 0;
+}
+
+// The whole call with the BGZF blocks inflated and the records framed on the device: the runs of encode_batch over every
+// batch, their byte ranges from the BAI bins, the touched blocks read as they are; then, group of runs by group of runs,
+// inflate, walk, frame, resolve and encode.  The host does no per-record work.
+int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Entry>& es, const Outs& out) {
+    const int64_t n = (int64_t)es.size();
+    const pe_options& o = h->opt;
+    std::vector<uint8_t> small;
+    std::vector<Run> runs;
+    for (int64_t b0 = 0; b0 < n; b0 += BATCH_LOCS) build_runs(o, contigs, es, b0, std::min<int64_t>(n, b0 + BATCH_LOCS), runs);
+    if (runs.empty()) return encode_pieces(h, es, 0, n, runs, 0, 0, nullptr, nullptr, out, small);
+    if (runs.size() > (size_t)INT32_MAX) return fail(h, -1, "too many runs of locations in one call");
+    hipStream_t s = h->stream;
+    // read: the byte ranges of every run, and the blocks they touch into pinned memory
+    const auto t_read = std::chrono::steady_clock::now();
+    std::vector<pgh::Region> regs(runs.size());
+    for (size_t r = 0; r < runs.size(); ++r) regs[r] = pgh::Region{runs[r].tid, runs[r].s0, runs[r].stop};
+    bz::BlockPlan all;
+    std::string perr;
+    all.plan(h->bai, regs.data(), (int64_t)regs.size());
+    struct stat sb;
+    if (fstat(h->fd, &sb) != 0) return fail(h, -3, "BGZF: cannot stat %s", h->bam_path.c_str());
+    if (!all.spans((uint64_t)sb.st_size, perr)) return fail(h, -3, "%s", perr.c_str());
+    if (!pinned_grow(h->h_buf, h->hc_buf, all.comp_bytes + 4)) return fail(h, -2, "hipHostMalloc(%llu) failed", (unsigned long long)all.comp_bytes);
+    if (!all.read(h->fd, h->bam_path, h->h_buf, perr)) return fail(h, -3, "%s", perr.c_str());
+    // every run's inflated size, from the trailers of the blocks its own ranges touch
+    std::vector<uint64_t> run_bytes(runs.size());
+    for (size_t r = 0; r < runs.size(); ++r) {
+        bz::BlockPlan one;
+        one.plan(h->bai, &regs[r], 1);
+        if (!one.adopt(all, perr)) return fail(h, -3, "%s", perr.c_str());
+        run_bytes[r] = one.infl_bytes;
+    }
+    h->st.read_ms += ms_since(t_read);
+    if (!grow(h->d_comp, h->c_comp, (size_t)all.comp_bytes + 16)) return fail(h, -2, "hipMalloc failed for %llu compressed bytes", (unsigned long long)all.comp_bytes);
+    PG_TRY(hipEventRecord(h->ev[0], s));
+    if (all.comp_bytes) PG_TRY(hipMemcpyAsync(h->d_comp, h->h_buf, all.comp_bytes, hipMemcpyHostToDevice, s));
+    PG_TRY(hipEventRecord(h->ev[1], s));
+    PG_TRY(hipStreamSynchronize(s));
+    {
+        float ms = 0.f;
+        PG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        h->st.upload_ms += ms;
+    }
+    h->st.compressed_bytes += (int64_t)all.comp_bytes;
+    if (!h->walker) h->walker = bz::framer_create();
+    if (!h->framing) h->framing = pg::framing_create();
+    const int nt = thread_count(runs.size());
+    if (const int rc = ensure_workers(h, nt)) return rc;
+    for (size_t g0 = 0; g0 < runs.size();) {
+        // the longest prefix of the remaining runs within the budget (one run over it is a group of its own)
+        size_t g1 = g0 + 1;
+        uint64_t sum = run_bytes[g0];
+        while (g1 < runs.size() && sum + run_bytes[g1] <= h->max_inflated) sum += run_bytes[g1++];
+        const auto t_plan = std::chrono::steady_clock::now();
+        bz::BlockPlan pl;
+        pl.plan(h->bai, regs.data() + g0, (int64_t)(g1 - g0));
+        if (!pl.adopt(all, perr) || !pl.segments(perr)) return fail(h, -3, "%s", perr.c_str());
+        h->st.read_ms += ms_since(t_plan);
+        ++h->st.groups;
+        h->st.blocks += (int64_t)pl.tab.size();
+        h->st.inflated_bytes += (int64_t)pl.infl_bytes;
+        const size_t nblk = pl.tab.size();
+        if (!grow(h->d_tab, h->c_tab, nblk + 1) || !grow(h->d_infl, h->c_infl, (size_t)pl.infl_bytes + 16) || !grow(h->d_bstatus, h->c_bstatus, nblk + 1))
+            return fail(h, -2, "hipMalloc failed for a group of %llu inflated bytes", (unsigned long long)pl.infl_bytes);
+        if (nblk) PG_TRY(hipMemcpyAsync(h->d_tab, pl.tab.data(), nblk * sizeof(bz::BlockDesc), hipMemcpyHostToDevice, s));
+        PG_TRY(hipEventRecord(h->ev[0], s));
+        PG_TRY(bz::launch_inflate(h->d_comp, h->d_tab, (int64_t)nblk, h->d_infl, h->d_bstatus, s));
+        PG_TRY(hipEventRecord(h->ev[1], s));
+        std::vector<int32_t> bstatus(nblk);
+        if (nblk) PG_TRY(hipMemcpyAsync(bstatus.data(), h->d_bstatus, nblk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        // the reference tokens of the group's runs, on the worker threads while the device inflates
+        const std::string werr = on_workers(h, nt, g0, g1, [&](Worker* wk, size_t r) { fetch_ref(wk->fasta, runs[r]); });
+        PG_TRY(hipStreamSynchronize(s));
+        if (!werr.empty()) return fail(h, -3, "%s", werr.c_str());
+        float ms = 0.f;
+        PG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        h->st.inflate_ms += ms;
+        for (size_t i = 0; i < nblk; ++i)
+            if (bstatus[i] != BZ_OK)
+                return fail(h, -3, "BGZF block fails its CRC / size check (%s, block at file offset %llu)", bz_status_text(bstatus[i]),
+                            (unsigned long long)pl.blocks[i].coff);
+        // walk, frame, list per run (both calls wait for their kernels: the events bracket them)
+        PG_TRY(hipEventRecord(h->ev[2], s));
+        const uint64_t* d_rec_off = nullptr;
+        uint64_t n_walked = 0, err = bz::NO_ERROR;
+        const char* msg = nullptr;
+        if (bz::walk_records(h->walker, h->d_infl, pl.infl_bytes, pl.segs.data(), pl.segs.size(), pl.n_slots, s, &d_rec_off, &n_walked, &err, &msg))
+            return fail(h, -2, "device framing: %s", msg);
+        if (err != bz::NO_ERROR)
+            return fail(h, -3, "%s (record at virtual offset %lld)", pg::frame::why_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
+        std::vector<pg::RunDesc> rd(g1 - g0);
+        for (size_t r = g0; r < g1; ++r) rd[r - g0] = pg::RunDesc{runs[r].tid, 0, runs[r].s0, runs[r].stop};
+        pg::Rec* d_grecs = nullptr;
+        const pg::RunOut* d_run_out = nullptr;
+        int64_t n_recs = 0, n_res = 0;
+        if (pg::frame_runs(h->framing, h->d_infl, d_rec_off, d_rec_off ? pl.n_slots : 0, rd.data(), (int32_t)rd.size(), s, &d_grecs, &n_recs, &n_res,
+                           &d_run_out, &err, &msg))
+            return fail(h, -2, "device framing: %s", msg);
+        if (err != pg::FRAME_NO_ERROR)
+            return fail(h, -3, "%s (record at virtual offset %lld)", pg::frame::why_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
+        PG_TRY(hipEventRecord(h->ev[3], s));
+        PG_TRY(hipEventSynchronize(h->ev[3]));
+        PG_TRY(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+        h->st.frame_ms += ms;
+        h->st.records += n_recs;
+        if (n_res > INT32_MAX || n_recs > INT32_MAX) return fail(h, -1, "batch too large (%lld reference positions of records)", (long long)n_res);
+        if (!grow(h->d_qpos, h->c_qpos, (size_t)n_res + 1) || !grow(h->d_indel, h->c_indel, (size_t)n_res + 1) || !grow(h->d_isdel, h->c_isdel, (size_t)n_res + 1))
+            return fail(h, -2, "hipMalloc failed (group of %lld records)", (long long)n_recs);
+        PG_TRY(hipEventRecord(h->ev[0], s));
+        PG_TRY(pg::launch_resolve(h->d_infl, d_grecs, (int32_t)n_recs, h->d_qpos, h->d_indel, h->d_isdel, s));
+        PG_TRY(hipEventRecord(h->ev[1], s));
+        PG_TRY(hipStreamSynchronize(s));
+        PG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        h->st.encode_ms += ms;
+        // the group's entries; the last group takes the entries decided on the host as well
+        const int64_t e0 = g0 == 0 ? 0 : runs[g0].e0, e1 = g1 == runs.size() ? n : runs[g1].e0;
+        if (const int rc = encode_pieces(h, es, e0, e1, runs, g0, g1, d_grecs, d_run_out, out, small)) return rc;
+        for (size_t r = g0; r < g1; ++r) std::vector<uint8_t>().swap(runs[r].ref);
+        g0 = g1;
+    }
+    return 0;
+}
+#undef PG_TRY
+
 
 int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads, uint8_t* qual,
                uint8_t* strand, uint8_t* ref_out, int32_t* num_out, int8_t* status_out, bool device_planes, void* stream) {
@@ -394,6 +651,9 @@ int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positio
     if (hipGetDevice(&guard.prev) != hipSuccess) guard.prev = -1;
     if (hipSetDevice(h->device) != hipSuccess) return fail(h, -2, "hipSetDevice(%d) failed", h->device);
     if (!h->stream && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(h, -2, "hipStreamCreate failed");
+    for (hipEvent_t& e : h->ev)
+        if (!e && hipEventCreate(&e) != hipSuccess) return fail(h, -2, "hipEventCreate failed");
+    h->st = pg_stats{};
     // the caller's stream must not run ahead of (or behind) our work on its planes
     hipStream_t cs = (hipStream_t)stream;
     if (device_planes) {
@@ -429,35 +689,18 @@ int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positio
         return fail(h, -2, "hipMalloc of the plane buffer failed");
     if (!device_planes && !pinned_grow(h->h_planes, h->hc_planes, 3 * plane * BATCH_LOCS))
         return fail(h, -2, "hipHostMalloc of the plane buffer failed");
+    if (h->inflate_device)
+        return encode_all_device(h, contigs, es, Outs{reads, qual, strand, ref_out, num_out, status_out, device_planes});
     std::vector<uint8_t> small;
     for (int64_t b0 = 0; b0 < n; b0 += BATCH_LOCS) {
-        const int64_t b1 = std::min<int64_t>(n, b0 + BATCH_LOCS), nb = b1 - b0;
+        const int64_t b1 = std::min<int64_t>(n, b0 + BATCH_LOCS);
         uint8_t* R = device_planes ? reads : h->d_planes;
         uint8_t* Q = device_planes ? qual : h->d_planes + plane * BATCH_LOCS;
         uint8_t* S = device_planes ? strand : h->d_planes + 2 * plane * BATCH_LOCS;
         int rc = encode_batch(h, contigs, es, b0, b1, R, Q, S, device_planes);
         if (rc) return rc;
-        const size_t small_bytes = (((size_t)nb * W + 3) & ~(size_t)3) + (size_t)nb * 5;
-        small.resize(small_bytes);
-        if (hipMemcpy(small.data(), h->d_small, small_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, -2, "hipMemcpy failed");
-        const int32_t* num = (const int32_t*)(small.data() + (((size_t)nb * W + 3) & ~(size_t)3));
-        const int8_t* st = (const int8_t*)(num + nb);
-        if (!device_planes) {
-            for (int c = 0; c < 3; ++c)
-                if (hipMemcpy(h->h_planes + c * plane * BATCH_LOCS, h->d_planes + c * plane * BATCH_LOCS, plane * nb, hipMemcpyDeviceToHost) != hipSuccess)
-                    return fail(h, -2, "hipMemcpy failed");
-        }
-        for (int64_t i = 0; i < nb; ++i) {
-            const int64_t j = es[b0 + i].idx;
-            status_out[j] = st[i];
-            num_out[j] = num[i];
-            memcpy(ref_out + (size_t)j * W, small.data() + (size_t)i * W, W);
-            if (!device_planes)
-                for (int c = 0; c < 3; ++c) {
-                    uint8_t* dst = c == 0 ? reads : c == 1 ? qual : strand;
-                    memcpy(dst + (size_t)j * plane, h->h_planes + c * plane * BATCH_LOCS + (size_t)i * plane, plane);
-                }
-        }
+        rc = copy_back(h, es, b0, b1, reads, qual, strand, ref_out, num_out, status_out, device_planes, small);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -533,7 +776,7 @@ int assemble(pg_encoder* h, const uint8_t* reads_src, const uint8_t* qual_src, c
 
 extern "C" {
 
-const char* pg_last_error(const pg_encoder_t* h) { return h ? h->err.c_str() : g_err.c_str(); }
+const char* pg_last_error(const pg_encoder_t* h) { return h ? h->err.c_str() : pgh::g_err.c_str(); }
 
 int pg_open(const char* bam_path, const char* bai_path, const char* fasta_path, const pe_options* opt, int32_t device, pg_encoder_t** out) {
     try {
@@ -603,6 +846,26 @@ int pg_assemble_device(pg_encoder_t* h, const uint8_t* reads_src, const uint8_t*
     } catch (...) {
         return fail(h, -4, "pg_assemble_device: unknown exception");
     }
+}
+
+int pg_set_inflate_device(pg_encoder_t* h, int on, uint64_t max_inflated_bytes) {
+    if (!h) return fail(nullptr, -1, "pg_set_inflate_device: null handle");
+    try {
+        if (on && (!h->have_bai || h->bai.bins.empty()))
+            return fail(h, -1, "inflate on the device needs the BAI index of %s: its bins give the byte ranges to read", h->bam_path.c_str());
+        if (on && h->fd < 0 && (h->fd = open(h->bam_path.c_str(), O_RDONLY)) < 0) return fail(h, -3, "cannot open %s", h->bam_path.c_str());
+        h->inflate_device = on != 0;
+        h->max_inflated = max_inflated_bytes ? max_inflated_bytes : DEFAULT_INFLATED;
+        return 0;
+    } catch (...) {
+        return fail(h, -4, "pg_set_inflate_device: unknown exception");
+    }
+}
+
+int pg_get_stats(const pg_encoder_t* h, pg_stats* out) {
+    if (!h || !out) return fail(nullptr, -1, "pg_get_stats: null argument");
+    *out = h->st;
+    return 0;
 }
 
 void pg_close(pg_encoder_t* h) {

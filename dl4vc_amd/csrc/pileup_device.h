@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "pileup_frame.h"
+
 namespace pg {
 
 constexpr int BLOCK = 256;                   // threads per location workgroup (four wave64)
@@ -14,20 +16,7 @@ constexpr int MAX_POS = 2 * MAX_WINDOW + 5;  // reference positions of one locat
 constexpr int HASH_SLOTS = 2 * MAX_TRACKS;   // LDS open-addressing table of name:sequence hashes
 constexpr uint8_t REF_UNKNOWN = 0xff;        // a reference base outside the token table
 
-enum : uint32_t { R_FLAG_OK = 1, R_HAS_REF = 2, R_SKIP = 4, R_REVERSE = 8, R_EQ = 16, R_SHORT_SEQ = 32 };
-
-// One framed record of a batch (the host fills all but hash and R_EQ, which the resolve kernel adds;
-// R_SHORT_SEQ: SEQ holds fewer bases than the CIGAR's query length, e.g. SEQ '*').
-struct Rec {
-    uint64_t off;          // first byte of the record (after block_size) in the batch buffer
-    uint64_t hash;         // FNV-1a 64 of name ':' sequence, never 0
-    int32_t pos, end;      // end = pos + reference-consuming length (nref)
-    int32_t res;           // first of the record's nref entries in the resolution arrays
-    int32_t l_seq;
-    uint32_t cigar_off, seq_off, qual_off;
-    uint32_t n_cig, l_name;
-    uint32_t bits;
-};
+// (pg::Rec, one framed record of a batch, and its bits: pileup_frame.h)
 
 // One location of a batch.
 struct Loc {
@@ -48,6 +37,34 @@ hipError_t launch_encode(const uint8_t* buf, const Rec* recs, const Loc* locs, i
                          const int32_t* qpos, const int32_t* indel, const uint8_t* isdel, Params p, uint8_t* reads,
                          uint8_t* qual, uint8_t* strand, uint8_t* ref_small, int32_t* num_small, int8_t* status_small,
                          hipStream_t s);
+
+// ---- framing on the device (pileup_frame_kernels.hip; pg_set_inflate_device) ----
+// One run of locations, in the order of the call: sorted by (tid, s0), and stop rises with s0 inside a contig.
+struct RunDesc {
+    int32_t tid, pad;
+    int64_t s0, stop;
+};
+// What the framing found for a run: its records [rec0, rec1) of the group, its longest reference span, positions never decreasing.
+struct RunOut {
+    int32_t rec0, rec1;
+    int64_t max_nref;
+    int32_t sorted, pad;
+};
+constexpr uint64_t FRAME_NO_ERROR = ~0ull;   // else (offset of the record's block_size field) << 8 | frame::Why, the lowest offset wins
+
+struct Framing;   // device buffers of the framing passes, grown on demand
+Framing* framing_create();
+void framing_destroy(Framing* f);
+// rec_off: the n_slots record slots bz::walk_records left over infl (device).  Frames every record, lists it once for each of
+// the n_runs runs (host) it belongs to, run-major and in file order inside a run: *recs (device, the framing's own, *n_recs
+// entries with off into infl and res from the exclusive scan of their reference lengths, *n_res in all) and *run_out (device).
+// *err = FRAME_NO_ERROR or the first refused record.  0 or -2 with msg.
+int frame_runs(Framing* f, const uint8_t* infl, const uint64_t* rec_off, uint64_t n_slots, const RunDesc* runs, int32_t n_runs,
+               hipStream_t stream, Rec** recs, int64_t* n_recs, int64_t* n_res, const RunOut** run_out, uint64_t* err, const char** msg);
+// Fills first / last (or pre = 2 in a run that is not sorted) of the device locations whose pre is -1; loc_run (host): each
+// location's run, -1 for none.  `uploaded` (may be null) is recorded between the copy of loc_run and the kernel.
+int locate(Framing* f, const Rec* recs, const RunOut* run_out, int32_t n_runs, const int32_t* loc_run, Loc* locs, int32_t n_locs,
+           hipStream_t stream, const char** msg, hipEvent_t uploaded = nullptr);
 
 // ---- site assembly (assemble_kernels.hip) ----
 constexpr int ASSEMBLE_BLOCK = 256;          // threads per (site, plane) workgroup

@@ -187,7 +187,8 @@ class _Scored:
 
 class _BamBatches:
     """Worker side of ``score_bam``: a thread that turns ``sites_per_launch`` locations at a time into assembled device
-    planes.  Per round: ``pg_encode_device`` into the stored planes (the BAM fetch and framing run in its host threads),
+    planes.  Per round: ``pg_encode_device`` into the stored planes (the BAM fetch and framing run in its host threads, or on
+    the device with ``inflate_device="gpu"``),
     ``pe_encode`` for what it declines and the Python builder for what that declines (their planes are copied into the
     location's slot), rows and masks on the host (``site_assembly.plan_sites``), ``pg_assemble_device`` into one of two plane
     sets.  A forward batch holds exactly ``sites_per_launch`` RECORDS, as a batch of the candidate file does, so a round's
@@ -196,7 +197,8 @@ class _BamBatches:
     Device memory, allocated once: the stored planes 3 * B * S * L bytes and two sets of 3 * B * (R + 1) * L bytes.  At B = 4096,
     S = 200, R = 100, L = 201 that is 494 MB + 2 * 249 MB = 0.99 GB (about 120 KB per site for the stored planes alone)."""
 
-    def __init__(self, cfg, bam, fasta, locations, opt, sites_per_launch, reads_seed, site_limit, device_id, threads, counts):
+    def __init__(self, cfg, bam, fasta, locations, opt, sites_per_launch, reads_seed, site_limit, device_id, threads, counts,
+                 inflate_device=None):
         import queue
         import threading
         import torch
@@ -210,7 +212,9 @@ class _BamBatches:
             raise ValueError("the model reads %d rows per site but the encoder stores only %d" % (self.R, self.S))
         self.dev = torch.device("cuda", device_id)
         self.enc = pileup_gpu.GpuPileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
-                                               opt.max_insert_length_variant, opt.min_base_quality, device=device_id)
+                                               opt.max_insert_length_variant, opt.min_base_quality, device=device_id,
+                                               inflate_device=inflate_device)
+        self.stage = {}                                  # pg_stats summed over the encoder's calls
         self.cpu = loader.NativePileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
                                               opt.max_insert_length_variant, opt.min_base_quality)
         u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=self.dev)   # noqa: E731
@@ -256,6 +260,8 @@ class _BamBatches:
         from .hdf5_schema import record_dtype
         contigs, positions = [l.contig for l in locs], [l.pos for l in locs]
         _r, _q, _s, ref, num, status = self.enc.encode_device(contigs, positions, stream=self.stream, out=self.stored)
+        for k, v in self.enc.stats().items():
+            self.stage[k] = self.stage.get(k, 0) + v
         c = self.counts
         c["locations"] += len(locs)
         c["gpu"] += int((status == 1).sum())
@@ -350,7 +356,8 @@ class _BamBatches:
 
 def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None], sites_per_launch: int = 4096,
               reads_seed: int = 0, use_var_type_threshold: bool = False, log=None, stats=None, site_limit: int = 0,
-              encoder_options=None, device_id: int = 0, threads: int = 0, encoder_counts=None) -> int:
+              encoder_options=None, device_id: int = 0, threads: int = 0, encoder_counts=None,
+              inflate_device: Optional[str] = None) -> int:
     """Score ``locations`` (``pileup_encoder.Location``s, e.g. ``locations_from_vcf(candidates.vcf, label=2)``) straight from
     the BAM: the same lines ``tools/convert_bam_single_reads.py`` + ``score_records`` write, without a candidate file.  The
     pileup planes are encoded (``pg_encode_device``) and assembled (``pg_assemble_device``) in device memory and scored there
@@ -360,7 +367,9 @@ def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None]
     are formatted.  Site i draws its read subset with ``reads_seed + i``, i counting the locations that gave a record;
     ``site_limit`` > 0 stops after that many records.  ``encoder_options``: ``pileup_encoder.EncoderOptions`` (default: what
     call_variants.sh passes to the converter).  ``encoder_counts`` (a dict) receives how many locations each encoder took
-    (``ENCODER_COUNTS``).  Device memory: see ``_BamBatches`` -- about 1 GB at 4096 sites per launch.  ``net`` must have been
+    (``ENCODER_COUNTS``).  ``inflate_device="gpu"``: the encoder inflates the BAM's BGZF blocks and frames its records on the
+    device too (``pg_set_inflate_device``; needs the ``.bai``), same lines; with ``log``, the summary line then gives the
+    encoder's stage times (``pg_stats`` summed over its calls).  Device memory: see ``_BamBatches`` -- about 1 GB at 4096 sites per launch.  ``net`` must have been
     created after ``import torch`` (see the error below).  Returns the number of sites scored."""
     import os
     import torch
@@ -376,7 +385,7 @@ def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None]
     threads = threads or max(2, min(16, (os.cpu_count() or 4)))
     emit = _Pipeline(net, write, use_var_type_threshold, stats)._emit
     src = _BamBatches(net.config, bam, fasta, list(locations), opt, sites_per_launch, reads_seed, site_limit, device_id, threads,
-                      counts)
+                      counts, inflate_device)
     fwd = torch.cuda.Stream(src.dev)
     done = 0
     total = len(src.locations)
@@ -419,4 +428,8 @@ def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None]
             prev["done"].synchronize()
         fwd.synchronize()
         src.close()
+    if log:
+        st = src.stage
+        log("  pileup encoder (%s): %s" % ("BGZF inflate and framing on the device" if inflate_device == "gpu" else "host framing",
+                                          ", ".join("%s %s" % (k, ("%.1f" % v) if k.endswith("_ms") else int(v)) for k, v in st.items())))
     return done

@@ -420,7 +420,7 @@ def encode_location(bam, fasta, loc: Location, opt: EncoderOptions, reader=None)
 
 def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Location], opt: EncoderOptions,
                      native: Optional[bool] = None, threads: int = 1, device: Optional[str] = None,
-                     device_id: int = 0) -> Tuple[np.ndarray, int]:
+                     device_id: int = 0, inflate_device: Optional[str] = None) -> Tuple[np.ndarray, int]:
     """Records for ``locations`` in input order and the number of locations that produced none.
 
     ``native`` (default: when libdl4vc_loader.so is built): the image planes come from the C++ encoder (``pe_encode``:
@@ -431,6 +431,8 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
     ``device="gpu"`` (default None: the host encoders above): the planes come from the GPU encoder (libdl4vc_pileup.so on HIP device ``device_id``) first; what it
     declines goes to ``pe_encode``, and what that declines to the Python encoder -- the same bytes and error count as
     ``native=True`` (tests/test_pileup_gpu.py).  A missing libdl4vc_pileup.so is an error, not a fall-back.
+    ``inflate_device="gpu"`` (with ``device="gpu"`` only): the GPU encoder inflates the BAM's BGZF blocks and frames its records on
+    the device as well (needs the ``.bai``; same bytes, tests/test_pileup_inflate_gpu.py).
 
     Raises ``ValueError`` naming the read where a location's window holds a read the specification has no answer for (a
     zero-length alignment such as ``0M 5I``, a SEQ shorter than the CIGAR's query length such as SEQ ``*``): the native and
@@ -439,6 +441,10 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
     from . import loader
     if device not in (None, "gpu"):
         raise ValueError("device must be None (host encoders) or 'gpu', not %r" % (device,))
+    if inflate_device not in (None, "gpu"):
+        raise ValueError("inflate_device must be None or 'gpu', not %r" % (inflate_device,))
+    if inflate_device == "gpu" and device != "gpu":
+        raise ValueError("inflate_device='gpu' is the GPU pileup encoder's option: it needs device='gpu'")
     dtype = record_dtype(opt.max_reads, 2 * opt.window_size + 1)
     out = np.zeros(len(locations), dtype)
     n = errors = 0
@@ -448,7 +454,8 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
     if device == "gpu" and len(locations):
         from . import pileup_gpu
         with pileup_gpu.GpuPileupEncoder(bam_path, fasta_path, opt.window_size, opt.max_reads, opt.max_insert_length,
-                                         opt.max_insert_length_variant, opt.min_base_quality, device=device_id) as enc:
+                                         opt.max_insert_length_variant, opt.min_base_quality, device=device_id,
+                                         inflate_device=inflate_device) as enc:
             planes = enc.encode(contigs, positions)
         declined = np.flatnonzero(planes[5] == 2)
         if len(declined):

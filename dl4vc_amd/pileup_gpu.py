@@ -16,10 +16,51 @@ from .loader import PileupOptions
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_pileup.so")
-SYMBOLS = ("pg_open", "pg_encode", "pg_encode_device", "pg_assemble_device", "pg_close", "pg_last_error")
+SYMBOLS = ("pg_open", "pg_encode", "pg_encode_device", "pg_assemble_device", "pg_close", "pg_last_error",
+           "pg_set_inflate_device", "pg_get_stats", "pg_debug_run_records")
 MAX_TRACKS = 1024            # PG_MAX_TRACKS
 MAX_WINDOW = 100             # PG_MAX_WINDOW
 _lib = None
+
+
+class Stats(C.Structure):
+    """``pg_stats``: the stages of the last ``pg_encode`` / ``pg_encode_device`` call (times in ms)."""
+    _fields_ = [(n, C.c_double) for n in ("host_frame_ms", "read_ms", "upload_ms", "inflate_ms", "frame_ms", "encode_ms", "copy_back_ms")] + \
+               [(n, C.c_int64) for n in ("host_records", "blocks", "compressed_bytes", "inflated_bytes", "records", "groups")]
+
+
+class RecView(C.Structure):
+    """``pg_rec_view``: one framed record of ``pg_debug_run_records``."""
+    _fields_ = [(n, C.c_int32) for n in ("pos", "end", "res", "l_seq")] + \
+               [(n, C.c_uint32) for n in ("cigar_off", "seq_off", "qual_off", "n_cig", "l_name", "bits")] + [("bytes_hash", C.c_uint64)]
+
+
+def _bind_debug(lib):
+    lib.pg_debug_run_records.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int64, C.c_int, C.POINTER(RecView), C.c_int64,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.pg_last_error.argtypes = [C.c_void_p]
+    lib.pg_last_error.restype = C.c_char_p
+
+
+def debug_run_records(bam_path: str, bai_path: str, tid: int, s0: int, stop: int, path: int, lib=None):
+    """``pg_debug_run_records`` -> (list of field tuples, max_nref, sorted); no GPU is touched.  ``path`` 0: the host framing, 1: the
+    CPU twin of the device path.  ``lib``: another build of the entry point (the sanitizer build)."""
+    if lib is None:
+        lib = load_library()
+    else:
+        _bind_debug(lib)
+    n, mx, srt = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    cap = 1 << 12
+    while True:
+        buf = (RecView * cap)()
+        rc = lib.pg_debug_run_records(bam_path.encode(), bai_path.encode(), tid, s0, stop, path, buf, cap, C.byref(n), C.byref(mx), C.byref(srt))
+        if rc != 0:
+            raise RuntimeError("pg_debug_run_records failed: %s" % lib.pg_last_error(None).decode())
+        if n.value <= cap:
+            break
+        cap = n.value
+    names = [f[0] for f in RecView._fields_]
+    return [tuple(getattr(buf[i], k) for k in names) for i in range(n.value)], mx.value, bool(srt.value)
 
 
 def available() -> bool:
@@ -38,6 +79,9 @@ def load_library() -> C.CDLL:
         lib.pg_encode_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
         lib.pg_assemble_device.argtypes = ([vp] * 4 + [C.c_int64, C.c_int32, C.c_int32] + [vp] * 3 + [C.c_int64, C.c_int32] + [vp] * 3 +
                                            [C.c_int32, C.c_int32] + [vp] * 6 + [vp])
+        lib.pg_set_inflate_device.argtypes = [vp, C.c_int, C.c_uint64]
+        lib.pg_get_stats.argtypes = [vp, C.POINTER(Stats)]
+        _bind_debug(lib)
         lib.pg_close.argtypes = [vp]
         lib.pg_close.restype = None
         lib.pg_last_error.argtypes = [vp]
@@ -50,7 +94,12 @@ class GpuPileupEncoder:
     """Image planes of a list of locations, in input order; the same outputs as ``loader.NativePileupEncoder.encode``."""
 
     def __init__(self, bam_path: str, fasta_path: str, window_size: int, max_reads: int, max_insert_length: int,
-                 max_insert_length_variant: int, min_base_quality: int = 0, bai_path: Optional[str] = None, device: int = 0):
+                 max_insert_length_variant: int, min_base_quality: int = 0, bai_path: Optional[str] = None, device: int = 0,
+                 inflate_device: Optional[str] = None, max_inflated_bytes: int = 0):
+        """``inflate_device="gpu"``: the BGZF blocks are inflated and the records framed on the device (``pg_set_inflate_device``;
+        needs the ``.bai``), same outputs.  ``max_inflated_bytes``: inflated bytes per group of runs, 0 = the default."""
+        if inflate_device not in (None, "gpu"):
+            raise ValueError("inflate_device: None or 'gpu', not %r" % (inflate_device,))
         self.lib = load_library()
         self._h = C.c_void_p()
         self.window, self.max_reads, self.device = 2 * window_size + 1, max_reads, device
@@ -60,6 +109,21 @@ class GpuPileupEncoder:
         if rc != 0:
             self._h = None
             raise RuntimeError("pg_open failed: %s" % self.lib.pg_last_error(None).decode())
+        if inflate_device == "gpu":
+            try:
+                self.set_inflate_device(True, max_inflated_bytes)
+            except RuntimeError:
+                self.close()
+                raise
+
+    def set_inflate_device(self, on: bool, max_inflated_bytes: int = 0) -> None:
+        self._check(self.lib.pg_set_inflate_device(self._h, int(bool(on)), int(max_inflated_bytes)), "pg_set_inflate_device")
+
+    def stats(self) -> dict:
+        """The stages of the last ``encode`` / ``encode_device`` call (``pg_stats``)."""
+        st = Stats()
+        self._check(self.lib.pg_get_stats(self._h, C.byref(st)), "pg_get_stats")
+        return {n: getattr(st, n) for n, _ in Stats._fields_}
 
     def _args(self, contigs: Sequence[str], positions):
         n = len(positions)

@@ -64,6 +64,55 @@ int pg_assemble_device(pg_encoder_t* h, const uint8_t* reads_src, const uint8_t*
                        const uint8_t* first_rows, int64_t m, int32_t reads, const uint8_t* ref, const uint8_t* ref_mask,
                        const uint8_t* var_mask, int32_t use_q, int32_t use_strand, uint8_t* reads_out, uint8_t* qual_out,
                        uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out, uint8_t* var_mask_out, void* stream);
+/* ---- records inflated and framed on the device ------------------------------------------------------------------------------
+ * With pg_set_inflate_device(h, 1, budget) the host threads above do no per-record work.  Each call builds the same runs of
+ * locations, takes every run's byte ranges from the BAI bins, reads the BGZF blocks they touch as they are into pinned memory
+ * and uploads them; the device inflates them (a group of runs at a time, at most `max_inflated_bytes` of inflated data per
+ * group, 0 = 256 MB; one run larger than that is a group of its own), walks the record chain, frames every record with the
+ * checks of the host path, lists it once for each run it belongs to (run-major, file order within a run) and finds every
+ * location's records.  The encode kernels then read the records where they lie in the inflated buffer.  The host still reads
+ * the index, the file and the reference tokens.  Outputs are byte-identical to the encoder with the option off.
+ * Refused (an error, pg_last_error(h) says why): an encoder without the bins of a .bai (opened without one: the scan builds
+ * only the linear index), and, at encode time, a BGZF block with ISIZE > 65536.  A block that two byte ranges touch is
+ * inflated once for each.  A damaged block is "BGZF block fails its CRC / size check (<status>, block at file offset N)"; a
+ * refused record is the host path's text with "(record at virtual offset N)".  on = 0 restores the host path. */
+int pg_set_inflate_device(pg_encoder_t* h, int on, uint64_t max_inflated_bytes /* 0: default */);
+
+/* Stages of the last pg_encode / pg_encode_device call, times in ms.  With the option off only host_frame_ms, upload_ms,
+ * encode_ms, copy_back_ms, host_records and records are filled.  upload_ms, inflate_ms, frame_ms and encode_ms are device time
+ * between events on the encoder's stream, on both paths; host_frame_ms, read_ms and copy_back_ms are host wall clock (copy_back_ms
+ * around blocking copies). */
+typedef struct {
+    double host_frame_ms;     /* wall time of the fetch threads, plus the gather */
+    double read_ms;           /* index ranges, pread into pinned memory, header and trailer checks */
+    double upload_ms;         /* host -> device copies (records or blocks, locations, reference tokens) */
+    double inflate_ms;        /* device events around the inflate kernel */
+    double frame_ms;          /* walk, frame, scans, emit and location search */
+    double encode_ms;         /* resolve_records and encode_locations */
+    double copy_back_ms;      /* planes back to the host (pg_encode only) */
+    int64_t host_records;     /* records framed on the host; 0 on the device path */
+    int64_t blocks, compressed_bytes, inflated_bytes;
+    int64_t records;          /* records listed for the runs (a record shared by two runs counts twice) */
+    int64_t groups;
+} pg_stats;
+int pg_get_stats(const pg_encoder_t* h, pg_stats* out);
+
+/* Test hook, no device call: the framed records of the run [s0, stop) of contig `tid`, by the host path (path 0) or by the
+ * CPU twin of the device path (path 1: index ranges, the host form of the inflate, the shared frame core, serially; path 2:
+ * the same, with the run's blocks taken from the plan of a larger call).
+ * Every field of a record but its hash; bytes_hash stands for `off`: FNV-1a 64 of the bytes it points at (up to the end of
+ * the qualities).  *n = records of the run (the first `cap` are written).  Errors: pg_last_error(NULL). */
+typedef struct {
+    int32_t pos, end, res, l_seq;
+    uint32_t cigar_off, seq_off, qual_off, n_cig, l_name, bits;
+    uint64_t bytes_hash;
+} pg_rec_view;
+int pg_debug_run_records(const char* bam, const char* bai, int32_t tid, int64_t s0, int64_t stop,
+                         int path /* 0: fetch_run, 1: index ranges + bz_inflate_host + the shared frame core, serially;
+                                     2: as 1, inside a call that also asks for [0, 64) of the contig: the blocks are read for
+                                     the call's plan and the run takes its own from it, as a group of runs does */,
+                         pg_rec_view* out, int64_t cap, int64_t* n, int64_t* max_nref, int32_t* sorted);
+
 void pg_close(pg_encoder_t* h);
 const char* pg_last_error(const pg_encoder_t* h);      /* h may be NULL: error of the last failed pg_open */
 

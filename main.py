@@ -275,6 +275,11 @@ def check_bam_arguments(args) -> None:
 def main(argv=None) -> int:
     args = parse_args(argv)
     print(args)
+    if args.inflate_device not in (None, "gpu"):
+        raise SystemExit("--inflate-device must be gpu")
+    if args.inflate_device and not args.test_bam:
+        raise SystemExit("--inflate-device gpu is an option of --test_bam (the GPU pileup encoder reads the BAM); a --test_file holds "
+                         "pileups already encoded")
     if args.test_bam:
         check_bam_arguments(args)
     if args.train_file:
@@ -381,7 +386,7 @@ def main(argv=None) -> int:
         with open(target, "w") as f:
             n = score_bam(net, args.test_bam, args.test_fasta, locations, f.write, sites_per_launch=args.sites_per_launch,
                           reads_seed=args.reads_seed, use_var_type_threshold=args.use_var_type_threshold, site_limit=site_limit,
-                          log=lambda m: print(m, end="\r"), stats=stats, encoder_counts=counts)
+                          log=lambda m: print(m, end="\r"), stats=stats, encoder_counts=counts, inflate_device=args.inflate_device)
     else:
         n = run_shard(net, args.test_file, target, shard_i, shard_n, sites_per_launch=args.sites_per_launch,
                       reads_seed=args.reads_seed, use_var_type_threshold=args.use_var_type_threshold,

@@ -61,7 +61,12 @@ def main(argv=None):
     ap.add_argument("--pileup-device", type=str, default=None, choices=["gpu"],
                     help="gpu: build the image planes with the GPU pileup encoder (libdl4vc_pileup.so); what it declines goes to the "
                          "host encoders, so the file is the same bytes (default: the host encoders)")
+    ap.add_argument("--inflate-device", type=str, default=None, choices=["gpu"],
+                    help="gpu: with --pileup-device gpu, the GPU encoder inflates the BAM's BGZF blocks and frames its records on the "
+                         "device as well (needs the .bai); the file is the same bytes")
     args = ap.parse_args(argv)
+    if args.inflate_device and args.pileup_device != "gpu":
+        raise SystemExit("--inflate-device gpu is an option of the GPU pileup encoder: give --pileup-device gpu as well")
     for flag, why in (("locations", "numpy location tables"), ("restrict_locations", "location restriction files"),
                       ("non_restrict_match_random", "location restriction files")):
         if getattr(args, flag):
@@ -114,7 +119,7 @@ def main(argv=None):
                 errors = sum(p[1] for p in parts)
             else:
                 recs, errors = encode_locations(args.input, args.fasta_input, chunk, opt, native=native, threads=procs,
-                                                device=args.pileup_device)
+                                                device=args.pileup_device, inflate_device=args.inflate_device)
             total_errors += errors
             if not created:
                 hdf5io.write_candidates(args.output, recs, chunk=8)

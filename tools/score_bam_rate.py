@@ -87,6 +87,7 @@ def main():
     ap.add_argument("--precision", default="fp32")
     ap.add_argument("--threads", type=int, default=16, help="--num-processes of the converter")
     ap.add_argument("--no-bench", action="store_true", help="skip the bench.py run of the forward alone")
+    ap.add_argument("--inflate-device", default=None, choices=["gpu"], help="passed to main.py --test_bam")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
@@ -112,7 +113,8 @@ def main():
         t_file, out_file = timed([sys.executable, os.path.join(ROOT, "main.py"), "--test_file", hdf, "--save_vcf_records_file",
                                   os.path.join(a.dir, "two_step.vcf")] + common)
         t_bam, out_bam = timed([sys.executable, os.path.join(ROOT, "main.py"), "--test_bam", bam, "--test_fasta", fa,
-                                "--save_vcf_records_file", os.path.join(a.dir, "direct.vcf")] + common)
+                                "--save_vcf_records_file", os.path.join(a.dir, "direct.vcf")] + common +
+                               (["--inflate-device", a.inflate_device] if a.inflate_device else []))
         same = open(os.path.join(a.dir, "epoch1_two_step.vcf"), "rb").read() == open(os.path.join(a.dir, "epoch1_direct.vcf"), "rb").read()
         if not same:
             sys.exit("round %d: the two paths wrote different scored VCFs" % k)
@@ -127,7 +129,7 @@ def main():
     best_bam = min(r["test_bam_wall_s"] for r in rounds)
     fwd = max(r["test_file_loop"]["sites_per_s"] for r in rounds)
     loop = max(r["test_bam_loop"]["sites_per_s"] for r in rounds)
-    res = {"tool": "score_bam_rate", "locations": n_loc, "sites": sites, "precision": a.precision, "rounds": rounds,
+    res = {"tool": "score_bam_rate", "inflate_device": a.inflate_device, "locations": n_loc, "sites": sites, "precision": a.precision, "rounds": rounds,
            "i_test_bam_sites_per_s_whole_process": round(sites / best_bam), "i_test_bam_sites_per_s_scoring_loop": loop,
            "ii_two_step_wall_s": [r["two_step_wall_s"] for r in rounds], "i_test_bam_wall_s": [r["test_bam_wall_s"] for r in rounds],
            "test_bam_faster_in_every_round": all(r["test_bam_wall_s"] < r["two_step_wall_s"] for r in rounds),
