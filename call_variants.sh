@@ -12,13 +12,17 @@
 # -z: the candidate generator inflates the BAM's BGZF blocks and frames its records on the GPU (--inflate-device gpu; needs
 # BAM.bai); candidates.vcf is the same.  With -d, main.py --test_bam gets --inflate-device gpu as well, so no stage inflates or
 # frames a record on the host; the scored VCF is the same.
+# -c (on the path through candidates.hdf, no effect with -d): the converter builds the pileups on the GPU and packs and compresses
+# the file's chunks there as well (--pileup-device gpu --compress-device gpu); candidates.hdf holds the same records, the scored
+# VCF is the same.
 set -e
-usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z]"; exit 1; }
+usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-c]"; exit 1; }
 GPUS=1
 PROCS=16
 DIRECT=0
 INFLATE=""
-while getopts "m:o:g:i:r:b:p:dzh" opt; do
+COMPRESS=""
+while getopts "m:o:g:i:r:b:p:dzch" opt; do
   case $opt in
     m) MODEL=$OPTARG ;;
     o) OUTDIR=$OPTARG ;;
@@ -29,6 +33,7 @@ while getopts "m:o:g:i:r:b:p:dzh" opt; do
     p) PROCS=$OPTARG ;;
     d) DIRECT=1 ;;          # score straight from the BAM (main.py --test_bam)
     z) INFLATE=gpu ;;       # BGZF inflate and record framing on the GPU: candidate generation, and with -d the pileup encoder
+    c) COMPRESS=gpu ;;      # candidates.hdf: pileups, record packing and chunk compression on the GPU
     *) usage ;;
   esac
 done
@@ -54,7 +59,7 @@ if [ "$DIRECT" != 1 ] && [ ! -f "$OUTDIR/candidates.hdf" ]; then
   python "$SCRIPTDIR/tools/convert_bam_single_reads.py" --input "$BAM" --fp_vcf "$OUTDIR/candidates.vcf" \
       --fasta-input "$REFERENCE" --output "$OUTDIR/candidates.hdf" --max-reads 200 --num-processes "$PROCS" \
       --locations-process-step 100000 --max-insert-length 10 --max-insert-length-variant 50 \
-      --save-q-scores --save-strand > "$OUTDIR/training_data.log" 2>&1
+      --save-q-scores --save-strand ${COMPRESS:+--pileup-device gpu --compress-device "$COMPRESS"} > "$OUTDIR/training_data.log" 2>&1
 fi
 
 printf "Run inference...\n"

@@ -9,12 +9,16 @@
 // the BAI bins (bgzf_plan.h), reads their BGZF blocks as they are into pinned memory, and the device inflates them group of runs
 // by group of runs, walks the record chain (bgzf_kernels.hip), frames the records and finds each location's records
 // (pileup_frame_kernels.hip); the same resolve / encode kernels follow, reading the records where they lie in the inflated buffer.
+//
+// pg_compress_records_device() takes the stored planes where pg_encode_device left them: the records are packed into the HDF5
+// compound layout, compressed into the dataset's chunks (zdeflate_kernels.hip, zdeflate.h) and only those bytes come back.
 #include "../../include/dl4vc_pileup_gpu.h"
 #include "bam_native.h"
 #include "bgzf_device.h"
 #include "fasta_native.h"
 #include "pileup_device.h"
 #include "pileup_fetch.h"
+#include "zdeflate_device.h"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -121,7 +125,21 @@ struct pg_encoder {
     bz::BlockDesc* d_tab = nullptr; size_t c_tab = 0;
     uint8_t* d_infl = nullptr; size_t c_infl = 0;
     int32_t* d_bstatus = nullptr; size_t c_bstatus = 0;
+    // pg_compress_records_device: the compressor's buffers, the packed chunk image, the streams, the blob and slots (device and
+    // pinned staging), the pinned bytes handed to the caller
+    zd::Ctx* zctx = nullptr;
+    uint8_t* d_image = nullptr; size_t c_image = 0;
+    uint8_t* d_zout = nullptr; size_t c_zout = 0;
+    uint8_t* d_blob = nullptr; size_t c_blob = 0;
+    uint8_t* h_blob = nullptr; size_t hc_blob = 0;
+    uint8_t* h_zout = nullptr; size_t hc_zout = 0;
+    hipEvent_t zev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     ~pg_encoder() {
+        zd::ctx_destroy(zctx);
+        for (hipEvent_t e : zev) if (e) (void)hipEventDestroy(e);
+        for (void* p : {(void*)d_image, (void*)d_zout, (void*)d_blob}) if (p) (void)hipFree(p);
+        if (h_blob) (void)hipHostFree(h_blob);
+        if (h_zout) (void)hipHostFree(h_zout);
         if (fd >= 0) close(fd);
         bz::framer_destroy(walker);
         pg::framing_destroy(framing);
@@ -772,6 +790,111 @@ int assemble(pg_encoder* h, const uint8_t* reads_src, const uint8_t* qual_src, c
     return 0;
 }
 
+constexpr int64_t Z_CHUNKS = 512;           // chunks per pass of pg_compress_records_device (4 096 records at 8 per chunk)
+
+int compress_records(pg_encoder* h, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots, const int32_t* slots,
+                     const uint8_t* blob, int64_t n, int32_t rpc, const uint8_t** out, uint64_t* offsets, uint64_t* sizes, uint32_t* adlers,
+                     uint8_t* store, void* stream) {
+    if (!out || n < 0 || n_slots < 0) return fail(h, -1, "pg_compress_records_device: null argument or negative count");
+    *out = nullptr;
+    if (rpc < 1 || rpc > 64) return fail(h, -1, "pg_compress_records_device: 1..64 records per chunk");
+    const pe_options& o = h->opt;
+    const uint32_t W = 2 * (uint32_t)o.window_size + 1;
+    if ((uint64_t)o.max_reads * W > (1u << 24)) return fail(h, -1, "pg_compress_records_device: record planes too large");
+    const uint32_t plane = (uint32_t)o.max_reads * W, head = 16 + 15 * W, mid = W + 4 + 1 + 128, blob_bytes = head + mid;
+    const uint64_t itemsize = (uint64_t)blob_bytes + 3ull * plane, chunk_bytes = itemsize * (uint64_t)rpc;
+    if (chunk_bytes > zd::MAX_STREAM) return fail(h, -1, "pg_compress_records_device: a chunk of %llu bytes is too large", (unsigned long long)chunk_bytes);
+    h->st.pack_ms = h->st.deflate_ms = h->st.gather_ms = h->st.compress_copy_back_ms = 0;
+    h->st.chunks = h->st.raw_bytes = h->st.chunk_bytes_out = h->st.stored_chunks = 0;
+    if (n == 0) return 0;
+    if (!reads || !qual || !strand || !slots || !blob || !offsets || !sizes || !adlers || !store)
+        return fail(h, -1, "pg_compress_records_device: null argument");
+    // every index the pack kernel follows is checked here
+    for (int64_t i = 0; i < n; ++i)
+        if (slots[i] < 0 || slots[i] >= n_slots)
+            return fail(h, -1, "pg_compress_records_device: record %lld names slot %d of %lld", (long long)i, slots[i], (long long)n_slots);
+    struct DeviceGuard {
+        int prev = -1;
+        ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+    } guard;
+    if (hipGetDevice(&guard.prev) != hipSuccess) guard.prev = -1;
+    if (hipSetDevice(h->device) != hipSuccess) return fail(h, -2, "hipSetDevice(%d) failed", h->device);
+    for (hipEvent_t& e : h->zev)
+        if (!e && hipEventCreate(&e) != hipSuccess) return fail(h, -2, "hipEventCreate failed");
+    if (!h->zctx) h->zctx = zd::ctx_create();
+    const int64_t n_chunks = (n + rpc - 1) / rpc;
+    const int64_t pass_chunks = std::min<int64_t>(n_chunks, Z_CHUNKS), pass_records = pass_chunks * rpc;
+    const uint64_t cbound = zd::bound(chunk_bytes, zd::DEFAULT_SEG);
+    const size_t stage = (size_t)pass_records * (blob_bytes + 4);            // blob | slots of one pass
+    if (!grow(h->d_image, h->c_image, (size_t)pass_chunks * chunk_bytes + 8) || !grow(h->d_zout, h->c_zout, (size_t)pass_chunks * cbound) ||
+        !grow(h->d_blob, h->c_blob, stage))
+        return fail(h, -2, "hipMalloc failed (%lld chunks of %llu bytes)", (long long)pass_chunks, (unsigned long long)chunk_bytes);
+    if (!pinned_grow(h->h_blob, h->hc_blob, stage)) return fail(h, -2, "hipHostMalloc of the blob staging failed");
+    hipStream_t s = (hipStream_t)stream;
+#define PZ_TRY(x)                                                                                                  \
+    do {                                                                                                           \
+        const hipError_t e_ = (x);                                                                                 \
+        if (e_ != hipSuccess) return fail(h, -2, "pg_compress_records_device: %s: %s", #x, hipGetErrorString(e_)); \
+    } while (0)
+    uint64_t total = 0;
+    for (int64_t c0 = 0; c0 < n_chunks; c0 += pass_chunks) {
+        const int64_t nc = std::min<int64_t>(pass_chunks, n_chunks - c0);
+        const int64_t r0 = c0 * rpc, nr = std::min<int64_t>(n - r0, nc * rpc);
+        const size_t b_blob = (size_t)nr * blob_bytes;
+        memcpy(h->h_blob, blob + (size_t)r0 * blob_bytes, b_blob);
+        memcpy(h->h_blob + (size_t)pass_records * blob_bytes, slots + r0, (size_t)nr * 4);
+        PZ_TRY(hipEventRecord(h->zev[0], s));
+        PZ_TRY(hipMemcpyAsync(h->d_blob, h->h_blob, b_blob, hipMemcpyHostToDevice, s));
+        PZ_TRY(hipMemcpyAsync(h->d_blob + (size_t)pass_records * blob_bytes, h->h_blob + (size_t)pass_records * blob_bytes, (size_t)nr * 4,
+                              hipMemcpyHostToDevice, s));
+        zd::PackArgs a{};
+        a.planes[0] = reads; a.planes[1] = qual; a.planes[2] = strand;
+        a.blob = h->d_blob;
+        a.slots = (const int32_t*)(h->d_blob + (size_t)pass_records * blob_bytes);
+        a.n_records = nr; a.plane = plane; a.head = head; a.mid = mid;
+        const uint64_t image_bytes = ((uint64_t)nc * chunk_bytes + 7) & ~7ull;       // (chunk_bytes * rpc-of-8 is a multiple of 8; any rpc: + 8 above)
+        PZ_TRY(zd::launch_pack(a, image_bytes, h->d_image, s));
+        PZ_TRY(hipEventRecord(h->zev[1], s));
+        zd::Streams r{};
+        const char* msg = nullptr;
+        if (zd::run(h->zctx, h->d_image, chunk_bytes, nc, zd::DEFAULT_SEG, false, true, h->d_zout, s, h->zev[2], &r, &msg))
+            return fail(h, -2, "pg_compress_records_device: %s", msg);
+        PZ_TRY(hipEventRecord(h->zev[3], s));
+        PZ_TRY(hipMemcpyAsync(offsets + c0, r.offs, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
+        PZ_TRY(hipMemcpyAsync(sizes + c0, r.sizes, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
+        PZ_TRY(hipMemcpyAsync(adlers + c0, r.adlers, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
+        PZ_TRY(hipMemcpyAsync(store + c0, r.store, (size_t)nc, hipMemcpyDeviceToHost, s));
+        PZ_TRY(hipStreamSynchronize(s));
+        const uint64_t bytes = offsets[c0 + nc - 1] + sizes[c0 + nc - 1];
+        if (bytes > (uint64_t)nc * cbound) return fail(h, -2, "pg_compress_records_device: the streams exceed their bound");
+        if (total && total + bytes > h->hc_zout) {             // a later pass outgrows the pinned buffer: keep what it holds
+            const std::vector<uint8_t> earlier(h->h_zout, h->h_zout + total);
+            if (!pinned_grow(h->h_zout, h->hc_zout, (size_t)(total + bytes))) return fail(h, -2, "hipHostMalloc(%llu) failed", (unsigned long long)(total + bytes));
+            memcpy(h->h_zout, earlier.data(), total);
+        } else if (!pinned_grow(h->h_zout, h->hc_zout, (size_t)(total + bytes)))
+            return fail(h, -2, "hipHostMalloc(%llu) failed", (unsigned long long)(total + bytes));
+        PZ_TRY(hipMemcpyAsync(h->h_zout + total, h->d_zout, bytes, hipMemcpyDeviceToHost, s));
+        PZ_TRY(hipEventRecord(h->zev[4], s));
+        PZ_TRY(hipStreamSynchronize(s));
+        for (int64_t c = c0; c < c0 + nc; ++c) {
+            offsets[c] += total;
+            h->st.stored_chunks += store[c] != 0;
+        }
+        total += bytes;
+        float ms = 0.f;
+        PZ_TRY(hipEventElapsedTime(&ms, h->zev[0], h->zev[1])); h->st.pack_ms += ms;
+        PZ_TRY(hipEventElapsedTime(&ms, h->zev[1], h->zev[2])); h->st.deflate_ms += ms;
+        PZ_TRY(hipEventElapsedTime(&ms, h->zev[2], h->zev[3])); h->st.gather_ms += ms;
+        PZ_TRY(hipEventElapsedTime(&ms, h->zev[3], h->zev[4])); h->st.compress_copy_back_ms += ms;
+    }
+#undef PZ_TRY
+    h->st.chunks = n_chunks;
+    h->st.raw_bytes = (int64_t)((uint64_t)n_chunks * chunk_bytes);
+    h->st.chunk_bytes_out = (int64_t)total;
+    *out = h->h_zout;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -845,6 +968,21 @@ int pg_assemble_device(pg_encoder_t* h, const uint8_t* reads_src, const uint8_t*
         return fail(h, -4, "pg_assemble_device: %s", e.what());
     } catch (...) {
         return fail(h, -4, "pg_assemble_device: unknown exception");
+    }
+}
+
+int pg_compress_records_device(pg_encoder_t* h, const uint8_t* reads_dev, const uint8_t* qual_dev, const uint8_t* strand_dev,
+                               int64_t n_slots, const int32_t* slots, const uint8_t* blob, int64_t n_records,
+                               int32_t records_per_chunk, const uint8_t** out, uint64_t* offsets, uint64_t* sizes, uint32_t* adlers,
+                               uint8_t* store, void* stream) {
+    if (!h) return fail(nullptr, -1, "pg_compress_records_device: null handle");
+    try {
+        return compress_records(h, reads_dev, qual_dev, strand_dev, n_slots, slots, blob, n_records, records_per_chunk, out, offsets, sizes,
+                                adlers, store, stream);
+    } catch (const std::exception& e) {
+        return fail(h, -4, "pg_compress_records_device: %s", e.what());
+    } catch (...) {
+        return fail(h, -4, "pg_compress_records_device: unknown exception");
     }
 }
 

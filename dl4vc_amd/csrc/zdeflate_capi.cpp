@@ -1,0 +1,109 @@
+// zd_* of libdl4vc_pileup.so (include/dl4vc_pileup_gpu.h): the compressor's size bound, its host form (the text of zdeflate.h,
+// serially) and its device form over caller-supplied device buffers.  With -DZD_HOST_ONLY the file compiles with a plain C++
+// compiler into the host entries alone (tools/asan_zdeflate.sh).  Errors go to the text pg_last_error(NULL) returns.
+#include "../../include/dl4vc_pileup_gpu.h"
+#include "zdeflate.h"
+
+#include <mutex>
+#include <string>
+#include <vector>
+
+namespace pgh {
+extern std::string g_err __attribute__((visibility("hidden")));
+}
+#ifdef ZD_HOST_ONLY
+std::string pgh::g_err;
+#else
+#include "zdeflate_device.h"
+#endif
+
+namespace {
+
+int zfail(int code, const std::string& what) {
+    pgh::g_err = what;
+    return code;
+}
+
+bool seg_ok(uint32_t seg) { return seg >= zd::MIN_SEG && seg <= zd::MAX_SEG; }
+
+}  // namespace
+
+extern "C" {
+
+int zd_bound(uint64_t n, uint32_t segment, uint64_t* bound) {
+    if (!bound) return zfail(-1, "zd_bound: null argument");
+    if (!seg_ok(segment)) return zfail(-1, "zd_bound: segment must be 1024..32768 bytes");
+    if (n > zd::MAX_STREAM) return zfail(-1, "zd_bound: more than 2^31 bytes in one stream");
+    *bound = zd::bound(n, segment);
+    return 0;
+}
+
+int zd_deflate_host(const uint8_t* in, uint64_t n, uint32_t segment, uint8_t* out, uint64_t out_cap, uint64_t* size, uint32_t* adler,
+                    int32_t* store) {
+    try {
+        if ((n && !in) || !out || !size || !adler || !store) return zfail(-1, "zd_deflate_host: null argument");
+        if (!seg_ok(segment)) return zfail(-1, "zd_deflate_host: segment must be 1024..32768 bytes");
+        if (n > zd::MAX_STREAM) return zfail(-1, "zd_deflate_host: more than 2^31 bytes in one stream");
+        if (out_cap < zd::bound(n, segment)) return zfail(-1, "zd_deflate_host: the output buffer is smaller than zd_bound");
+        const uint64_t ns = zd::n_segments(n, segment);
+        std::vector<uint32_t> sizes(ns), adlers(ns);
+        std::vector<uint64_t> offs(ns);
+        std::vector<uint16_t> head(zd::HASH_SIZE);
+        // the segments land where the device's gather puts them: one behind the other after the 2-byte header
+        uint64_t at = 2;
+        for (uint64_t k = 0; k < ns; ++k) {
+            const uint32_t len = (uint32_t)(k + 1 < ns ? segment : n - k * segment);
+            const uint8_t* src = in + k * segment;
+            adlers[k] = zd::adler32(src, len);
+            sizes[k] = zd::deflate_segment(src, len, k + 1 == ns, out + at, head.data(), 1);    // (at + seg_cap(len) + 4 <= bound)
+            at += sizes[k];
+        }
+        const zd::StreamInfo r = zd::finish_stream(n, segment, sizes.data(), adlers.data(), offs.data());
+        out[0] = zd::ZLIB_CMF;
+        out[1] = zd::ZLIB_FLG;
+        for (int b = 0; b < 4; ++b) out[at + b] = (uint8_t)(r.adler >> (8 * (3 - b)));
+        *size = r.size;
+        *adler = r.adler;
+        *store = (int32_t)r.store;
+        return 0;
+    } catch (const std::exception& e) {
+        return zfail(-4, std::string("zd_deflate_host: ") + e.what());
+    } catch (...) {
+        return zfail(-4, "zd_deflate_host: unknown exception");
+    }
+}
+
+#ifndef ZD_HOST_ONLY
+int zd_deflate(const uint8_t* in_dev, uint64_t chunk_bytes, int64_t n_chunks, uint32_t segment, int32_t flags, uint8_t* out_dev,
+               uint64_t out_cap, uint64_t* offsets, uint64_t* sizes, uint32_t* adlers, uint8_t* store, void* stream) {
+    static std::mutex mu;
+    static zd::Ctx* ctx = nullptr;             // (a test entry: one set of work buffers per process, kept)
+    try {
+        if (!in_dev || !out_dev || !offsets || !sizes || !adlers || !store) return zfail(-1, "zd_deflate: null argument");
+        if (!seg_ok(segment)) return zfail(-1, "zd_deflate: segment must be 1024..32768 bytes");
+        if (chunk_bytes > zd::MAX_STREAM || n_chunks < 1 || n_chunks > 65535) return zfail(-1, "zd_deflate: 1..65535 chunks of at most 2^31 bytes");
+        if (flags & ~3) return zfail(-1, "zd_deflate: flags are ZD_REVERSED | ZD_RAW_ON_STORE");
+        if (out_cap / (uint64_t)n_chunks < zd::bound(chunk_bytes, segment)) return zfail(-1, "zd_deflate: the output buffer is smaller than n_chunks * zd_bound");
+        std::lock_guard<std::mutex> lk(mu);
+        if (!ctx) ctx = zd::ctx_create();
+        hipStream_t s = (hipStream_t)stream;
+        zd::Streams r{};
+        const char* msg = nullptr;
+        if (zd::run(ctx, in_dev, chunk_bytes, n_chunks, segment, flags & ZD_REVERSED, flags & ZD_RAW_ON_STORE, out_dev, s, nullptr, &r, &msg))
+            return zfail(-2, std::string("zd_deflate: ") + msg);
+        hipError_t e = hipMemcpyAsync(offsets, r.offs, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(sizes, r.sizes, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(adlers, r.adlers, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(store, r.store, (size_t)n_chunks, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return zfail(-2, std::string("zd_deflate: device: ") + hipGetErrorString(e));
+        return 0;
+    } catch (const std::exception& e) {
+        return zfail(-4, std::string("zd_deflate: ") + e.what());
+    } catch (...) {
+        return zfail(-4, "zd_deflate: unknown exception");
+    }
+}
+#endif
+
+}  // extern "C"

@@ -33,6 +33,16 @@ def record_dtype(store_reads: int = STORE_MAX_READS, window: int = WINDOW) -> np
     return np.dtype(fields)          # packed: offsets are cumulative sizes
 
 
+PLANE_FIELDS = ("single_reads", "q-scores", "strand")
+
+
+def blob_dtype(window: int = WINDOW) -> np.dtype:
+    """A record without its three planes, the other members in the record's order and packed as there (149 + 16 * window
+    bytes): what the host hands ``pg_compress_records_device`` per record, next to the planes that stay on the device."""
+    dt = record_dtype(1, window)
+    return np.dtype([(n, dt.fields[n][0]) for n in dt.names if n not in PLANE_FIELDS])
+
+
 def field_offsets(store_reads: int = STORE_MAX_READS, window: int = WINDOW):
     dt = record_dtype(store_reads, window)
     return {name: dt.fields[name][1] for name in dt.names}, dt.itemsize
@@ -40,3 +50,4 @@ def field_offsets(store_reads: int = STORE_MAX_READS, window: int = WINDOW):
 
 assert record_dtype().itemsize == 123965
 assert field_offsets()[0]["single_reads"] == 3031 and field_offsets()[0]["strand"] == 83765
+assert blob_dtype().itemsize == 149 + 16 * WINDOW == record_dtype().itemsize - 3 * STORE_MAX_READS * WINDOW

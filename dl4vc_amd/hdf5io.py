@@ -4,7 +4,8 @@ The reference reads ``hdfile['data'][idx]`` through h5py (dl4vc/dataset.py:500-5
 compound record at a time.  h5py is not installable here, so this module offers two back-ends behind
 one class: h5py when it is importable, otherwise ``libhdf5`` (1.10) through ctypes.  Records are read
 in RANGES (one H5Dread per batch) in the packed on-disk layout of ``hdf5_schema.record_dtype`` -- no
-type conversion, no per-record Python work.
+type conversion, no per-record Python work.  ``ChunkWriter`` writes the same dataset from chunks that were compressed
+elsewhere (the GPU compressor of libdl4vc_pileup.so), with ``H5Dwrite_chunk``.
 """
 from __future__ import annotations
 
@@ -318,3 +319,219 @@ def append_candidates(path: str, records: np.ndarray) -> int:
     if rc < 0:
         raise OSError("appending %d records to %s failed" % (n, path))
     return n0 + n
+
+
+# ---- chunks compressed elsewhere (the GPU compressor of libdl4vc_pileup.so), written past the filter -------------------------
+FILTER_DEFLATE = 1
+
+
+def _chunk_api(lib):
+    """The direct-chunk and layout calls (libhdf5 >= 1.10.3), bound on first use."""
+    if getattr(lib, "_chunk_bound", False):
+        return lib
+    sig = {
+        "H5Dwrite_chunk": (C.c_int, [hid_t, hid_t, C.c_uint32, C.POINTER(hsize_t), C.c_size_t, C.c_void_p]),
+        "H5Dget_create_plist": (hid_t, [hid_t]), "H5Pget_chunk": (C.c_int, [hid_t, C.c_int, C.POINTER(hsize_t)]),
+        "H5Pget_nfilters": (C.c_int, [hid_t]),
+        "H5Pget_filter2": (C.c_int, [hid_t, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_size_t), C.POINTER(C.c_uint), C.c_size_t,
+                                     C.c_char_p, C.POINTER(C.c_uint)]),
+        "H5Dget_chunk_storage_size": (C.c_int, [hid_t, C.POINTER(hsize_t), C.POINTER(hsize_t)]),
+    }
+    for name, (res, args) in sig.items():
+        if not hasattr(lib, name):
+            raise RuntimeError("this libhdf5 has no %s: writing compressed chunks directly needs HDF5 1.10.3 or newer" % name)
+        f = getattr(lib, name)
+        f.restype, f.argtypes = res, args
+    lib._chunk_bound = True
+    return lib
+
+
+def _layout_of(lib, did):
+    pl = lib.H5Dget_create_plist(did)
+    dims = (hsize_t * 1)()
+    rank = lib.H5Pget_chunk(pl, 1, dims)
+    filters = []
+    for i in range(max(0, lib.H5Pget_nfilters(pl))):
+        flags, ncd, cd = C.c_uint(0), C.c_size_t(8), (C.c_uint * 8)()
+        fid = lib.H5Pget_filter2(pl, i, C.byref(flags), C.byref(ncd), cd, 0, None, None)
+        filters.append((int(fid), tuple(int(cd[k]) for k in range(ncd.value))))
+    lib.H5Pclose(pl)
+    return (int(dims[0]) if rank == 1 else None), filters
+
+
+def dataset_layout(path: str):
+    """-> (length, chunk size in records or None, [(filter id, its values)]) of the ``data`` dataset."""
+    lib = _chunk_api(libhdf5())
+    fid = lib.H5Fopen(path.encode(), H5F_ACC_RDONLY, 0)
+    if fid < 0:
+        raise OSError("cannot open %s as HDF5" % path)
+    did = lib.H5Dopen2(fid, DATASET_NAME.encode(), 0)
+    if did < 0:
+        lib.H5Fclose(fid)
+        raise KeyError("%s has no dataset '%s'" % (path, DATASET_NAME))
+    sid = lib.H5Dget_space(did)
+    dims = (hsize_t * 1)()
+    lib.H5Sget_simple_extent_dims(sid, dims, None)
+    lib.H5Sclose(sid)
+    chunk, filters = _layout_of(lib, did)
+    lib.H5Dclose(did)
+    lib.H5Fclose(fid)
+    return int(dims[0]), chunk, filters
+
+
+class ChunkWriter:
+    """Writes the ``data`` dataset chunk by chunk with ``H5Dwrite_chunk``: the chunks arrive compressed (zlib streams the
+    deflate filter reads back, or raw bytes with the filter skipped) and go to the file as they are.  The dataset is created
+    with ``write_candidates``'s properties -- chunks of ``chunk`` records, deflate ``gzip`` in the pipeline, unlimited -- so any
+    HDF5 reader sees an ordinary gzip-chunked dataset.
+
+    A chunk is only ever written whole and at a multiple of ``chunk``.  ``write_chunks`` takes chunks compressed elsewhere and
+    needs the dataset's length to be such a multiple; ``append_records`` takes records, compresses every full chunk with the
+    compressor's CPU twin (``zd_deflate_host``) and CARRIES the tail of fewer than ``chunk`` records to the next call;
+    ``close`` writes a carried tail as the last chunk, padded with zero records (HDF5 stores an edge chunk at full size; the
+    dataset's length says how many are real).  Appending to a file whose length is not a multiple of its chunk size is
+    refused: its partial last chunk would have to be rewritten."""
+
+    def __init__(self, path: str, dtype: np.dtype, chunk: int = 8, gzip: int = 4, append: bool = False):
+        lib = self._lib = _chunk_api(libhdf5())
+        self.path, self.dtype, self.chunk = path, np.dtype(dtype), int(chunk)
+        self.pending = np.zeros(0, self.dtype)
+        self.write_s = 0.0                      # wall time inside H5Dset_extent / H5Dwrite_chunk
+        self.host_chunks = self.direct_chunks = self.stored_chunks = 0
+        self.bytes_written = 0
+        self._did = self._fid = -1
+        self._tail_written = False
+        if append:
+            self._fid = lib.H5Fopen(path.encode(), H5F_ACC_RDWR, 0)
+            if self._fid < 0:
+                raise OSError("cannot open %s for appending" % path)
+            self._did = lib.H5Dopen2(self._fid, DATASET_NAME.encode(), 0)
+            if self._did < 0:
+                lib.H5Fclose(self._fid)
+                raise KeyError("%s has no dataset '%s'" % (path, DATASET_NAME))
+            sid = lib.H5Dget_space(self._did)
+            dims = (hsize_t * 1)()
+            lib.H5Sget_simple_extent_dims(sid, dims, None)
+            lib.H5Sclose(sid)
+            self.n = int(dims[0])
+            have, filters = _layout_of(lib, self._did)
+            tid = lib.H5Dget_type(self._did)
+            size = int(lib.H5Tget_size(tid))
+            lib.H5Tclose(tid)
+            why = None
+            if have != self.chunk or [f[0] for f in filters] != [FILTER_DEFLATE] or size != self.dtype.itemsize:
+                why = "its dataset has chunks of %s records of %d bytes and filters %s, not chunks of %d records of %d bytes and deflate" \
+                      % (have, size, [f[0] for f in filters], self.chunk, self.dtype.itemsize)
+            elif self.n % self.chunk:
+                why = "it holds %d records, not a multiple of the chunk size %d: its partial last chunk would have to be rewritten " \
+                      "(append without --compress-device gpu, or start a new file)" % (self.n, self.chunk)
+            if why:
+                self.close()
+                raise ValueError("cannot append compressed chunks to %s: %s" % (path, why))
+            return
+        self._fid = lib.H5Fcreate(path.encode(), H5F_ACC_TRUNC, 0, 0)
+        if self._fid < 0:
+            raise OSError("cannot create %s" % path)
+        tid = _h5_compound_type(lib, self.dtype)
+        sid = lib.H5Screate_simple(1, (hsize_t * 1)(0), (hsize_t * 1)(H5S_UNLIMITED))
+        pl = lib.H5Pcreate(lib._g("H5P_CLS_DATASET_CREATE_ID_g"))
+        lib.H5Pset_chunk(pl, 1, (hsize_t * 1)(self.chunk))
+        lib.H5Pset_deflate(pl, gzip)
+        self._did = lib.H5Dcreate2(self._fid, DATASET_NAME.encode(), tid, sid, 0, pl, 0)
+        for closer, h in ((lib.H5Pclose, pl), (lib.H5Sclose, sid), (lib.H5Tclose, tid)):
+            closer(h)
+        self.n = 0
+        if self._did < 0:
+            self.close()
+            raise OSError("H5Dcreate2 failed")
+
+    @property
+    def chunk_bytes(self) -> int:
+        return self.chunk * self.dtype.itemsize
+
+    def __len__(self):
+        return self.n + len(self.pending)
+
+    def _put(self, first: int, n_records: int, pieces):
+        """``pieces``: (buffer, offset, size, store) per chunk, the first one at record ``first``."""
+        import time
+        if self._did < 0:
+            raise ValueError("the writer is closed")
+        if self._tail_written or first % self.chunk:
+            raise ValueError("a chunk would start at record %d, not at a multiple of %d" % (first, self.chunk))
+        lib = self._lib
+        t0 = time.perf_counter()
+        if lib.H5Dset_extent(self._did, (hsize_t * 1)(first + n_records)) < 0:
+            raise OSError("H5Dset_extent(%d) failed on %s" % (first + n_records, self.path))
+        for c, (buf, off, size, store) in enumerate(pieces):
+            if store and size != self.chunk_bytes:
+                raise ValueError("a chunk without the filter holds %d bytes, not %d" % (size, self.chunk_bytes))
+            ptr = C.c_void_p(buf.ctypes.data + off)
+            if lib.H5Dwrite_chunk(self._did, 0, 1 if store else 0, (hsize_t * 1)(first + c * self.chunk), size, ptr) < 0:
+                raise OSError("H5Dwrite_chunk failed on %s at record %d" % (self.path, first + c * self.chunk))
+            self.bytes_written += size
+            self.stored_chunks += bool(store)
+        self.write_s += time.perf_counter() - t0
+        self.n = first + n_records
+        self._tail_written = bool(n_records % self.chunk)
+
+    def write_chunks(self, chunks) -> int:
+        """``chunks``: ``pileup_gpu.CompressedChunks`` (``n_records`` records in ``ceil(n_records / chunk)`` chunks, every one
+        full but the last, which is padded).  The dataset's length must be a multiple of the chunk size and no tail carried."""
+        if len(self.pending):
+            raise ValueError("%d carried records: compressed chunks would not start at a multiple of %d" % (len(self.pending), self.chunk))
+        if len(chunks) != -(-chunks.n_records // self.chunk):
+            raise ValueError("%d records in %d chunks of %d" % (chunks.n_records, len(chunks), self.chunk))
+        data = np.ascontiguousarray(chunks.data, np.uint8)
+        for c in range(len(chunks)):
+            if int(chunks.offsets[c]) + int(chunks.sizes[c]) > data.size:
+                raise ValueError("chunk %d lies outside the data" % c)
+        self._put(self.n, chunks.n_records, [(data, int(chunks.offsets[c]), int(chunks.sizes[c]), int(chunks.store[c]))
+                                             for c in range(len(chunks))])
+        self.direct_chunks += len(chunks)
+        return self.n
+
+    def _host_chunk(self, recs: np.ndarray):
+        from . import pileup_gpu
+        raw = np.zeros(self.chunk, self.dtype)
+        raw[:len(recs)] = recs
+        stream, _adler, store = pileup_gpu.zd_deflate_host(raw)
+        buf = raw.view(np.uint8).reshape(-1) if store else np.frombuffer(stream, np.uint8)
+        self._put(self.n, len(recs), [(buf, 0, buf.size, store)])
+        self.host_chunks += 1
+
+    def append_records(self, records: np.ndarray) -> int:
+        """Records in the dataset's dtype: full chunks are compressed on the host and written, the tail is carried."""
+        if len(records):
+            if records.dtype != self.dtype:
+                raise ValueError("records of another layout")
+            self.pending = np.concatenate([self.pending, records]) if len(self.pending) else np.array(records)
+        while len(self.pending) >= self.chunk:
+            self._host_chunk(self.pending[:self.chunk])
+            self.pending = self.pending[self.chunk:]
+        return len(self)
+
+    def need(self) -> int:
+        """Records ``append_records`` must still get before ``write_chunks`` may be called."""
+        return (self.chunk - len(self.pending)) % self.chunk
+
+    def close(self):
+        try:
+            if self._did >= 0 and len(self.pending):
+                tail, self.pending = self.pending, self.pending[:0]
+                self._host_chunk(tail)
+        finally:
+            if self._did >= 0:
+                self._lib.H5Dclose(self._did)
+                self._did = -1
+            if self._fid >= 0:
+                self._lib.H5Fclose(self._fid)
+                self._fid = -1
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, *a):
+        if exc_type is not None:
+            self.pending = self.pending[:0]        # (nothing more is written behind an error)
+        self.close()

@@ -420,7 +420,8 @@ def encode_location(bam, fasta, loc: Location, opt: EncoderOptions, reader=None)
 
 def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Location], opt: EncoderOptions,
                      native: Optional[bool] = None, threads: int = 1, device: Optional[str] = None,
-                     device_id: int = 0, inflate_device: Optional[str] = None) -> Tuple[np.ndarray, int]:
+                     device_id: int = 0, inflate_device: Optional[str] = None, compress_device: Optional[str] = None,
+                     pending: int = 0, records_per_chunk: int = 8):
     """Records for ``locations`` in input order and the number of locations that produced none.
 
     ``native`` (default: when libdl4vc_loader.so is built): the image planes come from the C++ encoder (``pe_encode``:
@@ -434,6 +435,13 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
     ``inflate_device="gpu"`` (with ``device="gpu"`` only): the GPU encoder inflates the BAM's BGZF blocks and frames its records on
     the device as well (needs the ``.bai``; same bytes, tests/test_pileup_inflate_gpu.py).
 
+    ``compress_device="gpu"`` (with ``device="gpu"`` only): instead of the record array, a generator of ``EncodedBatch`` -- one
+    per ``COMPRESS_BATCH`` locations -- whose records were packed into the HDF5 compound layout and compressed into the
+    dataset's chunks on the device (``pg_compress_records_device``); only the compressed bytes come to the host, and no record
+    array of the whole step is ever held.  ``pending``: the records a ``hdf5io.ChunkWriter`` already carries; each batch hands
+    the few records in front of and behind its whole chunks over as ordinary records (``head`` / ``tail``), so every compressed
+    chunk starts at a multiple of ``records_per_chunk`` (tests/test_compress_gpu.py).
+
     Raises ``ValueError`` naming the read where a location's window holds a read the specification has no answer for (a
     zero-length alignment such as ``0M 5I``, a SEQ shorter than the CIGAR's query length such as SEQ ``*``): the native and
     GPU encoders decline such a location, so all three paths end here (tests/test_pileup_edges.py)."""
@@ -445,6 +453,12 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
         raise ValueError("inflate_device must be None or 'gpu', not %r" % (inflate_device,))
     if inflate_device == "gpu" and device != "gpu":
         raise ValueError("inflate_device='gpu' is the GPU pileup encoder's option: it needs device='gpu'")
+    if compress_device not in (None, "gpu"):
+        raise ValueError("compress_device must be None or 'gpu', not %r" % (compress_device,))
+    if compress_device == "gpu":
+        if device != "gpu":
+            raise ValueError("compress_device='gpu' compresses the GPU pileup encoder's planes where they lie: it needs device='gpu'")
+        return _encode_compressed(bam_path, fasta_path, locations, opt, threads, device_id, inflate_device, pending, records_per_chunk)
     dtype = record_dtype(opt.max_reads, 2 * opt.window_size + 1)
     out = np.zeros(len(locations), dtype)
     n = errors = 0
@@ -497,3 +511,101 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
             bam.close()
             fasta.close()
     return out[:n], errors
+
+
+COMPRESS_BATCH = 4096          # locations per device batch of encode_locations(compress_device="gpu")
+
+
+@dataclass
+class EncodedBatch:
+    """One batch of ``encode_locations(compress_device="gpu")``, in the order it goes to a ``hdf5io.ChunkWriter``:
+    ``append_records(head)``, ``write_chunks(chunks)`` (None where the batch holds no whole chunk), ``append_records(tail)``."""
+    head: np.ndarray
+    chunks: object
+    tail: np.ndarray
+    records: int
+    errors: int
+    stats: dict
+
+
+def _encode_compressed(bam_path, fasta_path, locations, opt, threads, device_id, inflate_device, pending, chunk):
+    import torch
+    from . import loader, pileup_gpu
+    from .bamio import BamFile, FastaFile, WindowReader
+    from .hdf5_schema import blob_dtype
+    W = 2 * opt.window_size + 1
+    dtype, bdt = record_dtype(opt.max_reads, W), blob_dtype(W)
+    if not len(locations):
+        return
+    dev = torch.device("cuda", device_id)
+    B = min(COMPRESS_BATCH, len(locations))
+    stored = [torch.empty((B, opt.max_reads, W), dtype=torch.uint8, device=dev) for _ in range(3)]
+    args = (opt.window_size, opt.max_reads, opt.max_insert_length, opt.max_insert_length_variant, opt.min_base_quality)
+    cpu = bam = fasta = reader = None
+    enc = pileup_gpu.GpuPileupEncoder(bam_path, fasta_path, *args, device=device_id, inflate_device=inflate_device)
+    try:
+        for l0 in range(0, len(locations), B):
+            locs = locations[l0:l0 + B]
+            contigs, positions = [l.contig for l in locs], [l.pos for l in locs]
+            planes = enc.encode_device(contigs, positions, out=stored)
+            reads, qual, strand, ref, num, status = planes
+            stats = enc.stats()
+            # what the GPU declines goes to pe_encode, what that declines to the Python encoder; their planes into the slots
+            declined = np.flatnonzero(status == 2)
+            if len(declined):
+                if cpu is None:
+                    cpu = loader.NativePileupEncoder(bam_path, fasta_path, *args)
+                sub = cpu.encode([contigs[i] for i in declined], [positions[i] for i in declined], threads)
+                for k, i in enumerate(declined):
+                    st, host = int(sub[5][k]), None
+                    if st == 1:
+                        host = (sub[0][k], sub[1][k], sub[2][k], sub[3][k], int(sub[4][k]))
+                    elif st == 2:
+                        if bam is None:
+                            bam, fasta = BamFile(bam_path), FastaFile(fasta_path)
+                            reader = WindowReader(bam)
+                        res = encode_location(bam, fasta, locs[i], opt, reader)
+                        rec = finish_record(res, locs[i], opt, dtype) if res is not None else None
+                        st = 0
+                        if rec is not None:
+                            host, st = (rec["single_reads"], rec["q-scores"], rec["strand"], rec["ref_bases"], int(rec["num_reads"])), 1
+                    status[i] = st
+                    if host is not None:
+                        for plane, src in zip((reads, qual, strand), host[:3]):
+                            plane[int(i)].copy_(torch.from_numpy(np.ascontiguousarray(src, np.uint8)))
+                        ref[i], num[i] = host[3], host[4]
+            keep = np.flatnonzero(status == 1)
+            m = len(keep)
+            blob = np.zeros(m, bdt)
+            blob["ref_bases"], blob["num_reads"] = ref[keep], num[keep]
+            if m:
+                blob["name"] = [locs[i].name.encode()[:bdt["name"].itemsize] for i in keep]
+                blob["label"] = [locs[i].label for i in keep]
+                blob["vcfrec"] = [locs[i].vcf_string.encode()[:bdt["vcfrec"].itemsize] for i in keep]
+
+            def records(lo, hi):
+                out = np.zeros(hi - lo, dtype)
+                if hi > lo:
+                    idx = torch.from_numpy(keep[lo:hi]).to(dev)
+                    for name, plane in zip(("single_reads", "q-scores", "strand"), (reads, qual, strand)):
+                        out[name] = plane[idx].cpu().numpy()
+                    for name in bdt.names:
+                        out[name] = blob[name][lo:hi]
+                return out
+
+            n_head = min((chunk - pending) % chunk, m)
+            n_tail = (m - n_head) % chunk
+            head, tail = records(0, n_head), records(m - n_tail, m)
+            chunks = None
+            if m - n_tail > n_head:
+                chunks = enc.compress_records((reads, qual, strand), keep[n_head:m - n_tail], blob[n_head:m - n_tail], chunk)
+                stats = enc.stats()
+            pending = (pending + m) % chunk
+            yield EncodedBatch(head, chunks, tail, m, int((status == 0).sum()), stats)
+    finally:
+        enc.close()
+        if cpu is not None:
+            cpu.close()
+        if bam is not None:
+            bam.close()
+            fasta.close()

@@ -17,7 +17,10 @@ from .loader import PileupOptions
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_pileup.so")
 SYMBOLS = ("pg_open", "pg_encode", "pg_encode_device", "pg_assemble_device", "pg_close", "pg_last_error",
-           "pg_set_inflate_device", "pg_get_stats", "pg_debug_run_records")
+           "pg_set_inflate_device", "pg_get_stats", "pg_debug_run_records", "pg_compress_records_device")
+ZD_SYMBOLS = ("zd_bound", "zd_deflate_host", "zd_deflate")      # the zlib compressor of the same library (csrc/zdeflate.h)
+ZD_MIN_SEGMENT, ZD_MAX_SEGMENT, ZD_DEFAULT_SEGMENT = 1024, 32768, 16384
+ZD_REVERSED, ZD_RAW_ON_STORE = 1, 2
 MAX_TRACKS = 1024            # PG_MAX_TRACKS
 MAX_WINDOW = 100             # PG_MAX_WINDOW
 _lib = None
@@ -26,7 +29,9 @@ _lib = None
 class Stats(C.Structure):
     """``pg_stats``: the stages of the last ``pg_encode`` / ``pg_encode_device`` call (times in ms)."""
     _fields_ = [(n, C.c_double) for n in ("host_frame_ms", "read_ms", "upload_ms", "inflate_ms", "frame_ms", "encode_ms", "copy_back_ms")] + \
-               [(n, C.c_int64) for n in ("host_records", "blocks", "compressed_bytes", "inflated_bytes", "records", "groups")]
+               [(n, C.c_int64) for n in ("host_records", "blocks", "compressed_bytes", "inflated_bytes", "records", "groups")] + \
+               [(n, C.c_double) for n in ("pack_ms", "deflate_ms", "gather_ms", "compress_copy_back_ms")] + \
+               [(n, C.c_int64) for n in ("chunks", "raw_bytes", "chunk_bytes_out", "stored_chunks")]
 
 
 class RecView(C.Structure):
@@ -81,6 +86,11 @@ def load_library() -> C.CDLL:
                                            [C.c_int32, C.c_int32] + [vp] * 6 + [vp])
         lib.pg_set_inflate_device.argtypes = [vp, C.c_int, C.c_uint64]
         lib.pg_get_stats.argtypes = [vp, C.POINTER(Stats)]
+        lib.pg_compress_records_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.POINTER(vp), vp, vp, vp, vp, vp]
+        lib.zd_bound.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+        lib.zd_deflate_host.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_int32)]
+        lib.zd_deflate.argtypes = [vp, C.c_uint64, C.c_int64, C.c_uint32, C.c_int32, vp, C.c_uint64, vp, vp, vp, vp, vp]
         _bind_debug(lib)
         lib.pg_close.argtypes = [vp]
         lib.pg_close.restype = None
@@ -88,6 +98,61 @@ def load_library() -> C.CDLL:
         lib.pg_last_error.restype = C.c_char_p
         _lib = lib
     return _lib
+
+
+def _zd_check(lib, rc, what):
+    if rc != 0:
+        raise RuntimeError("%s failed: %s" % (what, lib.pg_last_error(None).decode()))
+
+
+def zd_bound(n: int, segment: int = ZD_DEFAULT_SEGMENT) -> int:
+    """``zd_bound``: no stream of ``n`` input bytes is longer."""
+    lib = load_library()
+    b = C.c_uint64(0)
+    _zd_check(lib, lib.zd_bound(int(n), int(segment), C.byref(b)), "zd_bound")
+    return b.value
+
+
+def zd_deflate_host(data, segment: int = ZD_DEFAULT_SEGMENT):
+    """``zd_deflate_host`` -> (the zlib stream as bytes, Adler-32, store): the CPU twin of the device compressor.  ``store``: the
+    stream is not smaller than ``data`` (it is still a valid stream within ``zd_bound``)."""
+    lib = load_library()
+    src = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    out = np.empty(zd_bound(src.size, segment), np.uint8)
+    size, adler, store = C.c_uint64(0), C.c_uint32(0), C.c_int32(0)
+    _zd_check(lib, lib.zd_deflate_host(src.ctypes.data_as(C.c_void_p) if src.size else None, src.size, int(segment),
+                                       out.ctypes.data_as(C.c_void_p), out.size, C.byref(size), C.byref(adler), C.byref(store)),
+              "zd_deflate_host")
+    return out[:size.value].tobytes(), adler.value, bool(store.value)
+
+
+def zd_deflate_device(in_ptr: int, chunk_bytes: int, n_chunks: int, out_ptr: int, out_cap: int, segment: int = ZD_DEFAULT_SEGMENT,
+                      flags: int = 0, stream: int = 0):
+    """``zd_deflate``: ``n_chunks`` streams of the device buffer at ``in_ptr`` into the device buffer at ``out_ptr`` ->
+    (offsets, sizes u64, adlers u32, store u8), host arrays, one entry per chunk."""
+    lib = load_library()
+    offs, sizes = np.zeros(n_chunks, np.uint64), np.zeros(n_chunks, np.uint64)
+    adlers, store = np.zeros(n_chunks, np.uint32), np.zeros(n_chunks, np.uint8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    _zd_check(lib, lib.zd_deflate(C.c_void_p(in_ptr), int(chunk_bytes), int(n_chunks), int(segment), int(flags), C.c_void_p(out_ptr),
+                                  int(out_cap), p(offs), p(sizes), p(adlers), p(store), C.c_void_p(stream or None)), "zd_deflate")
+    return offs, sizes, adlers, store
+
+
+class CompressedChunks:
+    """Chunks of the candidate dataset as ``hdf5io.ChunkWriter.write_chunks`` takes them: ``n_records`` records in
+    ``len(sizes)`` chunks; chunk ``c`` is ``data[offsets[c]:offsets[c] + sizes[c]]`` -- its zlib stream, or its raw bytes where
+    ``store[c]`` is set."""
+
+    def __init__(self, n_records, data, offsets, sizes, adlers, store):
+        self.n_records, self.data, self.offsets, self.sizes, self.adlers, self.store = n_records, data, offsets, sizes, adlers, store
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def chunk(self, c: int) -> bytes:
+        o = int(self.offsets[c])
+        return self.data[o:o + int(self.sizes[c])].tobytes()
 
 
 class GpuPileupEncoder:
@@ -190,6 +255,37 @@ class GpuPileupEncoder:
                                                 int(window if window is not None else self.window), p(slots), p(rows), p(first), m, R,
                                                 *[p(a) for a in lines], int(bool(use_q)), int(bool(use_strand)),
                                                 *[v(x) for x in out_ptrs], v(stream)), "pg_assemble_device")
+
+    def compress_records(self, planes, slots, blob: np.ndarray, records_per_chunk: int = 8, stream=None) -> CompressedChunks:
+        """``pg_compress_records_device``: the records whose stored planes lie at ``slots`` of ``planes`` (the three device
+        tensors ``encode_device`` returned) and whose other members are ``blob`` (``hdf5_schema.blob_dtype``, one entry per
+        record) -> the dataset's chunks, packed and compressed on the device.  The last chunk is padded with zero records.
+        The returned bytes are a copy: they stay valid after the next call."""
+        import torch
+        reads, qual, strand = planes
+        n_slots = int(reads.shape[0])
+        slots = np.ascontiguousarray(slots, np.int32)
+        n = len(slots)
+        blob = np.ascontiguousarray(blob)
+        want = 149 + 16 * self.window
+        if blob.dtype.itemsize != want or len(blob) != n:
+            raise ValueError("blob: %d entries of %d bytes, not %d of %d" % (n, want, len(blob), blob.dtype.itemsize))
+        for x in planes:
+            if x.dtype != torch.uint8 or not x.is_contiguous() or tuple(x.shape) != (n_slots, self.max_reads, self.window):
+                raise ValueError("planes: three contiguous uint8 tensors [%d][%d][%d]" % (n_slots, self.max_reads, self.window))
+        nc = -(-n // records_per_chunk)
+        offs, sizes = np.zeros(nc, np.uint64), np.zeros(nc, np.uint64)
+        adlers, store = np.zeros(nc, np.uint32), np.zeros(nc, np.uint8)
+        out = C.c_void_p()
+        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        t = lambda x: C.c_void_p(x.data_ptr() if x.numel() else None)   # noqa: E731
+        self._check(self.lib.pg_compress_records_device(self._h, t(reads), t(qual), t(strand), n_slots, p(slots), p(blob), n,
+                                                        int(records_per_chunk), C.byref(out), p(offs), p(sizes), p(adlers), p(store),
+                                                        C.c_void_p(s.cuda_stream)), "pg_compress_records_device")
+        total = int(offs[-1] + sizes[-1]) if nc else 0
+        data = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), (total,)).copy() if total else np.zeros(0, np.uint8)
+        return CompressedChunks(n, data, offs, sizes, adlers, store)
 
     def close(self):
         if self._h is not None:

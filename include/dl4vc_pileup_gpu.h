@@ -94,8 +94,51 @@ typedef struct {
     int64_t blocks, compressed_bytes, inflated_bytes;
     int64_t records;          /* records listed for the runs (a record shared by two runs counts twice) */
     int64_t groups;
+    /* the last pg_compress_records_device call (device time between events on the caller's stream; an encode call clears them) */
+    double pack_ms;           /* blob and slot upload, hdf_pack_kernel */
+    double deflate_ms;        /* zd_deflate_kernel */
+    double gather_ms;         /* stream sizes, their scan, zd_gather_kernel */
+    double compress_copy_back_ms;   /* the chunks' bytes and their table to the host */
+    int64_t chunks, raw_bytes, chunk_bytes_out, stored_chunks;
 } pg_stats;
 int pg_get_stats(const pg_encoder_t* h, pg_stats* out);
+
+/* ---- candidate HDF5 chunks compressed on the device ---------------------------------------------------------------------------
+ * The zlib compressor (csrc/zdeflate.h): an RFC 1950 stream of fixed-Huffman DEFLATE blocks, the input cut into segments of
+ * `segment` bytes (ZD_MIN_SEGMENT..ZD_MAX_SEGMENT) that are compressed on their own and joined byte-aligned, so the bytes depend
+ * on the input and the segment size alone.  zlib's inflate (and so HDF5's deflate filter) reads it.  A stream that is not smaller
+ * than its input is flagged "store": it is still a valid stream within zd_bound, and the writer of an HDF5 chunk passes the raw
+ * bytes with filter mask 1 instead.  Errors: the text pg_last_error(NULL) returns. */
+#define ZD_MIN_SEGMENT 1024
+#define ZD_MAX_SEGMENT 32768
+#define ZD_DEFAULT_SEGMENT 16384
+#define ZD_REVERSED 1        /* zd_deflate: the kernel takes the segments in the opposite launch order (same bytes) */
+#define ZD_RAW_ON_STORE 2    /* zd_deflate: a "store" chunk's output is its raw bytes (size = chunk_bytes), not its stream */
+int zd_bound(uint64_t n, uint32_t segment, uint64_t* bound);      /* n <= 2^31; no stream of n bytes is longer */
+/* CPU twin: the same text, the segments one after the other.  out_cap >= zd_bound. */
+int zd_deflate_host(const uint8_t* in, uint64_t n, uint32_t segment, uint8_t* out, uint64_t out_cap, uint64_t* size, uint32_t* adler,
+                    int32_t* store);
+/* n_chunks (1..65535) streams, one per chunk of chunk_bytes of in_dev (DEVICE), written one behind the other into out_dev (DEVICE,
+ * out_cap >= n_chunks * zd_bound; nothing but the streams' own bytes is written).  offsets / sizes / adlers / store [n_chunks]: HOST.
+ * Runs on `stream` (a hipStream_t, NULL = the default stream) and returns when the streams are written. */
+int zd_deflate(const uint8_t* in_dev, uint64_t chunk_bytes, int64_t n_chunks, uint32_t segment, int32_t flags, uint8_t* out_dev,
+               uint64_t out_cap, uint64_t* offsets, uint64_t* sizes, uint32_t* adlers, uint8_t* store, void* stream);
+/* n_records candidate records -> the chunks of the HDF5 dataset, compressed.  Record i is packed on the device in the layout of
+ * dl4vc_amd/hdf5_schema.py (packed compound, window = the encoder's 2 w + 1, max_reads stored rows) from
+ *   the stored planes at slot slots[i] (HOST int32, each in [0, n_slots)) of reads_dev / qual_dev / strand_dev
+ *     (DEVICE [n_slots][max_reads][window], what pg_encode_device wrote), and
+ *   blob[i] (HOST, blob_bytes = 149 + 16 * window each): the record's other members as the schema lays them out, the three
+ *     planes left out -- name, ref, reads | ref_bases, num_reads, label, vcfrec.
+ * Chunk c holds records [c * records_per_chunk, ...); the last chunk is padded with zero bytes to the full records_per_chunk
+ * (HDF5 stores edge chunks at full size).  Every chunk is compressed with ZD_DEFAULT_SEGMENT; *out (HOST, pinned, the encoder's
+ * own: valid until the next call or pg_close) holds chunk c's bytes at offsets[c], sizes[c] of them: its zlib stream, or, where
+ * store[c] != 0, its raw bytes (H5Dwrite_chunk with filter mask 1).  offsets / sizes / adlers / store: HOST
+ * [ceil(n_records / records_per_chunk)].  Runs behind the work already enqueued on `stream` (a hipStream_t, NULL = the default
+ * stream), on it, and returns when the bytes are on the host. */
+int pg_compress_records_device(pg_encoder_t* h, const uint8_t* reads_dev, const uint8_t* qual_dev, const uint8_t* strand_dev,
+                               int64_t n_slots, const int32_t* slots, const uint8_t* blob, int64_t n_records,
+                               int32_t records_per_chunk, const uint8_t** out, uint64_t* offsets, uint64_t* sizes, uint32_t* adlers,
+                               uint8_t* store, void* stream);
 
 /* Test hook, no device call: the framed records of the run [s0, stop) of contig `tid`, by the host path (path 0) or by the
  * CPU twin of the device path (path 1: index ranges, the host form of the inflate, the shared frame core, serially; path 2:

@@ -10,6 +10,8 @@ VCF(s) -> ``candidates.hdf`` in the record layout main.py reads.  Same flags as 
 (``--tp_vcf`` / ``--tp_full_vcf`` / ``--fn_vcf`` label locations 0 / 1 as the reference does.)  Options of the reference that
 this path never used are refused, not ignored.  BAM / BAI / FASTA are read by dl4vc_amd/bamio.py (no htslib needed); records
 are written in input order; ``--num-processes`` worker processes each take contiguous runs of locations.
+``--pileup-device gpu`` builds the records' planes on the GPU; ``--compress-device gpu`` (with it) also packs and compresses the
+file's chunks there and writes them past the HDF5 filter: the same records, in chunks another encoder compressed.
 """
 import argparse
 import math
@@ -29,6 +31,41 @@ from dl4vc_amd.pileup_encoder import EncoderOptions, encode_locations, locations
 def _work(task):
     bam, fasta, locs, opt = task
     return encode_locations(bam, fasta, locs, opt)
+
+
+def _convert_compressed(args, locations, opt, start, step, procs, append):
+    """The loop of ``main`` with ``--compress-device gpu``: every batch's whole chunks arrive compressed and go to the file with
+    ``H5Dwrite_chunk``; ``hdf5io.ChunkWriter`` carries the records between them, across batches and process steps."""
+    import json
+    from dl4vc_amd.hdf5_schema import record_dtype
+    n_loc = len(locations)
+    dtype = record_dtype(opt.max_reads, 2 * opt.window_size + 1)
+    total_errors = written = 0
+    stages = {k: 0.0 for k in ("pack_ms", "deflate_ms", "gather_ms", "compress_copy_back_ms", "raw_bytes", "chunk_bytes_out", "stored_chunks")}
+    t0 = time.time()
+    try:
+        writer = hdf5io.ChunkWriter(args.output, dtype, chunk=8, append=append)
+    except ValueError as e:
+        raise SystemExit("--compress-device gpu: %s" % e)
+    with writer:
+        while start < n_loc:
+            for b in encode_locations(args.input, args.fasta_input, locations[start:start + step], opt, threads=procs, device="gpu",
+                                      inflate_device=args.inflate_device, compress_device="gpu", pending=len(writer.pending)):
+                writer.append_records(b.head)
+                if b.chunks is not None:
+                    writer.write_chunks(b.chunks)
+                    for k in stages:
+                        stages[k] += b.stats[k]
+                writer.append_records(b.tail)
+                total_errors += b.errors
+                written += b.records
+            start += step
+            print("Total errors %d through %d steps (%d records, %.1f s)" % (total_errors, min(start, n_loc), written, time.time() - t0), flush=True)
+    stages.update(chunk_write_ms=round(writer.write_s * 1e3, 3), chunks_from_device=writer.direct_chunks, chunks_from_host=writer.host_chunks,
+                  chunks_unfiltered=writer.stored_chunks, records=written)
+    print("compress-device gpu stages: %s" % json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in stages.items()}))
+    print("Parsing errors in %d / %d locations -- saved to: %s" % (total_errors, n_loc, args.output))
+    return 0
 
 
 def main(argv=None):
@@ -64,9 +101,16 @@ def main(argv=None):
     ap.add_argument("--inflate-device", type=str, default=None, choices=["gpu"],
                     help="gpu: with --pileup-device gpu, the GPU encoder inflates the BAM's BGZF blocks and frames its records on the "
                          "device as well (needs the .bai); the file is the same bytes")
+    ap.add_argument("--compress-device", type=str, default=None, choices=["gpu"],
+                    help="gpu: with --pileup-device gpu, the records are packed and compressed into the file's chunks on the device "
+                         "and written past the HDF5 filter; the same records in a file any HDF5 reader inflates (other bytes: "
+                         "another encoder)")
     args = ap.parse_args(argv)
     if args.inflate_device and args.pileup_device != "gpu":
         raise SystemExit("--inflate-device gpu is an option of the GPU pileup encoder: give --pileup-device gpu as well")
+    if args.compress_device and args.pileup_device != "gpu":
+        raise SystemExit("--compress-device gpu compresses the GPU pileup encoder's planes where they lie, in device memory: "
+                         "give --pileup-device gpu as well")
     for flag, why in (("locations", "numpy location tables"), ("restrict_locations", "location restriction files"),
                       ("non_restrict_match_random", "location restriction files")):
         if getattr(args, flag):
@@ -108,6 +152,8 @@ def main(argv=None):
         pool = mp.get_context("spawn").Pool(procs)
     total_errors, written, created = 0, 0, append
     t0 = time.time()
+    if args.compress_device == "gpu":
+        return _convert_compressed(args, locations, opt, start, step, procs, append)
     try:
         while start < n_loc or not created:
             chunk = locations[start:start + step]

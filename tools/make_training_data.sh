@@ -6,10 +6,13 @@
 # GT, isec/0001.vcf as --fp_vcf with label 2).  A multi-allelic truth record (1/2) pairs only with a candidate of the same
 # ALT set, so its split candidates are labelled false positives; split such truth records beforehand if that is not wanted.
 # Stages whose output already exists in OUTDIR are skipped.
+# -c: the converter builds the pileups on the GPU and packs and compresses train.hdf's chunks there (--pileup-device gpu
+# --compress-device gpu): the same records.
 set -e
-usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES]"; exit 1; }
+usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c]"; exit 1; }
 PROCS=16
-while getopts "i:r:t:o:b:p:h" opt; do
+COMPRESS=""
+while getopts "i:r:t:o:b:p:ch" opt; do
   case $opt in
     i) BAM=$OPTARG ;;
     r) REFERENCE=$OPTARG ;;
@@ -17,6 +20,7 @@ while getopts "i:r:t:o:b:p:h" opt; do
     o) OUTDIR=$OPTARG ;;
     b) BED=$OPTARG ;;       # candidate generation only
     p) PROCS=$OPTARG ;;
+    c) COMPRESS=gpu ;;
     *) usage ;;
   esac
 done
@@ -38,6 +42,7 @@ if [ ! -f "$OUTDIR/train.hdf" ]; then
   python "$SCRIPTDIR/tools/convert_bam_single_reads.py" --input "$BAM" --tp_vcf "$OUTDIR/isec/0003.vcf" \
       --tp_full_vcf "$OUTDIR/isec/0002.vcf" --fp_vcf "$OUTDIR/isec/0001.vcf" --fasta-input "$REFERENCE" \
       --output "$OUTDIR/train.hdf" --max-reads 200 --num-processes "$PROCS" --locations-process-step 100000 \
-      --max-insert-length 10 --max-insert-length-variant 50 --save-q-scores --save-strand > "$OUTDIR/training_data.log" 2>&1
+      --max-insert-length 10 --max-insert-length-variant 50 --save-q-scores --save-strand \
+      ${COMPRESS:+--pileup-device gpu --compress-device "$COMPRESS"} > "$OUTDIR/training_data.log" 2>&1
 fi
 echo "Training data in $OUTDIR/train.hdf"
