@@ -14,6 +14,8 @@
 #include <string>
 #include <vector>
 
+#include "bam_frame.h"
+
 namespace bamn {
 
 // ---- BGZF -------------------------------------------------------------------------------------------------------------------------
@@ -90,7 +92,7 @@ struct Bgzf {
     }
 };
 
-// ---- BAM header and record framing ------------------------------------------------------------------------------------------
+// ---- BAM header and record chain (a record itself is framed by bam_frame.h) -------------------------------------------------------
 struct BamFile {
     Bgzf r;
     std::vector<std::string> refs;
@@ -128,77 +130,12 @@ struct BamFile {
         int32_t size = 0;
         const size_t g = r.read(&size, 4);
         if (g < 4) { if (!r.err.empty()) err = r.err; return r.err.empty() ? 0 : -1; }
-        if (size < 32 || size > (1 << 28)) { err = "corrupt BAM record (block_size)"; return -1; }
+        if (size < 32 || size > (1 << 28)) { err = frame::why_text(frame::W_BLOCK_SIZE); return -1; }
         b.resize((size_t)size);
-        if (r.read(b.data(), b.size()) != b.size()) { err = r.err.empty() ? "truncated BAM record" : r.err; return -1; }
+        if (r.read(b.data(), b.size()) != b.size()) { err = r.err.empty() ? frame::why_text(frame::W_TRUNCATED) : r.err; return -1; }
         return 1;
     }
 };
-
-// The fixed fields of one record and the offsets of its variable parts, every one checked to lie inside the record's
-// ``size`` bytes (the aux area is walked tag by tag).  md_off / md_len locate the MD:Z value (without its NUL), -1 if absent.
-struct RecordFrame {
-    int32_t tid, pos, l_seq;
-    uint16_t n_cig, flag;
-    uint8_t l_name;
-    uint32_t cigar_off, seq_off, qual_off, aux_off;
-    int32_t md_off, md_len;
-};
-
-inline int aux_value_size(uint8_t type) {
-    switch (type) {
-        case 'A': case 'c': case 'C': return 1;
-        case 's': case 'S': return 2;
-        case 'i': case 'I': case 'f': return 4;
-        default: return -1;
-    }
-}
-
-// nullptr when the record is well framed, else what is wrong with it
-inline const char* frame_record(const uint8_t* b, size_t size, RecordFrame& fr) {
-    if (size < 32) return "corrupt BAM record (block_size)";
-    memcpy(&fr.tid, b, 4); memcpy(&fr.pos, b + 4, 4);
-    fr.l_name = b[8];
-    memcpy(&fr.n_cig, b + 12, 2); memcpy(&fr.flag, b + 14, 2); memcpy(&fr.l_seq, b + 16, 4);
-    if (fr.l_name < 1) return "corrupt BAM record (l_read_name)";
-    if (fr.l_seq < 0) return "corrupt BAM record (l_seq)";
-    const uint64_t cig = 32 + (uint64_t)fr.l_name;
-    if (cig > size) return "corrupt BAM record (l_read_name exceeds the record)";
-    const uint64_t seq = cig + 4 * (uint64_t)fr.n_cig;
-    if (seq > size) return "corrupt BAM record (n_cigar_op exceeds the record)";
-    const uint64_t qual = seq + ((uint64_t)fr.l_seq + 1) / 2;
-    const uint64_t aux = qual + (uint64_t)fr.l_seq;
-    if (aux > size) return "corrupt BAM record (l_seq exceeds the record)";
-    fr.cigar_off = (uint32_t)cig; fr.seq_off = (uint32_t)seq; fr.qual_off = (uint32_t)qual; fr.aux_off = (uint32_t)aux;
-    fr.md_off = -1; fr.md_len = -1;
-    size_t o = (size_t)aux;
-    while (o < size) {
-        if (o + 3 > size) return "corrupt BAM record (aux tag runs past the record)";
-        const bool md = b[o] == 'M' && b[o + 1] == 'D';
-        const uint8_t t = b[o + 2];
-        o += 3;
-        if (t == 'Z' || t == 'H') {
-            const uint8_t* z = (const uint8_t*)memchr(b + o, 0, size - o);
-            if (!z) return "corrupt BAM record (aux string without its NUL)";
-            if (md && t == 'Z' && fr.md_off < 0) { fr.md_off = (int32_t)o; fr.md_len = (int32_t)(z - (b + o)); }
-            o = (size_t)(z - b) + 1;
-        } else if (t == 'B') {
-            if (o + 5 > size) return "corrupt BAM record (aux array runs past the record)";
-            const int es = aux_value_size(b[o]);
-            uint32_t n;
-            memcpy(&n, b + o + 1, 4);
-            if (es < 0) return "corrupt BAM record (aux array element type)";
-            if ((uint64_t)n * (uint64_t)es > size - (o + 5)) return "corrupt BAM record (aux array runs past the record)";
-            o += 5 + (size_t)n * (size_t)es;
-        } else {
-            const int vs = aux_value_size(t);
-            if (vs < 0) return "corrupt BAM record (aux value type)";
-            if (o + (size_t)vs > size) return "corrupt BAM record (aux value runs past the record)";
-            o += (size_t)vs;
-        }
-    }
-    return nullptr;
-}
 
 // ---- BAI: the linear index, and the chunks of every bin ------------------------------------------------------------------------
 struct Bai {

@@ -3,24 +3,18 @@
 // kernels as cand::ReadMeta without leaving the device.
 #pragma once
 
+#include "bam_frame.h"
 #include "bgzf_inflate.h"
 #include "bgzf_plan.h"
 #include "cand_device.h"
 
 namespace bz {
 
-// why a record was refused (the texts of bamn::frame_record and BamFile::next_block, same order as reason_text())
-enum Reason : uint32_t {
-    R_NONE = 0, R_BLOCK_SIZE, R_TRUNCATED, R_OVER_STOP, R_L_NAME, R_L_SEQ, R_NAME_EXCEEDS, R_CIGAR_EXCEEDS, R_SEQ_EXCEEDS,
-    R_AUX_TAG, R_AUX_NUL, R_AUX_ARRAY, R_AUX_ARRAY_TYPE, R_AUX_TYPE, R_AUX_VALUE, R_COUNT
-};
-const char* reason_text(uint32_t r);
-
 struct SubRange {
     int32_t tid, start, end;
 };
 
-constexpr uint64_t NO_ERROR = ~0ull;   // else (offset of the record's block_size field) << 8 | Reason, the lowest offset wins
+constexpr uint64_t NO_ERROR = ~0ull;   // else (offset of the record's block_size field) << 8 | bamn::frame::Why, the lowest offset wins
 
 // inflates n blocks of comp (device) into out (device); status[i] per block.  Blocks whose desc.status is set are skipped.
 hipError_t launch_inflate(const uint8_t* comp, const BlockDesc* tab, int64_t n, uint8_t* out, int32_t* status, hipStream_t stream);
@@ -28,7 +22,7 @@ hipError_t launch_inflate(const uint8_t* comp, const BlockDesc* tab, int64_t n, 
 struct Framer;   // device buffers of the walk / frame / emit passes, grown on demand
 Framer* framer_create();
 void framer_destroy(Framer* f);
-constexpr uint64_t NO_RECORD = ~0ull;   // a record slot the walk left empty
+using bamn::frame::NO_RECORD;           // a record slot the walk left empty
 // Walks segs (bgzf_plan.h) over infl[0, infl_bytes): *rec_off (device, owned by the framer, n_slots entries) holds the offset of
 // every record's block_size field, NO_RECORD in the slots left over; *n_records = records walked; *err = NO_ERROR or the first
 // refused record.  0 or -2 with msg.  The first pass of frame_records(), and of the pileup encoder's framing.

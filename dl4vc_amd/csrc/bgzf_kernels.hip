@@ -9,15 +9,17 @@
 // its status.
 //
 // bam_walk_kernel / bam_frame_kernel / bam_emit_kernel: record starts are found by following block_size from known record
-// boundaries (one thread per segment), each record is framed with the checks of bamn::frame_record (one thread per slot), and
+// boundaries (one thread per segment), each record is framed by the frame core of bam_frame.h (one thread per slot), and
 // listed once per subregion it overlaps, at the place an exclusive scan of the per-record counts gives it.
 #include "bgzf_device.h"
+#include "device_buffer.h"
 
 #include <rocprim/device/device_scan.hpp>
 
 namespace bz {
 namespace {
 
+namespace F = bamn::frame;
 constexpr int WAVE = 64;
 
 // The wave's writes into the LDS window.  All 64 lanes call each method with the same arguments (the decode is uniform).  A match
@@ -104,10 +106,6 @@ __global__ __launch_bounds__(WAVE) void bgzf_inflate_kernel(const uint8_t* __res
     if (done + lane < d.isize) g[done + lane] = w[done + lane];
 }
 
-__device__ inline uint32_t ld16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ inline uint32_t ld32(const uint8_t* p) {
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
 __device__ inline void report(unsigned long long* err, uint64_t off, uint32_t reason) {
     atomicMin(err, (unsigned long long)((off << 8) | reason));
 }
@@ -119,16 +117,13 @@ __global__ void bam_walk_kernel(const uint8_t* __restrict__ infl, uint64_t total
     const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_segs) return;
     const Segment sg = segs[s];
-    if (sg.start > sg.stop || sg.stop > total) { report(err, sg.start, R_OVER_STOP); return; }
+    if (sg.start > sg.stop || sg.stop > total) { report(err, sg.start, F::W_OVER_STOP); return; }
     const uint64_t cap = (sg.stop - sg.start) / 36 + 1;
     uint64_t at = sg.start, k = 0;
     while (at < sg.stop) {                                  // (each turn advances at by at least 36)
-        if (sg.stop - at < 4) { report(err, at, R_OVER_STOP); return; }
-        const uint32_t size = ld32(infl + at);
-        if (size < 32 || size > (1u << 28)) { report(err, at, R_BLOCK_SIZE); return; }
-        if ((uint64_t)size + 4 > total - at) { report(err, at, R_TRUNCATED); return; }
-        if ((uint64_t)size + 4 > sg.stop - at) { report(err, at, R_OVER_STOP); return; }
-        if (k >= cap || sg.slot_base + k >= n_slots) { report(err, at, R_OVER_STOP); return; }
+        uint32_t size;
+        if (const uint32_t why = F::next_record(infl, total, sg.stop, at, size)) { report(err, at, why); return; }
+        if (k >= cap || sg.slot_base + k >= n_slots) { report(err, at, F::W_OVER_STOP); return; }
         rec_off[sg.slot_base + k] = at;
         ++k;
         at += (uint64_t)size + 4;
@@ -136,78 +131,9 @@ __global__ void bam_walk_kernel(const uint8_t* __restrict__ infl, uint64_t total
     atomicAdd(n_records, (unsigned long long)k);
 }
 
-__device__ inline int aux_value_size(uint8_t type) {
-    switch (type) {
-        case 'A': case 'c': case 'C': return 1;
-        case 's': case 'S': return 2;
-        case 'i': case 'I': case 'f': return 4;
-        default: return -1;
-    }
-}
-
-struct Framed {
-    int32_t tid, pos, md_off, md_len;
-    int64_t endpos;
-};
-
-// bamn::frame_record and cand_capi.cpp::endpos on the device; R_NONE or the reason
-__device__ uint32_t frame(const uint8_t* __restrict__ b, uint64_t size, Framed& fr) {
-    fr.tid = (int32_t)ld32(b);
-    fr.pos = (int32_t)ld32(b + 4);
-    const uint32_t l_name = b[8];
-    const uint32_t n_cig = ld16(b + 12), flag = ld16(b + 14);
-    const int32_t l_seq = (int32_t)ld32(b + 16);
-    if (l_name < 1) return R_L_NAME;
-    if (l_seq < 0) return R_L_SEQ;
-    const uint64_t cig = 32 + (uint64_t)l_name;
-    if (cig > size) return R_NAME_EXCEEDS;
-    const uint64_t seq = cig + 4 * (uint64_t)n_cig;
-    if (seq > size) return R_CIGAR_EXCEEDS;
-    const uint64_t aux = seq + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq;
-    if (aux > size) return R_SEQ_EXCEEDS;
-    fr.md_off = -1; fr.md_len = -1;
-    uint64_t o = aux;
-    while (o < size) {                                      // (each turn advances o by at least 3)
-        if (o + 3 > size) return R_AUX_TAG;
-        const bool md = b[o] == 'M' && b[o + 1] == 'D';
-        const uint8_t t = b[o + 2];
-        o += 3;
-        if (t == 'Z' || t == 'H') {
-            uint64_t z = o;
-            while (z < size && b[z] != 0) ++z;
-            if (z >= size) return R_AUX_NUL;
-            if (md && t == 'Z' && fr.md_off < 0) { fr.md_off = (int32_t)o; fr.md_len = (int32_t)(z - o); }
-            o = z + 1;
-        } else if (t == 'B') {
-            if (o + 5 > size) return R_AUX_ARRAY;
-            const int es = aux_value_size(b[o]);
-            const uint32_t n = ld32(b + o + 1);
-            if (es < 0) return R_AUX_ARRAY_TYPE;
-            if ((uint64_t)n * (uint64_t)es > size - (o + 5)) return R_AUX_ARRAY;
-            o += 5 + (uint64_t)n * (uint64_t)es;
-        } else {
-            const int vs = aux_value_size(t);
-            if (vs < 0) return R_AUX_TYPE;
-            if (o + (uint64_t)vs > size) return R_AUX_VALUE;
-            o += (uint64_t)vs;
-        }
-    }
-    if (flag & 0x4) {
-        fr.endpos = (int64_t)fr.pos + 1;
-    } else {
-        int64_t rlen = 0;
-        for (uint32_t i = 0; i < n_cig; ++i) {
-            const uint32_t v = ld32(b + cig + 4 * i);
-            const int op = v & 0xf;
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += v >> 4;
-        }
-        fr.endpos = (int64_t)fr.pos + (rlen > 0 ? rlen : 1);
-    }
-    return R_NONE;
-}
-
-__device__ inline bool belongs(const Framed& fr, const SubRange& s) {
-    return fr.tid == s.tid && fr.pos < s.end && fr.endpos > (int64_t)s.start;
+// the record's overlap with a subregion (htslib's rule); fr holds the CIGAR sums
+__device__ inline bool belongs(const F::Framed& fr, const SubRange& s) {
+    return fr.tid == s.tid && fr.pos < s.end && F::endpos(fr) > (int64_t)s.start;
 }
 
 // One thread per slot: frames the record there (if any) and counts the subregions it belongs to.
@@ -219,12 +145,14 @@ __global__ void bam_frame_kernel(const uint8_t* __restrict__ infl, const uint64_
     uint32_t c = 0;
     const uint64_t at = rec_off[i];
     if (at != NO_RECORD) {
-        const uint32_t size = ld32(infl + at);              // (checked by the walk: 32 <= size, at + 4 + size <= total)
-        Framed fr;
-        const uint32_t why = frame(infl + at + 4, size, fr);
-        if (why != R_NONE) {
+        const uint32_t size = F::ld32(infl + at);           // (checked by the walk: 32 <= size, at + 4 + size <= total)
+        const uint8_t* b = infl + at + 4;
+        F::Framed fr;
+        const uint32_t why = F::frame_record(b, size, fr);
+        if (why != F::W_NONE) {
             report(err, at, why);
         } else {
+            F::cigar_sums(b, fr);
             for (uint32_t s = 0; s < n_subs; ++s) c += belongs(fr, subs[s]) ? 1u : 0u;
             md_off[i] = fr.md_off;
             md_len[i] = fr.md_len;
@@ -242,19 +170,10 @@ __global__ void bam_emit_kernel(const uint8_t* __restrict__ infl, const uint64_t
     if (i >= n_slots || count[i] == 0) return;
     const uint64_t at = rec_off[i];
     const uint8_t* b = infl + at + 4;
-    const uint32_t size = ld32(infl + at);
-    Framed fr;
-    fr.tid = (int32_t)ld32(b);
-    fr.pos = (int32_t)ld32(b + 4);
-    const uint32_t l_name = b[8], n_cig = ld16(b + 12), flag = ld16(b + 14);
-    int64_t rlen = 0;
-    if (!(flag & 0x4))
-        for (uint32_t k = 0; k < n_cig; ++k) {
-            const uint32_t v = ld32(b + 32 + l_name + 4 * k);
-            const int op = v & 0xf;
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += v >> 4;
-        }
-    fr.endpos = (int64_t)fr.pos + (rlen > 0 ? rlen : 1);
+    const uint32_t size = F::ld32(infl + at);
+    F::Framed fr;
+    (void)F::frame_record(b, size, fr, false);              // (framed cleanly by bam_frame_kernel)
+    F::cigar_sums(b, fr);
     cand::ReadMeta m;
     m.off = at + 4;
     m.len = size;
@@ -269,44 +188,7 @@ __global__ void bam_emit_kernel(const uint8_t* __restrict__ infl, const uint64_t
         }
 }
 
-struct DBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    template <class T> T* as() const { return (T*)p; }
-    ~DBuf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
-
-const char* reason_text(uint32_t r) {
-    static const char* const TEXT[R_COUNT] = {
-        "no error",
-        "corrupt BAM record (block_size)",
-        "truncated BAM record",
-        "corrupt BAM record (block_size runs past the next indexed record)",
-        "corrupt BAM record (l_read_name)",
-        "corrupt BAM record (l_seq)",
-        "corrupt BAM record (l_read_name exceeds the record)",
-        "corrupt BAM record (n_cigar_op exceeds the record)",
-        "corrupt BAM record (l_seq exceeds the record)",
-        "corrupt BAM record (aux tag runs past the record)",
-        "corrupt BAM record (aux string without its NUL)",
-        "corrupt BAM record (aux array runs past the record)",
-        "corrupt BAM record (aux array element type)",
-        "corrupt BAM record (aux value type)",
-        "corrupt BAM record (aux value runs past the record)",
-    };
-    return r < R_COUNT ? TEXT[r] : "corrupt BAM record";
-}
 
 hipError_t launch_inflate(const uint8_t* comp, const BlockDesc* tab, int64_t n, uint8_t* out, int32_t* status, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
@@ -315,37 +197,31 @@ hipError_t launch_inflate(const uint8_t* comp, const BlockDesc* tab, int64_t n, 
 }
 
 struct Framer {
-    DBuf segs, subs, rec_off, count, first, md_off, md_len, meta, scalars, temp;
+    dev::Buffer segs, subs, rec_off, count, first, md_off, md_len, meta, scalars, temp;
 };
 
 Framer* framer_create() { return new Framer(); }
 void framer_destroy(Framer* f) { delete f; }
-
-#define BZ_CHECK(x)                                                        \
-    do {                                                                   \
-        const hipError_t e_ = (x);                                         \
-        if (e_ != hipSuccess) { *msg = hipGetErrorString(e_); return -2; } \
-    } while (0)
 
 int walk_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Segment* segs, uint64_t n_segs, uint64_t n_slots,
                  hipStream_t stream, const uint64_t** rec_off, uint64_t* n_records, uint64_t* err, const char** msg) {
     *rec_off = nullptr; *n_records = 0; *err = NO_ERROR;
     if (n_segs == 0 || n_slots == 0) return 0;
     if (n_slots >= (1ull << 31)) { *msg = "too many record slots in one batch"; return -2; }
-    BZ_CHECK(f->segs.ensure(n_segs * sizeof(Segment)));
-    BZ_CHECK(f->rec_off.ensure(n_slots * 8));
-    BZ_CHECK(f->scalars.ensure(2 * 8));
+    HIP_CHECK_MSG(f->segs.ensure(n_segs * sizeof(Segment)));
+    HIP_CHECK_MSG(f->rec_off.ensure(n_slots * 8));
+    HIP_CHECK_MSG(f->scalars.ensure(2 * 8));
     unsigned long long* sc = f->scalars.as<unsigned long long>();   // [0] records walked, [1] first refused record
-    BZ_CHECK(hipMemcpyAsync(f->segs.p, segs, n_segs * sizeof(Segment), hipMemcpyHostToDevice, stream));
-    BZ_CHECK(hipMemsetAsync(f->rec_off.p, 0xff, n_slots * 8, stream));
-    BZ_CHECK(hipMemsetAsync(sc, 0, 8, stream));
-    BZ_CHECK(hipMemsetAsync(sc + 1, 0xff, 8, stream));
+    HIP_CHECK_MSG(hipMemcpyAsync(f->segs.p, segs, n_segs * sizeof(Segment), hipMemcpyHostToDevice, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(f->rec_off.p, 0xff, n_slots * 8, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(sc, 0, 8, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(sc + 1, 0xff, 8, stream));
     hipLaunchKernelGGL(bam_walk_kernel, dim3((unsigned)((n_segs + 63) / 64)), dim3(64), 0, stream, infl, infl_bytes,
                        f->segs.as<const Segment>(), n_segs, n_slots, f->rec_off.as<uint64_t>(), sc, sc + 1);
-    BZ_CHECK(hipGetLastError());
+    HIP_CHECK_MSG(hipGetLastError());
     unsigned long long h[2];
-    BZ_CHECK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, stream));
-    BZ_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK_MSG(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK_MSG(hipStreamSynchronize(stream));
     *n_records = h[0];
     *err = h[1];                                           // (a refused walk leaves slots unset: nothing is framed from them)
     *rec_off = f->rec_off.as<const uint64_t>();
@@ -361,38 +237,38 @@ int frame_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Seg
     const uint64_t* walked = nullptr;
     if (const int rc = walk_records(f, infl, infl_bytes, segs, n_segs, n_slots, stream, &walked, n_records, err, msg)) return rc;
     if (*err != NO_ERROR) return 0;
-    BZ_CHECK(f->subs.ensure((n_subs + 1) * sizeof(SubRange)));
-    BZ_CHECK(f->count.ensure((n_slots + 1) * 4));
-    BZ_CHECK(f->first.ensure((n_slots + 1) * 4));
-    BZ_CHECK(f->md_off.ensure(n_slots * 4));
-    BZ_CHECK(f->md_len.ensure(n_slots * 4));
+    HIP_CHECK_MSG(f->subs.ensure((n_subs + 1) * sizeof(SubRange)));
+    HIP_CHECK_MSG(f->count.ensure((n_slots + 1) * 4));
+    HIP_CHECK_MSG(f->first.ensure((n_slots + 1) * 4));
+    HIP_CHECK_MSG(f->md_off.ensure(n_slots * 4));
+    HIP_CHECK_MSG(f->md_len.ensure(n_slots * 4));
     unsigned long long* sc = f->scalars.as<unsigned long long>();
     unsigned long long h[2];
-    BZ_CHECK(hipMemcpyAsync(f->subs.p, subs, n_subs * sizeof(SubRange), hipMemcpyHostToDevice, stream));
+    HIP_CHECK_MSG(hipMemcpyAsync(f->subs.p, subs, n_subs * sizeof(SubRange), hipMemcpyHostToDevice, stream));
     const unsigned grid = (unsigned)((n_slots + TB - 1) / TB);
     hipLaunchKernelGGL(bam_frame_kernel, dim3(grid), dim3(TB), 0, stream, infl, f->rec_off.as<const uint64_t>(), n_slots,
                        f->subs.as<const SubRange>(), n_subs, f->count.as<uint32_t>(), f->md_off.as<int32_t>(), f->md_len.as<int32_t>(),
                        sc + 1);
-    BZ_CHECK(hipGetLastError());
-    BZ_CHECK(hipMemsetAsync(f->count.as<uint32_t>() + n_slots, 0, 4, stream));
+    HIP_CHECK_MSG(hipGetLastError());
+    HIP_CHECK_MSG(hipMemsetAsync(f->count.as<uint32_t>() + n_slots, 0, 4, stream));
     size_t tb = 0;
-    BZ_CHECK(rocprim::exclusive_scan(nullptr, tb, f->count.as<uint32_t>(), f->first.as<uint32_t>(), 0u, (size_t)n_slots + 1,
-                                     rocprim::plus<uint32_t>(), stream));
-    BZ_CHECK(f->temp.ensure(tb));
+    HIP_CHECK_MSG(rocprim::exclusive_scan(nullptr, tb, f->count.as<uint32_t>(), f->first.as<uint32_t>(), 0u, (size_t)n_slots + 1,
+                                          rocprim::plus<uint32_t>(), stream));
+    HIP_CHECK_MSG(f->temp.ensure(tb));
     tb = f->temp.cap;
-    BZ_CHECK(rocprim::exclusive_scan(f->temp.p, tb, f->count.as<uint32_t>(), f->first.as<uint32_t>(), 0u, (size_t)n_slots + 1,
-                                     rocprim::plus<uint32_t>(), stream));
+    HIP_CHECK_MSG(rocprim::exclusive_scan(f->temp.p, tb, f->count.as<uint32_t>(), f->first.as<uint32_t>(), 0u, (size_t)n_slots + 1,
+                                          rocprim::plus<uint32_t>(), stream));
     uint32_t total = 0;
-    BZ_CHECK(hipMemcpyAsync(&total, f->first.as<uint32_t>() + n_slots, 4, hipMemcpyDeviceToHost, stream));
-    BZ_CHECK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, stream));
-    BZ_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK_MSG(hipMemcpyAsync(&total, f->first.as<uint32_t>() + n_slots, 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK_MSG(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK_MSG(hipStreamSynchronize(stream));
     if (h[1] != NO_ERROR) { *err = h[1]; return 0; }
-    BZ_CHECK(f->meta.ensure(((size_t)total + 1) * sizeof(cand::ReadMeta)));
+    HIP_CHECK_MSG(f->meta.ensure(((size_t)total + 1) * sizeof(cand::ReadMeta)));
     if (total) {
         hipLaunchKernelGGL(bam_emit_kernel, dim3(grid), dim3(TB), 0, stream, infl, f->rec_off.as<const uint64_t>(), n_slots,
                            f->subs.as<const SubRange>(), n_subs, f->count.as<const uint32_t>(), f->first.as<const uint32_t>(),
                            f->md_off.as<const int32_t>(), f->md_len.as<const int32_t>(), f->meta.as<cand::ReadMeta>());
-        BZ_CHECK(hipGetLastError());
+        HIP_CHECK_MSG(hipGetLastError());
     }
     *meta = f->meta.as<const cand::ReadMeta>();
     *n_reads = total;

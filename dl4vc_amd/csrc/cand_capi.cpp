@@ -1,6 +1,6 @@
 // Host side of libdl4vc_cand.so (C ABI: include/dl4vc_candgen.h).  Worker threads, each with its own BAM handle, fetch the
 // records of a batch of subregions (BAI linear index, htslib's overlap rule: pos < end and bam_endpos > start, no flag
-// filter), frame and validate every record (bam_native.h::frame_record) and gather them into one pinned buffer; the device
+// filter), frame and validate every record (the frame core of bam_frame.h) and gather them into one pinned buffer; the device
 // does the rest (cand_kernels.hip).  A read overlapping two subregions is listed once for each, as the reference's per
 // subregion fetch counts it.  Every extern "C" body catches what it throws: a corrupt file is an error code, never an abort.
 //
@@ -8,6 +8,7 @@
 // reads their BGZF blocks as they are into pinned memory, and the device inflates them, walks the record chain, frames the
 // records and lists them per subregion (bgzf_kernels.hip); the same count / emit / filter kernels follow.
 #include "../../include/dl4vc_candgen.h"
+#include "bam_frame.h"
 #include "bam_native.h"
 #include "bgzf_device.h"
 #include "cand_device.h"
@@ -42,19 +43,6 @@ int fail(int code, const char* fmt, ...) {
 const char BASES[] = "=ACMGRSVTWYHKDBN";
 constexpr int64_t BATCH_BASES = 4000000;     // subregion length gathered per device batch
 constexpr uint32_t MAX_BATCH_SUBS = 1u << 20;
-
-// htslib's bam_endpos: an unmapped read, or one without reference-consuming operations, covers one position
-int64_t endpos(const uint8_t* b, const bamn::RecordFrame& fr) {
-    if (fr.flag & 0x4) return (int64_t)fr.pos + 1;
-    int64_t rlen = 0;
-    for (int i = 0; i < fr.n_cig; ++i) {
-        uint32_t v;
-        memcpy(&v, b + fr.cigar_off + 4 * i, 4);
-        const int op = v & 0xf;
-        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += v >> 4;
-    }
-    return (int64_t)fr.pos + (rlen > 0 ? rlen : 1);
-}
 
 struct Gathered {
     std::vector<uint8_t> bytes;
@@ -98,6 +86,7 @@ namespace {
 
 // the records of subregion s (one BAM handle per worker)
 bool fetch_sub(cg_handle* h, bamn::BamFile& bam, std::vector<uint8_t>& blk, const cg_region& rg, uint32_t s, Gathered& g) {
+    namespace F = bamn::frame;
     int64_t at = bam.first_record;
     if (h->have_bai) {
         const uint64_t off = h->bai.linear_offset(rg.tid, rg.start);
@@ -110,15 +99,18 @@ bool fetch_sub(cg_handle* h, bamn::BamFile& bam, std::vector<uint8_t>& blk, cons
         const int got = bam.next_block(blk);
         if (got == 0) return true;
         if (got < 0) { g.err = bam.err + " (record at virtual offset " + std::to_string(voff) + ")"; return false; }
-        bamn::RecordFrame fr;
-        const char* why = bamn::frame_record(blk.data(), blk.size(), fr);
-        if (why) { g.err = std::string(why) + " (record at virtual offset " + std::to_string(voff) + ")"; return false; }
+        F::Framed fr;
+        if (const uint32_t why = F::frame_record(blk.data(), blk.size(), fr)) {
+            g.err = std::string(F::why_text(why)) + " (record at virtual offset " + std::to_string(voff) + ")";
+            return false;
+        }
         if (fr.tid != rg.tid) {
             if (fr.tid < 0 || fr.tid > rg.tid) return true;
             continue;
         }
         if (fr.pos >= rg.end) return true;
-        if (endpos(blk.data(), fr) <= rg.start) continue;
+        F::cigar_sums(blk.data(), fr);
+        if (F::endpos(fr) <= rg.start) continue;
         cand::ReadMeta m;
         m.off = g.bytes.size();
         m.len = (uint32_t)blk.size();
@@ -347,9 +339,8 @@ int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t
     if (bz::frame_records(h->framer, (const uint8_t*)h->d_infl, infl_bytes, segs.data(), segs.size(), n_slots, sr.data(), n_subs, h->stream,
                           &meta_dev, &n_reads, &n_records, &err, &msg))
         return fail(-2, "device framing: %s", msg);
-    if (err != bz::NO_ERROR) {
-        return fail(-3, "%s (record at virtual offset %lld)", bz::reason_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
-    }
+    if (err != bz::NO_ERROR)
+        return fail(-3, "%s (record at virtual offset %lld)", bamn::frame::why_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
     CG_TRY(hipEventRecord(h->ev[3], h->stream));
     CG_TRY(hipStreamSynchronize(h->stream));
     float ms = 0.f;

@@ -16,7 +16,9 @@
 //   * an allele whose REF or ALT is longer than max_len is dropped; only alleles at start <= pos <= end count.
 // A read whose MD does not agree with its CIGAR (runs past it, ends short, a '^' run of the wrong length, a letter outside the
 // BAM alphabet) is marked malformed and gives no alleles.  Every byte read is bounded by the read's framed length.
+#include "bam_frame.h"
 #include "cand_device.h"
+#include "device_buffer.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_run_length_encode.hpp>
@@ -27,10 +29,8 @@
 namespace cand {
 namespace {
 
-__device__ inline uint32_t ld16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ inline uint32_t ld32(const uint8_t* p) {
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
+using bamn::frame::ld16;
+using bamn::frame::ld32;
 
 // an MD letter as a BAM nibble code ("=ACMGRSVTWYHKDBN"), -1 outside the alphabet (lower case included)
 __device__ inline int letter_code(uint8_t c) {
@@ -374,24 +374,8 @@ struct IndelDecomposer {
 
 }  // namespace
 
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    template <class T> T* as() const { return (T*)p; }
-    ~Buf() { if (p) (void)hipFree(p); }
-};
-
 struct Workspace {
-    Buf recs, meta, subs, cov, depth, n_snp, n_indel, snp_off, indel_off, status, snp_keys, snp_sorted, indel_keys, indel_sorted,
+    dev::Buffer recs, meta, subs, cov, depth, n_snp, n_indel, snp_off, indel_off, status, snp_keys, snp_sorted, indel_keys, indel_sorted,
         snp_unique, snp_counts, indel_unique, indel_counts, scalars, cands, temp;
     std::vector<uint8_t> h_status;
     std::vector<DevCand> h_cands;
@@ -412,22 +396,16 @@ void workspace_destroy(Workspace* ws) {
     delete ws;
 }
 
-#define CG_CHECK(x)                                                        \
-    do {                                                                   \
-        const hipError_t e_ = (x);                                         \
-        if (e_ != hipSuccess) { *msg = hipGetErrorString(e_); return -2; } \
-    } while (0)
-
 int upload(Workspace* ws, const uint8_t* recs, uint64_t rec_bytes, const ReadMeta* meta, uint64_t n_reads, const SubDesc* subs,
            uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg) {
-    CG_CHECK(ws->recs.ensure(rec_bytes + 1));
-    CG_CHECK(ws->meta.ensure((n_reads + 1) * sizeof(ReadMeta)));
-    CG_CHECK(ws->subs.ensure((n_subs + 1) * sizeof(SubDesc)));
-    CG_CHECK(ws->cov.ensure((size_t)(cov_len + 1) * sizeof(int)));
-    if (rec_bytes) CG_CHECK(hipMemcpyAsync(ws->recs.p, recs, rec_bytes, hipMemcpyHostToDevice, stream));
-    if (n_reads) CG_CHECK(hipMemcpyAsync(ws->meta.p, meta, n_reads * sizeof(ReadMeta), hipMemcpyHostToDevice, stream));
-    CG_CHECK(hipMemcpyAsync(ws->subs.p, subs, n_subs * sizeof(SubDesc), hipMemcpyHostToDevice, stream));
-    CG_CHECK(hipMemsetAsync(ws->cov.p, 0, (size_t)cov_len * sizeof(int), stream));
+    HIP_CHECK_MSG(ws->recs.ensure(rec_bytes + 1));
+    HIP_CHECK_MSG(ws->meta.ensure((n_reads + 1) * sizeof(ReadMeta)));
+    HIP_CHECK_MSG(ws->subs.ensure((n_subs + 1) * sizeof(SubDesc)));
+    HIP_CHECK_MSG(ws->cov.ensure((size_t)(cov_len + 1) * sizeof(int)));
+    if (rec_bytes) HIP_CHECK_MSG(hipMemcpyAsync(ws->recs.p, recs, rec_bytes, hipMemcpyHostToDevice, stream));
+    if (n_reads) HIP_CHECK_MSG(hipMemcpyAsync(ws->meta.p, meta, n_reads * sizeof(ReadMeta), hipMemcpyHostToDevice, stream));
+    HIP_CHECK_MSG(hipMemcpyAsync(ws->subs.p, subs, n_subs * sizeof(SubDesc), hipMemcpyHostToDevice, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(ws->cov.p, 0, (size_t)cov_len * sizeof(int), stream));
     ws->recs_p = ws->recs.as<const uint8_t>();
     ws->meta_p = ws->meta.as<const ReadMeta>();
     return 0;
@@ -435,10 +413,10 @@ int upload(Workspace* ws, const uint8_t* recs, uint64_t rec_bytes, const ReadMet
 
 int upload_device(Workspace* ws, const uint8_t* recs_dev, const ReadMeta* meta_dev, const SubDesc* subs, uint32_t n_subs,
                   int64_t cov_len, hipStream_t stream, const char** msg) {
-    CG_CHECK(ws->subs.ensure((n_subs + 1) * sizeof(SubDesc)));
-    CG_CHECK(ws->cov.ensure((size_t)(cov_len + 1) * sizeof(int)));
-    CG_CHECK(hipMemcpyAsync(ws->subs.p, subs, n_subs * sizeof(SubDesc), hipMemcpyHostToDevice, stream));
-    CG_CHECK(hipMemsetAsync(ws->cov.p, 0, (size_t)cov_len * sizeof(int), stream));
+    HIP_CHECK_MSG(ws->subs.ensure((n_subs + 1) * sizeof(SubDesc)));
+    HIP_CHECK_MSG(ws->cov.ensure((size_t)(cov_len + 1) * sizeof(int)));
+    HIP_CHECK_MSG(hipMemcpyAsync(ws->subs.p, subs, n_subs * sizeof(SubDesc), hipMemcpyHostToDevice, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(ws->cov.p, 0, (size_t)cov_len * sizeof(int), stream));
     ws->recs_p = recs_dev;
     ws->meta_p = meta_dev;
     return 0;
@@ -451,112 +429,112 @@ int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len,
     *n_out = 0; *n_events = 0; *n_unique = 0;
     ws->h_status.assign(n_reads, 0);
     *status = ws->h_status.data();
-    CG_CHECK(hipEventRecord(ws->ev0, stream));
+    HIP_CHECK_MSG(hipEventRecord(ws->ev0, stream));
     const uint64_t nr1 = n_reads + 1;
-    CG_CHECK(ws->n_snp.ensure(nr1 * 4));
-    CG_CHECK(ws->n_indel.ensure(nr1 * 4));
-    CG_CHECK(ws->snp_off.ensure(nr1 * 4));
-    CG_CHECK(ws->indel_off.ensure(nr1 * 4));
-    CG_CHECK(ws->status.ensure(nr1));
-    CG_CHECK(ws->depth.ensure((size_t)(cov_len + 1) * sizeof(int)));
-    CG_CHECK(ws->scalars.ensure(16 * sizeof(uint32_t)));
+    HIP_CHECK_MSG(ws->n_snp.ensure(nr1 * 4));
+    HIP_CHECK_MSG(ws->n_indel.ensure(nr1 * 4));
+    HIP_CHECK_MSG(ws->snp_off.ensure(nr1 * 4));
+    HIP_CHECK_MSG(ws->indel_off.ensure(nr1 * 4));
+    HIP_CHECK_MSG(ws->status.ensure(nr1));
+    HIP_CHECK_MSG(ws->depth.ensure((size_t)(cov_len + 1) * sizeof(int)));
+    HIP_CHECK_MSG(ws->scalars.ensure(16 * sizeof(uint32_t)));
     uint32_t* sc = ws->scalars.as<uint32_t>();     // [0] snp runs, [1] indel runs, [2] survivors
-    CG_CHECK(hipMemsetAsync(sc, 0, 16 * sizeof(uint32_t), stream));
+    HIP_CHECK_MSG(hipMemsetAsync(sc, 0, 16 * sizeof(uint32_t), stream));
     const int TB = 256;
     const unsigned grid = (unsigned)((n_reads + TB - 1) / TB);
     if (n_reads) {
         hipLaunchKernelGGL(count_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs_p, ws->meta_p,
                            n_reads, ws->subs.as<const SubDesc>(), max_len, ws->cov.as<int>(), ws->n_snp.as<uint32_t>(),
                            ws->n_indel.as<uint32_t>(), ws->status.as<uint8_t>());
-        CG_CHECK(hipGetLastError());
+        HIP_CHECK_MSG(hipGetLastError());
     }
     // per-read output offsets (exclusive scans; the element past the last read carries the total)
-    CG_CHECK(hipMemsetAsync(ws->n_snp.as<uint32_t>() + n_reads, 0, 4, stream));
-    CG_CHECK(hipMemsetAsync(ws->n_indel.as<uint32_t>() + n_reads, 0, 4, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(ws->n_snp.as<uint32_t>() + n_reads, 0, 4, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(ws->n_indel.as<uint32_t>() + n_reads, 0, 4, stream));
     size_t tb = 0, tb2 = 0;
-    CG_CHECK(rocprim::exclusive_scan(nullptr, tb, ws->n_snp.as<uint32_t>(), ws->snp_off.as<uint32_t>(), 0u, nr1,
-                                     rocprim::plus<uint32_t>(), stream));
-    CG_CHECK(rocprim::inclusive_scan(nullptr, tb2, ws->cov.as<int>(), ws->depth.as<int>(), (size_t)cov_len, rocprim::plus<int>(), stream));
+    HIP_CHECK_MSG(rocprim::exclusive_scan(nullptr, tb, ws->n_snp.as<uint32_t>(), ws->snp_off.as<uint32_t>(), 0u, nr1,
+                                          rocprim::plus<uint32_t>(), stream));
+    HIP_CHECK_MSG(rocprim::inclusive_scan(nullptr, tb2, ws->cov.as<int>(), ws->depth.as<int>(), (size_t)cov_len, rocprim::plus<int>(), stream));
     tb = std::max(tb, tb2);
-    CG_CHECK(ws->temp.ensure(tb));
+    HIP_CHECK_MSG(ws->temp.ensure(tb));
     tb = ws->temp.cap;
-    CG_CHECK(rocprim::exclusive_scan(ws->temp.p, tb, ws->n_snp.as<uint32_t>(), ws->snp_off.as<uint32_t>(), 0u, nr1,
-                                     rocprim::plus<uint32_t>(), stream));
+    HIP_CHECK_MSG(rocprim::exclusive_scan(ws->temp.p, tb, ws->n_snp.as<uint32_t>(), ws->snp_off.as<uint32_t>(), 0u, nr1,
+                                          rocprim::plus<uint32_t>(), stream));
     tb = ws->temp.cap;
-    CG_CHECK(rocprim::exclusive_scan(ws->temp.p, tb, ws->n_indel.as<uint32_t>(), ws->indel_off.as<uint32_t>(), 0u, nr1,
-                                     rocprim::plus<uint32_t>(), stream));
+    HIP_CHECK_MSG(rocprim::exclusive_scan(ws->temp.p, tb, ws->n_indel.as<uint32_t>(), ws->indel_off.as<uint32_t>(), 0u, nr1,
+                                          rocprim::plus<uint32_t>(), stream));
     tb = ws->temp.cap;
     if (cov_len > 0)
-        CG_CHECK(rocprim::inclusive_scan(ws->temp.p, tb, ws->cov.as<int>(), ws->depth.as<int>(), (size_t)cov_len, rocprim::plus<int>(), stream));
+        HIP_CHECK_MSG(rocprim::inclusive_scan(ws->temp.p, tb, ws->cov.as<int>(), ws->depth.as<int>(), (size_t)cov_len, rocprim::plus<int>(), stream));
     uint32_t tot[2];
-    CG_CHECK(hipMemcpyAsync(&tot[0], ws->snp_off.as<uint32_t>() + n_reads, 4, hipMemcpyDeviceToHost, stream));
-    CG_CHECK(hipMemcpyAsync(&tot[1], ws->indel_off.as<uint32_t>() + n_reads, 4, hipMemcpyDeviceToHost, stream));
-    CG_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK_MSG(hipMemcpyAsync(&tot[0], ws->snp_off.as<uint32_t>() + n_reads, 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK_MSG(hipMemcpyAsync(&tot[1], ws->indel_off.as<uint32_t>() + n_reads, 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK_MSG(hipStreamSynchronize(stream));
     const uint64_t ns = tot[0], ni = tot[1];
     *n_events = ns + ni;
-    CG_CHECK(ws->snp_keys.ensure((ns + 1) * 8));
-    CG_CHECK(ws->snp_sorted.ensure((ns + 1) * 8));
-    CG_CHECK(ws->snp_unique.ensure((ns + 1) * 8));
-    CG_CHECK(ws->snp_counts.ensure((ns + 1) * 4));
-    CG_CHECK(ws->indel_keys.ensure((ni + 1) * sizeof(IndelKey)));
-    CG_CHECK(ws->indel_sorted.ensure((ni + 1) * sizeof(IndelKey)));
-    CG_CHECK(ws->indel_unique.ensure((ni + 1) * sizeof(IndelKey)));
-    CG_CHECK(ws->indel_counts.ensure((ni + 1) * 4));
-    CG_CHECK(ws->cands.ensure((ns + ni + 1) * sizeof(DevCand)));
+    HIP_CHECK_MSG(ws->snp_keys.ensure((ns + 1) * 8));
+    HIP_CHECK_MSG(ws->snp_sorted.ensure((ns + 1) * 8));
+    HIP_CHECK_MSG(ws->snp_unique.ensure((ns + 1) * 8));
+    HIP_CHECK_MSG(ws->snp_counts.ensure((ns + 1) * 4));
+    HIP_CHECK_MSG(ws->indel_keys.ensure((ni + 1) * sizeof(IndelKey)));
+    HIP_CHECK_MSG(ws->indel_sorted.ensure((ni + 1) * sizeof(IndelKey)));
+    HIP_CHECK_MSG(ws->indel_unique.ensure((ni + 1) * sizeof(IndelKey)));
+    HIP_CHECK_MSG(ws->indel_counts.ensure((ni + 1) * 4));
+    HIP_CHECK_MSG(ws->cands.ensure((ns + ni + 1) * sizeof(DevCand)));
     if (ns + ni > 0) {
         hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs_p, ws->meta_p,
                            n_reads, ws->subs.as<const SubDesc>(), max_len, ws->snp_off.as<const uint32_t>(),
                            ws->indel_off.as<const uint32_t>(), ws->n_snp.as<const uint32_t>(), ws->n_indel.as<const uint32_t>(),
                            ws->snp_keys.as<uint64_t>(), ws->indel_keys.as<IndelKey>());
-        CG_CHECK(hipGetLastError());
+        HIP_CHECK_MSG(hipGetLastError());
     }
     if (ns > 0) {
         size_t a = 0, b = 0;
-        CG_CHECK(rocprim::radix_sort_keys(nullptr, a, ws->snp_keys.as<uint64_t>(), ws->snp_sorted.as<uint64_t>(), (size_t)ns, 0u, 64u, stream));
-        CG_CHECK(rocprim::run_length_encode(nullptr, b, ws->snp_sorted.as<uint64_t>(), (unsigned)ns, ws->snp_unique.as<uint64_t>(),
-                                            ws->snp_counts.as<uint32_t>(), sc + 0, stream));
-        CG_CHECK(ws->temp.ensure(std::max(a, b)));
+        HIP_CHECK_MSG(rocprim::radix_sort_keys(nullptr, a, ws->snp_keys.as<uint64_t>(), ws->snp_sorted.as<uint64_t>(), (size_t)ns, 0u, 64u, stream));
+        HIP_CHECK_MSG(rocprim::run_length_encode(nullptr, b, ws->snp_sorted.as<uint64_t>(), (unsigned)ns, ws->snp_unique.as<uint64_t>(),
+                                                 ws->snp_counts.as<uint32_t>(), sc + 0, stream));
+        HIP_CHECK_MSG(ws->temp.ensure(std::max(a, b)));
         a = b = ws->temp.cap;
-        CG_CHECK(rocprim::radix_sort_keys(ws->temp.p, a, ws->snp_keys.as<uint64_t>(), ws->snp_sorted.as<uint64_t>(), (size_t)ns, 0u, 64u, stream));
-        CG_CHECK(rocprim::run_length_encode(ws->temp.p, b, ws->snp_sorted.as<uint64_t>(), (unsigned)ns, ws->snp_unique.as<uint64_t>(),
-                                            ws->snp_counts.as<uint32_t>(), sc + 0, stream));
+        HIP_CHECK_MSG(rocprim::radix_sort_keys(ws->temp.p, a, ws->snp_keys.as<uint64_t>(), ws->snp_sorted.as<uint64_t>(), (size_t)ns, 0u, 64u, stream));
+        HIP_CHECK_MSG(rocprim::run_length_encode(ws->temp.p, b, ws->snp_sorted.as<uint64_t>(), (unsigned)ns, ws->snp_unique.as<uint64_t>(),
+                                                 ws->snp_counts.as<uint32_t>(), sc + 0, stream));
         hipLaunchKernelGGL(filter_snp_kernel, dim3((unsigned)((ns + TB - 1) / TB)), dim3(TB), 0, stream, ws->snp_unique.as<const uint64_t>(),
                            ws->snp_counts.as<const uint32_t>(), sc + 0, ws->subs.as<const SubDesc>(), ws->depth.as<const int>(), snp_min,
                            ws->cands.as<DevCand>(), sc + 2);
-        CG_CHECK(hipGetLastError());
+        HIP_CHECK_MSG(hipGetLastError());
     }
     if (ni > 0) {
         size_t a = 0, b = 0;
-        CG_CHECK(rocprim::radix_sort_keys(nullptr, a, ws->indel_keys.as<IndelKey>(), ws->indel_sorted.as<IndelKey>(), (size_t)ni,
-                                          IndelDecomposer(), stream));
-        CG_CHECK(rocprim::run_length_encode(nullptr, b, ws->indel_sorted.as<IndelKey>(), (unsigned)ni, ws->indel_unique.as<IndelKey>(),
-                                            ws->indel_counts.as<uint32_t>(), sc + 1, stream));
-        CG_CHECK(ws->temp.ensure(std::max(a, b)));
+        HIP_CHECK_MSG(rocprim::radix_sort_keys(nullptr, a, ws->indel_keys.as<IndelKey>(), ws->indel_sorted.as<IndelKey>(), (size_t)ni,
+                                               IndelDecomposer(), stream));
+        HIP_CHECK_MSG(rocprim::run_length_encode(nullptr, b, ws->indel_sorted.as<IndelKey>(), (unsigned)ni, ws->indel_unique.as<IndelKey>(),
+                                                 ws->indel_counts.as<uint32_t>(), sc + 1, stream));
+        HIP_CHECK_MSG(ws->temp.ensure(std::max(a, b)));
         a = b = ws->temp.cap;
-        CG_CHECK(rocprim::radix_sort_keys(ws->temp.p, a, ws->indel_keys.as<IndelKey>(), ws->indel_sorted.as<IndelKey>(), (size_t)ni,
-                                          IndelDecomposer(), stream));
-        CG_CHECK(rocprim::run_length_encode(ws->temp.p, b, ws->indel_sorted.as<IndelKey>(), (unsigned)ni, ws->indel_unique.as<IndelKey>(),
-                                            ws->indel_counts.as<uint32_t>(), sc + 1, stream));
+        HIP_CHECK_MSG(rocprim::radix_sort_keys(ws->temp.p, a, ws->indel_keys.as<IndelKey>(), ws->indel_sorted.as<IndelKey>(), (size_t)ni,
+                                               IndelDecomposer(), stream));
+        HIP_CHECK_MSG(rocprim::run_length_encode(ws->temp.p, b, ws->indel_sorted.as<IndelKey>(), (unsigned)ni, ws->indel_unique.as<IndelKey>(),
+                                                 ws->indel_counts.as<uint32_t>(), sc + 1, stream));
         hipLaunchKernelGGL(filter_indel_kernel, dim3((unsigned)((ni + TB - 1) / TB)), dim3(TB), 0, stream, ws->indel_unique.as<const IndelKey>(),
                            ws->indel_counts.as<const uint32_t>(), sc + 1, ws->subs.as<const SubDesc>(), ws->depth.as<const int>(), indel_min,
                            ws->cands.as<DevCand>(), sc + 2);
-        CG_CHECK(hipGetLastError());
+        HIP_CHECK_MSG(hipGetLastError());
     }
-    CG_CHECK(hipEventRecord(ws->ev1, stream));
+    HIP_CHECK_MSG(hipEventRecord(ws->ev1, stream));
     uint32_t hs[3];
-    CG_CHECK(hipMemcpyAsync(hs, sc, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (n_reads) CG_CHECK(hipMemcpyAsync(ws->h_status.data(), ws->status.p, n_reads, hipMemcpyDeviceToHost, stream));
-    CG_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK_MSG(hipMemcpyAsync(hs, sc, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (n_reads) HIP_CHECK_MSG(hipMemcpyAsync(ws->h_status.data(), ws->status.p, n_reads, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK_MSG(hipStreamSynchronize(stream));
     *n_unique = (uint64_t)hs[0] + hs[1];
     ws->h_cands.resize(hs[2]);
     if (hs[2]) {
-        CG_CHECK(hipMemcpyAsync(ws->h_cands.data(), ws->cands.p, hs[2] * sizeof(DevCand), hipMemcpyDeviceToHost, stream));
-        CG_CHECK(hipStreamSynchronize(stream));
+        HIP_CHECK_MSG(hipMemcpyAsync(ws->h_cands.data(), ws->cands.p, hs[2] * sizeof(DevCand), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK_MSG(hipStreamSynchronize(stream));
     }
     *out = ws->h_cands.data();
     *n_out = hs[2];
     float ms = 0.f;
-    CG_CHECK(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
+    HIP_CHECK_MSG(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
     t->device_ms = ms;
     return 0;
 }

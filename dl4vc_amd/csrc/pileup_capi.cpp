@@ -1,6 +1,6 @@
 // Host side of libdl4vc_pileup.so (C ABI: include/dl4vc_pileup_gpu.h).  Locations are sorted by (tid, position) and cut
 // into runs; worker threads, each with its own BAM and FASTA handles, fetch every run's records once (BAI linear index; a
-// BAM without one gets the same index built by one scan), frame and validate them (bam_native.h::frame_record), and read
+// BAM without one gets the same index built by one scan), frame and validate them (the frame core of bam_frame.h), and read
 // the run's reference slice as tokens.  The records of a batch of locations go to the device in one pinned buffer; the
 // kernels (pileup_kernels.hip) do the rest.  Every extern "C" body catches what it throws: a corrupt file is an error code,
 // never an abort.
@@ -15,6 +15,7 @@
 #include "../../include/dl4vc_pileup_gpu.h"
 #include "bam_native.h"
 #include "bgzf_device.h"
+#include "device_buffer.h"
 #include "fasta_native.h"
 #include "pileup_device.h"
 #include "pileup_fetch.h"
@@ -74,16 +75,7 @@ struct Worker {
     std::vector<uint8_t> blk;
 };
 
-template <class T>
-bool grow(T*& p, size_t& cap, size_t n) {
-    if (n <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    const size_t want = n + n / 4 + 64;
-    if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) return false;
-    cap = want;
-    return true;
-}
+using dev::grow;
 
 }  // namespace
 

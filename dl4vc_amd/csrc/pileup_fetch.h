@@ -1,6 +1,6 @@
 // The records of one run of locations, framed on the host (libdl4vc_pileup.so without pg_set_inflate_device), and the CPU twin of
 // the device path: the index ranges and block table of bgzf_plan.h, the decode core of bgzf_inflate.h and the frame core of
-// pileup_frame.h, run serially.  No device call: tools/asan_pileup_frame.sh builds this under sanitizers.
+// bam_frame.h, run serially.  No device call: tools/asan_pileup_frame.sh builds this under sanitizers.
 #pragma once
 
 #include <fcntl.h>
@@ -122,15 +122,8 @@ inline void twin_records(const bamn::Bai& bai, const std::string& path, int32_t 
     for (const bz::Segment& sg : pl.segs) {                 // (bam_walk_kernel's checks, then the frame kernel's, record by record)
         uint64_t at = sg.start;
         while (at < sg.stop) {
-            uint32_t why = F::W_NONE;
             uint32_t size = 0;
-            if (sg.stop - at < 4) why = F::W_OVER_STOP;
-            else {
-                size = F::ld32(infl + at);
-                if (size < 32 || size > (1u << 28)) why = F::W_BLOCK_SIZE;
-                else if ((uint64_t)size + 4 > total - at) why = F::W_TRUNCATED;
-                else if ((uint64_t)size + 4 > sg.stop - at) why = F::W_OVER_STOP;
-            }
+            uint32_t why = F::next_record(infl, total, sg.stop, at, size);
             F::Framed fr;
             if (!why) why = F::frame_record(infl + at + 4, size, fr);
             if (!why && fr.tid == tid) why = F::walk_cigar(infl + at + 4, fr);

@@ -1,6 +1,6 @@
 // Framing for the GPU pileup encoder when the BAM is inflated on the device (pg_set_inflate_device; gfx950).  The inflate and the
 // record walk are bgzf_kernels.hip's; these kernels turn the walked record slots into what the encode kernels read:
-//   pileup_frame_kernel   one thread per record slot: the checks of the frame core (pileup_frame.h, the text the host path runs),
+//   pileup_frame_kernel   one thread per record slot: the checks of the frame core (bam_frame.h, the text the host path runs),
 //                         then the runs the record belongs to, found by binary search in the run table (sorted by tid and start;
 //                         the runs' stops rise with their starts, so they are neighbours);
 //   pileup_pair_kernel    one (run, slot) pair per membership, at the place an exclusive scan of the counts gives it; a stable
@@ -10,6 +10,7 @@
 //                         span and whether its positions never decrease;
 //   pileup_locate_kernel  one thread per location: the two lower bounds that give Loc::first and Loc::last.
 // Every output element has one writer; the only atomic is the integer minimum on the error word (lowest offset wins).
+#include "device_buffer.h"
 #include "pileup_device.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -19,7 +20,6 @@ namespace pg {
 namespace {
 
 namespace F = pg::frame;
-constexpr uint64_t NO_RECORD = ~0ull;
 constexpr int TB = 256;
 
 __device__ inline void report(unsigned long long* err, uint64_t off, uint32_t why) {
@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(TB) pileup_frame_kernel(const uint8_t* __restr
     uint32_t c = 0;
     int32_t k0 = 0;
     const uint64_t at = rec_off[i];
-    if (at != NO_RECORD) {
+    if (at != F::NO_RECORD) {
         const uint32_t size = F::ld32(infl + at);           // (checked by the walk: 32 <= size, at + 4 + size <= total)
         const uint8_t* b = infl + at + 4;
         F::Framed fr;
@@ -151,36 +151,14 @@ __global__ void __launch_bounds__(TB) pileup_locate_kernel(const Rec* __restrict
     locs[i].last = lower_pos(recs, ro.rec0, ro.rec1, (int64_t)locs[i].stop);
 }
 
-struct DBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    template <class T> T* as() const { return (T*)p; }
-    ~DBuf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 struct Framing {
-    DBuf runs, count, first, first_run, keys, vals, keys2, vals2, recs, nref, res, rec0, rec1, out, err, temp, loc_run;
+    dev::Buffer runs, count, first, first_run, keys, vals, keys2, vals2, recs, nref, res, rec0, rec1, out, err, temp, loc_run;
 };
 
 Framing* framing_create() { return new Framing(); }
 void framing_destroy(Framing* f) { delete f; }
-
-#define PG_CHECK(x)                                                        \
-    do {                                                                   \
-        const hipError_t e_ = (x);                                         \
-        if (e_ != hipSuccess) { *msg = hipGetErrorString(e_); return -2; } \
-    } while (0)
 
 int frame_runs(Framing* f, const uint8_t* infl, const uint64_t* rec_off, uint64_t n_slots, const RunDesc* runs, int32_t n_runs,
                hipStream_t stream, Rec** recs, int64_t* n_recs, int64_t* n_res, const RunOut** run_out, uint64_t* err, const char** msg) {
@@ -188,80 +166,80 @@ int frame_runs(Framing* f, const uint8_t* infl, const uint64_t* rec_off, uint64_
     if (n_runs <= 0) return 0;
     if (n_slots >= (1ull << 31)) { *msg = "too many record slots in one group"; return -2; }
     const uint32_t ns = (uint32_t)n_slots;
-    PG_CHECK(f->runs.ensure((size_t)n_runs * sizeof(RunDesc)));
-    PG_CHECK(f->rec0.ensure((size_t)n_runs * 4));
-    PG_CHECK(f->rec1.ensure((size_t)n_runs * 4));
-    PG_CHECK(f->out.ensure((size_t)n_runs * sizeof(RunOut)));
-    PG_CHECK(f->count.ensure(((size_t)ns + 1) * 4));
-    PG_CHECK(f->first.ensure(((size_t)ns + 1) * 4));
-    PG_CHECK(f->first_run.ensure(((size_t)ns + 1) * 4));
-    PG_CHECK(f->err.ensure(8));
+    HIP_CHECK_MSG(f->runs.ensure((size_t)n_runs * sizeof(RunDesc)));
+    HIP_CHECK_MSG(f->rec0.ensure((size_t)n_runs * 4));
+    HIP_CHECK_MSG(f->rec1.ensure((size_t)n_runs * 4));
+    HIP_CHECK_MSG(f->out.ensure((size_t)n_runs * sizeof(RunOut)));
+    HIP_CHECK_MSG(f->count.ensure(((size_t)ns + 1) * 4));
+    HIP_CHECK_MSG(f->first.ensure(((size_t)ns + 1) * 4));
+    HIP_CHECK_MSG(f->first_run.ensure(((size_t)ns + 1) * 4));
+    HIP_CHECK_MSG(f->err.ensure(8));
     unsigned long long* d_err = f->err.as<unsigned long long>();
-    PG_CHECK(hipMemcpyAsync(f->runs.p, runs, (size_t)n_runs * sizeof(RunDesc), hipMemcpyHostToDevice, stream));
-    PG_CHECK(hipMemsetAsync(d_err, 0xff, 8, stream));
-    PG_CHECK(hipMemsetAsync(f->rec0.p, 0, (size_t)n_runs * 4, stream));
-    PG_CHECK(hipMemsetAsync(f->rec1.p, 0, (size_t)n_runs * 4, stream));
+    HIP_CHECK_MSG(hipMemcpyAsync(f->runs.p, runs, (size_t)n_runs * sizeof(RunDesc), hipMemcpyHostToDevice, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(d_err, 0xff, 8, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(f->rec0.p, 0, (size_t)n_runs * 4, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(f->rec1.p, 0, (size_t)n_runs * 4, stream));
     uint32_t total = 0;
     if (ns > 0) {
         const unsigned grid = (ns + TB - 1) / TB;
         hipLaunchKernelGGL(pileup_frame_kernel, dim3(grid), dim3(TB), 0, stream, infl, rec_off, ns, f->runs.as<const RunDesc>(), n_runs,
                            f->count.as<uint32_t>(), f->first_run.as<int32_t>(), d_err);
-        PG_CHECK(hipGetLastError());
-        PG_CHECK(hipMemsetAsync(f->count.as<uint32_t>() + ns, 0, 4, stream));
+        HIP_CHECK_MSG(hipGetLastError());
+        HIP_CHECK_MSG(hipMemsetAsync(f->count.as<uint32_t>() + ns, 0, 4, stream));
         size_t tb = 0;
-        PG_CHECK(rocprim::exclusive_scan(nullptr, tb, f->count.as<uint32_t>(), f->first.as<uint32_t>(), 0u, (size_t)ns + 1,
-                                         rocprim::plus<uint32_t>(), stream));
-        PG_CHECK(f->temp.ensure(tb));
+        HIP_CHECK_MSG(rocprim::exclusive_scan(nullptr, tb, f->count.as<uint32_t>(), f->first.as<uint32_t>(), 0u, (size_t)ns + 1,
+                                              rocprim::plus<uint32_t>(), stream));
+        HIP_CHECK_MSG(f->temp.ensure(tb));
         tb = f->temp.cap;
-        PG_CHECK(rocprim::exclusive_scan(f->temp.p, tb, f->count.as<uint32_t>(), f->first.as<uint32_t>(), 0u, (size_t)ns + 1,
-                                         rocprim::plus<uint32_t>(), stream));
+        HIP_CHECK_MSG(rocprim::exclusive_scan(f->temp.p, tb, f->count.as<uint32_t>(), f->first.as<uint32_t>(), 0u, (size_t)ns + 1,
+                                              rocprim::plus<uint32_t>(), stream));
         unsigned long long h_err = 0;
-        PG_CHECK(hipMemcpyAsync(&total, f->first.as<uint32_t>() + ns, 4, hipMemcpyDeviceToHost, stream));
-        PG_CHECK(hipMemcpyAsync(&h_err, d_err, 8, hipMemcpyDeviceToHost, stream));
-        PG_CHECK(hipStreamSynchronize(stream));
+        HIP_CHECK_MSG(hipMemcpyAsync(&total, f->first.as<uint32_t>() + ns, 4, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK_MSG(hipMemcpyAsync(&h_err, d_err, 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK_MSG(hipStreamSynchronize(stream));
         if (h_err != FRAME_NO_ERROR) { *err = h_err; return 0; }
         if (total >= (1u << 31)) { *msg = "too many records in one group"; return -2; }
     }
-    PG_CHECK(f->recs.ensure(((size_t)total + 1) * sizeof(Rec)));
+    HIP_CHECK_MSG(f->recs.ensure(((size_t)total + 1) * sizeof(Rec)));
     if (total > 0) {
         const unsigned grid = (ns + TB - 1) / TB, pgrid = (total + TB - 1) / TB;
-        PG_CHECK(f->keys.ensure((size_t)total * 4));
-        PG_CHECK(f->vals.ensure((size_t)total * 4));
-        PG_CHECK(f->keys2.ensure((size_t)total * 4));
-        PG_CHECK(f->vals2.ensure((size_t)total * 4));
-        PG_CHECK(f->nref.ensure(((size_t)total + 1) * 8));
-        PG_CHECK(f->res.ensure(((size_t)total + 1) * 8));
+        HIP_CHECK_MSG(f->keys.ensure((size_t)total * 4));
+        HIP_CHECK_MSG(f->vals.ensure((size_t)total * 4));
+        HIP_CHECK_MSG(f->keys2.ensure((size_t)total * 4));
+        HIP_CHECK_MSG(f->vals2.ensure((size_t)total * 4));
+        HIP_CHECK_MSG(f->nref.ensure(((size_t)total + 1) * 8));
+        HIP_CHECK_MSG(f->res.ensure(((size_t)total + 1) * 8));
         hipLaunchKernelGGL(pileup_pair_kernel, dim3(grid), dim3(TB), 0, stream, ns, f->count.as<const uint32_t>(), f->first.as<const uint32_t>(),
                            f->first_run.as<const int32_t>(), f->keys.as<uint32_t>(), f->vals.as<uint32_t>());
-        PG_CHECK(hipGetLastError());
+        HIP_CHECK_MSG(hipGetLastError());
         unsigned bits = 1;
         while (bits < 32 && (1ull << bits) < (unsigned long long)n_runs) ++bits;
         size_t tb = 0;
-        PG_CHECK(rocprim::radix_sort_pairs(nullptr, tb, f->keys.as<uint32_t>(), f->keys2.as<uint32_t>(), f->vals.as<uint32_t>(),
-                                           f->vals2.as<uint32_t>(), (size_t)total, 0, bits, stream));
-        PG_CHECK(f->temp.ensure(tb));
+        HIP_CHECK_MSG(rocprim::radix_sort_pairs(nullptr, tb, f->keys.as<uint32_t>(), f->keys2.as<uint32_t>(), f->vals.as<uint32_t>(),
+                                                f->vals2.as<uint32_t>(), (size_t)total, 0, bits, stream));
+        HIP_CHECK_MSG(f->temp.ensure(tb));
         tb = f->temp.cap;
-        PG_CHECK(rocprim::radix_sort_pairs(f->temp.p, tb, f->keys.as<uint32_t>(), f->keys2.as<uint32_t>(), f->vals.as<uint32_t>(),
-                                           f->vals2.as<uint32_t>(), (size_t)total, 0, bits, stream));
+        HIP_CHECK_MSG(rocprim::radix_sort_pairs(f->temp.p, tb, f->keys.as<uint32_t>(), f->keys2.as<uint32_t>(), f->vals.as<uint32_t>(),
+                                                f->vals2.as<uint32_t>(), (size_t)total, 0, bits, stream));
         hipLaunchKernelGGL(pileup_emit_kernel, dim3(pgrid), dim3(TB), 0, stream, infl, rec_off, f->keys2.as<const uint32_t>(),
                            f->vals2.as<const uint32_t>(), total, f->recs.as<Rec>(), f->nref.as<unsigned long long>(), f->rec0.as<int32_t>(),
                            f->rec1.as<int32_t>());
-        PG_CHECK(hipGetLastError());
-        PG_CHECK(hipMemsetAsync(f->nref.as<unsigned long long>() + total, 0, 8, stream));
+        HIP_CHECK_MSG(hipGetLastError());
+        HIP_CHECK_MSG(hipMemsetAsync(f->nref.as<unsigned long long>() + total, 0, 8, stream));
         tb = 0;
-        PG_CHECK(rocprim::exclusive_scan(nullptr, tb, f->nref.as<unsigned long long>(), f->res.as<unsigned long long>(), 0ull,
-                                         (size_t)total + 1, rocprim::plus<unsigned long long>(), stream));
-        PG_CHECK(f->temp.ensure(tb));
+        HIP_CHECK_MSG(rocprim::exclusive_scan(nullptr, tb, f->nref.as<unsigned long long>(), f->res.as<unsigned long long>(), 0ull,
+                                              (size_t)total + 1, rocprim::plus<unsigned long long>(), stream));
+        HIP_CHECK_MSG(f->temp.ensure(tb));
         tb = f->temp.cap;
-        PG_CHECK(rocprim::exclusive_scan(f->temp.p, tb, f->nref.as<unsigned long long>(), f->res.as<unsigned long long>(), 0ull,
-                                         (size_t)total + 1, rocprim::plus<unsigned long long>(), stream));
+        HIP_CHECK_MSG(rocprim::exclusive_scan(f->temp.p, tb, f->nref.as<unsigned long long>(), f->res.as<unsigned long long>(), 0ull,
+                                              (size_t)total + 1, rocprim::plus<unsigned long long>(), stream));
     }
     hipLaunchKernelGGL(pileup_run_kernel, dim3((unsigned)n_runs), dim3(TB), 0, stream, f->recs.as<Rec>(), f->res.as<const unsigned long long>(),
                        f->rec0.as<const int32_t>(), f->rec1.as<const int32_t>(), n_runs, f->out.as<RunOut>());
-    PG_CHECK(hipGetLastError());
+    HIP_CHECK_MSG(hipGetLastError());
     unsigned long long h_res = 0;
-    if (total > 0) PG_CHECK(hipMemcpyAsync(&h_res, f->res.as<unsigned long long>() + total, 8, hipMemcpyDeviceToHost, stream));
-    PG_CHECK(hipStreamSynchronize(stream));
+    if (total > 0) HIP_CHECK_MSG(hipMemcpyAsync(&h_res, f->res.as<unsigned long long>() + total, 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK_MSG(hipStreamSynchronize(stream));
     *recs = f->recs.as<Rec>();
     *n_recs = (int64_t)total;
     *n_res = (int64_t)std::min<unsigned long long>(h_res, (unsigned long long)INT64_MAX);
@@ -272,15 +250,15 @@ int frame_runs(Framing* f, const uint8_t* infl, const uint64_t* rec_off, uint64_
 int locate(Framing* f, const Rec* recs, const RunOut* run_out, int32_t n_runs, const int32_t* loc_run, Loc* locs, int32_t n_locs,
            hipStream_t stream, const char** msg, hipEvent_t uploaded) {
     if (n_locs <= 0) {
-        if (uploaded) PG_CHECK(hipEventRecord(uploaded, stream));
+        if (uploaded) HIP_CHECK_MSG(hipEventRecord(uploaded, stream));
         return 0;
     }
-    PG_CHECK(f->loc_run.ensure((size_t)n_locs * 4));
-    PG_CHECK(hipMemcpyAsync(f->loc_run.p, loc_run, (size_t)n_locs * 4, hipMemcpyHostToDevice, stream));
-    if (uploaded) PG_CHECK(hipEventRecord(uploaded, stream));
+    HIP_CHECK_MSG(f->loc_run.ensure((size_t)n_locs * 4));
+    HIP_CHECK_MSG(hipMemcpyAsync(f->loc_run.p, loc_run, (size_t)n_locs * 4, hipMemcpyHostToDevice, stream));
+    if (uploaded) HIP_CHECK_MSG(hipEventRecord(uploaded, stream));
     hipLaunchKernelGGL(pileup_locate_kernel, dim3((unsigned)((n_locs + TB - 1) / TB)), dim3(TB), 0, stream, recs, run_out, n_runs,
                        f->loc_run.as<const int32_t>(), locs, n_locs);
-    PG_CHECK(hipGetLastError());
+    HIP_CHECK_MSG(hipGetLastError());
     return 0;
 }
 

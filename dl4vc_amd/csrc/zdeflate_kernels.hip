@@ -1,5 +1,6 @@
 // Kernels of the device compressor (zdeflate_device.h): the candidate records of an HDF5 chunk packed into the compound layout,
 // compressed into zlib streams (zdeflate.h, one lane per segment), and the streams placed one behind the other.  wave64, gfx950.
+#include "device_buffer.h"
 #include "zdeflate_device.h"
 
 #include <rocprim/device/device_scan.hpp>
@@ -105,17 +106,7 @@ __global__ __launch_bounds__(COPY_BLOCK) void zd_gather_kernel(const uint8_t* in
     for (uint64_t i = threadIdx.x; i < n; i += COPY_BLOCK) dst[i] = src[i];
 }
 
-template <class T>
-bool grow(T*& p, size_t& cap, size_t n) {
-    if (n <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = n + n / 4 + 64;
-    if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) return false;
-    cap = want;
-    return true;
-}
+using dev::grow;
 
 }  // namespace
 

@@ -191,7 +191,8 @@ def shared_block(tmp):
 
 
 # ---- damaged inputs: the file of one contig below, damaged, beside the index of its undamaged twin --------------------------
-DAMAGED = ["crc_flipped", "truncated_bgzf", "block_size_past_eof", "l_seq_past_record", "n_cigar_past_record", "cigar_600m"]
+DAMAGED = ["crc_flipped", "truncated_bgzf", "block_size_past_eof", "l_seq_past_record", "n_cigar_past_record", "cigar_600m",
+           "aux_string_without_nul", "aux_value_type"]
 # what the error says: (the host path, the device path and its CPU twin).  A cut block is met by the host's block reader and by
 # the device path's range planner (the index points past the end of the cut file), which have their own words for it.
 EXPECT = {"crc_flipped": ("BGZF block fails its CRC / size check", "BGZF block fails its CRC / size check (CRC mismatch, block at file offset"),
@@ -199,7 +200,9 @@ EXPECT = {"crc_flipped": ("BGZF block fails its CRC / size check", "BGZF block f
           "block_size_past_eof": ("truncated BAM record (record at virtual offset", "truncated BAM record (record at virtual offset"),
           "l_seq_past_record": ("corrupt BAM record (l_seq exceeds the record) (record at virtual offset",) * 2,
           "n_cigar_past_record": ("corrupt BAM record (n_cigar_op exceeds the record) (record at virtual offset",) * 2,
-          "cigar_600m": ("corrupt BAM record (CIGAR reference length) (record at virtual offset",) * 2}
+          "cigar_600m": ("corrupt BAM record (CIGAR reference length) (record at virtual offset",) * 2,
+          "aux_string_without_nul": ("corrupt BAM record (aux string without its NUL) (record at virtual offset",) * 2,
+          "aux_value_type": ("corrupt BAM record (aux value type) (record at virtual offset",) * 2}
 DAMAGED_WINDOW = (0, 0, 3200)
 
 
@@ -212,10 +215,14 @@ def _bgzf(data):
 
 def damaged(tmp, kind):
     """-> (bam, bai, fasta).  The header is a block of its own (the encoder reads it on the host when it opens the file); the
-    records follow in blocks of 20 000 bytes; the third record is the damaged one."""
+    records follow in blocks of 20 000 bytes; the third record is the damaged one (for the aux kinds it carries an MD:Z tag, in
+    the twin as well)."""
     ref = make_ref(4000, 77)
     rs = [read(ref, 20 + 7 * i, "20M20M20M", "k%d" % i, 16 * (i & 1), 30) for i in range(500)]
     recs = [_pack(r) for r in rs]
+    if kind.startswith("aux_"):
+        r = rs[2]
+        recs[2] = bamio.pack_record(r.tid, r.pos, r.name, r.flag, r.mapq, list(r.cigar), r.seq, r.qual.tolist(), aux=b"NMC\x00MDZ60\x00")
     text = "@HD\tVN:1.6\tSO:coordinate\n@SQ\tSN:ctg\tLN:4000\n".encode()
     head = bamio.BAM_MAGIC + struct.pack("<i", len(text)) + text + struct.pack("<i", 1) + struct.pack("<i", 4) + b"ctg\x00" + struct.pack("<i", 4000)
     d = os.path.join(str(tmp), kind)
@@ -245,6 +252,10 @@ def damaged(tmp, kind):
     elif kind == "cigar_600m":                               # 600 000 000 M, as three operations of 200 000 000 M (28 bits each)
         o = 4 + 32 + bad[12]
         bad[o:o + 12] = struct.pack("<I", (200_000_000 << 4) | bamio.CMATCH) * 3
+    elif kind == "aux_string_without_nul":                   # the MD terminator, the record's last byte
+        bad[-1] = ord("A")
+    elif kind == "aux_value_type":
+        bad[-4] = ord("x")                                   # MD:Z -> MD:x
     recs2 = list(recs)
     recs2[2] = bytes(bad)
     write(bam, recs2, cut=kind == "truncated_bgzf", flip=kind == "crc_flipped")

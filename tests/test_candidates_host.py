@@ -112,6 +112,10 @@ def _bgzf(data):
             struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data)))
 
 
+AUX_KINDS = {"aux_string_without_nul": "corrupt BAM record (aux string without its NUL) (record at virtual offset",
+             "aux_value_type": "corrupt BAM record (aux value type) (record at virtual offset"}
+
+
 def _damaged(tmp_path, kind):
     fx = load("nochr")
     good = write_bam(fx, str(tmp_path / "good.bam"), index=False)
@@ -131,6 +135,13 @@ def _damaged(tmp_path, kind):
         rec[20:24] = struct.pack("<i", 5000)
     elif kind == "n_cigar_past_record":
         rec[16:18] = struct.pack("<H", 4000)
+    elif kind in AUX_KINDS:
+        md = rec.index(b"MDZ", 4 + 32)                       # the first record's MD tag (its name, CIGAR and bases hold no "MDZ")
+        if kind == "aux_string_without_nul":                 # the terminator and everything behind it
+            nul = rec.index(b"\x00", md + 3)
+            rec[nul:] = b"A" * (len(rec) - nul)
+        else:
+            rec[md + 2] = ord("x")
     data = raw[:first] + bytes(rec) + rest
     p = str(tmp_path / (kind + ".bam"))
     blob = b"".join(_bgzf(data[i:i + 60000]) for i in range(0, len(data), 60000)) + _bgzf(b"")
@@ -143,7 +154,7 @@ def _damaged(tmp_path, kind):
     return p
 
 
-@pytest.mark.parametrize("kind", ["truncated_bgzf", "block_size_past_eof", "l_seq_past_record", "n_cigar_past_record"])
+@pytest.mark.parametrize("kind", ["truncated_bgzf", "block_size_past_eof", "l_seq_past_record", "n_cigar_past_record"] + list(AUX_KINDS))
 def test_corrupt_bam_is_an_error_not_a_crash(tmp_path, kind):
     """Run in a child process so that an abort would show as a signal, not take the test run down."""
     bam = _damaged(tmp_path, kind)
@@ -158,3 +169,5 @@ def test_corrupt_bam_is_an_error_not_a_crash(tmp_path, kind):
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert r.returncode == 3, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     assert "corrupt BAM record" in r.stdout or "truncated" in r.stdout or "BGZF" in r.stdout, r.stdout
+    if kind in AUX_KINDS:
+        assert AUX_KINDS[kind] in r.stdout, r.stdout

@@ -14,7 +14,7 @@ from dl4vc_amd import bamio, candidates as C
 from dl4vc_amd.candgen import CandidateCounter, Stats
 from dl4vc_amd.vcfpost import BGZF_BLOCK
 from tests.candidates_fixture import NAMES, load, write_bam
-from tests.test_candidates_host import _bgzf, _blocks, _damaged
+from tests.test_candidates_host import AUX_KINDS, _bgzf, _blocks, _damaged
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -180,20 +180,38 @@ def _with_twin_index(tmp_path, kind):
     return bam
 
 
-@pytest.mark.parametrize("kind", ["truncated_bgzf", "block_size_past_eof", "l_seq_past_record", "n_cigar_past_record", "crc_flipped"])
+REFUSED_RECORD = ["block_size_past_eof", "l_seq_past_record", "n_cigar_past_record"] + list(AUX_KINDS)
+
+
+@pytest.mark.parametrize("kind", ["truncated_bgzf", "crc_flipped"] + REFUSED_RECORD)
 def test_corrupt_bam_is_an_error_on_the_device_path(tmp_path, kind):
+    """In a child process, so that an abort would show as a signal.  A record the framing refuses is refused with the host
+    path's message on the same file: one table of texts, and the same virtual offset."""
     bam = _with_twin_index(tmp_path, kind)
     code = ("import sys; sys.path.insert(0, %r)\n"
             "from dl4vc_amd.candgen import CandidateCounter\n"
-            "try:\n"
-            "    cc = CandidateCounter(%r, threads=2, inflate_device='gpu')\n"
-            "    cc.run([(0, 0, 3200)])\n"
-            "except RuntimeError as e:\n"
-            "    print('ERR', e); sys.exit(3)\n"
-            "print('OK')\n") % (ROOT, bam)
+            "def refusal(**kw):\n"
+            "    try:\n"
+            "        CandidateCounter(%r, threads=2, **kw).run([(0, 0, 3200)])\n"
+            "    except RuntimeError as e:\n"
+            "        return str(e)\n"
+            "dev = refusal(inflate_device='gpu')\n"
+            "if dev is None:\n"
+            "    print('OK'); sys.exit(0)\n"
+            "print('ERR', dev)\n"
+            "if %r:\n"
+            "    print('HOST', refusal())\n"
+            "sys.exit(3)\n") % (ROOT, bam, kind in REFUSED_RECORD)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert r.returncode == 3, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     assert "corrupt BAM record" in r.stdout or "truncated" in r.stdout or "BGZF" in r.stdout, r.stdout
+    if kind in REFUSED_RECORD:
+        lines = r.stdout.splitlines()
+        dev = [l[4:] for l in lines if l.startswith("ERR ")]
+        host = [l[5:] for l in lines if l.startswith("HOST ")]
+        assert len(dev) == 1 and dev == host and "(record at virtual offset " in dev[0], r.stdout
+    if kind in AUX_KINDS:
+        assert AUX_KINDS[kind] in r.stdout, r.stdout
 
 
 def test_no_index_is_refused_with_the_reason(tmp_path):

@@ -163,7 +163,7 @@ def test_encode_device_equals_host_encode(tmp_path):
 
 
 @pytest.mark.parametrize("kind", ["truncated_bgzf", "block_size_past_eof", "l_seq_past_record", "n_cigar_past_record",
-                                  "cigar_span_overflow"])
+                                  "cigar_span_overflow", "aux_string_without_nul", "aux_value_type"])
 def test_corrupt_bam_is_an_error_not_a_crash(tmp_path, kind):
     """Run in a child process so that an abort would show as a signal, not take the test run down."""
     if kind == "cigar_span_overflow":        # nine D operations of 2^28 - 1: the span overflows 32 bits
@@ -173,7 +173,7 @@ def test_corrupt_bam_is_an_error_not_a_crash(tmp_path, kind):
         bam, fa = write_inputs(tmp_path, fa_ref, [r], tag="overflow", index=False)
         name = "ref"
     else:
-        from tests.test_candidates_host import _damaged
+        from tests.test_candidates_host import AUX_KINDS, _damaged
         bam = _damaged(tmp_path, kind)
         name, length = load("nochr")["references"][0]
         fa = str(tmp_path / "r.fa")
@@ -189,3 +189,5 @@ def test_corrupt_bam_is_an_error_not_a_crash(tmp_path, kind):
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 3, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     assert "corrupt BAM record" in r.stdout or "truncated" in r.stdout or "BGZF" in r.stdout, r.stdout
+    if kind.startswith("aux_"):
+        assert AUX_KINDS[kind] in r.stdout, r.stdout

@@ -1,9 +1,9 @@
 #!/bin/bash
 # CPU sanitizer pass over the framing of the GPU pileup encoder's device inflate path: builds pg_debug_run_records
 # (dl4vc_amd/csrc/pileup_debug.cpp: the planning of bgzf_plan.h, the decode core of bgzf_inflate.h and the frame core of
-# pileup_frame.h, the text the kernels run) with -fsanitize=address,undefined into a scratch directory and runs the grid and the
-# damaged inputs of tests/pileup_inflate_cases.py through both of its paths.  CPU only; run it before damaged files go near a
-# GPU.  usage: tools/asan_pileup_frame.sh
+# bam_frame.h with the encoder's own part in pileup_frame.h, the text the kernels run) with -fsanitize=address,undefined into a
+# scratch directory and runs the grid and the damaged inputs of tests/pileup_inflate_cases.py through both of its paths.  CPU
+# only; run it before damaged files go near a GPU.  usage: tools/asan_pileup_frame.sh
 set -e
 cd "$(dirname "$0")/.."
 out=$(mktemp -d)
