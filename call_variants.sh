@@ -15,14 +15,17 @@
 # -c (on the path through candidates.hdf, no effect with -d): the converter builds the pileups on the GPU and packs and compresses
 # the file's chunks there as well (--pileup-device gpu --compress-device gpu); candidates.hdf holds the same records, the scored
 # VCF is the same.
+# -y (with -c): the compressed chunks get dynamic Huffman codes where they are smaller (--compress-codes dynamic): a smaller
+# candidates.hdf with the same records.
 set -e
-usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-c]"; exit 1; }
+usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-c [-y]]"; exit 1; }
 GPUS=1
 PROCS=16
 DIRECT=0
 INFLATE=""
 COMPRESS=""
-while getopts "m:o:g:i:r:b:p:dzch" opt; do
+CODES=""
+while getopts "m:o:g:i:r:b:p:dzcyh" opt; do
   case $opt in
     m) MODEL=$OPTARG ;;
     o) OUTDIR=$OPTARG ;;
@@ -34,10 +37,12 @@ while getopts "m:o:g:i:r:b:p:dzch" opt; do
     d) DIRECT=1 ;;          # score straight from the BAM (main.py --test_bam)
     z) INFLATE=gpu ;;       # BGZF inflate and record framing on the GPU: candidate generation, and with -d the pileup encoder
     c) COMPRESS=gpu ;;      # candidates.hdf: pileups, record packing and chunk compression on the GPU
+    y) CODES=dynamic ;;     # with -c: dynamic Huffman codes in the compressed chunks
     *) usage ;;
   esac
 done
 [ -z "$MODEL" ] || [ -z "$OUTDIR" ] && usage
+[ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
 SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 if [ ! -f "$OUTDIR/candidates.hdf" ] && [ ! -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ]; then
   mkdir -p "$OUTDIR"
@@ -59,7 +64,8 @@ if [ "$DIRECT" != 1 ] && [ ! -f "$OUTDIR/candidates.hdf" ]; then
   python "$SCRIPTDIR/tools/convert_bam_single_reads.py" --input "$BAM" --fp_vcf "$OUTDIR/candidates.vcf" \
       --fasta-input "$REFERENCE" --output "$OUTDIR/candidates.hdf" --max-reads 200 --num-processes "$PROCS" \
       --locations-process-step 100000 --max-insert-length 10 --max-insert-length-variant 50 \
-      --save-q-scores --save-strand ${COMPRESS:+--pileup-device gpu --compress-device "$COMPRESS"} > "$OUTDIR/training_data.log" 2>&1
+      --save-q-scores --save-strand ${COMPRESS:+--pileup-device gpu --compress-device "$COMPRESS"} \
+      ${CODES:+--compress-codes "$CODES"} > "$OUTDIR/training_data.log" 2>&1
 fi
 
 printf "Run inference...\n"

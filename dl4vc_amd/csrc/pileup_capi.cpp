@@ -120,6 +120,8 @@ struct pg_encoder {
     // pg_compress_records_device: the compressor's buffers, the packed chunk image, the streams, the blob and slots (device and
     // pinned staging), the pinned bytes handed to the caller
     zd::Ctx* zctx = nullptr;
+    bool compress_dynamic = false;              // pg_set_compress_codes
+    std::vector<uint8_t> seg_kind;
     uint8_t* d_image = nullptr; size_t c_image = 0;
     uint8_t* d_zout = nullptr; size_t c_zout = 0;
     uint8_t* d_blob = nullptr; size_t c_blob = 0;
@@ -798,6 +800,7 @@ int compress_records(pg_encoder* h, const uint8_t* reads, const uint8_t* qual, c
     if (chunk_bytes > zd::MAX_STREAM) return fail(h, -1, "pg_compress_records_device: a chunk of %llu bytes is too large", (unsigned long long)chunk_bytes);
     h->st.pack_ms = h->st.deflate_ms = h->st.gather_ms = h->st.compress_copy_back_ms = 0;
     h->st.chunks = h->st.raw_bytes = h->st.chunk_bytes_out = h->st.stored_chunks = 0;
+    h->st.fixed_segments = h->st.dynamic_segments = h->st.stored_segments = 0;
     if (n == 0) return 0;
     if (!reads || !qual || !strand || !slots || !blob || !offsets || !sizes || !adlers || !store)
         return fail(h, -1, "pg_compress_records_device: null argument");
@@ -849,14 +852,21 @@ int compress_records(pg_encoder* h, const uint8_t* reads, const uint8_t* qual, c
         PZ_TRY(hipEventRecord(h->zev[1], s));
         zd::Streams r{};
         const char* msg = nullptr;
-        if (zd::run(h->zctx, h->d_image, chunk_bytes, nc, zd::DEFAULT_SEG, false, true, h->d_zout, s, h->zev[2], &r, &msg))
+        if (zd::run(h->zctx, h->d_image, chunk_bytes, nc, zd::DEFAULT_SEG, false, true, h->compress_dynamic, h->d_zout, s, h->zev[2], &r, &msg))
             return fail(h, -2, "pg_compress_records_device: %s", msg);
         PZ_TRY(hipEventRecord(h->zev[3], s));
         PZ_TRY(hipMemcpyAsync(offsets + c0, r.offs, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
         PZ_TRY(hipMemcpyAsync(sizes + c0, r.sizes, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
         PZ_TRY(hipMemcpyAsync(adlers + c0, r.adlers, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
         PZ_TRY(hipMemcpyAsync(store + c0, r.store, (size_t)nc, hipMemcpyDeviceToHost, s));
+        if (r.seg_kind) {
+            h->seg_kind.resize((size_t)r.n_segs);
+            PZ_TRY(hipMemcpyAsync(h->seg_kind.data(), r.seg_kind, (size_t)r.n_segs, hipMemcpyDeviceToHost, s));
+        }
         PZ_TRY(hipStreamSynchronize(s));
+        if (r.seg_kind)
+            for (const uint8_t kind : h->seg_kind)
+                ++*(kind == zd::KIND_DYNAMIC ? &h->st.dynamic_segments : kind == zd::KIND_STORED ? &h->st.stored_segments : &h->st.fixed_segments);
         const uint64_t bytes = offsets[c0 + nc - 1] + sizes[c0 + nc - 1];
         if (bytes > (uint64_t)nc * cbound) return fail(h, -2, "pg_compress_records_device: the streams exceed their bound");
         if (total && total + bytes > h->hc_zout) {             // a later pass outgrows the pinned buffer: keep what it holds
@@ -990,6 +1000,13 @@ int pg_set_inflate_device(pg_encoder_t* h, int on, uint64_t max_inflated_bytes) 
     } catch (...) {
         return fail(h, -4, "pg_set_inflate_device: unknown exception");
     }
+}
+
+int pg_set_compress_codes(pg_encoder_t* h, int mode) {
+    if (!h) return fail(nullptr, -1, "pg_set_compress_codes: null handle");
+    if (mode != 0 && mode != 1) return fail(h, -1, "pg_set_compress_codes: mode %d is neither 0 (fixed) nor 1 (dynamic)", mode);
+    h->compress_dynamic = mode == 1;
+    return 0;
 }
 
 int pg_get_stats(const pg_encoder_t* h, pg_stats* out) {

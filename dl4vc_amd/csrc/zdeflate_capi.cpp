@@ -26,6 +26,46 @@ int zfail(int code, const std::string& what) {
 
 bool seg_ok(uint32_t seg) { return seg >= zd::MIN_SEG && seg <= zd::MAX_SEG; }
 
+int deflate_host(const char* who, const uint8_t* in, uint64_t n, uint32_t segment, int32_t flags, uint8_t* out, uint64_t out_cap,
+                 uint64_t* size, uint32_t* adler, int32_t* store) {
+    const std::string name(who);
+    try {
+        if ((n && !in) || !out || !size || !adler || !store) return zfail(-1, name + ": null argument");
+        if (!seg_ok(segment)) return zfail(-1, name + ": segment must be 1024..32768 bytes");
+        if (n > zd::MAX_STREAM) return zfail(-1, name + ": more than 2^31 bytes in one stream");
+        if (out_cap < zd::bound(n, segment)) return zfail(-1, name + ": the output buffer is smaller than zd_bound");
+        const uint64_t ns = zd::n_segments(n, segment);
+        std::vector<uint32_t> sizes(ns), adlers(ns);
+        std::vector<uint64_t> offs(ns);
+        std::vector<uint16_t> head(zd::HASH_SIZE);
+        std::vector<uint32_t> work(flags & ZD_DYNAMIC ? zd::WORK_SIZE : 0), build(flags & ZD_DYNAMIC ? zd::BUILD_SIZE : 0);
+        // the segments land where the device's gather puts them: one behind the other after the 2-byte header
+        uint64_t at = 2;
+        for (uint64_t k = 0; k < ns; ++k) {
+            const uint32_t len = (uint32_t)(k + 1 < ns ? segment : n - k * segment);
+            const uint8_t* src = in + k * segment;
+            int kind = 0;
+            adlers[k] = zd::adler32(src, len);
+            sizes[k] = flags & ZD_DYNAMIC                  // (at + seg_cap(len) + 4 <= bound)
+                           ? zd::deflate_segment_dynamic(src, len, k + 1 == ns, out + at, head.data(), 1, work.data(), 1, build.data(), &kind)
+                           : zd::deflate_segment(src, len, k + 1 == ns, out + at, head.data(), 1);
+            at += sizes[k];
+        }
+        const zd::StreamInfo r = zd::finish_stream(n, segment, sizes.data(), adlers.data(), offs.data());
+        out[0] = zd::ZLIB_CMF;
+        out[1] = zd::ZLIB_FLG;
+        for (int b = 0; b < 4; ++b) out[at + b] = (uint8_t)(r.adler >> (8 * (3 - b)));
+        *size = r.size;
+        *adler = r.adler;
+        *store = (int32_t)r.store;
+        return 0;
+    } catch (const std::exception& e) {
+        return zfail(-4, name + ": " + e.what());
+    } catch (...) {
+        return zfail(-4, name + ": unknown exception");
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -40,36 +80,31 @@ int zd_bound(uint64_t n, uint32_t segment, uint64_t* bound) {
 
 int zd_deflate_host(const uint8_t* in, uint64_t n, uint32_t segment, uint8_t* out, uint64_t out_cap, uint64_t* size, uint32_t* adler,
                     int32_t* store) {
+    return deflate_host("zd_deflate_host", in, n, segment, 0, out, out_cap, size, adler, store);
+}
+
+int zd_deflate_host_flags(const uint8_t* in, uint64_t n, uint32_t segment, int32_t flags, uint8_t* out, uint64_t out_cap, uint64_t* size,
+                          uint32_t* adler, int32_t* store) {
+    if (flags & ~ZD_DYNAMIC) return zfail(-1, "zd_deflate_host_flags: the only flag of the host form is ZD_DYNAMIC");
+    return deflate_host("zd_deflate_host_flags", in, n, segment, flags, out, out_cap, size, adler, store);
+}
+
+int zd_code_lengths_host(const uint32_t* freq, int32_t n, int32_t limit, uint8_t* lens) {
     try {
-        if ((n && !in) || !out || !size || !adler || !store) return zfail(-1, "zd_deflate_host: null argument");
-        if (!seg_ok(segment)) return zfail(-1, "zd_deflate_host: segment must be 1024..32768 bytes");
-        if (n > zd::MAX_STREAM) return zfail(-1, "zd_deflate_host: more than 2^31 bytes in one stream");
-        if (out_cap < zd::bound(n, segment)) return zfail(-1, "zd_deflate_host: the output buffer is smaller than zd_bound");
-        const uint64_t ns = zd::n_segments(n, segment);
-        std::vector<uint32_t> sizes(ns), adlers(ns);
-        std::vector<uint64_t> offs(ns);
-        std::vector<uint16_t> head(zd::HASH_SIZE);
-        // the segments land where the device's gather puts them: one behind the other after the 2-byte header
-        uint64_t at = 2;
-        for (uint64_t k = 0; k < ns; ++k) {
-            const uint32_t len = (uint32_t)(k + 1 < ns ? segment : n - k * segment);
-            const uint8_t* src = in + k * segment;
-            adlers[k] = zd::adler32(src, len);
-            sizes[k] = zd::deflate_segment(src, len, k + 1 == ns, out + at, head.data(), 1);    // (at + seg_cap(len) + 4 <= bound)
-            at += sizes[k];
-        }
-        const zd::StreamInfo r = zd::finish_stream(n, segment, sizes.data(), adlers.data(), offs.data());
-        out[0] = zd::ZLIB_CMF;
-        out[1] = zd::ZLIB_FLG;
-        for (int b = 0; b < 4; ++b) out[at + b] = (uint8_t)(r.adler >> (8 * (3 - b)));
-        *size = r.size;
-        *adler = r.adler;
-        *store = (int32_t)r.store;
+        if (!freq || !lens) return zfail(-1, "zd_code_lengths_host: null argument");
+        if (n < 2 || n > (int32_t)zd::N_LL || limit < 1 || limit > zd::MAX_BITS || (n > 2 && (1 << limit) < n))
+            return zfail(-1, "zd_code_lengths_host: 2..286 symbols, a limit of 1..15 bits that holds them");
+        uint64_t sum = 0;
+        for (int32_t s = 0; s < n; ++s) sum += freq[s];
+        if (sum > 65535) return zfail(-1, "zd_code_lengths_host: the counts add up to more than 65535");
+        std::vector<uint32_t> t(freq, freq + n), build(zd::BUILD_SIZE);
+        zd::code_lengths(t.data(), 1, (uint32_t)n, limit, build.data());
+        for (int32_t s = 0; s < n; ++s) lens[s] = (uint8_t)t[s];
         return 0;
     } catch (const std::exception& e) {
-        return zfail(-4, std::string("zd_deflate_host: ") + e.what());
+        return zfail(-4, std::string("zd_code_lengths_host: ") + e.what());
     } catch (...) {
-        return zfail(-4, "zd_deflate_host: unknown exception");
+        return zfail(-4, "zd_code_lengths_host: unknown exception");
     }
 }
 
@@ -82,14 +117,15 @@ int zd_deflate(const uint8_t* in_dev, uint64_t chunk_bytes, int64_t n_chunks, ui
         if (!in_dev || !out_dev || !offsets || !sizes || !adlers || !store) return zfail(-1, "zd_deflate: null argument");
         if (!seg_ok(segment)) return zfail(-1, "zd_deflate: segment must be 1024..32768 bytes");
         if (chunk_bytes > zd::MAX_STREAM || n_chunks < 1 || n_chunks > 65535) return zfail(-1, "zd_deflate: 1..65535 chunks of at most 2^31 bytes");
-        if (flags & ~3) return zfail(-1, "zd_deflate: flags are ZD_REVERSED | ZD_RAW_ON_STORE");
+        if (flags & ~7) return zfail(-1, "zd_deflate: flags are ZD_REVERSED | ZD_RAW_ON_STORE | ZD_DYNAMIC");
         if (out_cap / (uint64_t)n_chunks < zd::bound(chunk_bytes, segment)) return zfail(-1, "zd_deflate: the output buffer is smaller than n_chunks * zd_bound");
         std::lock_guard<std::mutex> lk(mu);
         if (!ctx) ctx = zd::ctx_create();
         hipStream_t s = (hipStream_t)stream;
         zd::Streams r{};
         const char* msg = nullptr;
-        if (zd::run(ctx, in_dev, chunk_bytes, n_chunks, segment, flags & ZD_REVERSED, flags & ZD_RAW_ON_STORE, out_dev, s, nullptr, &r, &msg))
+        if (zd::run(ctx, in_dev, chunk_bytes, n_chunks, segment, flags & ZD_REVERSED, flags & ZD_RAW_ON_STORE, flags & ZD_DYNAMIC, out_dev, s, nullptr,
+                    &r, &msg))
             return zfail(-2, std::string("zd_deflate: ") + msg);
         hipError_t e = hipMemcpyAsync(offsets, r.offs, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(sizes, r.sizes, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s);

@@ -38,13 +38,16 @@ struct Streams {
     const uint64_t* sizes;
     const uint32_t* adlers;
     const uint8_t* store;
+    const uint8_t* seg_kind;    // dynamic mode: KIND_* of each of the n_segs segments, chunk-major; else null
+    uint64_t n_segs;
 };
 // n_chunks streams, one per chunk of chunk_bytes (<= MAX_STREAM) of `in` (device), placed one behind the other in `out` (device,
 // n_chunks * bound(chunk_bytes, seg) bytes at least; only the streams' own bytes are written).  reversed: the deflate kernel takes
-// the segments in the opposite launch order (same bytes).  raw_on_store: a "store" chunk's bytes in `out` are its chunk_bytes raw
+// the segments in the opposite launch order (same bytes).  dynamic: zd_deflate_dyn_kernel in place of zd_deflate_kernel (ZD_DYNAMIC).
+// raw_on_store: a "store" chunk's bytes in `out` are its chunk_bytes raw
 // bytes instead of its stream.  `mid` (may be null) is recorded behind the deflate kernel.  Enqueues on s and does not wait.
 // 0, or -2 with msg.
-int run(Ctx* c, const uint8_t* in, uint64_t chunk_bytes, int64_t n_chunks, uint32_t seg, bool reversed, bool raw_on_store, uint8_t* out,
-        hipStream_t s, hipEvent_t mid, Streams* res, const char** msg);
+int run(Ctx* c, const uint8_t* in, uint64_t chunk_bytes, int64_t n_chunks, uint32_t seg, bool reversed, bool raw_on_store, bool dynamic,
+        uint8_t* out, hipStream_t s, hipEvent_t mid, Streams* res, const char** msg);
 
 }  // namespace zd

@@ -58,6 +58,30 @@ __global__ __launch_bounds__(DEFLATE_BLOCK) void zd_deflate_kernel(const uint8_t
     seg_size[g] = deflate_segment(src, len, k + 1 == spc, tmp + g * tmp_stride, heads + threadIdx.x, DEFLATE_BLOCK);
 }
 
+// The same mapping in dynamic mode (ZD_DYNAMIC): a lane counts its segment's symbols, builds its three codes and parses again to
+// emit.  The hash heads and the counts, which become the code tables, lie in LDS interleaved by lane (118 528 bytes: one workgroup
+// per CU); the code construction's array is the lane's own (scratch), touched between the two parses only.
+__global__ __launch_bounds__(DEFLATE_BLOCK) void zd_deflate_dyn_kernel(const uint8_t* in, uint64_t chunk_bytes, uint32_t spc, uint64_t n_segs,
+                                                                       uint32_t seg, int reversed, uint8_t* tmp, uint32_t tmp_stride,
+                                                                       uint32_t* seg_size, uint32_t* seg_adler, uint8_t* seg_kind) {
+    __shared__ uint16_t heads[HASH_SIZE * DEFLATE_BLOCK];       // entry h of lane t: heads[h * DEFLATE_BLOCK + t]
+    __shared__ uint32_t work[WORK_SIZE * DEFLATE_BLOCK];        // entry e of lane t: work[e * DEFLATE_BLOCK + t]
+    uint32_t build[BUILD_SIZE];
+    uint64_t g = (uint64_t)blockIdx.x * DEFLATE_BLOCK + threadIdx.x;
+    if (g >= n_segs) return;
+    if (reversed) g = n_segs - 1 - g;
+    const uint64_t chunk = g / spc;
+    const uint32_t k = (uint32_t)(g % spc);
+    const uint64_t off = (uint64_t)k * seg;
+    const uint32_t len = (uint32_t)(chunk_bytes - off < seg ? chunk_bytes - off : seg);
+    const uint8_t* src = in + chunk * chunk_bytes + off;
+    int kind = KIND_FIXED;
+    seg_adler[g] = adler32(src, len);
+    seg_size[g] = deflate_segment_dynamic(src, len, k + 1 == spc, tmp + g * tmp_stride, heads + threadIdx.x, DEFLATE_BLOCK,
+                                          work + threadIdx.x, DEFLATE_BLOCK, build, &kind);
+    seg_kind[g] = (uint8_t)kind;
+}
+
 // One thread per chunk: its segments' offsets, the stream's size, Adler-32 and "store"; out_size is what the gather places.
 __global__ __launch_bounds__(COPY_BLOCK) void zd_finish_kernel(uint64_t chunk_bytes, uint32_t spc, uint32_t seg, int64_t n_chunks,
                                                                int raw_on_store, const uint32_t* seg_size, const uint32_t* seg_adler,
@@ -120,6 +144,7 @@ struct Ctx {
     uint32_t* adlers = nullptr; size_t c_adlers = 0;
     uint8_t* store = nullptr; size_t c_store = 0;
     uint8_t* scan = nullptr; size_t c_scan = 0;
+    uint8_t* seg_kind = nullptr; size_t c_seg_kind = 0;         // dynamic mode only
 };
 
 Ctx* ctx_create() { return new Ctx(); }
@@ -127,7 +152,7 @@ Ctx* ctx_create() { return new Ctx(); }
 void ctx_destroy(Ctx* c) {
     if (!c) return;
     for (void* p : {(void*)c->tmp, (void*)c->seg_size, (void*)c->seg_adler, (void*)c->seg_off, (void*)c->out_size, (void*)c->chunk_off,
-                    (void*)c->adlers, (void*)c->store, (void*)c->scan})
+                    (void*)c->adlers, (void*)c->store, (void*)c->scan, (void*)c->seg_kind})
         if (p) (void)hipFree(p);
     delete c;
 }
@@ -140,8 +165,8 @@ hipError_t launch_pack(const PackArgs& a, uint64_t image_bytes, uint8_t* image, 
     return hipGetLastError();
 }
 
-int run(Ctx* c, const uint8_t* in, uint64_t chunk_bytes, int64_t n_chunks, uint32_t seg, bool reversed, bool raw_on_store, uint8_t* out,
-        hipStream_t s, hipEvent_t mid, Streams* res, const char** msg) {
+int run(Ctx* c, const uint8_t* in, uint64_t chunk_bytes, int64_t n_chunks, uint32_t seg, bool reversed, bool raw_on_store, bool dynamic,
+        uint8_t* out, hipStream_t s, hipEvent_t mid, Streams* res, const char** msg) {
     static thread_local char text[256];
     auto bad = [&](const char* what, hipError_t e) {
         snprintf(text, sizeof text, "%s: %s", what, hipGetErrorString(e));
@@ -159,7 +184,8 @@ int run(Ctx* c, const uint8_t* in, uint64_t chunk_bytes, int64_t n_chunks, uint3
     if (!grow(c->tmp, c->c_tmp, (size_t)n_segs * tmp_stride) || !grow(c->seg_size, c->c_seg_size, (size_t)n_segs) ||
         !grow(c->seg_adler, c->c_seg_adler, (size_t)n_segs) || !grow(c->seg_off, c->c_seg_off, (size_t)n_segs) ||
         !grow(c->out_size, c->c_out_size, (size_t)n_chunks) || !grow(c->chunk_off, c->c_chunk_off, (size_t)n_chunks) ||
-        !grow(c->adlers, c->c_adlers, (size_t)n_chunks) || !grow(c->store, c->c_store, (size_t)n_chunks)) {
+        !grow(c->adlers, c->c_adlers, (size_t)n_chunks) || !grow(c->store, c->c_store, (size_t)n_chunks) ||
+        (dynamic && !grow(c->seg_kind, c->c_seg_kind, (size_t)n_segs))) {
         *msg = "zd::run: hipMalloc failed";
         return -2;
     }
@@ -170,9 +196,14 @@ int run(Ctx* c, const uint8_t* in, uint64_t chunk_bytes, int64_t n_chunks, uint3
         *msg = "zd::run: hipMalloc failed";
         return -2;
     }
-    hipLaunchKernelGGL(zd_deflate_kernel, dim3((unsigned)((n_segs + DEFLATE_BLOCK - 1) / DEFLATE_BLOCK)), dim3(DEFLATE_BLOCK), 0, s, in,
-                       chunk_bytes, spc, n_segs, seg, reversed ? 1 : 0, c->tmp, tmp_stride, c->seg_size, c->seg_adler);
-    if ((e = hipGetLastError()) != hipSuccess) return bad("zd_deflate_kernel", e);
+    const dim3 deflate_grid((unsigned)((n_segs + DEFLATE_BLOCK - 1) / DEFLATE_BLOCK));
+    if (dynamic)
+        hipLaunchKernelGGL(zd_deflate_dyn_kernel, deflate_grid, dim3(DEFLATE_BLOCK), 0, s, in, chunk_bytes, spc, n_segs, seg, reversed ? 1 : 0,
+                           c->tmp, tmp_stride, c->seg_size, c->seg_adler, c->seg_kind);
+    else
+        hipLaunchKernelGGL(zd_deflate_kernel, deflate_grid, dim3(DEFLATE_BLOCK), 0, s, in, chunk_bytes, spc, n_segs, seg, reversed ? 1 : 0,
+                           c->tmp, tmp_stride, c->seg_size, c->seg_adler);
+    if ((e = hipGetLastError()) != hipSuccess) return bad(dynamic ? "zd_deflate_dyn_kernel" : "zd_deflate_kernel", e);
     if (mid && (e = hipEventRecord(mid, s)) != hipSuccess) return bad("hipEventRecord", e);
     hipLaunchKernelGGL(zd_finish_kernel, dim3((unsigned)((n_chunks + COPY_BLOCK - 1) / COPY_BLOCK)), dim3(COPY_BLOCK), 0, s, chunk_bytes, spc, seg,
                        n_chunks, raw_on_store ? 1 : 0, c->seg_size, c->seg_adler, c->seg_off, c->out_size, c->adlers, c->store);
@@ -182,7 +213,7 @@ int run(Ctx* c, const uint8_t* in, uint64_t chunk_bytes, int64_t n_chunks, uint3
     hipLaunchKernelGGL(zd_gather_kernel, dim3(spc + 1, (unsigned)n_chunks), dim3(COPY_BLOCK), 0, s, in, chunk_bytes, spc, seg,
                        raw_on_store ? 1 : 0, c->tmp, tmp_stride, c->seg_size, c->seg_off, c->chunk_off, c->adlers, c->store, out);
     if ((e = hipGetLastError()) != hipSuccess) return bad("zd_gather_kernel", e);
-    *res = Streams{c->chunk_off, c->out_size, c->adlers, c->store};
+    *res = Streams{c->chunk_off, c->out_size, c->adlers, c->store, dynamic ? c->seg_kind : nullptr, n_segs};
     return 0;
 }
 

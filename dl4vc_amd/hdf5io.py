@@ -387,12 +387,15 @@ class ChunkWriter:
 
     A chunk is only ever written whole and at a multiple of ``chunk``.  ``write_chunks`` takes chunks compressed elsewhere and
     needs the dataset's length to be such a multiple; ``append_records`` takes records, compresses every full chunk with the
-    compressor's CPU twin (``zd_deflate_host``) and CARRIES the tail of fewer than ``chunk`` records to the next call;
+    compressor's CPU twin (``zd_deflate_host``, in the code mode ``codes``: ``"fixed"`` or ``"dynamic"``) and CARRIES the tail of fewer than ``chunk`` records to the next call;
     ``close`` writes a carried tail as the last chunk, padded with zero records (HDF5 stores an edge chunk at full size; the
     dataset's length says how many are real).  Appending to a file whose length is not a multiple of its chunk size is
     refused: its partial last chunk would have to be rewritten."""
 
-    def __init__(self, path: str, dtype: np.dtype, chunk: int = 8, gzip: int = 4, append: bool = False):
+    def __init__(self, path: str, dtype: np.dtype, chunk: int = 8, gzip: int = 4, append: bool = False, codes: str = "fixed"):
+        if codes not in ("fixed", "dynamic"):
+            raise ValueError("codes: 'fixed' or 'dynamic', not %r" % (codes,))
+        self.codes = codes
         lib = self._lib = _chunk_api(libhdf5())
         self.path, self.dtype, self.chunk = path, np.dtype(dtype), int(chunk)
         self.pending = np.zeros(0, self.dtype)
@@ -495,7 +498,7 @@ class ChunkWriter:
         from . import pileup_gpu
         raw = np.zeros(self.chunk, self.dtype)
         raw[:len(recs)] = recs
-        stream, _adler, store = pileup_gpu.zd_deflate_host(raw)
+        stream, _adler, store = pileup_gpu.zd_deflate_host(raw, codes=self.codes)
         buf = raw.view(np.uint8).reshape(-1) if store else np.frombuffer(stream, np.uint8)
         self._put(self.n, len(recs), [(buf, 0, buf.size, store)])
         self.host_chunks += 1

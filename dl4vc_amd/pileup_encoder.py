@@ -421,7 +421,7 @@ def encode_location(bam, fasta, loc: Location, opt: EncoderOptions, reader=None)
 def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Location], opt: EncoderOptions,
                      native: Optional[bool] = None, threads: int = 1, device: Optional[str] = None,
                      device_id: int = 0, inflate_device: Optional[str] = None, compress_device: Optional[str] = None,
-                     pending: int = 0, records_per_chunk: int = 8):
+                     pending: int = 0, records_per_chunk: int = 8, compress_codes: str = "fixed"):
     """Records for ``locations`` in input order and the number of locations that produced none.
 
     ``native`` (default: when libdl4vc_loader.so is built): the image planes come from the C++ encoder (``pe_encode``:
@@ -440,7 +440,8 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
     dataset's chunks on the device (``pg_compress_records_device``); only the compressed bytes come to the host, and no record
     array of the whole step is ever held.  ``pending``: the records a ``hdf5io.ChunkWriter`` already carries; each batch hands
     the few records in front of and behind its whole chunks over as ordinary records (``head`` / ``tail``), so every compressed
-    chunk starts at a multiple of ``records_per_chunk`` (tests/test_compress_gpu.py).
+    chunk starts at a multiple of ``records_per_chunk`` (tests/test_compress_gpu.py).  ``compress_codes``: ``"fixed"`` or
+    ``"dynamic"`` (with ``compress_device="gpu"`` only), the Huffman codes of those chunks (tests/test_compress_dynamic_gpu.py).
 
     Raises ``ValueError`` naming the read where a location's window holds a read the specification has no answer for (a
     zero-length alignment such as ``0M 5I``, a SEQ shorter than the CIGAR's query length such as SEQ ``*``): the native and
@@ -455,10 +456,15 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
         raise ValueError("inflate_device='gpu' is the GPU pileup encoder's option: it needs device='gpu'")
     if compress_device not in (None, "gpu"):
         raise ValueError("compress_device must be None or 'gpu', not %r" % (compress_device,))
+    if compress_codes not in ("fixed", "dynamic"):
+        raise ValueError("compress_codes must be 'fixed' or 'dynamic', not %r" % (compress_codes,))
+    if compress_codes != "fixed" and compress_device != "gpu":
+        raise ValueError("compress_codes=%r is the device compressor's option: it needs compress_device='gpu'" % (compress_codes,))
     if compress_device == "gpu":
         if device != "gpu":
             raise ValueError("compress_device='gpu' compresses the GPU pileup encoder's planes where they lie: it needs device='gpu'")
-        return _encode_compressed(bam_path, fasta_path, locations, opt, threads, device_id, inflate_device, pending, records_per_chunk)
+        return _encode_compressed(bam_path, fasta_path, locations, opt, threads, device_id, inflate_device, pending, records_per_chunk,
+                                  compress_codes)
     dtype = record_dtype(opt.max_reads, 2 * opt.window_size + 1)
     out = np.zeros(len(locations), dtype)
     n = errors = 0
@@ -528,7 +534,7 @@ class EncodedBatch:
     stats: dict
 
 
-def _encode_compressed(bam_path, fasta_path, locations, opt, threads, device_id, inflate_device, pending, chunk):
+def _encode_compressed(bam_path, fasta_path, locations, opt, threads, device_id, inflate_device, pending, chunk, codes):
     import torch
     from . import loader, pileup_gpu
     from .bamio import BamFile, FastaFile, WindowReader
@@ -542,7 +548,7 @@ def _encode_compressed(bam_path, fasta_path, locations, opt, threads, device_id,
     stored = [torch.empty((B, opt.max_reads, W), dtype=torch.uint8, device=dev) for _ in range(3)]
     args = (opt.window_size, opt.max_reads, opt.max_insert_length, opt.max_insert_length_variant, opt.min_base_quality)
     cpu = bam = fasta = reader = None
-    enc = pileup_gpu.GpuPileupEncoder(bam_path, fasta_path, *args, device=device_id, inflate_device=inflate_device)
+    enc = pileup_gpu.GpuPileupEncoder(bam_path, fasta_path, *args, device=device_id, inflate_device=inflate_device, compress_codes=codes)
     try:
         for l0 in range(0, len(locations), B):
             locs = locations[l0:l0 + B]

@@ -17,10 +17,12 @@ from .loader import PileupOptions
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_pileup.so")
 SYMBOLS = ("pg_open", "pg_encode", "pg_encode_device", "pg_assemble_device", "pg_close", "pg_last_error",
-           "pg_set_inflate_device", "pg_get_stats", "pg_debug_run_records", "pg_compress_records_device")
-ZD_SYMBOLS = ("zd_bound", "zd_deflate_host", "zd_deflate")      # the zlib compressor of the same library (csrc/zdeflate.h)
+           "pg_set_inflate_device", "pg_get_stats", "pg_debug_run_records", "pg_compress_records_device", "pg_set_compress_codes")
+# the zlib compressor of the same library (csrc/zdeflate.h)
+ZD_SYMBOLS = ("zd_bound", "zd_deflate_host", "zd_deflate", "zd_deflate_host_flags", "zd_code_lengths_host")
 ZD_MIN_SEGMENT, ZD_MAX_SEGMENT, ZD_DEFAULT_SEGMENT = 1024, 32768, 16384
-ZD_REVERSED, ZD_RAW_ON_STORE = 1, 2
+ZD_REVERSED, ZD_RAW_ON_STORE, ZD_DYNAMIC = 1, 2, 4
+COMPRESS_CODES = {"fixed": 0, "dynamic": 1}          # pg_set_compress_codes' modes
 MAX_TRACKS = 1024            # PG_MAX_TRACKS
 MAX_WINDOW = 100             # PG_MAX_WINDOW
 _lib = None
@@ -31,7 +33,8 @@ class Stats(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("host_frame_ms", "read_ms", "upload_ms", "inflate_ms", "frame_ms", "encode_ms", "copy_back_ms")] + \
                [(n, C.c_int64) for n in ("host_records", "blocks", "compressed_bytes", "inflated_bytes", "records", "groups")] + \
                [(n, C.c_double) for n in ("pack_ms", "deflate_ms", "gather_ms", "compress_copy_back_ms")] + \
-               [(n, C.c_int64) for n in ("chunks", "raw_bytes", "chunk_bytes_out", "stored_chunks")]
+               [(n, C.c_int64) for n in ("chunks", "raw_bytes", "chunk_bytes_out", "stored_chunks", "fixed_segments", "dynamic_segments",
+                                         "stored_segments")]
 
 
 class RecView(C.Structure):
@@ -90,6 +93,10 @@ def load_library() -> C.CDLL:
         lib.zd_bound.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
         lib.zd_deflate_host.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_int32)]
+        lib.zd_deflate_host_flags.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int32, vp, C.c_uint64, C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+        lib.zd_code_lengths_host.argtypes = [vp, C.c_int32, C.c_int32, vp]
+        lib.pg_set_compress_codes.argtypes = [vp, C.c_int]
         lib.zd_deflate.argtypes = [vp, C.c_uint64, C.c_int64, C.c_uint32, C.c_int32, vp, C.c_uint64, vp, vp, vp, vp, vp]
         _bind_debug(lib)
         lib.pg_close.argtypes = [vp]
@@ -113,9 +120,28 @@ def zd_bound(n: int, segment: int = ZD_DEFAULT_SEGMENT) -> int:
     return b.value
 
 
-def zd_deflate_host(data, segment: int = ZD_DEFAULT_SEGMENT):
-    """``zd_deflate_host`` -> (the zlib stream as bytes, Adler-32, store): the CPU twin of the device compressor.  ``store``: the
-    stream is not smaller than ``data`` (it is still a valid stream within ``zd_bound``)."""
+def _codes_mode(codes: str) -> int:
+    if codes not in COMPRESS_CODES:
+        raise ValueError("codes: 'fixed' or 'dynamic', not %r" % (codes,))
+    return COMPRESS_CODES[codes]
+
+
+def zd_code_lengths(freq, limit: int = 15):
+    """``zd_code_lengths_host``: the compressor's code construction, counts -> code lengths of at most ``limit`` bits."""
+    lib = load_library()
+    f = np.ascontiguousarray(freq, np.uint32)
+    lens = np.zeros(f.size, np.uint8)
+    _zd_check(lib, lib.zd_code_lengths_host(f.ctypes.data_as(C.c_void_p), f.size, int(limit), lens.ctypes.data_as(C.c_void_p)),
+              "zd_code_lengths_host")
+    return lens
+
+
+def zd_deflate_host(data, segment: int = ZD_DEFAULT_SEGMENT, codes: str = "fixed"):
+    """``zd_deflate_host`` (``codes="dynamic"``: ``zd_deflate_host_flags`` with ``ZD_DYNAMIC``) -> (the zlib stream as bytes,
+    Adler-32, store): the CPU twin of the device compressor.  ``store``: the stream is not smaller than ``data`` (it is still a
+    valid stream within ``zd_bound``)."""
+    if _codes_mode(codes):
+        return zd_deflate_host_flags(data, segment, ZD_DYNAMIC)
     lib = load_library()
     src = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
     out = np.empty(zd_bound(src.size, segment), np.uint8)
@@ -126,10 +152,23 @@ def zd_deflate_host(data, segment: int = ZD_DEFAULT_SEGMENT):
     return out[:size.value].tobytes(), adler.value, bool(store.value)
 
 
+def zd_deflate_host_flags(data, segment: int = ZD_DEFAULT_SEGMENT, flags: int = 0):
+    """``zd_deflate_host_flags`` -> as ``zd_deflate_host``; ``flags``: 0 or ``ZD_DYNAMIC``."""
+    lib = load_library()
+    src = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    out = np.empty(zd_bound(src.size, segment), np.uint8)
+    size, adler, store = C.c_uint64(0), C.c_uint32(0), C.c_int32(0)
+    _zd_check(lib, lib.zd_deflate_host_flags(src.ctypes.data_as(C.c_void_p) if src.size else None, src.size, int(segment), int(flags),
+                                             out.ctypes.data_as(C.c_void_p), out.size, C.byref(size), C.byref(adler), C.byref(store)),
+              "zd_deflate_host_flags")
+    return out[:size.value].tobytes(), adler.value, bool(store.value)
+
+
 def zd_deflate_device(in_ptr: int, chunk_bytes: int, n_chunks: int, out_ptr: int, out_cap: int, segment: int = ZD_DEFAULT_SEGMENT,
                       flags: int = 0, stream: int = 0):
     """``zd_deflate``: ``n_chunks`` streams of the device buffer at ``in_ptr`` into the device buffer at ``out_ptr`` ->
-    (offsets, sizes u64, adlers u32, store u8), host arrays, one entry per chunk."""
+    (offsets, sizes u64, adlers u32, store u8), host arrays, one entry per chunk.  ``flags``: ``ZD_REVERSED | ZD_RAW_ON_STORE |
+    ZD_DYNAMIC``."""
     lib = load_library()
     offs, sizes = np.zeros(n_chunks, np.uint64), np.zeros(n_chunks, np.uint64)
     adlers, store = np.zeros(n_chunks, np.uint32), np.zeros(n_chunks, np.uint8)
@@ -160,9 +199,11 @@ class GpuPileupEncoder:
 
     def __init__(self, bam_path: str, fasta_path: str, window_size: int, max_reads: int, max_insert_length: int,
                  max_insert_length_variant: int, min_base_quality: int = 0, bai_path: Optional[str] = None, device: int = 0,
-                 inflate_device: Optional[str] = None, max_inflated_bytes: int = 0):
+                 inflate_device: Optional[str] = None, max_inflated_bytes: int = 0, compress_codes: str = "fixed"):
         """``inflate_device="gpu"``: the BGZF blocks are inflated and the records framed on the device (``pg_set_inflate_device``;
-        needs the ``.bai``), same outputs.  ``max_inflated_bytes``: inflated bytes per group of runs, 0 = the default."""
+        needs the ``.bai``), same outputs.  ``max_inflated_bytes``: inflated bytes per group of runs, 0 = the default.
+        ``compress_codes``: ``"fixed"`` or ``"dynamic"``, the codes ``compress_records`` writes (``pg_set_compress_codes``)."""
+        mode = _codes_mode(compress_codes)
         if inflate_device not in (None, "gpu"):
             raise ValueError("inflate_device: None or 'gpu', not %r" % (inflate_device,))
         self.lib = load_library()
@@ -174,6 +215,8 @@ class GpuPileupEncoder:
         if rc != 0:
             self._h = None
             raise RuntimeError("pg_open failed: %s" % self.lib.pg_last_error(None).decode())
+        if mode:
+            self._check(self.lib.pg_set_compress_codes(self._h, mode), "pg_set_compress_codes")
         if inflate_device == "gpu":
             try:
                 self.set_inflate_device(True, max_inflated_bytes)

@@ -96,17 +96,19 @@ typedef struct {
     int64_t groups;
     /* the last pg_compress_records_device call (device time between events on the caller's stream; an encode call clears them) */
     double pack_ms;           /* blob and slot upload, hdf_pack_kernel */
-    double deflate_ms;        /* zd_deflate_kernel */
+    double deflate_ms;        /* zd_deflate_kernel or zd_deflate_dyn_kernel */
     double gather_ms;         /* stream sizes, their scan, zd_gather_kernel */
     double compress_copy_back_ms;   /* the chunks' bytes and their table to the host */
     int64_t chunks, raw_bytes, chunk_bytes_out, stored_chunks;
+    /* segments of those chunks by what they were written as; counted with pg_set_compress_codes(h, 1) only (0 otherwise) */
+    int64_t fixed_segments, dynamic_segments, stored_segments;
 } pg_stats;
 int pg_get_stats(const pg_encoder_t* h, pg_stats* out);
 
 /* ---- candidate HDF5 chunks compressed on the device ---------------------------------------------------------------------------
- * The zlib compressor (csrc/zdeflate.h): an RFC 1950 stream of fixed-Huffman DEFLATE blocks, the input cut into segments of
- * `segment` bytes (ZD_MIN_SEGMENT..ZD_MAX_SEGMENT) that are compressed on their own and joined byte-aligned, so the bytes depend
- * on the input and the segment size alone.  zlib's inflate (and so HDF5's deflate filter) reads it.  A stream that is not smaller
+ * The zlib compressor (csrc/zdeflate.h): an RFC 1950 stream of DEFLATE blocks (fixed codes, or with ZD_DYNAMIC the smaller of a
+ * fixed and a dynamic block per segment), the input cut into segments of `segment` bytes (ZD_MIN_SEGMENT..ZD_MAX_SEGMENT) that are
+ * compressed on their own and joined byte-aligned, so the bytes depend on the input, the segment size and the mode alone.  zlib's inflate (and so HDF5's deflate filter) reads it.  A stream that is not smaller
  * than its input is flagged "store": it is still a valid stream within zd_bound, and the writer of an HDF5 chunk passes the raw
  * bytes with filter mask 1 instead.  Errors: the text pg_last_error(NULL) returns. */
 #define ZD_MIN_SEGMENT 1024
@@ -114,10 +116,19 @@ int pg_get_stats(const pg_encoder_t* h, pg_stats* out);
 #define ZD_DEFAULT_SEGMENT 16384
 #define ZD_REVERSED 1        /* zd_deflate: the kernel takes the segments in the opposite launch order (same bytes) */
 #define ZD_RAW_ON_STORE 2    /* zd_deflate: a "store" chunk's output is its raw bytes (size = chunk_bytes), not its stream */
+#define ZD_DYNAMIC 4         /* dynamic codes: a segment is parsed twice, first to count its symbols; it is written as a dynamic
+                              * block where that is smaller than the fixed one, so no stream is larger than without the flag */
 int zd_bound(uint64_t n, uint32_t segment, uint64_t* bound);      /* n <= 2^31; no stream of n bytes is longer */
 /* CPU twin: the same text, the segments one after the other.  out_cap >= zd_bound. */
 int zd_deflate_host(const uint8_t* in, uint64_t n, uint32_t segment, uint8_t* out, uint64_t out_cap, uint64_t* size, uint32_t* adler,
                     int32_t* store);
+/* The same with flags: 0 (zd_deflate_host's bytes) or ZD_DYNAMIC. */
+int zd_deflate_host_flags(const uint8_t* in, uint64_t n, uint32_t segment, int32_t flags, uint8_t* out, uint64_t out_cap, uint64_t* size,
+                          uint32_t* adler, int32_t* store);
+/* The compressor's code construction on its own (a test entry): counts freq[n] (n 2..286, their sum <= 65535) -> code lengths
+ * lens[n] of at most `limit` bits (1..15, 2^limit >= n): optimal where the Huffman code's depth fits the limit, Kraft sum 1; two
+ * codes of length 1 where fewer than two symbols occur. */
+int zd_code_lengths_host(const uint32_t* freq, int32_t n, int32_t limit, uint8_t* lens);
 /* n_chunks (1..65535) streams, one per chunk of chunk_bytes of in_dev (DEVICE), written one behind the other into out_dev (DEVICE,
  * out_cap >= n_chunks * zd_bound; nothing but the streams' own bytes is written).  offsets / sizes / adlers / store [n_chunks]: HOST.
  * Runs on `stream` (a hipStream_t, NULL = the default stream) and returns when the streams are written. */
@@ -139,6 +150,10 @@ int pg_compress_records_device(pg_encoder_t* h, const uint8_t* reads_dev, const 
                                int64_t n_slots, const int32_t* slots, const uint8_t* blob, int64_t n_records,
                                int32_t records_per_chunk, const uint8_t** out, uint64_t* offsets, uint64_t* sizes, uint32_t* adlers,
                                uint8_t* store, void* stream);
+
+/* The codes pg_compress_records_device compresses with: 0 = fixed (the default), 1 = dynamic (ZD_DYNAMIC).  No chunk is larger
+ * with 1 than with 0. */
+int pg_set_compress_codes(pg_encoder_t* h, int mode);
 
 /* Test hook, no device call: the framed records of the run [s0, stop) of contig `tid`, by the host path (path 0) or by the
  * CPU twin of the device path (path 1: index ranges, the host form of the inflate, the shared frame core, serially; path 2:

@@ -11,7 +11,8 @@ VCF(s) -> ``candidates.hdf`` in the record layout main.py reads.  Same flags as 
 this path never used are refused, not ignored.  BAM / BAI / FASTA are read by dl4vc_amd/bamio.py (no htslib needed); records
 are written in input order; ``--num-processes`` worker processes each take contiguous runs of locations.
 ``--pileup-device gpu`` builds the records' planes on the GPU; ``--compress-device gpu`` (with it) also packs and compresses the
-file's chunks there and writes them past the HDF5 filter: the same records, in chunks another encoder compressed.
+file's chunks there and writes them past the HDF5 filter: the same records, in chunks another encoder compressed;
+``--compress-codes dynamic`` (with it) gives those chunks dynamic Huffman codes where they are smaller than the fixed ones.
 """
 import argparse
 import math
@@ -41,16 +42,18 @@ def _convert_compressed(args, locations, opt, start, step, procs, append):
     n_loc = len(locations)
     dtype = record_dtype(opt.max_reads, 2 * opt.window_size + 1)
     total_errors = written = 0
-    stages = {k: 0.0 for k in ("pack_ms", "deflate_ms", "gather_ms", "compress_copy_back_ms", "raw_bytes", "chunk_bytes_out", "stored_chunks")}
+    stages = {k: 0.0 for k in ("pack_ms", "deflate_ms", "gather_ms", "compress_copy_back_ms", "raw_bytes", "chunk_bytes_out", "stored_chunks",
+                                "fixed_segments", "dynamic_segments", "stored_segments")}
     t0 = time.time()
     try:
-        writer = hdf5io.ChunkWriter(args.output, dtype, chunk=8, append=append)
+        writer = hdf5io.ChunkWriter(args.output, dtype, chunk=8, append=append, codes=args.compress_codes)
     except ValueError as e:
         raise SystemExit("--compress-device gpu: %s" % e)
     with writer:
         while start < n_loc:
             for b in encode_locations(args.input, args.fasta_input, locations[start:start + step], opt, threads=procs, device="gpu",
-                                      inflate_device=args.inflate_device, compress_device="gpu", pending=len(writer.pending)):
+                                      inflate_device=args.inflate_device, compress_device="gpu", pending=len(writer.pending),
+                                      compress_codes=args.compress_codes):
                 writer.append_records(b.head)
                 if b.chunks is not None:
                     writer.write_chunks(b.chunks)
@@ -105,12 +108,18 @@ def main(argv=None):
                     help="gpu: with --pileup-device gpu, the records are packed and compressed into the file's chunks on the device "
                          "and written past the HDF5 filter; the same records in a file any HDF5 reader inflates (other bytes: "
                          "another encoder)")
+    ap.add_argument("--compress-codes", type=str, default="fixed", choices=["fixed", "dynamic"],
+                    help="with --compress-device gpu: dynamic gives a chunk's segments dynamic Huffman codes where that is smaller "
+                         "(a smaller file, the same records; the compressor parses every segment twice); default fixed")
     args = ap.parse_args(argv)
     if args.inflate_device and args.pileup_device != "gpu":
         raise SystemExit("--inflate-device gpu is an option of the GPU pileup encoder: give --pileup-device gpu as well")
     if args.compress_device and args.pileup_device != "gpu":
         raise SystemExit("--compress-device gpu compresses the GPU pileup encoder's planes where they lie, in device memory: "
                          "give --pileup-device gpu as well")
+    if args.compress_codes != "fixed" and args.compress_device != "gpu":
+        raise SystemExit("--compress-codes %s chooses the codes of the device compressor: give --compress-device gpu as well "
+                         "(without it the file's chunks are libhdf5's gzip)" % args.compress_codes)
     for flag, why in (("locations", "numpy location tables"), ("restrict_locations", "location restriction files"),
                       ("non_restrict_match_random", "location restriction files")):
         if getattr(args, flag):

@@ -8,11 +8,13 @@
 # Stages whose output already exists in OUTDIR are skipped.
 # -c: the converter builds the pileups on the GPU and packs and compresses train.hdf's chunks there (--pileup-device gpu
 # --compress-device gpu): the same records.
+# -y (with -c): the compressed chunks get dynamic Huffman codes where they are smaller (--compress-codes dynamic): a smaller file.
 set -e
-usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c]"; exit 1; }
+usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c [-y]]"; exit 1; }
 PROCS=16
 COMPRESS=""
-while getopts "i:r:t:o:b:p:ch" opt; do
+CODES=""
+while getopts "i:r:t:o:b:p:cyh" opt; do
   case $opt in
     i) BAM=$OPTARG ;;
     r) REFERENCE=$OPTARG ;;
@@ -21,10 +23,12 @@ while getopts "i:r:t:o:b:p:ch" opt; do
     b) BED=$OPTARG ;;       # candidate generation only
     p) PROCS=$OPTARG ;;
     c) COMPRESS=gpu ;;
+    y) CODES=dynamic ;;
     *) usage ;;
   esac
 done
 [ -z "$BAM" ] || [ -z "$REFERENCE" ] || [ -z "$TRUTH" ] || [ -z "$OUTDIR" ] && usage
+[ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
 SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 mkdir -p "$OUTDIR"
 if [ ! -f "$OUTDIR/candidates.vcf" ]; then
@@ -43,6 +47,7 @@ if [ ! -f "$OUTDIR/train.hdf" ]; then
       --tp_full_vcf "$OUTDIR/isec/0002.vcf" --fp_vcf "$OUTDIR/isec/0001.vcf" --fasta-input "$REFERENCE" \
       --output "$OUTDIR/train.hdf" --max-reads 200 --num-processes "$PROCS" --locations-process-step 100000 \
       --max-insert-length 10 --max-insert-length-variant 50 --save-q-scores --save-strand \
-      ${COMPRESS:+--pileup-device gpu --compress-device "$COMPRESS"} > "$OUTDIR/training_data.log" 2>&1
+      ${COMPRESS:+--pileup-device gpu --compress-device "$COMPRESS"} \
+      ${CODES:+--compress-codes "$CODES"} > "$OUTDIR/training_data.log" 2>&1
 fi
 echo "Training data in $OUTDIR/train.hdf"
