@@ -75,6 +75,8 @@ _EXTRA = [
     ("--test_fasta", "str", None, "reference FASTA of --test_bam"),
     ("--inflate-device", "str", None, "gpu: with --test_bam, the pileup encoder inflates the BAM's BGZF blocks and frames its records "
                                       "on the GPU as well (needs the .bai; same scored VCF)"),
+    ("--loader-device", "str", None, "gpu: with --test_file, the file's HDF5 chunks are inflated and its sites assembled on the GPU "
+                                     "(the host only reads the raw chunks and plans rows and allele masks); same scored VCF"),
     ("--conv-algo", "str", "auto", "fp32 conv form: auto (Winograd F(2,3) where every layer after the first has "
                                    "dilation 2), direct, or winograd"),
 ]

@@ -17,15 +17,18 @@
 # VCF is the same.
 # -y (with -c): the compressed chunks get dynamic Huffman codes where they are smaller (--compress-codes dynamic): a smaller
 # candidates.hdf with the same records.
+# -l (on the path through candidates.hdf; an error with -d): main.py inflates the file's chunks and assembles its sites on the GPU
+# (--loader-device gpu); the scored VCF is the same.
 set -e
-usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-c [-y]]"; exit 1; }
+usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-c [-y]] [-l]"; exit 1; }
 GPUS=1
 PROCS=16
 DIRECT=0
 INFLATE=""
 COMPRESS=""
 CODES=""
-while getopts "m:o:g:i:r:b:p:dzcyh" opt; do
+LOADER=""
+while getopts "m:o:g:i:r:b:p:ldzcyh" opt; do
   case $opt in
     m) MODEL=$OPTARG ;;
     o) OUTDIR=$OPTARG ;;
@@ -38,11 +41,13 @@ while getopts "m:o:g:i:r:b:p:dzcyh" opt; do
     z) INFLATE=gpu ;;       # BGZF inflate and record framing on the GPU: candidate generation, and with -d the pileup encoder
     c) COMPRESS=gpu ;;      # candidates.hdf: pileups, record packing and chunk compression on the GPU
     y) CODES=dynamic ;;     # with -c: dynamic Huffman codes in the compressed chunks
+    l) LOADER=gpu ;;        # candidates.hdf is inflated and its sites assembled on the GPU (main.py --loader-device gpu)
     *) usage ;;
   esac
 done
 [ -z "$MODEL" ] || [ -z "$OUTDIR" ] && usage
 [ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
+[ -n "$LOADER" ] && [ "$DIRECT" = 1 ] && { echo "-l loads candidates.hdf on the GPU and -d reads no candidates.hdf: give one of them"; exit 1; }
 SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 if [ ! -f "$OUTDIR/candidates.hdf" ] && [ ! -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ]; then
   mkdir -p "$OUTDIR"
@@ -56,7 +61,7 @@ if [ "$DIRECT" = 1 ]; then
   [ -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ] && [ -n "$REFERENCE" ] || { echo "-d needs -i BAM -r REFERENCE (and $OUTDIR/candidates.vcf, made from the BAM when absent)"; exit 1; }
   TEST_INPUT=(--test_bam "$BAM" --test_fasta "$REFERENCE" ${INFLATE:+--inflate-device "$INFLATE"})
 else
-  TEST_INPUT=(--test_file "$OUTDIR/candidates.hdf")
+  TEST_INPUT=(--test_file "$OUTDIR/candidates.hdf" ${LOADER:+--loader-device "$LOADER"})
 fi
 if [ "$DIRECT" != 1 ] && [ ! -f "$OUTDIR/candidates.hdf" ]; then
   [ -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ] && [ -n "$REFERENCE" ] || { echo "missing $OUTDIR/candidates.hdf (or candidates.vcf with -i BAM -r REFERENCE to make it)"; exit 1; }

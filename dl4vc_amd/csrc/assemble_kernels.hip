@@ -1,5 +1,7 @@
 // Site assembly of libdl4vc_pileup.so (pg_assemble_device): the stored planes [n][S][L] the encoder left in device memory ->
-// the planes [m][R][L] the forward reads, compacted over the locations that gave a record, R chosen rows per site.
+// the planes [m][R][L] the forward reads, compacted over the locations that gave a record, R chosen rows per site.  A slot's plane
+// starts slot_stride bytes after the one before: S * L for the encoder's planes, the record size where the planes lie inside the
+// inflated records of a candidate file (cl_assemble_device).
 //
 // One workgroup copies one plane of one site: a span of R * L output bytes.  Rows are L = 2 w + 1 bytes (201), so neither a row
 // nor a site slab starts on a 16-byte boundary.  The span is cut at the 16-byte boundaries of the DESTINATION: the bytes before
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(ASSEMBLE_BLOCK) void assemble_planes(AssembleArgs a
         return;
     }
     const SiteSrc s = a.sites[site];
-    const uint8_t* slab = a.src[plane] + (size_t)s.slot * a.S * a.L;
+    const uint8_t* slab = a.src[plane] + (size_t)s.slot * (size_t)a.slot_stride;
     if (s.first_rows) {
         for (int o = threadIdx.x; o < head; o += ASSEMBLE_BLOCK) dst[o] = slab[o];
         for (int j = threadIdx.x; j < n16; j += ASSEMBLE_BLOCK) body[j] = load16_any(slab + head + (j << 4));

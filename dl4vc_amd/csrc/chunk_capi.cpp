@@ -1,0 +1,214 @@
+// cl_* of libdl4vc_pileup.so (include/dl4vc_chunks.h): the raw chunks of a candidate file, read by the caller, are uploaded and
+// inflated on the device (zinflate_kernels.hip) into a buffer of records the handle owns; the members outside the three planes
+// come back to pinned host memory in two pitched copies per call, and the sites are assembled from the planes where they lie
+// inside the records (assemble_kernels.hip with the record size as the slot stride).  Every extern "C" body catches what it
+// throws; a damaged chunk is a status.
+#include "assemble_host.h"
+#include "zinflate_device.h"
+
+#include <vector>
+
+struct cl_loader : pgh::AssembleState {
+    int64_t record_bytes = 0, max_chunks = 0, plane = 0, blob_bytes = 0;
+    int32_t chunk_records = 0, window = 0, stored_rows = 0;
+    int64_t plane_off[3] = {0, 0, 0};
+    int64_t span0 = 0, span1_off = 0, span1 = 0;      // the non-plane members: [0, span0) and [span1_off, span1_off + span1)
+    int64_t n_records = 0;                            // of the last cl_inflate_chunks_device call
+    uint8_t* d_comp = nullptr; size_t c_comp = 0;
+    uint8_t* d_records = nullptr;
+    zi::StreamDesc* d_tab = nullptr;
+    int32_t* d_status = nullptr;
+    uint8_t* h_tab = nullptr;                         // pinned: the table, then the statuses
+    uint8_t* h_blob = nullptr;                        // pinned
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // upload | inflate | copy back | ; assemble
+    bool assemble_timed = false;
+    cl_stats st{};
+    ~cl_loader() {
+        wait_meta();
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (void* p : {(void*)d_comp, (void*)d_records, (void*)d_tab, (void*)d_status}) if (p) (void)hipFree(p);
+        if (h_tab) (void)hipHostFree(h_tab);
+        if (h_blob) (void)hipHostFree(h_blob);
+    }
+};
+
+namespace {
+
+std::string g_cl_err;
+
+int cfail(cl_loader* h, int code, const char* fmt, ...) {
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    (h ? h->err : g_cl_err) = buf;
+    return code;
+}
+
+#define CL_TRY(x)                                                                          \
+    do {                                                                                   \
+        const hipError_t e_ = (x);                                                         \
+        if (e_ != hipSuccess) return cfail(h, -2, "%s: %s", #x, hipGetErrorString(e_));    \
+    } while (0)
+
+int open_loader(cl_loader* h, int64_t max_records) {
+    const int64_t SL = h->plane, W = h->window, rb = h->record_bytes;
+    const int64_t* p = h->plane_off;
+    // the packed record of hdf5_schema.record_dtype: 16 + 15 W bytes, reads, W + 133 bytes, quality, strand
+    if (p[0] != 16 + 15 * W || p[1] != p[0] + SL + W + 133 || p[2] != p[1] + SL || rb != p[2] + SL)
+        return cfail(h, -1, "cl_open: planes at %lld / %lld / %lld of a %lld-byte record are not the candidate record's layout at %d rows "
+                            "of %d columns", (long long)p[0], (long long)p[1], (long long)p[2], (long long)rb, h->stored_rows, h->window);
+    h->span0 = p[0]; h->span1_off = p[0] + SL; h->span1 = W + 133;
+    h->blob_bytes = h->span0 + h->span1;
+    const uint64_t chunk_bytes = (uint64_t)rb * h->chunk_records;
+    if (chunk_bytes > zi::MAX_OUTPUT) return cfail(h, -1, "cl_open: a chunk of %llu bytes is more than one stream may hold", (unsigned long long)chunk_bytes);
+    h->max_chunks = (max_records + h->chunk_records - 1) / h->chunk_records + 1;
+    if (h->max_chunks * h->chunk_records > INT32_MAX / 2) return cfail(h, -1, "cl_open: too many records per call");
+    CL_TRY(hipSetDevice(h->device));
+    CL_TRY(hipMalloc((void**)&h->d_records, (size_t)h->max_chunks * chunk_bytes + 16));
+    CL_TRY(hipMalloc((void**)&h->d_tab, (size_t)h->max_chunks * sizeof(zi::StreamDesc)));
+    CL_TRY(hipMalloc((void**)&h->d_status, (size_t)h->max_chunks * sizeof(int32_t)));
+    CL_TRY(hipHostMalloc((void**)&h->h_tab, (size_t)h->max_chunks * (sizeof(zi::StreamDesc) + sizeof(int32_t)), hipHostMallocDefault));
+    CL_TRY(hipHostMalloc((void**)&h->h_blob, (size_t)h->max_chunks * h->chunk_records * h->blob_bytes + 16, hipHostMallocDefault));
+    for (hipEvent_t& e : h->ev) CL_TRY(hipEventCreate(&e));
+    return 0;
+}
+
+int inflate_chunks(cl_loader* h, const uint8_t* comp, uint64_t nbytes, const uint64_t* off, const uint64_t* len, const uint8_t* raw,
+                   int64_t n, void* stream, const uint8_t** blob, int32_t* status) {
+    if (n < 0 || n > h->max_chunks) return cfail(h, -1, "cl_inflate_chunks_device: %lld chunks, the handle was opened for %lld",
+                                                 (long long)n, (long long)h->max_chunks);
+    if (!blob || (n > 0 && (!comp || !off || !len || !status))) return cfail(h, -1, "cl_inflate_chunks_device: null argument");
+    *blob = h->h_blob;
+    h->st = cl_stats{};
+    h->assemble_timed = false;
+    h->n_records = 0;
+    if (n == 0) return 0;
+    const uint64_t chunk_bytes = (uint64_t)h->record_bytes * h->chunk_records;
+    zi::StreamDesc* tab = (zi::StreamDesc*)h->h_tab;
+    int32_t* h_status = (int32_t*)(h->h_tab + (size_t)h->max_chunks * sizeof(zi::StreamDesc));
+    for (int64_t c = 0; c < n; ++c) {
+        zi::StreamDesc d{};
+        d.raw = raw && raw[c] ? 1 : 0;
+        if (off[c] > nbytes || nbytes - off[c] < len[c] || len[c] > 0xffffffffull) d.status = ZI_BAD_RANGE;
+        else { d.in_off = off[c]; d.in_len = (uint32_t)len[c]; d.out_off = (uint64_t)c * chunk_bytes; d.out_len = (uint32_t)chunk_bytes; }
+        tab[c] = d;
+        h->st.compressed_bytes += (int64_t)len[c];
+        h->st.raw_chunks += d.raw;
+    }
+    CL_TRY(hipSetDevice(h->device));
+    if (!dev::grow(h->d_comp, h->c_comp, (size_t)nbytes + 16)) return cfail(h, -2, "hipMalloc of the chunk buffer failed");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_rec = n * h->chunk_records;
+    CL_TRY(hipEventRecord(h->ev[0], s));
+    CL_TRY(hipMemcpyAsync(h->d_comp, comp, nbytes, hipMemcpyHostToDevice, s));
+    CL_TRY(hipMemcpyAsync(h->d_tab, tab, (size_t)n * sizeof(zi::StreamDesc), hipMemcpyHostToDevice, s));
+    CL_TRY(hipEventRecord(h->ev[1], s));
+    CL_TRY(zi::launch_inflate(h->d_comp, h->d_tab, n, h->d_records, h->d_status, s));
+    CL_TRY(hipEventRecord(h->ev[2], s));
+    // two spans per record: device pitch = the record, host pitch = the blob
+    CL_TRY(hipMemcpy2DAsync(h->h_blob, (size_t)h->blob_bytes, h->d_records, (size_t)h->record_bytes, (size_t)h->span0, (size_t)n_rec,
+                            hipMemcpyDeviceToHost, s));
+    CL_TRY(hipMemcpy2DAsync(h->h_blob + h->span0, (size_t)h->blob_bytes, h->d_records + h->span1_off, (size_t)h->record_bytes,
+                            (size_t)h->span1, (size_t)n_rec, hipMemcpyDeviceToHost, s));
+    CL_TRY(hipMemcpyAsync(h_status, h->d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CL_TRY(hipEventRecord(h->ev[3], s));
+    CL_TRY(hipStreamSynchronize(s));
+    float ms[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) CL_TRY(hipEventElapsedTime(&ms[k], h->ev[k], h->ev[k + 1]));
+    h->st.upload_ms = ms[0]; h->st.inflate_ms = ms[1]; h->st.blob_copy_back_ms = ms[2];
+    h->st.chunks = n;
+    h->st.inflated_bytes = (int64_t)(n * chunk_bytes);
+    memcpy(status, h_status, (size_t)n * sizeof(int32_t));
+    h->n_records = n_rec;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* cl_last_error(const cl_loader_t* h) { return h ? h->err.c_str() : g_cl_err.c_str(); }
+
+int cl_open(int64_t record_bytes, int32_t chunk_records, int32_t window, int32_t stored_rows, const int64_t* plane_off, int64_t max_records,
+            int32_t device, cl_loader_t** out) {
+    if (!out || !plane_off) return cfail(nullptr, -1, "cl_open: null argument");
+    *out = nullptr;
+    if (record_bytes < 1 || chunk_records < 1 || window < 1 || stored_rows < 1 || stored_rows > INT16_MAX || max_records < 1 ||
+        (int64_t)window * stored_rows > (1 << 24))
+        return cfail(nullptr, -1, "cl_open: bad shape");
+    try {
+        cl_loader* h = new cl_loader();
+        h->record_bytes = record_bytes; h->chunk_records = chunk_records; h->window = window; h->stored_rows = stored_rows;
+        h->plane = (int64_t)window * stored_rows;
+        h->device = device;
+        for (int k = 0; k < 3; ++k) h->plane_off[k] = plane_off[k];
+        const int rc = open_loader(h, max_records);
+        if (rc) {
+            g_cl_err = h->err;
+            delete h;
+            return rc;
+        }
+        *out = h;
+        return 0;
+    } catch (const std::exception& e) {
+        return cfail(nullptr, -4, "cl_open: %s", e.what());
+    } catch (...) {
+        return cfail(nullptr, -4, "cl_open: unknown exception");
+    }
+}
+
+void cl_close(cl_loader_t* h) {
+    try {
+        if (h) (void)hipSetDevice(h->device);
+        delete h;
+    } catch (...) {
+    }
+}
+
+int cl_inflate_chunks_device(cl_loader_t* h, const uint8_t* comp, uint64_t nbytes, const uint64_t* off, const uint64_t* len,
+                             const uint8_t* raw, int64_t n_chunks, void* stream, const uint8_t** blob, int32_t* status) {
+    if (!h) return cfail(nullptr, -1, "cl_inflate_chunks_device: null handle");
+    try {
+        return inflate_chunks(h, comp, nbytes, off, len, raw, n_chunks, stream, blob, status);
+    } catch (const std::exception& e) {
+        return cfail(h, -4, "cl_inflate_chunks_device: %s", e.what());
+    } catch (...) {
+        return cfail(h, -4, "cl_inflate_chunks_device: unknown exception");
+    }
+}
+
+int cl_assemble_device(cl_loader_t* h, const int32_t* slots, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t reads,
+                       const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int32_t use_q, int32_t use_strand,
+                       uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out,
+                       uint8_t* var_mask_out, void* stream) {
+    if (!h) return cfail(nullptr, -1, "cl_assemble_device: null handle");
+    try {
+        const uint8_t* src[3] = {h->d_records + h->plane_off[0], h->d_records + h->plane_off[1], h->d_records + h->plane_off[2]};
+        hipStream_t s = (hipStream_t)stream;
+        const bool timed = m > 0 && hipEventRecord(h->ev[4], s) == hipSuccess;
+        const int rc = pgh::assemble(h, "cl_assemble_device", src, h->record_bytes, h->n_records, h->stored_rows, h->window, slots, rows,
+                                     first_rows, m, reads, ref, ref_mask, var_mask, use_q, use_strand, reads_out, qual_out, strand_out,
+                                     ref_out, ref_mask_out, var_mask_out, stream);
+        h->assemble_timed = rc == 0 && timed && hipEventRecord(h->ev[5], s) == hipSuccess;
+        return rc;
+    } catch (const std::exception& e) {
+        return cfail(h, -4, "cl_assemble_device: %s", e.what());
+    } catch (...) {
+        return cfail(h, -4, "cl_assemble_device: unknown exception");
+    }
+}
+
+int cl_get_stats(cl_loader_t* h, cl_stats* out) {
+    if (!h || !out) return cfail(nullptr, -1, "cl_get_stats: null argument");
+    if (h->assemble_timed) {
+        float ms = 0;
+        if (hipEventSynchronize(h->ev[5]) == hipSuccess && hipEventElapsedTime(&ms, h->ev[4], h->ev[5]) == hipSuccess) h->st.assemble_ms = ms;
+        h->assemble_timed = false;
+    }
+    *out = h->st;
+    return 0;
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@
 // pg_compress_records_device() takes the stored planes where pg_encode_device left them: the records are packed into the HDF5
 // compound layout, compressed into the dataset's chunks (zdeflate_kernels.hip, zdeflate.h) and only those bytes come back.
 #include "../../include/dl4vc_pileup_gpu.h"
+#include "assemble_host.h"
 #include "bam_native.h"
 #include "bgzf_device.h"
 #include "device_buffer.h"
@@ -79,10 +80,9 @@ using dev::grow;
 
 }  // namespace
 
-struct pg_encoder {
-    std::string bam_path, fasta_path, err;
+struct pg_encoder : pgh::AssembleState {   // (err, device and the staging of pg_assemble_device: assemble_host.h)
+    std::string bam_path, fasta_path;
     pe_options opt{};
-    int32_t device = 0;
     bamn::BamFile header;
     fastan::Fasta fasta;
     bamn::Bai bai;
@@ -100,11 +100,6 @@ struct pg_encoder {
     uint8_t* d_planes = nullptr; size_t c_planes = 0; // pg_encode: [3][B][max_reads][W]
     uint8_t* h_buf = nullptr; size_t hc_buf = 0;      // pinned
     uint8_t* h_planes = nullptr; size_t hc_planes = 0;
-    // pg_assemble_device: site sources and rows (device), their pinned staging (+ the three [m][L] host planes), and the event
-    // after which the staging of the previous call may be overwritten
-    uint8_t* d_meta = nullptr; size_t c_meta = 0;
-    uint8_t* h_meta = nullptr; size_t hc_meta = 0;
-    hipEvent_t ev_meta = nullptr; bool meta_busy = false;
     pg_stats st{};                                    // stages of the last encode call
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // the device inflate path (pg_set_inflate_device)
@@ -139,13 +134,12 @@ struct pg_encoder {
         pg::framing_destroy(framing);
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         for (void* p : {(void*)d_comp, (void*)d_tab, (void*)d_infl, (void*)d_bstatus}) if (p) (void)hipFree(p);
-        if (ev_meta) { if (meta_busy) (void)hipEventSynchronize(ev_meta); (void)hipEventDestroy(ev_meta); }
+        wait_meta();                                      // (the last assembly may still be reading its staging)
         for (void* p : {(void*)d_buf, (void*)d_recs, (void*)d_locs, (void*)d_ref, (void*)d_qpos, (void*)d_indel, (void*)d_isdel,
-                        (void*)d_small, (void*)d_planes, (void*)d_meta})
+                        (void*)d_small, (void*)d_planes})
             if (p) (void)hipFree(p);
         if (h_buf) (void)hipHostFree(h_buf);
         if (h_planes) (void)hipHostFree(h_planes);
-        if (h_meta) (void)hipHostFree(h_meta);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -162,15 +156,7 @@ int fail(pg_encoder* h, int code, const char* fmt, ...) {
     return code;
 }
 
-bool pinned_grow(uint8_t*& p, size_t& cap, size_t n) {
-    if (n <= cap) return true;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    const size_t want = n + n / 4 + 4096;
-    if (hipHostMalloc((void**)&p, want, hipHostMallocDefault) != hipSuccess) return false;
-    cap = want;
-    return true;
-}
+using pgh::pinned_grow;
 
 int get_tid(const bamn::BamFile& b, const std::string& name) {
     auto it = b.tid_of.find(name);
@@ -717,73 +703,6 @@ int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positio
     return 0;
 }
 
-int assemble(pg_encoder* h, const uint8_t* reads_src, const uint8_t* qual_src, const uint8_t* strand_src, int64_t n_slots,
-             int32_t S, int32_t L, const int32_t* slots, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t R,
-             const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int32_t use_q, int32_t use_strand,
-             uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out,
-             uint8_t* var_mask_out, void* stream) {
-    if (m < 0 || n_slots < 0 || S < 1 || L < 1 || R < 1) return fail(h, -1, "pg_assemble_device: bad shape");
-    if (R > S) return fail(h, -1, "pg_assemble_device: %d rows per site but only %d are stored", R, S);
-    if (S > INT16_MAX) return fail(h, -1, "pg_assemble_device: %d stored rows do not fit the int16 row index", S);
-    if (m > INT32_MAX / 4 || (int64_t)R * L > INT32_MAX / 2) return fail(h, -1, "pg_assemble_device: too large");
-    if (m == 0) return 0;
-    if (!reads_src || !qual_src || !strand_src || !slots || !ref || !ref_mask || !var_mask || !reads_out || !qual_out ||
-        !strand_out || !ref_out || !ref_mask_out || !var_mask_out)
-        return fail(h, -1, "pg_assemble_device: null argument");
-    // every index the kernel follows is checked here: a slot or a row outside the stored planes never reaches the device
-    bool any_rows = false;
-    for (int64_t i = 0; i < m; ++i) {
-        if (slots[i] < 0 || slots[i] >= n_slots) return fail(h, -1, "pg_assemble_device: site %lld names slot %d of %lld",
-                                                             (long long)i, slots[i], (long long)n_slots);
-        if (rows && !(first_rows && first_rows[i])) {
-            any_rows = true;
-            const int16_t* r = rows + (size_t)i * R;
-            for (int k = 0; k < R; ++k)
-                if (r[k] < 0 || r[k] >= S) return fail(h, -1, "pg_assemble_device: site %lld row %d names stored row %d of %d",
-                                                       (long long)i, k, (int)r[k], S);
-        }
-    }
-    struct DeviceGuard {
-        int prev = -1;
-        ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-    } guard;
-    if (hipGetDevice(&guard.prev) != hipSuccess) guard.prev = -1;
-    if (hipSetDevice(h->device) != hipSuccess) return fail(h, -2, "hipSetDevice(%d) failed", h->device);
-    if (!h->ev_meta && hipEventCreateWithFlags(&h->ev_meta, hipEventDisableTiming) != hipSuccess) return fail(h, -2, "hipEventCreate failed");
-    if (h->meta_busy) {                                  // the previous call's staging and device copies are still its own
-        if (hipEventSynchronize(h->ev_meta) != hipSuccess) return fail(h, -2, "hipEventSynchronize failed");
-        h->meta_busy = false;
-    }
-    const size_t b_sites = (size_t)m * sizeof(pg::SiteSrc), b_rows = any_rows ? (size_t)m * R * sizeof(int16_t) : 0;
-    const size_t b_dev = b_sites + b_rows, b_line = (size_t)m * L;
-    if (!grow(h->d_meta, h->c_meta, b_dev)) return fail(h, -2, "hipMalloc of the assembly table failed");
-    if (!pinned_grow(h->h_meta, h->hc_meta, b_dev + 3 * b_line)) return fail(h, -2, "hipHostMalloc of the assembly staging failed");
-    pg::SiteSrc* hs = (pg::SiteSrc*)h->h_meta;
-    for (int64_t i = 0; i < m; ++i) hs[i] = pg::SiteSrc{slots[i], (!rows || (first_rows && first_rows[i])) ? 1 : 0};
-    if (b_rows) memcpy(h->h_meta + b_sites, rows, b_rows);
-    uint8_t* lines = h->h_meta + b_dev;
-    memcpy(lines, ref, b_line); memcpy(lines + b_line, ref_mask, b_line); memcpy(lines + 2 * b_line, var_mask, b_line);
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t rc = hipMemcpyAsync(h->d_meta, h->h_meta, b_dev, hipMemcpyHostToDevice, s);
-    uint8_t* line_out[3] = {ref_out, ref_mask_out, var_mask_out};
-    for (int c = 0; c < 3 && rc == hipSuccess; ++c)
-        rc = hipMemcpyAsync(line_out[c], lines + c * b_line, b_line, hipMemcpyHostToDevice, s);
-    if (rc == hipSuccess) {
-        pg::AssembleArgs a{};
-        a.src[0] = reads_src; a.src[1] = qual_src; a.src[2] = strand_src;
-        a.dst[0] = reads_out; a.dst[1] = qual_out; a.dst[2] = strand_out;
-        a.sites = (const pg::SiteSrc*)h->d_meta;
-        a.rows = (const int16_t*)(h->d_meta + b_sites);
-        a.S = S; a.R = R; a.L = L;
-        a.use[0] = 1; a.use[1] = use_q != 0; a.use[2] = use_strand != 0;
-        rc = pg::launch_assemble(a, (int32_t)m, s);
-    }
-    h->meta_busy = true;                                 // (also after a failure: some of the copies may be enqueued)
-    if (hipEventRecord(h->ev_meta, s) != hipSuccess && rc == hipSuccess) rc = hipErrorUnknown;
-    if (rc != hipSuccess) return fail(h, -2, "device: %s", hipGetErrorString(rc));
-    return 0;
-}
-
 constexpr int64_t Z_CHUNKS = 512;           // chunks per pass of pg_compress_records_device (4 096 records at 8 per chunk)
 
 int compress_records(pg_encoder* h, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots, const int32_t* slots,
@@ -963,9 +882,10 @@ int pg_assemble_device(pg_encoder_t* h, const uint8_t* reads_src, const uint8_t*
                        uint8_t* ref_out, uint8_t* ref_mask_out, uint8_t* var_mask_out, void* stream) {
     if (!h) return fail(nullptr, -1, "pg_assemble_device: null handle");
     try {
-        return assemble(h, reads_src, qual_src, strand_src, n_slots, stored_rows, window, slots, rows, first_rows, m, reads, ref,
-                        ref_mask, var_mask, use_q, use_strand, reads_out, qual_out, strand_out, ref_out, ref_mask_out,
-                        var_mask_out, stream);
+        const uint8_t* src[3] = {reads_src, qual_src, strand_src};    // [n_slots][stored_rows][window]: a slot is one plane of a site
+        return pgh::assemble(h, "pg_assemble_device", src, (int64_t)stored_rows * window, n_slots, stored_rows, window, slots, rows,
+                             first_rows, m, reads, ref, ref_mask, var_mask, use_q, use_strand, reads_out, qual_out, strand_out, ref_out,
+                             ref_mask_out, var_mask_out, stream);
     } catch (const std::exception& e) {
         return fail(h, -4, "pg_assemble_device: %s", e.what());
     } catch (...) {

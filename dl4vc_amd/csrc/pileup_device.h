@@ -76,10 +76,11 @@ struct SiteSrc {
 };
 
 struct AssembleArgs {
-    const uint8_t* src[3];  // stored reads / qual / strand [n][S][L]
+    const uint8_t* src[3];  // stored reads / qual / strand: slot i's [S][L] plane at src[plane] + i * slot_stride
     uint8_t* dst[3];        // assembled reads / qual / strand [m][R][L]
     const SiteSrc* sites;   // [m], device
     const int16_t* rows;    // [m][R], device; read only where first_rows == 0
+    int64_t slot_stride;    // bytes; S * L for planes [n][S][L], the record size for planes inside records
     int32_t S, R, L;
     int32_t use[3];         // 0: the plane is zero-filled (a model without q-scores / strands)
 };

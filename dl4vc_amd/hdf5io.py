@@ -379,6 +379,96 @@ def dataset_layout(path: str):
     return int(dims[0]), chunk, filters
 
 
+class RawChunkFile:
+    """The ``data`` dataset's chunks as the file holds them, read past the filter pipeline with ``H5Dread_chunk``: a zlib stream
+    per chunk (the deflate filter's), or the chunk's bytes themselves where its filter mask skips the filter (a chunk
+    ``ChunkWriter`` stored raw).  An edge chunk is stored at full size.  What the device loader (``chunk_loader``) inflates.
+
+    Refused, with the reason: a dataset that is not chunked in one dimension, a filter pipeline that is anything but deflate
+    alone, a libhdf5 without ``H5Dread_chunk``."""
+
+    def __init__(self, path: str):
+        if not os.path.isfile(path):
+            raise FileNotFoundError(path)
+        lib = self._lib = _chunk_api(libhdf5())
+        if not hasattr(lib, "H5Dread_chunk"):
+            raise RuntimeError("this libhdf5 has no H5Dread_chunk: reading compressed chunks directly needs HDF5 1.10.3 or newer")
+        lib.H5Dread_chunk.restype = C.c_int
+        lib.H5Dread_chunk.argtypes = [hid_t, hid_t, C.POINTER(hsize_t), C.POINTER(C.c_uint32), C.c_void_p]
+        self.path = path
+        self._did = self._fid = -1
+        self._fid = lib.H5Fopen(path.encode(), H5F_ACC_RDONLY, 0)
+        if self._fid < 0:
+            raise OSError("cannot open %s as HDF5" % path)
+        self._did = lib.H5Dopen2(self._fid, DATASET_NAME.encode(), 0)
+        if self._did < 0:
+            self.close()
+            raise KeyError("%s has no dataset '%s'" % (path, DATASET_NAME))
+        try:
+            sid = lib.H5Dget_space(self._did)
+            dims = (hsize_t * 1)()
+            ndims = lib.H5Sget_simple_extent_ndims(sid)
+            if ndims == 1:
+                lib.H5Sget_simple_extent_dims(sid, dims, None)
+            lib.H5Sclose(sid)
+            if ndims != 1:
+                raise ValueError("dataset '%s' of %s must be one-dimensional" % (DATASET_NAME, path))
+            self.n = int(dims[0])
+            tid = lib.H5Dget_type(self._did)
+            self.itemsize = int(lib.H5Tget_size(tid))
+            self.offsets = {}
+            if lib.H5Tget_class(tid) == H5T_COMPOUND:
+                for i in range(lib.H5Tget_nmembers(tid)):
+                    p = lib.H5Tget_member_name(tid, i)
+                    self.offsets[C.string_at(p).decode()] = int(lib.H5Tget_member_offset(tid, i))
+                    lib.H5free_memory(p)
+            lib.H5Tclose(tid)
+            self.chunk, filters = _layout_of(lib, self._did)
+            if not self.chunk or self.chunk < 1:
+                raise ValueError("the dataset of %s is not chunked: there are no chunks to inflate on the device" % path)
+            if [f[0] for f in filters] != [FILTER_DEFLATE]:
+                raise ValueError("the dataset of %s has the filters %s, not deflate alone: only zlib streams are inflated on the device"
+                                 % (path, [f[0] for f in filters]))
+        except Exception:
+            self.close()
+            raise
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def chunk_bytes(self) -> int:
+        return self.chunk * self.itemsize
+
+    def stored_size(self, c: int) -> int:
+        """Bytes chunk ``c`` takes in the file."""
+        size = hsize_t(0)
+        if self._lib.H5Dget_chunk_storage_size(self._did, (hsize_t * 1)(c * self.chunk), C.byref(size)) < 0:
+            raise OSError("H5Dget_chunk_storage_size failed on %s at record %d" % (self.path, c * self.chunk))
+        return int(size.value)
+
+    def read_chunk(self, c: int, address: int) -> int:
+        """Chunk ``c``'s ``stored_size(c)`` bytes to memory at ``address`` -> its filter mask (bit 0: not deflated)."""
+        mask = C.c_uint32(0)
+        if self._lib.H5Dread_chunk(self._did, 0, (hsize_t * 1)(c * self.chunk), C.byref(mask), C.c_void_p(address)) < 0:
+            raise OSError("H5Dread_chunk failed on %s at record %d" % (self.path, c * self.chunk))
+        return int(mask.value)
+
+    def close(self):
+        if self._did >= 0:
+            self._lib.H5Dclose(self._did)
+            self._did = -1
+        if self._fid >= 0:
+            self._lib.H5Fclose(self._fid)
+            self._fid = -1
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class ChunkWriter:
     """Writes the ``data`` dataset chunk by chunk with ``H5Dwrite_chunk``: the chunks arrive compressed (zlib streams the
     deflate filter reads back, or raw bytes with the filter skipped) and go to the file as they are.  The dataset is created

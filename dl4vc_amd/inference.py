@@ -152,16 +152,21 @@ def index_runs(idx: np.ndarray):
 
 
 def run_shard(net, hdf_path: str, out_path: str, shard_index: int = 0, shard_count: int = 1, native: bool = True,
-              holdout_chromosomes=(), site_limit: int = 0, **kw) -> int:
-    """Score this rank's contiguous slice of the selected sites into ``out_path`` (records only, no header)."""
+              holdout_chromosomes=(), site_limit: int = 0, loader_device: Optional[str] = None, **kw) -> int:
+    """Score this rank's contiguous slice of the selected sites into ``out_path`` (records only, no header).
+    ``loader_device="gpu"``: every run goes through ``score_file_device`` (same lines)."""
     from . import loader
+    if loader_device not in (None, "gpu"):
+        raise ValueError("loader_device: None or 'gpu', not %r" % (loader_device,))
     idx = select_sites(hdf_path, holdout_chromosomes, site_limit)
     lo, hi = shard_range(len(idx), shard_index, shard_count)
     runs = index_runs(idx[lo:hi])
     done = 0
     with open(out_path, "w") as f:
         for a, b in runs:
-            if native and loader.available():
+            if loader_device == "gpu":
+                done += score_file_device(net, hdf_path, f.write, a, b, **kw)
+            elif native and loader.available():
                 done += score_file_native(net, hdf_path, f.write, a, b, **kw)
             else:
                 with CandidateFile(hdf_path) as src:
@@ -354,6 +359,137 @@ class _BamBatches:
         self.cpu.close()
 
 
+class _FileBatches(_BamBatches):
+    """Worker side of ``score_file_device``: ``_BamBatches``' hand-over (two plane sets, a free and a ready queue) with a
+    candidate file in front instead of an encoder.  Per batch of ``sites_per_launch`` records: the raw chunks covering it are read
+    into pinned memory, inflated on the device and assembled into a free plane set (``chunk_loader.DeviceChunkLoader.load``)."""
+
+    def __init__(self, cfg, hdf_path, lo, hi, sites_per_launch, reads_seed, device_id):
+        import queue
+        import threading
+        import torch
+        from .chunk_loader import DeviceChunkLoader
+        self.torch, self.cfg, self.lo, self.hi = torch, cfg, lo, hi
+        self.B, self.R = int(sites_per_launch), cfg.reads
+        self.dev = torch.device("cuda", device_id)
+        self.loader = DeviceChunkLoader(hdf_path, cfg.reads, self.B, seed=reads_seed, device=device_id, use_q=cfg.use_q,
+                                        use_strand=cfg.use_strand)
+        self.L = self.loader.window
+        if self.L != cfg.length:
+            self.loader.close()
+            raise ValueError("the file's windows have %d columns, the model reads %d" % (self.L, cfg.length))
+        self.hi = min(hi, len(self.loader))
+        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=self.dev)   # noqa: E731
+        self.sets = []
+        for _ in range(2):
+            planes = [u8(self.B, self.R, self.L) for _ in range(3)] + [u8(self.B, self.L) for _ in range(3)]
+            self.sets.append({"planes": planes, "vt": torch.empty((self.B, 3), dtype=torch.float32, device=self.dev),
+                              "bp": torch.empty((self.B,), dtype=torch.float32, device=self.dev),
+                              "h_vt": torch.empty((self.B, 3), dtype=torch.float32).pin_memory(),
+                              "h_bp": torch.empty((self.B,), dtype=torch.float32).pin_memory(),
+                              "done": torch.cuda.Event(), "vcfrec": [], "filled": 0})
+        self.stream = torch.cuda.Stream(self.dev)
+        self.free, self.ready = queue.Queue(), queue.Queue(maxsize=1)
+        for s in self.sets:
+            self.free.put(s)
+        self.stop = threading.Event()
+        self.thread = threading.Thread(target=self._run, name="score_file-loader", daemon=True)
+
+    def _run(self):
+        try:
+            with self.torch.cuda.device(self.dev):
+                for b0 in range(self.lo, self.hi, self.B):
+                    cur = self._get_free()
+                    plan = self.loader.load(b0, min(b0 + self.B, self.hi), [t.data_ptr() for t in cur["planes"]], self.stream.cuda_stream)
+                    cur["vcfrec"], cur["filled"] = plan.vcfrec, len(plan)
+                    self.stream.synchronize()
+                    self._put_ready(cur)
+            self._put_ready(None)
+        except _Stopped:
+            pass
+        except BaseException as e:      # noqa: BLE001 -- handed to the consumer, which raises it
+            try:
+                self._put_ready(e)
+            except _Stopped:
+                pass
+
+    def close(self):
+        self.stop.set()
+        if self.thread.is_alive():
+            self.thread.join()
+        self.loader.close()
+
+
+def score_file_device(net, hdf_path: str, write: Callable[[str], None], lo: int, hi: int, sites_per_launch: int = 4096,
+                      reads_seed: int = 0, use_var_type_threshold: bool = False, log=None, stats=None, device_id: int = 0,
+                      loader_stats=None) -> int:
+    """Same contract and same lines as ``score_file_native``, with the file's chunks inflated and its sites assembled on the
+    device (``chunk_loader.DeviceChunkLoader``): the host reads the raw chunks and plans rows and allele masks, nothing else.
+    While batch k's forward runs, a worker thread reads, inflates and assembles batch k+1 and batch k-1's text is formatted.
+    ``loader_stats`` (a dict) receives the loader's stage times summed over the run.  ``net`` must have been created after
+    ``import torch``."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("score_file_device: torch sees no HIP device.  It shares buffers and streams with torch, so torch has to be "
+                           "imported before libdl4vc_dan.so / libdl4vc_pileup.so are loaded (one HIP runtime per process)")
+    emit = _Pipeline(net, write, use_var_type_threshold, stats)._emit
+    src = _FileBatches(net.config, hdf_path, lo, hi, sites_per_launch, reads_seed, device_id)
+    done = _score_device_batches(net, src, emit, log, "%d records" % (src.hi - lo))
+    if loader_stats is not None:
+        for k, v in src.loader.stage.items():
+            loader_stats[k] = loader_stats.get(k, 0) + v
+    return done
+
+
+def _score_device_batches(net, src, emit, log, of_what: str) -> int:
+    """Consumer side of ``score_bam`` / ``score_file_device``: ``src`` (a ``_BamBatches`` or ``_FileBatches``) hands over sets of
+    assembled device planes; each is scored on a stream of its own (``dan_forward_device``) and its scores copied back while the
+    worker prepares the next set and the previous set's text is formatted.  Closes ``src``.  -> sites scored."""
+    import torch
+    fwd = torch.cuda.Stream(src.dev)
+    done = 0
+    t0 = time.perf_counter()
+
+    def finish(s):
+        s["done"].synchronize()
+        n = s["filled"]
+        emit(_Scored(s["vcfrec"]), {"vt_prob": s["h_vt"][:n].numpy().copy(), "bp": s["h_bp"][:n].numpy().copy()})
+        src.free.put(s)
+
+    prev = None
+    try:
+        src.thread.start()
+        while True:
+            item = src.ready.get()
+            if isinstance(item, BaseException):
+                raise item
+            if item is None:
+                break
+            n = item["filled"]
+            net.handle.forward_device([t.data_ptr() for t in item["planes"]], n, (0, 0, item["vt"].data_ptr(), item["bp"].data_ptr(), 0),
+                                      stream=fwd.cuda_stream)
+            with torch.cuda.stream(fwd):
+                item["h_vt"][:n].copy_(item["vt"][:n], non_blocking=True)
+                item["h_bp"][:n].copy_(item["bp"][:n], non_blocking=True)
+                item["done"].record(fwd)
+            if prev is not None:
+                finish(prev)
+            prev = item
+            done += n
+            if log:
+                dt = time.perf_counter() - t0
+                log("  submitted %d sites of %s (%.0f sites/s)" % (done, of_what, done / max(dt, 1e-9)))
+        if prev is not None:
+            finish(prev)
+            prev = None
+    finally:
+        if prev is not None:
+            prev["done"].synchronize()
+        fwd.synchronize()
+        src.close()
+    return done
+
+
 def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None], sites_per_launch: int = 4096,
               reads_seed: int = 0, use_var_type_threshold: bool = False, log=None, stats=None, site_limit: int = 0,
               encoder_options=None, device_id: int = 0, threads: int = 0, encoder_counts=None,
@@ -386,48 +522,7 @@ def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None]
     emit = _Pipeline(net, write, use_var_type_threshold, stats)._emit
     src = _BamBatches(net.config, bam, fasta, list(locations), opt, sites_per_launch, reads_seed, site_limit, device_id, threads,
                       counts, inflate_device)
-    fwd = torch.cuda.Stream(src.dev)
-    done = 0
-    total = len(src.locations)
-    t0 = time.perf_counter()
-
-    def finish(s):
-        s["done"].synchronize()
-        n = s["filled"]
-        emit(_Scored(s["vcfrec"]), {"vt_prob": s["h_vt"][:n].numpy().copy(), "bp": s["h_bp"][:n].numpy().copy()})
-        src.free.put(s)
-
-    prev = None
-    try:
-        src.thread.start()
-        while True:
-            item = src.ready.get()
-            if isinstance(item, BaseException):
-                raise item
-            if item is None:
-                break
-            n = item["filled"]
-            net.handle.forward_device([t.data_ptr() for t in item["planes"]], n, (0, 0, item["vt"].data_ptr(), item["bp"].data_ptr(), 0),
-                                      stream=fwd.cuda_stream)
-            with torch.cuda.stream(fwd):
-                item["h_vt"][:n].copy_(item["vt"][:n], non_blocking=True)
-                item["h_bp"][:n].copy_(item["bp"][:n], non_blocking=True)
-                item["done"].record(fwd)
-            if prev is not None:
-                finish(prev)
-            prev = item
-            done += n
-            if log:
-                dt = time.perf_counter() - t0
-                log("  submitted %d sites of %d locations (%.0f sites/s)" % (done, total, done / max(dt, 1e-9)))
-        if prev is not None:
-            finish(prev)
-            prev = None
-    finally:
-        if prev is not None:
-            prev["done"].synchronize()
-        fwd.synchronize()
-        src.close()
+    done = _score_device_batches(net, src, emit, log, "%d locations" % len(src.locations))
     if log:
         st = src.stage
         log("  pileup encoder (%s): %s" % ("BGZF inflate and framing on the device" if inflate_device == "gpu" else "host framing",

@@ -28,13 +28,15 @@ class SitePlan:
     var_mask: np.ndarray     # (m,L) u8
     vcfrec: List[str]        # record text as the candidate file would hold it (truncated to S128)
     num_reads: np.ndarray    # (m,) i32
+    blacklist: np.ndarray = None   # (m,) bool  the allele masks are the blacklist fallback (``NativeLoader``'s ``blacklist``)
 
     def __len__(self):
         return len(self.slots)
 
     def slice(self, lo: int, hi: int) -> "SitePlan":
         return SitePlan(self.slots[lo:hi], self.rows[lo:hi], self.first_rows[lo:hi], self.ref[lo:hi], self.ref_mask[lo:hi],
-                        self.var_mask[lo:hi], self.vcfrec[lo:hi], self.num_reads[lo:hi])
+                        self.var_mask[lo:hi], self.vcfrec[lo:hi], self.num_reads[lo:hi],
+                        None if self.blacklist is None else self.blacklist[lo:hi])
 
 
 def stored_vcfrec(vcf_string: str) -> str:
@@ -63,6 +65,7 @@ def plan_sites(status, num_reads, ref, vcf_strings: Sequence[str], reads: int, s
     rmask, vmask = np.zeros((m, L), np.uint8), np.zeros((m, L), np.uint8)
     nr = np.ascontiguousarray(np.asarray(num_reads)[slots], np.int32)
     recs = []
+    black = np.zeros(m, bool)
     draw = np.empty(max(R, S), np.int32)
     p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
     base = int(seed) & 0xFFFFFFFF
@@ -81,7 +84,8 @@ def plan_sites(status, num_reads, ref, vcf_strings: Sequence[str], reads: int, s
         st = lib.dl_allele_masks(text.encode(), p(out_ref[i:i + 1]), p(rmask[i:i + 1]), p(vmask[i:i + 1]))
         if st not in (0, 1):
             raise ValueError("record %d (%s): the allele masks cannot be built" % (first_record + i, text.split("\t", 2)[:2]))
-    return SitePlan(slots, rows, first, out_ref, rmask, vmask, recs, nr)
+        black[i] = st == 1
+    return SitePlan(slots, rows, first, out_ref, rmask, vmask, recs, nr, black)
 
 
 def assemble_host(reads, qual, strand, plan: SitePlan, use_q: bool = True, use_strand: bool = True):

@@ -272,6 +272,17 @@ def check_bam_arguments(args) -> None:
                          "would give; filter the candidate VCF instead")
 
 
+def check_loader_device_arguments(args) -> None:
+    """--loader-device: what it refuses (the file's own properties are checked when it is opened)."""
+    if args.loader_device != "gpu":
+        raise SystemExit("--loader-device must be gpu")
+    if args.test_bam:
+        raise SystemExit("--loader-device gpu is an option of --test_file (it inflates the candidate file's chunks on the GPU); "
+                         "--test_bam reads no candidate file (its device option is --inflate-device gpu)")
+    if args.train_file:
+        raise SystemExit("--loader-device gpu is an inference option: training and its evaluation keep the host loaders")
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     print(args)
@@ -280,6 +291,8 @@ def main(argv=None) -> int:
     if args.inflate_device and not args.test_bam:
         raise SystemExit("--inflate-device gpu is an option of --test_bam (the GPU pileup encoder reads the BAM); a --test_file holds "
                          "pileups already encoded")
+    if args.loader_device is not None:
+        check_loader_device_arguments(args)
     if args.test_bam:
         check_bam_arguments(args)
     if args.train_file:
@@ -359,12 +372,13 @@ def main(argv=None) -> int:
         print("\tTime elapsed for inference/testing {:.4f}".format(time.time() - t0))
         return 0
 
-    if args.test_bam:
+    if args.test_bam or args.loader_device:
         # this path shares device buffers and streams with torch: torch's HIP runtime has to be the process's only one, so it
         # is loaded before libdl4vc_dan.so brings in its own
         import torch
         if not torch.cuda.is_available():
-            raise SystemExit("--test_bam needs a HIP device visible to torch; there is no CPU path")
+            raise SystemExit("%s needs a HIP device visible to torch; there is no CPU path"
+                             % ("--test_bam" if args.test_bam else "--loader-device gpu"))
     from dl4vc_amd.model import DanNet, load_checkpoint
     from dl4vc_amd.inference import run_shard
 
@@ -378,6 +392,7 @@ def main(argv=None) -> int:
     t_loop = time.time()
     stats = None if os.environ.get("DL4VC_NO_THRESHOLD_STATS") else {}      # (the near-threshold count is a log line: opt out for raw rate)
     counts = {}
+    loader_stage = {}
     if args.test_bam:
         # the encoder options are what call_variants.sh passes to the converter (score_bam's default)
         from dl4vc_amd.inference import score_bam
@@ -388,21 +403,30 @@ def main(argv=None) -> int:
                           reads_seed=args.reads_seed, use_var_type_threshold=args.use_var_type_threshold, site_limit=site_limit,
                           log=lambda m: print(m, end="\r"), stats=stats, encoder_counts=counts, inflate_device=args.inflate_device)
     else:
-        n = run_shard(net, args.test_file, target, shard_i, shard_n, sites_per_launch=args.sites_per_launch,
-                      reads_seed=args.reads_seed, use_var_type_threshold=args.use_var_type_threshold,
-                      holdout_chromosomes=holdout, site_limit=site_limit, log=lambda m: print(m, end="\r"), stats=stats)
+        extra = {"loader_device": "gpu", "loader_stats": loader_stage} if args.loader_device else {}
+        try:
+            n = run_shard(net, args.test_file, target, shard_i, shard_n, sites_per_launch=args.sites_per_launch,
+                          reads_seed=args.reads_seed, use_var_type_threshold=args.use_var_type_threshold,
+                          holdout_chromosomes=holdout, site_limit=site_limit, log=lambda m: print(m, end="\r"), stats=stats, **extra)
+        except (ValueError, RuntimeError) as e:
+            if not args.loader_device:
+                raise
+            raise SystemExit("--loader-device gpu: %s" % e)   # (a refused file or a damaged chunk: the reason, not a traceback)
     t_loop = time.time() - t_loop
     net.close()
     if args.test_bam:
         print("\npileup encoder: %d locations: %d on the GPU, %d by pe_encode, %d by the Python builder, %d without a record"
               % tuple(counts[k] for k in ("locations", "gpu", "native", "python", "no_record")))
+    if loader_stage:
+        print("\ndevice loader: %s" % ", ".join("%s %s" % (k, ("%.1f" % v) if k.endswith("_ms") else int(v)) for k, v in loader_stage.items()))
     if stats is not None:
         print("\n%d of %d sites lie within 1e-4 of a genotype threshold of the published pipeline (format_vcf flags of "
               "call_variants.sh:154-160; main.py has no threshold flags of its own -- tools/format_vcf.py takes them later): only "
               "there could a call differ from another correct fp32 evaluation of the same scores"
               % (stats.get("near_threshold", 0), stats.get("sites", 0)))
     print("\nscoring loop (%s + assembly + forward + VCF text): %d sites in %.2f s = %.0f sites/s"
-          % ("BAM fetch + pileup encoder" if args.test_bam else "HDF5 read", n, t_loop, n / max(t_loop, 1e-9)))
+          % ("BAM fetch + pileup encoder" if args.test_bam else "HDF5 raw chunks + device inflate" if args.loader_device else "HDF5 read",
+             n, t_loop, n / max(t_loop, 1e-9)))
     if shard_n == 1:
         if args.sample_vcf:
             start_scored_vcf(args.sample_vcf, out_base)
