@@ -77,6 +77,11 @@ _EXTRA = [
                                       "on the GPU as well (needs the .bai; same scored VCF)"),
     ("--loader-device", "str", None, "gpu: with --test_file, the file's HDF5 chunks are inflated and its sites assembled on the GPU "
                                      "(the host only reads the raw chunks and plans rows and allele masks); same scored VCF"),
+    ("--record-census", "str", None, "gpu: with --test_bam, the locations are censused first (which of them give a record, by the GPU "
+                                     "encoder's status rule without its planes), so that --gpus N, --shard g/N, "
+                                     "--test_holdout_chromosomes and --max-test-batches select and seed the records as --test_file "
+                                     "does; same scored VCF"),
+    ("--census-timeout", "float", 600.0, "seconds a --record-census shard waits for the census of the other shards"),
     ("--conv-algo", "str", "auto", "fp32 conv form: auto (Winograd F(2,3) where every layer after the first has "
                                    "dilation 2), direct, or winograd"),
 ]

@@ -7,8 +7,10 @@
 # detection and per-locus counting on the GPU (libdl4vc_cand.so), with the reference's flags; -b restricts it to a BED file
 # (the reference requires -b; here it is optional and its absence means the whole BAM).  An existing candidates.vcf is used
 # as it is.  With an OUTDIR that also holds candidates.hdf, -i / -r are not needed and the conversion is skipped.
-# -d (direct; needs -i and -r, one GPU): no candidates.hdf at all -- main.py --test_bam encodes the pileups on the GPU, assembles
+# -d (direct; needs -i and -r): no candidates.hdf at all -- main.py --test_bam encodes the pileups on the GPU, assembles
 # and scores them there.  The scored VCF is byte-identical to the two-step path's.  Without -d nothing changes.
+# -d with -g N, N > 1: the candidate generator runs one process per GPU (--gpus N) and main.py counts the records first
+# (--record-census gpu), so that its N shards seed their read subsets as one process does; both outputs are the same bytes.
 # -z: the candidate generator inflates the BAM's BGZF blocks and frames its records on the GPU (--inflate-device gpu; needs
 # BAM.bai); candidates.vcf is the same.  With -d, main.py --test_bam gets --inflate-device gpu as well, so no stage inflates or
 # frames a record on the host; the scored VCF is the same.
@@ -48,18 +50,20 @@ done
 [ -z "$MODEL" ] || [ -z "$OUTDIR" ] && usage
 [ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
 [ -n "$LOADER" ] && [ "$DIRECT" = 1 ] && { echo "-l loads candidates.hdf on the GPU and -d reads no candidates.hdf: give one of them"; exit 1; }
+MULTI=""
+[ "$DIRECT" = 1 ] && [ "$GPUS" -gt 1 ] && MULTI=1
 SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 if [ ! -f "$OUTDIR/candidates.hdf" ] && [ ! -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ]; then
   mkdir -p "$OUTDIR"
   printf "Generate candidate VCF...\n"
   python "$SCRIPTDIR/tools/candidate_generator.py" --input "$BAM" --output "$OUTDIR/candidates.vcf" \
       --snp_min_freq 0.075 --indel_min_freq 0.02 ${BED:+--bedfile "$BED"} --keep_multialleles \
-      ${INFLATE:+--inflate-device "$INFLATE"} \
+      ${INFLATE:+--inflate-device "$INFLATE"} ${MULTI:+--gpus "$GPUS"} \
       > "$OUTDIR/candidate_generator.log" 2>&1
 fi
 if [ "$DIRECT" = 1 ]; then
   [ -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ] && [ -n "$REFERENCE" ] || { echo "-d needs -i BAM -r REFERENCE (and $OUTDIR/candidates.vcf, made from the BAM when absent)"; exit 1; }
-  TEST_INPUT=(--test_bam "$BAM" --test_fasta "$REFERENCE" ${INFLATE:+--inflate-device "$INFLATE"})
+  TEST_INPUT=(--test_bam "$BAM" --test_fasta "$REFERENCE" ${INFLATE:+--inflate-device "$INFLATE"} ${MULTI:+--record-census gpu})
 else
   TEST_INPUT=(--test_file "$OUTDIR/candidates.hdf" ${LOADER:+--loader-device "$LOADER"})
 fi

@@ -19,6 +19,7 @@ pysam / htslib here to compare them with.
 """
 from __future__ import annotations
 
+import json
 import logging
 import os
 from collections import OrderedDict, namedtuple
@@ -194,9 +195,12 @@ def candidate_tuples(subregions: Sequence[Region], counted: Sequence[tuple], kee
 def generate(bam_path: str, output: str, contigs: Optional[str] = None, bedfile: Optional[str] = None,
              keep_contig_chr: bool = False, chunk_size: int = 1000, threads: Optional[int] = None, snp_min_freq: float = 0.01,
              indel_min_freq: float = 0.01, keep_multialleles: bool = False, max_len_indel_allele: int = 60,
-             device: int = 0, inflate_device: Optional[str] = None) -> dict:
+             device: int = 0, inflate_device: Optional[str] = None, shard: Optional[Tuple[int, int]] = None) -> dict:
     """Writes ``output`` and returns the run's summary (counts of reads by kind, candidates, times).  ``inflate_device="gpu"``
-    inflates and frames the BAM's records on the device (needs the ``.bai``) and adds the ``inflate_*`` figures to the summary."""
+    inflates and frames the BAM's records on the device (needs the ``.bai``) and adds the ``inflate_*`` figures to the summary.
+    ``shard=(g, n)``: only the g-th of n contiguous ranges of the groups is counted, and instead of ``output`` the shard's
+    unsorted body lines go to ``part_path(output, g)`` with its summary and the header beside them (``merge_parts`` makes
+    ``output`` of the n parts)."""
     from .candgen import CandidateCounter, MAX_ALLELE_LEN
     if max_len_indel_allele > MAX_ALLELE_LEN:
         raise ValueError("--max_len_indel_allele %d exceeds the allele key's limit of %d bases" % (max_len_indel_allele,
@@ -212,10 +216,66 @@ def generate(bam_path: str, output: str, contigs: Optional[str] = None, bedfile:
         missing = sorted({c for c, _, _ in subregions if c not in tid_of})
         if missing:
             raise ValueError("contig(s) %s not in the BAM header" % ", ".join(missing))
-        counted, stats = cc.run([(tid_of[c], s, e) for c, s, e in subregions])
+        if shard is not None:
+            from .shard import shard_range
+            a, b = shard_range(len(groups), shard[0], shard[1])
+            groups = groups[a:b]
+            subregions = [sub for g in groups for sub in g]
+            logging.info("Shard %d/%d: %d subregions in %d groups", shard[0], shard[1], len(subregions), len(groups))
+        counted, stats = cc.run([(tid_of[c], s, e) for c, s, e in subregions])    # (a shard beyond the last group: no region, zero counts)
         cands = candidate_tuples(subregions, counted, keep_multialleles)
-        lines = sort_lines([record_line(*c) for c in cands])
-        with open(output, "w") as f:
-            f.write("\n".join(header_lines(cc.references, cc.lengths) + lines) + "\n")
+        header = header_lines(cc.references, cc.lengths)
+        if shard is None:
+            lines = sort_lines([record_line(*c) for c in cands])
+            with open(output, "w") as f:
+                f.write("\n".join(header + lines) + "\n")
+        else:
+            lines = [record_line(*c) for c in cands]
     stats.update(regions=len(regions), subregions=len(subregions), groups=len(groups), records=len(lines))
+    if shard is not None:
+        write_part(output, shard[0], lines, header, stats)
     return stats
+
+
+# ---- one process per GPU: parts of unsorted body lines, merged by the parent ------------------------------------------------
+def write_part(output: str, index: int, lines: Sequence[str], header: Sequence[str], stats: dict) -> None:
+    from .shard import part_path
+    with open(part_path(output, index), "w") as f:
+        f.write("".join(line + "\n" for line in lines))
+    with open(part_path(output, index) + ".stats.json", "w") as f:
+        json.dump({"header": list(header), "stats": stats}, f)
+
+
+def merge_parts(output: str, count: int, keep_parts: bool = False) -> dict:
+    """``output`` = the header, once, and ``sort_lines`` over the body lines of parts 0..count-1: byte for byte the file one
+    process writes, since the sort key is the whole line.  Returns the summed summaries (``regions`` is the job's, not a
+    sum; the times are summed over processes that ran side by side) and removes the parts and their side files."""
+    from .shard import part_path
+    lines: List[str] = []
+    total: dict = {}
+    header = None
+    for g in range(count):
+        with open(part_path(output, g)) as f:
+            lines += f.read().splitlines()
+        with open(part_path(output, g) + ".stats.json") as f:
+            side = json.load(f)
+        header = side["header"] if header is None else header
+        for k, v in side["stats"].items():
+            total[k] = v if k == "regions" else total.get(k, 0) + v
+    lines = sort_lines(lines)
+    with open(output, "w") as f:
+        f.write("\n".join(list(header or []) + lines) + "\n")
+    if not keep_parts:
+        remove_parts(output, count)
+    total["records"] = len(lines)
+    return total
+
+
+def remove_parts(output: str, count: int) -> None:
+    from .shard import part_path
+    for g in range(count):
+        for p in (part_path(output, g), part_path(output, g) + ".stats.json"):
+            try:
+                os.remove(p)
+            except OSError:
+                pass

@@ -101,6 +101,7 @@ struct pg_encoder : pgh::AssembleState {   // (err, device and the staging of pg
     uint8_t* h_buf = nullptr; size_t hc_buf = 0;      // pinned
     uint8_t* h_planes = nullptr; size_t hc_planes = 0;
     pg_stats st{};                                    // stages of the last encode call
+    bool census = false;                              // the call in progress is pg_census: statuses only, no plane is written
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // the device inflate path (pg_set_inflate_device)
     bool inflate_device = false;
@@ -360,14 +361,17 @@ int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& 
     ok(hipEventRecord(h->ev[1], s));
     ok(pg::launch_resolve(h->d_buf, h->d_recs, (int32_t)recs.size(), h->d_qpos, h->d_indel, h->d_isdel, s));
     const pg::Params P{w, W, o.max_reads, o.max_insert_length, o.max_insert_length_variant};
-    ok(pg::launch_encode(h->d_buf, h->d_recs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, reads, qual,
-                         strand, d_ref_small, d_num, d_status, s));
+    if (h->census)
+        ok(pg::launch_census(h->d_buf, h->d_recs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, d_status, s));
+    else
+        ok(pg::launch_encode(h->d_buf, h->d_recs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, reads, qual,
+                             strand, d_ref_small, d_num, d_status, s));
     ok(hipEventRecord(h->ev[2], s));
     // (the pageable copies above read the host vectors before this returns)
     ok(hipStreamSynchronize(s));
     float ms = 0.f;
     if (rc == hipSuccess && hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->st.upload_ms += ms;
-    if (rc == hipSuccess && hipEventElapsedTime(&ms, h->ev[1], h->ev[2]) == hipSuccess) h->st.encode_ms += ms;
+    if (rc == hipSuccess && hipEventElapsedTime(&ms, h->ev[1], h->ev[2]) == hipSuccess) (h->census ? h->st.census_ms : h->st.encode_ms) += ms;
     if (rc != hipSuccess) return fail(h, -2, "device: %s", hipGetErrorString(rc));
     return 0;
 }
@@ -381,6 +385,12 @@ int copy_back(pg_encoder* h, const std::vector<Entry>& es, int64_t i0, int64_t i
     const int64_t nb = i1 - i0;
     const size_t small_bytes = (((size_t)nb * W + 3) & ~(size_t)3) + (size_t)nb * 5;
     small.resize(small_bytes);
+    if (h->census) {                                       // (census_locations wrote the statuses alone)
+        const size_t at = small_bytes - (size_t)nb;
+        if (nb && hipMemcpy(small.data() + at, h->d_small + at, (size_t)nb, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, -2, "hipMemcpy failed");
+        for (int64_t i = 0; i < nb; ++i) status_out[es[i0 + i].idx] = (int8_t)small[at + i];
+        return 0;
+    }
     if (hipMemcpy(small.data(), h->d_small, small_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, -2, "hipMemcpy failed");
     const int32_t* num = (const int32_t*)(small.data() + (((size_t)nb * W + 3) & ~(size_t)3));
     const int8_t* st = (const int8_t*)(num + nb);
@@ -461,8 +471,11 @@ int encode_piece(pg_encoder* h, const std::vector<Entry>& es, int64_t i0, int64_
     if (g1 == g0) PG_TRY(hipEventRecord(h->ev[1], s));
     PG_TRY(hipEventRecord(h->ev[2], s));
     const pg::Params P{w, W, o.max_reads, o.max_insert_length, o.max_insert_length_variant};
-    PG_TRY(pg::launch_encode(h->d_infl, d_grecs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, reads, qual, strand,
-                             d_ref_small, d_num, d_status, s));
+    if (h->census)
+        PG_TRY(pg::launch_census(h->d_infl, d_grecs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, d_status, s));
+    else
+        PG_TRY(pg::launch_encode(h->d_infl, d_grecs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, reads, qual, strand,
+                                 d_ref_small, d_num, d_status, s));
     PG_TRY(hipEventRecord(h->ev[3], s));
     PG_TRY(hipStreamSynchronize(s));                       // (the pageable copies above have read the host vectors)
     float ms = 0.f;
@@ -471,7 +484,7 @@ int encode_piece(pg_encoder* h, const std::vector<Entry>& es, int64_t i0, int64_
     PG_TRY(hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
     h->st.frame_ms += ms;
     PG_TRY(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
-    h->st.encode_ms += ms;
+    (h->census ? h->st.census_ms : h->st.encode_ms) += ms;
     return 0;
 }
 
@@ -616,7 +629,7 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
         PG_TRY(hipEventRecord(h->ev[1], s));
         PG_TRY(hipStreamSynchronize(s));
         PG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-        h->st.encode_ms += ms;
+        (h->census ? h->st.census_ms : h->st.encode_ms) += ms;
         // the group's entries; the last group takes the entries decided on the host as well
         const int64_t e0 = g0 == 0 ? 0 : runs[g0].e0, e1 = g1 == runs.size() ? n : runs[g1].e0;
         if (const int rc = encode_pieces(h, es, e0, e1, runs, g0, g1, d_grecs, d_run_out, out, small)) return rc;
@@ -629,9 +642,13 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
 
 
 int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads, uint8_t* qual,
-               uint8_t* strand, uint8_t* ref_out, int32_t* num_out, int8_t* status_out, bool device_planes, void* stream) {
-    if (n < 0 || (n > 0 && (!contigs || !positions || !reads || !qual || !strand || !ref_out || !num_out || !status_out)))
+               uint8_t* strand, uint8_t* ref_out, int32_t* num_out, int8_t* status_out, bool device_planes, void* stream,
+               bool census = false) {
+    // (pg_census: device_planes with no plane -- nothing but status_out is written, on the device or here)
+    if (n < 0 || (n > 0 && (!contigs || !positions || !status_out)) ||
+        (n > 0 && !census && (!reads || !qual || !strand || !ref_out || !num_out)))
         return fail(h, -1, "null argument");
+    h->census = census;
     const pe_options& o = h->opt;
     const int W = 2 * o.window_size + 1, MR = o.max_reads;
     const size_t plane = (size_t)MR * W;
@@ -872,6 +889,17 @@ int pg_encode_device(pg_encoder_t* h, const char* const* contigs, const int32_t*
         return fail(h, -4, "pg_encode_device: %s", e.what());
     } catch (...) {
         return fail(h, -4, "pg_encode_device: unknown exception");
+    }
+}
+
+int pg_census(pg_encoder_t* h, const char* const* contigs, const int32_t* positions, int64_t n, int8_t* status_out, void* stream) {
+    if (!h) return fail(nullptr, -1, "pg_census: null handle");
+    try {
+        return encode_all(h, contigs, positions, n, nullptr, nullptr, nullptr, nullptr, nullptr, status_out, true, stream, true);
+    } catch (const std::exception& e) {
+        return fail(h, -4, "pg_census: %s", e.what());
+    } catch (...) {
+        return fail(h, -4, "pg_census: unknown exception");
     }
 }
 

@@ -37,6 +37,10 @@ hipError_t launch_encode(const uint8_t* buf, const Rec* recs, const Loc* locs, i
                          const int32_t* qpos, const int32_t* indel, const uint8_t* isdel, Params p, uint8_t* reads,
                          uint8_t* qual, uint8_t* strand, uint8_t* ref_small, int32_t* num_small, int8_t* status_small,
                          hipStream_t s);
+// The statuses launch_encode would leave in status_small, and nothing else (census_locations).
+hipError_t launch_census(const uint8_t* buf, const Rec* recs, const Loc* locs, int32_t n_locs, const uint8_t* reftok,
+                         const int32_t* qpos, const int32_t* indel, const uint8_t* isdel, Params p, int8_t* status_small,
+                         hipStream_t s);
 
 // ---- framing on the device (pileup_frame_kernels.hip; pg_set_inflate_device) ----
 // One run of locations, in the order of the call: sorted by (tid, s0), and stop rises with s0 inside a contig.

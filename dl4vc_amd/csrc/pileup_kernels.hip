@@ -2,6 +2,8 @@
 //
 // resolve_records: one thread per record -- Rec::resolve (query position, deletion / skip, merged indel length for every
 // reference position of the record), the name:sequence hash and the '=' flag.
+// location_status: the status rule of one location, shared by the two kernels below.
+// census_locations: one workgroup per location -- location_status and one status byte, no plane (pg_census).
 // encode_locations: one workgroup per location -- the track filter, the duplicate-key check (LDS hash table), coverage and
 // the longest capped insertion per position (LDS atomics), the column map (a serial scan over <= MAX_POS positions), then
 // per track the three "has a nonzero cell inside the crop" bits, the trim / centre arithmetic of finish_record and the
@@ -149,36 +151,36 @@ __device__ inline void block_zero(uint8_t* p, int64_t n) {
     for (int64_t i = threadIdx.x; i < n; i += BLOCK) p[i] = 0;
 }
 
-__global__ void __launch_bounds__(BLOCK) encode_locations(
-    const uint8_t* __restrict__ buf, const Rec* __restrict__ recs, const Loc* __restrict__ locs, const uint8_t* __restrict__ reftok,
-    const int32_t* __restrict__ qpos, const int32_t* __restrict__ indel, const uint8_t* __restrict__ isdel, Params P,
-    uint8_t* __restrict__ reads, uint8_t* __restrict__ qual, uint8_t* __restrict__ strand, uint8_t* __restrict__ ref_small,
-    int32_t* __restrict__ num_small, int8_t* __restrict__ status_small) {
-    __shared__ int32_t s_cover[MAX_POS + 1], s_longest[MAX_POS], s_col[MAX_POS], s_prev[MAX_POS];
-    __shared__ uint8_t s_covered[MAX_POS];
-    __shared__ int32_t s_tracks[MAX_TRACKS];
-    __shared__ unsigned long long s_hash[HASH_SLOTS];
-    __shared__ uint8_t s_bits[MAX_TRACKS], s_pad[MAX_TRACKS];
-    __shared__ int32_t s_wave[BLOCK / 64];
-    __shared__ int32_t s_n, s_decline, s_status, s_k, s_first, s_f[3], s_clo, s_chi, s_off;
+// LDS of one location's workgroup: what the status rule builds and, for a record, what the rendering reads.
+struct Work {
+    int32_t cover[MAX_POS + 1], longest[MAX_POS], col[MAX_POS], prev[MAX_POS];
+    uint8_t covered[MAX_POS];
+    int32_t tracks[MAX_TRACKS];
+    unsigned long long hash[HASH_SLOTS];
+    uint8_t bits[MAX_TRACKS], pad[MAX_TRACKS];
+    int32_t wave[BLOCK / 64];
+    int32_t n, decline, status, k, first, f[3], clo, chi, off;
+};
 
+__device__ inline Ctx make_ctx(const Work& w, const Loc& L, const Params& P, const uint8_t* buf, const int32_t* qpos,
+                               const int32_t* indel, const uint8_t* isdel) {
+    return Ctx{buf, qpos, indel, isdel, w.col, w.prev, w.longest, L.s0, L.stop, L.ci, P.max_insert_length,
+               max(P.max_insert_length_variant, P.max_insert_length)};
+}
+
+// The status of one location (0 no record, 1 record, 2 declined), the same value in every thread of the workgroup: the one
+// rule of encode_locations and census_locations.  For status 1, w holds the tracks, the column map, the crop (clo, chi, off),
+// the pad strands and the kept rows (k, first, f) the rendering needs.  It reads qpos / indel / isdel: the last step
+// (finish_record's trim, which gives 0 when the planes keep different row counts) needs every track's cells inside the crop.
+__device__ int location_status(Work& w, const Loc& L, const Params& P, const uint8_t* __restrict__ buf, const Rec* __restrict__ recs,
+                               const uint8_t* __restrict__ reftok, const int32_t* __restrict__ qpos,
+                               const int32_t* __restrict__ indel, const uint8_t* __restrict__ isdel) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = blockIdx.x;
-    const Loc L = locs[li];
-    const int64_t plane = (int64_t)P.max_reads * P.W;
-    uint8_t* out[3] = {reads + L.slot * plane, qual + L.slot * plane, strand + L.slot * plane};
-    // Every byte of the location's slot is stored once, by one thread (zeros unless status 1): no two threads of the
-    // workgroup store to one global address, so no ordering between their stores is needed.
-    auto empty = [&](int status) {
-        for (int c = 0; c < 3; ++c) block_zero(out[c], plane);
-        block_zero(ref_small + (int64_t)li * P.W, P.W);
-        if (tid == 0) { status_small[li] = (int8_t)status; num_small[li] = 0; }
-    };
-    if (L.pre >= 0) { empty(L.pre); return; }
+    if (L.pre >= 0) return L.pre;
     const int n_pos = L.stop - L.s0;
-    for (int p = tid; p <= n_pos; p += BLOCK) { s_cover[p] = 0; if (p < n_pos) s_longest[p] = 0; }
-    for (int i = tid; i < HASH_SLOTS; i += BLOCK) s_hash[i] = 0;
-    if (tid == 0) { s_n = 0; s_decline = 0; }
+    for (int p = tid; p <= n_pos; p += BLOCK) { w.cover[p] = 0; if (p < n_pos) w.longest[p] = 0; }
+    for (int i = tid; i < HASH_SLOTS; i += BLOCK) w.hash[i] = 0;
+    if (tid == 0) { w.n = 0; w.decline = 0; }
     __syncthreads();
 
     // ---- resolve_reads + the window filter of process_tracks: tracks in record order (= stable order by clipped start,
@@ -191,47 +193,47 @@ __global__ void __launch_bounds__(BLOCK) encode_locations(
             if (m.bits & R_FLAG_OK) {
                 if (m.end > m.pos && m.pos < L.stop && m.end > L.s0) {
                     sel = 1;
-                    if (m.bits & (R_SKIP | R_EQ | R_SHORT_SEQ)) s_decline = 1;
+                    if (m.bits & (R_SKIP | R_EQ | R_SHORT_SEQ)) w.decline = 1;
                 } else if ((m.bits & R_HAS_REF) && m.end == m.pos && m.pos >= L.s0 && m.pos < L.stop) {
-                    s_decline = 1;                                     // a zero-length alignment inside the window
+                    w.decline = 1;                                     // a zero-length alignment inside the window
                 }
             }
         }
         const unsigned long long mask = __ballot(sel);
         const int before = __popcll(mask & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[wave] = __popcll(mask);
+        if (lane == 0) w.wave[wave] = __popcll(mask);
         __syncthreads();
-        int off = s_n, total = 0;
-        for (int v = 0; v < BLOCK / 64; ++v) { if (v < wave) off += s_wave[v]; total += s_wave[v]; }
-        if (sel && off + before < MAX_TRACKS) s_tracks[off + before] = i;
+        int off = w.n, total = 0;
+        for (int v = 0; v < BLOCK / 64; ++v) { if (v < wave) off += w.wave[v]; total += w.wave[v]; }
+        if (sel && off + before < MAX_TRACKS) w.tracks[off + before] = i;
         __syncthreads();
-        if (tid == 0) s_n += total;
+        if (tid == 0) w.n += total;
         __syncthreads();
     }
-    const int n = s_n;
-    if (n > MAX_TRACKS || s_decline) { empty(2); return; }
+    const int n = w.n;
+    if (n > MAX_TRACKS || w.decline) return 2;
     // ---- two tracks sharing a name:sequence key
     for (int t = tid; t < n; t += BLOCK) {
-        const unsigned long long h = recs[s_tracks[t]].hash;
+        const unsigned long long h = recs[w.tracks[t]].hash;
         for (unsigned s = (unsigned)h & (HASH_SLOTS - 1);; s = (s + 1) & (HASH_SLOTS - 1)) {
-            const unsigned long long prev = atomicCAS(&s_hash[s], 0ull, h);
+            const unsigned long long prev = atomicCAS(&w.hash[s], 0ull, h);
             if (prev == 0ull) break;
-            if (prev == h) { s_decline = 1; break; }
+            if (prev == h) { w.decline = 1; break; }
         }
     }
     __syncthreads();
-    if (s_decline) { empty(2); return; }
+    if (w.decline) return 2;
     // ---- coverage and the longest capped insertion per position
     const int cap = P.max_insert_length, cap_ci = max(P.max_insert_length_variant, P.max_insert_length);
     for (int t = tid; t < n; t += BLOCK) {
-        const Rec& m = recs[s_tracks[t]];
+        const Rec& m = recs[w.tracks[t]];
         const int lo = max(m.pos, L.s0) - L.s0, hi = min(m.end, L.stop) - L.s0;
-        atomicAdd(&s_cover[lo], 1);
-        atomicAdd(&s_cover[hi], -1);
+        atomicAdd(&w.cover[lo], 1);
+        atomicAdd(&w.cover[hi], -1);
         const int32_t* Id = indel + m.res + (L.s0 - m.pos);
         for (int p = lo; p < hi; ++p) {
             const int ins = Id[p];
-            if (ins > 0) atomicMax(&s_longest[p], min(ins, p == L.ci ? cap_ci : cap));
+            if (ins > 0) atomicMax(&w.longest[p], min(ins, p == L.ci ? cap_ci : cap));
         }
     }
     __syncthreads();
@@ -239,30 +241,30 @@ __global__ void __launch_bounds__(BLOCK) encode_locations(
     if (tid == 0) {
         int run = 0, col = 1, prev = 0, covered = 0;
         for (int p = 0; p < n_pos; ++p) {
-            run += s_cover[p];
-            s_covered[p] = run > 0;
-            if (run > 0) { s_col[p] = col; s_prev[p] = prev; prev = col; col += 1 + s_longest[p]; ++covered; }
+            run += w.cover[p];
+            w.covered[p] = run > 0;
+            if (run > 0) { w.col[p] = col; w.prev[p] = prev; prev = col; col += 1 + w.longest[p]; ++covered; }
         }
         int status = -1;
-        if (covered == 0 || L.ci < 0 || L.ci >= n_pos || !s_covered[L.ci]) status = 0;
+        if (covered == 0 || L.ci < 0 || L.ci >= n_pos || !w.covered[L.ci]) status = 0;
         else
             for (int p = 0; p < n_pos; ++p)
-                if (s_covered[p] && reftok[L.ref + p] == REF_UNKNOWN) { status = 2; break; }
-        s_status = status;
+                if (w.covered[p] && reftok[L.ref + p] == REF_UNKNOWN) { status = 2; break; }
+        w.status = status;
         if (status < 0) {
-            const int center = s_col[L.ci], n_cols = col + 1;
-            s_clo = max(0, center - P.w);
-            s_chi = min(center + P.w + 1, n_cols);
-            s_off = P.w - (center - s_clo);
+            const int center = w.col[L.ci], n_cols = col + 1;
+            w.clo = max(0, center - P.w);
+            w.chi = min(center + P.w + 1, n_cols);
+            w.off = P.w - (center - w.clo);
         }
     }
     __syncthreads();
-    if (s_status >= 0) { empty(s_status); return; }
-    const Ctx x{buf, qpos, indel, isdel, s_col, s_prev, s_longest, L.s0, L.stop, L.ci, cap, cap_ci};
-    const int clo = s_clo, chi = s_chi, off = s_off;
+    if (w.status >= 0) return w.status;
+    const Ctx x = make_ctx(w, L, P, buf, qpos, indel, isdel);
+    const int clo = w.clo, chi = w.chi;
     // ---- per track: nonzero cells inside the crop (base, quality, strand planes) and the strand that fills its pads
     for (int t = tid; t < n; t += BLOCK) {
-        const Rec& m = recs[s_tracks[t]];
+        const Rec& m = recs[w.tracks[t]];
         const int lo = max(m.pos, L.s0) - L.s0, hi = min(m.end, L.stop) - L.s0;
         const uint8_t* Dl = isdel + m.res + (lo + L.s0 - m.pos);
         bool aligned = false;
@@ -275,8 +277,8 @@ __global__ void __launch_bounds__(BLOCK) encode_locations(
             bits |= 1;
             if (qs) bits |= 4 | (q ? 2 : 0);
         });
-        s_bits[t] = bits;
-        s_pad[t] = pad;
+        w.bits[t] = bits;
+        w.pad[t] = pad;
     }
     __syncthreads();
     // ---- finish_record: trim the leading rows with nothing inside the crop (each plane alone), keep the middle rows
@@ -284,26 +286,51 @@ __global__ void __launch_bounds__(BLOCK) encode_locations(
         int f[3] = {0, 0, 0};
         for (int c = 0; c < 3; ++c)
             for (int r = 0; r < n; ++r)
-                if (s_bits[r] & (1 << c)) { f[c] = r; break; }
+                if (w.bits[r] & (1 << c)) { f[c] = r; break; }
         const int nbr = n - f[0], nq = n - f[1], ns = n - f[2];
         const int first = max(0, (nbr - P.max_reads) / 2);
         const int last = min(first + P.max_reads, nbr);
         auto count = [&](int v) { return max(0, min(last, v) - min(first, v)); };
         const int kb = count(nbr), kq = count(nq), ks = count(ns);
-        s_status = (kq != kb || ks != kb || kb == 0) ? 0 : 1;
-        s_k = min(P.max_reads, kb);
-        s_first = first;
-        for (int c = 0; c < 3; ++c) s_f[c] = f[c];
+        w.status = (kq != kb || ks != kb || kb == 0) ? 0 : 1;
+        w.k = min(P.max_reads, kb);
+        w.first = first;
+        for (int c = 0; c < 3; ++c) w.f[c] = f[c];
     }
     __syncthreads();
-    if (s_status != 1) { empty(0); return; }
-    const int k = s_k;
+    return w.status == 1 ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(BLOCK) encode_locations(
+    const uint8_t* __restrict__ buf, const Rec* __restrict__ recs, const Loc* __restrict__ locs, const uint8_t* __restrict__ reftok,
+    const int32_t* __restrict__ qpos, const int32_t* __restrict__ indel, const uint8_t* __restrict__ isdel, Params P,
+    uint8_t* __restrict__ reads, uint8_t* __restrict__ qual, uint8_t* __restrict__ strand, uint8_t* __restrict__ ref_small,
+    int32_t* __restrict__ num_small, int8_t* __restrict__ status_small) {
+    __shared__ Work w;
+    const int tid = threadIdx.x;
+    const int li = blockIdx.x;
+    const Loc L = locs[li];
+    const int64_t plane = (int64_t)P.max_reads * P.W;
+    uint8_t* out[3] = {reads + L.slot * plane, qual + L.slot * plane, strand + L.slot * plane};
+    // Every byte of the location's slot is stored once, by one thread (zeros unless status 1): no two threads of the
+    // workgroup store to one global address, so no ordering between their stores is needed.
+    auto empty = [&](int status) {
+        for (int c = 0; c < 3; ++c) block_zero(out[c], plane);
+        block_zero(ref_small + (int64_t)li * P.W, P.W);
+        if (tid == 0) { status_small[li] = (int8_t)status; num_small[li] = 0; }
+    };
+    const int status = location_status(w, L, P, buf, recs, reftok, qpos, indel, isdel);
+    if (status != 1) { empty(status); return; }
+    const int n_pos = L.stop - L.s0;
+    const Ctx x = make_ctx(w, L, P, buf, qpos, indel, isdel);
+    const int clo = w.clo, chi = w.chi, off = w.off;
+    const int k = w.k;
     for (int job = tid; job < 3 * k; job += BLOCK) {            // one thread zeroes a kept row, then writes its cells
         const int c = job / k, r = job - c * k;
-        const int t = s_f[c] + s_first + r;
+        const int t = w.f[c] + w.first + r;
         uint8_t* row = out[c] + (int64_t)r * P.W;
         for (int i = 0; i < P.W; ++i) row[i] = 0;
-        track_cells(x, recs[s_tracks[t]], s_pad[t], [&](int col, uint8_t b, uint8_t q, uint8_t s, bool qs) {
+        track_cells(x, recs[w.tracks[t]], w.pad[t], [&](int col, uint8_t b, uint8_t q, uint8_t s, bool qs) {
             if (col < clo || col >= chi) return;
             if (c == 0) row[off + col - clo] = b;
             else if (qs) row[off + col - clo] = c == 1 ? q : s;
@@ -315,11 +342,22 @@ __global__ void __launch_bounds__(BLOCK) encode_locations(
     for (int i = tid; i < chi - clo; i += BLOCK) s_ref[i] = TOK_GAP;
     __syncthreads();
     for (int p = tid; p < n_pos; p += BLOCK)
-        if (s_covered[p] && s_col[p] >= clo && s_col[p] < chi) s_ref[s_col[p] - clo] = reftok[L.ref + p];
+        if (w.covered[p] && w.col[p] >= clo && w.col[p] < chi) s_ref[w.col[p] - clo] = reftok[L.ref + p];
     __syncthreads();
     uint8_t* ref_out = ref_small + (int64_t)li * P.W;
     for (int i = tid; i < P.W; i += BLOCK) ref_out[i] = (i >= off && i < off + chi - clo) ? s_ref[i - off] : 0;
     if (tid == 0) { status_small[li] = 1; num_small[li] = k; }
+}
+
+// The census: the status of every location and nothing else -- one byte per location, stored by thread 0.
+__global__ void __launch_bounds__(BLOCK) census_locations(
+    const uint8_t* __restrict__ buf, const Rec* __restrict__ recs, const Loc* __restrict__ locs, const uint8_t* __restrict__ reftok,
+    const int32_t* __restrict__ qpos, const int32_t* __restrict__ indel, const uint8_t* __restrict__ isdel, Params P,
+    int8_t* __restrict__ status_small) {
+    __shared__ Work w;
+    const Loc L = locs[blockIdx.x];
+    const int status = location_status(w, L, P, buf, recs, reftok, qpos, indel, isdel);
+    if (threadIdx.x == 0) status_small[blockIdx.x] = (int8_t)status;
 }
 
 }  // namespace
@@ -338,6 +376,14 @@ hipError_t launch_encode(const uint8_t* buf, const Rec* recs, const Loc* locs, i
     if (n_locs <= 0) return hipSuccess;
     hipLaunchKernelGGL(encode_locations, dim3(n_locs), dim3(BLOCK), 0, s, buf, recs, locs, reftok, qpos, indel, isdel, p, reads,
                        qual, strand, ref_small, num_small, status_small);
+    return hipGetLastError();
+}
+
+hipError_t launch_census(const uint8_t* buf, const Rec* recs, const Loc* locs, int32_t n_locs, const uint8_t* reftok,
+                         const int32_t* qpos, const int32_t* indel, const uint8_t* isdel, Params p, int8_t* status_small,
+                         hipStream_t s) {
+    if (n_locs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(census_locations, dim3(n_locs), dim3(BLOCK), 0, s, buf, recs, locs, reftok, qpos, indel, isdel, p, status_small);
     return hipGetLastError();
 }
 

@@ -190,6 +190,99 @@ class _Scored:
         self.vcfrec = vcfrec
 
 
+class _HostEncoders:
+    """What takes a location the GPU encoder declines (status 2): ``pe_encode``, then the Python builder for what that
+    declines.  One rule for ``_BamBatches._encode``, which needs the planes, and ``census_bam``, which needs only whether
+    there is a record.  The Python builder's files are opened on first use, by the thread that calls ``encode``."""
+
+    def __init__(self, bam, fasta, opt, threads):
+        from . import loader
+        self.bam, self.fasta, self.opt, self.threads = bam, fasta, opt, threads
+        self.cpu = loader.NativePileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
+                                              opt.max_insert_length_variant, opt.min_base_quality)
+        self._py = None
+
+    def encode(self, locs, declined, counts=None) -> dict:
+        """``declined``: indices into ``locs`` -> {index: (reads, qual, strand, ref, num_reads)} for those that give a record;
+        an index that is absent gives none.  ``counts["native"]`` / ``counts["python"]`` count the records of each encoder."""
+        from .pileup_encoder import encode_location, finish_record
+        from .hdf5_schema import record_dtype
+        host = {}
+        if len(declined) == 0:
+            return host
+        S, L = self.opt.max_reads, 2 * self.opt.window_size + 1
+        sub = self.cpu.encode([locs[i].contig for i in declined], [locs[i].pos for i in declined], self.threads)
+        for k, i in enumerate(declined):
+            st = int(sub[5][k])
+            if st == 1:
+                host[int(i)] = (sub[0][k], sub[1][k], sub[2][k], sub[3][k], int(sub[4][k]))
+                if counts is not None:
+                    counts["native"] += 1
+            elif st == 2:
+                if self._py is None:
+                    from .bamio import BamFile, FastaFile, WindowReader
+                    b = BamFile(self.bam)
+                    self._py = (b, FastaFile(self.fasta), WindowReader(b))
+                b, f, reader = self._py
+                res = encode_location(b, f, locs[i], self.opt, reader)
+                rec = finish_record(res, locs[i], self.opt, record_dtype(S, L)) if res is not None else None
+                if rec is not None:
+                    host[int(i)] = (rec["single_reads"], rec["q-scores"], rec["strand"], rec["ref_bases"], int(rec["num_reads"]))
+                    if counts is not None:
+                        counts["python"] += 1
+        return host
+
+    def close_python(self):
+        if self._py is not None:
+            self._py[0].close()
+            self._py[1].close()
+            self._py = None
+
+    def close(self):
+        self.close_python()
+        self.cpu.close()
+
+
+def census_bam(bam: str, fasta: str, locations, encoder_options=None, device_id: int = 0, threads: int = 0,
+               inflate_device: Optional[str] = None, batch: int = 16384, stage=None, log=None) -> np.ndarray:
+    """The record census: one uint8 per location, 1 where ``score_bam`` would get a record from it.  The GPU encoder's status
+    rule runs without writing a plane (``pg_census``); what it declines goes through the fallback of ``score_bam``
+    (``_HostEncoders``).  ``stage`` (a dict) receives ``pg_stats`` summed over the calls.  Needs torch's HIP device, as
+    ``score_bam`` does."""
+    import os
+    import torch
+    from . import pileup_gpu
+    from .pileup_encoder import EncoderOptions
+    if not torch.cuda.is_available():
+        raise RuntimeError("census_bam: torch sees no HIP device")
+    opt = encoder_options or EncoderOptions(window_size=100, max_reads=200, max_insert_length=10, max_insert_length_variant=50,
+                                            min_base_quality=0)
+    threads = threads or max(2, min(16, (os.cpu_count() or 4)))
+    locations = list(locations)
+    flags = np.zeros(len(locations), np.uint8)
+    enc = pileup_gpu.GpuPileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
+                                      opt.max_insert_length_variant, opt.min_base_quality, device=device_id, inflate_device=inflate_device)
+    host = _HostEncoders(bam, fasta, opt, threads)
+    try:
+        with torch.cuda.device(device_id):
+            for l0 in range(0, len(locations), batch):
+                locs = locations[l0:l0 + batch]
+                status = enc.census([l.contig for l in locs], [l.pos for l in locs])
+                if stage is not None:
+                    for k, v in enc.stats().items():
+                        stage[k] = stage.get(k, 0) + v
+                got = flags[l0:l0 + len(locs)]
+                got[status == 1] = 1
+                for i in host.encode(locs, np.flatnonzero(status == 2)):
+                    got[i] = 1
+                if log:
+                    log("  census of %d/%d locations" % (l0 + len(locs), len(locations)))
+    finally:
+        host.close()
+        enc.close()
+    return flags
+
+
 class _BamBatches:
     """Worker side of ``score_bam``: a thread that turns ``sites_per_launch`` locations at a time into assembled device
     planes.  Per round: ``pg_encode_device`` into the stored planes (the BAM fetch and framing run in its host threads, or on
@@ -203,13 +296,16 @@ class _BamBatches:
     S = 200, R = 100, L = 201 that is 494 MB + 2 * 249 MB = 0.99 GB (about 120 KB per site for the stored planes alone)."""
 
     def __init__(self, cfg, bam, fasta, locations, opt, sites_per_launch, reads_seed, site_limit, device_id, threads, counts,
-                 inflate_device=None):
+                 inflate_device=None, first_record=0, census=None):
         import queue
         import threading
         import torch
-        from . import pileup_gpu, loader
+        from . import pileup_gpu
         self.torch, self.cfg, self.bam, self.fasta, self.locations, self.opt = torch, cfg, bam, fasta, locations, opt
         self.B, self.seed, self.limit, self.threads, self.counts = int(sites_per_launch), reads_seed, site_limit, threads, counts
+        self.first_record, self.census = int(first_record), census
+        if census is not None and len(census) != len(locations):
+            raise ValueError("census: %d flags for %d locations" % (len(census), len(locations)))
         self.S, self.L, self.R = opt.max_reads, 2 * opt.window_size + 1, cfg.reads
         if self.L != cfg.length:
             raise ValueError("the encoder's window gives %d columns, the model reads %d" % (self.L, cfg.length))
@@ -220,8 +316,7 @@ class _BamBatches:
                                                opt.max_insert_length_variant, opt.min_base_quality, device=device_id,
                                                inflate_device=inflate_device)
         self.stage = {}                                  # pg_stats summed over the encoder's calls
-        self.cpu = loader.NativePileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
-                                              opt.max_insert_length_variant, opt.min_base_quality)
+        self.host = _HostEncoders(bam, fasta, opt, threads)
         u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=self.dev)   # noqa: E731
         self.stored = [u8(self.B, self.S, self.L) for _ in range(3)]
         self.sets = []
@@ -261,8 +356,6 @@ class _BamBatches:
     def _encode(self, locs):
         """One round: the stored planes of ``locs`` in device memory -> (ref, num_reads, status) with status in {0, 1}."""
         torch = self.torch
-        from .pileup_encoder import encode_location, finish_record
-        from .hdf5_schema import record_dtype
         contigs, positions = [l.contig for l in locs], [l.pos for l in locs]
         _r, _q, _s, ref, num, status = self.enc.encode_device(contigs, positions, stream=self.stream, out=self.stored)
         for k, v in self.enc.stats().items():
@@ -272,39 +365,18 @@ class _BamBatches:
         c["gpu"] += int((status == 1).sum())
         declined = np.flatnonzero(status == 2)
         if len(declined):
-            sub = self.cpu.encode([contigs[i] for i in declined], [positions[i] for i in declined], self.threads)
-            host = {}
-            for k, i in enumerate(declined):
-                st = int(sub[5][k])
-                if st == 1:
-                    host[int(i)] = (sub[0][k], sub[1][k], sub[2][k], sub[3][k], int(sub[4][k]))
-                    c["native"] += 1
-                elif st == 2:
-                    if self._py is None:
-                        from .bamio import BamFile, FastaFile, WindowReader
-                        b = BamFile(self.bam)
-                        self._py = (b, FastaFile(self.fasta), WindowReader(b))
-                    b, f, reader = self._py
-                    res = encode_location(b, f, locs[i], self.opt, reader)
-                    rec = finish_record(res, locs[i], self.opt, record_dtype(self.S, self.L)) if res is not None else None
-                    if rec is not None:
-                        host[int(i)] = (rec["single_reads"], rec["q-scores"], rec["strand"], rec["ref_bases"], int(rec["num_reads"]))
-                        c["python"] += 1
-                        st = 1
-                    else:
-                        st = 0
-                status[i] = st
+            host = self.host.encode(locs, declined, c)
+            status[declined] = 0
             with torch.cuda.stream(self.stream):
                 for i, (rd, ql, sd, rf, n) in host.items():
                     for plane, src in zip(self.stored, (rd, ql, sd)):
                         plane[i].copy_(torch.from_numpy(np.ascontiguousarray(src, np.uint8)))
-                    ref[i], num[i] = rf, n
+                    ref[i], num[i], status[i] = rf, n, 1
         c["no_record"] += int((status == 0).sum())
         return ref, num, status
 
     def _run(self):
         from .site_assembly import plan_sites
-        self._py = None
         cur = None
         records = 0
         try:
@@ -312,7 +384,10 @@ class _BamBatches:
                 for l0 in range(0, len(self.locations), self.B):
                     locs = self.locations[l0:l0 + self.B]
                     ref, num, status = self._encode(locs)
-                    plan = plan_sites(status, num, ref, [l.vcf_string for l in locs], self.R, self.S, self.seed, first_record=records)
+                    if self.census is not None:
+                        self._check_census(l0, locs, status)
+                    plan = plan_sites(status, num, ref, [l.vcf_string for l in locs], self.R, self.S, self.seed,
+                                      first_record=self.first_record + records)
                     if self.limit > 0:
                         plan = plan.slice(0, max(0, self.limit - records))
                     records += len(plan)
@@ -347,16 +422,24 @@ class _BamBatches:
             except _Stopped:
                 pass
         finally:
-            if self._py is not None:
-                self._py[0].close()
-                self._py[1].close()
+            self.host.close_python()
+
+    def _check_census(self, l0, locs, status):
+        """A location whose status differs from its census flag would shift every later record's seed: an error, never that."""
+        flags = np.asarray(self.census[l0:l0 + len(locs)])
+        bad = np.flatnonzero((status == 1) != (flags == 1))
+        if len(bad):
+            i = int(bad[0])
+            raise RuntimeError("record census mismatch at location %s (%d of this run): the census says status %d, the encoder %d; "
+                               "%d location(s) of this round differ.  The read-subset seeds of the records behind it would be wrong"
+                               % (locs[i].name, l0 + i, int(flags[i]), int(status[i]), len(bad)))
 
     def close(self):
         self.stop.set()
         if self.thread.is_alive():
             self.thread.join()
         self.enc.close()
-        self.cpu.close()
+        self.host.close()
 
 
 class _FileBatches(_BamBatches):
@@ -493,7 +576,7 @@ def _score_device_batches(net, src, emit, log, of_what: str) -> int:
 def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None], sites_per_launch: int = 4096,
               reads_seed: int = 0, use_var_type_threshold: bool = False, log=None, stats=None, site_limit: int = 0,
               encoder_options=None, device_id: int = 0, threads: int = 0, encoder_counts=None,
-              inflate_device: Optional[str] = None) -> int:
+              inflate_device: Optional[str] = None, first_record: int = 0, census=None, stage=None) -> int:
     """Score ``locations`` (``pileup_encoder.Location``s, e.g. ``locations_from_vcf(candidates.vcf, label=2)``) straight from
     the BAM: the same lines ``tools/convert_bam_single_reads.py`` + ``score_records`` write, without a candidate file.  The
     pileup planes are encoded (``pg_encode_device``) and assembled (``pg_assemble_device``) in device memory and scored there
@@ -506,7 +589,12 @@ def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None]
     (``ENCODER_COUNTS``).  ``inflate_device="gpu"``: the encoder inflates the BAM's BGZF blocks and frames its records on the
     device too (``pg_set_inflate_device``; needs the ``.bai``), same lines; with ``log``, the summary line then gives the
     encoder's stage times (``pg_stats`` summed over its calls).  Device memory: see ``_BamBatches`` -- about 1 GB at 4096 sites per launch.  ``net`` must have been
-    created after ``import torch`` (see the error below).  Returns the number of sites scored."""
+    created after ``import torch`` (see the error below).  Returns the number of sites scored.
+
+    ``first_record``: the record index of the first record these locations give (a shard of a longer list, planned by
+    ``shard.plan_bam_shard`` from the record census): site i then draws with ``reads_seed + first_record + i``.  ``census``: one
+    flag per location (``census_bam``); a location whose status differs from its flag raises ``RuntimeError``.  ``stage`` (a
+    dict) receives the encoder's stage times."""
     import os
     import torch
     if not torch.cuda.is_available():
@@ -521,8 +609,11 @@ def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None]
     threads = threads or max(2, min(16, (os.cpu_count() or 4)))
     emit = _Pipeline(net, write, use_var_type_threshold, stats)._emit
     src = _BamBatches(net.config, bam, fasta, list(locations), opt, sites_per_launch, reads_seed, site_limit, device_id, threads,
-                      counts, inflate_device)
+                      counts, inflate_device, first_record, census)
     done = _score_device_batches(net, src, emit, log, "%d locations" % len(src.locations))
+    if stage is not None:
+        for k, v in src.stage.items():
+            stage[k] = stage.get(k, 0) + v
     if log:
         st = src.stage
         log("  pileup encoder (%s): %s" % ("BGZF inflate and framing on the device" if inflate_device == "gpu" else "host framing",

@@ -17,7 +17,8 @@ from .loader import PileupOptions
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_pileup.so")
 SYMBOLS = ("pg_open", "pg_encode", "pg_encode_device", "pg_assemble_device", "pg_close", "pg_last_error",
-           "pg_set_inflate_device", "pg_get_stats", "pg_debug_run_records", "pg_compress_records_device", "pg_set_compress_codes")
+           "pg_set_inflate_device", "pg_get_stats", "pg_debug_run_records", "pg_compress_records_device", "pg_set_compress_codes",
+           "pg_census")
 # the zlib compressor of the same library (csrc/zdeflate.h)
 ZD_SYMBOLS = ("zd_bound", "zd_deflate_host", "zd_deflate", "zd_deflate_host_flags", "zd_code_lengths_host")
 ZD_MIN_SEGMENT, ZD_MAX_SEGMENT, ZD_DEFAULT_SEGMENT = 1024, 32768, 16384
@@ -30,7 +31,8 @@ _lib = None
 
 class Stats(C.Structure):
     """``pg_stats``: the stages of the last ``pg_encode`` / ``pg_encode_device`` call (times in ms)."""
-    _fields_ = [(n, C.c_double) for n in ("host_frame_ms", "read_ms", "upload_ms", "inflate_ms", "frame_ms", "encode_ms", "copy_back_ms")] + \
+    _fields_ = [(n, C.c_double) for n in ("host_frame_ms", "read_ms", "upload_ms", "inflate_ms", "frame_ms", "encode_ms", "copy_back_ms",
+                                          "census_ms")] + \
                [(n, C.c_int64) for n in ("host_records", "blocks", "compressed_bytes", "inflated_bytes", "records", "groups")] + \
                [(n, C.c_double) for n in ("pack_ms", "deflate_ms", "gather_ms", "compress_copy_back_ms")] + \
                [(n, C.c_int64) for n in ("chunks", "raw_bytes", "chunk_bytes_out", "stored_chunks", "fixed_segments", "dynamic_segments",
@@ -85,6 +87,7 @@ def load_library() -> C.CDLL:
         lib.pg_open.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PileupOptions), C.c_int32, C.POINTER(vp)]
         lib.pg_encode.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
         lib.pg_encode_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
+        lib.pg_census.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
         lib.pg_assemble_device.argtypes = ([vp] * 4 + [C.c_int64, C.c_int32, C.c_int32] + [vp] * 3 + [C.c_int64, C.c_int32] + [vp] * 3 +
                                            [C.c_int32, C.c_int32] + [vp] * 6 + [vp])
         lib.pg_set_inflate_device.argtypes = [vp, C.c_int, C.c_uint64]
@@ -276,6 +279,15 @@ class GpuPileupEncoder:
         self._check(self.lib.pg_encode_device(self._h, C.cast(names, C.c_void_p), p(pos), n, t(reads), t(qual), t(strand),
                                               p(ref), p(num), p(status), C.c_void_p(s.cuda_stream)), "pg_encode_device")
         return reads, qual, strand, ref, num, status
+
+    def census(self, contigs: Sequence[str], positions, stream=None):
+        """``pg_census`` -> status [n] i8 (host): exactly what ``encode_device`` returns as status, with no plane written."""
+        import torch
+        n, names, pos, _ref, _num, status = self._args(contigs, positions)
+        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
+        self._check(self.lib.pg_census(self._h, C.cast(names, C.c_void_p), pos.ctypes.data_as(C.c_void_p), n,
+                                       status.ctypes.data_as(C.c_void_p), C.c_void_p(s.cuda_stream)), "pg_census")
+        return status
 
     def assemble_device(self, src_ptrs, n_slots: int, plan, out_ptrs, use_q: bool = True, use_strand: bool = True,
                         stream: int = 0, stored_rows: Optional[int] = None, window: Optional[int] = None) -> None:

@@ -47,6 +47,12 @@ int pg_encode(pg_encoder_t* h, const char* const* contigs, const int32_t* positi
 int pg_encode_device(pg_encoder_t* h, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads_dev,
                      uint8_t* qual_dev, uint8_t* strand_dev, uint8_t* ref_out, int32_t* num_reads_out, int8_t* status_out,
                      void* stream);
+/* The record census: for n locations exactly the statuses pg_encode_device would return (0 no record, 1 record, 2 declined),
+ * by the same status rule (csrc/pileup_kernels.hip::location_status, which both kernels call) over the same fetched and framed
+ * records, with pg_set_inflate_device off or on.  No plane, reference line or read count is written anywhere: status_out
+ * [n] is the only output (HOST).  The rule's last step needs every record's resolved CIGAR, so the resolve kernel runs as in
+ * an encode call.  `stream` as above.  pg_get_stats then gives the call's stages, with census_ms in place of encode_ms. */
+int pg_census(pg_encoder_t* h, const char* const* contigs, const int32_t* positions, int64_t n, int8_t* status_out, void* stream);
 /* Site assembly on the device: the stored planes pg_encode_device wrote -> the six planes dan_forward_device reads
  * (include/dl4vc_dan.h), compacted over the m locations that gave a record.
  *   reads_src / qual_src / strand_src: DEVICE, [n_slots][stored_rows][window] (stored_rows = the encoder's max_reads);
@@ -78,7 +84,7 @@ int pg_assemble_device(pg_encoder_t* h, const uint8_t* reads_src, const uint8_t*
  * refused record is the host path's text with "(record at virtual offset N)".  on = 0 restores the host path. */
 int pg_set_inflate_device(pg_encoder_t* h, int on, uint64_t max_inflated_bytes /* 0: default */);
 
-/* Stages of the last pg_encode / pg_encode_device call, times in ms.  With the option off only host_frame_ms, upload_ms,
+/* Stages of the last pg_encode / pg_encode_device / pg_census call, times in ms.  With the option off only host_frame_ms, upload_ms,
  * encode_ms, copy_back_ms, host_records and records are filled.  upload_ms, inflate_ms, frame_ms and encode_ms are device time
  * between events on the encoder's stream, on both paths; host_frame_ms, read_ms and copy_back_ms are host wall clock (copy_back_ms
  * around blocking copies). */
@@ -90,6 +96,7 @@ typedef struct {
     double frame_ms;          /* walk, frame, scans, emit and location search */
     double encode_ms;         /* resolve_records and encode_locations */
     double copy_back_ms;      /* planes back to the host (pg_encode only) */
+    double census_ms;         /* pg_census only: resolve_records and census_locations (device events; encode_ms stays 0) */
     int64_t host_records;     /* records framed on the host; 0 on the device path */
     int64_t blocks, compressed_bytes, inflated_bytes;
     int64_t records;          /* records listed for the runs (a record shared by two runs counts twice) */

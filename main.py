@@ -23,47 +23,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from arguments import parse_args                              # noqa: E402
-
-
-def child_devices(n: int):
-    """HIP_VISIBLE_DEVICES value of each of the ``n`` shard processes: the g-th entry of the PARENT's device mask
-    (HIP_VISIBLE_DEVICES, else CUDA_VISIBLE_DEVICES, which HIP honours too), or plain g without a mask.  A
-    ROCR_VISIBLE_DEVICES mask needs no handling: HIP indices are already relative to it and the children inherit it."""
-    if os.environ.get("DL4VC_FORCE_DEVICE0"):                 # rehearse the multi-process path on a one-GPU box (tests)
-        return ["0"] * n
-    mask = os.environ.get("HIP_VISIBLE_DEVICES", os.environ.get("CUDA_VISIBLE_DEVICES"))
-    if mask is None:
-        return [str(g) for g in range(n)]
-    have = [d.strip() for d in mask.split(",") if d.strip()]
-    if len(have) < n:
-        raise SystemExit("--gpus %d but the device mask '%s' lists only %d device(s)" % (n, mask, len(have)))
-    return have[:n]
-
-
-def wait_children(procs, poll_s: float = 0.2):
-    """Return codes of the child processes; as soon as ONE exits non-zero the others are terminated (a rank that died leaves
-    its siblings blocked in a collective until the backend's timeout -- and a parent waiting on them in rank order blocked
-    with them)."""
-    rcs = [None] * len(procs)
-    failed = False
-    while any(rc is None for rc in rcs):
-        for i, p in enumerate(procs):
-            if rcs[i] is None:
-                rcs[i] = p.poll()
-        if not failed and any(rc not in (None, 0) for rc in rcs):
-            failed = True
-            for i, p in enumerate(procs):
-                if rcs[i] is None:
-                    p.terminate()
-            deadline = time.time() + 20.0
-            while time.time() < deadline and any(p.poll() is None for p in procs):
-                time.sleep(poll_s)
-            for p in procs:
-                if p.poll() is None:
-                    p.kill()
-        if any(rc is None for rc in rcs):
-            time.sleep(poll_s)
-    return rcs
+from dl4vc_amd.procs import child_devices, wait_children      # noqa: E402,F401
 
 
 def train_main(args, argv) -> int:
@@ -253,7 +213,8 @@ def train_main(args, argv) -> int:
 
 GPUS_WITH_BAM = ("--test_bam runs on one GPU: a shard's read subsets are seeded with the index of its first RECORD, which needs the "
                  "number of locations without a record in every shard before it; drop --gpus, or convert to candidates.hdf "
-                 "(tools/convert_bam_single_reads.py) and use --test_file --gpus N")
+                 "(tools/convert_bam_single_reads.py) and use --test_file --gpus N; or count the records first with --record-census gpu")
+CENSUS_SIBLINGS = "DL4VC_CENSUS_SIBLINGS"      # set by the --gpus parent: the shards census a slice each and exchange side files
 
 
 def check_bam_arguments(args) -> None:
@@ -264,12 +225,72 @@ def check_bam_arguments(args) -> None:
         raise SystemExit("--test_bam is an inference input; training evaluates on a --test_file")
     if not args.test_fasta or not args.sample_vcf:
         raise SystemExit("--test_bam needs --test_fasta (the reference) and --sample_vcf (the candidate VCF: its records are the sites)")
+    if args.record_census:
+        return                                                # (the census gives every record's index: shards and holdout are planned from it)
     if args.gpus > 1 or args.shard:
         raise SystemExit(GPUS_WITH_BAM)
     if args.test_holdout_chromosomes:
         raise SystemExit("--test_holdout_chromosomes is not supported with --test_bam: on a candidate file the held-out records keep "
                          "the record index (the read-subset seed) they have among ALL records, which only encoding every location "
-                         "would give; filter the candidate VCF instead")
+                         "would give; filter the candidate VCF instead, or count the records first with --record-census gpu")
+
+
+def census_text(st) -> str:
+    """The census figures of a shard's statistics, for its line; "" for a shard without a census."""
+    if "census_s" not in st:
+        return ""
+    return ("; census_s %.2f for %d locations (%d records; census_ms %.1f on the device), census_wait_s %.2f for the other shards"
+            % (st["census_s"], st.get("census_locations", 0), st.get("census_records", 0), st.get("census_ms", 0.0),
+               st.get("census_wait_s", 0.0)))
+
+
+def score_bam_census(args, net, target, out_final, shard_i, shard_n, holdout, site_limit, stats, counts, census_stats) -> int:
+    """--test_bam --record-census gpu: census, plan (``shard.plan_bam_shard``), score this shard's runs into ``target``.
+    Under a --gpus parent the shards census a contiguous slice of ALL locations each and exchange the flags through side files
+    next to their parts; a --shard without siblings, and a run without shards, censuses every location itself."""
+    import numpy as np
+    from dl4vc_amd.inference import census_bam, score_bam
+    from dl4vc_amd.pileup_encoder import locations_from_vcf
+    from dl4vc_amd.shard import census_path, plan_bam_shard, shard_range, wait_census, write_census
+    locations = locations_from_vcf(args.sample_vcf, label=2)
+    siblings = int(os.environ.get(CENSUS_SIBLINGS, "0") or 0)
+    if siblings and siblings != shard_n:
+        raise SystemExit("%s=%d but --shard %s" % (CENSUS_SIBLINGS, siblings, args.shard))
+    lo, hi = shard_range(len(locations), shard_i, shard_n) if siblings else (0, len(locations))
+    if shard_n > 1 and not siblings:
+        print("--shard %d/%d without sibling processes: this process censuses all %d locations itself" % (shard_i, shard_n, len(locations)))
+    stage = {}
+    t0 = time.time()
+    mine = census_bam(args.test_bam, args.test_fasta, locations[lo:hi], inflate_device=args.inflate_device, stage=stage,
+                      log=lambda m: print(m, end="\r"))
+    census_stats.update(census_s=time.time() - t0, census_ms=float(stage.get("census_ms", 0.0)), census_locations=hi - lo,
+                        census_records=int(mine.sum()), census_wait_s=0.0)
+    if siblings:
+        write_census(census_path(out_final, shard_i), mine)
+        t1 = time.time()
+        try:
+            flags = wait_census(out_final, shard_n, [b - a for a, b in (shard_range(len(locations), g, shard_n) for g in range(shard_n))],
+                                timeout_s=args.census_timeout)
+        except RuntimeError as e:
+            raise SystemExit("--record-census gpu: %s" % e)
+        census_stats["census_wait_s"] = time.time() - t1
+    else:
+        flags = mine
+    held = None
+    if holdout:
+        want = set(holdout)                                   # (select_sites: the text before the record's first tab)
+        held = np.fromiter((l.vcf_string.split("\t", 1)[0] in want for l in locations), bool, len(locations))
+    runs = plan_bam_shard(flags, held, site_limit, shard_i, shard_n)
+    n = 0
+    with open(target, "w") as f:
+        for a, b, first in runs:
+            n += score_bam(net, args.test_bam, args.test_fasta, locations[a:b], f.write, sites_per_launch=args.sites_per_launch,
+                           reads_seed=args.reads_seed, use_var_type_threshold=args.use_var_type_threshold,
+                           log=lambda m: print(m, end="\r"), stats=stats, encoder_counts=counts, inflate_device=args.inflate_device,
+                           first_record=first, census=flags[a:b])
+    for k in ("locations", "gpu", "native", "python", "no_record"):
+        counts.setdefault(k, 0)
+    return n
 
 
 def check_loader_device_arguments(args) -> None:
@@ -291,6 +312,11 @@ def main(argv=None) -> int:
     if args.inflate_device and not args.test_bam:
         raise SystemExit("--inflate-device gpu is an option of --test_bam (the GPU pileup encoder reads the BAM); a --test_file holds "
                          "pileups already encoded")
+    if args.record_census not in (None, "gpu"):
+        raise SystemExit("--record-census must be gpu")
+    if args.record_census and not args.test_bam:
+        raise SystemExit("--record-census gpu is an option of --test_bam (it counts the locations of the candidate VCF that give a "
+                         "record); the records of a --test_file are already counted")
     if args.loader_device is not None:
         check_loader_device_arguments(args)
     if args.test_bam:
@@ -334,12 +360,20 @@ def main(argv=None) -> int:
         t0 = time.time()
         procs = []
         devices = child_devices(args.gpus)
+        census = bool(args.test_bam and args.record_census)
+        if census:
+            from dl4vc_amd.shard import remove_census
+            remove_census(out_final, args.gpus)               # (a sibling never reads the census of an earlier run)
         for g in range(args.gpus):
             env = dict(os.environ, HIP_VISIBLE_DEVICES=devices[g], HSA_ENABLE_IPC_MODE_LEGACY="0")
             env.pop("CUDA_VISIBLE_DEVICES", None)             # (HIP honours both; the mask is carried in HIP_VISIBLE_DEVICES)
+            if census:
+                env[CENSUS_SIBLINGS] = str(args.gpus)
             cmd = [sys.executable, os.path.abspath(__file__)] + list(argv or sys.argv[1:]) + ["--shard", "%d/%d" % (g, args.gpus)]
             procs.append(subprocess.Popen(cmd, env=env))
         rcs = wait_children(procs)
+        if census:
+            remove_census(out_final, args.gpus)
         if any(rcs):
             for g in range(args.gpus):                        # no half-written parts left behind
                 try:
@@ -360,8 +394,8 @@ def main(argv=None) -> int:
                 os.remove(side)
                 total += st["sites"]
                 print("\tshard %d/%d on device %s: %d sites, scoring loop %.2f s = %.0f sites/s (process %.2f s incl. start-up and "
-                      "checkpoint load)" % (g, args.gpus, devices[g], st["sites"], st["loop_s"], st["sites"] / max(st["loop_s"], 1e-9),
-                                            st["process_s"]))
+                      "checkpoint load)%s" % (g, args.gpus, devices[g], st["sites"], st["loop_s"], st["sites"] / max(st["loop_s"], 1e-9),
+                                              st["process_s"], census_text(st)))
             except (OSError, ValueError, KeyError):
                 print("\tshard %d/%d: no statistics file" % (g, args.gpus))
         t1 = time.time()
@@ -393,7 +427,10 @@ def main(argv=None) -> int:
     stats = None if os.environ.get("DL4VC_NO_THRESHOLD_STATS") else {}      # (the near-threshold count is a log line: opt out for raw rate)
     counts = {}
     loader_stage = {}
-    if args.test_bam:
+    census_stats = {}
+    if args.test_bam and args.record_census:
+        n = score_bam_census(args, net, target, out_final, shard_i, shard_n, holdout, site_limit, stats, counts, census_stats)
+    elif args.test_bam:
         # the encoder options are what call_variants.sh passes to the converter (score_bam's default)
         from dl4vc_amd.inference import score_bam
         from dl4vc_amd.pileup_encoder import locations_from_vcf
@@ -412,8 +449,10 @@ def main(argv=None) -> int:
             if not args.loader_device:
                 raise
             raise SystemExit("--loader-device gpu: %s" % e)   # (a refused file or a damaged chunk: the reason, not a traceback)
-    t_loop = time.time() - t_loop
+    t_loop = time.time() - t_loop - census_stats.get("census_s", 0.0) - census_stats.get("census_wait_s", 0.0)
     net.close()
+    if census_stats:
+        print("\nrecord census: %s" % census_text(census_stats).lstrip("; "))
     if args.test_bam:
         print("\npileup encoder: %d locations: %d on the GPU, %d by pe_encode, %d by the Python builder, %d without a record"
               % tuple(counts[k] for k in ("locations", "gpu", "native", "python", "no_record")))
@@ -438,7 +477,8 @@ def main(argv=None) -> int:
     if shard_n > 1:
         import json
         with open(target + ".stats.json", "w") as f:
-            json.dump({"sites": int(n), "loop_s": t_loop, "process_s": time.time() - s_eval, "shard": shard_i, "of": shard_n}, f)
+            json.dump(dict({"sites": int(n), "loop_s": t_loop, "process_s": time.time() - s_eval, "shard": shard_i, "of": shard_n},
+                           **census_stats), f)
     print("\nscored %d sites -> %s" % (n, out_final if shard_n == 1 else target))
     print("\tTime elapsed for inference/testing {:.4f}".format(time.time() - s_eval))
     return 0

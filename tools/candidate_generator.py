@@ -44,20 +44,56 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def run_children(args, argv) -> int:
+    """--gpus N: a fresh process per GPU (``--shard g/N``, its own HIP_VISIBLE_DEVICES), then the merge of their parts."""
+    import subprocess
+    from dl4vc_amd.candidates import merge_parts, remove_parts
+    from dl4vc_amd.procs import child_devices, child_env, wait_children
+    devices = child_devices(args.gpus)
+    remove_parts(args.output, args.gpus)                      # (nothing of an earlier run is merged)
+    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__)] + argv + ["--shard", "%d/%d" % (g, args.gpus)],
+                              env=child_env(devices[g])) for g in range(args.gpus)]
+    rcs = wait_children(procs)
+    if any(rcs):
+        remove_parts(args.output, args.gpus)
+        raise SystemExit("shard process failed: %s" % rcs)
+    stats = merge_parts(args.output, args.gpus)
+    logging.info("Generated final VCF file at %s from %d parts.", args.output, args.gpus)
+    print("summary " + json.dumps(stats, sort_keys=True))
+    return 0
+
+
 def main(argv=None) -> int:
     p = build_parser()
     # (added here, after build_parser(): its table of flags stays the reference tool's)
     p.add_argument("--inflate-device", dest="inflate_device", choices=["gpu"], default=None,
                    help="Inflate the BAM's BGZF blocks and frame its records on the GPU instead of in host threads (needs INPUT.bai)")
+    p.add_argument("--gpus", type=int, default=1,
+                   help="One process per GPU: the groups of subregions are dealt to them in contiguous ranges, each writes its "
+                   "unsorted records to OUTPUT.part<g>, and this process sorts them into OUTPUT (the same bytes as with 1)")
+    p.add_argument("--shard", default="", help="g/N: count only the g-th of N ranges of groups into OUTPUT.part<g> (--gpus sets this)")
     args = p.parse_args(argv)
     print(args)
     logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.DEBUG if args.debug else logging.INFO)
     from dl4vc_amd.candidates import generate
+    from dl4vc_amd.shard import parse_shard
+    if args.gpus < 1:
+        p.error("--gpus must be at least 1")
+    try:
+        shard = parse_shard(args.shard) if args.shard else None
+    except ValueError as e:
+        p.error(str(e))
+    if args.gpus > 1 and shard is None:
+        return run_children(args, list(sys.argv[1:] if argv is None else argv))
     stats = generate(args.input, args.output, contigs=args.contigs, bedfile=args.bedfile, keep_contig_chr=args.keep_contig_chr,
                      chunk_size=args.chunk_size, threads=args.threads, snp_min_freq=args.snp_min_freq,
                      indel_min_freq=args.indel_min_freq, keep_multialleles=args.keep_multialleles,
-                     max_len_indel_allele=args.max_len_indel_allele, inflate_device=args.inflate_device)
-    logging.info("Generated final VCF file at %s.", args.output)
+                     max_len_indel_allele=args.max_len_indel_allele, inflate_device=args.inflate_device, shard=shard)
+    if shard is not None:
+        from dl4vc_amd.shard import part_path
+        logging.info("Wrote the records of shard %d/%d to %s.", shard[0], shard[1], part_path(args.output, shard[0]))
+    else:
+        logging.info("Generated final VCF file at %s.", args.output)
     print("summary " + json.dumps(stats, sort_keys=True))
     return 0
 

@@ -12,6 +12,11 @@ Alternating rounds (A B A B ...), each a fresh process as a user would start it,
 Both paths must write the same scored VCF; the tool fails if they do not.  One JSON record.
 
     python tools/score_bam_rate.py --dir /tmp/sbr [--length 200000 --rounds 3 --precision fp32] [--out profiles/x.json]
+
+``--record-census gpu``: what the record census costs instead -- ``main.py --test_bam --record-census gpu`` (one GPU, one shard)
+beside ``main.py --test_bam`` without the flag, alternating rounds of fresh processes on the same input, with ``--inflate-device
+gpu`` off and on: each round's ``census_s`` (wall clock around the census) and ``census_ms`` (device time of its resolve and
+census kernels), the census's locations/s, and the whole-process time of both arms.  Both arms must write the same scored VCF.
 """
 import argparse
 import json
@@ -79,6 +84,38 @@ def loop_clock(stdout):
     return {"sites": int(m.group(1)), "s": float(m.group(2)), "sites_per_s": int(m.group(3))}
 
 
+def census_arms(a, bam, fa, n_loc, common):
+    """The arm with the record census beside the arm without, with the BAM inflated on the host and on the device."""
+    res = {"tool": "score_bam_rate", "arm": "record_census", "locations": n_loc, "precision": a.precision, "same_scored_vcf": True}
+    for inflate in (None, "gpu"):
+        extra = ["--inflate-device", inflate] if inflate else []
+        rounds = []
+        for k in range(a.rounds):
+            r = {}
+            for arm, flag in (("test_bam", []), ("census", ["--record-census", "gpu"])):
+                dt, out = timed([sys.executable, os.path.join(ROOT, "main.py"), "--test_bam", bam, "--test_fasta", fa,
+                                 "--save_vcf_records_file", os.path.join(a.dir, arm + ".vcf")] + common + extra + flag)
+                r[arm + "_wall_s"] = round(dt, 3)
+                r[arm + "_loop"] = loop_clock(out)
+                if flag:
+                    m = re.search(r"record census: census_s ([0-9.]+) for (\d+) locations \((\d+) records; census_ms ([0-9.]+) on the device\)", out)
+                    if not m:
+                        sys.exit("no census line in:\n%s" % out[-1500:])
+                    r.update(census_s=float(m.group(1)), census_records=int(m.group(3)), census_ms=float(m.group(4)),
+                             census_locations_per_s=round(int(m.group(2)) / max(float(m.group(1)), 1e-9)))
+            if open(os.path.join(a.dir, "epoch1_test_bam.vcf"), "rb").read() != open(os.path.join(a.dir, "epoch1_census.vcf"), "rb").read():
+                sys.exit("round %d: the two arms wrote different scored VCFs" % k)
+            rounds.append(r)
+            print("inflate %s round %d: %s" % (inflate, k, json.dumps(r)), file=sys.stderr, flush=True)
+        key = "inflate_device_gpu" if inflate else "inflate_host"
+        res[key] = {"rounds": rounds, "sites": rounds[0]["census_loop"]["sites"],
+                    "test_bam_wall_s": [r["test_bam_wall_s"] for r in rounds], "census_wall_s": [r["census_wall_s"] for r in rounds],
+                    "census_s": [r["census_s"] for r in rounds], "census_ms": [r["census_ms"] for r in rounds],
+                    "census_locations_per_s": [r["census_locations_per_s"] for r in rounds],
+                    "census_arm_slower_by_s_median": round(float(np.median([r["census_wall_s"] - r["test_bam_wall_s"] for r in rounds])), 3)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dir", required=True, help="working directory (inputs are made there once and reused)")
@@ -88,6 +125,8 @@ def main():
     ap.add_argument("--threads", type=int, default=16, help="--num-processes of the converter")
     ap.add_argument("--no-bench", action="store_true", help="skip the bench.py run of the forward alone")
     ap.add_argument("--inflate-device", default=None, choices=["gpu"], help="passed to main.py --test_bam")
+    ap.add_argument("--record-census", dest="record_census", default=None, choices=["gpu"],
+                    help="measure main.py --test_bam --record-census gpu beside --test_bam instead (see above)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
@@ -101,6 +140,13 @@ def main():
     if not os.path.isfile(ck):
         torch.save({"state_dict": {"module." + k: torch.from_numpy(v) for k, v in random_state_dict(DanConfig(), seed=1).items()}}, ck)
     common = ["--modelload", ck, "--sample_vcf", vcf, "--save_vcf_records", "--sites-per-launch", "4096", "--precision", a.precision] + MODEL
+    if a.record_census:
+        line = json.dumps(census_arms(a, bam, fa, n_loc, common))
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+            open(a.out, "w").write(line + "\n")
+        return 0
     hdf = os.path.join(a.dir, "candidates.hdf")
     rounds = []
     for k in range(a.rounds):
