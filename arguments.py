@@ -77,6 +77,10 @@ _EXTRA = [
                                       "on the GPU as well (needs the .bai; same scored VCF)"),
     ("--loader-device", "str", None, "gpu: with --test_file, the file's HDF5 chunks are inflated and its sites assembled on the GPU "
                                      "(the host only reads the raw chunks and plans rows and allele masks); same scored VCF"),
+    ("--train-loader-device", "str", None, "gpu: with --train_file, the training batches and the per-epoch evaluation batches are "
+                                           "assembled on the GPU (raw HDF5 chunks inflated on the device, shuffled records "
+                                           "gathered there, targets from a device histogram); --num-data-workers starts no "
+                                           "worker process; same losses, checkpoints and scored VCF"),
     ("--record-census", "str", None, "gpu: with --test_bam, the locations are censused first (which of them give a record, by the GPU "
                                      "encoder's status rule without its planes), so that --gpus N, --shard g/N, "
                                      "--test_holdout_chromosomes and --max-test-batches select and seed the records as --test_file "

@@ -202,3 +202,21 @@ def count_center_support(reads_pos_major: np.ndarray, reference: np.ndarray, var
     agree = hist.get(ref_base, 0)
     disagree = sum(hist.get(t, 0) for t in _SUPPORT_TOKENS - {ref_base})
     return agree + disagree, agree, disagree
+
+
+def center_support_from_counts(counts: np.ndarray, reference: np.ndarray, var_mode: int):
+    """``count_center_support`` from the histogram instead of the reads: ``counts[k][t]`` = the selected rows whose token at
+    column ``CENTER + k`` is ``t`` (k = 0, 1; t = 0..15) -- what ``cl_center_counts_device`` leaves of an assembled reads plane."""
+    if var_mode == V.MUTATION_SNP:
+        ref_base, hist = int(reference[CENTER]), counts[0]
+    elif var_mode == V.MUTATION_DELETE:
+        ref_base, hist = int(reference[CENTER + 1]), counts[1]
+    elif var_mode == V.MUTATION_INSERT:
+        ref_base, hist = V.NOINSERT, counts[1]
+    else:
+        raise UnboundLocalError("unknown mutation type")
+    if ref_base >= len(hist):
+        raise ValueError("reference token %d at the window centre is outside the %d counted tokens" % (ref_base, len(hist)))
+    agree = int(hist[ref_base])
+    disagree = sum(int(hist[t]) for t in _SUPPORT_TOKENS - {ref_base})
+    return agree + disagree, agree, disagree

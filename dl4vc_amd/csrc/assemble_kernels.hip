@@ -10,6 +10,11 @@
 // read with one 16-byte load at the source's own (arbitrary) alignment.  A store that straddles two output rows gathers its bytes
 // one by one.  "First R rows" is the same code with the whole span as one row of R * L bytes: no store straddles, the copy is
 // one contiguous stream.  A plane the model does not use is zero-filled by the same head / body / tail split.
+//
+// center_counts (cl_center_counts_device): the read tokens of an assembled reads plane [m][R][L] counted at the two columns the
+// training targets look at (alleles.count_center_support: the centre column and the one after it).  One 64-lane wave per site:
+// lane i takes rows i, i + 64, ..., adds its two tokens to 2 x 16 integer counters in LDS, and lanes 0..31 write the counters out,
+// every output element once.  Integer adds in LDS: the counts do not depend on the order the lanes arrive in.
 #include "pileup_device.h"
 
 namespace pg {
@@ -71,7 +76,29 @@ __global__ __launch_bounds__(ASSEMBLE_BLOCK) void assemble_planes(AssembleArgs a
     for (int o = tail0 + threadIdx.x; o < span; o += ASSEMBLE_BLOCK) dst[o] = gather_byte(slab, rows, L, o);
 }
 
+__global__ __launch_bounds__(COUNTS_BLOCK) void center_counts(const uint8_t* __restrict__ reads, int R, int L, int col,
+                                                              int32_t* __restrict__ counts) {
+    __shared__ int32_t cnt[2 * COUNT_TOKENS];
+    const int lane = threadIdx.x;
+    if (lane < 2 * COUNT_TOKENS) cnt[lane] = 0;
+    __syncthreads();
+    const uint8_t* site = reads + (size_t)blockIdx.x * (size_t)R * (size_t)L + col;
+    for (int r = lane; r < R; r += COUNTS_BLOCK) {
+        const uint8_t a = site[(size_t)r * L], b = site[(size_t)r * L + 1];
+        if (a < COUNT_TOKENS) atomicAdd(&cnt[a], 1);
+        if (b < COUNT_TOKENS) atomicAdd(&cnt[COUNT_TOKENS + b], 1);
+    }
+    __syncthreads();
+    if (lane < 2 * COUNT_TOKENS) counts[(size_t)blockIdx.x * (2 * COUNT_TOKENS) + lane] = cnt[lane];
+}
+
 }  // namespace
+
+hipError_t launch_center_counts(const uint8_t* reads, int64_t m, int32_t R, int32_t L, int32_t col, int32_t* counts, hipStream_t s) {
+    if (m <= 0) return hipSuccess;
+    hipLaunchKernelGGL(center_counts, dim3((unsigned)m), dim3(COUNTS_BLOCK), 0, s, reads, R, L, col, counts);
+    return hipGetLastError();
+}
 
 hipError_t launch_assemble(const AssembleArgs& a, int32_t m, hipStream_t s) {
     if (m <= 0) return hipSuccess;

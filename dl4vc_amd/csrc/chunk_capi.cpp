@@ -71,7 +71,8 @@ int open_loader(cl_loader* h, int64_t max_records) {
     CL_TRY(hipMalloc((void**)&h->d_status, (size_t)h->max_chunks * sizeof(int32_t)));
     CL_TRY(hipHostMalloc((void**)&h->h_tab, (size_t)h->max_chunks * (sizeof(zi::StreamDesc) + sizeof(int32_t)), hipHostMallocDefault));
     CL_TRY(hipHostMalloc((void**)&h->h_blob, (size_t)h->max_chunks * h->chunk_records * h->blob_bytes + 16, hipHostMallocDefault));
-    for (hipEvent_t& e : h->ev) CL_TRY(hipEventCreate(&e));
+    // blocking-sync events: the thread that waits for an inflate (tens of ms for a chunk of a megabyte) sleeps instead of spinning
+    for (hipEvent_t& e : h->ev) CL_TRY(hipEventCreateWithFlags(&e, hipEventBlockingSync));
     return 0;
 }
 
@@ -114,7 +115,7 @@ int inflate_chunks(cl_loader* h, const uint8_t* comp, uint64_t nbytes, const uin
                             (size_t)h->span1, (size_t)n_rec, hipMemcpyDeviceToHost, s));
     CL_TRY(hipMemcpyAsync(h_status, h->d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     CL_TRY(hipEventRecord(h->ev[3], s));
-    CL_TRY(hipStreamSynchronize(s));
+    CL_TRY(hipEventSynchronize(h->ev[3]));               // (everything of this call on `s` lies in front of the event)
     float ms[3] = {0, 0, 0};
     for (int k = 0; k < 3; ++k) CL_TRY(hipEventElapsedTime(&ms[k], h->ev[k], h->ev[k + 1]));
     h->st.upload_ms = ms[0]; h->st.inflate_ms = ms[1]; h->st.blob_copy_back_ms = ms[2];
@@ -122,6 +123,13 @@ int inflate_chunks(cl_loader* h, const uint8_t* comp, uint64_t nbytes, const uin
     h->st.inflated_bytes = (int64_t)(n * chunk_bytes);
     memcpy(status, h_status, (size_t)n * sizeof(int32_t));
     h->n_records = n_rec;
+    return 0;
+}
+
+// What both cl_center_counts_* entries refuse: 0 = fine.
+int counts_arguments(cl_loader* h, const char* who, const uint8_t* reads, int64_t m, int32_t rows, int32_t window, const int32_t* counts) {
+    if (m < 0 || m > INT32_MAX || rows < 1 || window < 3) return cfail(h, -1, "%s: bad shape", who);
+    if (m > 0 && (!reads || !counts)) return cfail(h, -1, "%s: null argument", who);
     return 0;
 }
 
@@ -198,6 +206,37 @@ int cl_assemble_device(cl_loader_t* h, const int32_t* slots, const int16_t* rows
     } catch (...) {
         return cfail(h, -4, "cl_assemble_device: unknown exception");
     }
+}
+
+int cl_center_counts_device(cl_loader_t* h, const uint8_t* reads, int64_t m, int32_t rows, int32_t window, int32_t* counts, void* stream) {
+    if (!h) return cfail(nullptr, -1, "cl_center_counts_device: null handle");
+    try {
+        if (const int rc = counts_arguments(h, "cl_center_counts_device", reads, m, rows, window, counts)) return rc;
+        CL_TRY(hipSetDevice(h->device));
+        CL_TRY(pg::launch_center_counts(reads, m, rows, window, (window - 1) / 2, counts, (hipStream_t)stream));
+        return 0;
+    } catch (const std::exception& e) {
+        return cfail(h, -4, "cl_center_counts_device: %s", e.what());
+    } catch (...) {
+        return cfail(h, -4, "cl_center_counts_device: unknown exception");
+    }
+}
+
+int cl_center_counts_host(cl_loader_t* h, const uint8_t* reads, int64_t m, int32_t rows, int32_t window, int32_t* counts, void* stream) {
+    (void)stream;
+    if (const int rc = counts_arguments(h, "cl_center_counts_host", reads, m, rows, window, counts)) return rc;
+    const int64_t col = (window - 1) / 2;
+    for (int64_t i = 0; i < m; ++i) {
+        int32_t* c = counts + i * 2 * pg::COUNT_TOKENS;
+        for (int k = 0; k < 2 * pg::COUNT_TOKENS; ++k) c[k] = 0;
+        const uint8_t* site = reads + (size_t)i * rows * window + col;
+        for (int32_t r = 0; r < rows; ++r)
+            for (int k = 0; k < 2; ++k) {
+                const uint8_t t = site[(size_t)r * window + k];
+                if (t < pg::COUNT_TOKENS) ++c[k * pg::COUNT_TOKENS + t];
+            }
+    }
+    return 0;
 }
 
 int cl_get_stats(cl_loader_t* h, cl_stats* out) {

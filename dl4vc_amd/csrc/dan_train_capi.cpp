@@ -563,13 +563,11 @@ void fill_encode(RowArgs& a, const dan_trainer* t, int B) {
     a.emb = t->P + t->params[t->p_emb].off; a.pe = t->d_pe;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dan_train_backward_begin(dan_trainer_t* t, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, const uint8_t* ref,
-                             const uint8_t* ref_mask, const uint8_t* var_mask, int64_t n_sites, const dan_train_targets* tg,
-                             const uint8_t* const* dropout_masks, uint64_t seed) {
+// dan_train_backward_begin and dan_train_backward_begin_device: the six planes are host arrays (device_planes == false: they go
+// up through the pinned mirror) or lie in device memory already (true: six device-to-device copies into d_in, behind `ready`).
+int backward_begin(dan_trainer_t* t, bool device_planes, void* ready, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand,
+                   const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int64_t n_sites, const dan_train_targets* tg,
+                   const uint8_t* const* dropout_masks, uint64_t seed) {
     if (!t) return DAN_ERR_INVALID_ARG;
     if (!t->finalized) return failt(t, DAN_ERR_STATE, "dan_train_backward before dan_train_finalize");
     if (t->pending) return failt(t, DAN_ERR_STATE, "dan_train_backward_begin: the previous step has not been ended (dan_train_backward_end)");
@@ -592,13 +590,23 @@ int dan_train_backward_begin(dan_trainer_t* t, const uint8_t* reads, const uint8
         uint8_t* h = t->h_stage;
         size_t o = 0;
         auto stage = [&](const void* src, size_t n) { memcpy(h + o, src, n); o += n; };
-        stage(reads, B * rl); stage(qual, B * rl); stage(strand, B * rl);
-        stage(ref, (size_t)B * L); stage(ref_mask, (size_t)B * L); stage(var_mask, (size_t)B * L);
+        const uint8_t* planes[6] = {reads, qual, strand, ref, ref_mask, var_mask};
+        const size_t plane_bytes[6] = {B * rl, B * rl, B * rl, (size_t)B * L, (size_t)B * L, (size_t)B * L};
+        if (device_planes) {
+            // the planes are where another stream assembled them: wait for it, then copy them to the places fill_encode reads
+            if (ready) HIPT(t, hipStreamWaitEvent(s, (hipEvent_t)ready, 0));
+            for (int k = 0; k < 6; ++k) {
+                HIPT(t, hipMemcpyAsync(t->d_in + o, planes[k], plane_bytes[k], hipMemcpyDeviceToDevice, s));
+                o += plane_bytes[k];
+            }
+        } else {
+            for (int k = 0; k < 6; ++k) stage(planes[k], plane_bytes[k]);
+        }
         const size_t n_in = o;
         stage(tg->label, B); stage(tg->var_type, B); stage(tg->var_base_enum, B); stage(tg->var_ref_enum, B);
         const size_t n_tg8 = o - n_in;
         stage(tg->allele_freq, B * sizeof(float)); stage(tg->coverage, B * sizeof(float)); stage(tg->weight, B * sizeof(float));
-        HIPT(t, hipMemcpyAsync(t->d_in, h, n_in, hipMemcpyHostToDevice, s));
+        if (!device_planes) HIPT(t, hipMemcpyAsync(t->d_in, h, n_in, hipMemcpyHostToDevice, s));
         HIPT(t, hipMemcpyAsync(t->d_tg8, h + n_in, n_tg8, hipMemcpyHostToDevice, s));
         HIPT(t, hipMemcpyAsync(t->d_tgf, h + n_in + n_tg8, o - n_in - n_tg8, hipMemcpyHostToDevice, s));
     }
@@ -824,6 +832,22 @@ int dan_train_backward_begin(dan_trainer_t* t, const uint8_t* reads, const uint8
     HIPT(t, hipGetLastError());
     t->pending = true;
     return DAN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dan_train_backward_begin(dan_trainer_t* t, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, const uint8_t* ref,
+                             const uint8_t* ref_mask, const uint8_t* var_mask, int64_t n_sites, const dan_train_targets* tg,
+                             const uint8_t* const* dropout_masks, uint64_t seed) {
+    return backward_begin(t, false, nullptr, reads, qual, strand, ref, ref_mask, var_mask, n_sites, tg, dropout_masks, seed);
+}
+
+int dan_train_backward_begin_device(dan_trainer_t* t, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, const uint8_t* ref,
+                                    const uint8_t* ref_mask, const uint8_t* var_mask, int64_t n_sites, const dan_train_targets* tg,
+                                    const uint8_t* const* dropout_masks, uint64_t seed, void* ready_event) {
+    return backward_begin(t, true, ready_event, reads, qual, strand, ref, ref_mask, var_mask, n_sites, tg, dropout_masks, seed);
 }
 
 int dan_train_backward_end(dan_trainer_t* t, float* losses, uint8_t* close) {

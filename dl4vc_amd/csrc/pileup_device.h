@@ -91,4 +91,11 @@ struct AssembleArgs {
 
 hipError_t launch_assemble(const AssembleArgs& a, int32_t m, hipStream_t s);
 
+constexpr int COUNTS_BLOCK = 64;             // one wave per site
+constexpr int COUNT_TOKENS = 16;             // tokens 0..15 are counted, larger bytes are not
+
+// counts[site][k][t] = rows of reads[site] ([R][L]) whose byte at column col + k is t (k = 0, 1; t < COUNT_TOKENS).  The caller
+// has checked 0 <= col, col + 1 < L and 0 < m <= INT32_MAX.
+hipError_t launch_center_counts(const uint8_t* reads, int64_t m, int32_t R, int32_t L, int32_t col, int32_t* counts, hipStream_t s);
+
 }  // namespace pg

@@ -127,7 +127,9 @@ class CandidateFile:
             offs[C.string_at(p).decode()] = int(lib.H5Tget_member_offset(self._tid, i))
             lib.H5free_memory(p)
         # window fixed at 201 (dl4vc/dataset.py:114); the stored read count follows from the item size
-        for store in (200, 100, 50, 300, 400, 1000):
+        rest, plane = record_dtype(0, 201).itemsize, 3 * 201          # (any row count: the small files of the tests store 20)
+        fits = (self._itemsize - rest) // plane if self._itemsize > rest and (self._itemsize - rest) % plane == 0 else 200
+        for store in (200, 100, 50, 300, 400, 1000, fits):
             dt = record_dtype(store, 201)
             if dt.itemsize == self._itemsize and all(dt.fields[k][1] == offs.get(k, -1) for k in dt.names):
                 return dt

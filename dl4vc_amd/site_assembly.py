@@ -48,10 +48,22 @@ def plan_sites(status, num_reads, ref, vcf_strings: Sequence[str], reads: int, s
                first_record: int = 0) -> SitePlan:
     """Rows and masks of the locations with ``status == 1``, in order.  Site i (counting records only) draws with
     ``seed + first_record + i``, as ``score_records`` / ``NativeLoader`` seed record ``first_record + i`` of a file."""
+    slots = np.flatnonzero(np.asarray(status) == 1).astype(np.int32)
+    return plan_records(slots, first_record + np.arange(len(slots), dtype=np.int64), num_reads, ref, vcf_strings, reads, stored_rows,
+                        seed)
+
+
+def plan_records(slots, record_index, num_reads, ref, vcf_strings: Sequence[str], reads: int, stored_rows: int, seed: int) -> SitePlan:
+    """``plan_sites`` with the sites named one by one: site i is slot ``slots[i]`` (any order, a slot may repeat) and draws the
+    subset of a deep pileup with ``seed + record_index[i]`` -- the rule of ``train_data.assemble_training_batch``
+    (``RandomState(seed + idx)``) for the shuffled records of a training batch.  ``num_reads``, ``ref`` and ``vcf_strings`` are
+    indexed by slot."""
     from . import loader
     lib = loader.load_library()
-    status = np.asarray(status)
-    slots = np.flatnonzero(status == 1).astype(np.int32)
+    slots = np.ascontiguousarray(slots, np.int32)
+    record_index = np.asarray(record_index, np.int64)
+    if record_index.shape != slots.shape:
+        raise ValueError("%d record indices for %d slots" % (len(record_index), len(slots)))
     m, R, S = len(slots), int(reads), int(stored_rows)
     L = ref.shape[1] if ref.ndim == 2 else 0
     if R > S:
@@ -74,7 +86,7 @@ def plan_sites(status, num_reads, ref, vcf_strings: Sequence[str], reads: int, s
         if n > R:
             if n > S:
                 raise ValueError("location slot %d holds %d reads, more than the %d stored rows" % (slots[i], n, S))
-            k = lib.dl_select_rows((base + first_record + i) & 0xFFFFFFFF, n, S, R, draw.ctypes.data_as(C.POINTER(C.c_int32)))
+            k = lib.dl_select_rows((base + int(record_index[i])) & 0xFFFFFFFF, n, S, R, draw.ctypes.data_as(C.POINTER(C.c_int32)))
             if k != R:
                 raise ValueError("dl_select_rows gave %d rows, not %d" % (k, R))
             rows[i] = draw[:R]
@@ -83,7 +95,7 @@ def plan_sites(status, num_reads, ref, vcf_strings: Sequence[str], reads: int, s
         recs.append(text)
         st = lib.dl_allele_masks(text.encode(), p(out_ref[i:i + 1]), p(rmask[i:i + 1]), p(vmask[i:i + 1]))
         if st not in (0, 1):
-            raise ValueError("record %d (%s): the allele masks cannot be built" % (first_record + i, text.split("\t", 2)[:2]))
+            raise ValueError("record %d (%s): the allele masks cannot be built" % (int(record_index[i]), text.split("\t", 2)[:2]))
         black[i] = st == 1
     return SitePlan(slots, rows, first, out_ref, rmask, vmask, recs, nr, black)
 

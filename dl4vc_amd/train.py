@@ -23,7 +23,7 @@ from .model import normalise_state_dict
 TRAIN_SYMBOLS = ("dan_train_create", "dan_train_set_tensor", "dan_train_finalize", "dan_train_destroy", "dan_train_last_error",
                  "dan_train_backward", "dan_train_apply", "dan_train_step", "dan_train_set_lr", "dan_train_grad_buffer", "dan_train_get_tensor",
                  "dan_train_put_tensor", "dan_train_query", "dan_train_backward_begin", "dan_train_backward_end", "dan_train_wait_bucket",
-                 "dan_train_grad_bucket", "dan_train_set_global_batch")
+                 "dan_train_grad_bucket", "dan_train_set_global_batch", "dan_train_backward_begin_device")
 
 LOSS_NAMES = ("loss", "bin", "vt", "af", "cov", "vb", "vr")
 
@@ -83,6 +83,7 @@ def _bind(lib):
     planes = [vp] * 6
     lib.dan_train_backward.argtypes = [vp] + planes + [C.c_int64, C.POINTER(_CTargets), C.POINTER(vp), C.c_uint64, vp, vp]
     lib.dan_train_backward_begin.argtypes = [vp] + planes + [C.c_int64, C.POINTER(_CTargets), C.POINTER(vp), C.c_uint64]
+    lib.dan_train_backward_begin_device.argtypes = [vp] + planes + [C.c_int64, C.POINTER(_CTargets), C.POINTER(vp), C.c_uint64, vp]
     lib.dan_train_backward_end.argtypes = [vp, vp, vp]
     lib.dan_train_wait_bucket.argtypes = [vp, C.c_int32]
     lib.dan_train_grad_bucket.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -210,6 +211,7 @@ class DanTrainer:
         # (model.py:369-377); a loaded checkpoint's own indices win
         self._fc_keys = ("conv2hidden.1", "conv2hidden.4") if hyper.dropout > 0 else ("conv2hidden.0", "conv2hidden.3")
         self._extra: Dict[str, np.ndarray] = {}
+        self._pending_planes = None                 # device planes of a step begun and not ended
 
     def _check(self, rc, what):
         if rc != 0:
@@ -261,6 +263,12 @@ class DanTrainer:
             if a.shape != shp:
                 raise ValueError("%s has shape %s, expected %s" % (nm, a.shape, shp))
             ins.append(a)
+        ct, mp, alive = self._marshal_targets(B, targets, dropout_masks)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        return B, [p(a) for a in ins] + [B, C.byref(ct), mp], (ins, alive)
+
+    def _marshal_targets(self, B, targets, dropout_masks):
+        """The host arrays behind the planes: targets and dropout masks, whichever memory the planes are in."""
         u8 = lambda k: np.ascontiguousarray(np.asarray(targets[k]).reshape(-1), np.uint8)        # noqa: E731
         f32 = lambda k: np.ascontiguousarray(np.asarray(targets[k]).reshape(-1), np.float32)     # noqa: E731
         tg = {"label": u8("label"), "var_type": u8("var_type"), "allele_freq": f32("allele_freq"), "coverage": f32("coverage"),
@@ -281,8 +289,24 @@ class DanTrainer:
                 keep.append(m)
                 arr[i] = m.ctypes.data
             mp = arr
-        p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
-        return B, [p(a) for a in ins] + [B, C.byref(ct), mp], (ins, tg, ct, keep)
+        return ct, mp, (tg, ct, keep)
+
+    def _marshal_device(self, planes, targets, dropout_masks):
+        """``_marshal`` for six uint8 torch tensors in this trainer's device memory: their addresses, the same shape checks."""
+        B = int(planes[0].shape[0])
+        R, L = self.config.reads, self.config.length
+        shapes = [(B, R, L)] * 3 + [(B, L)] * 3
+        if len(planes) != 6:
+            raise ValueError("six planes are needed, got %d" % len(planes))
+        ptrs = []
+        for a, shp, nm in zip(planes, shapes, ("reads", "qual", "strand", "ref", "ref_mask", "var_mask")):
+            if not a.is_cuda or str(a.dtype) != "torch.uint8" or not a.is_contiguous():
+                raise ValueError("%s must be a contiguous uint8 tensor in device memory" % nm)
+            if tuple(a.shape) != shp:
+                raise ValueError("%s has shape %s, expected %s" % (nm, tuple(a.shape), shp))
+            ptrs.append(C.c_void_p(a.data_ptr()) if B else None)
+        ct, mp, alive = self._marshal_targets(B, targets, dropout_masks)
+        return B, ptrs + [B, C.byref(ct), mp], (list(planes), alive)
 
     @staticmethod
     def _outputs(losses, close, norm=None):
@@ -305,10 +329,22 @@ class DanTrainer:
         return self._outputs(losses, close, norm)
 
     # ---- the same step in two halves (``GradientExchange`` runs between them) --------------------------------------
-    def backward_begin(self, planes: Sequence, targets: Mapping, dropout_masks=None, seed: int = 0) -> None:
-        """Stage the inputs and enqueue forward + backward; returns while the device works."""
-        B, head, _alive = self._marshal(planes, targets, dropout_masks)      # (the inputs are copied before the call returns)
-        self._check(self.lib.dan_train_backward_begin(*([self._h] + head + [C.c_uint64(seed)])), "dan_train_backward_begin")
+    def backward_begin(self, planes: Sequence, targets: Mapping, dropout_masks=None, seed: int = 0, event=None) -> None:
+        """Stage the inputs and enqueue forward + backward; returns while the device works.  ``planes``: six host arrays, or six
+        uint8 torch tensors in device memory (``dan_train_backward_begin_device``: the trainer's stream waits for ``event``, a
+        ``torch.cuda.Event`` recorded behind whatever wrote them, and copies them device to device; they must stay untouched
+        until ``backward_end`` has returned)."""
+        if hasattr(planes[0], "data_ptr"):
+            B, head, _alive = self._marshal_device(planes, targets, dropout_masks)
+            ev = C.c_void_p(int(event.cuda_event)) if event is not None else None
+            self._check(self.lib.dan_train_backward_begin_device(*([self._h] + head + [C.c_uint64(seed), ev])),
+                        "dan_train_backward_begin_device")
+            self._pending_planes = _alive                                     # (the tensors live until backward_end)
+        else:
+            if event is not None:
+                raise ValueError("event goes with planes in device memory")
+            B, head, _alive = self._marshal(planes, targets, dropout_masks)      # (the inputs are copied before the call returns)
+            self._check(self.lib.dan_train_backward_begin(*([self._h] + head + [C.c_uint64(seed)])), "dan_train_backward_begin")
         self._pending_B = B
 
     def wait_bucket(self, bucket: int) -> None:
@@ -320,6 +356,7 @@ class DanTrainer:
         close = np.zeros((self._pending_B, 2), np.uint8)
         self._check(self.lib.dan_train_backward_end(self._h, losses.ctypes.data_as(C.c_void_p), close.ctypes.data_as(C.c_void_p)),
                     "dan_train_backward_end")
+        self._pending_planes = None
         return self._outputs(losses, close)
 
     def set_global_batch(self, sites_per_rank: float, vb_weight_per_rank: float, vr_weight_per_rank: float) -> None:

@@ -29,7 +29,7 @@ from typing import Dict, Iterable, Iterator, List, Optional, Sequence
 
 import numpy as np
 
-from .alleles import parse_candidate, count_center_support
+from .alleles import parse_candidate, count_center_support, center_support_from_counts
 from .dataset import assemble_site
 from .synth import SiteBatch
 
@@ -66,6 +66,44 @@ def site_targets(record, site, keep_candidate_af: bool = True) -> Dict[str, floa
             "var_ref_enum": int(info["ref_base"]), "is_snp": int(bool(info["is_snp"]))}
 
 
+def site_targets_from_counts(label: int, vcfrec: str, ref, counts, keep_candidate_af: bool = True) -> Dict[str, float]:
+    """``site_targets`` of a site whose reads stayed on the device: the record's label and text, its reference row and the
+    ``[2][16]`` centre-token counts of its selected rows (``cl_center_counts_device``).  Same arithmetic."""
+    info = parse_candidate(vcfrec)
+    coverage = info["coverage"]
+    allele_freq = info["allele_freq"]
+    cover, _agree, variant = center_support_from_counts(counts, ref, info["var_mode"])
+    if cover > 0:                                               # dataset.py:614-620
+        coverage = cover
+        if not keep_candidate_af:
+            allele_freq = variant / cover
+    return {"label": int(label), "var_type": int(info["var_type"]), "allele_freq": float(allele_freq), "coverage": float(coverage),
+            "var_base_enum": int(info["var_base"]), "var_ref_enum": int(info["ref_base"]), "is_snp": int(bool(info["is_snp"]))}
+
+
+def target_arrays(tgs: Sequence[Dict[str, float]], non_snp_train_weight: float = 1.0, trust_weight=None) -> Dict[str, np.ndarray]:
+    """The per-site dicts of ``site_targets`` -> the arrays of a batch, with the example weight (trainer.py:169-172)."""
+    t = {"label": np.array([g["label"] for g in tgs], np.uint8), "var_type": np.array([g["var_type"] for g in tgs], np.uint8),
+         "allele_freq": np.array([g["allele_freq"] for g in tgs], np.float32),
+         "coverage": np.array([g["coverage"] for g in tgs], np.float32),
+         "var_base_enum": np.array([g["var_base_enum"] for g in tgs], np.uint8),
+         "var_ref_enum": np.array([g["var_ref_enum"] for g in tgs], np.uint8),
+         "is_snp": np.array([g["is_snp"] for g in tgs], np.uint8)}
+    s = t["is_snp"].astype(np.float32)
+    w = s + (1.0 - s) * np.float32(non_snp_train_weight)         # trainer.py:169-172
+    if trust_weight is not None:
+        w = w * np.asarray(trust_weight, np.float32)
+    t["weight"] = w.astype(np.float32)
+    return t
+
+
+def targets_from_counts(plan, label, counts, non_snp_train_weight: float = 1.0, keep_candidate_af: bool = True,
+                        trust_weight=None) -> Dict[str, np.ndarray]:
+    """The target arrays of the sites of ``plan`` (``site_assembly.SitePlan``) from their labels and centre-token counts."""
+    tgs = [site_targets_from_counts(label[i], plan.vcfrec[i], plan.ref[i], counts[i], keep_candidate_af) for i in range(len(plan))]
+    return target_arrays(tgs, non_snp_train_weight, trust_weight)
+
+
 def assemble_training_batch(records, indices: Sequence[int], max_reads: int, seed: Optional[int] = None,
                             non_snp_train_weight: float = 1.0, keep_candidate_af: bool = True, use_q: bool = True,
                             use_strand: bool = True, trust_weight=None) -> TrainBatch:
@@ -80,17 +118,7 @@ def assemble_training_batch(records, indices: Sequence[int], max_reads: int, see
     stack = lambda f: np.stack([getattr(s, f) for s in sites])   # noqa: E731
     batch = SiteBatch(stack("reads"), stack("qual"), stack("strand"), stack("ref"), stack("ref_mask"), stack("var_mask"),
                       [s.vcfrec for s in sites], np.array([s.num_reads for s in sites], np.int32))
-    t = {"label": np.array([g["label"] for g in tgs], np.uint8), "var_type": np.array([g["var_type"] for g in tgs], np.uint8),
-         "allele_freq": np.array([g["allele_freq"] for g in tgs], np.float32),
-         "coverage": np.array([g["coverage"] for g in tgs], np.float32),
-         "var_base_enum": np.array([g["var_base_enum"] for g in tgs], np.uint8),
-         "var_ref_enum": np.array([g["var_ref_enum"] for g in tgs], np.uint8),
-         "is_snp": np.array([g["is_snp"] for g in tgs], np.uint8)}
-    s = t["is_snp"].astype(np.float32)
-    w = s + (1.0 - s) * np.float32(non_snp_train_weight)         # trainer.py:169-172
-    if trust_weight is not None:
-        w = w * np.asarray(trust_weight, np.float32)
-    t["weight"] = w.astype(np.float32)
+    t = target_arrays(tgs, non_snp_train_weight, trust_weight)
     return TrainBatch(batch, t, np.asarray(indices, np.int64), np.array([s.blacklist for s in sites], bool),
                       [s.name for s in sites])
 
@@ -177,6 +205,177 @@ class BatchPrefetcher:
         if self._source is not None:
             self._source.close()
             self._source = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+@dataclass
+class DeviceTrainBatch:
+    """A batch whose six planes lie in device memory (``DeviceBatchPrefetcher``): uint8 torch tensors, views of one of the
+    prefetcher's plane sets.  ``event`` was recorded on the loader's stream behind the assembly.  ``release()`` hands the
+    plane set back to the loader; call it once the step (``backward_end``) or the forward that read the planes has returned."""
+    device_planes: list
+    targets: Dict[str, np.ndarray]
+    index: np.ndarray
+    blacklist: np.ndarray
+    vcfrec: List[str]
+    event: object
+    _release: object = None
+
+    def planes(self):
+        return self.device_planes
+
+    def release(self) -> None:
+        rel, self._release = self._release, None
+        if rel is not None:
+            rel()
+
+    def __len__(self):
+        return len(self.index)
+
+
+class _Stopped(Exception):
+    pass
+
+
+class BatchError(ValueError):
+    """The device loader's worker could not make a batch of the records it was asked for (a record with more reads than stored
+    rows, allele masks that cannot be built, a damaged chunk): the reason, for the command line to end the run with."""
+
+
+class DeviceBatchPrefetcher:
+    """``BatchPrefetcher``'s ``batches(index_lists, **kwargs)`` with the batches assembled on the GPU
+    (``--train-loader-device gpu``): one worker thread with plane sets handed back and forth, the pattern of
+    ``inference._FileBatches``.
+    The worker reads the raw chunks the indices of the next ``ahead`` index lists fall in and inflates them on the device in one
+    launch (``DeviceChunkLoader.inflate_lists``: a megabyte chunk keeps its one decoding lane busy for tens of milliseconds however
+    many chunks the launch holds, longer than a training step, so a launch per batch would bound the step rate); then, per list,
+    it plans rows and masks on the host, assembles the six planes into a free plane set and counts the centre tokens for the
+    targets (``assemble_list``), all on its own stream, while the consumer's steps run, and records the batch's event.  There are
+    ``2 * ahead`` plane sets, so that the lists of one launch can be assembled while the consumer still holds those of the one
+    before.  The lists of an epoch are known at its start (the sampler's feedback acts at the next epoch), so the worker
+    runs ahead as far as the plane sets allow.  A plane set returns to the worker through ``DeviceTrainBatch.release``.
+
+    torch must have been imported before the HIP libraries were loaded (one HIP runtime per process).  Every queue wait ends
+    after ``wait_s`` seconds with an error that names what it waited for; an exception of the worker is raised in the consumer."""
+
+    AHEAD = 4        # index lists whose chunks are inflated in one launch; twice as many plane sets
+
+    def __init__(self, path: str, reads: int, batch_sites: int, device: int = 0, use_q: bool = True, use_strand: bool = True,
+                 wait_s: float = 600.0, ahead: int = AHEAD):
+        import torch
+        from .chunk_loader import DeviceChunkLoader
+        self.torch, self.path = torch, path
+        self.B, self.wait_s = max(1, int(batch_sites)), float(wait_s)
+        self.ahead = max(1, int(ahead))
+        # the record buffer starts at one chunk and is sized by ``batches`` for the lists it is given: a shuffled epoch needs up to
+        # ``ahead * batch_sites`` chunks (1 MB each in the production layout), a sequential evaluation pass an eighth of that
+        self.loader = DeviceChunkLoader(path, reads, self.B, device=device, use_q=use_q, use_strand=use_strand, shuffled=self.ahead,
+                                        chunks=1)
+        self.dev = torch.device("cuda", device)
+        R, L = self.loader.reads, self.loader.window
+        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=self.dev)   # noqa: E731
+        self.sets = [[u8(self.B, R, L) for _ in range(3)] + [u8(self.B, L) for _ in range(3)]
+                     for _ in range(2 * self.ahead)]
+        self.stream = torch.cuda.Stream(self.dev)
+
+    @property
+    def stage(self):
+        return self.loader.stage
+
+    def __len__(self):
+        return len(self.loader)
+
+    def _wait(self, q, what: str, stop, put=None, alive=None):
+        """``q.get()`` (or ``q.put(put)``) in short waits: gives up when ``stop`` is set, when ``alive`` says the other side has
+        gone, and after ``wait_s`` seconds -- naming ``what``."""
+        import queue
+        import time
+        deadline = time.monotonic() + self.wait_s
+        while not stop.is_set():
+            try:
+                return q.get(timeout=0.2) if put is None else q.put(put[0], timeout=0.2)
+            except (queue.Empty, queue.Full):
+                pass
+            if alive is not None and not alive() and (put is not None or q.empty()):
+                raise RuntimeError("the device loader's worker thread ended while the consumer waited for %s" % what)
+            if time.monotonic() > deadline:
+                raise TimeoutError("the device loader of %s waited %.0f s for %s" % (self.path, self.wait_s, what))
+        raise _Stopped()
+
+    def _work(self, lists, kwargs, free, ready, stop):
+        try:
+            with self.torch.cuda.device(self.dev):
+                for k, idx in enumerate(lists):
+                    if k % self.ahead == 0:             # the chunks of the next few batches, inflated in one launch
+                        self.loader.inflate_lists(lists[k:k + self.ahead], self.stream.cuda_stream)
+                    planes = self._wait(free, "a free plane set for batch %d (the step that read it has not released it)" % k, stop)
+                    got = self.loader.assemble_list(idx, kwargs["seed"], [t.data_ptr() for t in planes], self.stream.cuda_stream)
+                    targets = targets_from_counts(got.plan, got.label, got.counts, kwargs.get("non_snp_train_weight", 1.0),
+                                                  kwargs.get("keep_candidate_af", True), kwargs.get("trust_weight"))
+                    event = self.torch.cuda.Event()
+                    event.record(self.stream)
+                    batch = DeviceTrainBatch([t[:len(idx)] for t in planes], targets, idx, np.array(got.plan.blacklist, bool),
+                                             list(got.plan.vcfrec), event, lambda planes=planes: free.put(planes))
+                    self._wait(ready, "the consumer to take batch %d" % k, stop, put=(batch,))
+                self._wait(ready, "the consumer to take the end of the batches", stop, put=(None,))
+        except _Stopped:
+            pass
+        except BaseException as e:      # noqa: BLE001 -- handed to the consumer, which raises it
+            try:
+                self._wait(ready, "the consumer to take the worker's error", stop, put=(e,))
+            except (_Stopped, TimeoutError):
+                pass
+
+    def batches(self, index_lists: Iterable[Sequence[int]], **kwargs) -> Iterator[DeviceTrainBatch]:
+        """A ``DeviceTrainBatch`` per index list, in the order given; ``kwargs`` as ``assemble_training_batch`` takes them
+        (``seed`` is required: it pins the read subsets of deep pileups)."""
+        import queue
+        import threading
+        if kwargs.get("seed") is None:
+            raise ValueError("the device loader needs the seed of the read subsets")
+        want = (self.loader.reads, bool(self.loader.use_q), bool(self.loader.use_strand))
+        have = (kwargs.get("max_reads", want[0]), bool(kwargs.get("use_q", True)), bool(kwargs.get("use_strand", True)))
+        if have != want:
+            raise ValueError("the loader was opened for (reads, use_q, use_strand) = %s, the batches ask for %s" % (want, have))
+        lists = [np.asarray(idx, np.int64) for idx in index_lists]
+        self.loader.reserve(max([self.loader.chunks_of(lists[k:k + self.ahead]) for k in range(0, len(lists), self.ahead)] or [0]))
+        free, ready, stop = queue.Queue(), queue.Queue(), threading.Event()     # (the plane sets bound what is ready)
+        for planes in self.sets:
+            free.put(planes)
+        worker = threading.Thread(target=self._work, args=(lists, kwargs, free, ready, stop), name="train-loader-device", daemon=True)
+        worker.start()
+        held = []                                        # batches handed out and (perhaps) not yet released, oldest first
+        try:
+            for k in range(len(lists) + 1):
+                # the consumer asks for batch k after it began the step of batch k - 1, so the step of batch k - 2 has ended:
+                # a batch the consumer did not release itself goes back now
+                while len(held) > 1:
+                    held.pop(0).release()
+                item = self._wait(ready, "batch %d of %d" % (k, len(lists)), stop, alive=worker.is_alive)
+                if isinstance(item, ValueError) and not isinstance(item, BatchError):
+                    raise BatchError(str(item)) from item         # (a record the loader refuses, a damaged chunk)
+                if isinstance(item, BaseException):
+                    raise item
+                if item is None:
+                    return
+                held.append(item)
+                yield item
+        finally:
+            stop.set()
+            worker.join(self.wait_s)
+            if worker.is_alive():
+                raise TimeoutError("the device loader's worker thread did not end within %.0f s" % self.wait_s)
+            self.stream.synchronize()
+
+    def close(self) -> None:
+        if self.loader is not None:
+            self.loader.close()
+            self.loader = None
 
     def __enter__(self):
         return self

@@ -94,8 +94,10 @@ def train_epoch(trainer, source: CandidateFile, sampler: EasyExampleSampler, hyp
     ``grad_tensor`` when ``world > 1``) -- ``DanTrainer`` on the GPU.  With ``exchange`` (and a trainer that has the
     ``backward_begin`` / ``wait_bucket`` / ``backward_end`` split) the FC-side gradient bucket is averaged while the
     convolution layers' backward still runs; otherwise one ``all_reduce`` of the flat buffer after the backward pass.
-    ``prefetcher``: loader workers assembling this rank's batches ahead of the GPU (``--num-data-workers``); without it the
-    batches are assembled in this process between steps.  Returns the epoch's mean losses."""
+    ``prefetcher``: loader workers assembling this rank's batches ahead of the GPU (``--num-data-workers``), or a
+    ``DeviceBatchPrefetcher`` (``--train-loader-device gpu``: the planes of its batches are device tensors, which take the
+    ``backward_begin`` / ``backward_end`` split and go back to the loader after ``backward_end``); without it the batches are
+    assembled in this process between steps.  Returns the epoch's mean losses."""
     order = sampler.epoch()
     cfg = trainer.config
     tot = {k: 0.0 for k in ("loss", "bin", "vt", "af", "cov", "vb", "vr")}
@@ -167,7 +169,8 @@ def train_epoch(trainer, source: CandidateFile, sampler: EasyExampleSampler, hyp
             nxt = next(feed, None)
         elif split:
             # enqueue the step, then take delivery of the next batch (worker hand-over, unpickling) while the device works
-            trainer.backward_begin(batch.planes(), batch.targets, seed=drop_seed)
+            on_device = hasattr(batch, "release")
+            trainer.backward_begin(batch.planes(), batch.targets, seed=drop_seed, **({"event": batch.event} if on_device else {}))
             nxt = next(feed, None)
             if world > 1 and exchange is not None:
                 grad = trainer.grad_tensor()
@@ -181,6 +184,8 @@ def train_epoch(trainer, source: CandidateFile, sampler: EasyExampleSampler, hyp
                 out = trainer.backward_end()
                 if world > 1:
                     average_gradients(trainer.grad_tensor(), world, all_reduce)
+            if on_device:
+                batch.release()                                        # the step that read the plane set has ended
         else:
             out = trainer.backward(batch.planes(), batch.targets, seed=drop_seed)
             nxt = next(feed, None)
@@ -235,14 +240,39 @@ def evaluate(net, source: CandidateFile, hyper: TrainHyper, batch_size: int, wri
     else:
         stream = (assemble_training_batch(read_indices(source, idx), idx, **kwargs) for idx in plan)
     for batch in stream:
-        out = net.forward_u8(*batch.planes(), aux=True)
+        if hasattr(batch, "release"):                                  # planes in device memory (DeviceBatchPrefetcher)
+            out = forward_device_planes(net, batch.planes(), batch.event)
+            batch.release()
+            vcfrec = batch.vcfrec
+        else:
+            out = net.forward_u8(*batch.planes(), aux=True)
+            vcfrec = batch.sites.vcfrec
         total += eval_losses(out, batch.targets, hyper)["loss"]
         n_batches += 1
         if write:
-            write("".join(scored_record(r, bp, v) + "\n" for r, bp, v in zip(batch.sites.vcfrec, out["bp"], out["vt_prob"])))
+            write("".join(scored_record(r, bp, v) + "\n" for r, bp, v in zip(vcfrec, out["bp"], out["vt_prob"])))
     if not reduce:
         return total, n_batches
     return total / max(n_batches, 1)
+
+
+def forward_device_planes(net, planes, event=None) -> Dict[str, np.ndarray]:
+    """``net.forward_u8(..., aux=True)`` for six uint8 torch tensors in device memory (``dan_forward_device`` with the aux
+    output): the same dict of host arrays.  ``event``: recorded behind whatever wrote the planes; waited for first."""
+    import torch
+    n, dev = int(planes[0].shape[0]), planes[0].device
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+    o = {"bin_logits": f32(n, 2), "vt_logits": f32(n, 3), "vt_prob": f32(n, 3), "bp": f32(n), "aux": f32(n, 22)}
+    if event is not None:
+        event.synchronize()
+    with torch.cuda.device(dev):
+        net.handle.forward_device([t.data_ptr() for t in planes], n, [o[k].data_ptr() for k in ("bin_logits", "vt_logits", "vt_prob", "bp", "aux")],
+                                  stream=0)
+        torch.cuda.synchronize(dev)
+    out = {k: v.cpu().numpy() for k, v in o.items()}
+    a = out.pop("aux")
+    out.update(af=a[:, 0:1].copy(), cov=a[:, 1:2].copy(), vb=a[:, 2:12].copy(), vr=a[:, 12:22].copy())
+    return out
 
 
 def save_checkpoint(state: dict, is_best: bool, filename: str = "checkpoint.pth.tar") -> None:

@@ -80,6 +80,15 @@ int cl_assemble_device(cl_loader_t* h, const int32_t* slots, const int16_t* rows
                        uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out,
                        uint8_t* var_mask_out, void* stream);
 
+/* The read tokens at the two columns the training targets count ((window - 1) / 2 and the column after it: 100 and 101 of the
+ * 201-column window) in an assembled reads plane reads[m][rows][window], a device pointer -- cl_assemble_device's reads_out:
+ * counts[i][k][t] (int32 [m][2][16], a device pointer) = rows of site i whose byte at column (window - 1) / 2 + k is t.  Bytes above 15
+ * are not counted.  One wave per site, no global atomics; every element of counts[m][2][16] is written once and nothing else is.
+ * Asynchronous on `stream`. */
+int cl_center_counts_device(cl_loader_t* h, const uint8_t* reads, int64_t m, int32_t rows, int32_t window, int32_t* counts, void* stream);
+/* Its definition on the CPU, same arguments with host pointers: h may be NULL (it only receives the error text), stream is ignored. */
+int cl_center_counts_host(cl_loader_t* h, const uint8_t* reads, int64_t m, int32_t rows, int32_t window, int32_t* counts, void* stream);
+
 /* The last cl_inflate_chunks_device call and the last cl_assemble_device call since: device time between events on the caller's
  * stream, in ms.  (cl_get_stats waits for that assembly.) */
 typedef struct {

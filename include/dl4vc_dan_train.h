@@ -83,6 +83,16 @@ int dan_train_backward(dan_trainer_t* t, const uint8_t* reads, const uint8_t* qu
 int dan_train_backward_begin(dan_trainer_t* t, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand,
                              const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int64_t n_sites,
                              const dan_train_targets* targets, const uint8_t* const* dropout_masks, uint64_t seed);
+/* dan_train_backward_begin for planes that are in device memory already (a loader assembled them there): the six plane arguments
+ * are DEVICE pointers, everything else is as above -- targets and dropout masks stay host arrays and go through the same staging,
+ * the same entry checks and errors apply, and the step behind the inputs is the same code.  The trainer's stream copies the planes
+ * into its input buffer (device to device) before the call returns control of them to the stream order: ready_event (a
+ * hipEvent_t, may be NULL) is what that stream waits for first -- the event the loader recorded behind its assembly.  The planes
+ * may be overwritten once dan_train_backward_end has returned. */
+int dan_train_backward_begin_device(dan_trainer_t* t, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand,
+                                    const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int64_t n_sites,
+                                    const dan_train_targets* targets, const uint8_t* const* dropout_masks, uint64_t seed,
+                                    void* ready_event);
 int dan_train_wait_bucket(dan_trainer_t* t, int32_t bucket);
 int dan_train_backward_end(dan_trainer_t* t, float* losses, uint8_t* close);
 int dan_train_grad_bucket(dan_trainer_t* t, int32_t bucket, int64_t* offset, int64_t* count);

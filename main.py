@@ -43,14 +43,25 @@ def train_main(args, argv) -> int:
     if args.precision != "fp32":
         raise SystemExit("training runs in fp32 only")
     from dl4vc_amd.config import DanConfig
+    device_loader = args.train_loader_device == "gpu"
+    if device_loader:
+        # a file the device loader cannot take is refused before anything starts, with the device loader's own reasons
+        from dl4vc_amd.chunk_loader import check_layout
+        from dl4vc_amd.hdf5io import RawChunkFile
+        try:
+            for path in (args.train_file, args.test_file):
+                with RawChunkFile(path) as raw:
+                    check_layout(raw, DanConfig.from_args(args).reads)
+        except (ValueError, RuntimeError, OSError, KeyError) as e:
+            raise SystemExit("--train-loader-device gpu: %s" % e)
+        # the loader shares device buffers and streams with torch: torch's HIP runtime has to be the process's only one, so it
+        # is loaded before libdl4vc_dan.so brings in its own (as on --test_bam)
+        import torch
+        if args.gpus <= 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            if not torch.cuda.is_available():
+                raise SystemExit("--train-loader-device gpu needs a HIP device visible to torch; there is no CPU path")
     from dl4vc_amd.train import DanTrainer, TrainHyper
-    from dl4vc_amd.trainer import train_epoch, evaluate, save_checkpoint, checkpoint_state
-    from dl4vc_amd.train_data import EasyExampleSampler
-    from dl4vc_amd.hdf5io import CandidateFile
-    from dl4vc_amd.model import DanNet, load_checkpoint
-    from dl4vc_amd.vcf import start_scored_vcf, scored_vcf_path
-    from dl4vc_amd.inference import select_sites
-    from dl4vc_amd.shard import check_replicas_agree
+    from dl4vc_amd.model import load_checkpoint
     from dl4vc_amd import synth
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -95,6 +106,9 @@ def train_main(args, argv) -> int:
     cfg = DanConfig.from_args(args)
     hyper = TrainHyper.from_args(args)
     print("Train on %d rank(s); lr %s, batch %d, dropout %s" % (world, hyper.lr, args.batch_size, hyper.dropout))
+    if device_loader:
+        print("--train-loader-device gpu: batches are assembled on the GPU by one loader thread per file; --num-data-workers %d "
+              "starts no worker process" % args.num_data_workers)
     per_rank = -(-args.batch_size // world)
     trainer = DanTrainer(cfg, hyper, max_batch=per_rank, device_id=0)
     if args.modelload:
@@ -102,12 +116,43 @@ def train_main(args, argv) -> int:
         trainer.load_state_dict(load_checkpoint(args.modelload))
     else:
         trainer.load_state_dict(synth.torch_default_init(cfg, seed=args.seed, dropout_keys=hyper.dropout > 0))
+    from dl4vc_amd.train_data import BatchPrefetcher, DeviceBatchPrefetcher
+    from dl4vc_amd.train_data import BatchError
+
+    def open_loader(path, batch_sites):
+        # loader workers (main.py:59-60: DataLoader(num_workers=args.num_data_workers)); 0 = assemble in this process
+        if not device_loader:
+            return BatchPrefetcher(path, args.num_data_workers)
+        try:
+            return DeviceBatchPrefetcher(path, cfg.reads, batch_sites, device=0, use_q=cfg.use_q, use_strand=cfg.use_strand)
+        except (ValueError, RuntimeError) as e:
+            raise SystemExit("--train-loader-device gpu: %s" % e)
+
+    try:
+        train_loop(args, cfg, hyper, trainer, open_loader, per_rank, rank, world, dist, all_reduce, gather, exchange)
+    except BatchError as e:
+        # a damaged chunk or a record the loader refuses: the reason, not a traceback (under --gpus N the parent ends the other
+        # ranks as soon as this one has exited, ``procs.wait_children``)
+        raise SystemExit("--train-loader-device gpu: %s" % e)
+    trainer.close()
+    if dist is not None:
+        dist.destroy_process_group()
+    return 0
+
+
+def train_loop(args, cfg, hyper, trainer, open_loader, per_rank, rank, world, dist, all_reduce, gather, exchange) -> None:
+    """The epochs of ``train_main``: train, decay the learning rate, evaluate, save."""
+    import numpy as np
+    from dl4vc_amd.trainer import train_epoch, evaluate, save_checkpoint, checkpoint_state
+    from dl4vc_amd.train_data import EasyExampleSampler
+    from dl4vc_amd.hdf5io import CandidateFile
+    from dl4vc_amd.model import DanNet
+    from dl4vc_amd.vcf import start_scored_vcf, scored_vcf_path
+    from dl4vc_amd.inference import select_sites
+    from dl4vc_amd.shard import check_replicas_agree
     best_loss = None
-    from dl4vc_amd.train_data import BatchPrefetcher
-    # loader workers (main.py:59-60: DataLoader(num_workers=args.num_data_workers)); 0 = assemble in this process
     with CandidateFile(args.train_file) as train_src, CandidateFile(args.test_file) as test_src, \
-            BatchPrefetcher(args.train_file, args.num_data_workers) as train_loader, \
-            BatchPrefetcher(args.test_file, args.num_data_workers) as test_loader:
+            open_loader(args.train_file, per_rank) as train_loader, open_loader(args.test_file, args.test_batch_size) as test_loader:
         holdout = None
         if args.train_holdout_chromosomes:
             holdout = np.zeros(len(train_src), bool)
@@ -205,10 +250,10 @@ def train_main(args, argv) -> int:
             print("\tTime elapsed overall {:.4f}\n".format(time.time() - s), flush=True)
             if dist is not None:
                 dist.barrier()
-    trainer.close()
-    if dist is not None:
-        dist.destroy_process_group()
-    return 0
+        for name, l in (("training", train_loader), ("evaluation", test_loader)):
+            if hasattr(l, "stage") and rank == 0:
+                print("device loader (%s file): %s" % (name, ", ".join("%s %s" % (k, ("%.1f" % v) if k.endswith("_ms") else int(v))
+                                                                          for k, v in l.stage.items())))
 
 
 GPUS_WITH_BAM = ("--test_bam runs on one GPU: a shard's read subsets are seeded with the index of its first RECORD, which needs the "
@@ -293,6 +338,15 @@ def score_bam_census(args, net, target, out_final, shard_i, shard_n, holdout, si
     return n
 
 
+def check_train_loader_device_arguments(args) -> None:
+    """--train-loader-device: what it refuses (the files' own properties are checked when training starts)."""
+    if args.train_loader_device != "gpu":
+        raise SystemExit("--train-loader-device must be gpu")
+    if not args.train_file:
+        raise SystemExit("--train-loader-device gpu is an option of --train_file (it assembles the training and evaluation batches "
+                         "on the GPU); inference from a --test_file has --loader-device gpu")
+
+
 def check_loader_device_arguments(args) -> None:
     """--loader-device: what it refuses (the file's own properties are checked when it is opened)."""
     if args.loader_device != "gpu":
@@ -319,6 +373,8 @@ def main(argv=None) -> int:
                          "record); the records of a --test_file are already counted")
     if args.loader_device is not None:
         check_loader_device_arguments(args)
+    if args.train_loader_device is not None:
+        check_train_loader_device_arguments(args)
     if args.test_bam:
         check_bam_arguments(args)
     if args.train_file:
