@@ -19,6 +19,8 @@
 namespace bamn {
 
 // ---- BGZF -------------------------------------------------------------------------------------------------------------------------
+constexpr const char* BAD_BLOCK = "BGZF block fails its CRC / size check";   // the host reader's refusal; the device path adds the status
+
 struct Bgzf {
     FILE* f = nullptr;                                           // owned: closed with the reader (also when an exception unwinds past it)
     Bgzf() = default;
@@ -64,7 +66,7 @@ struct Bgzf {
         const int rc = inflate(&zs, Z_FINISH);
         const bool ok = rc == Z_STREAM_END && zs.total_out == isize;
         inflateEnd(&zs);
-        if (!ok || (uint32_t)crc32(0L, isize ? data.data() : scratch, isize) != crc) { err = "BGZF block fails its CRC / size check"; return false; }
+        if (!ok || (uint32_t)crc32(0L, isize ? data.data() : scratch, isize) != crc) { err = BAD_BLOCK; return false; }
         block_start = file_off; next_block = file_off + bsize + 1; off = 0;
         return true;
     }

@@ -5,12 +5,11 @@
 // With -DBZ_HOST_ONLY a plain C++ compiler builds the host entry alone (tools/asan_bgzf.sh runs it under sanitizers).
 #ifdef BZ_HOST_ONLY
 #include "bgzf_inflate.h"
+#include "capi_shell.h"
 #else
 #include "bgzf_device.h"
 #endif
 
-#include <cstdarg>
-#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -18,15 +17,8 @@ namespace {
 
 thread_local std::string g_bz_err;
 
-int bz_fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_bz_err = buf;
-    return code;
-}
+template <class... A>
+int bz_fail(int code, const char* fmt, A... a) { return capi::failf(g_bz_err, code, fmt, a...); }
 
 // the block table of a call: headers and trailers validated, slots checked against out_cap
 int make_table(const uint8_t* blocks, uint64_t nbytes, const uint64_t* block_off, int64_t n, uint64_t out_cap, const uint64_t* out_off,
@@ -41,13 +33,6 @@ int make_table(const uint8_t* blocks, uint64_t nbytes, const uint64_t* block_off
     }
     return 0;
 }
-
-#ifndef BZ_HOST_ONLY
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem() { if (p) (void)hipFree(p); }
-};
-#endif
 
 }  // namespace
 
@@ -76,7 +61,7 @@ const char* bz_status_text(int status) {
 
 int bz_inflate_host(const uint8_t* blocks, uint64_t nbytes, const uint64_t* block_off, int64_t n_blocks, uint8_t* out, uint64_t out_cap,
                     const uint64_t* out_off, int32_t* status) {
-    try {
+    return capi::guarded(g_bz_err, "bz_inflate_host", [&] {
         if (n_blocks > 0 && (!out || !status)) return bz_fail(-1, "bz_inflate_host: null argument");
         std::vector<bz::BlockDesc> tab;
         const int rc = make_table(blocks, nbytes, block_off, n_blocks, out_cap, out_off, tab);
@@ -86,49 +71,38 @@ int bz_inflate_host(const uint8_t* blocks, uint64_t nbytes, const uint64_t* bloc
         std::vector<bz::Tables> t(1);
         for (int64_t i = 0; i < n_blocks; ++i) status[i] = bz::inflate_block_host(blocks, tab[i], out, t[0], table);
         return 0;
-    } catch (const std::exception& e) {
-        return bz_fail(-4, "bz_inflate_host: %s", e.what());
-    } catch (...) {
-        return bz_fail(-4, "bz_inflate_host: unknown exception");
-    }
+    });
 }
 
 #ifndef BZ_HOST_ONLY
 int bz_inflate(const uint8_t* blocks, uint64_t nbytes, const uint64_t* block_off, int64_t n_blocks, uint8_t* out, uint64_t out_cap,
                const uint64_t* out_off, int32_t* status, int device) {
-    try {
+    return capi::guarded(g_bz_err, "bz_inflate", [&] {
         if (n_blocks > 0 && (!out || !status)) return bz_fail(-1, "bz_inflate: null argument");
         if (n_blocks > (int64_t)1 << 30) return bz_fail(-1, "bz_inflate: too many blocks in one call");
         std::vector<bz::BlockDesc> tab;
         const int rc = make_table(blocks, nbytes, block_off, n_blocks, out_cap, out_off, tab);
         if (rc) return rc;
         if (n_blocks == 0) return 0;
-#define BZ_TRY(x)                                                                                       \
-    do {                                                                                                \
-        const hipError_t e_ = (x);                                                                      \
-        if (e_ != hipSuccess) return bz_fail(-2, "bz_inflate: %s: %s", #x, hipGetErrorString(e_));      \
-    } while (0)
+#define BZ_TRY(x) DEV_TRY(g_bz_err, "bz_inflate: ", x)
         BZ_TRY(hipSetDevice(device));
-        DevMem d_comp, d_tab, d_out, d_status;
-        BZ_TRY(hipMalloc(&d_comp.p, nbytes + 16));
-        BZ_TRY(hipMalloc(&d_tab.p, tab.size() * sizeof(bz::BlockDesc)));
-        BZ_TRY(hipMalloc(&d_out.p, out_cap + 16));
-        BZ_TRY(hipMalloc(&d_status.p, (size_t)n_blocks * sizeof(int32_t)));
+        dev::Buffer d_comp, d_out;
+        dev::Array<bz::BlockDesc> d_tab;
+        dev::Array<int32_t> d_status;
+        BZ_TRY(d_comp.alloc(nbytes + 16));
+        BZ_TRY(d_tab.alloc(tab.size()));
+        BZ_TRY(d_out.alloc(out_cap + 16));
+        BZ_TRY(d_status.alloc((size_t)n_blocks));
         BZ_TRY(hipMemcpy(d_comp.p, blocks, nbytes, hipMemcpyHostToDevice));
         BZ_TRY(hipMemcpy(d_tab.p, tab.data(), tab.size() * sizeof(bz::BlockDesc), hipMemcpyHostToDevice));
         if (out_cap) BZ_TRY(hipMemcpy(d_out.p, out, out_cap, hipMemcpyHostToDevice));   // (what no slot covers comes back as it went)
-        BZ_TRY(bz::launch_inflate((const uint8_t*)d_comp.p, (const bz::BlockDesc*)d_tab.p, n_blocks, (uint8_t*)d_out.p,
-                                  (int32_t*)d_status.p, nullptr));
+        BZ_TRY(bz::launch_inflate(d_comp.p, d_tab.p, n_blocks, d_out.p, d_status.p, nullptr));
         BZ_TRY(hipDeviceSynchronize());
         if (out_cap) BZ_TRY(hipMemcpy(out, d_out.p, out_cap, hipMemcpyDeviceToHost));
         BZ_TRY(hipMemcpy(status, d_status.p, (size_t)n_blocks * sizeof(int32_t), hipMemcpyDeviceToHost));
 #undef BZ_TRY
         return 0;
-    } catch (const std::exception& e) {
-        return bz_fail(-4, "bz_inflate: %s", e.what());
-    } catch (...) {
-        return bz_fail(-4, "bz_inflate: unknown exception");
-    }
+    });
 }
 #endif
 

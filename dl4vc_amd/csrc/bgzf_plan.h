@@ -215,6 +215,12 @@ struct BlockPlan {
         const HostBlock& b = *(it == blocks.begin() ? it : it - 1);
         return (int64_t)((b.coff << 16) | std::min<uint64_t>(off - b.out_off, 0xffff));
     }
+
+    // what every path says of block i of tab when its inflate ends with a status other than BZ_OK
+    std::string bad_block(size_t i, int status) const {
+        return std::string(bamn::BAD_BLOCK) + " (" + bz_status_text(status) + ", block at file offset " +
+               std::to_string(blocks[i].coff) + ")";
+    }
 };
 
 }  // namespace bz

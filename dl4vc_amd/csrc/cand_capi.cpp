@@ -13,13 +13,8 @@
 #include "bgzf_device.h"
 #include "cand_device.h"
 
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <atomic>
 #include <chrono>
-#include <cstdarg>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -30,15 +25,8 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
+template <class... A>
+int fail(int code, const char* fmt, A... a) { return capi::failf(g_err, code, fmt, a...); }
 
 const char BASES[] = "=ACMGRSVTWYHKDBN";
 constexpr int64_t BATCH_BASES = 4000000;     // subregion length gathered per device batch
@@ -52,34 +40,22 @@ struct Gathered {
 
 }  // namespace
 
-struct cg_handle {
+struct cg_handle {   // (members are destroyed last to first: the stream outlives everything that was used on it)
     std::string bam_path;
     bamn::BamFile header;
     bamn::Bai bai;
     bool have_bai = false;
     cg_options opt{};
-    hipStream_t stream = nullptr;
-    cand::Workspace* ws = nullptr;
-    uint8_t* pinned = nullptr;
-    size_t pinned_cap = 0;
+    dev::Stream stream;
+    std::unique_ptr<cand::Workspace, void (*)(cand::Workspace*)> ws{nullptr, cand::workspace_destroy};
+    dev::Pinned pinned;                         // the gathered records of the host framing path
     std::vector<cg_candidate> out;
     // the device inflate path (cg_set_inflate_device)
     bool inflate_device = false;
-    int fd = -1;
-    bz::Framer* framer = nullptr;
-    void *d_comp = nullptr, *d_tab = nullptr, *d_infl = nullptr, *d_bstatus = nullptr;
-    size_t d_comp_cap = 0, d_tab_cap = 0, d_infl_cap = 0, d_bstatus_cap = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bz::InflateStage inflate;
+    std::unique_ptr<bz::Framer, void (*)(bz::Framer*)> framer{nullptr, bz::framer_destroy};
+    dev::Event ev[2];                           // around walk + frame
     cg_inflate_stats ist{};
-    ~cg_handle() {
-        if (fd >= 0) close(fd);
-        bz::framer_destroy(framer);
-        for (void* p : {d_comp, d_tab, d_infl, d_bstatus}) if (p) (void)hipFree(p);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (pinned) (void)hipHostFree(pinned);
-        cand::workspace_destroy(ws);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace {
@@ -146,7 +122,7 @@ int finish_batch(cg_handle* h, const cg_region* regions, int64_t b0, uint64_t n_
     const uint8_t* status = nullptr;
     uint64_t n_out = 0, n_events = 0, n_unique = 0;
     cand::BatchTimes bt{};
-    if (cand::run_batch(h->ws, n_reads, n_subs, cov, h->opt.max_len_indel_allele, h->opt.snp_min_freq, h->opt.indel_min_freq,
+    if (cand::run_batch(h->ws.get(), n_reads, n_subs, cov, h->opt.max_len_indel_allele, h->opt.snp_min_freq, h->opt.indel_min_freq,
                         h->stream, &dc, &n_out, &status, &n_events, &n_unique, &bt, &msg))
         return fail(-2, "device: %s", msg);
     st.device_ms += bt.device_ms;
@@ -215,18 +191,13 @@ int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg
         if (!per[s].err.empty()) return fail(-3, "%s", per[s].err.c_str());
     // the device is set up only now, after the first batch framed cleanly (framing errors need no GPU)
     if (hipSetDevice(h->opt.device) != hipSuccess) return fail(-2, "hipSetDevice(%d) failed", h->opt.device);
-    if (!h->stream && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(-2, "hipStreamCreate failed");
-    if (!h->ws && !(h->ws = cand::workspace_create())) return fail(-2, "cannot create the device workspace");
+    if (h->stream.ensure() != hipSuccess) return fail(-2, "hipStreamCreate failed");
+    if (!h->ws) h->ws.reset(cand::workspace_create());
+    if (!h->ws) return fail(-2, "cannot create the device workspace");
     // gather into the pinned buffer, subregion by subregion
     uint64_t bytes = 0, n_reads = 0;
     for (auto& g : per) { bytes += g.bytes.size(); n_reads += g.meta.size(); }
-    if (bytes + 1 > h->pinned_cap) {
-        if (h->pinned) (void)hipHostFree(h->pinned);
-        h->pinned = nullptr; h->pinned_cap = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        if (hipHostMalloc((void**)&h->pinned, want, hipHostMallocDefault) != hipSuccess) return fail(-2, "hipHostMalloc(%zu) failed", want);
-        h->pinned_cap = want;
-    }
+    if (h->pinned.ensure(bytes + 1) != hipSuccess) return fail(-2, "pinned allocation of %llu bytes failed", (unsigned long long)bytes);
     std::vector<cand::ReadMeta> meta;
     meta.reserve(n_reads);
     std::vector<cand::SubDesc> subs(n_subs);
@@ -239,7 +210,7 @@ int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg
         subs[s].cov_base = cov;
         cov += (int64_t)rg.end - rg.start + 2;
         Gathered& g = per[s];
-        if (!g.bytes.empty()) memcpy(h->pinned + at, g.bytes.data(), g.bytes.size());
+        if (!g.bytes.empty()) memcpy(h->pinned.p + at, g.bytes.data(), g.bytes.size());
         for (auto m : g.meta) { m.off += at; meta.push_back(m); }
         at += g.bytes.size();
         std::vector<uint8_t>().swap(g.bytes);
@@ -247,7 +218,7 @@ int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg
     const auto t1 = std::chrono::steady_clock::now();
     st.host_frame_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
     const char* msg = nullptr;
-    if (cand::upload(h->ws, h->pinned, bytes, meta.data(), n_reads, subs.data(), n_subs, cov, h->stream, &msg))
+    if (cand::upload(h->ws.get(), h->pinned.p, bytes, meta.data(), n_reads, subs.data(), n_subs, cov, h->stream, &msg))
         return fail(-2, "device upload: %s", msg);
     if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(-2, "device upload failed");
     const auto t2 = std::chrono::steady_clock::now();
@@ -256,19 +227,11 @@ int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg
 }
 
 // ---- the device inflate path ---------------------------------------------------------------------------------------------
-bool dev_ensure(void*& p, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (hipMalloc(&p, want) != hipSuccess) return false;
-    cap = want;
-    return true;
-}
-
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
     return std::chrono::duration<double, std::milli>(b - a).count();
 }
+
+#define CG_TRY(x) DEV_TRY(g_err, "device inflate: ", x)
 
 int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg_stats& st) {
     const uint32_t n_subs = (uint32_t)(b1 - b0);
@@ -276,77 +239,43 @@ int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t
     bz::BlockPlan pl;
     std::string perr;
     pl.plan(h->bai, regions + b0, b1 - b0);
-    struct stat sb;
-    if (fstat(h->fd, &sb) != 0) return fail(-3, "BGZF: cannot stat %s", h->bam_path.c_str());
-    if (!pl.spans((uint64_t)sb.st_size, perr)) return fail(-3, "%s", perr.c_str());
-    const uint64_t comp_bytes = pl.comp_bytes;
     if (hipSetDevice(h->opt.device) != hipSuccess) return fail(-2, "hipSetDevice(%d) failed", h->opt.device);
-    if (comp_bytes + 1 > h->pinned_cap) {
-        if (h->pinned) (void)hipHostFree(h->pinned);
-        h->pinned = nullptr; h->pinned_cap = 0;
-        const size_t want = comp_bytes + comp_bytes / 4 + 4096;
-        if (hipHostMalloc((void**)&h->pinned, want, hipHostMallocDefault) != hipSuccess) return fail(-2, "hipHostMalloc(%zu) failed", want);
-        h->pinned_cap = want;
-    }
-    if (!pl.read(h->fd, h->bam_path, h->pinned, perr) || !pl.segments(perr)) return fail(-3, "%s", perr.c_str());
-    const std::vector<bz::BlockDesc>& tab = pl.tab;
-    const std::vector<bz::HostBlock>& blocks = pl.blocks;
-    const std::vector<bz::Segment>& segs = pl.segs;
-    const uint64_t infl_bytes = pl.infl_bytes, n_slots = pl.n_slots;
+    if (const int rc = h->inflate.read(pl, h->bam_path, g_err)) return rc;
+    if (!pl.segments(perr)) return fail(-3, "%s", perr.c_str());
+    const uint64_t infl_bytes = pl.infl_bytes;
     const auto t1 = std::chrono::steady_clock::now();
     st.host_frame_ms += ms_between(t0, t1);
     h->ist.read_ms += ms_between(t0, t1);
-    h->ist.blocks += (int64_t)blocks.size();
-    h->ist.compressed_bytes += (int64_t)comp_bytes;
+    h->ist.blocks += (int64_t)pl.blocks.size();
+    h->ist.compressed_bytes += (int64_t)pl.comp_bytes;
     h->ist.inflated_bytes += (int64_t)infl_bytes;
     // the device
-    if (!h->stream && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(-2, "hipStreamCreate failed");
-    if (!h->ws && !(h->ws = cand::workspace_create())) return fail(-2, "cannot create the device workspace");
-    if (!h->framer) h->framer = bz::framer_create();
-    for (hipEvent_t& e : h->ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) return fail(-2, "hipEventCreate failed");
-    if (!dev_ensure(h->d_comp, h->d_comp_cap, comp_bytes + 16) || !dev_ensure(h->d_tab, h->d_tab_cap, (tab.size() + 1) * sizeof(bz::BlockDesc)) ||
-        !dev_ensure(h->d_infl, h->d_infl_cap, infl_bytes + 16) || !dev_ensure(h->d_bstatus, h->d_bstatus_cap, (tab.size() + 1) * sizeof(int32_t)))
-        return fail(-2, "hipMalloc failed for a batch of %llu compressed and %llu inflated bytes", (unsigned long long)comp_bytes,
-                    (unsigned long long)infl_bytes);
-#define CG_TRY(x)                                                                                 \
-    do {                                                                                          \
-        const hipError_t e_ = (x);                                                                \
-        if (e_ != hipSuccess) return fail(-2, "device inflate: %s: %s", #x, hipGetErrorString(e_)); \
-    } while (0)
-    if (comp_bytes) CG_TRY(hipMemcpyAsync(h->d_comp, h->pinned, comp_bytes, hipMemcpyHostToDevice, h->stream));
-    if (!tab.empty()) CG_TRY(hipMemcpyAsync(h->d_tab, tab.data(), tab.size() * sizeof(bz::BlockDesc), hipMemcpyHostToDevice, h->stream));
+    if (h->stream.ensure() != hipSuccess) return fail(-2, "hipStreamCreate failed");
+    if (!h->ws) h->ws.reset(cand::workspace_create());
+    if (!h->ws) return fail(-2, "cannot create the device workspace");
+    if (!h->framer) h->framer.reset(bz::framer_create());
+    for (dev::Event& e : h->ev)
+        if (e.ensure() != hipSuccess) return fail(-2, "hipEventCreate failed");
+    if (const int rc = h->inflate.upload(pl, h->stream, g_err)) return rc;
     CG_TRY(hipStreamSynchronize(h->stream));
-    const auto t2 = std::chrono::steady_clock::now();
-    st.upload_ms += ms_between(t1, t2);
-    CG_TRY(hipEventRecord(h->ev[0], h->stream));
-    CG_TRY(bz::launch_inflate((const uint8_t*)h->d_comp, (const bz::BlockDesc*)h->d_tab, (int64_t)tab.size(), (uint8_t*)h->d_infl,
-                              (int32_t*)h->d_bstatus, h->stream));
-    CG_TRY(hipEventRecord(h->ev[1], h->stream));
-    std::vector<int32_t> bstatus(tab.size());
-    if (!tab.empty()) CG_TRY(hipMemcpyAsync(bstatus.data(), h->d_bstatus, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    CG_TRY(hipStreamSynchronize(h->stream));
-    for (size_t i = 0; i < tab.size(); ++i)
-        if (bstatus[i] != BZ_OK)
-            return fail(-3, "BGZF block fails its CRC / size check (%s, block at file offset %llu)", bz_status_text(bstatus[i]),
-                        (unsigned long long)blocks[i].coff);
+    st.upload_ms += ms_between(t1, std::chrono::steady_clock::now());
+    if (const int rc = h->inflate.enqueue(pl, h->stream, g_err)) return rc;
+    if (const int rc = h->inflate.finish(pl, h->stream, &h->ist.inflate_ms, g_err)) return rc;
     std::vector<bz::SubRange> sr(n_subs);
     for (uint32_t s = 0; s < n_subs; ++s) sr[s] = bz::SubRange{regions[b0 + s].tid, regions[b0 + s].start, regions[b0 + s].end};
     const cand::ReadMeta* meta_dev = nullptr;
     uint64_t n_reads = 0, n_records = 0, err = bz::NO_ERROR;
     const char* msg = nullptr;
-    CG_TRY(hipEventRecord(h->ev[2], h->stream));
-    if (bz::frame_records(h->framer, (const uint8_t*)h->d_infl, infl_bytes, segs.data(), segs.size(), n_slots, sr.data(), n_subs, h->stream,
-                          &meta_dev, &n_reads, &n_records, &err, &msg))
+    CG_TRY(hipEventRecord(h->ev[0], h->stream));
+    if (bz::frame_records(h->framer.get(), h->inflate.d_infl.p, infl_bytes, pl.segs.data(), pl.segs.size(), pl.n_slots, sr.data(), n_subs,
+                          h->stream, &meta_dev, &n_reads, &n_records, &err, &msg))
         return fail(-2, "device framing: %s", msg);
     if (err != bz::NO_ERROR)
         return fail(-3, "%s (record at virtual offset %lld)", bamn::frame::why_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
-    CG_TRY(hipEventRecord(h->ev[3], h->stream));
+    CG_TRY(hipEventRecord(h->ev[1], h->stream));
     CG_TRY(hipStreamSynchronize(h->stream));
     float ms = 0.f;
     CG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->ist.inflate_ms += ms;
-    CG_TRY(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
     h->ist.walk_frame_ms += ms;
     h->ist.records += (int64_t)n_records;
 #undef CG_TRY
@@ -359,7 +288,7 @@ int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t
         subs[s].cov_base = cov;
         cov += (int64_t)rg.end - rg.start + 2;
     }
-    if (cand::upload_device(h->ws, (const uint8_t*)h->d_infl, meta_dev, subs.data(), n_subs, cov, h->stream, &msg))
+    if (cand::upload_device(h->ws.get(), h->inflate.d_infl.p, meta_dev, subs.data(), n_subs, cov, h->stream, &msg))
         return fail(-2, "device upload: %s", msg);
     return finish_batch(h, regions, b0, n_reads, n_subs, cov, st);
 }
@@ -371,7 +300,7 @@ extern "C" {
 const char* cg_last_error(void) { return g_err.c_str(); }
 
 int cg_open(const char* bam_path, const char* bai_path, const cg_options* opt, cg_handle_t** out) {
-    try {
+    return capi::guarded(g_err, "cg_open", [&] {
         if (!out || !bam_path || !opt) return fail(-1, "cg_open: null argument");
         *out = nullptr;
         if (opt->max_len_indel_allele > CG_MAX_ALLELE_LEN)
@@ -388,15 +317,11 @@ int cg_open(const char* bam_path, const char* bai_path, const cg_options* opt, c
         }
         *out = h.release();
         return 0;
-    } catch (const std::exception& e) {
-        return fail(-4, "cg_open: %s", e.what());
-    } catch (...) {
-        return fail(-4, "cg_open: unknown exception");
-    }
+    });
 }
 
 int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg_candidate** out, int64_t* n_out, cg_stats* stats) {
-    try {
+    return capi::guarded(g_err, "cg_run", [&] {
         if (!h || !out || !n_out || (n_regions > 0 && !regions)) return fail(-1, "cg_run: null argument");
         const auto t0 = std::chrono::steady_clock::now();
         cg_stats st{};
@@ -423,24 +348,18 @@ int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg
         *out = h->out.data();
         *n_out = (int64_t)h->out.size();
         return 0;
-    } catch (const std::exception& e) {
-        return fail(-4, "cg_run: %s", e.what());
-    } catch (...) {
-        return fail(-4, "cg_run: unknown exception");
-    }
+    });
 }
 
 int cg_set_inflate_device(cg_handle_t* h, int on) {
-    try {
+    return capi::guarded(g_err, "cg_set_inflate_device", [&] {
         if (!h) return fail(-1, "cg_set_inflate_device: null handle");
         if (on && !h->have_bai)
             return fail(-1, "inflate on the device needs the BAI index of %s: its bins give the byte ranges to read", h->bam_path.c_str());
-        if (on && h->fd < 0 && (h->fd = open(h->bam_path.c_str(), O_RDONLY)) < 0) return fail(-3, "cannot open %s", h->bam_path.c_str());
+        if (on && !h->inflate.open(h->bam_path)) return fail(-3, "cannot open %s", h->bam_path.c_str());
         h->inflate_device = on != 0;
         return 0;
-    } catch (...) {
-        return fail(-4, "cg_set_inflate_device: unknown exception");
-    }
+    });
 }
 
 int cg_get_inflate_stats(const cg_handle_t* h, cg_inflate_stats* out) {
@@ -451,7 +370,7 @@ int cg_get_inflate_stats(const cg_handle_t* h, cg_inflate_stats* out) {
 
 int cg_debug_ranges(const cg_handle_t* h, int32_t tid, int32_t start, int32_t end, uint64_t* ranges, int64_t cap_ranges, int64_t* n_ranges,
                     uint64_t* bounds, int64_t cap_bounds, int64_t* n_bounds) {
-    try {
+    return capi::guarded(g_err, "cg_debug_ranges", [&] {
         if (!h || !n_ranges || !n_bounds) return fail(-1, "cg_debug_ranges: null argument");
         if (!h->have_bai) return fail(-1, "cg_debug_ranges: the handle has no BAI index");
         const cg_region rg{tid, start, end};
@@ -468,11 +387,7 @@ int cg_debug_ranges(const cg_handle_t* h, int32_t tid, int32_t start, int32_t en
         }
         *n_bounds = nb;
         return 0;
-    } catch (const std::exception& e) {
-        return fail(-4, "cg_debug_ranges: %s", e.what());
-    } catch (...) {
-        return fail(-4, "cg_debug_ranges: unknown exception");
-    }
+    });
 }
 
 int32_t cg_n_refs(const cg_handle_t* h) { return h ? (int32_t)h->header.refs.size() : 0; }

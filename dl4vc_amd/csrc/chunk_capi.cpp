@@ -14,43 +14,25 @@ struct cl_loader : pgh::AssembleState {
     int64_t plane_off[3] = {0, 0, 0};
     int64_t span0 = 0, span1_off = 0, span1 = 0;      // the non-plane members: [0, span0) and [span1_off, span1_off + span1)
     int64_t n_records = 0;                            // of the last cl_inflate_chunks_device call
-    uint8_t* d_comp = nullptr; size_t c_comp = 0;
-    uint8_t* d_records = nullptr;
-    zi::StreamDesc* d_tab = nullptr;
-    int32_t* d_status = nullptr;
-    uint8_t* h_tab = nullptr;                         // pinned: the table, then the statuses
-    uint8_t* h_blob = nullptr;                        // pinned
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // upload | inflate | copy back | ; assemble
+    dev::Buffer d_comp, d_records;
+    dev::Array<zi::StreamDesc> d_tab;
+    dev::Array<int32_t> d_status;
+    dev::Pinned h_tab;                                // the table, then the statuses
+    dev::Pinned h_blob;
+    dev::Event ev[6];                                 // upload | inflate | copy back | ; assemble
     bool assemble_timed = false;
     cl_stats st{};
-    ~cl_loader() {
-        wait_meta();
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        for (void* p : {(void*)d_comp, (void*)d_records, (void*)d_tab, (void*)d_status}) if (p) (void)hipFree(p);
-        if (h_tab) (void)hipHostFree(h_tab);
-        if (h_blob) (void)hipHostFree(h_blob);
-    }
+    ~cl_loader() { wait_meta(); }                     // (the last assembly may still be reading the records)
 };
 
 namespace {
 
 std::string g_cl_err;
 
-int cfail(cl_loader* h, int code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    (h ? h->err : g_cl_err) = buf;
-    return code;
-}
+template <class... A>
+int cfail(cl_loader* h, int code, const char* fmt, A... a) { return capi::failf(h ? h->err : g_cl_err, code, fmt, a...); }
 
-#define CL_TRY(x)                                                                          \
-    do {                                                                                   \
-        const hipError_t e_ = (x);                                                         \
-        if (e_ != hipSuccess) return cfail(h, -2, "%s: %s", #x, hipGetErrorString(e_));    \
-    } while (0)
+#define CL_TRY(x) DEV_TRY(h->err, "", x)
 
 int open_loader(cl_loader* h, int64_t max_records) {
     const int64_t SL = h->plane, W = h->window, rb = h->record_bytes;
@@ -66,13 +48,13 @@ int open_loader(cl_loader* h, int64_t max_records) {
     h->max_chunks = (max_records + h->chunk_records - 1) / h->chunk_records + 1;
     if (h->max_chunks * h->chunk_records > INT32_MAX / 2) return cfail(h, -1, "cl_open: too many records per call");
     CL_TRY(hipSetDevice(h->device));
-    CL_TRY(hipMalloc((void**)&h->d_records, (size_t)h->max_chunks * chunk_bytes + 16));
-    CL_TRY(hipMalloc((void**)&h->d_tab, (size_t)h->max_chunks * sizeof(zi::StreamDesc)));
-    CL_TRY(hipMalloc((void**)&h->d_status, (size_t)h->max_chunks * sizeof(int32_t)));
-    CL_TRY(hipHostMalloc((void**)&h->h_tab, (size_t)h->max_chunks * (sizeof(zi::StreamDesc) + sizeof(int32_t)), hipHostMallocDefault));
-    CL_TRY(hipHostMalloc((void**)&h->h_blob, (size_t)h->max_chunks * h->chunk_records * h->blob_bytes + 16, hipHostMallocDefault));
+    CL_TRY(h->d_records.alloc((size_t)h->max_chunks * chunk_bytes + 16));
+    CL_TRY(h->d_tab.alloc((size_t)h->max_chunks));
+    CL_TRY(h->d_status.alloc((size_t)h->max_chunks));
+    CL_TRY(h->h_tab.alloc((size_t)h->max_chunks * (sizeof(zi::StreamDesc) + sizeof(int32_t))));
+    CL_TRY(h->h_blob.alloc((size_t)h->max_chunks * h->chunk_records * h->blob_bytes + 16));
     // blocking-sync events: the thread that waits for an inflate (tens of ms for a chunk of a megabyte) sleeps instead of spinning
-    for (hipEvent_t& e : h->ev) CL_TRY(hipEventCreateWithFlags(&e, hipEventBlockingSync));
+    for (dev::Event& e : h->ev) CL_TRY(e.ensure(hipEventBlockingSync));
     return 0;
 }
 
@@ -81,14 +63,14 @@ int inflate_chunks(cl_loader* h, const uint8_t* comp, uint64_t nbytes, const uin
     if (n < 0 || n > h->max_chunks) return cfail(h, -1, "cl_inflate_chunks_device: %lld chunks, the handle was opened for %lld",
                                                  (long long)n, (long long)h->max_chunks);
     if (!blob || (n > 0 && (!comp || !off || !len || !status))) return cfail(h, -1, "cl_inflate_chunks_device: null argument");
-    *blob = h->h_blob;
+    *blob = h->h_blob.p;
     h->st = cl_stats{};
     h->assemble_timed = false;
     h->n_records = 0;
     if (n == 0) return 0;
     const uint64_t chunk_bytes = (uint64_t)h->record_bytes * h->chunk_records;
-    zi::StreamDesc* tab = (zi::StreamDesc*)h->h_tab;
-    int32_t* h_status = (int32_t*)(h->h_tab + (size_t)h->max_chunks * sizeof(zi::StreamDesc));
+    zi::StreamDesc* tab = (zi::StreamDesc*)h->h_tab.p;
+    int32_t* h_status = (int32_t*)(h->h_tab.p + (size_t)h->max_chunks * sizeof(zi::StreamDesc));
     for (int64_t c = 0; c < n; ++c) {
         zi::StreamDesc d{};
         d.raw = raw && raw[c] ? 1 : 0;
@@ -99,21 +81,21 @@ int inflate_chunks(cl_loader* h, const uint8_t* comp, uint64_t nbytes, const uin
         h->st.raw_chunks += d.raw;
     }
     CL_TRY(hipSetDevice(h->device));
-    if (!dev::grow(h->d_comp, h->c_comp, (size_t)nbytes + 16)) return cfail(h, -2, "hipMalloc of the chunk buffer failed");
+    if (h->d_comp.ensure((size_t)nbytes + 16) != hipSuccess) return cfail(h, -2, "hipMalloc of the chunk buffer failed");
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_rec = n * h->chunk_records;
     CL_TRY(hipEventRecord(h->ev[0], s));
-    CL_TRY(hipMemcpyAsync(h->d_comp, comp, nbytes, hipMemcpyHostToDevice, s));
-    CL_TRY(hipMemcpyAsync(h->d_tab, tab, (size_t)n * sizeof(zi::StreamDesc), hipMemcpyHostToDevice, s));
+    CL_TRY(hipMemcpyAsync(h->d_comp.p, comp, nbytes, hipMemcpyHostToDevice, s));
+    CL_TRY(hipMemcpyAsync(h->d_tab.p, tab, (size_t)n * sizeof(zi::StreamDesc), hipMemcpyHostToDevice, s));
     CL_TRY(hipEventRecord(h->ev[1], s));
-    CL_TRY(zi::launch_inflate(h->d_comp, h->d_tab, n, h->d_records, h->d_status, s));
+    CL_TRY(zi::launch_inflate(h->d_comp.p, h->d_tab.p, n, h->d_records.p, h->d_status.p, s));
     CL_TRY(hipEventRecord(h->ev[2], s));
     // two spans per record: device pitch = the record, host pitch = the blob
-    CL_TRY(hipMemcpy2DAsync(h->h_blob, (size_t)h->blob_bytes, h->d_records, (size_t)h->record_bytes, (size_t)h->span0, (size_t)n_rec,
+    CL_TRY(hipMemcpy2DAsync(h->h_blob.p, (size_t)h->blob_bytes, h->d_records.p, (size_t)h->record_bytes, (size_t)h->span0, (size_t)n_rec,
                             hipMemcpyDeviceToHost, s));
-    CL_TRY(hipMemcpy2DAsync(h->h_blob + h->span0, (size_t)h->blob_bytes, h->d_records + h->span1_off, (size_t)h->record_bytes,
+    CL_TRY(hipMemcpy2DAsync(h->h_blob.p + h->span0, (size_t)h->blob_bytes, h->d_records.p + h->span1_off, (size_t)h->record_bytes,
                             (size_t)h->span1, (size_t)n_rec, hipMemcpyDeviceToHost, s));
-    CL_TRY(hipMemcpyAsync(h_status, h->d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CL_TRY(hipMemcpyAsync(h_status, h->d_status.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     CL_TRY(hipEventRecord(h->ev[3], s));
     CL_TRY(hipEventSynchronize(h->ev[3]));               // (everything of this call on `s` lies in front of the event)
     float ms[3] = {0, 0, 0};
@@ -146,7 +128,7 @@ int cl_open(int64_t record_bytes, int32_t chunk_records, int32_t window, int32_t
     if (record_bytes < 1 || chunk_records < 1 || window < 1 || stored_rows < 1 || stored_rows > INT16_MAX || max_records < 1 ||
         (int64_t)window * stored_rows > (1 << 24))
         return cfail(nullptr, -1, "cl_open: bad shape");
-    try {
+    return capi::guarded(g_cl_err, "cl_open", [&] {
         cl_loader* h = new cl_loader();
         h->record_bytes = record_bytes; h->chunk_records = chunk_records; h->window = window; h->stored_rows = stored_rows;
         h->plane = (int64_t)window * stored_rows;
@@ -160,11 +142,7 @@ int cl_open(int64_t record_bytes, int32_t chunk_records, int32_t window, int32_t
         }
         *out = h;
         return 0;
-    } catch (const std::exception& e) {
-        return cfail(nullptr, -4, "cl_open: %s", e.what());
-    } catch (...) {
-        return cfail(nullptr, -4, "cl_open: unknown exception");
-    }
+    });
 }
 
 void cl_close(cl_loader_t* h) {
@@ -178,13 +156,9 @@ void cl_close(cl_loader_t* h) {
 int cl_inflate_chunks_device(cl_loader_t* h, const uint8_t* comp, uint64_t nbytes, const uint64_t* off, const uint64_t* len,
                              const uint8_t* raw, int64_t n_chunks, void* stream, const uint8_t** blob, int32_t* status) {
     if (!h) return cfail(nullptr, -1, "cl_inflate_chunks_device: null handle");
-    try {
+    return capi::guarded(h->err, "cl_inflate_chunks_device", [&] {
         return inflate_chunks(h, comp, nbytes, off, len, raw, n_chunks, stream, blob, status);
-    } catch (const std::exception& e) {
-        return cfail(h, -4, "cl_inflate_chunks_device: %s", e.what());
-    } catch (...) {
-        return cfail(h, -4, "cl_inflate_chunks_device: unknown exception");
-    }
+    });
 }
 
 int cl_assemble_device(cl_loader_t* h, const int32_t* slots, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t reads,
@@ -192,8 +166,8 @@ int cl_assemble_device(cl_loader_t* h, const int32_t* slots, const int16_t* rows
                        uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out,
                        uint8_t* var_mask_out, void* stream) {
     if (!h) return cfail(nullptr, -1, "cl_assemble_device: null handle");
-    try {
-        const uint8_t* src[3] = {h->d_records + h->plane_off[0], h->d_records + h->plane_off[1], h->d_records + h->plane_off[2]};
+    return capi::guarded(h->err, "cl_assemble_device", [&] {
+        const uint8_t* src[3] = {h->d_records.p + h->plane_off[0], h->d_records.p + h->plane_off[1], h->d_records.p + h->plane_off[2]};
         hipStream_t s = (hipStream_t)stream;
         const bool timed = m > 0 && hipEventRecord(h->ev[4], s) == hipSuccess;
         const int rc = pgh::assemble(h, "cl_assemble_device", src, h->record_bytes, h->n_records, h->stored_rows, h->window, slots, rows,
@@ -201,25 +175,17 @@ int cl_assemble_device(cl_loader_t* h, const int32_t* slots, const int16_t* rows
                                      ref_out, ref_mask_out, var_mask_out, stream);
         h->assemble_timed = rc == 0 && timed && hipEventRecord(h->ev[5], s) == hipSuccess;
         return rc;
-    } catch (const std::exception& e) {
-        return cfail(h, -4, "cl_assemble_device: %s", e.what());
-    } catch (...) {
-        return cfail(h, -4, "cl_assemble_device: unknown exception");
-    }
+    });
 }
 
 int cl_center_counts_device(cl_loader_t* h, const uint8_t* reads, int64_t m, int32_t rows, int32_t window, int32_t* counts, void* stream) {
     if (!h) return cfail(nullptr, -1, "cl_center_counts_device: null handle");
-    try {
+    return capi::guarded(h->err, "cl_center_counts_device", [&] {
         if (const int rc = counts_arguments(h, "cl_center_counts_device", reads, m, rows, window, counts)) return rc;
         CL_TRY(hipSetDevice(h->device));
         CL_TRY(pg::launch_center_counts(reads, m, rows, window, (window - 1) / 2, counts, (hipStream_t)stream));
         return 0;
-    } catch (const std::exception& e) {
-        return cfail(h, -4, "cl_center_counts_device: %s", e.what());
-    } catch (...) {
-        return cfail(h, -4, "cl_center_counts_device: unknown exception");
-    }
+    });
 }
 
 int cl_center_counts_host(cl_loader_t* h, const uint8_t* reads, int64_t m, int32_t rows, int32_t window, int32_t* counts, void* stream) {

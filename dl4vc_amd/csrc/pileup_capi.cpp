@@ -22,14 +22,9 @@
 #include "pileup_fetch.h"
 #include "zdeflate_device.h"
 
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cstdarg>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -76,10 +71,9 @@ struct Worker {
     std::vector<uint8_t> blk;
 };
 
-using dev::grow;
-
 }  // namespace
 
+// (members are destroyed last to first: the buffers and the kernel-side contexts go before the stream they were used on)
 struct pg_encoder : pgh::AssembleState {   // (err, device and the staging of pg_assemble_device: assemble_host.h)
     std::string bam_path, fasta_path;
     pe_options opt{};
@@ -88,76 +82,40 @@ struct pg_encoder : pgh::AssembleState {   // (err, device and the staging of pg
     bamn::Bai bai;
     bool have_bai = false, scanned = false;
     std::vector<std::unique_ptr<Worker>> workers;
-    hipStream_t stream = nullptr;
-    uint8_t* d_buf = nullptr; size_t c_buf = 0;
-    pg::Rec* d_recs = nullptr; size_t c_recs = 0;
-    pg::Loc* d_locs = nullptr; size_t c_locs = 0;
-    uint8_t* d_ref = nullptr; size_t c_ref = 0;
-    int32_t* d_qpos = nullptr; size_t c_qpos = 0;
-    int32_t* d_indel = nullptr; size_t c_indel = 0;
-    uint8_t* d_isdel = nullptr; size_t c_isdel = 0;
-    uint8_t* d_small = nullptr; size_t c_small = 0;   // ref [B][W] | num [B] i32 | status [B] i8
-    uint8_t* d_planes = nullptr; size_t c_planes = 0; // pg_encode: [3][B][max_reads][W]
-    uint8_t* h_buf = nullptr; size_t hc_buf = 0;      // pinned
-    uint8_t* h_planes = nullptr; size_t hc_planes = 0;
+    dev::Stream stream;
+    dev::Buffer d_buf;
+    dev::Array<pg::Rec> d_recs;
+    dev::Array<pg::Loc> d_locs;
+    dev::Buffer d_ref;
+    dev::Array<int32_t> d_qpos, d_indel;
+    dev::Buffer d_isdel;
+    dev::Buffer d_small;                              // ref [B][W] | num [B] i32 | status [B] i8 (SmallLayout)
+    dev::Buffer d_planes;                             // pg_encode: [3][B][max_reads][W]
+    dev::Pinned h_buf, h_planes;
     pg_stats st{};                                    // stages of the last encode call
     bool census = false;                              // the call in progress is pg_census: statuses only, no plane is written
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    dev::Event ev[4];
     // the device inflate path (pg_set_inflate_device)
     bool inflate_device = false;
     uint64_t max_inflated = DEFAULT_INFLATED;
-    int fd = -1;
-    bz::Framer* walker = nullptr;
-    pg::Framing* framing = nullptr;
-    uint8_t* d_comp = nullptr; size_t c_comp = 0;
-    bz::BlockDesc* d_tab = nullptr; size_t c_tab = 0;
-    uint8_t* d_infl = nullptr; size_t c_infl = 0;
-    int32_t* d_bstatus = nullptr; size_t c_bstatus = 0;
+    bz::InflateStage inflate;
+    std::unique_ptr<bz::Framer, void (*)(bz::Framer*)> walker{nullptr, bz::framer_destroy};
+    std::unique_ptr<pg::Framing, void (*)(pg::Framing*)> framing{nullptr, pg::framing_destroy};
     // pg_compress_records_device: the compressor's buffers, the packed chunk image, the streams, the blob and slots (device and
     // pinned staging), the pinned bytes handed to the caller
-    zd::Ctx* zctx = nullptr;
+    std::unique_ptr<zd::Ctx, void (*)(zd::Ctx*)> zctx{nullptr, zd::ctx_destroy};
     bool compress_dynamic = false;              // pg_set_compress_codes
     std::vector<uint8_t> seg_kind;
-    uint8_t* d_image = nullptr; size_t c_image = 0;
-    uint8_t* d_zout = nullptr; size_t c_zout = 0;
-    uint8_t* d_blob = nullptr; size_t c_blob = 0;
-    uint8_t* h_blob = nullptr; size_t hc_blob = 0;
-    uint8_t* h_zout = nullptr; size_t hc_zout = 0;
-    hipEvent_t zev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~pg_encoder() {
-        zd::ctx_destroy(zctx);
-        for (hipEvent_t e : zev) if (e) (void)hipEventDestroy(e);
-        for (void* p : {(void*)d_image, (void*)d_zout, (void*)d_blob}) if (p) (void)hipFree(p);
-        if (h_blob) (void)hipHostFree(h_blob);
-        if (h_zout) (void)hipHostFree(h_zout);
-        if (fd >= 0) close(fd);
-        bz::framer_destroy(walker);
-        pg::framing_destroy(framing);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        for (void* p : {(void*)d_comp, (void*)d_tab, (void*)d_infl, (void*)d_bstatus}) if (p) (void)hipFree(p);
-        wait_meta();                                      // (the last assembly may still be reading its staging)
-        for (void* p : {(void*)d_buf, (void*)d_recs, (void*)d_locs, (void*)d_ref, (void*)d_qpos, (void*)d_indel, (void*)d_isdel,
-                        (void*)d_small, (void*)d_planes})
-            if (p) (void)hipFree(p);
-        if (h_buf) (void)hipHostFree(h_buf);
-        if (h_planes) (void)hipHostFree(h_planes);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    dev::Buffer d_image, d_zout, d_blob;
+    dev::Pinned h_blob, h_zout;
+    dev::Event zev[5];
+    ~pg_encoder() { wait_meta(); }              // (the last assembly may still be reading its staging and the planes)
 };
 
 namespace {
 
-int fail(pg_encoder* h, int code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    (h ? h->err : pgh::g_err) = buf;
-    return code;
-}
-
-using pgh::pinned_grow;
+template <class... A>
+int fail(pg_encoder* h, int code, const char* fmt, A... a) { return capi::failf(h ? h->err : pgh::g_err, code, fmt, a...); }
 
 int get_tid(const bamn::BamFile& b, const std::string& name) {
     auto it = b.tid_of.find(name);
@@ -212,6 +170,13 @@ void fetch_run(pg_encoder* h, bamn::BamFile& bam, fastan::Fasta& fasta, std::vec
     pgh::fetch_records(h->bai, bam, blk, run.tid, run.s0, run.stop, run);
 }
 
+// the fetch window of the location at pos1 (1-based): bases [s0, stop), the location's own column at ci
+struct Window { int64_t s0, stop; int32_t ci; };
+Window loc_window(int32_t pos1, int w) {
+    const int64_t s0 = std::max<int64_t>((int64_t)pos1 - (w + 2), 0);
+    return Window{s0, (int64_t)pos1 + w + 3, (int32_t)(pos1 - 1 - s0)};
+}
+
 // The runs of sorted entries [b0, b1), appended to runs: locations closer than RUN_GAP, at most RUN_SPAN bases, one contig name.
 void build_runs(const pe_options& o, const char* const* contigs, const std::vector<Entry>& es, int64_t b0, int64_t b1, std::vector<Run>& runs) {
     const int w = o.window_size;
@@ -219,7 +184,8 @@ void build_runs(const pe_options& o, const char* const* contigs, const std::vect
     for (int64_t i = b0; i < b1; ++i) {
         const Entry& e = es[i];
         if (e.pre >= 0) continue;
-        const int64_t s0 = std::max<int64_t>((int64_t)e.pos1 - (w + 2), 0), stop = (int64_t)e.pos1 + w + 3;
+        const Window v = loc_window(e.pos1, w);
+        const int64_t s0 = v.s0, stop = v.stop;
         if (runs.size() > first) {
             Run& r = runs.back();
             if (r.e1 == i && r.tid == e.tid && strcmp(r.contig, contigs[e.idx]) == 0 && s0 <= r.stop + RUN_GAP && stop - r.s0 <= RUN_SPAN) {
@@ -276,10 +242,73 @@ int thread_count(size_t jobs) {
     return std::max(1, std::min<int>({MAX_THREADS, (int)std::max(1u, std::thread::hardware_concurrency()), (int)jobs}));
 }
 
-// Encodes sorted entries [b0, b1) on h->stream.  Planes go to (reads, qual, strand) at slot = entry.idx when `by_index`,
-// else at slot = position in the batch; ref / num / status of the batch are left in h->d_small.
-int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& es, int64_t b0, int64_t b1, uint8_t* reads,
-                 uint8_t* qual, uint8_t* strand, bool by_index) {
+struct Outs {
+    uint8_t *reads, *qual, *strand, *ref;
+    int32_t* num;
+    int8_t* status;
+    bool device_planes;   // the planes are the caller's device arrays, written at slot = entry.idx; else the encoder's own, at the
+                          // position in the batch, and copied back
+};
+
+// where the kernel writes a batch's three planes
+struct Planes { uint8_t *R, *Q, *S; };
+Planes batch_planes(pg_encoder* h, const Outs& out) {
+    const size_t stride = (size_t)h->opt.max_reads * (2 * h->opt.window_size + 1) * BATCH_LOCS;
+    uint8_t* own = h->d_planes.p;
+    return out.device_planes ? Planes{out.reads, out.qual, out.strand} : Planes{own, own + stride, own + 2 * stride};
+}
+
+// d_small of a batch of nb locations: ref [nb][W] at 0 | num [nb] i32 | status [nb] i8
+struct SmallLayout {
+    size_t num, status, bytes;
+    SmallLayout(int64_t nb, int W) : num(((size_t)nb * W + 3) & ~(size_t)3), status(num + (size_t)nb * 4), bytes(status + (size_t)nb) {}
+};
+
+// The location table of sorted entries [b0, b0 + nb): slot and pre.  An entry that place_loc() does not reach lies in no run of
+// the batch: its status is decided already, or it is declined.
+std::vector<pg::Loc> loc_table(const std::vector<Entry>& es, int64_t b0, int64_t nb, bool by_index) {
+    std::vector<pg::Loc> locs((size_t)nb);
+    for (int64_t i = 0; i < nb; ++i) {
+        const Entry& e = es[b0 + i];
+        locs[i] = pg::Loc{};
+        locs[i].pre = e.pre >= 0 ? e.pre : 2;
+        locs[i].slot = by_index ? e.idx : i;
+    }
+    return locs;
+}
+
+// entry e of a run that begins at base run_s0 and whose reference tokens begin at ref0 of the batch's
+void place_loc(pg::Loc& L, const Entry& e, int w, int64_t ref0, int64_t run_s0) {
+    const Window v = loc_window(e.pos1, w);
+    L.s0 = (int32_t)v.s0; L.stop = (int32_t)v.stop; L.ci = v.ci;
+    L.ref = ref0 + (v.s0 - run_s0);
+    L.pre = e.pre;
+}
+
+// Census or encode of the nb locations in d_locs over the records at (buf, recs), then `end` is recorded and the stream waited for
+// (also after a failure: the pageable uploads in front have then read their host vectors); begin..end is the stage's time.
+hipError_t run_locations(pg_encoder* h, const uint8_t* buf, const pg::Rec* recs, int64_t nb, const Planes& pl, hipEvent_t begin, hipEvent_t end) {
+    const pe_options& o = h->opt;
+    const int w = o.window_size, W = 2 * w + 1;
+    const SmallLayout sl(nb, W);
+    const pg::Params P{w, W, o.max_reads, o.max_insert_length, o.max_insert_length_variant};
+    hipStream_t s = h->stream;
+    int8_t* d_status = (int8_t*)(h->d_small.p + sl.status);
+    hipError_t e = h->census ? pg::launch_census(buf, recs, h->d_locs.p, (int32_t)nb, h->d_ref.p, h->d_qpos.p, h->d_indel.p, h->d_isdel.p, P, d_status, s)
+                             : pg::launch_encode(buf, recs, h->d_locs.p, (int32_t)nb, h->d_ref.p, h->d_qpos.p, h->d_indel.p, h->d_isdel.p, P, pl.R, pl.Q,
+                                                 pl.S, h->d_small.p, (int32_t*)(h->d_small.p + sl.num), d_status, s);
+    if (e == hipSuccess) e = hipEventRecord(end, s);
+    const hipError_t waited = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = waited;
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, begin, end);
+    if (e == hipSuccess) (h->census ? h->st.census_ms : h->st.encode_ms) += ms;
+    return e;
+}
+
+// Encodes sorted entries [b0, b1) on h->stream with the records framed on the host; ref / num / status of the batch are left
+// in h->d_small.
+int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& es, int64_t b0, int64_t b1, const Outs& out) {
     const pe_options& o = h->opt;
     const int w = o.window_size, W = 2 * w + 1;
     const auto t_host = std::chrono::steady_clock::now();
@@ -298,38 +327,28 @@ int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& 
     int64_t n_res = 0;
     for (auto& r : runs) { bytes += r.bytes.size(); n_recs += r.recs.size(); n_ref += r.ref.size(); n_res += r.nres; }
     if (n_res > INT32_MAX || n_recs > INT32_MAX) return fail(h, -1, "batch too large (%lld reference positions of records)", (long long)n_res);
-    if (!pinned_grow(h->h_buf, h->hc_buf, bytes + 4)) return fail(h, -2, "hipHostMalloc(%zu) failed", bytes);
+    if (h->h_buf.ensure(bytes + 4)) return fail(h, -2, "pinned allocation of %zu bytes failed", bytes);
     std::vector<pg::Rec> recs;
     recs.reserve(n_recs);
     std::vector<uint8_t> ref;
     ref.reserve(n_ref);
     const int64_t nb = b1 - b0;
-    std::vector<pg::Loc> locs((size_t)nb);
-    for (int64_t i = 0; i < nb; ++i) {
-        const Entry& e = es[b0 + i];
-        pg::Loc& L = locs[i];
-        L = pg::Loc{};
-        L.pre = e.pre;
-        L.slot = by_index ? e.idx : i;
-    }
+    std::vector<pg::Loc> locs = loc_table(es, b0, nb, out.device_planes);
     size_t at = 0;
     int64_t res = 0;
     for (auto& r : runs) {
         const int32_t rec0 = (int32_t)recs.size();
         const int64_t ref0 = (int64_t)ref.size();
-        if (!r.bytes.empty()) memcpy(h->h_buf + at, r.bytes.data(), r.bytes.size());
+        if (!r.bytes.empty()) memcpy(h->h_buf.p + at, r.bytes.data(), r.bytes.size());
         for (auto m : r.recs) { m.off += at; m.res += (int32_t)res; recs.push_back(m); }   // (res + nres <= INT32_MAX, checked above)
         ref.insert(ref.end(), r.ref.begin(), r.ref.end());
         for (int64_t i = r.e0; i < r.e1; ++i) {
-            const Entry& e = es[i];
             pg::Loc& L = locs[i - b0];
-            const int64_t s0 = std::max<int64_t>((int64_t)e.pos1 - (w + 2), 0), stop = (int64_t)e.pos1 + w + 3;
-            L.s0 = (int32_t)s0; L.stop = (int32_t)stop; L.ci = (int32_t)(e.pos1 - 1 - s0);
-            L.ref = ref0 + (s0 - r.s0);
+            place_loc(L, es[i], w, ref0, r.s0);
             if (!r.sorted) { L.pre = 2; continue; }                // (the stable order by clipped start needs sorted records)
-            auto lower = std::lower_bound(r.recs.begin(), r.recs.end(), s0 - r.max_nref,
+            auto lower = std::lower_bound(r.recs.begin(), r.recs.end(), (int64_t)L.s0 - r.max_nref,
                                           [](const pg::Rec& m, int64_t v) { return (int64_t)m.pos < v; });
-            auto upper = std::lower_bound(r.recs.begin(), r.recs.end(), stop, [](const pg::Rec& m, int64_t v) { return (int64_t)m.pos < v; });
+            auto upper = std::lower_bound(r.recs.begin(), r.recs.end(), (int64_t)L.stop, [](const pg::Rec& m, int64_t v) { return (int64_t)m.pos < v; });
             L.first = rec0 + (int32_t)(lower - r.recs.begin());
             L.last = rec0 + (int32_t)(upper - r.recs.begin());
         }
@@ -342,174 +361,118 @@ int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& 
     h->st.records += (int64_t)recs.size();
     // device
     hipStream_t s = h->stream;
-    const size_t small = (size_t)nb * (W + 4 + 1);
-    if (!grow(h->d_buf, h->c_buf, bytes + 4) || !grow(h->d_recs, h->c_recs, recs.size() + 1) || !grow(h->d_locs, h->c_locs, locs.size() + 1) ||
-        !grow(h->d_ref, h->c_ref, ref.size() + 1) || !grow(h->d_qpos, h->c_qpos, (size_t)res + 1) ||
-        !grow(h->d_indel, h->c_indel, (size_t)res + 1) || !grow(h->d_isdel, h->c_isdel, (size_t)res + 1) ||
-        !grow(h->d_small, h->c_small, small + 16))
+    if (h->d_buf.ensure(bytes + 4) || h->d_recs.ensure(recs.size() + 1) || h->d_locs.ensure(locs.size() + 1) || h->d_ref.ensure(ref.size() + 1) ||
+        h->d_qpos.ensure((size_t)res + 1) || h->d_indel.ensure((size_t)res + 1) || h->d_isdel.ensure((size_t)res + 1) ||
+        h->d_small.ensure(SmallLayout(nb, W).bytes + 16))
         return fail(h, -2, "hipMalloc failed (batch of %lld locations, %zu records)", (long long)nb, recs.size());
-    uint8_t* d_ref_small = h->d_small;
-    int32_t* d_num = (int32_t*)(h->d_small + (((size_t)nb * W + 3) & ~(size_t)3));
-    int8_t* d_status = (int8_t*)(d_num + nb);
     hipError_t rc = hipSuccess;
     auto ok = [&](hipError_t r) { if (rc == hipSuccess) rc = r; };
     ok(hipEventRecord(h->ev[0], s));
-    if (bytes) ok(hipMemcpyAsync(h->d_buf, h->h_buf, bytes, hipMemcpyHostToDevice, s));
-    if (!recs.empty()) ok(hipMemcpyAsync(h->d_recs, recs.data(), recs.size() * sizeof(pg::Rec), hipMemcpyHostToDevice, s));
-    ok(hipMemcpyAsync(h->d_locs, locs.data(), locs.size() * sizeof(pg::Loc), hipMemcpyHostToDevice, s));
-    if (!ref.empty()) ok(hipMemcpyAsync(h->d_ref, ref.data(), ref.size(), hipMemcpyHostToDevice, s));
+    if (bytes) ok(hipMemcpyAsync(h->d_buf.p, h->h_buf.p, bytes, hipMemcpyHostToDevice, s));
+    if (!recs.empty()) ok(hipMemcpyAsync(h->d_recs.p, recs.data(), recs.size() * sizeof(pg::Rec), hipMemcpyHostToDevice, s));
+    ok(hipMemcpyAsync(h->d_locs.p, locs.data(), locs.size() * sizeof(pg::Loc), hipMemcpyHostToDevice, s));
+    if (!ref.empty()) ok(hipMemcpyAsync(h->d_ref.p, ref.data(), ref.size(), hipMemcpyHostToDevice, s));
     ok(hipEventRecord(h->ev[1], s));
-    ok(pg::launch_resolve(h->d_buf, h->d_recs, (int32_t)recs.size(), h->d_qpos, h->d_indel, h->d_isdel, s));
-    const pg::Params P{w, W, o.max_reads, o.max_insert_length, o.max_insert_length_variant};
-    if (h->census)
-        ok(pg::launch_census(h->d_buf, h->d_recs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, d_status, s));
-    else
-        ok(pg::launch_encode(h->d_buf, h->d_recs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, reads, qual,
-                             strand, d_ref_small, d_num, d_status, s));
-    ok(hipEventRecord(h->ev[2], s));
-    // (the pageable copies above read the host vectors before this returns)
-    ok(hipStreamSynchronize(s));
+    ok(pg::launch_resolve(h->d_buf.p, h->d_recs.p, (int32_t)recs.size(), h->d_qpos.p, h->d_indel.p, h->d_isdel.p, s));
+    ok(run_locations(h, h->d_buf.p, h->d_recs.p, nb, batch_planes(h, out), h->ev[1], h->ev[2]));
     float ms = 0.f;
     if (rc == hipSuccess && hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->st.upload_ms += ms;
-    if (rc == hipSuccess && hipEventElapsedTime(&ms, h->ev[1], h->ev[2]) == hipSuccess) (h->census ? h->st.census_ms : h->st.encode_ms) += ms;
     if (rc != hipSuccess) return fail(h, -2, "device: %s", hipGetErrorString(rc));
     return 0;
 }
 
 // Copies ref / num / status (and, unless the planes are the caller's device arrays, the planes) of the piece [i0, i1) of the
 // sorted entries, which the encode kernel left at the piece's slots, to the caller's arrays.
-int copy_back(pg_encoder* h, const std::vector<Entry>& es, int64_t i0, int64_t i1, uint8_t* reads, uint8_t* qual, uint8_t* strand,
-              uint8_t* ref_out, int32_t* num_out, int8_t* status_out, bool device_planes, std::vector<uint8_t>& small) {
+int copy_back(pg_encoder* h, const std::vector<Entry>& es, int64_t i0, int64_t i1, const Outs& out, std::vector<uint8_t>& small) {
     const int W = 2 * h->opt.window_size + 1;
     const size_t plane = (size_t)h->opt.max_reads * W;
     const int64_t nb = i1 - i0;
-    const size_t small_bytes = (((size_t)nb * W + 3) & ~(size_t)3) + (size_t)nb * 5;
-    small.resize(small_bytes);
-    if (h->census) {                                       // (census_locations wrote the statuses alone)
-        const size_t at = small_bytes - (size_t)nb;
-        if (nb && hipMemcpy(small.data() + at, h->d_small + at, (size_t)nb, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, -2, "hipMemcpy failed");
-        for (int64_t i = 0; i < nb; ++i) status_out[es[i0 + i].idx] = (int8_t)small[at + i];
+    const SmallLayout sl(nb, W);
+    small.resize(sl.bytes);
+    // (census_locations wrote the statuses alone)
+    const size_t from = h->census ? sl.status : 0;
+    if (sl.bytes > from && hipMemcpy(small.data() + from, h->d_small.p + from, sl.bytes - from, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(h, -2, "hipMemcpy failed");
+    const int32_t* num = (const int32_t*)(small.data() + sl.num);
+    const int8_t* st = (const int8_t*)(small.data() + sl.status);
+    if (h->census) {
+        for (int64_t i = 0; i < nb; ++i) out.status[es[i0 + i].idx] = st[i];
         return 0;
     }
-    if (hipMemcpy(small.data(), h->d_small, small_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, -2, "hipMemcpy failed");
-    const int32_t* num = (const int32_t*)(small.data() + (((size_t)nb * W + 3) & ~(size_t)3));
-    const int8_t* st = (const int8_t*)(num + nb);
-    if (!device_planes) {
+    if (!out.device_planes) {
         const auto t0 = std::chrono::steady_clock::now();
         for (int c = 0; c < 3; ++c)
-            if (hipMemcpy(h->h_planes + c * plane * BATCH_LOCS, h->d_planes + c * plane * BATCH_LOCS, plane * nb, hipMemcpyDeviceToHost) != hipSuccess)
+            if (hipMemcpy(h->h_planes.p + c * plane * BATCH_LOCS, h->d_planes.p + c * plane * BATCH_LOCS, plane * nb, hipMemcpyDeviceToHost) != hipSuccess)
                 return fail(h, -2, "hipMemcpy failed");
         h->st.copy_back_ms += ms_since(t0);
     }
     for (int64_t i = 0; i < nb; ++i) {
         const int64_t j = es[i0 + i].idx;
-        status_out[j] = st[i];
-        num_out[j] = num[i];
-        memcpy(ref_out + (size_t)j * W, small.data() + (size_t)i * W, W);
-        if (!device_planes)
+        out.status[j] = st[i];
+        out.num[j] = num[i];
+        memcpy(out.ref + (size_t)j * W, small.data() + (size_t)i * W, W);
+        if (!out.device_planes)
             for (int c = 0; c < 3; ++c) {
-                uint8_t* dst = c == 0 ? reads : c == 1 ? qual : strand;
-                memcpy(dst + (size_t)j * plane, h->h_planes + c * plane * BATCH_LOCS + (size_t)i * plane, plane);
+                uint8_t* dst = c == 0 ? out.reads : c == 1 ? out.qual : out.strand;
+                memcpy(dst + (size_t)j * plane, h->h_planes.p + c * plane * BATCH_LOCS + (size_t)i * plane, plane);
             }
     }
     return 0;
 }
 
 // ---- the device inflate path (pg_set_inflate_device) ------------------------------------------------------------------------
-#define PG_TRY(x)                                                                                     \
-    do {                                                                                              \
-        const hipError_t e_ = (x);                                                                    \
-        if (e_ != hipSuccess) return fail(h, -2, "device inflate: %s: %s", #x, hipGetErrorString(e_)); \
-    } while (0)
+#define PG_TRY(x) DEV_TRY(h->err, "device inflate: ", x)
 
 // Encodes the piece [i0, i1) of the sorted entries (at most BATCH_LOCS) from the group's records on the device; runs
 // [ra, rb) are the group's runs that lie in the piece (g0: the group's first run).
 int encode_piece(pg_encoder* h, const std::vector<Entry>& es, int64_t i0, int64_t i1, const std::vector<Run>& runs, size_t ra, size_t rb,
-                 size_t g0, size_t g1, const pg::Rec* d_grecs, const pg::RunOut* d_run_out, uint8_t* reads, uint8_t* qual, uint8_t* strand,
-                 bool by_index) {
-    const pe_options& o = h->opt;
-    const int w = o.window_size, W = 2 * w + 1;
+                 size_t g0, size_t g1, const pg::Rec* d_grecs, const pg::RunOut* d_run_out, const Outs& out) {
+    const int w = h->opt.window_size, W = 2 * w + 1;
     const int64_t nb = i1 - i0;
-    std::vector<pg::Loc> locs((size_t)nb);
+    std::vector<pg::Loc> locs = loc_table(es, i0, nb, out.device_planes);
     std::vector<int32_t> loc_run((size_t)nb, -1);
     std::vector<uint8_t> ref;
-    for (int64_t i = 0; i < nb; ++i) {
-        const Entry& e = es[i0 + i];
-        pg::Loc& L = locs[i];
-        L = pg::Loc{};
-        L.pre = e.pre >= 0 ? e.pre : 2;                    // (an entry of no run of this piece has its status already)
-        L.slot = by_index ? e.idx : i;
-    }
     for (size_t r = ra; r < rb; ++r) {
         const Run& run = runs[r];
         const int64_t ref0 = (int64_t)ref.size();
         ref.insert(ref.end(), run.ref.begin(), run.ref.end());
         for (int64_t i = run.e0; i < run.e1; ++i) {
-            const Entry& e = es[i];
-            pg::Loc& L = locs[i - i0];
-            const int64_t s0 = std::max<int64_t>((int64_t)e.pos1 - (w + 2), 0), stop = (int64_t)e.pos1 + w + 3;
-            L.s0 = (int32_t)s0; L.stop = (int32_t)stop; L.ci = (int32_t)(e.pos1 - 1 - s0);
-            L.ref = ref0 + (s0 - run.s0);
-            L.pre = e.pre;
+            place_loc(locs[i - i0], es[i], w, ref0, run.s0);
             loc_run[i - i0] = (int32_t)(r - g0);
         }
     }
     hipStream_t s = h->stream;
-    const size_t small = (size_t)nb * (W + 4 + 1);
-    if (!grow(h->d_locs, h->c_locs, locs.size() + 1) || !grow(h->d_ref, h->c_ref, ref.size() + 1) || !grow(h->d_small, h->c_small, small + 16))
+    if (h->d_locs.ensure(locs.size() + 1) || h->d_ref.ensure(ref.size() + 1) || h->d_small.ensure(SmallLayout(nb, W).bytes + 16))
         return fail(h, -2, "hipMalloc failed (piece of %lld locations)", (long long)nb);
-    uint8_t* d_ref_small = h->d_small;
-    int32_t* d_num = (int32_t*)(h->d_small + (((size_t)nb * W + 3) & ~(size_t)3));
-    int8_t* d_status = (int8_t*)(d_num + nb);
     // device events between the stages, as on the host path: upload | location search | encode
     PG_TRY(hipEventRecord(h->ev[0], s));
-    PG_TRY(hipMemcpyAsync(h->d_locs, locs.data(), locs.size() * sizeof(pg::Loc), hipMemcpyHostToDevice, s));
-    if (!ref.empty()) PG_TRY(hipMemcpyAsync(h->d_ref, ref.data(), ref.size(), hipMemcpyHostToDevice, s));
+    PG_TRY(hipMemcpyAsync(h->d_locs.p, locs.data(), locs.size() * sizeof(pg::Loc), hipMemcpyHostToDevice, s));
+    if (!ref.empty()) PG_TRY(hipMemcpyAsync(h->d_ref.p, ref.data(), ref.size(), hipMemcpyHostToDevice, s));
     const char* msg = nullptr;
-    if (g1 > g0 && pg::locate(h->framing, d_grecs, d_run_out, (int32_t)(g1 - g0), loc_run.data(), h->d_locs, (int32_t)nb, s, &msg, h->ev[1]))
+    if (g1 > g0 && pg::locate(h->framing.get(), d_grecs, d_run_out, (int32_t)(g1 - g0), loc_run.data(), h->d_locs.p, (int32_t)nb, s, &msg, h->ev[1]))
         return fail(h, -2, "device framing: %s", msg);
     if (g1 == g0) PG_TRY(hipEventRecord(h->ev[1], s));
     PG_TRY(hipEventRecord(h->ev[2], s));
-    const pg::Params P{w, W, o.max_reads, o.max_insert_length, o.max_insert_length_variant};
-    if (h->census)
-        PG_TRY(pg::launch_census(h->d_infl, d_grecs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, d_status, s));
-    else
-        PG_TRY(pg::launch_encode(h->d_infl, d_grecs, h->d_locs, (int32_t)nb, h->d_ref, h->d_qpos, h->d_indel, h->d_isdel, P, reads, qual, strand,
-                                 d_ref_small, d_num, d_status, s));
-    PG_TRY(hipEventRecord(h->ev[3], s));
-    PG_TRY(hipStreamSynchronize(s));                       // (the pageable copies above have read the host vectors)
+    PG_TRY(run_locations(h, h->inflate.d_infl.p, d_grecs, nb, batch_planes(h, out), h->ev[2], h->ev[3]));
     float ms = 0.f;
     PG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
     h->st.upload_ms += ms;
     PG_TRY(hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
     h->st.frame_ms += ms;
-    PG_TRY(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
-    (h->census ? h->st.census_ms : h->st.encode_ms) += ms;
     return 0;
 }
-
-struct Outs {
-    uint8_t *reads, *qual, *strand, *ref;
-    int32_t* num;
-    int8_t* status;
-    bool device_planes;
-};
 
 // the pieces of [e0, e1): cut where the BATCH_LOCS batches of the sorted list are cut
 int encode_pieces(pg_encoder* h, const std::vector<Entry>& es, int64_t e0, int64_t e1, const std::vector<Run>& runs, size_t g0, size_t g1,
                   const pg::Rec* d_grecs, const pg::RunOut* d_run_out, const Outs& out, std::vector<uint8_t>& small) {
-    const size_t plane = (size_t)h->opt.max_reads * (2 * h->opt.window_size + 1);
     size_t r = g0;
     for (int64_t i0 = e0; i0 < e1;) {
         const int64_t i1 = std::min<int64_t>(e1, (i0 / BATCH_LOCS + 1) * BATCH_LOCS);
         const size_t ra = r;
         while (r < g1 && runs[r].e1 <= i1) ++r;
-        uint8_t* R = out.device_planes ? out.reads : h->d_planes;
-        uint8_t* Q = out.device_planes ? out.qual : h->d_planes + plane * BATCH_LOCS;
-        uint8_t* S = out.device_planes ? out.strand : h->d_planes + 2 * plane * BATCH_LOCS;
-        int rc = encode_piece(h, es, i0, i1, runs, ra, r, g0, g1, d_grecs, d_run_out, R, Q, S, out.device_planes);
+        int rc = encode_piece(h, es, i0, i1, runs, ra, r, g0, g1, d_grecs, d_run_out, out);
         if (rc) return rc;
-        rc = copy_back(h, es, i0, i1, out.reads, out.qual, out.strand, out.ref, out.num, out.status, out.device_planes, small);
+        rc = copy_back(h, es, i0, i1, out, small);
         if (rc) return rc;
         i0 = i1;
     }
@@ -528,6 +491,7 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
     if (runs.empty()) return encode_pieces(h, es, 0, n, runs, 0, 0, nullptr, nullptr, out, small);
     if (runs.size() > (size_t)INT32_MAX) return fail(h, -1, "too many runs of locations in one call");
     hipStream_t s = h->stream;
+    bz::InflateStage& inf = h->inflate;
     // read: the byte ranges of every run, and the blocks they touch into pinned memory
     const auto t_read = std::chrono::steady_clock::now();
     std::vector<pgh::Region> regs(runs.size());
@@ -535,11 +499,7 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
     bz::BlockPlan all;
     std::string perr;
     all.plan(h->bai, regs.data(), (int64_t)regs.size());
-    struct stat sb;
-    if (fstat(h->fd, &sb) != 0) return fail(h, -3, "BGZF: cannot stat %s", h->bam_path.c_str());
-    if (!all.spans((uint64_t)sb.st_size, perr)) return fail(h, -3, "%s", perr.c_str());
-    if (!pinned_grow(h->h_buf, h->hc_buf, all.comp_bytes + 4)) return fail(h, -2, "hipHostMalloc(%llu) failed", (unsigned long long)all.comp_bytes);
-    if (!all.read(h->fd, h->bam_path, h->h_buf, perr)) return fail(h, -3, "%s", perr.c_str());
+    if (const int rc = inf.read(all, h->bam_path, h->err)) return rc;
     // every run's inflated size, from the trailers of the blocks its own ranges touch
     std::vector<uint64_t> run_bytes(runs.size());
     for (size_t r = 0; r < runs.size(); ++r) {
@@ -549,19 +509,15 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
         run_bytes[r] = one.infl_bytes;
     }
     h->st.read_ms += ms_since(t_read);
-    if (!grow(h->d_comp, h->c_comp, (size_t)all.comp_bytes + 16)) return fail(h, -2, "hipMalloc failed for %llu compressed bytes", (unsigned long long)all.comp_bytes);
-    PG_TRY(hipEventRecord(h->ev[0], s));
-    if (all.comp_bytes) PG_TRY(hipMemcpyAsync(h->d_comp, h->h_buf, all.comp_bytes, hipMemcpyHostToDevice, s));
+    if (const int rc = inf.upload(all, s, h->err, h->ev[0])) return rc;
     PG_TRY(hipEventRecord(h->ev[1], s));
     PG_TRY(hipStreamSynchronize(s));
-    {
-        float ms = 0.f;
-        PG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-        h->st.upload_ms += ms;
-    }
+    float ms = 0.f;
+    PG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    h->st.upload_ms += ms;
     h->st.compressed_bytes += (int64_t)all.comp_bytes;
-    if (!h->walker) h->walker = bz::framer_create();
-    if (!h->framing) h->framing = pg::framing_create();
+    if (!h->walker) h->walker.reset(bz::framer_create());
+    if (!h->framing) h->framing.reset(pg::framing_create());
     const int nt = thread_count(runs.size());
     if (const int rc = ensure_workers(h, nt)) return rc;
     for (size_t g0 = 0; g0 < runs.size();) {
@@ -577,32 +533,18 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
         ++h->st.groups;
         h->st.blocks += (int64_t)pl.tab.size();
         h->st.inflated_bytes += (int64_t)pl.infl_bytes;
-        const size_t nblk = pl.tab.size();
-        if (!grow(h->d_tab, h->c_tab, nblk + 1) || !grow(h->d_infl, h->c_infl, (size_t)pl.infl_bytes + 16) || !grow(h->d_bstatus, h->c_bstatus, nblk + 1))
-            return fail(h, -2, "hipMalloc failed for a group of %llu inflated bytes", (unsigned long long)pl.infl_bytes);
-        if (nblk) PG_TRY(hipMemcpyAsync(h->d_tab, pl.tab.data(), nblk * sizeof(bz::BlockDesc), hipMemcpyHostToDevice, s));
-        PG_TRY(hipEventRecord(h->ev[0], s));
-        PG_TRY(bz::launch_inflate(h->d_comp, h->d_tab, (int64_t)nblk, h->d_infl, h->d_bstatus, s));
-        PG_TRY(hipEventRecord(h->ev[1], s));
-        std::vector<int32_t> bstatus(nblk);
-        if (nblk) PG_TRY(hipMemcpyAsync(bstatus.data(), h->d_bstatus, nblk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (const int rc = inf.enqueue(pl, s, h->err)) return rc;
         // the reference tokens of the group's runs, on the worker threads while the device inflates
         const std::string werr = on_workers(h, nt, g0, g1, [&](Worker* wk, size_t r) { fetch_ref(wk->fasta, runs[r]); });
-        PG_TRY(hipStreamSynchronize(s));
+        const int inflated = inf.finish(pl, s, &h->st.inflate_ms, h->err);
         if (!werr.empty()) return fail(h, -3, "%s", werr.c_str());
-        float ms = 0.f;
-        PG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-        h->st.inflate_ms += ms;
-        for (size_t i = 0; i < nblk; ++i)
-            if (bstatus[i] != BZ_OK)
-                return fail(h, -3, "BGZF block fails its CRC / size check (%s, block at file offset %llu)", bz_status_text(bstatus[i]),
-                            (unsigned long long)pl.blocks[i].coff);
+        if (inflated) return inflated;
         // walk, frame, list per run (both calls wait for their kernels: the events bracket them)
         PG_TRY(hipEventRecord(h->ev[2], s));
         const uint64_t* d_rec_off = nullptr;
         uint64_t n_walked = 0, err = bz::NO_ERROR;
         const char* msg = nullptr;
-        if (bz::walk_records(h->walker, h->d_infl, pl.infl_bytes, pl.segs.data(), pl.segs.size(), pl.n_slots, s, &d_rec_off, &n_walked, &err, &msg))
+        if (bz::walk_records(h->walker.get(), inf.d_infl.p, pl.infl_bytes, pl.segs.data(), pl.segs.size(), pl.n_slots, s, &d_rec_off, &n_walked, &err, &msg))
             return fail(h, -2, "device framing: %s", msg);
         if (err != bz::NO_ERROR)
             return fail(h, -3, "%s (record at virtual offset %lld)", pg::frame::why_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
@@ -611,8 +553,8 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
         pg::Rec* d_grecs = nullptr;
         const pg::RunOut* d_run_out = nullptr;
         int64_t n_recs = 0, n_res = 0;
-        if (pg::frame_runs(h->framing, h->d_infl, d_rec_off, d_rec_off ? pl.n_slots : 0, rd.data(), (int32_t)rd.size(), s, &d_grecs, &n_recs, &n_res,
-                           &d_run_out, &err, &msg))
+        if (pg::frame_runs(h->framing.get(), inf.d_infl.p, d_rec_off, d_rec_off ? pl.n_slots : 0, rd.data(), (int32_t)rd.size(), s, &d_grecs, &n_recs,
+                           &n_res, &d_run_out, &err, &msg))
             return fail(h, -2, "device framing: %s", msg);
         if (err != pg::FRAME_NO_ERROR)
             return fail(h, -3, "%s (record at virtual offset %lld)", pg::frame::why_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
@@ -622,10 +564,10 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
         h->st.frame_ms += ms;
         h->st.records += n_recs;
         if (n_res > INT32_MAX || n_recs > INT32_MAX) return fail(h, -1, "batch too large (%lld reference positions of records)", (long long)n_res);
-        if (!grow(h->d_qpos, h->c_qpos, (size_t)n_res + 1) || !grow(h->d_indel, h->c_indel, (size_t)n_res + 1) || !grow(h->d_isdel, h->c_isdel, (size_t)n_res + 1))
+        if (h->d_qpos.ensure((size_t)n_res + 1) || h->d_indel.ensure((size_t)n_res + 1) || h->d_isdel.ensure((size_t)n_res + 1))
             return fail(h, -2, "hipMalloc failed (group of %lld records)", (long long)n_recs);
         PG_TRY(hipEventRecord(h->ev[0], s));
-        PG_TRY(pg::launch_resolve(h->d_infl, d_grecs, (int32_t)n_recs, h->d_qpos, h->d_indel, h->d_isdel, s));
+        PG_TRY(pg::launch_resolve(inf.d_infl.p, d_grecs, (int32_t)n_recs, h->d_qpos.p, h->d_indel.p, h->d_isdel.p, s));
         PG_TRY(hipEventRecord(h->ev[1], s));
         PG_TRY(hipStreamSynchronize(s));
         PG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
@@ -640,13 +582,11 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
 }
 #undef PG_TRY
 
-
-int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads, uint8_t* qual,
-               uint8_t* strand, uint8_t* ref_out, int32_t* num_out, int8_t* status_out, bool device_planes, void* stream,
+int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positions, int64_t n, const Outs& out, void* stream,
                bool census = false) {
     // (pg_census: device_planes with no plane -- nothing but status_out is written, on the device or here)
-    if (n < 0 || (n > 0 && (!contigs || !positions || !status_out)) ||
-        (n > 0 && !census && (!reads || !qual || !strand || !ref_out || !num_out)))
+    if (n < 0 || (n > 0 && (!contigs || !positions || !out.status)) ||
+        (n > 0 && !census && (!out.reads || !out.qual || !out.strand || !out.ref || !out.num)))
         return fail(h, -1, "null argument");
     h->census = census;
     const pe_options& o = h->opt;
@@ -658,25 +598,19 @@ int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positio
         const int rc = build_linear_index(h);
         if (rc) { h->scanned = false; return rc; }
     }
-    // the caller's current device is restored on every return
-    struct DeviceGuard {
-        int prev = -1;
-        ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-    } guard;
-    if (hipGetDevice(&guard.prev) != hipSuccess) guard.prev = -1;
+    dev::DeviceGuard guard;                               // the caller's current device is restored on every return
     if (hipSetDevice(h->device) != hipSuccess) return fail(h, -2, "hipSetDevice(%d) failed", h->device);
-    if (!h->stream && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(h, -2, "hipStreamCreate failed");
-    for (hipEvent_t& e : h->ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) return fail(h, -2, "hipEventCreate failed");
+    if (h->stream.ensure() != hipSuccess) return fail(h, -2, "hipStreamCreate failed");
+    for (dev::Event& e : h->ev)
+        if (e.ensure() != hipSuccess) return fail(h, -2, "hipEventCreate failed");
     h->st = pg_stats{};
     // the caller's stream must not run ahead of (or behind) our work on its planes
     hipStream_t cs = (hipStream_t)stream;
-    if (device_planes) {
-        hipEvent_t ev;
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(h, -2, "hipEventCreate failed");
-        const bool good = hipEventRecord(ev, cs) == hipSuccess && hipStreamWaitEvent(h->stream, ev, 0) == hipSuccess;
-        (void)hipEventDestroy(ev);
-        if (!good) return fail(h, -2, "cannot order the encoder after the caller's stream");
+    if (out.device_planes) {
+        dev::Event ev;
+        if (ev.ensure(hipEventDisableTiming) != hipSuccess) return fail(h, -2, "hipEventCreate failed");
+        if (hipEventRecord(ev, cs) != hipSuccess || hipStreamWaitEvent(h->stream, ev, 0) != hipSuccess)
+            return fail(h, -2, "cannot order the encoder after the caller's stream");
     }
     std::vector<Entry> es((size_t)n);
     const bool plan = o.window_size <= pg::MAX_WINDOW && o.min_base_quality <= 0;
@@ -700,21 +634,15 @@ int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positio
         if (ka != kb) return ka < kb;
         return a.tid != b.tid ? a.tid < b.tid : a.pos1 < b.pos1;
     });
-    if (!device_planes && !grow(h->d_planes, h->c_planes, 3 * plane * BATCH_LOCS))
-        return fail(h, -2, "hipMalloc of the plane buffer failed");
-    if (!device_planes && !pinned_grow(h->h_planes, h->hc_planes, 3 * plane * BATCH_LOCS))
-        return fail(h, -2, "hipHostMalloc of the plane buffer failed");
-    if (h->inflate_device)
-        return encode_all_device(h, contigs, es, Outs{reads, qual, strand, ref_out, num_out, status_out, device_planes});
+    if (!out.device_planes && h->d_planes.ensure(3 * plane * BATCH_LOCS)) return fail(h, -2, "hipMalloc of the plane buffer failed");
+    if (!out.device_planes && h->h_planes.ensure(3 * plane * BATCH_LOCS)) return fail(h, -2, "hipHostMalloc of the plane buffer failed");
+    if (h->inflate_device) return encode_all_device(h, contigs, es, out);
     std::vector<uint8_t> small;
     for (int64_t b0 = 0; b0 < n; b0 += BATCH_LOCS) {
         const int64_t b1 = std::min<int64_t>(n, b0 + BATCH_LOCS);
-        uint8_t* R = device_planes ? reads : h->d_planes;
-        uint8_t* Q = device_planes ? qual : h->d_planes + plane * BATCH_LOCS;
-        uint8_t* S = device_planes ? strand : h->d_planes + 2 * plane * BATCH_LOCS;
-        int rc = encode_batch(h, contigs, es, b0, b1, R, Q, S, device_planes);
+        int rc = encode_batch(h, contigs, es, b0, b1, out);
         if (rc) return rc;
-        rc = copy_back(h, es, b0, b1, reads, qual, strand, ref_out, num_out, status_out, device_planes, small);
+        rc = copy_back(h, es, b0, b1, out, small);
         if (rc) return rc;
     }
     return 0;
@@ -744,51 +672,42 @@ int compress_records(pg_encoder* h, const uint8_t* reads, const uint8_t* qual, c
     for (int64_t i = 0; i < n; ++i)
         if (slots[i] < 0 || slots[i] >= n_slots)
             return fail(h, -1, "pg_compress_records_device: record %lld names slot %d of %lld", (long long)i, slots[i], (long long)n_slots);
-    struct DeviceGuard {
-        int prev = -1;
-        ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-    } guard;
-    if (hipGetDevice(&guard.prev) != hipSuccess) guard.prev = -1;
+    dev::DeviceGuard guard;
     if (hipSetDevice(h->device) != hipSuccess) return fail(h, -2, "hipSetDevice(%d) failed", h->device);
-    for (hipEvent_t& e : h->zev)
-        if (!e && hipEventCreate(&e) != hipSuccess) return fail(h, -2, "hipEventCreate failed");
-    if (!h->zctx) h->zctx = zd::ctx_create();
+    for (dev::Event& e : h->zev)
+        if (e.ensure() != hipSuccess) return fail(h, -2, "hipEventCreate failed");
+    if (!h->zctx) h->zctx.reset(zd::ctx_create());
     const int64_t n_chunks = (n + rpc - 1) / rpc;
     const int64_t pass_chunks = std::min<int64_t>(n_chunks, Z_CHUNKS), pass_records = pass_chunks * rpc;
     const uint64_t cbound = zd::bound(chunk_bytes, zd::DEFAULT_SEG);
     const size_t stage = (size_t)pass_records * (blob_bytes + 4);            // blob | slots of one pass
-    if (!grow(h->d_image, h->c_image, (size_t)pass_chunks * chunk_bytes + 8) || !grow(h->d_zout, h->c_zout, (size_t)pass_chunks * cbound) ||
-        !grow(h->d_blob, h->c_blob, stage))
+    if (h->d_image.ensure((size_t)pass_chunks * chunk_bytes + 8) || h->d_zout.ensure((size_t)pass_chunks * cbound) || h->d_blob.ensure(stage))
         return fail(h, -2, "hipMalloc failed (%lld chunks of %llu bytes)", (long long)pass_chunks, (unsigned long long)chunk_bytes);
-    if (!pinned_grow(h->h_blob, h->hc_blob, stage)) return fail(h, -2, "hipHostMalloc of the blob staging failed");
+    if (h->h_blob.ensure(stage)) return fail(h, -2, "hipHostMalloc of the blob staging failed");
     hipStream_t s = (hipStream_t)stream;
-#define PZ_TRY(x)                                                                                                  \
-    do {                                                                                                           \
-        const hipError_t e_ = (x);                                                                                 \
-        if (e_ != hipSuccess) return fail(h, -2, "pg_compress_records_device: %s: %s", #x, hipGetErrorString(e_)); \
-    } while (0)
+#define PZ_TRY(x) DEV_TRY(h->err, "pg_compress_records_device: ", x)
     uint64_t total = 0;
     for (int64_t c0 = 0; c0 < n_chunks; c0 += pass_chunks) {
         const int64_t nc = std::min<int64_t>(pass_chunks, n_chunks - c0);
         const int64_t r0 = c0 * rpc, nr = std::min<int64_t>(n - r0, nc * rpc);
         const size_t b_blob = (size_t)nr * blob_bytes;
-        memcpy(h->h_blob, blob + (size_t)r0 * blob_bytes, b_blob);
-        memcpy(h->h_blob + (size_t)pass_records * blob_bytes, slots + r0, (size_t)nr * 4);
+        memcpy(h->h_blob.p, blob + (size_t)r0 * blob_bytes, b_blob);
+        memcpy(h->h_blob.p + (size_t)pass_records * blob_bytes, slots + r0, (size_t)nr * 4);
         PZ_TRY(hipEventRecord(h->zev[0], s));
-        PZ_TRY(hipMemcpyAsync(h->d_blob, h->h_blob, b_blob, hipMemcpyHostToDevice, s));
-        PZ_TRY(hipMemcpyAsync(h->d_blob + (size_t)pass_records * blob_bytes, h->h_blob + (size_t)pass_records * blob_bytes, (size_t)nr * 4,
+        PZ_TRY(hipMemcpyAsync(h->d_blob.p, h->h_blob.p, b_blob, hipMemcpyHostToDevice, s));
+        PZ_TRY(hipMemcpyAsync(h->d_blob.p + (size_t)pass_records * blob_bytes, h->h_blob.p + (size_t)pass_records * blob_bytes, (size_t)nr * 4,
                               hipMemcpyHostToDevice, s));
         zd::PackArgs a{};
         a.planes[0] = reads; a.planes[1] = qual; a.planes[2] = strand;
-        a.blob = h->d_blob;
-        a.slots = (const int32_t*)(h->d_blob + (size_t)pass_records * blob_bytes);
+        a.blob = h->d_blob.p;
+        a.slots = (const int32_t*)(h->d_blob.p + (size_t)pass_records * blob_bytes);
         a.n_records = nr; a.plane = plane; a.head = head; a.mid = mid;
         const uint64_t image_bytes = ((uint64_t)nc * chunk_bytes + 7) & ~7ull;       // (chunk_bytes * rpc-of-8 is a multiple of 8; any rpc: + 8 above)
-        PZ_TRY(zd::launch_pack(a, image_bytes, h->d_image, s));
+        PZ_TRY(zd::launch_pack(a, image_bytes, h->d_image.p, s));
         PZ_TRY(hipEventRecord(h->zev[1], s));
         zd::Streams r{};
         const char* msg = nullptr;
-        if (zd::run(h->zctx, h->d_image, chunk_bytes, nc, zd::DEFAULT_SEG, false, true, h->compress_dynamic, h->d_zout, s, h->zev[2], &r, &msg))
+        if (zd::run(h->zctx.get(), h->d_image.p, chunk_bytes, nc, zd::DEFAULT_SEG, false, true, h->compress_dynamic, h->d_zout.p, s, h->zev[2], &r, &msg))
             return fail(h, -2, "pg_compress_records_device: %s", msg);
         PZ_TRY(hipEventRecord(h->zev[3], s));
         PZ_TRY(hipMemcpyAsync(offsets + c0, r.offs, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
@@ -805,13 +724,9 @@ int compress_records(pg_encoder* h, const uint8_t* reads, const uint8_t* qual, c
                 ++*(kind == zd::KIND_DYNAMIC ? &h->st.dynamic_segments : kind == zd::KIND_STORED ? &h->st.stored_segments : &h->st.fixed_segments);
         const uint64_t bytes = offsets[c0 + nc - 1] + sizes[c0 + nc - 1];
         if (bytes > (uint64_t)nc * cbound) return fail(h, -2, "pg_compress_records_device: the streams exceed their bound");
-        if (total && total + bytes > h->hc_zout) {             // a later pass outgrows the pinned buffer: keep what it holds
-            const std::vector<uint8_t> earlier(h->h_zout, h->h_zout + total);
-            if (!pinned_grow(h->h_zout, h->hc_zout, (size_t)(total + bytes))) return fail(h, -2, "hipHostMalloc(%llu) failed", (unsigned long long)(total + bytes));
-            memcpy(h->h_zout, earlier.data(), total);
-        } else if (!pinned_grow(h->h_zout, h->hc_zout, (size_t)(total + bytes)))
-            return fail(h, -2, "hipHostMalloc(%llu) failed", (unsigned long long)(total + bytes));
-        PZ_TRY(hipMemcpyAsync(h->h_zout + total, h->d_zout, bytes, hipMemcpyDeviceToHost, s));
+        if (h->h_zout.ensure_keep((size_t)(total + bytes), (size_t)total))   // (a later pass may outgrow it: the earlier passes' bytes stay)
+            return fail(h, -2, "pinned allocation of %llu bytes failed", (unsigned long long)(total + bytes));
+        PZ_TRY(hipMemcpyAsync(h->h_zout.p + total, h->d_zout.p, bytes, hipMemcpyDeviceToHost, s));
         PZ_TRY(hipEventRecord(h->zev[4], s));
         PZ_TRY(hipStreamSynchronize(s));
         for (int64_t c = c0; c < c0 + nc; ++c) {
@@ -829,7 +744,7 @@ int compress_records(pg_encoder* h, const uint8_t* reads, const uint8_t* qual, c
     h->st.chunks = n_chunks;
     h->st.raw_bytes = (int64_t)((uint64_t)n_chunks * chunk_bytes);
     h->st.chunk_bytes_out = (int64_t)total;
-    *out = h->h_zout;
+    *out = h->h_zout.p;
     return 0;
 }
 
@@ -840,7 +755,7 @@ extern "C" {
 const char* pg_last_error(const pg_encoder_t* h) { return h ? h->err.c_str() : pgh::g_err.c_str(); }
 
 int pg_open(const char* bam_path, const char* bai_path, const char* fasta_path, const pe_options* opt, int32_t device, pg_encoder_t** out) {
-    try {
+    return capi::guarded(pgh::g_err, "pg_open", [&] {
         if (!bam_path || !fasta_path || !opt || !out) return fail(nullptr, -1, "pg_open: null argument");
         *out = nullptr;
         if (opt->window_size < 1 || opt->max_reads < 1) return fail(nullptr, -1, "pg_open: window_size and max_reads must be positive");
@@ -860,47 +775,31 @@ int pg_open(const char* bam_path, const char* bai_path, const char* fasta_path, 
         for (auto& c : cands) if (h->bai.load(c)) { h->have_bai = true; break; }
         *out = h.release();
         return 0;
-    } catch (const std::exception& e) {
-        return fail(nullptr, -4, "pg_open: %s", e.what());
-    } catch (...) {
-        return fail(nullptr, -4, "pg_open: unknown exception");
-    }
+    });
 }
 
 int pg_encode(pg_encoder_t* h, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads_out, uint8_t* qual_out,
               uint8_t* strand_out, uint8_t* ref_out, int32_t* num_reads_out, int8_t* status_out) {
     if (!h) return fail(nullptr, -1, "pg_encode: null handle");
-    try {
-        return encode_all(h, contigs, positions, n, reads_out, qual_out, strand_out, ref_out, num_reads_out, status_out, false, nullptr);
-    } catch (const std::exception& e) {
-        return fail(h, -4, "pg_encode: %s", e.what());
-    } catch (...) {
-        return fail(h, -4, "pg_encode: unknown exception");
-    }
+    return capi::guarded(h->err, "pg_encode", [&] {
+        return encode_all(h, contigs, positions, n, Outs{reads_out, qual_out, strand_out, ref_out, num_reads_out, status_out, false}, nullptr);
+    });
 }
 
 int pg_encode_device(pg_encoder_t* h, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads_dev,
                      uint8_t* qual_dev, uint8_t* strand_dev, uint8_t* ref_out, int32_t* num_reads_out, int8_t* status_out,
                      void* stream) {
     if (!h) return fail(nullptr, -1, "pg_encode_device: null handle");
-    try {
-        return encode_all(h, contigs, positions, n, reads_dev, qual_dev, strand_dev, ref_out, num_reads_out, status_out, true, stream);
-    } catch (const std::exception& e) {
-        return fail(h, -4, "pg_encode_device: %s", e.what());
-    } catch (...) {
-        return fail(h, -4, "pg_encode_device: unknown exception");
-    }
+    return capi::guarded(h->err, "pg_encode_device", [&] {
+        return encode_all(h, contigs, positions, n, Outs{reads_dev, qual_dev, strand_dev, ref_out, num_reads_out, status_out, true}, stream);
+    });
 }
 
 int pg_census(pg_encoder_t* h, const char* const* contigs, const int32_t* positions, int64_t n, int8_t* status_out, void* stream) {
     if (!h) return fail(nullptr, -1, "pg_census: null handle");
-    try {
-        return encode_all(h, contigs, positions, n, nullptr, nullptr, nullptr, nullptr, nullptr, status_out, true, stream, true);
-    } catch (const std::exception& e) {
-        return fail(h, -4, "pg_census: %s", e.what());
-    } catch (...) {
-        return fail(h, -4, "pg_census: unknown exception");
-    }
+    return capi::guarded(h->err, "pg_census", [&] {
+        return encode_all(h, contigs, positions, n, Outs{nullptr, nullptr, nullptr, nullptr, nullptr, status_out, true}, stream, true);
+    });
 }
 
 int pg_assemble_device(pg_encoder_t* h, const uint8_t* reads_src, const uint8_t* qual_src, const uint8_t* strand_src, int64_t n_slots,
@@ -909,16 +808,12 @@ int pg_assemble_device(pg_encoder_t* h, const uint8_t* reads_src, const uint8_t*
                        int32_t use_q, int32_t use_strand, uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out,
                        uint8_t* ref_out, uint8_t* ref_mask_out, uint8_t* var_mask_out, void* stream) {
     if (!h) return fail(nullptr, -1, "pg_assemble_device: null handle");
-    try {
+    return capi::guarded(h->err, "pg_assemble_device", [&] {
         const uint8_t* src[3] = {reads_src, qual_src, strand_src};    // [n_slots][stored_rows][window]: a slot is one plane of a site
         return pgh::assemble(h, "pg_assemble_device", src, (int64_t)stored_rows * window, n_slots, stored_rows, window, slots, rows,
                              first_rows, m, reads, ref, ref_mask, var_mask, use_q, use_strand, reads_out, qual_out, strand_out, ref_out,
                              ref_mask_out, var_mask_out, stream);
-    } catch (const std::exception& e) {
-        return fail(h, -4, "pg_assemble_device: %s", e.what());
-    } catch (...) {
-        return fail(h, -4, "pg_assemble_device: unknown exception");
-    }
+    });
 }
 
 int pg_compress_records_device(pg_encoder_t* h, const uint8_t* reads_dev, const uint8_t* qual_dev, const uint8_t* strand_dev,
@@ -926,28 +821,22 @@ int pg_compress_records_device(pg_encoder_t* h, const uint8_t* reads_dev, const 
                                int32_t records_per_chunk, const uint8_t** out, uint64_t* offsets, uint64_t* sizes, uint32_t* adlers,
                                uint8_t* store, void* stream) {
     if (!h) return fail(nullptr, -1, "pg_compress_records_device: null handle");
-    try {
+    return capi::guarded(h->err, "pg_compress_records_device", [&] {
         return compress_records(h, reads_dev, qual_dev, strand_dev, n_slots, slots, blob, n_records, records_per_chunk, out, offsets, sizes,
                                 adlers, store, stream);
-    } catch (const std::exception& e) {
-        return fail(h, -4, "pg_compress_records_device: %s", e.what());
-    } catch (...) {
-        return fail(h, -4, "pg_compress_records_device: unknown exception");
-    }
+    });
 }
 
 int pg_set_inflate_device(pg_encoder_t* h, int on, uint64_t max_inflated_bytes) {
     if (!h) return fail(nullptr, -1, "pg_set_inflate_device: null handle");
-    try {
+    return capi::guarded(h->err, "pg_set_inflate_device", [&] {
         if (on && (!h->have_bai || h->bai.bins.empty()))
             return fail(h, -1, "inflate on the device needs the BAI index of %s: its bins give the byte ranges to read", h->bam_path.c_str());
-        if (on && h->fd < 0 && (h->fd = open(h->bam_path.c_str(), O_RDONLY)) < 0) return fail(h, -3, "cannot open %s", h->bam_path.c_str());
+        if (on && !h->inflate.open(h->bam_path)) return fail(h, -3, "cannot open %s", h->bam_path.c_str());
         h->inflate_device = on != 0;
         h->max_inflated = max_inflated_bytes ? max_inflated_bytes : DEFAULT_INFLATED;
         return 0;
-    } catch (...) {
-        return fail(h, -4, "pg_set_inflate_device: unknown exception");
-    }
+    });
 }
 
 int pg_set_compress_codes(pg_encoder_t* h, int mode) {

@@ -2,6 +2,7 @@
 // device path, for tests without a GPU.  No device call.  With -DPG_HOST_ONLY a plain C++ compiler builds this file alone
 // (tools/asan_pileup_frame.sh runs it under sanitizers, together with the host entry of bgzf_capi.cpp).
 #include "../../include/dl4vc_pileup_gpu.h"
+#include "capi_shell.h"
 #include "pileup_fetch.h"
 
 std::string pgh::g_err;
@@ -12,16 +13,16 @@ extern "C" const char* pg_last_error(const pg_encoder_t*) { return pgh::g_err.c_
 
 extern "C" int pg_debug_run_records(const char* bam_path, const char* bai_path, int32_t tid, int64_t s0, int64_t stop, int path,
                                     pg_rec_view* out, int64_t cap, int64_t* n, int64_t* max_nref, int32_t* sorted) {
-    try {
-        if (!bam_path || !bai_path || !n || !max_nref || !sorted || (cap > 0 && !out)) { pgh::g_err = "pg_debug_run_records: null argument"; return -1; }
-        if (path < 0 || path > 2) { pgh::g_err = "pg_debug_run_records: path is 0, 1 or 2"; return -1; }
+    return capi::guarded(pgh::g_err, "pg_debug_run_records", [&] {
+        if (!bam_path || !bai_path || !n || !max_nref || !sorted || (cap > 0 && !out)) return capi::failf(pgh::g_err, -1, "pg_debug_run_records: null argument");
+        if (path < 0 || path > 2) return capi::failf(pgh::g_err, -1, "pg_debug_run_records: path is 0, 1 or 2");
         bamn::Bai bai;
-        if (!bai.load(bai_path)) { pgh::g_err = std::string("cannot read the BAI index ") + bai_path; return -3; }
+        if (!bai.load(bai_path)) return capi::failf(pgh::g_err, -3, "cannot read the BAI index %s", bai_path);
         pgh::RunRecs run;
         if (path == 0) {
             bamn::BamFile bam;
             std::vector<uint8_t> blk;
-            if (!bam.open(bam_path)) { pgh::g_err = bam.err; return -3; }
+            if (!bam.open(bam_path)) return capi::failf(pgh::g_err, -3, "%s", bam.err.c_str());
             pgh::fetch_records(bai, bam, blk, tid, s0, stop, run);
         } else if (path == 1) {
             pgh::twin_records(bai, bam_path, tid, s0, stop, run);
@@ -29,7 +30,7 @@ extern "C" int pg_debug_run_records(const char* bam_path, const char* bai_path, 
             const pgh::Region first{tid, 0, 64};
             pgh::twin_records(bai, bam_path, tid, s0, stop, run, &first, 1);
         }
-        if (!run.err.empty()) { pgh::g_err = run.err; return -3; }
+        if (!run.err.empty()) return capi::failf(pgh::g_err, -3, "%s", run.err.c_str());
         *n = (int64_t)run.recs.size();
         *max_nref = run.max_nref;
         *sorted = run.sorted ? 1 : 0;
@@ -45,11 +46,5 @@ extern "C" int pg_debug_run_records(const char* bam_path, const char* bai_path, 
             v.bytes_hash = hsh;
         }
         return 0;
-    } catch (const std::exception& e) {
-        pgh::g_err = std::string("pg_debug_run_records: ") + e.what();
-        return -4;
-    } catch (...) {
-        pgh::g_err = "pg_debug_run_records: unknown exception";
-        return -4;
-    }
+    });
 }

@@ -14,8 +14,6 @@
 #include "bgzf_plan.h"
 #include "pileup_frame.h"
 
-extern "C" const char* bz_status_text(int status);
-
 namespace pgh {
 
 // what pg_last_error(NULL) returns: the error of the last failed pg_open or pg_debug_run_records (defined in pileup_debug.cpp)
@@ -110,11 +108,7 @@ inline void twin_records(const bamn::Bai& bai, const std::string& path, int32_t 
     std::vector<bz::Tables> t(1);
     for (size_t i = 0; i < pl.tab.size(); ++i) {
         const int st = bz::inflate_block_host(comp.data(), pl.tab[i], run.bytes.data(), t[0], table);
-        if (st != BZ_OK) {
-            run.err = std::string("BGZF block fails its CRC / size check (") + bz_status_text(st) + ", block at file offset " +
-                      std::to_string(pl.blocks[i].coff) + ")";
-            return;
-        }
+        if (st != BZ_OK) { run.err = pl.bad_block(i, st); return; }
     }
     const uint8_t* infl = run.bytes.data();
     const uint64_t total = pl.infl_bytes;

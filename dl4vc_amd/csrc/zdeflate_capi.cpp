@@ -2,6 +2,7 @@
 // serially) and its device form over caller-supplied device buffers.  With -DZD_HOST_ONLY the file compiles with a plain C++
 // compiler into the host entries alone (tools/asan_zdeflate.sh).  Errors go to the text pg_last_error(NULL) returns.
 #include "../../include/dl4vc_pileup_gpu.h"
+#include "capi_shell.h"
 #include "zdeflate.h"
 
 #include <mutex>
@@ -19,21 +20,18 @@ std::string pgh::g_err;
 
 namespace {
 
-int zfail(int code, const std::string& what) {
-    pgh::g_err = what;
-    return code;
-}
+template <class... A>
+int zfail(int code, const char* fmt, A... a) { return capi::failf(pgh::g_err, code, fmt, a...); }
 
 bool seg_ok(uint32_t seg) { return seg >= zd::MIN_SEG && seg <= zd::MAX_SEG; }
 
 int deflate_host(const char* who, const uint8_t* in, uint64_t n, uint32_t segment, int32_t flags, uint8_t* out, uint64_t out_cap,
                  uint64_t* size, uint32_t* adler, int32_t* store) {
-    const std::string name(who);
-    try {
-        if ((n && !in) || !out || !size || !adler || !store) return zfail(-1, name + ": null argument");
-        if (!seg_ok(segment)) return zfail(-1, name + ": segment must be 1024..32768 bytes");
-        if (n > zd::MAX_STREAM) return zfail(-1, name + ": more than 2^31 bytes in one stream");
-        if (out_cap < zd::bound(n, segment)) return zfail(-1, name + ": the output buffer is smaller than zd_bound");
+    return capi::guarded(pgh::g_err, who, [&] {
+        if ((n && !in) || !out || !size || !adler || !store) return zfail(-1, "%s: null argument", who);
+        if (!seg_ok(segment)) return zfail(-1, "%s: segment must be 1024..32768 bytes", who);
+        if (n > zd::MAX_STREAM) return zfail(-1, "%s: more than 2^31 bytes in one stream", who);
+        if (out_cap < zd::bound(n, segment)) return zfail(-1, "%s: the output buffer is smaller than zd_bound", who);
         const uint64_t ns = zd::n_segments(n, segment);
         std::vector<uint32_t> sizes(ns), adlers(ns);
         std::vector<uint64_t> offs(ns);
@@ -59,11 +57,7 @@ int deflate_host(const char* who, const uint8_t* in, uint64_t n, uint32_t segmen
         *adler = r.adler;
         *store = (int32_t)r.store;
         return 0;
-    } catch (const std::exception& e) {
-        return zfail(-4, name + ": " + e.what());
-    } catch (...) {
-        return zfail(-4, name + ": unknown exception");
-    }
+    });
 }
 
 }  // namespace
@@ -90,7 +84,7 @@ int zd_deflate_host_flags(const uint8_t* in, uint64_t n, uint32_t segment, int32
 }
 
 int zd_code_lengths_host(const uint32_t* freq, int32_t n, int32_t limit, uint8_t* lens) {
-    try {
+    return capi::guarded(pgh::g_err, "zd_code_lengths_host", [&] {
         if (!freq || !lens) return zfail(-1, "zd_code_lengths_host: null argument");
         if (n < 2 || n > (int32_t)zd::N_LL || limit < 1 || limit > zd::MAX_BITS || (n > 2 && (1 << limit) < n))
             return zfail(-1, "zd_code_lengths_host: 2..286 symbols, a limit of 1..15 bits that holds them");
@@ -101,11 +95,7 @@ int zd_code_lengths_host(const uint32_t* freq, int32_t n, int32_t limit, uint8_t
         zd::code_lengths(t.data(), 1, (uint32_t)n, limit, build.data());
         for (int32_t s = 0; s < n; ++s) lens[s] = (uint8_t)t[s];
         return 0;
-    } catch (const std::exception& e) {
-        return zfail(-4, std::string("zd_code_lengths_host: ") + e.what());
-    } catch (...) {
-        return zfail(-4, "zd_code_lengths_host: unknown exception");
-    }
+    });
 }
 
 #ifndef ZD_HOST_ONLY
@@ -113,7 +103,7 @@ int zd_deflate(const uint8_t* in_dev, uint64_t chunk_bytes, int64_t n_chunks, ui
                uint64_t out_cap, uint64_t* offsets, uint64_t* sizes, uint32_t* adlers, uint8_t* store, void* stream) {
     static std::mutex mu;
     static zd::Ctx* ctx = nullptr;             // (a test entry: one set of work buffers per process, kept)
-    try {
+    return capi::guarded(pgh::g_err, "zd_deflate", [&] {
         if (!in_dev || !out_dev || !offsets || !sizes || !adlers || !store) return zfail(-1, "zd_deflate: null argument");
         if (!seg_ok(segment)) return zfail(-1, "zd_deflate: segment must be 1024..32768 bytes");
         if (chunk_bytes > zd::MAX_STREAM || n_chunks < 1 || n_chunks > 65535) return zfail(-1, "zd_deflate: 1..65535 chunks of at most 2^31 bytes");
@@ -126,19 +116,15 @@ int zd_deflate(const uint8_t* in_dev, uint64_t chunk_bytes, int64_t n_chunks, ui
         const char* msg = nullptr;
         if (zd::run(ctx, in_dev, chunk_bytes, n_chunks, segment, flags & ZD_REVERSED, flags & ZD_RAW_ON_STORE, flags & ZD_DYNAMIC, out_dev, s, nullptr,
                     &r, &msg))
-            return zfail(-2, std::string("zd_deflate: ") + msg);
+            return zfail(-2, "zd_deflate: %s", msg);
         hipError_t e = hipMemcpyAsync(offsets, r.offs, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(sizes, r.sizes, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(adlers, r.adlers, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(store, r.store, (size_t)n_chunks, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return zfail(-2, std::string("zd_deflate: device: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return zfail(-2, "zd_deflate: device: %s", hipGetErrorString(e));
         return 0;
-    } catch (const std::exception& e) {
-        return zfail(-4, std::string("zd_deflate: ") + e.what());
-    } catch (...) {
-        return zfail(-4, "zd_deflate: unknown exception");
-    }
+    });
 }
 #endif
 

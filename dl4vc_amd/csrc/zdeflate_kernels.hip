@@ -130,32 +130,20 @@ __global__ __launch_bounds__(COPY_BLOCK) void zd_gather_kernel(const uint8_t* in
     for (uint64_t i = threadIdx.x; i < n; i += COPY_BLOCK) dst[i] = src[i];
 }
 
-using dev::grow;
-
 }  // namespace
 
 struct Ctx {
-    uint8_t* tmp = nullptr; size_t c_tmp = 0;
-    uint32_t* seg_size = nullptr; size_t c_seg_size = 0;
-    uint32_t* seg_adler = nullptr; size_t c_seg_adler = 0;
-    uint64_t* seg_off = nullptr; size_t c_seg_off = 0;
-    uint64_t* out_size = nullptr; size_t c_out_size = 0;
-    uint64_t* chunk_off = nullptr; size_t c_chunk_off = 0;
-    uint32_t* adlers = nullptr; size_t c_adlers = 0;
-    uint8_t* store = nullptr; size_t c_store = 0;
-    uint8_t* scan = nullptr; size_t c_scan = 0;
-    uint8_t* seg_kind = nullptr; size_t c_seg_kind = 0;         // dynamic mode only
+    dev::Buffer tmp;
+    dev::Array<uint32_t> seg_size, seg_adler;
+    dev::Array<uint64_t> seg_off, out_size, chunk_off;
+    dev::Array<uint32_t> adlers;
+    dev::Buffer store, scan;
+    dev::Buffer seg_kind;                                       // dynamic mode only
 };
 
 Ctx* ctx_create() { return new Ctx(); }
 
-void ctx_destroy(Ctx* c) {
-    if (!c) return;
-    for (void* p : {(void*)c->tmp, (void*)c->seg_size, (void*)c->seg_adler, (void*)c->seg_off, (void*)c->out_size, (void*)c->chunk_off,
-                    (void*)c->adlers, (void*)c->store, (void*)c->scan, (void*)c->seg_kind})
-        if (p) (void)hipFree(p);
-    delete c;
-}
+void ctx_destroy(Ctx* c) { delete c; }
 
 hipError_t launch_pack(const PackArgs& a, uint64_t image_bytes, uint8_t* image, hipStream_t s) {
     const uint64_t n_words = image_bytes / 8;
@@ -181,39 +169,37 @@ int run(Ctx* c, const uint8_t* in, uint64_t chunk_bytes, int64_t n_chunks, uint3
     }
     const uint32_t spc = (uint32_t)spc64;
     const uint32_t tmp_stride = seg_cap(seg);
-    if (!grow(c->tmp, c->c_tmp, (size_t)n_segs * tmp_stride) || !grow(c->seg_size, c->c_seg_size, (size_t)n_segs) ||
-        !grow(c->seg_adler, c->c_seg_adler, (size_t)n_segs) || !grow(c->seg_off, c->c_seg_off, (size_t)n_segs) ||
-        !grow(c->out_size, c->c_out_size, (size_t)n_chunks) || !grow(c->chunk_off, c->c_chunk_off, (size_t)n_chunks) ||
-        !grow(c->adlers, c->c_adlers, (size_t)n_chunks) || !grow(c->store, c->c_store, (size_t)n_chunks) ||
-        (dynamic && !grow(c->seg_kind, c->c_seg_kind, (size_t)n_segs))) {
+    if (c->tmp.ensure((size_t)n_segs * tmp_stride) || c->seg_size.ensure((size_t)n_segs) || c->seg_adler.ensure((size_t)n_segs) ||
+        c->seg_off.ensure((size_t)n_segs) || c->out_size.ensure((size_t)n_chunks) || c->chunk_off.ensure((size_t)n_chunks) ||
+        c->adlers.ensure((size_t)n_chunks) || c->store.ensure((size_t)n_chunks) || (dynamic && c->seg_kind.ensure((size_t)n_segs))) {
         *msg = "zd::run: hipMalloc failed";
         return -2;
     }
     size_t scan_bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, scan_bytes, c->out_size, c->chunk_off, (uint64_t)0, (size_t)n_chunks, rocprim::plus<uint64_t>(), s);
+    hipError_t e = rocprim::exclusive_scan(nullptr, scan_bytes, c->out_size.p, c->chunk_off.p, (uint64_t)0, (size_t)n_chunks, rocprim::plus<uint64_t>(), s);
     if (e != hipSuccess) return bad("rocprim::exclusive_scan (size)", e);
-    if (!grow(c->scan, c->c_scan, scan_bytes + 16)) {
+    if (c->scan.ensure(scan_bytes + 16)) {
         *msg = "zd::run: hipMalloc failed";
         return -2;
     }
     const dim3 deflate_grid((unsigned)((n_segs + DEFLATE_BLOCK - 1) / DEFLATE_BLOCK));
     if (dynamic)
         hipLaunchKernelGGL(zd_deflate_dyn_kernel, deflate_grid, dim3(DEFLATE_BLOCK), 0, s, in, chunk_bytes, spc, n_segs, seg, reversed ? 1 : 0,
-                           c->tmp, tmp_stride, c->seg_size, c->seg_adler, c->seg_kind);
+                           c->tmp.p, tmp_stride, c->seg_size.p, c->seg_adler.p, c->seg_kind.p);
     else
         hipLaunchKernelGGL(zd_deflate_kernel, deflate_grid, dim3(DEFLATE_BLOCK), 0, s, in, chunk_bytes, spc, n_segs, seg, reversed ? 1 : 0,
-                           c->tmp, tmp_stride, c->seg_size, c->seg_adler);
+                           c->tmp.p, tmp_stride, c->seg_size.p, c->seg_adler.p);
     if ((e = hipGetLastError()) != hipSuccess) return bad(dynamic ? "zd_deflate_dyn_kernel" : "zd_deflate_kernel", e);
     if (mid && (e = hipEventRecord(mid, s)) != hipSuccess) return bad("hipEventRecord", e);
     hipLaunchKernelGGL(zd_finish_kernel, dim3((unsigned)((n_chunks + COPY_BLOCK - 1) / COPY_BLOCK)), dim3(COPY_BLOCK), 0, s, chunk_bytes, spc, seg,
-                       n_chunks, raw_on_store ? 1 : 0, c->seg_size, c->seg_adler, c->seg_off, c->out_size, c->adlers, c->store);
+                       n_chunks, raw_on_store ? 1 : 0, c->seg_size.p, c->seg_adler.p, c->seg_off.p, c->out_size.p, c->adlers.p, c->store.p);
     if ((e = hipGetLastError()) != hipSuccess) return bad("zd_finish_kernel", e);
-    e = rocprim::exclusive_scan(c->scan, scan_bytes, c->out_size, c->chunk_off, (uint64_t)0, (size_t)n_chunks, rocprim::plus<uint64_t>(), s);
+    e = rocprim::exclusive_scan(c->scan.p, scan_bytes, c->out_size.p, c->chunk_off.p, (uint64_t)0, (size_t)n_chunks, rocprim::plus<uint64_t>(), s);
     if (e != hipSuccess) return bad("rocprim::exclusive_scan", e);
     hipLaunchKernelGGL(zd_gather_kernel, dim3(spc + 1, (unsigned)n_chunks), dim3(COPY_BLOCK), 0, s, in, chunk_bytes, spc, seg,
-                       raw_on_store ? 1 : 0, c->tmp, tmp_stride, c->seg_size, c->seg_off, c->chunk_off, c->adlers, c->store, out);
+                       raw_on_store ? 1 : 0, c->tmp.p, tmp_stride, c->seg_size.p, c->seg_off.p, c->chunk_off.p, c->adlers.p, c->store.p, out);
     if ((e = hipGetLastError()) != hipSuccess) return bad("zd_gather_kernel", e);
-    *res = Streams{c->chunk_off, c->out_size, c->adlers, c->store, dynamic ? c->seg_kind : nullptr, n_segs};
+    *res = Streams{c->chunk_off.p, c->out_size.p, c->adlers.p, c->store.p, dynamic ? c->seg_kind.p : nullptr, n_segs};
     return 0;
 }
 

@@ -4,13 +4,13 @@
 //
 // With -DZI_HOST_ONLY a plain C++ compiler builds the host entry alone (tools/asan_zinflate.sh runs it under sanitizers).
 #ifdef ZI_HOST_ONLY
+#include "capi_shell.h"
 #include "zinflate.h"
 #else
+#include "device_buffer.h"
 #include "zinflate_device.h"
 #endif
 
-#include <cstdarg>
-#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -18,15 +18,8 @@ namespace {
 
 thread_local std::string g_zi_err;
 
-int zi_fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_zi_err = buf;
-    return code;
-}
+template <class... A>
+int zi_fail(int code, const char* fmt, A... a) { return capi::failf(g_zi_err, code, fmt, a...); }
 
 // the stream table of a call: input ranges checked against nbytes, slots against out_cap
 int make_table(const char* who, const uint8_t* streams, uint64_t nbytes, const uint64_t* off, const uint64_t* len, int64_t n, uint8_t* out,
@@ -53,13 +46,6 @@ int make_table(const char* who, const uint8_t* streams, uint64_t nbytes, const u
     }
     return 0;
 }
-
-#ifndef ZI_HOST_ONLY
-struct DevMem {
-    void* p = nullptr;
-    ~DevMem() { if (p) (void)hipFree(p); }
-};
-#endif
 
 }  // namespace
 
@@ -90,7 +76,7 @@ const char* zi_status_text(int status) {
 
 int zi_inflate_host(const uint8_t* streams, uint64_t nbytes, const uint64_t* off, const uint64_t* len, int64_t n, uint8_t* out,
                     uint64_t out_cap, const uint64_t* out_off, const uint64_t* out_len, const uint8_t* raw, int32_t* status) {
-    try {
+    return capi::guarded(g_zi_err, "zi_inflate_host", [&] {
         std::vector<zi::StreamDesc> tab;
         const int rc = make_table("zi_inflate_host", streams, nbytes, off, len, n, out, out_cap, out_off, out_len, raw, status, tab);
         if (rc) return rc;
@@ -99,47 +85,36 @@ int zi_inflate_host(const uint8_t* streams, uint64_t nbytes, const uint64_t* off
         uint32_t scratch[zi::OneLane::WIDTH];
         for (int64_t i = 0; i < n; ++i) status[i] = zi::run_stream(streams, tab[i], out, ring.data(), t[0], scratch, zi::OneLane{});
         return 0;
-    } catch (const std::exception& e) {
-        return zi_fail(-4, "zi_inflate_host: %s", e.what());
-    } catch (...) {
-        return zi_fail(-4, "zi_inflate_host: unknown exception");
-    }
+    });
 }
 
 #ifndef ZI_HOST_ONLY
 int zi_inflate(const uint8_t* streams, uint64_t nbytes, const uint64_t* off, const uint64_t* len, int64_t n, uint8_t* out, uint64_t out_cap,
                const uint64_t* out_off, const uint64_t* out_len, const uint8_t* raw, int32_t* status, int device) {
-    try {
+    return capi::guarded(g_zi_err, "zi_inflate", [&] {
         std::vector<zi::StreamDesc> tab;
         const int rc = make_table("zi_inflate", streams, nbytes, off, len, n, out, out_cap, out_off, out_len, raw, status, tab);
         if (rc) return rc;
         if (n == 0) return 0;
-#define ZI_TRY(x)                                                                                       \
-    do {                                                                                                \
-        const hipError_t e_ = (x);                                                                      \
-        if (e_ != hipSuccess) return zi_fail(-2, "zi_inflate: %s: %s", #x, hipGetErrorString(e_));      \
-    } while (0)
+#define ZI_TRY(x) DEV_TRY(g_zi_err, "zi_inflate: ", x)
         ZI_TRY(hipSetDevice(device));
-        DevMem d_comp, d_tab, d_out, d_status;
-        ZI_TRY(hipMalloc(&d_comp.p, nbytes + 16));
-        ZI_TRY(hipMalloc(&d_tab.p, tab.size() * sizeof(zi::StreamDesc)));
-        ZI_TRY(hipMalloc(&d_out.p, out_cap + 16));
-        ZI_TRY(hipMalloc(&d_status.p, (size_t)n * sizeof(int32_t)));
+        dev::Buffer d_comp, d_out;
+        dev::Array<zi::StreamDesc> d_tab;
+        dev::Array<int32_t> d_status;
+        ZI_TRY(d_comp.alloc(nbytes + 16));
+        ZI_TRY(d_tab.alloc(tab.size()));
+        ZI_TRY(d_out.alloc(out_cap + 16));
+        ZI_TRY(d_status.alloc((size_t)n));
         if (nbytes) ZI_TRY(hipMemcpy(d_comp.p, streams, nbytes, hipMemcpyHostToDevice));
         ZI_TRY(hipMemcpy(d_tab.p, tab.data(), tab.size() * sizeof(zi::StreamDesc), hipMemcpyHostToDevice));
         if (out_cap) ZI_TRY(hipMemcpy(d_out.p, out, out_cap, hipMemcpyHostToDevice));   // (what no slot covers comes back as it went)
-        ZI_TRY(zi::launch_inflate((const uint8_t*)d_comp.p, (const zi::StreamDesc*)d_tab.p, n, (uint8_t*)d_out.p, (int32_t*)d_status.p,
-                                  nullptr));
+        ZI_TRY(zi::launch_inflate(d_comp.p, d_tab.p, n, d_out.p, d_status.p, nullptr));
         ZI_TRY(hipDeviceSynchronize());
         if (out_cap) ZI_TRY(hipMemcpy(out, d_out.p, out_cap, hipMemcpyDeviceToHost));
         ZI_TRY(hipMemcpy(status, d_status.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
 #undef ZI_TRY
         return 0;
-    } catch (const std::exception& e) {
-        return zi_fail(-4, "zi_inflate: %s", e.what());
-    } catch (...) {
-        return zi_fail(-4, "zi_inflate: unknown exception");
-    }
+    });
 }
 #endif
 
