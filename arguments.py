@@ -81,6 +81,16 @@ _EXTRA = [
                                            "assembled on the GPU (raw HDF5 chunks inflated on the device, shuffled records "
                                            "gathered there, targets from a device histogram); --num-data-workers starts no "
                                            "worker process; same losses, checkpoints and scored VCF"),
+    ("--train-cache-device", "str", argparse.SUPPRESS,
+     "gpu: with --train-loader-device gpu, each of the two files is inflated ONCE when its loader opens and kept in device memory, "
+     "its records trimmed of their trailing all-zero rows (an estimated sixth of the inflated size at 30x, not measured; the fill prints the real ratio); every batch of every epoch "
+     "and every evaluation pass is gathered from there, with no file read and no inflate beside the step.  The whole file is resident "
+     "or the run ends (no fallback); a damaged chunk ends the run during the fill, whether or not an index would ever have fallen "
+     "in it; --gpus N keeps one copy per rank; 3.4 KB of host memory per record; same losses, checkpoints and scored VCF"),
+    ("--train-cache-bytes", "int", argparse.SUPPRESS,
+     "with --train-cache-device gpu: the bytes the trimmed records of --train_file and --test_file may take together in device "
+     "memory (default 0: three quarters of the device memory that is free when the first loader opens).  It bounds the records' bytes, "
+     "not the allocations: the store grows in slabs of 256 MiB (or what the budget leaves), so each file may take up to one slab more"),
     ("--record-census", "str", None, "gpu: with --test_bam, the locations are censused first (which of them give a record, by the GPU "
                                      "encoder's status rule without its planes), so that --gpus N, --shard g/N, "
                                      "--test_holdout_chromosomes and --max-test-batches select and seed the records as --test_file "

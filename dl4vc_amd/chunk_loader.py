@@ -23,7 +23,12 @@ from .hdf5io import RawChunkFile
 from .site_assembly import SitePlan, plan_records, plan_sites
 
 CL_SYMBOLS = ("cl_open", "cl_close", "cl_last_error", "cl_inflate_chunks_device", "cl_assemble_device", "cl_get_stats",
-              "cl_center_counts_device", "cl_center_counts_host")
+              "cl_center_counts_device", "cl_center_counts_host",
+              "cl_store_open", "cl_store_close", "cl_store_last_error", "cl_store_append_device", "cl_store_assemble_device",
+              "cl_store_center_counts_device", "cl_store_extent_host", "cl_store_pack_host", "cl_store_assemble_host", "cl_store_record",
+              "cl_store_slab", "cl_store_debug_fill", "cl_store_get_stats")
+STORE_SLAB_BYTES = 256 << 20        # the record store grows in device slabs of this size
+FILL_GROUP_CHUNKS = 512             # chunks one inflate launch of the store's fill holds (a chunk keeps one lane busy whatever else runs)
 _bound = None
 # libhdf5 is not thread-safe: the raw chunk reads of every loader of the process (the training file's and the test file's workers)
 # take this lock, so at most one thread is inside the library
@@ -34,6 +39,12 @@ class Stats(C.Structure):
     """``cl_stats``."""
     _fields_ = [(n, C.c_double) for n in ("upload_ms", "inflate_ms", "blob_copy_back_ms", "assemble_ms")] + \
                [(n, C.c_int64) for n in ("chunks", "compressed_bytes", "inflated_bytes", "raw_chunks")]
+
+
+class StoreStats(C.Structure):
+    """``cl_store_stats``."""
+    _fields_ = [(n, C.c_int64) for n in ("records", "stored_bytes", "inflated_bytes", "slabs", "refused_fit_records", "refused_fit_bytes")] + \
+               [(n, C.c_double) for n in ("extent_ms", "pack_ms", "assemble_ms")]
 
 
 def load_library() -> C.CDLL:
@@ -51,6 +62,21 @@ def load_library() -> C.CDLL:
         lib.cl_get_stats.argtypes = [vp, C.POINTER(Stats)]
         for fn in (lib.cl_center_counts_device, lib.cl_center_counts_host):
             fn.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp]
+        lib.cl_store_open.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(vp)]
+        lib.cl_store_close.argtypes = [vp]
+        lib.cl_store_close.restype = None
+        lib.cl_store_last_error.argtypes = [vp]
+        lib.cl_store_last_error.restype = C.c_char_p
+        lib.cl_store_append_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp]
+        for fn in (lib.cl_store_assemble_device, lib.cl_store_assemble_host):
+            fn.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32] + [vp] * 6 + [vp]
+        lib.cl_store_center_counts_device.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp]
+        lib.cl_store_extent_host.argtypes = [vp, C.c_uint64, C.c_int64, vp, C.c_int32, C.c_int32, vp, C.c_int64, vp]
+        lib.cl_store_pack_host.argtypes = [vp, vp, C.c_uint64, C.c_int64, vp, vp, vp, C.c_int64, vp]
+        lib.cl_store_record.argtypes = [vp, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        lib.cl_store_slab.argtypes = [vp, C.c_int32, vp, C.c_uint64] + [C.POINTER(C.c_int64)] * 3
+        lib.cl_store_debug_fill.argtypes = [vp, C.c_int32]
+        lib.cl_store_get_stats.argtypes = [vp, C.POINTER(StoreStats)]
         _bound = lib
     return _bound
 
@@ -392,6 +418,281 @@ class DeviceChunkLoader:
             self.lib.cl_close(self._h)
             self._h = None
         self.file.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+# ---- the record store: a file's records inflated once and kept in device memory (--train-cache-device gpu) ------------------------
+class StoreFull(ValueError):
+    """The records do not fit the store's capacity (``--train-cache-bytes``)."""
+
+
+def record_extents_host(inflated, record_bytes: int, plane_off, stored_rows: int, window: int, slots=None) -> np.ndarray:
+    """``cl_store_extent_host``: ``kept`` of the records ``slots`` (all of them by default) of the inflated bytes."""
+    inflated = np.ascontiguousarray(inflated, np.uint8).reshape(-1)
+    slots = np.arange(len(inflated) // record_bytes, dtype=np.int32) if slots is None else np.ascontiguousarray(slots, np.int32)
+    kept = np.zeros(len(slots), np.int32)
+    lib = load_library()
+    offs = (C.c_int64 * 3)(*[int(x) for x in plane_off])
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    if lib.cl_store_extent_host(p(inflated), inflated.nbytes, record_bytes, offs, stored_rows, window, p(slots), len(slots), p(kept)) != 0:
+        raise ValueError(lib.cl_store_last_error(None).decode())
+    return kept
+
+
+class RecordStore:
+    """A ``cl_store_t``: trimmed records in slabs, on ``device`` or (``device < 0``) in host memory, where the CPU definitions
+    ``pack_host`` / ``assemble_host`` stand in for ``append_device`` / ``assemble_device``.  A refused call raises ``ValueError``
+    (``StoreFull`` for the capacity) with the library's text and leaves the store as it was."""
+
+    def __init__(self, window: int, stored_rows: int, n_records: int, capacity_bytes: int, slab_bytes: int = STORE_SLAB_BYTES,
+                 device: int = 0):
+        self.lib = load_library()
+        self.window, self.stored_rows, self.n_records, self.device = int(window), int(stored_rows), int(n_records), int(device)
+        self.capacity_bytes, self.slab_bytes = int(capacity_bytes), int(slab_bytes)
+        h = C.c_void_p()
+        if self.lib.cl_store_open(self.window, self.stored_rows, self.n_records, self.capacity_bytes, self.slab_bytes, self.device,
+                                  C.byref(h)) != 0:
+            raise ValueError("cl_store_open failed: %s" % self.lib.cl_store_last_error(None).decode())
+        self._h = h
+
+    def _check(self, rc):
+        if rc != 0:
+            raise (StoreFull if rc == -3 else ValueError if rc == -1 else RuntimeError)(self.lib.cl_store_last_error(self._h).decode())
+
+    def debug_fill(self, value: int) -> None:
+        self._check(self.lib.cl_store_debug_fill(self._h, value))
+
+    def stats(self) -> StoreStats:
+        st = StoreStats()
+        self._check(self.lib.cl_store_get_stats(self._h, C.byref(st)))
+        return st
+
+    def span(self, kept):
+        """Bytes the records of these extents take in a slab."""
+        return (3 * np.asarray(kept, np.int64) * self.window + 15) & ~np.int64(15)
+
+    def pack_host(self, inflated, record_bytes: int, plane_off, slots, records) -> np.ndarray:
+        inflated = np.ascontiguousarray(inflated, np.uint8).reshape(-1)
+        slots, records = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(records, np.int32)
+        kept = np.zeros(len(slots), np.int32)
+        offs = (C.c_int64 * 3)(*[int(x) for x in plane_off])
+        p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self._check(self.lib.cl_store_pack_host(self._h, p(inflated), inflated.nbytes, record_bytes, offs, p(slots), p(records), len(slots),
+                                                p(kept)))
+        return kept
+
+    def append_device(self, loader_handle, slots, records, stream: int = 0) -> np.ndarray:
+        slots, records = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(records, np.int32)
+        kept = np.zeros(len(slots), np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self._check(self.lib.cl_store_append_device(self._h, loader_handle, p(slots), p(records), len(slots), C.c_void_p(stream or None),
+                                                    p(kept)))
+        return kept
+
+    def _assemble(self, fn, records, rows, first_rows, reads, lines, use_q, use_strand, outs, stream):
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
+        v = lambda x: C.c_void_p(int(x)) if x else None   # noqa: E731
+        records = np.ascontiguousarray(records, np.int32)
+        rows = np.ascontiguousarray(rows, np.int16) if rows is not None else None
+        first = np.ascontiguousarray(first_rows, np.uint8) if first_rows is not None else None
+        lines = [np.ascontiguousarray(a, np.uint8) for a in lines]
+        self._check(fn(self._h, p(records), p(rows), p(first), len(records), int(reads), *[p(a) for a in lines], int(bool(use_q)),
+                       int(bool(use_strand)), *[v(x) for x in outs], v(stream)))
+
+    def assemble_device(self, records, rows, first_rows, reads, lines, use_q, use_strand, outs, stream: int = 0) -> None:
+        """``cl_store_assemble_device``: ``lines`` = (ref, ref_mask, var_mask) ``[m][window]`` host arrays, ``outs`` six device
+        addresses; asynchronous on ``stream``."""
+        self._assemble(self.lib.cl_store_assemble_device, records, rows, first_rows, reads, lines, use_q, use_strand, outs, stream)
+
+    def assemble_host(self, records, rows, first_rows, reads, lines, use_q=True, use_strand=True):
+        """``cl_store_assemble_host`` -> the six planes as numpy arrays."""
+        m, L = len(records), self.window
+        outs = [np.full((m, reads, L), 0xAB, np.uint8) for _ in range(3)] + [np.full((m, L), 0xAB, np.uint8) for _ in range(3)]
+        self._assemble(self.lib.cl_store_assemble_host, records, rows, first_rows, reads, lines, use_q, use_strand,
+                       [a.ctypes.data for a in outs], 0)
+        return outs
+
+    def record(self, i: int):
+        """-> (slab, offset, kept) of record ``i``; of a device store, as the table in device memory has it."""
+        slab, off, kept = C.c_int32(), C.c_int64(), C.c_int32()
+        self._check(self.lib.cl_store_record(self._h, int(i), C.byref(slab), C.byref(off), C.byref(kept)))
+        return slab.value, off.value, kept.value
+
+    def slab(self, k: int):
+        """-> (the slab's whole allocation as bytes, offset of its data in it, used bytes, capacity)."""
+        off, used, cap = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.lib.cl_store_slab(self._h, int(k), None, 0, C.byref(off), C.byref(used), C.byref(cap)))
+        buf = np.zeros(cap.value + (0 if self.device < 0 else off.value + 16), np.uint8)
+        self._check(self.lib.cl_store_slab(self._h, int(k), buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(off), C.byref(used), C.byref(cap)))
+        return buf, off.value, used.value, cap.value
+
+    def close(self):
+        if self._h is not None:
+            self.lib.cl_store_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class _RecordTexts:
+    """``vcfrec`` of the records of a blob array, decoded when asked for."""
+
+    def __init__(self, blob):
+        self.vcfrec = blob["vcfrec"]
+
+    def __getitem__(self, i):
+        return bytes(self.vcfrec[i]).decode()
+
+
+class ResidentRecords:
+    """A candidate file resident on the device (``--train-cache-device gpu``): ``fill()`` inflates every chunk of the file once, in
+    groups of ``group_chunks`` through a ``DeviceChunkLoader``'s handle (``cl_inflate_chunks_device``), appends each group's records
+    to a ``RecordStore`` (trimmed of their trailing all-zero rows: 0.36 of the inflated bytes on the synthetic 100-read records measured; a sixth is the
+    estimate for a 30x pileup, not measured) and keeps every
+    record's non-plane members (3 365 bytes a record) in one host array; then it closes the inflate handle and the file.  From
+    then on ``assemble_list`` is ``DeviceChunkLoader.assemble_list`` with the record indices as the slots and the store as the
+    source: no file read, no upload, no inflate launch.
+
+    The whole file is resident or the fill ends with ``StoreFull`` (how many records fit, in how many bytes, the budget); a damaged
+    chunk ends it with ``DamagedChunk`` wherever it lies."""
+
+    def __init__(self, path: str, reads: int, batch_sites: int, device: int = 0, use_q: bool = True, use_strand: bool = True,
+                 capacity_bytes: int = 0, slab_bytes: int = STORE_SLAB_BYTES, group_chunks: int = FILL_GROUP_CHUNKS, stream: int = 0,
+                 debug_fill: Optional[int] = None):
+        import torch
+        self.torch, self.path = torch, path
+        self.store = None
+        with RawChunkFile(path) as f:
+            n_chunks = -(-len(f) // f.chunk)
+            group = max(1, min(int(group_chunks), n_chunks))
+            chunk = f.chunk
+        # (a sequential handle for ``group`` whole chunks at a time)
+        self._inflater = DeviceChunkLoader(path, reads, batch_sites=group * chunk, device=device, use_q=use_q, use_strand=use_strand)
+        try:
+            dl = self._inflater
+            self.window, self.stored_rows, self.reads, self.B = dl.window, dl.stored_rows, dl.reads, int(batch_sites)
+            self.use_q, self.use_strand, self.device, self.lib = use_q, use_strand, device, dl.lib
+            self.n, self.chunk, self.n_chunks, self.group = len(dl), chunk, n_chunks, group
+            self.blob_dtype = dl.blob_dtype
+            self.blob = np.zeros(self.n, self.blob_dtype)
+            self.capacity_bytes = int(capacity_bytes)
+            self.store = RecordStore(self.window, self.stored_rows, self.n, self.capacity_bytes, slab_bytes, device)
+            if debug_fill is not None:                       # (tests: every slab filled with this byte before anything is packed)
+                self.store.debug_fill(debug_fill)
+            self._counts = None
+            self.stage = dict(dl.stage)
+            self.stage.update(counts_ms=0.0, fill_ms=0.0, store_bytes=0, store_records=0, extent_ms=0.0, pack_ms=0.0)
+            self.fill(stream)
+        except Exception:
+            self.close()
+            raise
+
+    def __len__(self):
+        return self.n
+
+    def fill(self, stream: int = 0) -> None:
+        dl, f = self._inflater, self._inflater.file
+        p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        t_fill = time.perf_counter()
+        for c0 in range(0, self.n_chunks, self.group):
+            c1 = min(self.n_chunks, c0 + self.group)
+            n = c1 - c0
+            t0 = time.perf_counter()
+            total, offs, sizes, raw = dl._read_chunks(c0, c1)
+            self.stage["read_ms"] += (time.perf_counter() - t0) * 1e3
+            blob_p = C.c_void_p()
+            status = np.zeros(n, np.int32)
+            dl._check(dl.lib.cl_inflate_chunks_device(dl._h, C.c_void_p(dl._comp.data_ptr()), total, p(offs), p(sizes), p(raw), n,
+                                                      C.c_void_p(stream or None), C.byref(blob_p), p(status)), "cl_inflate_chunks_device")
+            bad = np.flatnonzero(status)
+            if len(bad):
+                from . import zinflate
+                raise DamagedChunk("%s: chunk at record %d: %s" % (f.path, (c0 + int(bad[0])) * f.chunk, zinflate.status_text(status[bad[0]])))
+            r0 = c0 * f.chunk
+            n_rec = min(self.n, c1 * f.chunk) - r0               # (the padding of the edge chunk is not a record)
+            blob = np.ctypeslib.as_array(C.cast(blob_p, C.POINTER(C.c_uint8)), (n * f.chunk * self.blob_dtype.itemsize,)).view(self.blob_dtype)
+            self.blob[r0:r0 + n_rec] = blob[:n_rec]
+            st = Stats()
+            dl._check(dl.lib.cl_get_stats(dl._h, C.byref(st)), "cl_get_stats")
+            for k, _t in Stats._fields_:
+                if k != "assemble_ms":
+                    self.stage[k] += getattr(st, k)
+            slots = np.arange(n_rec, dtype=np.int32)
+            try:
+                self.store.append_device(dl._h, slots, r0 + slots, stream)
+            except StoreFull:
+                have = self.store.stats()                   # (the library counted what of the refused group would fit)
+                raise StoreFull("%s does not fit the record store: %d of its %d records fit, in %d bytes of the budget of %d bytes; raise "
+                                "--train-cache-bytes or drop --train-cache-device"
+                                % (f.path, have.records + have.refused_fit_records, self.n, have.refused_fit_bytes, self.capacity_bytes)) from None
+        have = self.store.stats()
+        self.stage.update(store_bytes=have.stored_bytes, store_records=have.records, extent_ms=have.extent_ms, pack_ms=have.pack_ms)
+        self.inflated_bytes = have.inflated_bytes
+        # the members every plan reads, contiguous once (a field of the blob array is a strided view)
+        self._num_reads = np.ascontiguousarray(self.blob["num_reads"].reshape(-1))
+        self._ref_bases = np.ascontiguousarray(self.blob["ref_bases"].reshape(self.n, self.window))
+        self._label = np.ascontiguousarray(self.blob["label"].reshape(-1)) if "label" in self.blob_dtype.names else np.zeros(self.n, np.uint8)
+        # the inflate handle's record buffer and the file go: every batch from here on comes from the store
+        self._inflater.close()
+        self._inflater = None
+        self.stage["fill_ms"] = (time.perf_counter() - t_fill) * 1e3
+
+    def assemble_list(self, indices, seed: int, outs, stream: int = 0) -> IndexedSites:
+        """``DeviceChunkLoader.assemble_list`` from the store: site i is record ``indices[i]`` of the file."""
+        torch = self.torch
+        idx = np.asarray(indices, np.int64).reshape(-1)
+        m = len(idx)
+        if m > self.B:
+            raise ValueError("%d indices: at most %d per call" % (m, self.B))
+        if m and (idx.min() < 0 or idx.max() >= self.n):
+            raise ValueError("record indices %d..%d outside the file's %d records" % (idx.min(), idx.max(), self.n))
+        v = lambda x: C.c_void_p(int(x)) if x else None   # noqa: E731
+        t2 = time.perf_counter()
+        slots = idx.astype(np.int32)
+        plan = plan_records(slots, idx, self._num_reads, self._ref_bases, _RecordTexts(self.blob), self.reads, self.stored_rows, seed)
+        label = np.array(self._label[slots])
+        t3 = time.perf_counter()
+        counts = np.zeros((m, 2, 16), np.int32)
+        if m:
+            first = np.ascontiguousarray(plan.first_rows, np.uint8)
+            rows = np.ascontiguousarray(plan.rows, np.int16) if not first.all() else None
+            self.store.assemble_device(plan.slots, rows, first, self.reads, (plan.ref, plan.ref_mask, plan.var_mask), self.use_q,
+                                       self.use_strand, outs, stream)
+            if self._counts is None:
+                dev = torch.device("cuda", self.device)
+                self._counts = (torch.empty((self.B, 2, 16), dtype=torch.int32, device=dev),
+                                torch.empty((self.B, 2, 16), dtype=torch.int32).pin_memory())
+            d_counts, h_counts = self._counts
+            self.store._check(self.lib.cl_store_center_counts_device(self.store._h, v(outs[0]), m, self.reads, self.window,
+                                                                     v(d_counts.data_ptr()), v(stream)))
+            ts = torch.cuda.ExternalStream(stream, device=d_counts.device) if stream else torch.cuda.default_stream(d_counts.device)
+            with torch.cuda.stream(ts):
+                h_counts[:m].copy_(d_counts[:m], non_blocking=True)
+            ts.synchronize()
+            counts[:] = h_counts[:m].numpy()
+            self.stage["assemble_ms"] += self.store.stats().assemble_ms
+        t4 = time.perf_counter()
+        self.stage["plan_ms"] += (t3 - t2) * 1e3
+        self.stage["counts_ms"] += (t4 - t3) * 1e3
+        self.stage["records"] += m
+        return IndexedSites(plan, label, counts)
+
+    def close(self):
+        if self._inflater is not None:
+            self._inflater.close()
+            self._inflater = None
+        if self.store is not None:
+            self.store.close()
+            self.store = None
 
     def __enter__(self):
         return self

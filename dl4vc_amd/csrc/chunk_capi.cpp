@@ -4,6 +4,7 @@
 // inside the records (assemble_kernels.hip with the record size as the slot stride).  Every extern "C" body catches what it
 // throws; a damaged chunk is a status.
 #include "assemble_host.h"
+#include "chunk_view.h"
 #include "zinflate_device.h"
 
 #include <vector>
@@ -24,6 +25,15 @@ struct cl_loader : pgh::AssembleState {
     cl_stats st{};
     ~cl_loader() { wait_meta(); }                     // (the last assembly may still be reading the records)
 };
+
+// what the record store (store_capi.cpp) reads of a loader: the records of its last cl_inflate_chunks_device call
+clh::RecordsView clh::records_view(const cl_loader* h) {
+    RecordsView v{};
+    v.records = h->d_records.p; v.record_bytes = h->record_bytes; v.n_records = h->n_records;
+    for (int k = 0; k < 3; ++k) v.plane_off[k] = h->plane_off[k];
+    v.window = h->window; v.stored_rows = h->stored_rows; v.device = h->device;
+    return v;
+}
 
 namespace {
 

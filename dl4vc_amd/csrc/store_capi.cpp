@@ -1,0 +1,573 @@
+// cl_store_* of libdl4vc_pileup.so (include/dl4vc_chunks.h): the record store.  The records a cl_loader handle inflated are
+// measured (record_extent), laid out on the host (store_host.h: record order, 16-byte boundaries, slabs no record straddles, the
+// capacity checked before anything is packed), packed into device slabs (store_pack) and from then on assembled from there
+// (store_assemble) -- the file is inflated once per run, not once per epoch.  A store opened with device < 0 keeps its slabs in
+// host memory and takes the CPU twins of the three kernels (cl_store_pack_host, cl_store_assemble_host): the definitions the
+// kernels are tested against.  Every extern "C" body catches what it throws; every index is checked before it is followed.
+//
+// With -DCL_STORE_HOST_ONLY a plain C++ compiler builds the host store alone (tools/asan_store.sh runs it under sanitizers).
+#include "../../include/dl4vc_chunks.h"
+#include "store_host.h"
+
+#ifdef CL_STORE_HOST_ONLY
+#include "capi_shell.h"
+#else
+#include "assemble_host.h"
+#include "chunk_view.h"
+#include "store_device.h"
+#endif
+
+#include <algorithm>
+#include <climits>
+#include <memory>
+#include <string>
+#include <vector>
+
+namespace {
+
+struct Slab {
+    uint64_t cap = 0, used = 0;
+    std::unique_ptr<uint8_t[]> host;                  // a host store's slab: cap bytes
+#ifndef CL_STORE_HOST_ONLY
+    dev::Buffer d;                                    // a device store's: SLAB_GUARD | cap | SLAB_PAD
+#endif
+    uint8_t* data = nullptr;                          // the first of the cap bytes
+};
+
+struct Rec {
+    int32_t slab = 0, kept = -1;                      // kept < 0: not appended yet
+    uint64_t off = 0;
+};
+
+#ifdef CL_STORE_HOST_ONLY
+struct StoreBase {
+    std::string err;
+    int32_t device = -1;
+};
+#else
+typedef pgh::AssembleState StoreBase;
+#endif
+
+}  // namespace
+
+struct cl_store : StoreBase {
+    int32_t window = 0, stored_rows = 0;
+    int64_t n_records = 0;
+    uint64_t capacity = 0, slab_bytes = 0;
+    bool on_host = false;
+    int fill = -1;                                    // >= 0: every new slab's allocation is filled with this byte first
+    st::Cursor cur;
+    std::vector<std::unique_ptr<Slab>> slabs;
+    std::vector<Rec> table;
+    cl_store_stats stats{};
+#ifndef CL_STORE_HOST_ONLY
+    dev::Array<st::DevRec> d_table;
+    dev::Buffer d_app;                                // an append's slots, extents and pack items
+    dev::Pinned h_app;
+    dev::Event ev[6];                                 // extent | copy back ; pack | ; assemble |
+    bool assemble_timed = false;
+    ~cl_store() { wait_meta(); }
+#endif
+};
+
+namespace {
+
+std::string g_store_err;
+
+template <class... A>
+int sfail(cl_store* h, int code, const char* fmt, A... a) { return capi::failf(h ? h->err : g_store_err, code, fmt, a...); }
+
+// the planes of a record lie inside it
+bool planes_inside(const int64_t* plane_off, int64_t record_bytes, int64_t plane) {
+    for (int p = 0; p < 3; ++p)
+        if (plane_off[p] < 0 || plane_off[p] > record_bytes - plane) return false;
+    return true;
+}
+
+// What both append entries check of the records they are given: 0 = fine.
+int check_append(cl_store* h, const char* who, const int32_t* slots, const int32_t* records, int64_t n, int64_t n_slots, int32_t* kept_out) {
+    if (n < 0 || n > INT32_MAX / 4) return sfail(h, -1, "%s: bad record count", who);
+    if (n > 0 && (!slots || !records || !kept_out)) return sfail(h, -1, "%s: null argument", who);
+    for (int64_t i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= n_slots) return sfail(h, -1, "%s: entry %lld names slot %d of %lld", who, (long long)i, slots[i],
+                                                          (long long)n_slots);
+        if (records[i] < 0 || records[i] >= h->n_records) return sfail(h, -1, "%s: entry %lld names record %d of %lld", who, (long long)i,
+                                                                     records[i], (long long)h->n_records);
+        if (h->table[records[i]].kept >= 0) return sfail(h, -1, "%s: record %d is in the store already", who, records[i]);
+    }
+    std::vector<int32_t> seen(records, records + n);
+    std::sort(seen.begin(), seen.end());
+    const auto dup = std::adjacent_find(seen.begin(), seen.end());
+    if (dup != seen.end()) return sfail(h, -1, "%s: record %d is named twice", who, *dup);
+    return 0;
+}
+
+// the layout of an append: places and the new slabs' sizes, or the refusal (-3: the capacity)
+int place_records(cl_store* h, const char* who, st::Cursor& cur, const int32_t* kept, int64_t n, std::vector<st::Place>& places,
+                  std::vector<uint64_t>& new_caps) {
+    places.resize((size_t)n);
+    int64_t at = 0;
+    const int rc = st::layout(cur, kept, n, h->window, h->slab_bytes, h->capacity, places.data(), new_caps, &at);
+    if (rc == st::LAYOUT_CAPACITY) {
+        h->stats.refused_fit_records = at;               // what the caller's message needs: counted here, once
+        h->stats.refused_fit_bytes = (int64_t)h->cur.stored;
+        for (int64_t i = 0; i < at; ++i) h->stats.refused_fit_bytes += (int64_t)st::record_span(kept[i], h->window);
+        return sfail(h, -3, "%s: the store's capacity of %llu bytes would be exceeded: it holds %lld records in %llu bytes, and %lld of "
+                            "the %lld records of this call fit", who, (unsigned long long)h->capacity, (long long)h->stats.records,
+                     (unsigned long long)h->cur.stored, (long long)at, (long long)n);
+    }
+    if (rc == st::LAYOUT_SLAB)
+        return sfail(h, -1, "%s: a record of %llu bytes does not fit a slab of %llu", who,
+                     (unsigned long long)st::record_span(kept[at], h->window), (unsigned long long)h->slab_bytes);
+    return 0;
+}
+
+void commit(cl_store* h, const st::Cursor& cur, const int32_t* records, const int32_t* kept, const std::vector<st::Place>& places, int64_t n,
+            int64_t record_bytes) {
+    for (int64_t i = 0; i < n; ++i) {
+        Rec& r = h->table[records[i]];
+        r.slab = places[i].slab; r.off = places[i].off; r.kept = kept[i];
+        const uint64_t b = st::record_span(kept[i], h->window);
+        if (b) h->slabs[r.slab]->used = r.off + b;
+    }
+    h->cur = cur;
+    h->stats.records += n;
+    h->stats.stored_bytes = (int64_t)cur.stored;
+    h->stats.inflated_bytes += n * record_bytes;
+    h->stats.slabs = (int64_t)h->slabs.size();
+}
+
+// What both assemble entries check: 0 = fine.
+int check_assemble(cl_store* h, const char* who, const int32_t* records, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t R,
+                   const void* const* pointers, int n_pointers) {
+    const int32_t S = h->stored_rows;
+    if (m < 0 || R < 1) return sfail(h, -1, "%s: bad shape", who);
+    if (R > S) return sfail(h, -1, "%s: %d rows per site but only %d are stored", who, R, S);
+    if (m > INT32_MAX / 4 || (int64_t)R * h->window > INT32_MAX / 2) return sfail(h, -1, "%s: too large", who);
+    if (m == 0) return 0;
+    if (!records) return sfail(h, -1, "%s: null argument", who);
+    for (int k = 0; k < n_pointers; ++k)
+        if (!pointers[k]) return sfail(h, -1, "%s: null argument", who);
+    for (int64_t i = 0; i < m; ++i) {
+        if (records[i] < 0 || records[i] >= h->n_records) return sfail(h, -1, "%s: site %lld names record %d of %lld", who, (long long)i,
+                                                                     records[i], (long long)h->n_records);
+        if (h->table[records[i]].kept < 0) return sfail(h, -1, "%s: site %lld names record %d, which is not in the store", who, (long long)i,
+                                                       records[i]);
+        if (rows && !(first_rows && first_rows[i])) {
+            const int16_t* r = rows + (size_t)i * R;
+            for (int k = 0; k < R; ++k)
+                if (r[k] < 0 || r[k] >= S) return sfail(h, -1, "%s: site %lld row %d names stored row %d of %d", who, (long long)i, k, (int)r[k], S);
+        }
+    }
+    return 0;
+}
+
+int extent_arguments(cl_store* h, const char* who, const uint8_t* inflated, uint64_t inflated_bytes, int64_t record_bytes,
+                     const int64_t* plane_off, int32_t S, int32_t W, int64_t* n_slots) {
+    if (!plane_off || S < 1 || W < 1 || record_bytes < 1 || (int64_t)S * W > (1 << 24)) return sfail(h, -1, "%s: bad shape", who);
+    if (!planes_inside(plane_off, record_bytes, (int64_t)S * W))
+        return sfail(h, -1, "%s: a plane of %d rows of %d columns does not lie inside a record of %lld bytes", who, S, W, (long long)record_bytes);
+    if (inflated_bytes && !inflated) return sfail(h, -1, "%s: null argument", who);
+    *n_slots = (int64_t)(inflated_bytes / (uint64_t)record_bytes);
+    return 0;
+}
+
+#ifndef CL_STORE_HOST_ONLY
+#define ST_TRY(x) DEV_TRY(h->err, "", x)
+
+int open_device(cl_store* h) {
+    ST_TRY(hipSetDevice(h->device));
+    ST_TRY(h->d_table.alloc((size_t)std::max<int64_t>(h->n_records, 1)));
+    ST_TRY(hipMemset(h->d_table.p, 0, (size_t)std::max<int64_t>(h->n_records, 1) * sizeof(st::DevRec)));
+    for (dev::Event& e : h->ev) ST_TRY(e.ensure(hipEventBlockingSync));
+    return 0;
+}
+
+int append_device(cl_store* h, cl_loader_t* loader, const int32_t* slots, const int32_t* records, int64_t n, void* stream, int32_t* kept_out) {
+    const char* who = "cl_store_append_device";
+    if (h->on_host) return sfail(h, -1, "%s: the store was opened in host memory", who);
+    if (!loader) return sfail(h, -1, "%s: null loader", who);
+    const clh::RecordsView v = clh::records_view(loader);
+    if (v.window != h->window || v.stored_rows != h->stored_rows)
+        return sfail(h, -1, "%s: the loader holds records of %d rows of %d columns, the store of %d of %d", who, v.stored_rows, v.window,
+                     h->stored_rows, h->window);
+    if (v.device != h->device) return sfail(h, -1, "%s: the loader is on device %d, the store on device %d", who, v.device, h->device);
+    if (const int rc = check_append(h, who, slots, records, n, v.n_records, kept_out)) return rc;
+    if (n == 0) return 0;
+    dev::DeviceGuard guard;
+    ST_TRY(hipSetDevice(h->device));
+    h->wait_meta();
+    hipStream_t s = (hipStream_t)stream;
+    const size_t b_i32 = (size_t)n * sizeof(int32_t), b_items = (size_t)n * sizeof(st::PackItem);
+    const size_t o_kept = (b_i32 + 15) & ~(size_t)15, o_items = 2 * o_kept;
+    if (h->d_app.ensure(o_items + b_items) != hipSuccess) return sfail(h, -2, "hipMalloc of the append tables failed");
+    if (h->h_app.ensure(o_items + b_items) != hipSuccess) return sfail(h, -2, "hipHostMalloc of the append staging failed");
+    st::Source src{};
+    src.records = v.records; src.record_bytes = v.record_bytes; src.S = h->stored_rows; src.W = h->window;
+    for (int p = 0; p < 3; ++p) src.plane_off[p] = v.plane_off[p];
+    memcpy(h->h_app.p, slots, b_i32);
+    int32_t* h_kept = (int32_t*)(h->h_app.p + o_kept);
+    ST_TRY(hipMemcpyAsync(h->d_app.p, h->h_app.p, b_i32, hipMemcpyHostToDevice, s));
+    ST_TRY(hipEventRecord(h->ev[0], s));
+    ST_TRY(st::launch_extent(src, (const int32_t*)h->d_app.p, n, (int32_t*)(h->d_app.p + o_kept), s));
+    ST_TRY(hipEventRecord(h->ev[1], s));
+    ST_TRY(hipMemcpyAsync(h_kept, h->d_app.p + o_kept, b_i32, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+    for (int64_t i = 0; i < n; ++i) {
+        if (h_kept[i] < 0 || h_kept[i] > h->stored_rows) return sfail(h, -2, "%s: the device gave an extent of %d rows", who, h_kept[i]);
+        kept_out[i] = h_kept[i];
+    }
+    st::Cursor cur = h->cur;
+    std::vector<st::Place> places;
+    std::vector<uint64_t> new_caps;
+    if (const int rc = place_records(h, who, cur, kept_out, n, places, new_caps)) return rc;
+    const size_t had = h->slabs.size();
+    for (uint64_t cap : new_caps) {
+        std::unique_ptr<Slab> slab(new Slab());
+        const size_t bytes = (size_t)(st::SLAB_GUARD + cap + st::SLAB_PAD);
+        hipError_t e = slab->d.alloc(bytes);
+        if (e == hipSuccess && h->fill >= 0) e = hipMemsetAsync(slab->d.p, h->fill, bytes, s);
+        if (e != hipSuccess) {
+            h->slabs.resize(had);
+            return sfail(h, -2, "%s: hipMalloc of a slab of %llu bytes failed: %s", who, (unsigned long long)cap, hipGetErrorString(e));
+        }
+        slab->cap = cap;
+        slab->data = slab->d.p + st::SLAB_GUARD;
+        h->slabs.push_back(std::move(slab));
+    }
+    st::PackItem* items = (st::PackItem*)(h->h_app.p + o_items);
+    for (int64_t i = 0; i < n; ++i) {
+        const uint64_t addr = kept_out[i] ? (uint64_t)reinterpret_cast<uintptr_t>(h->slabs[places[i].slab]->data + places[i].off) : 0;
+        items[i] = st::PackItem{addr, slots[i], kept_out[i], records[i], 0};
+    }
+    hipError_t rc = hipMemcpyAsync(h->d_app.p + o_items, items, b_items, hipMemcpyHostToDevice, s);
+    if (rc == hipSuccess) rc = hipEventRecord(h->ev[2], s);
+    if (rc == hipSuccess) rc = st::launch_pack(src, (const st::PackItem*)(h->d_app.p + o_items), n, h->d_table.p, s);
+    if (rc == hipSuccess) rc = hipEventRecord(h->ev[3], s);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(s);
+    if (rc != hipSuccess) {
+        (void)hipStreamSynchronize(s);                    // (nothing of the call is in flight when its slabs go)
+        h->slabs.resize(had);
+        return sfail(h, -2, "%s: device: %s", who, hipGetErrorString(rc));
+    }
+    float ms[2] = {0, 0};
+    ST_TRY(hipEventElapsedTime(&ms[0], h->ev[0], h->ev[1]));
+    ST_TRY(hipEventElapsedTime(&ms[1], h->ev[2], h->ev[3]));
+    h->stats.extent_ms += ms[0];
+    h->stats.pack_ms += ms[1];
+    commit(h, cur, records, kept_out, places, n, v.record_bytes);
+    return 0;
+}
+
+int assemble_device(cl_store* h, const int32_t* records, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t R,
+                    const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int32_t use_q, int32_t use_strand, uint8_t* const out[6],
+                    void* stream) {
+    const char* who = "cl_store_assemble_device";
+    if (h->on_host) return sfail(h, -1, "%s: the store was opened in host memory", who);
+    const void* ptrs[9] = {ref, ref_mask, var_mask, out[0], out[1], out[2], out[3], out[4], out[5]};
+    if (const int rc = check_assemble(h, who, records, rows, first_rows, m, R, ptrs, 9)) return rc;
+    if (m == 0) return 0;
+    const int32_t L = h->window;
+    bool any_rows = false;
+    for (int64_t i = 0; i < m && rows && !any_rows; ++i) any_rows = !(first_rows && first_rows[i]);
+    dev::DeviceGuard guard;
+    if (hipSetDevice(h->device) != hipSuccess) return sfail(h, -2, "hipSetDevice(%d) failed", h->device);
+    if (h->ev_meta.ensure(hipEventDisableTiming) != hipSuccess) return sfail(h, -2, "hipEventCreate failed");
+    if (h->meta_busy) {                                  // the previous call's staging and device copies are still its own
+        if (hipEventSynchronize(h->ev_meta) != hipSuccess) return sfail(h, -2, "hipEventSynchronize failed");
+        h->meta_busy = false;
+    }
+    const size_t b_sites = (size_t)m * sizeof(pg::SiteSrc), b_rows = any_rows ? (size_t)m * R * sizeof(int16_t) : 0;
+    const size_t b_dev = b_sites + b_rows, b_line = (size_t)m * L;
+    if (h->d_meta.ensure(b_dev) != hipSuccess) return sfail(h, -2, "hipMalloc of the assembly table failed");
+    if (h->h_meta.ensure(b_dev + 3 * b_line) != hipSuccess) return sfail(h, -2, "hipHostMalloc of the assembly staging failed");
+    pg::SiteSrc* hs = (pg::SiteSrc*)h->h_meta.p;
+    for (int64_t i = 0; i < m; ++i) hs[i] = pg::SiteSrc{records[i], (!rows || (first_rows && first_rows[i])) ? 1 : 0};
+    if (b_rows) memcpy(h->h_meta.p + b_sites, rows, b_rows);
+    uint8_t* lines = h->h_meta.p + b_dev;
+    memcpy(lines, ref, b_line); memcpy(lines + b_line, ref_mask, b_line); memcpy(lines + 2 * b_line, var_mask, b_line);
+    hipStream_t s = (hipStream_t)stream;
+    const bool timed = hipEventRecord(h->ev[4], s) == hipSuccess;
+    hipError_t rc = hipMemcpyAsync(h->d_meta.p, h->h_meta.p, b_dev, hipMemcpyHostToDevice, s);
+    for (int c = 0; c < 3 && rc == hipSuccess; ++c)
+        rc = hipMemcpyAsync(out[3 + c], lines + c * b_line, b_line, hipMemcpyHostToDevice, s);
+    if (rc == hipSuccess) {
+        st::AssembleArgs a{};
+        a.table = h->d_table.p;
+        a.dst[0] = out[0]; a.dst[1] = out[1]; a.dst[2] = out[2];
+        a.sites = (const pg::SiteSrc*)h->d_meta.p;
+        a.rows = (const int16_t*)(h->d_meta.p + b_sites);
+        a.R = R; a.L = L;
+        a.use[0] = 1; a.use[1] = use_q != 0; a.use[2] = use_strand != 0;
+        rc = st::launch_store_assemble(a, (int32_t)m, s);
+    }
+    h->meta_busy = true;                                 // (also after a failure: some of the copies may be enqueued)
+    if (hipEventRecord(h->ev_meta, s) != hipSuccess && rc == hipSuccess) rc = hipErrorUnknown;
+    if (rc != hipSuccess) return sfail(h, -2, "device: %s", hipGetErrorString(rc));
+    h->assemble_timed = timed && hipEventRecord(h->ev[5], s) == hipSuccess;
+    return 0;
+}
+#endif
+
+int pack_host(cl_store* h, const uint8_t* inflated, uint64_t inflated_bytes, int64_t record_bytes, const int64_t* plane_off, const int32_t* slots,
+              const int32_t* records, int64_t n, int32_t* kept_out) {
+    const char* who = "cl_store_pack_host";
+    if (!h->on_host) return sfail(h, -1, "%s: the store was opened on a device", who);
+    int64_t n_slots = 0;
+    if (const int rc = extent_arguments(h, who, inflated, inflated_bytes, record_bytes, plane_off, h->stored_rows, h->window, &n_slots)) return rc;
+    if (const int rc = check_append(h, who, slots, records, n, n_slots, kept_out)) return rc;
+    for (int64_t i = 0; i < n; ++i)
+        kept_out[i] = st::extent_host(inflated + (size_t)slots[i] * (size_t)record_bytes, plane_off, h->stored_rows, h->window);
+    st::Cursor cur = h->cur;
+    std::vector<st::Place> places;
+    std::vector<uint64_t> new_caps;
+    if (const int rc = place_records(h, who, cur, kept_out, n, places, new_caps)) return rc;
+    for (uint64_t cap : new_caps) {
+        std::unique_ptr<Slab> slab(new Slab());
+        slab->host.reset(new uint8_t[(size_t)cap]);
+        if (h->fill >= 0) memset(slab->host.get(), h->fill, (size_t)cap);
+        slab->cap = cap;
+        slab->data = slab->host.get();
+        h->slabs.push_back(std::move(slab));
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (kept_out[i])
+            st::pack_host(inflated + (size_t)slots[i] * (size_t)record_bytes, plane_off, h->window, kept_out[i],
+                          h->slabs[places[i].slab]->data + places[i].off);
+    commit(h, cur, records, kept_out, places, n, record_bytes);
+    return 0;
+}
+
+int assemble_host(cl_store* h, const int32_t* records, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t R, const uint8_t* ref,
+                  const uint8_t* ref_mask, const uint8_t* var_mask, int32_t use_q, int32_t use_strand, uint8_t* const out[6]) {
+    const char* who = "cl_store_assemble_host";
+    if (!h->on_host) return sfail(h, -1, "%s: the store was opened on a device", who);
+    const void* ptrs[9] = {ref, ref_mask, var_mask, out[0], out[1], out[2], out[3], out[4], out[5]};
+    if (const int rc = check_assemble(h, who, records, rows, first_rows, m, R, ptrs, 9)) return rc;
+    const int32_t L = h->window;
+    const size_t span = (size_t)R * L;
+    const int use[3] = {1, use_q != 0, use_strand != 0};
+    for (int64_t i = 0; i < m; ++i) {
+        const Rec& r = h->table[records[i]];
+        const bool first = !rows || (first_rows && first_rows[i]);
+        for (int p = 0; p < 3; ++p) {
+            uint8_t* dst = out[p] + (size_t)i * span;
+            if (!use[p]) {
+                memset(dst, 0, span);
+                continue;
+            }
+            const uint8_t* src = r.kept ? h->slabs[r.slab]->data + r.off + (size_t)p * r.kept * L : nullptr;
+            st::assemble_plane_host(src, r.kept, first ? nullptr : rows + (size_t)i * R, R, L, dst);
+        }
+    }
+    const size_t b_line = (size_t)m * L;
+    if (b_line) {
+        memcpy(out[3], ref, b_line); memcpy(out[4], ref_mask, b_line); memcpy(out[5], var_mask, b_line);
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* cl_store_last_error(const cl_store_t* h) { return h ? h->err.c_str() : g_store_err.c_str(); }
+
+int cl_store_open(int32_t window, int32_t stored_rows, int64_t n_records, uint64_t capacity_bytes, uint64_t slab_bytes, int32_t device,
+                  cl_store_t** out) {
+    if (!out) return sfail(nullptr, -1, "cl_store_open: null argument");
+    *out = nullptr;
+    if (window < 1 || stored_rows < 1 || stored_rows > INT16_MAX || (int64_t)window * stored_rows > (1 << 24) || n_records < 0 ||
+        n_records > INT32_MAX / 2)
+        return sfail(nullptr, -1, "cl_store_open: bad shape");
+    if (slab_bytes < 16 || (slab_bytes & 15) || slab_bytes > ((uint64_t)1 << 40))
+        return sfail(nullptr, -1, "cl_store_open: a slab holds a multiple of 16 bytes, 16 to 2^40");
+#ifdef CL_STORE_HOST_ONLY
+    if (device >= 0) return sfail(nullptr, -1, "cl_store_open: this build has the host store only (device < 0)");
+#endif
+    return capi::guarded(g_store_err, "cl_store_open", [&] {
+        std::unique_ptr<cl_store> h(new cl_store());
+        h->window = window; h->stored_rows = stored_rows; h->n_records = n_records;
+        h->capacity = capacity_bytes; h->slab_bytes = slab_bytes;
+        h->device = device; h->on_host = device < 0;
+        h->table.resize((size_t)n_records);
+#ifndef CL_STORE_HOST_ONLY
+        if (!h->on_host) {
+            dev::DeviceGuard guard;
+            if (const int rc = open_device(h.get())) {
+                g_store_err = h->err;
+                return rc;
+            }
+        }
+#endif
+        *out = h.release();
+        return 0;
+    });
+}
+
+void cl_store_close(cl_store_t* h) {
+    try {
+#ifndef CL_STORE_HOST_ONLY
+        if (h && !h->on_host) {
+            dev::DeviceGuard guard;
+            (void)hipSetDevice(h->device);
+            delete h;
+            return;
+        }
+#endif
+        delete h;
+    } catch (...) {
+    }
+}
+
+int cl_store_debug_fill(cl_store_t* h, int32_t value) {
+    if (!h) return sfail(nullptr, -1, "cl_store_debug_fill: null handle");
+    if (value < -1 || value > 255) return sfail(h, -1, "cl_store_debug_fill: -1 (no fill) or a byte");
+    h->fill = value;
+    return 0;
+}
+
+int cl_store_append_device(cl_store_t* h, cl_loader_t* loader, const int32_t* slots, const int32_t* records, int64_t n, void* stream,
+                           int32_t* kept_out) {
+    if (!h) return sfail(nullptr, -1, "cl_store_append_device: null handle");
+#ifdef CL_STORE_HOST_ONLY
+    (void)loader; (void)slots; (void)records; (void)n; (void)stream; (void)kept_out;
+    return sfail(h, -1, "cl_store_append_device: this build has the host store only");
+#else
+    return capi::guarded(h->err, "cl_store_append_device", [&] { return append_device(h, loader, slots, records, n, stream, kept_out); });
+#endif
+}
+
+int cl_store_assemble_device(cl_store_t* h, const int32_t* records, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t reads,
+                             const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int32_t use_q, int32_t use_strand,
+                             uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out,
+                             uint8_t* var_mask_out, void* stream) {
+    if (!h) return sfail(nullptr, -1, "cl_store_assemble_device: null handle");
+#ifdef CL_STORE_HOST_ONLY
+    (void)records; (void)rows; (void)first_rows; (void)m; (void)reads; (void)ref; (void)ref_mask; (void)var_mask; (void)use_q; (void)use_strand;
+    (void)reads_out; (void)qual_out; (void)strand_out; (void)ref_out; (void)ref_mask_out; (void)var_mask_out; (void)stream;
+    return sfail(h, -1, "cl_store_assemble_device: this build has the host store only");
+#else
+    return capi::guarded(h->err, "cl_store_assemble_device", [&] {
+        uint8_t* const out[6] = {reads_out, qual_out, strand_out, ref_out, ref_mask_out, var_mask_out};
+        return assemble_device(h, records, rows, first_rows, m, reads, ref, ref_mask, var_mask, use_q, use_strand, out, stream);
+    });
+#endif
+}
+
+int cl_store_center_counts_device(cl_store_t* h, const uint8_t* reads, int64_t m, int32_t rows, int32_t window, int32_t* counts, void* stream) {
+    if (!h) return sfail(nullptr, -1, "cl_store_center_counts_device: null handle");
+#ifdef CL_STORE_HOST_ONLY
+    (void)reads; (void)m; (void)rows; (void)window; (void)counts; (void)stream;
+    return sfail(h, -1, "cl_store_center_counts_device: this build has the host store only");
+#else
+    return capi::guarded(h->err, "cl_store_center_counts_device", [&] {
+        if (h->on_host) return sfail(h, -1, "cl_store_center_counts_device: the store was opened in host memory");
+        if (m < 0 || m > INT32_MAX || rows < 1 || window < 3) return sfail(h, -1, "cl_store_center_counts_device: bad shape");
+        if (m > 0 && (!reads || !counts)) return sfail(h, -1, "cl_store_center_counts_device: null argument");
+        dev::DeviceGuard guard;
+        ST_TRY(hipSetDevice(h->device));
+        ST_TRY(pg::launch_center_counts(reads, m, rows, window, (window - 1) / 2, counts, (hipStream_t)stream));
+        return 0;
+    });
+#endif
+}
+
+int cl_store_extent_host(const uint8_t* inflated, uint64_t inflated_bytes, int64_t record_bytes, const int64_t* plane_off, int32_t stored_rows,
+                         int32_t window, const int32_t* slots, int64_t n, int32_t* kept_out) {
+    const char* who = "cl_store_extent_host";
+    return capi::guarded(g_store_err, who, [&] {
+        int64_t n_slots = 0;
+        if (const int rc = extent_arguments(nullptr, who, inflated, inflated_bytes, record_bytes, plane_off, stored_rows, window, &n_slots)) return rc;
+        if (n < 0) return sfail(nullptr, -1, "%s: bad record count", who);
+        if (n > 0 && (!slots || !kept_out)) return sfail(nullptr, -1, "%s: null argument", who);
+        for (int64_t i = 0; i < n; ++i)
+            if (slots[i] < 0 || slots[i] >= n_slots) return sfail(nullptr, -1, "%s: entry %lld names slot %d of %lld", who, (long long)i, slots[i],
+                                                              (long long)n_slots);
+        for (int64_t i = 0; i < n; ++i) kept_out[i] = st::extent_host(inflated + (size_t)slots[i] * (size_t)record_bytes, plane_off, stored_rows, window);
+        return 0;
+    });
+}
+
+int cl_store_pack_host(cl_store_t* h, const uint8_t* inflated, uint64_t inflated_bytes, int64_t record_bytes, const int64_t* plane_off,
+                       const int32_t* slots, const int32_t* records, int64_t n, int32_t* kept_out) {
+    if (!h) return sfail(nullptr, -1, "cl_store_pack_host: null handle");
+    return capi::guarded(h->err, "cl_store_pack_host", [&] {
+        return pack_host(h, inflated, inflated_bytes, record_bytes, plane_off, slots, records, n, kept_out);
+    });
+}
+
+int cl_store_assemble_host(cl_store_t* h, const int32_t* records, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t reads,
+                           const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int32_t use_q, int32_t use_strand,
+                           uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out,
+                           uint8_t* var_mask_out, void* stream) {
+    (void)stream;
+    if (!h) return sfail(nullptr, -1, "cl_store_assemble_host: null handle");
+    return capi::guarded(h->err, "cl_store_assemble_host", [&] {
+        uint8_t* const out[6] = {reads_out, qual_out, strand_out, ref_out, ref_mask_out, var_mask_out};
+        return assemble_host(h, records, rows, first_rows, m, reads, ref, ref_mask, var_mask, use_q, use_strand, out);
+    });
+}
+
+int cl_store_record(cl_store_t* h, int64_t record, int32_t* slab, int64_t* offset, int32_t* kept) {
+    if (!h || !slab || !offset || !kept) return sfail(h, -1, "cl_store_record: null argument");
+    return capi::guarded(h->err, "cl_store_record", [&] {
+        if (record < 0 || record >= h->n_records) return sfail(h, -1, "cl_store_record: record %lld of %lld", (long long)record, (long long)h->n_records);
+        const Rec& r = h->table[(size_t)record];
+        if (r.kept < 0) return sfail(h, -1, "cl_store_record: record %lld is not in the store", (long long)record);
+        *slab = r.slab; *offset = (int64_t)r.off; *kept = r.kept;
+#ifndef CL_STORE_HOST_ONLY
+        if (!h->on_host) {                               // what the kernels follow: the device's table entry
+            dev::DeviceGuard guard;
+            st::DevRec d{};
+            ST_TRY(hipSetDevice(h->device));
+            ST_TRY(hipMemcpy(&d, h->d_table.p + record, sizeof d, hipMemcpyDeviceToHost));
+            *kept = d.kept; *slab = -1; *offset = -1;
+            if (d.addr == 0) { *slab = 0; *offset = 0; }
+            for (size_t k = 0; k < h->slabs.size() && d.addr; ++k) {
+                const uint64_t base = (uint64_t)reinterpret_cast<uintptr_t>(h->slabs[k]->data);
+                if (d.addr >= base && d.addr < base + h->slabs[k]->cap) { *slab = (int32_t)k; *offset = (int64_t)(d.addr - base); }
+            }
+        }
+#endif
+        return 0;
+    });
+}
+
+int cl_store_slab(cl_store_t* h, int32_t slab, uint8_t* dst, uint64_t dst_bytes, int64_t* data_off, int64_t* used, int64_t* capacity) {
+    if (!h || !data_off || !used || !capacity) return sfail(h, -1, "cl_store_slab: null argument");
+    return capi::guarded(h->err, "cl_store_slab", [&] {
+        if (slab < 0 || (size_t)slab >= h->slabs.size()) return sfail(h, -1, "cl_store_slab: slab %d of %lld", slab, (long long)h->slabs.size());
+        const Slab& s = *h->slabs[slab];
+        *used = (int64_t)s.used; *capacity = (int64_t)s.cap;
+        *data_off = h->on_host ? 0 : st::SLAB_GUARD;
+        const uint64_t bytes = h->on_host ? s.cap : (uint64_t)(st::SLAB_GUARD + s.cap + st::SLAB_PAD);
+        if (!dst) return 0;                              // (the sizes alone)
+        if (dst_bytes < bytes) return sfail(h, -1, "cl_store_slab: the slab's allocation holds %llu bytes", (unsigned long long)bytes);
+        if (h->on_host) {
+            memcpy(dst, s.host.get(), (size_t)bytes);
+            return 0;
+        }
+#ifndef CL_STORE_HOST_ONLY
+        dev::DeviceGuard guard;
+        ST_TRY(hipSetDevice(h->device));
+        ST_TRY(hipMemcpy(dst, s.d.p, (size_t)bytes, hipMemcpyDeviceToHost));
+#endif
+        return 0;
+    });
+}
+
+int cl_store_get_stats(cl_store_t* h, cl_store_stats* out) {
+    if (!h || !out) return sfail(h, -1, "cl_store_get_stats: null argument");
+#ifndef CL_STORE_HOST_ONLY
+    if (h->assemble_timed) {
+        float ms = 0;
+        if (hipEventSynchronize(h->ev[5]) == hipSuccess && hipEventElapsedTime(&ms, h->ev[4], h->ev[5]) == hipSuccess) h->stats.assemble_ms = ms;
+        h->assemble_timed = false;
+    }
+#endif
+    *out = h->stats;
+    return 0;
+}
+
+}  // extern "C"

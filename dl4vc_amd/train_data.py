@@ -260,23 +260,37 @@ class DeviceBatchPrefetcher:
     before.  The lists of an epoch are known at its start (the sampler's feedback acts at the next epoch), so the worker
     runs ahead as far as the plane sets allow.  A plane set returns to the worker through ``DeviceTrainBatch.release``.
 
+    ``resident=True`` (``--train-cache-device gpu``): the file is inflated once, at construction, into a record store in device
+    memory of at most ``cache_bytes`` (``chunk_loader.ResidentRecords``; a file that does not fit, or a damaged chunk, ends the
+    construction with the reason) and closed; the worker skips ``inflate_lists`` and ``batches`` skips ``reserve``: a batch is the
+    host plan, one gather kernel from the store and the counts.  ``stage`` then also holds ``fill_ms``, ``store_bytes`` and
+    ``store_records``, and its ``chunks``, ``compressed_bytes`` and ``inflate_ms`` stop growing once the loader is open.
+
     torch must have been imported before the HIP libraries were loaded (one HIP runtime per process).  Every queue wait ends
     after ``wait_s`` seconds with an error that names what it waited for; an exception of the worker is raised in the consumer."""
 
     AHEAD = 4        # index lists whose chunks are inflated in one launch; twice as many plane sets
 
     def __init__(self, path: str, reads: int, batch_sites: int, device: int = 0, use_q: bool = True, use_strand: bool = True,
-                 wait_s: float = 600.0, ahead: int = AHEAD):
+                 wait_s: float = 600.0, ahead: int = AHEAD, resident: bool = False, cache_bytes: int = 0, slab_bytes: Optional[int] = None):
         import torch
-        from .chunk_loader import DeviceChunkLoader
+        from .chunk_loader import DeviceChunkLoader, ResidentRecords, STORE_SLAB_BYTES
         self.torch, self.path = torch, path
         self.B, self.wait_s = max(1, int(batch_sites)), float(wait_s)
         self.ahead = max(1, int(ahead))
-        # the record buffer starts at one chunk and is sized by ``batches`` for the lists it is given: a shuffled epoch needs up to
-        # ``ahead * batch_sites`` chunks (1 MB each in the production layout), a sequential evaluation pass an eighth of that
-        self.loader = DeviceChunkLoader(path, reads, self.B, device=device, use_q=use_q, use_strand=use_strand, shuffled=self.ahead,
-                                        chunks=1)
+        self.resident = bool(resident)
         self.dev = torch.device("cuda", device)
+        if self.resident:
+            # ``--train-cache-device gpu``: the whole file is inflated once, here, into a record store of at most ``cache_bytes``
+            # (``chunk_loader.ResidentRecords``); every batch of every ``batches`` call is assembled from it
+            with torch.cuda.device(self.dev):
+                self.loader = ResidentRecords(path, reads, self.B, device=device, use_q=use_q, use_strand=use_strand,
+                                              capacity_bytes=cache_bytes, slab_bytes=slab_bytes or STORE_SLAB_BYTES)
+        else:
+            # the record buffer starts at one chunk and is sized by ``batches`` for the lists it is given: a shuffled epoch needs up
+            # to ``ahead * batch_sites`` chunks (1 MB each in the production layout), a sequential evaluation pass an eighth of that
+            self.loader = DeviceChunkLoader(path, reads, self.B, device=device, use_q=use_q, use_strand=use_strand, shuffled=self.ahead,
+                                            chunks=1)
         R, L = self.loader.reads, self.loader.window
         u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=self.dev)   # noqa: E731
         self.sets = [[u8(self.B, R, L) for _ in range(3)] + [u8(self.B, L) for _ in range(3)]
@@ -311,7 +325,7 @@ class DeviceBatchPrefetcher:
         try:
             with self.torch.cuda.device(self.dev):
                 for k, idx in enumerate(lists):
-                    if k % self.ahead == 0:             # the chunks of the next few batches, inflated in one launch
+                    if k % self.ahead == 0 and not self.resident:    # the chunks of the next few batches, inflated in one launch
                         self.loader.inflate_lists(lists[k:k + self.ahead], self.stream.cuda_stream)
                     planes = self._wait(free, "a free plane set for batch %d (the step that read it has not released it)" % k, stop)
                     got = self.loader.assemble_list(idx, kwargs["seed"], [t.data_ptr() for t in planes], self.stream.cuda_stream)
@@ -343,7 +357,8 @@ class DeviceBatchPrefetcher:
         if have != want:
             raise ValueError("the loader was opened for (reads, use_q, use_strand) = %s, the batches ask for %s" % (want, have))
         lists = [np.asarray(idx, np.int64) for idx in index_lists]
-        self.loader.reserve(max([self.loader.chunks_of(lists[k:k + self.ahead]) for k in range(0, len(lists), self.ahead)] or [0]))
+        if not self.resident:
+            self.loader.reserve(max([self.loader.chunks_of(lists[k:k + self.ahead]) for k in range(0, len(lists), self.ahead)] or [0]))
         free, ready, stop = queue.Queue(), queue.Queue(), threading.Event()     # (the plane sets bound what is ready)
         for planes in self.sets:
             free.put(planes)

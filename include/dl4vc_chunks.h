@@ -100,6 +100,81 @@ typedef struct {
 } cl_stats;
 int cl_get_stats(cl_loader_t* h, cl_stats* out);
 
+/* ---- the record store: a file's records inflated once and kept in device memory ---------------------------------------------------
+ * A stored record is its three planes trimmed of their trailing all-zero rows: reads[kept][window] | qual[kept][window] |
+ * strand[kept][window] and zero bytes up to the next multiple of 16, where kept = 1 + the last stored row that holds a non-zero
+ * byte in ANY of the three planes (0: none does).  The trimming is by the bytes, not by num_reads: rows >= kept are all-zero by
+ * definition and the assembly writes them as zeros, so what is assembled from the store equals what cl_assemble_device makes of
+ * the inflated records, byte for byte, for any file.  Records lie in the order they are appended, each at a 16-byte boundary of
+ * a slab; a record that does not fit what is left of the last slab opens the next (none straddles two), a record without rows
+ * takes no byte (slab 0, offset 0).  A slab holds slab_bytes, or what capacity_bytes leaves when that is less.  capacity_bytes
+ * bounds the sum of the stored records' bytes, NOT the allocations: a slab is allocated whole, so the device memory a store takes
+ * exceeds its records' bytes by the unused part of its slabs (less than one slab when the records are many; 272 bytes of guard and
+ * pad per slab besides).  One thread at a time uses a handle. */
+typedef struct cl_store cl_store_t;
+
+/* n_records: the records the store may come to hold (the table's size).  slab_bytes: a multiple of 16.  device < 0: the slabs lie
+ * in host memory and the store takes cl_store_pack_host / cl_store_assemble_host (the CPU definitions) instead of the device
+ * entries. */
+int cl_store_open(int32_t window, int32_t stored_rows, int64_t n_records, uint64_t capacity_bytes, uint64_t slab_bytes, int32_t device,
+                  cl_store_t** out);
+void cl_store_close(cl_store_t* h);
+const char* cl_store_last_error(const cl_store_t* h);   /* h == NULL: the error of a failed cl_store_open or of cl_store_extent_host */
+
+/* Record slots[i] of the loader's last cl_inflate_chunks_device call becomes record records[i] of the store (not in it yet, named
+ * once): the extents are measured on the device (kept_out[i], host memory), the records laid out on the host and packed on the
+ * device.  Enqueued on `stream` and waited for: the loader's record buffer is free again when the call returns.  Returns -3,
+ * with kept_out filled and the store unchanged, when capacity_bytes would be exceeded; any other failure leaves it unchanged too. */
+int cl_store_append_device(cl_store_t* h, cl_loader_t* loader, const int32_t* slots, const int32_t* records, int64_t n, void* stream,
+                           int32_t* kept_out);
+
+/* cl_assemble_device's contract with the store's records as the source: site i takes rows[i] (or the first `reads` rows) of record
+ * records[i]; a row >= kept is zeros.  Records and rows are range-checked before anything is enqueued.  The six outputs are
+ * device pointers; asynchronous on `stream`. */
+int cl_store_assemble_device(cl_store_t* h, const int32_t* records, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t reads,
+                             const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int32_t use_q, int32_t use_strand,
+                             uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out,
+                             uint8_t* var_mask_out, void* stream);
+/* cl_center_counts_device (same kernel, same contract) for a caller that holds a store and no loader any more: the resident loader
+ * closes its cl_loader after the fill, and cl_center_counts_device needs one. */
+int cl_store_center_counts_device(cl_store_t* h, const uint8_t* reads, int64_t m, int32_t rows, int32_t window, int32_t* counts, void* stream);
+
+/* The CPU definitions, all pointers host pointers.  inflated: records of record_bytes, inflated_bytes of them in all (slots are
+ * checked against it), the planes [stored_rows][window] at plane_off[0..2] of each.  cl_store_extent_host: kept_out[i] = the
+ * extent of record slots[i].  cl_store_pack_host: cl_store_append_device on a host store.  cl_store_assemble_host:
+ * cl_store_assemble_device on a host store, same arguments (stream is ignored). */
+int cl_store_extent_host(const uint8_t* inflated, uint64_t inflated_bytes, int64_t record_bytes, const int64_t* plane_off, int32_t stored_rows,
+                         int32_t window, const int32_t* slots, int64_t n, int32_t* kept_out);
+int cl_store_pack_host(cl_store_t* h, const uint8_t* inflated, uint64_t inflated_bytes, int64_t record_bytes, const int64_t* plane_off,
+                       const int32_t* slots, const int32_t* records, int64_t n, int32_t* kept_out);
+int cl_store_assemble_host(cl_store_t* h, const int32_t* records, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t reads,
+                           const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int32_t use_q, int32_t use_strand,
+                           uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out,
+                           uint8_t* var_mask_out, void* stream);
+
+/* ---- test and debug entries: what the tests need to see of a store; no loader or command-line path calls them ------------------- */
+/* Where a record lies: for a device store read from the table in device memory that the kernels follow. */
+int cl_store_record(cl_store_t* h, int64_t record, int32_t* slab, int64_t* offset, int32_t* kept);
+/* A slab's sizes, and with dst != NULL a copy of its whole allocation (host memory): the slab's `capacity` bytes begin data_off
+ * bytes in (a device slab has 256 bytes that are never written in front of them and 16 behind, so that a 16-byte load at a
+ * record's last bytes stays inside the allocation), the first `used` of them hold records. */
+int cl_store_slab(cl_store_t* h, int32_t slab, uint8_t* dst, uint64_t dst_bytes, int64_t* data_off, int64_t* used, int64_t* capacity);
+/* Debug only (it adds a fill to every slab allocation): every slab allocated from now on is filled with `value` (0..255; -1: not
+ * filled, the default) before records are packed into it: what a test needs to see that no byte outside the records is written. */
+int cl_store_debug_fill(cl_store_t* h, int32_t value);
+
+typedef struct {
+    int64_t records;             /* in the store */
+    int64_t stored_bytes;        /* the sum of their bytes in the slabs */
+    int64_t inflated_bytes;      /* the bytes of the inflated records they replace */
+    int64_t slabs;
+    int64_t refused_fit_records; /* of the last append the capacity refused (-3): how many of its records would have fit, */
+    int64_t refused_fit_bytes;   /* and the bytes the store would hold with them (0 / 0: no append was refused) */
+    double extent_ms, pack_ms;   /* record_extent / store_pack of all appends, device time */
+    double assemble_ms;          /* the last cl_store_assemble_device (cl_store_get_stats waits for it) */
+} cl_store_stats;
+int cl_store_get_stats(cl_store_t* h, cl_store_stats* out);
+
 #ifdef __cplusplus
 }
 #endif

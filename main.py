@@ -109,6 +109,8 @@ def train_main(args, argv) -> int:
     if device_loader:
         print("--train-loader-device gpu: batches are assembled on the GPU by one loader thread per file; --num-data-workers %d "
               "starts no worker process" % args.num_data_workers)
+    resident = getattr(args, "train_cache_device", None) == "gpu"
+    cache = {"left": None}                               # bytes of the budget the files still to be opened may take
     per_rank = -(-args.batch_size // world)
     trainer = DanTrainer(cfg, hyper, max_batch=per_rank, device_id=0)
     if args.modelload:
@@ -123,10 +125,28 @@ def train_main(args, argv) -> int:
         # loader workers (main.py:59-60: DataLoader(num_workers=args.num_data_workers)); 0 = assemble in this process
         if not device_loader:
             return BatchPrefetcher(path, args.num_data_workers)
+        if not resident:
+            try:
+                return DeviceBatchPrefetcher(path, cfg.reads, batch_sites, device=0, use_q=cfg.use_q, use_strand=cfg.use_strand)
+            except (ValueError, RuntimeError) as e:
+                raise SystemExit("--train-loader-device gpu: %s" % e)
+        if cache["left"] is None:
+            # one budget for the trimmed records of both files; by default three quarters of what is free now that the trainer has
+            # allocated (it bounds the records' bytes: each file's last slab is allocated whole)
+            import torch
+            cache["left"] = getattr(args, "train_cache_bytes", 0) or torch.cuda.mem_get_info(0)[0] * 3 // 4
+        t0 = time.time()
         try:
-            return DeviceBatchPrefetcher(path, cfg.reads, batch_sites, device=0, use_q=cfg.use_q, use_strand=cfg.use_strand)
+            loader = DeviceBatchPrefetcher(path, cfg.reads, batch_sites, device=0, use_q=cfg.use_q, use_strand=cfg.use_strand,
+                                           resident=True, cache_bytes=cache["left"])
         except (ValueError, RuntimeError) as e:
-            raise SystemExit("--train-loader-device gpu: %s" % e)
+            raise SystemExit("--train-cache-device gpu: %s" % e)
+        st = loader.stage
+        cache["left"] -= st["store_bytes"]
+        print("--train-cache-device gpu: %s: %d records resident in %d bytes (%.3f of their %d inflated bytes), filled in %.2f s"
+              % (path, st["store_records"], st["store_bytes"], st["store_bytes"] / max(1, loader.loader.inflated_bytes),
+                 loader.loader.inflated_bytes, time.time() - t0), flush=True)
+        return loader
 
     try:
         train_loop(args, cfg, hyper, trainer, open_loader, per_rank, rank, world, dist, all_reduce, gather, exchange)
@@ -347,6 +367,19 @@ def check_train_loader_device_arguments(args) -> None:
                          "on the GPU); inference from a --test_file has --loader-device gpu")
 
 
+def check_train_cache_arguments(args) -> None:
+    """--train-cache-device / --train-cache-bytes: what they refuse (whether the files fit is known when they are filled)."""
+    device, budget = getattr(args, "train_cache_device", None), getattr(args, "train_cache_bytes", None)
+    if device is None:
+        raise SystemExit("--train-cache-bytes is the budget of --train-cache-device gpu, which is not given")
+    if device != "gpu":
+        raise SystemExit("--train-cache-device must be gpu")
+    if args.train_loader_device != "gpu":
+        raise SystemExit("--train-cache-device gpu keeps the records of --train-loader-device gpu resident: it needs that option")
+    if budget is not None and budget < 0:
+        raise SystemExit("--train-cache-bytes must not be negative (0: three quarters of the free device memory)")
+
+
 def check_loader_device_arguments(args) -> None:
     """--loader-device: what it refuses (the file's own properties are checked when it is opened)."""
     if args.loader_device != "gpu":
@@ -375,6 +408,8 @@ def main(argv=None) -> int:
         check_loader_device_arguments(args)
     if args.train_loader_device is not None:
         check_train_loader_device_arguments(args)
+    if hasattr(args, "train_cache_device") or hasattr(args, "train_cache_bytes"):
+        check_train_cache_arguments(args)
     if args.test_bam:
         check_bam_arguments(args)
     if args.train_file:

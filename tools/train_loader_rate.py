@@ -2,7 +2,9 @@
 """``--train-loader-device gpu`` against the loader workers, on one generated file of production-layout records (200 stored rows of
 201 columns, a model of 100 reads) read in shuffled order.
 
-Arms: ``--num-data-workers 5``, ``--num-data-workers 16`` and the device loader.  Every measurement is a fresh process that runs
+Arms: ``--num-data-workers 5``, ``--num-data-workers 16``, the device loader (``device``) and the device loader with the files resident
+(``resident``: ``--train-cache-device gpu``; its fill lies in front of the timed window and is reported on its own as ``fill_ms``, with
+the stored bytes per record and their ratio to the inflated bytes).  Every measurement is a fresh process that runs
 the epoch loop of ``main.py --train_file`` -- ``trainer.train_epoch`` over the whole file (a plain shuffled epoch, batches of
 ``--batch``), then ``trainer.evaluate`` over the test file -- under its own ``timeout``; three alternating rounds; the first
 process that fails or runs out of time ends the run.  Per arm and round:
@@ -19,7 +21,7 @@ process that fails or runs out of time ends the run.  Per arm and round:
 
 One JSON record.
 
-    python tools/train_loader_rate.py --dir /tmp/tlr [--records 4096 --test-records 2048 --rounds 3] [--out profiles/train_loader_device.json]
+    python tools/train_loader_rate.py --dir /tmp/tlr [--records 4096 --test-records 2048 --rounds 3] [--out profiles/train_cache_device.json]
 """
 import argparse
 import json
@@ -31,7 +33,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ARMS = (("workers5", 5), ("workers16", 16), ("device", None))
+ARMS = (("workers5", 5), ("workers16", 16), ("device", None), ("resident", "resident"))
 
 
 def make_inputs(d, records, test_records):
@@ -74,6 +76,9 @@ def child(workers, train, test, batch, skip):
     def loader(path):
         if workers is None:
             return DeviceBatchPrefetcher(path, cfg.reads, batch, use_q=cfg.use_q, use_strand=cfg.use_strand)
+        if workers == "resident":
+            return DeviceBatchPrefetcher(path, cfg.reads, batch, use_q=cfg.use_q, use_strand=cfg.use_strand, resident=True,
+                                         cache_bytes=torch.cuda.mem_get_info(0)[0] * 3 // 8)
         return BatchPrefetcher(path, workers)
 
     stamps = {"train": [], "eval": []}
@@ -86,7 +91,7 @@ def child(workers, train, test, batch, skip):
             evaluate(net, tsrc, hyper, batch, write=lambda _t: stamps["eval"].append(time.perf_counter()), prefetcher=el)
             net.close()
             stages = {}
-            if workers is None:
+            if workers is None or workers == "resident":
                 for name, l in (("train", tl), ("eval", el)):
                     stages[name] = {k: round(v, 2) if isinstance(v, float) else int(v) for k, v in l.stage.items()}
         cpu1 = cpu_seconds()                                          # (the workers are reaped: their time is in RUSAGE_CHILDREN)
@@ -95,12 +100,17 @@ def child(workers, train, test, batch, skip):
     tr, ev = stamps["train"][:-1], stamps["eval"]                     # (train_epoch's last call is its closing summary line)
     k = min(skip, len(tr) - 2)
     ke = min(2, len(ev) - 2)
-    res = {"arm": "device" if workers is None else "workers%d" % workers, "train_sites": n_train, "eval_sites": n_eval, "steps": len(tr),
+    res = {"arm": "device" if workers is None else workers if workers == "resident" else "workers%d" % workers, "train_sites": n_train, "eval_sites": n_eval, "steps": len(tr),
            "steps_per_s": round((len(tr) - 1 - k) / (tr[-1] - tr[k]), 3),
            "eval_sites_per_s": round((len(ev) - 1 - ke) * batch / (ev[-1] - ev[ke]), 1),
            "cpu_s": round(cpu1 - cpu0, 2), "cpu_s_per_1000_sites": round((cpu1 - cpu0) * 1000.0 / (n_train + n_eval), 3)}
     if stages:
         res["stages"] = stages
+    if workers == "resident":
+        both = [stages["train"], stages["eval"]]
+        res["fill_ms"] = round(sum(s["fill_ms"] for s in both), 1)
+        res["stored_bytes_per_record"] = round(sum(s["store_bytes"] for s in both) / sum(s["store_records"] for s in both), 1)
+        res["stored_over_inflated"] = round(sum(s["store_bytes"] for s in both) / sum(s["inflated_bytes"] for s in both), 4)
     print(json.dumps(res))
 
 
@@ -153,6 +163,9 @@ def main():
                     "steps_over_device_resident": [round(r[arm]["steps_per_s"] / resident, 3) for r in rounds],
                     "eval_sites_per_s": [r[arm]["eval_sites_per_s"] for r in rounds],
                     "cpu_s_per_1000_sites": [r[arm]["cpu_s_per_1000_sites"] for r in rounds]}
+        for k in ("fill_ms", "stored_bytes_per_record", "stored_over_inflated"):
+            if k in rounds[0][arm]:
+                res[arm][k] = [r[arm][k] for r in rounds]
     line = json.dumps(res)
     print(line)
     if a.out:
