@@ -73,7 +73,7 @@ _EXTRA = [
     ("--test_bam", "str", None, "inference straight from a coordinate-sorted BAM (with --test_fasta and --sample_vcf, the candidate "
                                 "VCF): pileups are encoded and scored on the GPU and no candidates.hdf is written; replaces --test_file"),
     ("--test_fasta", "str", None, "reference FASTA of --test_bam"),
-    ("--inflate-device", "str", None, "gpu: with --test_bam, the pileup encoder inflates the BAM's BGZF blocks and frames its records "
+    ("--inflate-device", "str", None, "gpu: with --test_bam or --train_bam, the pileup encoder inflates the BAM's BGZF blocks and frames its records "
                                       "on the GPU as well (needs the .bai; same scored VCF)"),
     ("--loader-device", "str", None, "gpu: with --test_file, the file's HDF5 chunks are inflated and its sites assembled on the GPU "
                                      "(the host only reads the raw chunks and plans rows and allele masks); same scored VCF"),
@@ -91,6 +91,21 @@ _EXTRA = [
      "with --train-cache-device gpu: the bytes the trimmed records of --train_file and --test_file may take together in device "
      "memory (default 0: three quarters of the device memory that is free when the first loader opens).  It bounds the records' bytes, "
      "not the allocations: the store grows in slabs of 256 MiB (or what the budget leaves), so each file may take up to one slab more"),
+    ("--train_bam", "str", argparse.SUPPRESS,
+     "training straight from a coordinate-sorted BAM (with --train_fasta, the labelled location VCFs --train_tp_vcf / --train_fn_vcf / "
+     "--train_fp_vcf, --train-loader-device gpu and --train-cache-device gpu): the GPU pileup encoder's planes go into the resident "
+     "record store where they lie and no train.hdf is written; replaces --train_file.  Record i is record i of the file "
+     "tools/convert_bam_single_reads.py would write from the same VCFs; same losses, checkpoints and scored VCF.  Evaluation reads "
+     "--test_file, or --test_bam with --test_fasta (locations from the --test_*_vcf flags, or --sample_vcf with label 2)"),
+    ("--train_fasta", "str", argparse.SUPPRESS, "reference FASTA of --train_bam"),
+    ("--train_tp_vcf", "str", argparse.SUPPRESS, "with --train_bam: VCF of the true-positive locations (label 0), the converter's --tp_vcf"),
+    ("--train_tp_full_vcf", "str", argparse.SUPPRESS, "with --train_tp_vcf: the VCF that carries their genotypes, the converter's --tp_full_vcf"),
+    ("--train_fn_vcf", "str", argparse.SUPPRESS, "with --train_bam: VCF of the false-negative locations (label 1), the converter's --fn_vcf"),
+    ("--train_fp_vcf", "str", argparse.SUPPRESS, "with --train_bam: VCF of the false-positive locations (label 2), the converter's --fp_vcf"),
+    ("--test_tp_vcf", "str", argparse.SUPPRESS, "with --train_bam and --test_bam: as --train_tp_vcf, for the evaluation records"),
+    ("--test_tp_full_vcf", "str", argparse.SUPPRESS, "with --test_tp_vcf: as --train_tp_full_vcf"),
+    ("--test_fn_vcf", "str", argparse.SUPPRESS, "with --train_bam and --test_bam: as --train_fn_vcf"),
+    ("--test_fp_vcf", "str", argparse.SUPPRESS, "with --train_bam and --test_bam: as --train_fp_vcf"),
     ("--record-census", "str", None, "gpu: with --test_bam, the locations are censused first (which of them give a record, by the GPU "
                                      "encoder's status rule without its planes), so that --gpus N, --shard g/N, "
                                      "--test_holdout_chromosomes and --max-test-batches select and seed the records as --test_file "
@@ -125,11 +140,12 @@ def create_arg_parser() -> argparse.ArgumentParser:
 
 def parse_args(argv=None) -> argparse.Namespace:
     """``create_arg_parser().parse_args(argv)``, except that ``--test_file`` is not required where ``--test_bam`` stands in
-    for it (the parser itself keeps the reference's ``required=True``)."""
+    for it, or where ``--train_bam`` is given (main.py then says which of the two is missing); the parser itself keeps the
+    reference's ``required=True``."""
     import sys
     argv = list(sys.argv[1:] if argv is None else argv)
     p = create_arg_parser()
-    if any(a == "--test_bam" or a.startswith("--test_bam=") for a in argv):
+    if any(a in ("--test_bam", "--train_bam") or a.startswith(("--test_bam=", "--train_bam=")) for a in argv):
         for a in p._actions:
             if a.dest == "test_file":
                 a.required = False

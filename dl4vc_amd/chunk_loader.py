@@ -26,8 +26,10 @@ CL_SYMBOLS = ("cl_open", "cl_close", "cl_last_error", "cl_inflate_chunks_device"
               "cl_center_counts_device", "cl_center_counts_host",
               "cl_store_open", "cl_store_close", "cl_store_last_error", "cl_store_append_device", "cl_store_assemble_device",
               "cl_store_center_counts_device", "cl_store_extent_host", "cl_store_pack_host", "cl_store_assemble_host", "cl_store_record",
-              "cl_store_slab", "cl_store_debug_fill", "cl_store_get_stats")
+              "cl_store_slab", "cl_store_debug_fill", "cl_store_get_stats",
+              "cl_store_append_planes_device", "cl_store_extent_planes_host", "cl_store_pack_planes_host")
 STORE_SLAB_BYTES = 256 << 20        # the record store grows in device slabs of this size
+FILL_ROUND_LOCATIONS = 4096         # locations one round of the store's fill from a BAM encodes (3 x 4096 x 200 x 201 bytes of staging)
 FILL_GROUP_CHUNKS = 512             # chunks one inflate launch of the store's fill holds (a chunk keeps one lane busy whatever else runs)
 _bound = None
 # libhdf5 is not thread-safe: the raw chunk reads of every loader of the process (the training file's and the test file's workers)
@@ -73,6 +75,9 @@ def load_library() -> C.CDLL:
         lib.cl_store_center_counts_device.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp]
         lib.cl_store_extent_host.argtypes = [vp, C.c_uint64, C.c_int64, vp, C.c_int32, C.c_int32, vp, C.c_int64, vp]
         lib.cl_store_pack_host.argtypes = [vp, vp, C.c_uint64, C.c_int64, vp, vp, vp, C.c_int64, vp]
+        lib.cl_store_append_planes_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp]
+        lib.cl_store_extent_planes_host.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int64, vp]
+        lib.cl_store_pack_planes_host.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp]
         lib.cl_store_record.argtypes = [vp, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         lib.cl_store_slab.argtypes = [vp, C.c_int32, vp, C.c_uint64] + [C.POINTER(C.c_int64)] * 3
         lib.cl_store_debug_fill.argtypes = [vp, C.c_int32]
@@ -444,6 +449,19 @@ def record_extents_host(inflated, record_bytes: int, plane_off, stored_rows: int
     return kept
 
 
+def plane_extents_host(reads, qual, strand, slots=None) -> np.ndarray:
+    """``cl_store_extent_planes_host``: ``kept`` of the slots ``slots`` (all of them by default) of three arrays ``[n][S][W]``."""
+    planes = [np.ascontiguousarray(a, np.uint8) for a in (reads, qual, strand)]
+    n, S, W = planes[0].shape
+    slots = np.arange(n, dtype=np.int32) if slots is None else np.ascontiguousarray(slots, np.int32)
+    kept = np.zeros(len(slots), np.int32)
+    lib = load_library()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    if lib.cl_store_extent_planes_host(*[p(a) for a in planes], n, S, W, p(slots), len(slots), p(kept)) != 0:
+        raise ValueError(lib.cl_store_last_error(None).decode())
+    return kept
+
+
 class RecordStore:
     """A ``cl_store_t``: trimmed records in slabs, on ``device`` or (``device < 0``) in host memory, where the CPU definitions
     ``pack_host`` / ``assemble_host`` stand in for ``append_device`` / ``assemble_device``.  A refused call raises ``ValueError``
@@ -492,6 +510,31 @@ class RecordStore:
         p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
         self._check(self.lib.cl_store_append_device(self._h, loader_handle, p(slots), p(records), len(slots), C.c_void_p(stream or None),
                                                     p(kept)))
+        return kept
+
+    def pack_planes_host(self, reads, qual, strand, slots, records) -> np.ndarray:
+        """``cl_store_pack_planes_host``: slots ``slots`` of three host arrays ``[n_slots][stored_rows][window]`` become the
+        records ``records`` of a host store."""
+        planes = [np.ascontiguousarray(a, np.uint8) for a in (reads, qual, strand)]
+        for a in planes:
+            if a.shape != (planes[0].shape[0], self.stored_rows, self.window):
+                raise ValueError("planes: three arrays [n][%d][%d], not %s" % (self.stored_rows, self.window, a.shape))
+        slots, records = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(records, np.int32)
+        kept = np.zeros(len(slots), np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        self._check(self.lib.cl_store_pack_planes_host(self._h, *[p(a) for a in planes], len(planes[0]), p(slots), p(records), len(slots),
+                                                       p(kept)))
+        return kept
+
+    def append_planes_device(self, planes, n_slots: int, slots, records, stream: int = 0) -> np.ndarray:
+        """``cl_store_append_planes_device``: ``planes`` = the device addresses of three arrays ``[n_slots][stored_rows][window]``
+        (the pileup encoder's output; read only, any alignment)."""
+        slots, records = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(records, np.int32)
+        kept = np.zeros(len(slots), np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        v = lambda x: C.c_void_p(int(x)) if x else None   # noqa: E731
+        self._check(self.lib.cl_store_append_planes_device(self._h, *[v(x) for x in planes], int(n_slots), p(slots), p(records), len(slots),
+                                                           C.c_void_p(stream or None), p(kept)))
         return kept
 
     def _assemble(self, fn, records, rows, first_rows, reads, lines, use_q, use_strand, outs, stream):
@@ -543,6 +586,17 @@ class RecordStore:
         self.close()
 
 
+@dataclass
+class BamSource:
+    """What ``ResidentRecords.from_bam`` reads instead of a candidate file (``--train_bam`` / ``--test_bam`` beside it)."""
+    bam: str
+    fasta: str
+    locations: list                      # ``pileup_encoder.Location``s, in the order the converter would write their records
+    inflate_device: Optional[str] = None
+    encoder_options: object = None       # ``pileup_encoder.EncoderOptions``; None = what ``--test_bam`` uses
+    threads: int = 0
+
+
 class _RecordTexts:
     """``vcfrec`` of the records of a blob array, decoded when asked for."""
 
@@ -563,7 +617,9 @@ class ResidentRecords:
     source: no file read, no upload, no inflate launch.
 
     The whole file is resident or the fill ends with ``StoreFull`` (how many records fit, in how many bytes, the budget); a damaged
-    chunk ends it with ``DamagedChunk`` wherever it lies."""
+    chunk ends it with ``DamagedChunk`` wherever it lies.
+
+    ``ResidentRecords.from_bam`` fills the same store from the GPU pileup encoder instead (``--train_bam``): no file at all."""
 
     def __init__(self, path: str, reads: int, batch_sites: int, device: int = 0, use_q: bool = True, use_strand: bool = True,
                  capacity_bytes: int = 0, slab_bytes: int = STORE_SLAB_BYTES, group_chunks: int = FILL_GROUP_CHUNKS, stream: int = 0,
@@ -634,20 +690,159 @@ class ResidentRecords:
                 raise StoreFull("%s does not fit the record store: %d of its %d records fit, in %d bytes of the budget of %d bytes; raise "
                                 "--train-cache-bytes or drop --train-cache-device"
                                 % (f.path, have.records + have.refused_fit_records, self.n, have.refused_fit_bytes, self.capacity_bytes)) from None
-        have = self.store.stats()
-        self.stage.update(store_bytes=have.stored_bytes, store_records=have.records, extent_ms=have.extent_ms, pack_ms=have.pack_ms)
-        self.inflated_bytes = have.inflated_bytes
-        # the members every plan reads, contiguous once (a field of the blob array is a strided view)
-        self._num_reads = np.ascontiguousarray(self.blob["num_reads"].reshape(-1))
-        self._ref_bases = np.ascontiguousarray(self.blob["ref_bases"].reshape(self.n, self.window))
-        self._label = np.ascontiguousarray(self.blob["label"].reshape(-1)) if "label" in self.blob_dtype.names else np.zeros(self.n, np.uint8)
         # the inflate handle's record buffer and the file go: every batch from here on comes from the store
         self._inflater.close()
         self._inflater = None
+        self._filled(t_fill)
+
+    def _filled(self, t_fill: float) -> None:
+        """What both fills end with: the store's figures and the members every plan reads."""
+        have = self.store.stats()
+        self.stage.update(store_bytes=have.stored_bytes, store_records=have.records, extent_ms=have.extent_ms, pack_ms=have.pack_ms)
+        self.inflated_bytes = have.inflated_bytes
+        # contiguous once (a field of the blob array is a strided view)
+        self._num_reads = np.ascontiguousarray(self.blob["num_reads"].reshape(-1))
+        self._ref_bases = np.ascontiguousarray(self.blob["ref_bases"].reshape(self.n, self.window))
+        self._label = np.ascontiguousarray(self.blob["label"].reshape(-1)) if "label" in self.blob_dtype.names else np.zeros(self.n, np.uint8)
         self.stage["fill_ms"] = (time.perf_counter() - t_fill) * 1e3
 
+    @classmethod
+    def from_bam(cls, bam: str, fasta: str, locations, reads: int, batch_sites: int, device: int = 0, use_q: bool = True,
+                 use_strand: bool = True, capacity_bytes=0, slab_bytes: int = STORE_SLAB_BYTES, stream: int = 0,
+                 debug_fill: Optional[int] = None, encoder_options=None, inflate_device: Optional[str] = None, threads: int = 0,
+                 round_locations: int = FILL_ROUND_LOCATIONS):
+        """The resident records of a BAM (``--train_bam``): what ``tools/convert_bam_single_reads.py`` would write for ``locations``
+        (``pileup_encoder.Location``s, in the converter's order) and ``ResidentRecords(path)`` would then inflate, without the file.
+        Per round of ``round_locations`` locations: the GPU pileup encoder writes its planes into three staging arrays
+        (``encode_device(out=)``), what it declines goes to ``pe_encode`` and then the Python builder (``inference._HostEncoders``)
+        and into the location's slot; the locations that gave a record are the records, in input order, and their slots go into the
+        store (``cl_store_append_planes_device``: the same extent and pack kernels as the file fill, reading the planes where the
+        encoder left them); their other members (``hdf5_schema.blob_dtype``, the texts cut as the file cuts them) are appended to
+        the host array the plans read.  Afterwards the encoders are closed and the staging is freed.
+
+        ``capacity_bytes``: the budget, or a function that gives it -- called once the staging planes (3 x ``round_locations`` x
+        ``max_reads`` x window bytes) are allocated, so that a budget taken from the free device memory does not count them.
+        ``device < 0``: the CPU definition -- ``pe_encode`` for every location, a host store, ``cl_store_pack_planes_host``; no GPU.
+
+        ``stage`` also holds the encoders' counts (``inference.ENCODER_COUNTS``) and ``encode_ms``."""
+        from .inference import ENCODER_COUNTS, _HostEncoders
+        from .pileup_encoder import EncoderOptions
+        import os
+        self = cls.__new__(cls)
+        opt = encoder_options or EncoderOptions(window_size=100, max_reads=200, max_insert_length=10, max_insert_length_variant=50,
+                                                min_base_quality=0)
+        locations = list(locations)
+        self.path = bam
+        self.store = self._inflater = None
+        self.window, self.stored_rows, self.reads, self.B = 2 * opt.window_size + 1, opt.max_reads, int(reads), int(batch_sites)
+        if self.window != 201:
+            raise ValueError("the encoder gives windows of %d columns: the allele masks are defined on the 201-column window (window size "
+                             "100)" % self.window)
+        if self.reads > self.stored_rows:
+            raise ValueError("the model reads %d rows per site but the encoder stores only %d" % (self.reads, self.stored_rows))
+        self.use_q, self.use_strand, self.device, self.lib = use_q, use_strand, int(device), load_library()
+        self.blob_dtype = blob_dtype(self.window)
+        self._counts = None
+        self.stage = {k: 0.0 for k in ("plan_ms", "assemble_ms", "counts_ms", "fill_ms", "encode_ms", "extent_ms", "pack_ms")}
+        self.stage.update({k: 0 for k in ("records", "store_bytes", "store_records") + ENCODER_COUNTS})
+        threads = threads or max(2, min(16, (os.cpu_count() or 4)))
+        B = max(1, min(int(round_locations), len(locations)))
+        S, W = self.stored_rows, self.window
+        enc = host = staging = None
+        try:
+            if self.device >= 0:
+                import torch
+                from . import pileup_gpu
+                self.torch = torch
+                dev = torch.device("cuda", self.device)
+                staging = [torch.empty((B, S, W), dtype=torch.uint8, device=dev) for _ in range(3)]
+                ts = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.current_stream(dev)
+                enc = pileup_gpu.GpuPileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
+                                                  opt.max_insert_length_variant, opt.min_base_quality, device=self.device,
+                                                  inflate_device=inflate_device)
+            else:
+                if inflate_device is not None:
+                    raise ValueError("inflate_device is the GPU encoder's option: the host filler (device < 0) has none")
+                self.torch = None
+                staging = [np.zeros((B, S, W), np.uint8) for _ in range(3)]
+            self.capacity_bytes = int(capacity_bytes() if callable(capacity_bytes) else capacity_bytes)
+            host = _HostEncoders(bam, fasta, opt, threads)
+            # (the table's size is an upper bound: a location without a record leaves no hole among the records)
+            self.store = RecordStore(W, S, len(locations), self.capacity_bytes, slab_bytes, self.device)
+            if debug_fill is not None:
+                self.store.debug_fill(debug_fill)
+            self.blob = np.zeros(len(locations), self.blob_dtype)
+            self.n = 0
+            t_fill = time.perf_counter()
+            c = self.stage
+            for l0 in range(0, len(locations), B):
+                locs = locations[l0:l0 + B]
+                t0 = time.perf_counter()
+                if enc is not None:
+                    _r, _q, _s, ref, num, status = enc.encode_device([l.contig for l in locs], [l.pos for l in locs], stream=ts, out=staging)
+                    c["gpu"] += int((status == 1).sum())
+                else:
+                    ref, num = np.zeros((len(locs), W), np.uint8), np.zeros(len(locs), np.int32)
+                    status = np.full(len(locs), 2, np.int8)
+                c["locations"] += len(locs)
+                declined = np.flatnonzero(status == 2)
+                if len(declined):
+                    got = host.encode(locs, declined, c)
+                    status[declined] = 0
+                    for i, (rd, ql, sd, rf, n_reads) in got.items():
+                        for plane, src in zip(staging, (rd, ql, sd)):
+                            src = np.ascontiguousarray(src, np.uint8)
+                            if enc is not None:
+                                with self.torch.cuda.stream(ts):
+                                    plane[i].copy_(self.torch.from_numpy(src))
+                            else:
+                                plane[i] = src
+                        ref[i], num[i], status[i] = rf, n_reads, 1
+                c["no_record"] += int((status == 0).sum())
+                c["encode_ms"] += (time.perf_counter() - t0) * 1e3
+                keep = np.flatnonzero(status == 1).astype(np.int32)
+                m = len(keep)
+                records = self.n + np.arange(m, dtype=np.int32)
+                try:
+                    if enc is not None:
+                        self.store.append_planes_device([t.data_ptr() for t in staging], len(locs), keep, records, ts.cuda_stream)
+                    else:
+                        self.store.pack_planes_host(staging[0][:len(locs)], staging[1][:len(locs)], staging[2][:len(locs)], keep, records)
+                except StoreFull:
+                    have = self.store.stats()
+                    raise StoreFull("the records of %s do not fit the record store: %d records (of the first %d of its %d locations) fit, in "
+                                    "%d bytes of the budget of %d bytes; raise --train-cache-bytes"
+                                    % (bam, have.records + have.refused_fit_records, l0 + len(locs), len(locations),
+                                       have.refused_fit_bytes, self.capacity_bytes)) from None
+                blob = self.blob[self.n:self.n + m]
+                blob["ref_bases"], blob["num_reads"] = ref[keep], num[keep]
+                if m:
+                    bdt = self.blob_dtype
+                    blob["name"] = [locs[i].name.encode()[:bdt["name"].itemsize] for i in keep]
+                    blob["label"] = [locs[i].label for i in keep]
+                    blob["vcfrec"] = [locs[i].vcf_string.encode()[:bdt["vcfrec"].itemsize] for i in keep]
+                self.n += m
+            self.blob = self.blob[:self.n].copy()
+            self._filled(t_fill)
+        except Exception:
+            self.close()
+            raise
+        finally:
+            # the encoder's buffers, the host encoders' files and the staging planes go: every batch comes from the store
+            if enc is not None:
+                enc.close()
+            if host is not None:
+                host.close()
+            staging = None
+        return self
+
+    def chromosomes(self):
+        """The text before the first tab of every record's ``vcfrec``: what ``inference.select_sites`` holds out by."""
+        return [bytes(v).split(b"\t", 1)[0].decode() for v in self.blob["vcfrec"]]
+
     def assemble_list(self, indices, seed: int, outs, stream: int = 0) -> IndexedSites:
-        """``DeviceChunkLoader.assemble_list`` from the store: site i is record ``indices[i]`` of the file."""
+        """``DeviceChunkLoader.assemble_list`` from the store: site i is record ``indices[i]`` of the file.  A host store
+        (``device < 0``) takes six numpy arrays as ``outs`` and assembles and counts on the host."""
         torch = self.torch
         idx = np.asarray(indices, np.int64).reshape(-1)
         m = len(idx)
@@ -662,7 +857,16 @@ class ResidentRecords:
         label = np.array(self._label[slots])
         t3 = time.perf_counter()
         counts = np.zeros((m, 2, 16), np.int32)
-        if m:
+        if m and self.device < 0:
+            # the CPU definition: ``outs`` are six numpy arrays with room for the m sites
+            first = np.ascontiguousarray(plan.first_rows, np.uint8)
+            rows = np.ascontiguousarray(plan.rows, np.int16) if not first.all() else None
+            got = self.store.assemble_host(plan.slots, rows, first, self.reads, (plan.ref, plan.ref_mask, plan.var_mask), self.use_q,
+                                           self.use_strand)
+            for dst, src in zip(outs, got):
+                dst[:m] = src
+            counts[:] = center_counts_host(got[0])
+        elif m:
             first = np.ascontiguousarray(plan.first_rows, np.uint8)
             rows = np.ascontiguousarray(plan.rows, np.int16) if not first.all() else None
             self.store.assemble_device(plan.slots, rows, first, self.reads, (plan.ref, plan.ref_mask, plan.var_mask), self.use_q,

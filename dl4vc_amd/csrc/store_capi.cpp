@@ -1,4 +1,5 @@
-// cl_store_* of libdl4vc_pileup.so (include/dl4vc_chunks.h): the record store.  The records a cl_loader handle inflated are
+// cl_store_* of libdl4vc_pileup.so (include/dl4vc_chunks.h): the record store.  The records a cl_loader handle inflated (or the
+// slots of the pileup encoder's three plane arrays, cl_store_append_planes_device: the same kernels, another address rule) are
 // measured (record_extent), laid out on the host (store_host.h: record order, 16-byte boundaries, slabs no record straddles, the
 // capacity checked before anything is packed), packed into device slabs (store_pack) and from then on assembled from there
 // (store_assemble) -- the file is inflated once per run, not once per epoch.  A store opened with device < 0 keeps its slabs in
@@ -172,6 +173,14 @@ int extent_arguments(cl_store* h, const char* who, const uint8_t* inflated, uint
     return 0;
 }
 
+// the same for three plane arrays [n_slots][S][W]
+int planes_arguments(cl_store* h, const char* who, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots, int32_t S,
+                     int32_t W) {
+    if (S < 1 || W < 1 || (int64_t)S * W > (1 << 24) || n_slots < 0 || n_slots > INT32_MAX) return sfail(h, -1, "%s: bad shape", who);
+    if (n_slots && (!reads || !qual || !strand)) return sfail(h, -1, "%s: null argument", who);
+    return 0;
+}
+
 #ifndef CL_STORE_HOST_ONLY
 #define ST_TRY(x) DEV_TRY(h->err, "", x)
 
@@ -183,16 +192,11 @@ int open_device(cl_store* h) {
     return 0;
 }
 
-int append_device(cl_store* h, cl_loader_t* loader, const int32_t* slots, const int32_t* records, int64_t n, void* stream, int32_t* kept_out) {
-    const char* who = "cl_store_append_device";
-    if (h->on_host) return sfail(h, -1, "%s: the store was opened in host memory", who);
-    if (!loader) return sfail(h, -1, "%s: null loader", who);
-    const clh::RecordsView v = clh::records_view(loader);
-    if (v.window != h->window || v.stored_rows != h->stored_rows)
-        return sfail(h, -1, "%s: the loader holds records of %d rows of %d columns, the store of %d of %d", who, v.stored_rows, v.window,
-                     h->stored_rows, h->window);
-    if (v.device != h->device) return sfail(h, -1, "%s: the loader is on device %d, the store on device %d", who, v.device, h->device);
-    if (const int rc = check_append(h, who, slots, records, n, v.n_records, kept_out)) return rc;
+// What both device appends do once their source is known: slots[i] of src (n_slots of them, source_bytes each in the statistics)
+// becomes record records[i].
+int append_source(cl_store* h, const char* who, const st::Source& src, int64_t n_slots, int64_t source_bytes, const int32_t* slots,
+                  const int32_t* records, int64_t n, void* stream, int32_t* kept_out) {
+    if (const int rc = check_append(h, who, slots, records, n, n_slots, kept_out)) return rc;
     if (n == 0) return 0;
     dev::DeviceGuard guard;
     ST_TRY(hipSetDevice(h->device));
@@ -202,9 +206,6 @@ int append_device(cl_store* h, cl_loader_t* loader, const int32_t* slots, const 
     const size_t o_kept = (b_i32 + 15) & ~(size_t)15, o_items = 2 * o_kept;
     if (h->d_app.ensure(o_items + b_items) != hipSuccess) return sfail(h, -2, "hipMalloc of the append tables failed");
     if (h->h_app.ensure(o_items + b_items) != hipSuccess) return sfail(h, -2, "hipHostMalloc of the append staging failed");
-    st::Source src{};
-    src.records = v.records; src.record_bytes = v.record_bytes; src.S = h->stored_rows; src.W = h->window;
-    for (int p = 0; p < 3; ++p) src.plane_off[p] = v.plane_off[p];
     memcpy(h->h_app.p, slots, b_i32);
     int32_t* h_kept = (int32_t*)(h->h_app.p + o_kept);
     ST_TRY(hipMemcpyAsync(h->d_app.p, h->h_app.p, b_i32, hipMemcpyHostToDevice, s));
@@ -255,8 +256,34 @@ int append_device(cl_store* h, cl_loader_t* loader, const int32_t* slots, const 
     ST_TRY(hipEventElapsedTime(&ms[1], h->ev[2], h->ev[3]));
     h->stats.extent_ms += ms[0];
     h->stats.pack_ms += ms[1];
-    commit(h, cur, records, kept_out, places, n, v.record_bytes);
+    commit(h, cur, records, kept_out, places, n, source_bytes);
     return 0;
+}
+
+int append_device(cl_store* h, cl_loader_t* loader, const int32_t* slots, const int32_t* records, int64_t n, void* stream, int32_t* kept_out) {
+    const char* who = "cl_store_append_device";
+    if (h->on_host) return sfail(h, -1, "%s: the store was opened in host memory", who);
+    if (!loader) return sfail(h, -1, "%s: null loader", who);
+    const clh::RecordsView v = clh::records_view(loader);
+    if (v.window != h->window || v.stored_rows != h->stored_rows)
+        return sfail(h, -1, "%s: the loader holds records of %d rows of %d columns, the store of %d of %d", who, v.stored_rows, v.window,
+                     h->stored_rows, h->window);
+    if (v.device != h->device) return sfail(h, -1, "%s: the loader is on device %d, the store on device %d", who, v.device, h->device);
+    st::Source src{};
+    for (int p = 0; p < 3; ++p) src.plane[p] = v.records + v.plane_off[p];
+    src.stride = v.record_bytes; src.S = h->stored_rows; src.W = h->window;
+    return append_source(h, who, src, v.n_records, v.record_bytes, slots, records, n, stream, kept_out);
+}
+
+int append_planes_device(cl_store* h, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots, const int32_t* slots,
+                         const int32_t* records, int64_t n, void* stream, int32_t* kept_out) {
+    const char* who = "cl_store_append_planes_device";
+    if (h->on_host) return sfail(h, -1, "%s: the store was opened in host memory", who);
+    if (const int rc = planes_arguments(h, who, reads, qual, strand, n_slots, h->stored_rows, h->window)) return rc;
+    st::Source src{};
+    src.plane[0] = reads; src.plane[1] = qual; src.plane[2] = strand;
+    src.stride = (int64_t)h->stored_rows * h->window; src.S = h->stored_rows; src.W = h->window;
+    return append_source(h, who, src, n_slots, 3 * src.stride, slots, records, n, stream, kept_out);
 }
 
 int assemble_device(cl_store* h, const int32_t* records, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t R,
@@ -309,15 +336,11 @@ int assemble_device(cl_store* h, const int32_t* records, const int16_t* rows, co
 }
 #endif
 
-int pack_host(cl_store* h, const uint8_t* inflated, uint64_t inflated_bytes, int64_t record_bytes, const int64_t* plane_off, const int32_t* slots,
-              const int32_t* records, int64_t n, int32_t* kept_out) {
-    const char* who = "cl_store_pack_host";
-    if (!h->on_host) return sfail(h, -1, "%s: the store was opened on a device", who);
-    int64_t n_slots = 0;
-    if (const int rc = extent_arguments(h, who, inflated, inflated_bytes, record_bytes, plane_off, h->stored_rows, h->window, &n_slots)) return rc;
+// What both host appends do once their source is known (append_source on a host store).
+int pack_source(cl_store* h, const char* who, const st::HostSource& src, int64_t n_slots, int64_t source_bytes, const int32_t* slots,
+                const int32_t* records, int64_t n, int32_t* kept_out) {
     if (const int rc = check_append(h, who, slots, records, n, n_slots, kept_out)) return rc;
-    for (int64_t i = 0; i < n; ++i)
-        kept_out[i] = st::extent_host(inflated + (size_t)slots[i] * (size_t)record_bytes, plane_off, h->stored_rows, h->window);
+    for (int64_t i = 0; i < n; ++i) kept_out[i] = st::extent_host(src, slots[i], h->stored_rows, h->window);
     st::Cursor cur = h->cur;
     std::vector<st::Place> places;
     std::vector<uint64_t> new_caps;
@@ -331,11 +354,27 @@ int pack_host(cl_store* h, const uint8_t* inflated, uint64_t inflated_bytes, int
         h->slabs.push_back(std::move(slab));
     }
     for (int64_t i = 0; i < n; ++i)
-        if (kept_out[i])
-            st::pack_host(inflated + (size_t)slots[i] * (size_t)record_bytes, plane_off, h->window, kept_out[i],
-                          h->slabs[places[i].slab]->data + places[i].off);
-    commit(h, cur, records, kept_out, places, n, record_bytes);
+        if (kept_out[i]) st::pack_host(src, slots[i], h->window, kept_out[i], h->slabs[places[i].slab]->data + places[i].off);
+    commit(h, cur, records, kept_out, places, n, source_bytes);
     return 0;
+}
+
+int pack_host(cl_store* h, const uint8_t* inflated, uint64_t inflated_bytes, int64_t record_bytes, const int64_t* plane_off, const int32_t* slots,
+              const int32_t* records, int64_t n, int32_t* kept_out) {
+    const char* who = "cl_store_pack_host";
+    if (!h->on_host) return sfail(h, -1, "%s: the store was opened on a device", who);
+    int64_t n_slots = 0;
+    if (const int rc = extent_arguments(h, who, inflated, inflated_bytes, record_bytes, plane_off, h->stored_rows, h->window, &n_slots)) return rc;
+    return pack_source(h, who, st::record_source(inflated, record_bytes, plane_off), n_slots, record_bytes, slots, records, n, kept_out);
+}
+
+int pack_planes_host(cl_store* h, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots, const int32_t* slots,
+                     const int32_t* records, int64_t n, int32_t* kept_out) {
+    const char* who = "cl_store_pack_planes_host";
+    if (!h->on_host) return sfail(h, -1, "%s: the store was opened on a device", who);
+    if (const int rc = planes_arguments(h, who, reads, qual, strand, n_slots, h->stored_rows, h->window)) return rc;
+    return pack_source(h, who, st::planar_source(reads, qual, strand, h->stored_rows, h->window), n_slots,
+                       3 * (int64_t)h->stored_rows * h->window, slots, records, n, kept_out);
 }
 
 int assemble_host(cl_store* h, const int32_t* records, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t R, const uint8_t* ref,
@@ -438,6 +477,19 @@ int cl_store_append_device(cl_store_t* h, cl_loader_t* loader, const int32_t* sl
 #endif
 }
 
+int cl_store_append_planes_device(cl_store_t* h, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots,
+                                  const int32_t* slots, const int32_t* records, int64_t n, void* stream, int32_t* kept_out) {
+    if (!h) return sfail(nullptr, -1, "cl_store_append_planes_device: null handle");
+#ifdef CL_STORE_HOST_ONLY
+    (void)reads; (void)qual; (void)strand; (void)n_slots; (void)slots; (void)records; (void)n; (void)stream; (void)kept_out;
+    return sfail(h, -1, "cl_store_append_planes_device: this build has the host store only");
+#else
+    return capi::guarded(h->err, "cl_store_append_planes_device", [&] {
+        return append_planes_device(h, reads, qual, strand, n_slots, slots, records, n, stream, kept_out);
+    });
+#endif
+}
+
 int cl_store_assemble_device(cl_store_t* h, const int32_t* records, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t reads,
                              const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int32_t use_q, int32_t use_strand,
                              uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out,
@@ -484,8 +536,33 @@ int cl_store_extent_host(const uint8_t* inflated, uint64_t inflated_bytes, int64
         for (int64_t i = 0; i < n; ++i)
             if (slots[i] < 0 || slots[i] >= n_slots) return sfail(nullptr, -1, "%s: entry %lld names slot %d of %lld", who, (long long)i, slots[i],
                                                               (long long)n_slots);
-        for (int64_t i = 0; i < n; ++i) kept_out[i] = st::extent_host(inflated + (size_t)slots[i] * (size_t)record_bytes, plane_off, stored_rows, window);
+        const st::HostSource src = st::record_source(inflated, record_bytes, plane_off);
+        for (int64_t i = 0; i < n; ++i) kept_out[i] = st::extent_host(src, slots[i], stored_rows, window);
         return 0;
+    });
+}
+
+int cl_store_extent_planes_host(const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots, int32_t stored_rows,
+                                int32_t window, const int32_t* slots, int64_t n, int32_t* kept_out) {
+    const char* who = "cl_store_extent_planes_host";
+    return capi::guarded(g_store_err, who, [&] {
+        if (const int rc = planes_arguments(nullptr, who, reads, qual, strand, n_slots, stored_rows, window)) return rc;
+        if (n < 0) return sfail(nullptr, -1, "%s: bad record count", who);
+        if (n > 0 && (!slots || !kept_out)) return sfail(nullptr, -1, "%s: null argument", who);
+        for (int64_t i = 0; i < n; ++i)
+            if (slots[i] < 0 || slots[i] >= n_slots) return sfail(nullptr, -1, "%s: entry %lld names slot %d of %lld", who, (long long)i, slots[i],
+                                                              (long long)n_slots);
+        const st::HostSource src = st::planar_source(reads, qual, strand, stored_rows, window);
+        for (int64_t i = 0; i < n; ++i) kept_out[i] = st::extent_host(src, slots[i], stored_rows, window);
+        return 0;
+    });
+}
+
+int cl_store_pack_planes_host(cl_store_t* h, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots,
+                              const int32_t* slots, const int32_t* records, int64_t n, int32_t* kept_out) {
+    if (!h) return sfail(nullptr, -1, "cl_store_pack_planes_host: null handle");
+    return capi::guarded(h->err, "cl_store_pack_planes_host", [&] {
+        return pack_planes_host(h, reads, qual, strand, n_slots, slots, records, n, kept_out);
     });
 }
 

@@ -12,11 +12,12 @@ namespace st {
 
 constexpr int STORE_BLOCK = 256;             // threads per workgroup of the three kernels (four waves)
 
-// the inflated records the extent and pack kernels read: record i at records + i * record_bytes, its planes [S][W] at plane_off
+// what the extent and pack kernels read: slot i's plane p, [S][W], at plane[p] + i * stride (st::HostSource's rule).  Inflated
+// records of record_bytes: plane[p] = records + plane_off[p], stride = record_bytes.  The pileup encoder's three arrays
+// [n_slots][S][W]: plane[p] = the array, stride = S * W.
 struct Source {
-    const uint8_t* records;
-    int64_t record_bytes;
-    int64_t plane_off[3];
+    const uint8_t* plane[3];
+    int64_t stride;
     int32_t S, W;
 };
 

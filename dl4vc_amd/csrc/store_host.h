@@ -19,11 +19,26 @@ constexpr int64_t SLAB_PAD = 16;     // and behind them: a 16-byte load at a rec
 
 inline uint64_t record_span(int64_t kept, int64_t W) { return ((uint64_t)(3 * kept * W) + 15u) & ~(uint64_t)15; }
 
-// kept of the record at rec: planes of S rows of W bytes at rec + plane_off[0..2]
-inline int32_t extent_host(const uint8_t* rec, const int64_t* plane_off, int32_t S, int32_t W) {
+// Where the planes of the records to store lie: slot i's plane p, S rows of W bytes, at plane[p] + i * stride.  Records of
+// record_bytes with their planes at plane_off (the inflated chunks of a file): plane[p] = records + plane_off[p], stride =
+// record_bytes.  Three separate arrays [n_slots][S][W] (the pileup encoder's output): plane[p] = the array, stride = S * W.
+struct HostSource {
+    const uint8_t* plane[3];
+    int64_t stride;
+    const uint8_t* at(int p, int64_t slot) const { return plane[p] + (size_t)slot * (size_t)stride; }
+};
+inline HostSource record_source(const uint8_t* records, int64_t record_bytes, const int64_t* plane_off) {
+    return HostSource{{records + plane_off[0], records + plane_off[1], records + plane_off[2]}, record_bytes};
+}
+inline HostSource planar_source(const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int32_t S, int32_t W) {
+    return HostSource{{reads, qual, strand}, (int64_t)S * W};
+}
+
+// kept of the record at slot: planes of S rows of W bytes
+inline int32_t extent_host(const HostSource& src, int64_t slot, int32_t S, int32_t W) {
     int32_t kept = 0;
     for (int p = 0; p < 3; ++p) {
-        const uint8_t* q = rec + plane_off[p];
+        const uint8_t* q = src.at(p, slot);
         for (int64_t i = (int64_t)S * W - 1; i >= (int64_t)kept * W; --i)
             if (q[i]) {
                 kept = (int32_t)(i / W) + 1;
@@ -33,11 +48,11 @@ inline int32_t extent_host(const uint8_t* rec, const int64_t* plane_off, int32_t
     return kept;
 }
 
-// the trimmed record of rec at dst: record_span(kept, W) bytes
-inline void pack_host(const uint8_t* rec, const int64_t* plane_off, int32_t W, int32_t kept, uint8_t* dst) {
+// the trimmed record of slot at dst: record_span(kept, W) bytes
+inline void pack_host(const HostSource& src, int64_t slot, int32_t W, int32_t kept, uint8_t* dst) {
     const size_t n = (size_t)kept * W;
     for (int p = 0; p < 3; ++p)
-        if (n) memcpy(dst + p * n, rec + plane_off[p], n);
+        if (n) memcpy(dst + p * n, src.at(p, slot), n);
     const size_t pad = (size_t)record_span(kept, W) - 3 * n;
     if (pad) memset(dst + 3 * n, 0, pad);
 }

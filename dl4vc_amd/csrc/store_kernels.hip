@@ -2,8 +2,10 @@
 // device memory trimmed of their trailing all-zero rows, and the sites of every batch assembled from there.  The CPU twins of the
 // three kernels are in store_host.h; store_capi.cpp checks every index before a launch.
 //
-// record_extent: one workgroup per inflated record.  Each plane's S * W bytes are cut at the 16-byte boundaries of the SOURCE
-// (a record is an odd number of bytes, so planes start at every alignment): the bytes before the first boundary and behind the
+// record_extent: one workgroup per source slot (Source: an inflated record, or a slot of the pileup encoder's three plane
+// arrays -- only the address of a slot's plane differs).  Each plane's S * W bytes are cut at the 16-byte boundaries of the SOURCE
+// (a record is an odd number of bytes, so planes start at every alignment; a slot of S * W = 40 200 bytes starts 0 or 8 bytes
+// past one, and a view of an allocation anywhere): the bytes before the first boundary and behind the
 // last one are read one by one, everything between with aligned 16-byte loads.  Every lane keeps the highest row in which it saw
 // a non-zero byte, the wave takes the maximum by shuffles, the four waves theirs through LDS, and lane 0 writes kept.
 //
@@ -34,11 +36,11 @@ __device__ __forceinline__ int head_bytes(const void* p, int span) {
 __global__ __launch_bounds__(STORE_BLOCK) void record_extent(Source src, const int32_t* __restrict__ slots, int32_t* __restrict__ kept) {
     __shared__ int32_t wave_rows[STORE_BLOCK / 64];
     const int tid = threadIdx.x;
-    const uint8_t* rec = src.records + (size_t)slots[blockIdx.x] * (size_t)src.record_bytes;
+    const size_t slot_off = (size_t)slots[blockIdx.x] * (size_t)src.stride;
     const int n = src.S * src.W;
     int rows = 0;                                          // 1 + the last row in which this lane saw a non-zero byte
     for (int p = 0; p < 3; ++p) {
-        const uint8_t* q = rec + src.plane_off[p];
+        const uint8_t* q = src.plane[p] + slot_off;
         const int head = head_bytes(q, n);
         const int n16 = (n - head) >> 4;
         const int tail0 = head + (n16 << 4);
@@ -76,7 +78,7 @@ __global__ __launch_bounds__(STORE_BLOCK) void store_pack(Source src, const Pack
     if (plane == 0 && tid == 0) table[it.record] = DevRec{it.dst, it.kept, 0};
     if (n == 0) return;
     uint8_t* dst = reinterpret_cast<uint8_t*>(it.dst) + (size_t)plane * n;
-    const uint8_t* s = src.records + (size_t)it.slot * (size_t)src.record_bytes + src.plane_off[plane];
+    const uint8_t* s = src.plane[plane] + (size_t)it.slot * (size_t)src.stride;
     const int head = head_bytes(dst, n);
     const int n16 = (n - head) >> 4;
     const int tail0 = head + (n16 << 4);

@@ -141,6 +141,19 @@ def select_sites(hdf_path: str, holdout_chromosomes=(), site_limit: int = 0, blo
     return idx.astype(np.int64)
 
 
+def select_records(chromosomes, holdout_chromosomes=(), site_limit: int = 0) -> np.ndarray:
+    """``select_sites`` for records that are in no file (``chunk_loader.ResidentRecords.chromosomes()``: the text before the first
+    tab of each record's ``vcfrec``), by the same rule."""
+    if holdout_chromosomes:
+        want = set(str(c) for c in holdout_chromosomes)
+        idx = np.flatnonzero(np.fromiter((c in want for c in chromosomes), bool, len(chromosomes)))
+    else:
+        idx = np.arange(len(chromosomes), dtype=np.int64)
+    if site_limit > 0:
+        idx = idx[:site_limit]
+    return idx.astype(np.int64)
+
+
 def index_runs(idx: np.ndarray):
     """Ascending indices -> maximal runs ``[(lo, hi), ...]`` of consecutive records."""
     if len(idx) == 0:

@@ -266,6 +266,11 @@ class DeviceBatchPrefetcher:
     host plan, one gather kernel from the store and the counts.  ``stage`` then also holds ``fill_ms``, ``store_bytes`` and
     ``store_records``, and its ``chunks``, ``compressed_bytes`` and ``inflate_ms`` stop growing once the loader is open.
 
+    ``path`` may be a ``chunk_loader.BamSource`` instead (``--train_bam``): the store is then filled from the GPU pileup encoder
+    (``ResidentRecords.from_bam``) and no candidate file exists; ``resident=True`` is required (there is no other form), and
+    ``cache_bytes`` may be a function, called once the fill's staging planes are allocated.  ``stage`` then holds the encoders'
+    counts and ``encode_ms``.
+
     torch must have been imported before the HIP libraries were loaded (one HIP runtime per process).  Every queue wait ends
     after ``wait_s`` seconds with an error that names what it waited for; an exception of the worker is raised in the consumer."""
 
@@ -274,7 +279,12 @@ class DeviceBatchPrefetcher:
     def __init__(self, path: str, reads: int, batch_sites: int, device: int = 0, use_q: bool = True, use_strand: bool = True,
                  wait_s: float = 600.0, ahead: int = AHEAD, resident: bool = False, cache_bytes: int = 0, slab_bytes: Optional[int] = None):
         import torch
-        from .chunk_loader import DeviceChunkLoader, ResidentRecords, STORE_SLAB_BYTES
+        from .chunk_loader import BamSource, DeviceChunkLoader, ResidentRecords, STORE_SLAB_BYTES
+        source = path if isinstance(path, BamSource) else None
+        if source is not None:
+            path = source.bam
+            if not resident:
+                raise ValueError("records encoded from a BAM are kept resident in device memory: there is no non-resident form")
         self.torch, self.path = torch, path
         self.B, self.wait_s = max(1, int(batch_sites)), float(wait_s)
         self.ahead = max(1, int(ahead))
@@ -284,8 +294,14 @@ class DeviceBatchPrefetcher:
             # ``--train-cache-device gpu``: the whole file is inflated once, here, into a record store of at most ``cache_bytes``
             # (``chunk_loader.ResidentRecords``); every batch of every ``batches`` call is assembled from it
             with torch.cuda.device(self.dev):
-                self.loader = ResidentRecords(path, reads, self.B, device=device, use_q=use_q, use_strand=use_strand,
-                                              capacity_bytes=cache_bytes, slab_bytes=slab_bytes or STORE_SLAB_BYTES)
+                if source is not None:
+                    self.loader = ResidentRecords.from_bam(source.bam, source.fasta, source.locations, reads, self.B, device=device,
+                                                           use_q=use_q, use_strand=use_strand, capacity_bytes=cache_bytes,
+                                                           slab_bytes=slab_bytes or STORE_SLAB_BYTES, inflate_device=source.inflate_device,
+                                                           encoder_options=source.encoder_options, threads=source.threads)
+                else:
+                    self.loader = ResidentRecords(path, reads, self.B, device=device, use_q=use_q, use_strand=use_strand,
+                                                  capacity_bytes=cache_bytes, slab_bytes=slab_bytes or STORE_SLAB_BYTES)
         else:
             # the record buffer starts at one chunk and is sized by ``batches`` for the lists it is given: a shuffled epoch needs up
             # to ``ahead * batch_sites`` chunks (1 MB each in the production layout), a sequential evaluation pass an eighth of that

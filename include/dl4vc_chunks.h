@@ -128,6 +128,15 @@ const char* cl_store_last_error(const cl_store_t* h);   /* h == NULL: the error 
 int cl_store_append_device(cl_store_t* h, cl_loader_t* loader, const int32_t* slots, const int32_t* records, int64_t n, void* stream,
                            int32_t* kept_out);
 
+/* cl_store_append_device with the pileup encoder's output as the source (pg_encode_device's status-1 planes, or any planes of that
+ * layout): three device arrays [n_slots][stored_rows][window], read only, not necessarily aligned; slot slots[i] (range-checked
+ * against n_slots before anything is enqueued) becomes record records[i].  Same kernels, same contract: extents on the device,
+ * layout on the host, packed on the device, waited for; -3 with the store unchanged when capacity_bytes would be exceeded.
+ * cl_store_get_stats counts 3 * stored_rows * window inflated bytes per record.  n_records of cl_store_open is an upper bound:
+ * a caller that stores only the locations that gave a record opens the store for the number of locations. */
+int cl_store_append_planes_device(cl_store_t* h, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots,
+                                  const int32_t* slots, const int32_t* records, int64_t n, void* stream, int32_t* kept_out);
+
 /* cl_assemble_device's contract with the store's records as the source: site i takes rows[i] (or the first `reads` rows) of record
  * records[i]; a row >= kept is zeros.  Records and rows are range-checked before anything is enqueued.  The six outputs are
  * device pointers; asynchronous on `stream`. */
@@ -147,6 +156,12 @@ int cl_store_extent_host(const uint8_t* inflated, uint64_t inflated_bytes, int64
                          int32_t window, const int32_t* slots, int64_t n, int32_t* kept_out);
 int cl_store_pack_host(cl_store_t* h, const uint8_t* inflated, uint64_t inflated_bytes, int64_t record_bytes, const int64_t* plane_off,
                        const int32_t* slots, const int32_t* records, int64_t n, int32_t* kept_out);
+/* cl_store_extent_host / cl_store_pack_host for three host arrays [n_slots][stored_rows][window]: the CPU definitions of
+ * cl_store_append_planes_device. */
+int cl_store_extent_planes_host(const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots, int32_t stored_rows,
+                                int32_t window, const int32_t* slots, int64_t n, int32_t* kept_out);
+int cl_store_pack_planes_host(cl_store_t* h, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots,
+                              const int32_t* slots, const int32_t* records, int64_t n, int32_t* kept_out);
 int cl_store_assemble_host(cl_store_t* h, const int32_t* records, const int16_t* rows, const uint8_t* first_rows, int64_t m, int32_t reads,
                            const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int32_t use_q, int32_t use_strand,
                            uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out,

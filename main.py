@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's ``main.py`` (main.py:47-229): inference-only mode (branch :213-222) and, with
-``--train_file``, training + per-epoch evaluation (branch :151-199).
+``--train_file`` (or ``--train_bam``: the records encoded from the BAM on the GPU, no file), training + per-epoch evaluation
+(branch :151-199).
 
     python main.py <the flags call_variants.sh passes> --test_file X.hdf --modelload CKPT \
         --save_vcf_records --save_vcf_records_file OUT/model_test.vcf --sample_vcf OUT/candidates.vcf
@@ -26,11 +27,26 @@ from arguments import parse_args                              # noqa: E402
 from dl4vc_amd.procs import child_devices, wait_children      # noqa: E402,F401
 
 
+def whole_lines(stream) -> None:
+    """The ranks of a --gpus N run write to one stdout.  Where Python writes it through (``python -u``, PYTHONUNBUFFERED), ``print``
+    hands a line's text and its line end to the pipe one after the other, and another rank's line can land between the two: two
+    lines on one, an empty one behind them.  Buffered up to the next flush -- what a pipe gets by default -- a line goes out in
+    one piece; every line a reader looks for here is printed with ``flush=True``."""
+    if getattr(stream, "write_through", False):
+        try:
+            stream.reconfigure(write_through=False)
+        except (AttributeError, ValueError, OSError):
+            pass
+
+
 def train_main(args, argv) -> int:
     """main.py:60-80,114-117,151-199: train for --epochs, evaluate on --test_file after every epoch, save checkpoints."""
     import numpy as np
-    assert args.train_file[-3:] == "hdf", "Train dataset must be in HDF format"                   # main.py:66
-    assert args.test_file[-3:] == "hdf", "Test dataset must be in HDF format"
+    train_bam = getattr(args, "train_bam", None)
+    if not train_bam:
+        assert args.train_file[-3:] == "hdf", "Train dataset must be in HDF format"               # main.py:66
+    if args.test_file:
+        assert args.test_file[-3:] == "hdf", "Test dataset must be in HDF format"
     refused = [("--augment-single-reads", args.augment_single_reads), ("--augment-reference", args.augment_reference),
                ("--reads-dynamic-downsample-rate", args.reads_dynamic_downsample_rate > 0), ("--rm_var_reads_rate", args.rm_var_reads_rate > 0),
                ("--rm_non_var_reads_rate", args.rm_non_var_reads_rate > 0),
@@ -42,6 +58,9 @@ def train_main(args, argv) -> int:
                          "silently training something else" % ", ".join(bad))
     if args.precision != "fp32":
         raise SystemExit("training runs in fp32 only")
+    train_source, test_source = args.train_file, args.test_file
+    if train_bam:
+        train_source, test_source = bam_sources(args)         # (VCFs that cannot be read end the run here, before any device work)
     from dl4vc_amd.config import DanConfig
     device_loader = args.train_loader_device == "gpu"
     if device_loader:
@@ -50,6 +69,8 @@ def train_main(args, argv) -> int:
         from dl4vc_amd.hdf5io import RawChunkFile
         try:
             for path in (args.train_file, args.test_file):
+                if not path:
+                    continue                                  # (--train_bam / --test_bam stand in for it)
                 with RawChunkFile(path) as raw:
                     check_layout(raw, DanConfig.from_args(args).reads)
         except (ValueError, RuntimeError, OSError, KeyError) as e:
@@ -66,6 +87,8 @@ def train_main(args, argv) -> int:
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    if world > 1:
+        whole_lines(sys.stdout)                               # (the ranks share one stdout)
     if args.gpus > 1 and world == 1:
         # one process per GPU (the reference: one process, nn.DataParallel over args.gpus devices, main.py:117)
         import socket
@@ -121,8 +144,33 @@ def train_main(args, argv) -> int:
     from dl4vc_amd.train_data import BatchPrefetcher, DeviceBatchPrefetcher
     from dl4vc_amd.train_data import BatchError
 
+    def budget():
+        # one budget for the trimmed records of both files; by default three quarters of what is free now that the trainer has
+        # allocated (it bounds the records' bytes: each file's last slab is allocated whole).  A fill from a BAM asks once its
+        # staging planes are allocated, so that they are not counted as free
+        if cache["left"] is None:
+            import torch
+            cache["left"] = getattr(args, "train_cache_bytes", 0) or torch.cuda.mem_get_info(0)[0] * 3 // 4
+        return cache["left"]
+
     def open_loader(path, batch_sites):
         # loader workers (main.py:59-60: DataLoader(num_workers=args.num_data_workers)); 0 = assemble in this process
+        from dl4vc_amd.chunk_loader import BamSource
+        if isinstance(path, BamSource):
+            t0 = time.time()
+            try:
+                loader = DeviceBatchPrefetcher(path, cfg.reads, batch_sites, device=0, use_q=cfg.use_q, use_strand=cfg.use_strand,
+                                               resident=True, cache_bytes=budget)
+            except (ValueError, RuntimeError) as e:
+                raise SystemExit("--train-cache-device gpu: %s" % e)
+            st = loader.stage
+            cache["left"] -= st["store_bytes"]
+            print("--train-cache-device gpu: %s: %d records resident in %d bytes (%.3f of their %d plane bytes), filled in %.2f s; %d "
+                  "locations: %d on the GPU, %d by pe_encode, %d by the Python builder, %d without a record"
+                  % (path.bam, st["store_records"], st["store_bytes"], st["store_bytes"] / max(1, loader.loader.inflated_bytes),
+                     loader.loader.inflated_bytes, time.time() - t0, st["locations"], st["gpu"], st["native"], st["python"],
+                     st["no_record"]), flush=True)
+            return loader
         if not device_loader:
             return BatchPrefetcher(path, args.num_data_workers)
         if not resident:
@@ -130,15 +178,10 @@ def train_main(args, argv) -> int:
                 return DeviceBatchPrefetcher(path, cfg.reads, batch_sites, device=0, use_q=cfg.use_q, use_strand=cfg.use_strand)
             except (ValueError, RuntimeError) as e:
                 raise SystemExit("--train-loader-device gpu: %s" % e)
-        if cache["left"] is None:
-            # one budget for the trimmed records of both files; by default three quarters of what is free now that the trainer has
-            # allocated (it bounds the records' bytes: each file's last slab is allocated whole)
-            import torch
-            cache["left"] = getattr(args, "train_cache_bytes", 0) or torch.cuda.mem_get_info(0)[0] * 3 // 4
         t0 = time.time()
         try:
             loader = DeviceBatchPrefetcher(path, cfg.reads, batch_sites, device=0, use_q=cfg.use_q, use_strand=cfg.use_strand,
-                                           resident=True, cache_bytes=cache["left"])
+                                           resident=True, cache_bytes=budget())
         except (ValueError, RuntimeError) as e:
             raise SystemExit("--train-cache-device gpu: %s" % e)
         st = loader.stage
@@ -149,7 +192,8 @@ def train_main(args, argv) -> int:
         return loader
 
     try:
-        train_loop(args, cfg, hyper, trainer, open_loader, per_rank, rank, world, dist, all_reduce, gather, exchange)
+        train_loop(args, cfg, hyper, trainer, open_loader, per_rank, rank, world, dist, all_reduce, gather, exchange,
+                   train_source, test_source)
     except BatchError as e:
         # a damaged chunk or a record the loader refuses: the reason, not a traceback (under --gpus N the parent ends the other
         # ranks as soon as this one has exited, ``procs.wait_children``)
@@ -160,23 +204,84 @@ def train_main(args, argv) -> int:
     return 0
 
 
-def train_loop(args, cfg, hyper, trainer, open_loader, per_rank, rank, world, dist, all_reduce, gather, exchange) -> None:
-    """The epochs of ``train_main``: train, decay the learning rate, evaluate, save."""
+class RecordCount:
+    """What ``train_epoch`` and ``evaluate`` need of a source when a loader makes their batches: how many records there are."""
+
+    def __init__(self, n):
+        self.n = int(n)
+
+    def __len__(self):
+        return self.n
+
+
+def bam_sources(args):
+    """--train_bam -> (the training source, the evaluation source): ``chunk_loader.BamSource``s, or --test_file's path.  The
+    locations are built as tools/convert_bam_single_reads.py builds them -- tp (label 0, with the full VCF's genotypes), fn (1), fp (2),
+    in that order -- so record i is record i of the file the converter would write and draws its read subset with the same seed."""
+    from dl4vc_amd.chunk_loader import BamSource
+    from dl4vc_amd.pileup_encoder import locations_from_vcf
+    get = lambda k: getattr(args, k, None)   # noqa: E731
+
+    def labelled(prefix):
+        locs = []
+        if get(prefix + "_tp_vcf"):
+            locs += locations_from_vcf(get(prefix + "_tp_vcf"), 0, get(prefix + "_tp_full_vcf"))
+        if get(prefix + "_fn_vcf"):
+            locs += locations_from_vcf(get(prefix + "_fn_vcf"), 1)
+        if get(prefix + "_fp_vcf"):
+            locs += locations_from_vcf(get(prefix + "_fp_vcf"), 2)
+        return locs
+
+    try:
+        train = BamSource(args.train_bam, args.train_fasta, labelled("train"), inflate_device=args.inflate_device)
+        if not args.test_bam:
+            return train, args.test_file
+        if any(get("test_%s_vcf" % k) for k in ("tp", "fn", "fp")):
+            locs = labelled("test")
+        else:
+            locs = locations_from_vcf(args.sample_vcf, label=2)   # (as in inference)
+        return train, BamSource(args.test_bam, args.test_fasta, locs, inflate_device=args.inflate_device)
+    except (OSError, ValueError, IndexError) as e:
+        raise SystemExit("--train_bam: the location VCFs could not be read: %s" % e)
+
+
+def train_loop(args, cfg, hyper, trainer, open_loader, per_rank, rank, world, dist, all_reduce, gather, exchange,
+               train_source=None, test_source=None) -> None:
+    """The epochs of ``train_main``: train, decay the learning rate, evaluate, save.  ``train_source`` / ``test_source``:
+    --train_file's and --test_file's paths (the default), or the ``BamSource``s of --train_bam / --test_bam -- then the resident
+    records give the record count and the chromosomes that a file gives otherwise."""
+    import contextlib
     import numpy as np
     from dl4vc_amd.trainer import train_epoch, evaluate, save_checkpoint, checkpoint_state
     from dl4vc_amd.train_data import EasyExampleSampler
     from dl4vc_amd.hdf5io import CandidateFile
     from dl4vc_amd.model import DanNet
     from dl4vc_amd.vcf import start_scored_vcf, scored_vcf_path
-    from dl4vc_amd.inference import select_sites
+    from dl4vc_amd.inference import select_records, select_sites
     from dl4vc_amd.shard import check_replicas_agree
     best_loss = None
-    with CandidateFile(args.train_file) as train_src, CandidateFile(args.test_file) as test_src, \
-            open_loader(args.train_file, per_rank) as train_loader, open_loader(args.test_file, args.test_batch_size) as test_loader:
+    train_source = args.train_file if train_source is None else train_source
+    test_source = args.test_file if test_source is None else test_source
+    with contextlib.ExitStack() as stack:
+        on_file = [isinstance(s, str) for s in (train_source, test_source)]
+        train_src = stack.enter_context(CandidateFile(train_source)) if on_file[0] else None
+        test_src = stack.enter_context(CandidateFile(test_source)) if on_file[1] else None
+        train_loader = stack.enter_context(open_loader(train_source, per_rank))
+        test_loader = stack.enter_context(open_loader(test_source, args.test_batch_size))
+        if train_src is None:
+            train_src = RecordCount(len(train_loader))
+        if test_src is None:
+            test_src = RecordCount(len(test_loader))
+
+        def held_out(source, loader, chromosomes):
+            if isinstance(source, str):
+                return select_sites(source, chromosomes)
+            return select_records(loader.loader.chromosomes(), chromosomes)
+
         holdout = None
         if args.train_holdout_chromosomes:
             holdout = np.zeros(len(train_src), bool)
-            holdout[select_sites(args.train_file, args.train_holdout_chromosomes)] = True
+            holdout[held_out(train_source, train_loader, args.train_holdout_chromosomes)] = True
         # every rank draws the same epoch order (same seed) and takes its DataParallel-style share of every batch
         plain = args.close_examples_sample_rate >= 1.0                # main.py:72-77: then a plain shuffled loader, no sampler
         if plain:
@@ -186,7 +291,7 @@ def train_loop(args, cfg, hyper, trainer, open_loader, per_rank, rank, world, di
                       "skipped; use --close_examples_sample_rate < 1 to hold them out" % int(holdout.sum()))
         sampler = EasyExampleSampler(len(train_src), close_keep=min(1.0, args.close_examples_sample_rate), holdout=holdout,
                                      rng=np.random.RandomState(args.seed), plain=plain)
-        test_idx = select_sites(args.test_file, args.test_holdout_chromosomes) if args.test_holdout_chromosomes else None
+        test_idx = held_out(test_source, test_loader, args.test_holdout_chromosomes) if args.test_holdout_chromosomes else None
         for epoch in range(1, args.epochs + 1):
             s = time.time()
             print("Train Epoch: %d lr: [%s] on %d GPUs!" % (epoch, trainer.hyper.lr, world))
@@ -287,7 +392,8 @@ def check_bam_arguments(args) -> None:
     if args.test_file:
         raise SystemExit("--test_file and --test_bam are two sources of the same sites: give exactly one")
     if args.train_file:
-        raise SystemExit("--test_bam is an inference input; training evaluates on a --test_file")
+        raise SystemExit("--test_bam is an inference input; training from a --train_file evaluates on a --test_file (--train_bam takes a "
+                         "--test_bam beside it)")
     if not args.test_fasta or not args.sample_vcf:
         raise SystemExit("--test_bam needs --test_fasta (the reference) and --sample_vcf (the candidate VCF: its records are the sites)")
     if args.record_census:
@@ -358,11 +464,64 @@ def score_bam_census(args, net, target, out_final, shard_i, shard_n, holdout, si
     return n
 
 
+TRAIN_BAM_VCFS = ("train_tp_vcf", "train_tp_full_vcf", "train_fn_vcf", "train_fp_vcf")
+TEST_BAM_VCFS = ("test_tp_vcf", "test_tp_full_vcf", "test_fn_vcf", "test_fp_vcf")
+
+
+def flag(name: str) -> str:
+    return "--" + name
+
+
+def check_train_bam_arguments(args) -> None:
+    """--train_bam and the flags that belong to it: what they need and what they refuse, before anything touches a device."""
+    get = lambda k: getattr(args, k, None)   # noqa: E731
+    if not get("train_bam"):
+        given = [flag(k) for k in ("train_fasta",) + TRAIN_BAM_VCFS if get(k)]
+        if given:
+            raise SystemExit("%s belong(s) to --train_bam, which is not given (a --train_file holds its labels already)" % ", ".join(given))
+        given = [flag(k) for k in TEST_BAM_VCFS if get(k)]
+        if given:
+            raise SystemExit("%s belong(s) to --test_bam beside --train_bam (the labelled evaluation locations); %s"
+                             % (", ".join(given), "inference from --test_bam takes its locations from --sample_vcf" if args.test_bam
+                                else "--test_bam is not given"))
+        return
+    if args.train_file:
+        raise SystemExit("--train_file and --train_bam are two sources of the same records: give exactly one")
+    if not get("train_fasta"):
+        raise SystemExit("--train_bam needs --train_fasta (the reference)")
+    if not any(get(k) for k in ("train_tp_vcf", "train_fn_vcf", "train_fp_vcf")):
+        raise SystemExit("--train_bam needs its labelled locations: at least one of --train_tp_vcf (label 0), --train_fn_vcf (1), "
+                         "--train_fp_vcf (2)")
+    if get("train_tp_full_vcf") and not get("train_tp_vcf"):
+        raise SystemExit("--train_tp_full_vcf carries the genotypes of --train_tp_vcf, which is not given")
+    if args.train_loader_device != "gpu" or get("train_cache_device") != "gpu":
+        raise SystemExit("--train_bam needs --train-loader-device gpu --train-cache-device gpu: the records are encoded on the GPU into "
+                         "the resident record store; there is no host path and no non-resident path (convert to a --train_file with "
+                         "tools/convert_bam_single_reads.py for those)")
+    if bool(args.test_file) == bool(args.test_bam):
+        raise SystemExit("--train_bam evaluates on exactly one of --test_file and --test_bam: %s given"
+                         % ("both are" if args.test_file else "neither is"))
+    if not args.test_bam:
+        given = [flag(k) for k in TEST_BAM_VCFS if get(k)]
+        if given:
+            raise SystemExit("%s belong(s) to --test_bam, which is not given (a --test_file holds its labels already)" % ", ".join(given))
+    else:
+        if not args.test_fasta:
+            raise SystemExit("--test_bam needs --test_fasta (the reference)")
+        if get("test_tp_full_vcf") and not get("test_tp_vcf"):
+            raise SystemExit("--test_tp_full_vcf carries the genotypes of --test_tp_vcf, which is not given")
+        if not any(get(k) for k in ("test_tp_vcf", "test_fn_vcf", "test_fp_vcf")) and not args.sample_vcf:
+            raise SystemExit("--test_bam beside --train_bam needs its locations: --test_tp_vcf / --test_fn_vcf / --test_fp_vcf, or "
+                             "--sample_vcf (every location with label 2)")
+    if args.record_census:
+        raise SystemExit("--record-census gpu is an inference option: the resident records of --train_bam are counted when they are filled")
+
+
 def check_train_loader_device_arguments(args) -> None:
     """--train-loader-device: what it refuses (the files' own properties are checked when training starts)."""
     if args.train_loader_device != "gpu":
         raise SystemExit("--train-loader-device must be gpu")
-    if not args.train_file:
+    if not args.train_file and not getattr(args, "train_bam", None):
         raise SystemExit("--train-loader-device gpu is an option of --train_file (it assembles the training and evaluation batches "
                          "on the GPU); inference from a --test_file has --loader-device gpu")
 
@@ -387,7 +546,7 @@ def check_loader_device_arguments(args) -> None:
     if args.test_bam:
         raise SystemExit("--loader-device gpu is an option of --test_file (it inflates the candidate file's chunks on the GPU); "
                          "--test_bam reads no candidate file (its device option is --inflate-device gpu)")
-    if args.train_file:
+    if args.train_file or getattr(args, "train_bam", None):
         raise SystemExit("--loader-device gpu is an inference option: training and its evaluation keep the host loaders")
 
 
@@ -396,7 +555,8 @@ def main(argv=None) -> int:
     print(args)
     if args.inflate_device not in (None, "gpu"):
         raise SystemExit("--inflate-device must be gpu")
-    if args.inflate_device and not args.test_bam:
+    train_bam = getattr(args, "train_bam", None)
+    if args.inflate_device and not args.test_bam and not train_bam:
         raise SystemExit("--inflate-device gpu is an option of --test_bam (the GPU pileup encoder reads the BAM); a --test_file holds "
                          "pileups already encoded")
     if args.record_census not in (None, "gpu"):
@@ -404,15 +564,16 @@ def main(argv=None) -> int:
     if args.record_census and not args.test_bam:
         raise SystemExit("--record-census gpu is an option of --test_bam (it counts the locations of the candidate VCF that give a "
                          "record); the records of a --test_file are already counted")
+    check_train_bam_arguments(args)
     if args.loader_device is not None:
         check_loader_device_arguments(args)
     if args.train_loader_device is not None:
         check_train_loader_device_arguments(args)
     if hasattr(args, "train_cache_device") or hasattr(args, "train_cache_bytes"):
         check_train_cache_arguments(args)
-    if args.test_bam:
+    if args.test_bam and not train_bam:
         check_bam_arguments(args)
-    if args.train_file:
+    if args.train_file or train_bam:
         return train_main(args, list(argv if argv is not None else sys.argv[1:]))
     if not args.test_bam:
         assert args.test_file[-3:] == "hdf", "Test dataset must be in HDF format"                 # main.py:84

@@ -9,12 +9,15 @@
 # -c: the converter builds the pileups on the GPU and packs and compresses train.hdf's chunks there (--pileup-device gpu
 # --compress-device gpu): the same records.
 # -y (with -c): the compressed chunks get dynamic Huffman codes where they are smaller (--compress-codes dynamic): a smaller file.
+# -n: stop after isec/ -- no train.hdf is written -- and print the main.py flags that train straight from the BAM with these
+# outputs (--train_bam: the pileups are encoded on the GPU into the resident record store, the same records in the same order).
 set -e
-usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c [-y]]"; exit 1; }
+usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c [-y]] [-n]"; exit 1; }
 PROCS=16
 COMPRESS=""
 CODES=""
-while getopts "i:r:t:o:b:p:cyh" opt; do
+NOFILE=""
+while getopts "i:r:t:o:b:p:ncyh" opt; do
   case $opt in
     i) BAM=$OPTARG ;;
     r) REFERENCE=$OPTARG ;;
@@ -24,11 +27,13 @@ while getopts "i:r:t:o:b:p:cyh" opt; do
     p) PROCS=$OPTARG ;;
     c) COMPRESS=gpu ;;
     y) CODES=dynamic ;;
+    n) NOFILE=1 ;;
     *) usage ;;
   esac
 done
 [ -z "$BAM" ] || [ -z "$REFERENCE" ] || [ -z "$TRUTH" ] || [ -z "$OUTDIR" ] && usage
 [ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
+[ -n "$NOFILE" ] && [ -n "$COMPRESS" ] && { echo "-n writes no train.hdf, so there is nothing for -c to compress: give one of them"; exit 1; }
 SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 mkdir -p "$OUTDIR"
 if [ ! -f "$OUTDIR/candidates.vcf" ]; then
@@ -40,6 +45,14 @@ fi
 if [ ! -f "$OUTDIR/isec/0003.vcf" ]; then
   printf "Intersect candidates with the truth set...\n"
   python "$SCRIPTDIR/tools/vcf_isec.py" -p "$OUTDIR/isec" "$TRUTH" "$OUTDIR/candidates.vcf" > "$OUTDIR/isec.log" 2>&1
+fi
+if [ -n "$NOFILE" ]; then
+  echo "No train.hdf written.  Train straight from the BAM with:"
+  echo "  python $SCRIPTDIR/main.py --train_bam $BAM --train_fasta $REFERENCE --train_tp_vcf $OUTDIR/isec/0003.vcf" \
+       "--train_tp_full_vcf $OUTDIR/isec/0002.vcf --train_fp_vcf $OUTDIR/isec/0001.vcf --train-loader-device gpu --train-cache-device gpu" \
+       "( --test_file V.hdf | --test_bam Y.bam --test_fasta REF [--test_tp_vcf ... --test_tp_full_vcf ... --test_fp_vcf ...] )" \
+       "<flags of train_variant_caller.sh>"
+  exit 0
 fi
 if [ ! -f "$OUTDIR/train.hdf" ]; then
   printf "Convert candidates to HDF...\n"
