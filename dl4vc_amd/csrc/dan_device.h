@@ -153,6 +153,8 @@ constexpr int WHB = 102;                // first position of the upper half's ti
 // The split kernel's short units (windows of 209..304 columns, two units of <= 190 columns each: 161 at 301 columns) take SIX tiles per
 // lane: the lower-half lanes tile [0, 96), the upper-half lanes [94, 190) -- 94 == 2 mod 4 like 102, so that the sixteen lanes of a
 // ds_read_b128 group still touch rows of all eight residues mod 8.  6 / 7 of the matrix work of a layer for such a unit.
+// One-unit reads of up to MPOS_SHORT + 16 = 206 columns take the same six tiles and, for columns [190, 206), one direct-form
+// position tile per wave (conv_gemm_wino REM): 27 / 28 of the seven-tile form's conv MFMAs, and no tile slot past column 206.
 constexpr int MW_SHORT = 6;
 constexpr int WHB_SHORT = 94;
 constexpr int MPOS_SHORT = WHB_SHORT + 16 * MW_SHORT;    // 190: the longest unit the six-tile form covers
@@ -178,8 +180,15 @@ __device__ __forceinline__ v4f pk_sub(v4f a, v4f b, v2f m1) {
     return (v4f){lo[0], lo[1], hi[0], hi[1]};
 }
 __device__ __forceinline__ v4f pk_add(v4f a, v4f b) { return a + b; }
-template <int TW>
-__device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* xrow, gv4f_ptr wl, const v4f (&a_first)[4]) {
+// REM (the one-unit six-tile form, dan_kernels.hip): columns [MPOS_SHORT, MPOS_SHORT + 16) as ONE direct-form position tile beside the
+// walk -- per k-step three MFMAs (taps at rows p - 2, p, p + 2) on the layer's plain 3-tap fragments (wd: this wave's tile of the
+// W_OFF block, [tap][kg][tile][lane]), B fragments in the direct form's layout (xr: row p - 2 of position p = MPOS_SHORT + (lane & 15),
+// channels 4 (lane >> 4)).  The three weight fragments of a k-group are requested at its top and each tap's ds_read_b128 one
+// Winograd tile ahead of its MFMAs, which follow tiles 1, 3 and 5: nothing of the tile trails the walk.
+template <int TW, bool REM = false>
+__device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* xrow, gv4f_ptr wl, const v4f (&a_first)[4],
+                                               [[maybe_unused]] v4f& racc, [[maybe_unused]] const float* xr, [[maybe_unused]] gv4f_ptr wd) {
+    static_assert(!REM || TW == 6, "the remainder tile's taps follow tiles 1, 3 and 5 of a six-tile walk");
     v4f a_nxt[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) a_nxt[k] = a_first[k];
@@ -195,6 +204,11 @@ __device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* x
         const int gn = (g + 1 < KGC) ? g + 1 : g;            // last step: harmless re-read
 #pragma unroll
         for (int k = 0; k < 4; ++k) a_nxt[k] = wl[(size_t)(k * KGC + gn) * (KGC * 64)];
+        [[maybe_unused]] v4f ra[3], rb;
+        if constexpr (REM) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) ra[t] = wd[(size_t)(t * KGC + g) * (KGC * 64)];
+        }
         const float* xg = xrow + g * 16;
         const float* xn = xrow + gn * 16;
 #pragma unroll
@@ -209,6 +223,9 @@ __device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* x
                 xa = *(const v4f*)(xn); xb = *(const v4f*)(xn + 2 * LDS_S);
                 xc = *(const v4f*)(xn + 4 * LDS_S); xd = *(const v4f*)(xn + 6 * LDS_S);
             }
+            if constexpr (REM) {
+                if ((m & 1) == 0) rb = *(const v4f*)(xr + (m >> 1) * 2 * LDS_S + g * 16);
+            }
             // MFMAs at s_setprio 3, the VALU/LDS stretch that forms the next V at 0: the arbiter then serves the other
             // wave's MFMAs ahead of this wave's VALU stream (by default the OLDER wave's instructions of either kind come
             // first, and its VALU batches stall the younger wave's MFMA issue).  tools/ubench/wino_loop.hip: 37.6 -> 36.4
@@ -218,9 +235,20 @@ __device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* x
             for (int s = 0; s < 4; ++s)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) acc[m][k] = mfma16(a[k][s], v[k][s], acc[m][k]);
+            if constexpr (REM) {
+                if (m & 1) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) racc = mfma16(ra[m >> 1][s], rb[s], racc);
+                }
+            }
             __builtin_amdgcn_s_setprio(0);
         }
     }
+}
+template <int TW>
+__device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* xrow, gv4f_ptr wl, const v4f (&a_first)[4]) {
+    v4f none = splat(0.f);
+    conv_gemm_wino<TW, false>(acc, xrow, wl, a_first, none, nullptr, nullptr);
 }
 
 // LDS rows a Winograd GEMM may read: tiles past the window read beyond the activation rows (into whatever follows them)

@@ -50,14 +50,23 @@ constexpr int NSTAMP = 64;
 // may run past the activation into the constants that follow it in LDS) produce columns nobody stores.
 static_assert((HALO + WHB + 4 * (4 * MW - 1) + 1 + 4 + 1) * LDS_S <= LDS_ROWS * LDS_S + MAX_LAYERS * CST_FLOATS, "wino reads stay inside LDS");
 static_assert(WHB + 4 * (4 * MW - 1) + 3 >= MPOS - 1 && 4 * (4 * MW - 1) + 3 >= WHB - 1, "wino tiling covers the read");
-// ... and the six-tile form of the split kernel's short units (dan_device.h MW_SHORT): [0, 96) + [94, 190)
+// ... and the six-tile form (dan_device.h MW_SHORT): [0, 96) + [94, 190) -- the split kernel's short units, and every one-unit
+// read of up to 206 columns, whose columns [190, 206) are ONE direct-form position tile per wave (three MFMAs per k-step on the
+// layer's plain 3-tap fragments, conv_gemm_wino REM): 27 conv MFMAs per k-step and wave where seven tiles take 28.  Its taps
+// read rows p - 2 .. p + 2 of the image; rows at and past L keep the prologue's zeros.
+static_assert(HALO + MPOS_SHORT + 15 + 2 < LDS_ROWS && MPOS_SHORT + 16 <= MPOS, "the remainder tile's taps stay inside the image");
 static_assert(WHB_SHORT + 4 * (4 * MW_SHORT - 1) + 3 >= MPOS_SHORT - 1 && 4 * (4 * MW_SHORT - 1) + 3 >= WHB_SHORT - 1 && WHB_SHORT % 4 == 2,
               "short wino tiling covers its unit");
 
 // 1x1 GEMM in the same column mapping: acc[m][o] += W[own 16 channels][128] * x(P(m) + 2 o)
-template <int TW>
-__device__ __forceinline__ void gemm1x1_wino(v4f (&acc)[TW][2], const float* xrow, gv4f_ptr wl, v4f a_first) {
+// REM: one more column tile, the direct-form remainder tile (racc, B fragments from xr = row MPOS_SHORT + (lane & 15)), on the same
+// weight fragment; its four MFMAs close the k-group and its next ds_read_b128 goes out with the last Winograd tile's
+template <int TW, bool REM = false>
+__device__ __forceinline__ void gemm1x1_wino(v4f (&acc)[TW][2], const float* xrow, gv4f_ptr wl, v4f a_first,
+                                             [[maybe_unused]] v4f& racc, [[maybe_unused]] const float* xr) {
     v4f a_nxt = a_first, b[TW][2];
+    [[maybe_unused]] v4f rb;
+    if constexpr (REM) rb = *(const v4f*)xr;
 #pragma unroll
     for (int m = 0; m < TW; ++m)
 #pragma unroll
@@ -73,9 +82,18 @@ __device__ __forceinline__ void gemm1x1_wino(v4f (&acc)[TW][2], const float* xro
             for (int s = 0; s < 4; ++s)
 #pragma unroll
                 for (int o = 0; o < 2; ++o) acc[m][o] = mfma16(a[s], b[m][o][s], acc[m][o]);
+            if constexpr (REM) {
+                if (m + 1 == TW) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) racc = mfma16(a[s], rb[s], racc);
+                }
+            }
             __builtin_amdgcn_s_setprio(0);
 #pragma unroll
             for (int o = 0; o < 2; ++o) b[m][o] = *(const v4f*)(xrow + (4 * m + 2 * o) * LDS_S + gn * 16);
+            if constexpr (REM) {
+                if (m + 1 == TW) rb = *(const v4f*)(xr + gn * 16);
+            }
         }
     }
 }
@@ -93,19 +111,22 @@ __device__ __forceinline__ void gemm1x1_wino(v4f (&acc)[TW][2], const float* xro
 // item is (row, unit), `L` below is the UNIT's length and every position-indexed pointer is offset to the unit's first column;
 // what differs from the one-unit form is addressing (window stride Lw), the allele-agreement predicates (taken over the whole
 // window, not the unit) and the stores (own columns only, y out of place).  SPLIT = false compiles to the code it always was.
-// TW: Winograd tiles per lane -- MW = 7 (one unit of up to 208 columns) or, SPLIT, MW_SHORT = 6 (units of up to 190 columns: every
-// unit of a split Winograd read, e.g. 161 columns at a 301-column window; launch_segment).
+// TW: Winograd tiles per lane -- MW = 7 (one unit of 207 or 208 columns; and every direct form) or MW_SHORT = 6: SPLIT, units of up
+// to 190 columns (every unit of a split Winograd read, e.g. 161 columns at a 301-column window); one unit, a read of up to 206
+// columns -- REM = true with the remainder tile for 191 .. 206 columns, REM = false without it for a read that ends before the tile
+// (an instantiation of its own, chosen by L in launch_segment: no remainder MFMA, load, store or branch in it).
 // FOLD = true (with PERSIST, one unit per read, every row computed): the workgroup owns WHOLE SITES -- site s, rows 0 .. R-1 in
 // order, then its next site -- and forms the reductions over the read axis itself: after a row's last layer it adds the LDS
 // image to its own running planes in device memory (SegmentArgs::fold_scratch: sum, and max for the network's last segment;
 // fetched under the row's bottleneck GEMM, a thread only ever re-reads what it stored itself) and after the site's last row it
 // writes what read_mean_kernel / final_pool_kernel would have written, from the same operations in the same order.  The last
 // segment then writes no y at all.  No atomics and no hand-off between workgroups: the bits do not depend on the grid.
-template <bool WINO, bool PERSIST, bool SPLIT, int TW = MW, bool FOLD = false>
+template <bool WINO, bool PERSIST, bool SPLIT, int TW = MW, bool FOLD = false, bool REM = false>
 __global__ __launch_bounds__(SEG_THREADS, NWAVE / 4) void segment_kernel(SegmentArgs a_by_value) {
     static_assert(!FOLD || (PERSIST && !SPLIT), "the site-owning form is a persistent one-unit form");
-    static_assert((!(SPLIT && WINO) && TW == MW) || (SPLIT && WINO && TW == MW_SHORT), "six tiles per lane: the split Winograd kernel, and only it");
-    constexpr int TILES = TW == MW ? MT : (MPOS_SHORT + 15) / 16;           // 16-column tiles of the unit (bottleneck, table walk)
+    static_assert(TW == MW ? !(SPLIT && WINO) : (WINO && TW == MW_SHORT), "six tiles per lane: Winograd forms only, and the split one always");
+    static_assert(!REM || (WINO && !SPLIT && TW == MW_SHORT), "the remainder tile [190, 206): beside six Winograd tiles of a one-unit read");
+    constexpr int TILES = (SPLIT && WINO) ? (MPOS_SHORT + 15) / 16 : MT;    // 16-column tiles of the unit (bottleneck, table walk)
     // one allocation, so that the layout the Winograd tiles past the window rely on (constants right after the activation
     // rows) is explicit
     __shared__ __attribute__((aligned(16))) float lds[LDS_ROWS * LDS_S + MAX_LAYERS * CST_FLOATS];
@@ -468,6 +489,10 @@ next_row:                                                   // (PERSIST only: ba
         gv4f_ptr w_r1 = (gv4f_ptr)(wblk + WRES_OFF) + wave * 64 + lane;
         float* xw = xs + (HALO + wP0) * LDS_S;          // row of x(P(0)) (channel 0)
         v4f out[TW][2], pre_r1;
+        // REM: the remainder tile -- position rp = MPOS_SHORT + (lane & 15), this wave's channels chw .. chw + 3 (the MFMA's own
+        // output layout)
+        [[maybe_unused]] v4f rout = splat(0.f);
+        [[maybe_unused]] int rp = MPOS_SHORT + pos;
         int wp = wP0;
         float* xq;
         {
@@ -475,17 +500,25 @@ next_row:                                                   // (PERSIST only: ba
             const v4f bias = *(const v4f*)(lc + CST_BIAS + chw);
 #pragma unroll
             for (int m = 0; m < TW; ++m) { acc[m][0] = splat(0.f); acc[m][1] = bias; acc[m][2] = splat(0.f); acc[m][3] = splat(0.f); }
+            if constexpr (REM) rout = bias;
             STAMP(sb + 0);
+            auto gemm = [&](const v4f (&pre_w)[4]) {
+                if constexpr (REM)
+                    conv_gemm_wino<TW, true>(acc, xw - 2 * LDS_S + kk * 4, w_w, pre_w, rout, xs + (HALO + rp - 2) * LDS_S + kk * 4, (gv4f_ptr)(wblk + W_OFF) + wave * 64 + lane);
+                else
+                    conv_gemm_wino(acc, xw - 2 * LDS_S + kk * 4, w_w, pre_w);
+            };
             if constexpr (CARRY) {
                 const v4f pre_w[4] = {pc0, pc1, pc2, pc3};
-                conv_gemm_wino(acc, xw - 2 * LDS_S + kk * 4, w_w, pre_w);
+                gemm(pre_w);
             } else {
                 gv4f_ptr w0 = w_w;
                 const v4f pre_w[4] = {w0[0], w0[(size_t)KGC * (KGC * 64)], w0[(size_t)2 * KGC * (KGC * 64)], w0[(size_t)3 * KGC * (KGC * 64)]};
-                conv_gemm_wino(acc, xw - 2 * LDS_S + kk * 4, w_w, pre_w);
+                gemm(pre_w);
             }
             STAMP(sb + 1);
             asm volatile("" : "+v"(wp));       // keeps everything derived from it (addresses, masks) out of the GEMM's live set
+            if constexpr (REM) asm volatile("" : "+v"(rp));
             xq = xs + (HALO + wp) * LDS_S;
             // output transform, then ReLU and the folded BatchNorm (model.py:749-751); positions >= L stay zero
             // (on register pairs: packed fp32 adds and multiply-adds, the same operations in the same order per element.  Columns
@@ -509,7 +542,12 @@ next_row:                                                   // (PERSIST only: ba
                 out[m][0] = (v4f){o0l[0], o0l[1], o0h[0], o0h[1]};
                 out[m][1] = (v4f){o1l[0], o1l[1], o1h[0], o1h[1]};
             }
+            if constexpr (REM) {                            // the remainder tile is in direct form: relu(acc + b) sc + sh
+                const v2f rl = act(half(rout, 0), sc_lo, sh_lo), rh = act(half(rout, 1), sc_hi, sh_hi);
+                rout = (v4f){rl[0], rl[1], rh[0], rh[1]};
+            }
         }
+        [[maybe_unused]] float* const rcell = xs + (HALO + rp) * LDS_S + chw;     // the remainder tile's cell of the image
         int wl = min(wlim, L);                           // columns this lane stores: its tiling's, inside the window
         asm volatile("" : "+v"(wl));                    // (opaque: hipcc, knowing p < wl implies p < L, merges the residual's two loads below into one through a selected POINTER and fails on the LDS one's cast)
         // the accumulators fill the register file through the GEMM and the output transform: the later stages' first
@@ -550,6 +588,13 @@ next_row:                                                   // (PERSIST only: ba
                             out[m][o] = old + bres;
                         }
                     }
+                if constexpr (REM) {
+                    if (rp < L) {
+                        const v4f old = *(const v4f*)((const char*)yrow + (unsigned)(rp * CPAD + chw) * 4u);
+                        *(v4f*)rcell = rout;
+                        rout = old + bres;
+                    }
+                }
             } else {
 #pragma unroll
                 for (int m = 0; m < TW; ++m)
@@ -563,10 +608,17 @@ next_row:                                                   // (PERSIST only: ba
                             out[m][o] = old + bres;
                         }
                     }
+                if constexpr (REM) {
+                    if (rp < L) {
+                        const v4f old = *(const v4f*)rcell;
+                        *(v4f*)rcell = rout;
+                        rout = old + bres;
+                    }
+                }
             }
             __syncthreads();
             STAMP(sb + 4);
-            gemm1x1_wino(out, xq + kk * 4, w_r1, pre_r1);
+            gemm1x1_wino<TW, REM>(out, xq + kk * 4, w_r1, pre_r1, rout, xs + (HALO + rp) * LDS_S + kk * 4);
             STAMP(sb + 5);
             if (CARRY && l + 1 < a.l_end) first_frags(l + 1, pn0, pn1, pn2, pn3);
             if (bot_here) {
@@ -581,6 +633,9 @@ next_row:                                                   // (PERSIST only: ba
                     const int p = wp + 4 * m + 2 * o;
                     if (p < wl) *(v4f*)(xq + (4 * m + 2 * o) * LDS_S + chw) = out[m][o];
                 }
+            if constexpr (REM) {
+                if (rp < L) *(v4f*)rcell = rout;
+            }
         } else {
 #pragma unroll
             for (int m = 0; m < TW; ++m)
@@ -589,6 +644,9 @@ next_row:                                                   // (PERSIST only: ba
                     const int p = wp + 4 * m + 2 * o;
                     if (p < wl) *(v4f*)(xq + (4 * m + 2 * o) * LDS_S + chw) = out[m][o];
                 }
+            if constexpr (REM) {
+                if (rp < L) *(v4f*)rcell = rout;
+            }
         }
         layer_tail(l, lc, false);
         }
@@ -806,11 +864,16 @@ void launch_segment(const SegmentArgs& a0, int n_sites, int max_wgs, hipStream_t
     const bool split = a.units == 2;
     if (!split) { a.units = 1; a.Lw = a.L; a.y_out = a.y; }   // (callers that never heard of units: one unit, the whole window, in place)
     const int units = split ? 2 : 1;
+    // one-unit Winograd reads: up to 190 columns six Winograd tiles per lane, 191 .. 206 the same + the direct remainder tile, 207 and
+    // 208 seven tiles
+    const bool six = !split && a.L <= MPOS_SHORT, rem = !split && !six && a.L <= MPOS_SHORT + 16;
     if (a.fold) {                                           // (callers ask for it only where it applies: dan_capi.cpp)
         a.n_sites = n_sites;
         a.xcd_sites = (n_sites + 7) / 8;                    // the same XCD slices of whole sites as the row forms
         const dim3 grid((unsigned)segment_fold_workgroups(n_sites, max_wgs)), blk(SEG_THREADS);
-        if (a.wino) hipLaunchKernelGGL((segment_kernel<true, true, false, MW, true>), grid, blk, 0, s, a);
+        if (a.wino && rem) hipLaunchKernelGGL((segment_kernel<true, true, false, MW_SHORT, true, true>), grid, blk, 0, s, a);
+        else if (a.wino && six) hipLaunchKernelGGL((segment_kernel<true, true, false, MW_SHORT, true>), grid, blk, 0, s, a);
+        else if (a.wino) hipLaunchKernelGGL((segment_kernel<true, true, false, MW, true>), grid, blk, 0, s, a);
         else hipLaunchKernelGGL((segment_kernel<false, true, false, MW, true>), grid, blk, 0, s, a);
         return;
     }
@@ -831,10 +894,14 @@ void launch_segment(const SegmentArgs& a0, int n_sites, int max_wgs, hipStream_t
             else hipLaunchKernelGGL((segment_kernel<false, false, true>), grid, blk, 0, s, a);
         }
     } else if (persist) {
-        if (a.wino) hipLaunchKernelGGL((segment_kernel<true, true, false>), grid, blk, 0, s, a);
+        if (a.wino && rem) hipLaunchKernelGGL((segment_kernel<true, true, false, MW_SHORT, false, true>), grid, blk, 0, s, a);
+        else if (a.wino && six) hipLaunchKernelGGL((segment_kernel<true, true, false, MW_SHORT>), grid, blk, 0, s, a);
+        else if (a.wino) hipLaunchKernelGGL((segment_kernel<true, true, false>), grid, blk, 0, s, a);
         else hipLaunchKernelGGL((segment_kernel<false, true, false>), grid, blk, 0, s, a);
     } else {
-        if (a.wino) hipLaunchKernelGGL((segment_kernel<true, false, false>), grid, blk, 0, s, a);
+        if (a.wino && rem) hipLaunchKernelGGL((segment_kernel<true, false, false, MW_SHORT, false, true>), grid, blk, 0, s, a);
+        else if (a.wino && six) hipLaunchKernelGGL((segment_kernel<true, false, false, MW_SHORT>), grid, blk, 0, s, a);
+        else if (a.wino) hipLaunchKernelGGL((segment_kernel<true, false, false>), grid, blk, 0, s, a);
         else hipLaunchKernelGGL((segment_kernel<false, false, false>), grid, blk, 0, s, a);
     }
 }
