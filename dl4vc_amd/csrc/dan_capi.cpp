@@ -32,6 +32,8 @@ struct KernelStat {
     double ms = 0.0;
 };
 
+struct Family;
+
 }  // namespace
 
 struct dan_handle {
@@ -56,9 +58,9 @@ struct dan_handle {
     char* d_wlp = nullptr;                   // [layers][WP_LAYER_BYTES] 32x32x16 fragments of the ping-pong bf16 kernel (precision 2)
     char* d_wlr = nullptr;                   // the same blocks as 16x16x32 fragments (sixteen-wave form, dan_config.bf16_form = 1)
     float* d_wc16 = nullptr;                 // compression weights in the channel order of a 16-byte bf16 load of h
+    const float* d_hw = nullptr;             // d_wc or d_wc16: what the family's highway kernel reads
     float *d_wpool = nullptr, *d_cols = nullptr, *d_cp = nullptr, *d_zero = nullptr;   // conv(read-mean): weights [segment][128][384], scratch, result
-    bool use_p = false;                      // precision 2 on dan_kernels_bf16p.hip: y and h cross HBM as bf16
-    bool use_x = false;                      // precision 1 on dan_kernels_bf16x.hip: y crosses HBM as two bf16 planes (hi, lo)
+    const Family* fam = nullptr;             // the kernel family of cfg.precision (FAMILIES below), chosen by dan_finalize
     char* d_wlx = nullptr;                   // [layers][WX_LAYER_BYTES] hi / lo 16x16x32 fragments of the bf16x3 kernel
     unsigned res_mask = 0;
     float *d_emb = nullptr, *d_pe = nullptr;
@@ -173,15 +175,13 @@ const Tensor* need(dan_handle* h, const std::string& name, std::initializer_list
 //   packed[((tap*kg + g)*tiles + n)*64 + lane][s] = W[o = 16n + (lane&15)][c = 16g + 4(lane>>4) + s][tap]
 // W(o,c,tap) is supplied by the functor (zero outside the real extents).
 template <typename F>
-std::vector<float> pack_frag(int taps, int kg, int tiles, F W) {
-    std::vector<float> out((size_t)taps * kg * tiles * 64 * 4);
+void pack_frag(float* out, int taps, int kg, int tiles, F W) {
     size_t i = 0;
     for (int t = 0; t < taps; ++t)
         for (int g = 0; g < kg; ++g)
             for (int n = 0; n < tiles; ++n)
                 for (int lane = 0; lane < 64; ++lane)
                     for (int s = 0; s < 4; ++s) out[i++] = W(16 * n + (lane & 15), 16 * g + 4 * (lane >> 4) + s, t);
-    return out;
 }
 
 hipStream_t as_stream(void* s) { return (hipStream_t)s; }
@@ -197,11 +197,7 @@ uint16_t bf16_bits(float x) {
 // MFMA 32x32x16 bf16 A-fragment order of the ping-pong kernel (dan_kernels.h): fragment ((ks * taps + t) * nq + q), lane, j
 // (channel-group major: layer 1's three groups are the first nine steps of the walk):
 //   row m = lane & 31 -> output channel 32 q + 16 ((m >> 2) & 1) + 4 (m >> 3) + (m & 3),  k = 16 ks + 8 (lane >> 5) + j
-template <typename F>
-void pack_fragp(uint16_t* dst, int taps, int ksteps, int nq, F W);
-
 float bf16_float(uint16_t b) { uint32_t u = (uint32_t)b << 16; float x; memcpy(&x, &u, 4); return x; }
-
 template <typename F>
 void pack_fragp(uint16_t* dst, int taps, int ksteps, int nq, F W) {
     for (int t = 0; t < taps; ++t)
@@ -217,32 +213,16 @@ void pack_fragp(uint16_t* dst, int taps, int ksteps, int nq, F W) {
             }
 }
 
-// MFMA 16x16x32 bf16 A-fragment order of the sixteen-wave form: fragment ((ks * taps + t) * n_ct + ct), lane, j with
+// MFMA 16x16x32 bf16 A-fragment order of the sixteen-wave form (PLANES 1) and of the bf16x3 kernel (PLANES 2: hi and lo plane of a
+// tile side by side, lo = bf16(w - hi)): fragment (((ks * taps + t) * n_ct + ct) * PLANES + plane), lane, j with
 //   row r = lane & 15 of channel tile ct -> output channel 32 (ct >> 1) + 8 (r >> 2) + 4 (ct & 1) + (r & 3)   (a lane's two tiles of a
 //   column are 8 consecutive channels),  k = 32 ks + 8 (lane >> 4) + j
-template <typename F>
-void pack_fragr(uint16_t* dst, int taps, int ksteps, int n_ct, F W) {
+template <int PLANES, typename F>
+void pack_frag16(uint16_t* dst, int taps, int ksteps, int n_ct, F W) {
     for (int ks = 0; ks < ksteps; ++ks)
         for (int t = 0; t < taps; ++t)
             for (int ct = 0; ct < n_ct; ++ct) {
-                uint16_t* f = dst + ((size_t)(ks * taps + t) * n_ct + ct) * (WP_FRAG / 2);
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int r = lane & 15;
-                        const int o = 32 * (ct >> 1) + 8 * (r >> 2) + 4 * (ct & 1) + (r & 3);
-                        f[lane * 8 + j] = bf16_bits(W(o, 32 * ks + 8 * (lane >> 4) + j, t));
-                    }
-            }
-}
-
-// MFMA 16x16x32 bf16 A-fragment order of the bf16x3 kernel (dan_kernels_bf16x.hip): pack_fragr's row order, hi and lo plane of a
-// tile side by side -- fragment ((ks * taps + t) * n_ct + ct) * 2 + plane, lo = bf16(w - hi)
-template <typename F>
-void pack_fragx(uint16_t* dst, int taps, int ksteps, int n_ct, F W) {
-    for (int ks = 0; ks < ksteps; ++ks)
-        for (int t = 0; t < taps; ++t)
-            for (int ct = 0; ct < n_ct; ++ct) {
-                uint16_t* f = dst + ((size_t)(ks * taps + t) * n_ct + ct) * 2 * (WP_FRAG / 2);
+                uint16_t* f = dst + ((size_t)(ks * taps + t) * n_ct + ct) * PLANES * (WP_FRAG / 2);
                 for (int lane = 0; lane < 64; ++lane)
                     for (int j = 0; j < 8; ++j) {
                         const int r = lane & 15;
@@ -250,7 +230,7 @@ void pack_fragx(uint16_t* dst, int taps, int ksteps, int n_ct, F W) {
                         const float w = W(o, 32 * ks + 8 * (lane >> 4) + j, t);
                         const uint16_t hi = bf16_bits(w);
                         f[lane * 8 + j] = hi;
-                        f[WP_FRAG / 2 + lane * 8 + j] = bf16_bits(w - bf16_float(hi));
+                        if (PLANES == 2) f[WP_FRAG / 2 + lane * 8 + j] = bf16_bits(w - bf16_float(hi));
                     }
             }
 }
@@ -289,6 +269,411 @@ int segment_halo(const dan_config& c, int l_begin, int l_end) {
     int halo = 0;
     for (int l = l_begin; l < l_end; ++l) halo += (l == 0) ? 1 : (l + 1 < c.layers ? c.dil_mid : c.dil_final);
     return halo;
+}
+
+// ---- one seam per kernel family (dan_config.precision) ------------------------------------------------------------------------
+// One segment launch of one chunk, as the chunk loop sees it; a family's function below turns it into its kernel's arguments.
+struct SegmentCall {
+    int sg, ns;                              // segment, sites of the chunk
+    const uint8_t *reads, *qual, *strand, *ref, *ref_mask, *var_mask;   // the six input planes at the chunk's offset
+    float *y_in, *y_out;                     // the previous segment's output and this one's (two buffers only where the window is split)
+    float* tap;                              // null: the tap layer is not in this segment
+    bool fold;                               // fp32 only: the read-axis pooling inside the segment kernel ...
+    float* feat;                             // ... which writes the chunk's feature rows from the last segment
+};
+
+// the fields SegmentArgs, SegmentXArgs and SegmentPArgs name alike
+template <class Args>
+void fill_segment_common(Args& a, const dan_handle* h, const SegmentCall& q) {
+    const dan_config& c = h->cfg;
+    a.l_begin = h->seg_begin[q.sg]; a.l_end = h->seg_end[q.sg];
+    a.n_layers = c.layers; a.dil_mid = c.dil_mid; a.dil_final = c.dil_final;
+    a.res_mask = h->res_mask; a.has_hw = c.bottleneck > 0;
+    a.R = c.reads; a.L = c.length;
+    a.reads = q.reads; a.qual = q.qual; a.strand = q.strand; a.ref = q.ref; a.ref_mask = q.ref_mask; a.var_mask = q.var_mask;
+    a.emb = h->d_emb; a.pe = h->d_pe;
+    a.h_layer_stride = (long long)h->chunk * c.reads * c.length * HPAD;
+    a.tap = q.tap; a.tap_layer = h->tap_layer;
+    a.work = h->d_work; a.work_count = h->d_rowsrc ? h->d_work_count : nullptr;
+}
+
+int segment_fp32(dan_handle* h, const SegmentCall& q, hipStream_t s) {
+    SegmentArgs a{};
+    fill_segment_common(a, h, q);
+    // one unit per read and y in place -- or, above MPOS columns, two units per read and y alternating between two buffers (a unit
+    // reads the other unit's columns of the input while that one stores its output); dan_create checked that the units fit
+    if (!plan_units(a, a.L, segment_halo(h->cfg, a.l_begin, a.l_end))) return fail(h, DAN_ERR_STATE, "unit plan failed for segment %d", q.sg);
+    a.wl = h->d_wl; a.wino = h->wino; a.l0_tab = h->d_l0tab;
+    a.y = q.y_in; a.y_out = q.y_out; a.pool = q.sg > 0 ? h->d_pool : nullptr; a.h = h->d_h;
+    if (q.fold) {
+        a.fold = 1; a.fold_scratch = h->d_fold;
+        if (q.sg + 1 < h->n_segments) a.fold_pool = h->d_pool;
+        else { a.fold_feat = q.feat; a.fold_feat_stride = h->F_stride; a.fold_C = h->cfg.c_final; }
+    }
+    launch_segment(a, q.ns, h->n_cus, s);
+    return DAN_OK;
+}
+
+int segment_bf16x(dan_handle* h, const SegmentCall& q, hipStream_t s) {
+    SegmentXArgs a{};
+    fill_segment_common(a, h, q);
+    if (!plan_units(a, a.L, segment_halo(h->cfg, a.l_begin, a.l_end))) return fail(h, DAN_ERR_STATE, "unit plan failed for segment %d", q.sg);   // (as in segment_fp32)
+    a.wl = h->d_wlx;
+    a.stagger = -1;                                          // (the launcher's own start offsets)
+    a.y = (uint16_t*)q.y_in; a.y_out = (uint16_t*)q.y_out; a.pool = q.sg > 0 ? h->d_cp : nullptr; a.h = h->d_h;
+    launch_segmentx(a, q.ns, h->n_cus, s);
+    return DAN_OK;
+}
+
+int segment_bf16p(dan_handle* h, const SegmentCall& q, hipStream_t s) {
+    SegmentPArgs a{};
+    fill_segment_common(a, h, q);
+    a.wl = h->d_wlp; a.wlr = h->d_wlr; a.form = h->cfg.bf16_form;
+    a.y = (uint16_t*)h->d_y; a.pool = q.sg > 0 ? h->d_cp : nullptr; a.h = (uint16_t*)h->d_h;     // (one unit up to P_LMAX: y in place)
+    launch_segmentp(a, q.ns, h->n_cus, s);
+    return DAN_OK;
+}
+
+// the launchers of dan_kernels.h behind one signature per tail: y / h as const void* (fp32, bf16 or two bf16 planes)
+typedef void ReadMeanFn(const void* y, float* pool, int n, int R, int L, const int* rs, hipStream_t s);
+typedef void FinalPoolFn(const void* y, float* feat, long long fs, int n, int R, int L, int C, const int* rs, hipStream_t s);
+typedef void HighwayFn(const void* hb, long long hls, const float* wc, long long wcls, const float* bc, float* feat, long long fs, int off, int n, int R, int L, int H, int nl, const int* rs, hipStream_t s);
+void read_mean_f32(const void* y, float* pool, int n, int R, int L, const int* rs, hipStream_t s) { launch_read_mean((const float*)y, pool, n, R, L, rs, s); }
+void read_mean_x(const void* y, float* pool, int n, int R, int L, const int* rs, hipStream_t s) { launch_read_meanx((const uint16_t*)y, pool, n, R, L, rs, s); }
+void read_mean_16(const void* y, float* pool, int n, int R, int L, const int* rs, hipStream_t s) { launch_read_mean16((const uint16_t*)y, pool, n, R, L, rs, s); }
+void final_pool_f32(const void* y, float* feat, long long fs, int n, int R, int L, int C, const int* rs, hipStream_t s) { launch_final_pool((const float*)y, feat, fs, n, R, L, C, rs, s); }
+void final_pool_x(const void* y, float* feat, long long fs, int n, int R, int L, int C, const int* rs, hipStream_t s) { launch_final_poolx((const uint16_t*)y, feat, fs, n, R, L, C, rs, s); }
+void final_pool_16(const void* y, float* feat, long long fs, int n, int R, int L, int C, const int* rs, hipStream_t s) { launch_final_pool16((const uint16_t*)y, feat, fs, n, R, L, C, rs, s); }
+void highway_f32(const void* hb, long long hls, const float* wc, long long wcls, const float* bc, float* feat, long long fs, int off, int n, int R, int L, int H,
+                 int nl, const int* rs, hipStream_t s) { launch_highway((const float*)hb, hls, wc, wcls, bc, feat, fs, off, n, R, L, H, nl, rs, s); }
+void highway_16(const void* hb, long long hls, const float* wc, long long wcls, const float* bc, float* feat, long long fs, int off, int n, int R, int L, int H,
+                int nl, const int* rs, hipStream_t s) { launch_highway16((const uint16_t*)hb, hls, wc, wcls, bc, feat, fs, off, n, R, L, H, nl, rs, s); }
+
+// What the forward asks of a family, one row per precision; everything else in forward_device_impl is the same for the three.
+struct Family {
+    int (*segment)(dan_handle*, const SegmentCall&, hipStream_t);
+    ReadMeanFn* read_mean;
+    FinalPoolFn* final_pool;
+    HighwayFn* highway;                      // (reads dan_handle::d_hw: the compression weights in its order)
+    bool conv_pool;                          // the read-mean enters the layer behind it as conv(pool) (launch_conv_pool), not inside the segment
+    int elem_bytes;                          // bytes per element of y and h in HBM
+    int y_copies;                            // buffers of y for windows above MPOS columns (two units per read: y out of place)
+    // the reductions read the buffer the last segment wrote (false: always d_y).  This documents an invariant and switches nothing: a
+    bool tails_follow_y;                     // family with one y buffer never splits a window, so that buffer IS d_y there
+};
+const Family FAMILIES[3] = {
+    {segment_fp32, read_mean_f32, final_pool_f32, highway_f32, false, 4, 2, true},   // 0: fp32 MFMA (dan_kernels.hip)
+    {segment_bf16x, read_mean_x, final_pool_x, highway_f32, true, 4, 2, true},       // 1: bf16x3 (dan_kernels_bf16x.hip): y as hi / lo bf16 planes, h fp32
+    {segment_bf16p, read_mean_16, final_pool_16, highway_16, true, 2, 1, false},     // 2: plain bf16 (dan_kernels_bf16p.hip): y and h as bf16
+};
+
+// ---- dan_finalize: the conv stack's weights, packed per family from one per-layer source ---------------------------------------
+// What every family packs conv layer l from: the checkpoint's tensors behind the canonical channel order (zero outside the real
+// extents).  layer_source also writes the layer's fp32 constants, which every family copies from the fp32 block.
+struct LayerSrc {
+    int l = 0, cin = 0, cout = 0, H = 0, L = 0;
+    std::vector<int> inv;                                    // canonical channel -> reference channel
+    const Tensor *w = nullptr, *wr = nullptr, *wb = nullptr, *wcm = nullptr, *bcm = nullptr;
+    float Wf(int o, int cc, int t) const {
+        if (o >= cout || cc >= (int)inv.size() || inv[cc] < 0) return 0.f;
+        return w->data[((size_t)o * cin + inv[cc]) * 3 + t];
+    }
+    float Wr(int o, int cc) const { return (o < cout && cc < cout) ? wr->data[(size_t)o * cout + cc] : 0.f; }
+    float Wb(int o, int cc) const { return (o < H && cc < cout) ? wb->data[(size_t)o * cout + cc] : 0.f; }
+    float Wc(int o, int cc, int pp) const { return (o < H && cc < H) ? wcm->data[((size_t)o * H + cc) * L + pp] : 0.f; }
+};
+
+// the tensors of 0-based layer l (checked), its constants cst[CST_FLOATS] (bias, folded eval BN, residual and bottleneck biases)
+// and its bit of res_mask
+int layer_source(dan_handle* h, int l, float* cst, LayerSrc* s) {
+    const dan_config& c = h->cfg;
+    const int l1 = l + 1;
+    int rc = DAN_OK, dil;
+    s->l = l; s->H = c.bottleneck; s->L = c.length;
+    layer_dims(c, l1, &s->cin, &s->cout, &dil);
+    const int cin = s->cin, cout = s->cout, H = s->H;
+    const std::string p = "conv1D_layers." + std::to_string(l);
+    s->w = need(h, p + ".weight", {cout, cin, 1, 3}, &rc); if (!s->w) return rc;
+    const Tensor* b = need(h, p + ".bias", {cout}, &rc); if (!b) return rc;
+    // canonical position of the reference's layer-1 input channels (model.py:517,543,558,625)
+    std::vector<int> canon;
+    for (int i = 0; i < 2 * EMBED; ++i) canon.push_back(i);
+    if (c.use_q) canon.push_back(40);
+    if (c.use_strand) canon.push_back(41);
+    if (c.use_mask) { canon.push_back(42); canon.push_back(43); canon.push_back(44); }
+    s->inv.assign((l == 0 ? KG0 : KGC) * 16, -1);
+    for (int i = 0; i < cin; ++i) s->inv[l == 0 ? canon[i] : i] = i;
+    for (int o = 0; o < cout; ++o) { cst[CST_BIAS + o] = b->data[o]; cst[CST_SCALE + o] = 1.f; }
+    if (c.use_bn) {                                          // eval-mode BN after the ReLU, eps 1e-5 (model.py:750-751)
+        const std::string q = "bn1D_layers." + std::to_string(l);
+        const Tensor* g = need(h, q + ".weight", {cout}, &rc); if (!g) return rc;
+        const Tensor* be = need(h, q + ".bias", {cout}, &rc); if (!be) return rc;
+        const Tensor* mu = need(h, q + ".running_mean", {cout}, &rc); if (!mu) return rc;
+        const Tensor* var = need(h, q + ".running_var", {cout}, &rc); if (!var) return rc;
+        for (int o = 0; o < cout; ++o) {
+            const double sc = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
+            cst[CST_SCALE + o] = (float)sc;
+            cst[CST_SHIFT + o] = (float)((double)be->data[o] - (double)mu->data[o] * sc);
+        }
+    }
+    if (is_residual(c, l1)) {
+        const std::string q = "residual_conv_layers." + std::to_string(l1 - c.residual_start);   // model.py:760
+        s->wr = need(h, q + ".weight", {cout, cout, 1, 1}, &rc); if (!s->wr) return rc;
+        const Tensor* br = need(h, q + ".bias", {cout}, &rc); if (!br) return rc;
+        for (int o = 0; o < cout; ++o) cst[CST_BRES + o] = br->data[o];
+        h->res_mask |= 1u << l;
+    }
+    if (H > 0) {
+        const std::string q = "conv1D_bottleneck_layers." + std::to_string(l);
+        s->wb = need(h, q + ".weight", {H, cout, 1, 1}, &rc); if (!s->wb) return rc;
+        const Tensor* bb = need(h, q + ".bias", {H}, &rc); if (!bb) return rc;
+        for (int o = 0; o < H; ++o) cst[CST_BBOT + o] = bb->data[o];
+        const std::string z = "conv1D_compression_layers." + std::to_string(l);
+        s->wcm = need(h, z + ".weight", {H, H, 1, c.length}, &rc); if (!s->wcm) return rc;
+        s->bcm = need(h, z + ".bias", {H}, &rc); if (!s->bcm) return rc;
+    }
+    return DAN_OK;
+}
+
+// layer 1 by table (dan_kernels.h L0_*): conv1 is linear in the terms its input column is a sum of; sums in double
+std::vector<float> layer0_table(const LayerSrc& s, const Tensor& emb, const Tensor& pe) {
+    const int L = s.L;
+    std::vector<float> tab(l0_tab_floats(L), 0.f);
+    for (int t = 0; t < 3; ++t)
+        for (int o = 0; o < CPAD; ++o) {
+            for (int ta = 0; ta < VOCAB; ++ta)
+                for (int tb = 0; tb < VOCAB; ++tb) {
+                    double v = 0.0;
+                    for (int e = 0; e < EMBED; ++e)
+                        v += (double)s.Wf(o, e, t) * emb.data[(size_t)ta * EMBED + e] + (double)s.Wf(o, EMBED + e, t) * emb.data[(size_t)tb * EMBED + e];
+                    tab[L0_TJ_OFF + ((size_t)t * L0_NTJ + ta * 10 + tb) * CPAD + o] = (float)v;
+                }
+            for (int k = 0; k < 5; ++k) tab[L0_WSC_OFF + ((size_t)k * 3 + t) * CPAD + o] = s.Wf(o, 2 * EMBED + k, t);
+        }
+    // the positional term of tap t at column w: sum_e (W[o][e][t] + W[o][20 + e][t]) pe[w][e]; PE[variant][w] = the taps whose
+    // column w + t - 1 exists for a unit that has / lacks a left / right neighbour at w (and lies inside the window anyway)
+    std::vector<double> pet((size_t)3 * L * CPAD);
+    for (int t = 0; t < 3; ++t)
+        for (int wcol = 0; wcol < L; ++wcol)
+            for (int o = 0; o < CPAD; ++o) {
+                double v = 0.0;
+                for (int e = 0; e < EMBED; ++e) v += ((double)s.Wf(o, e, t) + (double)s.Wf(o, EMBED + e, t)) * pe.data[(size_t)wcol * EMBED + e];
+                pet[((size_t)t * L + wcol) * CPAD + o] = v;
+            }
+    for (int var = 0; var < 3; ++var)
+        for (int wcol = 0; wcol < L; ++wcol)
+            for (int o = 0; o < CPAD; ++o) {
+                double v = pet[((size_t)1 * L + wcol) * CPAD + o];
+                if (var != 1 && wcol - 1 >= 0) v += pet[((size_t)0 * L + wcol - 1) * CPAD + o];
+                if (var != 2 && wcol + 1 < L) v += pet[((size_t)2 * L + wcol + 1) * CPAD + o];
+                tab[L0_PE_OFF + ((size_t)var * L + wcol) * CPAD + o] = (float)v;
+            }
+    return tab;
+}
+
+// the fp32 block of a layer (dan_kernels.h): MFMA fragments of the conv, its Winograd F(2,3) form, the residual and the bottleneck
+void pack_layer_fp32(const LayerSrc& s, float* blk) {
+    auto Wf = [&](int o, int cc, int t) { return s.Wf(o, cc, t); };
+    pack_frag(blk + W_OFF, 3, s.l == 0 ? KG0 : KGC, KGC, Wf);
+    if (s.l > 0) {
+        // Winograd F(2,3) weight transform U = [g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2], formed in double
+        auto Wu = [&](int o, int cc, int k) -> float {
+            const double g0 = s.Wf(o, cc, 0), g1 = s.Wf(o, cc, 1), g2 = s.Wf(o, cc, 2);
+            return k == 0 ? (float)g0 : k == 1 ? (float)((g0 + g1 + g2) * 0.5) : k == 2 ? (float)((g0 - g1 + g2) * 0.5) : (float)g2;
+        };
+        pack_frag(blk + WW_OFF, 4, KGC, KGC, Wu);
+    }
+    if (s.wr) pack_frag(blk + WRES_OFF, 1, KGC, KGC, [&](int o, int cc, int) { return s.Wr(o, cc); });
+    if (s.wb) pack_frag(blk + WBOT_OFF, 1, KGC, 2, [&](int o, int cc, int) { return s.Wb(o, cc); });
+}
+
+// the plain-bf16 blocks of a layer: 32x32x16 fragments of the eight-wave form (blkp), 16x16x32 of the sixteen-wave form (blkr)
+void pack_layer_bf16p(const LayerSrc& s, const float* cst, char* blkp, char* blkr) {
+    auto Wf = [&](int o, int cc, int t) { return s.Wf(o, cc, t); };
+    auto Wr = [&](int o, int cc, int) { return s.Wr(o, cc); };
+    auto Wb = [&](int o, int cc, int) { return s.Wb(o, cc); };
+    pack_fragp((uint16_t*)(blkp + WP_CONV_OFF), 3, s.l == 0 ? P_KS0 : P_KSC, 4, Wf);
+    pack_frag16<1>((uint16_t*)(blkr + WP_CONV_OFF), 3, s.l == 0 ? 2 : 4, 8, Wf);
+    if (s.wr) {
+        pack_fragp((uint16_t*)(blkp + WP_RES_OFF), 1, P_KSC, 4, Wr);
+        pack_frag16<1>((uint16_t*)(blkr + WP_RES_OFF), 1, 4, 8, Wr);
+    }
+    if (s.wb) {
+        pack_fragp((uint16_t*)(blkp + WP_BOT_OFF), 1, P_KSC, 1, Wb);
+        pack_frag16<1>((uint16_t*)(blkr + WP_BOT_OFF), 1, 4, 2, Wb);
+    }
+    memcpy(blkp + WP_CST_OFF, cst, CST_FLOATS * sizeof(float));
+    memcpy(blkr + WP_CST_OFF, cst, CST_FLOATS * sizeof(float));
+}
+
+// the bf16x3 block of a layer: hi / lo 16x16x32 fragments and the constants in this family's form
+void pack_layer_bf16x(const LayerSrc& s, const float* cst, char* blkx) {
+    pack_frag16<2>((uint16_t*)(blkx + WX_CONV_OFF), 3, s.l == 0 ? X_KS0 : X_KS, 8, [&](int o, int cc, int t) { return s.Wf(o, cc, t); });
+    if (s.wr) pack_frag16<2>((uint16_t*)(blkx + WX_RES_OFF), 1, X_KS, 8, [&](int o, int cc, int) { return s.Wr(o, cc); });
+    if (s.wb) pack_frag16<2>((uint16_t*)(blkx + WX_BOT_OFF), 1, X_KS, 2, [&](int o, int cc, int) { return s.Wb(o, cc); });
+    float* cx = (float*)(blkx + WX_CST_OFF);
+    memcpy(cx, cst, CST_FLOATS * sizeof(float));
+    // this family's epilogue computes relu(acc + b) * sc + sh as max(acc, -b) * sc + (sh + b * sc) (dan_kernels_bf16x.hip):
+    // the bias slot holds -b, the shift slot sh + b * sc (formed in double)
+    for (int ch = 0; ch < CPAD; ++ch) {
+        const double b = cx[CST_BIAS + ch];
+        cx[CST_SHIFT + ch] = (float)((double)cx[CST_SHIFT + ch] + b * (double)cx[CST_SCALE + ch]);
+        cx[CST_BIAS + ch] = (float)-b;
+    }
+}
+
+// conv(pool): the weights of a layer behind a pool layer as [o][t * 128 + c] -- bf16-rounded for the plain-bf16 kernel (its oracle's
+// "storage" mode), fp32 for bf16x3
+void pack_conv_pool(const LayerSrc& s, bool round_bf16, float* wp) {
+    for (int o = 0; o < CPAD; ++o)
+        for (int t = 0; t < 3; ++t)
+            for (int cc = 0; cc < CPAD; ++cc)
+                wp[((size_t)o * 3 + t) * CPAD + cc] = round_bf16 ? bf16_float(bf16_bits(s.Wf(o, cc, t))) : s.Wf(o, cc, t);
+}
+
+// highway compression weights of a layer: fp32 MFMA order (wc), the bias (bc) and, for launch_highway16, two bf16 planes (wc16 or null)
+void pack_highway(const LayerSrc& s, float* wc, float* bc, uint16_t* wc16) {
+    const int L = s.L;
+    // k = p*32 + c, k-group g = 2p + (c >> 4):  packed[g][n][lane][s] = Wc[o][c][p]
+    size_t i = 0;
+    for (int g = 0; g < 2 * L; ++g)
+        for (int n = 0; n < 2; ++n)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int k = 0; k < 4; ++k) wc[i++] = s.Wc(16 * n + (lane & 15), 16 * (g & 1) + 4 * (lane >> 4) + k, g >> 1);
+    for (int o = 0; o < s.H; ++o) bc[o] = s.bcm->data[o];
+    if (!wc16) return;
+    for (int pp = 0; pp < L; ++pp)
+        for (int n = 0; n < 2; ++n)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int s8 = 0; s8 < 8; ++s8) {
+                    const float w = s.Wc(16 * n + (lane & 15), 8 * (lane >> 4) + s8, pp);
+                    const uint16_t hi = bf16_bits(w);
+                    const size_t base = (((size_t)pp * 2 + n) * 2) * 64 * 8;
+                    wc16[base + (size_t)lane * 8 + s8] = hi;                                   // plane 0
+                    wc16[base + 64 * 8 + (size_t)lane * 8 + s8] = bf16_bits(w - bf16_float(hi));   // plane 1
+                }
+}
+
+// conv stack: one fixed-stride weight block per layer and family (dan_kernels.h), packed and uploaded; the fp32 block is packed at
+// every precision and is the source of every family's constants
+int pack_conv_stack(dan_handle* h, const Tensor& emb, const Tensor& pe) {
+    const dan_config& c = h->cfg;
+    const int L = c.length, H = c.bottleneck;
+    const bool is_x = c.precision == 1, is_p = c.precision == 2, conv_pool = h->fam->conv_pool;
+    const size_t hw_layer = (size_t)L * 2 * 2 * 64 * 4;      // floats: [g = 2L][tile 2][lane 64][4] = [pos][n 2][plane 2][lane 64][8 bf16]
+    const size_t wpool_seg = (size_t)CPAD * 3 * CPAD;
+    std::vector<float> wl((size_t)c.layers * LAYER_STRIDE, 0.f), wpool(conv_pool ? (size_t)h->n_segments * wpool_seg : 0, 0.f);
+    std::vector<char> wlp(is_p ? (size_t)c.layers * WP_LAYER_BYTES : 0, 0), wlr(wlp.size(), 0), wlx(is_x ? (size_t)c.layers * WX_LAYER_BYTES : 0, 0);
+    std::vector<float> wc16(is_p && H > 0 ? (size_t)c.layers * hw_layer : 0), wc(H > 0 ? (size_t)c.layers * hw_layer : 0);
+    std::vector<float> bc((size_t)c.layers * HPAD, 0.f);
+    int rc = DAN_OK;
+    h->res_mask = 0;
+    for (int l = 0; l < c.layers; ++l) {
+        float* blk = wl.data() + (size_t)l * LAYER_STRIDE;
+        LayerSrc src;
+        if ((rc = layer_source(h, l, blk + CST_OFF, &src))) return rc;
+        pack_layer_fp32(src, blk);
+        if (l == 0 && c.precision == 0 && (rc = dev_upload(h, &h->d_l0tab, layer0_table(src, emb, pe)))) return rc;
+        if (is_p) pack_layer_bf16p(src, blk + CST_OFF, wlp.data() + (size_t)l * WP_LAYER_BYTES, wlr.data() + (size_t)l * WP_LAYER_BYTES);
+        if (is_x) pack_layer_bf16x(src, blk + CST_OFF, wlx.data() + (size_t)l * WX_LAYER_BYTES);
+        if (conv_pool && l > 0)
+            for (int sg = 1; sg < h->n_segments; ++sg)
+                if (h->seg_begin[sg] == l) pack_conv_pool(src, is_p, wpool.data() + (size_t)sg * wpool_seg);   // the layer behind a pool layer
+        if (H > 0)
+            pack_highway(src, wc.data() + (size_t)l * hw_layer, bc.data() + (size_t)l * HPAD,
+                         is_p ? (uint16_t*)(wc16.data() + (size_t)l * hw_layer) : nullptr);
+    }
+    if (is_p) {
+        if ((rc = dev_upload(h, &h->d_wlp, wlp)) || (rc = dev_upload(h, &h->d_wlr, wlr))) return rc;
+        if (H > 0 && (rc = dev_upload(h, &h->d_wc16, wc16))) return rc;
+    }
+    if (is_x && (rc = dev_upload(h, &h->d_wlx, wlx))) return rc;
+    if (conv_pool && h->n_segments > 1) {
+        if ((rc = dev_upload(h, &h->d_wpool, wpool)) || (rc = dev_upload(h, &h->d_zero, std::vector<float>(CPAD, 0.f)))) return rc;
+    }
+    if ((rc = dev_upload(h, &h->d_wl, wl))) return rc;
+    if (H > 0 && ((rc = dev_upload(h, &h->d_wc, wc)) || (rc = dev_upload(h, &h->d_bc, bc)))) return rc;
+    h->d_hw = is_p ? h->d_wc16 : h->d_wc;
+    return DAN_OK;
+}
+
+// FC stack + heads (model.py:362-377,406-415)
+int upload_fc_heads(dan_handle* h) {
+    const dan_config& c = h->cfg;
+    int rc = DAN_OK;
+    const int n0 = c.fc_sizes[0], n1 = c.fc_sizes[1];
+    const Tensor* w0 = need(h, "fc.0.weight", {n0, h->F}, &rc); if (!w0) return rc;
+    const Tensor* b0 = need(h, "fc.0.bias", {n0}, &rc); if (!b0) return rc;
+    const Tensor* w1 = need(h, "fc.1.weight", {n1, n0}, &rc); if (!w1) return rc;
+    const Tensor* b1 = need(h, "fc.1.bias", {n1}, &rc); if (!b1) return rc;
+    if (c.precision == 0) {
+        if ((rc = dev_alloc(h, &h->d_w0, (size_t)n0 * h->F_stride))) return rc;
+        HIPCHK(h, hipMemset(h->d_w0, 0, (size_t)n0 * h->F_stride * sizeof(float)));
+        HIPCHK(h, hipMemcpy2D(h->d_w0, h->F_stride * sizeof(float), w0->data.data(), (size_t)h->F * sizeof(float),
+                              (size_t)h->F * sizeof(float), n0, hipMemcpyHostToDevice));
+    } else {
+        // the bf16 modes run FC1 (99.5 % of the FC stack's FLOPs) on the bf16 matrix cores with split operands: the weights as two
+        // bf16 planes, hi = bf16(w), lo = bf16(w - hi) -- the bytes of the fp32 matrix
+        const size_t plane = (size_t)n0 * h->F_stride;
+        std::vector<uint16_t> wx(2 * plane, 0);
+        for (int o = 0; o < n0; ++o)
+            for (int64_t k = 0; k < h->F; ++k) {
+                const float w = w0->data[(size_t)o * h->F + k];
+                const uint16_t hi = bf16_bits(w);
+                wx[(size_t)o * h->F_stride + k] = hi;
+                wx[plane + (size_t)o * h->F_stride + k] = bf16_bits(w - bf16_float(hi));
+            }
+        if ((rc = dev_upload(h, &h->d_w0x, wx))) return rc;
+    }
+    if ((rc = dev_alloc(h, &h->d_w1, (size_t)n1 * h->n0_stride))) return rc;
+    HIPCHK(h, hipMemset(h->d_w1, 0, (size_t)n1 * h->n0_stride * sizeof(float)));
+    HIPCHK(h, hipMemcpy2D(h->d_w1, h->n0_stride * sizeof(float), w1->data.data(), (size_t)n0 * sizeof(float),
+                          (size_t)n0 * sizeof(float), n1, hipMemcpyHostToDevice));
+    if ((rc = dev_upload(h, &h->d_b0, b0->data)) || (rc = dev_upload(h, &h->d_b1, b1->data))) return rc;
+    static const struct { const char* name; int n; } heads[] = {{"fcHidden2BinTarget", 2}, {"fcHidden2VT", 3}, {"fcHidden2AF", 1},
+                                                                 {"fcHidden2Coverage", 1}, {"fcHidden2VB", VOCAB}, {"fcHidden2VR", VOCAB}};
+    std::vector<float> wh, bh;
+    for (auto& hd : heads) {
+        const Tensor* w = need(h, std::string(hd.name) + ".weight", {hd.n, n1}, &rc); if (!w) return rc;
+        const Tensor* b = need(h, std::string(hd.name) + ".bias", {hd.n}, &rc); if (!b) return rc;
+        wh.insert(wh.end(), w->data.begin(), w->data.end());
+        bh.insert(bh.end(), b->data.begin(), b->data.end());
+    }
+    if ((rc = dev_upload(h, &h->d_wh, wh)) || (rc = dev_upload(h, &h->d_bh, bh))) return rc;
+    return DAN_OK;
+}
+
+// activations / workspaces, sized for one chunk (conv) and one macro-batch (FC)
+int alloc_workspaces(dan_handle* h) {
+    const dan_config& c = h->cfg;
+    int rc = DAN_OK;
+    const int L = c.length, R = c.reads, H = c.bottleneck, n1 = c.fc_sizes[1];
+    const size_t read_floats = (size_t)L * CPAD;
+    const size_t act_div = sizeof(float) / h->fam->elem_bytes;   // (bf16 y / h: half a float per element)
+    if ((rc = dev_alloc(h, &h->d_y, (size_t)h->chunk * R * read_floats / act_div))) return rc;
+    if (h->split && h->fam->y_copies < 2) return fail(h, DAN_ERR_STATE, "a split window needs a family with two y buffers");
+    if (h->split && (rc = dev_alloc(h, &h->d_y2, (size_t)h->chunk * R * read_floats))) return rc;
+    if ((rc = dev_alloc(h, &h->d_pool, (size_t)h->chunk * read_floats))) return rc;
+    if (!h->fold_why_not && (rc = dev_alloc(h, &h->d_fold, (size_t)(h->n_cus & ~7) * 2 * read_floats))) return rc;
+    if (h->fam->conv_pool && h->n_segments > 1) {
+        if ((rc = dev_alloc(h, &h->d_cp, (size_t)h->chunk * read_floats))) return rc;
+        if ((rc = dev_alloc(h, &h->d_cols, (size_t)h->chunk * L * 3 * CPAD))) return rc;
+    }
+    if (c.skip_empty_rows) {
+        if ((rc = dev_alloc(h, &h->d_rowsrc, (size_t)h->chunk * R))) return rc;     // int32 per pileup row
+        if ((rc = dev_alloc(h, &h->d_work, (size_t)h->chunk * R + 4))) return rc;
+        h->d_work_count = h->d_work + (size_t)h->chunk * R;
+    }
+    if (H > 0 && (rc = dev_alloc(h, &h->d_h, (size_t)c.layers * h->chunk * R * L * HPAD / act_div))) return rc;
+    if ((rc = dev_alloc(h, &h->d_feat, (size_t)h->max_batch * h->F_stride))) return rc;
+    HIPCHK(h, hipMemset(h->d_feat, 0, (size_t)h->max_batch * h->F_stride * sizeof(float)));
+    if ((rc = dev_alloc(h, &h->d_hid0, (size_t)h->max_batch * h->n0_stride)) || (rc = dev_alloc(h, &h->d_hid1, (size_t)h->max_batch * n1))) return rc;
+    HIPCHK(h, hipMemset(h->d_hid0, 0, (size_t)h->max_batch * h->n0_stride * sizeof(float)));
+    if ((rc = dev_alloc(h, &h->d_fc_ws, (size_t)2 * h->max_batch * c.fc_sizes[0]))) return rc;
+    const size_t in_site = (size_t)3 * R * L + 3 * L;
+    if ((rc = dev_alloc(h, &h->d_in, (size_t)h->max_batch * in_site))) return rc;
+    if ((rc = dev_alloc(h, &h->d_out, (size_t)h->max_batch * (2 + 3 + 3 + 1 + 22)))) return rc;
+    return DAN_OK;
 }
 
 }  // namespace
@@ -425,7 +810,7 @@ int dan_finalize(dan_t* h) {
     const dan_config& c = h->cfg;
     HIPCHK(h, hipSetDevice(c.device_id));
     int rc = DAN_OK;
-    const int L = c.length, R = c.reads, H = c.bottleneck;
+    const int L = c.length;
 
     // ---- embeddings + positional encoding (model.py:143-145,154-162)
     const Tensor* emb = need(h, "embeddings.weight", {VOCAB, EMBED}, &rc); if (!emb) return rc;
@@ -433,278 +818,8 @@ int dan_finalize(dan_t* h) {
     if ((rc = dev_upload(h, &h->d_emb, emb->data))) return rc;
     if ((rc = dev_upload(h, &h->d_pe, pe->data))) return rc;
 
-    // ---- conv stack: one fixed-stride weight block per layer (dan_kernels.h)
-    std::vector<float> wl((size_t)c.layers * LAYER_STRIDE, 0.f);
-    // precision 2: the ping-pong kernel (bf16 y / h in HBM); precision 1: the split kernel (y as two bf16 planes)
-    h->use_p = c.precision == 2;
-    h->use_x = c.precision == 1;
-    const bool conv_pool = h->use_p || h->use_x;                 // the read-mean enters the layer behind it as conv(pool)
-    std::vector<char> wlp(h->use_p ? (size_t)c.layers * WP_LAYER_BYTES : 0, 0);
-    std::vector<char> wlr(h->use_p ? (size_t)c.layers * WP_LAYER_BYTES : 0, 0);
-    std::vector<char> wlx(h->use_x ? (size_t)c.layers * WX_LAYER_BYTES : 0, 0);
-    std::vector<float> wpool_all(conv_pool ? (size_t)h->n_segments * CPAD * 3 * CPAD : 0, 0.f);
-    std::vector<float> wc16_all;
-    const size_t wc16_layer = (size_t)L * 2 * 2 * 64 * 4;    // floats: [pos][n 2][plane 2][lane 64][8 bf16]
-    if (h->use_p && H > 0) wc16_all.resize((size_t)c.layers * wc16_layer);
-    std::vector<float> wc_all, bc_all((size_t)c.layers * HPAD, 0.f);
-    const size_t wc_layer = (size_t)L * 2 * 2 * 64 * 4;      // [g = 2L][tile 2][lane 64][4]
-    if (H > 0) wc_all.resize((size_t)c.layers * wc_layer);
-    // canonical position of the reference's layer-1 input channels (model.py:517,543,558,625)
-    std::vector<int> canon;
-    for (int i = 0; i < 2 * EMBED; ++i) canon.push_back(i);
-    if (c.use_q) canon.push_back(40);
-    if (c.use_strand) canon.push_back(41);
-    if (c.use_mask) { canon.push_back(42); canon.push_back(43); canon.push_back(44); }
-    h->res_mask = 0;
-
-    for (int l = 0; l < c.layers; ++l) {
-        const int l1 = l + 1;
-        int cin, cout, dil;
-        layer_dims(c, l1, &cin, &cout, &dil);
-        float* blk = wl.data() + (size_t)l * LAYER_STRIDE;
-        const std::string p = "conv1D_layers." + std::to_string(l);
-        const Tensor* w = need(h, p + ".weight", {cout, cin, 1, 3}, &rc); if (!w) return rc;
-        const Tensor* b = need(h, p + ".bias", {cout}, &rc); if (!b) return rc;
-        const int kg = (l == 0) ? KG0 : KGC;
-        std::vector<int> inv(kg * 16, -1);                   // canonical channel -> reference channel
-        for (int i = 0; i < cin; ++i) inv[l == 0 ? canon[i] : i] = i;
-        auto Wf = [&](int o, int cc, int t) -> float {
-            if (o >= cout || cc >= (int)inv.size() || inv[cc] < 0) return 0.f;
-            return w->data[((size_t)o * cin + inv[cc]) * 3 + t];
-        };
-        std::vector<float> packed = pack_frag(3, kg, KGC, Wf);
-        std::copy(packed.begin(), packed.end(), blk + W_OFF);
-        if (l == 0 && c.precision == 0) {
-            // layer 1 by table (dan_kernels.h L0_*): conv1 is linear in the terms its input column is a sum of; sums in double
-            std::vector<float> tab(l0_tab_floats(L), 0.f);
-            for (int t = 0; t < 3; ++t)
-                for (int o = 0; o < CPAD; ++o) {
-                    for (int ta = 0; ta < VOCAB; ++ta)
-                        for (int tb = 0; tb < VOCAB; ++tb) {
-                            double v = 0.0;
-                            for (int e = 0; e < EMBED; ++e)
-                                v += (double)Wf(o, e, t) * emb->data[(size_t)ta * EMBED + e] + (double)Wf(o, EMBED + e, t) * emb->data[(size_t)tb * EMBED + e];
-                            tab[L0_TJ_OFF + ((size_t)t * L0_NTJ + ta * 10 + tb) * CPAD + o] = (float)v;
-                        }
-                    for (int k = 0; k < 5; ++k) tab[L0_WSC_OFF + ((size_t)k * 3 + t) * CPAD + o] = Wf(o, 2 * EMBED + k, t);
-                }
-            // the positional term of tap t at column w: sum_e (W[o][e][t] + W[o][20 + e][t]) pe[w][e]; PE[variant][w] = the taps whose
-            // column w + t - 1 exists for a unit that has / lacks a left / right neighbour at w (and lies inside the window anyway)
-            std::vector<double> pet((size_t)3 * L * CPAD);
-            for (int t = 0; t < 3; ++t)
-                for (int wcol = 0; wcol < L; ++wcol)
-                    for (int o = 0; o < CPAD; ++o) {
-                        double v = 0.0;
-                        for (int e = 0; e < EMBED; ++e) v += ((double)Wf(o, e, t) + (double)Wf(o, EMBED + e, t)) * pe->data[(size_t)wcol * EMBED + e];
-                        pet[((size_t)t * L + wcol) * CPAD + o] = v;
-                    }
-            for (int var = 0; var < 3; ++var)
-                for (int wcol = 0; wcol < L; ++wcol)
-                    for (int o = 0; o < CPAD; ++o) {
-                        double v = pet[((size_t)1 * L + wcol) * CPAD + o];
-                        if (var != 1 && wcol - 1 >= 0) v += pet[((size_t)0 * L + wcol - 1) * CPAD + o];
-                        if (var != 2 && wcol + 1 < L) v += pet[((size_t)2 * L + wcol + 1) * CPAD + o];
-                        tab[L0_PE_OFF + ((size_t)var * L + wcol) * CPAD + o] = (float)v;
-                    }
-            if ((rc = dev_upload(h, &h->d_l0tab, tab))) return rc;
-        }
-        if (l > 0) {
-            // Winograd F(2,3) weight transform U = [g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2], formed in double
-            auto Wu = [&](int o, int cc, int k) -> float {
-                const double g0 = Wf(o, cc, 0), g1 = Wf(o, cc, 1), g2 = Wf(o, cc, 2);
-                return k == 0 ? (float)g0 : k == 1 ? (float)((g0 + g1 + g2) * 0.5) : k == 2 ? (float)((g0 - g1 + g2) * 0.5) : (float)g2;
-            };
-            std::vector<float> pw = pack_frag(4, KGC, KGC, Wu);
-            std::copy(pw.begin(), pw.end(), blk + WW_OFF);
-        }
-        char* blkp = h->use_p ? wlp.data() + (size_t)l * WP_LAYER_BYTES : nullptr;
-        if (blkp) pack_fragp((uint16_t*)(blkp + WP_CONV_OFF), 3, l == 0 ? P_KS0 : P_KSC, 4, Wf);
-        char* blkr = h->use_p ? wlr.data() + (size_t)l * WP_LAYER_BYTES : nullptr;
-        if (blkr) pack_fragr((uint16_t*)(blkr + WP_CONV_OFF), 3, l == 0 ? 2 : 4, 8, Wf);
-        char* blkx = h->use_x ? wlx.data() + (size_t)l * WX_LAYER_BYTES : nullptr;
-        if (blkx) pack_fragx((uint16_t*)(blkx + WX_CONV_OFF), 3, l == 0 ? X_KS0 : X_KS, 8, Wf);
-        if (conv_pool && l > 0)
-            for (int sg = 1; sg < h->n_segments; ++sg)
-                if (h->seg_begin[sg] == l) {                     // the layer behind a pool layer: its weights, [o][t * 128 + c] -- bf16-rounded for the
-                    float* wp = wpool_all.data() + (size_t)sg * CPAD * 3 * CPAD;   // plain-bf16 kernel (its oracle's "storage" mode), fp32 for bf16x3
-                    for (int o = 0; o < CPAD; ++o)
-                        for (int t = 0; t < 3; ++t)
-                            for (int cc = 0; cc < CPAD; ++cc)
-                                wp[((size_t)o * 3 + t) * CPAD + cc] = h->use_p ? bf16_float(bf16_bits(Wf(o, cc, t))) : Wf(o, cc, t);
-                }
-        float* cst = blk + CST_OFF;
-        for (int o = 0; o < cout; ++o) { cst[CST_BIAS + o] = b->data[o]; cst[CST_SCALE + o] = 1.f; }
-        if (c.use_bn) {                                      // eval-mode BN after the ReLU, eps 1e-5 (model.py:750-751)
-            const std::string q = "bn1D_layers." + std::to_string(l);
-            const Tensor* g = need(h, q + ".weight", {cout}, &rc); if (!g) return rc;
-            const Tensor* be = need(h, q + ".bias", {cout}, &rc); if (!be) return rc;
-            const Tensor* mu = need(h, q + ".running_mean", {cout}, &rc); if (!mu) return rc;
-            const Tensor* var = need(h, q + ".running_var", {cout}, &rc); if (!var) return rc;
-            for (int o = 0; o < cout; ++o) {
-                const double sc = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
-                cst[CST_SCALE + o] = (float)sc;
-                cst[CST_SHIFT + o] = (float)((double)be->data[o] - (double)mu->data[o] * sc);
-            }
-        }
-        if (is_residual(c, l1)) {
-            const std::string q = "residual_conv_layers." + std::to_string(l1 - c.residual_start);   // model.py:760
-            const Tensor* wr = need(h, q + ".weight", {cout, cout, 1, 1}, &rc); if (!wr) return rc;
-            const Tensor* br = need(h, q + ".bias", {cout}, &rc); if (!br) return rc;
-            auto Wr = [&](int o, int cc, int) -> float { return (o < cout && cc < cout) ? wr->data[(size_t)o * cout + cc] : 0.f; };
-            std::vector<float> pr = pack_frag(1, KGC, KGC, Wr);
-            std::copy(pr.begin(), pr.end(), blk + WRES_OFF);
-            if (blkp) pack_fragp((uint16_t*)(blkp + WP_RES_OFF), 1, P_KSC, 4, Wr);
-            if (blkr) pack_fragr((uint16_t*)(blkr + WP_RES_OFF), 1, 4, 8, Wr);
-            if (blkx) pack_fragx((uint16_t*)(blkx + WX_RES_OFF), 1, X_KS, 8, Wr);
-            for (int o = 0; o < cout; ++o) cst[CST_BRES + o] = br->data[o];
-            h->res_mask |= 1u << l;
-        }
-        if (H > 0) {
-            const std::string q = "conv1D_bottleneck_layers." + std::to_string(l);
-            const Tensor* wb = need(h, q + ".weight", {H, cout, 1, 1}, &rc); if (!wb) return rc;
-            const Tensor* bb = need(h, q + ".bias", {H}, &rc); if (!bb) return rc;
-            auto Wb = [&](int o, int cc, int) -> float { return (o < H && cc < cout) ? wb->data[(size_t)o * cout + cc] : 0.f; };
-            std::vector<float> pb = pack_frag(1, KGC, 2, Wb);
-            std::copy(pb.begin(), pb.end(), blk + WBOT_OFF);
-            if (blkp) pack_fragp((uint16_t*)(blkp + WP_BOT_OFF), 1, P_KSC, 1, Wb);
-            if (blkr) pack_fragr((uint16_t*)(blkr + WP_BOT_OFF), 1, 4, 2, Wb);
-            if (blkx) pack_fragx((uint16_t*)(blkx + WX_BOT_OFF), 1, X_KS, 2, Wb);
-            for (int o = 0; o < H; ++o) cst[CST_BBOT + o] = bb->data[o];
-            const std::string z = "conv1D_compression_layers." + std::to_string(l);
-            const Tensor* wcm = need(h, z + ".weight", {H, H, 1, L}, &rc); if (!wcm) return rc;
-            const Tensor* bcm = need(h, z + ".bias", {H}, &rc); if (!bcm) return rc;
-            // k = p*32 + c, k-group g = 2p + (c >> 4):  packed[g][n][lane][s] = Wc[o][c][p]
-            float* dst = wc_all.data() + (size_t)l * wc_layer;
-            size_t i = 0;
-            for (int g = 0; g < 2 * L; ++g)
-                for (int n = 0; n < 2; ++n)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int s = 0; s < 4; ++s) {
-                            const int o = 16 * n + (lane & 15), cc = 16 * (g & 1) + 4 * (lane >> 4) + s, pp = g >> 1;
-                            dst[i++] = (o < H && cc < H) ? wcm->data[((size_t)o * H + cc) * L + pp] : 0.f;
-                        }
-            for (int o = 0; o < H; ++o) bc_all[(size_t)l * HPAD + o] = bcm->data[o];
-            if (h->use_p) {
-                uint16_t* d16 = (uint16_t*)(wc16_all.data() + (size_t)l * wc16_layer);
-                for (int pp = 0; pp < L; ++pp)
-                    for (int n = 0; n < 2; ++n)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int s8 = 0; s8 < 8; ++s8) {
-                                const int o = 16 * n + (lane & 15), cc = 8 * (lane >> 4) + s8;
-                                const float w = (o < H && cc < H) ? wcm->data[((size_t)o * H + cc) * L + pp] : 0.f;
-                                const uint16_t hi = bf16_bits(w);
-                                const size_t base = (((size_t)pp * 2 + n) * 2) * 64 * 8;
-                                d16[base + (size_t)lane * 8 + s8] = hi;                                   // plane 0
-                                d16[base + 64 * 8 + (size_t)lane * 8 + s8] = bf16_bits(w - bf16_float(hi));   // plane 1
-                            }
-            }
-        }
-    }
-    if (h->use_p) {
-        for (int l = 0; l < c.layers; ++l)
-        {
-            memcpy(wlp.data() + (size_t)l * WP_LAYER_BYTES + WP_CST_OFF, wl.data() + (size_t)l * LAYER_STRIDE + CST_OFF,
-                   CST_FLOATS * sizeof(float));
-            memcpy(wlr.data() + (size_t)l * WP_LAYER_BYTES + WP_CST_OFF, wl.data() + (size_t)l * LAYER_STRIDE + CST_OFF,
-                   CST_FLOATS * sizeof(float));
-        }
-        if ((rc = dev_upload(h, &h->d_wlp, wlp))) return rc;
-        if ((rc = dev_upload(h, &h->d_wlr, wlr))) return rc;
-        if (H > 0 && (rc = dev_upload(h, &h->d_wc16, wc16_all))) return rc;
-    }
-    if (h->use_x) {
-        for (int l = 0; l < c.layers; ++l) {
-            float* cx = (float*)(wlx.data() + (size_t)l * WX_LAYER_BYTES + WX_CST_OFF);
-            memcpy(cx, wl.data() + (size_t)l * LAYER_STRIDE + CST_OFF, CST_FLOATS * sizeof(float));
-            // this family's epilogue computes relu(acc + b) * sc + sh as max(acc, -b) * sc + (sh + b * sc) (dan_kernels_bf16x.hip):
-            // the bias slot holds -b, the shift slot sh + b * sc (formed in double)
-            for (int ch = 0; ch < CPAD; ++ch) {
-                const double b = cx[CST_BIAS + ch];
-                cx[CST_SHIFT + ch] = (float)((double)cx[CST_SHIFT + ch] + b * (double)cx[CST_SCALE + ch]);
-                cx[CST_BIAS + ch] = (float)-b;
-            }
-        }
-        if ((rc = dev_upload(h, &h->d_wlx, wlx))) return rc;
-    }
-    if (conv_pool && h->n_segments > 1) {
-        if ((rc = dev_upload(h, &h->d_wpool, wpool_all))) return rc;
-        std::vector<float> zeros(CPAD, 0.f);
-        if ((rc = dev_upload(h, &h->d_zero, zeros))) return rc;
-    }
-    if ((rc = dev_upload(h, &h->d_wl, wl))) return rc;
-    if (H > 0) {
-        if ((rc = dev_upload(h, &h->d_wc, wc_all)) || (rc = dev_upload(h, &h->d_bc, bc_all))) return rc;
-    }
-
-    // ---- FC stack + heads (model.py:362-377,406-415)
-    const int n0 = c.fc_sizes[0], n1 = c.fc_sizes[1];
-    const Tensor* w0 = need(h, "fc.0.weight", {n0, h->F}, &rc); if (!w0) return rc;
-    const Tensor* b0 = need(h, "fc.0.bias", {n0}, &rc); if (!b0) return rc;
-    const Tensor* w1 = need(h, "fc.1.weight", {n1, n0}, &rc); if (!w1) return rc;
-    const Tensor* b1 = need(h, "fc.1.bias", {n1}, &rc); if (!b1) return rc;
-    if (c.precision == 0) {
-        if ((rc = dev_alloc(h, &h->d_w0, (size_t)n0 * h->F_stride))) return rc;
-        HIPCHK(h, hipMemset(h->d_w0, 0, (size_t)n0 * h->F_stride * sizeof(float)));
-        HIPCHK(h, hipMemcpy2D(h->d_w0, h->F_stride * sizeof(float), w0->data.data(), (size_t)h->F * sizeof(float),
-                              (size_t)h->F * sizeof(float), n0, hipMemcpyHostToDevice));
-    } else {
-        // the bf16 modes run FC1 (99.5 % of the FC stack's FLOPs) on the bf16 matrix cores with split operands: the weights as two
-        // bf16 planes, hi = bf16(w), lo = bf16(w - hi) -- the bytes of the fp32 matrix
-        const size_t plane = (size_t)n0 * h->F_stride;
-        std::vector<uint16_t> wx(2 * plane, 0);
-        for (int o = 0; o < n0; ++o)
-            for (int64_t k = 0; k < h->F; ++k) {
-                const float w = w0->data[(size_t)o * h->F + k];
-                const uint16_t hi = bf16_bits(w);
-                wx[(size_t)o * h->F_stride + k] = hi;
-                wx[plane + (size_t)o * h->F_stride + k] = bf16_bits(w - bf16_float(hi));
-            }
-        if ((rc = dev_upload(h, &h->d_w0x, wx))) return rc;
-    }
-    if ((rc = dev_alloc(h, &h->d_w1, (size_t)n1 * h->n0_stride))) return rc;
-    HIPCHK(h, hipMemset(h->d_w1, 0, (size_t)n1 * h->n0_stride * sizeof(float)));
-    HIPCHK(h, hipMemcpy2D(h->d_w1, h->n0_stride * sizeof(float), w1->data.data(), (size_t)n0 * sizeof(float),
-                          (size_t)n0 * sizeof(float), n1, hipMemcpyHostToDevice));
-    if ((rc = dev_upload(h, &h->d_b0, b0->data)) || (rc = dev_upload(h, &h->d_b1, b1->data))) return rc;
-    static const struct { const char* name; int n; } heads[] = {{"fcHidden2BinTarget", 2}, {"fcHidden2VT", 3}, {"fcHidden2AF", 1},
-                                                                 {"fcHidden2Coverage", 1}, {"fcHidden2VB", VOCAB}, {"fcHidden2VR", VOCAB}};
-    std::vector<float> wh, bh;
-    for (auto& hd : heads) {
-        const Tensor* w = need(h, std::string(hd.name) + ".weight", {hd.n, n1}, &rc); if (!w) return rc;
-        const Tensor* b = need(h, std::string(hd.name) + ".bias", {hd.n}, &rc); if (!b) return rc;
-        wh.insert(wh.end(), w->data.begin(), w->data.end());
-        bh.insert(bh.end(), b->data.begin(), b->data.end());
-    }
-    if ((rc = dev_upload(h, &h->d_wh, wh)) || (rc = dev_upload(h, &h->d_bh, bh))) return rc;
-
-    // ---- activations / workspaces, sized for one chunk (conv) and one macro-batch (FC)
-    const size_t read_floats = (size_t)L * CPAD;
-    const size_t act_div = h->use_p ? 2 : 1;                 // (bf16 y / h: half a float per element)
-    if ((rc = dev_alloc(h, &h->d_y, (size_t)h->chunk * R * read_floats / act_div))) return rc;
-    if (h->split && (rc = dev_alloc(h, &h->d_y2, (size_t)h->chunk * R * read_floats))) return rc;
-    if ((rc = dev_alloc(h, &h->d_pool, (size_t)h->chunk * read_floats))) return rc;
-    if (!h->fold_why_not && (rc = dev_alloc(h, &h->d_fold, (size_t)(h->n_cus & ~7) * 2 * read_floats))) return rc;
-    if (conv_pool && h->n_segments > 1) {
-        if ((rc = dev_alloc(h, &h->d_cp, (size_t)h->chunk * read_floats))) return rc;
-        if ((rc = dev_alloc(h, &h->d_cols, (size_t)h->chunk * L * 3 * CPAD))) return rc;
-    }
-    if (c.skip_empty_rows) {
-        float* tmp = nullptr;
-        if ((rc = dev_alloc(h, &tmp, (size_t)h->chunk * R))) return rc;     // int32 per pileup row
-        h->d_rowsrc = (int*)tmp;
-        if ((rc = dev_alloc(h, &tmp, (size_t)h->chunk * R + 4))) return rc;
-        h->d_work = (int*)tmp;
-        h->d_work_count = h->d_work + (size_t)h->chunk * R;
-    }
-    if (H > 0 && (rc = dev_alloc(h, &h->d_h, (size_t)c.layers * h->chunk * R * L * HPAD / act_div))) return rc;
-    if ((rc = dev_alloc(h, &h->d_feat, (size_t)h->max_batch * h->F_stride))) return rc;
-    HIPCHK(h, hipMemset(h->d_feat, 0, (size_t)h->max_batch * h->F_stride * sizeof(float)));
-    if ((rc = dev_alloc(h, &h->d_hid0, (size_t)h->max_batch * h->n0_stride)) || (rc = dev_alloc(h, &h->d_hid1, (size_t)h->max_batch * n1))) return rc;
-    HIPCHK(h, hipMemset(h->d_hid0, 0, (size_t)h->max_batch * h->n0_stride * sizeof(float)));
-    if ((rc = dev_alloc(h, &h->d_fc_ws, (size_t)2 * h->max_batch * h->cfg.fc_sizes[0]))) return rc;
-    const size_t in_site = (size_t)3 * R * L + 3 * L;
-    if ((rc = dev_alloc(h, &h->d_in, (size_t)h->max_batch * in_site))) return rc;
-    if ((rc = dev_alloc(h, &h->d_out, (size_t)h->max_batch * (2 + 3 + 3 + 1 + 22)))) return rc;
+    h->fam = &FAMILIES[c.precision];
+    if ((rc = pack_conv_stack(h, *emb, *pe)) || (rc = upload_fc_heads(h)) || (rc = alloc_workspaces(h))) return rc;
     HIPCHK(h, hipDeviceSynchronize());
     h->tensors.clear();
     h->finalized = true;
@@ -767,6 +882,7 @@ static int forward_device_impl(dan_t* h, const uint8_t* reads, const uint8_t* qu
     if (n_sites == 0) return DAN_OK;
     if (!reads || !qual || !strand || !ref || !ref_mask || !var_mask) return fail(h, DAN_ERR_INVALID_ARG, "null input plane");
     const dan_config& c = h->cfg;
+    const Family& fam = *h->fam;
     HIPCHK(h, hipSetDevice(c.device_id));
     hipStream_t s = as_stream(stream);
     const int L = c.length, R = c.reads, H = c.bottleneck;
@@ -792,74 +908,31 @@ static int forward_device_impl(dan_t* h, const uint8_t* reads, const uint8_t* qu
             float* const feat = h->d_feat + (size_t)c0 * h->F_stride;
             float* y_seg = h->d_y;                           // where the segment just launched left its output
             for (int sg = 0; sg < h->n_segments; ++sg) {
-                SegmentArgs a{};
-                a.wl = h->d_wl;
-                a.l_begin = h->seg_begin[sg]; a.l_end = h->seg_end[sg];
-                a.n_layers = c.layers; a.dil_mid = c.dil_mid; a.dil_final = c.dil_final;
-                a.res_mask = h->res_mask; a.has_hw = H > 0;
-                a.R = R; a.L = L;
-                a.reads = reads + g0 * rl; a.qual = qual + g0 * rl; a.strand = strand + g0 * rl;
-                a.ref = ref + g0 * L; a.ref_mask = ref_mask + g0 * L; a.var_mask = var_mask + g0 * L;
-                a.emb = h->d_emb; a.pe = h->d_pe;
-                // one unit per read and y in place -- or, above MPOS columns at precision 0, two units per read and y alternating
-                // between two buffers (a unit reads the other unit's columns of the input while that one stores its output)
-                float* const y_in = y_seg;                   // the previous segment's output
+                SegmentCall q{};
+                q.sg = sg; q.ns = ns;
+                q.reads = reads + g0 * rl; q.qual = qual + g0 * rl; q.strand = strand + g0 * rl;
+                q.ref = ref + g0 * L; q.ref_mask = ref_mask + g0 * L; q.var_mask = var_mask + g0 * L;
+                q.y_in = y_seg;                              // the previous segment's output
                 if (h->split) y_seg = (y_seg == h->d_y) ? h->d_y2 : h->d_y;
-                a.y = y_in; a.y_out = y_seg;
-                if (c.precision != 2 && !plan_units(a, L, segment_halo(c, a.l_begin, a.l_end)))
-                    return fail(h, DAN_ERR_STATE, "unit plan failed for segment %d", sg);
-                a.pool = sg > 0 ? h->d_pool : nullptr;
-                a.h = h->d_h; a.h_layer_stride = h_layer_stride;
-                const bool tap_here = h->tap_layer >= 0 &&
-                                      ((h->tap_layer == 0 && sg == 0) || (h->tap_layer > a.l_begin && h->tap_layer <= a.l_end));
-                a.tap = tap_here ? h->d_tap : nullptr;
-                a.tap_layer = h->tap_layer;
-                a.wino = h->wino;
-                a.l0_tab = h->d_l0tab;
-                a.work = h->d_work; a.work_count = h->d_rowsrc ? h->d_work_count : nullptr;
-                if (fold) {
-                    a.fold = 1; a.fold_scratch = h->d_fold;
-                    if (sg + 1 < h->n_segments) a.fold_pool = h->d_pool;
-                    else { a.fold_feat = feat; a.fold_feat_stride = h->F_stride; a.fold_C = c.c_final; }
-                }
+                q.y_out = y_seg;
+                const bool tap_here = h->tap_layer >= 0 && ((h->tap_layer == 0 && sg == 0) ||
+                                                            (h->tap_layer > h->seg_begin[sg] && h->tap_layer <= h->seg_end[sg]));
+                q.tap = tap_here ? h->d_tap : nullptr;
+                q.fold = fold; q.feat = feat;
                 EventPair ev{};
                 int rc = prof_begin(h, "conv_segment", s, &ev); if (rc) return rc;
-                if (c.precision == 0) {
-                    launch_segment(a, ns, h->n_cus, s);
-                } else if (h->use_x) {
-                    SegmentXArgs b{};
-                    b.wl = h->d_wlx; b.l_begin = a.l_begin; b.l_end = a.l_end; b.n_layers = a.n_layers;
-                    b.dil_mid = a.dil_mid; b.dil_final = a.dil_final; b.res_mask = a.res_mask; b.has_hw = a.has_hw;
-                    b.R = a.R; b.L = a.L; b.reads = a.reads; b.qual = a.qual; b.strand = a.strand; b.ref = a.ref;
-                    b.ref_mask = a.ref_mask; b.var_mask = a.var_mask; b.emb = a.emb; b.pe = a.pe;
-                    b.y = (uint16_t*)a.y; b.y_out = (uint16_t*)a.y_out; b.pool = sg > 0 ? h->d_cp : nullptr; b.h = h->d_h; b.h_layer_stride = a.h_layer_stride;
-                    b.units = a.units; b.Lw = a.Lw;               // (plan_units above: b.L = the unit length)
-                    for (int u = 0; u < 2; ++u) { b.u_off[u] = a.u_off[u]; b.u_len[u] = a.u_len[u]; b.own_lo[u] = a.own_lo[u]; b.own_hi[u] = a.own_hi[u]; }
-                    b.tap = a.tap; b.tap_layer = a.tap_layer; b.work = a.work; b.work_count = a.work_count;
-                    b.stagger = -1;                              // (the launcher's own start offsets)
-                    launch_segmentx(b, ns, h->n_cus, s);
-                } else if (h->use_p) {
-                    SegmentPArgs b{};
-                    b.wl = h->d_wlp; b.wlr = h->d_wlr; b.form = c.bf16_form; b.l_begin = a.l_begin; b.l_end = a.l_end; b.n_layers = a.n_layers;
-                    b.dil_mid = a.dil_mid; b.dil_final = a.dil_final; b.res_mask = a.res_mask; b.has_hw = a.has_hw;
-                    b.R = a.R; b.L = a.L; b.reads = a.reads; b.qual = a.qual; b.strand = a.strand; b.ref = a.ref;
-                    b.ref_mask = a.ref_mask; b.var_mask = a.var_mask; b.emb = a.emb; b.pe = a.pe;
-                    b.y = (uint16_t*)h->d_y; b.pool = sg > 0 ? h->d_cp : nullptr; b.h = (uint16_t*)h->d_h; b.h_layer_stride = a.h_layer_stride;
-                    b.tap = a.tap; b.tap_layer = a.tap_layer; b.work = a.work; b.work_count = a.work_count;
-                    launch_segmentp(b, ns, h->n_cus, s);
-                }
+                rc = fam.segment(h, q, s); if (rc) return rc;
                 rc = prof_end(h, "conv_segment", s, &ev); if (rc) return rc;
                 if (fold) {
                     HIPCHK(h, hipGetLastError());
                 } else if (sg + 1 < h->n_segments) {
                     rc = prof_begin(h, "pool", s, &ev); if (rc) return rc;
-                    if (h->use_p || h->use_x) {
-                        if (h->use_x) launch_read_meanx((const uint16_t*)y_seg, h->d_pool, ns, R, L, h->d_rowsrc, s);
-                        else launch_read_mean16((const uint16_t*)h->d_y, h->d_pool, ns, R, L, h->d_rowsrc, s);
+                    fam.read_mean(fam.tails_follow_y ? y_seg : h->d_y, h->d_pool, ns, R, L, h->d_rowsrc, s);
+                    if (fam.conv_pool) {
                         const int ln = h->seg_begin[sg + 1];                      // 0-based layer behind the pool: its dilation
                         launch_conv_pool(h->d_pool, h->d_wpool + (size_t)(sg + 1) * CPAD * 3 * CPAD, h->d_zero, h->d_cols, h->d_cp, ns, L,
                                          ln + 1 < c.layers ? c.dil_mid : c.dil_final, s);
-                    } else launch_read_mean(y_seg, h->d_pool, ns, R, L, h->d_rowsrc, s);
+                    }
                     rc = prof_end(h, "pool", s, &ev); if (rc) return rc;
                     HIPCHK(h, hipGetLastError());            // a refused launch must not let garbage flow on to the FC
                 }
@@ -868,20 +941,14 @@ static int forward_device_impl(dan_t* h, const uint8_t* reads, const uint8_t* qu
             int rc = DAN_OK;
             if (!fold) {                                     // (in-segment form: the last segment has written the pooled blocks)
                 rc = prof_begin(h, "pool", s, &ev); if (rc) return rc;
-                if (h->use_x) launch_final_poolx((const uint16_t*)y_seg, feat, h->F_stride, ns, R, L, c.c_final, h->d_rowsrc, s);
-                else if (h->use_p) launch_final_pool16((const uint16_t*)h->d_y, feat, h->F_stride, ns, R, L, c.c_final, h->d_rowsrc, s);
-                else launch_final_pool(y_seg, feat, h->F_stride, ns, R, L, c.c_final, h->d_rowsrc, s);
+                fam.final_pool(fam.tails_follow_y ? y_seg : h->d_y, feat, h->F_stride, ns, R, L, c.c_final, h->d_rowsrc, s);
                 rc = prof_end(h, "pool", s, &ev); if (rc) return rc;
                 HIPCHK(h, hipGetLastError());
             }
             if (H > 0) {
                 rc = prof_begin(h, "highway", s, &ev); if (rc) return rc;
-                if (h->use_p)
-                    launch_highway16((const uint16_t*)h->d_h, h_layer_stride, h->d_wc16, (long long)L * 2 * 2 * 64 * 4, h->d_bc, feat,
-                                     h->F_stride, 2 * c.c_final * L, ns, R, L, H, c.layers, h->d_rowsrc, s);
-                else
-                    launch_highway(h->d_h, h_layer_stride, h->d_wc, (long long)L * 2 * 2 * 64 * 4, h->d_bc, feat, h->F_stride,
-                                   2 * c.c_final * L, ns, R, L, H, c.layers, h->d_rowsrc, s);
+                fam.highway(h->d_h, h_layer_stride, h->d_hw, (long long)L * 2 * 2 * 64 * 4, h->d_bc, feat, h->F_stride,
+                            2 * c.c_final * L, ns, R, L, H, c.layers, h->d_rowsrc, s);
                 rc = prof_end(h, "highway", s, &ev); if (rc) return rc;
             }
             h->last_chunk_sites = ns;
@@ -1116,8 +1183,8 @@ int64_t dan_query(const dan_t* h, const char* what) {
     if (w == "cpad") return CPAD;
     if (w == "tap_sites") return h->last_chunk_sites;
     if (w == "segments") return h->n_segments;
-    if (w == "bf16_pingpong") return h->use_p ? 1 : 0;
-    if (w == "bf16x3_split_kernel") return h->use_x ? 1 : 0;
+    if (w == "bf16_pingpong") return h->fam == &FAMILIES[2] ? 1 : 0;            // (0 before dan_finalize, as ever)
+    if (w == "bf16x3_split_kernel") return h->fam == &FAMILIES[1] ? 1 : 0;
     if (w == "hidden0_stride") return h->n0_stride;
     if (w == "pool_form") return h->last_pool_form;
     return fail(h, DAN_ERR_INVALID_ARG, "dan_query: unknown key '%s'", what);
@@ -1148,9 +1215,10 @@ int64_t dan_read_buffer(dan_t* h, const char* name, float* dst, int64_t capacity
         n = std::min<int64_t>(per_layer * c.layers, capacity) / per_layer * per_layer;
         HIPCHK(h, hipSetDevice(c.device_id));
         HIPCHK(h, hipDeviceSynchronize());
-        std::vector<uint16_t> tmp(h->use_p ? (size_t)per_layer : 0);
+        const bool h_bf16 = h->fam->elem_bytes == 2;
+        std::vector<uint16_t> tmp(h_bf16 ? (size_t)per_layer : 0);
         for (int64_t l = 0; l * per_layer < n; ++l) {
-            if (h->use_p) {
+            if (h_bf16) {
                 HIPCHK(h, hipMemcpy(tmp.data(), (const uint16_t*)h->d_h + l * stride, (size_t)per_layer * 2, hipMemcpyDeviceToHost));
                 for (int64_t i = 0; i < per_layer; ++i) dst[l * per_layer + i] = bf16_float(tmp[(size_t)i]);
             } else {

@@ -16,6 +16,7 @@
 // :728-778 (layer loop), :824-859 (pool + highway concat), :917-958 (FC + heads),
 // dl4vc/trainer.py:609-623 (softmax scores).
 #include "dan_device.h"
+#include "dan_reduce.h"
 
 namespace dan {
 
@@ -857,6 +858,16 @@ int segment_fold_workgroups(int n_sites, int max_wgs) {
     return w < need ? w : need;
 }
 
+// a one-unit read in the fold, persistent or row form: six Winograd tiles per lane + the direct remainder tile, six, seven, or direct
+template <bool PERSIST, bool FOLD>
+static void launch_one_unit(const SegmentArgs& a, bool six, bool rem, dim3 grid, hipStream_t s) {
+    const dim3 blk(SEG_THREADS);
+    if (a.wino && rem) hipLaunchKernelGGL((segment_kernel<true, PERSIST, false, MW_SHORT, FOLD, true>), grid, blk, 0, s, a);
+    else if (a.wino && six) hipLaunchKernelGGL((segment_kernel<true, PERSIST, false, MW_SHORT, FOLD>), grid, blk, 0, s, a);
+    else if (a.wino) hipLaunchKernelGGL((segment_kernel<true, PERSIST, false, MW, FOLD>), grid, blk, 0, s, a);
+    else hipLaunchKernelGGL((segment_kernel<false, PERSIST, false, MW, FOLD>), grid, blk, 0, s, a);
+}
+
 void launch_segment(const SegmentArgs& a0, int n_sites, int max_wgs, hipStream_t s) {
     SegmentArgs a = a0;
     a.n_rows = n_sites * a.R;
@@ -870,11 +881,8 @@ void launch_segment(const SegmentArgs& a0, int n_sites, int max_wgs, hipStream_t
     if (a.fold) {                                           // (callers ask for it only where it applies: dan_capi.cpp)
         a.n_sites = n_sites;
         a.xcd_sites = (n_sites + 7) / 8;                    // the same XCD slices of whole sites as the row forms
-        const dim3 grid((unsigned)segment_fold_workgroups(n_sites, max_wgs)), blk(SEG_THREADS);
-        if (a.wino && rem) hipLaunchKernelGGL((segment_kernel<true, true, false, MW_SHORT, true, true>), grid, blk, 0, s, a);
-        else if (a.wino && six) hipLaunchKernelGGL((segment_kernel<true, true, false, MW_SHORT, true>), grid, blk, 0, s, a);
-        else if (a.wino) hipLaunchKernelGGL((segment_kernel<true, true, false, MW, true>), grid, blk, 0, s, a);
-        else hipLaunchKernelGGL((segment_kernel<false, true, false, MW, true>), grid, blk, 0, s, a);
+        const dim3 grid((unsigned)segment_fold_workgroups(n_sites, max_wgs));
+        launch_one_unit<true, true>(a, six, rem, grid, s);
         return;
     }
     const bool persist = a.work_count != nullptr && max_wgs >= 8 && max_wgs < a.n_rows * units;
@@ -894,15 +902,9 @@ void launch_segment(const SegmentArgs& a0, int n_sites, int max_wgs, hipStream_t
             else hipLaunchKernelGGL((segment_kernel<false, false, true>), grid, blk, 0, s, a);
         }
     } else if (persist) {
-        if (a.wino && rem) hipLaunchKernelGGL((segment_kernel<true, true, false, MW_SHORT, false, true>), grid, blk, 0, s, a);
-        else if (a.wino && six) hipLaunchKernelGGL((segment_kernel<true, true, false, MW_SHORT>), grid, blk, 0, s, a);
-        else if (a.wino) hipLaunchKernelGGL((segment_kernel<true, true, false>), grid, blk, 0, s, a);
-        else hipLaunchKernelGGL((segment_kernel<false, true, false>), grid, blk, 0, s, a);
+        launch_one_unit<true, false>(a, six, rem, grid, s);
     } else {
-        if (a.wino && rem) hipLaunchKernelGGL((segment_kernel<true, false, false, MW_SHORT, false, true>), grid, blk, 0, s, a);
-        else if (a.wino && six) hipLaunchKernelGGL((segment_kernel<true, false, false, MW_SHORT>), grid, blk, 0, s, a);
-        else if (a.wino) hipLaunchKernelGGL((segment_kernel<true, false, false>), grid, blk, 0, s, a);
-        else hipLaunchKernelGGL((segment_kernel<false, false, false>), grid, blk, 0, s, a);
+        launch_one_unit<false, false>(a, six, rem, grid, s);
     }
 }
 
@@ -966,78 +968,17 @@ void launch_row_map(const uint8_t* reads, const uint8_t* qual, const uint8_t* st
     hipLaunchKernelGGL(work_list_kernel, dim3(1), dim3(1024), 0, s, row_src, work, count, n_sites, R);
 }
 
-__global__ __launch_bounds__(256) void read_mean_kernel(const v4f* __restrict__ y, v4f* __restrict__ pool, int R, int L,
-                                                        const int* __restrict__ row_src) {
-    const int n4 = L * (CPAD / 4);
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    const int site = blockIdx.y;
-    v4f sum = splat(0.f);
-    if (row_src) {                                          // same rows, same order: skipped rows are read through the map
-        const int* rs = row_src + (size_t)site * R;
-#pragma unroll 8
-        for (int r = 0; r < R; ++r) sum += y[(size_t)rs[r] * n4 + i];
-    } else {
-        const v4f* src = y + (size_t)site * R * n4 + i;
-#pragma unroll 8
-        for (int r = 0; r < R; ++r) sum += src[(size_t)r * n4];
-    }
-    pool[(size_t)site * n4 + i] = sum / splat((float)R);
-}
+// the read mean and the final pool of fp32 y (dan_reduce.h)
+template __global__ void read_mean_kernel<RowsFp32>(const v4f*, v4f*, int, int, const int*);
+template __global__ void final_pool_kernel<RowsFp32>(const v4f*, float*, long long, int, int, int, const int*);
 
 void launch_read_mean(const float* y, float* pool, int n_sites, int R, int L, const int* row_src, hipStream_t s) {
-    const int n4 = L * (CPAD / 4);
-    hipLaunchKernelGGL(read_mean_kernel, dim3((n4 + 255) / 256, n_sites), dim3(256), 0, s, (const v4f*)y, (v4f*)pool, R, L,
-                       row_src);
-}
-
-__global__ __launch_bounds__(256) void final_pool_kernel(const v4f* __restrict__ y, float* __restrict__ feat,
-                                                         long long fs, int R, int L, int C, const int* __restrict__ row_src) {
-    constexpr int PT = 32, PS = PT + 1;                        // 32 positions per workgroup: 128-byte runs in the feature row
-    __shared__ float tmax[CPAD * PS], tavg[CPAD * PS];
-    const int pt = blockIdx.x, site = blockIdx.y, tid = threadIdx.x;
-    const int c4 = tid & 31, pl = tid >> 5;
-    const int n4 = L * (CPAD / 4);
-#pragma unroll
-    for (int half = 0; half < PT / 8; ++half) {
-        const int pp = half * 8 + pl, p = pt * PT + pp;
-        v4f mx = splat(0.f), av = splat(0.f);
-        if (p < L) {
-            const size_t off = (size_t)p * (CPAD / 4) + c4;
-            const int* rs = row_src ? row_src + (size_t)site * R : nullptr;
-            auto row = [&](int r) { return rs ? y[(size_t)rs[r] * n4 + off] : y[((size_t)site * R + r) * n4 + off]; };
-            mx = row(0);
-            v4f sum = mx;
-#pragma unroll 8
-            for (int r = 1; r < R; ++r) {
-                const v4f v = row(r);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mx[j] = fmaxf(mx[j], v[j]);
-                sum += v;
-            }
-            av = sum / splat((float)R);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            tmax[(c4 * 4 + j) * PS + pp] = mx[j];
-            tavg[(c4 * 4 + j) * PS + pp] = av[j];
-        }
-    }
-    __syncthreads();
-    float* row = feat + (size_t)site * fs;
-    for (int idx = tid; idx < CPAD * PT; idx += 256) {
-        const int c = idx / PT, pp = idx % PT, p = pt * PT + pp;
-        if (c < C && p < L) {
-            row[(size_t)c * L + p] = tmax[c * PS + pp];                         // max block first (model.py:833)
-            row[(size_t)C * L + (size_t)c * L + p] = tavg[c * PS + pp];
-        }
-    }
+    launch_read_mean_t<RowsFp32>(y, pool, n_sites, R, L, row_src, s);
 }
 
 void launch_final_pool(const float* y, float* feat, long long fs, int n_sites, int R, int L, int C, const int* row_src,
                        hipStream_t s) {
-    hipLaunchKernelGGL(final_pool_kernel, dim3((L + 31) / 32, n_sites), dim3(256), 0, s, (const v4f*)y, feat, fs, R, L, C,
-                       row_src);
+    launch_final_pool_t<RowsFp32>(y, feat, fs, n_sites, R, L, C, row_src, s);
 }
 
 // ------------------------------------------------------------------------------------------------

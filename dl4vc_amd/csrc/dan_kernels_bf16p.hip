@@ -21,6 +21,7 @@
 // Numerics (the oracle's bf16 = "storage" mode, oracle/dan_oracle.py::conv_layer): GEMM operands bf16, sums fp32, bias / ReLU /
 // BatchNorm / residual add in fp32, every stored activation rounded to bf16 (ties to even, v_cvt_pk_bf16_f32).
 #include "dan_kernels.h"
+#include "dan_reduce.h"
 
 namespace dan {
 
@@ -544,7 +545,7 @@ __global__ __launch_bounds__(SEG_THREADS, NWAVE / 4) void segmentp_kernel(Segmen
 // (channel quarter q, position quarter) = 32 channels x PT tiles of 16 columns holds 8 PT accumulators (40 at PT = 5) and the
 // whole wave fits 128 registers.  Why: the lockstep form's SIMDs idle ~25 % of the time with BOTH waves in a wait (L2 round
 // trips of the bottleneck weights, LDS store drains, pipeline fills); four waves leave fewer such moments.  The instruction
-// counts per SIMD are the same.  Weight rows are permuted (dan_capi.cpp::pack_fragr) so that a lane's 2 x 4 accumulators of a
+// counts per SIMD are the same.  Weight rows are permuted (dan_capi.cpp::pack_frag16) so that a lane's 2 x 4 accumulators of a
 // column are 8 CONSECUTIVE channels: one 16-byte LDS store per tile.
 //   lane (n = lane & 15, g = lane >> 4):  B fragment = chunk 4 ks + g of row n (k = 32 ks + 8 g + j),
 //   C: column n, rows 4 g + i of channel tile e  ->  channel 32 q + 8 g + 4 e + i.
@@ -1016,83 +1017,16 @@ void launch_conv_pool(const float* pool, const float* wpool, const float* zero_b
 // ------------------------------------------------------------------------------------------------
 // bf16-input forms of the HBM-bound reductions (fp32 sums in the same order as the fp32 forms)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void read_mean16_kernel(const bf8* __restrict__ y, v4f* __restrict__ pool, int R, int L,
-                                                          const int* __restrict__ row_src) {
-    const int n8 = L * (CPAD / 8);
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n8) return;
-    const int site = blockIdx.y;
-    float sum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const int* rs = row_src ? row_src + (size_t)site * R : nullptr;
-#pragma unroll 8
-    for (int r = 0; r < R; ++r) {
-        const bf8 v = y[(size_t)(rs ? rs[r] : site * R + r) * n8 + i];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sum[j] += (float)v[j];
-    }
-    const float inv = 1.f / (float)R;
-    v4f o0, o1;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { o0[j] = sum[j] / (float)R; o1[j] = sum[4 + j] / (float)R; }
-    (void)inv;
-    pool[((size_t)site * n8 + i) * 2] = o0;
-    pool[((size_t)site * n8 + i) * 2 + 1] = o1;
-}
+template __global__ void read_mean_kernel<RowsBf16>(const bf8*, v4f*, int, int, const int*);
+template __global__ void final_pool_kernel<RowsBf16>(const bf8*, float*, long long, int, int, int, const int*);
 
 void launch_read_mean16(const uint16_t* y, float* pool, int n_sites, int R, int L, const int* row_src, hipStream_t s) {
-    const int n8 = L * (CPAD / 8);
-    hipLaunchKernelGGL(read_mean16_kernel, dim3((n8 + 255) / 256, n_sites), dim3(256), 0, s, (const bf8*)y, (v4f*)pool, R, L, row_src);
-}
-
-__global__ __launch_bounds__(256) void final_pool16_kernel(const bf8* __restrict__ y, float* __restrict__ feat, long long fs,
-                                                           int R, int L, int C, const int* __restrict__ row_src) {
-    constexpr int PT = 32, PS = PT + 1;                        // 32 positions per workgroup: 128-byte runs in the feature row
-    __shared__ float tmax[CPAD * PS], tavg[CPAD * PS];
-    const int pt = blockIdx.x, site = blockIdx.y, tid = threadIdx.x;
-    const int c8 = tid & 15, pl = tid >> 4;
-    const int n8 = L * (CPAD / 8);
-#pragma unroll
-    for (int pass = 0; pass < PT / 16; ++pass) {
-        const int pp = pass * 16 + pl, p = pt * PT + pp;
-        float mx[8], sum[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { mx[j] = 0.f; sum[j] = 0.f; }
-        if (p < L) {
-            const size_t off = (size_t)p * (CPAD / 8) + c8;
-            const int* rs = row_src ? row_src + (size_t)site * R : nullptr;
-            auto row = [&](int r) { return y[(size_t)(rs ? rs[r] : site * R + r) * n8 + off]; };
-            const bf8 v0 = row(0);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { mx[j] = (float)v0[j]; sum[j] = mx[j]; }
-#pragma unroll 8
-            for (int r = 1; r < R; ++r) {
-                const bf8 v = row(r);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float f = (float)v[j]; mx[j] = fmaxf(mx[j], f); sum[j] += f; }
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sum[j] = sum[j] / (float)R;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            tmax[(c8 * 8 + j) * PS + pp] = mx[j];
-            tavg[(c8 * 8 + j) * PS + pp] = sum[j];
-        }
-    }
-    __syncthreads();
-    float* row = feat + (size_t)site * fs;
-    for (int idx = tid; idx < CPAD * PT; idx += 256) {
-        const int c = idx / PT, pp = idx % PT, p = pt * PT + pp;
-        if (c < C && p < L) {
-            row[(size_t)c * L + p] = tmax[c * PS + pp];                         // max block first (model.py:833)
-            row[(size_t)C * L + (size_t)c * L + p] = tavg[c * PS + pp];
-        }
-    }
+    launch_read_mean_t<RowsBf16>(y, pool, n_sites, R, L, row_src, s);
 }
 
 void launch_final_pool16(const uint16_t* y, float* feat, long long fs, int n_sites, int R, int L, int C, const int* row_src,
                          hipStream_t s) {
-    hipLaunchKernelGGL(final_pool16_kernel, dim3((L + 31) / 32, n_sites), dim3(256), 0, s, (const bf8*)y, feat, fs, R, L, C, row_src);
+    launch_final_pool_t<RowsBf16>(y, feat, fs, n_sites, R, L, C, row_src, s);
 }
 
 // highway compression from bf16 h on the bf16 matrix cores (model.py:776-777,859).  A k-group = ONE position (32 channels) = one

@@ -21,6 +21,7 @@
 // split loses of an operand (2^-17).  Bias / ReLU / BatchNorm / residual add in fp32.  Scores within 1e-4 of the reference
 // (tests/test_hip_bf16.py, all golden cases and layer taps).
 #include "dan_kernels.h"
+#include "dan_reduce.h"
 
 namespace dan {
 namespace x3 {
@@ -638,83 +639,11 @@ void launch_segmentx(const SegmentXArgs& a0, int n_sites, int n_cus, hipStream_t
     else hipLaunchKernelGGL(x3::segmentx_kernel<false>, dim3((unsigned)wgs), dim3(SEG_THREADS), 0, s, a);
 }
 
-// ------------------------------------------------------------------------------------------------
-// The two reductions over reads from the two-plane y: value = hi + lo (exact in fp32), fp32 sums in read order, as the fp32 forms
-// ------------------------------------------------------------------------------------------------
+// the two reductions over reads from the two-plane y (dan_reduce.h: value = hi + lo, exact in fp32), under this object's schedule
+template __global__ void read_mean_kernel<RowsBf16x2>(const bf8*, v4f*, int, int, const int*);
+template __global__ void final_pool_kernel<RowsBf16x2>(const bf8*, float*, long long, int, int, int, const int*);
+
 namespace x3 {
-
-__global__ __launch_bounds__(256) void read_meanx_kernel(const bf8* __restrict__ y, v4f* __restrict__ pool, int R, int L,
-                                                         const int* __restrict__ row_src) {
-    const int n8 = L * (CPAD / 8);
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n8) return;
-    const int site = blockIdx.y;
-    float sum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const int* rs = row_src ? row_src + (size_t)site * R : nullptr;
-#pragma unroll 4
-    for (int r = 0; r < R; ++r) {
-        const bf8* row = y + (size_t)(rs ? rs[r] : site * R + r) * (2 * n8);
-        const bf8 vh = row[i], vl = row[n8 + i];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sum[j] += (float)vh[j] + (float)vl[j];
-    }
-    v4f o0, o1;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { o0[j] = sum[j] / (float)R; o1[j] = sum[4 + j] / (float)R; }
-    pool[((size_t)site * n8 + i) * 2] = o0;
-    pool[((size_t)site * n8 + i) * 2 + 1] = o1;
-}
-
-__global__ __launch_bounds__(256) void final_poolx_kernel(const bf8* __restrict__ y, float* __restrict__ feat, long long fs,
-                                                          int R, int L, int C, const int* __restrict__ row_src) {
-    constexpr int PT = 32, PS = PT + 1;                        // 32 positions per workgroup: 128-byte runs in the feature row
-    __shared__ float tmax[CPAD * PS], tavg[CPAD * PS];
-    const int pt = blockIdx.x, site = blockIdx.y, tid = threadIdx.x;
-    const int c8 = tid & 15, pl = tid >> 4;
-    const int n8 = L * (CPAD / 8);
-#pragma unroll
-    for (int pass = 0; pass < PT / 16; ++pass) {
-        const int pp = pass * 16 + pl, p = pt * PT + pp;
-        float mx[8], sum[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { mx[j] = 0.f; sum[j] = 0.f; }
-        if (p < L) {
-            const size_t off = (size_t)p * (CPAD / 8) + c8;
-            const int* rs = row_src ? row_src + (size_t)site * R : nullptr;
-            auto rowp = [&](int r) { return y + (size_t)(rs ? rs[r] : site * R + r) * (2 * n8) + off; };
-            {
-                const bf8* r0 = rowp(0);
-                const bf8 vh = r0[0], vl = r0[n8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { mx[j] = (float)vh[j] + (float)vl[j]; sum[j] = mx[j]; }
-            }
-#pragma unroll 4
-            for (int r = 1; r < R; ++r) {
-                const bf8* rp = rowp(r);
-                const bf8 vh = rp[0], vl = rp[n8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float f = (float)vh[j] + (float)vl[j]; mx[j] = fmaxf(mx[j], f); sum[j] += f; }
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sum[j] = sum[j] / (float)R;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            tmax[(c8 * 8 + j) * PS + pp] = mx[j];
-            tavg[(c8 * 8 + j) * PS + pp] = sum[j];
-        }
-    }
-    __syncthreads();
-    float* row = feat + (size_t)site * fs;
-    for (int idx = tid; idx < CPAD * PT; idx += 256) {
-        const int c = idx / PT, pp = idx % PT, p = pt * PT + pp;
-        if (c < C && p < L) {
-            row[(size_t)c * L + p] = tmax[c * PS + pp];                         // max block first (model.py:833)
-            row[(size_t)C * L + (size_t)c * L + p] = tavg[c * PS + pp];
-        }
-    }
-}
-
 
 // ------------------------------------------------------------------------------------------------
 // FC on the bf16 matrix cores, split operands (dan_config.precision >= 1):  C = relu?(A W^T + bias), A fp32 [M][lda] (split into
@@ -845,14 +774,12 @@ void launch_fcx(const float* A, long long lda, const uint16_t* W, long long ldw,
 }
 
 void launch_read_meanx(const uint16_t* y, float* pool, int n_sites, int R, int L, const int* row_src, hipStream_t s) {
-    const int n8 = L * (CPAD / 8);
-    hipLaunchKernelGGL(x3::read_meanx_kernel, dim3((n8 + 255) / 256, n_sites), dim3(256), 0, s, (const x3::bf8*)y, (x3::v4f*)pool, R, L,
-                       row_src);
+    launch_read_mean_t<RowsBf16x2>(y, pool, n_sites, R, L, row_src, s);
 }
 
 void launch_final_poolx(const uint16_t* y, float* feat, long long fs, int n_sites, int R, int L, int C, const int* row_src,
                         hipStream_t s) {
-    hipLaunchKernelGGL(x3::final_poolx_kernel, dim3((L + 31) / 32, n_sites), dim3(256), 0, s, (const x3::bf8*)y, feat, fs, R, L, C, row_src);
+    launch_final_pool_t<RowsBf16x2>(y, feat, fs, n_sites, R, L, C, row_src, s);
 }
 
 }  // namespace dan
