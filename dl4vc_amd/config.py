@@ -18,6 +18,7 @@ MAX_READS = 100
 MIN_RESIDUAL_LAYER = 2
 MAX_LAYERS = 16       # capacity of the C-ABI config struct (include/dl4vc_dan.h)
 L0_MAX_LAYERS = 12    # csrc/dan_kernels.h: layer 1 is summed from tables when the first segment has at most this many layers
+WINO_F43_MAX_LENGTH = 206   # csrc/dan_device.h MPOS_SHORT + 16: windows up to this run their Winograd layers in F(4,3) form, longer ones in F(2,3)
 
 PRECISION_F32 = 0     # v_mfma_f32_16x16x4_f32: exact fp32 FMA chains (parity path, the default)
 PRECISION_BF16X3 = 1  # split-bf16: hi+lo operands, three bf16 MFMAs per product, fp32 accumulate (L <= 304)
@@ -47,7 +48,7 @@ class DanConfig:
     fc_sizes: Tuple[int, ...] = (1024, 256)  # layer_sizes (constructor default, model.py:35)
     embed_dim: int = 20                      # embed_dim   (constructor default)
     precision: int = PRECISION_F32
-    conv_algo: int = 0                       # fp32 path: 0 auto, 1 direct 3-tap GEMM, 2 Winograd F(2,3) (include/dl4vc_dan.h)
+    conv_algo: int = 0                       # fp32 path: 0 auto, 1 direct 3-tap GEMM, 2 Winograd, F(4,3) or F(2,3) by window (include/dl4vc_dan.h)
     skip_empty_rows: bool = False            # all-padding pileup rows computed once per site (bit-identical outputs)
     bf16_form: int = 0                       # precision 2: 0 = eight-wave kernel form (default), 1 = sixteen-wave form (include/dl4vc_dan.h)
 
@@ -109,19 +110,22 @@ class DanConfig:
         return 2.0 * (self.reads * self.length * self.macs_per_position() + fc)
 
     def winograd_applies(self) -> bool:
-        """The fp32 path runs the 3-tap convolutions after the first layer in Winograd F(2,3) form when all of them have
+        """The fp32 path runs the 3-tap convolutions after the first layer in Winograd form (F(4,3) for windows of up to 206 columns, F(2,3) above) when all of them have
         dilation 2 (the production network) and ``conv_algo`` does not force the direct form."""
         dil_ok = (self.layers < 3 or self.dil_mid == 2) and (self.layers < 2 or self.dil_final == 2)
         return self.precision == PRECISION_F32 and dil_ok and self.conv_algo != 1 and self.layers > 1
 
     def executed_macs_per_position(self) -> float:
         """MFMA multiply-accumulates per (read, position) actually issued: ``macs_per_position`` with the Winograd layers'
-        3-tap term replaced by 4 GEMMs per 2 outputs (2 * cin * cout).  Tile padding is not counted."""
+        3-tap term replaced by 6 GEMMs per 4 outputs (1.5 * cin * cout: F(4,3), the one-unit reads of up to 206 columns) or by
+        4 GEMMs per 2 outputs (2 * cin * cout: F(2,3), the longer windows).  Tile padding and the direct-form remainder tile of
+        columns 190 .. 205 are not counted."""
         total = float(self.macs_per_position())
         if self.winograd_applies():
+            saved = 1.5 if self.length <= WINO_F43_MAX_LENGTH else 1.0
             for l in range(2, self.layers + 1):
                 cin, cout, _ = self.layer_dims(l)
-                total -= cin * cout
+                total -= saved * cin * cout
         first_segment = min(self.pool_layers) if self.pool_layers else self.layers
         if self.precision == PRECISION_F32 and first_segment <= L0_MAX_LAYERS:
             # the fp32 path computes layer 1 from tables on the vector ALUs (csrc/dan_kernels.h L0_*): its 3 * cin * cout

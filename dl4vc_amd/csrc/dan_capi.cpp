@@ -48,7 +48,7 @@ struct dan_handle {
     int n0_stride = 0;                       // fc_sizes[0] padded to a multiple of 16 (K of the second FC)
     int chunk = 0, max_batch = 0;
     bool chunk_auto = false;                                   // the chunk was sized by dan_create (free device memory), not by the caller
-    int wino = 0;                            // dilation-2 layers in Winograd F(2,3) form
+    int wino = 0;                            // dilation-2 layers in Winograd form (F(4,3) or F(2,3) by window: launch_segment)
     int tap_layer = -1;
     int last_chunk_sites = 0;
     int64_t last_batch = 0;
@@ -471,7 +471,7 @@ std::vector<float> layer0_table(const LayerSrc& s, const Tensor& emb, const Tens
     return tab;
 }
 
-// the fp32 block of a layer (dan_kernels.h): MFMA fragments of the conv, its Winograd F(2,3) form, the residual and the bottleneck
+// the fp32 block of a layer (dan_kernels.h): MFMA fragments of the conv, its Winograd F(2,3) and F(4,3) forms, the residual and the bottleneck
 void pack_layer_fp32(const LayerSrc& s, float* blk) {
     auto Wf = [&](int o, int cc, int t) { return s.Wf(o, cc, t); };
     pack_frag(blk + W_OFF, 3, s.l == 0 ? KG0 : KGC, KGC, Wf);
@@ -482,6 +482,20 @@ void pack_layer_fp32(const LayerSrc& s, float* blk) {
             return k == 0 ? (float)g0 : k == 1 ? (float)((g0 + g1 + g2) * 0.5) : k == 2 ? (float)((g0 - g1 + g2) * 0.5) : (float)g2;
         };
         pack_frag(blk + WW_OFF, 4, KGC, KGC, Wu);
+        // Winograd F(4,3) weight transform U = G g for the points 0, +-1, +-2, formed in double: G = [1/4, 0, 0], -1/6 [1, 1, 1],
+        // -1/6 [1, -1, 1], [1/24, 1/12, 1/6], [1/24, -1/12, 1/6], [0, 0, 1]
+        auto Wu43 = [&](int o, int cc, int k) -> float {
+            const double g0 = s.Wf(o, cc, 0), g1 = s.Wf(o, cc, 1), g2 = s.Wf(o, cc, 2);
+            switch (k) {
+                case 0: return (float)(g0 / 4.0);
+                case 1: return (float)(-(g0 + g1 + g2) / 6.0);
+                case 2: return (float)(-(g0 - g1 + g2) / 6.0);
+                case 3: return (float)(g0 / 24.0 + g1 / 12.0 + g2 / 6.0);
+                case 4: return (float)(g0 / 24.0 - g1 / 12.0 + g2 / 6.0);
+                default: return (float)g2;
+            }
+        };
+        pack_frag(blk + W43_OFF, 6, KGC, KGC, Wu43);
     }
     if (s.wr) pack_frag(blk + WRES_OFF, 1, KGC, KGC, [&](int o, int cc, int) { return s.Wr(o, cc); });
     if (s.wb) pack_frag(blk + WBOT_OFF, 1, KGC, 2, [&](int o, int cc, int) { return s.Wb(o, cc); });
@@ -713,7 +727,7 @@ int dan_create(const dan_config* cfg, dan_t** out) {
         return fail(nullptr, DAN_ERR_INVALID_ARG, "Do not allow residuals starting at conv layer %d", c.residual_start);   // model.py:209
     if ((c.pool_layers_mask & 1u) || (c.pool_layers_mask >> c.layers))
         return fail(nullptr, DAN_ERR_INVALID_ARG, "pool layers must lie in 1..layers-1");
-    // Winograd F(2,3) form (dan_kernels.hip): fp32 path, and every conv after the first must have dilation 2
+    // Winograd forms (dan_kernels.hip): fp32 path, and every conv after the first must have dilation 2
     const bool wino_ok = c.precision == 0 && (c.layers < 3 || c.dil_mid == 2) && (c.layers < 2 || c.dil_final == 2);
     if (c.conv_algo < 0 || c.conv_algo > 2) return fail(nullptr, DAN_ERR_INVALID_ARG, "conv_algo %d unknown (0 = auto, 1 = direct, 2 = winograd)", c.conv_algo);
     if (c.skip_empty_rows < 0 || c.skip_empty_rows > 1) return fail(nullptr, DAN_ERR_INVALID_ARG, "skip_empty_rows must be 0 or 1");
@@ -1181,6 +1195,9 @@ int64_t dan_query(const dan_t* h, const char* what) {
     if (w == "chunk_sites_auto") return h->chunk_auto ? 1 : 0;
     if (w == "max_batch") return h->max_batch;
     if (w == "cpad") return CPAD;
+    if (w == "layer_stride") return LAYER_STRIDE;          // floats per layer of the "wl" buffer, and its two Winograd blocks
+    if (w == "wino_f23_offset") return WW_OFF;
+    if (w == "wino_f43_offset") return W43_OFF;
     if (w == "tap_sites") return h->last_chunk_sites;
     if (w == "segments") return h->n_segments;
     if (w == "bf16_pingpong") return h->fam == &FAMILIES[2] ? 1 : 0;            // (0 before dan_finalize, as ever)
@@ -1201,6 +1218,10 @@ int64_t dan_read_buffer(dan_t* h, const char* name, float* dst, int64_t capacity
     else if (w == "feature") { src = h->d_feat; n = h->last_batch * h->F_stride; }
     else if (w == "hidden0") { src = h->d_hid0; n = h->last_batch * h->n0_stride; }
     else if (w == "hidden1") { src = h->d_hid1; n = h->last_batch * c.fc_sizes[1]; }
+    else if (w == "wl") {                    // the fp32 family's packed weight blocks, [layer][LAYER_STRIDE] (dan_kernels.h)
+        if (!h->d_wl) return fail(h, DAN_ERR_STATE, "dan_read_buffer('wl'): this precision keeps no fp32 weight blocks");
+        src = h->d_wl; n = (int64_t)c.layers * LAYER_STRIDE;
+    }
     else if (w == "pool") { src = h->d_pool; n = (int64_t)h->last_chunk_sites * c.length * CPAD; }
     else if (w == "h") {
         // bottleneck outputs of the last chunk, [layer][site][read][L][HPAD] (layer stride = the chunk's capacity); bf16 on the

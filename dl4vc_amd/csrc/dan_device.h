@@ -38,6 +38,10 @@ __device__ __forceinline__ void gemm_tile(v4f (&acc)[NT], const v4f (&a)[NT], v4
     b = *(const v4f*)next;
 }
 
+// JOIN_WAIT: the F(4,3) kernels' direct first layer (taken only off the table path).  There hipcc's register allocation lets the
+// step's last tile borrow a register that the next step's weight addresses overwrite, and behind the join of the `full` branch
+// the hazard recognizer places no wait states on the taken path (tests/test_isa_hazards.py): the source carries them.
+template <bool JOIN_WAIT = false>
 __device__ __forceinline__ void conv_gemm(v4f (&acc)[MTW][NT], const float* xs, gv4f_ptr wl, const v4f (&a_first)[NT],
                                           int kg, int ntaps, int dil, int lane, int m_base, int cnt) {
     const int pos = lane & 15, kk = lane >> 4;
@@ -75,6 +79,10 @@ __device__ __forceinline__ void conv_gemm(v4f (&acc)[MTW][NT], const float* xs, 
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // 1 DS read
         }
         if (full) gemm_tile(acc[MTW - 1], a, b[MTW - 1], xn + (MTW - 1) * 16 * LDS_S);
+        if constexpr (JOIN_WAIT) {
+            asm volatile("s_nop 7");
+            __builtin_amdgcn_sched_barrier(0);
+        }
         t = tn; g = gn;
     }
 }
@@ -154,7 +162,7 @@ constexpr int WHB = 102;                // first position of the upper half's ti
 // lane: the lower-half lanes tile [0, 96), the upper-half lanes [94, 190) -- 94 == 2 mod 4 like 102, so that the sixteen lanes of a
 // ds_read_b128 group still touch rows of all eight residues mod 8.  6 / 7 of the matrix work of a layer for such a unit.
 // One-unit reads of up to MPOS_SHORT + 16 = 206 columns take the same six tiles and, for columns [190, 206), one direct-form
-// position tile per wave (conv_gemm_wino REM): 27 / 28 of the seven-tile form's conv MFMAs, and no tile slot past column 206.
+// position tile per wave: no tile slot past column 206.  Those reads walk the strip in F(4,3) form (conv_gemm_wino43 below).
 constexpr int MW_SHORT = 6;
 constexpr int WHB_SHORT = 94;
 constexpr int MPOS_SHORT = WHB_SHORT + 16 * MW_SHORT;    // 190: the longest unit the six-tile form covers
@@ -180,15 +188,8 @@ __device__ __forceinline__ v4f pk_sub(v4f a, v4f b, v2f m1) {
     return (v4f){lo[0], lo[1], hi[0], hi[1]};
 }
 __device__ __forceinline__ v4f pk_add(v4f a, v4f b) { return a + b; }
-// REM (the one-unit six-tile form, dan_kernels.hip): columns [MPOS_SHORT, MPOS_SHORT + 16) as ONE direct-form position tile beside the
-// walk -- per k-step three MFMAs (taps at rows p - 2, p, p + 2) on the layer's plain 3-tap fragments (wd: this wave's tile of the
-// W_OFF block, [tap][kg][tile][lane]), B fragments in the direct form's layout (xr: row p - 2 of position p = MPOS_SHORT + (lane & 15),
-// channels 4 (lane >> 4)).  The three weight fragments of a k-group are requested at its top and each tap's ds_read_b128 one
-// Winograd tile ahead of its MFMAs, which follow tiles 1, 3 and 5: nothing of the tile trails the walk.
-template <int TW, bool REM = false>
-__device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* xrow, gv4f_ptr wl, const v4f (&a_first)[4],
-                                               [[maybe_unused]] v4f& racc, [[maybe_unused]] const float* xr, [[maybe_unused]] gv4f_ptr wd) {
-    static_assert(!REM || TW == 6, "the remainder tile's taps follow tiles 1, 3 and 5 of a six-tile walk");
+template <int TW>
+__device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* xrow, gv4f_ptr wl, const v4f (&a_first)[4]) {
     v4f a_nxt[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) a_nxt[k] = a_first[k];
@@ -204,11 +205,6 @@ __device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* x
         const int gn = (g + 1 < KGC) ? g + 1 : g;            // last step: harmless re-read
 #pragma unroll
         for (int k = 0; k < 4; ++k) a_nxt[k] = wl[(size_t)(k * KGC + gn) * (KGC * 64)];
-        [[maybe_unused]] v4f ra[3], rb;
-        if constexpr (REM) {
-#pragma unroll
-            for (int t = 0; t < 3; ++t) ra[t] = wd[(size_t)(t * KGC + g) * (KGC * 64)];
-        }
         const float* xg = xrow + g * 16;
         const float* xn = xrow + gn * 16;
 #pragma unroll
@@ -223,9 +219,6 @@ __device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* x
                 xa = *(const v4f*)(xn); xb = *(const v4f*)(xn + 2 * LDS_S);
                 xc = *(const v4f*)(xn + 4 * LDS_S); xd = *(const v4f*)(xn + 6 * LDS_S);
             }
-            if constexpr (REM) {
-                if ((m & 1) == 0) rb = *(const v4f*)(xr + (m >> 1) * 2 * LDS_S + g * 16);
-            }
             // MFMAs at s_setprio 3, the VALU/LDS stretch that forms the next V at 0: the arbiter then serves the other
             // wave's MFMAs ahead of this wave's VALU stream (by default the OLDER wave's instructions of either kind come
             // first, and its VALU batches stall the younger wave's MFMA issue).  tools/ubench/wino_loop.hip: 37.6 -> 36.4
@@ -235,20 +228,89 @@ __device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* x
             for (int s = 0; s < 4; ++s)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) acc[m][k] = mfma16(a[k][s], v[k][s], acc[m][k]);
-            if constexpr (REM) {
-                if (m & 1) {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) racc = mfma16(ra[m >> 1][s], rb[s], racc);
-                }
-            }
             __builtin_amdgcn_s_setprio(0);
         }
     }
 }
-template <int TW>
-__device__ __forceinline__ void conv_gemm_wino(v4f (&acc)[TW][4], const float* xrow, gv4f_ptr wl, const v4f (&a_first)[4]) {
-    v4f none = splat(0.f);
-    conv_gemm_wino<TW, false>(acc, xrow, wl, a_first, none, nullptr, nullptr);
+
+// ------------------------------------------------------------------------------------------------
+// Winograd F(4,3) core (points 0, +-1, +-2): the one-unit reads of up to 206 columns (see dan_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+// The lane's strip is the six-tile form's (wino_base<MW_SHORT>), walked as THREE tiles of four outputs: tile m takes rows
+// d_i = x(P + 8 m - 2 + 2 i), i < 6, and gives y(P + 8 m + 2 o), o < 4.  Two rows carry over from tile to tile, the four new
+// ones are read at the row residues the six-tile walk reads.  acc[m][k] += U_k[own 16 channels][all 128 in-channels] * V_k[tile m]
+// over six components k: 18 MFMAs per k-step where the F(2,3) walk of the same strip takes 24.
+//   V0 = 4 d0 - 5 d2 + d4,  V1,2 = (d4 - 4 d2) +- (d3 - 4 d1),  V3,4 = (d4 - d2) +- 2 (d3 - d1),  V5 = 4 d1 - 5 d3 + d5:
+// twelve packed operations per tile on each register pair, the constants in registers the compiler cannot see through (pk_sub).
+// REM: columns [MPOS_SHORT, MPOS_SHORT + 16) as ONE direct-form position tile beside the walk -- per k-step three MFMAs (taps at
+// rows p - 2, p, p + 2) on the layer's plain 3-tap fragments (wd: this wave's tile of the W_OFF block, [tap][kg][tile][lane]), B
+// fragments in the direct form's layout (xr: row p - 2 of position p = MPOS_SHORT + (lane & 15), channels 4 (lane >> 4)).  Tap t's
+// MFMAs follow tile t's; its ds_read_b128 goes out behind the previous tap's MFMAs, one tile ahead: nothing trails the walk.
+constexpr int MW43 = MW_SHORT / 2;      // F(4,3) tiles per lane
+__device__ __forceinline__ v4f pk_fma(v4f a, v2f k, v4f c) {        // a * k + c
+    const v2f lo = __builtin_elementwise_fma((v2f){a[0], a[1]}, k, (v2f){c[0], c[1]});
+    const v2f hi = __builtin_elementwise_fma((v2f){a[2], a[3]}, k, (v2f){c[2], c[3]});
+    return (v4f){lo[0], lo[1], hi[0], hi[1]};
+}
+template <bool REM>
+__device__ __forceinline__ void conv_gemm_wino43(v4f (&acc)[MW43][6], const float* xrow, gv4f_ptr wl, const v4f (&a_first)[6],
+                                                 [[maybe_unused]] v4f& racc, [[maybe_unused]] const float* xr, [[maybe_unused]] gv4f_ptr wd) {
+    v4f a_nxt[6], d[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a_nxt[k] = a_first[k];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) d[i] = *(const v4f*)(xrow + 2 * i * LDS_S);
+    [[maybe_unused]] v4f rb;
+    if constexpr (REM) rb = *(const v4f*)xr;
+    float c1 = -1.f, c2 = 2.f, c4 = 4.f, c5 = -5.f;
+    asm volatile("" : "+v"(c1), "+v"(c2), "+v"(c4), "+v"(c5));
+    const v2f m1 = {c1, c1}, p2 = {c2, c2}, m2 = {-c2, -c2}, p4 = {c4, c4}, m4 = {-c4, -c4}, m5 = {c5, c5};
+    for (int g = 0; g < KGC; ++g) {
+        v4f a[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) a[k] = a_nxt[k];
+        const int gn = (g + 1 < KGC) ? g + 1 : g;            // last step: harmless re-read
+#pragma unroll
+        for (int k = 0; k < 6; ++k) a_nxt[k] = wl[(size_t)(k * KGC + gn) * (KGC * 64)];
+        [[maybe_unused]] v4f ra[3];
+        if constexpr (REM) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) ra[t] = wd[(size_t)(t * KGC + g) * (KGC * 64)];
+        }
+        const float* xg = xrow + g * 16;
+        const float* xn = xrow + gn * 16;
+#pragma unroll
+        for (int m = 0; m < MW43; ++m) {
+            v4f v[6];
+            {
+                const v4f a42 = pk_fma(d[2], m4, d[4]), b31 = pk_fma(d[1], m4, d[3]);
+                const v4f c42 = pk_fma(d[2], m1, d[4]), e31 = pk_fma(d[1], m1, d[3]);
+                v[0] = pk_fma(d[2], m5, pk_fma(d[0], p4, d[4]));
+                v[1] = pk_add(a42, b31); v[2] = pk_fma(b31, m1, a42);
+                v[3] = pk_fma(e31, p2, c42); v[4] = pk_fma(e31, m2, c42);
+                v[5] = pk_fma(d[3], m5, pk_fma(d[1], p4, d[5]));
+            }
+            if (m + 1 < MW43) {
+                d[0] = d[4]; d[1] = d[5];
+#pragma unroll
+                for (int i = 2; i < 6; ++i) d[i] = *(const v4f*)(xg + (8 * (m + 1) + 2 * i) * LDS_S);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) d[i] = *(const v4f*)(xn + 2 * i * LDS_S);
+            }
+            __builtin_amdgcn_s_setprio(3);                      // (as in conv_gemm_wino)
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int k = 0; k < 6; ++k) acc[m][k] = mfma16(a[k][s], v[k][s], acc[m][k]);
+            if constexpr (REM) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) racc = mfma16(ra[m][s], rb[s], racc);
+            }
+            __builtin_amdgcn_s_setprio(0);
+            if constexpr (REM) rb = *(const v4f*)(m + 1 < MW43 ? xr + (m + 1) * 2 * LDS_S + g * 16 : xr + gn * 16);
+        }
+    }
 }
 
 // LDS rows a Winograd GEMM may read: tiles past the window read beyond the activation rows (into whatever follows them)

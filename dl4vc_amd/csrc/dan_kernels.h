@@ -42,7 +42,9 @@ constexpr int CST_BIAS = 0, CST_SCALE = CPAD, CST_SHIFT = 2 * CPAD, CST_BRES = 3
 constexpr int CST_FLOATS = 4 * CPAD + HPAD;                  // 544
 //   [WW_OFF)   Winograd F(2,3) weights U_k of the conv   [k 4][kg 8][tile 8][lane 64][4]   (layers > 1 only)
 constexpr int WW_OFF = CST_OFF + CST_FLOATS + 32;            // 70208
-constexpr int LAYER_STRIDE = WW_OFF + 4 * KGC * KGC * 256;   // 135744 floats (16-byte aligned blocks)
+//   [W43_OFF)  Winograd F(4,3) weights U_k of the conv   [k 6][kg 8][tile 8][lane 64][4]   (layers > 1 only; behind every older block)
+constexpr int W43_OFF = WW_OFF + 4 * KGC * KGC * 256;        // 135744
+constexpr int LAYER_STRIDE = W43_OFF + 6 * KGC * KGC * 256;  // 234048 floats (16-byte aligned blocks)
 constexpr int MAX_LAYERS = 16;
 
 struct SegmentArgs {
@@ -64,7 +66,7 @@ struct SegmentArgs {
     long long h_layer_stride;    // floats between layers of h
     float* tap;                  // [site][read][L][CPAD] or nullptr
     int tap_layer;               // 0 = encoded input, l = after conv layer l (1-based), -1 = none
-    int wino;                    // 1: dilation-2 layers after the first run in Winograd F(2,3) form
+    int wino;                    // 1: dilation-2 layers after the first run in Winograd form (F(4,3) for one-unit reads of up to 206 columns, else F(2,3))
     int n_rows;                  // filled by launch_segment: n_sites * R
     int xcd_rows;                // filled by launch_segment: rows per XCD slice (whole sites)
     const int* work;             // rows to compute (device list, see launch_row_map); read only when work_count is set

@@ -51,10 +51,14 @@ constexpr int NSTAMP = 64;
 // may run past the activation into the constants that follow it in LDS) produce columns nobody stores.
 static_assert((HALO + WHB + 4 * (4 * MW - 1) + 1 + 4 + 1) * LDS_S <= LDS_ROWS * LDS_S + MAX_LAYERS * CST_FLOATS, "wino reads stay inside LDS");
 static_assert(WHB + 4 * (4 * MW - 1) + 3 >= MPOS - 1 && 4 * (4 * MW - 1) + 3 >= WHB - 1, "wino tiling covers the read");
-// ... and the six-tile form (dan_device.h MW_SHORT): [0, 96) + [94, 190) -- the split kernel's short units, and every one-unit
+// ... and the six-tile strips (dan_device.h MW_SHORT): [0, 96) + [94, 190) -- the split kernel's short units, and every one-unit
 // read of up to 206 columns, whose columns [190, 206) are ONE direct-form position tile per wave (three MFMAs per k-step on the
-// layer's plain 3-tap fragments, conv_gemm_wino REM): 27 conv MFMAs per k-step and wave where seven tiles take 28.  Its taps
-// read rows p - 2 .. p + 2 of the image; rows at and past L keep the prologue's zeros.
+// layer's plain 3-tap fragments).  Its taps read rows p - 2 .. p + 2 of the image; rows at and past L keep the prologue's zeros.
+// The one-unit reads walk their strip in Winograd F(4,3) form (dan_device.h conv_gemm_wino43: points 0, +-1, +-2, U = G g host-packed
+// behind the F(2,3) block), THREE tiles of four outputs per lane instead of six of two -- 6 channel GEMMs per 4 outputs:
+//   rows d_i = x(P - 2 + 2 i), i < 6;  M_k = U_k V_k;  y(P), y(P+2), y(P+4), y(P+6) = A^T M  (the layer body's output transform)
+// The same rows are read (the last one is P + 24 in either walk) and the same cells stored, so everything around the conv GEMM is
+// shared with the F(2,3) form: 21 conv MFMAs per k-step and wave where six F(2,3) tiles + the remainder tile took 27.
 static_assert(HALO + MPOS_SHORT + 15 + 2 < LDS_ROWS && MPOS_SHORT + 16 <= MPOS, "the remainder tile's taps stay inside the image");
 static_assert(WHB_SHORT + 4 * (4 * MW_SHORT - 1) + 3 >= MPOS_SHORT - 1 && 4 * (4 * MW_SHORT - 1) + 3 >= WHB_SHORT - 1 && WHB_SHORT % 4 == 2,
               "short wino tiling covers its unit");
@@ -112,10 +116,11 @@ __device__ __forceinline__ void gemm1x1_wino(v4f (&acc)[TW][2], const float* xro
 // item is (row, unit), `L` below is the UNIT's length and every position-indexed pointer is offset to the unit's first column;
 // what differs from the one-unit form is addressing (window stride Lw), the allele-agreement predicates (taken over the whole
 // window, not the unit) and the stores (own columns only, y out of place).  SPLIT = false compiles to the code it always was.
-// TW: Winograd tiles per lane -- MW = 7 (one unit of 207 or 208 columns; and every direct form) or MW_SHORT = 6: SPLIT, units of up
-// to 190 columns (every unit of a split Winograd read, e.g. 161 columns at a 301-column window); one unit, a read of up to 206
-// columns -- REM = true with the remainder tile for 191 .. 206 columns, REM = false without it for a read that ends before the tile
-// (an instantiation of its own, chosen by L in launch_segment: no remainder MFMA, load, store or branch in it).
+// TW: F(2,3) tiles a lane's strip holds -- MW = 7 (one unit of 207 or 208 columns; and every direct form) or MW_SHORT = 6: SPLIT, units of up
+// to 190 columns (every unit of a split Winograd read, e.g. 161 columns at a 301-column window), walked in F(2,3) form; one unit, a read
+// of up to 206 columns, walked as three F(4,3) tiles -- REM = true with the remainder tile for 191 .. 206 columns, REM = false without
+// it for a read that ends before the tile (an instantiation of its own, chosen by L in launch_segment: no remainder MFMA, load, store
+// or branch in it).
 // FOLD = true (with PERSIST, one unit per read, every row computed): the workgroup owns WHOLE SITES -- site s, rows 0 .. R-1 in
 // order, then its next site -- and forms the reductions over the read axis itself: after a row's last layer it adds the LDS
 // image to its own running planes in device memory (SegmentArgs::fold_scratch: sum, and max for the network's last segment;
@@ -128,6 +133,9 @@ __global__ __launch_bounds__(SEG_THREADS, NWAVE / 4) void segment_kernel(Segment
     static_assert(TW == MW ? !(SPLIT && WINO) : (WINO && TW == MW_SHORT), "six tiles per lane: Winograd forms only, and the split one always");
     static_assert(!REM || (WINO && !SPLIT && TW == MW_SHORT), "the remainder tile [190, 206): beside six Winograd tiles of a one-unit read");
     constexpr int TILES = (SPLIT && WINO) ? (MPOS_SHORT + 15) / 16 : MT;    // 16-column tiles of the unit (bottleneck, table walk)
+    // the one-unit six-tile strips are walked in F(4,3) form, three tiles of four outputs (conv_gemm_wino43); the split form's and the
+    // seven-tile strips in F(2,3) form
+    constexpr bool W43 = WINO && !SPLIT && TW == MW_SHORT;
     // one allocation, so that the layout the Winograd tiles past the window rely on (constants right after the activation
     // rows) is explicit
     __shared__ __attribute__((aligned(16))) float lds[LDS_ROWS * LDS_S + MAX_LAYERS * CST_FLOATS];
@@ -192,8 +200,8 @@ next_row:                                                   // (PERSIST only: ba
     auto wino_layer = [&](int l) { return WINO && l > 0; };
     // First weight fragments of a conv GEMM, requested a stage ahead of it (eight plain vector variables: an aggregate, or an
     // array, captured by reference in the layer lambdas ends up in scratch memory).  The PERSIST Winograd form has no
-    // registers to carry them across stages: its conv GEMM fetches its own.
-    constexpr bool CARRY = !(WINO && PERSIST);
+    // registers to carry them across stages: its conv GEMM fetches its own.  So does every F(4,3) form (six fragments, not four).
+    constexpr bool CARRY = !(WINO && (PERSIST || W43));
     v4f pc0 = splat(0.f), pc1 = pc0, pc2 = pc0, pc3 = pc0, pn0 = pc0, pn1 = pc0, pn2 = pc0, pn3 = pc0;
     auto first_frags = [&](int l, v4f& f0, v4f& f1, v4f& f2, v4f& f3) {
         const float* blk = a.wl + (size_t)l * LAYER_STRIDE;
@@ -383,7 +391,7 @@ next_row:                                                   // (PERSIST only: ba
                 for (int n = 0; n < NT; ++n) acc[m][n] = bias[n];
         }
         STAMP(sb + 0);
-        conv_gemm(acc, xs, w_conv, pre_dir, kg, 3, dil, lane, m_base, cnt);
+        conv_gemm<W43>(acc, xs, w_conv, pre_dir, kg, 3, dil, lane, m_base, cnt);
         STAMP(sb + 1);
         // this wave's eight bottleneck weight fragments of the layer: issued now, consumed after the epilogue
         // (and the residual GEMM), so the ~1.5k-cycle loaded-L2 latency is off the critical path
@@ -497,25 +505,28 @@ next_row:                                                   // (PERSIST only: ba
         int wp = wP0;
         float* xq;
         {
-            v4f acc[TW][4];
+            // accumulators of the walk, [tile][component]: the bias seeds component 1, whose column of A^T is all ones in either form
+            constexpr int NTL = W43 ? MW43 : TW, NCP = W43 ? 6 : 4;
+            v4f acc[NTL][NCP];
             const v4f bias = *(const v4f*)(lc + CST_BIAS + chw);
 #pragma unroll
-            for (int m = 0; m < TW; ++m) { acc[m][0] = splat(0.f); acc[m][1] = bias; acc[m][2] = splat(0.f); acc[m][3] = splat(0.f); }
+            for (int m = 0; m < NTL; ++m)
+#pragma unroll
+                for (int k = 0; k < NCP; ++k) acc[m][k] = (k == 1) ? bias : splat(0.f);
             if constexpr (REM) rout = bias;
             STAMP(sb + 0);
-            auto gemm = [&](const v4f (&pre_w)[4]) {
-                if constexpr (REM)
-                    conv_gemm_wino<TW, true>(acc, xw - 2 * LDS_S + kk * 4, w_w, pre_w, rout, xs + (HALO + rp - 2) * LDS_S + kk * 4, (gv4f_ptr)(wblk + W_OFF) + wave * 64 + lane);
-                else
-                    conv_gemm_wino(acc, xw - 2 * LDS_S + kk * 4, w_w, pre_w);
-            };
-            if constexpr (CARRY) {
+            if constexpr (W43) {
+                gv4f_ptr w0 = (gv4f_ptr)(wblk + W43_OFF) + wave * 64 + lane;
+                constexpr size_t KS = (size_t)KGC * (KGC * 64);
+                const v4f pre_w[6] = {w0[0], w0[KS], w0[2 * KS], w0[3 * KS], w0[4 * KS], w0[5 * KS]};
+                conv_gemm_wino43<REM>(acc, xw - 2 * LDS_S + kk * 4, w0, pre_w, rout, xs + (HALO + rp - 2) * LDS_S + kk * 4, (gv4f_ptr)(wblk + W_OFF) + wave * 64 + lane);
+            } else if constexpr (CARRY) {
                 const v4f pre_w[4] = {pc0, pc1, pc2, pc3};
-                gemm(pre_w);
+                conv_gemm_wino(acc, xw - 2 * LDS_S + kk * 4, w_w, pre_w);
             } else {
                 gv4f_ptr w0 = w_w;
                 const v4f pre_w[4] = {w0[0], w0[(size_t)KGC * (KGC * 64)], w0[(size_t)2 * KGC * (KGC * 64)], w0[(size_t)3 * KGC * (KGC * 64)]};
-                gemm(pre_w);
+                conv_gemm_wino(acc, xw - 2 * LDS_S + kk * 4, w_w, pre_w);
             }
             STAMP(sb + 1);
             asm volatile("" : "+v"(wp));       // keeps everything derived from it (addresses, masks) out of the GEMM's live set
@@ -533,15 +544,41 @@ next_row:                                                   // (PERSIST only: ba
                 const v2f r = {relu1(y[0]), relu1(y[1])};
                 return __builtin_elementwise_fma(r, s, t);
             };
+            if constexpr (W43) {
+                // F(4,3): Y0 = M0 + s1 + s2, Y1 = d1 + 2 d2, Y2 = s1 + 4 s2, Y3 = d1 + 8 d2 + M5 with s1, d1 = M1 +- M2 and s2, d2 = M3 +- M4;
+                // output o of tile m is column wp + 8 m + 2 o: out[2 m + (o >> 1)][o & 1] of the six-tile layout everything below works on
+                v2f c2 = {2.f, 2.f}, c4 = {4.f, 4.f}, c8 = {8.f, 8.f};
+                asm volatile("" : "+v"(c2), "+v"(c4), "+v"(c8));
 #pragma unroll
-            for (int m = 0; m < TW; ++m) {
-                const v2f y0l = half(acc[m][0], 0) + half(acc[m][1], 0) + half(acc[m][2], 0), y0h = half(acc[m][0], 1) + half(acc[m][1], 1) + half(acc[m][2], 1);
-                // (a - b as fma(b, -1, a): exact, and a packed instruction -- hipcc splits a subtraction of pairs into two scalar ones)
-                const v2f y1l = __builtin_elementwise_fma(half(acc[m][3], 0), neg1, __builtin_elementwise_fma(half(acc[m][2], 0), neg1, half(acc[m][1], 0)));
-                const v2f y1h = __builtin_elementwise_fma(half(acc[m][3], 1), neg1, __builtin_elementwise_fma(half(acc[m][2], 1), neg1, half(acc[m][1], 1)));
-                const v2f o0l = act(y0l, sc_lo, sh_lo), o0h = act(y0h, sc_hi, sh_hi), o1l = act(y1l, sc_lo, sh_lo), o1h = act(y1h, sc_hi, sh_hi);
-                out[m][0] = (v4f){o0l[0], o0l[1], o0h[0], o0h[1]};
-                out[m][1] = (v4f){o1l[0], o1l[1], o1h[0], o1h[1]};
+                for (int m = 0; m < MW43; ++m) {
+                    v2f y[4][2];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const v2f M0 = half(acc[m][0], h), M1 = half(acc[m][1], h), M2 = half(acc[m][2], h), M3 = half(acc[m][3], h), M4 = half(acc[m][4], h),
+                                  M5 = half(acc[m][5], h);
+                        const v2f s1 = M1 + M2, d1 = __builtin_elementwise_fma(M2, neg1, M1), s2 = M3 + M4, d2 = __builtin_elementwise_fma(M4, neg1, M3);
+                        y[0][h] = M0 + s1 + s2;
+                        y[1][h] = __builtin_elementwise_fma(d2, c2, d1);
+                        y[2][h] = __builtin_elementwise_fma(s2, c4, s1);
+                        y[3][h] = __builtin_elementwise_fma(d2, c8, d1) + M5;
+                    }
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) {
+                        const v2f lo = act(y[o][0], sc_lo, sh_lo), hi = act(y[o][1], sc_hi, sh_hi);
+                        out[2 * m + (o >> 1)][o & 1] = (v4f){lo[0], lo[1], hi[0], hi[1]};
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int m = 0; m < TW; ++m) {
+                    const v2f y0l = half(acc[m][0], 0) + half(acc[m][1], 0) + half(acc[m][2], 0), y0h = half(acc[m][0], 1) + half(acc[m][1], 1) + half(acc[m][2], 1);
+                    // (a - b as fma(b, -1, a): exact, and a packed instruction -- hipcc splits a subtraction of pairs into two scalar ones)
+                    const v2f y1l = __builtin_elementwise_fma(half(acc[m][3], 0), neg1, __builtin_elementwise_fma(half(acc[m][2], 0), neg1, half(acc[m][1], 0)));
+                    const v2f y1h = __builtin_elementwise_fma(half(acc[m][3], 1), neg1, __builtin_elementwise_fma(half(acc[m][2], 1), neg1, half(acc[m][1], 1)));
+                    const v2f o0l = act(y0l, sc_lo, sh_lo), o0h = act(y0h, sc_hi, sh_hi), o1l = act(y1l, sc_lo, sh_lo), o1h = act(y1h, sc_hi, sh_hi);
+                    out[m][0] = (v4f){o0l[0], o0l[1], o0h[0], o0h[1]};
+                    out[m][1] = (v4f){o1l[0], o1l[1], o1h[0], o1h[1]};
+                }
             }
             if constexpr (REM) {                            // the remainder tile is in direct form: relu(acc + b) sc + sh
                 const v2f rl = act(half(rout, 0), sc_lo, sh_lo), rh = act(half(rout, 1), sc_hi, sh_hi);
@@ -858,7 +895,8 @@ int segment_fold_workgroups(int n_sites, int max_wgs) {
     return w < need ? w : need;
 }
 
-// a one-unit read in the fold, persistent or row form: six Winograd tiles per lane + the direct remainder tile, six, seven, or direct
+// a one-unit read in the fold, persistent or row form: the six-tile strip in F(4,3) form + the direct remainder tile, the strip alone,
+// seven F(2,3) tiles, or direct
 template <bool PERSIST, bool FOLD>
 static void launch_one_unit(const SegmentArgs& a, bool six, bool rem, dim3 grid, hipStream_t s) {
     const dim3 blk(SEG_THREADS);
@@ -875,8 +913,8 @@ void launch_segment(const SegmentArgs& a0, int n_sites, int max_wgs, hipStream_t
     const bool split = a.units == 2;
     if (!split) { a.units = 1; a.Lw = a.L; a.y_out = a.y; }   // (callers that never heard of units: one unit, the whole window, in place)
     const int units = split ? 2 : 1;
-    // one-unit Winograd reads: up to 190 columns six Winograd tiles per lane, 191 .. 206 the same + the direct remainder tile, 207 and
-    // 208 seven tiles
+    // one-unit Winograd reads: up to 190 columns the six-tile strip as three F(4,3) tiles per lane, 191 .. 206 the same + the direct
+    // remainder tile, 207 and 208 seven F(2,3) tiles
     const bool six = !split && a.L <= MPOS_SHORT, rem = !split && !six && a.L <= MPOS_SHORT + 16;
     if (a.fold) {                                           // (callers ask for it only where it applies: dan_capi.cpp)
         a.n_sites = n_sites;

@@ -62,9 +62,10 @@ typedef struct dan_config {
     int32_t chunk_sites;      /* sites per conv-stack chunk (0 = largest power of two whose y + h fit 48 GB and a third of the
                                * device memory that is free at dan_create) */
     int32_t conv_algo;        /* fp32 path, form of the 3-tap convolutions after the first layer: 1 = direct implicit
-                               * GEMM; 2 = Winograd F(2,3) over the dilated positions (needs every such layer to
-                               * have dilation 2: 4 exact-fp32 GEMMs per 2 outputs instead of 6); 0 = Winograd
-                               * where it applies, else direct                                     */
+                               * GEMM; 2 = Winograd over the dilated positions (needs every such layer to have
+                               * dilation 2): F(4,3), 6 exact-fp32 GEMMs per 4 outputs instead of 12, for windows
+                               * of up to 206 columns, F(2,3), 4 per 2 instead of 6, above; 0 = Winograd where it
+                               * applies, else direct                                              */
     int32_t skip_empty_rows;  /* 1 = compute the all-padding rows of a pileup (reads, q-scores and strand bytes all zero:
                                * the rows below the site's coverage) once per site and let every other such row use
                                * that result -- their encoded input is identical, so every output is bit-identical to
@@ -134,7 +135,8 @@ int dan_wait(dan_t* h, int64_t ticket);
 /* Parity-test taps (debug export).  dan_set_tap(): keep a copy of the activations after conv layer
  * `layer` (1..layers; 0 = the encoded 48-channel input; -1 = off) of the LAST chunk processed.
  * dan_read_buffer(): copy an internal fp32 buffer to the host: "tap" [sites][R][L][128],
- * "feature" [B][feature_stride], "hidden0" [B][fc0], "hidden1" [B][fc1]; returns the number of floats
+ * "feature" [B][feature_stride], "hidden0" [B][fc0], "hidden1" [B][fc1], "wl" [layers][layer_stride] (the fp32
+ * family's packed weight blocks; dan_query "layer_stride", "wino_f23_offset", "wino_f43_offset"); returns the number of floats
  * copied (<= capacity) or a negative status.  dan_query(): integer facts by name ("feature_width",
  * "feature_stride", "chunk_sites", "max_batch", "cpad", "tap_sites"). */
 /* (With skip_empty_rows = 1 the tap and "y" rows of skipped empty pileup rows are not written: read their source row.) */

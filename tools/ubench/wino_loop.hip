@@ -1,5 +1,7 @@
 // Microbenchmark of the two conv GEMM cores of dan_kernels.hip in isolation (LDS-resident read, weights from L2):
-// SIMD-level cycles per MFMA of conv_gemm (direct, 3 taps) and conv_gemm_wino, at 1 and 2 waves per SIMD.
+// SIMD-level cycles per MFMA of conv_gemm (direct, 3 taps), conv_gemm_wino (F(2,3), seven tiles) and conv_gemm_wino43 (F(4,3), three
+// tiles, with and without the direct remainder tile), at 1 and 2 waves per SIMD.  What decides between the two Winograd forms is
+// cycles per MFMA x conv MFMAs per k-step and wave: 27 for six F(2,3) tiles + the remainder tile, 21 for three F(4,3) tiles + it.
 //   hipcc -O3 --offload-arch=gfx950 tools/ubench/wino_loop.hip -o tools/ubench/wino_loop.bin
 #include "../../dl4vc_amd/csrc/dan_kernels.hip"
 #include <cstdio>
@@ -81,6 +83,21 @@ __global__ __launch_bounds__(SEG_THREADS, 2) void k(const float* wl, float* out,
         else for (int it = 0; it < iters; ++it) conv_gemm_wino2<3>(acc, xrow, w_w, 4);
         t1 = __builtin_amdgcn_s_memtime();
         for (int m = 0; m < 4; ++m) for (int q = 0; q < 4; ++q) for (int n = 0; n < 2; ++n) s += acc[m][q][n][0] + acc[m][q][n][1] + acc[m][q][n][2] + acc[m][q][n][3];
+    } else if (WHICH == 3 || WHICH == 4) {
+        constexpr bool REM = WHICH == 3;
+        const int wP0 = wino_base<MW_SHORT>(lane);
+        gv4f_ptr w_w = (gv4f_ptr)(wl + W43_OFF) + wave * 64 + lane;
+        v4f acc[MW43][6], pre[6], racc = splat(0.f);
+        for (int m = 0; m < MW43; ++m) for (int q = 0; q < 6; ++q) acc[m][q] = splat(0.f);
+        for (int q = 0; q < 6; ++q) pre[q] = w_w[(size_t)q * KGC * (KGC * 64)];
+        const float* xrow = xs + (HALO + wP0 - 2) * LDS_S + kk * 4;
+        const float* xr = xs + (HALO + MPOS_SHORT + (lane & 15) - 2) * LDS_S + kk * 4;
+        gv4f_ptr w_d = (gv4f_ptr)(wl + W_OFF) + wave * 64 + lane;
+        t0 = __builtin_amdgcn_s_memtime();
+        for (int it = 0; it < iters; ++it) conv_gemm_wino43<REM>(acc, xrow, w_w, pre, racc, xr, w_d);
+        t1 = __builtin_amdgcn_s_memtime();
+        for (int m = 0; m < MW43; ++m) for (int q = 0; q < 6; ++q) s += acc[m][q][0] + acc[m][q][1] + acc[m][q][2] + acc[m][q][3];
+        s += racc[0] + racc[1] + racc[2] + racc[3];
     } else {
         const int wP0 = wino_base(lane);
         gv4f_ptr w_w = (gv4f_ptr)(wl + WW_OFF) + wave * 64 + lane;
@@ -133,6 +150,9 @@ int main() {
         run<0>("direct 3-tap conv_gemm", threads, d_wl, threads == 512 ? 2496.0 : 2.0 * 1344.0);
         run<1>("conv_gemm_wino", threads, d_wl, 1792.0);
         if (threads == 512) run<2>("wino, 2 channel tiles per wave", threads, d_wl, 1792.0);
+        // F(4,3): 2 waves x (3 tiles x 6 components [+ 3 remainder taps]) x 4 x 8 kg
+        run<3>("conv_gemm_wino43 + remainder", threads, d_wl, 2.0 * 21 * 32);
+        run<4>("conv_gemm_wino43", threads, d_wl, 2.0 * 18 * 32);
     }
     return 0;
 }
