@@ -17,14 +17,14 @@ constexpr int WG_CH = 104;                // positions per staged chunk (half a 
 constexpr int TRAIN_PARTIAL_WGS = 256;    // workgroups of a weight-gradient launch = slices of the split-K partial buffer
 
 // ---- T1: one layer-shaped step on the LDS-resident read -------------------------------------------------------------------
-//   image  = load(mode)                                   encode | rows src1 [affine with src2] [masked by src2 > 0] [+ pool]
+//   image  = load                                         rows src1 [affine with src2] [masked by src2 > 0] [+ pool]
 //   acc    = w1 ? GEMM(image; taps, kg, dil) : image
 //            [+ W3 * (src4 > 0 ? src3 : 0)]               (half-read 3-tap launches only)
 //   out1   = [relu](acc + bias1 + add1 + add2 + addb)     rows, CPAD stride;  stats[row] = (sum out1, sum out1 * aux)
 //   out2   = relu(W2 * out1 + bias2)                      the 128 -> 32 bottleneck (rows, HPAD stride), optional
 struct RowArgs {
     int R, L;
-    int mode;                               // 0 = encode from the uint8 planes, 1 = rows
+    int mode = 1;                           // (unread: the image is always rows; layer 1 runs from tables, launch_l0_train_forward)
     const uint8_t *reads, *qual, *strand, *ref, *ref_mask, *var_mask;
     const float *emb, *pe;
     const float* src1; int s1_stride;       // floats per position: CPAD or HPAD
@@ -69,8 +69,8 @@ struct WgradArgs {
     const float* a2;                        // optional second tensor for the affine / mask (same stride)
     const float* a_coef;                    // [3][CPAD] as RowArgs::coef, or nullptr
     int a_mask;                             // A = (a2 > 0) ? A : 0
-    int b_mode;                             // (1 = rows; the encode form is gone: layer 1 goes through launch_l0_backward)
-    const uint8_t *reads, *qual, *strand, *ref, *ref_mask, *var_mask;
+    int b_mode = 1;                         // (unread: B is always rows)
+    const uint8_t *reads, *qual, *strand, *ref, *ref_mask, *var_mask;   // the token planes: launch_l0_backward only
     const float *emb, *pe;
     const float* b1;                        // B rows, CPAD stride
     const float* b_coef;                    // [3][CPAD]: B = A[c] * b1 + C[c]   (nullptr: B = b1)
@@ -80,7 +80,9 @@ struct WgradArgs {
     float* partial;                         // [wgs][taps][o_tiles*16][c_tiles*16]
     float* bias_partial;                    // [wgs][o_tiles*16]
 };
-int launch_train_wgrad(const WgradArgs& a, hipStream_t s);     // returns the number of workgroups (partial slices) used
+// returns the number of workgroups (partial slices) used; 0, with nothing launched, for a shape no kernel form serves: the forms are
+// 1 tap without a_coef / b_pool (A 128 or 32 wide), and 3 taps on 128 x 128 channels
+int launch_train_wgrad(const WgradArgs& a, hipStream_t s);
 // G[(o * n_in + i) * taps + t] = sum_wg partial[wg][t][o][cmap ? cmap[i] : i];  gb[o] = sum_wg bias_partial[wg][o]
 void launch_wgrad_reduce(const float* partial, const float* bias_partial, int wgs, int taps, int o_pad, int c_pad, int n_out,
                          int n_in, const int* cmap, float* g_w, float* g_b, hipStream_t s);
@@ -104,13 +106,11 @@ void launch_pack_frag(float* dst, const float* src, int taps, int kg, int tiles,
                       long long st, int flip, const int* omap, const int* cmap, hipStream_t s);
 // U[(o * n_in + c)][4] = Winograd F(2,3) transform of the 3-tap kernel at src[o*so + c*sc + t] (flip: taps reversed)
 void launch_wino_u(float* dst, const float* src, int n_out, int n_in, long long so, long long sc, int flip, hipStream_t s);
-// highway compression weights Wc[o][c][p] (torch (H,H,1,L)) -> the highway kernel's fragment order [2L][2][64][4]
-void launch_pack_wc(float* dst, const float* src, int H, int L, hipStream_t s);
-// WcT[p][c][o] = Wc[o][c][p] padded to HPAD x HPAD: the operand of launch_highway_bwd
-void launch_pack_wct(float* dst, const float* src, int H, int L, hipStream_t s);
-void launch_pad_copy(float* dst, const float* src, int n, int n_pad, hipStream_t s);
-// one launch for a table of the four job kinds above (type 0 pack_frag: i = taps, kg, tiles, n_out, n_in, flip; l = so, sc, st;
-// 1 pad_copy: i = n, n_pad; 2 pack_wc / 3 pack_wct: i = H, L); first_block = the job's first block of the launch
+// one launch for a table of jobs of four kinds; first_block = the job's first block of the launch
+//   0 pack_frag as above: i = taps, kg, tiles, n_out, n_in, flip; l = so, sc, st
+//   1 pad_copy: dst[k] = k < n ? src[k] : 0 for k < n_pad; i = n, n_pad
+//   2 pack_wc:  highway compression weights Wc[o][c][p] (torch (H,H,1,L)) -> the highway kernel's fragment order [2L][2][64][4]; i = H, L
+//   3 pack_wct: WcT[p][c][o] = Wc[o][c][p] padded to HPAD x HPAD, the operand of launch_highway_dh; i = H, L
 struct PackJob { int type, first_block; float* dst; const float* src; int i[6]; long long l[3]; const int *omap, *cmap; };
 int pack_job_blocks(const PackJob& q);
 void launch_pack_jobs(const PackJob* jobs_on_device, int n_jobs, int n_blocks, hipStream_t s);
@@ -118,28 +118,15 @@ void launch_pack_jobs(const PackJob* jobs_on_device, int n_jobs, int n_blocks, h
 // ---- pools / highway ---------------------------------------------------------------------------------------------------------------
 // g[site][r][p][c] = dfeat[site][C*L + c*L + p] / R + (r == first argmax_r y[.][r][p][c]) * dfeat[site][c*L + p]
 void launch_final_pool_bwd(const float* y, const float* dfeat, long long fs, float* g, int n_sites, int R, int L, int C, hipStream_t s);
-// dh[layer][row][p][c] = sum_o dhw[row][layer][o] * Wc[layer][o][c][p], dhw = dfeat_hw * (feat_hw > 0)
-void launch_highway_bwd(const float* dfeat, const float* feat, long long fs, int feat_off, const float* wc, long long wc_layer,
-                        float* dh, long long dh_layer, int n_sites, int R, int L, int H, int layers, hipStream_t s);
-// dhw[layer][row][HPAD] = dfeat_hw * (feat_hw > 0): with it both highway products are plain GEMMs (launch_gemm):
-//   dh[layer][row][e] = dhw[row][:] . WcT[e][:]            (M = rows, N = L*HPAD, K = HPAD; both K-contiguous)
-//   gWcT[o][e]        = sum_rows dhw[row][o] h[row][e]      (M = HPAD, N = L*HPAD, K = rows; both K-slow, split-K)
+// dhw[layer][row][HPAD] = dfeat_hw * (feat_hw > 0): the operand of both highway products below
 void launch_highway_dhw(const float* dfeat, const float* feat, long long fs, int feat_off, float* dhw, int n_sites, int R, int H,
                         int layers, hipStream_t s);
-void launch_highway_wc_transpose(const float* t, float* g_wc, int L, int H, hipStream_t s);
 // the highway compression's backward, all layers per launch: dh[l][row][p][c] = sum_o dhw[l][row][o] WcT[l][p][c][o];
 // gWc[l] (torch layout (o, c, p) at g_base + w_off[l]) = sum_row dhw[l][row][o] h[l][row][p][c]
 void launch_highway_dh(const float* dhw, const float* wct, float* dh, int n_rows, int L, int layers, hipStream_t s);
 void launch_highway_gwc(const float* dhw, const float* h, float* g_base, const long long* w_off, int n_rows, int L, int H, int layers, hipStream_t s);
 void launch_highway_bias_grad_all(const float* dfeat, const float* feat, long long fs, int feat_off, float* partial /*[layers][64][HPAD]*/,
                                   float* g_base, const long long* g_off_on_device, int n_sites, int R, int H, int layers, hipStream_t s);
-void launch_highway_bias_grad(const float* dfeat, const float* feat, long long fs, int feat_off, float* partial /*[64][HPAD]*/,
-                              float* g_bc, int n_sites, int R, int H, hipStream_t s);
-// (VALU forms, kept as the reference implementation of the two products)
-// gWc[layer][o][c][p] = sum_rows dhw * h[layer][row][p][c];  gbc[layer][o] = sum_rows dhw   (split over row blocks -> partials)
-void launch_highway_wgrad(const float* dfeat, const float* feat, long long fs, int feat_off, const float* h, long long h_layer,
-                          float* partial, float* g_wc, long long wc_layer, float* g_bc, int n_sites, int R, int L, int H, int layers,
-                          int layer_stride_b, hipStream_t s);
 // Layer 1's backward by bins (dan_train.hip): conv1's weight and bias gradients and the embedding gradient from ONE pass over
 // dz_1 = the transform (a1, a2, a_coef, a_mask) of WgradArgs -- no encode-form GEMM, no data-gradient launch, no embedding launches.
 // a: R, L, n_rows, a1, a2, a_coef, a_mask, the six token planes, emb, pe, partial (TRAIN_PARTIAL_WGS slices of 3 CPAD CPAD floats);

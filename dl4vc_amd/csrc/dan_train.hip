@@ -687,9 +687,8 @@ bool train_row_fuses_second_product(const RowArgs& a) {
 // Returns the number of `stats` entries the launch writes (reads for the whole-read form, half-read units for the half-read form,
 // 64-position tiles for the pointwise one), or TRAIN_ROW_ERR_* without launching.
 int launch_train_row(const RowArgs& a, int n_rows, hipStream_t s, int stat_cap) {
-    if (a.mode == 0) return TRAIN_ROW_ERR_FORM;                  // (the encode form is gone: layer 1 runs from tables, launch_l0_train_forward)
     const bool pointwise = !a.pool_in && !a.wino && (a.w1 == nullptr || a.taps == 1);
-    static const int n_cus_h = [] {
+    static const int n_cus = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
         return n;
@@ -710,22 +709,17 @@ int launch_train_row(const RowArgs& a, int n_rows, hipStream_t s, int stat_cap) 
     if (half_units) {
         // as many workgroups as give every one the same number of units (2 000 units at 10 sites: 500 workgroups of 4, not 512 of
         // which 464 run a fourth round at 94 % idle), an even count (the half a workgroup takes alternates with its round)
-        const int n_units = 2 * n_rows, rounds = (n_units + 2 * n_cus_h - 1) / (2 * n_cus_h);
+        const int n_units = 2 * n_rows, rounds = (n_units + 2 * n_cus - 1) / (2 * n_cus);
         const int wgs = std::min(n_units, ((n_units + rounds - 1) / rounds + 1) & ~1);
         // the second workgroup of a CU starts half a unit late (three s_sleep 127: ~10 us) when there is a second one per CU
         const dim3 grid((unsigned)wgs), blk(RH_THREADS);
-        const int st = wgs > n_cus_h ? 3 : 0;
+        const int st = wgs > n_cus ? 3 : 0;
         if (f2) hipLaunchKernelGGL((train_rowh_kernel<true, false, true>), grid, blk, 0, s, a, n_rows, st);
         else if (src2) hipLaunchKernelGGL((train_rowh_kernel<true, false, false>), grid, blk, 0, s, a, n_rows, st);
         else if (pool) hipLaunchKernelGGL((train_rowh_kernel<false, true, false>), grid, blk, 0, s, a, n_rows, st);
         else hipLaunchKernelGGL((train_rowh_kernel<false, false, false>), grid, blk, 0, s, a, n_rows, st);
         return n_units;
     }
-    static const int n_cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-        return n;
-    }();
     hipLaunchKernelGGL(train_row_kernel, dim3((unsigned)std::min(n_rows, n_cus)), dim3(SEG_THREADS), 0, s, a, n_rows);
     return n_rows;
 }
@@ -1258,10 +1252,9 @@ int launch_train_wgrad(const WgradArgs& a, hipStream_t s) {
         hipLaunchKernelGGL((train_wgrad3_kernel<KGC>), grid, blk, 0, s, a);                    // the next chunk in flight under the MFMAs
         return wgs;
     }
-    if (a.o_tiles <= 2 && a.taps == 1) hipLaunchKernelGGL((train_wgrad_kernel<1, false, 1>), grid, blk, 0, s, a);   // A 32 wide: both its tiles per wave
-    else if (a.taps == 1) hipLaunchKernelGGL((train_wgrad_kernel<1, true, KGC>), grid, blk, 0, s, a);
-    else if (a.c_tiles <= KG0) hipLaunchKernelGGL((train_wgrad_kernel<3, true, KG0>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((train_wgrad_kernel<3, true, KGC>), grid, blk, 0, s, a);
+    // the generic form is instantiated for the one shape left to it: the 3-tap gradient of a pooled layer, 128 x 128 channels
+    if (a.taps != 3 || a.o_tiles != KGC || a.c_tiles != KGC) return 0;
+    hipLaunchKernelGGL((train_wgrad_kernel<3, true, KGC>), grid, blk, 0, s, a);
     return wgs;
 }
 
@@ -1478,18 +1471,12 @@ __device__ __forceinline__ void pack_wc_body(int idx, float* __restrict__ dst, c
     const int o = 16 * n + (lane & 15), c = 16 * (g & 1) + 4 * (lane >> 4) + sidx, p = g >> 1;
     dst[idx] = (o < H && c < H) ? src[((size_t)o * H + c) * L + p] : 0.f;
 }
-__global__ __launch_bounds__(256) void pack_wc_kernel(float* __restrict__ dst, const float* __restrict__ src, int H, int L) {
-    pack_wc_body(blockIdx.x * 256 + threadIdx.x, dst, src, H, L);
-}
 
 // WcT[p][c][o] = Wc[o][c][p], zero-padded to HPAD x HPAD (the highway backward reads 32 consecutive o per (p, c))
 __device__ __forceinline__ void pack_wct_body(int idx, float* __restrict__ dst, const float* __restrict__ src, int H, int L) {
     if (idx >= L * HPAD * HPAD) return;
     const int o = idx & 31, c = (idx >> 5) & 31, p = idx >> 10;
     dst[idx] = (o < H && c < H) ? src[((size_t)o * H + c) * L + p] : 0.f;
-}
-__global__ __launch_bounds__(256) void pack_wct_kernel(float* __restrict__ dst, const float* __restrict__ src, int H, int L) {
-    pack_wct_body(blockIdx.x * 256 + threadIdx.x, dst, src, H, L);
 }
 
 // Every re-packing of a step in ONE launch: the job table is fixed once the trainer is finalized (pointers into the flat
@@ -1519,24 +1506,6 @@ int pack_job_blocks(const PackJob& q) {
     default: n = (long long)q.i[1] * HPAD * HPAD; break;
     }
     return (int)((n + 255) / 256);
-}
-
-void launch_pack_wct(float* dst, const float* src, int H, int L, hipStream_t s) {
-    hipLaunchKernelGGL(pack_wct_kernel, dim3((L * HPAD * HPAD + 255) / 256), dim3(256), 0, s, dst, src, H, L);
-}
-
-// dst[i] = i < n ? src[i] : 0 for i < n_pad   (biases padded to the kernels' channel capacity)
-__global__ __launch_bounds__(256) void pad_copy_kernel(float* __restrict__ dst, const float* __restrict__ src, int n, int n_pad) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n_pad) dst[i] = i < n ? src[i] : 0.f;
-}
-
-void launch_pad_copy(float* dst, const float* src, int n, int n_pad, hipStream_t s) {
-    hipLaunchKernelGGL(pad_copy_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, s, dst, src, n, n_pad);
-}
-
-void launch_pack_wc(float* dst, const float* src, int H, int L, hipStream_t s) {
-    hipLaunchKernelGGL(pack_wc_kernel, dim3((2 * L * 2 * 256 + 255) / 256), dim3(256), 0, s, dst, src, H, L);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1617,18 +1586,6 @@ void launch_highway_dhw(const float* dfeat, const float* feat, long long fs, int
                         int layers, hipStream_t s) {
     const int n_rows = n_sites * R;
     hipLaunchKernelGGL(highway_dhw_kernel, dim3((n_rows * HPAD + 255) / 256, layers), dim3(256), 0, s, dfeat, feat, fs, feat_off, dhw, n_rows, R, H);
-}
-
-// gWc[o][c][p] = t[o][p*HPAD + c]  (the wgrad GEMM's output is [o][e = (p, c)]: the torch layout wants (o, c, p))
-__global__ __launch_bounds__(256) void highway_wc_transpose_kernel(const float* __restrict__ t, float* __restrict__ g_wc, int L, int H) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= H * H * L) return;
-    const int p = idx % L, c = (idx / L) % H, o = idx / (L * H);
-    g_wc[idx] = t[(size_t)o * L * HPAD + p * HPAD + c];
-}
-
-void launch_highway_wc_transpose(const float* t, float* g_wc, int L, int H, hipStream_t s) {
-    hipLaunchKernelGGL(highway_wc_transpose_kernel, dim3((H * H * L + 255) / 256), dim3(256), 0, s, t, g_wc, L, H);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1781,78 +1738,6 @@ void launch_highway_gwc(const float* dhw, const float* h, float* g_base, const l
     hipLaunchKernelGGL(highway_gwc_kernel, dim3((L + 7) / 8, layers), dim3(512), 0, s, dhw, h, g_base, w_off, n_rows, L, H);
 }
 
-constexpr int HB_ROWS = 8;
-__global__ __launch_bounds__(256) void highway_bwd_kernel(const float* __restrict__ dfeat, const float* __restrict__ feat, long long fs,
-                                                          int feat_off, const float* __restrict__ wc, long long wc_layer,
-                                                          float* __restrict__ dh, long long dh_layer, int n_rows, int R, int L, int H) {
-    __shared__ float d[HB_ROWS][HPAD];
-    const int layer = blockIdx.y, row0 = blockIdx.x * HB_ROWS, tid = threadIdx.x;
-    {
-        const int rr = tid >> 5, o = tid & 31, row = row0 + rr;
-        d[rr][o] = (row < n_rows && o < H) ? dhw_of(dfeat, feat, fs, feat_off, layer, H, R, row, o) : 0.f;
-    }
-    __syncthreads();
-    const float* w = wc + (size_t)layer * wc_layer;             // transposed copy WcT[p][c][o] (launch_pack_wct): 128-byte runs per thread
-    for (int e = tid; e < L * HPAD; e += 256) {
-        float acc[HB_ROWS];
-#pragma unroll
-        for (int rr = 0; rr < HB_ROWS; ++rr) acc[rr] = 0.f;
-        const v4f* wv4 = (const v4f*)(w + (size_t)e * HPAD);
-#pragma unroll
-        for (int o4 = 0; o4 < HPAD / 4; ++o4) {
-            const v4f wv = wv4[o4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int rr = 0; rr < HB_ROWS; ++rr) acc[rr] = fmaf(d[rr][o4 * 4 + j], wv[j], acc[rr]);
-        }
-#pragma unroll
-        for (int rr = 0; rr < HB_ROWS; ++rr)
-            if (row0 + rr < n_rows) dh[(size_t)layer * dh_layer + (size_t)(row0 + rr) * L * HPAD + e] = acc[rr];
-    }
-}
-
-void launch_highway_bwd(const float* dfeat, const float* feat, long long fs, int feat_off, const float* wc, long long wc_layer,
-                        float* dh, long long dh_layer, int n_sites, int R, int L, int H, int layers, hipStream_t s) {
-    const int n_rows = n_sites * R;
-    hipLaunchKernelGGL(highway_bwd_kernel, dim3((n_rows + HB_ROWS - 1) / HB_ROWS, layers), dim3(256), 0, s, dfeat, feat, fs, feat_off, wc,
-                       wc_layer, dh, dh_layer, n_rows, R, L, H);
-}
-
-// gWc[o][c][p] partial over a block of rows: thread = one (p, c) element, 32 outputs in registers
-constexpr int HW_SPLITS = 8;
-__global__ __launch_bounds__(256) void highway_wgrad_kernel(const float* __restrict__ dfeat, const float* __restrict__ feat, long long fs,
-                                                            int feat_off, int layer, const float* __restrict__ h, float* __restrict__ partial,
-                                                            int n_rows, int R, int L, int H) {
-    __shared__ float d[32][HPAD];
-    const int tid = threadIdx.x, split = blockIdx.y;
-    const int e = blockIdx.x * 256 + tid, n_e = L * HPAD;
-    const int per = (n_rows + HW_SPLITS - 1) / HW_SPLITS, lo = split * per, hi = min(n_rows, lo + per);
-    float acc[HPAD];
-#pragma unroll
-    for (int o = 0; o < HPAD; ++o) acc[o] = 0.f;
-    for (int r0 = lo; r0 < hi; r0 += 32) {
-        __syncthreads();
-        for (int i = tid; i < 32 * HPAD; i += 256) {
-            const int rr = i >> 5, o = i & 31, row = r0 + rr;
-            d[rr][o] = (row < hi && o < H) ? dhw_of(dfeat, feat, fs, feat_off, layer, H, R, row, o) : 0.f;
-        }
-        __syncthreads();
-        if (e < n_e) {
-            const int nr = min(32, hi - r0);
-            for (int rr = 0; rr < nr; ++rr) {
-                const float hv = h[(size_t)(r0 + rr) * n_e + e];
-#pragma unroll
-                for (int o = 0; o < HPAD; ++o) acc[o] = fmaf(d[rr][o], hv, acc[o]);
-            }
-        }
-    }
-    if (e < n_e) {
-#pragma unroll
-        for (int o = 0; o < HPAD; ++o) partial[((size_t)split * HPAD + o) * n_e + e] = acc[o];
-    }
-}
-
 // gbc[o] = sum over rows of dhw[row][o]: one block per split of the rows, fixed-order tree inside, splits summed by the reduce
 __global__ __launch_bounds__(256) void highway_bias_partial_kernel(const float* __restrict__ dfeat, const float* __restrict__ feat, long long fs,
                                                                   int feat_off, float* __restrict__ bias_partial, int n_rows, int R, int H) {
@@ -1884,24 +1769,6 @@ __global__ __launch_bounds__(64) void highway_bias_reduce_kernel(const float* __
     dst[o] = ordered_sum<float>(n_blocks, [&](int b) { return bp[b * HPAD + o]; });
 }
 
-__global__ __launch_bounds__(256) void highway_wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ g_wc, int L, int H) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;             // over (o, c, p) of the torch layout (H, H, 1, L)
-    if (idx >= H * H * L) return;
-    const int p = idx % L, c = (idx / L) % H, o = idx / (L * H);
-    const int n_e = L * HPAD, e = p * HPAD + c;
-    float sum = 0.f;
-    for (int sp = 0; sp < HW_SPLITS; ++sp) sum += partial[((size_t)sp * HPAD + o) * n_e + e];
-    g_wc[idx] = sum;
-}
-
-// gbc[o] = sum over rows of dhw[row][o] for ONE layer (feat_off points at that layer's block of the feature row)
-void launch_highway_bias_grad(const float* dfeat, const float* feat, long long fs, int feat_off, float* partial, float* g_bc,
-                              int n_sites, int R, int H, hipStream_t s) {
-    constexpr int BIAS_BLOCKS = 64;
-    const int n_rows = n_sites * R;
-    hipLaunchKernelGGL(highway_bias_partial_kernel, dim3(BIAS_BLOCKS), dim3(256), 0, s, dfeat, feat, fs, feat_off, partial, n_rows, R, H);
-    hipLaunchKernelGGL(highway_bias_reduce_kernel, dim3(1), dim3(64), 0, s, partial, BIAS_BLOCKS, g_bc, (const long long*)nullptr, H);
-}
 // every layer at once: partial [layers][64][HPAD]; the gradient of layer l's bias goes to g_base + g_off[l] (g_off on the device)
 void launch_highway_bias_grad_all(const float* dfeat, const float* feat, long long fs, int feat_off, float* partial, float* g_base,
                                   const long long* g_off, int n_sites, int R, int H, int layers, hipStream_t s) {
@@ -1909,23 +1776,6 @@ void launch_highway_bias_grad_all(const float* dfeat, const float* feat, long lo
     const int n_rows = n_sites * R;
     hipLaunchKernelGGL(highway_bias_partial_kernel, dim3(BIAS_BLOCKS, (unsigned)layers), dim3(256), 0, s, dfeat, feat, fs, feat_off, partial, n_rows, R, H);
     hipLaunchKernelGGL(highway_bias_reduce_kernel, dim3((unsigned)layers), dim3(64), 0, s, partial, BIAS_BLOCKS, g_base, g_off, H);
-}
-
-void launch_highway_wgrad(const float* dfeat, const float* feat, long long fs, int feat_off, const float* h, long long h_layer,
-                          float* partial, float* g_wc, long long wc_layer, float* g_bc, int n_sites, int R, int L, int H, int layers,
-                          int layer_stride_b, hipStream_t s) {
-    const int n_rows = n_sites * R, n_e = L * HPAD;
-    for (int l = 0; l < layers; ++l) {
-        hipLaunchKernelGGL(highway_wgrad_kernel, dim3((n_e + 255) / 256, HW_SPLITS), dim3(256), 0, s, dfeat, feat, fs, feat_off, l,
-                           h + (size_t)l * h_layer, partial, n_rows, R, L, H);
-        hipLaunchKernelGGL(highway_wgrad_reduce_kernel, dim3((H * H * L + 255) / 256), dim3(256), 0, s, partial, g_wc + (size_t)l * wc_layer, L, H);
-    }
-    // (one layer per call: the compression layers' gradient tensors are not contiguous in the flat buffer)
-    constexpr int BIAS_BLOCKS = 64;
-    float* bias_partial = partial + (size_t)HW_SPLITS * HPAD * n_e;
-    hipLaunchKernelGGL(highway_bias_partial_kernel, dim3(BIAS_BLOCKS), dim3(256), 0, s, dfeat, feat, fs, feat_off, bias_partial, n_rows, R, H);
-    hipLaunchKernelGGL(highway_bias_reduce_kernel, dim3(1), dim3(64), 0, s, bias_partial, BIAS_BLOCKS, g_bc, (const long long*)nullptr, H);
-    (void)layer_stride_b;
 }
 
 // ------------------------------------------------------------------------------------------------

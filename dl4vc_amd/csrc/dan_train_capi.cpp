@@ -4,13 +4,14 @@
 #include "../../include/dl4vc_dan_train.h"
 #include "dan_kernels.h"
 #include "dan_train.h"
+#include "device_buffer.h"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
+#include <deque>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -64,7 +65,7 @@ struct dan_trainer {
     float *d_rmean = nullptr, *d_rvar = nullptr;
     // flat buffers
     float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr;
-    std::vector<void*> allocs;
+    std::deque<dev::Buffer> blocks;          // every device allocation (talloc); the typed pointers below point into them
     // constants / packed weights (refreshed every step)
     float* d_pe = nullptr;
     int *d_inv = nullptr, *d_canon = nullptr;                 // layer-1 channel maps: canonical -> reference (48), reference -> canonical
@@ -83,7 +84,7 @@ struct dan_trainer {
     float *d_coef_f = nullptr, *d_coef_b = nullptr, *d_smean = nullptr, *d_sinv = nullptr;
     // inputs / targets
     uint8_t* d_in = nullptr;
-    uint8_t* h_stage = nullptr;                  // pinned mirror of d_in | d_tg8 | d_tgf: a step's inputs go up in three asynchronous copies
+    dev::Pinned h_stage;                         // pinned mirror of d_in | d_tg8 | d_tgf: a step's inputs go up in three asynchronous copies
     uint8_t* d_tg8 = nullptr;
     float* d_tgf = nullptr;
     uint8_t* d_mask[3] = {nullptr, nullptr, nullptr};
@@ -99,11 +100,9 @@ struct dan_trainer {
     // gradients of activations
     float *d_dhid1d = nullptr, *d_dhid1 = nullptr, *d_dhid0d = nullptr, *d_dhid0 = nullptr, *d_dfeatd = nullptr, *d_dfeat = nullptr;
     float *d_du = nullptr, *d_g[2] = {nullptr, nullptr}, *d_dn = nullptr, *d_dpool = nullptr, *d_dh = nullptr;
-    float *d_partial = nullptr, *d_bias_partial = nullptr, *d_hw_partial = nullptr;
+    float *d_partial = nullptr, *d_bias_partial = nullptr;
     float* d_clip = nullptr;
     float* d_dhw = nullptr;                                    // [layers][rows][HPAD]
-    float* d_split_hw = nullptr;                               // split-K partials of the highway weight-gradient GEMM
-    long long split_hw_floats = 0;
     float* d_split_ws = nullptr;                               // split-K partials of the forward FC GEMMs
     long long split_ws_floats = 0;
     double* d_l0tot = nullptr;                                  // layer 1's backward by bins: the totals (launch_l0_backward)
@@ -111,21 +110,19 @@ struct dan_trainer {
     int last_B = 0;
     // dan_train_backward_begin / _end: the step in flight and the event behind which the FC-side gradients are final
     bool pending = false;
-    hipEvent_t ev_tail = nullptr;
+    dev::Event ev_tail;
     float dp_mean_sites = 0.f, dp_ce_den[2] = {0.f, 0.f};     // dan_train_set_global_batch: for the next backward only
 };
 
 namespace {
 
-int failt(const dan_trainer* t, int code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (t) t->err = buf; else g_create_error = buf;
-    return code;
-}
+template <class... A>
+int failt(const dan_trainer* t, int code, const char* fmt, A... a) { return capi::failf(t ? t->err : g_create_error, code, fmt, a...); }
+
+// an extern "C" body: what it throws becomes code -4 and "<who>: <what()>" in the trainer's error text (before a handle exists:
+// in dan_train_create's)
+template <class F>
+int guarded(const dan_trainer* t, const char* who, F&& body) { return capi::guarded(t ? t->err : g_create_error, who, std::forward<F>(body)); }
 
 // launch_train_row's result: the statistics entries it wrote, or < 0 when it refused (nothing was launched then)
 int check_row_launch(const dan_trainer* t, int entries, const char* what, int layer) {
@@ -147,8 +144,9 @@ template <typename T>
 int talloc(dan_trainer* t, T** p, size_t count, bool zero = true) {
     void* q = nullptr;
     const size_t bytes = std::max<size_t>(count * sizeof(T), 256);
+    t->blocks.emplace_back();
     HIPT(t, hipMalloc(&q, bytes));
-    t->allocs.push_back(q);
+    t->blocks.back().p = (uint8_t*)q; t->blocks.back().cap = bytes;
     if (zero) HIPT(t, hipMemset(q, 0, bytes));
     *p = (T*)q;
     return DAN_OK;
@@ -188,13 +186,18 @@ int add_vec(dan_trainer* t, const std::string& name, std::vector<int64_t> shape,
 float* pp(dan_trainer* t, int idx) { return t->P + t->params[idx].off; }
 float* gp(dan_trainer* t, int idx) { return t->G + t->params[idx].off; }
 
-}  // namespace
+// layer l's forward BatchNorm coefficients [3][CPAD], its bias triple (conv, residual, bottleneck), and its slices of d_h / d_dh
+float* coef_f(const dan_trainer* t, int l) { return t->d_coef_f + (size_t)l * 3 * CPAD; }
+float* bias3(const dan_trainer* t, int l) { return t->d_bias + (size_t)l * 3 * CPAD; }
+float* h_of(const dan_trainer* t, int l, size_t n_rows) { return t->d_h + (size_t)l * n_rows * t->cfg.length * HPAD; }
+float* dh_of(const dan_trainer* t, int l, size_t n_rows) { return t->d_dh + (size_t)l * n_rows * t->cfg.length * HPAD; }
 
-extern "C" {
+// The tensor that stands for x_l: x_l itself, or -- where x_l is never written (lazy_x) -- a_l with layer l's forward coefficients,
+// from which the consumer forms x_l = A a_l + C as it loads.
+struct XRef { const float* p; const float* coef; };
+XRef x_of(const dan_trainer* t, int l) { return t->lazy_x[l] ? XRef{t->d_a[l], coef_f(t, l)} : XRef{t->d_x[l], nullptr}; }
 
-const char* dan_train_last_error(const dan_trainer_t* t) { return t ? t->err.c_str() : g_create_error.c_str(); }
-
-int dan_train_create(const dan_config* cfg, const dan_train_hyper* hyper, int32_t max_batch, dan_trainer_t** out) {
+int create(const dan_config* cfg, const dan_train_hyper* hyper, int32_t max_batch, dan_trainer_t** out) {
     if (!cfg || !hyper || !out) return failt(nullptr, DAN_ERR_INVALID_ARG, "dan_train_create: null argument");
     *out = nullptr;
     const dan_config& c = *cfg;
@@ -215,7 +218,8 @@ int dan_train_create(const dan_config* cfg, const dan_train_hyper* hyper, int32_
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || c.device_id < 0 || c.device_id >= ndev)
         return failt(nullptr, DAN_ERR_NO_DEVICE, "no HIP device %d (found %d): the training step has no CPU path", c.device_id, ndev);
-    dan_trainer* t = new dan_trainer();
+    std::unique_ptr<dan_trainer> owner(new dan_trainer());
+    dan_trainer* t = owner.get();
     t->cfg = c; t->hp = *hyper; t->max_batch = max_batch;
     t->F = 2 * c.c_final * c.length + c.layers * c.bottleneck * c.reads;
     t->F_stride = ((int64_t)t->F + 15) / 16 * 16;
@@ -268,11 +272,11 @@ int dan_train_create(const dan_config* cfg, const dan_train_hyper* hyper, int32_
         t->views[std::string(hd.name) + ".bias"] = b;
         row += hd.n;
     }
-    *out = t;
+    *out = owner.release();
     return DAN_OK;
 }
 
-int dan_train_set_tensor(dan_trainer_t* t, const char* name, const float* data, const int64_t* shape, int32_t ndim) {
+int set_tensor(dan_trainer_t* t, const char* name, const float* data, const int64_t* shape, int32_t ndim) {
     if (!t || !name || !data || ndim < 0 || ndim > 8 || (ndim > 0 && !shape)) return failt(t, DAN_ERR_INVALID_ARG, "dan_train_set_tensor: bad argument");
     if (t->finalized) return failt(t, DAN_ERR_STATE, "dan_train_set_tensor('%s') after dan_train_finalize (use dan_train_put_tensor)", name);
     std::vector<int64_t> shp(shape, shape + ndim);
@@ -298,8 +302,7 @@ int dan_train_set_tensor(dan_trainer_t* t, const char* name, const float* data, 
     return DAN_OK;
 }
 
-int dan_train_finalize(dan_trainer_t* t) {
-    if (!t) return DAN_ERR_INVALID_ARG;
+int finalize(dan_trainer_t* t) {
     if (t->finalized) return failt(t, DAN_ERR_STATE, "dan_train_finalize called twice");
     const dan_config& c = t->cfg;
     HIPT(t, hipSetDevice(c.device_id));
@@ -377,7 +380,7 @@ int dan_train_finalize(dan_trainer_t* t) {
     // ---- inputs, targets, masks
     const size_t in_site = (size_t)3 * R * L + 3 * L;
     if ((rc = talloc(t, &t->d_in, (size_t)B * in_site)) || (rc = talloc(t, &t->d_tg8, (size_t)B * 4)) || (rc = talloc(t, &t->d_tgf, (size_t)B * 3))) return rc;
-    HIPT(t, hipHostMalloc((void**)&t->h_stage, (size_t)B * (in_site + 4 + 3 * sizeof(float)), hipHostMallocDefault));
+    HIPT(t, t->h_stage.alloc((size_t)B * (in_site + 4 + 3 * sizeof(float))));
     if ((rc = talloc(t, &t->d_mask[0], (size_t)B * t->F)) || (rc = talloc(t, &t->d_mask[1], (size_t)B * t->n0)) || (rc = talloc(t, &t->d_mask[2], (size_t)B * t->n1))) return rc;
     // ---- activations
     const size_t rowf = (size_t)L * CPAD;
@@ -413,13 +416,9 @@ int dan_train_finalize(dan_trainer_t* t) {
     if ((rc = talloc(t, &t->d_du, rows * rowf, false)) || (rc = talloc(t, &t->d_g[0], rows * rowf, false)) || (rc = talloc(t, &t->d_g[1], rows * rowf, false)) ||
         (rc = talloc(t, &t->d_dn, rows * rowf, false)) || (rc = talloc(t, &t->d_dpool, (size_t)B * rowf, false))) return rc;
     if ((rc = talloc(t, &t->d_partial, (size_t)TRAIN_PARTIAL_WGS * 3 * CPAD * CPAD, false)) || (rc = talloc(t, &t->d_bias_partial, (size_t)2 * TRAIN_PARTIAL_WGS * CPAD, false)) ||
-        (rc = talloc(t, &t->d_hw_partial, (size_t)8 * HPAD * L * HPAD + 64 * HPAD, false)) ||
         (rc = talloc(t, &t->d_l0tot, (size_t)L0_BINS_TOTALS)) || (rc = talloc(t, &t->d_l0tab, l0_tab_floats(L))) ||
         (rc = talloc(t, &t->d_clip, 4))) return rc;
-    if (H > 0) {
-        t->split_hw_floats = (long long)8 * HPAD * L * HPAD;
-        if ((rc = talloc(t, &t->d_dhw, (size_t)NL * rows * HPAD, false)) || (rc = talloc(t, &t->d_split_hw, (size_t)t->split_hw_floats, false))) return rc;
-    }
+    if (H > 0 && (rc = talloc(t, &t->d_dhw, (size_t)NL * rows * HPAD, false))) return rc;
     // (split-K partials of the FC GEMMs; at <= 16 sites the FC1 forms of fc_skinny_*_kernel: one partial per 1024-float slab of
     // the feature row forward, up to 12 row groups of the weight matrix in the data gradient)
     const long long skinny = (long long)std::min(B, 16) * std::max((t->F_stride + 1023) / 1024 * (long long)t->n0, 12 * (long long)t->F_stride);
@@ -427,28 +426,13 @@ int dan_train_finalize(dan_trainer_t* t) {
     if ((rc = talloc(t, &t->d_split_ws, (size_t)t->split_ws_floats, false))) return rc;
     if ((rc = build_pack_jobs(t))) return rc;
     HIPT(t, hipDeviceSynchronize());
-    HIPT(t, hipEventCreateWithFlags(&t->ev_tail, hipEventDisableTiming));
+    HIPT(t, t->ev_tail.ensure(hipEventDisableTiming));
     t->finalized = true;
     return DAN_OK;
 }
 
-void dan_train_destroy(dan_trainer_t* t) {
-    if (!t) return;
-    (void)hipSetDevice(t->cfg.device_id);
-    (void)hipDeviceSynchronize();
-    for (void* p : t->allocs) (void)hipFree(p);
-    if (t->ev_tail) (void)hipEventDestroy(t->ev_tail);
-    if (t->h_stage) (void)hipHostFree(t->h_stage);
-    delete t;
-}
-
-}  // extern "C"
-
-namespace {
-
-// weights -> the fragment orders the kernels consume, biases -> padded copies; run at the start of every step
-// The same re-packing as refresh_packed below as a job table for ONE launch (built at finalize: every pointer is fixed by then).
-// The Winograd transforms (opt-in form) go through a scratch buffer and stay separate launches.
+// The step's re-packing (weights -> the fragment orders the kernels consume, biases -> padded copies) as a job table for ONE
+// launch, built at finalize: every pointer is fixed by then.  Comments give each packed tensor's index map.
 int build_pack_jobs(dan_trainer* t) {
     const dan_config& c = t->cfg;
     const int L = c.length, H = c.bottleneck;
@@ -465,9 +449,11 @@ int build_pack_jobs(dan_trainer* t) {
         const float* W = pp(t, lp.conv_w);
         const int* cmap = (l == 0) ? t->d_inv : nullptr;
         const int cin_canon = (l == 0) ? CIN0 : lp.cin;
+        // forward: W(o, c, tap) = W[o][c][tap]
         frag(t->pk_conv_f[l], W, 3, lp.kg, KGC, lp.cout, cin_canon, (long long)lp.cin * 3, 3, 1, 0, nullptr, cmap);
+        // data gradient: du[p][c] = sum_{o,t'} W[o][c][2 - t'] dz[p + (t' - 1) d][o]: outputs c (canonical for layer 1), k = o
         frag(t->pk_conv_d[l], W, 3, KGC, KGC, cin_canon, lp.cout, 3, (long long)lp.cin * 3, 1, 1, cmap, nullptr);
-        float* b = t->d_bias + (size_t)l * 3 * CPAD;
+        float* b = bias3(t, l);
         pad(b, pp(t, lp.conv_b), lp.cout, CPAD);
         if (lp.residual) {
             const float* Wr = pp(t, lp.res_w);
@@ -478,7 +464,7 @@ int build_pack_jobs(dan_trainer* t) {
         if (H > 0) {
             const float* Wb = pp(t, lp.bot_w);
             frag(t->pk_bot_f[l], Wb, 1, KGC, 2, H, lp.cout, lp.cout, 1, 0, 0, nullptr, nullptr);
-            frag(t->pk_bot_d[l], Wb, 1, 2, KGC, lp.cout, H, 1, lp.cout, 0, 0, nullptr, nullptr);
+            frag(t->pk_bot_d[l], Wb, 1, 2, KGC, lp.cout, H, 1, lp.cout, 0, 0, nullptr, nullptr);      // out = c, k = o2
             pad(b + 2 * CPAD, pp(t, lp.bot_b), H, HPAD);
             wc(2, t->d_wc_pk + (size_t)l * L * 2 * 2 * 256, pp(t, lp.cmp_w));
             wc(3, t->d_wct + (size_t)l * L * HPAD * HPAD, pp(t, lp.cmp_w));
@@ -504,71 +490,345 @@ int build_pack_jobs(dan_trainer* t) {
     return DAN_OK;
 }
 
-void refresh_packed(dan_trainer* t, hipStream_t s) {
-    const dan_config& c = t->cfg;
-    const int L = c.length, H = c.bottleneck;
-    if (t->d_pack_jobs) {
-        launch_pack_jobs(t->d_pack_jobs, t->n_pack_jobs, t->n_pack_blocks, s);
-        for (int l = 0; l < c.layers; ++l) {
-            if (!t->wino_layer[l]) continue;
-            const LayerP& lp = t->layers[l];
-            const float* W = pp(t, lp.conv_w);
-            launch_wino_u(t->d_wino_u, W, lp.cout, lp.cin, (long long)lp.cin * 3, 3, 0, s);
-            launch_pack_frag(t->pk_wino_f[l], t->d_wino_u, 4, KGC, KGC, lp.cout, lp.cin, (long long)lp.cin * 4, 4, 1, 0, nullptr, nullptr, s);
-            launch_wino_u(t->d_wino_u, W, lp.cin, lp.cout, 3, (long long)lp.cin * 3, 1, s);
-            launch_pack_frag(t->pk_wino_d[l], t->d_wino_u, 4, KGC, KGC, lp.cin, lp.cout, (long long)lp.cout * 4, 4, 1, 0, nullptr, nullptr, s);
-        }
-        return;
-    }
-    for (int l = 0; l < c.layers; ++l) {
+// run at the start of every step: the job table, then the Winograd transforms (opt-in form), which go through a scratch buffer
+// and stay separate launches
+int refresh_packed(dan_trainer* t, hipStream_t s) {
+    if (!t->d_pack_jobs) return failt(t, DAN_ERR_STATE, "the re-packing job table was not built (dan_train_finalize)");
+    launch_pack_jobs(t->d_pack_jobs, t->n_pack_jobs, t->n_pack_blocks, s);
+    for (int l = 0; l < t->cfg.layers; ++l) {
+        if (!t->wino_layer[l]) continue;
         const LayerP& lp = t->layers[l];
         const float* W = pp(t, lp.conv_w);
-        const int* cmap = (l == 0) ? t->d_inv : nullptr;
-        const int cin_canon = (l == 0) ? CIN0 : lp.cin;
-        // forward: W(o, c, tap) = W[o][c][tap]
-        launch_pack_frag(t->pk_conv_f[l], W, 3, lp.kg, KGC, lp.cout, cin_canon, (long long)lp.cin * 3, 3, 1, 0, nullptr, cmap, s);
-        // data gradient: du[p][c] = sum_{o,t'} W[o][c][2 - t'] dz[p + (t' - 1) d][o]: outputs c (canonical for layer 1), k = o
-        launch_pack_frag(t->pk_conv_d[l], W, 3, KGC, KGC, cin_canon, lp.cout, 3, (long long)lp.cin * 3, 1, 1, cmap, nullptr, s);
-        if (t->wino_layer[l]) {
-            // forward: U(o, c);  data gradient: outputs c, inputs o, flipped taps
-            launch_wino_u(t->d_wino_u, W, lp.cout, lp.cin, (long long)lp.cin * 3, 3, 0, s);
-            launch_pack_frag(t->pk_wino_f[l], t->d_wino_u, 4, KGC, KGC, lp.cout, lp.cin, (long long)lp.cin * 4, 4, 1, 0, nullptr, nullptr, s);
-            launch_wino_u(t->d_wino_u, W, lp.cin, lp.cout, 3, (long long)lp.cin * 3, 1, s);
-            launch_pack_frag(t->pk_wino_d[l], t->d_wino_u, 4, KGC, KGC, lp.cin, lp.cout, (long long)lp.cout * 4, 4, 1, 0, nullptr, nullptr, s);
-        }
-        float* b = t->d_bias + (size_t)l * 3 * CPAD;
-        launch_pad_copy(b, pp(t, lp.conv_b), lp.cout, CPAD, s);
-        if (lp.residual) {
-            const float* Wr = pp(t, lp.res_w);
-            launch_pack_frag(t->pk_res_f[l], Wr, 1, KGC, KGC, lp.cout, lp.cout, lp.cout, 1, 0, 0, nullptr, nullptr, s);
-            launch_pack_frag(t->pk_res_d[l], Wr, 1, KGC, KGC, lp.cout, lp.cout, 1, lp.cout, 0, 0, nullptr, nullptr, s);
-            launch_pad_copy(b + CPAD, pp(t, lp.res_b), lp.cout, CPAD, s);
-        }
-        if (H > 0) {
-            const float* Wb = pp(t, lp.bot_w);
-            launch_pack_frag(t->pk_bot_f[l], Wb, 1, KGC, 2, H, lp.cout, lp.cout, 1, 0, 0, nullptr, nullptr, s);
-            launch_pack_frag(t->pk_bot_d[l], Wb, 1, 2, KGC, lp.cout, H, 1, lp.cout, 0, 0, nullptr, nullptr, s);      // out = c, k = o2
-            launch_pad_copy(b + 2 * CPAD, pp(t, lp.bot_b), H, HPAD, s);
-            launch_pack_wc(t->d_wc_pk + (size_t)l * L * 2 * 2 * 256, pp(t, lp.cmp_w), H, L, s);
-            launch_pack_wct(t->d_wct + (size_t)l * L * HPAD * HPAD, pp(t, lp.cmp_w), H, L, s);
-            launch_pad_copy(t->d_bc_pad + (size_t)l * HPAD, pp(t, lp.cmp_b), H, HPAD, s);
-        }
+        // forward: U(o, c);  data gradient: outputs c, inputs o, flipped taps
+        launch_wino_u(t->d_wino_u, W, lp.cout, lp.cin, (long long)lp.cin * 3, 3, 0, s);
+        launch_pack_frag(t->pk_wino_f[l], t->d_wino_u, 4, KGC, KGC, lp.cout, lp.cin, (long long)lp.cin * 4, 4, 1, 0, nullptr, nullptr, s);
+        launch_wino_u(t->d_wino_u, W, lp.cin, lp.cout, 3, (long long)lp.cin * 3, 1, s);
+        launch_pack_frag(t->pk_wino_d[l], t->d_wino_u, 4, KGC, KGC, lp.cin, lp.cout, (long long)lp.cout * 4, 4, 1, 0, nullptr, nullptr, s);
     }
+    return DAN_OK;
 }
 
-void fill_encode(RowArgs& a, const dan_trainer* t, int B) {
+template <class Args>                    // RowArgs or WgradArgs: the six token planes of d_in, the embedding table, the positional encoding
+void fill_encode(Args& a, const dan_trainer* t, int B) {
     const size_t rl = (size_t)t->cfg.reads * t->cfg.length, L = t->cfg.length;
     const uint8_t* d = t->d_in;
     a.reads = d; a.qual = d + B * rl; a.strand = d + 2 * B * rl; a.ref = d + 3 * B * rl; a.ref_mask = a.ref + B * L; a.var_mask = a.ref_mask + B * L;
     a.emb = t->P + t->params[t->p_emb].off; a.pe = t->d_pe;
 }
 
-// dan_train_backward_begin and dan_train_backward_begin_device: the six planes are host arrays (device_planes == false: they go
-// up through the pinned mirror) or lie in device memory already (true: six device-to-device copies into d_in, behind `ready`).
+// What the passes of one step share.
+struct Step {
+    int B, n_rows;
+    double n_pos;                            // positions of a layer: the count behind its BatchNorm statistics
+    hipStream_t s;
+    float dscale;                            // 1 / (1 - dropout)
+    const uint8_t* mk[3];                    // the three dropout masks on the device, null without dropout
+    int stat_entries;                        // entries of d_stats the last statistics-producing launch wrote
+    int cur;                                 // backward: d_g[cur] receives g_l; d_g[cur ^ 1] holds g_{l+1}
+    bool fused_g;                            // backward: layer l+1's data-gradient launch already wrote g_l into d_g[cur]
+};
+
+RowArgs row_args(const dan_trainer* t) {
+    RowArgs a{};
+    a.R = t->cfg.reads; a.L = t->cfg.length;
+    return a;
+}
+
+// The seventeen caller arrays are gathered in the pinned mirror (same layout as on the device) and go up in three stream-ordered
+// copies; the mirror is free again: the previous step's copies completed before its dan_train_backward_end returned.  The six planes
+// are host arrays (device_planes == false) or lie in device memory already, where another stream assembled them (true: wait for
+// it behind `ready`, then six device-to-device copies to the places fill_encode reads).
+int stage_inputs(dan_trainer* t, const Step& st, bool device_planes, void* ready, const uint8_t* const planes[6], const dan_train_targets* tg) {
+    const int B = st.B, L = t->cfg.length;
+    const size_t rl = (size_t)t->cfg.reads * L;
+    hipStream_t s = st.s;
+    uint8_t* h = t->h_stage.get();
+    size_t o = 0;
+    auto stage = [&](const void* src, size_t n) { memcpy(h + o, src, n); o += n; };
+    const size_t plane_bytes[6] = {B * rl, B * rl, B * rl, (size_t)B * L, (size_t)B * L, (size_t)B * L};
+    if (device_planes) {
+        if (ready) HIPT(t, hipStreamWaitEvent(s, (hipEvent_t)ready, 0));
+        for (int k = 0; k < 6; ++k) {
+            HIPT(t, hipMemcpyAsync(t->d_in + o, planes[k], plane_bytes[k], hipMemcpyDeviceToDevice, s));
+            o += plane_bytes[k];
+        }
+    } else {
+        for (int k = 0; k < 6; ++k) stage(planes[k], plane_bytes[k]);
+    }
+    const size_t n_in = o;
+    stage(tg->label, B); stage(tg->var_type, B); stage(tg->var_base_enum, B); stage(tg->var_ref_enum, B);
+    const size_t n_tg8 = o - n_in;
+    stage(tg->allele_freq, B * sizeof(float)); stage(tg->coverage, B * sizeof(float)); stage(tg->weight, B * sizeof(float));
+    if (!device_planes) HIPT(t, hipMemcpyAsync(t->d_in, h, n_in, hipMemcpyHostToDevice, s));
+    HIPT(t, hipMemcpyAsync(t->d_tg8, h + n_in, n_tg8, hipMemcpyHostToDevice, s));
+    HIPT(t, hipMemcpyAsync(t->d_tgf, h + n_in + n_tg8, o - n_in - n_tg8, hipMemcpyHostToDevice, s));
+    return DAN_OK;
+}
+
+// the caller's masks, or masks from the counter-based generator (seed, step, tensor)
+int make_dropout_masks(dan_trainer* t, Step& st, const uint8_t* const* dropout_masks, uint64_t seed) {
+    const float p = t->hp.dropout;
+    const bool drop = p > 0.f;
+    const int B = st.B;
+    const int64_t mcols[3] = {t->F, t->n0, t->n1};
+    st.dscale = drop ? 1.f / (1.f - p) : 1.f;
+    for (int i = 0; i < 3; ++i) {
+        st.mk[i] = drop ? t->d_mask[i] : nullptr;
+        if (!drop) continue;
+        if (dropout_masks && dropout_masks[i]) HIPT(t, hipMemcpy(t->d_mask[i], dropout_masks[i], (size_t)B * mcols[i], hipMemcpyHostToDevice));
+        else if (dropout_masks) return failt(t, DAN_ERR_INVALID_ARG, "dropout mask %d is null", i);
+        else launch_dropout_mask(t->d_mask[i], (long long)B * mcols[i], p, seed, (unsigned long long)t->step * 3 + i, st.s);
+    }
+    return DAN_OK;
+}
+
+// ================================================= forward (train mode) =================================================
+// layer l: a_l, its batch statistics, x_l (unless never written) and h_l
+int forward_layer(dan_trainer* t, Step& st, int l) {
+    const dan_config& c = t->cfg;
+    const LayerP& lp = t->layers[l];
+    const int stat_cap = t->stat_entries_max;
+    const float* bias = bias3(t, l);
+    hipStream_t s = st.s;
+    int rc;
+    {   // a_l = relu(conv(u_l) + b), u_l = x_{l-1} (+ read-mean of x_{l-1} when layer l-1 pools; model.py:742,749)
+        RowArgs a = row_args(t);
+        if (l == 0) {
+            // layer 1 by table: the tables from this step's weights, then the walk (dan_train.hip)
+            fill_encode(a, t, st.B);
+            launch_l0_train_tables(pp(t, lp.conv_w), t->d_inv, a.emb, a.pe, c.length, lp.cout, lp.cin, t->d_l0tab, s);
+            st.stat_entries = launch_l0_train_forward(a, t->d_l0tab, bias, st.n_rows, t->d_a[l], c.use_bn ? t->d_stats : nullptr, s);
+            if (st.stat_entries > stat_cap) return failt(t, DAN_ERR_STATE, "layer 1's forward writes %d statistics entries, the buffer holds %d", st.stat_entries, stat_cap);
+        } else {
+            const XRef x = x_of(t, l - 1);
+            a.src1 = x.p; a.s1_stride = CPAD; a.coef = x.coef; a.pool_in = t->d_pool[l];
+            a.w1 = t->pk_conv_f[l]; a.taps = 3; a.kg = lp.kg; a.dil = lp.dil;
+            if (t->wino_layer[l]) { a.w1 = t->pk_wino_f[l]; a.wino = 1; }
+            a.bias1 = bias; a.relu_out = 1; a.out1 = t->d_a[l];
+            a.stats = c.use_bn ? t->d_stats : nullptr;
+            st.stat_entries = launch_train_row(a, st.n_rows, s, stat_cap);
+            if ((rc = check_row_launch(t, st.stat_entries, "conv forward", l))) return rc;
+        }
+    }
+    if (c.use_bn) {                                      // batch statistics over (B, R, L) per channel (model.py:750-751, train mode)
+        int nb = 0;
+        launch_stats_partial(t->d_stats, st.stat_entries, t->d_bp, &nb, s);
+        launch_bn_forward_finalize(t->d_bp, nb, st.n_pos, pp(t, lp.bn_g), pp(t, lp.bn_b), lp.cout, coef_f(t, l), t->d_smean + (size_t)l * CPAD,
+                                   t->d_sinv + (size_t)l * CPAD, t->d_rmean + (size_t)l * CPAD, t->d_rvar + (size_t)l * CPAD, s);
+    }
+    {   // x_l = [W_r] bn(a_l) [+ b_r + x_{l-1}]  (model.py:753-761);  h_l = relu(W_b x_l + b_b)  (model.py:774)
+        RowArgs a = row_args(t);
+        a.src1 = t->d_a[l]; a.s1_stride = CPAD; a.coef = coef_f(t, l);
+        if (lp.residual) {
+            const XRef x = x_of(t, l - 1);
+            a.w1 = t->pk_res_f[l]; a.taps = 1; a.kg = KGC; a.dil = 0; a.bias1 = bias + CPAD; a.add1 = x.p; a.add1_coef = x.coef;
+        }
+        a.out1 = t->d_x[l];                              // (nullptr for a lazy layer: the launch then only writes h_l)
+        if (c.bottleneck > 0) { a.w2 = t->pk_bot_f[l]; a.bias2 = bias + 2 * CPAD; a.out2 = h_of(t, l, st.n_rows); }
+        if ((rc = check_row_launch(t, launch_train_row(a, st.n_rows, s, stat_cap), "BatchNorm-apply / residual / bottleneck", l))) return rc;
+    }
+    if (pool_after(c, l + 1)) launch_read_mean(t->d_x[l], t->d_pool[l + 1], st.B, c.reads, c.length, nullptr, s);
+    return DAN_OK;
+}
+
+// final pools, highway compression, the FC stack (Dropout -> Linear -> ReLU -> Dropout -> Linear -> ReLU -> Dropout, model.py:369-377),
+// heads and losses
+void forward_tail(dan_trainer* t, const Step& st) {
+    const dan_config& c = t->cfg;
+    const dan_train_hyper& hp = t->hp;
+    const int B = st.B, L = c.length, R = c.reads, NL = c.layers;
+    hipStream_t s = st.s;
+    launch_final_pool(t->d_x[NL - 1], t->d_feat, t->F_stride, B, R, L, c.c_final, nullptr, s);
+    if (c.bottleneck > 0)
+        launch_highway(t->d_h, (long long)st.n_rows * L * HPAD, t->d_wc_pk, (long long)L * 2 * 2 * 256, t->d_bc_pad, t->d_feat, t->F_stride, 2 * c.c_final * L, B, R, L,
+                       c.bottleneck, NL, nullptr, s);
+    launch_dropout(t->d_feat, st.mk[0], st.dscale, t->d_featd, B, t->F, t->F_stride, s);
+    launch_gemm(t->d_featd, t->F_stride, 0, pp(t, t->p_fc0w), t->F_stride, 0, pp(t, t->p_fc0b), t->d_hid0, t->n0_stride, B, t->n0, (int)t->F_stride, 1, t->d_split_ws, t->split_ws_floats, s);
+    launch_dropout(t->d_hid0, st.mk[1], st.dscale, t->d_hid0d, B, t->n0, t->n0_stride, s);
+    launch_gemm(t->d_hid0d, t->n0_stride, 0, pp(t, t->p_fc1w), t->n0_stride, 0, pp(t, t->p_fc1b), t->d_hid1, t->n1_stride, B, t->n1, (int)t->n0_stride, 1, t->d_split_ws, t->split_ws_floats, s);
+    launch_dropout(t->d_hid1, st.mk[2], st.dscale, t->d_hid1d, B, t->n1, t->n1_stride, s);
+    LossArgs a{};
+    a.B = B; a.hid = t->n1; a.hid_stride = (int)t->n1_stride; a.hidden = t->d_hid1d; a.wh = pp(t, t->p_hw); a.bh = pp(t, t->p_hb);
+    a.label = t->d_tg8; a.var_type = t->d_tg8 + B; a.var_base = t->d_tg8 + 2 * B; a.var_ref = t->d_tg8 + 3 * B;
+    a.allele_freq = t->d_tgf; a.coverage = t->d_tgf + B; a.weight = t->d_tgf + 2 * B;
+    a.label_smoothing = hp.label_smoothing; a.close_window = hp.close_match_window; a.focal_alpha = hp.focal_alpha; a.focal_gamma = hp.focal_gamma;
+    a.fp_weight = hp.fp_train_weight; a.binary_weight = hp.binary_weight; a.aux_weight = hp.aux_weight;
+    a.aux_bases_weight = hp.aux_bases_weight; a.aux_allele_weight = hp.aux_allele_weight;
+    a.logits = t->d_logits; a.dlogits = t->d_dlogits; a.losses = t->d_losses; a.close = t->d_close; a.site_terms = t->d_site_terms;
+    a.mean_sites = t->dp_mean_sites; a.ce_den[0] = t->dp_ce_den[0]; a.ce_den[1] = t->dp_ce_den[1];
+    t->dp_mean_sites = 0.f; t->dp_ce_den[0] = t->dp_ce_den[1] = 0.f;
+    launch_heads_loss(a, s);
+}
+
+// ====================================================== backward ======================================================
+// heads (their gradient tensors are contiguous in the flat buffer, like the weights) and the FC stack, down to dfeat
+int backward_fc(dan_trainer* t, const Step& st) {
+    const int B = st.B;
+    hipStream_t s = st.s;
+    launch_heads_bwd(t->d_dlogits, t->d_hid1d, pp(t, t->p_hw), B, t->n1, (int)t->n1_stride, t->d_dhid1d, gp(t, t->p_hw), gp(t, t->p_hb), s);
+    launch_dropout_relu_bwd(t->d_dhid1d, st.mk[2], st.dscale, t->d_hid1, 1, t->d_dhid1, B, t->n1, t->n1_stride, s);
+    // FC2: gW1[n][k] = sum_b d1[b][n] hid0d[b][k];  d(hid0d) = d1 W1
+    launch_gemm(t->d_dhid1, t->n1_stride, 1, t->d_hid0d, t->n0_stride, 1, nullptr, gp(t, t->p_fc1w), t->n0_stride, t->n1, t->n0, B, 0, t->d_split_ws, t->split_ws_floats, s);
+    launch_colsum(t->d_dhid1, B, t->n1, t->n1_stride, gp(t, t->p_fc1b), s);
+    launch_gemm(t->d_dhid1, t->n1_stride, 0, pp(t, t->p_fc1w), t->n0_stride, 1, nullptr, t->d_dhid0d, t->n0_stride, B, t->n0, t->n1, 0, t->d_split_ws, t->split_ws_floats, s);
+    launch_dropout_relu_bwd(t->d_dhid0d, st.mk[1], st.dscale, t->d_hid0, 1, t->d_dhid0, B, t->n0, t->n0_stride, s);
+    // FC1
+    launch_gemm(t->d_dhid0, t->n0_stride, 1, t->d_featd, t->F_stride, 1, nullptr, gp(t, t->p_fc0w), t->F_stride, t->n0, t->F, B, 0, t->d_split_ws, t->split_ws_floats, s);
+    launch_colsum(t->d_dhid0, B, t->n0, t->n0_stride, gp(t, t->p_fc0b), s);
+    HIPT(t, hipEventRecord(t->ev_tail, s));                  // bucket 0 (FC stack + heads: the tail of the flat buffer) is final
+    launch_gemm(t->d_dhid0, t->n0_stride, 0, pp(t, t->p_fc0w), t->F_stride, 1, nullptr, t->d_dfeatd, t->F_stride, B, t->F, t->n0, 0, t->d_split_ws, t->split_ws_floats, s);
+    launch_dropout_relu_bwd(t->d_dfeatd, st.mk[0], st.dscale, nullptr, 0, t->d_dfeat, B, t->F, t->F_stride, s);
+    return DAN_OK;
+}
+
+// highway compression: dhw = dfeat_hw * (feat_hw > 0) as [layer][row][HPAD]; then one launch for every layer's dh (a 165-MB write
+// stream per layer at 64 sites), one for every layer's weight gradient (h read once, no split, straight into the torch layout) and
+// two for the compression biases' gradients of all layers (column sums of dhw)
+// Then the final max + mean pool (model.py:824-839): du of the last layer.
+void backward_highway_pools(dan_trainer* t, const Step& st) {
+    const dan_config& c = t->cfg;
+    const int B = st.B, L = c.length, R = c.reads, H = c.bottleneck, NL = c.layers, hw_off = 2 * c.c_final * L;
+    if (H > 0) {
+        launch_highway_dhw(t->d_dfeat, t->d_feat, t->F_stride, hw_off, t->d_dhw, B, R, H, NL, st.s);
+        launch_highway_dh(t->d_dhw, t->d_wct, t->d_dh, st.n_rows, L, NL, st.s);
+        launch_highway_gwc(t->d_dhw, t->d_h, t->G, t->d_cmpw_off, st.n_rows, L, H, NL, st.s);
+        launch_highway_bias_grad_all(t->d_dfeat, t->d_feat, t->F_stride, hw_off, t->d_bias_partial, t->G, t->d_cmpb_off, B, R, H, NL, st.s);
+    }
+    launch_final_pool_bwd(t->d_x[NL - 1], t->d_dfeat, t->F_stride, t->d_du, B, R, L, c.c_final, st.s);
+}
+
+// one weight (and bias) gradient of layer l: the partials of launch_train_wgrad, summed into gw / gb
+int wgrad(dan_trainer* t, const Step& st, WgradArgs& w, int l, const char* what, int n_out, int n_in, float* gw, float* gb) {
+    w.R = t->cfg.reads; w.L = t->cfg.length; w.n_rows = st.n_rows; w.partial = t->d_partial; w.bias_partial = t->d_bias_partial;
+    const int wgs = launch_train_wgrad(w, st.s);
+    if (wgs < 1) return failt(t, DAN_ERR_STATE, "%s weight gradient of layer %d: no kernel form for its shape", what, l + 1);
+    launch_wgrad_reduce(t->d_partial, t->d_bias_partial, wgs, w.taps, w.o_tiles * 16, w.c_tiles * 16, n_out, n_in, nullptr, gw, gb, st.s);
+    return DAN_OK;
+}
+
+// g_l = du_{l+1} (or the pool gradient) [+ g_{l+1} through the residual skip] [+ mean_r du_{l+1}] [+ W_b^T (dh_l * (h_l > 0))]
+int accumulate_g(dan_trainer* t, Step& st, int l) {
+    const dan_config& c = t->cfg;
+    const bool residual = t->layers[l].residual, next_res = (l + 1 < c.layers) && t->layers[l + 1].residual;
+    RowArgs a = row_args(t);
+    if (c.bottleneck > 0) {
+        a.src1 = dh_of(t, l, st.n_rows); a.s1_stride = HPAD; a.src2 = h_of(t, l, st.n_rows); a.mask_src2 = 1;
+        a.w1 = t->pk_bot_d[l]; a.taps = 1; a.kg = 2; a.dil = 0;
+        a.add1 = t->d_du;
+    } else {
+        a.src1 = t->d_du; a.s1_stride = CPAD;
+    }
+    a.add2 = next_res ? t->d_g[st.cur ^ 1] : nullptr;
+    a.addb = pool_after(c, l + 1) ? t->d_dpool : nullptr;
+    a.out1 = t->d_g[st.cur];
+    if (!residual) { a.stats = t->d_stats; a.stat_aux = t->d_a[l]; }
+    const int e = launch_train_row(a, st.n_rows, st.s, t->stat_entries_max);
+    if (!residual) st.stat_entries = e;
+    return check_row_launch(t, e, "g accumulation", l);
+}
+
+// x_l = W_r n_l + b_r + x_{l-1}:  dn_l = W_r^T g_l (into d_dn);  gW_r = g_l n_l^T;  g_{l-1} += g_l (the next layer down's add2)
+int backward_residual(dan_trainer* t, Step& st, int l, const float* g) {
+    const LayerP& lp = t->layers[l];
+    RowArgs a = row_args(t);
+    a.src1 = g; a.s1_stride = CPAD;
+    a.w1 = t->pk_res_d[l]; a.taps = 1; a.kg = KGC; a.dil = 0;
+    a.out1 = t->d_dn; a.stats = t->d_stats; a.stat_aux = t->d_a[l];
+    st.stat_entries = launch_train_row(a, st.n_rows, st.s, t->stat_entries_max);
+    if (int rc = check_row_launch(t, st.stat_entries, "residual data gradient", l)) return rc;
+    WgradArgs w{};
+    w.a1 = g; w.a_stride = CPAD; w.b1 = t->d_a[l]; w.b_coef = coef_f(t, l);
+    w.taps = 1; w.dil = 0; w.o_tiles = KGC; w.c_tiles = KGC;
+    return wgrad(t, st, w, l, "residual", lp.cout, lp.cout, gp(t, lp.res_w), gp(t, lp.res_b));
+}
+
+// layer 1: its weight and bias gradients AND the embedding gradient from one pass over dz_1 (dan_train.hip: layer 1's backward by
+// bins) -- no encode-form GEMM, no data-gradient launch (its only reader was the embedding gradient)
+int backward_layer1(dan_trainer* t, const Step& st, const float* dn) {
+    const LayerP& lp = t->layers[0];
+    WgradArgs w{};
+    w.R = t->cfg.reads; w.L = t->cfg.length; w.n_rows = st.n_rows; w.a1 = dn; w.a_stride = CPAD; w.a2 = t->d_a[0]; w.a_coef = t->d_coef_b; w.a_mask = 1;
+    fill_encode(w, t, st.B);
+    w.partial = t->d_partial;
+    const int e0 = launch_l0_backward(w, st.B, t->d_l0tot, pp(t, lp.conv_w), t->d_canon, lp.cout, lp.cin, gp(t, lp.conv_w), gp(t, lp.conv_b), gp(t, t->p_emb), st.s);
+    if (e0) return failt(t, DAN_ERR_HIP, "layer 1's backward: the device refuses %d B of dynamic LDS for l0_bins_kernel: %s", l0_bins_lds_bytes(), hipGetErrorString((hipError_t)e0));
+    return DAN_OK;
+}
+
+// data gradient du_l = conv^T(dz_l), l >= 1.  Where it can, the launch goes on to g_{l-1} = du_l + W_b^T (dh_{l-1} * (h_{l-1} > 0))
+// [+ g_l through the residual skip], with the statistics of layer l-1's BatchNorm backward, so that du_l is never written: the
+// half-read direct form, unless layer l-1 pools -- the read mean of du_l must exist before g_{l-1} does.
+// (train_row_fuses_second_product: the launcher's own predicate for the only kernel form that honours w3 -- the two conditions
+// cannot drift apart, and launch_train_row refuses a w3 it would ignore)
+int backward_conv_data(dan_trainer* t, Step& st, int l, const float* dn, const float* g) {
+    const dan_config& c = t->cfg;
+    const LayerP& lp = t->layers[l];
+    RowArgs a = row_args(t);
+    a.src1 = dn; a.s1_stride = CPAD; a.src2 = t->d_a[l]; a.coef = t->d_coef_b; a.mask_src2 = 1;
+    a.w1 = t->pk_conv_d[l]; a.taps = 3; a.kg = KGC; a.dil = lp.dil;
+    if (t->wino_layer[l]) { a.w1 = t->pk_wino_d[l]; a.wino = 1; }
+    a.out1 = t->d_du;
+    const bool stats_below = !t->layers[l - 1].residual;
+    if (c.bottleneck > 0 && !pool_after(c, l) && train_row_fuses_second_product(a)) {
+        a.w3 = t->pk_bot_d[l - 1]; a.src3 = dh_of(t, l - 1, st.n_rows); a.src4 = h_of(t, l - 1, st.n_rows);
+        a.add2 = lp.residual ? g : nullptr;
+        a.out1 = t->d_g[st.cur ^ 1];
+        if (stats_below) { a.stats = t->d_stats; a.stat_aux = t->d_a[l - 1]; }
+        st.fused_g = true;
+    }
+    const int e = launch_train_row(a, st.n_rows, st.s, t->stat_entries_max);
+    if (int rc = check_row_launch(t, e, "conv data gradient", l)) return rc;
+    if (st.fused_g && stats_below) st.stat_entries = e;
+    if (pool_after(c, l)) launch_read_mean(t->d_du, t->d_dpool, st.B, c.reads, c.length, nullptr, st.s);     // u_l = x_{l-1} + mean_r x_{l-1}
+    return DAN_OK;
+}
+
+// layer l: g_l, [the residual's dn_l and gW_r,] the BatchNorm coefficients with dgamma / dbeta, gW_b, the conv's gW and du_l
+int backward_layer(dan_trainer* t, Step& st, int l) {
+    const dan_config& c = t->cfg;
+    const LayerP& lp = t->layers[l];
+    int rc;
+    const float* g = t->d_g[st.cur];
+    if (st.fused_g) st.fused_g = false;      // g_l (and its statistics) came out of layer l+1's data-gradient launch
+    else if ((rc = accumulate_g(t, st, l))) return rc;
+    const float* dn = g;
+    if (lp.residual) {
+        if ((rc = backward_residual(t, st, l, g))) return rc;
+        dn = t->d_dn;
+    }
+    {   // BatchNorm backward coefficients from sum(dn), sum(dn * a)  (identity without BatchNorm)
+        int nb = 0;
+        launch_stats_partial(t->d_stats, st.stat_entries, t->d_bp, &nb, st.s);
+        launch_bn_backward_coef(t->d_bp, nb, st.n_pos, pp(t, lp.bn_g), t->d_smean + (size_t)l * CPAD, t->d_sinv + (size_t)l * CPAD, lp.cout, c.use_bn,
+                                t->d_coef_b, gp(t, lp.bn_g), gp(t, lp.bn_b), st.s);
+    }
+    if (c.bottleneck > 0) {   // h_l = relu(W_b x_l + b_b):  gW_b = (dh_l * (h_l > 0)) x_l^T
+        const XRef x = x_of(t, l);
+        WgradArgs w{};
+        w.a1 = dh_of(t, l, st.n_rows); w.a_stride = HPAD; w.a2 = h_of(t, l, st.n_rows); w.a_mask = 1;
+        w.b1 = x.p; w.b_coef = x.coef;
+        w.taps = 1; w.dil = 0; w.o_tiles = 2; w.c_tiles = KGC;
+        if ((rc = wgrad(t, st, w, l, "bottleneck", c.bottleneck, lp.cout, gp(t, lp.bot_w), gp(t, lp.bot_b)))) return rc;
+    }
+    if (l == 0) {
+        if ((rc = backward_layer1(t, st, dn))) return rc;
+    } else {   // conv weight gradient: dz_l = (A dn + B a_l + C) * (a_l > 0);  gW[o][c][t] = sum_p dz[p][o] u_l[p + (t-1) d][c]
+        const XRef x = x_of(t, l - 1);
+        WgradArgs w{};
+        w.a1 = dn; w.a_stride = CPAD; w.a2 = t->d_a[l]; w.a_coef = t->d_coef_b; w.a_mask = 1;
+        w.b1 = x.p; w.b_coef = x.coef; w.b_pool = t->d_pool[l];
+        w.taps = 3; w.dil = lp.dil; w.o_tiles = KGC; w.c_tiles = KGC;
+        if ((rc = wgrad(t, st, w, l, "conv", lp.cout, lp.cin, gp(t, lp.conv_w), gp(t, lp.conv_b)))) return rc;
+        if ((rc = backward_conv_data(t, st, l, dn, g))) return rc;
+    }
+    st.cur ^= 1;
+    return DAN_OK;
+}
+
+// dan_train_backward_begin and dan_train_backward_begin_device: the whole schedule of a step's forward and backward on the null stream
 int backward_begin(dan_trainer_t* t, bool device_planes, void* ready, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand,
                    const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int64_t n_sites, const dan_train_targets* tg,
                    const uint8_t* const* dropout_masks, uint64_t seed) {
-    if (!t) return DAN_ERR_INVALID_ARG;
     if (!t->finalized) return failt(t, DAN_ERR_STATE, "dan_train_backward before dan_train_finalize");
     if (t->pending) return failt(t, DAN_ERR_STATE, "dan_train_backward_begin: the previous step has not been ended (dan_train_backward_end)");
     if (n_sites < 1 || n_sites > t->max_batch) return failt(t, DAN_ERR_INVALID_ARG, "a training batch holds 1..%d sites, got %lld", t->max_batch, (long long)n_sites);
@@ -576,259 +836,22 @@ int backward_begin(dan_trainer_t* t, bool device_planes, void* ready, const uint
     if (!tg || !tg->label || !tg->var_type || !tg->allele_freq || !tg->coverage || !tg->var_base_enum || !tg->var_ref_enum || !tg->weight)
         return failt(t, DAN_ERR_INVALID_ARG, "null target array");
     const dan_config& c = t->cfg;
-    const dan_train_hyper& hp = t->hp;
     HIPT(t, hipSetDevice(c.device_id));
-    hipStream_t s = nullptr;
-    const int B = (int)n_sites, L = c.length, R = c.reads, H = c.bottleneck, NL = c.layers;
-    const int n_rows = B * R;
-    const size_t rl = (size_t)R * L;
-    const double n_pos = (double)n_rows * L;
-    t->last_B = B;
-    // ---- inputs
-    {   // the seventeen caller arrays are gathered in the pinned mirror (same layout as on the device) and go up in three
-        // stream-ordered copies; the mirror is free again: the previous step's copies completed before its dan_train_backward_end returned
-        uint8_t* h = t->h_stage;
-        size_t o = 0;
-        auto stage = [&](const void* src, size_t n) { memcpy(h + o, src, n); o += n; };
-        const uint8_t* planes[6] = {reads, qual, strand, ref, ref_mask, var_mask};
-        const size_t plane_bytes[6] = {B * rl, B * rl, B * rl, (size_t)B * L, (size_t)B * L, (size_t)B * L};
-        if (device_planes) {
-            // the planes are where another stream assembled them: wait for it, then copy them to the places fill_encode reads
-            if (ready) HIPT(t, hipStreamWaitEvent(s, (hipEvent_t)ready, 0));
-            for (int k = 0; k < 6; ++k) {
-                HIPT(t, hipMemcpyAsync(t->d_in + o, planes[k], plane_bytes[k], hipMemcpyDeviceToDevice, s));
-                o += plane_bytes[k];
-            }
-        } else {
-            for (int k = 0; k < 6; ++k) stage(planes[k], plane_bytes[k]);
-        }
-        const size_t n_in = o;
-        stage(tg->label, B); stage(tg->var_type, B); stage(tg->var_base_enum, B); stage(tg->var_ref_enum, B);
-        const size_t n_tg8 = o - n_in;
-        stage(tg->allele_freq, B * sizeof(float)); stage(tg->coverage, B * sizeof(float)); stage(tg->weight, B * sizeof(float));
-        if (!device_planes) HIPT(t, hipMemcpyAsync(t->d_in, h, n_in, hipMemcpyHostToDevice, s));
-        HIPT(t, hipMemcpyAsync(t->d_tg8, h + n_in, n_tg8, hipMemcpyHostToDevice, s));
-        HIPT(t, hipMemcpyAsync(t->d_tgf, h + n_in + n_tg8, o - n_in - n_tg8, hipMemcpyHostToDevice, s));
-    }
-    int rc = DAN_OK;
-    const int stat_cap = t->stat_entries_max;
-    const bool drop = hp.dropout > 0.f;
-    const float dscale = drop ? 1.f / (1.f - hp.dropout) : 1.f;
-    const int64_t mcols[3] = {t->F, t->n0, t->n1};
-    if (drop) {
-        for (int i = 0; i < 3; ++i) {
-            if (dropout_masks && dropout_masks[i]) HIPT(t, hipMemcpy(t->d_mask[i], dropout_masks[i], (size_t)B * mcols[i], hipMemcpyHostToDevice));
-            else if (dropout_masks) return failt(t, DAN_ERR_INVALID_ARG, "dropout mask %d is null", i);
-            else launch_dropout_mask(t->d_mask[i], (long long)B * mcols[i], hp.dropout, seed, (unsigned long long)t->step * 3 + i, s);
-        }
-    }
-    const uint8_t* mk[3] = {drop ? t->d_mask[0] : nullptr, drop ? t->d_mask[1] : nullptr, drop ? t->d_mask[2] : nullptr};
-    HIPT(t, hipMemsetAsync(t->G, 0, (size_t)t->n_flat * sizeof(float), s));
-    refresh_packed(t, s);
-
-    int stat_entries = 0;                                    // entries of d_stats the last statistics-producing launch wrote
-    // =========================================== forward (train mode) ===========================================
-    for (int l = 0; l < NL; ++l) {
-        const LayerP& lp = t->layers[l];
-        const float* bias = t->d_bias + (size_t)l * 3 * CPAD;
-        float* coef_f = t->d_coef_f + (size_t)l * 3 * CPAD;
-        {   // a_l = relu(conv(u_l) + b), u_l = x_{l-1} (+ read-mean of x_{l-1} when layer l-1 pools; model.py:742,749)
-            RowArgs a{};
-            a.R = R; a.L = L;
-            if (l == 0) {
-                // layer 1 by table: the tables from this step's weights, then the walk (dan_train.hip)
-                fill_encode(a, t, B);
-                launch_l0_train_tables(pp(t, lp.conv_w), t->d_inv, a.emb, a.pe, L, lp.cout, lp.cin, t->d_l0tab, s);
-                stat_entries = launch_l0_train_forward(a, t->d_l0tab, bias, n_rows, t->d_a[l], c.use_bn ? t->d_stats : nullptr, s);
-                if (stat_entries > stat_cap) return failt(t, DAN_ERR_STATE, "layer 1's forward writes %d statistics entries, the buffer holds %d", stat_entries, stat_cap);
-            } else {
-            if (t->lazy_x[l - 1]) { a.mode = 1; a.src1 = t->d_a[l - 1]; a.s1_stride = CPAD; a.coef = t->d_coef_f + (size_t)(l - 1) * 3 * CPAD; }
-            else { a.mode = 1; a.src1 = t->d_x[l - 1]; a.s1_stride = CPAD; a.pool_in = t->d_pool[l]; }
-            a.w1 = t->pk_conv_f[l]; a.taps = 3; a.kg = lp.kg; a.dil = lp.dil;
-            if (t->wino_layer[l]) { a.w1 = t->pk_wino_f[l]; a.wino = 1; }
-            a.bias1 = bias; a.relu_out = 1; a.out1 = t->d_a[l];
-            a.stats = c.use_bn ? t->d_stats : nullptr;
-            stat_entries = launch_train_row(a, n_rows, s, stat_cap);
-            if ((rc = check_row_launch(t, stat_entries, "conv forward", l))) return rc;
-            }
-        }
-        if (c.use_bn) {                                      // batch statistics over (B, R, L) per channel (model.py:750-751, train mode)
-            int nb = 0;
-            launch_stats_partial(t->d_stats, stat_entries, t->d_bp, &nb, s);
-            launch_bn_forward_finalize(t->d_bp, nb, n_pos, pp(t, lp.bn_g), pp(t, lp.bn_b), lp.cout, coef_f, t->d_smean + (size_t)l * CPAD,
-                                       t->d_sinv + (size_t)l * CPAD, t->d_rmean + (size_t)l * CPAD, t->d_rvar + (size_t)l * CPAD, s);
-        }
-        {   // x_l = [W_r] bn(a_l) [+ b_r + x_{l-1}]  (model.py:753-761);  h_l = relu(W_b x_l + b_b)  (model.py:774)
-            RowArgs a{};
-            a.R = R; a.L = L; a.mode = 1; a.src1 = t->d_a[l]; a.s1_stride = CPAD; a.coef = coef_f;
-            if (lp.residual) { a.w1 = t->pk_res_f[l]; a.taps = 1; a.kg = KGC; a.dil = 0; a.bias1 = bias + CPAD; a.add1 = t->d_x[l - 1]; }
-            if (lp.residual && t->lazy_x[l - 1]) { a.add1 = t->d_a[l - 1]; a.add1_coef = t->d_coef_f + (size_t)(l - 1) * 3 * CPAD; }
-            a.out1 = t->d_x[l];                              // (nullptr for a lazy layer: the launch then only writes h_l)
-            if (H > 0) { a.w2 = t->pk_bot_f[l]; a.bias2 = bias + 2 * CPAD; a.out2 = t->d_h + (size_t)l * n_rows * L * HPAD; }
-            if ((rc = check_row_launch(t, launch_train_row(a, n_rows, s, stat_cap), "BatchNorm-apply / residual / bottleneck", l))) return rc;
-        }
-        if (pool_after(c, l + 1)) launch_read_mean(t->d_x[l], t->d_pool[l + 1], B, R, L, nullptr, s);
-    }
-    const long long h_layer = (long long)n_rows * L * HPAD;
-    launch_final_pool(t->d_x[NL - 1], t->d_feat, t->F_stride, B, R, L, c.c_final, nullptr, s);
-    if (H > 0)
-        launch_highway(t->d_h, h_layer, t->d_wc_pk, (long long)L * 2 * 2 * 256, t->d_bc_pad, t->d_feat, t->F_stride, 2 * c.c_final * L, B, R, L, H, NL, nullptr, s);
-    // FC stack: Dropout -> Linear -> ReLU -> Dropout -> Linear -> ReLU -> Dropout (model.py:369-377)
-    launch_dropout(t->d_feat, mk[0], dscale, t->d_featd, B, t->F, t->F_stride, s);
-    launch_gemm(t->d_featd, t->F_stride, 0, pp(t, t->p_fc0w), t->F_stride, 0, pp(t, t->p_fc0b), t->d_hid0, t->n0_stride, B, t->n0, (int)t->F_stride, 1, t->d_split_ws, t->split_ws_floats, s);
-    launch_dropout(t->d_hid0, mk[1], dscale, t->d_hid0d, B, t->n0, t->n0_stride, s);
-    launch_gemm(t->d_hid0d, t->n0_stride, 0, pp(t, t->p_fc1w), t->n0_stride, 0, pp(t, t->p_fc1b), t->d_hid1, t->n1_stride, B, t->n1, (int)t->n0_stride, 1, t->d_split_ws, t->split_ws_floats, s);
-    launch_dropout(t->d_hid1, mk[2], dscale, t->d_hid1d, B, t->n1, t->n1_stride, s);
-    {
-        LossArgs a{};
-        a.B = B; a.hid = t->n1; a.hid_stride = (int)t->n1_stride; a.hidden = t->d_hid1d; a.wh = pp(t, t->p_hw); a.bh = pp(t, t->p_hb);
-        a.label = t->d_tg8; a.var_type = t->d_tg8 + B; a.var_base = t->d_tg8 + 2 * B; a.var_ref = t->d_tg8 + 3 * B;
-        a.allele_freq = t->d_tgf; a.coverage = t->d_tgf + B; a.weight = t->d_tgf + 2 * B;
-        a.label_smoothing = hp.label_smoothing; a.close_window = hp.close_match_window; a.focal_alpha = hp.focal_alpha; a.focal_gamma = hp.focal_gamma;
-        a.fp_weight = hp.fp_train_weight; a.binary_weight = hp.binary_weight; a.aux_weight = hp.aux_weight;
-        a.aux_bases_weight = hp.aux_bases_weight; a.aux_allele_weight = hp.aux_allele_weight;
-        a.logits = t->d_logits; a.dlogits = t->d_dlogits; a.losses = t->d_losses; a.close = t->d_close; a.site_terms = t->d_site_terms;
-        a.mean_sites = t->dp_mean_sites; a.ce_den[0] = t->dp_ce_den[0]; a.ce_den[1] = t->dp_ce_den[1];
-        t->dp_mean_sites = 0.f; t->dp_ce_den[0] = t->dp_ce_den[1] = 0.f;
-        launch_heads_loss(a, s);
-    }
-
-    // ================================================= backward =================================================
-    // heads (their gradient tensors are contiguous in the flat buffer, like the weights)
-    launch_heads_bwd(t->d_dlogits, t->d_hid1d, pp(t, t->p_hw), B, t->n1, (int)t->n1_stride, t->d_dhid1d, gp(t, t->p_hw), gp(t, t->p_hb), s);
-    launch_dropout_relu_bwd(t->d_dhid1d, mk[2], dscale, t->d_hid1, 1, t->d_dhid1, B, t->n1, t->n1_stride, s);
-    // FC2: gW1[n][k] = sum_b d1[b][n] hid0d[b][k];  d(hid0d) = d1 W1
-    launch_gemm(t->d_dhid1, t->n1_stride, 1, t->d_hid0d, t->n0_stride, 1, nullptr, gp(t, t->p_fc1w), t->n0_stride, t->n1, t->n0, B, 0, t->d_split_ws, t->split_ws_floats, s);
-    launch_colsum(t->d_dhid1, B, t->n1, t->n1_stride, gp(t, t->p_fc1b), s);
-    launch_gemm(t->d_dhid1, t->n1_stride, 0, pp(t, t->p_fc1w), t->n0_stride, 1, nullptr, t->d_dhid0d, t->n0_stride, B, t->n0, t->n1, 0, t->d_split_ws, t->split_ws_floats, s);
-    launch_dropout_relu_bwd(t->d_dhid0d, mk[1], dscale, t->d_hid0, 1, t->d_dhid0, B, t->n0, t->n0_stride, s);
-    // FC1
-    launch_gemm(t->d_dhid0, t->n0_stride, 1, t->d_featd, t->F_stride, 1, nullptr, gp(t, t->p_fc0w), t->F_stride, t->n0, t->F, B, 0, t->d_split_ws, t->split_ws_floats, s);
-    launch_colsum(t->d_dhid0, B, t->n0, t->n0_stride, gp(t, t->p_fc0b), s);
-    HIPT(t, hipEventRecord(t->ev_tail, s));                  // bucket 0 (FC stack + heads: the tail of the flat buffer) is final
-    launch_gemm(t->d_dhid0, t->n0_stride, 0, pp(t, t->p_fc0w), t->F_stride, 1, nullptr, t->d_dfeatd, t->F_stride, B, t->F, t->n0, 0, t->d_split_ws, t->split_ws_floats, s);
-    launch_dropout_relu_bwd(t->d_dfeatd, mk[0], dscale, nullptr, 0, t->d_dfeat, B, t->F, t->F_stride, s);
-    // highway compression
-    const int hw_off = 2 * c.c_final * L;
-    if (H > 0) {
-        // dhw = dfeat_hw * (feat_hw > 0) as [layer][row][HPAD]; then one launch for every layer's dh (a 165-MB write stream per layer at
-        // 64 sites) and one for every layer's weight gradient (h read once, no split, straight into the torch layout)
-        launch_highway_dhw(t->d_dfeat, t->d_feat, t->F_stride, hw_off, t->d_dhw, B, R, H, NL, s);
-        launch_highway_dh(t->d_dhw, t->d_wct, t->d_dh, n_rows, L, NL, s);
-        launch_highway_gwc(t->d_dhw, t->d_h, t->G, t->d_cmpw_off, n_rows, L, H, NL, s);
-        // the compression biases' gradients of all layers (column sums of dhw) in two launches
-        launch_highway_bias_grad_all(t->d_dfeat, t->d_feat, t->F_stride, hw_off, t->d_bias_partial, t->G, t->d_cmpb_off, B, R, H, NL, s);
-    }
-    // final max + mean pool (model.py:824-839)
-    launch_final_pool_bwd(t->d_x[NL - 1], t->d_dfeat, t->F_stride, t->d_du, B, R, L, c.c_final, s);
-    int cur = 0;                                             // d_g[cur] receives g_l; d_g[cur ^ 1] holds g_{l+1}
-    bool fused_g = false;                                    // the previous iteration's data-gradient launch already wrote g_l into d_g[cur]
-    for (int l = NL - 1; l >= 0; --l) {
-        const LayerP& lp = t->layers[l];
-        const bool next_res = (l + 1 < NL) && t->layers[l + 1].residual;
-        const bool pooled = pool_after(c, l + 1);
-        float* g = t->d_g[cur];
-        const float* g_next = t->d_g[cur ^ 1];
-        if (fused_g) {       // g_l (and its statistics) came out of layer l+1's data-gradient launch, below in the previous iteration
-            fused_g = false;
-        } else {   // g_l = du_{l+1} (or the pool gradient) [+ g_{l+1} through the residual skip] [+ mean_r du_{l+1}] [+ W_b^T (dh_l * (h_l > 0))]
-            RowArgs a{};
-            a.R = R; a.L = L; a.mode = 1;
-            if (H > 0) {
-                a.src1 = t->d_dh + (size_t)l * h_layer; a.s1_stride = HPAD; a.src2 = t->d_h + (size_t)l * h_layer; a.mask_src2 = 1;
-                a.w1 = t->pk_bot_d[l]; a.taps = 1; a.kg = 2; a.dil = 0;
-                a.add1 = t->d_du;
-            } else {
-                a.src1 = t->d_du; a.s1_stride = CPAD;
-            }
-            a.add2 = next_res ? g_next : nullptr;
-            a.addb = pooled ? t->d_dpool : nullptr;
-            a.out1 = g;
-            if (!lp.residual) { a.stats = t->d_stats; a.stat_aux = t->d_a[l]; }
-            const int e = launch_train_row(a, n_rows, s, stat_cap);
-            if ((rc = check_row_launch(t, e, "g accumulation", l))) return rc;
-            if (!lp.residual) stat_entries = e;
-        }
-        const float* dn = g;
-        if (lp.residual) {   // x_l = W_r n_l + b_r + x_{l-1}:  dn_l = W_r^T g_l;  gW_r = g_l n_l^T;  g_{l-1} += g_l (next iteration's add2)
-            RowArgs a{};
-            a.R = R; a.L = L; a.mode = 1; a.src1 = g; a.s1_stride = CPAD;
-            a.w1 = t->pk_res_d[l]; a.taps = 1; a.kg = KGC; a.dil = 0;
-            a.out1 = t->d_dn; a.stats = t->d_stats; a.stat_aux = t->d_a[l];
-            stat_entries = launch_train_row(a, n_rows, s, stat_cap);
-            if ((rc = check_row_launch(t, stat_entries, "residual data gradient", l))) return rc;
-            dn = t->d_dn;
-            WgradArgs w{};
-            w.R = R; w.L = L; w.n_rows = n_rows; w.a1 = g; w.a_stride = CPAD;
-            w.b_mode = 1; w.b1 = t->d_a[l]; w.b_coef = t->d_coef_f + (size_t)l * 3 * CPAD;
-            w.taps = 1; w.dil = 0; w.o_tiles = KGC; w.c_tiles = KGC; w.partial = t->d_partial; w.bias_partial = t->d_bias_partial;
-            const int wgs = launch_train_wgrad(w, s);
-            launch_wgrad_reduce(t->d_partial, t->d_bias_partial, wgs, 1, CPAD, CPAD, lp.cout, lp.cout, nullptr, gp(t, lp.res_w), gp(t, lp.res_b), s);
-        }
-        {   // BatchNorm backward coefficients from sum(dn), sum(dn * a)  (identity without BatchNorm)
-            int nb = 0;
-            launch_stats_partial(t->d_stats, stat_entries, t->d_bp, &nb, s);
-            launch_bn_backward_coef(t->d_bp, nb, n_pos, pp(t, lp.bn_g), t->d_smean + (size_t)l * CPAD, t->d_sinv + (size_t)l * CPAD, lp.cout, c.use_bn,
-                                    t->d_coef_b, gp(t, lp.bn_g), gp(t, lp.bn_b), s);
-        }
-        if (H > 0) {         // h_l = relu(W_b x_l + b_b):  gW_b = (dh_l * (h_l > 0)) x_l^T
-            WgradArgs w{};
-            w.R = R; w.L = L; w.n_rows = n_rows; w.a1 = t->d_dh + (size_t)l * h_layer; w.a_stride = HPAD; w.a2 = t->d_h + (size_t)l * h_layer; w.a_mask = 1;
-            w.b_mode = 1; w.b1 = t->d_x[l];
-            if (t->lazy_x[l]) { w.b1 = t->d_a[l]; w.b_coef = t->d_coef_f + (size_t)l * 3 * CPAD; }
-            w.taps = 1; w.dil = 0; w.o_tiles = 2; w.c_tiles = KGC; w.partial = t->d_partial; w.bias_partial = t->d_bias_partial;
-            const int wgs = launch_train_wgrad(w, s);
-            launch_wgrad_reduce(t->d_partial, t->d_bias_partial, wgs, 1, 2 * 16, CPAD, H, lp.cout, nullptr, gp(t, lp.bot_w), gp(t, lp.bot_b), s);
-        }
-        if (l == 0) {
-            // layer 1: its weight and bias gradients AND the embedding gradient from one pass over dz_1 (dan_train.hip: layer 1's
-            // backward by bins) -- no encode-form GEMM, no data-gradient launch (its only reader was the embedding gradient)
-            WgradArgs w{};
-            w.R = R; w.L = L; w.n_rows = n_rows; w.a1 = dn; w.a_stride = CPAD; w.a2 = t->d_a[l]; w.a_coef = t->d_coef_b; w.a_mask = 1;
-            RowArgs e{};
-            fill_encode(e, t, B);
-            w.reads = e.reads; w.qual = e.qual; w.strand = e.strand; w.ref = e.ref; w.ref_mask = e.ref_mask; w.var_mask = e.var_mask;
-            w.emb = e.emb; w.pe = e.pe; w.partial = t->d_partial;
-            const int e0 = launch_l0_backward(w, B, t->d_l0tot, pp(t, lp.conv_w), t->d_canon, lp.cout, lp.cin, gp(t, lp.conv_w), gp(t, lp.conv_b), gp(t, t->p_emb), s);
-            if (e0) return failt(t, DAN_ERR_HIP, "layer 1's backward: the device refuses %d B of dynamic LDS for l0_bins_kernel: %s", l0_bins_lds_bytes(), hipGetErrorString((hipError_t)e0));
-            cur ^= 1;
-            continue;
-        }
-        {   // conv weight gradient: dz_l = (A dn + B a_l + C) * (a_l > 0);  gW[o][c][t] = sum_p dz[p][o] u_l[p + (t-1) d][c]
-            WgradArgs w{};
-            w.R = R; w.L = L; w.n_rows = n_rows; w.a1 = dn; w.a_stride = CPAD; w.a2 = t->d_a[l]; w.a_coef = t->d_coef_b; w.a_mask = 1;
-            w.b_mode = 1; w.b1 = t->d_x[l - 1]; w.b_pool = t->d_pool[l];
-            if (t->lazy_x[l - 1]) { w.b1 = t->d_a[l - 1]; w.b_coef = t->d_coef_f + (size_t)(l - 1) * 3 * CPAD; }
-            w.taps = 3; w.dil = lp.dil; w.o_tiles = KGC; w.c_tiles = KGC; w.partial = t->d_partial; w.bias_partial = t->d_bias_partial;
-            const int wgs = launch_train_wgrad(w, s);
-            launch_wgrad_reduce(t->d_partial, t->d_bias_partial, wgs, 3, CPAD, w.c_tiles * 16, lp.cout, lp.cin, nullptr, gp(t, lp.conv_w), gp(t, lp.conv_b), s);
-        }
-        {   // data gradient du_l = conv^T(dz_l)   (for layer 1: the gradient of the 48 encoded channels)
-            RowArgs a{};
-            a.R = R; a.L = L; a.mode = 1; a.src1 = dn; a.s1_stride = CPAD; a.src2 = t->d_a[l]; a.coef = t->d_coef_b; a.mask_src2 = 1;
-            a.w1 = t->pk_conv_d[l]; a.taps = 3; a.kg = KGC; a.dil = lp.dil;
-            if (t->wino_layer[l]) { a.w1 = t->pk_wino_d[l]; a.wino = 1; }
-            a.out1 = t->d_du;
-            // g_{l-1} = du_l + W_b^T (dh_{l-1} * (h_{l-1} > 0)) [+ g_l through the residual skip], with the statistics of layer l-1's
-            // BatchNorm backward: folded into this launch (half-read direct form) unless layer l-1 pools -- the read mean of du_l
-            // must exist before g_{l-1} does -- so that du_l is never written
-            // (train_row_fuses_second_product: the launcher's own predicate for the only kernel form that honours w3 -- the two
-            // conditions cannot drift apart, and launch_train_row refuses a w3 it would ignore)
-            if (l > 0 && H > 0 && !pool_after(c, l) && train_row_fuses_second_product(a)) {
-                const LayerP& lq = t->layers[l - 1];
-                a.w3 = t->pk_bot_d[l - 1]; a.src3 = t->d_dh + (size_t)(l - 1) * h_layer; a.src4 = t->d_h + (size_t)(l - 1) * h_layer;
-                a.add2 = lp.residual ? g : nullptr;
-                a.out1 = t->d_g[cur ^ 1];
-                if (!lq.residual) { a.stats = t->d_stats; a.stat_aux = t->d_a[l - 1]; }
-                fused_g = true;
-            }
-            const int e = launch_train_row(a, n_rows, s, stat_cap);
-            if ((rc = check_row_launch(t, e, "conv data gradient", l))) return rc;
-            if (fused_g && !t->layers[l - 1].residual) stat_entries = e;
-        }
-        if (l > 0 && pool_after(c, l)) launch_read_mean(t->d_du, t->d_dpool, B, R, L, nullptr, s);     // u_l = x_{l-1} + mean_r x_{l-1}
-        cur ^= 1;
-    }
+    Step st{};
+    st.B = (int)n_sites; st.n_rows = st.B * c.reads; st.n_pos = (double)st.n_rows * c.length; st.s = nullptr;
+    t->last_B = st.B;
+    const uint8_t* const planes[6] = {reads, qual, strand, ref, ref_mask, var_mask};
+    int rc;
+    if ((rc = stage_inputs(t, st, device_planes, ready, planes, tg)) || (rc = make_dropout_masks(t, st, dropout_masks, seed))) return rc;
+    HIPT(t, hipMemsetAsync(t->G, 0, (size_t)t->n_flat * sizeof(float), st.s));
+    if ((rc = refresh_packed(t, st.s))) return rc;
+    for (int l = 0; l < c.layers; ++l)
+        if ((rc = forward_layer(t, st, l))) return rc;
+    forward_tail(t, st);
+    if ((rc = backward_fc(t, st))) return rc;
+    backward_highway_pools(t, st);
+    for (int l = c.layers - 1; l >= 0; --l)
+        if ((rc = backward_layer(t, st, l))) return rc;
     HIPT(t, hipGetLastError());
     t->pending = true;
     return DAN_OK;
@@ -838,16 +861,39 @@ int backward_begin(dan_trainer_t* t, bool device_planes, void* ready, const uint
 
 extern "C" {
 
+const char* dan_train_last_error(const dan_trainer_t* t) { return t ? t->err.c_str() : g_create_error.c_str(); }
+
+int dan_train_create(const dan_config* cfg, const dan_train_hyper* hyper, int32_t max_batch, dan_trainer_t** out) {
+    return guarded(nullptr, "dan_train_create", [&] { return create(cfg, hyper, max_batch, out); });
+}
+
+int dan_train_set_tensor(dan_trainer_t* t, const char* name, const float* data, const int64_t* shape, int32_t ndim) {
+    return guarded(t, "dan_train_set_tensor", [&] { return set_tensor(t, name, data, shape, ndim); });
+}
+
+int dan_train_finalize(dan_trainer_t* t) {
+    return t ? guarded(t, "dan_train_finalize", [&] { return finalize(t); }) : DAN_ERR_INVALID_ARG;
+}
+
+void dan_train_destroy(dan_trainer_t* t) {
+    if (!t) return;
+    (void)hipSetDevice(t->cfg.device_id);
+    (void)hipDeviceSynchronize();
+    delete t;
+}
+
 int dan_train_backward_begin(dan_trainer_t* t, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, const uint8_t* ref,
                              const uint8_t* ref_mask, const uint8_t* var_mask, int64_t n_sites, const dan_train_targets* tg,
                              const uint8_t* const* dropout_masks, uint64_t seed) {
-    return backward_begin(t, false, nullptr, reads, qual, strand, ref, ref_mask, var_mask, n_sites, tg, dropout_masks, seed);
+    if (!t) return DAN_ERR_INVALID_ARG;
+    return guarded(t, "dan_train_backward_begin", [&] { return backward_begin(t, false, nullptr, reads, qual, strand, ref, ref_mask, var_mask, n_sites, tg, dropout_masks, seed); });
 }
 
 int dan_train_backward_begin_device(dan_trainer_t* t, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, const uint8_t* ref,
                                     const uint8_t* ref_mask, const uint8_t* var_mask, int64_t n_sites, const dan_train_targets* tg,
                                     const uint8_t* const* dropout_masks, uint64_t seed, void* ready_event) {
-    return backward_begin(t, true, ready_event, reads, qual, strand, ref, ref_mask, var_mask, n_sites, tg, dropout_masks, seed);
+    if (!t) return DAN_ERR_INVALID_ARG;
+    return guarded(t, "dan_train_backward_begin_device", [&] { return backward_begin(t, true, ready_event, reads, qual, strand, ref, ref_mask, var_mask, n_sites, tg, dropout_masks, seed); });
 }
 
 int dan_train_backward_end(dan_trainer_t* t, float* losses, uint8_t* close) {
@@ -965,8 +1011,7 @@ static int find_tensor(dan_trainer* t, const std::string& name, float** base, co
     return failt(t, DAN_ERR_INVALID_ARG, "no tensor '%s' in the training state", name.c_str());
 }
 
-int64_t dan_train_get_tensor(dan_trainer_t* t, const char* name, float* dst, int64_t capacity) {
-    if (!t || !name || !dst || capacity < 0) return DAN_ERR_INVALID_ARG;
+static int64_t get_tensor(dan_trainer_t* t, const char* name, float* dst, int64_t capacity) {
     if (!t->finalized) return failt(t, DAN_ERR_STATE, "dan_train_get_tensor before dan_train_finalize");
     HIPT(t, hipSetDevice(t->cfg.device_id));
     HIPT(t, hipDeviceSynchronize());
@@ -981,17 +1026,19 @@ int64_t dan_train_get_tensor(dan_trainer_t* t, const char* name, float* dst, int
         const int l = atoi(nm.c_str() + 5) - 1;
         if (l < 0 || l >= c.layers) return failt(t, DAN_ERR_INVALID_ARG, "'%s': no such layer", name);
         if (nm[4] == 'a') { src = t->d_a[l]; n = rows * c.length * CPAD; }
-        else if (nm[4] == 'x' && t->lazy_x[l]) {              // a layer whose x is never written: formed here for the tap
-            int rc0 = 0;
-            if (!t->d_xtap && (rc0 = talloc(t, &t->d_xtap, (size_t)t->max_batch * c.reads * c.length * CPAD, false))) return rc0;
-            RowArgs a{};
-            a.R = c.reads; a.L = c.length; a.mode = 1; a.src1 = t->d_a[l]; a.s1_stride = CPAD; a.coef = t->d_coef_f + (size_t)l * 3 * CPAD;
-            a.out1 = t->d_xtap;
-            launch_train_row(a, (int)rows, nullptr);
-            HIPT(t, hipDeviceSynchronize());
-            src = t->d_xtap; n = rows * c.length * CPAD;
-        } else if (nm[4] == 'x') { src = t->d_x[l]; n = rows * c.length * CPAD; }
-        else if (nm[4] == 'h' && t->d_h) { src = t->d_h + (size_t)l * rows * c.length * HPAD; n = rows * c.length * HPAD; }
+        else if (nm[4] == 'x') {
+            const XRef x = x_of(t, l);
+            src = x.p; n = rows * c.length * CPAD;
+            if (x.coef) {                                    // a layer whose x is never written: formed here for the tap
+                int rc0 = 0;
+                if (!t->d_xtap && (rc0 = talloc(t, &t->d_xtap, (size_t)t->max_batch * c.reads * c.length * CPAD, false))) return rc0;
+                RowArgs a = row_args(t);
+                a.src1 = x.p; a.s1_stride = CPAD; a.coef = x.coef; a.out1 = t->d_xtap;
+                launch_train_row(a, (int)rows, nullptr);
+                HIPT(t, hipDeviceSynchronize());
+                src = t->d_xtap;
+            }
+        } else if (nm[4] == 'h' && t->d_h) { src = h_of(t, l, rows); n = rows * c.length * HPAD; }
     } else if (nm == "feature") { src = t->d_feat; n = (int64_t)B * t->F_stride; }
     else if (nm == "dfeature") { src = t->d_dfeat; n = (int64_t)B * t->F_stride; }
     else if (nm == "du0")      // (was: the gradient of the encoded input; layer 1's backward no longer forms it -- dan_train.hip, layer 1's backward by bins)
@@ -1013,8 +1060,15 @@ int64_t dan_train_get_tensor(dan_trainer_t* t, const char* name, float* dst, int
     return n;
 }
 
-int dan_train_put_tensor(dan_trainer_t* t, const char* name, const float* src, int64_t count) {
-    if (!t || !name || !src) return DAN_ERR_INVALID_ARG;
+// (an entry that returns int64_t: the guard's code, or the body's count / code)
+int64_t dan_train_get_tensor(dan_trainer_t* t, const char* name, float* dst, int64_t capacity) {
+    if (!t || !name || !dst || capacity < 0) return DAN_ERR_INVALID_ARG;
+    int64_t n = 0;
+    const int rc = guarded(t, "dan_train_get_tensor", [&] { n = get_tensor(t, name, dst, capacity); return DAN_OK; });
+    return rc ? rc : n;
+}
+
+static int put_tensor(dan_trainer_t* t, const char* name, const float* src, int64_t count) {
     if (!t->finalized) return failt(t, DAN_ERR_STATE, "dan_train_put_tensor before dan_train_finalize");
     HIPT(t, hipSetDevice(t->cfg.device_id));
     float* base = nullptr;
@@ -1027,14 +1081,18 @@ int dan_train_put_tensor(dan_trainer_t* t, const char* name, const float* src, i
     return DAN_OK;
 }
 
+int dan_train_put_tensor(dan_trainer_t* t, const char* name, const float* src, int64_t count) {
+    if (!t || !name || !src) return DAN_ERR_INVALID_ARG;
+    return guarded(t, "dan_train_put_tensor", [&] { return put_tensor(t, name, src, count); });
+}
+
 int64_t dan_train_query(const dan_trainer_t* t, const char* what) {
     if (!t || !what) return DAN_ERR_INVALID_ARG;
-    const std::string w(what);
-    if (w == "step") return t->step;
-    if (w == "max_batch") return t->max_batch;
-    if (w == "num_param_floats") return t->n_flat;
-    if (w == "feature_stride") return t->F_stride;
-    if (w == "feature_width") return t->F;
+    if (!strcmp(what, "step")) return t->step;
+    if (!strcmp(what, "max_batch")) return t->max_batch;
+    if (!strcmp(what, "num_param_floats")) return t->n_flat;
+    if (!strcmp(what, "feature_stride")) return t->F_stride;
+    if (!strcmp(what, "feature_width")) return t->F;
     return failt(t, DAN_ERR_INVALID_ARG, "dan_train_query: unknown key '%s'", what);
 }
 

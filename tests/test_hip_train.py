@@ -710,3 +710,53 @@ def test_data_parallel_average_equals_the_full_batch_gradient():
             assert worst < 2e-5, sorted(errs.items(), key=lambda kv: -kv[1])[:4]
         else:
             assert worst > 1e-3, worst                            # (equal-weight averaging of unequal shards is not the full-batch mean)
+
+
+BACKWARD_STATE_CASES = [
+    # the smallest structure at which every branch of the schedule is taken: the shortest legal window, a pool after layer 2, residual
+    # layers from 3, a bottleneck (layers whose x is never written beside layers whose x is), BatchNorm
+    dict(length=8, reads=5, bottleneck=8, use_bn=True, sites=(3, 1)),
+    # half-read units of uneven length (33 + 32 columns), the weight-streaming FC forms on both sides of their 16-site limit, no highway
+    dict(length=65, reads=3, bottleneck=0, use_bn=False, sites=(17, 2)),
+]
+
+
+@pytest.mark.parametrize("case", BACKWARD_STATE_CASES, ids=lambda c: "L%d" % c["length"])
+def test_backward_is_a_function_of_the_parameters_and_the_batch_alone(case):
+    """One trainer, no dan_train_apply, host-supplied dropout masks (the step counter plays no part): backward on batch X, on a
+    batch Y of another size, on X again.  The third pass's gradients (every tensor), losses and close flags are the first's byte
+    for byte: nothing a pass leaves behind -- the statistics count, the g buffer in turn, a fused g, scratch sized by the batch --
+    reaches the next one.  No tolerance anywhere."""
+    BX, BY = case["sites"]
+    cfg = DanConfig(reads=case["reads"], length=case["length"], layers=4, pool_layers=(2,), residual_start=3, c_init=16, c_final=16,
+                    bottleneck=case["bottleneck"], use_bn=case["use_bn"], fc_sizes=(24, 12))
+    hp = TrainHyper(dropout=0.3)
+    sd = random_state_dict(cfg, seed=31)
+    rng = np.random.default_rng(32)
+
+    def batch(B, seed):
+        planes = synth.make_sites(B, reads=cfg.reads, length=cfg.length, seed=seed).arrays()
+        tg = {"label": rng.integers(0, 3, B), "var_type": rng.integers(0, 3, B), "allele_freq": rng.random(B).astype(np.float32),
+              "coverage": rng.integers(1, 90, B).astype(np.float32), "var_base_enum": rng.integers(0, 10, B),
+              "var_ref_enum": rng.integers(0, 10, B), "weight": np.ones(B, np.float32)}
+        masks = [(rng.random((B, w)) >= hp.dropout).astype(np.uint8) for w in (cfg.feature_width,) + tuple(cfg.fc_sizes)]
+        return planes, tg, masks
+
+    X, Y = batch(BX, 33), batch(BY, 34)
+    tr = DanTrainer(cfg, hp, max_batch=max(BX, BY)).load_state_dict(sd)
+
+    def backward(b):
+        out = tr.backward(b[0], b[1], dropout_masks=b[2])
+        return out, {k: tr.tensor("grad:" + k).copy() for k in tr._shapes if k.endswith((".weight", ".bias"))}
+
+    out1, g1 = backward(X)
+    out2, g2 = backward(Y)
+    out3, g3 = backward(X)
+    tr.close()
+    assert any(np.abs(g).max() > 0 for g in g1.values()) and out2["loss"] != out1["loss"]      # (the passes did something, Y is another batch)
+    assert len(g1) == 1 + 4 * 4 + 2 * 2 + (4 * 4 if cfg.bottleneck else 0) + 4 + 6 * 2      # every parameter tensor of the structure
+    for k in ("loss", "bin", "vt", "af", "cov", "vb", "vr"):
+        assert np.float32(out3[k]).tobytes() == np.float32(out1[k]).tobytes(), (k, out1[k], out3[k])
+    assert np.array_equal(out3["bin_close"], out1["bin_close"]) and np.array_equal(out3["vt_close"], out1["vt_close"])
+    for k, g in g1.items():
+        assert g3[k].tobytes() == g.tobytes(), "grad:%s differs after a pass on another batch (max |diff| %.3g)" % (k, float(np.abs(g3[k] - g).max()))
