@@ -21,8 +21,11 @@
 # candidates.hdf with the same records.
 # -l (on the path through candidates.hdf; an error with -d): main.py inflates the file's chunks and assembles its sites on the GPU
 # (--loader-device gpu); the scored VCF is the same.
+# -f (needs -r): the candidate generator walks the reads that have no MD tag against REFERENCE (--reference; whole contigs on the
+# GPU, 1 byte per base) instead of giving them no alleles; reads with an MD tag are walked by it as before.  Not passed by
+# default: without -f candidates.vcf is what it was.
 set -e
-usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-c [-y]] [-l]"; exit 1; }
+usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-f] [-c [-y]] [-l]"; exit 1; }
 GPUS=1
 PROCS=16
 DIRECT=0
@@ -30,7 +33,8 @@ INFLATE=""
 COMPRESS=""
 CODES=""
 LOADER=""
-while getopts "m:o:g:i:r:b:p:ldzcyh" opt; do
+FROMREF=""
+while getopts "m:o:g:i:r:b:p:fldzcyh" opt; do
   case $opt in
     m) MODEL=$OPTARG ;;
     o) OUTDIR=$OPTARG ;;
@@ -43,6 +47,7 @@ while getopts "m:o:g:i:r:b:p:ldzcyh" opt; do
     z) INFLATE=gpu ;;       # BGZF inflate and record framing on the GPU: candidate generation, and with -d the pileup encoder
     c) COMPRESS=gpu ;;      # candidates.hdf: pileups, record packing and chunk compression on the GPU
     y) CODES=dynamic ;;     # with -c: dynamic Huffman codes in the compressed chunks
+    f) FROMREF=1 ;;         # candidate generation: reads without MD are walked against REFERENCE
     l) LOADER=gpu ;;        # candidates.hdf is inflated and its sites assembled on the GPU (main.py --loader-device gpu)
     *) usage ;;
   esac
@@ -50,6 +55,7 @@ done
 [ -z "$MODEL" ] || [ -z "$OUTDIR" ] && usage
 [ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
 [ -n "$LOADER" ] && [ "$DIRECT" = 1 ] && { echo "-l loads candidates.hdf on the GPU and -d reads no candidates.hdf: give one of them"; exit 1; }
+[ -n "$FROMREF" ] && [ -z "$REFERENCE" ] && { echo "-f walks the reads without MD against the reference: give -r REFERENCE as well"; exit 1; }
 MULTI=""
 [ "$DIRECT" = 1 ] && [ "$GPUS" -gt 1 ] && MULTI=1
 SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -58,7 +64,7 @@ if [ ! -f "$OUTDIR/candidates.hdf" ] && [ ! -f "$OUTDIR/candidates.vcf" ] && [ -
   printf "Generate candidate VCF...\n"
   python "$SCRIPTDIR/tools/candidate_generator.py" --input "$BAM" --output "$OUTDIR/candidates.vcf" \
       --snp_min_freq 0.075 --indel_min_freq 0.02 ${BED:+--bedfile "$BED"} --keep_multialleles \
-      ${INFLATE:+--inflate-device "$INFLATE"} ${MULTI:+--gpus "$GPUS"} \
+      ${INFLATE:+--inflate-device "$INFLATE"} ${MULTI:+--gpus "$GPUS"} ${FROMREF:+--reference "$REFERENCE"} \
       > "$OUTDIR/candidate_generator.log" 2>&1
 fi
 if [ "$DIRECT" = 1 ]; then

@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_cand.so")
 MAX_ALLELE_LEN = 63          # CG_MAX_ALLELE_LEN
 SYMBOLS = ("cg_open", "cg_run", "cg_last_error", "cg_close", "cg_n_refs", "cg_ref_name", "cg_ref_length",
            "cg_set_inflate_device", "cg_get_inflate_stats", "cg_debug_ranges",
+           "cg_set_reference", "cg_get_reference_stats", "cg_reference_codes", "cg_reference_codes_host",
            "bz_inflate", "bz_inflate_host", "bz_status_text", "bz_last_error")
 INFLATE_DEVICES = ("gpu",)
 
@@ -47,6 +48,14 @@ class InflateStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ReferenceStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("reads", "contigs", "bases", "other_bytes")] + \
+               [(n, C.c_double) for n in ("read_ms", "upload_convert_ms")]
+
+    def as_dict(self) -> Dict[str, float]:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -70,6 +79,11 @@ def load_library() -> C.CDLL:
         lib.cg_get_inflate_stats.argtypes = [C.c_void_p, C.POINTER(InflateStats)]
         lib.cg_debug_ranges.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
                                         C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        lib.cg_set_reference.argtypes = [C.c_void_p, C.c_char_p]
+        lib.cg_get_reference_stats.argtypes = [C.c_void_p, C.POINTER(ReferenceStats)]
+        lib.cg_reference_codes.argtypes = [C.c_char_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64),
+                                           C.c_int]
+        lib.cg_reference_codes_host.argtypes = lib.cg_reference_codes.argtypes[:-1]
         lib.bz_inflate.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                    C.c_int]
         lib.bz_inflate_host.argtypes = lib.bz_inflate.argtypes[:-1]
@@ -115,14 +129,33 @@ def inflate_blocks(blocks: bytes, block_off, out, out_off, device: Optional[int]
     return [int(v) for v in status]
 
 
+def reference_codes(raw: bytes, linebases: int, linewidth: int, length: int, device: Optional[int] = None):
+    """The BAM nibble codes of the ``length`` bases in ``raw`` (a FASTA contig's bytes from its first base on, line breaks
+    included, ``linebases`` bases on lines of ``linewidth`` bytes) as a uint8 numpy array, and the count of bytes outside the
+    alphabet (read as N).  ``device`` None runs the rule on the CPU (``cg_reference_codes_host``), an ordinal runs the kernel on
+    that GPU (``cg_reference_codes``).  Raises RuntimeError when the layout does not describe the bytes."""
+    import numpy as np
+    lib = load_library()
+    raw = bytes(raw)
+    out = np.zeros(max(1, length), np.uint8)
+    other = C.c_int64()
+    args = [raw, len(raw), linebases, linewidth, length, out.ctypes.data, C.byref(other)]
+    rc = lib.cg_reference_codes_host(*args) if device is None else lib.cg_reference_codes(*args, int(device))
+    if rc != 0:
+        raise RuntimeError(lib.cg_last_error().decode())
+    return out[:max(0, length)], other.value
+
+
 class CandidateCounter:
     """One open BAM.  ``run(subregions)`` -> ``[(region_index, tid, pos0, ref, alt, depth, count)]`` (unordered) and stats.
     ``inflate_device="gpu"`` sends each batch's BGZF blocks to the device compressed (inflate, record walk and framing there;
-    needs the ``.bai``); the stats then carry ``inflate_*`` entries as well."""
+    needs the ``.bai``); the stats then carry ``inflate_*`` entries as well.  ``reference="ref.fa"``: a read without an MD tag is
+    walked against the FASTA's bases of its contig (whole contigs, resident on the device, 1 byte per base) instead of giving
+    no alleles; reads with MD are walked by their MD as before.  The stats then carry ``reference_*`` entries."""
 
     def __init__(self, bam_path: str, bai_path: Optional[str] = None, threads: Optional[int] = None,
                  max_len_indel_allele: int = 60, snp_min_freq: float = 0.01, indel_min_freq: float = 0.01, device: int = 0,
-                 inflate_device: Optional[str] = None):
+                 inflate_device: Optional[str] = None, reference: Optional[str] = None):
         if inflate_device is not None and inflate_device not in INFLATE_DEVICES:
             raise ValueError("inflate_device must be None or one of %s" % (INFLATE_DEVICES,))
         self.lib = load_library()
@@ -139,6 +172,11 @@ class CandidateCounter:
             msg = self.lib.cg_last_error().decode()
             self.close()
             raise RuntimeError("cg_set_inflate_device: %s" % msg)
+        self.reference = reference
+        if reference is not None and self.lib.cg_set_reference(h, os.fsencode(reference)) != 0:
+            msg = self.lib.cg_last_error().decode()
+            self.close()
+            raise RuntimeError("cg_set_reference: %s" % msg)
         n = self.lib.cg_n_refs(h)
         self.references: List[str] = [self.lib.cg_ref_name(h, i).decode() for i in range(n)]
         self.lengths: List[int] = [int(self.lib.cg_ref_length(h, i)) for i in range(n)]
@@ -157,6 +195,10 @@ class CandidateCounter:
             ist = InflateStats()
             self.lib.cg_get_inflate_stats(self.h, C.byref(ist))
             stats.update((k if k == "inflate_ms" else "inflate_" + k, v) for k, v in ist.as_dict().items())
+        if self.reference is not None:
+            rst = ReferenceStats()
+            self.lib.cg_get_reference_stats(self.h, C.byref(rst))
+            stats.update(("reference_" + k, v) for k, v in rst.as_dict().items())
         return res, stats
 
     def debug_ranges(self, tid: int, start: int, end: int):

@@ -7,23 +7,34 @@
 // With cg_set_inflate_device() the host does none of that: run_batch_device() takes the batch's byte ranges from the BAI bins,
 // reads their BGZF blocks as they are into pinned memory, and the device inflates them, walks the record chain, frames the
 // records and lists them per subregion (bgzf_kernels.hip); the same count / emit / filter kernels follow.
+//
+// With cg_set_reference() a read without MD is walked against the FASTA's bases of its contig: batch_refs() makes the contigs a
+// batch touches resident (load_contig(): the raw byte range read with fasta_native.h's index, uploaded, and turned into one code
+// per base by reference_codes_kernel) and hands the kernels one RefDesc per subregion, on either record path.
 #include "../../include/dl4vc_candgen.h"
 #include "bam_frame.h"
 #include "bam_native.h"
 #include "bgzf_device.h"
 #include "cand_device.h"
+#include "cand_reference.h"
+#include "fasta_native.h"
 
 #include <atomic>
 #include <chrono>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+namespace cand {
+std::string& last_error();     // this thread's error text (cand_reference_capi.cpp, with cg_last_error)
+}
+
 namespace {
 
-thread_local std::string g_err;
+thread_local std::string& g_err = cand::last_error();
 
 template <class... A>
 int fail(int code, const char* fmt, A... a) { return capi::failf(g_err, code, fmt, a...); }
@@ -56,6 +67,11 @@ struct cg_handle {   // (members are destroyed last to first: the stream outlive
     std::unique_ptr<bz::Framer, void (*)(bz::Framer*)> framer{nullptr, bz::framer_destroy};
     dev::Event ev[2];                           // around walk + frame
     cg_inflate_stats ist{};
+    // the reference source (cg_set_reference): whole contigs as codes, loaded at the first batch that touches them
+    std::string fasta_path;
+    std::unique_ptr<fastan::Fasta> fasta;
+    std::map<int32_t, dev::Buffer> contigs;     // tid -> exactly header.lengths[tid] bytes
+    cg_reference_stats rst{};
 };
 
 namespace {
@@ -115,6 +131,74 @@ void decode(const cand::DevCand& c, cg_candidate& o) {
     one[0] = seq[0];
 }
 
+// ---- the reference source ---------------------------------------------------------------------------------------------------
+// The contig of tid as codes in `codes` (exactly its length in bytes): its raw byte range, line breaks included, read from the
+// FASTA, uploaded and converted by reference_codes_kernel.  The caller has set the device and created the stream.
+int load_contig(cg_handle* h, int32_t tid, dev::Buffer& codes) {
+    namespace R = cand::refc;
+    const int64_t length = h->header.lengths[tid];
+    const char* name = h->header.refs[tid].c_str();
+    const char* fa = h->fasta_path.c_str();
+    const fastan::Fasta::Entry* e = h->fasta->entry(h->header.refs[tid]);
+    if (!e) return fail(-3, "reference: contig %s of the BAM header is not in %s", name, fa);
+    if (e->length != length)
+        return fail(-3, "reference: contig %s has %lld bases in %s and %lld in the BAM header: not the reference these reads were aligned to",
+                    name, (long long)e->length, fa, (long long)length);
+    if (!R::layout_ok(e->lb, e->lw, length) || e->offset < 0)
+        return fail(-3, "reference: contig %s: the index of %s gives lines of %lld bases in %lld bytes", name, fa, (long long)e->lb,
+                    (long long)e->lw);
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t span = R::raw_span(e->lb, e->lw, length);
+    std::vector<uint8_t> raw(span);
+    uint64_t got = 0;
+    if (span) {
+        if (fseeko(h->fasta->f, (off_t)e->offset, SEEK_SET) != 0) return fail(-3, "reference: cannot seek to contig %s in %s", name, fa);
+        got = fread(raw.data(), 1, span, h->fasta->f);       // (a short read leaves base positions past the bytes: refused below)
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+#define CG_TRY(x) DEV_TRY(g_err, "reference: ", x)
+    dev::Buffer d_raw;
+    dev::Array<unsigned long long> d_counts;
+    unsigned long long counts[2] = {0, R::NONE};
+    CG_TRY(codes.alloc((size_t)std::max<int64_t>(length, 1)));
+    CG_TRY(d_raw.alloc(got + 16));
+    CG_TRY(d_counts.alloc(2));
+    if (got) CG_TRY(hipMemcpy(d_raw.p, raw.data(), got, hipMemcpyHostToDevice));      // (pageable memory: complete on return)
+    CG_TRY(hipMemcpy(d_counts.p, counts, sizeof counts, hipMemcpyHostToDevice));
+    CG_TRY(cand::launch_reference_codes(d_raw.p, got, e->lb, e->lw, length, codes.p, d_counts.p, h->stream));
+    CG_TRY(hipStreamSynchronize(h->stream));
+    CG_TRY(hipMemcpy(counts, d_counts.p, sizeof counts, hipMemcpyDeviceToHost));
+#undef CG_TRY
+    if (counts[1] != R::NONE)
+        return fail(-3, "reference: contig %s: a line end, '>' or the end of the file at base %llu: the index of %s (lines of %lld bases in "
+                    "%lld bytes from offset %lld) does not describe the file", name, counts[1], fa, (long long)e->lb, (long long)e->lw,
+                    (long long)e->offset);
+    const auto t2 = std::chrono::steady_clock::now();
+    ++h->rst.contigs;
+    h->rst.bases += length;
+    h->rst.other_bytes += (int64_t)counts[0];
+    h->rst.read_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    h->rst.upload_convert_ms += std::chrono::duration<double, std::milli>(t2 - t1).count();
+    return 0;
+}
+
+// one RefDesc per subregion of the batch (none when the reference is off); contigs not yet resident are loaded
+int batch_refs(cg_handle* h, const cg_region* regions, int64_t b0, uint32_t n_subs, std::vector<cand::RefDesc>& refs) {
+    refs.clear();
+    if (!h->fasta) return 0;
+    refs.resize(n_subs);
+    for (uint32_t s = 0; s < n_subs; ++s) {
+        const int32_t tid = regions[b0 + s].tid;
+        auto it = h->contigs.find(tid);
+        if (it == h->contigs.end()) {
+            it = h->contigs.try_emplace(tid).first;
+            if (const int rc = load_contig(h, tid, it->second)) { h->contigs.erase(it); return rc; }
+        }
+        refs[s] = cand::RefDesc{it->second.p, h->header.lengths[tid]};
+    }
+    return 0;
+}
+
 // the counting kernels over what upload() / upload_device() left in the workspace, and the batch's results
 int finish_batch(cg_handle* h, const cg_region* regions, int64_t b0, uint64_t n_reads, uint32_t n_subs, int64_t cov, cg_stats& st) {
     const char* msg = nullptr;
@@ -137,6 +221,7 @@ int finish_batch(cg_handle* h, const cg_region* regions, int64_t b0, uint64_t n_
             default: break;
         }
         if (v & cand::ST_DEL_DROPPED) ++st.reads_deletions_dropped;
+        if (v & cand::ST_REFERENCE) ++h->rst.reads;
     }
     st.allele_events += (int64_t)n_events;
     st.alleles += (int64_t)n_unique;
@@ -194,6 +279,8 @@ int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg
     if (h->stream.ensure() != hipSuccess) return fail(-2, "hipStreamCreate failed");
     if (!h->ws) h->ws.reset(cand::workspace_create());
     if (!h->ws) return fail(-2, "cannot create the device workspace");
+    std::vector<cand::RefDesc> refs;
+    if (const int rc = batch_refs(h, regions, b0, n_subs, refs)) return rc;
     // gather into the pinned buffer, subregion by subregion
     uint64_t bytes = 0, n_reads = 0;
     for (auto& g : per) { bytes += g.bytes.size(); n_reads += g.meta.size(); }
@@ -218,7 +305,8 @@ int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg
     const auto t1 = std::chrono::steady_clock::now();
     st.host_frame_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
     const char* msg = nullptr;
-    if (cand::upload(h->ws.get(), h->pinned.p, bytes, meta.data(), n_reads, subs.data(), n_subs, cov, h->stream, &msg))
+    if (cand::upload(h->ws.get(), h->pinned.p, bytes, meta.data(), n_reads, subs.data(), refs.empty() ? nullptr : refs.data(), n_subs, cov,
+                     h->stream, &msg))
         return fail(-2, "device upload: %s", msg);
     if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(-2, "device upload failed");
     const auto t2 = std::chrono::steady_clock::now();
@@ -288,7 +376,10 @@ int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t
         subs[s].cov_base = cov;
         cov += (int64_t)rg.end - rg.start + 2;
     }
-    if (cand::upload_device(h->ws.get(), h->inflate.d_infl.p, meta_dev, subs.data(), n_subs, cov, h->stream, &msg))
+    std::vector<cand::RefDesc> refs;
+    if (const int rc = batch_refs(h, regions, b0, n_subs, refs)) return rc;
+    if (cand::upload_device(h->ws.get(), h->inflate.d_infl.p, meta_dev, subs.data(), refs.empty() ? nullptr : refs.data(), n_subs, cov,
+                            h->stream, &msg))
         return fail(-2, "device upload: %s", msg);
     return finish_batch(h, regions, b0, n_reads, n_subs, cov, st);
 }
@@ -296,8 +387,6 @@ int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t
 }  // namespace
 
 extern "C" {
-
-const char* cg_last_error(void) { return g_err.c_str(); }
 
 int cg_open(const char* bam_path, const char* bai_path, const cg_options* opt, cg_handle_t** out) {
     return capi::guarded(g_err, "cg_open", [&] {
@@ -326,6 +415,7 @@ int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg
         const auto t0 = std::chrono::steady_clock::now();
         cg_stats st{};
         h->ist = cg_inflate_stats{};
+        h->rst.reads = 0;
         h->out.clear();
         for (int64_t i = 0; i < n_regions; ++i) {
             const cg_region& r = regions[i];
@@ -365,6 +455,29 @@ int cg_set_inflate_device(cg_handle_t* h, int on) {
 int cg_get_inflate_stats(const cg_handle_t* h, cg_inflate_stats* out) {
     if (!h || !out) return fail(-1, "cg_get_inflate_stats: null argument");
     *out = h->ist;
+    return 0;
+}
+
+int cg_set_reference(cg_handle_t* h, const char* fasta_path) {
+    return capi::guarded(g_err, "cg_set_reference", [&] {
+        if (!h) return fail(-1, "cg_set_reference: null handle");
+        std::unique_ptr<fastan::Fasta> fa;
+        if (fasta_path && *fasta_path) {
+            std::string err;
+            fa.reset(new fastan::Fasta());
+            if (!fa->open(fasta_path, err)) return fail(-3, "reference: %s", err.c_str());
+        }
+        h->contigs.clear();                     // (codes of another file, or of none)
+        h->rst = cg_reference_stats{};
+        h->fasta = std::move(fa);
+        h->fasta_path = h->fasta ? fasta_path : "";
+        return 0;
+    });
+}
+
+int cg_get_reference_stats(const cg_handle_t* h, cg_reference_stats* out) {
+    if (!h || !out) return fail(-1, "cg_get_reference_stats: null argument");
+    *out = h->rst;
     return 0;
 }
 

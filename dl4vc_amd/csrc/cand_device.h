@@ -21,9 +21,17 @@ struct SubDesc {
     int64_t cov_base;    // first element of this subregion's coverage slot (end - start + 2 ints)
 };
 
-// per-read status (the low bits) and flag
+// the reference bases under one subregion (cg_set_reference): its contig's codes, one BAM nibble code per base, resident on the
+// device; a batch with a reference carries one per subregion, beside SubDesc
+struct RefDesc {
+    const uint8_t* codes;
+    int64_t length;
+};
+
+// per-read status (the low bits) and flags
 enum : uint8_t { ST_OK = 0, ST_NO_MD = 1, ST_NO_PAIRS = 2, ST_UNSUPPORTED = 3, ST_MALFORMED = 4 };
 constexpr uint8_t ST_DEL_DROPPED = 0x10;
+constexpr uint8_t ST_REFERENCE = 0x20;   // a read without MD, taken against the reference bases
 
 // Allele keys.  SNP: sub(24) | pos(32) | ref(4) | alt(4).  Indel: w[0] = sub(24) | pos(32) | kind(2) | len(6), then the bases
 // (anchor first: ALT of an insertion, REF of a deletion) as BAM nibble codes, 16 per word from the top.
@@ -53,14 +61,21 @@ Workspace* workspace_create();
 void workspace_destroy(Workspace* ws);
 // Runs one batch whose framed records are already on the device (ws buffers from upload()).  Returns 0 or a negative code
 // with msg set.  out / n_out: survivors in a host array owned by the workspace; status: one byte per read, host.
+// refs: one RefDesc per subregion (reads without MD are walked against them), or nullptr (such reads are ST_NO_MD).
 int upload(Workspace* ws, const uint8_t* recs, uint64_t rec_bytes, const ReadMeta* meta, uint64_t n_reads,
-           const SubDesc* subs, uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg);
+           const SubDesc* subs, const RefDesc* refs, uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg);
 // The same for records and meta that are already on the device (the BGZF path, bgzf_device.h): they are used in place and must
 // stay valid until run_batch() returns.
-int upload_device(Workspace* ws, const uint8_t* recs_dev, const ReadMeta* meta_dev, const SubDesc* subs, uint32_t n_subs,
-                  int64_t cov_len, hipStream_t stream, const char** msg);
+int upload_device(Workspace* ws, const uint8_t* recs_dev, const ReadMeta* meta_dev, const SubDesc* subs, const RefDesc* refs,
+                  uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg);
 int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len, int max_len, double snp_min, double indel_min,
               hipStream_t stream, const DevCand** out, uint64_t* n_out, const uint8_t** status, uint64_t* n_events,
               uint64_t* n_unique, BatchTimes* t, const char** msg);
+
+// Reference bases (cand_reference.h has the rule): raw_dev[0, raw_len) -> out_dev[0, length), on the stream.  counts_dev[0]
+// gains the bytes outside the alphabet, counts_dev[1] takes the minimum with the first base that is a line end, '>' or past
+// raw_len (the caller sets them to 0 and refc::NONE first).  Needs refc::layout_ok(lb, lw, length).
+hipError_t launch_reference_codes(const uint8_t* raw_dev, uint64_t raw_len, int64_t lb, int64_t lw, int64_t length, uint8_t* out_dev,
+                                  unsigned long long* counts_dev, hipStream_t stream);
 
 }  // namespace cand

@@ -16,8 +16,11 @@
 //   * an allele whose REF or ALT is longer than max_len is dropped; only alleles at start <= pos <= end count.
 // A read whose MD does not agree with its CIGAR (runs past it, ends short, a '^' run of the wrong length, a letter outside the
 // BAM alphabet) is marked malformed and gives no alleles.  Every byte read is bounded by the read's framed length.
+// A read without MD gives coverage and no alleles, unless the batch carries the reference bases of its contig (cg_set_reference):
+// then the same walk takes them from there (RefSeq below; reference_codes_kernel makes them of the FASTA's bytes).
 #include "bam_frame.h"
 #include "cand_device.h"
+#include "cand_reference.h"
 #include "device_buffer.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -109,6 +112,29 @@ struct Md {
     }
 };
 
+// The other source of reference bases, for a read without MD (cg_set_reference): the contig's codes at the walk's own
+// reference position.  An aligned base is a mismatch when the codes differ or the read's is N (samtools calmd's rule, so the
+// letter an MD tag would carry is the code returned here); a position outside the contig makes the read malformed, as an MD
+// that runs past its CIGAR does, and no byte outside codes[0, length) is read.
+struct RefSeq {
+    const uint8_t* codes;
+    int64_t length, at;
+    bool bad;
+
+    __device__ int next() {
+        if ((uint64_t)at >= (uint64_t)length) { bad = true; return 0; }
+        return codes[at++];
+    }
+    __device__ int match(int rc, bool& mism) {
+        const int code = next();
+        mism = code != rc || rc == 15;
+        return code;
+    }
+    __device__ int del() { return next(); }
+    __device__ void end_del() {}
+    __device__ void finish() {}
+};
+
 struct Sink {
     // count mode (keys == nullptr) or emit mode
     uint64_t* snp;
@@ -133,10 +159,10 @@ struct Walk {
 
     __device__ int read_code(int q) const { return (q & 1) ? (seq[q >> 1] & 0xf) : (seq[q >> 1] >> 4); }
 
-    // dry = true: only the MD walk, returning the last pair (the anchor of a deletion run at the first pair)
-    __device__ bool run(bool dry, Pair last_pair, Sink& out, Pair* last_out) const {
-        Md md{nullptr, 0, 0, 0, false, false};
-        md.p = md_p; md.n = md_n;
+    // md: the read's reference source at its start (Md or RefSeq), taken by value: each run walks it from the beginning.
+    // dry = true: only the walk of the source, returning the last pair (the anchor of a deletion run at the first pair)
+    template <class Ref>
+    __device__ bool run(Ref md, bool dry, Pair last_pair, Sink& out, Pair* last_out) const {
         int32_t rp = pos;
         int qp = 0;
         Pair prev{-1, 0, 0};
@@ -222,14 +248,23 @@ struct Walk {
         if (last_out) *last_out = prev;
         return true;
     }
-    const uint8_t* md_p;
-    int md_n;
+
+    // the dry run for a deletion run at the first pair, then the run that counts or emits
+    template <class Ref>
+    __device__ bool run_read(const Ref& src, Sink& out) const {
+        Pair last{-1, 0, 0};
+        Sink dry{nullptr, nullptr, 0, 0};
+        if ((ld32(cig + 4 * k0) & 0xf) == OP_D) {
+            if (!run(src, true, last, dry, &last)) return false;
+        }
+        return run(src, false, last, out, nullptr);
+    }
 };
 
 // Shared by both passes: frames the read (again, on the device), adds its coverage events (count pass), and walks it.
 template <bool EMIT>
-__device__ void process_read(const uint8_t* __restrict__ buf, const ReadMeta& m, const SubDesc* __restrict__ subs, int max_len,
-                             int* __restrict__ cov, Sink& out, uint8_t& status) {
+__device__ void process_read(const uint8_t* __restrict__ buf, const ReadMeta& m, const SubDesc* __restrict__ subs,
+                             const RefDesc* __restrict__ refs, int max_len, int* __restrict__ cov, Sink& out, uint8_t& status) {
     const uint8_t* b = buf + m.off;
     const uint32_t len = m.len;
     status = ST_MALFORMED;
@@ -260,8 +295,12 @@ __device__ void process_read(const uint8_t* __restrict__ buf, const ReadMeta& m,
             if (aligned_op(op) || op == OP_D || op == OP_N) rp += l;
         }
     }
-    if (m.md_off < 0) { status = ST_NO_MD; return; }
-    if ((uint64_t)m.md_off + (uint64_t)(m.md_len < 0 ? 0 : m.md_len) > len) return;
+    // the reference source: the read's MD when it has one (whatever it says), else the contig's bases when the batch has them
+    const bool from_ref = m.md_off < 0;
+    if (from_ref && !refs) { status = ST_NO_MD; return; }
+    if (!from_ref && (uint64_t)m.md_off + (uint64_t)(m.md_len < 0 ? 0 : m.md_len) > len) return;
+    const uint8_t flag = from_ref ? ST_REFERENCE : 0;
+    status = ST_MALFORMED | flag;
     int k0 = -1, k1 = -1;
     int64_t qlen = 0;
     bool unsupported = l_seq == 0, bad_op = false, dd = false;
@@ -275,8 +314,8 @@ __device__ void process_read(const uint8_t* __restrict__ buf, const ReadMeta& m,
         if ((aligned_op(op) || op == OP_D) && (c >> 4) > 0) { if (k0 < 0) k0 = k; k1 = k; }
     }
     if (bad_op) return;
-    if (k0 < 0) { status = ST_NO_PAIRS; return; }
-    if (unsupported) { status = ST_UNSUPPORTED; return; }
+    if (k0 < 0) { status = ST_NO_PAIRS | flag; return; }
+    if (unsupported) { status = ST_UNSUPPORTED | flag; return; }
     if (qlen != l_seq) return;
     for (int k = k0; k <= k1; ++k) {
         const uint32_t c = ld32(cig + 4 * k);
@@ -290,38 +329,40 @@ __device__ void process_read(const uint8_t* __restrict__ buf, const ReadMeta& m,
     Walk w;
     w.cig = cig; w.seq = b + seq_off; w.n_cig = n_cig; w.k0 = k0; w.k1 = k1; w.pos = pos;
     w.lo = sd.start; w.hi = sd.end; w.sub = m.sub; w.max_len = max_len; w.del_dropped = dd;
-    w.md_p = b + m.md_off; w.md_n = m.md_len;
-    Pair last{-1, 0, 0};
-    Sink dry{nullptr, nullptr, 0, 0};
-    if ((ld32(cig + 4 * k0) & 0xf) == OP_D) {
-        if (!w.run(true, last, dry, &last)) return;
+    bool ok;
+    if (from_ref) {
+        const RefDesc rd = refs[m.sub];
+        ok = w.run_read(RefSeq{rd.codes, rd.length, (int64_t)pos, false}, out);
+    } else {
+        ok = w.run_read(Md{b + m.md_off, m.md_len, 0, 0, false, false}, out);
     }
-    if (!w.run(false, last, out, nullptr)) { out.n_snp = out.n_indel = 0; return; }
-    status = dd ? (uint8_t)(ST_OK | ST_DEL_DROPPED) : ST_OK;
+    if (!ok) { out.n_snp = out.n_indel = 0; return; }
+    status = (uint8_t)((dd ? ST_OK | ST_DEL_DROPPED : ST_OK) | flag);
 }
 
 __global__ void count_kernel(const uint8_t* __restrict__ buf, const ReadMeta* __restrict__ meta, uint64_t n,
-                             const SubDesc* __restrict__ subs, int max_len, int* __restrict__ cov, uint32_t* __restrict__ n_snp,
-                             uint32_t* __restrict__ n_indel, uint8_t* __restrict__ status) {
+                             const SubDesc* __restrict__ subs, const RefDesc* __restrict__ refs, int max_len, int* __restrict__ cov,
+                             uint32_t* __restrict__ n_snp, uint32_t* __restrict__ n_indel, uint8_t* __restrict__ status) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     Sink s{nullptr, nullptr, 0, 0};
     uint8_t st;
-    process_read<false>(buf, meta[r], subs, max_len, cov, s, st);
+    process_read<false>(buf, meta[r], subs, refs, max_len, cov, s, st);
     n_snp[r] = s.n_snp;
     n_indel[r] = s.n_indel;
     status[r] = st;
 }
 
 __global__ void emit_kernel(const uint8_t* __restrict__ buf, const ReadMeta* __restrict__ meta, uint64_t n,
-                            const SubDesc* __restrict__ subs, int max_len, const uint32_t* __restrict__ snp_off,
-                            const uint32_t* __restrict__ indel_off, const uint32_t* __restrict__ n_snp,
-                            const uint32_t* __restrict__ n_indel, uint64_t* __restrict__ snp_keys, IndelKey* __restrict__ indel_keys) {
+                            const SubDesc* __restrict__ subs, const RefDesc* __restrict__ refs, int max_len,
+                            const uint32_t* __restrict__ snp_off, const uint32_t* __restrict__ indel_off,
+                            const uint32_t* __restrict__ n_snp, const uint32_t* __restrict__ n_indel, uint64_t* __restrict__ snp_keys,
+                            IndelKey* __restrict__ indel_keys) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n || (n_snp[r] == 0 && n_indel[r] == 0)) return;
     Sink s{snp_keys + snp_off[r], indel_keys + indel_off[r], 0, 0};
     uint8_t st;
-    process_read<true>(buf, meta[r], subs, max_len, nullptr, s, st);
+    process_read<true>(buf, meta[r], subs, refs, max_len, nullptr, s, st);
 }
 
 __device__ inline void keep_if(const SubDesc* subs, const int* depth, uint32_t sub, int32_t pos, uint32_t count, bool snp,
@@ -366,6 +407,26 @@ __global__ void filter_indel_kernel(const IndelKey* __restrict__ keys, const uin
     out[atomicAdd(n_out, 1u)] = c;
 }
 
+// Reference bases: four bases per lane, one 32-bit store where all four exist (out is a device allocation, p a multiple of 4).
+__global__ void reference_codes_kernel(const uint8_t* __restrict__ raw, uint64_t raw_len, int64_t lb, int64_t lw, int64_t length,
+                                       uint8_t* __restrict__ out, unsigned long long* __restrict__ counts) {
+    const int64_t p0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (p0 >= length) return;
+    uint32_t word = 0, other = 0;
+    int64_t broken = -1;
+    const int n = (int)min((int64_t)4, length - p0);
+    for (int j = 0; j < n; ++j) {
+        const int c = refc::base_code(raw, raw_len, lb, lw, p0 + j);
+        if (c == refc::BROKEN && broken < 0) broken = p0 + j;
+        if (c == refc::OTHER) ++other;
+        word |= (uint32_t)(c >= refc::OTHER ? 15 : c) << (8 * j);
+    }
+    if (n == 4) *(uint32_t*)(out + p0) = word;
+    else for (int j = 0; j < n; ++j) out[p0 + j] = (uint8_t)(word >> (8 * j));
+    if (other) atomicAdd(counts + 0, (unsigned long long)other);
+    if (broken >= 0) atomicMin(counts + 1, (unsigned long long)broken);
+}
+
 struct IndelDecomposer {
     __host__ __device__ ::rocprim::tuple<uint64_t&, uint64_t&, uint64_t&, uint64_t&, uint64_t&> operator()(IndelKey& k) const {
         return ::rocprim::tuple<uint64_t&, uint64_t&, uint64_t&, uint64_t&, uint64_t&>(k.w[0], k.w[1], k.w[2], k.w[3], k.w[4]);
@@ -375,12 +436,13 @@ struct IndelDecomposer {
 }  // namespace
 
 struct Workspace {
-    dev::Buffer recs, meta, subs, cov, depth, n_snp, n_indel, snp_off, indel_off, status, snp_keys, snp_sorted, indel_keys, indel_sorted,
+    dev::Buffer recs, meta, subs, refs, cov, depth, n_snp, n_indel, snp_off, indel_off, status, snp_keys, snp_sorted, indel_keys, indel_sorted,
         snp_unique, snp_counts, indel_unique, indel_counts, scalars, cands, temp;
     std::vector<uint8_t> h_status;
     std::vector<DevCand> h_cands;
     const uint8_t* recs_p = nullptr;      // the batch's records and their meta: ws->recs / ws->meta after upload(), the
     const ReadMeta* meta_p = nullptr;     // caller's device buffers after upload_device()
+    const RefDesc* refs_p = nullptr;      // the batch's reference bases per subregion (ws->refs), nullptr without a reference
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
@@ -396,27 +458,37 @@ void workspace_destroy(Workspace* ws) {
     delete ws;
 }
 
-int upload(Workspace* ws, const uint8_t* recs, uint64_t rec_bytes, const ReadMeta* meta, uint64_t n_reads, const SubDesc* subs,
-           uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg) {
-    HIP_CHECK_MSG(ws->recs.ensure(rec_bytes + 1));
-    HIP_CHECK_MSG(ws->meta.ensure((n_reads + 1) * sizeof(ReadMeta)));
+// the batch's subregions, their reference bases (or none) and an empty coverage array
+static int upload_subs(Workspace* ws, const SubDesc* subs, const RefDesc* refs, uint32_t n_subs, int64_t cov_len, hipStream_t stream,
+                       const char** msg) {
     HIP_CHECK_MSG(ws->subs.ensure((n_subs + 1) * sizeof(SubDesc)));
     HIP_CHECK_MSG(ws->cov.ensure((size_t)(cov_len + 1) * sizeof(int)));
-    if (rec_bytes) HIP_CHECK_MSG(hipMemcpyAsync(ws->recs.p, recs, rec_bytes, hipMemcpyHostToDevice, stream));
-    if (n_reads) HIP_CHECK_MSG(hipMemcpyAsync(ws->meta.p, meta, n_reads * sizeof(ReadMeta), hipMemcpyHostToDevice, stream));
     HIP_CHECK_MSG(hipMemcpyAsync(ws->subs.p, subs, n_subs * sizeof(SubDesc), hipMemcpyHostToDevice, stream));
     HIP_CHECK_MSG(hipMemsetAsync(ws->cov.p, 0, (size_t)cov_len * sizeof(int), stream));
+    ws->refs_p = nullptr;
+    if (refs) {
+        HIP_CHECK_MSG(ws->refs.ensure((n_subs + 1) * sizeof(RefDesc)));
+        HIP_CHECK_MSG(hipMemcpyAsync(ws->refs.p, refs, n_subs * sizeof(RefDesc), hipMemcpyHostToDevice, stream));
+        ws->refs_p = ws->refs.as<const RefDesc>();
+    }
+    return 0;
+}
+
+int upload(Workspace* ws, const uint8_t* recs, uint64_t rec_bytes, const ReadMeta* meta, uint64_t n_reads, const SubDesc* subs,
+           const RefDesc* refs, uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg) {
+    HIP_CHECK_MSG(ws->recs.ensure(rec_bytes + 1));
+    HIP_CHECK_MSG(ws->meta.ensure((n_reads + 1) * sizeof(ReadMeta)));
+    if (rec_bytes) HIP_CHECK_MSG(hipMemcpyAsync(ws->recs.p, recs, rec_bytes, hipMemcpyHostToDevice, stream));
+    if (n_reads) HIP_CHECK_MSG(hipMemcpyAsync(ws->meta.p, meta, n_reads * sizeof(ReadMeta), hipMemcpyHostToDevice, stream));
+    if (const int rc = upload_subs(ws, subs, refs, n_subs, cov_len, stream, msg)) return rc;
     ws->recs_p = ws->recs.as<const uint8_t>();
     ws->meta_p = ws->meta.as<const ReadMeta>();
     return 0;
 }
 
-int upload_device(Workspace* ws, const uint8_t* recs_dev, const ReadMeta* meta_dev, const SubDesc* subs, uint32_t n_subs,
-                  int64_t cov_len, hipStream_t stream, const char** msg) {
-    HIP_CHECK_MSG(ws->subs.ensure((n_subs + 1) * sizeof(SubDesc)));
-    HIP_CHECK_MSG(ws->cov.ensure((size_t)(cov_len + 1) * sizeof(int)));
-    HIP_CHECK_MSG(hipMemcpyAsync(ws->subs.p, subs, n_subs * sizeof(SubDesc), hipMemcpyHostToDevice, stream));
-    HIP_CHECK_MSG(hipMemsetAsync(ws->cov.p, 0, (size_t)cov_len * sizeof(int), stream));
+int upload_device(Workspace* ws, const uint8_t* recs_dev, const ReadMeta* meta_dev, const SubDesc* subs, const RefDesc* refs,
+                  uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg) {
+    if (const int rc = upload_subs(ws, subs, refs, n_subs, cov_len, stream, msg)) return rc;
     ws->recs_p = recs_dev;
     ws->meta_p = meta_dev;
     return 0;
@@ -444,7 +516,7 @@ int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len,
     const unsigned grid = (unsigned)((n_reads + TB - 1) / TB);
     if (n_reads) {
         hipLaunchKernelGGL(count_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs_p, ws->meta_p,
-                           n_reads, ws->subs.as<const SubDesc>(), max_len, ws->cov.as<int>(), ws->n_snp.as<uint32_t>(),
+                           n_reads, ws->subs.as<const SubDesc>(), ws->refs_p, max_len, ws->cov.as<int>(), ws->n_snp.as<uint32_t>(),
                            ws->n_indel.as<uint32_t>(), ws->status.as<uint8_t>());
         HIP_CHECK_MSG(hipGetLastError());
     }
@@ -483,7 +555,7 @@ int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len,
     HIP_CHECK_MSG(ws->cands.ensure((ns + ni + 1) * sizeof(DevCand)));
     if (ns + ni > 0) {
         hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs_p, ws->meta_p,
-                           n_reads, ws->subs.as<const SubDesc>(), max_len, ws->snp_off.as<const uint32_t>(),
+                           n_reads, ws->subs.as<const SubDesc>(), ws->refs_p, max_len, ws->snp_off.as<const uint32_t>(),
                            ws->indel_off.as<const uint32_t>(), ws->n_snp.as<const uint32_t>(), ws->n_indel.as<const uint32_t>(),
                            ws->snp_keys.as<uint64_t>(), ws->indel_keys.as<IndelKey>());
         HIP_CHECK_MSG(hipGetLastError());
@@ -537,6 +609,16 @@ int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len,
     HIP_CHECK_MSG(hipEventElapsedTime(&ms, ws->ev0, ws->ev1));
     t->device_ms = ms;
     return 0;
+}
+
+hipError_t launch_reference_codes(const uint8_t* raw_dev, uint64_t raw_len, int64_t lb, int64_t lw, int64_t length, uint8_t* out_dev,
+                                  unsigned long long* counts_dev, hipStream_t stream) {
+    if (length <= 0) return hipSuccess;
+    const int TB = 256;
+    const int64_t lanes = (length + 3) / 4;
+    hipLaunchKernelGGL(reference_codes_kernel, dim3((unsigned)((lanes + TB - 1) / TB)), dim3(TB), 0, stream, raw_dev, raw_len, lb, lw, length,
+                       out_dev, counts_dev);
+    return hipGetLastError();
 }
 
 }  // namespace cand

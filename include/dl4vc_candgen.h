@@ -74,6 +74,17 @@ typedef struct {
     double walk_frame_ms;          /* device events around the walk, frame, scan and emit passes */
 } cg_inflate_stats;
 
+/* What the reference source did (all zero when it is off).  reads is of the last cg_run; the rest describe the contigs that are
+ * resident now and the one-time cost of loading them, summed since cg_set_reference. */
+typedef struct {
+    int64_t reads;                 /* reads without MD taken against the FASTA (a read in two subregions counts twice) */
+    int64_t contigs;               /* contigs resident on the device */
+    int64_t bases;                 /* their bases = their bytes on the device */
+    int64_t other_bytes;           /* bytes outside "=ACMGRSVTWYHKDBN" (either case) at base positions: read as N */
+    double read_ms;                /* host: the contigs' raw byte ranges read from the FASTA */
+    double upload_convert_ms;      /* host -> device copy of the raw bytes and the kernel that makes codes of them */
+} cg_reference_stats;
+
 int cg_open(const char* bam_path, const char* bai_path /* NULL or "": linear scan */, const cg_options* opt,
             cg_handle_t** out);
 /* Runs every region (internally in batches).  On success *out points at n_out candidates owned by the handle, valid until the
@@ -87,6 +98,23 @@ int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg
  * meaning (host wall time in front of the device work). */
 int cg_set_inflate_device(cg_handle_t* h, int on);
 int cg_get_inflate_stats(const cg_handle_t* h, cg_inflate_stats* out);
+/* fasta_path: a read WITHOUT an MD tag is walked against the bases of its contig in this FASTA (indexed by fasta_path.fai when
+ * that file exists, else scanned once), in the same kernels; a read WITH an MD tag is walked by its MD as before, whatever the
+ * FASTA says.  NULL or "": off again (such reads count in cg_stats.reads_no_md and give no alleles), and the resident contigs
+ * are freed.  A contig is read, uploaded and converted to one byte per base the first time a cg_run touches it and stays on the
+ * device for the handle's life: 1 byte per base, whole contigs, no eviction.  Fails here when the FASTA cannot be opened; cg_run
+ * fails, naming the contig, when the FASTA lacks a contig it needs, when its length there differs from the BAM header's (both
+ * lengths are given), or when the index does not describe the file (a line end or '>' at a base position). */
+int cg_set_reference(cg_handle_t* h, const char* fasta_path);
+int cg_get_reference_stats(const cg_handle_t* h, cg_reference_stats* out);
+/* For tests: the conversion cg_set_reference applies, on raw[0, raw_len) = the contig's bytes from its first base on, line
+ * breaks included: out[p] = the BAM nibble code of base p for p < length, *n_other = the bytes read as N for being outside the
+ * alphabet.  cg_reference_codes_host runs the rule on the CPU, cg_reference_codes the kernel on `device`.  -3 when a base
+ * position holds a line end or '>' or lies past raw_len (out is then unspecified). */
+int cg_reference_codes_host(const uint8_t* raw, uint64_t raw_len, int64_t linebases, int64_t linewidth, int64_t length,
+                            uint8_t* out, int64_t* n_other);
+int cg_reference_codes(const uint8_t* raw, uint64_t raw_len, int64_t linebases, int64_t linewidth, int64_t length, uint8_t* out,
+                       int64_t* n_other, int device);
 /* For tests: the byte ranges and walk boundaries the device path would use for one region, as BGZF virtual offsets.
  * ranges: n_ranges pairs [begin, end), merged and sorted; bounds: every walk boundary (range ends included), sorted.  At most
  * cap_* entries are written; the counts are always the full ones.  Reads the index only. */

@@ -5,10 +5,15 @@ host's inflate-and-frame time against the device time (per-stage device times co
 ``rocprofv3 --kernel-trace --stats`` run of this tool).
 
     python tools/candgen_rate.py --bam /tmp/cg_rate.bam [--reads 2000000 --length 10000000] [--out profiles/x.json]
-        [--inflate-device gpu] [--chunk_size 1000]
+        [--inflate-device gpu] [--chunk_size 1000] [--no-md] [--fasta REF.fa] [--reference REF.fa]
 
 ``--inflate-device gpu`` measures the device inflate path (the line then carries its read / inflate / walk-and-frame times);
 ``--chunk_size`` other than 1000 changes the subregions, and with them the candidates at their boundaries: a timing line only.
+
+The reference arm: ``--no-md`` writes the same reads without aux tags (when ``--bam`` has to be made), ``--fasta`` writes the
+genome they were drawn from beside it (60 bases a line, with its ``.fai``), and ``--reference REF.fa`` walks the reads that have
+no MD tag against it; the line then carries the ``reference_*`` figures.  Every repeat opens its own handle, so the contig's
+one-time load (read, upload and convert) is inside every repeat's wall time.
 """
 import argparse
 import json
@@ -22,12 +27,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dl4vc_amd.bamio import BamWriter, build_bai, CMATCH, CINS, CDEL   # noqa: E402
 
 
-def make_bam(path, n_reads, length, seed=1):
+def make_bam(path, n_reads, length, seed=1, md_tags=True, fasta=None):
     rng = np.random.default_rng(seed)
     ref = rng.choice(np.frombuffer(b"ACGT", np.uint8), length)
     sites = np.zeros(length, bool)
     sites[rng.choice(length, length // 1000, replace=False)] = True
     starts = np.sort(rng.integers(0, length - 200, n_reads))
+    if fasta:
+        with open(fasta, "wb") as f:
+            f.write(b">chr1\n")
+            at = f.tell()
+            f.write(b"\n".join(ref[i:i + 60].tobytes() for i in range(0, length, 60)) + b"\n")
+        open(fasta + ".fai", "w").write("chr1\t%d\t%d\t60\t61\n" % (length, at))
     L = 150
     with BamWriter(path, [("chr1", length)], level=1) as w:
         for i, s in enumerate(starts.tolist()):
@@ -56,7 +67,7 @@ def make_bam(path, n_reads, length, seed=1):
                     cigar = [(CMATCH, 70), (CINS, 2), (CMATCH, 78)]
                     sq = ref[s:s + 70].tobytes().decode() + "GT" + ref[s + 70:s + 148].tobytes().decode()
                     md = "148"
-            w.write(0, s, "r%d" % i, 16 if i & 1 else 0, 60, cigar, sq, aux=b"MDZ" + md.encode() + b"\x00")
+            w.write(0, s, "r%d" % i, 16 if i & 1 else 0, 60, cigar, sq, aux=b"MDZ" + md.encode() + b"\x00" if md_tags else b"")
     build_bai(path, path + ".bai")
 
 
@@ -70,17 +81,20 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--inflate-device", dest="inflate_device", choices=["gpu"], default=None)
     ap.add_argument("--chunk_size", type=int, default=1000)
+    ap.add_argument("--no-md", dest="no_md", action="store_true", help="write the BAM without aux tags (when it has to be made)")
+    ap.add_argument("--fasta", default=None, help="write the BAM's genome here, with its .fai (when the BAM has to be made)")
+    ap.add_argument("--reference", default=None, help="walk the reads that have no MD tag against this FASTA")
     a = ap.parse_args()
     if not os.path.isfile(a.bam + ".bai"):
         t = time.time()
-        make_bam(a.bam, a.reads, a.length)
+        make_bam(a.bam, a.reads, a.length, md_tags=not a.no_md, fasta=a.fasta)
         print("wrote %s in %.1f s" % (a.bam, time.time() - t), file=sys.stderr)
     from dl4vc_amd.candidates import generate
     runs = []
     for k in range(a.repeats):
         t = time.perf_counter()
         st = generate(a.bam, a.bam + ".vcf", threads=a.threads, snp_min_freq=0.075, indel_min_freq=0.02, keep_multialleles=True,
-                      chunk_size=a.chunk_size, inflate_device=a.inflate_device)
+                      chunk_size=a.chunk_size, inflate_device=a.inflate_device, reference=a.reference)
         st["wall_s"] = time.perf_counter() - t
         runs.append(st)
     best = min(runs, key=lambda r: r["wall_s"])
@@ -89,9 +103,11 @@ def main():
            "upload_ms": round(best["upload_ms"], 1), "device_ms": round(best["device_ms"], 1),
            "native_total_ms": round(best["total_ms"], 1), "candidates": best["candidates"], "alleles": best["alleles"],
            "allele_events": best["allele_events"], "batches": best["batches"], "threads": a.threads or min(16, len(os.sched_getaffinity(0))),
-           "chunk_size": a.chunk_size, "inflate_device": a.inflate_device}
+           "chunk_size": a.chunk_size, "inflate_device": a.inflate_device, "reference": bool(a.reference),
+           "reads_no_md": best["reads_no_md"]}
     for k in ("inflate_blocks", "inflate_compressed_bytes", "inflate_inflated_bytes", "inflate_records", "inflate_read_ms", "inflate_ms",
-              "inflate_walk_frame_ms"):
+              "inflate_walk_frame_ms", "reference_reads", "reference_contigs", "reference_bases", "reference_other_bytes",
+              "reference_read_ms", "reference_upload_convert_ms"):
         if k in best:
             res[k] = round(best[k], 1) if isinstance(best[k], float) else best[k]
     if best.get("inflate_ms"):

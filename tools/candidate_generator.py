@@ -44,6 +44,13 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def warn_no_md(stats, reference) -> None:
+    """One line in the log (never in the VCF) when most reads gave no alleles for want of an MD tag."""
+    if reference is None and 2 * stats.get("reads_no_md", 0) > stats.get("reads", 0):
+        logging.warning("%d of %d reads have no MD tag and gave no alleles: give --reference REF.fa to walk them against the "
+                        "reference bases", stats["reads_no_md"], stats["reads"])
+
+
 def run_children(args, argv) -> int:
     """--gpus N: a fresh process per GPU (``--shard g/N``, its own HIP_VISIBLE_DEVICES), then the merge of their parts."""
     import subprocess
@@ -58,6 +65,7 @@ def run_children(args, argv) -> int:
         remove_parts(args.output, args.gpus)
         raise SystemExit("shard process failed: %s" % rcs)
     stats = merge_parts(args.output, args.gpus)
+    warn_no_md(stats, args.reference)
     logging.info("Generated final VCF file at %s from %d parts.", args.output, args.gpus)
     print("summary " + json.dumps(stats, sort_keys=True))
     return 0
@@ -72,9 +80,15 @@ def main(argv=None) -> int:
                    help="One process per GPU: the groups of subregions are dealt to them in contiguous ranges, each writes its "
                    "unsorted records to OUTPUT.part<g>, and this process sorts them into OUTPUT (the same bytes as with 1)")
     p.add_argument("--shard", default="", help="g/N: count only the g-th of N ranges of groups into OUTPUT.part<g> (--gpus sets this)")
+    p.add_argument("--reference", default=None, metavar="REF.fa",
+                   help="Walk the reads that have no MD tag against this FASTA's bases (REF.fa.fai when that file exists) instead "
+                   "of giving them no alleles; reads with an MD tag are walked by it as before. Each contig touched stays on the GPU "
+                   "as 1 byte per base")
     args = p.parse_args(argv)
     print(args)
     logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.DEBUG if args.debug else logging.INFO)
+    if args.reference is not None and not (os.path.isfile(args.reference) and os.access(args.reference, os.R_OK)):
+        p.error("--reference %s is not a readable file" % args.reference)      # (before any device work, --gpus children included)
     from dl4vc_amd.candidates import generate
     from dl4vc_amd.shard import parse_shard
     if args.gpus < 1:
@@ -88,7 +102,10 @@ def main(argv=None) -> int:
     stats = generate(args.input, args.output, contigs=args.contigs, bedfile=args.bedfile, keep_contig_chr=args.keep_contig_chr,
                      chunk_size=args.chunk_size, threads=args.threads, snp_min_freq=args.snp_min_freq,
                      indel_min_freq=args.indel_min_freq, keep_multialleles=args.keep_multialleles,
-                     max_len_indel_allele=args.max_len_indel_allele, inflate_device=args.inflate_device, shard=shard)
+                     max_len_indel_allele=args.max_len_indel_allele, inflate_device=args.inflate_device, shard=shard,
+                     reference=args.reference)
+    if shard is None:                      # (the parent of shards says it once, of the summed counts)
+        warn_no_md(stats, args.reference)
     if shard is not None:
         from dl4vc_amd.shard import part_path
         logging.info("Wrote the records of shard %d/%d to %s.", shard[0], shard[1], part_path(args.output, shard[0]))

@@ -11,13 +11,16 @@
 # -y (with -c): the compressed chunks get dynamic Huffman codes where they are smaller (--compress-codes dynamic): a smaller file.
 # -n: stop after isec/ -- no train.hdf is written -- and print the main.py flags that train straight from the BAM with these
 # outputs (--train_bam: the pileups are encoded on the GPU into the resident record store, the same records in the same order).
+# -f: the candidate generator walks the reads that have no MD tag against REFERENCE (--reference; whole contigs on the GPU, 1 byte
+# per base) instead of giving them no alleles; reads with an MD tag are walked by it as before.  Not passed by default.
 set -e
-usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c [-y]] [-n]"; exit 1; }
+usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c [-y]] [-n] [-f]"; exit 1; }
 PROCS=16
 COMPRESS=""
 CODES=""
 NOFILE=""
-while getopts "i:r:t:o:b:p:ncyh" opt; do
+FROMREF=""
+while getopts "i:r:t:o:b:p:nfcyh" opt; do
   case $opt in
     i) BAM=$OPTARG ;;
     r) REFERENCE=$OPTARG ;;
@@ -28,9 +31,11 @@ while getopts "i:r:t:o:b:p:ncyh" opt; do
     c) COMPRESS=gpu ;;
     y) CODES=dynamic ;;
     n) NOFILE=1 ;;
+    f) FROMREF=1 ;;         # candidate generation: reads without MD are walked against REFERENCE
     *) usage ;;
   esac
 done
+[ -n "$FROMREF" ] && [ -z "$REFERENCE" ] && { echo "-f walks the reads without MD against the reference: give -r REFERENCE as well"; exit 1; }
 [ -z "$BAM" ] || [ -z "$REFERENCE" ] || [ -z "$TRUTH" ] || [ -z "$OUTDIR" ] && usage
 [ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
 [ -n "$NOFILE" ] && [ -n "$COMPRESS" ] && { echo "-n writes no train.hdf, so there is nothing for -c to compress: give one of them"; exit 1; }
@@ -40,7 +45,7 @@ if [ ! -f "$OUTDIR/candidates.vcf" ]; then
   printf "Generate candidate VCF...\n"
   python "$SCRIPTDIR/tools/candidate_generator.py" --input "$BAM" --output "$OUTDIR/candidates.vcf" \
       --snp_min_freq 0.075 --indel_min_freq 0.02 ${BED:+--bedfile "$BED"} --keep_multialleles \
-      > "$OUTDIR/candidate_generator.log" 2>&1
+      ${FROMREF:+--reference "$REFERENCE"} > "$OUTDIR/candidate_generator.log" 2>&1
 fi
 if [ ! -f "$OUTDIR/isec/0003.vcf" ]; then
   printf "Intersect candidates with the truth set...\n"
