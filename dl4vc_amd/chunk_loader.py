@@ -608,7 +608,7 @@ class _RecordTexts:
 
 
 class ResidentRecords:
-    """A candidate file resident on the device (``--train-cache-device gpu``): ``fill()`` inflates every chunk of the file once, in
+    """A candidate file resident on the device (``--train-cache-device gpu``): ``_fill_from_file`` inflates every chunk of the file once, in
     groups of ``group_chunks`` through a ``DeviceChunkLoader``'s handle (``cl_inflate_chunks_device``), appends each group's records
     to a ``RecordStore`` (trimmed of their trailing all-zero rows: 0.36 of the inflated bytes on the synthetic 100-read records measured; a sixth is the
     estimate for a 30x pileup, not measured) and keeps every
@@ -619,48 +619,88 @@ class ResidentRecords:
     The whole file is resident or the fill ends with ``StoreFull`` (how many records fit, in how many bytes, the budget); a damaged
     chunk ends it with ``DamagedChunk`` wherever it lies.
 
-    ``ResidentRecords.from_bam`` fills the same store from the GPU pileup encoder instead (``--train_bam``): no file at all."""
+    ``ResidentRecords.from_bam`` (a ``BamSource`` as the source) fills the same store from the GPU pileup encoder instead
+    (``_fill_from_bam``, ``--train_bam``): no file at all."""
 
-    def __init__(self, path: str, reads: int, batch_sites: int, device: int = 0, use_q: bool = True, use_strand: bool = True,
-                 capacity_bytes: int = 0, slab_bytes: int = STORE_SLAB_BYTES, group_chunks: int = FILL_GROUP_CHUNKS, stream: int = 0,
-                 debug_fill: Optional[int] = None):
-        import torch
-        self.torch, self.path = torch, path
-        self.store = None
-        with RawChunkFile(path) as f:
-            n_chunks = -(-len(f) // f.chunk)
+    def __init__(self, source, reads: int, batch_sites: int, device: int = 0, use_q: bool = True, use_strand: bool = True,
+                 capacity_bytes=0, slab_bytes: int = STORE_SLAB_BYTES, group_chunks: int = FILL_GROUP_CHUNKS, stream: int = 0,
+                 debug_fill: Optional[int] = None, round_locations: int = FILL_ROUND_LOCATIONS):
+        """``source``: the candidate file's path (``group_chunks`` is its fill's option), or a ``BamSource`` (``round_locations`` is;
+        see ``from_bam``).  ``debug_fill`` (tests): every slab is filled with this byte before anything is packed."""
+        self._inflater = self.store = self._counts = self.torch = None
+        bam = source if isinstance(source, BamSource) else None
+        self.path, self.reads, self.B = bam.bam if bam else source, int(reads), int(batch_sites)
+        self.use_q, self.use_strand, self.device = use_q, use_strand, int(device)
+        if bam:
+            from .location_round import default_encoder_options
+            opt = bam.encoder_options or default_encoder_options()
+            self.window, self.stored_rows = 2 * opt.window_size + 1, opt.max_reads
+            if self.window != 201:
+                raise ValueError("the encoder gives windows of %d columns: the allele masks are defined on the 201-column window (window size "
+                                 "100)" % self.window)
+            if self.reads > self.stored_rows:
+                raise ValueError("the model reads %d rows per site but the encoder stores only %d" % (self.reads, self.stored_rows))
+        else:
+            with RawChunkFile(source) as f:
+                n_chunks, chunk = -(-len(f) // f.chunk), f.chunk
             group = max(1, min(int(group_chunks), n_chunks))
-            chunk = f.chunk
-        # (a sequential handle for ``group`` whole chunks at a time)
-        self._inflater = DeviceChunkLoader(path, reads, batch_sites=group * chunk, device=device, use_q=use_q, use_strand=use_strand)
+            # (a sequential handle for ``group`` whole chunks at a time; it knows the file's layout)
+            self._inflater = DeviceChunkLoader(source, reads, batch_sites=group * chunk, device=device, use_q=use_q, use_strand=use_strand)
+            self.window, self.stored_rows = self._inflater.window, self._inflater.stored_rows
+        if self.device >= 0:
+            import torch
+            self.torch = torch
+        self.blob_dtype = blob_dtype(self.window)
+        self.n, self.blob, self.capacity_bytes, self.stage = 0, None, 0, {}
+        self.inflated_bytes = self._num_reads = self._ref_bases = self._label = None          # (``_filled``)
         try:
-            dl = self._inflater
-            self.window, self.stored_rows, self.reads, self.B = dl.window, dl.stored_rows, dl.reads, int(batch_sites)
-            self.use_q, self.use_strand, self.device, self.lib = use_q, use_strand, device, dl.lib
-            self.n, self.chunk, self.n_chunks, self.group = len(dl), chunk, n_chunks, group
-            self.blob_dtype = dl.blob_dtype
-            self.blob = np.zeros(self.n, self.blob_dtype)
-            self.capacity_bytes = int(capacity_bytes)
-            self.store = RecordStore(self.window, self.stored_rows, self.n, self.capacity_bytes, slab_bytes, device)
-            if debug_fill is not None:                       # (tests: every slab filled with this byte before anything is packed)
-                self.store.debug_fill(debug_fill)
-            self._counts = None
-            self.stage = dict(dl.stage)
-            self.stage.update(counts_ms=0.0, fill_ms=0.0, store_bytes=0, store_records=0, extent_ms=0.0, pack_ms=0.0)
-            self.fill(stream)
+            self.lib = load_library()
+            if bam:
+                self._fill_from_bam(bam, opt, capacity_bytes, slab_bytes, stream, debug_fill, round_locations)
+            else:
+                self._fill_from_file(n_chunks, group, capacity_bytes, slab_bytes, stream, debug_fill)
         except Exception:
             self.close()
             raise
 
+    @classmethod
+    def from_bam(cls, bam: str, fasta: str, locations, reads: int, batch_sites: int, device: int = 0, use_q: bool = True,
+                 use_strand: bool = True, capacity_bytes=0, slab_bytes: int = STORE_SLAB_BYTES, stream: int = 0,
+                 debug_fill: Optional[int] = None, encoder_options=None, inflate_device: Optional[str] = None, threads: int = 0,
+                 round_locations: int = FILL_ROUND_LOCATIONS):
+        """The resident records of a BAM (``--train_bam``): what ``tools/convert_bam_single_reads.py`` would write for ``locations``
+        (``pileup_encoder.Location``s, in the converter's order) and ``ResidentRecords(path)`` would then inflate, without the file
+        (``_fill_from_bam``).
+
+        ``capacity_bytes``: the budget, or a function that gives it -- called once the staging planes (3 x ``round_locations`` x
+        ``max_reads`` x window bytes) are allocated, so that a budget taken from the free device memory does not count them.
+        ``device < 0``: the CPU definition -- ``pe_encode`` for every location, a host store, ``cl_store_pack_planes_host``; no GPU.
+
+        ``stage`` also holds the encoders' counts (``location_round.ENCODER_COUNTS``) and ``encode_ms``."""
+        return cls(BamSource(bam, fasta, locations, inflate_device, encoder_options, threads), reads, batch_sites, device, use_q,
+                   use_strand, capacity_bytes, slab_bytes, stream=stream, debug_fill=debug_fill, round_locations=round_locations)
+
+    def _open_store(self, n_records: int, capacity_bytes: int, slab_bytes: int, debug_fill: Optional[int]) -> None:
+        self.capacity_bytes = int(capacity_bytes)
+        self.store = RecordStore(self.window, self.stored_rows, n_records, self.capacity_bytes, slab_bytes, self.device)
+        if debug_fill is not None:
+            self.store.debug_fill(debug_fill)
+
     def __len__(self):
         return self.n
 
-    def fill(self, stream: int = 0) -> None:
+    def _fill_from_file(self, n_chunks: int, group: int, capacity_bytes: int, slab_bytes: int, stream: int, debug_fill) -> None:
+        """Every chunk of the file through the inflate handle, ``group`` at a time, into the store; then the handle and the file go."""
         dl, f = self._inflater, self._inflater.file
+        self.n = len(dl)
+        self.blob = np.zeros(self.n, self.blob_dtype)
+        self._open_store(self.n, capacity_bytes, slab_bytes, debug_fill)
+        self.stage.update(dl.stage)
+        self.stage.update(counts_ms=0.0, fill_ms=0.0, store_bytes=0, store_records=0, extent_ms=0.0, pack_ms=0.0)
         p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
         t_fill = time.perf_counter()
-        for c0 in range(0, self.n_chunks, self.group):
-            c1 = min(self.n_chunks, c0 + self.group)
+        for c0 in range(0, n_chunks, group):
+            c1 = min(n_chunks, c0 + group)
             n = c1 - c0
             t0 = time.perf_counter()
             total, offs, sizes, raw = dl._read_chunks(c0, c1)
@@ -706,135 +746,55 @@ class ResidentRecords:
         self._label = np.ascontiguousarray(self.blob["label"].reshape(-1)) if "label" in self.blob_dtype.names else np.zeros(self.n, np.uint8)
         self.stage["fill_ms"] = (time.perf_counter() - t_fill) * 1e3
 
-    @classmethod
-    def from_bam(cls, bam: str, fasta: str, locations, reads: int, batch_sites: int, device: int = 0, use_q: bool = True,
-                 use_strand: bool = True, capacity_bytes=0, slab_bytes: int = STORE_SLAB_BYTES, stream: int = 0,
-                 debug_fill: Optional[int] = None, encoder_options=None, inflate_device: Optional[str] = None, threads: int = 0,
-                 round_locations: int = FILL_ROUND_LOCATIONS):
-        """The resident records of a BAM (``--train_bam``): what ``tools/convert_bam_single_reads.py`` would write for ``locations``
-        (``pileup_encoder.Location``s, in the converter's order) and ``ResidentRecords(path)`` would then inflate, without the file.
-        Per round of ``round_locations`` locations: the GPU pileup encoder writes its planes into three staging arrays
-        (``encode_device(out=)``), what it declines goes to ``pe_encode`` and then the Python builder (``inference._HostEncoders``)
-        and into the location's slot; the locations that gave a record are the records, in input order, and their slots go into the
-        store (``cl_store_append_planes_device``: the same extent and pack kernels as the file fill, reading the planes where the
-        encoder left them); their other members (``hdf5_schema.blob_dtype``, the texts cut as the file cuts them) are appended to
-        the host array the plans read.  Afterwards the encoders are closed and the staging is freed.
-
-        ``capacity_bytes``: the budget, or a function that gives it -- called once the staging planes (3 x ``round_locations`` x
-        ``max_reads`` x window bytes) are allocated, so that a budget taken from the free device memory does not count them.
-        ``device < 0``: the CPU definition -- ``pe_encode`` for every location, a host store, ``cl_store_pack_planes_host``; no GPU.
-
-        ``stage`` also holds the encoders' counts (``inference.ENCODER_COUNTS``) and ``encode_ms``."""
-        from .inference import ENCODER_COUNTS, _HostEncoders
-        from .pileup_encoder import EncoderOptions
-        import os
-        self = cls.__new__(cls)
-        opt = encoder_options or EncoderOptions(window_size=100, max_reads=200, max_insert_length=10, max_insert_length_variant=50,
-                                                min_base_quality=0)
-        locations = list(locations)
-        self.path = bam
-        self.store = self._inflater = None
-        self.window, self.stored_rows, self.reads, self.B = 2 * opt.window_size + 1, opt.max_reads, int(reads), int(batch_sites)
-        if self.window != 201:
-            raise ValueError("the encoder gives windows of %d columns: the allele masks are defined on the 201-column window (window size "
-                             "100)" % self.window)
-        if self.reads > self.stored_rows:
-            raise ValueError("the model reads %d rows per site but the encoder stores only %d" % (self.reads, self.stored_rows))
-        self.use_q, self.use_strand, self.device, self.lib = use_q, use_strand, int(device), load_library()
-        self.blob_dtype = blob_dtype(self.window)
-        self._counts = None
-        self.stage = {k: 0.0 for k in ("plan_ms", "assemble_ms", "counts_ms", "fill_ms", "encode_ms", "extent_ms", "pack_ms")}
+    def _fill_from_bam(self, src: BamSource, opt, capacity_bytes, slab_bytes: int, stream: int, debug_fill, round_locations: int) -> None:
+        """Per round of ``round_locations`` locations: the location round (``location_round.LocationRounds.encode``) leaves the planes
+        of every location that gives a record in its slot of three staging arrays; those locations are the records, in input order,
+        and their slots go into the store (``cl_store_append_planes_device``: the same extent and pack kernels as the file fill,
+        reading the planes where the encoder left them); their other members (``hdf5_schema.blob_dtype``, the texts cut as the file
+        cuts them) are appended to the host array the plans read.  Afterwards the encoders are closed and the staging is freed."""
+        from .location_round import ENCODER_COUNTS, LocationRounds, record_members
+        locations = list(src.locations)
+        self.stage.update({k: 0.0 for k in ("plan_ms", "assemble_ms", "counts_ms", "fill_ms", "encode_ms", "extent_ms", "pack_ms")})
         self.stage.update({k: 0 for k in ("records", "store_bytes", "store_records") + ENCODER_COUNTS})
-        threads = threads or max(2, min(16, (os.cpu_count() or 4)))
         B = max(1, min(int(round_locations), len(locations)))
-        S, W = self.stored_rows, self.window
-        enc = host = staging = None
+        ts = None
+        if self.device >= 0:
+            dev = self.torch.device("cuda", self.device)
+            ts = self.torch.cuda.ExternalStream(stream, device=dev) if stream else self.torch.cuda.current_stream(dev)
+        rounds = LocationRounds(src.bam, src.fasta, opt, B, self.device, inflate_device=src.inflate_device, threads=src.threads, stream=ts,
+                                counts=self.stage)
         try:
-            if self.device >= 0:
-                import torch
-                from . import pileup_gpu
-                self.torch = torch
-                dev = torch.device("cuda", self.device)
-                staging = [torch.empty((B, S, W), dtype=torch.uint8, device=dev) for _ in range(3)]
-                ts = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.current_stream(dev)
-                enc = pileup_gpu.GpuPileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
-                                                  opt.max_insert_length_variant, opt.min_base_quality, device=self.device,
-                                                  inflate_device=inflate_device)
-            else:
-                if inflate_device is not None:
-                    raise ValueError("inflate_device is the GPU encoder's option: the host filler (device < 0) has none")
-                self.torch = None
-                staging = [np.zeros((B, S, W), np.uint8) for _ in range(3)]
-            self.capacity_bytes = int(capacity_bytes() if callable(capacity_bytes) else capacity_bytes)
-            host = _HostEncoders(bam, fasta, opt, threads)
-            # (the table's size is an upper bound: a location without a record leaves no hole among the records)
-            self.store = RecordStore(W, S, len(locations), self.capacity_bytes, slab_bytes, self.device)
-            if debug_fill is not None:
-                self.store.debug_fill(debug_fill)
-            self.blob = np.zeros(len(locations), self.blob_dtype)
-            self.n = 0
+            # (the budget is asked for now that the staging planes are allocated; the table's size is an upper bound: a location
+            # without a record leaves no hole among the records)
+            self._open_store(len(locations), capacity_bytes() if callable(capacity_bytes) else capacity_bytes, slab_bytes, debug_fill)
+            blobs = [np.zeros(0, self.blob_dtype)]
             t_fill = time.perf_counter()
-            c = self.stage
             for l0 in range(0, len(locations), B):
                 locs = locations[l0:l0 + B]
                 t0 = time.perf_counter()
-                if enc is not None:
-                    _r, _q, _s, ref, num, status = enc.encode_device([l.contig for l in locs], [l.pos for l in locs], stream=ts, out=staging)
-                    c["gpu"] += int((status == 1).sum())
-                else:
-                    ref, num = np.zeros((len(locs), W), np.uint8), np.zeros(len(locs), np.int32)
-                    status = np.full(len(locs), 2, np.int8)
-                c["locations"] += len(locs)
-                declined = np.flatnonzero(status == 2)
-                if len(declined):
-                    got = host.encode(locs, declined, c)
-                    status[declined] = 0
-                    for i, (rd, ql, sd, rf, n_reads) in got.items():
-                        for plane, src in zip(staging, (rd, ql, sd)):
-                            src = np.ascontiguousarray(src, np.uint8)
-                            if enc is not None:
-                                with self.torch.cuda.stream(ts):
-                                    plane[i].copy_(self.torch.from_numpy(src))
-                            else:
-                                plane[i] = src
-                        ref[i], num[i], status[i] = rf, n_reads, 1
-                c["no_record"] += int((status == 0).sum())
-                c["encode_ms"] += (time.perf_counter() - t0) * 1e3
+                ref, num, status = rounds.encode(locs)
+                self.stage["encode_ms"] += (time.perf_counter() - t0) * 1e3
                 keep = np.flatnonzero(status == 1).astype(np.int32)
                 m = len(keep)
                 records = self.n + np.arange(m, dtype=np.int32)
                 try:
-                    if enc is not None:
-                        self.store.append_planes_device([t.data_ptr() for t in staging], len(locs), keep, records, ts.cuda_stream)
+                    if self.device >= 0:
+                        self.store.append_planes_device([t.data_ptr() for t in rounds.stored], len(locs), keep, records, ts.cuda_stream)
                     else:
-                        self.store.pack_planes_host(staging[0][:len(locs)], staging[1][:len(locs)], staging[2][:len(locs)], keep, records)
+                        self.store.pack_planes_host(*[a[:len(locs)] for a in rounds.stored], keep, records)
                 except StoreFull:
                     have = self.store.stats()
                     raise StoreFull("the records of %s do not fit the record store: %d records (of the first %d of its %d locations) fit, in "
                                     "%d bytes of the budget of %d bytes; raise --train-cache-bytes"
-                                    % (bam, have.records + have.refused_fit_records, l0 + len(locs), len(locations),
+                                    % (src.bam, have.records + have.refused_fit_records, l0 + len(locs), len(locations),
                                        have.refused_fit_bytes, self.capacity_bytes)) from None
-                blob = self.blob[self.n:self.n + m]
-                blob["ref_bases"], blob["num_reads"] = ref[keep], num[keep]
-                if m:
-                    bdt = self.blob_dtype
-                    blob["name"] = [locs[i].name.encode()[:bdt["name"].itemsize] for i in keep]
-                    blob["label"] = [locs[i].label for i in keep]
-                    blob["vcfrec"] = [locs[i].vcf_string.encode()[:bdt["vcfrec"].itemsize] for i in keep]
+                blobs.append(record_members(locs, keep, ref, num, self.blob_dtype))
                 self.n += m
-            self.blob = self.blob[:self.n].copy()
+            self.blob = np.concatenate(blobs)
             self._filled(t_fill)
-        except Exception:
-            self.close()
-            raise
         finally:
             # the encoder's buffers, the host encoders' files and the staging planes go: every batch comes from the store
-            if enc is not None:
-                enc.close()
-            if host is not None:
-                host.close()
-            staging = None
-        return self
+            rounds.close()
 
     def chromosomes(self):
         """The text before the first tab of every record's ``vcfrec``: what ``inference.select_sites`` holds out by."""

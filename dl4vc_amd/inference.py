@@ -15,6 +15,7 @@ import numpy as np
 
 from .dataset import assemble_batch
 from .hdf5io import CandidateFile
+from .location_round import ENCODER_COUNTS, LocationRounds, default_encoder_options, default_threads   # noqa: F401 -- ENCODER_COUNTS is public here
 from .shard import shard_range
 from .vcf import scored_record, threshold_distance, FormatOptions, PIPELINE_OPTIONS
 
@@ -90,10 +91,9 @@ def score_file_native(net, hdf_path: str, write: Callable[[str], None], lo: int,
                       threads: int = 0, stats=None) -> int:
     """Same contract as ``score_records`` but fed by the native batched loader (dl4vc_amd/loader.py): chunk
     inflate and site assembly of batch k+1.. run in C++ threads while the GPU scores batch k."""
-    import os
     from .loader import NativeLoader
     cfg = net.config
-    threads = threads or max(2, min(16, (os.cpu_count() or 4)))
+    threads = threads or default_threads()
     done = 0
     t0 = time.perf_counter()
     with NativeLoader(hdf_path, cfg.reads, batch_sites=sites_per_launch, lo=lo, hi=hi, seed=reads_seed,
@@ -189,11 +189,8 @@ def run_shard(net, hdf_path: str, out_path: str, shard_index: int = 0, shard_cou
 
 # ---- BAM in, scored records out: no candidates.hdf ----------------------------------------------------------------------
 
-ENCODER_COUNTS = ("locations", "gpu", "native", "python", "no_record")
-
-
 class _Stopped(Exception):
-    """The consumer of ``_BamBatches`` has gone: the worker thread ends."""
+    """The consumer of a ``_DeviceBatches`` has gone: the worker thread ends."""
 
 
 class _Scored:
@@ -203,149 +200,54 @@ class _Scored:
         self.vcfrec = vcfrec
 
 
-class _HostEncoders:
-    """What takes a location the GPU encoder declines (status 2): ``pe_encode``, then the Python builder for what that
-    declines.  One rule for ``_BamBatches._encode``, which needs the planes, and ``census_bam``, which needs only whether
-    there is a record.  The Python builder's files are opened on first use, by the thread that calls ``encode``."""
-
-    def __init__(self, bam, fasta, opt, threads):
-        from . import loader
-        self.bam, self.fasta, self.opt, self.threads = bam, fasta, opt, threads
-        self.cpu = loader.NativePileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
-                                              opt.max_insert_length_variant, opt.min_base_quality)
-        self._py = None
-
-    def encode(self, locs, declined, counts=None) -> dict:
-        """``declined``: indices into ``locs`` -> {index: (reads, qual, strand, ref, num_reads)} for those that give a record;
-        an index that is absent gives none.  ``counts["native"]`` / ``counts["python"]`` count the records of each encoder."""
-        from .pileup_encoder import encode_location, finish_record
-        from .hdf5_schema import record_dtype
-        host = {}
-        if len(declined) == 0:
-            return host
-        S, L = self.opt.max_reads, 2 * self.opt.window_size + 1
-        sub = self.cpu.encode([locs[i].contig for i in declined], [locs[i].pos for i in declined], self.threads)
-        for k, i in enumerate(declined):
-            st = int(sub[5][k])
-            if st == 1:
-                host[int(i)] = (sub[0][k], sub[1][k], sub[2][k], sub[3][k], int(sub[4][k]))
-                if counts is not None:
-                    counts["native"] += 1
-            elif st == 2:
-                if self._py is None:
-                    from .bamio import BamFile, FastaFile, WindowReader
-                    b = BamFile(self.bam)
-                    self._py = (b, FastaFile(self.fasta), WindowReader(b))
-                b, f, reader = self._py
-                res = encode_location(b, f, locs[i], self.opt, reader)
-                rec = finish_record(res, locs[i], self.opt, record_dtype(S, L)) if res is not None else None
-                if rec is not None:
-                    host[int(i)] = (rec["single_reads"], rec["q-scores"], rec["strand"], rec["ref_bases"], int(rec["num_reads"]))
-                    if counts is not None:
-                        counts["python"] += 1
-        return host
-
-    def close_python(self):
-        if self._py is not None:
-            self._py[0].close()
-            self._py[1].close()
-            self._py = None
-
-    def close(self):
-        self.close_python()
-        self.cpu.close()
-
-
 def census_bam(bam: str, fasta: str, locations, encoder_options=None, device_id: int = 0, threads: int = 0,
                inflate_device: Optional[str] = None, batch: int = 16384, stage=None, log=None) -> np.ndarray:
     """The record census: one uint8 per location, 1 where ``score_bam`` would get a record from it.  The GPU encoder's status
     rule runs without writing a plane (``pg_census``); what it declines goes through the fallback of ``score_bam``
-    (``_HostEncoders``).  ``stage`` (a dict) receives ``pg_stats`` summed over the calls.  Needs torch's HIP device, as
-    ``score_bam`` does."""
-    import os
+    (``location_round.LocationRounds.census``).  ``stage`` (a dict) receives ``pg_stats`` summed over the calls.  Needs torch's HIP
+    device, as ``score_bam`` does."""
     import torch
-    from . import pileup_gpu
-    from .pileup_encoder import EncoderOptions
     if not torch.cuda.is_available():
         raise RuntimeError("census_bam: torch sees no HIP device")
-    opt = encoder_options or EncoderOptions(window_size=100, max_reads=200, max_insert_length=10, max_insert_length_variant=50,
-                                            min_base_quality=0)
-    threads = threads or max(2, min(16, (os.cpu_count() or 4)))
     locations = list(locations)
     flags = np.zeros(len(locations), np.uint8)
-    enc = pileup_gpu.GpuPileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
-                                      opt.max_insert_length_variant, opt.min_base_quality, device=device_id, inflate_device=inflate_device)
-    host = _HostEncoders(bam, fasta, opt, threads)
+    # (no stored planes: a census writes none)
+    rounds = LocationRounds(bam, fasta, encoder_options or default_encoder_options(), 0, device_id, inflate_device=inflate_device,
+                            threads=threads)
     try:
         with torch.cuda.device(device_id):
             for l0 in range(0, len(locations), batch):
-                locs = locations[l0:l0 + batch]
-                status = enc.census([l.contig for l in locs], [l.pos for l in locs])
-                if stage is not None:
-                    for k, v in enc.stats().items():
-                        stage[k] = stage.get(k, 0) + v
-                got = flags[l0:l0 + len(locs)]
-                got[status == 1] = 1
-                for i in host.encode(locs, np.flatnonzero(status == 2)):
-                    got[i] = 1
+                flags[l0:l0 + batch] = rounds.census(locations[l0:l0 + batch])
                 if log:
-                    log("  census of %d/%d locations" % (l0 + len(locs), len(locations)))
+                    log("  census of %d/%d locations" % (min(l0 + batch, len(locations)), len(locations)))
     finally:
-        host.close()
-        enc.close()
+        rounds.close()
+        if stage is not None:
+            for k, v in rounds.stage.items():
+                stage[k] = stage.get(k, 0) + v
     return flags
 
 
-class _BamBatches:
-    """Worker side of ``score_bam``: a thread that turns ``sites_per_launch`` locations at a time into assembled device
-    planes.  Per round: ``pg_encode_device`` into the stored planes (the BAM fetch and framing run in its host threads, or on
-    the device with ``inflate_device="gpu"``),
-    ``pe_encode`` for what it declines and the Python builder for what that declines (their planes are copied into the
-    location's slot), rows and masks on the host (``site_assembly.plan_sites``), ``pg_assemble_device`` into one of two plane
-    sets.  A forward batch holds exactly ``sites_per_launch`` RECORDS, as a batch of the candidate file does, so a round's
-    records may finish one set and start the next.
+class _DeviceBatches:
+    """The hand-over of ``score_bam`` and ``score_file_device``: a worker thread (``_run``) fills one of two plane sets on a stream
+    of its own while ``_score_device_batches`` scores the other; a free and a ready queue carry them back and forth."""
 
-    Device memory, allocated once: the stored planes 3 * B * S * L bytes and two sets of 3 * B * (R + 1) * L bytes.  At B = 4096,
-    S = 200, R = 100, L = 201 that is 494 MB + 2 * 249 MB = 0.99 GB (about 120 KB per site for the stored planes alone)."""
-
-    def __init__(self, cfg, bam, fasta, locations, opt, sites_per_launch, reads_seed, site_limit, device_id, threads, counts,
-                 inflate_device=None, first_record=0, census=None):
+    def __init__(self, torch, dev, B, R, L, thread_name):
         import queue
         import threading
-        import torch
-        from . import pileup_gpu
-        self.torch, self.cfg, self.bam, self.fasta, self.locations, self.opt = torch, cfg, bam, fasta, locations, opt
-        self.B, self.seed, self.limit, self.threads, self.counts = int(sites_per_launch), reads_seed, site_limit, threads, counts
-        self.first_record, self.census = int(first_record), census
-        if census is not None and len(census) != len(locations):
-            raise ValueError("census: %d flags for %d locations" % (len(census), len(locations)))
-        self.S, self.L, self.R = opt.max_reads, 2 * opt.window_size + 1, cfg.reads
-        if self.L != cfg.length:
-            raise ValueError("the encoder's window gives %d columns, the model reads %d" % (self.L, cfg.length))
-        if self.R > self.S:
-            raise ValueError("the model reads %d rows per site but the encoder stores only %d" % (self.R, self.S))
-        self.dev = torch.device("cuda", device_id)
-        self.enc = pileup_gpu.GpuPileupEncoder(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length,
-                                               opt.max_insert_length_variant, opt.min_base_quality, device=device_id,
-                                               inflate_device=inflate_device)
-        self.stage = {}                                  # pg_stats summed over the encoder's calls
-        self.host = _HostEncoders(bam, fasta, opt, threads)
-        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=self.dev)   # noqa: E731
-        self.stored = [u8(self.B, self.S, self.L) for _ in range(3)]
-        self.sets = []
-        for _ in range(2):
-            planes = [u8(self.B, self.R, self.L) for _ in range(3)] + [u8(self.B, self.L) for _ in range(3)]
-            self.sets.append({"planes": planes, "vt": torch.empty((self.B, 3), dtype=torch.float32, device=self.dev),
-                              "bp": torch.empty((self.B,), dtype=torch.float32, device=self.dev),
-                              "h_vt": torch.empty((self.B, 3), dtype=torch.float32).pin_memory(),
-                              "h_bp": torch.empty((self.B,), dtype=torch.float32).pin_memory(),
-                              "done": torch.cuda.Event(), "vcfrec": [], "filled": 0})
-        self.stream = torch.cuda.Stream(self.dev)
+        from .site_assembly import plane_set
+        self.torch, self.dev, self.B, self.R, self.L = torch, dev, B, R, L
+        self.sets = [{"planes": plane_set(torch, dev, B, R, L), "vt": torch.empty((B, 3), dtype=torch.float32, device=dev),
+                      "bp": torch.empty((B,), dtype=torch.float32, device=dev),
+                      "h_vt": torch.empty((B, 3), dtype=torch.float32).pin_memory(),
+                      "h_bp": torch.empty((B,), dtype=torch.float32).pin_memory(),
+                      "done": torch.cuda.Event(), "vcfrec": [], "filled": 0} for _ in range(2)]
+        self.stream = torch.cuda.Stream(dev)
         self.free, self.ready = queue.Queue(), queue.Queue(maxsize=1)
         for s in self.sets:
             self.free.put(s)
         self.stop = threading.Event()
-        self.thread = threading.Thread(target=self._run, name="score_bam-encoder", daemon=True)
+        self.thread = threading.Thread(target=self._run, name=thread_name, daemon=True)
 
     # -- queue plumbing that gives up when the consumer has gone
     def _get_free(self):
@@ -366,66 +268,11 @@ class _BamBatches:
                 pass
         raise _Stopped()
 
-    def _encode(self, locs):
-        """One round: the stored planes of ``locs`` in device memory -> (ref, num_reads, status) with status in {0, 1}."""
-        torch = self.torch
-        contigs, positions = [l.contig for l in locs], [l.pos for l in locs]
-        _r, _q, _s, ref, num, status = self.enc.encode_device(contigs, positions, stream=self.stream, out=self.stored)
-        for k, v in self.enc.stats().items():
-            self.stage[k] = self.stage.get(k, 0) + v
-        c = self.counts
-        c["locations"] += len(locs)
-        c["gpu"] += int((status == 1).sum())
-        declined = np.flatnonzero(status == 2)
-        if len(declined):
-            host = self.host.encode(locs, declined, c)
-            status[declined] = 0
-            with torch.cuda.stream(self.stream):
-                for i, (rd, ql, sd, rf, n) in host.items():
-                    for plane, src in zip(self.stored, (rd, ql, sd)):
-                        plane[i].copy_(torch.from_numpy(np.ascontiguousarray(src, np.uint8)))
-                    ref[i], num[i], status[i] = rf, n, 1
-        c["no_record"] += int((status == 0).sum())
-        return ref, num, status
-
-    def _run(self):
-        from .site_assembly import plan_sites
-        cur = None
-        records = 0
+    def _run_guarded(self, body):
+        """``body()`` on the worker's device, then the end mark; an exception goes to the consumer, which raises it."""
         try:
             with self.torch.cuda.device(self.dev):
-                for l0 in range(0, len(self.locations), self.B):
-                    locs = self.locations[l0:l0 + self.B]
-                    ref, num, status = self._encode(locs)
-                    if self.census is not None:
-                        self._check_census(l0, locs, status)
-                    plan = plan_sites(status, num, ref, [l.vcf_string for l in locs], self.R, self.S, self.seed,
-                                      first_record=self.first_record + records)
-                    if self.limit > 0:
-                        plan = plan.slice(0, max(0, self.limit - records))
-                    records += len(plan)
-                    off = 0
-                    while off < len(plan):
-                        if cur is None:
-                            cur = self._get_free()
-                            cur["vcfrec"], cur["filled"] = [], 0
-                        take = min(len(plan) - off, self.B - cur["filled"])
-                        part, at = plan.slice(off, off + take), cur["filled"]
-                        outs = [t[at:].data_ptr() for t in cur["planes"]]
-                        self.enc.assemble_device([t.data_ptr() for t in self.stored], len(locs), part, outs, self.cfg.use_q,
-                                                 self.cfg.use_strand, stream=self.stream.cuda_stream)
-                        cur["vcfrec"] += part.vcfrec
-                        cur["filled"] += take
-                        off += take
-                        if cur["filled"] == self.B:
-                            self.stream.synchronize()
-                            self._put_ready(cur)
-                            cur = None
-                    self.stream.synchronize()          # the next round overwrites the stored planes
-                    if self.limit > 0 and records >= self.limit:
-                        break
-                if cur is not None and cur["filled"]:
-                    self._put_ready(cur)
+                body()
             self._put_ready(None)
         except _Stopped:
             pass
@@ -434,8 +281,84 @@ class _BamBatches:
                 self._put_ready(e)
             except _Stopped:
                 pass
+
+    def close(self):
+        self.stop.set()
+        if self.thread.is_alive():
+            self.thread.join()
+
+
+class _BamBatches(_DeviceBatches):
+    """Worker side of ``score_bam``: a thread that turns ``sites_per_launch`` locations at a time into assembled device
+    planes.  Per round: the location round into its stored planes (``location_round.LocationRounds.encode``; the BAM fetch and
+    framing run in the encoder's host threads, or on the device with ``inflate_device="gpu"``), rows and masks on the host
+    (``site_assembly.plan_sites``), ``pg_assemble_device`` into one of two plane sets.  A forward batch holds exactly
+    ``sites_per_launch`` RECORDS, as a batch of the candidate file does, so a round's records may finish one set and start the next.
+
+    Device memory, allocated once: the stored planes 3 * B * S * L bytes and two sets of 3 * B * (R + 1) * L bytes.  At B = 4096,
+    S = 200, R = 100, L = 201 that is 494 MB + 2 * 249 MB = 0.99 GB (about 120 KB per site for the stored planes alone)."""
+
+    def __init__(self, cfg, bam, fasta, locations, opt, sites_per_launch, reads_seed, site_limit, device_id, threads, counts,
+                 inflate_device=None, first_record=0, census=None):
+        import torch
+        self.cfg, self.locations, self.seed, self.limit = cfg, locations, reads_seed, site_limit
+        self.first_record, self.census = int(first_record), census
+        if census is not None and len(census) != len(locations):
+            raise ValueError("census: %d flags for %d locations" % (len(census), len(locations)))
+        S, L = opt.max_reads, 2 * opt.window_size + 1
+        if L != cfg.length:
+            raise ValueError("the encoder's window gives %d columns, the model reads %d" % (L, cfg.length))
+        if cfg.reads > S:
+            raise ValueError("the model reads %d rows per site but the encoder stores only %d" % (cfg.reads, S))
+        super().__init__(torch, torch.device("cuda", device_id), int(sites_per_launch), cfg.reads, L, "score_bam-encoder")
+        self.S = S
+        self.rounds = LocationRounds(bam, fasta, opt, self.B, device_id, inflate_device=inflate_device, threads=threads,
+                                     stream=self.stream, counts=counts)
+        self.stage = self.rounds.stage                   # pg_stats summed over the encoder's calls
+
+    def _run(self):
+        try:
+            self._run_guarded(self._rounds)
         finally:
-            self.host.close_python()
+            self.rounds.host.close_python()              # (opened by this thread)
+
+    def _rounds(self):
+        from .site_assembly import plan_sites
+        enc, stored = self.rounds.enc, self.rounds.stored
+        cur = None
+        records = 0
+        for l0 in range(0, len(self.locations), self.B):
+            locs = self.locations[l0:l0 + self.B]
+            ref, num, status = self.rounds.encode(locs)
+            if self.census is not None:
+                self._check_census(l0, locs, status)
+            plan = plan_sites(status, num, ref, [l.vcf_string for l in locs], self.R, self.S, self.seed,
+                              first_record=self.first_record + records)
+            if self.limit > 0:
+                plan = plan.slice(0, max(0, self.limit - records))
+            records += len(plan)
+            off = 0
+            while off < len(plan):
+                if cur is None:
+                    cur = self._get_free()
+                    cur["vcfrec"], cur["filled"] = [], 0
+                take = min(len(plan) - off, self.B - cur["filled"])
+                part, at = plan.slice(off, off + take), cur["filled"]
+                outs = [t[at:].data_ptr() for t in cur["planes"]]
+                enc.assemble_device([t.data_ptr() for t in stored], len(locs), part, outs, self.cfg.use_q, self.cfg.use_strand,
+                                    stream=self.stream.cuda_stream)
+                cur["vcfrec"] += part.vcfrec
+                cur["filled"] += take
+                off += take
+                if cur["filled"] == self.B:
+                    self.stream.synchronize()
+                    self._put_ready(cur)
+                    cur = None
+            self.stream.synchronize()          # the next round overwrites the stored planes
+            if self.limit > 0 and records >= self.limit:
+                break
+        if cur is not None and cur["filled"]:
+            self._put_ready(cur)
 
     def _check_census(self, l0, locs, status):
         """A location whose status differs from its census flag would shift every later record's seed: an error, never that."""
@@ -448,71 +371,39 @@ class _BamBatches:
                                % (locs[i].name, l0 + i, int(flags[i]), int(status[i]), len(bad)))
 
     def close(self):
-        self.stop.set()
-        if self.thread.is_alive():
-            self.thread.join()
-        self.enc.close()
-        self.host.close()
+        super().close()
+        self.rounds.close()
 
 
-class _FileBatches(_BamBatches):
-    """Worker side of ``score_file_device``: ``_BamBatches``' hand-over (two plane sets, a free and a ready queue) with a
-    candidate file in front instead of an encoder.  Per batch of ``sites_per_launch`` records: the raw chunks covering it are read
-    into pinned memory, inflated on the device and assembled into a free plane set (``chunk_loader.DeviceChunkLoader.load``)."""
+class _FileBatches(_DeviceBatches):
+    """Worker side of ``score_file_device``: the hand-over with a candidate file in front instead of an encoder.  Per batch of
+    ``sites_per_launch`` records: the raw chunks covering it are read into pinned memory, inflated on the device and assembled into
+    a free plane set (``chunk_loader.DeviceChunkLoader.load``)."""
 
     def __init__(self, cfg, hdf_path, lo, hi, sites_per_launch, reads_seed, device_id):
-        import queue
-        import threading
         import torch
         from .chunk_loader import DeviceChunkLoader
-        self.torch, self.cfg, self.lo, self.hi = torch, cfg, lo, hi
-        self.B, self.R = int(sites_per_launch), cfg.reads
-        self.dev = torch.device("cuda", device_id)
-        self.loader = DeviceChunkLoader(hdf_path, cfg.reads, self.B, seed=reads_seed, device=device_id, use_q=cfg.use_q,
+        self.loader = DeviceChunkLoader(hdf_path, cfg.reads, int(sites_per_launch), seed=reads_seed, device=device_id, use_q=cfg.use_q,
                                         use_strand=cfg.use_strand)
-        self.L = self.loader.window
-        if self.L != cfg.length:
+        if self.loader.window != cfg.length:
             self.loader.close()
-            raise ValueError("the file's windows have %d columns, the model reads %d" % (self.L, cfg.length))
-        self.hi = min(hi, len(self.loader))
-        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=self.dev)   # noqa: E731
-        self.sets = []
-        for _ in range(2):
-            planes = [u8(self.B, self.R, self.L) for _ in range(3)] + [u8(self.B, self.L) for _ in range(3)]
-            self.sets.append({"planes": planes, "vt": torch.empty((self.B, 3), dtype=torch.float32, device=self.dev),
-                              "bp": torch.empty((self.B,), dtype=torch.float32, device=self.dev),
-                              "h_vt": torch.empty((self.B, 3), dtype=torch.float32).pin_memory(),
-                              "h_bp": torch.empty((self.B,), dtype=torch.float32).pin_memory(),
-                              "done": torch.cuda.Event(), "vcfrec": [], "filled": 0})
-        self.stream = torch.cuda.Stream(self.dev)
-        self.free, self.ready = queue.Queue(), queue.Queue(maxsize=1)
-        for s in self.sets:
-            self.free.put(s)
-        self.stop = threading.Event()
-        self.thread = threading.Thread(target=self._run, name="score_file-loader", daemon=True)
+            raise ValueError("the file's windows have %d columns, the model reads %d" % (self.loader.window, cfg.length))
+        self.lo, self.hi = lo, min(hi, len(self.loader))
+        super().__init__(torch, torch.device("cuda", device_id), int(sites_per_launch), cfg.reads, self.loader.window, "score_file-loader")
 
     def _run(self):
-        try:
-            with self.torch.cuda.device(self.dev):
-                for b0 in range(self.lo, self.hi, self.B):
-                    cur = self._get_free()
-                    plan = self.loader.load(b0, min(b0 + self.B, self.hi), [t.data_ptr() for t in cur["planes"]], self.stream.cuda_stream)
-                    cur["vcfrec"], cur["filled"] = plan.vcfrec, len(plan)
-                    self.stream.synchronize()
-                    self._put_ready(cur)
-            self._put_ready(None)
-        except _Stopped:
-            pass
-        except BaseException as e:      # noqa: BLE001 -- handed to the consumer, which raises it
-            try:
-                self._put_ready(e)
-            except _Stopped:
-                pass
+        self._run_guarded(self._batches)
+
+    def _batches(self):
+        for b0 in range(self.lo, self.hi, self.B):
+            cur = self._get_free()
+            plan = self.loader.load(b0, min(b0 + self.B, self.hi), [t.data_ptr() for t in cur["planes"]], self.stream.cuda_stream)
+            cur["vcfrec"], cur["filled"] = plan.vcfrec, len(plan)
+            self.stream.synchronize()
+            self._put_ready(cur)
 
     def close(self):
-        self.stop.set()
-        if self.thread.is_alive():
-            self.thread.join()
+        super().close()
         self.loader.close()
 
 
@@ -608,21 +499,14 @@ def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None]
     ``shard.plan_bam_shard`` from the record census): site i then draws with ``reads_seed + first_record + i``.  ``census``: one
     flag per location (``census_bam``); a location whose status differs from its flag raises ``RuntimeError``.  ``stage`` (a
     dict) receives the encoder's stage times."""
-    import os
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("score_bam: torch sees no HIP device.  It shares buffers and streams with torch, so torch has to be "
                            "imported before libdl4vc_dan.so / libdl4vc_pileup.so are loaded (one HIP runtime per process)")
-    from .pileup_encoder import EncoderOptions
-    opt = encoder_options or EncoderOptions(window_size=100, max_reads=200, max_insert_length=10, max_insert_length_variant=50,
-                                            min_base_quality=0)
-    counts = encoder_counts if encoder_counts is not None else {}
-    for k in ENCODER_COUNTS:
-        counts.setdefault(k, 0)
-    threads = threads or max(2, min(16, (os.cpu_count() or 4)))
     emit = _Pipeline(net, write, use_var_type_threshold, stats)._emit
-    src = _BamBatches(net.config, bam, fasta, list(locations), opt, sites_per_launch, reads_seed, site_limit, device_id, threads,
-                      counts, inflate_device, first_record, census)
+    src = _BamBatches(net.config, bam, fasta, list(locations), encoder_options or default_encoder_options(), sites_per_launch,
+                      reads_seed, site_limit, device_id, threads or default_threads(), encoder_counts, inflate_device, first_record,
+                      census)
     done = _score_device_batches(net, src, emit, log, "%d locations" % len(src.locations))
     if stage is not None:
         for k, v in src.stage.items():

@@ -131,6 +131,12 @@ class NativePileupEncoder:
             self._h = None
             raise RuntimeError("pe_open failed: %s" % self.lib.pe_last_error(None).decode())
 
+    @classmethod
+    def from_options(cls, bam, fasta, opt):
+        """The encoder of a ``pileup_encoder.EncoderOptions``."""
+        return cls(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length, opt.max_insert_length_variant,
+                   opt.min_base_quality)
+
     def encode(self, contigs, positions, threads: int = 1):
         """-> (reads, qual, strand [n][max_reads][W] u8, ref [n][W] u8, num_reads [n] i32, status [n] i8)."""
         n = len(positions)

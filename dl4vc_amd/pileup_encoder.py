@@ -36,7 +36,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .bamio import _CONSUMES_QUERY
-from .hdf5_schema import record_dtype
+from .hdf5_schema import blob_dtype, record_dtype
 
 # token tables (tools/convert_bam_single_reads.py:38-56)
 BASE_ENUM = {"A": 1, "a": 1, "T": 2, "t": 2, "U": 2, "u": 2, "G": 3, "g": 3, "C": 4, "c": 4,
@@ -446,7 +446,6 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
     Raises ``ValueError`` naming the read where a location's window holds a read the specification has no answer for (a
     zero-length alignment such as ``0M 5I``, a SEQ shorter than the CIGAR's query length such as SEQ ``*``): the native and
     GPU encoders decline such a location, so all three paths end here (tests/test_pileup_edges.py)."""
-    from .bamio import BamFile, FastaFile, WindowReader
     from . import loader
     if device not in (None, "gpu"):
         raise ValueError("device must be None (host encoders) or 'gpu', not %r" % (device,))
@@ -465,58 +464,38 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
             raise ValueError("compress_device='gpu' compresses the GPU pileup encoder's planes where they lie: it needs device='gpu'")
         return _encode_compressed(bam_path, fasta_path, locations, opt, threads, device_id, inflate_device, pending, records_per_chunk,
                                   compress_codes)
-    dtype = record_dtype(opt.max_reads, 2 * opt.window_size + 1)
-    out = np.zeros(len(locations), dtype)
-    n = errors = 0
+    from .location_round import HostEncoders, declined, record_members
+    W = 2 * opt.window_size + 1
+    dtype, bdt = record_dtype(opt.max_reads, W), blob_dtype(W)
+    n = len(locations)
     use_native = loader.available() if native is None else native
-    planes = None
-    contigs, positions = [l.contig for l in locations], [l.pos for l in locations]
-    if device == "gpu" and len(locations):
+    # the planes of the locations the GPU encoder takes (flag 1), then of those the host encoders take of the rest, in location order
+    gpu = np.zeros(n, bool)
+    ref, num = np.zeros((n, W), np.uint8), np.zeros(n, np.int32)
+    rest = np.arange(n)
+    if device == "gpu" and n:
         from . import pileup_gpu
-        with pileup_gpu.GpuPileupEncoder(bam_path, fasta_path, opt.window_size, opt.max_reads, opt.max_insert_length,
-                                         opt.max_insert_length_variant, opt.min_base_quality, device=device_id,
-                                         inflate_device=inflate_device) as enc:
-            planes = enc.encode(contigs, positions)
-        declined = np.flatnonzero(planes[5] == 2)
-        if len(declined):
-            with loader.NativePileupEncoder(bam_path, fasta_path, opt.window_size, opt.max_reads, opt.max_insert_length,
-                                            opt.max_insert_length_variant, opt.min_base_quality) as enc:
-                sub = enc.encode([contigs[i] for i in declined], [positions[i] for i in declined], threads)
-            for full, part in zip(planes, sub):
-                full[declined] = part
-    elif use_native and len(locations):
-        with loader.NativePileupEncoder(bam_path, fasta_path, opt.window_size, opt.max_reads, opt.max_insert_length,
-                                        opt.max_insert_length_variant, opt.min_base_quality) as enc:
-            planes = enc.encode(contigs, positions, threads)
-    bam = fasta = reader = None
-    try:
-        for i, loc in enumerate(locations):
-            status = int(planes[5][i]) if planes is not None else 2
-            if status == 1:
-                rec = np.zeros((), dtype)
-                rec["single_reads"], rec["q-scores"], rec["strand"] = planes[0][i], planes[1][i], planes[2][i]
-                rec["ref_bases"], rec["num_reads"] = planes[3][i], planes[4][i]
-                rec["name"] = loc.name.encode()[:dtype["name"].itemsize]
-                rec["label"] = loc.label
-                rec["vcfrec"] = loc.vcf_string.encode()[:dtype["vcfrec"].itemsize]
-            elif status == 0:
-                rec = None
-            else:
-                if bam is None:
-                    bam, fasta = BamFile(bam_path), FastaFile(fasta_path)
-                    reader = WindowReader(bam)
-                res = encode_location(bam, fasta, loc, opt, reader)
-                rec = finish_record(res, loc, opt, dtype) if res is not None else None
-            if rec is None:
-                errors += 1
-                continue
-            out[n] = rec
-            n += 1
-    finally:
-        if bam is not None:
-            bam.close()
-            fasta.close()
-    return out[:n], errors
+        with pileup_gpu.GpuPileupEncoder.from_options(bam_path, fasta_path, opt, device_id, inflate_device) as enc:
+            reads, qual, strand, ref, num, status = enc.encode([l.contig for l in locations], [l.pos for l in locations])
+        gpu, rest = status == 1, declined(status)
+    host = {}
+    if len(rest):
+        encoders = HostEncoders(bam_path, fasta_path, opt, threads, native=use_native or device == "gpu")
+        try:
+            host = encoders.encode(locations, rest)
+        finally:
+            encoders.close()
+    keep = np.array([i for i in range(n) if gpu[i] or i in host], np.int64)
+    out = np.zeros(len(keep), dtype)
+    for k, i in enumerate(keep):
+        if gpu[i]:
+            out["single_reads"][k], out["q-scores"][k], out["strand"][k] = reads[i], qual[i], strand[i]
+        else:               # (popped: a record of the Python builder is held only until it is copied)
+            out["single_reads"][k], out["q-scores"][k], out["strand"][k], ref[i], num[i] = host.pop(int(i))
+    blob = record_members(locations, keep, ref, num, bdt)
+    for name in bdt.names:
+        out[name] = blob[name]
+    return out, n - len(keep)
 
 
 COMPRESS_BATCH = 4096          # locations per device batch of encode_locations(compress_device="gpu")
@@ -536,58 +515,23 @@ class EncodedBatch:
 
 def _encode_compressed(bam_path, fasta_path, locations, opt, threads, device_id, inflate_device, pending, chunk, codes):
     import torch
-    from . import loader, pileup_gpu
-    from .bamio import BamFile, FastaFile, WindowReader
-    from .hdf5_schema import blob_dtype
+    from .location_round import LocationRounds, record_members
     W = 2 * opt.window_size + 1
     dtype, bdt = record_dtype(opt.max_reads, W), blob_dtype(W)
     if not len(locations):
         return
     dev = torch.device("cuda", device_id)
     B = min(COMPRESS_BATCH, len(locations))
-    stored = [torch.empty((B, opt.max_reads, W), dtype=torch.uint8, device=dev) for _ in range(3)]
-    args = (opt.window_size, opt.max_reads, opt.max_insert_length, opt.max_insert_length_variant, opt.min_base_quality)
-    cpu = bam = fasta = reader = None
-    enc = pileup_gpu.GpuPileupEncoder(bam_path, fasta_path, *args, device=device_id, inflate_device=inflate_device, compress_codes=codes)
+    rounds = LocationRounds(bam_path, fasta_path, opt, B, device_id, inflate_device=inflate_device, compress_codes=codes, threads=threads)
     try:
         for l0 in range(0, len(locations), B):
             locs = locations[l0:l0 + B]
-            contigs, positions = [l.contig for l in locs], [l.pos for l in locs]
-            planes = enc.encode_device(contigs, positions, out=stored)
-            reads, qual, strand, ref, num, status = planes
-            stats = enc.stats()
-            # what the GPU declines goes to pe_encode, what that declines to the Python encoder; their planes into the slots
-            declined = np.flatnonzero(status == 2)
-            if len(declined):
-                if cpu is None:
-                    cpu = loader.NativePileupEncoder(bam_path, fasta_path, *args)
-                sub = cpu.encode([contigs[i] for i in declined], [positions[i] for i in declined], threads)
-                for k, i in enumerate(declined):
-                    st, host = int(sub[5][k]), None
-                    if st == 1:
-                        host = (sub[0][k], sub[1][k], sub[2][k], sub[3][k], int(sub[4][k]))
-                    elif st == 2:
-                        if bam is None:
-                            bam, fasta = BamFile(bam_path), FastaFile(fasta_path)
-                            reader = WindowReader(bam)
-                        res = encode_location(bam, fasta, locs[i], opt, reader)
-                        rec = finish_record(res, locs[i], opt, dtype) if res is not None else None
-                        st = 0
-                        if rec is not None:
-                            host, st = (rec["single_reads"], rec["q-scores"], rec["strand"], rec["ref_bases"], int(rec["num_reads"])), 1
-                    status[i] = st
-                    if host is not None:
-                        for plane, src in zip((reads, qual, strand), host[:3]):
-                            plane[int(i)].copy_(torch.from_numpy(np.ascontiguousarray(src, np.uint8)))
-                        ref[i], num[i] = host[3], host[4]
+            ref, num, status = rounds.encode(locs)
+            reads, qual, strand = (p[:len(locs)] for p in rounds.stored)
+            stats = rounds.last_stats()
             keep = np.flatnonzero(status == 1)
             m = len(keep)
-            blob = np.zeros(m, bdt)
-            blob["ref_bases"], blob["num_reads"] = ref[keep], num[keep]
-            if m:
-                blob["name"] = [locs[i].name.encode()[:bdt["name"].itemsize] for i in keep]
-                blob["label"] = [locs[i].label for i in keep]
-                blob["vcfrec"] = [locs[i].vcf_string.encode()[:bdt["vcfrec"].itemsize] for i in keep]
+            blob = record_members(locs, keep, ref, num, bdt)
 
             def records(lo, hi):
                 out = np.zeros(hi - lo, dtype)
@@ -604,14 +548,9 @@ def _encode_compressed(bam_path, fasta_path, locations, opt, threads, device_id,
             head, tail = records(0, n_head), records(m - n_tail, m)
             chunks = None
             if m - n_tail > n_head:
-                chunks = enc.compress_records((reads, qual, strand), keep[n_head:m - n_tail], blob[n_head:m - n_tail], chunk)
-                stats = enc.stats()
+                chunks = rounds.enc.compress_records((reads, qual, strand), keep[n_head:m - n_tail], blob[n_head:m - n_tail], chunk)
+                stats = rounds.last_stats()
             pending = (pending + m) % chunk
             yield EncodedBatch(head, chunks, tail, m, int((status == 0).sum()), stats)
     finally:
-        enc.close()
-        if cpu is not None:
-            cpu.close()
-        if bam is not None:
-            bam.close()
-            fasta.close()
+        rounds.close()

@@ -227,6 +227,12 @@ class GpuPileupEncoder:
                 self.close()
                 raise
 
+    @classmethod
+    def from_options(cls, bam, fasta, opt, device: int = 0, inflate_device: Optional[str] = None, compress_codes: str = "fixed"):
+        """The encoder of a ``pileup_encoder.EncoderOptions``."""
+        return cls(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length, opt.max_insert_length_variant,
+                   opt.min_base_quality, device=device, inflate_device=inflate_device, compress_codes=compress_codes)
+
     def set_inflate_device(self, on: bool, max_inflated_bytes: int = 0) -> None:
         self._check(self.lib.pg_set_inflate_device(self._h, int(bool(on)), int(max_inflated_bytes)), "pg_set_inflate_device")
 

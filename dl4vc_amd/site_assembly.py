@@ -39,6 +39,13 @@ class SitePlan:
                         None if self.blacklist is None else self.blacklist[lo:hi])
 
 
+def plane_set(torch, dev, B, R, L):
+    """The six planes of a forward batch of B sites in device memory: reads, qual, strand ``[B][R][L]``, ref, ref_mask, var_mask
+    ``[B][L]``."""
+    u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)   # noqa: E731
+    return [u8(B, R, L) for _ in range(3)] + [u8(B, L) for _ in range(3)]
+
+
 def stored_vcfrec(vcf_string: str) -> str:
     """The text ``record_dtype``'s ``vcfrec`` field keeps of a location's record: 128 bytes, read back up to the first NUL."""
     return vcf_string.encode()[:VCFREC_BYTES].split(b"\x00", 1)[0].decode()

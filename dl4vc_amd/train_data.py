@@ -280,6 +280,7 @@ class DeviceBatchPrefetcher:
                  wait_s: float = 600.0, ahead: int = AHEAD, resident: bool = False, cache_bytes: int = 0, slab_bytes: Optional[int] = None):
         import torch
         from .chunk_loader import BamSource, DeviceChunkLoader, ResidentRecords, STORE_SLAB_BYTES
+        from .site_assembly import plane_set
         source = path if isinstance(path, BamSource) else None
         if source is not None:
             path = source.bam
@@ -294,23 +295,15 @@ class DeviceBatchPrefetcher:
             # ``--train-cache-device gpu``: the whole file is inflated once, here, into a record store of at most ``cache_bytes``
             # (``chunk_loader.ResidentRecords``); every batch of every ``batches`` call is assembled from it
             with torch.cuda.device(self.dev):
-                if source is not None:
-                    self.loader = ResidentRecords.from_bam(source.bam, source.fasta, source.locations, reads, self.B, device=device,
-                                                           use_q=use_q, use_strand=use_strand, capacity_bytes=cache_bytes,
-                                                           slab_bytes=slab_bytes or STORE_SLAB_BYTES, inflate_device=source.inflate_device,
-                                                           encoder_options=source.encoder_options, threads=source.threads)
-                else:
-                    self.loader = ResidentRecords(path, reads, self.B, device=device, use_q=use_q, use_strand=use_strand,
-                                                  capacity_bytes=cache_bytes, slab_bytes=slab_bytes or STORE_SLAB_BYTES)
+                self.loader = ResidentRecords(source or path, reads, self.B, device=device, use_q=use_q, use_strand=use_strand,
+                                              capacity_bytes=cache_bytes, slab_bytes=slab_bytes or STORE_SLAB_BYTES)
         else:
             # the record buffer starts at one chunk and is sized by ``batches`` for the lists it is given: a shuffled epoch needs up
             # to ``ahead * batch_sites`` chunks (1 MB each in the production layout), a sequential evaluation pass an eighth of that
             self.loader = DeviceChunkLoader(path, reads, self.B, device=device, use_q=use_q, use_strand=use_strand, shuffled=self.ahead,
                                             chunks=1)
         R, L = self.loader.reads, self.loader.window
-        u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=self.dev)   # noqa: E731
-        self.sets = [[u8(self.B, R, L) for _ in range(3)] + [u8(self.B, L) for _ in range(3)]
-                     for _ in range(2 * self.ahead)]
+        self.sets = [plane_set(torch, self.dev, self.B, R, L) for _ in range(2 * self.ahead)]
         self.stream = torch.cuda.Stream(self.dev)
 
     @property

@@ -156,39 +156,23 @@ def train_main(args, argv) -> int:
     def open_loader(path, batch_sites):
         # loader workers (main.py:59-60: DataLoader(num_workers=args.num_data_workers)); 0 = assemble in this process
         from dl4vc_amd.chunk_loader import BamSource
-        if isinstance(path, BamSource):
-            t0 = time.time()
-            try:
-                loader = DeviceBatchPrefetcher(path, cfg.reads, batch_sites, device=0, use_q=cfg.use_q, use_strand=cfg.use_strand,
-                                               resident=True, cache_bytes=budget)
-            except (ValueError, RuntimeError) as e:
-                raise SystemExit("--train-cache-device gpu: %s" % e)
-            st = loader.stage
-            cache["left"] -= st["store_bytes"]
-            print("--train-cache-device gpu: %s: %d records resident in %d bytes (%.3f of their %d plane bytes), filled in %.2f s; %d "
-                  "locations: %d on the GPU, %d by pe_encode, %d by the Python builder, %d without a record"
-                  % (path.bam, st["store_records"], st["store_bytes"], st["store_bytes"] / max(1, loader.loader.inflated_bytes),
-                     loader.loader.inflated_bytes, time.time() - t0, st["locations"], st["gpu"], st["native"], st["python"],
-                     st["no_record"]), flush=True)
-            return loader
-        if not device_loader:
+        from_bam = isinstance(path, BamSource)
+        if not from_bam and not device_loader:
             return BatchPrefetcher(path, args.num_data_workers)
-        if not resident:
+        if not from_bam and not resident:
             try:
                 return DeviceBatchPrefetcher(path, cfg.reads, batch_sites, device=0, use_q=cfg.use_q, use_strand=cfg.use_strand)
             except (ValueError, RuntimeError) as e:
                 raise SystemExit("--train-loader-device gpu: %s" % e)
         t0 = time.time()
         try:
+            # (a fill from a BAM asks for the budget itself, once its staging planes are allocated)
             loader = DeviceBatchPrefetcher(path, cfg.reads, batch_sites, device=0, use_q=cfg.use_q, use_strand=cfg.use_strand,
-                                           resident=True, cache_bytes=budget())
+                                           resident=True, cache_bytes=budget if from_bam else budget())
         except (ValueError, RuntimeError) as e:
             raise SystemExit("--train-cache-device gpu: %s" % e)
-        st = loader.stage
-        cache["left"] -= st["store_bytes"]
-        print("--train-cache-device gpu: %s: %d records resident in %d bytes (%.3f of their %d inflated bytes), filled in %.2f s"
-              % (path, st["store_records"], st["store_bytes"], st["store_bytes"] / max(1, loader.loader.inflated_bytes),
-                 loader.loader.inflated_bytes, time.time() - t0), flush=True)
+        cache["left"] -= loader.stage["store_bytes"]
+        report_resident(path, loader, time.time() - t0)
         return loader
 
     try:
@@ -202,6 +186,20 @@ def train_main(args, argv) -> int:
     if dist is not None:
         dist.destroy_process_group()
     return 0
+
+
+def report_resident(source, loader, seconds):
+    """The line of ``--train-cache-device gpu`` once a source (a candidate file's path or a ``BamSource``) is resident."""
+    from dl4vc_amd.chunk_loader import BamSource
+    from_bam = isinstance(source, BamSource)
+    st, planes = loader.stage, loader.loader.inflated_bytes
+    line = "--train-cache-device gpu: %s: %d records resident in %d bytes (%.3f of their %d %s bytes), filled in %.2f s" \
+        % (source.bam if from_bam else source, st["store_records"], st["store_bytes"], st["store_bytes"] / max(1, planes), planes,
+           "plane" if from_bam else "inflated", seconds)
+    if from_bam:
+        line += "; %d locations: %d on the GPU, %d by pe_encode, %d by the Python builder, %d without a record" \
+            % (st["locations"], st["gpu"], st["native"], st["python"], st["no_record"])
+    print(line, flush=True)
 
 
 class RecordCount:
