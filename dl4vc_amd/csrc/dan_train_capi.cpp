@@ -3,13 +3,13 @@
 // Host code only.  Reference: dl4vc/trainer.py:109-439 (loop body), dl4vc/model.py:434-961 (forward), main.py:99-117.
 #include "../../include/dl4vc_dan_train.h"
 #include "dan_kernels.h"
+#include "dan_net.h"
 #include "dan_train.h"
 #include "device_buffer.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <deque>
 #include <map>
 #include <memory>
 #include <string>
@@ -65,7 +65,7 @@ struct dan_trainer {
     float *d_rmean = nullptr, *d_rvar = nullptr;
     // flat buffers
     float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr;
-    std::deque<dev::Buffer> blocks;          // every device allocation (talloc); the typed pointers below point into them
+    dev::Blocks blocks;                      // every device allocation (talloc); the typed pointers below point into them
     // constants / packed weights (refreshed every step)
     float* d_pe = nullptr;
     int *d_inv = nullptr, *d_canon = nullptr;                 // layer-1 channel maps: canonical -> reference (48), reference -> canonical
@@ -142,27 +142,11 @@ int check_row_launch(const dan_trainer* t, int entries, const char* what, int la
 
 template <typename T>
 int talloc(dan_trainer* t, T** p, size_t count, bool zero = true) {
-    void* q = nullptr;
-    const size_t bytes = std::max<size_t>(count * sizeof(T), 256);
-    t->blocks.emplace_back();
-    HIPT(t, hipMalloc(&q, bytes));
-    t->blocks.back().p = (uint8_t*)q; t->blocks.back().cap = bytes;
-    if (zero) HIPT(t, hipMemset(q, 0, bytes));
-    *p = (T*)q;
+    HIPT(t, t->blocks.take(p, count, zero));
     return DAN_OK;
 }
 
 int build_pack_jobs(dan_trainer* t);
-bool pool_after(const dan_config& c, int l1) { return (c.pool_layers_mask >> l1) & 1u; }
-bool is_residual(const dan_config& c, int l1) {
-    return c.residual_start > 0 && l1 >= c.residual_start && !(l1 == c.layers && c.c_init != c.c_final);
-}
-void layer_dims(const dan_config& c, int l1, int* cin, int* cout, int* dil) {
-    const int in0 = 2 * EMBED + (c.use_q ? 1 : 0) + (c.use_strand ? 1 : 0) + (c.use_mask ? 3 : 0);
-    if (l1 == 1) { *cin = in0; *cout = c.c_init; *dil = 1; }
-    else if (l1 < c.layers) { *cin = c.c_init; *cout = c.c_init; *dil = c.dil_mid; }
-    else { *cin = c.c_init; *cout = c.c_final; *dil = c.dil_final; }
-}
 
 int add_param(dan_trainer* t, const std::string& name, std::vector<int64_t> shape, int64_t rows, int64_t cols, int64_t ld,
               bool trainable = true) {
@@ -221,11 +205,11 @@ int create(const dan_config* cfg, const dan_train_hyper* hyper, int32_t max_batc
     std::unique_ptr<dan_trainer> owner(new dan_trainer());
     dan_trainer* t = owner.get();
     t->cfg = c; t->hp = *hyper; t->max_batch = max_batch;
-    t->F = 2 * c.c_final * c.length + c.layers * c.bottleneck * c.reads;
-    t->F_stride = ((int64_t)t->F + 15) / 16 * 16;
+    t->F = feature_width(c);
+    t->F_stride = pad16(t->F);
     t->n0 = c.fc_sizes[0]; t->n1 = c.fc_sizes[1];
-    t->n0_stride = (t->n0 + 15) / 16 * 16;
-    t->n1_stride = (t->n1 + 15) / 16 * 16;
+    t->n0_stride = pad16(t->n0);
+    t->n1_stride = pad16(t->n1);
     // ---- parameter table (state-dict names; SURVEY.md section 8b "Weights contract")
     const int L = c.length, H = c.bottleneck;
     t->p_emb = add_vec(t, "embeddings.weight", {VOCAB, EMBED});

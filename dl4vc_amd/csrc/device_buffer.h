@@ -1,5 +1,5 @@
 // The one owner of device resources for the host code of the .hip files and the C-ABI files: device and pinned arrays that grow
-// on demand, events, streams, the guard that restores the caller's device, and the error macros of the functions that use them.
+// on demand, a handle's list of fixed blocks, events, streams, the guard that restores the caller's device, and the error macros of the functions that use them.
 // An array that grows is freed and allocated anew with a quarter and 4096 elements to spare: its contents are not kept
 // (Pinned::ensure_keep is the one exception).  A handle declares members only; they are destroyed in reverse order of declaration.
 #pragma once
@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <deque>
 
 #include "capi_shell.h"
 
@@ -37,6 +38,21 @@ struct Array {
     ~Array() { if (p) (void)hipFree(p); }
 };
 using Buffer = Array<uint8_t>;                            // bytes
+
+// the blocks of a handle whose sizes are known when it opens (weights, workspaces): each at least 256 bytes, all owned here and
+// freed with the list; the handle keeps typed pointers into them
+struct Blocks {
+    std::deque<Buffer> all;
+    template <class T>
+    hipError_t take(T** p, size_t count, bool zero) {
+        all.emplace_back();
+        Buffer& b = all.back();
+        hipError_t e = b.alloc(count * sizeof(T) < 256 ? 256 : count * sizeof(T));
+        if (e == hipSuccess && zero) e = hipMemset(b.p, 0, b.cap);
+        if (e == hipSuccess) *p = (T*)b.p;
+        return e;
+    }
+};
 
 // pinned host bytes, owned
 struct Pinned {

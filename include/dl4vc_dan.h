@@ -126,7 +126,8 @@ int dan_forward_device(dan_t* h, const uint8_t* reads, const uint8_t* qual, cons
  * and returns a ticket.  dan_wait(ticket) blocks until that batch's scores have arrived and copies them to the output
  * pointers given at enqueue (caller-owned, must stay valid until then; any may be NULL).  At most two tickets can be
  * in flight: a third dan_forward_async before the oldest was waited for fails with DAN_ERR_STATE.  n_sites <= max_batch.
- * Results are bit-identical to dan_forward.  Typical loop: enqueue batch k+1, wait for k, format k's VCF records. */
+ * Results are bit-identical to dan_forward.  Typical loop: enqueue batch k+1, wait for k, format k's VCF records.
+ * A failed dan_forward_async leaves nothing in flight: it returns after everything it had enqueued has finished, and no ticket is taken. */
 int dan_forward_async(dan_t* h, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand,
                       const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int64_t n_sites,
                       float* bin_logits, float* vt_logits, float* vt_prob, float* bp, float* aux, int64_t* ticket);
