@@ -91,6 +91,13 @@ _EXTRA = [
      "with --train-cache-device gpu: the bytes the trimmed records of --train_file and --test_file may take together in device "
      "memory (default 0: three quarters of the device memory that is free when the first loader opens).  It bounds the records' bytes, "
      "not the allocations: the store grows in slabs of 256 MiB (or what the budget leaves), so each file may take up to one slab more"),
+    ("--train-cache-format", "str", argparse.SUPPRESS,
+     "with --train-cache-device gpu: rows (the default: the three planes of every record trimmed of their trailing all-zero rows) or "
+     "compact (every stored row cut to the columns between its first and its last non-zero byte, token and strand merged into one "
+     "byte; a record with a token or strand value of 16 or more keeps the rows layout).  compact took 0.30 of the rows layout's "
+     "bytes on the records of a synthetic 30x pileup (computed on the CPU; no real pileup measured), so the same budget holds that "
+     "many more records; the fill prints the real ratio and how many records fell back; same batches, losses, checkpoints and "
+     "scored VCF"),
     ("--train_bam", "str", argparse.SUPPRESS,
      "training straight from a coordinate-sorted BAM (with --train_fasta, the labelled location VCFs --train_tp_vcf / --train_fn_vcf / "
      "--train_fp_vcf, --train-loader-device gpu and --train-cache-device gpu): the GPU pileup encoder's planes go into the resident "

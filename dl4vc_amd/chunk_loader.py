@@ -27,7 +27,11 @@ CL_SYMBOLS = ("cl_open", "cl_close", "cl_last_error", "cl_inflate_chunks_device"
               "cl_store_open", "cl_store_close", "cl_store_last_error", "cl_store_append_device", "cl_store_assemble_device",
               "cl_store_center_counts_device", "cl_store_extent_host", "cl_store_pack_host", "cl_store_assemble_host", "cl_store_record",
               "cl_store_slab", "cl_store_debug_fill", "cl_store_get_stats",
-              "cl_store_append_planes_device", "cl_store_extent_planes_host", "cl_store_pack_planes_host")
+              "cl_store_append_planes_device", "cl_store_extent_planes_host", "cl_store_pack_planes_host",
+              "cl_store_set_format", "cl_store_record_span", "cl_store_get_format_stats", "cl_store_spans_host",
+              "cl_store_spans_planes_host")
+RECORD_FORMATS = {"rows": 0, "compact": 1}   # ``cl_store_set_format``
+COMPACT_MAX_WINDOW = 255
 STORE_SLAB_BYTES = 256 << 20        # the record store grows in device slabs of this size
 FILL_ROUND_LOCATIONS = 4096         # locations one round of the store's fill from a BAM encodes (3 x 4096 x 200 x 201 bytes of staging)
 FILL_GROUP_CHUNKS = 512             # chunks one inflate launch of the store's fill holds (a chunk keeps one lane busy whatever else runs)
@@ -47,6 +51,12 @@ class StoreStats(C.Structure):
     """``cl_store_stats``."""
     _fields_ = [(n, C.c_int64) for n in ("records", "stored_bytes", "inflated_bytes", "slabs", "refused_fit_records", "refused_fit_bytes")] + \
                [(n, C.c_double) for n in ("extent_ms", "pack_ms", "assemble_ms")]
+
+
+class StoreFormatStats(C.Structure):
+    """``cl_store_format_stats``."""
+    _fields_ = [(n, C.c_int64) for n in ("format", "rows_records", "rows_bytes", "compact_records", "compact_bytes")] + \
+               [("spans_ms", C.c_double)]
 
 
 def load_library() -> C.CDLL:
@@ -82,6 +92,11 @@ def load_library() -> C.CDLL:
         lib.cl_store_slab.argtypes = [vp, C.c_int32, vp, C.c_uint64] + [C.POINTER(C.c_int64)] * 3
         lib.cl_store_debug_fill.argtypes = [vp, C.c_int32]
         lib.cl_store_get_stats.argtypes = [vp, C.POINTER(StoreStats)]
+        lib.cl_store_set_format.argtypes = [vp, C.c_int32]
+        lib.cl_store_record_span.argtypes = [vp, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        lib.cl_store_get_format_stats.argtypes = [vp, C.POINTER(StoreFormatStats)]
+        lib.cl_store_spans_host.argtypes = [vp, C.c_uint64, C.c_int64, vp, C.c_int32, C.c_int32, vp, C.c_int64, vp, vp, vp, vp]
+        lib.cl_store_spans_planes_host.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int64, vp, vp, vp, vp]
         _bound = lib
     return _bound
 
@@ -462,13 +477,49 @@ def plane_extents_host(reads, qual, strand, slots=None) -> np.ndarray:
     return kept
 
 
+def _spans_out(n: int, stored_rows: int):
+    return np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, stored_rows), np.uint16)
+
+
+def record_spans_host(inflated, record_bytes: int, plane_off, stored_rows: int, window: int, slots=None):
+    """``cl_store_spans_host``: the compact format's spans of the records ``slots`` (all of them by default) of the inflated bytes
+    -> (kept, cells, mergeable, rowspans ``[n][stored_rows]`` uint16 = ``c0 | n << 8``)."""
+    inflated = np.ascontiguousarray(inflated, np.uint8).reshape(-1)
+    slots = np.arange(len(inflated) // record_bytes, dtype=np.int32) if slots is None else np.ascontiguousarray(slots, np.int32)
+    out = _spans_out(len(slots), stored_rows)
+    lib = load_library()
+    offs = (C.c_int64 * 3)(*[int(x) for x in plane_off])
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    if lib.cl_store_spans_host(p(inflated), inflated.nbytes, record_bytes, offs, stored_rows, window, p(slots), len(slots), *[p(a) for a in out]) != 0:
+        raise ValueError(lib.cl_store_last_error(None).decode())
+    return out
+
+
+def plane_spans_host(reads, qual, strand, slots=None):
+    """``cl_store_spans_planes_host``: the same of the slots ``slots`` (all of them by default) of three arrays ``[n][S][W]``."""
+    planes = [np.ascontiguousarray(a, np.uint8) for a in (reads, qual, strand)]
+    n, S, W = planes[0].shape
+    slots = np.arange(n, dtype=np.int32) if slots is None else np.ascontiguousarray(slots, np.int32)
+    out = _spans_out(len(slots), S)
+    lib = load_library()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    if lib.cl_store_spans_planes_host(*[p(a) for a in planes], n, S, W, p(slots), len(slots), *[p(a) for a in out]) != 0:
+        raise ValueError(lib.cl_store_last_error(None).decode())
+    return out
+
+
 class RecordStore:
     """A ``cl_store_t``: trimmed records in slabs, on ``device`` or (``device < 0``) in host memory, where the CPU definitions
     ``pack_host`` / ``assemble_host`` stand in for ``append_device`` / ``assemble_device``.  A refused call raises ``ValueError``
-    (``StoreFull`` for the capacity) with the library's text and leaves the store as it was."""
+    (``StoreFull`` for the capacity) with the library's text and leaves the store as it was.  ``record_format="compact"``
+    (``cl_store_set_format``): every record that can be is stored as row spans with token and strand in one byte; the assembled
+    planes are the same."""
 
     def __init__(self, window: int, stored_rows: int, n_records: int, capacity_bytes: int, slab_bytes: int = STORE_SLAB_BYTES,
-                 device: int = 0):
+                 device: int = 0, record_format: str = "rows"):
+        if record_format not in RECORD_FORMATS:
+            raise ValueError("record_format must be one of %s, not %r" % (", ".join(RECORD_FORMATS), record_format))
+        self.record_format = record_format
         self.lib = load_library()
         self.window, self.stored_rows, self.n_records, self.device = int(window), int(stored_rows), int(n_records), int(device)
         self.capacity_bytes, self.slab_bytes = int(capacity_bytes), int(slab_bytes)
@@ -477,6 +528,12 @@ class RecordStore:
                                   C.byref(h)) != 0:
             raise ValueError("cl_store_open failed: %s" % self.lib.cl_store_last_error(None).decode())
         self._h = h
+        if record_format != "rows":
+            try:
+                self.set_format(record_format)
+            except Exception:
+                self.close()
+                raise
 
     def _check(self, rc):
         if rc != 0:
@@ -484,6 +541,21 @@ class RecordStore:
 
     def debug_fill(self, value: int) -> None:
         self._check(self.lib.cl_store_debug_fill(self._h, value))
+
+    def set_format(self, record_format) -> None:
+        """``cl_store_set_format``: a name of ``RECORD_FORMATS`` (or the library's number); before the first append."""
+        self._check(self.lib.cl_store_set_format(self._h, RECORD_FORMATS.get(record_format, record_format)))
+
+    def format_stats(self) -> StoreFormatStats:
+        st = StoreFormatStats()
+        self._check(self.lib.cl_store_get_format_stats(self._h, C.byref(st)))
+        return st
+
+    def record_span(self, i: int):
+        """-> (format, bytes) of record ``i``: 0 rows, 1 compact; the bytes it takes in its slab."""
+        fmt, b = C.c_int32(), C.c_int64()
+        self._check(self.lib.cl_store_record_span(self._h, int(i), C.byref(fmt), C.byref(b)))
+        return fmt.value, b.value
 
     def stats(self) -> StoreStats:
         st = StoreStats()
@@ -624,10 +696,12 @@ class ResidentRecords:
 
     def __init__(self, source, reads: int, batch_sites: int, device: int = 0, use_q: bool = True, use_strand: bool = True,
                  capacity_bytes=0, slab_bytes: int = STORE_SLAB_BYTES, group_chunks: int = FILL_GROUP_CHUNKS, stream: int = 0,
-                 debug_fill: Optional[int] = None, round_locations: int = FILL_ROUND_LOCATIONS):
+                 debug_fill: Optional[int] = None, round_locations: int = FILL_ROUND_LOCATIONS, record_format: str = "rows"):
         """``source``: the candidate file's path (``group_chunks`` is its fill's option), or a ``BamSource`` (``round_locations`` is;
-        see ``from_bam``).  ``debug_fill`` (tests): every slab is filled with this byte before anything is packed."""
+        see ``from_bam``).  ``debug_fill`` (tests): every slab is filled with this byte before anything is packed.
+        ``record_format``: ``RecordStore``'s (``--train-cache-format``); the batches are the same."""
         self._inflater = self.store = self._counts = self.torch = None
+        self.record_format = record_format
         bam = source if isinstance(source, BamSource) else None
         self.path, self.reads, self.B = bam.bam if bam else source, int(reads), int(batch_sites)
         self.use_q, self.use_strand, self.device = use_q, use_strand, int(device)
@@ -667,7 +741,7 @@ class ResidentRecords:
     def from_bam(cls, bam: str, fasta: str, locations, reads: int, batch_sites: int, device: int = 0, use_q: bool = True,
                  use_strand: bool = True, capacity_bytes=0, slab_bytes: int = STORE_SLAB_BYTES, stream: int = 0,
                  debug_fill: Optional[int] = None, encoder_options=None, inflate_device: Optional[str] = None, threads: int = 0,
-                 round_locations: int = FILL_ROUND_LOCATIONS):
+                 round_locations: int = FILL_ROUND_LOCATIONS, record_format: str = "rows"):
         """The resident records of a BAM (``--train_bam``): what ``tools/convert_bam_single_reads.py`` would write for ``locations``
         (``pileup_encoder.Location``s, in the converter's order) and ``ResidentRecords(path)`` would then inflate, without the file
         (``_fill_from_bam``).
@@ -678,11 +752,12 @@ class ResidentRecords:
 
         ``stage`` also holds the encoders' counts (``location_round.ENCODER_COUNTS``) and ``encode_ms``."""
         return cls(BamSource(bam, fasta, locations, inflate_device, encoder_options, threads), reads, batch_sites, device, use_q,
-                   use_strand, capacity_bytes, slab_bytes, stream=stream, debug_fill=debug_fill, round_locations=round_locations)
+                   use_strand, capacity_bytes, slab_bytes, stream=stream, debug_fill=debug_fill, round_locations=round_locations,
+                   record_format=record_format)
 
     def _open_store(self, n_records: int, capacity_bytes: int, slab_bytes: int, debug_fill: Optional[int]) -> None:
         self.capacity_bytes = int(capacity_bytes)
-        self.store = RecordStore(self.window, self.stored_rows, n_records, self.capacity_bytes, slab_bytes, self.device)
+        self.store = RecordStore(self.window, self.stored_rows, n_records, self.capacity_bytes, slab_bytes, self.device, self.record_format)
         if debug_fill is not None:
             self.store.debug_fill(debug_fill)
 
@@ -739,6 +814,9 @@ class ResidentRecords:
         """What both fills end with: the store's figures and the members every plan reads."""
         have = self.store.stats()
         self.stage.update(store_bytes=have.stored_bytes, store_records=have.records, extent_ms=have.extent_ms, pack_ms=have.pack_ms)
+        by = self.store.format_stats()
+        self.stage.update(store_rows_records=by.rows_records, store_rows_bytes=by.rows_bytes, store_compact_records=by.compact_records,
+                          store_compact_bytes=by.compact_bytes, spans_ms=by.spans_ms)
         self.inflated_bytes = have.inflated_bytes
         # contiguous once (a field of the blob array is a strided view)
         self._num_reads = np.ascontiguousarray(self.blob["num_reads"].reshape(-1))

@@ -6,6 +6,11 @@
 // host memory and takes the CPU twins of the three kernels (cl_store_pack_host, cl_store_assemble_host): the definitions the
 // kernels are tested against.  Every extern "C" body catches what it throws; every index is checked before it is followed.
 //
+// cl_store_set_format(h, 1) before the first append chooses the compact format of store_host.h: record_spans instead of
+// record_extent (kept, cells and the mergeable flag come back and are checked before they size anything; the rows' spans stay in
+// device scratch), the layout by each record's own span, store_pack_compact for the mergeable records and store_pack for the
+// others in the same append, and the assembly by each record's format.  A host store takes the CPU twins of all of them.
+//
 // With -DCL_STORE_HOST_ONLY a plain C++ compiler builds the host store alone (tools/asan_store.sh runs it under sanitizers).
 #include "../../include/dl4vc_chunks.h"
 #include "store_host.h"
@@ -38,6 +43,15 @@ struct Slab {
 struct Rec {
     int32_t slab = 0, kept = -1;                      // kept < 0: not appended yet
     uint64_t off = 0;
+    int32_t format = st::FORMAT_ROWS;                 // the layout of its bytes (a compact store's records that are not mergeable: rows)
+    uint64_t bytes = 0;                               // its span in the slab
+};
+
+// what an append knows of its records once they are measured
+struct Measured {
+    std::vector<int32_t> format, cells;
+    std::vector<uint64_t> span;
+    void resize(size_t n) { format.assign(n, st::FORMAT_ROWS); cells.assign(n, 0); span.assign(n, 0); }
 };
 
 #ifdef CL_STORE_HOST_ONLY
@@ -57,15 +71,17 @@ struct cl_store : StoreBase {
     uint64_t capacity = 0, slab_bytes = 0;
     bool on_host = false;
     int fill = -1;                                    // >= 0: every new slab's allocation is filled with this byte first
+    int32_t format = st::FORMAT_ROWS;                 // cl_store_set_format: what a mergeable record is stored as
+    cl_store_format_stats fstats{};
     st::Cursor cur;
     std::vector<std::unique_ptr<Slab>> slabs;
     std::vector<Rec> table;
     cl_store_stats stats{};
 #ifndef CL_STORE_HOST_ONLY
     dev::Array<st::DevRec> d_table;
-    dev::Buffer d_app;                                // an append's slots, extents and pack items
+    dev::Buffer d_app;                                // an append's slots, extents (or span sums and row spans) and pack items
     dev::Pinned h_app;
-    dev::Event ev[6];                                 // extent | copy back ; pack | ; assemble |
+    dev::Event ev[6];                                 // extent or spans | copy back ; pack | ; assemble |
     bool assemble_timed = false;
     ~cl_store() { wait_meta(); }
 #endif
@@ -104,32 +120,44 @@ int check_append(cl_store* h, const char* who, const int32_t* slots, const int32
 }
 
 // the layout of an append: places and the new slabs' sizes, or the refusal (-3: the capacity)
-int place_records(cl_store* h, const char* who, st::Cursor& cur, const int32_t* kept, int64_t n, std::vector<st::Place>& places,
+int place_records(cl_store* h, const char* who, st::Cursor& cur, const Measured& ms, int64_t n, std::vector<st::Place>& places,
                   std::vector<uint64_t>& new_caps) {
     places.resize((size_t)n);
     int64_t at = 0;
-    const int rc = st::layout(cur, kept, n, h->window, h->slab_bytes, h->capacity, places.data(), new_caps, &at);
+    const int rc = st::layout_spans(cur, ms.span.data(), n, h->slab_bytes, h->capacity, places.data(), new_caps, &at);
     if (rc == st::LAYOUT_CAPACITY) {
         h->stats.refused_fit_records = at;               // what the caller's message needs: counted here, once
         h->stats.refused_fit_bytes = (int64_t)h->cur.stored;
-        for (int64_t i = 0; i < at; ++i) h->stats.refused_fit_bytes += (int64_t)st::record_span(kept[i], h->window);
+        for (int64_t i = 0; i < at; ++i) h->stats.refused_fit_bytes += (int64_t)ms.span[(size_t)i];
         return sfail(h, -3, "%s: the store's capacity of %llu bytes would be exceeded: it holds %lld records in %llu bytes, and %lld of "
                             "the %lld records of this call fit", who, (unsigned long long)h->capacity, (long long)h->stats.records,
                      (unsigned long long)h->cur.stored, (long long)at, (long long)n);
     }
     if (rc == st::LAYOUT_SLAB)
-        return sfail(h, -1, "%s: a record of %llu bytes does not fit a slab of %llu", who,
-                     (unsigned long long)st::record_span(kept[at], h->window), (unsigned long long)h->slab_bytes);
+        return sfail(h, -1, "%s: a record of %llu bytes does not fit a slab of %llu", who, (unsigned long long)ms.span[(size_t)at],
+                     (unsigned long long)h->slab_bytes);
     return 0;
 }
 
-void commit(cl_store* h, const st::Cursor& cur, const int32_t* records, const int32_t* kept, const std::vector<st::Place>& places, int64_t n,
-            int64_t record_bytes) {
+// the spans of records in the rows layout, by their extents
+void rows_spans(const cl_store* h, const int32_t* kept, int64_t n, Measured& ms) {
+    ms.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) ms.span[(size_t)i] = st::record_span(kept[i], h->window);
+}
+
+void commit(cl_store* h, const st::Cursor& cur, const int32_t* records, const int32_t* kept, const Measured& ms,
+            const std::vector<st::Place>& places, int64_t n, int64_t record_bytes) {
     for (int64_t i = 0; i < n; ++i) {
         Rec& r = h->table[records[i]];
         r.slab = places[i].slab; r.off = places[i].off; r.kept = kept[i];
-        const uint64_t b = st::record_span(kept[i], h->window);
+        const uint64_t b = ms.span[(size_t)i];
+        r.format = ms.format[(size_t)i]; r.bytes = b;
         if (b) h->slabs[r.slab]->used = r.off + b;
+        if (r.format == st::FORMAT_COMPACT) {
+            ++h->fstats.compact_records; h->fstats.compact_bytes += (int64_t)b;
+        } else {
+            ++h->fstats.rows_records; h->fstats.rows_bytes += (int64_t)b;
+        }
     }
     h->cur = cur;
     h->stats.records += n;
@@ -202,26 +230,53 @@ int append_source(cl_store* h, const char* who, const st::Source& src, int64_t n
     ST_TRY(hipSetDevice(h->device));
     h->wait_meta();
     hipStream_t s = (hipStream_t)stream;
+    const bool compact = h->format == st::FORMAT_COMPACT;
+    // slots | extents, or span sums | pack items | (compact) the rows' spans, which stay on the device
     const size_t b_i32 = (size_t)n * sizeof(int32_t), b_items = (size_t)n * sizeof(st::PackItem);
-    const size_t o_kept = (b_i32 + 15) & ~(size_t)15, o_items = 2 * o_kept;
-    if (h->d_app.ensure(o_items + b_items) != hipSuccess) return sfail(h, -2, "hipMalloc of the append tables failed");
-    if (h->h_app.ensure(o_items + b_items) != hipSuccess) return sfail(h, -2, "hipHostMalloc of the append staging failed");
+    const size_t b_meas = compact ? (size_t)n * sizeof(st::SpanSums) : b_i32;
+    const size_t o_kept = (b_i32 + 15) & ~(size_t)15, o_items = o_kept + ((b_meas + 15) & ~(size_t)15);
+    const size_t o_rowspans = o_items + ((b_items + 15) & ~(size_t)15);
+    const size_t b_dev = o_rowspans + (compact ? (size_t)n * h->stored_rows * sizeof(uint16_t) : 0);
+    if (h->d_app.ensure(b_dev) != hipSuccess) return sfail(h, -2, "hipMalloc of the append tables failed");
+    if (h->h_app.ensure(o_rowspans) != hipSuccess) return sfail(h, -2, "hipHostMalloc of the append staging failed");
     memcpy(h->h_app.p, slots, b_i32);
-    int32_t* h_kept = (int32_t*)(h->h_app.p + o_kept);
     ST_TRY(hipMemcpyAsync(h->d_app.p, h->h_app.p, b_i32, hipMemcpyHostToDevice, s));
     ST_TRY(hipEventRecord(h->ev[0], s));
-    ST_TRY(st::launch_extent(src, (const int32_t*)h->d_app.p, n, (int32_t*)(h->d_app.p + o_kept), s));
+    if (compact)
+        ST_TRY(st::launch_spans(src, (const int32_t*)h->d_app.p, n, (st::SpanSums*)(h->d_app.p + o_kept), (uint16_t*)(h->d_app.p + o_rowspans), s));
+    else
+        ST_TRY(st::launch_extent(src, (const int32_t*)h->d_app.p, n, (int32_t*)(h->d_app.p + o_kept), s));
     ST_TRY(hipEventRecord(h->ev[1], s));
-    ST_TRY(hipMemcpyAsync(h_kept, h->d_app.p + o_kept, b_i32, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipMemcpyAsync(h->h_app.p + o_kept, h->d_app.p + o_kept, b_meas, hipMemcpyDeviceToHost, s));
     ST_TRY(hipStreamSynchronize(s));
-    for (int64_t i = 0; i < n; ++i) {
-        if (h_kept[i] < 0 || h_kept[i] > h->stored_rows) return sfail(h, -2, "%s: the device gave an extent of %d rows", who, h_kept[i]);
-        kept_out[i] = h_kept[i];
+    Measured ms;
+    if (compact) {
+        // every value the device returns is checked before it sizes anything
+        const st::SpanSums* got = (const st::SpanSums*)(h->h_app.p + o_kept);
+        ms.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            const st::SpanSums& g = got[i];
+            if (g.kept < 0 || g.kept > h->stored_rows) return sfail(h, -2, "%s: the device gave an extent of %d rows", who, g.kept);
+            if (g.cells < 0 || (int64_t)g.cells > (int64_t)g.kept * h->window)
+                return sfail(h, -2, "%s: the device gave %d cells in %d rows of %d columns", who, g.cells, g.kept, h->window);
+            if (g.mergeable != 0 && g.mergeable != 1) return sfail(h, -2, "%s: the device gave a mergeable flag of %d", who, g.mergeable);
+            kept_out[i] = g.kept;
+            ms.format[(size_t)i] = g.mergeable ? st::FORMAT_COMPACT : st::FORMAT_ROWS;
+            ms.cells[(size_t)i] = g.cells;
+            ms.span[(size_t)i] = st::format_span(ms.format[(size_t)i], g.kept, g.cells, h->window);
+        }
+    } else {
+        const int32_t* h_kept = (const int32_t*)(h->h_app.p + o_kept);
+        for (int64_t i = 0; i < n; ++i) {
+            if (h_kept[i] < 0 || h_kept[i] > h->stored_rows) return sfail(h, -2, "%s: the device gave an extent of %d rows", who, h_kept[i]);
+            kept_out[i] = h_kept[i];
+        }
+        rows_spans(h, kept_out, n, ms);
     }
     st::Cursor cur = h->cur;
     std::vector<st::Place> places;
     std::vector<uint64_t> new_caps;
-    if (const int rc = place_records(h, who, cur, kept_out, n, places, new_caps)) return rc;
+    if (const int rc = place_records(h, who, cur, ms, n, places, new_caps)) return rc;
     const size_t had = h->slabs.size();
     for (uint64_t cap : new_caps) {
         std::unique_ptr<Slab> slab(new Slab());
@@ -236,14 +291,21 @@ int append_source(cl_store* h, const char* who, const st::Source& src, int64_t n
         slab->data = slab->d.p + st::SLAB_GUARD;
         h->slabs.push_back(std::move(slab));
     }
+    // the items of the records in the rows layout from the front, of the compact records from the back: a launch each
     st::PackItem* items = (st::PackItem*)(h->h_app.p + o_items);
+    int64_t n_rows = 0, n_compact = 0;
     for (int64_t i = 0; i < n; ++i) {
         const uint64_t addr = kept_out[i] ? (uint64_t)reinterpret_cast<uintptr_t>(h->slabs[places[i].slab]->data + places[i].off) : 0;
-        items[i] = st::PackItem{addr, slots[i], kept_out[i], records[i], 0};
+        const st::PackItem it{addr, slots[i], kept_out[i], records[i], (int32_t)i, ms.cells[(size_t)i], (int32_t)ms.span[(size_t)i]};
+        if (ms.format[(size_t)i] == st::FORMAT_COMPACT) items[n - ++n_compact] = it;
+        else items[n_rows++] = it;
     }
+    const st::PackItem* d_items = (const st::PackItem*)(h->d_app.p + o_items);
     hipError_t rc = hipMemcpyAsync(h->d_app.p + o_items, items, b_items, hipMemcpyHostToDevice, s);
     if (rc == hipSuccess) rc = hipEventRecord(h->ev[2], s);
-    if (rc == hipSuccess) rc = st::launch_pack(src, (const st::PackItem*)(h->d_app.p + o_items), n, h->d_table.p, s);
+    if (rc == hipSuccess) rc = st::launch_pack(src, d_items, n_rows, h->d_table.p, s);
+    if (rc == hipSuccess)
+        rc = st::launch_pack_compact(src, d_items + n_rows, n_compact, (const uint16_t*)(h->d_app.p + o_rowspans), h->d_table.p, s);
     if (rc == hipSuccess) rc = hipEventRecord(h->ev[3], s);
     if (rc == hipSuccess) rc = hipStreamSynchronize(s);
     if (rc != hipSuccess) {
@@ -251,12 +313,12 @@ int append_source(cl_store* h, const char* who, const st::Source& src, int64_t n
         h->slabs.resize(had);
         return sfail(h, -2, "%s: device: %s", who, hipGetErrorString(rc));
     }
-    float ms[2] = {0, 0};
-    ST_TRY(hipEventElapsedTime(&ms[0], h->ev[0], h->ev[1]));
-    ST_TRY(hipEventElapsedTime(&ms[1], h->ev[2], h->ev[3]));
-    h->stats.extent_ms += ms[0];
-    h->stats.pack_ms += ms[1];
-    commit(h, cur, records, kept_out, places, n, source_bytes);
+    float t_ms[2] = {0, 0};
+    ST_TRY(hipEventElapsedTime(&t_ms[0], h->ev[0], h->ev[1]));
+    ST_TRY(hipEventElapsedTime(&t_ms[1], h->ev[2], h->ev[3]));
+    (compact ? h->fstats.spans_ms : h->stats.extent_ms) += t_ms[0];
+    h->stats.pack_ms += t_ms[1];
+    commit(h, cur, records, kept_out, ms, places, n, source_bytes);
     return 0;
 }
 
@@ -326,7 +388,7 @@ int assemble_device(cl_store* h, const int32_t* records, const int16_t* rows, co
         a.rows = (const int16_t*)(h->d_meta.p + b_sites);
         a.R = R; a.L = L;
         a.use[0] = 1; a.use[1] = use_q != 0; a.use[2] = use_strand != 0;
-        rc = st::launch_store_assemble(a, (int32_t)m, s);
+        rc = st::launch_store_assemble(a, (int32_t)m, h->fstats.compact_records > 0, s);
     }
     h->meta_busy = true;                                 // (also after a failure: some of the copies may be enqueued)
     if (hipEventRecord(h->ev_meta, s) != hipSuccess && rc == hipSuccess) rc = hipErrorUnknown;
@@ -340,11 +402,28 @@ int assemble_device(cl_store* h, const int32_t* records, const int16_t* rows, co
 int pack_source(cl_store* h, const char* who, const st::HostSource& src, int64_t n_slots, int64_t source_bytes, const int32_t* slots,
                 const int32_t* records, int64_t n, int32_t* kept_out) {
     if (const int rc = check_append(h, who, slots, records, n, n_slots, kept_out)) return rc;
-    for (int64_t i = 0; i < n; ++i) kept_out[i] = st::extent_host(src, slots[i], h->stored_rows, h->window);
+    const bool compact = h->format == st::FORMAT_COMPACT;
+    const size_t S = (size_t)h->stored_rows;
+    Measured ms;
+    std::vector<uint16_t> rowspans;
+    if (compact) {
+        ms.resize((size_t)n);
+        rowspans.resize((size_t)n * S);
+        for (int64_t i = 0; i < n; ++i) {
+            const st::SpanSums g = st::spans_host(src, slots[i], h->stored_rows, h->window, rowspans.data() + (size_t)i * S);
+            kept_out[i] = g.kept;
+            ms.format[(size_t)i] = g.mergeable ? st::FORMAT_COMPACT : st::FORMAT_ROWS;
+            ms.cells[(size_t)i] = g.cells;
+            ms.span[(size_t)i] = st::format_span(ms.format[(size_t)i], g.kept, g.cells, h->window);
+        }
+    } else {
+        for (int64_t i = 0; i < n; ++i) kept_out[i] = st::extent_host(src, slots[i], h->stored_rows, h->window);
+        rows_spans(h, kept_out, n, ms);
+    }
     st::Cursor cur = h->cur;
     std::vector<st::Place> places;
     std::vector<uint64_t> new_caps;
-    if (const int rc = place_records(h, who, cur, kept_out, n, places, new_caps)) return rc;
+    if (const int rc = place_records(h, who, cur, ms, n, places, new_caps)) return rc;
     for (uint64_t cap : new_caps) {
         std::unique_ptr<Slab> slab(new Slab());
         slab->host.reset(new uint8_t[(size_t)cap]);
@@ -353,9 +432,13 @@ int pack_source(cl_store* h, const char* who, const st::HostSource& src, int64_t
         slab->data = slab->host.get();
         h->slabs.push_back(std::move(slab));
     }
-    for (int64_t i = 0; i < n; ++i)
-        if (kept_out[i]) st::pack_host(src, slots[i], h->window, kept_out[i], h->slabs[places[i].slab]->data + places[i].off);
-    commit(h, cur, records, kept_out, places, n, source_bytes);
+    for (int64_t i = 0; i < n; ++i) {
+        if (!kept_out[i]) continue;
+        uint8_t* dst = h->slabs[places[i].slab]->data + places[i].off;
+        if (ms.format[(size_t)i] == st::FORMAT_COMPACT) st::pack_compact_host(src, slots[i], h->window, kept_out[i], rowspans.data() + (size_t)i * S, dst);
+        else st::pack_host(src, slots[i], h->window, kept_out[i], dst);
+    }
+    commit(h, cur, records, kept_out, ms, places, n, source_bytes);
     return 0;
 }
 
@@ -395,8 +478,10 @@ int assemble_host(cl_store* h, const int32_t* records, const int16_t* rows, cons
                 memset(dst, 0, span);
                 continue;
             }
-            const uint8_t* src = r.kept ? h->slabs[r.slab]->data + r.off + (size_t)p * r.kept * L : nullptr;
-            st::assemble_plane_host(src, r.kept, first ? nullptr : rows + (size_t)i * R, R, L, dst);
+            const uint8_t* rec = r.kept ? h->slabs[r.slab]->data + r.off : nullptr;
+            const int16_t* site_rows = first ? nullptr : rows + (size_t)i * R;
+            if (r.format == st::FORMAT_COMPACT) st::assemble_compact_plane_host(rec, r.kept, p, site_rows, R, L, dst);
+            else st::assemble_plane_host(rec ? rec + (size_t)p * r.kept * L : nullptr, r.kept, site_rows, R, L, dst);
         }
     }
     const size_t b_line = (size_t)m * L;
@@ -464,6 +549,20 @@ int cl_store_debug_fill(cl_store_t* h, int32_t value) {
     if (value < -1 || value > 255) return sfail(h, -1, "cl_store_debug_fill: -1 (no fill) or a byte");
     h->fill = value;
     return 0;
+}
+
+int cl_store_set_format(cl_store_t* h, int32_t format) {
+    if (!h) return sfail(nullptr, -1, "cl_store_set_format: null handle");
+    return capi::guarded(h->err, "cl_store_set_format", [&] {
+        if (format != st::FORMAT_ROWS && format != st::FORMAT_COMPACT)
+            return sfail(h, -1, "cl_store_set_format: format %d: 0 (rows) or 1 (compact)", format);
+        if (h->stats.records > 0) return sfail(h, -1, "cl_store_set_format: the store holds records already: the format is chosen before the first append");
+        if (format == st::FORMAT_COMPACT && h->window > st::COMPACT_MAX_WINDOW)
+            return sfail(h, -1, "cl_store_set_format: the compact format keeps a row's first column and length in eight bits each: a window of "
+                                "%d columns exceeds its %d", h->window, st::COMPACT_MAX_WINDOW);
+        h->format = format;
+        return 0;
+    });
 }
 
 int cl_store_append_device(cl_store_t* h, cl_loader_t* loader, const int32_t* slots, const int32_t* records, int64_t n, void* stream,
@@ -558,6 +657,49 @@ int cl_store_extent_planes_host(const uint8_t* reads, const uint8_t* qual, const
     });
 }
 
+namespace {
+
+// what both spans entries do once their source is known
+int spans_source(const char* who, const st::HostSource& src, int64_t n_slots, int32_t S, int32_t W, const int32_t* slots, int64_t n, int32_t* kept_out,
+                 int32_t* cells_out, int32_t* mergeable_out, uint16_t* rowspans_out) {
+    if (W > st::COMPACT_MAX_WINDOW) return sfail(nullptr, -1, "%s: a window of %d columns exceeds the compact format's %d", who, W, st::COMPACT_MAX_WINDOW);
+    if (n < 0) return sfail(nullptr, -1, "%s: bad record count", who);
+    if (n > 0 && (!slots || !kept_out || !cells_out || !mergeable_out || !rowspans_out)) return sfail(nullptr, -1, "%s: null argument", who);
+    for (int64_t i = 0; i < n; ++i)
+        if (slots[i] < 0 || slots[i] >= n_slots) return sfail(nullptr, -1, "%s: entry %lld names slot %d of %lld", who, (long long)i, slots[i],
+                                                          (long long)n_slots);
+    for (int64_t i = 0; i < n; ++i) {
+        const st::SpanSums g = st::spans_host(src, slots[i], S, W, rowspans_out + (size_t)i * S);
+        kept_out[i] = g.kept; cells_out[i] = g.cells; mergeable_out[i] = g.mergeable;
+    }
+    return 0;
+}
+
+}  // namespace
+
+int cl_store_spans_host(const uint8_t* inflated, uint64_t inflated_bytes, int64_t record_bytes, const int64_t* plane_off, int32_t stored_rows,
+                        int32_t window, const int32_t* slots, int64_t n, int32_t* kept_out, int32_t* cells_out, int32_t* mergeable_out,
+                        uint16_t* rowspans_out) {
+    const char* who = "cl_store_spans_host";
+    return capi::guarded(g_store_err, who, [&] {
+        int64_t n_slots = 0;
+        if (const int rc = extent_arguments(nullptr, who, inflated, inflated_bytes, record_bytes, plane_off, stored_rows, window, &n_slots)) return rc;
+        return spans_source(who, st::record_source(inflated, record_bytes, plane_off), n_slots, stored_rows, window, slots, n, kept_out, cells_out,
+                            mergeable_out, rowspans_out);
+    });
+}
+
+int cl_store_spans_planes_host(const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots, int32_t stored_rows,
+                               int32_t window, const int32_t* slots, int64_t n, int32_t* kept_out, int32_t* cells_out, int32_t* mergeable_out,
+                               uint16_t* rowspans_out) {
+    const char* who = "cl_store_spans_planes_host";
+    return capi::guarded(g_store_err, who, [&] {
+        if (const int rc = planes_arguments(nullptr, who, reads, qual, strand, n_slots, stored_rows, window)) return rc;
+        return spans_source(who, st::planar_source(reads, qual, strand, stored_rows, window), n_slots, stored_rows, window, slots, n, kept_out,
+                            cells_out, mergeable_out, rowspans_out);
+    });
+}
+
 int cl_store_pack_planes_host(cl_store_t* h, const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots,
                               const int32_t* slots, const int32_t* records, int64_t n, int32_t* kept_out) {
     if (!h) return sfail(nullptr, -1, "cl_store_pack_planes_host: null handle");
@@ -611,6 +753,27 @@ int cl_store_record(cl_store_t* h, int64_t record, int32_t* slab, int64_t* offse
     });
 }
 
+int cl_store_record_span(cl_store_t* h, int64_t record, int32_t* format, int64_t* bytes) {
+    if (!h || !format || !bytes) return sfail(h, -1, "cl_store_record_span: null argument");
+    return capi::guarded(h->err, "cl_store_record_span", [&] {
+        if (record < 0 || record >= h->n_records)
+            return sfail(h, -1, "cl_store_record_span: record %lld of %lld", (long long)record, (long long)h->n_records);
+        const Rec& r = h->table[(size_t)record];
+        if (r.kept < 0) return sfail(h, -1, "cl_store_record_span: record %lld is not in the store", (long long)record);
+        *format = r.format; *bytes = (int64_t)r.bytes;
+#ifndef CL_STORE_HOST_ONLY
+        if (!h->on_host) {                               // the format the kernels follow: the device's table entry
+            dev::DeviceGuard guard;
+            st::DevRec d{};
+            ST_TRY(hipSetDevice(h->device));
+            ST_TRY(hipMemcpy(&d, h->d_table.p + record, sizeof d, hipMemcpyDeviceToHost));
+            *format = d.format;
+        }
+#endif
+        return 0;
+    });
+}
+
 int cl_store_slab(cl_store_t* h, int32_t slab, uint8_t* dst, uint64_t dst_bytes, int64_t* data_off, int64_t* used, int64_t* capacity) {
     if (!h || !data_off || !used || !capacity) return sfail(h, -1, "cl_store_slab: null argument");
     return capi::guarded(h->err, "cl_store_slab", [&] {
@@ -644,6 +807,13 @@ int cl_store_get_stats(cl_store_t* h, cl_store_stats* out) {
     }
 #endif
     *out = h->stats;
+    return 0;
+}
+
+int cl_store_get_format_stats(cl_store_t* h, cl_store_format_stats* out) {
+    if (!h || !out) return sfail(h, -1, "cl_store_get_format_stats: null argument");
+    *out = h->fstats;
+    out->format = h->format;
     return 0;
 }
 

@@ -263,7 +263,8 @@ class DeviceBatchPrefetcher:
     ``resident=True`` (``--train-cache-device gpu``): the file is inflated once, at construction, into a record store in device
     memory of at most ``cache_bytes`` (``chunk_loader.ResidentRecords``; a file that does not fit, or a damaged chunk, ends the
     construction with the reason) and closed; the worker skips ``inflate_lists`` and ``batches`` skips ``reserve``: a batch is the
-    host plan, one gather kernel from the store and the counts.  ``stage`` then also holds ``fill_ms``, ``store_bytes`` and
+    host plan, one gather kernel from the store and the counts (``record_format``: ``chunk_loader.RecordStore``'s, the same batches
+    from fewer bytes).  ``stage`` then also holds ``fill_ms``, ``store_bytes`` and
     ``store_records``, and its ``chunks``, ``compressed_bytes`` and ``inflate_ms`` stop growing once the loader is open.
 
     ``path`` may be a ``chunk_loader.BamSource`` instead (``--train_bam``): the store is then filled from the GPU pileup encoder
@@ -277,7 +278,8 @@ class DeviceBatchPrefetcher:
     AHEAD = 4        # index lists whose chunks are inflated in one launch; twice as many plane sets
 
     def __init__(self, path: str, reads: int, batch_sites: int, device: int = 0, use_q: bool = True, use_strand: bool = True,
-                 wait_s: float = 600.0, ahead: int = AHEAD, resident: bool = False, cache_bytes: int = 0, slab_bytes: Optional[int] = None):
+                 wait_s: float = 600.0, ahead: int = AHEAD, resident: bool = False, cache_bytes: int = 0, slab_bytes: Optional[int] = None,
+                 record_format: str = "rows"):
         import torch
         from .chunk_loader import BamSource, DeviceChunkLoader, ResidentRecords, STORE_SLAB_BYTES
         from .site_assembly import plane_set
@@ -296,7 +298,8 @@ class DeviceBatchPrefetcher:
             # (``chunk_loader.ResidentRecords``); every batch of every ``batches`` call is assembled from it
             with torch.cuda.device(self.dev):
                 self.loader = ResidentRecords(source or path, reads, self.B, device=device, use_q=use_q, use_strand=use_strand,
-                                              capacity_bytes=cache_bytes, slab_bytes=slab_bytes or STORE_SLAB_BYTES)
+                                              capacity_bytes=cache_bytes, slab_bytes=slab_bytes or STORE_SLAB_BYTES,
+                                              record_format=record_format)
         else:
             # the record buffer starts at one chunk and is sized by ``batches`` for the lists it is given: a shuffled epoch needs up
             # to ``ahead * batch_sites`` chunks (1 MB each in the production layout), a sequential evaluation pass an eighth of that

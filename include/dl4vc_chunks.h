@@ -110,7 +110,18 @@ int cl_get_stats(cl_loader_t* h, cl_stats* out);
  * takes no byte (slab 0, offset 0).  A slab holds slab_bytes, or what capacity_bytes leaves when that is less.  capacity_bytes
  * bounds the sum of the stored records' bytes, NOT the allocations: a slab is allocated whole, so the device memory a store takes
  * exceeds its records' bytes by the unused part of its slabs (less than one slab when the records are many; 272 bytes of guard and
- * pad per slab besides).  One thread at a time uses a handle. */
+ * pad per slab besides).  One thread at a time uses a handle.
+ *
+ * The compact format (cl_store_set_format(h, 1), windows of at most 255 columns) stores the same record in fewer bytes and
+ * assembles the same planes byte for byte.  For stored row r < kept, [c0_r, c0_r + n_r) is the smallest column range that contains
+ * every non-zero byte of the three planes in that row (n_r = 0, c0_r = 0 for an all-zero row below kept).  A compact record is
+ *   rowtab[kept + 1]  little-endian uint32: bits 0-23 off_r = the cells of rows < r, bits 24-31 c0_r (0 in the last entry, whose
+ *                     off is the record's cells)
+ *   ts[cells]         token | strand << 4 of every cell, row by row
+ *   q[cells]          the quality byte of every cell
+ * and zeros up to the next multiple of 16: pad16(4 (kept + 1) + 2 cells) bytes, none for kept = 0.  A record with any byte >= 16
+ * in its reads or strand plane is stored in the rows layout above inside the same store; cl_store_record_span names the format
+ * of a record.  dl4vc_amd/csrc/store_host.h holds the definition the kernels are tested against. */
 typedef struct cl_store cl_store_t;
 
 /* n_records: the records the store may come to hold (the table's size).  slab_bytes: a multiple of 16.  device < 0: the slabs lie
@@ -120,6 +131,9 @@ int cl_store_open(int32_t window, int32_t stored_rows, int64_t n_records, uint64
                   cl_store_t** out);
 void cl_store_close(cl_store_t* h);
 const char* cl_store_last_error(const cl_store_t* h);   /* h == NULL: the error of a failed cl_store_open or of cl_store_extent_host */
+/* The format records appended from now on are stored in: 0 = rows (the default), 1 = compact.  Refused (-1, with the reason) once
+ * the store holds a record, for any other value, and for the compact format on a store whose window exceeds 255 columns. */
+int cl_store_set_format(cl_store_t* h, int32_t format);
 
 /* Record slots[i] of the loader's last cl_inflate_chunks_device call becomes record records[i] of the store (not in it yet, named
  * once): the extents are measured on the device (kept_out[i], host memory), the records laid out on the host and packed on the
@@ -166,10 +180,22 @@ int cl_store_assemble_host(cl_store_t* h, const int32_t* records, const int16_t*
                            const uint8_t* ref, const uint8_t* ref_mask, const uint8_t* var_mask, int32_t use_q, int32_t use_strand,
                            uint8_t* reads_out, uint8_t* qual_out, uint8_t* strand_out, uint8_t* ref_out, uint8_t* ref_mask_out,
                            uint8_t* var_mask_out, void* stream);
+/* The CPU definition of the compact format's spans (window <= 255), for inflated records and for three host arrays as above:
+ * kept_out[i], cells_out[i] (the sum of the rows' n), mergeable_out[i] (1: no byte >= 16 in the reads or strand plane) and
+ * rowspans_out[i * stored_rows + r] = c0_r | n_r << 8 for every stored row r of record slots[i]. */
+int cl_store_spans_host(const uint8_t* inflated, uint64_t inflated_bytes, int64_t record_bytes, const int64_t* plane_off, int32_t stored_rows,
+                        int32_t window, const int32_t* slots, int64_t n, int32_t* kept_out, int32_t* cells_out, int32_t* mergeable_out,
+                        uint16_t* rowspans_out);
+int cl_store_spans_planes_host(const uint8_t* reads, const uint8_t* qual, const uint8_t* strand, int64_t n_slots, int32_t stored_rows,
+                               int32_t window, const int32_t* slots, int64_t n, int32_t* kept_out, int32_t* cells_out, int32_t* mergeable_out,
+                               uint16_t* rowspans_out);
 
 /* ---- test and debug entries: what the tests need to see of a store; no loader or command-line path calls them ------------------- */
 /* Where a record lies: for a device store read from the table in device memory that the kernels follow. */
 int cl_store_record(cl_store_t* h, int64_t record, int32_t* slab, int64_t* offset, int32_t* kept);
+/* The format a record is stored in (0 rows, 1 compact; for a device store as the table in device memory has it) and the bytes it
+ * takes in its slab. */
+int cl_store_record_span(cl_store_t* h, int64_t record, int32_t* format, int64_t* bytes);
 /* A slab's sizes, and with dst != NULL a copy of its whole allocation (host memory): the slab's `capacity` bytes begin data_off
  * bytes in (a device slab has 256 bytes that are never written in front of them and 16 behind, so that a 16-byte load at a
  * record's last bytes stays inside the allocation), the first `used` of them hold records. */
@@ -189,6 +215,16 @@ typedef struct {
     double assemble_ms;          /* the last cl_store_assemble_device (cl_store_get_stats waits for it) */
 } cl_store_stats;
 int cl_store_get_stats(cl_store_t* h, cl_store_stats* out);
+
+typedef struct {
+    int64_t format;              /* what cl_store_set_format chose */
+    int64_t rows_records;        /* records stored in the rows layout (all of a rows store; of a compact store, those that fell back) */
+    int64_t rows_bytes;          /* and the sum of their bytes in the slabs */
+    int64_t compact_records;     /* records stored in the compact format */
+    int64_t compact_bytes;
+    double spans_ms;             /* record_spans of all appends of a compact store, device time (its extent_ms stays 0) */
+} cl_store_format_stats;
+int cl_store_get_format_stats(cl_store_t* h, cl_store_format_stats* out);
 
 #ifdef __cplusplus
 }

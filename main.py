@@ -133,6 +133,7 @@ def train_main(args, argv) -> int:
         print("--train-loader-device gpu: batches are assembled on the GPU by one loader thread per file; --num-data-workers %d "
               "starts no worker process" % args.num_data_workers)
     resident = getattr(args, "train_cache_device", None) == "gpu"
+    record_format = getattr(args, "train_cache_format", "rows")
     cache = {"left": None}                               # bytes of the budget the files still to be opened may take
     per_rank = -(-args.batch_size // world)
     trainer = DanTrainer(cfg, hyper, max_batch=per_rank, device_id=0)
@@ -168,7 +169,7 @@ def train_main(args, argv) -> int:
         try:
             # (a fill from a BAM asks for the budget itself, once its staging planes are allocated)
             loader = DeviceBatchPrefetcher(path, cfg.reads, batch_sites, device=0, use_q=cfg.use_q, use_strand=cfg.use_strand,
-                                           resident=True, cache_bytes=budget if from_bam else budget())
+                                           resident=True, cache_bytes=budget if from_bam else budget(), record_format=record_format)
         except (ValueError, RuntimeError) as e:
             raise SystemExit("--train-cache-device gpu: %s" % e)
         cache["left"] -= loader.stage["store_bytes"]
@@ -196,6 +197,10 @@ def report_resident(source, loader, seconds):
     line = "--train-cache-device gpu: %s: %d records resident in %d bytes (%.3f of their %d %s bytes), filled in %.2f s" \
         % (source.bam if from_bam else source, st["store_records"], st["store_bytes"], st["store_bytes"] / max(1, planes), planes,
            "plane" if from_bam else "inflated", seconds)
+    if loader.loader.record_format != "rows":
+        line += "; --train-cache-format %s: %d records in %d bytes (%.3f of their %d %s bytes), %d records fell back to rows (%d bytes)" \
+            % (loader.loader.record_format, st["store_compact_records"], st["store_compact_bytes"], st["store_compact_bytes"] / max(1, planes),
+               planes, "plane" if from_bam else "inflated", st["store_rows_records"], st["store_rows_bytes"])
     if from_bam:
         line += "; %d locations: %d on the GPU, %d by pe_encode, %d by the Python builder, %d without a record" \
             % (st["locations"], st["gpu"], st["native"], st["python"], st["no_record"])
@@ -525,8 +530,12 @@ def check_train_loader_device_arguments(args) -> None:
 
 
 def check_train_cache_arguments(args) -> None:
-    """--train-cache-device / --train-cache-bytes: what they refuse (whether the files fit is known when they are filled)."""
+    """--train-cache-device / --train-cache-bytes / --train-cache-format: what they refuse (whether the files fit is known when they
+    are filled)."""
     device, budget = getattr(args, "train_cache_device", None), getattr(args, "train_cache_bytes", None)
+    record_format = getattr(args, "train_cache_format", None)
+    if device is None and budget is None:
+        raise SystemExit("--train-cache-format is the record format of --train-cache-device gpu, which is not given")
     if device is None:
         raise SystemExit("--train-cache-bytes is the budget of --train-cache-device gpu, which is not given")
     if device != "gpu":
@@ -535,6 +544,8 @@ def check_train_cache_arguments(args) -> None:
         raise SystemExit("--train-cache-device gpu keeps the records of --train-loader-device gpu resident: it needs that option")
     if budget is not None and budget < 0:
         raise SystemExit("--train-cache-bytes must not be negative (0: three quarters of the free device memory)")
+    if record_format is not None and record_format not in ("rows", "compact"):
+        raise SystemExit("--train-cache-format must be rows or compact")
 
 
 def check_loader_device_arguments(args) -> None:
@@ -567,7 +578,7 @@ def main(argv=None) -> int:
         check_loader_device_arguments(args)
     if args.train_loader_device is not None:
         check_train_loader_device_arguments(args)
-    if hasattr(args, "train_cache_device") or hasattr(args, "train_cache_bytes"):
+    if hasattr(args, "train_cache_device") or hasattr(args, "train_cache_bytes") or hasattr(args, "train_cache_format"):
         check_train_cache_arguments(args)
     if args.test_bam and not train_bam:
         check_bam_arguments(args)

@@ -55,6 +55,7 @@ if [ -n "$NOFILE" ]; then
   echo "No train.hdf written.  Train straight from the BAM with:"
   echo "  python $SCRIPTDIR/main.py --train_bam $BAM --train_fasta $REFERENCE --train_tp_vcf $OUTDIR/isec/0003.vcf" \
        "--train_tp_full_vcf $OUTDIR/isec/0002.vcf --train_fp_vcf $OUTDIR/isec/0001.vcf --train-loader-device gpu --train-cache-device gpu" \
+       "[--train-cache-format compact]" \
        "( --test_file V.hdf | --test_bam Y.bam --test_fasta REF [--test_tp_vcf ... --test_tp_full_vcf ... --test_fp_vcf ...] )" \
        "<flags of train_variant_caller.sh>"
   exit 0

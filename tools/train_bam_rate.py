@@ -5,7 +5,11 @@ tools/score_bam_rate.py (by default 200 kbp at ~30x, 19 940 locations, all with 
 * ``file``: the converter with ``--pileup-device gpu`` writes train.hdf (libhdf5's gzip), then the resident fill
   (``--train-loader-device gpu --train-cache-device gpu``) inflates it into the record store;
 * ``file_compressed``: the same with ``--compress-device gpu`` (the chunks compressed on the device);
-* ``bam``: ``--train_bam`` -- the encoder's planes go into the record store where they lie, no file.
+* ``bam``: ``--train_bam`` -- the encoder's planes go into the record store where they lie, no file;
+* ``bam_compact``: the same with ``--train-cache-format compact`` (``record_spans`` and ``store_pack_compact`` instead of
+  ``record_extent`` and ``store_pack``; fewer stored bytes, which the record reports per format).
+
+``--arms`` runs a subset, in the order given.
 
 Alternating rounds (file file_compressed bam file ...), every process fresh and under its own ``timeout``; the first that fails or
 runs out of time ends the run.  Per arm and round: the converter's wall clock (0 for ``bam``), the fill (the construction of the
@@ -28,7 +32,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-ARMS = ("file", "file_compressed", "bam")
+ARMS = ("file", "file_compressed", "bam", "bam_compact")
+FROM_BAM = ("bam", "bam_compact")
 
 
 class Count:
@@ -68,12 +73,13 @@ def child(arm, bam, fa, vcf, hdf, batch, threads):
     trainer = DanTrainer(cfg, hyper, max_batch=batch).load_state_dict(synth.torch_default_init(cfg, seed=0, dropout_keys=True))
     budget = lambda: torch.cuda.mem_get_info(0)[0] * 3 // 8   # noqa: E731
     t0 = time.perf_counter()
-    if arm == "bam":
+    if arm in FROM_BAM:
         source, cache = BamSource(bam, fa, locations_from_vcf(vcf, label=2), threads=threads), budget
     else:
         source, cache = hdf, budget()
     stamps = []
-    with DeviceBatchPrefetcher(source, cfg.reads, batch, use_q=cfg.use_q, use_strand=cfg.use_strand, resident=True, cache_bytes=cache) as pf:
+    with DeviceBatchPrefetcher(source, cfg.reads, batch, use_q=cfg.use_q, use_strand=cfg.use_strand, resident=True, cache_bytes=cache,
+                               record_format="compact" if arm == "bam_compact" else "rows") as pf:
         t1 = time.perf_counter()
         sampler = EasyExampleSampler(len(pf), rng=np.random.RandomState(0), plain=True)
         train_epoch(trainer, Count(len(pf)), sampler, hyper, batch, 1, prefetcher=pf, max_batches=1,
@@ -106,6 +112,7 @@ def main():
     ap.add_argument("--threads", type=int, default=16, help="--num-processes of the converter; host threads of the encoders' fallback")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--limit", type=int, default=240, help="seconds each process may take")
+    ap.add_argument("--arms", default=",".join(ARMS), help="the arms to run, in this order")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -120,34 +127,44 @@ def main():
     convert = [sys.executable, os.path.join(ROOT, "tools", "convert_bam_single_reads.py"), "--input", bam, "--fp_vcf", vcf, "--fasta-input", fa,
                "--output", hdf, "--max-reads", "200", "--num-processes", str(a.threads), "--locations-process-step", "100000",
                "--max-insert-length", "10", "--max-insert-length-variant", "50", "--save-q-scores", "--save-strand", "--pileup-device", "gpu"]
+    arms = [n for n in a.arms.split(",") if n]
+    if not arms or any(n not in ARMS for n in arms):
+        sys.exit("--arms: a list of %s" % ", ".join(ARMS))
     rounds = []
     for k in range(a.rounds):
         r = {}
-        for arm in ARMS:
+        for arm in arms:
             wall = 0.0
-            if arm != "bam":
+            if arm not in FROM_BAM:
                 if os.path.isfile(hdf):
                     os.remove(hdf)
                 wall, _ = step(convert + (["--compress-device", "gpu"] if arm == "file_compressed" else []), a.limit)
             dt, out = step(me + ["--child", arm], a.limit)
             r[arm] = json.loads(out.strip().splitlines()[-1])
-            r[arm].update(convert_wall_s=round(wall, 3), file_bytes=os.path.getsize(hdf) if arm != "bam" else 0,
+            r[arm].update(convert_wall_s=round(wall, 3), file_bytes=os.path.getsize(hdf) if arm not in FROM_BAM else 0,
                           bam_to_first_step_s=round(wall + r[arm]["start_to_first_step_s"], 3), child_wall_s=round(dt, 3))
         rounds.append(r)
         print("round %d: %s" % (k, json.dumps(r)), file=sys.stderr, flush=True)
     if os.path.isfile(hdf):
         os.remove(hdf)
-    same = len({(r[arm]["store_records"], r[arm]["store_bytes"]) for r in rounds for arm in ARMS}) == 1
-    if not same:
-        sys.exit("the arms hold different records: %s" % [(arm, r[arm]["store_records"], r[arm]["store_bytes"]) for r in rounds for arm in ARMS])
-    res = {"tool": "train_bam_rate", "locations": n_loc, "records": rounds[0]["bam"]["store_records"], "store_bytes": rounds[0]["bam"]["store_bytes"],
+    # (the arms of one record format hold the same records in the same bytes)
+    held = {compact: {(r[arm]["store_records"], r[arm]["store_bytes"]) for r in rounds for arm in arms if (arm == "bam_compact") == compact}
+            for compact in (False, True)}
+    if any(len(v) > 1 for v in held.values()) or len({n for v in held.values() for n, _b in v}) != 1:
+        sys.exit("the arms hold different records: %s" % [(arm, r[arm]["store_records"], r[arm]["store_bytes"]) for r in rounds for arm in arms])
+    res = {"tool": "train_bam_rate", "locations": n_loc, "records": rounds[0][arms[0]]["store_records"],
+           "store_bytes": {"compact" if compact else "rows": b for compact, v in held.items() for _n, b in v},
            "batch": a.batch, "threads": a.threads, "same_store_in_every_arm": True, "rounds": rounds,
            "shape": "production network, fp32, batch %d; synthetic BAM of %d bp at ~30x; one GPU" % (a.batch, a.length),
            "not_measured": "more than one GPU; a real 30x genome"}
-    for arm in ARMS:
+    for arm in arms:
         res[arm] = {k: round(statistics.median(r[arm][k] for r in rounds), 3)
                     for k in ("convert_wall_s", "fill_s", "bam_to_first_step_s", "peak_device_bytes", "file_bytes")}
         res[arm]["bam_to_first_step_s_rounds"] = [r[arm]["bam_to_first_step_s"] for r in rounds]
+        stage = [r[arm]["stage"] for r in rounds]
+        res[arm]["bytes_per_record"] = round(stage[0]["store_bytes"] / max(1, stage[0]["store_records"]), 1)
+        res[arm]["measure_ms"] = [s["spans_ms"] if arm == "bam_compact" else s["extent_ms"] for s in stage]      # record_spans / record_extent
+        res[arm]["pack_ms"] = [s["pack_ms"] for s in stage]
     line = json.dumps(res)
     print(line)
     if a.out:

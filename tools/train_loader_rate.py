@@ -4,7 +4,8 @@
 
 Arms: ``--num-data-workers 5``, ``--num-data-workers 16``, the device loader (``device``) and the device loader with the files resident
 (``resident``: ``--train-cache-device gpu``; its fill lies in front of the timed window and is reported on its own as ``fill_ms``, with
-the stored bytes per record and their ratio to the inflated bytes).  Every measurement is a fresh process that runs
+the stored bytes per record and their ratio to the inflated bytes) and the same with ``--train-cache-format compact``
+(``resident_compact``; ``--arms`` runs a subset, in the order given).  Every measurement is a fresh process that runs
 the epoch loop of ``main.py --train_file`` -- ``trainer.train_epoch`` over the whole file (a plain shuffled epoch, batches of
 ``--batch``), then ``trainer.evaluate`` over the test file -- under its own ``timeout``; three alternating rounds; the first
 process that fails or runs out of time ends the run.  Per arm and round:
@@ -33,7 +34,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ARMS = (("workers5", 5), ("workers16", 16), ("device", None), ("resident", "resident"))
+ARMS = (("workers5", 5), ("workers16", 16), ("device", None), ("resident", "resident"), ("resident_compact", "resident_compact"))
+RESIDENT = ("resident", "resident_compact")
 
 
 def make_inputs(d, records, test_records):
@@ -76,9 +78,10 @@ def child(workers, train, test, batch, skip):
     def loader(path):
         if workers is None:
             return DeviceBatchPrefetcher(path, cfg.reads, batch, use_q=cfg.use_q, use_strand=cfg.use_strand)
-        if workers == "resident":
+        if workers in RESIDENT:
             return DeviceBatchPrefetcher(path, cfg.reads, batch, use_q=cfg.use_q, use_strand=cfg.use_strand, resident=True,
-                                         cache_bytes=torch.cuda.mem_get_info(0)[0] * 3 // 8)
+                                         cache_bytes=torch.cuda.mem_get_info(0)[0] * 3 // 8,
+                                         record_format="compact" if workers == "resident_compact" else "rows")
         return BatchPrefetcher(path, workers)
 
     stamps = {"train": [], "eval": []}
@@ -91,7 +94,7 @@ def child(workers, train, test, batch, skip):
             evaluate(net, tsrc, hyper, batch, write=lambda _t: stamps["eval"].append(time.perf_counter()), prefetcher=el)
             net.close()
             stages = {}
-            if workers is None or workers == "resident":
+            if workers is None or workers in RESIDENT:
                 for name, l in (("train", tl), ("eval", el)):
                     stages[name] = {k: round(v, 2) if isinstance(v, float) else int(v) for k, v in l.stage.items()}
         cpu1 = cpu_seconds()                                          # (the workers are reaped: their time is in RUSAGE_CHILDREN)
@@ -100,15 +103,17 @@ def child(workers, train, test, batch, skip):
     tr, ev = stamps["train"][:-1], stamps["eval"]                     # (train_epoch's last call is its closing summary line)
     k = min(skip, len(tr) - 2)
     ke = min(2, len(ev) - 2)
-    res = {"arm": "device" if workers is None else workers if workers == "resident" else "workers%d" % workers, "train_sites": n_train, "eval_sites": n_eval, "steps": len(tr),
+    res = {"arm": "device" if workers is None else workers if workers in RESIDENT else "workers%d" % workers, "train_sites": n_train, "eval_sites": n_eval, "steps": len(tr),
            "steps_per_s": round((len(tr) - 1 - k) / (tr[-1] - tr[k]), 3),
            "eval_sites_per_s": round((len(ev) - 1 - ke) * batch / (ev[-1] - ev[ke]), 1),
            "cpu_s": round(cpu1 - cpu0, 2), "cpu_s_per_1000_sites": round((cpu1 - cpu0) * 1000.0 / (n_train + n_eval), 3)}
     if stages:
         res["stages"] = stages
-    if workers == "resident":
+    if workers in RESIDENT:
         both = [stages["train"], stages["eval"]]
         res["fill_ms"] = round(sum(s["fill_ms"] for s in both), 1)
+        res["assemble_ms_per_batch"] = round(sum(s["assemble_ms"] for s in both) / (len(tr) + len(ev)), 4)
+        res["fallback_records"] = sum(s["store_rows_records"] for s in both) if workers == "resident_compact" else 0
         res["stored_bytes_per_record"] = round(sum(s["store_bytes"] for s in both) / sum(s["store_records"] for s in both), 1)
         res["stored_over_inflated"] = round(sum(s["store_bytes"] for s in both) / sum(s["inflated_bytes"] for s in both), 4)
     print(json.dumps(res))
@@ -133,6 +138,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--skip", type=int, default=8, help="training steps in front of the timed window")
     ap.add_argument("--limit", type=int, default=240, help="seconds each measured process may take")
+    ap.add_argument("--arms", default=",".join(n for n, _w in ARMS), help="the arms to run, in this order")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -143,10 +149,13 @@ def main():
         return 0
     me = [sys.executable, os.path.abspath(__file__), "--dir", a.dir, "--records", str(a.records), "--test-records", str(a.test_records),
           "--batch", str(a.batch), "--skip", str(a.skip)]
+    arms = [n for n in a.arms.split(",") if n]
+    if not arms or any(n not in dict(ARMS) for n in arms):
+        sys.exit("--arms: a list of %s" % ", ".join(n for n, _w in ARMS))
     rounds = []
     for k in range(a.rounds):
         r = {}
-        for arm, _w in ARMS:
+        for arm in arms:
             r[arm] = json.loads(step(me + ["--child", arm], a.limit).strip().splitlines()[-1])
         rounds.append(r)
         print("round %d: %s" % (k, json.dumps(r)), file=sys.stderr, flush=True)
@@ -158,12 +167,12 @@ def main():
            "shape": "batch %d, 100 reads x 201 bp, production network, fp32; synthetic labelled records, 200 stored rows, chunks of 8, "
                     "one plain shuffled epoch" % a.batch,
            "device_resident_steps_per_s": round(resident, 3), "rounds": rounds, "not_measured": "more than one GPU"}
-    for arm, _w in ARMS:
+    for arm in arms:
         res[arm] = {"steps_per_s": [r[arm]["steps_per_s"] for r in rounds],
                     "steps_over_device_resident": [round(r[arm]["steps_per_s"] / resident, 3) for r in rounds],
                     "eval_sites_per_s": [r[arm]["eval_sites_per_s"] for r in rounds],
                     "cpu_s_per_1000_sites": [r[arm]["cpu_s_per_1000_sites"] for r in rounds]}
-        for k in ("fill_ms", "stored_bytes_per_record", "stored_over_inflated"):
+        for k in ("fill_ms", "stored_bytes_per_record", "stored_over_inflated", "assemble_ms_per_batch", "fallback_records"):
             if k in rounds[0][arm]:
                 res[arm][k] = [r[arm][k] for r in rounds]
     line = json.dumps(res)
