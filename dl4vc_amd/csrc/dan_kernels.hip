@@ -172,7 +172,7 @@ next_row:                                                   // (PERSIST only: ba
     const int u_off = SPLIT ? (unit ? a.u_off[1] : a.u_off[0]) : 0;
     [[maybe_unused]] const int own_lo = SPLIT ? (unit ? a.own_lo[1] : a.own_lo[0]) : 0;
     [[maybe_unused]] const int own_hi = SPLIT ? (unit ? a.own_hi[1] : a.own_hi[0]) : L;
-    [[maybe_unused]] const int stamp_row = wk;
+    [[maybe_unused]] const int stamp_row = FOLD ? wk * a.R + fold_r : wk;    // (FOLD: a stamp row per read of the site)
     int tid = threadIdx.x;
     if (PERSIST) asm volatile("" : "+v"(tid));              // per-row: nothing derived from the thread index is hoisted out of
     const int lane = tid & 63;                              // the row loop (it would live through every GEMM and spill)
@@ -593,6 +593,25 @@ next_row:                                                   // (PERSIST only: ba
         __builtin_amdgcn_sched_barrier(0);
         pre_r1 = residual ? w_r1[0] : splat(0.f);
         if (CARRY && !residual && l + 1 < a.l_end) first_frags(l + 1, pn0, pn1, pn2, pn3);      // (residual layers: after their 1x1 GEMM)
+        // residual layers: the layer input under this lane's own cells seeds the 1x1 GEMM's accumulators.  Nobody writes a wave's
+        // own cells before the barrier below, so they are requested here (the conv accumulators are dead): their latency falls
+        // under the deferred bottleneck GEMM and the barrier wait, and between the two barriers only the stores remain.
+        // (F(4,3) forms only: the seven-tile and the split forms have no registers for it and read behind the barrier, as ever)
+        constexpr bool SEED_EARLY = W43;
+        [[maybe_unused]] v4f old[TW][2];
+        [[maybe_unused]] v4f rold;
+        if (SEED_EARLY && residual && !from_global) {
+#pragma unroll
+            for (int m = 0; m < TW; ++m)
+#pragma unroll
+                for (int o = 0; o < 2; ++o) {
+                    const int p = wp + 4 * m + 2 * o;
+                    if (p < wl) old[m][o] = *(const v4f*)(xq + (4 * m + 2 * o) * LDS_S + chw);
+                }
+            if constexpr (REM) {
+                if (rp < L) rold = *(const v4f*)rcell;
+            }
+        }
         // the previous layer's bottleneck GEMM (deferred by its layer_tail): the LDS image is still that layer's output
         if (a.has_hw && l > a.l_begin && wave < NWAVE / 2) {
             gv4f_ptr w_bp = (gv4f_ptr)(wblk - LAYER_STRIDE + WBOT_OFF) + lane;
@@ -641,16 +660,16 @@ next_row:                                                   // (PERSIST only: ba
                         const int p = wp + 4 * m + 2 * o;
                         if (p < wl) {
                             v4f* cell = (v4f*)(xq + (4 * m + 2 * o) * LDS_S + chw);
-                            const v4f old = *cell;
+                            if constexpr (!SEED_EARLY) old[m][o] = *cell;
                             *cell = out[m][o];
-                            out[m][o] = old + bres;
+                            out[m][o] = old[m][o] + bres;
                         }
                     }
                 if constexpr (REM) {
                     if (rp < L) {
-                        const v4f old = *(const v4f*)rcell;
+                        if constexpr (!SEED_EARLY) rold = *(const v4f*)rcell;
                         *(v4f*)rcell = rout;
-                        rout = old + bres;
+                        rout = rold + bres;
                     }
                 }
             }
@@ -796,11 +815,13 @@ next_row:                                                   // (PERSIST only: ba
 #pragma unroll
             for (int k = 0; k < NF; ++k) fmx[k] = splat(0.f);
         }
+        STAMP(56);
         if (a.has_hw) {
             const int ll = a.l_end - 1;
             bottleneck<NWAVE, false, TILES>(xs, wbot, cst + (ll - a.l_begin) * CST_FLOATS + CST_BBOT,
                                             a.h + (size_t)ll * a.h_layer_stride + read_idx * (size_t)Lw * HPAD, own_hi, wave, lane, own_lo);
         }
+        STAMP(57);
         const bool last_row = r + 1 == a.R;
         // read_mean_kernel: sum = +0, then += rows 0 .. R-1.  final_pool_kernel: max = sum = row 0, then rows 1 .. R-1.
 #pragma unroll
@@ -830,7 +851,9 @@ next_row:                                                   // (PERSIST only: ba
                     if (i < n4) sp[n4 + i] = fmx[k];
                 }
             }
+            STAMP(58);
         } else {
+            STAMP(58);
             // the site's last row: the image is free, so the results go out through it in rolled loops (once per site: short
             // code matters more than speed here) -- every thread puts its elements back where it read them
             const float fR = (float)a.R;

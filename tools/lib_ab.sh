@@ -1,7 +1,10 @@
 # same-box A/B of several builds of libdl4vc_dan.so on one bench command:  tools/lib_ab.sh "<bench args>" <rounds> <build> [<build> ...]
 #   <build> = tree (the tree's library) or NAME for tools/ab/libdl4vc_dan_NAME.so, e.g. built from HEAD's sources with other flags:
 #     git archive HEAD dl4vc_amd/csrc include | tar -x -C /tmp/b && make -C /tmp/b/dl4vc_amd/csrc libdl4vc_dan.so CXXFLAGS='...' && cp ... tools/ab/
+#   every bench runs under its own time limit (BENCH_LIMIT seconds, default 600); the first failure ends the script
 set -e
+PY=$(command -v python)
+python() { if [ "$1" = bench.py ]; then timeout -k 10 ${BENCH_LIMIT:-600} "$PY" "$@"; else "$PY" "$@"; fi; }
 ARGS="${1:---precision 1 --sites 32768}"
 N=${2:-2}
 TAG=$(echo "$ARGS" | tr -c "a-zA-Z0-9" "_")

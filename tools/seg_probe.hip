@@ -1,6 +1,8 @@
 // Diagnostic build of the conv-stack segment kernel with per-phase s_memtime stamps (never shipped,
 // never timed for throughput: stamps serialise the schedule -- read the SHARES, not the length).
-//   hipcc -O3 --offload-arch=gfx950 -DDAN_STAMPS tools/seg_probe.hip -o /tmp/seg_probe && /tmp/seg_probe [l_begin l_end [0 [wino [L [table 0|1]]]]]
+//   hipcc -O3 --offload-arch=gfx950 -DDAN_STAMPS tools/seg_probe.hip -o /tmp/seg_probe && /tmp/seg_probe [l_begin l_end [0 [wino [L [table 0|1 [fold 0|1]]]]]]
+// fold 1: the site-owning form (SegmentArgs::fold) at 256 sites, one per workgroup; its row end has stamps of its own (56 planes
+// requested, 57 last bottleneck GEMM done, 58 planes updated and stored) and every read of a site is a stamp row.
 #include "../dl4vc_amd/csrc/dan_kernels.hip"
 #include <cstdio>
 #include <cstdlib>
@@ -14,7 +16,8 @@ int main(int argc, char** argv) {
     const int precision = argc > 3 ? atoi(argv[3]) : 0;
     const int wino = argc > 4 ? atoi(argv[4]) : 0;
     const int L = argc > 5 ? atoi(argv[5]) : 201;
-    const int R = 64, sites = 64, layers = 7, nwg = sites * R;
+    const int fold = argc > 7 ? atoi(argv[7]) : 0;
+    const int R = 64, sites = fold ? 256 : 64, layers = 7, nwg = sites * R;
     std::vector<float> wl((size_t)layers * LAYER_STRIDE);
     srand(1);
     for (auto& v : wl) v = (rand() / (float)RAND_MAX - 0.5f) * 0.1f;
@@ -50,17 +53,27 @@ int main(int argc, char** argv) {
     float* d_l0;
     CK(hipMalloc(&d_l0, l0_tab_floats(L) * 4)); CK(hipMemset(d_l0, 0, l0_tab_floats(L) * 4));
     a.l0_tab = argc > 6 && atoi(argv[6]) == 0 ? nullptr : d_l0;
+    if (fold) {
+        float *d_planes, *d_feat;
+        CK(hipMalloc(&d_planes, (size_t)sites * 2 * L * CPAD * 4));
+        CK(hipMalloc(&d_feat, (size_t)sites * 2 * CPAD * L * 4));
+        a.fold = 1; a.fold_scratch = d_planes;
+        if (l_end < layers) a.fold_pool = d_pool;
+        else { a.fold_feat = d_feat; a.fold_feat_stride = 2LL * CPAD * L; a.fold_C = CPAD; }
+    }
     for (int rep = 0; rep < 3; ++rep) {
-        launch_segment(a, sites, 0, 0);
+        launch_segment(a, sites, fold ? sites : 0, 0);
         CK(hipDeviceSynchronize());
     }
     std::vector<unsigned long long> st(nst);
     CK(hipMemcpy(st.data(), d_st, nst * 8, hipMemcpyDeviceToHost));
     // median over workgroups/waves of each phase delta
-    auto med = [&](int k0, int k1, int wave_sel) {
+    // (rows: -1 every stamp row; fold form: 0 the rows in front of a site's last, 1 the last rows)
+    auto med = [&](int k0, int k1, int wave_sel, int rows = -1) {
         std::vector<long long> d;
         for (int wg = 0; wg < nwg; ++wg)
             for (int w = 0; w < NWAVE; ++w) {
+                if (rows >= 0 && (wg % R == R - 1) != (rows == 1)) continue;
                 if (wave_sel >= 0 && w != wave_sel) continue;
                 const unsigned long long* s = &st[((size_t)wg * NWAVE + w) * NSTAMP];
                 if (s[k0] && s[k1]) d.push_back((long long)(s[k1] - s[k0]));
@@ -96,7 +109,12 @@ int main(int argc, char** argv) {
         }
         printf("\n");
     }
-    printf("copy_out                    %8lld\n", med(62, 63, -1));
+    if (fold) {
+        printf("fold row end: request %6lld | last bottleneck %6lld %6lld %6lld | update+store %6lld | row end, rows 0..R-2 %7lld | site end (row R-1: update, results) %7lld %7lld\n",
+               med(62, 56, -1), med(56, 57, -1), med(56, 57, 0), med(56, 57, 3), med(57, 58, -1, 0), med(62, 63, -1, 0), med(57, 58, -1, 1), med(58, 63, -1, 1));
+        printf("row, rows 0..R-2            %8lld\n", med(0, 63, -1, 0));
+    }
+    printf("%s                    %8lld\n", fold ? "row end " : "copy_out", med(62, 63, -1));
     printf("total                       %8lld\n", med(0, 63, -1));
     return 0;
 }
