@@ -9,14 +9,15 @@
 //     a sorted random subset drawn with numpy's legacy RandomState algorithms (MT19937, random_sample,
 //     permutation) seeded with (seed + absolute record index) -- bit-compatible with dl4vc_amd/dataset.py;
 //   * allele mask vectors of get_read_mask_vectors (dataset.py:112-250) incl. the blacklist fallback.
-// libhdf5 is dlopen'ed at run time (no link-time dependency); plain C ABI below.
+// libhdf5 is dlopen'ed at run time (no link-time dependency); plain C ABI below, on the shell every native library shares
+// (capi_shell.h): one formatter, every entry whose body can throw under capi::guarded.  The handle owns what it opens.
 #include <dlfcn.h>
 #include <zlib.h>
 
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
-#include <cstdarg>
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "../../include/dl4vc_loader.h"
+#include "capi_shell.h"
 
 namespace {
 
@@ -276,6 +278,24 @@ struct dl_loader {
     int64_t next_issue = 0, next_deliver = 0, n_batches = 0;
     int prefetch = 4;
     bool stop = false;
+    bool piece_lost = false;        // a worker could not even publish its failed piece: dl_next fails instead of waiting for it
+
+    dl_loader() = default;
+    dl_loader(const dl_loader&) = delete;
+    dl_loader& operator=(const dl_loader&) = delete;
+    // (the dlopen'ed libhdf5 is reference-counted by the dynamic loader and deliberately never dlclose'd: it registers atexit
+    // handlers)
+    ~dl_loader() {
+        {
+            std::lock_guard<std::mutex> g(q_mutex);
+            stop = true;
+        }
+        cv_space.notify_all();
+        for (auto& t : workers) if (t.joinable()) t.join();
+        if (tid >= 0) h5.Tclose(tid);
+        if (did >= 0) h5.Dclose(did);
+        if (fid >= 0) h5.Fclose(fid);
+    }
 };
 
 namespace {
@@ -297,13 +317,25 @@ bool read_records(dl_loader* l, int64_t lo, int64_t hi, std::vector<uint8_t>& ou
                 raw.resize(nbytes);
                 if (h.Dread_chunk(l->did, 0, offset, &mask, raw.data()) < 0) { err = "H5Dread_chunk failed"; return false; }
             }
+            // no length from the file is trusted: the copy below takes the chunk's first `need` bytes (plain is reused from
+            // chunk to chunk, so a stream that inflates short would otherwise leave the previous chunk's records in it)
+            const int64_t c_lo = ch * c, a = std::max(lo, c_lo), b = std::min(hi, c_lo + c);
+            const size_t need = (size_t)(b - c_lo) * l->itemsize;
             const uint8_t* src = raw.data();
+            size_t have = (size_t)nbytes;
             if (l->deflate && !(mask & 1u)) {                   // inflate outside the lock: this is the parallel part
                 uLongf dlen = plain.size();
                 if (uncompress(plain.data(), &dlen, raw.data(), (uLong)nbytes) != Z_OK) { err = "zlib inflate failed"; return false; }
                 src = plain.data();
+                have = (size_t)dlen;
             }
-            const int64_t c_lo = ch * c, a = std::max(lo, c_lo), b = std::min(hi, c_lo + c);
+            if (have < need) {
+                char buf[160];
+                snprintf(buf, sizeof buf, "chunk %lld holds %llu bytes%s, the piece needs %llu of it", (long long)ch, (unsigned long long)have,
+                         src == plain.data() ? " once inflated" : "", (unsigned long long)need);
+                err = buf;
+                return false;
+            }
             memcpy(out.data() + (size_t)(a - lo) * l->itemsize, src + (size_t)(a - c_lo) * l->itemsize, (size_t)(b - a) * l->itemsize);
         }
         return true;
@@ -389,44 +421,36 @@ void worker_main(dl_loader* l) {
             if (l->stop || l->next_issue >= l->n_batches) return;
             b = l->next_issue++;
         }
-        std::unique_ptr<Batch> res = build_batch(l, b);
-        {
+        // (an exception leaving a std::thread terminates the process: what build_batch throws is the piece's error, delivered in
+        // order like any other; if not even that can be published, dl_next is told so rather than left waiting)
+        try {
+            std::unique_ptr<Batch> res;
+            try {
+                res = build_batch(l, b);
+            } catch (const std::exception& e) {
+                res.reset(new Batch());
+                res->error = std::string("native loader: ") + e.what();
+            }
             std::lock_guard<std::mutex> g(l->q_mutex);
             l->ready[b] = std::move(res);
+        } catch (...) {
+            std::lock_guard<std::mutex> g(l->q_mutex);
+            l->piece_lost = true;
         }
         l->cv_done.notify_all();
     }
 }
 
-int fail_open(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_open_error = buf;
-    return -1;
-}
+template <class... A>
+int fail_open(const char* fmt, A... a) { return capi::failf(g_open_error, -1, fmt, a...); }
 
-}  // namespace
+// [off, off + extent) lies inside a record of `itemsize` bytes
+bool inside(size_t off, size_t extent, size_t itemsize) { return off <= itemsize && extent <= itemsize - off; }
 
-extern "C" {
-
-const char* dl_last_error(const dl_loader_t* l) { return l ? l->err.c_str() : g_open_error.c_str(); }
-
-int dl_select_rows(uint32_t seed, int32_t num_reads, int32_t stored_rows, int32_t max_reads, int32_t* rows_out) {
-    return select_rows(true, seed, num_reads, stored_rows, max_reads, rows_out);
-}
-
-int dl_allele_masks(const char* vcfrec, const uint8_t* window, uint8_t* ref_mask, uint8_t* var_mask) {
-    std::string why;
-    return allele_masks(vcfrec, window, 201, ref_mask, var_mask, why);
-}
-
-int dl_open(const char* path, const char* libhdf5_path, int32_t reads, int64_t lo, int64_t hi, int32_t batch_sites,
-            uint64_t seed, int32_t use_seed, int32_t threads, int32_t prefetch, dl_loader_t** out) {
-    if (!path || !out || reads < 1 || batch_sites < 1) return fail_open("dl_open: bad argument");
-    *out = nullptr;
+// Every return and every throw before the last worker has started releases the handle, and with it the workers already
+// running and the HDF5 ids, through its destructor.
+int open_loader(const char* path, const char* libhdf5_path, int32_t reads, int64_t lo, int64_t hi, int32_t batch_sites, uint64_t seed,
+                int32_t use_seed, int32_t threads, int32_t prefetch, dl_loader_t** out) {
     std::unique_ptr<dl_loader> l(new dl_loader());
     std::string err;
     if (!load_h5(l->h5, libhdf5_path, err)) return fail_open("%s", err.c_str());
@@ -434,11 +458,8 @@ int dl_open(const char* path, const char* libhdf5_path, int32_t reads, int64_t l
     l->fid = h.Fopen(path, 0, 0);
     if (l->fid < 0) return fail_open("cannot open %s as HDF5", path);
     l->did = h.Dopen2(l->fid, "data", 0);
-    if (l->did < 0) { h.Fclose(l->fid); return fail_open("%s has no dataset 'data'", path); }
+    if (l->did < 0) return fail_open("%s has no dataset 'data'", path);
     l->tid = h.Dget_type(l->did);
-    // every error return below closes the type / dataset / file handles (the dlopen'ed libhdf5 is reference-counted by
-    // the dynamic loader and deliberately never dlclose'd: it registers atexit handlers)
-    auto close_all = [&]() { if (l->tid >= 0) h.Tclose(l->tid); h.Dclose(l->did); h.Fclose(l->fid); l->tid = l->did = l->fid = -1; };
     l->itemsize = h.Tget_size(l->tid);
     hid_t sp = h.Dget_space(l->did);
     hsize_t dims[1] = {0};
@@ -452,17 +473,18 @@ int dl_open(const char* path, const char* libhdf5_path, int32_t reads, int64_t l
         return true;
     };
     if (!(off("single_reads", l->off_reads) && off("ref_bases", l->off_ref) && off("num_reads", l->off_num) &&
-          off("vcfrec", l->off_vcf) && off("q-scores", l->off_q) && off("strand", l->off_strand))) {
-        close_all();
+          off("vcfrec", l->off_vcf) && off("q-scores", l->off_q) && off("strand", l->off_strand)))
         return fail_open("%s: record type lacks a field of the converter schema", path);
-    }
     l->L = 201;
-    // packed layout: ref_bases follows single_reads (tools/convert_bam_single_reads.py:694-698)
-    l->store_rows = (int)((l->off_ref - l->off_reads) / l->L);
-    if (l->store_rows < 1 || (l->off_ref - l->off_reads) % l->L || l->off_strand - l->off_q != (size_t)l->store_rows * l->L) {
-        close_all();
+    // packed layout: ref_bases follows single_reads (tools/convert_bam_single_reads.py:694-698), so their distance is the extent
+    // of each of the three planes; build_batch copies by these offsets, so every field must end inside the record
+    const size_t L = (size_t)l->L, sz = l->itemsize;
+    const size_t plane = l->off_ref >= l->off_reads ? l->off_ref - l->off_reads : 0;
+    if (plane < L || plane % L || plane / L > (size_t)INT_MAX || l->off_strand < l->off_q || l->off_strand - l->off_q != plane ||
+        !(inside(l->off_reads, plane, sz) && inside(l->off_q, plane, sz) && inside(l->off_strand, plane, sz) && inside(l->off_ref, L, sz) &&
+          inside(l->off_vcf, 128, sz) && inside(l->off_num, 4, sz)))
         return fail_open("%s: unexpected record layout", path);
-    }
+    l->store_rows = (int)(plane / L);
     hid_t pl = h.Dget_create_plist(l->did);
     if (pl >= 0) {
         if (h.Pget_layout(pl) == 2 /*H5D_CHUNKED*/) {
@@ -491,28 +513,25 @@ int dl_open(const char* path, const char* libhdf5_path, int32_t reads, int64_t l
     l->n_batches = (l->hi - l->lo + l->piece - 1) / l->piece;          // counted in pieces
     const int nt = std::max(1, std::min(threads, 64));
     l->prefetch = std::max(std::max(1, prefetch) * (batch_sites / l->piece), 2 * nt);
-    dl_loader* raw = l.release();
-    for (int i = 0; i < nt; ++i) raw->workers.emplace_back(worker_main, raw);
-    *out = raw;
+    l->workers.reserve((size_t)nt);
+    for (int i = 0; i < nt; ++i) l->workers.emplace_back(worker_main, l.get());
+    *out = l.release();
     return 0;
 }
 
-int64_t dl_num_records(const dl_loader_t* l) { return l ? l->n_records : -1; }
-int64_t dl_num_sites(const dl_loader_t* l) { return l ? l->hi - l->lo : -1; }
-int32_t dl_window(const dl_loader_t* l) { return l ? l->L : -1; }
-
-int64_t dl_next(dl_loader_t* l, uint8_t* reads, uint8_t* qual, uint8_t* strand, uint8_t* ref, uint8_t* ref_mask,
-                uint8_t* var_mask, char* vcfrec, int32_t* num_reads, uint8_t* blacklist) {
-    if (!l) return -1;
+// the pieces of one batch in order into the caller's buffers; 0 with `filled`, or -2 with the failed piece's text
+int next_batch(dl_loader* l, uint8_t* reads, uint8_t* qual, uint8_t* strand, uint8_t* ref, uint8_t* ref_mask, uint8_t* var_mask,
+               char* vcfrec, int32_t* num_reads, uint8_t* blacklist, size_t& filled) {
     const size_t rl = (size_t)l->R * l->L;
-    size_t filled = 0;
     while (filled < (size_t)l->batch && l->next_deliver < l->n_batches) {
         std::unique_ptr<Batch> b;
         {
             std::unique_lock<std::mutex> g(l->q_mutex);
-            l->cv_done.wait(g, [&] { return l->ready.count(l->next_deliver) > 0; });
-            b = std::move(l->ready[l->next_deliver]);
-            l->ready.erase(l->next_deliver);
+            l->cv_done.wait(g, [&] { return l->piece_lost || l->ready.count(l->next_deliver) > 0; });
+            const auto it = l->ready.find(l->next_deliver);
+            if (it == l->ready.end()) return capi::failf(l->err, -2, "native loader: a worker could not deliver its piece (out of memory)");
+            b = std::move(it->second);
+            l->ready.erase(it);
             l->next_deliver++;
         }
         l->cv_space.notify_all();
@@ -529,21 +548,50 @@ int64_t dl_next(dl_loader_t* l, uint8_t* reads, uint8_t* qual, uint8_t* strand, 
         if (blacklist) memcpy(blacklist + filled, b->black.data(), n);
         filled += n;
     }
-    return (int64_t)filled;
+    return 0;
 }
 
-void dl_close(dl_loader_t* l) {
-    if (!l) return;
-    {
-        std::lock_guard<std::mutex> g(l->q_mutex);
-        l->stop = true;
-    }
-    l->cv_space.notify_all();
-    for (auto& t : l->workers) t.join();
-    if (l->tid >= 0) l->h5.Tclose(l->tid);
-    if (l->did >= 0) l->h5.Dclose(l->did);
-    if (l->fid >= 0) l->h5.Fclose(l->fid);
-    delete l;
+}  // namespace
+
+extern "C" {
+
+const char* dl_last_error(const dl_loader_t* l) { return l ? l->err.c_str() : g_open_error.c_str(); }
+
+int dl_select_rows(uint32_t seed, int32_t num_reads, int32_t stored_rows, int32_t max_reads, int32_t* rows_out) {
+    return capi::guarded(g_open_error, "dl_select_rows", [&] { return select_rows(true, seed, num_reads, stored_rows, max_reads, rows_out); });
 }
+
+int dl_allele_masks(const char* vcfrec, const uint8_t* window, uint8_t* ref_mask, uint8_t* var_mask) {
+    return capi::guarded(g_open_error, "dl_allele_masks", [&] {
+        std::string why;
+        return allele_masks(vcfrec, window, 201, ref_mask, var_mask, why);
+    });
+}
+
+int dl_open(const char* path, const char* libhdf5_path, int32_t reads, int64_t lo, int64_t hi, int32_t batch_sites,
+            uint64_t seed, int32_t use_seed, int32_t threads, int32_t prefetch, dl_loader_t** out) {
+    if (!path || !out || reads < 1 || batch_sites < 1) return fail_open("dl_open: bad argument");
+    *out = nullptr;
+    return capi::guarded(g_open_error, "dl_open", [&] {
+        return open_loader(path, libhdf5_path, reads, lo, hi, batch_sites, seed, use_seed, threads, prefetch, out);
+    });
+}
+
+int64_t dl_num_records(const dl_loader_t* l) { return l ? l->n_records : -1; }
+int64_t dl_num_sites(const dl_loader_t* l) { return l ? l->hi - l->lo : -1; }
+int32_t dl_window(const dl_loader_t* l) { return l ? l->L : -1; }
+
+int64_t dl_next(dl_loader_t* l, uint8_t* reads, uint8_t* qual, uint8_t* strand, uint8_t* ref, uint8_t* ref_mask,
+                uint8_t* var_mask, char* vcfrec, int32_t* num_reads, uint8_t* blacklist) {
+    if (!l) return -1;
+    size_t filled = 0;
+    const int rc = capi::guarded(l->err, "dl_next", [&] {
+        return next_batch(l, reads, qual, strand, ref, ref_mask, var_mask, vcfrec, num_reads, blacklist, filled);
+    });
+    return rc < 0 ? (int64_t)rc : (int64_t)filled;
+}
+
+// (the destructor joins the workers and closes the ids; nothing in it throws)
+void dl_close(dl_loader_t* l) { delete l; }
 
 }  // extern "C"

@@ -14,12 +14,12 @@
 // tests/test_pileup_edges.py.  Worker threads take contiguous runs of locations, each with its own file handles and window.
 #include "../../include/dl4vc_loader.h"
 #include "bam_native.h"
+#include "capi_shell.h"
 #include "fasta_native.h"
 
 #include <zlib.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -131,40 +131,23 @@ struct Bam : bamn::BamFile {
     int next(std::shared_ptr<Rec>& out) {
         const int g = next_block(b);
         if (g <= 0) return g;
-        const int32_t size = (int32_t)b.size();
+        // framed by the one core (bam_frame.h), aux area not walked; the span is not a reason to refuse a record here
+        bamn::frame::Framed fr;
+        const uint32_t why = bamn::frame::frame_record(b.data(), b.size(), fr, /*aux=*/false);
+        if (why != bamn::frame::W_NONE) { err = bamn::frame::why_text(why); return -1; }
+        bamn::frame::cigar_sums(b.data(), fr);
         auto rec = std::make_shared<Rec>();
-        int32_t tid, pos, l_seq;
-        uint8_t l_name;
-        uint16_t n_cig, flag;
-        memcpy(&tid, &b[0], 4); memcpy(&pos, &b[4], 4);
-        l_name = b[8];
-        memcpy(&n_cig, &b[12], 2); memcpy(&flag, &b[14], 2); memcpy(&l_seq, &b[16], 4);
-        if (l_seq < 0 || (uint64_t)32 + l_name + 4 * (uint64_t)n_cig + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq > (uint64_t)size) {
-            err = "corrupt BAM record (name / CIGAR / sequence lengths exceed the record)";
-            return -1;
-        }
-        rec->tid = tid; rec->pos = pos; rec->flag = flag;
-        size_t o = 32;
-        rec->name.assign((const char*)&b[o], l_name > 0 ? (size_t)l_name - 1 : 0);
-        o += l_name;
-        rec->cigar.resize(n_cig);
-        int nref = 0;
-        for (int i = 0; i < n_cig; ++i) {
-            uint32_t v;
-            memcpy(&v, &b[o + 4 * i], 4);
-            rec->cigar[i] = v;
-            const int op = v & 0xf;
-            if (op == CMATCH || op == CDEL || op == CREF_SKIP || op == CEQUAL || op == CDIFF) nref += (int)(v >> 4);
-        }
-        rec->ref_end = pos + (nref > 0 ? nref : 1);
-        o += 4 * (size_t)n_cig;
-        rec->seq.resize((size_t)l_seq);
-        for (int i = 0; i < l_seq; ++i) {
-            const uint8_t p = b[o + i / 2];
+        rec->tid = fr.tid; rec->pos = fr.pos; rec->flag = (uint16_t)fr.flag;
+        rec->ref_end = (int32_t)(fr.pos + (fr.nref > 0 ? fr.nref : 1));
+        rec->name.assign((const char*)&b[32], (size_t)fr.l_name - 1);
+        rec->cigar.resize(fr.n_cig);
+        for (uint32_t i = 0; i < fr.n_cig; ++i) rec->cigar[i] = bamn::frame::ld32(&b[fr.cigar_off + 4 * i]);
+        rec->seq.resize((size_t)fr.l_seq);
+        for (int32_t i = 0; i < fr.l_seq; ++i) {
+            const uint8_t p = b[fr.seq_off + i / 2];
             rec->seq[i] = SEQ_CODES[(i & 1) ? (p & 0xf) : (p >> 4)];
         }
-        o += ((size_t)l_seq + 1) / 2;
-        rec->qual.assign(b.begin() + o, b.begin() + o + l_seq);
+        rec->qual.assign(b.begin() + fr.qual_off, b.begin() + fr.qual_off + fr.l_seq);
         out = rec;
         return 1;
     }
@@ -232,15 +215,8 @@ struct pe_encoder {
 
 namespace {
 
-int pe_fail(pe_encoder* e, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (e) e->err = buf; else g_pe_error = buf;
-    return -1;
-}
+template <class... A>
+int pe_fail(pe_encoder* e, const char* fmt, A... a) { return capi::failf(e ? e->err : g_pe_error, -1, fmt, a...); }
 
 // one location: status 1 = planes written, 0 = no record (the reference counts an error), 2 = needs the Python column path
 int encode_one(const pe_options& opt, Window& win, Bam& bam, Fasta& fasta, const std::string& contig, int32_t pos1,
@@ -409,15 +385,7 @@ int encode_one(const pe_options& opt, Window& win, Bam& bam, Fasta& fasta, const
     return 1;
 }
 
-}  // namespace
-
-extern "C" {
-
-const char* pe_last_error(const pe_encoder_t* e) { return e ? e->err.c_str() : g_pe_error.c_str(); }
-
-int pe_open(const char* bam_path, const char* bai_path, const char* fasta_path, const pe_options* opt, pe_encoder_t** out) {
-    if (!bam_path || !fasta_path || !opt || !out) return pe_fail(nullptr, "pe_open: null argument");
-    if (opt->window_size < 1 || opt->max_reads < 1) return pe_fail(nullptr, "pe_open: window_size and max_reads must be positive");
+int open_encoder(const char* bam_path, const char* bai_path, const char* fasta_path, const pe_options* opt, pe_encoder_t** out) {
     auto e = std::make_unique<pe_encoder>();
     e->bam_path = bam_path; e->fasta_path = fasta_path; e->opt = *opt;
     {   // both files must open (per-thread handles are opened in pe_encode)
@@ -440,10 +408,8 @@ int pe_open(const char* bam_path, const char* bai_path, const char* fasta_path, 
     return 0;
 }
 
-int pe_encode(pe_encoder_t* e, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads_out, uint8_t* qual_out,
-              uint8_t* strand_out, uint8_t* ref_out, int32_t* num_reads_out, int8_t* status_out, int32_t threads) {
-    if (!e || (n > 0 && (!contigs || !positions || !reads_out || !qual_out || !strand_out || !ref_out || !num_reads_out || !status_out)))
-        return pe_fail(e, "pe_encode: null argument");
+int encode(pe_encoder_t* e, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads_out, uint8_t* qual_out,
+           uint8_t* strand_out, uint8_t* ref_out, int32_t* num_reads_out, int8_t* status_out, int32_t threads) {
     const int W = 2 * e->opt.window_size + 1, MR = e->opt.max_reads;
     const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(threads > 0 ? threads : 1, n));
     std::vector<std::string> errors((size_t)nt);
@@ -471,11 +437,38 @@ int pe_encode(pe_encoder_t* e, const char* const* contigs, const int32_t* positi
       }
     };
     std::vector<std::thread> pool;
-    for (int ti = 1; ti < nt; ++ti) pool.emplace_back(work, ti);
+    pool.reserve((size_t)nt - 1);
+    try {
+        for (int ti = 1; ti < nt; ++ti) pool.emplace_back(work, ti);
+    } catch (...) {                                          // a thread that did not start: the ones that did still end before this frame
+        for (auto& t : pool) t.join();
+        throw;
+    }
     work(0);
     for (auto& t : pool) t.join();
     for (auto& s : errors) if (!s.empty()) return pe_fail(e, "%s", s.c_str());
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* pe_last_error(const pe_encoder_t* e) { return e ? e->err.c_str() : g_pe_error.c_str(); }
+
+int pe_open(const char* bam_path, const char* bai_path, const char* fasta_path, const pe_options* opt, pe_encoder_t** out) {
+    if (!bam_path || !fasta_path || !opt || !out) return pe_fail(nullptr, "pe_open: null argument");
+    if (opt->window_size < 1 || opt->max_reads < 1) return pe_fail(nullptr, "pe_open: window_size and max_reads must be positive");
+    return capi::guarded(g_pe_error, "pe_open", [&] { return open_encoder(bam_path, bai_path, fasta_path, opt, out); });
+}
+
+int pe_encode(pe_encoder_t* e, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads_out, uint8_t* qual_out,
+              uint8_t* strand_out, uint8_t* ref_out, int32_t* num_reads_out, int8_t* status_out, int32_t threads) {
+    if (!e || (n > 0 && (!contigs || !positions || !reads_out || !qual_out || !strand_out || !ref_out || !num_reads_out || !status_out)))
+        return pe_fail(e, "pe_encode: null argument");
+    return capi::guarded(e->err, "pe_encode", [&] {
+        return encode(e, contigs, positions, n, reads_out, qual_out, strand_out, ref_out, num_reads_out, status_out, threads);
+    });
 }
 
 void pe_close(pe_encoder_t* e) { delete e; }

@@ -9,7 +9,9 @@
  * It reads the HDF5 file the converter writes (dataset "data", packed compound records,
  * tools/convert_bam_single_reads.py:659,694-698) and delivers batches of the six uint8 planes that
  * dan_forward() consumes, in record order.  Host-only C++; libhdf5 is dlopen'ed at run time.
- * Every function returns 0 / a count on success and a negative value on error (text: dl_last_error).
+ * Every function returns 0 / a count on success and a negative value on error (text: dl_last_error / pe_last_error):
+ * -1 a refused argument or file, -2 a piece of dl_next that failed, -4 an exception caught at the entry (dl_open, dl_next,
+ * dl_select_rows, dl_allele_masks, pe_open, pe_encode), its text "<entry>: <what()>".  No entry lets an exception out.
  */
 #ifndef DL4VC_LOADER_H
 #define DL4VC_LOADER_H
@@ -27,17 +29,24 @@ typedef struct dl_loader dl_loader_t;
  * reads get a sorted random subset drawn like numpy's legacy RandomState seeded with (seed + absolute record
  * index) -- exactly np.random.seed(s); np.random.random(); np.random.choice(...) of the reference (dataset.py:274-281,
  * 531); with use_seed = 0 such a record is an error instead of an unpinned draw.  `threads` worker threads inflate
- * and assemble 128-site pieces; at most `prefetch` batches are prepared ahead.  `libhdf5_path` may be NULL/"". */
+ * and assemble 128-site pieces; at most `prefetch` batches are prepared ahead.  `libhdf5_path` may be NULL/"".
+ * Refused (-1) with "<path>: unexpected record layout": a record type in which single_reads, q-scores or strand (each
+ * stored rows x 201 bytes), ref_bases (201), vcfrec (128) or num_reads (4) does not end inside the record, or whose planes are
+ * not laid out as the converter packs them.  When it fails nothing stays open and no thread stays behind. */
 int dl_open(const char* hdf_path, const char* libhdf5_path, int32_t reads, int64_t lo, int64_t hi, int32_t batch_sites,
             uint64_t seed, int32_t use_seed, int32_t threads, int32_t prefetch, dl_loader_t** out);
 int64_t dl_num_records(const dl_loader_t* l);          /* len(dataset), dl4vc/dataset.py:489-491 */
 int64_t dl_num_sites(const dl_loader_t* l);            /* hi - lo */
 int32_t dl_window(const dl_loader_t* l);               /* columns per read (201) */
 /* Next batch in record order into caller buffers (any may be NULL): reads/qual/strand [n][R][L], ref/ref_mask/
- * var_mask [n][L], vcfrec [n][129] NUL-terminated, num_reads [n], blacklist [n].  Returns n (0 at the end). */
+ * var_mask [n][L], vcfrec [n][129] NUL-terminated, num_reads [n], blacklist [n].  Returns n (0 at the end), -2 when a piece
+ * failed: a record the loader refuses (named), "zlib inflate failed", "chunk <c> holds <have> bytes[ once inflated], the piece
+ * needs <need> of it" (no length in the file is trusted: a chunk that inflates short, or is stored short without the filter,
+ * is never served from a buffer another chunk left), "native loader: <what()>" for what a worker thread threw; -4 (as
+ * int64_t) for an exception in the call itself. */
 int64_t dl_next(dl_loader_t* l, uint8_t* reads, uint8_t* qual, uint8_t* strand, uint8_t* ref, uint8_t* ref_mask,
                 uint8_t* var_mask, char* vcfrec, int32_t* num_reads, uint8_t* blacklist);
-void dl_close(dl_loader_t* l);
+void dl_close(dl_loader_t* l);                         /* stops and joins the workers, closes the file; NULL is allowed */
 const char* dl_last_error(const dl_loader_t* l);       /* l may be NULL: error of the last failed dl_open */
 
 /* Exposed for parity tests: the subset draw and the allele masks on their own.
@@ -60,7 +69,9 @@ int dl_allele_masks(const char* vcfrec, const uint8_t* window /*[201]*/, uint8_t
  * module encodes those, so results are identical to dl4vc_amd/pileup_encoder.py for every location.  Also 2, because the
  * specification has no answer: a read inside the window whose alignment has no reference position (0M 5I) or whose SEQ
  * is shorter than its CIGAR's query length (SEQ '*'); the Python module raises ValueError there.  `threads` workers take
- * contiguous runs of locations (locations sorted by position keep every alignment parsed once per run). */
+ * contiguous runs of locations (locations sorted by position keep every alignment parsed once per run).
+ * A BAM record is framed by the core every BAM path shares (csrc/bam_frame.h); one it refuses fails pe_encode (-1) with the
+ * core's text, e.g. "corrupt BAM record (l_read_name)" for a name length of 0, "... (l_seq exceeds the record)". */
 typedef struct pe_encoder pe_encoder_t;
 typedef struct pe_options {
     int32_t window_size;                 /* --window-size (100) */
