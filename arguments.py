@@ -123,6 +123,17 @@ _EXTRA = [
 ]
 
 _TYPES = {"int": int, "float": float, "str": str}
+# help texts of reference flags whose meaning here needs a word
+_HELP = {
+    "--reads-dynamic-downsample-rate": "training: mean share of a site's reads dropped by dynamic read down-sampling, in [0, 1); the "
+                                       "site's own share is drawn from a normal around it and clipped to [0, 0.8].  Needs "
+                                       "--reads-dynamic-downsample-prob.  Every loader applies it, the GPU-resident ones included; "
+                                       "evaluation never does",
+    "--reads-dynamic-downsample-prob": "training: share of the sites that are down-sampled, in [0, 1].  The reference draws from "
+                                       "the unseeded global generator; here site i of a file of n records draws in epoch e (from 1) "
+                                       "with RandomState(reads_seed + e * n + i), the seed of its read subset, so every epoch "
+                                       "drops other reads and a run is reproducible",
+}
 
 
 def create_arg_parser() -> argparse.ArgumentParser:
@@ -136,7 +147,7 @@ def create_arg_parser() -> argparse.ArgumentParser:
         elif kind in ("ints", "strs"):
             p.add_argument(name, type=int if kind == "ints" else str, nargs="+", default=list(default))
         else:
-            p.add_argument(name, type=_TYPES[kind], default=default)
+            p.add_argument(name, type=_TYPES[kind], default=default, help=_HELP.get(name))
     for name, kind, default, text in _EXTRA:
         if kind == "flag":
             p.add_argument(name, action="store_true", default=default, help=text)

@@ -298,16 +298,18 @@ class DeviceChunkLoader:
         self.stage["records"] += len(plan)
         return plan
 
-    def load_indices(self, indices, seed: int, outs, stream: int = 0) -> IndexedSites:
+    def load_indices(self, indices, seed: int, outs, stream: int = 0, downsample_rate: float = 0.0,
+                     downsample_prob: float = 0.0) -> IndexedSites:
         """The records at ``indices`` -- absolute record indices in any order, at most ``batch_sites`` -- as the sites of ``outs``
         in that order: site i is record ``indices[i]`` and draws the subset of a deep pileup with ``seed + indices[i]``
         (``train_data.assemble_training_batch``'s rule).  Every distinct chunk an index falls in is read once, in ascending
         chunk order, and inflated on the device; two indices of one chunk share it.  After the assembly the reads plane's centre
         tokens are counted (``cl_center_counts_device``) for the targets.  Everything is enqueued on ``stream`` and waited for:
         the planes are complete when the call returns.  The handle must have been opened with ``shuffled``.
-        = ``inflate_lists([indices])`` + ``assemble_list(indices)``."""
+        = ``inflate_lists([indices])`` + ``assemble_list(indices)``.  ``downsample_rate`` / ``downsample_prob``: dynamic read
+        down-sampling of a training batch (``site_assembly.plan_records``)."""
         self.inflate_lists([indices], stream)
-        return self.assemble_list(indices, seed, outs, stream)
+        return self.assemble_list(indices, seed, outs, stream, downsample_rate, downsample_prob)
 
     def inflate_lists(self, lists, stream: int = 0) -> None:
         """The chunks of SEVERAL index lists (at most ``shuffled`` of them, each of at most ``batch_sites`` indices) read and
@@ -351,7 +353,8 @@ class DeviceChunkLoader:
                 self.stage[k] += getattr(st, k)
         self.stage["read_ms"] += (t1 - t0) * 1e3
 
-    def assemble_list(self, indices, seed: int, outs, stream: int = 0) -> IndexedSites:
+    def assemble_list(self, indices, seed: int, outs, stream: int = 0, downsample_rate: float = 0.0,
+                      downsample_prob: float = 0.0) -> IndexedSites:
         """One of the lists of the last ``inflate_lists`` (or any indices inside its chunks) assembled into ``outs``; the second
         half of ``load_indices``."""
         f, torch = self.file, self.torch
@@ -374,7 +377,7 @@ class DeviceChunkLoader:
         for s in set(slots.tolist()):
             texts[s] = bytes(blob["vcfrec"][s]).decode()
         plan = plan_records(slots, idx, blob["num_reads"].reshape(-1), blob["ref_bases"].reshape(n_slots, self.window), texts,
-                            self.reads, self.stored_rows, seed)
+                            self.reads, self.stored_rows, seed, downsample_rate, downsample_prob)
         label = np.array(blob["label"].reshape(-1)[slots]) if "label" in self.blob_dtype.names else np.zeros(m, np.uint8)
         t3 = time.perf_counter()
         counts = np.zeros((m, 2, 16), np.int32)
@@ -878,7 +881,8 @@ class ResidentRecords:
         """The text before the first tab of every record's ``vcfrec``: what ``inference.select_sites`` holds out by."""
         return [bytes(v).split(b"\t", 1)[0].decode() for v in self.blob["vcfrec"]]
 
-    def assemble_list(self, indices, seed: int, outs, stream: int = 0) -> IndexedSites:
+    def assemble_list(self, indices, seed: int, outs, stream: int = 0, downsample_rate: float = 0.0,
+                      downsample_prob: float = 0.0) -> IndexedSites:
         """``DeviceChunkLoader.assemble_list`` from the store: site i is record ``indices[i]`` of the file.  A host store
         (``device < 0``) takes six numpy arrays as ``outs`` and assembles and counts on the host."""
         torch = self.torch
@@ -891,7 +895,8 @@ class ResidentRecords:
         v = lambda x: C.c_void_p(int(x)) if x else None   # noqa: E731
         t2 = time.perf_counter()
         slots = idx.astype(np.int32)
-        plan = plan_records(slots, idx, self._num_reads, self._ref_bases, _RecordTexts(self.blob), self.reads, self.stored_rows, seed)
+        plan = plan_records(slots, idx, self._num_reads, self._ref_bases, _RecordTexts(self.blob), self.reads, self.stored_rows, seed,
+                            downsample_rate, downsample_prob)
         label = np.array(self._label[slots])
         t3 = time.perf_counter()
         counts = np.zeros((m, 2, 16), np.int32)

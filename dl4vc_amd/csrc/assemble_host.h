@@ -5,6 +5,7 @@
 
 #include "device_buffer.h"
 #include "pileup_device.h"
+#include "plan_entry.h"
 
 #include <climits>
 #include <cstring>
@@ -37,6 +38,7 @@ inline int assemble(AssembleState* h, const char* who, const uint8_t* const src[
     if (m < 0 || n_slots < 0 || S < 1 || L < 1 || R < 1) return capi::failf(h->err, -1, "%s: bad shape", who);
     if (R > S) return capi::failf(h->err, -1, "%s: %d rows per site but only %d are stored", who, R, S);
     if (S > INT16_MAX) return capi::failf(h->err, -1, "%s: %d stored rows do not fit the int16 row index", who, S);
+    if (rows && S > plan_entry::MAX_STORED) return capi::failf(h->err, -1, "%s: %d stored rows do not fit a plan entry beside its zero-reads bit", who, S);
     if (m > INT32_MAX / 4 || (int64_t)R * L > INT32_MAX / 2) return capi::failf(h->err, -1, "%s: too large", who);
     if (slot_stride < (int64_t)S * L) return capi::failf(h->err, -1, "%s: a slot stride of %lld bytes is less than a plane", who, (long long)slot_stride);
     if (m == 0) return 0;
@@ -51,9 +53,10 @@ inline int assemble(AssembleState* h, const char* who, const uint8_t* const src[
         if (rows && !(first_rows && first_rows[i])) {
             any_rows = true;
             const int16_t* r = rows + (size_t)i * R;
-            for (int k = 0; k < R; ++k)
-                if (r[k] < 0 || r[k] >= S) return capi::failf(h->err, -1, "%s: site %lld row %d names stored row %d of %d", who, (long long)i, k,
-                                                        (int)r[k], S);
+            for (int k = 0; k < R; ++k) {                   // (the zero-reads bit of an entry is not part of its row, plan_entry.h)
+                const int row = plan_entry::stored_row(r[k]);
+                if (row < 0 || row >= S) return capi::failf(h->err, -1, "%s: site %lld row %d names stored row %d of %d", who, (long long)i, k, row, S);
+            }
         }
     }
     dev::DeviceGuard guard;

@@ -9,13 +9,15 @@
 // byte by exactly one lane.  The 16 source bytes of a body store lie in one source row for all but one store in L / 16; they are
 // read with one 16-byte load at the source's own (arbitrary) alignment.  A store that straddles two output rows gathers its bytes
 // one by one.  "First R rows" is the same code with the whole span as one row of R * L bytes: no store straddles, the copy is
-// one contiguous stream.  A plane the model does not use is zero-filled by the same head / body / tail split.
+// one contiguous stream.  A plane the model does not use is zero-filled by the same head / body / tail split.  A row whose plan
+// entry carries the zero-reads bit (plan_entry.h) is zeros in the reads plane and the stored row in the other two.
 //
 // center_counts (cl_center_counts_device): the read tokens of an assembled reads plane [m][R][L] counted at the two columns the
 // training targets look at (alleles.count_center_support: the centre column and the one after it).  One 64-lane wave per site:
 // lane i takes rows i, i + 64, ..., adds its two tokens to 2 x 16 integer counters in LDS, and lanes 0..31 write the counters out,
 // every output element once.  Integer adds in LDS: the counts do not depend on the order the lanes arrive in.
 #include "pileup_device.h"
+#include "plan_entry.h"
 
 namespace pg {
 
@@ -26,9 +28,11 @@ struct __attribute__((packed, aligned(1))) U128 { u32x4 v; };   // a 16-byte loa
 
 __device__ __forceinline__ u32x4 load16_any(const uint8_t* p) { return reinterpret_cast<const U128*>(p)->v; }
 
-__device__ __forceinline__ uint8_t gather_byte(const uint8_t* slab, const int16_t* rows, int L, int o) {
+// (plan_entry.h: the reads plane of a row whose plan entry carries the zero-reads bit is zeros)
+__device__ __forceinline__ uint8_t gather_byte(const uint8_t* slab, const int16_t* rows, int plane, int L, int o) {
     const int r = o / L;
-    return slab[(size_t)rows[r] * L + (o - r * L)];
+    const int row = plan_entry::source_row(rows[r], plane);
+    return row == plan_entry::NO_ROW ? (uint8_t)0 : slab[(size_t)row * L + (o - r * L)];
 }
 
 __global__ __launch_bounds__(ASSEMBLE_BLOCK) void assemble_planes(AssembleArgs a) {
@@ -55,25 +59,26 @@ __global__ __launch_bounds__(ASSEMBLE_BLOCK) void assemble_planes(AssembleArgs a
     }
     const int16_t* rows = a.rows + (size_t)site * a.R;
     const int L = a.L;
-    for (int o = threadIdx.x; o < head; o += ASSEMBLE_BLOCK) dst[o] = gather_byte(slab, rows, L, o);
+    for (int o = threadIdx.x; o < head; o += ASSEMBLE_BLOCK) dst[o] = gather_byte(slab, rows, plane, L, o);
     for (int j = threadIdx.x; j < n16; j += ASSEMBLE_BLOCK) {
         const int o = head + (j << 4);
         const int r = o / L, c = o - r * L;
         u32x4 v;
         if (c + 16 <= L) {
-            v = load16_any(slab + (size_t)rows[r] * L + c);
+            const int row = plan_entry::source_row(rows[r], plane);
+            v = row == plan_entry::NO_ROW ? u32x4{0u, 0u, 0u, 0u} : load16_any(slab + (size_t)row * L + c);
         } else {                                           // the store straddles two (L < 16: more) output rows
             uint32_t w[4];
             for (int k = 0; k < 4; ++k) {
                 uint32_t x = 0;
-                for (int b = 0; b < 4; ++b) x |= (uint32_t)gather_byte(slab, rows, L, o + 4 * k + b) << (8 * b);
+                for (int b = 0; b < 4; ++b) x |= (uint32_t)gather_byte(slab, rows, plane, L, o + 4 * k + b) << (8 * b);
                 w[k] = x;
             }
             v = u32x4{w[0], w[1], w[2], w[3]};
         }
         body[j] = v;
     }
-    for (int o = tail0 + threadIdx.x; o < span; o += ASSEMBLE_BLOCK) dst[o] = gather_byte(slab, rows, L, o);
+    for (int o = tail0 + threadIdx.x; o < span; o += ASSEMBLE_BLOCK) dst[o] = gather_byte(slab, rows, plane, L, o);
 }
 
 __global__ __launch_bounds__(COUNTS_BLOCK) void center_counts(const uint8_t* __restrict__ reads, int R, int L, int col,

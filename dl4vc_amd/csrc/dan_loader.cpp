@@ -18,6 +18,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -129,7 +130,29 @@ struct MT {
         while ((v = (next32() & mask)) > max) {}
         return v;
     }
+    double gauss() {                           // numpy legacy_gauss of a fresh state: polar Box-Muller, the second variate
+        double x1, x2, r2;
+        do {
+            x1 = 2.0 * random_sample() - 1.0;
+            x2 = 2.0 * random_sample() - 1.0;
+            r2 = x1 * x1 + x2 * x2;
+        } while (r2 >= 1.0 || r2 == 0.0);
+        return std::sqrt(-2.0 * std::log(r2) / r2) * x2;
+    }
 };
+
+// np.sort(RandomState.choice(pool, k, replace=False)): the legacy shuffle of arange(pool), its first k sorted.  Returns k.
+int sorted_choice(MT& rng, int pool, int k, int32_t* rows) {
+    std::vector<int32_t> perm(pool);
+    for (int i = 0; i < pool; ++i) perm[i] = i;
+    for (int i = pool - 1; i >= 1; --i) {                      // legacy shuffle
+        const uint32_t j = rng.interval((uint32_t)i);
+        std::swap(perm[i], perm[j]);
+    }
+    std::sort(perm.begin(), perm.begin() + k);
+    for (int i = 0; i < k; ++i) rows[i] = perm[i];
+    return k;
+}
 
 // rows of sample_single_reads(random=True), dataset.py:256-287.  Returns count written, -1 if a seed is needed.
 int select_rows(bool have_seed, uint32_t seed, int num_reads, int stored_rows, int max_reads, int32_t* rows) {
@@ -141,17 +164,39 @@ int select_rows(bool have_seed, uint32_t seed, int num_reads, int stored_rows, i
     if (!have_seed) return -1;
     MT rng(seed);
     rng.random_sample();                                       // the disabled dynamic-down-sampling coin, dataset.py:531
-    const int pool = std::min(stored_rows, num_reads);
-    std::vector<int32_t> perm(pool);
-    for (int i = 0; i < pool; ++i) perm[i] = i;
-    for (int i = pool - 1; i >= 1; --i) {                      // legacy shuffle
-        const uint32_t j = rng.interval((uint32_t)i);
-        std::swap(perm[i], perm[j]);
+    return sorted_choice(rng, std::min(stored_rows, num_reads), std::min(max_reads, num_reads), rows);
+}
+
+// sample_single_reads with dynamic_downsample_rate (dataset.py:256-281) behind the coin of dataset.py:531.  rows and zero take
+// min(max_reads, stored_rows) entries; returns their count.
+int select_rows_downsample(uint32_t seed, int num_reads, int stored_rows, int max_reads, double rate, double prob, int32_t* rows,
+                           uint8_t* zero, int32_t* sampled_out) {
+    MT rng(seed);
+    const double u = rng.random_sample();                      // dataset.py:531
+    int sampled = num_reads;
+    if (u < prob && rate > 0.0) {
+        // double_sample_rate(rate, min_rate=0, max_rate=0.8, stdev=1), dataset.py:17-22
+        const double d = std::min(std::max(rate + std::max(0.001, rate / 2.0) * rng.gauss(), 0.0), 0.8);
+        sampled = (int)((1.0 - d) * num_reads);
     }
-    const int k = std::min(max_reads, num_reads);
-    std::sort(perm.begin(), perm.begin() + k);
-    for (int i = 0; i < k; ++i) rows[i] = perm[i];
-    return k;
+    if (sampled_out) *sampled_out = sampled;
+    const int R = std::min(max_reads, stored_rows);
+    std::fill(zero, zero + std::max(R, 0), (uint8_t)0);
+    if (sampled == num_reads) {                                // no read dropped: select_rows behind the same coin
+        if (R >= num_reads) {
+            for (int i = 0; i < R; ++i) rows[i] = i;
+            return R;
+        }
+        return sorted_choice(rng, std::min(stored_rows, num_reads), std::min(R, num_reads), rows);
+    }
+    const int k = sorted_choice(rng, std::min(stored_rows, num_reads), std::min(R, sampled), rows);
+    if (k < R) {
+        // the rows short of R name the last stored row; its reads plane is zeroed before the gather (dataset.py:278-281), also
+        // where the subset chose that row itself
+        for (int i = k; i < R; ++i) rows[i] = stored_rows - 1;
+        for (int i = 0; i < R; ++i) zero[i] = rows[i] == stored_rows - 1;
+    }
+    return R;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -559,6 +604,16 @@ const char* dl_last_error(const dl_loader_t* l) { return l ? l->err.c_str() : g_
 
 int dl_select_rows(uint32_t seed, int32_t num_reads, int32_t stored_rows, int32_t max_reads, int32_t* rows_out) {
     return capi::guarded(g_open_error, "dl_select_rows", [&] { return select_rows(true, seed, num_reads, stored_rows, max_reads, rows_out); });
+}
+
+int dl_select_rows_downsample(uint32_t seed, int32_t num_reads, int32_t stored_rows, int32_t max_reads, double rate, double prob,
+                              int32_t* rows_out, uint8_t* zero_reads_out, int32_t* sampled_out) {
+    if (!rows_out || !zero_reads_out || num_reads < 0 || stored_rows < 1 || max_reads < 1 || !(rate >= 0.0 && rate < 1.0) ||
+        !(prob >= 0.0 && prob <= 1.0))
+        return capi::failf(g_open_error, -1, "dl_select_rows_downsample: bad argument");
+    return capi::guarded(g_open_error, "dl_select_rows_downsample", [&] {
+        return select_rows_downsample(seed, num_reads, stored_rows, max_reads, rate, prob, rows_out, zero_reads_out, sampled_out);
+    });
 }
 
 int dl_allele_masks(const char* vcfrec, const uint8_t* window, uint8_t* ref_mask, uint8_t* var_mask) {

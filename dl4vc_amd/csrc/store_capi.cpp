@@ -172,6 +172,7 @@ int check_assemble(cl_store* h, const char* who, const int32_t* records, const i
     const int32_t S = h->stored_rows;
     if (m < 0 || R < 1) return sfail(h, -1, "%s: bad shape", who);
     if (R > S) return sfail(h, -1, "%s: %d rows per site but only %d are stored", who, R, S);
+    if (rows && S > plan_entry::MAX_STORED) return sfail(h, -1, "%s: %d stored rows do not fit a plan entry beside its zero-reads bit", who, S);
     if (m > INT32_MAX / 4 || (int64_t)R * h->window > INT32_MAX / 2) return sfail(h, -1, "%s: too large", who);
     if (m == 0) return 0;
     if (!records) return sfail(h, -1, "%s: null argument", who);
@@ -184,8 +185,10 @@ int check_assemble(cl_store* h, const char* who, const int32_t* records, const i
                                                        records[i]);
         if (rows && !(first_rows && first_rows[i])) {
             const int16_t* r = rows + (size_t)i * R;
-            for (int k = 0; k < R; ++k)
-                if (r[k] < 0 || r[k] >= S) return sfail(h, -1, "%s: site %lld row %d names stored row %d of %d", who, (long long)i, k, (int)r[k], S);
+            for (int k = 0; k < R; ++k) {                   // (the zero-reads bit of an entry is not part of its row, plan_entry.h)
+                const int row = plan_entry::stored_row(r[k]);
+                if (row < 0 || row >= S) return sfail(h, -1, "%s: site %lld row %d names stored row %d of %d", who, (long long)i, k, row, S);
+            }
         }
     }
     return 0;
@@ -481,7 +484,7 @@ int assemble_host(cl_store* h, const int32_t* records, const int16_t* rows, cons
             const uint8_t* rec = r.kept ? h->slabs[r.slab]->data + r.off : nullptr;
             const int16_t* site_rows = first ? nullptr : rows + (size_t)i * R;
             if (r.format == st::FORMAT_COMPACT) st::assemble_compact_plane_host(rec, r.kept, p, site_rows, R, L, dst);
-            else st::assemble_plane_host(rec ? rec + (size_t)p * r.kept * L : nullptr, r.kept, site_rows, R, L, dst);
+            else st::assemble_plane_host(rec ? rec + (size_t)p * r.kept * L : nullptr, r.kept, p, site_rows, R, L, dst);
         }
     }
     const size_t b_line = (size_t)m * L;

@@ -25,6 +25,8 @@
 #include <cstring>
 #include <vector>
 
+#include "plan_entry.h"
+
 namespace st {
 
 constexpr int64_t SLAB_GUARD = 256;  // bytes of a device slab's allocation in front of its data (never written)
@@ -188,10 +190,11 @@ inline int layout(Cursor& c, const int32_t* kept, int64_t n, int32_t W, uint64_t
 }
 
 // One site of one plane, the CPU twin of store_assemble: R rows of L bytes at dst from the stored plane src[kept][L].  rows ==
-// nullptr: the first R stored rows.  A row >= kept is zeros.
-inline void assemble_plane_host(const uint8_t* src, int32_t kept, const int16_t* rows, int32_t R, int32_t L, uint8_t* dst) {
+// nullptr: the first R stored rows.  A row >= kept is zeros, and so is the reads plane (plane 0) of a row whose plan entry carries
+// the zero-reads bit (plan_entry.h).
+inline void assemble_plane_host(const uint8_t* src, int32_t kept, int plane, const int16_t* rows, int32_t R, int32_t L, uint8_t* dst) {
     for (int32_t r = 0; r < R; ++r) {
-        const int32_t row = rows ? rows[r] : r;
+        const int32_t row = rows ? plan_entry::source_row(rows[r], plane) : r;
         if (row < kept) memcpy(dst + (size_t)r * L, src + (size_t)row * L, (size_t)L);
         else memset(dst + (size_t)r * L, 0, (size_t)L);
     }
@@ -212,7 +215,7 @@ inline void assemble_compact_plane_host(const uint8_t* rec, int32_t kept, int pl
     const uint8_t* ts = rec + 4 * ((size_t)kept + 1);
     const uint8_t* cell = plane == 1 ? ts + cells : ts;
     for (int32_t r = 0; r < R; ++r) {
-        const int32_t row = rows ? rows[r] : r;
+        const int32_t row = rows ? plan_entry::source_row(rows[r], plane) : r;
         uint8_t* d = dst + (size_t)r * L;
         memset(d, 0, (size_t)L);
         if (row >= kept) continue;

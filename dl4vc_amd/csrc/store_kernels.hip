@@ -16,13 +16,15 @@
 //
 // store_assemble: assemble_planes (assemble_kernels.hip) with the store as the source: one workgroup per (site, plane), the span
 // of R * L output bytes cut at the destination's 16-byte boundaries, every output byte written by exactly one lane.  A row >=
-// kept is zeros; a 16-byte store whose source bytes do not lie in one stored row (it straddles two output rows, or the end of
+// kept is zeros, and so is the reads plane of a row whose plan entry carries the zero-reads bit (plan_entry.h: a flagged row of a
+// compact record decodes its ts byte for the strand only); a 16-byte store whose source bytes do not lie in one stored row (it straddles two output rows, or the end of
 // the kept rows) gathers its bytes one by one.  "First R rows" is min(kept, R) * L contiguous bytes and zeros behind them.
 //
 // A store set to the compact format (store_host.h) measures with record_spans instead of record_extent, packs its mergeable
 // records with store_pack_compact (the others with store_pack) and, once it holds a compact record, assembles with
 // store_assemble<true>, which looks at each site's format; a store of rows records alone keeps store_assemble<false>, the kernel
 // above.  The three are described where they stand.
+#include "plan_entry.h"
 #include "store_device.h"
 
 namespace st {
@@ -97,10 +99,11 @@ __global__ __launch_bounds__(STORE_BLOCK) void store_pack(Source src, const Pack
     }
 }
 
-// byte o of a site's [R][L] span: stored row rows[o / L], zeros where that row was not kept
-__device__ __forceinline__ uint8_t row_byte(const uint8_t* plane, int kept, const int16_t* rows, int L, int o) {
+// byte o of a site's [R][L] span of plane p: the stored row of plan entry rows[o / L], zeros where that row was not kept or
+// the entry forces this plane to zero (plan_entry.h)
+__device__ __forceinline__ uint8_t row_byte(const uint8_t* plane, int kept, const int16_t* rows, int p, int L, int o) {
     const int r = o / L;
-    const int row = rows[r];
+    const int row = plan_entry::source_row(rows[r], p);
     return row < kept ? plane[(size_t)row * L + (o - r * L)] : (uint8_t)0;
 }
 
@@ -298,7 +301,7 @@ __device__ __forceinline__ uint32_t decode4(uint32_t x, int plane) {
 __device__ __forceinline__ uint32_t compact_byte(const uint32_t* rowtab, const uint8_t* cell, int kept, int plane, const int16_t* rows, int L,
                                                  int o) {
     const int r = o / L, c = o - r * L;
-    const int row = rows ? rows[r] : r;
+    const int row = rows ? plan_entry::source_row(rows[r], plane) : r;
     if (row >= kept) return 0;
     const uint32_t e = rowtab[row], off = e & OFF_MASK, n = (rowtab[row + 1] & OFF_MASK) - off;
     const uint32_t j = (uint32_t)(c - (int)(e >> 24));
@@ -322,7 +325,7 @@ __device__ __forceinline__ void assemble_compact(uint8_t* dst, int head, int n16
         const int r = o / L, c = o - r * L;
         u32x4 v = u32x4{0u, 0u, 0u, 0u};
         if (c + 16 <= L) {
-            const int row = rows ? rows[r] : r;
+            const int row = rows ? plan_entry::source_row(rows[r], plane) : r;
             if (row < kept) {
                 const uint32_t e = rowtab[row], off = e & OFF_MASK;
                 const int n = (int)((rowtab[row + 1] & OFF_MASK) - off);
@@ -410,26 +413,26 @@ __global__ __launch_bounds__(STORE_BLOCK) void store_assemble(AssembleArgs a) {
         return;
     }
     const int16_t* rows = a.rows + (size_t)site * a.R;
-    for (int o = tid; o < head; o += STORE_BLOCK) dst[o] = row_byte(src, kept, rows, L, o);
+    for (int o = tid; o < head; o += STORE_BLOCK) dst[o] = row_byte(src, kept, rows, plane, L, o);
     for (int j = tid; j < n16; j += STORE_BLOCK) {
         const int o = head + (j << 4);
         const int r = o / L, c = o - r * L;
         u32x4 v = zero;
         if (c + 16 <= L) {
-            const int row = rows[r];
+            const int row = plan_entry::source_row(rows[r], plane);
             if (row < kept) v = load16_any(src + (size_t)row * L + c);
         } else {                                           // the store straddles two (L < 16: more) output rows
             uint32_t w[4];
             for (int k = 0; k < 4; ++k) {
                 uint32_t x = 0;
-                for (int b = 0; b < 4; ++b) x |= (uint32_t)row_byte(src, kept, rows, L, o + 4 * k + b) << (8 * b);
+                for (int b = 0; b < 4; ++b) x |= (uint32_t)row_byte(src, kept, rows, plane, L, o + 4 * k + b) << (8 * b);
                 w[k] = x;
             }
             v = u32x4{w[0], w[1], w[2], w[3]};
         }
         body[j] = v;
     }
-    for (int o = tail0 + tid; o < span; o += STORE_BLOCK) dst[o] = row_byte(src, kept, rows, L, o);
+    for (int o = tail0 + tid; o < span; o += STORE_BLOCK) dst[o] = row_byte(src, kept, rows, plane, L, o);
 }
 
 }  // namespace

@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (DL4VC_LOADER_LIB: another build of the same library -- the CPU AddressSanitizer pass of tools/asan_pileup.sh)
 LIB_PATH = os.environ.get("DL4VC_LOADER_LIB") or os.path.join(_HERE, "csrc", "libdl4vc_loader.so")
 SYMBOLS = ("dl_open", "dl_num_records", "dl_num_sites", "dl_window", "dl_next", "dl_close", "dl_last_error",
-           "dl_select_rows", "dl_allele_masks", "pe_open", "pe_encode", "pe_close", "pe_last_error")
+           "dl_select_rows", "dl_select_rows_downsample", "dl_allele_masks", "pe_open", "pe_encode", "pe_close", "pe_last_error")
 _lib = None
 
 
@@ -40,6 +40,8 @@ def load_library() -> C.CDLL:
         lib.dl_close.argtypes = [vp]; lib.dl_close.restype = None
         lib.dl_last_error.argtypes = [vp]; lib.dl_last_error.restype = C.c_char_p
         lib.dl_select_rows.argtypes = [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+        lib.dl_select_rows_downsample.argtypes = [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                                  C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
         lib.dl_allele_masks.argtypes = [C.c_char_p, vp, vp, vp]
         lib.pe_open.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, vp, C.POINTER(vp)]
         lib.pe_encode.argtypes = [vp, C.POINTER(C.c_char_p), vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int32]
@@ -51,6 +53,20 @@ def load_library() -> C.CDLL:
 
 def available() -> bool:
     return os.path.isfile(LIB_PATH)
+
+
+def select_rows_downsample(seed: int, num_reads: int, stored_rows: int, max_reads: int, rate: float, prob: float):
+    """``dl_select_rows_downsample`` -> (rows int32, zero_reads bool, sampled): ``dataset.plan_rows`` with
+    ``RandomState(seed)``, natively."""
+    lib = load_library()
+    n = max(int(max_reads), int(stored_rows), 1)
+    rows, zero, sampled = np.zeros(n, np.int32), np.zeros(n, np.uint8), C.c_int32()
+    k = lib.dl_select_rows_downsample(int(seed) & 0xFFFFFFFF, int(num_reads), int(stored_rows), int(max_reads), float(rate), float(prob),
+                                      rows.ctypes.data_as(C.POINTER(C.c_int32)), zero.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                      C.byref(sampled))
+    if k < 0:
+        raise ValueError(lib.dl_last_error(None).decode())
+    return rows[:k], zero[:k].astype(bool), sampled.value
 
 
 class NativeLoader:

@@ -18,8 +18,12 @@ Restates what the reference's dataset adds for training on top of the six input 
   train_variant_caller.sh:115) -- at 64 sites per 45-ms step one process (≈60 ms per batch of shuffled records) would
   starve the GPU.
 
+* dynamic read down-sampling (``--reads-dynamic-downsample-rate`` / ``-prob``; dataset.py:17-22,256-281,531): ``downsample_rate``
+  and ``downsample_prob`` of ``assemble_training_batch`` and of the loaders' ``batches`` -- ``dataset.plan_rows`` on the host,
+  ``site_assembly.plan_records`` (the native draw, the flag bit of a plan entry) for the device loaders.  Training batches only.
+
 Not restated (off in the published scripts, rejected by the CLI when requested): read / reference noise augmentation
-(dataset.py:17-80,292-336), dynamic read down-sampling (dataset.py:258-262).
+(dataset.py:24-80,292-336).
 """
 from __future__ import annotations
 
@@ -43,12 +47,25 @@ class TrainBatch:
     index: np.ndarray              # absolute record indices (the loop writes close flags back by index, trainer.py:263)
     blacklist: np.ndarray
     names: List[str]
+    sampled: Optional[np.ndarray] = None   # (n,) reads dynamic down-sampling kept per site (``sites.num_reads`` where it did not act)
 
     def planes(self):
         return self.sites.arrays()
 
+    def downsampled(self):
+        return downsampled_share(self.sites.num_reads, self.sampled)
+
     def __len__(self):
         return len(self.index)
+
+
+def downsampled_share(num_reads, sampled):
+    """-> (sites dynamic down-sampling dropped reads of, the sum of their kept fractions ``sampled / num_reads``)."""
+    if sampled is None:
+        return 0, 0.0
+    n, k = np.asarray(num_reads, np.float64), np.asarray(sampled, np.float64)
+    hit = k < n
+    return int(hit.sum()), float((k[hit] / n[hit]).sum())
 
 
 def site_targets(record, site, keep_candidate_af: bool = True) -> Dict[str, float]:
@@ -106,13 +123,16 @@ def targets_from_counts(plan, label, counts, non_snp_train_weight: float = 1.0, 
 
 def assemble_training_batch(records, indices: Sequence[int], max_reads: int, seed: Optional[int] = None,
                             non_snp_train_weight: float = 1.0, keep_candidate_af: bool = True, use_q: bool = True,
-                            use_strand: bool = True, trust_weight=None) -> TrainBatch:
+                            use_strand: bool = True, trust_weight=None, downsample_rate: float = 0.0,
+                            downsample_prob: float = 0.0) -> TrainBatch:
     """``records[i]`` is the structured record of absolute index ``indices[i]``.  ``seed`` pins the read subset of deep
-    pileups as in ``dataset.assemble_batch`` (RandomState(seed + absolute index))."""
+    pileups as in ``dataset.assemble_batch`` (RandomState(seed + absolute index)), and with ``downsample_rate`` /
+    ``downsample_prob`` the site's dynamic down-sampling (``dataset.plan_rows``)."""
     sites, tgs = [], []
     for rec, idx in zip(records, indices):
         rng = np.random.RandomState(seed + int(idx)) if seed is not None else None
-        site = assemble_site(rec, max_reads, rng, use_q=use_q, use_strand=use_strand)
+        site = assemble_site(rec, max_reads, rng, use_q=use_q, use_strand=use_strand, downsample_rate=downsample_rate,
+                             downsample_prob=downsample_prob)
         sites.append(site)
         tgs.append(site_targets(rec, site, keep_candidate_af))
     stack = lambda f: np.stack([getattr(s, f) for s in sites])   # noqa: E731
@@ -120,7 +140,7 @@ def assemble_training_batch(records, indices: Sequence[int], max_reads: int, see
                       [s.vcfrec for s in sites], np.array([s.num_reads for s in sites], np.int32))
     t = target_arrays(tgs, non_snp_train_weight, trust_weight)
     return TrainBatch(batch, t, np.asarray(indices, np.int64), np.array([s.blacklist for s in sites], bool),
-                      [s.name for s in sites])
+                      [s.name for s in sites], np.array([s.sampled for s in sites], np.int32))
 
 
 def read_indices(source, indices: np.ndarray) -> np.ndarray:
@@ -225,9 +245,14 @@ class DeviceTrainBatch:
     vcfrec: List[str]
     event: object
     _release: object = None
+    num_reads: Optional[np.ndarray] = None
+    sampled: Optional[np.ndarray] = None   # as ``TrainBatch.sampled``
 
     def planes(self):
         return self.device_planes
+
+    def downsampled(self):
+        return downsampled_share(self.num_reads, self.sampled)
 
     def release(self) -> None:
         rel, self._release = self._release, None
@@ -340,13 +365,16 @@ class DeviceBatchPrefetcher:
                     if k % self.ahead == 0 and not self.resident:    # the chunks of the next few batches, inflated in one launch
                         self.loader.inflate_lists(lists[k:k + self.ahead], self.stream.cuda_stream)
                     planes = self._wait(free, "a free plane set for batch %d (the step that read it has not released it)" % k, stop)
-                    got = self.loader.assemble_list(idx, kwargs["seed"], [t.data_ptr() for t in planes], self.stream.cuda_stream)
+                    got = self.loader.assemble_list(idx, kwargs["seed"], [t.data_ptr() for t in planes], self.stream.cuda_stream,
+                                                    downsample_rate=kwargs.get("downsample_rate", 0.0),
+                                                    downsample_prob=kwargs.get("downsample_prob", 0.0))
                     targets = targets_from_counts(got.plan, got.label, got.counts, kwargs.get("non_snp_train_weight", 1.0),
                                                   kwargs.get("keep_candidate_af", True), kwargs.get("trust_weight"))
                     event = self.torch.cuda.Event()
                     event.record(self.stream)
                     batch = DeviceTrainBatch([t[:len(idx)] for t in planes], targets, idx, np.array(got.plan.blacklist, bool),
-                                             list(got.plan.vcfrec), event, lambda planes=planes: free.put(planes))
+                                             list(got.plan.vcfrec), event, lambda planes=planes: free.put(planes),
+                                             got.plan.num_reads, got.plan.sampled)
                     self._wait(ready, "the consumer to take batch %d" % k, stop, put=(batch,))
                 self._wait(ready, "the consumer to take the end of the batches", stop, put=(None,))
         except _Stopped:

@@ -89,7 +89,8 @@ def split_batch(n: int, rank: int, world: int):
 def train_epoch(trainer, source: CandidateFile, sampler: EasyExampleSampler, hyper: TrainHyper, batch_size: int, epoch: int,
                 reads_seed: int = 0, max_batches: int = 0, keep_candidate_af: bool = True, log: Optional[Callable] = print,
                 rank: int = 0, world: int = 1, all_reduce=None, gather=None, log_interval: int = 1,
-                exchange: Optional[GradientExchange] = None, prefetcher: Optional[BatchPrefetcher] = None) -> Dict[str, float]:
+                exchange: Optional[GradientExchange] = None, prefetcher: Optional[BatchPrefetcher] = None,
+                downsample_rate: float = 0.0, downsample_prob: float = 0.0) -> Dict[str, float]:
     """One pass of ``trainer.train`` (trainer.py:64-472).  ``trainer``: anything with ``backward`` / ``apply`` (and
     ``grad_tensor`` when ``world > 1``) -- ``DanTrainer`` on the GPU.  With ``exchange`` (and a trainer that has the
     ``backward_begin`` / ``wait_bucket`` / ``backward_end`` split) the FC-side gradient bucket is averaged while the
@@ -97,7 +98,9 @@ def train_epoch(trainer, source: CandidateFile, sampler: EasyExampleSampler, hyp
     ``prefetcher``: loader workers assembling this rank's batches ahead of the GPU (``--num-data-workers``), or a
     ``DeviceBatchPrefetcher`` (``--train-loader-device gpu``: the planes of its batches are device tensors, which take the
     ``backward_begin`` / ``backward_end`` split and go back to the loader after ``backward_end``); without it the batches are
-    assembled in this process between steps.  Returns the epoch's mean losses."""
+    assembled in this process between steps.  ``downsample_rate`` / ``downsample_prob``: dynamic read down-sampling of every
+    batch (``dataset.plan_rows``), drawn with the site's seed of this epoch, so an epoch drops other reads than the one before;
+    the epoch then logs how many sites it acted on and their mean kept fraction.  Returns the epoch's mean losses."""
     order = sampler.epoch()
     cfg = trainer.config
     tot = {k: 0.0 for k in ("loss", "bin", "vt", "af", "cov", "vb", "vr")}
@@ -117,6 +120,10 @@ def train_epoch(trainer, source: CandidateFile, sampler: EasyExampleSampler, hyp
     drop_seed = (reads_seed + epoch) * world + rank
     kwargs = dict(max_reads=cfg.reads, seed=draw_seed, non_snp_train_weight=hyper.non_snp_train_weight,
                   keep_candidate_af=keep_candidate_af, use_q=cfg.use_q, use_strand=cfg.use_strand)
+    down = downsample_rate > 0 or downsample_prob > 0
+    if down:                                                           # (the site's draws follow its coin in the same generator)
+        kwargs.update(downsample_rate=downsample_rate, downsample_prob=downsample_prob)
+    down_sites, down_kept, seen_sites = 0, 0.0, 0
     busy = [m for _, _, m in plan if len(m)]
     if prefetcher is not None:
         made = prefetcher.batches(iter(busy), **kwargs)
@@ -160,6 +167,9 @@ def train_epoch(trainer, source: CandidateFile, sampler: EasyExampleSampler, hyp
     nxt = next(feed, None)
     while nxt is not None:
         (b, lo, mine), batch = nxt
+        if down and batch is not None:
+            hit, share = batch.downsampled()
+            down_sites, down_kept, seen_sites = down_sites + hit, down_kept + share, seen_sites + len(batch)
         if world > 1 and exchange is not None and hasattr(trainer, "set_global_batch"):
             global_normalisers(batch)
         if batch is None:
@@ -212,6 +222,9 @@ def train_epoch(trainer, source: CandidateFile, sampler: EasyExampleSampler, hyp
     if log and rank == 0:
         log('%d/%d [%.2f%%] "close matches" within %.2f * %.5f (label smoothing) of true label' %
             (close_n, items, close_n / max(items, 1) * 100.0, hyper.close_match_window, hyper.label_smoothing))
+    if log and down and rank == 0:                                     # (rank 0's share of the batches; on a line of its own)
+        log("\ndynamic read down-sampling (rate %g, prob %g): %d of %d sites down-sampled, mean kept fraction %.4f"
+            % (downsample_rate, downsample_prob, down_sites, seen_sites, down_kept / max(down_sites, 1)))
     return {k: v / max(n_batches, 1) for k, v in tot.items()}
 
 

@@ -11,7 +11,7 @@
  * dan_forward() consumes, in record order.  Host-only C++; libhdf5 is dlopen'ed at run time.
  * Every function returns 0 / a count on success and a negative value on error (text: dl_last_error / pe_last_error):
  * -1 a refused argument or file, -2 a piece of dl_next that failed, -4 an exception caught at the entry (dl_open, dl_next,
- * dl_select_rows, dl_allele_masks, pe_open, pe_encode), its text "<entry>: <what()>".  No entry lets an exception out.
+ * dl_select_rows, dl_select_rows_downsample, dl_allele_masks, pe_open, pe_encode), its text "<entry>: <what()>".  No entry lets an exception out.
  */
 #ifndef DL4VC_LOADER_H
 #define DL4VC_LOADER_H
@@ -54,6 +54,16 @@ const char* dl_last_error(const dl_loader_t* l);       /* l may be NULL: error o
  * dl_allele_masks: 0 = ok, 1 = blacklisted (the reference's AssertionError cases: zero masks), 2 = fatal (the
  * reference dies with a non-assert exception). */
 int dl_select_rows(uint32_t seed, int32_t num_reads, int32_t stored_rows, int32_t max_reads, int32_t* rows_out);
+/* dl_select_rows with the reference's dynamic read down-sampling (dl4vc/dataset.py:17-22, 256-281, 531), draw for draw after
+ * np.random.seed(seed): the coin u = random(); if u < prob, d = clip(normal(rate, max(0.001, rate / 2)), 0, 0.8) (the legacy
+ * polar Box-Muller) and sampled = int((1 - d) * num_reads) reads are kept, else all.  If no read is dropped the rows are
+ * dl_select_rows's.  Otherwise min(R', sampled) sorted rows of the first min(stored_rows, num_reads), R' = min(max_reads,
+ * stored_rows), filled up to R' with stored row stored_rows - 1; where rows were filled, zero_reads_out[r] = 1 for every row r
+ * that names stored row stored_rows - 1 (the reference zeroes that row's reads plane, not its quality or strand), else 0.
+ * rows_out, zero_reads_out: max(max_reads, stored_rows) entries; sampled_out (may be NULL) gets sampled.  Returns the count of
+ * rows, -1 for a bad argument (a rate outside [0, 1), a prob outside [0, 1], a negative size). */
+int dl_select_rows_downsample(uint32_t seed, int32_t num_reads, int32_t stored_rows, int32_t max_reads, double rate, double prob,
+                              int32_t* rows_out, uint8_t* zero_reads_out, int32_t* sampled_out);
 int dl_allele_masks(const char* vcfrec, const uint8_t* window /*[201]*/, uint8_t* ref_mask, uint8_t* var_mask);
 
 /* ---- native pileup encoder -------------------------------------------------------------

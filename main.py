@@ -48,7 +48,7 @@ def train_main(args, argv) -> int:
     if args.test_file:
         assert args.test_file[-3:] == "hdf", "Test dataset must be in HDF format"
     refused = [("--augment-single-reads", args.augment_single_reads), ("--augment-reference", args.augment_reference),
-               ("--reads-dynamic-downsample-rate", args.reads_dynamic_downsample_rate > 0), ("--rm_var_reads_rate", args.rm_var_reads_rate > 0),
+               ("--rm_var_reads_rate", args.rm_var_reads_rate > 0),
                ("--rm_non_var_reads_rate", args.rm_non_var_reads_rate > 0),
                ("--training_use_directional_augmentation", args.training_use_directional_augmentation),
                ("--train-trust-region-table", bool(args.train_trust_region_table)), ("--gatk-table", bool(getattr(args, "gatk_table", "")))]
@@ -302,7 +302,9 @@ def train_loop(args, cfg, hyper, trainer, open_loader, per_rank, rank, world, di
                         max_batches=args.max_train_batches, keep_candidate_af=args.aux_keep_candidate_af, rank=rank, world=world,
                         all_reduce=all_reduce, gather=gather, exchange=exchange, prefetcher=train_loader,
                         log_interval=args.log_interval,
-                        log=lambda m: print(m, end="\r"))
+                        log=lambda m: print(m, end="\r"),
+                        # (dataset.py:531; --delay_augmentation_epochs gates the directional augmentation only, main.py:161-165)
+                        downsample_rate=args.reads_dynamic_downsample_rate, downsample_prob=args.reads_dynamic_downsample_prob)
             print("\n\tTime elapsed for training {:.4f}\n".format(time.time() - s), flush=True)
             s_eval = time.time()
             trainer.set_lr(trainer.hyper.lr * args.lr_decay)                                      # main.py:166
@@ -548,6 +550,24 @@ def check_train_cache_arguments(args) -> None:
         raise SystemExit("--train-cache-format must be rows or compact")
 
 
+def check_downsample_arguments(args) -> None:
+    """--reads-dynamic-downsample-rate / -prob: what they refuse (nothing is silently ignored)."""
+    rate, prob = args.reads_dynamic_downsample_rate, args.reads_dynamic_downsample_prob
+    if not 0.0 <= rate < 1.0:
+        raise SystemExit("--reads-dynamic-downsample-rate must lie in [0, 1): it is the mean share of a site's reads that is dropped "
+                         "(%r given)" % rate)
+    if not 0.0 <= prob <= 1.0:
+        raise SystemExit("--reads-dynamic-downsample-prob must lie in [0, 1]: it is the share of the sites that are down-sampled "
+                         "(%r given)" % prob)
+    if (rate > 0) != (prob > 0):
+        on, off = (("rate", "prob") if rate > 0 else ("prob", "rate"))
+        raise SystemExit("--reads-dynamic-downsample-%s is given without --reads-dynamic-downsample-%s: no site would be down-sampled; "
+                         "give both or neither" % (on, off))
+    if rate > 0 and not args.train_file and not getattr(args, "train_bam", None):
+        raise SystemExit("--reads-dynamic-downsample-rate / -prob are training options: they need --train_file or --train_bam "
+                         "(evaluation and inference never down-sample)")
+
+
 def check_loader_device_arguments(args) -> None:
     """--loader-device: what it refuses (the file's own properties are checked when it is opened)."""
     if args.loader_device != "gpu":
@@ -574,6 +594,7 @@ def main(argv=None) -> int:
         raise SystemExit("--record-census gpu is an option of --test_bam (it counts the locations of the candidate VCF that give a "
                          "record); the records of a --test_file are already counted")
     check_train_bam_arguments(args)
+    check_downsample_arguments(args)
     if args.loader_device is not None:
         check_loader_device_arguments(args)
     if args.train_loader_device is not None:

@@ -2,9 +2,14 @@
 """End-to-end rate of the TRAINING CLI on the GPU box: train.hdf -> main.py --train_file (loader workers, HIP training step)
 against the device-resident step rate of `bench.py --mode train`, written as one JSON record (profiles/rNN_e2e_train.json).
 Two epoch sizes per worker count separate the workers' start-up from the steady-state rate (a line through the two points).
+In place of a worker count an arm may be named: ``resident`` (--train-loader-device gpu --train-cache-device gpu) or
+``resident_downsample`` (the same with --reads-dynamic-downsample-rate 0.3 --reads-dynamic-downsample-prob 0.5).
 Usage: python tools/e2e_train_rate.py [n_sites] [workers...]      (E2E_TRAIN_OUT=path for the JSON, default gpurun_out/e2e_train.json)"""
 import json, os, re, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RESIDENT = ["--train-loader-device", "gpu", "--train-cache-device", "gpu"]
+NAMED_ARMS = {"resident": RESIDENT,
+              "resident_downsample": RESIDENT + ["--reads-dynamic-downsample-rate", "0.3", "--reads-dynamic-downsample-prob", "0.5"]}
 sys.path.insert(0, ROOT)
 import numpy as np
 
@@ -12,7 +17,7 @@ if __name__ == "__main__":
     from dl4vc_amd import hdf5io
     from dl4vc_amd.synth import make_labelled_records as make_records      # (synthetic labelled records with GT columns; test infrastructure)
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
-    workers = [int(w) for w in sys.argv[2:]] or [0, 5]
+    workers = [w if w in NAMED_ARMS else int(w) for w in sys.argv[2:]] or [0, 5]
     td = tempfile.mkdtemp(prefix="e2e_train_")
     base = make_records(256, 100, 900)
     recs = np.concatenate([base] * (n // 256))
@@ -38,7 +43,7 @@ if __name__ == "__main__":
         pts = []
         for path, m_sites in ((small, len(recs) // 4), (train, len(recs))):
             cmd = [sys.executable, os.path.join(ROOT, "main.py"), "--train_file", path, "--test_file", test, "--modelsave",
-                   os.path.join(td, "m%d.pth.tar" % w), "--num-data-workers", str(w)] + flags
+                   os.path.join(td, "m%s.pth.tar" % w)] + (NAMED_ARMS[w] if w in NAMED_ARMS else ["--num-data-workers", str(w)]) + flags
             t0 = time.perf_counter()
             r = subprocess.run(cmd, capture_output=True, text=True)
             dt = time.perf_counter() - t0
@@ -48,7 +53,8 @@ if __name__ == "__main__":
             m = re.search(r"Time elapsed for training ([0-9.]+)", r.stdout)
             tt = float(m.group(1))
             pts.append((m_sites, tt))
-            print("--num-data-workers %d: training epoch of %d sites in %.2f s = %.0f sites/s (whole process %.1f s)" % (w, m_sites, tt, m_sites / tt, dt), flush=True)
+            print("%s: training epoch of %d sites in %.2f s = %.0f sites/s (whole process %.1f s)"
+                  % (w if w in NAMED_ARMS else "--num-data-workers %d" % w, m_sites, tt, m_sites / tt, dt), flush=True)
         (n0, t0_), (n1, t1_) = pts
         per_site = (t1_ - t0_) / (n1 - n0)
         rec["epochs"][str(w)] = {"epoch_s": {str(n0): round(t0_, 3), str(n1): round(t1_, 3)}, "sites_per_s_large_epoch": round(n1 / t1_, 1),

@@ -5,7 +5,9 @@
 Arms: ``--num-data-workers 5``, ``--num-data-workers 16``, the device loader (``device``) and the device loader with the files resident
 (``resident``: ``--train-cache-device gpu``; its fill lies in front of the timed window and is reported on its own as ``fill_ms``, with
 the stored bytes per record and their ratio to the inflated bytes) and the same with ``--train-cache-format compact``
-(``resident_compact``; ``--arms`` runs a subset, in the order given).  Every measurement is a fresh process that runs
+(``resident_compact``), or with dynamic read down-sampling of the training epoch at rate 0.3 and prob 0.5 (``resident_downsample``:
+``--reads-dynamic-downsample-rate 0.3 --reads-dynamic-downsample-prob 0.5``; its evaluation is the ``resident`` arm's);
+``--arms`` runs a subset, in the order given.  Every measurement is a fresh process that runs
 the epoch loop of ``main.py --train_file`` -- ``trainer.train_epoch`` over the whole file (a plain shuffled epoch, batches of
 ``--batch``), then ``trainer.evaluate`` over the test file -- under its own ``timeout``; three alternating rounds; the first
 process that fails or runs out of time ends the run.  Per arm and round:
@@ -34,8 +36,10 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ARMS = (("workers5", 5), ("workers16", 16), ("device", None), ("resident", "resident"), ("resident_compact", "resident_compact"))
-RESIDENT = ("resident", "resident_compact")
+ARMS = (("workers5", 5), ("workers16", 16), ("device", None), ("resident", "resident"), ("resident_compact", "resident_compact"),
+        ("resident_downsample", "resident_downsample"))
+RESIDENT = ("resident", "resident_compact", "resident_downsample")
+DOWNSAMPLE = dict(downsample_rate=0.3, downsample_prob=0.5)          # the ``resident_downsample`` arm's training epoch
 
 
 def make_inputs(d, records, test_records):
@@ -89,7 +93,8 @@ def child(workers, train, test, batch, skip):
         cpu0 = cpu_seconds()
         with loader(train) as tl, loader(test) as el:
             sampler = EasyExampleSampler(len(src), rng=np.random.RandomState(0), plain=True)
-            train_epoch(trainer, src, sampler, hyper, batch, 1, prefetcher=tl, log=lambda _m: stamps["train"].append(time.perf_counter()))
+            train_epoch(trainer, src, sampler, hyper, batch, 1, prefetcher=tl, log=lambda _m: stamps["train"].append(time.perf_counter()),
+                        **(DOWNSAMPLE if workers == "resident_downsample" else {}))
             net = DanNet(cfg, device_id=0, max_batch=batch).load_state_dict(trainer.state_dict())
             evaluate(net, tsrc, hyper, batch, write=lambda _t: stamps["eval"].append(time.perf_counter()), prefetcher=el)
             net.close()
@@ -100,7 +105,8 @@ def child(workers, train, test, batch, skip):
         cpu1 = cpu_seconds()                                          # (the workers are reaped: their time is in RUSAGE_CHILDREN)
         n_train, n_eval = len(src), len(tsrc)
     trainer.close()
-    tr, ev = stamps["train"][:-1], stamps["eval"]                     # (train_epoch's last call is its closing summary line)
+    # (train_epoch's last calls are its closing summary lines: one, and a second with down-sampling)
+    tr, ev = stamps["train"][:-2 if workers == "resident_downsample" else -1], stamps["eval"]
     k = min(skip, len(tr) - 2)
     ke = min(2, len(ev) - 2)
     res = {"arm": "device" if workers is None else workers if workers in RESIDENT else "workers%d" % workers, "train_sites": n_train, "eval_sites": n_eval, "steps": len(tr),
