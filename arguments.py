@@ -113,6 +113,11 @@ _EXTRA = [
     ("--test_tp_full_vcf", "str", argparse.SUPPRESS, "with --test_tp_vcf: as --train_tp_full_vcf"),
     ("--test_fn_vcf", "str", argparse.SUPPRESS, "with --train_bam and --test_bam: as --train_fn_vcf"),
     ("--test_fp_vcf", "str", argparse.SUPPRESS, "with --train_bam and --test_bam: as --train_fp_vcf"),
+    ("--subsample", "float", argparse.SUPPRESS,
+     "with --test_bam / --train_bam: keep the fraction F in (0, 1] of the reads of every BAM this run opens, chosen by a hash of the "
+     "read name as `samtools view --subsample F` chooses them (mates stay together), in front of the pileup: the scored VCF, losses "
+     "and checkpoints are those of the BAM tools/subsample_bam.py writes.  Give candidate generation the same F and seed"),
+    ("--subsample-seed", "int", argparse.SUPPRESS, "seed of --subsample in [0, 2^32) (default 0): another seed keeps another subset"),
     ("--record-census", "str", None, "gpu: with --test_bam, the locations are censused first (which of them give a record, by the GPU "
                                      "encoder's status rule without its planes), so that --gpus N, --shard g/N, "
                                      "--test_holdout_chromosomes and --max-test-batches select and seed the records as --test_file "

@@ -24,8 +24,13 @@
 # -f (needs -r): the candidate generator walks the reads that have no MD tag against REFERENCE (--reference; whole contigs on the
 # GPU, 1 byte per base) instead of giving them no alleles; reads with an MD tag are walked by it as before.  Not passed by
 # default: without -f candidates.vcf is what it was.
+# -s F [-S SEED] (needs -i): every stage that reads the BAM keeps the fraction F in (0, 1] of its reads, chosen by a hash of the
+# read name as `samtools view --subsample F --subsample-seed SEED` chooses them (--subsample / --subsample-seed): candidate
+# generation and the pileup step (the converter, or main.py --test_bam with -d) see the same reads, so the calls are those of the
+# BAM tools/subsample_bam.py writes -- the run at F of the coverage.  A candidates.vcf or candidates.hdf already in OUTDIR is used
+# as it is: give a fresh OUTDIR per fraction.
 set -e
-usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-f] [-c [-y]] [-l]"; exit 1; }
+usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-f] [-c [-y]] [-l] [-s FRACTION [-S SEED]]"; exit 1; }
 GPUS=1
 PROCS=16
 DIRECT=0
@@ -34,7 +39,9 @@ COMPRESS=""
 CODES=""
 LOADER=""
 FROMREF=""
-while getopts "m:o:g:i:r:b:p:fldzcyh" opt; do
+SUBSAMPLE=""
+SEED=""
+while getopts "m:o:g:i:r:b:p:s:S:fldzcyh" opt; do
   case $opt in
     m) MODEL=$OPTARG ;;
     o) OUTDIR=$OPTARG ;;
@@ -48,6 +55,8 @@ while getopts "m:o:g:i:r:b:p:fldzcyh" opt; do
     c) COMPRESS=gpu ;;      # candidates.hdf: pileups, record packing and chunk compression on the GPU
     y) CODES=dynamic ;;     # with -c: dynamic Huffman codes in the compressed chunks
     f) FROMREF=1 ;;         # candidate generation: reads without MD are walked against REFERENCE
+    s) SUBSAMPLE=$OPTARG ;; # every BAM reader keeps this fraction of the reads (--subsample)
+    S) SEED=$OPTARG ;;      # with -s: the seed (--subsample-seed)
     l) LOADER=gpu ;;        # candidates.hdf is inflated and its sites assembled on the GPU (main.py --loader-device gpu)
     *) usage ;;
   esac
@@ -56,6 +65,9 @@ done
 [ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
 [ -n "$LOADER" ] && [ "$DIRECT" = 1 ] && { echo "-l loads candidates.hdf on the GPU and -d reads no candidates.hdf: give one of them"; exit 1; }
 [ -n "$FROMREF" ] && [ -z "$REFERENCE" ] && { echo "-f walks the reads without MD against the reference: give -r REFERENCE as well"; exit 1; }
+[ -n "$SEED" ] && [ -z "$SUBSAMPLE" ] && { echo "-S is the seed of -s: give -s FRACTION as well"; exit 1; }
+[ -n "$SUBSAMPLE" ] && [ -z "$BAM" ] && { echo "-s thins the reads of the BAM: give -i BAM as well (a candidates.hdf holds pileups already encoded)"; exit 1; }
+SUBFLAGS=(${SUBSAMPLE:+--subsample "$SUBSAMPLE"} ${SEED:+--subsample-seed "$SEED"})
 MULTI=""
 [ "$DIRECT" = 1 ] && [ "$GPUS" -gt 1 ] && MULTI=1
 SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -65,11 +77,11 @@ if [ ! -f "$OUTDIR/candidates.hdf" ] && [ ! -f "$OUTDIR/candidates.vcf" ] && [ -
   python "$SCRIPTDIR/tools/candidate_generator.py" --input "$BAM" --output "$OUTDIR/candidates.vcf" \
       --snp_min_freq 0.075 --indel_min_freq 0.02 ${BED:+--bedfile "$BED"} --keep_multialleles \
       ${INFLATE:+--inflate-device "$INFLATE"} ${MULTI:+--gpus "$GPUS"} ${FROMREF:+--reference "$REFERENCE"} \
-      > "$OUTDIR/candidate_generator.log" 2>&1
+      "${SUBFLAGS[@]}" > "$OUTDIR/candidate_generator.log" 2>&1
 fi
 if [ "$DIRECT" = 1 ]; then
   [ -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ] && [ -n "$REFERENCE" ] || { echo "-d needs -i BAM -r REFERENCE (and $OUTDIR/candidates.vcf, made from the BAM when absent)"; exit 1; }
-  TEST_INPUT=(--test_bam "$BAM" --test_fasta "$REFERENCE" ${INFLATE:+--inflate-device "$INFLATE"} ${MULTI:+--record-census gpu})
+  TEST_INPUT=(--test_bam "$BAM" --test_fasta "$REFERENCE" ${INFLATE:+--inflate-device "$INFLATE"} ${MULTI:+--record-census gpu} "${SUBFLAGS[@]}")
 else
   TEST_INPUT=(--test_file "$OUTDIR/candidates.hdf" ${LOADER:+--loader-device "$LOADER"})
 fi
@@ -80,7 +92,7 @@ if [ "$DIRECT" != 1 ] && [ ! -f "$OUTDIR/candidates.hdf" ]; then
       --fasta-input "$REFERENCE" --output "$OUTDIR/candidates.hdf" --max-reads 200 --num-processes "$PROCS" \
       --locations-process-step 100000 --max-insert-length 10 --max-insert-length-variant 50 \
       --save-q-scores --save-strand ${COMPRESS:+--pileup-device gpu --compress-device "$COMPRESS"} \
-      ${CODES:+--compress-codes "$CODES"} > "$OUTDIR/training_data.log" 2>&1
+      ${CODES:+--compress-codes "$CODES"} "${SUBFLAGS[@]}" > "$OUTDIR/training_data.log" 2>&1
 fi
 
 printf "Run inference...\n"

@@ -44,6 +44,66 @@ _CONSUMES_REF = (True, False, True, True, False, False, False, True, True)
 _SEQ_LUT = np.array([ord(c) for c in SEQ_CODES], np.uint8)
 
 
+# ------------------------------------------------------------------------------------------------------
+# Read subsampling by name hash: the Python restatement of csrc/bam_frame.h (name_hash, wang, SampleRule, sampled), the rule of
+# ``samtools view --subsample F --subsample-seed S``.  UNPINNED against samtools itself.
+# ------------------------------------------------------------------------------------------------------
+def name_hash(name: bytes) -> int:
+    """X31 over the bytes of a read name up to its first NUL, each widened as a signed char, mod 2**32; an empty name is 0."""
+    h = None
+    for c in name:
+        if c == 0:
+            break
+        v = c - 256 if c >= 128 else c
+        h = v & 0xffffffff if h is None else (h * 31 + v) & 0xffffffff
+    return 0 if h is None else h
+
+
+def wang(k: int) -> int:
+    """Wang's integer mix on uint32."""
+    m = 0xffffffff
+    k = (k + (~(k << 15) & m)) & m
+    k ^= k >> 10
+    k = (k + (k << 3)) & m
+    k ^= k >> 6
+    k = (k + (~(k << 11) & m)) & m
+    k ^= k >> 16
+    return k
+
+
+class SampleRule:
+    """Keep a read iff ``(wang(name_hash(name) ^ seed) & 0xffffff) < ceil(fraction * 2**24)``: mates share a name and so an
+    answer, and the answer depends on nothing else.  ``fraction`` in (0, 1] (1 keeps every read), ``seed`` in [0, 2**32)."""
+
+    def __init__(self, fraction: float, seed: int = 0):
+        fraction = float(fraction)
+        if not (0.0 < fraction <= 1.0):                      # (NaN fails both comparisons)
+            raise ValueError("the subsample fraction must lie in (0, 1], not %r" % (fraction,))
+        if int(seed) != seed or not (0 <= int(seed) < 1 << 32):
+            raise ValueError("the subsample seed must be an integer in [0, 2**32), not %r" % (seed,))
+        self.fraction, self.seed = fraction, int(seed)
+        v = fraction * 16777216.0                            # exact in double
+        self.threshold = int(v) + (1 if int(v) < v else 0)
+
+    @classmethod
+    def of(cls, subsample) -> Optional["SampleRule"]:
+        """``None``, a rule or ``(fraction, seed)`` -> a rule or None."""
+        if subsample is None or isinstance(subsample, cls):
+            return subsample
+        fraction, seed = subsample
+        return cls(fraction, seed)
+
+    def keeps(self, name: bytes) -> bool:
+        return (wang(name_hash(name) ^ self.seed) & 0xffffff) < self.threshold
+
+    def keeps_record(self, body: bytes) -> bool:
+        """``keeps`` for a record (the bytes behind its block_size field): its name field, at most l_read_name - 1 bytes."""
+        return self.keeps(body[32:32 + body[8] - 1])
+
+    def __repr__(self):
+        return "SampleRule(%r, %d)" % (self.fraction, self.seed)
+
+
 class BgzfReader:
     """Sequential BGZF reader with ``seek`` / ``tell`` on virtual offsets."""
 
@@ -123,6 +183,7 @@ class BamRecord:
     next_pos: int = -1
     tlen: int = 0
     aux: bytes = b""
+    sampled: bool = True          # False: the file's sample rule dropped it (BamFile(subsample=)); it overlaps no region
 
     @property
     def is_reverse(self) -> bool:
@@ -162,8 +223,11 @@ def parse_record(buf: bytes) -> BamRecord:
 class BamFile:
     """Header + sequential / indexed access to the alignments of one BAM file."""
 
-    def __init__(self, path: str, index: Optional[str] = None):
+    def __init__(self, path: str, index: Optional[str] = None, subsample=None):
+        """``subsample``: ``(fraction, seed)`` or a ``SampleRule``; ``fetch`` and ``WindowReader`` then drop the reads the rule
+        drops, where a read outside the region is dropped.  Iteration and ``raw_records`` give every record."""
         self.path = path
+        self.sample = SampleRule.of(subsample)
         self.r = BgzfReader(path)
         if self.r.read(4) != BAM_MAGIC:
             raise ValueError("%s is not a BAM file" % path)
@@ -209,7 +273,23 @@ class BamFile:
         body = self.r.read(size)
         if len(body) < size:
             raise ValueError("truncated BAM record in %s" % self.path)
-        return at, parse_record(body)
+        rec = parse_record(body)
+        if self.sample is not None:
+            rec.sampled = self.sample.keeps_record(body)
+        return at, rec
+
+    def raw_records(self) -> Iterator[bytes]:
+        """Every record's bytes (behind its block_size field) as they lie in the file, in file order."""
+        self.r.seek(self.first_record)
+        while True:
+            head = self.r.read(4)
+            if len(head) < 4:
+                return
+            size = struct.unpack("<i", head)[0]
+            body = self.r.read(size)
+            if size < 32 or len(body) < size:
+                raise ValueError("truncated BAM record in %s" % self.path)
+            yield body
 
     def __iter__(self) -> Iterator[BamRecord]:
         self.r.seek(self.first_record)
@@ -242,7 +322,7 @@ class BamFile:
                 continue
             if rec.pos >= stop:
                 return
-            if rec.reference_end > start:
+            if rec.reference_end > start and rec.sampled:
                 yield rec
 
 
@@ -295,7 +375,7 @@ class WindowReader:
                 elif rec.pos >= stop:
                     self.pending = rec
                     break
-                elif rec.reference_end > start:
+                elif rec.reference_end > start and rec.sampled:
                     self.kept.append(rec)
                 rec = None
             self.at = bam.r.tell()
@@ -448,6 +528,10 @@ class BamWriter:
 
     def write(self, *args, **kw) -> None:
         self.w.write(pack_record(*args, **kw))
+
+    def write_raw(self, body: bytes) -> None:
+        """A record's bytes (behind its block_size field) as they are, not re-packed."""
+        self.w.write(struct.pack("<i", len(body)) + body)
 
     def close(self) -> None:
         self.w.close()

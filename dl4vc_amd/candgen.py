@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_cand.so")
 MAX_ALLELE_LEN = 63          # CG_MAX_ALLELE_LEN
 SYMBOLS = ("cg_open", "cg_run", "cg_last_error", "cg_close", "cg_n_refs", "cg_ref_name", "cg_ref_length",
-           "cg_set_inflate_device", "cg_get_inflate_stats", "cg_debug_ranges",
+           "cg_set_inflate_device", "cg_get_inflate_stats", "cg_debug_ranges", "cg_set_subsample", "cg_get_subsample_stats",
            "cg_set_reference", "cg_get_reference_stats", "cg_reference_codes", "cg_reference_codes_host",
            "bz_inflate", "bz_inflate_host", "bz_status_text", "bz_last_error")
 INFLATE_DEVICES = ("gpu",)
@@ -56,6 +56,10 @@ class ReferenceStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class SubsampleStats(C.Structure):
+    _fields_ = [("records_seen", C.c_int64), ("records_kept", C.c_int64)]
+
+
 _lib = None
 
 
@@ -79,6 +83,8 @@ def load_library() -> C.CDLL:
         lib.cg_get_inflate_stats.argtypes = [C.c_void_p, C.POINTER(InflateStats)]
         lib.cg_debug_ranges.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
                                         C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        lib.cg_set_subsample.argtypes = [C.c_void_p, C.c_double, C.c_uint32]
+        lib.cg_get_subsample_stats.argtypes = [C.c_void_p, C.POINTER(SubsampleStats)]
         lib.cg_set_reference.argtypes = [C.c_void_p, C.c_char_p]
         lib.cg_get_reference_stats.argtypes = [C.c_void_p, C.POINTER(ReferenceStats)]
         lib.cg_reference_codes.argtypes = [C.c_char_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64),
@@ -151,11 +157,16 @@ class CandidateCounter:
     ``inflate_device="gpu"`` sends each batch's BGZF blocks to the device compressed (inflate, record walk and framing there;
     needs the ``.bai``); the stats then carry ``inflate_*`` entries as well.  ``reference="ref.fa"``: a read without an MD tag is
     walked against the FASTA's bases of its contig (whole contigs, resident on the device, 1 byte per base) instead of giving
-    no alleles; reads with MD are walked by their MD as before.  The stats then carry ``reference_*`` entries."""
+    no alleles; reads with MD are walked by their MD as before.  The stats then carry ``reference_*`` entries.
+    ``subsample=(fraction, seed)``: reads are subsampled by name hash (``bamio.SampleRule``, ``cg_set_subsample``) where a read
+    outside the subregion is dropped, on the host or in the device's frame kernel; the stats then carry ``subsample_records_seen``
+    and ``subsample_records_kept``."""
 
     def __init__(self, bam_path: str, bai_path: Optional[str] = None, threads: Optional[int] = None,
                  max_len_indel_allele: int = 60, snp_min_freq: float = 0.01, indel_min_freq: float = 0.01, device: int = 0,
-                 inflate_device: Optional[str] = None, reference: Optional[str] = None):
+                 inflate_device: Optional[str] = None, reference: Optional[str] = None, subsample=None):
+        from .bamio import SampleRule
+        self.subsample = SampleRule.of(subsample)
         if inflate_device is not None and inflate_device not in INFLATE_DEVICES:
             raise ValueError("inflate_device must be None or one of %s" % (INFLATE_DEVICES,))
         self.lib = load_library()
@@ -177,6 +188,10 @@ class CandidateCounter:
             msg = self.lib.cg_last_error().decode()
             self.close()
             raise RuntimeError("cg_set_reference: %s" % msg)
+        if self.subsample is not None and self.lib.cg_set_subsample(h, self.subsample.fraction, self.subsample.seed) != 0:
+            msg = self.lib.cg_last_error().decode()
+            self.close()
+            raise RuntimeError("cg_set_subsample: %s" % msg)
         n = self.lib.cg_n_refs(h)
         self.references: List[str] = [self.lib.cg_ref_name(h, i).decode() for i in range(n)]
         self.lengths: List[int] = [int(self.lib.cg_ref_length(h, i)) for i in range(n)]
@@ -199,6 +214,10 @@ class CandidateCounter:
             rst = ReferenceStats()
             self.lib.cg_get_reference_stats(self.h, C.byref(rst))
             stats.update(("reference_" + k, v) for k, v in rst.as_dict().items())
+        if self.subsample is not None:
+            sst = SubsampleStats()
+            self.lib.cg_get_subsample_stats(self.h, C.byref(sst))
+            stats.update(subsample_records_seen=sst.records_seen, subsample_records_kept=sst.records_kept)
         return res, stats
 
     def debug_ranges(self, tid: int, start: int, end: int):

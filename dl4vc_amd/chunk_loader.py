@@ -744,7 +744,7 @@ class ResidentRecords:
     def from_bam(cls, bam: str, fasta: str, locations, reads: int, batch_sites: int, device: int = 0, use_q: bool = True,
                  use_strand: bool = True, capacity_bytes=0, slab_bytes: int = STORE_SLAB_BYTES, stream: int = 0,
                  debug_fill: Optional[int] = None, encoder_options=None, inflate_device: Optional[str] = None, threads: int = 0,
-                 round_locations: int = FILL_ROUND_LOCATIONS, record_format: str = "rows"):
+                 round_locations: int = FILL_ROUND_LOCATIONS, record_format: str = "rows", subsample=None):
         """The resident records of a BAM (``--train_bam``): what ``tools/convert_bam_single_reads.py`` would write for ``locations``
         (``pileup_encoder.Location``s, in the converter's order) and ``ResidentRecords(path)`` would then inflate, without the file
         (``_fill_from_bam``).
@@ -753,7 +753,13 @@ class ResidentRecords:
         ``max_reads`` x window bytes) are allocated, so that a budget taken from the free device memory does not count them.
         ``device < 0``: the CPU definition -- ``pe_encode`` for every location, a host store, ``cl_store_pack_planes_host``; no GPU.
 
-        ``stage`` also holds the encoders' counts (``location_round.ENCODER_COUNTS``) and ``encode_ms``."""
+        ``stage`` also holds the encoders' counts (``location_round.ENCODER_COUNTS``) and ``encode_ms``.
+
+        ``subsample=(fraction, seed)``: every encoder of the fill drops the reads ``bamio.SampleRule`` drops (it is
+        ``encoder_options.subsample`` for this store): the records are those of the BAM ``tools/subsample_bam.py`` writes."""
+        if subsample is not None:
+            from .location_round import default_encoder_options, with_subsample
+            encoder_options = with_subsample(encoder_options or default_encoder_options(), subsample)
         return cls(BamSource(bam, fasta, locations, inflate_device, encoder_options, threads), reads, batch_sites, device, use_q,
                    use_strand, capacity_bytes, slab_bytes, stream=stream, debug_fill=debug_fill, round_locations=round_locations,
                    record_format=record_format)

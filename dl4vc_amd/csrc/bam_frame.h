@@ -124,6 +124,56 @@ BAMF_HD inline uint32_t frame_record(const uint8_t* b, uint64_t size, Framed& fr
     return W_NONE;
 }
 
+// ---- read subsampling by name hash (samtools view --subsample F --subsample-seed S) ------------------------------------------
+// X31 over the read name of a framed record: the bytes behind the fixed fields up to the first NUL, at most l_read_name - 1 of
+// them (frame_record has checked that 32 + l_read_name lies inside the record), each widened as a signed char as htslib's
+// __ac_X31_hash_string does on x86-64.  An empty name hashes to 0.
+BAMF_HD inline uint32_t name_hash(const uint8_t* b, const Framed& fr) {
+    const uint8_t* s = b + 32;
+    const uint32_t n = fr.l_name - 1;
+    if (n == 0 || s[0] == 0) return 0;
+    uint32_t h = (uint32_t)(int32_t)(int8_t)s[0];
+    for (uint32_t i = 1; i < n && s[i] != 0; ++i) h = h * 31u + (uint32_t)(int32_t)(int8_t)s[i];
+    return h;
+}
+
+// Wang's integer mix (htslib's __ac_Wang_hash)
+BAMF_HD inline uint32_t wang(uint32_t k) {
+    k += ~(k << 15);
+    k ^= k >> 10;
+    k += k << 3;
+    k ^= k >> 6;
+    k += ~(k << 11);
+    k ^= k >> 16;
+    return k;
+}
+
+// threshold = ceil(F * 2^24) for a fraction F in (0, 1], formed once on the host (sample_threshold); 0 = off, every read kept
+struct SampleRule {
+    uint32_t seed, threshold;
+};
+
+// keep iff (wang(name_hash ^ seed) & 0xffffff) / 2^24 < F; the name is not read when the rule is off
+BAMF_HD inline bool sampled(const uint8_t* b, const Framed& fr, const SampleRule& rule) {
+    if (rule.threshold == 0) return true;
+    return (wang(name_hash(b, fr) ^ rule.seed) & 0xffffffu) < rule.threshold;
+}
+
+// ceil(F * 2^24) in double (exact: F * 2^24 only moves the exponent); F is in (0, 1]
+inline uint32_t sample_threshold(double fraction) {
+    const double v = fraction * 16777216.0;
+    uint32_t t = (uint32_t)v;
+    if ((double)t < v) ++t;
+    return t;
+}
+
+// The rule of a setter's arguments: fraction 0 turns it off, a fraction outside [0, 1] or NaN is refused (the reason, else NULL).
+inline const char* sample_rule(double fraction, uint32_t seed, SampleRule& out) {
+    if (!(fraction >= 0.0 && fraction <= 1.0)) return "the subsample fraction must lie in [0, 1] (0 turns it off)";
+    out = SampleRule{seed, fraction > 0.0 ? sample_threshold(fraction) : 0u};
+    return nullptr;
+}
+
 // the reference and query lengths of a framed record's CIGAR, and whether it holds a reference-consuming operation or an N
 BAMF_HD inline void cigar_sums(const uint8_t* b, Framed& fr) {
     fr.nref = fr.nquery = 0;

@@ -47,6 +47,7 @@ struct Gathered {
     std::vector<uint8_t> bytes;
     std::vector<cand::ReadMeta> meta;   // off relative to bytes
     std::string err;
+    int64_t seen = 0;                   // records that passed the region test, in front of the sample rule
 };
 
 }  // namespace
@@ -72,6 +73,9 @@ struct cg_handle {   // (members are destroyed last to first: the stream outlive
     std::unique_ptr<fastan::Fasta> fasta;
     std::map<int32_t, dev::Buffer> contigs;     // tid -> exactly header.lengths[tid] bytes
     cg_reference_stats rst{};
+    // read subsampling (cg_set_subsample)
+    bamn::frame::SampleRule sample{0, 0};
+    cg_subsample_stats sst{};
 };
 
 namespace {
@@ -103,6 +107,8 @@ bool fetch_sub(cg_handle* h, bamn::BamFile& bam, std::vector<uint8_t>& blk, cons
         if (fr.pos >= rg.end) return true;
         F::cigar_sums(blk.data(), fr);
         if (F::endpos(fr) <= rg.start) continue;
+        ++g.seen;
+        if (!F::sampled(blk.data(), fr, h->sample)) continue;
         cand::ReadMeta m;
         m.off = g.bytes.size();
         m.len = (uint32_t)blk.size();
@@ -283,7 +289,8 @@ int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg
     if (const int rc = batch_refs(h, regions, b0, n_subs, refs)) return rc;
     // gather into the pinned buffer, subregion by subregion
     uint64_t bytes = 0, n_reads = 0;
-    for (auto& g : per) { bytes += g.bytes.size(); n_reads += g.meta.size(); }
+    for (auto& g : per) { bytes += g.bytes.size(); n_reads += g.meta.size(); h->sst.records_seen += g.seen; }
+    h->sst.records_kept += (int64_t)n_reads;
     if (h->pinned.ensure(bytes + 1) != hipSuccess) return fail(-2, "pinned allocation of %llu bytes failed", (unsigned long long)bytes);
     std::vector<cand::ReadMeta> meta;
     meta.reserve(n_reads);
@@ -352,11 +359,11 @@ int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t
     std::vector<bz::SubRange> sr(n_subs);
     for (uint32_t s = 0; s < n_subs; ++s) sr[s] = bz::SubRange{regions[b0 + s].tid, regions[b0 + s].start, regions[b0 + s].end};
     const cand::ReadMeta* meta_dev = nullptr;
-    uint64_t n_reads = 0, n_records = 0, err = bz::NO_ERROR;
+    uint64_t n_reads = 0, n_records = 0, n_seen = 0, err = bz::NO_ERROR;
     const char* msg = nullptr;
     CG_TRY(hipEventRecord(h->ev[0], h->stream));
     if (bz::frame_records(h->framer.get(), h->inflate.d_infl.p, infl_bytes, pl.segs.data(), pl.segs.size(), pl.n_slots, sr.data(), n_subs,
-                          h->stream, &meta_dev, &n_reads, &n_records, &err, &msg))
+                          h->stream, &meta_dev, &n_reads, &n_records, &err, &msg, h->sample, &n_seen))
         return fail(-2, "device framing: %s", msg);
     if (err != bz::NO_ERROR)
         return fail(-3, "%s (record at virtual offset %lld)", bamn::frame::why_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
@@ -366,6 +373,8 @@ int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t
     CG_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
     h->ist.walk_frame_ms += ms;
     h->ist.records += (int64_t)n_records;
+    h->sst.records_seen += (int64_t)n_seen;
+    h->sst.records_kept += (int64_t)n_reads;
 #undef CG_TRY
     std::vector<cand::SubDesc> subs(n_subs);
     int64_t cov = 0;
@@ -416,6 +425,7 @@ int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg
         cg_stats st{};
         h->ist = cg_inflate_stats{};
         h->rst.reads = 0;
+        h->sst = cg_subsample_stats{};
         h->out.clear();
         for (int64_t i = 0; i < n_regions; ++i) {
             const cg_region& r = regions[i];
@@ -455,6 +465,20 @@ int cg_set_inflate_device(cg_handle_t* h, int on) {
 int cg_get_inflate_stats(const cg_handle_t* h, cg_inflate_stats* out) {
     if (!h || !out) return fail(-1, "cg_get_inflate_stats: null argument");
     *out = h->ist;
+    return 0;
+}
+
+int cg_set_subsample(cg_handle_t* h, double fraction, uint32_t seed) {
+    return capi::guarded(g_err, "cg_set_subsample", [&] {
+        if (!h) return fail(-1, "cg_set_subsample: null handle");
+        if (const char* why = bamn::frame::sample_rule(fraction, seed, h->sample)) return fail(-1, "cg_set_subsample: %s", why);
+        return 0;
+    });
+}
+
+int cg_get_subsample_stats(const cg_handle_t* h, cg_subsample_stats* out) {
+    if (!h || !out) return fail(-1, "cg_get_subsample_stats: null argument");
+    *out = h->sst;
     return 0;
 }
 

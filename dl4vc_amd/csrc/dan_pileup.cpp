@@ -60,6 +60,7 @@ using bamn::Bai;
 struct Rec {
     int32_t tid = -1, pos = 0, ref_end = 0;
     uint16_t flag = 0;
+    bool sampled = true;                                         // false: the sample rule dropped it, it overlaps no window
     std::string name, seq;
     std::vector<uint32_t> cigar;                                 // (len << 4) | op
     std::vector<uint8_t> qual;
@@ -120,6 +121,7 @@ using fastan::Fasta;
 
 struct Bam : bamn::BamFile {
     std::vector<uint8_t> b;
+    bamn::frame::SampleRule sample{0, 0};                        // pe_set_subsample
     int get_tid(const std::string& name) const {
         auto it = tid_of.find(name);
         if (it != tid_of.end()) return it->second;
@@ -139,6 +141,7 @@ struct Bam : bamn::BamFile {
         auto rec = std::make_shared<Rec>();
         rec->tid = fr.tid; rec->pos = fr.pos; rec->flag = (uint16_t)fr.flag;
         rec->ref_end = (int32_t)(fr.pos + (fr.nref > 0 ? fr.nref : 1));
+        rec->sampled = bamn::frame::sampled(b.data(), fr, sample);
         rec->name.assign((const char*)&b[32], (size_t)fr.l_name - 1);
         rec->cigar.resize(fr.n_cig);
         for (uint32_t i = 0; i < fr.n_cig; ++i) rec->cigar[i] = bamn::frame::ld32(&b[fr.cigar_off + 4 * i]);
@@ -193,7 +196,7 @@ struct Window {
                 if (rec->tid != t) {
                     if (rec->tid > t || rec->tid < 0) { eof = true; break; }
                 } else if (rec->pos >= stop) { pending = rec; break; }
-                else if (rec->ref_end > start) kept.push_back(rec);
+                else if (rec->ref_end > start && rec->sampled) kept.push_back(rec);
                 rec.reset();
             }
             at = bam->r.tell();
@@ -211,6 +214,7 @@ struct pe_encoder {
     pe_options opt{};
     Bai bai;
     bool have_bai = false;
+    bamn::frame::SampleRule sample{0, 0};
 };
 
 namespace {
@@ -421,6 +425,7 @@ int encode(pe_encoder_t* e, const char* const* contigs, const int32_t* positions
         std::string err;
         if (!bam.open(e->bam_path)) { errors[ti] = bam.err; return; }
         if (!fasta.open(e->fasta_path, err)) { errors[ti] = err; return; }
+        bam.sample = e->sample;
         Window win;
         win.bam = &bam; win.bai = e->have_bai ? &e->bai : nullptr;
         for (int64_t i = lo; i < hi; ++i) {
@@ -468,6 +473,31 @@ int pe_encode(pe_encoder_t* e, const char* const* contigs, const int32_t* positi
         return pe_fail(e, "pe_encode: null argument");
     return capi::guarded(e->err, "pe_encode", [&] {
         return encode(e, contigs, positions, n, reads_out, qual_out, strand_out, ref_out, num_reads_out, status_out, threads);
+    });
+}
+
+int pe_set_subsample(pe_encoder_t* e, double fraction, uint32_t seed) {
+    if (!e) return pe_fail(nullptr, "pe_set_subsample: null handle");
+    return capi::guarded(e->err, "pe_set_subsample", [&] {
+        if (const char* why = bamn::frame::sample_rule(fraction, seed, e->sample)) return pe_fail(e, "pe_set_subsample: %s", why);
+        return 0;
+    });
+}
+
+int pe_subsample_keeps(const uint8_t* name, int32_t l_read_name, double fraction, uint32_t seed) {
+    return capi::guarded(g_pe_error, "pe_subsample_keeps", [&] {
+        namespace F = bamn::frame;
+        if (!name || l_read_name < 1 || l_read_name > 255) return pe_fail(nullptr, "pe_subsample_keeps: a name field of 1..255 bytes");
+        F::SampleRule rule{0, 0};
+        if (!(fraction > 0.0)) return pe_fail(nullptr, "pe_subsample_keeps: the fraction must lie in (0, 1]");
+        if (const char* why = F::sample_rule(fraction, seed, rule)) return pe_fail(nullptr, "pe_subsample_keeps: %s", why);
+        // a record of nothing but its fixed fields and the name field, framed by the one core
+        std::vector<uint8_t> rec(32 + (size_t)l_read_name, 0);
+        rec[8] = (uint8_t)l_read_name;
+        memcpy(rec.data() + 32, name, (size_t)l_read_name);
+        F::Framed fr;
+        if (const uint32_t w = F::frame_record(rec.data(), rec.size(), fr, /*aux=*/false)) return pe_fail(nullptr, "%s", F::why_text(w));
+        return F::sampled(rec.data(), fr, rule) ? 1 : 0;
     });
 }
 

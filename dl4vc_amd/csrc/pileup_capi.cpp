@@ -101,6 +101,9 @@ struct pg_encoder : pgh::AssembleState {   // (err, device and the staging of pg
     bz::InflateStage inflate;
     std::unique_ptr<bz::Framer, void (*)(bz::Framer*)> walker{nullptr, bz::framer_destroy};
     std::unique_ptr<pg::Framing, void (*)(pg::Framing*)> framing{nullptr, pg::framing_destroy};
+    // read subsampling (pg_set_subsample): the rule and the counts of the last call
+    pg::frame::SampleRule sample{0, 0};
+    pg_subsample_stats sst{};
     // pg_compress_records_device: the compressor's buffers, the packed chunk image, the streams, the blob and slots (device and
     // pinned staging), the pinned bytes handed to the caller
     std::unique_ptr<zd::Ctx, void (*)(zd::Ctx*)> zctx{nullptr, zd::ctx_destroy};
@@ -167,7 +170,7 @@ void fetch_ref(fastan::Fasta& fasta, Run& run) {
 // The records of one run (pileup_fetch.h), plus the run's reference tokens.
 void fetch_run(pg_encoder* h, bamn::BamFile& bam, fastan::Fasta& fasta, std::vector<uint8_t>& blk, Run& run) {
     fetch_ref(fasta, run);
-    pgh::fetch_records(h->bai, bam, blk, run.tid, run.s0, run.stop, run);
+    pgh::fetch_records(h->bai, bam, blk, run.tid, run.s0, run.stop, run, h->sample);
 }
 
 // the fetch window of the location at pos1 (1-based): bases [s0, stop), the location's own column at ci
@@ -354,11 +357,13 @@ int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& 
         }
         at += r.bytes.size();
         res += r.nres;
+        h->sst.records_seen += r.seen;
         std::vector<uint8_t>().swap(r.bytes);
     }
     h->st.host_frame_ms += ms_since(t_host);
     h->st.host_records += (int64_t)recs.size();
     h->st.records += (int64_t)recs.size();
+    h->sst.records_kept += (int64_t)recs.size();
     // device
     hipStream_t s = h->stream;
     if (h->d_buf.ensure(bytes + 4) || h->d_recs.ensure(recs.size() + 1) || h->d_locs.ensure(locs.size() + 1) || h->d_ref.ensure(ref.size() + 1) ||
@@ -552,9 +557,9 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
         for (size_t r = g0; r < g1; ++r) rd[r - g0] = pg::RunDesc{runs[r].tid, 0, runs[r].s0, runs[r].stop};
         pg::Rec* d_grecs = nullptr;
         const pg::RunOut* d_run_out = nullptr;
-        int64_t n_recs = 0, n_res = 0;
+        int64_t n_recs = 0, n_res = 0, n_seen = 0;
         if (pg::frame_runs(h->framing.get(), inf.d_infl.p, d_rec_off, d_rec_off ? pl.n_slots : 0, rd.data(), (int32_t)rd.size(), s, &d_grecs, &n_recs,
-                           &n_res, &d_run_out, &err, &msg))
+                           &n_res, &d_run_out, &err, &msg, h->sample, &n_seen))
             return fail(h, -2, "device framing: %s", msg);
         if (err != pg::FRAME_NO_ERROR)
             return fail(h, -3, "%s (record at virtual offset %lld)", pg::frame::why_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
@@ -563,6 +568,8 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
         PG_TRY(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
         h->st.frame_ms += ms;
         h->st.records += n_recs;
+        h->sst.records_seen += n_seen;
+        h->sst.records_kept += n_recs;
         if (n_res > INT32_MAX || n_recs > INT32_MAX) return fail(h, -1, "batch too large (%lld reference positions of records)", (long long)n_res);
         if (h->d_qpos.ensure((size_t)n_res + 1) || h->d_indel.ensure((size_t)n_res + 1) || h->d_isdel.ensure((size_t)n_res + 1))
             return fail(h, -2, "hipMalloc failed (group of %lld records)", (long long)n_recs);
@@ -604,6 +611,7 @@ int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positio
     for (dev::Event& e : h->ev)
         if (e.ensure() != hipSuccess) return fail(h, -2, "hipEventCreate failed");
     h->st = pg_stats{};
+    h->sst = pg_subsample_stats{};
     // the caller's stream must not run ahead of (or behind) our work on its planes
     hipStream_t cs = (hipStream_t)stream;
     if (out.device_planes) {
@@ -837,6 +845,20 @@ int pg_set_inflate_device(pg_encoder_t* h, int on, uint64_t max_inflated_bytes) 
         h->max_inflated = max_inflated_bytes ? max_inflated_bytes : DEFAULT_INFLATED;
         return 0;
     });
+}
+
+int pg_set_subsample(pg_encoder_t* h, double fraction, uint32_t seed) {
+    if (!h) return fail(nullptr, -1, "pg_set_subsample: null handle");
+    return capi::guarded(h->err, "pg_set_subsample", [&] {
+        if (const char* why = pg::frame::sample_rule(fraction, seed, h->sample)) return fail(h, -1, "pg_set_subsample: %s", why);
+        return 0;
+    });
+}
+
+int pg_get_subsample_stats(const pg_encoder_t* h, pg_subsample_stats* out) {
+    if (!h || !out) return fail(nullptr, -1, "pg_get_subsample_stats: null argument");
+    *out = h->sst;
+    return 0;
 }
 
 int pg_set_compress_codes(pg_encoder_t* h, int mode) {

@@ -26,6 +26,7 @@ struct RunRecs {
     int64_t nres = 0;
     bool sorted = true;
     std::string err;
+    int64_t seen = 0;            // records that passed the region test, in front of the sample rule
 };
 
 struct Region { int32_t tid; int64_t start, end; };
@@ -46,9 +47,10 @@ inline void append(RunRecs& run, const pg::frame::Framed& fr, uint64_t off, int3
 }
 
 // The records of one run: tid == run's, pos < stop and pos + max(nref, 1) > s0 (the window reader of dan_pileup.cpp), read
-// forward from the linear index's offset for s0.
+// forward from the linear index's offset for s0.  A record the sample rule drops (bam_frame.h) is framed and checked like every
+// other and then joins no run.
 inline void fetch_records(const bamn::Bai& bai, bamn::BamFile& bam, std::vector<uint8_t>& blk, int32_t tid, int64_t s0, int64_t stop,
-                          RunRecs& run) {
+                          RunRecs& run, pg::frame::SampleRule rule = pg::frame::SampleRule{0, 0}) {
     namespace F = pg::frame;
     const uint64_t at = bai.linear_offset(tid, s0);
     if (at == 0) return;
@@ -68,6 +70,8 @@ inline void fetch_records(const bamn::Bai& bai, bamn::BamFile& bam, std::vector<
         if (fr.pos >= stop) return;
         if (const uint32_t why = F::walk_cigar(blk.data(), fr)) { run.err = at_voff(F::why_text(why), voff); return; }
         if (!F::keeps(fr, tid, s0, stop)) continue;
+        ++run.seen;
+        if (!F::sampled(blk.data(), fr, rule)) continue;
         append(run, fr, run.bytes.size(), last_pos);
         run.bytes.insert(run.bytes.end(), blk.begin(), blk.end());
         run.bytes.resize((run.bytes.size() + 3) & ~(size_t)3);
@@ -80,7 +84,7 @@ inline void fetch_records(const bamn::Bai& bai, bamn::BamFile& bam, std::vector<
 // `others` (n_others of them): further regions of the same call.  With any, the blocks are read once for the call's plan over
 // all the regions and the run's own plan takes them from it (BlockPlan::adopt), as a group of runs does in the encoder.
 inline void twin_records(const bamn::Bai& bai, const std::string& path, int32_t tid, int64_t s0, int64_t stop, RunRecs& run,
-                         const Region* others = nullptr, int64_t n_others = 0) {
+                         const Region* others = nullptr, int64_t n_others = 0, pg::frame::SampleRule rule = pg::frame::SampleRule{0, 0}) {
     namespace F = pg::frame;
     const Region rg{tid, s0, stop};
     bz::BlockPlan pl, all;
@@ -122,7 +126,10 @@ inline void twin_records(const bamn::Bai& bai, const std::string& path, int32_t 
             if (!why) why = F::frame_record(infl + at + 4, size, fr);
             if (!why && fr.tid == tid) why = F::walk_cigar(infl + at + 4, fr);
             if (why) { run.err = at_voff(F::why_text(why), pl.voff_of(at)); return; }
-            if (F::keeps(fr, tid, s0, stop)) append(run, fr, at + 4, last_pos);
+            if (F::keeps(fr, tid, s0, stop)) {
+                ++run.seen;
+                if (F::sampled(infl + at + 4, fr, rule)) append(run, fr, at + 4, last_pos);
+            }
             at += (uint64_t)size + 4;
         }
     }

@@ -26,49 +26,67 @@ __device__ inline void report(unsigned long long* err, uint64_t off, uint32_t wh
     atomicMin(err, (unsigned long long)((off << 8) | why));
 }
 
+// With a sample rule (sample_threshold != 0, bam_frame.h) a record the rule drops belongs to no run, after it has been framed
+// and checked like every other; *seen then gathers the memberships in front of the rule, one atomic add per workgroup.
 __global__ void __launch_bounds__(TB) pileup_frame_kernel(const uint8_t* __restrict__ infl, const uint64_t* __restrict__ rec_off,
                                                           uint32_t n_slots, const RunDesc* __restrict__ runs, int32_t n_runs,
                                                           uint32_t* __restrict__ count, int32_t* __restrict__ first_run,
-                                                          unsigned long long* __restrict__ err) {
+                                                          unsigned long long* __restrict__ err, uint32_t sample_seed,
+                                                          uint32_t sample_threshold, unsigned long long* __restrict__ seen) {
+    __shared__ uint32_t s_seen;
+    const bool on = sample_threshold != 0;                  // (uniform)
+    if (on) {
+        if (threadIdx.x == 0) s_seen = 0;
+        __syncthreads();
+    }
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_slots) return;
-    uint32_t c = 0;
-    int32_t k0 = 0;
-    const uint64_t at = rec_off[i];
-    if (at != F::NO_RECORD) {
-        const uint32_t size = F::ld32(infl + at);           // (checked by the walk: 32 <= size, at + 4 + size <= total)
-        const uint8_t* b = infl + at + 4;
-        F::Framed fr;
-        uint32_t why = F::frame_record(b, size, fr);
-        if (why == F::W_NONE && fr.tid >= 0) {
-            why = F::walk_cigar(b, fr);
-            if (why != F::W_NONE) {                         // an error only for a contig some run asks for (the host meets no other)
-                int32_t lo = 0, hi = n_runs;
-                while (lo < hi) {
-                    const int32_t mid = (lo + hi) >> 1;
-                    if (runs[mid].tid < fr.tid) lo = mid + 1; else hi = mid;
-                }
-                if (lo >= n_runs || runs[lo].tid != fr.tid) why = F::W_NONE;
-            } else {
-                // the first run of the contig that stops after the record's start
-                int32_t lo = 0, hi = n_runs;
-                while (lo < hi) {
-                    const int32_t mid = (lo + hi) >> 1;
-                    const RunDesc r = runs[mid];
-                    if (r.tid < fr.tid || (r.tid == fr.tid && r.stop <= (int64_t)fr.pos)) lo = mid + 1; else hi = mid;
-                }
-                k0 = lo;
-                for (int32_t k = lo; k < n_runs; ++k) {
-                    const RunDesc r = runs[k];
-                    if (!F::keeps(fr, r.tid, r.s0, r.stop)) break;
-                    ++c;
+    if (i < n_slots) {
+        uint32_t c = 0;
+        int32_t k0 = 0;
+        const uint64_t at = rec_off[i];
+        if (at != F::NO_RECORD) {
+            const uint32_t size = F::ld32(infl + at);       // (checked by the walk: 32 <= size, at + 4 + size <= total)
+            const uint8_t* b = infl + at + 4;
+            F::Framed fr;
+            uint32_t why = F::frame_record(b, size, fr);
+            if (why == F::W_NONE && fr.tid >= 0) {
+                why = F::walk_cigar(b, fr);
+                if (why != F::W_NONE) {                     // an error only for a contig some run asks for (the host meets no other)
+                    int32_t lo = 0, hi = n_runs;
+                    while (lo < hi) {
+                        const int32_t mid = (lo + hi) >> 1;
+                        if (runs[mid].tid < fr.tid) lo = mid + 1; else hi = mid;
+                    }
+                    if (lo >= n_runs || runs[lo].tid != fr.tid) why = F::W_NONE;
+                } else {
+                    // the first run of the contig that stops after the record's start
+                    int32_t lo = 0, hi = n_runs;
+                    while (lo < hi) {
+                        const int32_t mid = (lo + hi) >> 1;
+                        const RunDesc r = runs[mid];
+                        if (r.tid < fr.tid || (r.tid == fr.tid && r.stop <= (int64_t)fr.pos)) lo = mid + 1; else hi = mid;
+                    }
+                    k0 = lo;
+                    for (int32_t k = lo; k < n_runs; ++k) {
+                        const RunDesc r = runs[k];
+                        if (!F::keeps(fr, r.tid, r.s0, r.stop)) break;
+                        ++c;
+                    }
+                    if (on && c) {
+                        atomicAdd(&s_seen, c);
+                        if (!F::sampled(b, fr, F::SampleRule{sample_seed, sample_threshold})) c = 0;
+                    }
                 }
             }
+            if (why != F::W_NONE) report(err, at, why);
         }
-        if (why != F::W_NONE) report(err, at, why);
+        count[i] = c;
+        first_run[i] = k0;
     }
-    count[i] = c;
-    first_run[i] = k0;
+    if (on) {
+        __syncthreads();
+        if (threadIdx.x == 0 && s_seen) atomicAdd(seen, (unsigned long long)s_seen);
+    }
 }
 
 __global__ void __launch_bounds__(TB) pileup_pair_kernel(uint32_t n_slots, const uint32_t* __restrict__ count,
@@ -161,7 +179,9 @@ Framing* framing_create() { return new Framing(); }
 void framing_destroy(Framing* f) { delete f; }
 
 int frame_runs(Framing* f, const uint8_t* infl, const uint64_t* rec_off, uint64_t n_slots, const RunDesc* runs, int32_t n_runs,
-               hipStream_t stream, Rec** recs, int64_t* n_recs, int64_t* n_res, const RunOut** run_out, uint64_t* err, const char** msg) {
+               hipStream_t stream, Rec** recs, int64_t* n_recs, int64_t* n_res, const RunOut** run_out, uint64_t* err, const char** msg,
+               F::SampleRule rule, int64_t* n_seen) {
+    if (n_seen) *n_seen = 0;
     *recs = nullptr; *n_recs = 0; *n_res = 0; *run_out = nullptr; *err = FRAME_NO_ERROR;
     if (n_runs <= 0) return 0;
     if (n_slots >= (1ull << 31)) { *msg = "too many record slots in one group"; return -2; }
@@ -173,17 +193,18 @@ int frame_runs(Framing* f, const uint8_t* infl, const uint64_t* rec_off, uint64_
     HIP_CHECK_MSG(f->count.ensure(((size_t)ns + 1) * 4));
     HIP_CHECK_MSG(f->first.ensure(((size_t)ns + 1) * 4));
     HIP_CHECK_MSG(f->first_run.ensure(((size_t)ns + 1) * 4));
-    HIP_CHECK_MSG(f->err.ensure(8));
+    HIP_CHECK_MSG(f->err.ensure(16));                       // [0] first refused record, [1] memberships in front of the sample rule
     unsigned long long* d_err = f->err.as<unsigned long long>();
     HIP_CHECK_MSG(hipMemcpyAsync(f->runs.p, runs, (size_t)n_runs * sizeof(RunDesc), hipMemcpyHostToDevice, stream));
     HIP_CHECK_MSG(hipMemsetAsync(d_err, 0xff, 8, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(d_err + 1, 0, 8, stream));
     HIP_CHECK_MSG(hipMemsetAsync(f->rec0.p, 0, (size_t)n_runs * 4, stream));
     HIP_CHECK_MSG(hipMemsetAsync(f->rec1.p, 0, (size_t)n_runs * 4, stream));
     uint32_t total = 0;
     if (ns > 0) {
         const unsigned grid = (ns + TB - 1) / TB;
         hipLaunchKernelGGL(pileup_frame_kernel, dim3(grid), dim3(TB), 0, stream, infl, rec_off, ns, f->runs.as<const RunDesc>(), n_runs,
-                           f->count.as<uint32_t>(), f->first_run.as<int32_t>(), d_err);
+                           f->count.as<uint32_t>(), f->first_run.as<int32_t>(), d_err, rule.seed, rule.threshold, d_err + 1);
         HIP_CHECK_MSG(hipGetLastError());
         HIP_CHECK_MSG(hipMemsetAsync(f->count.as<uint32_t>() + ns, 0, 4, stream));
         size_t tb = 0;
@@ -193,11 +214,12 @@ int frame_runs(Framing* f, const uint8_t* infl, const uint64_t* rec_off, uint64_
         tb = f->temp.cap;
         HIP_CHECK_MSG(rocprim::exclusive_scan(f->temp.p, tb, f->count.as<uint32_t>(), f->first.as<uint32_t>(), 0u, (size_t)ns + 1,
                                               rocprim::plus<uint32_t>(), stream));
-        unsigned long long h_err = 0;
+        unsigned long long h_err[2] = {0, 0};
         HIP_CHECK_MSG(hipMemcpyAsync(&total, f->first.as<uint32_t>() + ns, 4, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK_MSG(hipMemcpyAsync(&h_err, d_err, 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK_MSG(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, stream));
         HIP_CHECK_MSG(hipStreamSynchronize(stream));
-        if (h_err != FRAME_NO_ERROR) { *err = h_err; return 0; }
+        if (h_err[0] != FRAME_NO_ERROR) { *err = h_err[0]; return 0; }
+        if (n_seen) *n_seen = rule.threshold ? (int64_t)h_err[1] : (int64_t)total;
         if (total >= (1u << 31)) { *msg = "too many records in one group"; return -2; }
     }
     HIP_CHECK_MSG(f->recs.ensure(((size_t)total + 1) * sizeof(Rec)));

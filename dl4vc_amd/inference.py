@@ -201,11 +201,11 @@ class _Scored:
 
 
 def census_bam(bam: str, fasta: str, locations, encoder_options=None, device_id: int = 0, threads: int = 0,
-               inflate_device: Optional[str] = None, batch: int = 16384, stage=None, log=None) -> np.ndarray:
+               inflate_device: Optional[str] = None, batch: int = 16384, stage=None, log=None, subsample=None) -> np.ndarray:
     """The record census: one uint8 per location, 1 where ``score_bam`` would get a record from it.  The GPU encoder's status
     rule runs without writing a plane (``pg_census``); what it declines goes through the fallback of ``score_bam``
     (``location_round.LocationRounds.census``).  ``stage`` (a dict) receives ``pg_stats`` summed over the calls.  Needs torch's HIP
-    device, as ``score_bam`` does."""
+    device, as ``score_bam`` does.  ``subsample=(fraction, seed)``: as in ``score_bam``."""
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("census_bam: torch sees no HIP device")
@@ -213,7 +213,7 @@ def census_bam(bam: str, fasta: str, locations, encoder_options=None, device_id:
     flags = np.zeros(len(locations), np.uint8)
     # (no stored planes: a census writes none)
     rounds = LocationRounds(bam, fasta, encoder_options or default_encoder_options(), 0, device_id, inflate_device=inflate_device,
-                            threads=threads)
+                            threads=threads, subsample=subsample)
     try:
         with torch.cuda.device(device_id):
             for l0 in range(0, len(locations), batch):
@@ -480,7 +480,7 @@ def _score_device_batches(net, src, emit, log, of_what: str) -> int:
 def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None], sites_per_launch: int = 4096,
               reads_seed: int = 0, use_var_type_threshold: bool = False, log=None, stats=None, site_limit: int = 0,
               encoder_options=None, device_id: int = 0, threads: int = 0, encoder_counts=None,
-              inflate_device: Optional[str] = None, first_record: int = 0, census=None, stage=None) -> int:
+              inflate_device: Optional[str] = None, first_record: int = 0, census=None, stage=None, subsample=None) -> int:
     """Score ``locations`` (``pileup_encoder.Location``s, e.g. ``locations_from_vcf(candidates.vcf, label=2)``) straight from
     the BAM: the same lines ``tools/convert_bam_single_reads.py`` + ``score_records`` write, without a candidate file.  The
     pileup planes are encoded (``pg_encode_device``) and assembled (``pg_assemble_device``) in device memory and scored there
@@ -498,13 +498,18 @@ def score_bam(net, bam: str, fasta: str, locations, write: Callable[[str], None]
     ``first_record``: the record index of the first record these locations give (a shard of a longer list, planned by
     ``shard.plan_bam_shard`` from the record census): site i then draws with ``reads_seed + first_record + i``.  ``census``: one
     flag per location (``census_bam``); a location whose status differs from its flag raises ``RuntimeError``.  ``stage`` (a
-    dict) receives the encoder's stage times."""
+    dict) receives the encoder's stage times.
+
+    ``subsample=(fraction, seed)``: every encoder drops the reads ``bamio.SampleRule`` drops, in front of the pileup (it is
+    ``encoder_options.subsample`` for this call): the lines are those of the BAM ``tools/subsample_bam.py`` writes."""
     import torch
+    from .location_round import with_subsample
     if not torch.cuda.is_available():
         raise RuntimeError("score_bam: torch sees no HIP device.  It shares buffers and streams with torch, so torch has to be "
                            "imported before libdl4vc_dan.so / libdl4vc_pileup.so are loaded (one HIP runtime per process)")
     emit = _Pipeline(net, write, use_var_type_threshold, stats)._emit
-    src = _BamBatches(net.config, bam, fasta, list(locations), encoder_options or default_encoder_options(), sites_per_launch,
+    src = _BamBatches(net.config, bam, fasta, list(locations), with_subsample(encoder_options or default_encoder_options(), subsample),
+                      sites_per_launch,
                       reads_seed, site_limit, device_id, threads or default_threads(), encoder_counts, inflate_device, first_record,
                       census)
     done = _score_device_batches(net, src, emit, log, "%d locations" % len(src.locations))

@@ -20,7 +20,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (DL4VC_LOADER_LIB: another build of the same library -- the CPU AddressSanitizer pass of tools/asan_pileup.sh)
 LIB_PATH = os.environ.get("DL4VC_LOADER_LIB") or os.path.join(_HERE, "csrc", "libdl4vc_loader.so")
 SYMBOLS = ("dl_open", "dl_num_records", "dl_num_sites", "dl_window", "dl_next", "dl_close", "dl_last_error",
-           "dl_select_rows", "dl_select_rows_downsample", "dl_allele_masks", "pe_open", "pe_encode", "pe_close", "pe_last_error")
+           "dl_select_rows", "dl_select_rows_downsample", "dl_allele_masks", "pe_open", "pe_encode", "pe_close", "pe_last_error",
+           "pe_set_subsample", "pe_subsample_keeps")
 _lib = None
 
 
@@ -45,10 +46,21 @@ def load_library() -> C.CDLL:
         lib.dl_allele_masks.argtypes = [C.c_char_p, vp, vp, vp]
         lib.pe_open.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, vp, C.POINTER(vp)]
         lib.pe_encode.argtypes = [vp, C.POINTER(C.c_char_p), vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int32]
+        lib.pe_set_subsample.argtypes = [vp, C.c_double, C.c_uint32]
+        lib.pe_subsample_keeps.argtypes = [C.c_char_p, C.c_int32, C.c_double, C.c_uint32]
         lib.pe_close.argtypes = [vp]; lib.pe_close.restype = None
         lib.pe_last_error.argtypes = [vp]; lib.pe_last_error.restype = C.c_char_p
         _lib = lib
     return _lib
+
+
+def subsample_keeps(name_field: bytes, fraction: float, seed: int = 0) -> bool:
+    """``pe_subsample_keeps``: the native rule (csrc/bam_frame.h) on a record's read name field -- the bytes as they lie in the
+    record, NUL included, 1..255 of them."""
+    rc = load_library().pe_subsample_keeps(bytes(name_field), len(name_field), float(fraction), int(seed))
+    if rc < 0:
+        raise ValueError(load_library().pe_last_error(None).decode())
+    return bool(rc)
 
 
 def available() -> bool:
@@ -137,7 +149,10 @@ class NativePileupEncoder:
     """ctypes face of the native pileup encoder (``pe_*``, row N4): image planes of a run of locations, in order."""
 
     def __init__(self, bam_path: str, fasta_path: str, window_size: int, max_reads: int, max_insert_length: int,
-                 max_insert_length_variant: int, min_base_quality: int = 0, bai_path: Optional[str] = None):
+                 max_insert_length_variant: int, min_base_quality: int = 0, bai_path: Optional[str] = None, subsample=None):
+        """``subsample=(fraction, seed)``: reads are subsampled by name hash (``pe_set_subsample``, ``bamio.SampleRule``)."""
+        from .bamio import SampleRule
+        rule = SampleRule.of(subsample)
         self.lib = load_library()
         self._h = C.c_void_p()
         self.window, self.max_reads = 2 * window_size + 1, max_reads
@@ -146,12 +161,16 @@ class NativePileupEncoder:
         if rc != 0:
             self._h = None
             raise RuntimeError("pe_open failed: %s" % self.lib.pe_last_error(None).decode())
+        if rule is not None and self.lib.pe_set_subsample(self._h, rule.fraction, rule.seed) != 0:
+            msg = self.lib.pe_last_error(self._h).decode()
+            self.close()
+            raise RuntimeError("pe_set_subsample failed: %s" % msg)
 
     @classmethod
     def from_options(cls, bam, fasta, opt):
         """The encoder of a ``pileup_encoder.EncoderOptions``."""
         return cls(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length, opt.max_insert_length_variant,
-                   opt.min_base_quality)
+                   opt.min_base_quality, subsample=getattr(opt, "subsample", None))
 
     def encode(self, contigs, positions, threads: int = 1):
         """-> (reads, qual, strand [n][max_reads][W] u8, ref [n][W] u8, num_reads [n] i32, status [n] i8)."""

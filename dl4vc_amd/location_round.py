@@ -23,6 +23,16 @@ def default_encoder_options() -> EncoderOptions:
     return EncoderOptions(window_size=100, max_reads=200, max_insert_length=10, max_insert_length_variant=50, min_base_quality=0)
 
 
+def with_subsample(opt: EncoderOptions, subsample) -> EncoderOptions:
+    """``opt`` with ``subsample`` ((fraction, seed), a ``bamio.SampleRule`` or None: ``opt`` as it is) as its read subsampling."""
+    if subsample is None:
+        return opt
+    from dataclasses import replace
+    from .bamio import SampleRule
+    rule = SampleRule.of(subsample)
+    return replace(opt, subsample=(rule.fraction, rule.seed))
+
+
 def default_threads() -> int:
     return max(2, min(16, os.cpu_count() or 4))
 
@@ -47,7 +57,7 @@ class HostEncoders:
         """The Python builder's record of ``loc``, or None."""
         if self._py is None:
             from .bamio import BamFile, FastaFile, WindowReader
-            b = BamFile(self.bam)
+            b = BamFile(self.bam, subsample=getattr(self.opt, "subsample", None))
             self._py = (b, FastaFile(self.fasta), WindowReader(b))
         b, f, reader = self._py
         res = encode_location(b, f, loc, self.opt, reader)
@@ -95,10 +105,12 @@ class LocationRounds:
     -- every location starts as declined, the stored planes are numpy arrays.  ``stream``: the ``torch.cuda.Stream`` the encoder's
     planes and the slot copies are ordered on (None: the current one).  ``counts`` (``ENCODER_COUNTS``; a dict given is added to)
     and ``stage`` (``pg_stats`` summed over the calls) grow with every call.  ``encoder`` / ``host``: stand-ins for the
-    ``GpuPileupEncoder`` and the ``HostEncoders`` (tests); a stand-in encoder writes numpy planes."""
+    ``GpuPileupEncoder`` and the ``HostEncoders`` (tests); a stand-in encoder writes numpy planes.  ``subsample=(fraction, seed)``:
+    ``opt.subsample`` for these rounds -- every encoder of the ladder drops the reads the rule drops (``bamio.SampleRule``)."""
 
     def __init__(self, bam, fasta, opt, round_locations, device, inflate_device=None, compress_codes="fixed", threads=0, stream=None,
-                 counts=None, encoder=None, host=None):
+                 counts=None, encoder=None, host=None, subsample=None):
+        opt = with_subsample(opt, subsample)
         self.device, self.stream, self.stage = int(device), stream, {}
         self.counts = counts if counts is not None else {}
         for k in ENCODER_COUNTS:

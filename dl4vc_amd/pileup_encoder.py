@@ -60,6 +60,9 @@ class EncoderOptions:
     max_insert_length: int = 10
     max_insert_length_variant: int = 50
     min_base_quality: int = 0
+    # (fraction, seed): read subsampling by name hash (``bamio.SampleRule``), applied by every encoder where a read outside
+    # the window is dropped; None = every read
+    subsample: Optional[Tuple[float, int]] = None
 
 
 def decode_base(base_str: str):
@@ -421,8 +424,11 @@ def encode_location(bam, fasta, loc: Location, opt: EncoderOptions, reader=None)
 def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Location], opt: EncoderOptions,
                      native: Optional[bool] = None, threads: int = 1, device: Optional[str] = None,
                      device_id: int = 0, inflate_device: Optional[str] = None, compress_device: Optional[str] = None,
-                     pending: int = 0, records_per_chunk: int = 8, compress_codes: str = "fixed"):
+                     pending: int = 0, records_per_chunk: int = 8, compress_codes: str = "fixed", subsample=None):
     """Records for ``locations`` in input order and the number of locations that produced none.
+
+    ``subsample=(fraction, seed)``: ``opt.subsample`` for this call -- every encoder below drops the reads the rule drops
+    (``bamio.SampleRule``), so the records are those of the BAM ``tools/subsample_bam.py`` writes (tests/test_subsample_*.py).
 
     ``native`` (default: when libdl4vc_loader.so is built): the image planes come from the C++ encoder (``pe_encode``:
     BGZF / BAM / CIGAR / image builder in ``threads`` worker threads); a location it declines (status 2: the cases
@@ -447,6 +453,11 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
     zero-length alignment such as ``0M 5I``, a SEQ shorter than the CIGAR's query length such as SEQ ``*``): the native and
     GPU encoders decline such a location, so all three paths end here (tests/test_pileup_edges.py)."""
     from . import loader
+    if subsample is not None:
+        from dataclasses import replace
+        from .bamio import SampleRule
+        rule = SampleRule.of(subsample)
+        opt = replace(opt, subsample=(rule.fraction, rule.seed))
     if device not in (None, "gpu"):
         raise ValueError("device must be None (host encoders) or 'gpu', not %r" % (device,))
     if inflate_device not in (None, "gpu"):

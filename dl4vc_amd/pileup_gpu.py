@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_pileup.so")
 SYMBOLS = ("pg_open", "pg_encode", "pg_encode_device", "pg_assemble_device", "pg_close", "pg_last_error",
            "pg_set_inflate_device", "pg_get_stats", "pg_debug_run_records", "pg_compress_records_device", "pg_set_compress_codes",
-           "pg_census")
+           "pg_census", "pg_set_subsample", "pg_get_subsample_stats")
 # the zlib compressor of the same library (csrc/zdeflate.h)
 ZD_SYMBOLS = ("zd_bound", "zd_deflate_host", "zd_deflate", "zd_deflate_host_flags", "zd_code_lengths_host")
 ZD_MIN_SEGMENT, ZD_MAX_SEGMENT, ZD_DEFAULT_SEGMENT = 1024, 32768, 16384
@@ -37,6 +37,11 @@ class Stats(C.Structure):
                [(n, C.c_double) for n in ("pack_ms", "deflate_ms", "gather_ms", "compress_copy_back_ms")] + \
                [(n, C.c_int64) for n in ("chunks", "raw_bytes", "chunk_bytes_out", "stored_chunks", "fixed_segments", "dynamic_segments",
                                          "stored_segments")]
+
+
+class SubsampleStats(C.Structure):
+    """``pg_subsample_stats``: records in front of the sample rule and behind it, of the last call."""
+    _fields_ = [("records_seen", C.c_int64), ("records_kept", C.c_int64)]
 
 
 class RecView(C.Structure):
@@ -92,6 +97,8 @@ def load_library() -> C.CDLL:
                                            [C.c_int32, C.c_int32] + [vp] * 6 + [vp])
         lib.pg_set_inflate_device.argtypes = [vp, C.c_int, C.c_uint64]
         lib.pg_get_stats.argtypes = [vp, C.POINTER(Stats)]
+        lib.pg_set_subsample.argtypes = [vp, C.c_double, C.c_uint32]
+        lib.pg_get_subsample_stats.argtypes = [vp, C.POINTER(SubsampleStats)]
         lib.pg_compress_records_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.POINTER(vp), vp, vp, vp, vp, vp]
         lib.zd_bound.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
         lib.zd_deflate_host.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
@@ -202,15 +209,20 @@ class GpuPileupEncoder:
 
     def __init__(self, bam_path: str, fasta_path: str, window_size: int, max_reads: int, max_insert_length: int,
                  max_insert_length_variant: int, min_base_quality: int = 0, bai_path: Optional[str] = None, device: int = 0,
-                 inflate_device: Optional[str] = None, max_inflated_bytes: int = 0, compress_codes: str = "fixed"):
-        """``inflate_device="gpu"``: the BGZF blocks are inflated and the records framed on the device (``pg_set_inflate_device``;
+                 inflate_device: Optional[str] = None, max_inflated_bytes: int = 0, compress_codes: str = "fixed", subsample=None):
+        """``subsample=(fraction, seed)``: reads are subsampled by name hash where the framing runs, on the host threads or in the
+        device's frame kernel (``pg_set_subsample``, ``bamio.SampleRule``); ``subsample_stats()`` counts them.
+        ``inflate_device="gpu"``: the BGZF blocks are inflated and the records framed on the device (``pg_set_inflate_device``;
         needs the ``.bai``), same outputs.  ``max_inflated_bytes``: inflated bytes per group of runs, 0 = the default.
         ``compress_codes``: ``"fixed"`` or ``"dynamic"``, the codes ``compress_records`` writes (``pg_set_compress_codes``)."""
+        from .bamio import SampleRule
         mode = _codes_mode(compress_codes)
+        rule = SampleRule.of(subsample)
         if inflate_device not in (None, "gpu"):
             raise ValueError("inflate_device: None or 'gpu', not %r" % (inflate_device,))
         self.lib = load_library()
         self._h = C.c_void_p()
+        self.subsample = rule
         self.window, self.max_reads, self.device = 2 * window_size + 1, max_reads, device
         opt = PileupOptions(window_size, max_reads, max_insert_length, max_insert_length_variant, min_base_quality)
         rc = self.lib.pg_open(bam_path.encode(), bai_path.encode() if bai_path else None, fasta_path.encode(), C.byref(opt),
@@ -220,18 +232,31 @@ class GpuPileupEncoder:
             raise RuntimeError("pg_open failed: %s" % self.lib.pg_last_error(None).decode())
         if mode:
             self._check(self.lib.pg_set_compress_codes(self._h, mode), "pg_set_compress_codes")
-        if inflate_device == "gpu":
-            try:
+        try:
+            if rule is not None:
+                self.set_subsample(rule.fraction, rule.seed)
+            if inflate_device == "gpu":
                 self.set_inflate_device(True, max_inflated_bytes)
-            except RuntimeError:
-                self.close()
-                raise
+        except RuntimeError:
+            self.close()
+            raise
 
     @classmethod
     def from_options(cls, bam, fasta, opt, device: int = 0, inflate_device: Optional[str] = None, compress_codes: str = "fixed"):
         """The encoder of a ``pileup_encoder.EncoderOptions``."""
         return cls(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length, opt.max_insert_length_variant,
-                   opt.min_base_quality, device=device, inflate_device=inflate_device, compress_codes=compress_codes)
+                   opt.min_base_quality, device=device, inflate_device=inflate_device, compress_codes=compress_codes,
+                   subsample=getattr(opt, "subsample", None))
+
+    def set_subsample(self, fraction: float, seed: int = 0) -> None:
+        """``pg_set_subsample``; fraction 0 turns it off again."""
+        self._check(self.lib.pg_set_subsample(self._h, float(fraction), int(seed)), "pg_set_subsample")
+
+    def subsample_stats(self) -> dict:
+        """``records_seen`` / ``records_kept`` of the last ``encode`` / ``encode_device`` / ``census`` call."""
+        st = SubsampleStats()
+        self._check(self.lib.pg_get_subsample_stats(self._h, C.byref(st)), "pg_get_subsample_stats")
+        return {"records_seen": st.records_seen, "records_kept": st.records_kept}
 
     def set_inflate_device(self, on: bool, max_inflated_bytes: int = 0) -> None:
         self._check(self.lib.pg_set_inflate_device(self._h, int(bool(on)), int(max_inflated_bytes)), "pg_set_inflate_device")
@@ -240,7 +265,10 @@ class GpuPileupEncoder:
         """The stages of the last ``encode`` / ``encode_device`` call (``pg_stats``)."""
         st = Stats()
         self._check(self.lib.pg_get_stats(self._h, C.byref(st)), "pg_get_stats")
-        return {n: getattr(st, n) for n, _ in Stats._fields_}
+        out = {n: getattr(st, n) for n, _ in Stats._fields_}
+        if self.subsample is not None:                       # (only with the option: the stages stay pg_stats' otherwise)
+            out.update(("subsample_" + k, v) for k, v in self.subsample_stats().items())
+        return out
 
     def _args(self, contigs: Sequence[str], positions):
         n = len(positions)

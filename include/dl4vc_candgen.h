@@ -98,6 +98,20 @@ int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg
  * meaning (host wall time in front of the device work). */
 int cg_set_inflate_device(cg_handle_t* h, int on);
 int cg_get_inflate_stats(const cg_handle_t* h, cg_inflate_stats* out);
+/* Read subsampling by name hash, the rule of `samtools view --subsample fraction --subsample-seed seed` (csrc/bam_frame.h:
+ * keep iff (wang(X31(read name) ^ seed) & 0xffffff) < ceil(fraction * 2^24)).  A record is framed and checked as without the
+ * option and then dropped where a record outside the subregion is dropped, on the host or in the device's frame kernel: every
+ * count behind that point (depth, alleles, cg_stats.reads) sees the kept reads alone, and a damaged record gives the same error
+ * at the same offset.  Mates share a name and so an answer; a read in two subregions gets one answer.  fraction 0 turns it off
+ * again, 1 keeps every read; a fraction outside [0, 1] or NaN is refused.  Unpinned against samtools itself. */
+int cg_set_subsample(cg_handle_t* h, double fraction, uint32_t seed);
+/* Of the last cg_run: records that passed the region test (a read in two subregions counts twice, as in cg_stats.reads) and
+ * those of them the rule kept (= cg_stats.reads).  Equal with the option off. */
+typedef struct {
+    int64_t records_seen;
+    int64_t records_kept;
+} cg_subsample_stats;
+int cg_get_subsample_stats(const cg_handle_t* h, cg_subsample_stats* out);
 /* fasta_path: a read WITHOUT an MD tag is walked against the bases of its contig in this FASTA (indexed by fasta_path.fai when
  * that file exists, else scanned once), in the same kernels; a read WITH an MD tag is walked by its MD as before, whatever the
  * FASTA says.  NULL or "": off again (such reads count in cg_stats.reads_no_md and give no alleles), and the resident contigs

@@ -94,6 +94,12 @@ int pe_open(const char* bam_path, const char* bai_path /* NULL: <bam>.bai, <stem
             const pe_options* opt, pe_encoder_t** out);
 int pe_encode(pe_encoder_t* e, const char* const* contigs, const int32_t* positions, int64_t n, uint8_t* reads_out, uint8_t* qual_out,
               uint8_t* strand_out, uint8_t* ref_out, int32_t* num_reads_out, int8_t* status_out, int32_t threads);
+/* Read subsampling by name hash, the rule of `samtools view --subsample fraction --subsample-seed seed` (csrc/bam_frame.h): a
+ * record the rule drops overlaps no window.  fraction 0: off; outside [0, 1] or NaN: refused (-1, pe_last_error(e)). */
+int pe_set_subsample(pe_encoder_t* e, double fraction, uint32_t seed);
+/* The rule alone, for tests: 1 if a record whose read name field is name[0, l_read_name) (the bytes as they lie in the record,
+ * NUL included; 1 <= l_read_name <= 255) is kept at `fraction` in (0, 1] and `seed`, 0 if dropped, -1 for a refused argument. */
+int pe_subsample_keeps(const uint8_t* name, int32_t l_read_name, double fraction, uint32_t seed);
 void pe_close(pe_encoder_t* e);
 const char* pe_last_error(const pe_encoder_t* e);      /* e may be NULL: error of the last failed pe_open */
 

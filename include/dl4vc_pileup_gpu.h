@@ -112,6 +112,19 @@ typedef struct {
 } pg_stats;
 int pg_get_stats(const pg_encoder_t* h, pg_stats* out);
 
+/* Read subsampling by name hash (the rule of cg_set_subsample in dl4vc_candgen.h, one definition in csrc/bam_frame.h).  A record
+ * is framed and checked as without the option and then dropped where a record outside its run is dropped: by the host framing
+ * threads, or in the device's frame kernel with pg_set_inflate_device.  Everything behind sees the kept reads alone: coverage,
+ * track selection, duplicate keys, the track limit, the stored rows.  Holds for pg_encode, pg_encode_device and pg_census.
+ * fraction 0: off; outside [0, 1] or NaN: refused. */
+int pg_set_subsample(pg_encoder_t* h, double fraction, uint32_t seed);
+/* Of the last encode / census call: records that passed the run's region test (once per run they belong to) and those kept. */
+typedef struct {
+    int64_t records_seen;
+    int64_t records_kept;
+} pg_subsample_stats;
+int pg_get_subsample_stats(const pg_encoder_t* h, pg_subsample_stats* out);
+
 /* ---- candidate HDF5 chunks compressed on the device ---------------------------------------------------------------------------
  * The zlib compressor (csrc/zdeflate.h): an RFC 1950 stream of DEFLATE blocks (fixed codes, or with ZD_DYNAMIC the smaller of a
  * fixed and a dynamic block per segment), the input cut into segments of `segment` bytes (ZD_MIN_SEGMENT..ZD_MAX_SEGMENT) that are

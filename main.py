@@ -236,14 +236,15 @@ def bam_sources(args):
         return locs
 
     try:
-        train = BamSource(args.train_bam, args.train_fasta, labelled("train"), inflate_device=args.inflate_device)
+        opt = bam_encoder_options(args)
+        train = BamSource(args.train_bam, args.train_fasta, labelled("train"), inflate_device=args.inflate_device, encoder_options=opt)
         if not args.test_bam:
             return train, args.test_file
         if any(get("test_%s_vcf" % k) for k in ("tp", "fn", "fp")):
             locs = labelled("test")
         else:
             locs = locations_from_vcf(args.sample_vcf, label=2)   # (as in inference)
-        return train, BamSource(args.test_bam, args.test_fasta, locs, inflate_device=args.inflate_device)
+        return train, BamSource(args.test_bam, args.test_fasta, locs, inflate_device=args.inflate_device, encoder_options=opt)
     except (OSError, ValueError, IndexError) as e:
         raise SystemExit("--train_bam: the location VCFs could not be read: %s" % e)
 
@@ -420,7 +421,7 @@ def census_text(st) -> str:
                st.get("census_wait_s", 0.0)))
 
 
-def score_bam_census(args, net, target, out_final, shard_i, shard_n, holdout, site_limit, stats, counts, census_stats) -> int:
+def score_bam_census(args, net, target, out_final, shard_i, shard_n, holdout, site_limit, stats, counts, census_stats, score_stage=None) -> int:
     """--test_bam --record-census gpu: census, plan (``shard.plan_bam_shard``), score this shard's runs into ``target``.
     Under a --gpus parent the shards census a contiguous slice of ALL locations each and exchange the flags through side files
     next to their parts; a --shard without siblings, and a run without shards, censuses every location itself."""
@@ -437,8 +438,10 @@ def score_bam_census(args, net, target, out_final, shard_i, shard_n, holdout, si
         print("--shard %d/%d without sibling processes: this process censuses all %d locations itself" % (shard_i, shard_n, len(locations)))
     stage = {}
     t0 = time.time()
+    opt = bam_encoder_options(args)
+    sub = {"encoder_options": opt} if opt is not None else {}     # (without --subsample the calls are what they were)
     mine = census_bam(args.test_bam, args.test_fasta, locations[lo:hi], inflate_device=args.inflate_device, stage=stage,
-                      log=lambda m: print(m, end="\r"))
+                      log=lambda m: print(m, end="\r"), **sub)
     census_stats.update(census_s=time.time() - t0, census_ms=float(stage.get("census_ms", 0.0)), census_locations=hi - lo,
                         census_records=int(mine.sum()), census_wait_s=0.0)
     if siblings:
@@ -463,7 +466,7 @@ def score_bam_census(args, net, target, out_final, shard_i, shard_n, holdout, si
             n += score_bam(net, args.test_bam, args.test_fasta, locations[a:b], f.write, sites_per_launch=args.sites_per_launch,
                            reads_seed=args.reads_seed, use_var_type_threshold=args.use_var_type_threshold,
                            log=lambda m: print(m, end="\r"), stats=stats, encoder_counts=counts, inflate_device=args.inflate_device,
-                           first_record=first, census=flags[a:b])
+                           first_record=first, census=flags[a:b], **(dict(sub, stage=score_stage) if sub else {}))
     for k in ("locations", "gpu", "native", "python", "no_record"):
         counts.setdefault(k, 0)
     return n
@@ -568,6 +571,40 @@ def check_downsample_arguments(args) -> None:
                          "(evaluation and inference never down-sample)")
 
 
+def check_subsample_arguments(args):
+    """--subsample / --subsample-seed: (fraction, seed) or None; every refusal with its reason, before anything touches a device."""
+    f, s = getattr(args, "subsample", None), getattr(args, "subsample_seed", None)
+    if f is None:
+        if s is not None:
+            raise SystemExit("--subsample-seed %d without --subsample: the seed chooses among subsets of a fraction" % s)
+        return None
+    if not args.test_bam and not getattr(args, "train_bam", None):
+        raise SystemExit("--subsample thins the reads of --test_bam / --train_bam, and this run reads no BAM: a --test_file or "
+                         "--train_file holds pileups already encoded (give the flag to the converter that writes it)")
+    if not (0.0 < f <= 1.0):
+        raise SystemExit("--subsample %r: the fraction must lie in (0, 1]" % (f,))
+    s = 0 if s is None else s
+    if not (0 <= s < 1 << 32):
+        raise SystemExit("--subsample-seed %d: the seed must lie in [0, 2^32)" % s)
+    return (f, s)
+
+
+def bam_encoder_options(args):
+    """What the BAM consumers encode with: None (their default, what call_variants.sh passes to the converter) without
+    --subsample, else that default with the rule."""
+    rule = check_subsample_arguments(args)
+    if rule is None:
+        return None
+    from dl4vc_amd.location_round import default_encoder_options, with_subsample
+    return with_subsample(default_encoder_options(), rule)
+
+
+def subsample_text(args, stage) -> str:
+    from dl4vc_amd.subsample import report_line
+    return report_line(int(stage.get("subsample_records_seen", 0)), int(stage.get("subsample_records_kept", 0)),
+                       check_subsample_arguments(args)) + " (the GPU encoder's records)"
+
+
 def check_loader_device_arguments(args) -> None:
     """--loader-device: what it refuses (the file's own properties are checked when it is opened)."""
     if args.loader_device != "gpu":
@@ -594,6 +631,7 @@ def main(argv=None) -> int:
         raise SystemExit("--record-census gpu is an option of --test_bam (it counts the locations of the candidate VCF that give a "
                          "record); the records of a --test_file are already counted")
     check_train_bam_arguments(args)
+    check_subsample_arguments(args)
     check_downsample_arguments(args)
     if args.loader_device is not None:
         check_loader_device_arguments(args)
@@ -710,8 +748,9 @@ def main(argv=None) -> int:
     counts = {}
     loader_stage = {}
     census_stats = {}
+    score_stage = {}                                          # the encoder's stages summed over the scoring calls
     if args.test_bam and args.record_census:
-        n = score_bam_census(args, net, target, out_final, shard_i, shard_n, holdout, site_limit, stats, counts, census_stats)
+        n = score_bam_census(args, net, target, out_final, shard_i, shard_n, holdout, site_limit, stats, counts, census_stats, score_stage)
     elif args.test_bam:
         # the encoder options are what call_variants.sh passes to the converter (score_bam's default)
         from dl4vc_amd.inference import score_bam
@@ -720,7 +759,8 @@ def main(argv=None) -> int:
         with open(target, "w") as f:
             n = score_bam(net, args.test_bam, args.test_fasta, locations, f.write, sites_per_launch=args.sites_per_launch,
                           reads_seed=args.reads_seed, use_var_type_threshold=args.use_var_type_threshold, site_limit=site_limit,
-                          log=lambda m: print(m, end="\r"), stats=stats, encoder_counts=counts, inflate_device=args.inflate_device)
+                          log=lambda m: print(m, end="\r"), stats=stats, encoder_counts=counts, inflate_device=args.inflate_device,
+                          encoder_options=bam_encoder_options(args), stage=score_stage)
     else:
         extra = {"loader_device": "gpu", "loader_stats": loader_stage} if args.loader_device else {}
         try:
@@ -733,6 +773,8 @@ def main(argv=None) -> int:
             raise SystemExit("--loader-device gpu: %s" % e)   # (a refused file or a damaged chunk: the reason, not a traceback)
     t_loop = time.time() - t_loop - census_stats.get("census_s", 0.0) - census_stats.get("census_wait_s", 0.0)
     net.close()
+    if getattr(args, "subsample", None) is not None:
+        print("\n" + subsample_text(args, score_stage))
     if census_stats:
         print("\nrecord census: %s" % census_text(census_stats).lstrip("; "))
     if args.test_bam:

@@ -6,6 +6,7 @@ host's inflate-and-frame time against the device time (per-stage device times co
 
     python tools/candgen_rate.py --bam /tmp/cg_rate.bam [--reads 2000000 --length 10000000] [--out profiles/x.json]
         [--inflate-device gpu] [--chunk_size 1000] [--no-md] [--fasta REF.fa] [--reference REF.fa]
+        [--subsample F [--subsample-seed S]]
 
 ``--inflate-device gpu`` measures the device inflate path (the line then carries its read / inflate / walk-and-frame times);
 ``--chunk_size`` other than 1000 changes the subregions, and with them the candidates at their boundaries: a timing line only.
@@ -14,6 +15,9 @@ The reference arm: ``--no-md`` writes the same reads without aux tags (when ``--
 genome they were drawn from beside it (60 bases a line, with its ``.fai``), and ``--reference REF.fa`` walks the reads that have
 no MD tag against it; the line then carries the ``reference_*`` figures.  Every repeat opens its own handle, so the contig's
 one-time load (read, upload and convert) is inside every repeat's wall time.
+
+``--subsample F [--subsample-seed S]`` is passed through (reads subsampled by name hash in front of every count); the line then
+carries the records seen and kept, and ``reads_per_s`` counts the records SEEN, the work the framing did.
 """
 import argparse
 import json
@@ -84,17 +88,21 @@ def main():
     ap.add_argument("--no-md", dest="no_md", action="store_true", help="write the BAM without aux tags (when it has to be made)")
     ap.add_argument("--fasta", default=None, help="write the BAM's genome here, with its .fai (when the BAM has to be made)")
     ap.add_argument("--reference", default=None, help="walk the reads that have no MD tag against this FASTA")
+    from dl4vc_amd import subsample
+    subsample.add_flags(ap)
     a = ap.parse_args()
+    rule = subsample.parse(ap, a)
     if not os.path.isfile(a.bam + ".bai"):
         t = time.time()
         make_bam(a.bam, a.reads, a.length, md_tags=not a.no_md, fasta=a.fasta)
         print("wrote %s in %.1f s" % (a.bam, time.time() - t), file=sys.stderr)
     from dl4vc_amd.candidates import generate
+    extra = {"subsample": rule} if rule is not None else {}
     runs = []
     for k in range(a.repeats):
         t = time.perf_counter()
         st = generate(a.bam, a.bam + ".vcf", threads=a.threads, snp_min_freq=0.075, indel_min_freq=0.02, keep_multialleles=True,
-                      chunk_size=a.chunk_size, inflate_device=a.inflate_device, reference=a.reference)
+                      chunk_size=a.chunk_size, inflate_device=a.inflate_device, reference=a.reference, **extra)
         st["wall_s"] = time.perf_counter() - t
         runs.append(st)
     best = min(runs, key=lambda r: r["wall_s"])
@@ -110,6 +118,10 @@ def main():
               "reference_read_ms", "reference_upload_convert_ms"):
         if k in best:
             res[k] = round(best[k], 1) if isinstance(best[k], float) else best[k]
+    if rule is not None:
+        res.update(subsample=list(rule), subsample_records_seen=best["subsample_records_seen"],
+                   subsample_records_kept=best["subsample_records_kept"],
+                   reads_per_s=round(best["subsample_records_seen"] / best["wall_s"]))
     if best.get("inflate_ms"):
         res["inflate_MB_per_s"] = round(best["inflate_inflated_bytes"] / 1e6 / (best["inflate_ms"] / 1e3))
     line = json.dumps(res)

@@ -66,6 +66,10 @@ def run_children(args, argv) -> int:
         raise SystemExit("shard process failed: %s" % rcs)
     stats = merge_parts(args.output, args.gpus)
     warn_no_md(stats, args.reference)
+    if args.subsample is not None:
+        from dl4vc_amd import subsample
+        print(subsample.report_line(stats["subsample_records_seen"], stats["subsample_records_kept"],
+                                    (args.subsample, args.subsample_seed or 0)))
     logging.info("Generated final VCF file at %s from %d parts.", args.output, args.gpus)
     print("summary " + json.dumps(stats, sort_keys=True))
     return 0
@@ -84,7 +88,10 @@ def main(argv=None) -> int:
                    help="Walk the reads that have no MD tag against this FASTA's bases (REF.fa.fai when that file exists) instead "
                    "of giving them no alleles; reads with an MD tag are walked by it as before. Each contig touched stays on the GPU "
                    "as 1 byte per base")
+    from dl4vc_amd import subsample
+    subsample.add_flags(p)
     args = p.parse_args(argv)
+    rule = subsample.parse(p, args)                           # (before any device work, --gpus children included)
     print(args)
     logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.DEBUG if args.debug else logging.INFO)
     if args.reference is not None and not (os.path.isfile(args.reference) and os.access(args.reference, os.R_OK)):
@@ -103,9 +110,11 @@ def main(argv=None) -> int:
                      chunk_size=args.chunk_size, threads=args.threads, snp_min_freq=args.snp_min_freq,
                      indel_min_freq=args.indel_min_freq, keep_multialleles=args.keep_multialleles,
                      max_len_indel_allele=args.max_len_indel_allele, inflate_device=args.inflate_device, shard=shard,
-                     reference=args.reference)
+                     reference=args.reference, subsample=rule)
     if shard is None:                      # (the parent of shards says it once, of the summed counts)
         warn_no_md(stats, args.reference)
+        if rule is not None:
+            print(subsample.report_line(stats["subsample_records_seen"], stats["subsample_records_kept"], rule))
     if shard is not None:
         from dl4vc_amd.shard import part_path
         logging.info("Wrote the records of shard %d/%d to %s.", shard[0], shard[1], part_path(args.output, shard[0]))

@@ -111,7 +111,10 @@ def main(argv=None):
     ap.add_argument("--compress-codes", type=str, default="fixed", choices=["fixed", "dynamic"],
                     help="with --compress-device gpu: dynamic gives a chunk's segments dynamic Huffman codes where that is smaller "
                          "(a smaller file, the same records; the compressor parses every segment twice); default fixed")
+    from dl4vc_amd import subsample
+    subsample.add_flags(ap)
     args = ap.parse_args(argv)
+    rule = subsample.parse(ap, args)
     if args.inflate_device and args.pileup_device != "gpu":
         raise SystemExit("--inflate-device gpu is an option of the GPU pileup encoder: give --pileup-device gpu as well")
     if args.compress_device and args.pileup_device != "gpu":
@@ -128,7 +131,11 @@ def main(argv=None):
     assert args.save_q_scores, "Too many options, need to run with Q scores"
     assert args.save_strand, "Too many options, need to run with strand save"
     opt = EncoderOptions(window_size=args.window_size, max_reads=args.max_reads, max_insert_length=args.max_insert_length,
-                         max_insert_length_variant=args.max_insert_length_variant, min_base_quality=args.min_base_quality)
+                         max_insert_length_variant=args.max_insert_length_variant, min_base_quality=args.min_base_quality,
+                         subsample=rule)
+    if rule is not None:
+        # (the host encoders keep no count of the records they drop: tools/subsample_bam.py and the candidate generator print them)
+        print("subsample: every encoder keeps the reads of fraction %g, seed %d" % rule)
     locations = []
     if args.tp_vcf:
         locations.extend(locations_from_vcf(args.tp_vcf, label=0, full_vcf=args.tp_full_vcf))

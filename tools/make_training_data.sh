@@ -13,14 +13,18 @@
 # outputs (--train_bam: the pileups are encoded on the GPU into the resident record store, the same records in the same order).
 # -f: the candidate generator walks the reads that have no MD tag against REFERENCE (--reference; whole contigs on the GPU, 1 byte
 # per base) instead of giving them no alleles; reads with an MD tag are walked by it as before.  Not passed by default.
+# -s F [-S SEED]: candidate generation and the converter (with -n: the printed --train_bam flags) keep the fraction F in (0, 1] of
+# the BAM's reads, chosen by a hash of the read name (--subsample / --subsample-seed): training data at F of the coverage.
 set -e
-usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c [-y]] [-n] [-f]"; exit 1; }
+usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c [-y]] [-n] [-f] [-s FRACTION [-S SEED]]"; exit 1; }
 PROCS=16
 COMPRESS=""
 CODES=""
 NOFILE=""
 FROMREF=""
-while getopts "i:r:t:o:b:p:nfcyh" opt; do
+SUBSAMPLE=""
+SEED=""
+while getopts "i:r:t:o:b:p:s:S:nfcyh" opt; do
   case $opt in
     i) BAM=$OPTARG ;;
     r) REFERENCE=$OPTARG ;;
@@ -32,6 +36,8 @@ while getopts "i:r:t:o:b:p:nfcyh" opt; do
     y) CODES=dynamic ;;
     n) NOFILE=1 ;;
     f) FROMREF=1 ;;         # candidate generation: reads without MD are walked against REFERENCE
+    s) SUBSAMPLE=$OPTARG ;; # every BAM reader keeps this fraction of the reads (--subsample)
+    S) SEED=$OPTARG ;;      # with -s: the seed (--subsample-seed)
     *) usage ;;
   esac
 done
@@ -39,13 +45,15 @@ done
 [ -z "$BAM" ] || [ -z "$REFERENCE" ] || [ -z "$TRUTH" ] || [ -z "$OUTDIR" ] && usage
 [ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
 [ -n "$NOFILE" ] && [ -n "$COMPRESS" ] && { echo "-n writes no train.hdf, so there is nothing for -c to compress: give one of them"; exit 1; }
+[ -n "$SEED" ] && [ -z "$SUBSAMPLE" ] && { echo "-S is the seed of -s: give -s FRACTION as well"; exit 1; }
+SUBFLAGS=(${SUBSAMPLE:+--subsample "$SUBSAMPLE"} ${SEED:+--subsample-seed "$SEED"})
 SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 mkdir -p "$OUTDIR"
 if [ ! -f "$OUTDIR/candidates.vcf" ]; then
   printf "Generate candidate VCF...\n"
   python "$SCRIPTDIR/tools/candidate_generator.py" --input "$BAM" --output "$OUTDIR/candidates.vcf" \
       --snp_min_freq 0.075 --indel_min_freq 0.02 ${BED:+--bedfile "$BED"} --keep_multialleles \
-      ${FROMREF:+--reference "$REFERENCE"} > "$OUTDIR/candidate_generator.log" 2>&1
+      ${FROMREF:+--reference "$REFERENCE"} "${SUBFLAGS[@]}" > "$OUTDIR/candidate_generator.log" 2>&1
 fi
 if [ ! -f "$OUTDIR/isec/0003.vcf" ]; then
   printf "Intersect candidates with the truth set...\n"
@@ -55,7 +63,7 @@ if [ -n "$NOFILE" ]; then
   echo "No train.hdf written.  Train straight from the BAM with:"
   echo "  python $SCRIPTDIR/main.py --train_bam $BAM --train_fasta $REFERENCE --train_tp_vcf $OUTDIR/isec/0003.vcf" \
        "--train_tp_full_vcf $OUTDIR/isec/0002.vcf --train_fp_vcf $OUTDIR/isec/0001.vcf --train-loader-device gpu --train-cache-device gpu" \
-       "[--train-cache-format compact]" \
+       "[--train-cache-format compact]"${SUBSAMPLE:+ "${SUBFLAGS[*]}"} \
        "( --test_file V.hdf | --test_bam Y.bam --test_fasta REF [--test_tp_vcf ... --test_tp_full_vcf ... --test_fp_vcf ...] )" \
        "<flags of train_variant_caller.sh>"
   exit 0
@@ -67,6 +75,6 @@ if [ ! -f "$OUTDIR/train.hdf" ]; then
       --output "$OUTDIR/train.hdf" --max-reads 200 --num-processes "$PROCS" --locations-process-step 100000 \
       --max-insert-length 10 --max-insert-length-variant 50 --save-q-scores --save-strand \
       ${COMPRESS:+--pileup-device gpu --compress-device "$COMPRESS"} \
-      ${CODES:+--compress-codes "$CODES"} > "$OUTDIR/training_data.log" 2>&1
+      ${CODES:+--compress-codes "$CODES"} "${SUBFLAGS[@]}" > "$OUTDIR/training_data.log" 2>&1
 fi
 echo "Training data in $OUTDIR/train.hdf"

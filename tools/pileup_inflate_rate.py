@@ -10,12 +10,14 @@ rounds), each under its own time limit; a child that fails ends the tool, nothin
 the pass.  One JSON record; no number in it is a pass mark.
 
     python tools/pileup_inflate_rate.py --dir /tmp/pir [--rounds 3] [--wg-reads 2000000 --wg-length 10000000] [--out profiles/x.json]
-        [--kernel-trace] [--score-bam]
+        [--kernel-trace] [--score-bam] [--subsample F [--subsample-seed S]]
 
 ``--kernel-trace``: afterwards, for both shapes and both settings, one more child (one pass) under ``rocprofv3 --kernel-trace
 --stats``; the record gains the total time per kernel, warm-up included.  ``--score-bam``: afterwards, one round each of
 ``tools/score_bam_rate.py`` on the dense BAM at fp32 and bf16x3, without and with ``--inflate-device gpu``; the record gains the
 scoring-loop rates.  Every one of these is again one process at a time under its own time limit, and a failure ends the tool.
+``--subsample F [--subsample-seed S]`` is passed through to every child's encoder (reads subsampled by name hash where the
+framing runs); the summed stats then carry ``subsample_records_seen`` / ``subsample_records_kept``.
 """
 import argparse
 import glob
@@ -42,7 +44,8 @@ def child(a):
     contigs = [a.contig] * len(pos)
     dev = torch.device("cuda", 0)
     out = [torch.empty((CALL, 200, 201), dtype=torch.uint8, device=dev) for _ in range(3)]
-    with pileup_gpu.GpuPileupEncoder(a.bam, a.fasta, 100, 200, 10, 50, inflate_device=a.inflate_device) as g:
+    extra = {"subsample": (a.subsample, a.subsample_seed or 0)} if a.subsample is not None else {}
+    with pileup_gpu.GpuPileupEncoder(a.bam, a.fasta, 100, 200, 10, 50, inflate_device=a.inflate_device, **extra) as g:
         g.encode_device(contigs[:1000], pos[:1000], out=out)
         torch.cuda.synchronize()
         best = None
@@ -119,7 +122,11 @@ def main():
     for name, default in (("--first", 300), ("--step", 10), ("--count", 0), ("--repeats", 3)):
         ap.add_argument(name, type=int, default=default)
     ap.add_argument("--inflate-device", default=None, choices=["gpu"])
+    from dl4vc_amd import subsample
+    subsample.add_flags(ap)
     a = ap.parse_args()
+    rule = subsample.parse(ap, a)
+    sub_flags = ["--subsample", repr(rule[0]), "--subsample-seed", str(rule[1])] if rule is not None else []
     if a.child:
         return child(a)
     if not a.dir:
@@ -131,14 +138,14 @@ def main():
     shapes = [("dense", dense_bam, dense_fa, "chr20", 300, 10, n_dense),
               ("whole_genome", wg_bam, wg_fa, "chr1", 500, 500, (a.wg_length - 1000) // 500)]
     res = {"tool": "pileup_inflate_rate", "call_locations": CALL, "window_size": 100, "max_reads": 200, "dense_length": a.dense_length,
-           "wg_reads": a.wg_reads, "wg_length": a.wg_length, "shapes": {}}
+           "wg_reads": a.wg_reads, "wg_length": a.wg_length, "subsample": list(rule) if rule is not None else None, "shapes": {}}
     for name, bam, fa, contig, first, step, count in shapes:
         rounds = []
         for k in range(a.rounds):
             r = {}
             for tag, extra in (("off", []), ("on", ["--inflate-device", "gpu"])):      # one child at a time holds the GPU
                 cmd = [sys.executable, os.path.abspath(__file__), "--child", "--bam", bam, "--fasta", fa, "--contig", contig, "--first", str(first),
-                       "--step", str(step), "--count", str(count)] + extra
+                       "--step", str(step), "--count", str(count)] + extra + sub_flags
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
                 line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
                 if p.returncode != 0 or not line:
