@@ -118,6 +118,15 @@ _EXTRA = [
      "read name as `samtools view --subsample F` chooses them (mates stay together), in front of the pileup: the scored VCF, losses "
      "and checkpoints are those of the BAM tools/subsample_bam.py writes.  Give candidate generation the same F and seed"),
     ("--subsample-seed", "int", argparse.SUPPRESS, "seed of --subsample in [0, 2^32) (default 0): another seed keeps another subset"),
+    ("--min-mapq", "int", argparse.SUPPRESS,
+     "with --test_bam / --train_bam: drop the reads of every BAM this run opens whose mapping quality is below Q in [0, 255], in front "
+     "of the pileup (samtools view -q).  Give candidate generation the same filter"),
+    ("--exclude-flags", "str", argparse.SUPPRESS, "with --test_bam / --train_bam: drop the reads with any of these flag bits (decimal "
+                                                  "or 0x..., samtools view -F)"),
+    ("--require-flags", "str", argparse.SUPPRESS, "with --test_bam / --train_bam: drop the reads that lack any of these flag bits "
+                                                  "(decimal or 0x..., samtools view -f)"),
+    ("--read-stats", "flag", False, "with --test_bam / --train_bam: print the read census of the GPU encoder's records (totals, flag "
+                                    "bits by name, MAPQ histogram), with or without a filter"),
     ("--record-census", "str", None, "gpu: with --test_bam, the locations are censused first (which of them give a record, by the GPU "
                                      "encoder's status rule without its planes), so that --gpus N, --shard g/N, "
                                      "--test_holdout_chromosomes and --max-test-batches select and seed the records as --test_file "

@@ -29,8 +29,12 @@
 # generation and the pileup step (the converter, or main.py --test_bam with -d) see the same reads, so the calls are those of the
 # BAM tools/subsample_bam.py writes -- the run at F of the coverage.  A candidates.vcf or candidates.hdf already in OUTDIR is used
 # as it is: give a fresh OUTDIR per fraction.
+# -q Q, -F MASK, -R MASK (need -i): every stage that reads the BAM drops the reads with MAPQ < Q, with any flag bit of -F or
+# without a flag bit of -R (--min-mapq / --exclude-flags / --require-flags; the masks decimal or 0x..., as samtools view -q -F
+# -f): candidate generation and the pileup step are filtered alike, e.g. -q 20 -F 0x704 counts the candidates over the reads the
+# pileup shows.  As with -s, give a fresh OUTDIR per filter.
 set -e
-usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-f] [-c [-y]] [-l] [-s FRACTION [-S SEED]]"; exit 1; }
+usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-f] [-c [-y]] [-l] [-s FRACTION [-S SEED]] [-q MIN_MAPQ] [-F EXCLUDE_FLAGS] [-R REQUIRE_FLAGS]"; exit 1; }
 GPUS=1
 PROCS=16
 DIRECT=0
@@ -41,7 +45,10 @@ LOADER=""
 FROMREF=""
 SUBSAMPLE=""
 SEED=""
-while getopts "m:o:g:i:r:b:p:s:S:fldzcyh" opt; do
+MINMAPQ=""
+EXCLUDE=""
+REQUIRE=""
+while getopts "m:o:g:i:r:b:p:s:S:q:F:R:fldzcyh" opt; do
   case $opt in
     m) MODEL=$OPTARG ;;
     o) OUTDIR=$OPTARG ;;
@@ -57,6 +64,9 @@ while getopts "m:o:g:i:r:b:p:s:S:fldzcyh" opt; do
     f) FROMREF=1 ;;         # candidate generation: reads without MD are walked against REFERENCE
     s) SUBSAMPLE=$OPTARG ;; # every BAM reader keeps this fraction of the reads (--subsample)
     S) SEED=$OPTARG ;;      # with -s: the seed (--subsample-seed)
+    q) MINMAPQ=$OPTARG ;;   # every BAM reader drops the reads below this mapping quality (--min-mapq)
+    F) EXCLUDE=$OPTARG ;;   # ... and the reads with any of these flag bits (--exclude-flags)
+    R) REQUIRE=$OPTARG ;;   # ... and the reads without any of these flag bits (--require-flags)
     l) LOADER=gpu ;;        # candidates.hdf is inflated and its sites assembled on the GPU (main.py --loader-device gpu)
     *) usage ;;
   esac
@@ -67,7 +77,9 @@ done
 [ -n "$FROMREF" ] && [ -z "$REFERENCE" ] && { echo "-f walks the reads without MD against the reference: give -r REFERENCE as well"; exit 1; }
 [ -n "$SEED" ] && [ -z "$SUBSAMPLE" ] && { echo "-S is the seed of -s: give -s FRACTION as well"; exit 1; }
 [ -n "$SUBSAMPLE" ] && [ -z "$BAM" ] && { echo "-s thins the reads of the BAM: give -i BAM as well (a candidates.hdf holds pileups already encoded)"; exit 1; }
-SUBFLAGS=(${SUBSAMPLE:+--subsample "$SUBSAMPLE"} ${SEED:+--subsample-seed "$SEED"})
+[ -n "$MINMAPQ$EXCLUDE$REQUIRE" ] && [ -z "$BAM" ] && { echo "-q / -F / -R filter the reads of the BAM: give -i BAM as well (a candidates.hdf holds pileups already encoded)"; exit 1; }
+SUBFLAGS=(${SUBSAMPLE:+--subsample "$SUBSAMPLE"} ${SEED:+--subsample-seed "$SEED"} ${MINMAPQ:+--min-mapq "$MINMAPQ"} \
+          ${EXCLUDE:+--exclude-flags "$EXCLUDE"} ${REQUIRE:+--require-flags "$REQUIRE"})
 MULTI=""
 [ "$DIRECT" = 1 ] && [ "$GPUS" -gt 1 ] && MULTI=1
 SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"

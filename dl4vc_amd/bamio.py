@@ -104,6 +104,49 @@ class SampleRule:
         return "SampleRule(%r, %d)" % (self.fraction, self.seed)
 
 
+# ------------------------------------------------------------------------------------------------------
+# Read filter by flags and mapping quality: the Python restatement of csrc/bam_frame.h (ReadFilter, passes), the rule of
+# ``samtools view -F exclude -f require -q min_mapq``.  UNPINNED against samtools itself.
+# ------------------------------------------------------------------------------------------------------
+class ReadFilter:
+    """Keep a read iff ``(flag & exclude) == 0 and (flag & require) == require and mapq >= min_mapq``.  The masks lie in
+    [0, 0xFFFF], ``min_mapq`` in [0, 255]; a bit in both masks is refused (nothing could pass).  All zero keeps every read."""
+
+    def __init__(self, exclude: int = 0, require: int = 0, min_mapq: int = 0):
+        for what, v, top in (("excluded flags", exclude, 0xffff), ("required flags", require, 0xffff),
+                             ("minimum mapping quality", min_mapq, 255)):
+            if isinstance(v, bool) or int(v) != v or not (0 <= int(v) <= top):
+                raise ValueError("the %s must be an integer in [0, %s], not %r" % (what, "0xFFFF" if top > 255 else "255", v))
+        if int(exclude) & int(require):
+            raise ValueError("flag bits 0x%x are both excluded and required: no read could pass" % (int(exclude) & int(require)))
+        self.exclude, self.require, self.min_mapq = int(exclude), int(require), int(min_mapq)
+
+    @classmethod
+    def of(cls, read_filter) -> Optional["ReadFilter"]:
+        """``None``, a filter or ``(exclude, require, min_mapq)`` -> a filter, or None for one that keeps every read."""
+        if read_filter is None:
+            return None
+        f = read_filter if isinstance(read_filter, cls) else cls(*read_filter)
+        return f if f.on else None
+
+    @property
+    def on(self) -> bool:
+        return bool(self.exclude or self.require or self.min_mapq)
+
+    def as_tuple(self) -> Tuple[int, int, int]:
+        return (self.exclude, self.require, self.min_mapq)
+
+    def passes(self, flag: int, mapq: int) -> bool:
+        return (flag & self.exclude) == 0 and (flag & self.require) == self.require and mapq >= self.min_mapq
+
+    def passes_record(self, body: bytes) -> bool:
+        """``passes`` for a record (the bytes behind its block_size field): MAPQ at byte 9, FLAG at bytes 14..15."""
+        return self.passes(body[14] | body[15] << 8, body[9])
+
+    def __repr__(self):
+        return "ReadFilter(exclude=0x%x, require=0x%x, min_mapq=%d)" % self.as_tuple()
+
+
 class BgzfReader:
     """Sequential BGZF reader with ``seek`` / ``tell`` on virtual offsets."""
 
@@ -183,7 +226,8 @@ class BamRecord:
     next_pos: int = -1
     tlen: int = 0
     aux: bytes = b""
-    sampled: bool = True          # False: the file's sample rule dropped it (BamFile(subsample=)); it overlaps no region
+    sampled: bool = True          # False: the file's read filter or sample rule dropped it (BamFile(read_filter=, subsample=)):
+                                  # it overlaps no region
 
     @property
     def is_reverse(self) -> bool:
@@ -223,11 +267,13 @@ def parse_record(buf: bytes) -> BamRecord:
 class BamFile:
     """Header + sequential / indexed access to the alignments of one BAM file."""
 
-    def __init__(self, path: str, index: Optional[str] = None, subsample=None):
+    def __init__(self, path: str, index: Optional[str] = None, subsample=None, read_filter=None):
         """``subsample``: ``(fraction, seed)`` or a ``SampleRule``; ``fetch`` and ``WindowReader`` then drop the reads the rule
-        drops, where a read outside the region is dropped.  Iteration and ``raw_records`` give every record."""
+        drops, where a read outside the region is dropped.  ``read_filter``: ``(exclude, require, min_mapq)`` or a ``ReadFilter``,
+        applied at the same place in front of the rule.  Iteration and ``raw_records`` give every record."""
         self.path = path
         self.sample = SampleRule.of(subsample)
+        self.read_filter = ReadFilter.of(read_filter)
         self.r = BgzfReader(path)
         if self.r.read(4) != BAM_MAGIC:
             raise ValueError("%s is not a BAM file" % path)
@@ -274,7 +320,9 @@ class BamFile:
         if len(body) < size:
             raise ValueError("truncated BAM record in %s" % self.path)
         rec = parse_record(body)
-        if self.sample is not None:
+        if self.read_filter is not None and not self.read_filter.passes(rec.flag, rec.mapq):
+            rec.sampled = False                              # (the name hash of a filtered record is never computed)
+        elif self.sample is not None:
             rec.sampled = self.sample.keeps_record(body)
         return at, rec
 

@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_cand.so")
 MAX_ALLELE_LEN = 63          # CG_MAX_ALLELE_LEN
 SYMBOLS = ("cg_open", "cg_run", "cg_last_error", "cg_close", "cg_n_refs", "cg_ref_name", "cg_ref_length",
            "cg_set_inflate_device", "cg_get_inflate_stats", "cg_debug_ranges", "cg_set_subsample", "cg_get_subsample_stats",
+           "cg_set_read_filter", "cg_set_read_stats", "cg_get_read_stats",
            "cg_set_reference", "cg_get_reference_stats", "cg_reference_codes", "cg_reference_codes_host",
            "bz_inflate", "bz_inflate_host", "bz_status_text", "bz_last_error")
 INFLATE_DEVICES = ("gpu",)
@@ -85,6 +86,10 @@ def load_library() -> C.CDLL:
                                         C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         lib.cg_set_subsample.argtypes = [C.c_void_p, C.c_double, C.c_uint32]
         lib.cg_get_subsample_stats.argtypes = [C.c_void_p, C.POINTER(SubsampleStats)]
+        from .read_filter import ReadStats
+        lib.cg_set_read_filter.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        lib.cg_set_read_stats.argtypes = [C.c_void_p, C.c_int]
+        lib.cg_get_read_stats.argtypes = [C.c_void_p, C.POINTER(ReadStats)]
         lib.cg_set_reference.argtypes = [C.c_void_p, C.c_char_p]
         lib.cg_get_reference_stats.argtypes = [C.c_void_p, C.POINTER(ReferenceStats)]
         lib.cg_reference_codes.argtypes = [C.c_char_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64),
@@ -160,13 +165,18 @@ class CandidateCounter:
     no alleles; reads with MD are walked by their MD as before.  The stats then carry ``reference_*`` entries.
     ``subsample=(fraction, seed)``: reads are subsampled by name hash (``bamio.SampleRule``, ``cg_set_subsample``) where a read
     outside the subregion is dropped, on the host or in the device's frame kernel; the stats then carry ``subsample_records_seen``
-    and ``subsample_records_kept``."""
+    and ``subsample_records_kept``.  ``read_filter=(exclude, require, min_mapq)``: reads are dropped by flags and mapping quality
+    at the same place, in front of that rule (``bamio.ReadFilter``, ``cg_set_read_filter``); ``read_stats=True`` collects the read
+    census without a filter too.  With either, the stats carry the ``read_*`` entries (``read_filter.ReadStats.flat``)."""
 
     def __init__(self, bam_path: str, bai_path: Optional[str] = None, threads: Optional[int] = None,
                  max_len_indel_allele: int = 60, snp_min_freq: float = 0.01, indel_min_freq: float = 0.01, device: int = 0,
-                 inflate_device: Optional[str] = None, reference: Optional[str] = None, subsample=None):
-        from .bamio import SampleRule
+                 inflate_device: Optional[str] = None, reference: Optional[str] = None, subsample=None,
+                 read_filter=None, read_stats: bool = False):
+        from .bamio import ReadFilter, SampleRule
         self.subsample = SampleRule.of(subsample)
+        self.read_filter = ReadFilter.of(read_filter)
+        self.collects = bool(read_stats) or self.read_filter is not None
         if inflate_device is not None and inflate_device not in INFLATE_DEVICES:
             raise ValueError("inflate_device must be None or one of %s" % (INFLATE_DEVICES,))
         self.lib = load_library()
@@ -192,6 +202,11 @@ class CandidateCounter:
             msg = self.lib.cg_last_error().decode()
             self.close()
             raise RuntimeError("cg_set_subsample: %s" % msg)
+        if (self.read_filter is not None and self.lib.cg_set_read_filter(h, *self.read_filter.as_tuple()) != 0) or \
+                (read_stats and self.lib.cg_set_read_stats(h, 1) != 0):
+            msg = self.lib.cg_last_error().decode()
+            self.close()
+            raise RuntimeError("cg_set_read_filter: %s" % msg)
         n = self.lib.cg_n_refs(h)
         self.references: List[str] = [self.lib.cg_ref_name(h, i).decode() for i in range(n)]
         self.lengths: List[int] = [int(self.lib.cg_ref_length(h, i)) for i in range(n)]
@@ -218,6 +233,11 @@ class CandidateCounter:
             sst = SubsampleStats()
             self.lib.cg_get_subsample_stats(self.h, C.byref(sst))
             stats.update(subsample_records_seen=sst.records_seen, subsample_records_kept=sst.records_kept)
+        if self.collects:
+            from .read_filter import ReadStats
+            rs = ReadStats()
+            self.lib.cg_get_read_stats(self.h, C.byref(rs))
+            stats.update(rs.flat())
         return res, stats
 
     def debug_ranges(self, tid: int, start: int, end: int):

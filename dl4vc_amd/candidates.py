@@ -196,8 +196,10 @@ def generate(bam_path: str, output: str, contigs: Optional[str] = None, bedfile:
              keep_contig_chr: bool = False, chunk_size: int = 1000, threads: Optional[int] = None, snp_min_freq: float = 0.01,
              indel_min_freq: float = 0.01, keep_multialleles: bool = False, max_len_indel_allele: int = 60,
              device: int = 0, inflate_device: Optional[str] = None, shard: Optional[Tuple[int, int]] = None,
-             reference: Optional[str] = None, subsample=None) -> dict:
-    """Writes ``output`` and returns the run's summary (counts of reads by kind, candidates, times).  ``subsample=(fraction,
+             reference: Optional[str] = None, subsample=None, read_filter=None, read_stats: bool = False) -> dict:
+    """Writes ``output`` and returns the run's summary (counts of reads by kind, candidates, times).  ``read_filter=(exclude,
+    require, min_mapq)``: reads are dropped by flags and mapping quality in front of every count (``bamio.ReadFilter``); with it or
+    with ``read_stats`` the summary carries the read census (``read_*`` entries, ``read_filter.census_of``).  ``subsample=(fraction,
     seed)``: the reads are subsampled by name hash in front of every count (``bamio.SampleRule``; ``subsample_records_seen`` /
     ``subsample_records_kept`` in the summary).  ``inflate_device="gpu"``
     inflates and frames the BAM's records on the device (needs the ``.bai``) and adds the ``inflate_*`` figures to the summary.
@@ -211,7 +213,7 @@ def generate(bam_path: str, output: str, contigs: Optional[str] = None, bedfile:
                                                                                                   MAX_ALLELE_LEN))
     with CandidateCounter(bam_path, threads=threads, max_len_indel_allele=max_len_indel_allele, snp_min_freq=snp_min_freq,
                           indel_min_freq=indel_min_freq, device=device, inflate_device=inflate_device, reference=reference,
-                          subsample=subsample) as cc:
+                          subsample=subsample, read_filter=read_filter, read_stats=read_stats) as cc:
         regions = contig_regions(cc.references, cc.lengths, contigs, bedfile, keep_contig_chr)
         logging.info("Examining %d regions in the bamfile", len(regions))
         subregions = split_subregions(regions, chunk_size * 1000)

@@ -174,6 +174,96 @@ inline const char* sample_rule(double fraction, uint32_t seed, SampleRule& out) 
     return nullptr;
 }
 
+// ---- read filter by flags and mapping quality (samtools view -F exclude -f require -q min_mapq) -------------------------------
+// keep iff (flag & exclude) == 0 && (flag & require) == require && mapq >= min_mapq; all zero = off, every read kept
+struct ReadFilter {
+    uint16_t exclude, require;
+    uint8_t min_mapq;
+};
+
+BAMF_HD inline bool filter_on(const ReadFilter& f) { return (f.exclude | f.require | f.min_mapq) != 0; }
+
+// the MAPQ of a framed record: byte 9 of its fixed fields (frame_record has checked that they lie inside the record)
+BAMF_HD inline uint32_t mapq_of(const uint8_t* b) { return b[9]; }
+
+enum Verdict : uint32_t { V_KEPT = 0, V_FLAGS, V_MAPQ };    // the flags are tested first: a record counts in one
+
+BAMF_HD inline uint32_t verdict(uint32_t flag, uint32_t mapq, const ReadFilter& f) {
+    if ((flag & f.exclude) != 0 || (flag & f.require) != f.require) return V_FLAGS;
+    return mapq < f.min_mapq ? V_MAPQ : V_KEPT;
+}
+
+// the record is not read when the filter is off
+BAMF_HD inline bool passes(const uint8_t* b, const Framed& fr, const ReadFilter& f) {
+    if (!filter_on(f)) return true;
+    return verdict(fr.flag, mapq_of(b), f) == V_KEPT;
+}
+
+// The filter of a setter's arguments, or why not (else NULL).
+inline const char* read_filter(int64_t exclude, int64_t require, int64_t min_mapq, ReadFilter& out) {
+    if (exclude < 0 || exclude > 0xffff) return "the excluded flags must lie in [0, 0xFFFF]";
+    if (require < 0 || require > 0xffff) return "the required flags must lie in [0, 0xFFFF]";
+    if (min_mapq < 0 || min_mapq > 255) return "the minimum mapping quality must lie in [0, 255]";
+    if (exclude & require) return "a flag bit both excluded and required lets no read pass";
+    out = ReadFilter{(uint16_t)exclude, (uint16_t)require, (uint8_t)min_mapq};
+    return nullptr;
+}
+
+// The read census: the records that passed the region test, counted in front of the filter and the sample rule, once per
+// region they belong to.  One layout for the host threads, the device array and the C ABI's struct (include/dl4vc_loader.h).
+constexpr int CENSUS_MAPQ = 0, CENSUS_FLAG = 256, CENSUS_SEEN = 272, CENSUS_DROP_FLAGS = 273, CENSUS_DROP_MAPQ = 274,
+              CENSUS_KEPT = 275, CENSUS_WORDS = 276;
+struct Census {
+    uint64_t w[CENSUS_WORDS] = {};
+    void add(const Census& o) { for (int i = 0; i < CENSUS_WORDS; ++i) w[i] += o.w[i]; }
+};
+
+// One record of these flags and MAPQ into the census, `times` over (the regions it belongs to): v is the filter's verdict on it,
+// kept whether it is left behind the sample rule as well.  The one place the host paths count.
+inline void census_add(Census& c, uint32_t flag, uint32_t mapq, uint32_t v, bool kept, uint64_t times = 1) {
+    c.w[CENSUS_MAPQ + (mapq & 0xff)] += times;
+    for (int k = 0; k < 16; ++k)
+        if (flag >> k & 1) c.w[CENSUS_FLAG + k] += times;
+    c.w[CENSUS_SEEN] += times;
+    if (v != V_KEPT) c.w[v == V_FLAGS ? CENSUS_DROP_FLAGS : CENSUS_DROP_MAPQ] += times;
+    else if (kept) c.w[CENSUS_KEPT] += times;
+}
+
+// What becomes of one record that passed the region test: the filter first, then the sample rule (the name hash of a filtered
+// record is not computed).  With `c`, the record is counted in it; the answer is the same without.
+enum Fate : uint32_t { FATE_FILTERED = 0, FATE_UNSAMPLED, FATE_KEPT };
+inline uint32_t fate(Census* c, const uint8_t* b, const Framed& fr, const ReadFilter& f, const SampleRule& rule, uint64_t times = 1) {
+    if (!c && !filter_on(f)) return sampled(b, fr, rule) ? FATE_KEPT : FATE_UNSAMPLED;
+    const uint32_t q = mapq_of(b), v = verdict(fr.flag, q, f);
+    const bool kept = v == V_KEPT && sampled(b, fr, rule);
+    if (c) census_add(*c, fr.flag, q, v, kept, times);
+    return v != V_KEPT ? FATE_FILTERED : kept ? FATE_KEPT : FATE_UNSAMPLED;
+}
+
+#if defined(__HIPCC__)
+// The device side of the census, shared by the two frame kernels: a workgroup counts in s[CENSUS_WORDS] (LDS, uint32: a workgroup
+// of 256 threads times a record's memberships stays far below 2^32) and adds what is not zero to the call's array g[CENSUS_WORDS]
+// with integer atomics, so the sums are exact whatever the order.  A workgroup that saw nothing flushes nothing.
+__device__ inline void census_clear(uint32_t* s) {
+    for (uint32_t k = threadIdx.x; k < (uint32_t)CENSUS_WORDS; k += blockDim.x) s[k] = 0;
+}
+// a record with c > 0 memberships: returns whether the filter keeps it (CENSUS_KEPT is added by the caller, behind the sample rule)
+__device__ inline bool census_count(uint32_t* s, const uint8_t* b, const Framed& fr, const ReadFilter& f, uint32_t c) {
+    const uint32_t q = mapq_of(b), v = verdict(fr.flag, q, f);
+    atomicAdd(&s[CENSUS_MAPQ + q], c);
+    for (uint32_t m = fr.flag & 0xffffu; m; m &= m - 1) atomicAdd(&s[CENSUS_FLAG + __ffs((int)m) - 1], c);
+    atomicAdd(&s[CENSUS_SEEN], c);
+    if (v != V_KEPT) atomicAdd(&s[v == V_FLAGS ? CENSUS_DROP_FLAGS : CENSUS_DROP_MAPQ], c);
+    return v == V_KEPT;
+}
+// (behind a __syncthreads)
+__device__ inline void census_flush(const uint32_t* s, unsigned long long* g) {
+    if (s[CENSUS_SEEN] == 0) return;
+    for (uint32_t k = threadIdx.x; k < (uint32_t)CENSUS_WORDS; k += blockDim.x)
+        if (s[k]) atomicAdd(g + k, (unsigned long long)s[k]);
+}
+#endif
+
 // the reference and query lengths of a framed record's CIGAR, and whether it holds a reference-consuming operation or an N
 BAMF_HD inline void cigar_sums(const uint8_t* b, Framed& fr) {
     fr.nref = fr.nquery = 0;

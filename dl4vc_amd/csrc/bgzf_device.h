@@ -97,10 +97,13 @@ int walk_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Segm
 // Walks segs over infl[0, infl_bytes), frames every record and lists it once for each subregion it overlaps (same tid,
 // pos < end, endpos > start).  *meta (device, owned by the framer) then holds *n_reads entries with off into infl; *n_records
 // = records walked; *err = NO_ERROR or the first refused record.  0 or -2 with msg.  With a sample rule (threshold != 0) a record
-// it drops is listed nowhere; *n_seen (if given) = the entries in front of the rule (= *n_reads without one).
+// it drops is listed nowhere; *n_seen (if given) = the entries in front of the rule (= *n_reads without one).  A record the read
+// filter drops is listed nowhere either, in front of the rule; with a filter, or with `census` (the entries in front of the filter
+// are added to it), the frame kernel counts in LDS and flushes with integer atomics; with neither it runs as without the option.
 int frame_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Segment* segs, uint64_t n_segs, uint64_t n_slots,
                   const SubRange* subs /* host */, uint32_t n_subs, hipStream_t stream,
                   const cand::ReadMeta** meta, uint64_t* n_reads, uint64_t* n_records, uint64_t* err, const char** msg,
-                  bamn::frame::SampleRule rule = bamn::frame::SampleRule{0, 0}, uint64_t* n_seen = nullptr);
+                  bamn::frame::SampleRule rule = bamn::frame::SampleRule{0, 0}, uint64_t* n_seen = nullptr,
+                  bamn::frame::ReadFilter filter = bamn::frame::ReadFilter{0, 0, 0}, bamn::frame::Census* census = nullptr);
 
 }  // namespace bz

@@ -138,15 +138,21 @@ __device__ inline bool belongs(const F::Framed& fr, const SubRange& s) {
 
 // One thread per slot: frames the record there (if any) and counts the subregions it belongs to.  With a sample rule (threshold
 // != 0) a record the rule drops belongs to none, after it has been framed and checked like every other; *seen then gathers the
-// memberships in front of the rule, one atomic add per workgroup.
+// memberships in front of the rule, one atomic add per workgroup.  With `census` (given when the read filter is on or the read
+// stats were asked for; filter = exclude | require << 16) the workgroup counts its memberships in LDS in front of the filter, a
+// record the filter drops belongs to no subregion, and the rule and *seen come behind the filter.
 __global__ void bam_frame_kernel(const uint8_t* __restrict__ infl, const uint64_t* __restrict__ rec_off, uint64_t n_slots,
                                  const SubRange* __restrict__ subs, uint32_t n_subs, uint32_t* __restrict__ count,
                                  int32_t* __restrict__ md_off, int32_t* __restrict__ md_len, unsigned long long* __restrict__ err,
-                                 uint32_t sample_seed, uint32_t sample_threshold, unsigned long long* __restrict__ seen) {
+                                 uint32_t sample_seed, uint32_t sample_threshold, unsigned long long* __restrict__ seen,
+                                 uint32_t filter, uint32_t min_mapq, unsigned long long* __restrict__ census) {
     __shared__ uint32_t s_seen;
+    __shared__ uint32_t s_cen[F::CENSUS_WORDS];
     const bool on = sample_threshold != 0;                  // (uniform)
-    if (on) {
+    const bool cen = census != nullptr;                     // (uniform)
+    if (on || cen) {
         if (threadIdx.x == 0) s_seen = 0;
+        if (cen) F::census_clear(s_cen);
         __syncthreads();
     }
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -165,17 +171,23 @@ __global__ void bam_frame_kernel(const uint8_t* __restrict__ infl, const uint64_
                 for (uint32_t s = 0; s < n_subs; ++s) c += belongs(fr, subs[s]) ? 1u : 0u;
                 md_off[i] = fr.md_off;
                 md_len[i] = fr.md_len;
+                if (cen && c) {
+                    const F::ReadFilter flt{(uint16_t)filter, (uint16_t)(filter >> 16), (uint8_t)min_mapq};
+                    if (!F::census_count(s_cen, b, fr, flt, c)) c = 0;
+                }
                 if (on && c) {
                     atomicAdd(&s_seen, c);
                     if (!F::sampled(b, fr, F::SampleRule{sample_seed, sample_threshold})) c = 0;
                 }
+                if (cen && c) atomicAdd(&s_cen[F::CENSUS_KEPT], c);
             }
         }
         count[i] = c;
     }
-    if (on) {
+    if (on || cen) {
         __syncthreads();
-        if (threadIdx.x == 0 && s_seen) atomicAdd(seen, (unsigned long long)s_seen);
+        if (on && threadIdx.x == 0 && s_seen) atomicAdd(seen, (unsigned long long)s_seen);
+        if (cen) F::census_flush(s_cen, census);
     }
 }
 
@@ -228,8 +240,9 @@ int walk_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Segm
     if (n_slots >= (1ull << 31)) { *msg = "too many record slots in one batch"; return -2; }
     HIP_CHECK_MSG(f->segs.ensure(n_segs * sizeof(Segment)));
     HIP_CHECK_MSG(f->rec_off.ensure(n_slots * 8));
-    HIP_CHECK_MSG(f->scalars.ensure(3 * 8));
-    unsigned long long* sc = f->scalars.as<unsigned long long>();   // [0] records walked, [1] first refused record, [2] frame_records: seen
+    HIP_CHECK_MSG(f->scalars.ensure((3 + F::CENSUS_WORDS) * 8));
+    // [0] records walked, [1] first refused record, [2] frame_records: seen, [3, 3 + CENSUS_WORDS): frame_records: the read census
+    unsigned long long* sc = f->scalars.as<unsigned long long>();
     HIP_CHECK_MSG(hipMemcpyAsync(f->segs.p, segs, n_segs * sizeof(Segment), hipMemcpyHostToDevice, stream));
     HIP_CHECK_MSG(hipMemsetAsync(f->rec_off.p, 0xff, n_slots * 8, stream));
     HIP_CHECK_MSG(hipMemsetAsync(sc, 0, 8, stream));
@@ -248,7 +261,8 @@ int walk_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Segm
 
 int frame_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Segment* segs, uint64_t n_segs, uint64_t n_slots,
                   const SubRange* subs, uint32_t n_subs, hipStream_t stream, const cand::ReadMeta** meta, uint64_t* n_reads,
-                  uint64_t* n_records, uint64_t* err, const char** msg, F::SampleRule rule, uint64_t* n_seen) {
+                  uint64_t* n_records, uint64_t* err, const char** msg, F::SampleRule rule, uint64_t* n_seen, F::ReadFilter filter,
+                  F::Census* census) {
     *meta = nullptr; *n_reads = 0; *n_records = 0; *err = NO_ERROR;
     if (n_seen) *n_seen = 0;
     if (n_segs == 0 || n_slots == 0) return 0;
@@ -262,13 +276,15 @@ int frame_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Seg
     HIP_CHECK_MSG(f->md_off.ensure(n_slots * 4));
     HIP_CHECK_MSG(f->md_len.ensure(n_slots * 4));
     unsigned long long* sc = f->scalars.as<unsigned long long>();
-    unsigned long long h[3];
+    unsigned long long h[3 + F::CENSUS_WORDS];
+    const bool cen = census != nullptr || F::filter_on(filter);
     HIP_CHECK_MSG(hipMemcpyAsync(f->subs.p, subs, n_subs * sizeof(SubRange), hipMemcpyHostToDevice, stream));
-    HIP_CHECK_MSG(hipMemsetAsync(sc + 2, 0, 8, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(sc + 2, 0, cen ? (1 + F::CENSUS_WORDS) * 8 : 8, stream));
     const unsigned grid = (unsigned)((n_slots + TB - 1) / TB);
     hipLaunchKernelGGL(bam_frame_kernel, dim3(grid), dim3(TB), 0, stream, infl, f->rec_off.as<const uint64_t>(), n_slots,
                        f->subs.as<const SubRange>(), n_subs, f->count.as<uint32_t>(), f->md_off.as<int32_t>(), f->md_len.as<int32_t>(),
-                       sc + 1, rule.seed, rule.threshold, sc + 2);
+                       sc + 1, rule.seed, rule.threshold, sc + 2, (uint32_t)filter.exclude | (uint32_t)filter.require << 16,
+                       (uint32_t)filter.min_mapq, cen ? sc + 3 : nullptr);
     HIP_CHECK_MSG(hipGetLastError());
     HIP_CHECK_MSG(hipMemsetAsync(f->count.as<uint32_t>() + n_slots, 0, 4, stream));
     size_t tb = 0;
@@ -280,10 +296,12 @@ int frame_records(Framer* f, const uint8_t* infl, uint64_t infl_bytes, const Seg
                                           rocprim::plus<uint32_t>(), stream));
     uint32_t total = 0;
     HIP_CHECK_MSG(hipMemcpyAsync(&total, f->first.as<uint32_t>() + n_slots, 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK_MSG(hipMemcpyAsync(h, sc, 24, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK_MSG(hipMemcpyAsync(h, sc, cen ? sizeof(h) : 24, hipMemcpyDeviceToHost, stream));
     HIP_CHECK_MSG(hipStreamSynchronize(stream));
     if (h[1] != NO_ERROR) { *err = h[1]; return 0; }
     if (n_seen) *n_seen = rule.threshold ? h[2] : total;
+    if (census && cen)
+        for (int k = 0; k < F::CENSUS_WORDS; ++k) census->w[k] += h[3 + k];
     HIP_CHECK_MSG(f->meta.ensure(((size_t)total + 1) * sizeof(cand::ReadMeta)));
     if (total) {
         hipLaunchKernelGGL(bam_emit_kernel, dim3(grid), dim3(TB), 0, stream, infl, f->rec_off.as<const uint64_t>(), n_slots,

@@ -47,7 +47,8 @@ struct Gathered {
     std::vector<uint8_t> bytes;
     std::vector<cand::ReadMeta> meta;   // off relative to bytes
     std::string err;
-    int64_t seen = 0;                   // records that passed the region test, in front of the sample rule
+    int64_t seen = 0;                   // records that passed the region test and the read filter, in front of the sample rule
+    bamn::frame::Census census;         // filled when the handle collects the read census
 };
 
 }  // namespace
@@ -76,6 +77,11 @@ struct cg_handle {   // (members are destroyed last to first: the stream outlive
     // read subsampling (cg_set_subsample)
     bamn::frame::SampleRule sample{0, 0};
     cg_subsample_stats sst{};
+    // read filter and census (cg_set_read_filter, cg_set_read_stats): the census is collected with a filter or when asked for
+    bamn::frame::ReadFilter filter{0, 0, 0};
+    bool read_stats = false;
+    bamn::frame::Census census;
+    bool collects() const { return read_stats || bamn::frame::filter_on(filter); }
 };
 
 namespace {
@@ -107,8 +113,10 @@ bool fetch_sub(cg_handle* h, bamn::BamFile& bam, std::vector<uint8_t>& blk, cons
         if (fr.pos >= rg.end) return true;
         F::cigar_sums(blk.data(), fr);
         if (F::endpos(fr) <= rg.start) continue;
+        const uint32_t fate = F::fate(h->collects() ? &g.census : nullptr, blk.data(), fr, h->filter, h->sample);
+        if (fate == F::FATE_FILTERED) continue;
         ++g.seen;
-        if (!F::sampled(blk.data(), fr, h->sample)) continue;
+        if (fate != F::FATE_KEPT) continue;
         cand::ReadMeta m;
         m.off = g.bytes.size();
         m.len = (uint32_t)blk.size();
@@ -290,6 +298,8 @@ int run_batch(cg_handle* h, const cg_region* regions, int64_t b0, int64_t b1, cg
     // gather into the pinned buffer, subregion by subregion
     uint64_t bytes = 0, n_reads = 0;
     for (auto& g : per) { bytes += g.bytes.size(); n_reads += g.meta.size(); h->sst.records_seen += g.seen; }
+    if (h->collects())
+        for (auto& g : per) h->census.add(g.census);
     h->sst.records_kept += (int64_t)n_reads;
     if (h->pinned.ensure(bytes + 1) != hipSuccess) return fail(-2, "pinned allocation of %llu bytes failed", (unsigned long long)bytes);
     std::vector<cand::ReadMeta> meta;
@@ -363,7 +373,8 @@ int run_batch_device(cg_handle* h, const cg_region* regions, int64_t b0, int64_t
     const char* msg = nullptr;
     CG_TRY(hipEventRecord(h->ev[0], h->stream));
     if (bz::frame_records(h->framer.get(), h->inflate.d_infl.p, infl_bytes, pl.segs.data(), pl.segs.size(), pl.n_slots, sr.data(), n_subs,
-                          h->stream, &meta_dev, &n_reads, &n_records, &err, &msg, h->sample, &n_seen))
+                          h->stream, &meta_dev, &n_reads, &n_records, &err, &msg, h->sample, &n_seen, h->filter,
+                          h->collects() ? &h->census : nullptr))
         return fail(-2, "device framing: %s", msg);
     if (err != bz::NO_ERROR)
         return fail(-3, "%s (record at virtual offset %lld)", bamn::frame::why_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
@@ -426,6 +437,7 @@ int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg
         h->ist = cg_inflate_stats{};
         h->rst.reads = 0;
         h->sst = cg_subsample_stats{};
+        h->census = bamn::frame::Census{};
         h->out.clear();
         for (int64_t i = 0; i < n_regions; ++i) {
             const cg_region& r = regions[i];
@@ -479,6 +491,27 @@ int cg_set_subsample(cg_handle_t* h, double fraction, uint32_t seed) {
 int cg_get_subsample_stats(const cg_handle_t* h, cg_subsample_stats* out) {
     if (!h || !out) return fail(-1, "cg_get_subsample_stats: null argument");
     *out = h->sst;
+    return 0;
+}
+
+int cg_set_read_filter(cg_handle_t* h, int32_t exclude, int32_t require, int32_t min_mapq) {
+    return capi::guarded(g_err, "cg_set_read_filter", [&] {
+        if (!h) return fail(-1, "cg_set_read_filter: null handle");
+        if (const char* why = bamn::frame::read_filter(exclude, require, min_mapq, h->filter)) return fail(-1, "cg_set_read_filter: %s", why);
+        return 0;
+    });
+}
+
+int cg_set_read_stats(cg_handle_t* h, int on) {
+    if (!h) return fail(-1, "cg_set_read_stats: null handle");
+    h->read_stats = on != 0;
+    return 0;
+}
+
+int cg_get_read_stats(const cg_handle_t* h, dl4vc_read_stats* out) {
+    if (!h || !out) return fail(-1, "cg_get_read_stats: null argument");
+    static_assert(sizeof(dl4vc_read_stats) == sizeof(h->census.w), "dl4vc_read_stats is the census's words");
+    memcpy(out, h->census.w, sizeof(*out));
     return 0;
 }
 

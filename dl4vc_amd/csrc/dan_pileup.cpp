@@ -60,7 +60,8 @@ using bamn::Bai;
 struct Rec {
     int32_t tid = -1, pos = 0, ref_end = 0;
     uint16_t flag = 0;
-    bool sampled = true;                                         // false: the sample rule dropped it, it overlaps no window
+    bool sampled = true;                                         // false: the read filter or the sample rule dropped it
+    uint8_t mapq = 0, verdict = 0;                               // bamn::frame::Verdict of the read filter (0: it passes)
     std::string name, seq;
     std::vector<uint32_t> cigar;                                 // (len << 4) | op
     std::vector<uint8_t> qual;
@@ -122,6 +123,7 @@ using fastan::Fasta;
 struct Bam : bamn::BamFile {
     std::vector<uint8_t> b;
     bamn::frame::SampleRule sample{0, 0};                        // pe_set_subsample
+    bamn::frame::ReadFilter filter{0, 0, 0};                     // pe_set_read_filter
     int get_tid(const std::string& name) const {
         auto it = tid_of.find(name);
         if (it != tid_of.end()) return it->second;
@@ -141,7 +143,9 @@ struct Bam : bamn::BamFile {
         auto rec = std::make_shared<Rec>();
         rec->tid = fr.tid; rec->pos = fr.pos; rec->flag = (uint16_t)fr.flag;
         rec->ref_end = (int32_t)(fr.pos + (fr.nref > 0 ? fr.nref : 1));
-        rec->sampled = bamn::frame::sampled(b.data(), fr, sample);
+        rec->mapq = (uint8_t)bamn::frame::mapq_of(b.data());
+        rec->verdict = (uint8_t)bamn::frame::verdict(fr.flag, rec->mapq, filter);
+        rec->sampled = bamn::frame::fate(nullptr, b.data(), fr, filter, sample) == bamn::frame::FATE_KEPT;
         rec->name.assign((const char*)&b[32], (size_t)fr.l_name - 1);
         rec->cigar.resize(fr.n_cig);
         for (uint32_t i = 0; i < fr.n_cig; ++i) rec->cigar[i] = bamn::frame::ld32(&b[fr.cigar_off + 4 * i]);
@@ -166,6 +170,8 @@ struct Window {
     std::vector<std::shared_ptr<Rec>> kept;
     std::shared_ptr<Rec> pending;
     bool eof = true;
+    // with it, every record of a location's window is counted (a dropped one as well, so those stay in `kept` until it passes)
+    bamn::frame::Census* census = nullptr;
 
     bool reads(int t, int64_t start, int64_t stop, std::vector<std::shared_ptr<Rec>>& out) {
         out.clear();
@@ -196,13 +202,17 @@ struct Window {
                 if (rec->tid != t) {
                     if (rec->tid > t || rec->tid < 0) { eof = true; break; }
                 } else if (rec->pos >= stop) { pending = rec; break; }
-                else if (rec->ref_end > start && rec->sampled) kept.push_back(rec);
+                else if (rec->ref_end > start && (rec->sampled || census)) kept.push_back(rec);
                 rec.reset();
             }
             at = bam->r.tell();
             scanned_to = stop;
         }
-        for (auto& r : kept) if (r->pos < stop && r->ref_end > start) out.push_back(r);
+        for (auto& r : kept)
+            if (r->pos < stop && r->ref_end > start) {
+                if (census) bamn::frame::census_add(*census, r->flag, r->mapq, r->verdict, r->sampled);
+                if (r->sampled) out.push_back(r);
+            }
         return true;
     }
 };
@@ -215,6 +225,11 @@ struct pe_encoder {
     Bai bai;
     bool have_bai = false;
     bamn::frame::SampleRule sample{0, 0};
+    // read filter and census (pe_set_read_filter, pe_set_read_stats): the census of the last pe_encode, every location's window
+    bamn::frame::ReadFilter filter{0, 0, 0};
+    bool read_stats = false;
+    bamn::frame::Census census;
+    bool collects() const { return read_stats || bamn::frame::filter_on(filter); }
 };
 
 namespace {
@@ -417,6 +432,8 @@ int encode(pe_encoder_t* e, const char* const* contigs, const int32_t* positions
     const int W = 2 * e->opt.window_size + 1, MR = e->opt.max_reads;
     const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(threads > 0 ? threads : 1, n));
     std::vector<std::string> errors((size_t)nt);
+    std::vector<bamn::frame::Census> census(e->collects() ? (size_t)nt : 0);    // one per thread, added up behind the join
+    e->census = bamn::frame::Census{};
     auto work = [&](int ti) {
       try {                                                  // (an exception leaving a std::thread terminates the process)
         const int64_t lo = n * ti / nt, hi = n * (ti + 1) / nt;
@@ -426,7 +443,9 @@ int encode(pe_encoder_t* e, const char* const* contigs, const int32_t* positions
         if (!bam.open(e->bam_path)) { errors[ti] = bam.err; return; }
         if (!fasta.open(e->fasta_path, err)) { errors[ti] = err; return; }
         bam.sample = e->sample;
+        bam.filter = e->filter;
         Window win;
+        if (e->collects()) win.census = &census[(size_t)ti];
         win.bam = &bam; win.bai = e->have_bai ? &e->bai : nullptr;
         for (int64_t i = lo; i < hi; ++i) {
             const int st = encode_one(e->opt, win, bam, fasta, contigs[i], positions[i], reads_out + (size_t)i * MR * W,
@@ -451,6 +470,7 @@ int encode(pe_encoder_t* e, const char* const* contigs, const int32_t* positions
     }
     work(0);
     for (auto& t : pool) t.join();
+    for (auto& c : census) e->census.add(c);
     for (auto& s : errors) if (!s.empty()) return pe_fail(e, "%s", s.c_str());
     return 0;
 }
@@ -498,6 +518,45 @@ int pe_subsample_keeps(const uint8_t* name, int32_t l_read_name, double fraction
         F::Framed fr;
         if (const uint32_t w = F::frame_record(rec.data(), rec.size(), fr, /*aux=*/false)) return pe_fail(nullptr, "%s", F::why_text(w));
         return F::sampled(rec.data(), fr, rule) ? 1 : 0;
+    });
+}
+
+int pe_set_read_filter(pe_encoder_t* e, int32_t exclude, int32_t require, int32_t min_mapq) {
+    if (!e) return pe_fail(nullptr, "pe_set_read_filter: null handle");
+    return capi::guarded(e->err, "pe_set_read_filter", [&] {
+        if (const char* why = bamn::frame::read_filter(exclude, require, min_mapq, e->filter)) return pe_fail(e, "pe_set_read_filter: %s", why);
+        return 0;
+    });
+}
+
+int pe_set_read_stats(pe_encoder_t* e, int on) {
+    if (!e) return pe_fail(nullptr, "pe_set_read_stats: null handle");
+    e->read_stats = on != 0;
+    return 0;
+}
+
+int pe_get_read_stats(const pe_encoder_t* e, dl4vc_read_stats* out) {
+    if (!e || !out) return pe_fail(nullptr, "pe_get_read_stats: null argument");
+    static_assert(sizeof(dl4vc_read_stats) == sizeof(e->census.w), "dl4vc_read_stats is the census's words");
+    memcpy(out, e->census.w, sizeof(*out));
+    return 0;
+}
+
+int pe_read_filter_passes(int32_t flag, int32_t mapq, int32_t exclude, int32_t require, int32_t min_mapq) {
+    return capi::guarded(g_pe_error, "pe_read_filter_passes", [&] {
+        namespace F = bamn::frame;
+        if (flag < 0 || flag > 0xffff || mapq < 0 || mapq > 255) return pe_fail(nullptr, "pe_read_filter_passes: a flag in [0, 0xFFFF] and a MAPQ in [0, 255]");
+        F::ReadFilter f{0, 0, 0};
+        if (const char* why = F::read_filter(exclude, require, min_mapq, f)) return pe_fail(nullptr, "pe_read_filter_passes: %s", why);
+        // a record of nothing but its fixed fields and an empty name, framed by the one core
+        std::vector<uint8_t> rec(33, 0);
+        rec[8] = 1;
+        rec[9] = (uint8_t)mapq;
+        rec[14] = (uint8_t)(flag & 0xff);
+        rec[15] = (uint8_t)(flag >> 8);
+        F::Framed fr;
+        if (const uint32_t w = F::frame_record(rec.data(), rec.size(), fr, /*aux=*/false)) return pe_fail(nullptr, "%s", F::why_text(w));
+        return F::passes(rec.data(), fr, f) ? 1 : 0;
     });
 }
 

@@ -69,6 +69,7 @@ struct Worker {
     bamn::BamFile bam;
     fastan::Fasta fasta;
     std::vector<uint8_t> blk;
+    pg::frame::Census census;    // the read census of this thread's runs in the call in progress
 };
 
 }  // namespace
@@ -104,6 +105,11 @@ struct pg_encoder : pgh::AssembleState {   // (err, device and the staging of pg
     // read subsampling (pg_set_subsample): the rule and the counts of the last call
     pg::frame::SampleRule sample{0, 0};
     pg_subsample_stats sst{};
+    // read filter and census (pg_set_read_filter, pg_set_read_stats): the census is collected with a filter or when asked for
+    pg::frame::ReadFilter filter{0, 0, 0};
+    bool read_stats = false;
+    pg::frame::Census read_census;
+    bool collects() const { return read_stats || pg::frame::filter_on(filter); }
     // pg_compress_records_device: the compressor's buffers, the packed chunk image, the streams, the blob and slots (device and
     // pinned staging), the pinned bytes handed to the caller
     std::unique_ptr<zd::Ctx, void (*)(zd::Ctx*)> zctx{nullptr, zd::ctx_destroy};
@@ -168,9 +174,9 @@ void fetch_ref(fastan::Fasta& fasta, Run& run) {
 }
 
 // The records of one run (pileup_fetch.h), plus the run's reference tokens.
-void fetch_run(pg_encoder* h, bamn::BamFile& bam, fastan::Fasta& fasta, std::vector<uint8_t>& blk, Run& run) {
-    fetch_ref(fasta, run);
-    pgh::fetch_records(h->bai, bam, blk, run.tid, run.s0, run.stop, run, h->sample);
+void fetch_run(pg_encoder* h, Worker* wk, Run& run) {
+    fetch_ref(wk->fasta, run);
+    pgh::fetch_records(h->bai, wk->bam, wk->blk, run.tid, run.s0, run.stop, run, h->sample, h->filter, h->collects() ? &wk->census : nullptr);
 }
 
 // the fetch window of the location at pos1 (1-based): bases [s0, stop), the location's own column at ci
@@ -321,8 +327,11 @@ int encode_batch(pg_encoder* h, const char* const* contigs, std::vector<Entry>& 
     {
         const int nt = thread_count(runs.size());
         if (const int rc = ensure_workers(h, nt)) return rc;
-        const std::string job_err = on_workers(h, nt, 0, runs.size(), [&](Worker* wk, size_t r) { fetch_run(h, wk->bam, wk->fasta, wk->blk, runs[r]); });
+        for (int t = 0; t < nt; ++t) h->workers[t]->census = pg::frame::Census{};
+        const std::string job_err = on_workers(h, nt, 0, runs.size(), [&](Worker* wk, size_t r) { fetch_run(h, wk, runs[r]); });
         if (!job_err.empty()) return fail(h, -3, "%s", job_err.c_str());
+        if (h->collects())
+            for (int t = 0; t < nt; ++t) h->read_census.add(h->workers[t]->census);
         for (auto& r : runs) if (!r.err.empty()) return fail(h, -3, "%s", r.err.c_str());
     }
     // gather
@@ -559,7 +568,7 @@ int encode_all_device(pg_encoder* h, const char* const* contigs, std::vector<Ent
         const pg::RunOut* d_run_out = nullptr;
         int64_t n_recs = 0, n_res = 0, n_seen = 0;
         if (pg::frame_runs(h->framing.get(), inf.d_infl.p, d_rec_off, d_rec_off ? pl.n_slots : 0, rd.data(), (int32_t)rd.size(), s, &d_grecs, &n_recs,
-                           &n_res, &d_run_out, &err, &msg, h->sample, &n_seen))
+                           &n_res, &d_run_out, &err, &msg, h->sample, &n_seen, h->filter, h->collects() ? &h->read_census : nullptr))
             return fail(h, -2, "device framing: %s", msg);
         if (err != pg::FRAME_NO_ERROR)
             return fail(h, -3, "%s (record at virtual offset %lld)", pg::frame::why_text((uint32_t)(err & 0xff)), (long long)pl.voff_of(err >> 8));
@@ -612,6 +621,7 @@ int encode_all(pg_encoder* h, const char* const* contigs, const int32_t* positio
         if (e.ensure() != hipSuccess) return fail(h, -2, "hipEventCreate failed");
     h->st = pg_stats{};
     h->sst = pg_subsample_stats{};
+    h->read_census = pg::frame::Census{};
     // the caller's stream must not run ahead of (or behind) our work on its planes
     hipStream_t cs = (hipStream_t)stream;
     if (out.device_planes) {
@@ -858,6 +868,27 @@ int pg_set_subsample(pg_encoder_t* h, double fraction, uint32_t seed) {
 int pg_get_subsample_stats(const pg_encoder_t* h, pg_subsample_stats* out) {
     if (!h || !out) return fail(nullptr, -1, "pg_get_subsample_stats: null argument");
     *out = h->sst;
+    return 0;
+}
+
+int pg_set_read_filter(pg_encoder_t* h, int32_t exclude, int32_t require, int32_t min_mapq) {
+    if (!h) return fail(nullptr, -1, "pg_set_read_filter: null handle");
+    return capi::guarded(h->err, "pg_set_read_filter", [&] {
+        if (const char* why = pg::frame::read_filter(exclude, require, min_mapq, h->filter)) return fail(h, -1, "pg_set_read_filter: %s", why);
+        return 0;
+    });
+}
+
+int pg_set_read_stats(pg_encoder_t* h, int on) {
+    if (!h) return fail(nullptr, -1, "pg_set_read_stats: null handle");
+    h->read_stats = on != 0;
+    return 0;
+}
+
+int pg_get_read_stats(const pg_encoder_t* h, dl4vc_read_stats* out) {
+    if (!h || !out) return fail(nullptr, -1, "pg_get_read_stats: null argument");
+    static_assert(sizeof(dl4vc_read_stats) == sizeof(h->read_census.w), "dl4vc_read_stats is the census's words");
+    memcpy(out, h->read_census.w, sizeof(*out));
     return 0;
 }
 

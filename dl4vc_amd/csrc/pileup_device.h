@@ -63,10 +63,13 @@ void framing_destroy(Framing* f);
 // the n_runs runs (host) it belongs to, run-major and in file order inside a run: *recs (device, the framing's own, *n_recs
 // entries with off into infl and res from the exclusive scan of their reference lengths, *n_res in all) and *run_out (device).
 // *err = FRAME_NO_ERROR or the first refused record.  0 or -2 with msg.  With a sample rule (threshold != 0) a record it drops
-// is listed in no run; *n_seen (if given) = the entries in front of the rule (= *n_recs without one).
+// is listed in no run; *n_seen (if given) = the entries in front of the rule (= *n_recs without one).  A record the read filter
+// drops is listed in no run either, in front of the rule; with a filter, or with `census` (the entries in front of the filter are
+// added to it), the frame kernel counts in LDS and flushes with integer atomics.
 int frame_runs(Framing* f, const uint8_t* infl, const uint64_t* rec_off, uint64_t n_slots, const RunDesc* runs, int32_t n_runs,
                hipStream_t stream, Rec** recs, int64_t* n_recs, int64_t* n_res, const RunOut** run_out, uint64_t* err, const char** msg,
-               frame::SampleRule rule = frame::SampleRule{0, 0}, int64_t* n_seen = nullptr);
+               frame::SampleRule rule = frame::SampleRule{0, 0}, int64_t* n_seen = nullptr,
+               frame::ReadFilter filter = frame::ReadFilter{0, 0, 0}, frame::Census* census = nullptr);
 // Fills first / last (or pre = 2 in a run that is not sorted) of the device locations whose pre is -1; loc_run (host): each
 // location's run, -1 for none.  `uploaded` (may be null) is recorded between the copy of loc_run and the kernel.
 int locate(Framing* f, const Rec* recs, const RunOut* run_out, int32_t n_runs, const int32_t* loc_run, Loc* locs, int32_t n_locs,

@@ -26,7 +26,7 @@ struct RunRecs {
     int64_t nres = 0;
     bool sorted = true;
     std::string err;
-    int64_t seen = 0;            // records that passed the region test, in front of the sample rule
+    int64_t seen = 0;            // records that passed the region test and the read filter, in front of the sample rule
 };
 
 struct Region { int32_t tid; int64_t start, end; };
@@ -48,9 +48,11 @@ inline void append(RunRecs& run, const pg::frame::Framed& fr, uint64_t off, int3
 
 // The records of one run: tid == run's, pos < stop and pos + max(nref, 1) > s0 (the window reader of dan_pileup.cpp), read
 // forward from the linear index's offset for s0.  A record the sample rule drops (bam_frame.h) is framed and checked like every
-// other and then joins no run.
+// other and then joins no run; so is a record the read filter drops, in front of the rule.  `census` (the calling thread's own, may
+// be null): every record that passed the region test is counted in it, in front of the filter.
 inline void fetch_records(const bamn::Bai& bai, bamn::BamFile& bam, std::vector<uint8_t>& blk, int32_t tid, int64_t s0, int64_t stop,
-                          RunRecs& run, pg::frame::SampleRule rule = pg::frame::SampleRule{0, 0}) {
+                          RunRecs& run, pg::frame::SampleRule rule = pg::frame::SampleRule{0, 0},
+                          pg::frame::ReadFilter filter = pg::frame::ReadFilter{0, 0, 0}, pg::frame::Census* census = nullptr) {
     namespace F = pg::frame;
     const uint64_t at = bai.linear_offset(tid, s0);
     if (at == 0) return;
@@ -70,8 +72,10 @@ inline void fetch_records(const bamn::Bai& bai, bamn::BamFile& bam, std::vector<
         if (fr.pos >= stop) return;
         if (const uint32_t why = F::walk_cigar(blk.data(), fr)) { run.err = at_voff(F::why_text(why), voff); return; }
         if (!F::keeps(fr, tid, s0, stop)) continue;
+        const uint32_t fate = F::fate(census, blk.data(), fr, filter, rule);
+        if (fate == F::FATE_FILTERED) continue;
         ++run.seen;
-        if (!F::sampled(blk.data(), fr, rule)) continue;
+        if (fate != F::FATE_KEPT) continue;
         append(run, fr, run.bytes.size(), last_pos);
         run.bytes.insert(run.bytes.end(), blk.begin(), blk.end());
         run.bytes.resize((run.bytes.size() + 3) & ~(size_t)3);

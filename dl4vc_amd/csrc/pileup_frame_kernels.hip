@@ -27,16 +27,23 @@ __device__ inline void report(unsigned long long* err, uint64_t off, uint32_t wh
 }
 
 // With a sample rule (sample_threshold != 0, bam_frame.h) a record the rule drops belongs to no run, after it has been framed
-// and checked like every other; *seen then gathers the memberships in front of the rule, one atomic add per workgroup.
+// and checked like every other; *seen then gathers the memberships in front of the rule, one atomic add per workgroup.  With
+// `census` (given when the read filter is on or the read stats were asked for; filter = exclude | require << 16) the workgroup
+// counts its memberships in LDS in front of the filter, a record the filter drops belongs to no run, and the rule and *seen come
+// behind the filter.
 __global__ void __launch_bounds__(TB) pileup_frame_kernel(const uint8_t* __restrict__ infl, const uint64_t* __restrict__ rec_off,
                                                           uint32_t n_slots, const RunDesc* __restrict__ runs, int32_t n_runs,
                                                           uint32_t* __restrict__ count, int32_t* __restrict__ first_run,
                                                           unsigned long long* __restrict__ err, uint32_t sample_seed,
-                                                          uint32_t sample_threshold, unsigned long long* __restrict__ seen) {
+                                                          uint32_t sample_threshold, unsigned long long* __restrict__ seen,
+                                                          uint32_t filter, uint32_t min_mapq, unsigned long long* __restrict__ census) {
     __shared__ uint32_t s_seen;
+    __shared__ uint32_t s_cen[F::CENSUS_WORDS];
     const bool on = sample_threshold != 0;                  // (uniform)
-    if (on) {
+    const bool cen = census != nullptr;                     // (uniform)
+    if (on || cen) {
         if (threadIdx.x == 0) s_seen = 0;
+        if (cen) F::census_clear(s_cen);
         __syncthreads();
     }
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -72,10 +79,15 @@ __global__ void __launch_bounds__(TB) pileup_frame_kernel(const uint8_t* __restr
                         if (!F::keeps(fr, r.tid, r.s0, r.stop)) break;
                         ++c;
                     }
+                    if (cen && c) {
+                        const F::ReadFilter flt{(uint16_t)filter, (uint16_t)(filter >> 16), (uint8_t)min_mapq};
+                        if (!F::census_count(s_cen, b, fr, flt, c)) c = 0;
+                    }
                     if (on && c) {
                         atomicAdd(&s_seen, c);
                         if (!F::sampled(b, fr, F::SampleRule{sample_seed, sample_threshold})) c = 0;
                     }
+                    if (cen && c) atomicAdd(&s_cen[F::CENSUS_KEPT], c);
                 }
             }
             if (why != F::W_NONE) report(err, at, why);
@@ -83,9 +95,10 @@ __global__ void __launch_bounds__(TB) pileup_frame_kernel(const uint8_t* __restr
         count[i] = c;
         first_run[i] = k0;
     }
-    if (on) {
+    if (on || cen) {
         __syncthreads();
-        if (threadIdx.x == 0 && s_seen) atomicAdd(seen, (unsigned long long)s_seen);
+        if (on && threadIdx.x == 0 && s_seen) atomicAdd(seen, (unsigned long long)s_seen);
+        if (cen) F::census_flush(s_cen, census);
     }
 }
 
@@ -180,7 +193,7 @@ void framing_destroy(Framing* f) { delete f; }
 
 int frame_runs(Framing* f, const uint8_t* infl, const uint64_t* rec_off, uint64_t n_slots, const RunDesc* runs, int32_t n_runs,
                hipStream_t stream, Rec** recs, int64_t* n_recs, int64_t* n_res, const RunOut** run_out, uint64_t* err, const char** msg,
-               F::SampleRule rule, int64_t* n_seen) {
+               F::SampleRule rule, int64_t* n_seen, F::ReadFilter filter, F::Census* census) {
     if (n_seen) *n_seen = 0;
     *recs = nullptr; *n_recs = 0; *n_res = 0; *run_out = nullptr; *err = FRAME_NO_ERROR;
     if (n_runs <= 0) return 0;
@@ -193,18 +206,21 @@ int frame_runs(Framing* f, const uint8_t* infl, const uint64_t* rec_off, uint64_
     HIP_CHECK_MSG(f->count.ensure(((size_t)ns + 1) * 4));
     HIP_CHECK_MSG(f->first.ensure(((size_t)ns + 1) * 4));
     HIP_CHECK_MSG(f->first_run.ensure(((size_t)ns + 1) * 4));
-    HIP_CHECK_MSG(f->err.ensure(16));                       // [0] first refused record, [1] memberships in front of the sample rule
+    // [0] first refused record, [1] memberships in front of the sample rule, [2, 2 + CENSUS_WORDS): the read census
+    HIP_CHECK_MSG(f->err.ensure((2 + F::CENSUS_WORDS) * 8));
+    const bool cen = census != nullptr || F::filter_on(filter);
     unsigned long long* d_err = f->err.as<unsigned long long>();
     HIP_CHECK_MSG(hipMemcpyAsync(f->runs.p, runs, (size_t)n_runs * sizeof(RunDesc), hipMemcpyHostToDevice, stream));
     HIP_CHECK_MSG(hipMemsetAsync(d_err, 0xff, 8, stream));
-    HIP_CHECK_MSG(hipMemsetAsync(d_err + 1, 0, 8, stream));
+    HIP_CHECK_MSG(hipMemsetAsync(d_err + 1, 0, cen ? (1 + F::CENSUS_WORDS) * 8 : 8, stream));
     HIP_CHECK_MSG(hipMemsetAsync(f->rec0.p, 0, (size_t)n_runs * 4, stream));
     HIP_CHECK_MSG(hipMemsetAsync(f->rec1.p, 0, (size_t)n_runs * 4, stream));
     uint32_t total = 0;
     if (ns > 0) {
         const unsigned grid = (ns + TB - 1) / TB;
         hipLaunchKernelGGL(pileup_frame_kernel, dim3(grid), dim3(TB), 0, stream, infl, rec_off, ns, f->runs.as<const RunDesc>(), n_runs,
-                           f->count.as<uint32_t>(), f->first_run.as<int32_t>(), d_err, rule.seed, rule.threshold, d_err + 1);
+                           f->count.as<uint32_t>(), f->first_run.as<int32_t>(), d_err, rule.seed, rule.threshold, d_err + 1,
+                           (uint32_t)filter.exclude | (uint32_t)filter.require << 16, (uint32_t)filter.min_mapq, cen ? d_err + 2 : nullptr);
         HIP_CHECK_MSG(hipGetLastError());
         HIP_CHECK_MSG(hipMemsetAsync(f->count.as<uint32_t>() + ns, 0, 4, stream));
         size_t tb = 0;
@@ -214,12 +230,14 @@ int frame_runs(Framing* f, const uint8_t* infl, const uint64_t* rec_off, uint64_
         tb = f->temp.cap;
         HIP_CHECK_MSG(rocprim::exclusive_scan(f->temp.p, tb, f->count.as<uint32_t>(), f->first.as<uint32_t>(), 0u, (size_t)ns + 1,
                                               rocprim::plus<uint32_t>(), stream));
-        unsigned long long h_err[2] = {0, 0};
+        unsigned long long h_err[2 + F::CENSUS_WORDS] = {0, 0};
         HIP_CHECK_MSG(hipMemcpyAsync(&total, f->first.as<uint32_t>() + ns, 4, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK_MSG(hipMemcpyAsync(h_err, d_err, 16, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK_MSG(hipMemcpyAsync(h_err, d_err, cen ? sizeof(h_err) : 16, hipMemcpyDeviceToHost, stream));
         HIP_CHECK_MSG(hipStreamSynchronize(stream));
         if (h_err[0] != FRAME_NO_ERROR) { *err = h_err[0]; return 0; }
         if (n_seen) *n_seen = rule.threshold ? (int64_t)h_err[1] : (int64_t)total;
+        if (census && cen)
+            for (int k = 0; k < F::CENSUS_WORDS; ++k) census->w[k] += h_err[2 + k];
         if (total >= (1u << 31)) { *msg = "too many records in one group"; return -2; }
     }
     HIP_CHECK_MSG(f->recs.ensure(((size_t)total + 1) * sizeof(Rec)));

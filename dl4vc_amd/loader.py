@@ -21,7 +21,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DL4VC_LOADER_LIB") or os.path.join(_HERE, "csrc", "libdl4vc_loader.so")
 SYMBOLS = ("dl_open", "dl_num_records", "dl_num_sites", "dl_window", "dl_next", "dl_close", "dl_last_error",
            "dl_select_rows", "dl_select_rows_downsample", "dl_allele_masks", "pe_open", "pe_encode", "pe_close", "pe_last_error",
-           "pe_set_subsample", "pe_subsample_keeps")
+           "pe_set_subsample", "pe_subsample_keeps", "pe_set_read_filter", "pe_set_read_stats", "pe_get_read_stats",
+           "pe_read_filter_passes")
 _lib = None
 
 
@@ -48,6 +49,11 @@ def load_library() -> C.CDLL:
         lib.pe_encode.argtypes = [vp, C.POINTER(C.c_char_p), vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int32]
         lib.pe_set_subsample.argtypes = [vp, C.c_double, C.c_uint32]
         lib.pe_subsample_keeps.argtypes = [C.c_char_p, C.c_int32, C.c_double, C.c_uint32]
+        from .read_filter import ReadStats
+        lib.pe_set_read_filter.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+        lib.pe_set_read_stats.argtypes = [vp, C.c_int]
+        lib.pe_get_read_stats.argtypes = [vp, C.POINTER(ReadStats)]
+        lib.pe_read_filter_passes.argtypes = [C.c_int32] * 5
         lib.pe_close.argtypes = [vp]; lib.pe_close.restype = None
         lib.pe_last_error.argtypes = [vp]; lib.pe_last_error.restype = C.c_char_p
         _lib = lib
@@ -58,6 +64,14 @@ def subsample_keeps(name_field: bytes, fraction: float, seed: int = 0) -> bool:
     """``pe_subsample_keeps``: the native rule (csrc/bam_frame.h) on a record's read name field -- the bytes as they lie in the
     record, NUL included, 1..255 of them."""
     rc = load_library().pe_subsample_keeps(bytes(name_field), len(name_field), float(fraction), int(seed))
+    if rc < 0:
+        raise ValueError(load_library().pe_last_error(None).decode())
+    return bool(rc)
+
+
+def read_filter_passes(flag: int, mapq: int, exclude: int = 0, require: int = 0, min_mapq: int = 0) -> bool:
+    """``pe_read_filter_passes``: the native rule (csrc/bam_frame.h) on a record of these flags and MAPQ."""
+    rc = load_library().pe_read_filter_passes(int(flag), int(mapq), int(exclude), int(require), int(min_mapq))
     if rc < 0:
         raise ValueError(load_library().pe_last_error(None).decode())
     return bool(rc)
@@ -149,10 +163,14 @@ class NativePileupEncoder:
     """ctypes face of the native pileup encoder (``pe_*``, row N4): image planes of a run of locations, in order."""
 
     def __init__(self, bam_path: str, fasta_path: str, window_size: int, max_reads: int, max_insert_length: int,
-                 max_insert_length_variant: int, min_base_quality: int = 0, bai_path: Optional[str] = None, subsample=None):
-        """``subsample=(fraction, seed)``: reads are subsampled by name hash (``pe_set_subsample``, ``bamio.SampleRule``)."""
-        from .bamio import SampleRule
+                 max_insert_length_variant: int, min_base_quality: int = 0, bai_path: Optional[str] = None, subsample=None,
+                 read_filter=None, read_stats: bool = False):
+        """``subsample=(fraction, seed)``: reads are subsampled by name hash (``pe_set_subsample``, ``bamio.SampleRule``).
+        ``read_filter=(exclude, require, min_mapq)``: reads are dropped by flags and mapping quality in front of that rule
+        (``pe_set_read_filter``, ``bamio.ReadFilter``); ``read_stats``: the census is collected without a filter too."""
+        from .bamio import ReadFilter, SampleRule
         rule = SampleRule.of(subsample)
+        flt = ReadFilter.of(read_filter)
         self.lib = load_library()
         self._h = C.c_void_p()
         self.window, self.max_reads = 2 * window_size + 1, max_reads
@@ -165,12 +183,27 @@ class NativePileupEncoder:
             msg = self.lib.pe_last_error(self._h).decode()
             self.close()
             raise RuntimeError("pe_set_subsample failed: %s" % msg)
+        if (flt is not None and self.lib.pe_set_read_filter(self._h, *flt.as_tuple()) != 0) or \
+                (read_stats and self.lib.pe_set_read_stats(self._h, 1) != 0):
+            msg = self.lib.pe_last_error(self._h).decode()
+            self.close()
+            raise RuntimeError("pe_set_read_filter failed: %s" % msg)
 
     @classmethod
     def from_options(cls, bam, fasta, opt):
         """The encoder of a ``pileup_encoder.EncoderOptions``."""
         return cls(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length, opt.max_insert_length_variant,
-                   opt.min_base_quality, subsample=getattr(opt, "subsample", None))
+                   opt.min_base_quality, subsample=getattr(opt, "subsample", None), read_filter=getattr(opt, "read_filter", None),
+                   read_stats=getattr(opt, "read_stats", False))
+
+    def read_stats(self) -> dict:
+        """The read census of the last ``encode`` (``read_filter.ReadStats.flat``): every record of a location's window, once per
+        location; all zero unless a filter is on or the stats were asked for."""
+        from .read_filter import ReadStats
+        st = ReadStats()
+        if self.lib.pe_get_read_stats(self._h, C.byref(st)) != 0:
+            raise RuntimeError("pe_get_read_stats failed: %s" % self.lib.pe_last_error(self._h).decode())
+        return st.flat()
 
     def encode(self, contigs, positions, threads: int = 1):
         """-> (reads, qual, strand [n][max_reads][W] u8, ref [n][W] u8, num_reads [n] i32, status [n] i8)."""

@@ -33,6 +33,16 @@ def with_subsample(opt: EncoderOptions, subsample) -> EncoderOptions:
     return replace(opt, subsample=(rule.fraction, rule.seed))
 
 
+def with_read_filter(opt: EncoderOptions, read_filter, read_stats: bool = False) -> EncoderOptions:
+    """``opt`` with ``read_filter`` ((exclude, require, min_mapq), a ``bamio.ReadFilter`` or None) and ``read_stats``."""
+    if read_filter is None and not read_stats:
+        return opt
+    from dataclasses import replace
+    from .bamio import ReadFilter
+    f = ReadFilter.of(read_filter)
+    return replace(opt, read_filter=f.as_tuple() if f is not None else None, read_stats=bool(read_stats))
+
+
 def default_threads() -> int:
     return max(2, min(16, os.cpu_count() or 4))
 
@@ -57,7 +67,7 @@ class HostEncoders:
         """The Python builder's record of ``loc``, or None."""
         if self._py is None:
             from .bamio import BamFile, FastaFile, WindowReader
-            b = BamFile(self.bam, subsample=getattr(self.opt, "subsample", None))
+            b = BamFile(self.bam, subsample=getattr(self.opt, "subsample", None), read_filter=getattr(self.opt, "read_filter", None))
             self._py = (b, FastaFile(self.fasta), WindowReader(b))
         b, f, reader = self._py
         res = encode_location(b, f, loc, self.opt, reader)

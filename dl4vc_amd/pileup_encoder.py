@@ -63,6 +63,11 @@ class EncoderOptions:
     # (fraction, seed): read subsampling by name hash (``bamio.SampleRule``), applied by every encoder where a read outside
     # the window is dropped; None = every read
     subsample: Optional[Tuple[float, int]] = None
+    # (exclude, require, min_mapq): read filter by flags and mapping quality (``bamio.ReadFilter``), applied by every encoder at
+    # the same place in front of the sample rule; None = every read.  read_stats: the native encoders collect the read census
+    # without a filter too
+    read_filter: Optional[Tuple[int, int, int]] = None
+    read_stats: bool = False
 
 
 def decode_base(base_str: str):
@@ -421,11 +426,21 @@ def encode_location(bam, fasta, loc: Location, opt: EncoderOptions, reader=None)
     return process_columns(cols(), loc.pos, opt)
 
 
+def _add_counts(total: dict, part: dict) -> None:
+    for k, v in part.items():
+        total[k] = total.get(k, 0) + v
+
+
 def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Location], opt: EncoderOptions,
                      native: Optional[bool] = None, threads: int = 1, device: Optional[str] = None,
                      device_id: int = 0, inflate_device: Optional[str] = None, compress_device: Optional[str] = None,
-                     pending: int = 0, records_per_chunk: int = 8, compress_codes: str = "fixed", subsample=None):
+                     pending: int = 0, records_per_chunk: int = 8, compress_codes: str = "fixed", subsample=None,
+                     read_stats: Optional[dict] = None):
     """Records for ``locations`` in input order and the number of locations that produced none.
+
+    ``read_stats`` (a dict, with ``opt.read_filter`` or ``opt.read_stats``): the read census of this call is added to it
+    (``read_*`` entries, ``read_filter.census_of``) -- the GPU encoder's over all locations with ``device="gpu"``, else
+    ``pe_encode``'s; the Python builder keeps none.
 
     ``subsample=(fraction, seed)``: ``opt.subsample`` for this call -- every encoder below drops the reads the rule drops
     (``bamio.SampleRule``), so the records are those of the BAM ``tools/subsample_bam.py`` writes (tests/test_subsample_*.py).
@@ -488,12 +503,16 @@ def encode_locations(bam_path: str, fasta_path: str, locations: Sequence[Locatio
         from . import pileup_gpu
         with pileup_gpu.GpuPileupEncoder.from_options(bam_path, fasta_path, opt, device_id, inflate_device) as enc:
             reads, qual, strand, ref, num, status = enc.encode([l.contig for l in locations], [l.pos for l in locations])
+            if read_stats is not None:
+                _add_counts(read_stats, enc.read_stats())
         gpu, rest = status == 1, declined(status)
     host = {}
     if len(rest):
         encoders = HostEncoders(bam_path, fasta_path, opt, threads, native=use_native or device == "gpu")
         try:
             host = encoders.encode(locations, rest)
+            if read_stats is not None and device != "gpu" and encoders.cpu is not None:
+                _add_counts(read_stats, encoders.cpu.read_stats())
         finally:
             encoders.close()
     keep = np.array([i for i in range(n) if gpu[i] or i in host], np.int64)

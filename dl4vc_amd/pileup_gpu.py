@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdl4vc_pileup.so")
 SYMBOLS = ("pg_open", "pg_encode", "pg_encode_device", "pg_assemble_device", "pg_close", "pg_last_error",
            "pg_set_inflate_device", "pg_get_stats", "pg_debug_run_records", "pg_compress_records_device", "pg_set_compress_codes",
-           "pg_census", "pg_set_subsample", "pg_get_subsample_stats")
+           "pg_census", "pg_set_subsample", "pg_get_subsample_stats", "pg_set_read_filter", "pg_set_read_stats", "pg_get_read_stats")
 # the zlib compressor of the same library (csrc/zdeflate.h)
 ZD_SYMBOLS = ("zd_bound", "zd_deflate_host", "zd_deflate", "zd_deflate_host_flags", "zd_code_lengths_host")
 ZD_MIN_SEGMENT, ZD_MAX_SEGMENT, ZD_DEFAULT_SEGMENT = 1024, 32768, 16384
@@ -99,6 +99,10 @@ def load_library() -> C.CDLL:
         lib.pg_get_stats.argtypes = [vp, C.POINTER(Stats)]
         lib.pg_set_subsample.argtypes = [vp, C.c_double, C.c_uint32]
         lib.pg_get_subsample_stats.argtypes = [vp, C.POINTER(SubsampleStats)]
+        from .read_filter import ReadStats
+        lib.pg_set_read_filter.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+        lib.pg_set_read_stats.argtypes = [vp, C.c_int]
+        lib.pg_get_read_stats.argtypes = [vp, C.POINTER(ReadStats)]
         lib.pg_compress_records_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.POINTER(vp), vp, vp, vp, vp, vp]
         lib.zd_bound.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
         lib.zd_deflate_host.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
@@ -209,20 +213,26 @@ class GpuPileupEncoder:
 
     def __init__(self, bam_path: str, fasta_path: str, window_size: int, max_reads: int, max_insert_length: int,
                  max_insert_length_variant: int, min_base_quality: int = 0, bai_path: Optional[str] = None, device: int = 0,
-                 inflate_device: Optional[str] = None, max_inflated_bytes: int = 0, compress_codes: str = "fixed", subsample=None):
-        """``subsample=(fraction, seed)``: reads are subsampled by name hash where the framing runs, on the host threads or in the
+                 inflate_device: Optional[str] = None, max_inflated_bytes: int = 0, compress_codes: str = "fixed", subsample=None,
+                 read_filter=None, read_stats: bool = False):
+        """``read_filter=(exclude, require, min_mapq)``: reads are dropped by flags and mapping quality where the framing runs, in
+        front of the sample rule (``pg_set_read_filter``, ``bamio.ReadFilter``); ``read_stats``: the read census is collected
+        without a filter too (``pg_set_read_stats``); ``read_stats()`` gives it.
+        ``subsample=(fraction, seed)``: reads are subsampled by name hash where the framing runs, on the host threads or in the
         device's frame kernel (``pg_set_subsample``, ``bamio.SampleRule``); ``subsample_stats()`` counts them.
         ``inflate_device="gpu"``: the BGZF blocks are inflated and the records framed on the device (``pg_set_inflate_device``;
         needs the ``.bai``), same outputs.  ``max_inflated_bytes``: inflated bytes per group of runs, 0 = the default.
         ``compress_codes``: ``"fixed"`` or ``"dynamic"``, the codes ``compress_records`` writes (``pg_set_compress_codes``)."""
-        from .bamio import SampleRule
+        from .bamio import ReadFilter, SampleRule
         mode = _codes_mode(compress_codes)
         rule = SampleRule.of(subsample)
+        flt = ReadFilter.of(read_filter)
         if inflate_device not in (None, "gpu"):
             raise ValueError("inflate_device: None or 'gpu', not %r" % (inflate_device,))
         self.lib = load_library()
         self._h = C.c_void_p()
         self.subsample = rule
+        self.read_filter, self.collects = flt, bool(read_stats) or flt is not None
         self.window, self.max_reads, self.device = 2 * window_size + 1, max_reads, device
         opt = PileupOptions(window_size, max_reads, max_insert_length, max_insert_length_variant, min_base_quality)
         rc = self.lib.pg_open(bam_path.encode(), bai_path.encode() if bai_path else None, fasta_path.encode(), C.byref(opt),
@@ -235,6 +245,10 @@ class GpuPileupEncoder:
         try:
             if rule is not None:
                 self.set_subsample(rule.fraction, rule.seed)
+            if flt is not None:
+                self.set_read_filter(*flt.as_tuple())
+            if read_stats:
+                self._check(self.lib.pg_set_read_stats(self._h, 1), "pg_set_read_stats")
             if inflate_device == "gpu":
                 self.set_inflate_device(True, max_inflated_bytes)
         except RuntimeError:
@@ -246,7 +260,20 @@ class GpuPileupEncoder:
         """The encoder of a ``pileup_encoder.EncoderOptions``."""
         return cls(bam, fasta, opt.window_size, opt.max_reads, opt.max_insert_length, opt.max_insert_length_variant,
                    opt.min_base_quality, device=device, inflate_device=inflate_device, compress_codes=compress_codes,
-                   subsample=getattr(opt, "subsample", None))
+                   subsample=getattr(opt, "subsample", None), read_filter=getattr(opt, "read_filter", None),
+                   read_stats=getattr(opt, "read_stats", False))
+
+    def set_read_filter(self, exclude: int = 0, require: int = 0, min_mapq: int = 0) -> None:
+        """``pg_set_read_filter``; all zero turns it off again."""
+        self._check(self.lib.pg_set_read_filter(self._h, int(exclude), int(require), int(min_mapq)), "pg_set_read_filter")
+
+    def read_stats(self) -> dict:
+        """The read census of the last ``encode`` / ``encode_device`` / ``census`` call (``read_filter.ReadStats.flat``): all zero
+        unless a filter is on or the stats were asked for."""
+        from .read_filter import ReadStats
+        st = ReadStats()
+        self._check(self.lib.pg_get_read_stats(self._h, C.byref(st)), "pg_get_read_stats")
+        return st.flat()
 
     def set_subsample(self, fraction: float, seed: int = 0) -> None:
         """``pg_set_subsample``; fraction 0 turns it off again."""
@@ -268,6 +295,8 @@ class GpuPileupEncoder:
         out = {n: getattr(st, n) for n, _ in Stats._fields_}
         if self.subsample is not None:                       # (only with the option: the stages stay pg_stats' otherwise)
             out.update(("subsample_" + k, v) for k, v in self.subsample_stats().items())
+        if self.collects:
+            out.update(self.read_stats())
         return out
 
     def _args(self, contigs: Sequence[str], positions):

@@ -11,6 +11,8 @@
 
 #include <stdint.h>
 
+#include "dl4vc_loader.h"   /* dl4vc_read_stats */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -112,6 +114,16 @@ typedef struct {
     int64_t records_kept;
 } cg_subsample_stats;
 int cg_get_subsample_stats(const cg_handle_t* h, cg_subsample_stats* out);
+/* Read filter by flags and mapping quality (the rule of `samtools view -F exclude -f require -q min_mapq`, one definition in
+ * csrc/bam_frame.h; pe_set_read_filter in dl4vc_loader.h states it).  A record is framed and checked as without the option, then
+ * dropped where a record outside the subregion is dropped, in front of the sample rule, on the host or in the device's frame
+ * kernel: depth, alleles and cg_stats.reads see the kept reads alone, and cg_subsample_stats.records_seen counts what passed
+ * region and filter.  All zero: off.  Refused: a mask outside [0, 0xFFFF], min_mapq outside [0, 255], a bit in both masks.
+ * cg_set_read_stats(h, 1): the read census (dl4vc_read_stats, dl4vc_loader.h) of a cg_run is collected without a filter too; a
+ * read in two subregions counts twice, as in cg_stats.reads.  With neither, the frame kernel runs as without the option. */
+int cg_set_read_filter(cg_handle_t* h, int32_t exclude, int32_t require, int32_t min_mapq);
+int cg_set_read_stats(cg_handle_t* h, int on);
+int cg_get_read_stats(const cg_handle_t* h, dl4vc_read_stats* out);
 /* fasta_path: a read WITHOUT an MD tag is walked against the bases of its contig in this FASTA (indexed by fasta_path.fai when
  * that file exists, else scanned once), in the same kernels; a read WITH an MD tag is walked by its MD as before, whatever the
  * FASTA says.  NULL or "": off again (such reads count in cg_stats.reads_no_md and give no alleles), and the resident contigs

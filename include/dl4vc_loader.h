@@ -100,6 +100,28 @@ int pe_set_subsample(pe_encoder_t* e, double fraction, uint32_t seed);
 /* The rule alone, for tests: 1 if a record whose read name field is name[0, l_read_name) (the bytes as they lie in the record,
  * NUL included; 1 <= l_read_name <= 255) is kept at `fraction` in (0, 1] and `seed`, 0 if dropped, -1 for a refused argument. */
 int pe_subsample_keeps(const uint8_t* name, int32_t l_read_name, double fraction, uint32_t seed);
+/* Read filter by flags and mapping quality, the rule of `samtools view -F exclude -f require -q min_mapq` (csrc/bam_frame.h): a
+ * read is kept iff (flag & exclude) == 0 && (flag & require) == require && MAPQ >= min_mapq.  A record is framed and checked as
+ * without the option and then dropped where a record outside the window is dropped, in front of the sample rule; the encoder's own
+ * fixed mask (0x704) stays behind it.  All zero: off.  exclude or require outside [0, 0xFFFF], min_mapq outside [0, 255] or a bit
+ * in both masks (nothing could pass): refused (-1, pe_last_error(e)). */
+int pe_set_read_filter(pe_encoder_t* e, int32_t exclude, int32_t require, int32_t min_mapq);
+/* The read census, one struct for the three BAM consumers (pe_, pg_ and cg_get_read_stats): the records that passed the region
+ * test, counted in front of the filter and the sample rule, once per region they belong to (pe_: per location window, pg_: per run
+ * of locations, cg_: per subregion).  dropped_flags is tested before dropped_mapq, so a record counts in one; kept is what is left
+ * behind the sample rule as well.  Collected with a filter on or after *_set_read_stats(h, 1); all zero otherwise. */
+typedef struct dl4vc_read_stats {
+    uint64_t mapq_hist[256];   /* records by MAPQ */
+    uint64_t flag_bits[16];    /* records with flag bit k set */
+    uint64_t seen;
+    uint64_t dropped_flags;
+    uint64_t dropped_mapq;
+    uint64_t kept;
+} dl4vc_read_stats;
+int pe_set_read_stats(pe_encoder_t* e, int on);
+int pe_get_read_stats(const pe_encoder_t* e, dl4vc_read_stats* out);     /* of the last pe_encode */
+/* The rule alone, for tests: 1 if a record with these flags and MAPQ is kept, 0 if dropped, -1 for a refused argument. */
+int pe_read_filter_passes(int32_t flag, int32_t mapq, int32_t exclude, int32_t require, int32_t min_mapq);
 void pe_close(pe_encoder_t* e);
 const char* pe_last_error(const pe_encoder_t* e);      /* e may be NULL: error of the last failed pe_open */
 

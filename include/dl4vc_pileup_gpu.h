@@ -124,6 +124,16 @@ typedef struct {
     int64_t records_kept;
 } pg_subsample_stats;
 int pg_get_subsample_stats(const pg_encoder_t* h, pg_subsample_stats* out);
+/* Read filter by flags and mapping quality (the rule of `samtools view -F exclude -f require -q min_mapq`, one definition in
+ * csrc/bam_frame.h; pe_set_read_filter in dl4vc_loader.h states it).  A record is framed and checked as without the option, then
+ * dropped where a record outside its run is dropped, in front of the sample rule, by the host framing threads or in the device's
+ * frame kernel.  Everything behind sees the kept reads alone; the encoder's fixed mask 0x704 stays where it is.  Holds for
+ * pg_encode, pg_encode_device and pg_census; pg_subsample_stats.records_seen then counts what passed region and filter.
+ * pg_set_read_stats(h, 1): the read census (dl4vc_read_stats) of a call is collected without a filter too, once per run a record
+ * belongs to; on the device a workgroup counts in LDS and adds to one small array with integer atomics. */
+int pg_set_read_filter(pg_encoder_t* h, int32_t exclude, int32_t require, int32_t min_mapq);
+int pg_set_read_stats(pg_encoder_t* h, int on);
+int pg_get_read_stats(const pg_encoder_t* h, dl4vc_read_stats* out);
 
 /* ---- candidate HDF5 chunks compressed on the device ---------------------------------------------------------------------------
  * The zlib compressor (csrc/zdeflate.h): an RFC 1950 stream of DEFLATE blocks (fixed codes, or with ZD_DYNAMIC the smaller of a

@@ -439,7 +439,7 @@ def score_bam_census(args, net, target, out_final, shard_i, shard_n, holdout, si
     stage = {}
     t0 = time.time()
     opt = bam_encoder_options(args)
-    sub = {"encoder_options": opt} if opt is not None else {}     # (without --subsample the calls are what they were)
+    sub = {"encoder_options": opt} if opt is not None else {}     # (without --subsample or a read filter the calls are what they were)
     mine = census_bam(args.test_bam, args.test_fasta, locations[lo:hi], inflate_device=args.inflate_device, stage=stage,
                       log=lambda m: print(m, end="\r"), **sub)
     census_stats.update(census_s=time.time() - t0, census_ms=float(stage.get("census_ms", 0.0)), census_locations=hi - lo,
@@ -589,14 +589,50 @@ def check_subsample_arguments(args):
     return (f, s)
 
 
+def check_read_filter_arguments(args):
+    """--min-mapq / --exclude-flags / --require-flags / --read-stats: (exclude, require, min_mapq) or None; every refusal with its
+    reason, before anything touches a device."""
+    import types
+    from dl4vc_amd import read_filter
+
+    def fail(why):
+        raise SystemExit(why)
+
+    def mask(name):
+        v = getattr(args, name, None)
+        if v is None or isinstance(v, int):
+            return v
+        try:
+            return int(v, 0)
+        except ValueError:
+            fail("--%s %r is not a number (decimal or 0x...)" % (name.replace("_", "-"), v))
+
+    given = types.SimpleNamespace(min_mapq=getattr(args, "min_mapq", None), exclude_flags=mask("exclude_flags"),
+                                  require_flags=mask("require_flags"), read_stats=bool(getattr(args, "read_stats", False)))
+    return read_filter.check(given, fail, bool(args.test_bam or getattr(args, "train_bam", None)),
+                             "--test_bam / --train_bam (a --test_file or --train_file holds pileups already encoded: give the flags "
+                             "to the converter that writes it)")
+
+
 def bam_encoder_options(args):
     """What the BAM consumers encode with: None (their default, what call_variants.sh passes to the converter) without
-    --subsample, else that default with the rule."""
+    --subsample and the read filter flags, else that default with them."""
     rule = check_subsample_arguments(args)
-    if rule is None:
+    flt = check_read_filter_arguments(args)
+    stats = bool(getattr(args, "read_stats", False))
+    if rule is None and flt is None and not stats:
         return None
-    from dl4vc_amd.location_round import default_encoder_options, with_subsample
-    return with_subsample(default_encoder_options(), rule)
+    from dl4vc_amd.location_round import default_encoder_options, with_read_filter, with_subsample
+    return with_read_filter(with_subsample(default_encoder_options(), rule), flt, stats)
+
+
+def read_filter_text(args, stage) -> str:
+    from dl4vc_amd import read_filter
+    flt = check_read_filter_arguments(args)
+    lines = [read_filter.report_line(stage, flt) + " (the GPU encoder's records)"] if flt is not None else []
+    if getattr(args, "read_stats", False):
+        lines.append(read_filter.census_text(stage))
+    return "\n".join(lines)
 
 
 def subsample_text(args, stage) -> str:
@@ -632,6 +668,7 @@ def main(argv=None) -> int:
                          "record); the records of a --test_file are already counted")
     check_train_bam_arguments(args)
     check_subsample_arguments(args)
+    check_read_filter_arguments(args)
     check_downsample_arguments(args)
     if args.loader_device is not None:
         check_loader_device_arguments(args)
@@ -775,6 +812,9 @@ def main(argv=None) -> int:
     net.close()
     if getattr(args, "subsample", None) is not None:
         print("\n" + subsample_text(args, score_stage))
+    text = read_filter_text(args, score_stage)
+    if text:
+        print("\n" + text)
     if census_stats:
         print("\nrecord census: %s" % census_text(census_stats).lstrip("; "))
     if args.test_bam:

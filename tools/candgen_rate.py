@@ -6,7 +6,7 @@ host's inflate-and-frame time against the device time (per-stage device times co
 
     python tools/candgen_rate.py --bam /tmp/cg_rate.bam [--reads 2000000 --length 10000000] [--out profiles/x.json]
         [--inflate-device gpu] [--chunk_size 1000] [--no-md] [--fasta REF.fa] [--reference REF.fa]
-        [--subsample F [--subsample-seed S]]
+        [--subsample F [--subsample-seed S]] [--min-mapq Q] [--exclude-flags F] [--require-flags F] [--read-stats]
 
 ``--inflate-device gpu`` measures the device inflate path (the line then carries its read / inflate / walk-and-frame times);
 ``--chunk_size`` other than 1000 changes the subregions, and with them the candidates at their boundaries: a timing line only.
@@ -17,7 +17,8 @@ no MD tag against it; the line then carries the ``reference_*`` figures.  Every 
 one-time load (read, upload and convert) is inside every repeat's wall time.
 
 ``--subsample F [--subsample-seed S]`` is passed through (reads subsampled by name hash in front of every count); the line then
-carries the records seen and kept, and ``reads_per_s`` counts the records SEEN, the work the framing did.
+carries the records seen and kept, and ``reads_per_s`` counts the records SEEN, the work the framing did.  The read filter
+flags are passed through likewise; the line then carries the census totals, and ``reads_per_s`` counts the records the census saw.
 """
 import argparse
 import json
@@ -89,15 +90,20 @@ def main():
     ap.add_argument("--fasta", default=None, help="write the BAM's genome here, with its .fai (when the BAM has to be made)")
     ap.add_argument("--reference", default=None, help="walk the reads that have no MD tag against this FASTA")
     from dl4vc_amd import subsample
+    from dl4vc_amd import read_filter
     subsample.add_flags(ap)
+    read_filter.add_flags(ap)
     a = ap.parse_args()
     rule = subsample.parse(ap, a)
+    flt = read_filter.parse(ap, a)
     if not os.path.isfile(a.bam + ".bai"):
         t = time.time()
         make_bam(a.bam, a.reads, a.length, md_tags=not a.no_md, fasta=a.fasta)
         print("wrote %s in %.1f s" % (a.bam, time.time() - t), file=sys.stderr)
     from dl4vc_amd.candidates import generate
     extra = {"subsample": rule} if rule is not None else {}
+    if flt is not None or a.read_stats:
+        extra.update(read_filter=flt, read_stats=a.read_stats)
     runs = []
     for k in range(a.repeats):
         t = time.perf_counter()
@@ -122,6 +128,13 @@ def main():
         res.update(subsample=list(rule), subsample_records_seen=best["subsample_records_seen"],
                    subsample_records_kept=best["subsample_records_kept"],
                    reads_per_s=round(best["subsample_records_seen"] / best["wall_s"]))
+    if flt is not None or a.read_stats:
+        res.update(read_filter=list(flt) if flt is not None else None, reads_per_s=round(best["read_seen"] / best["wall_s"]),
+                   **{k: best[k] for k in ("read_seen", "read_dropped_flags", "read_dropped_mapq", "read_kept")})
+        if flt is not None:
+            print(read_filter.report_line(best, flt), file=sys.stderr)
+        if a.read_stats:
+            print(read_filter.census_text(best), file=sys.stderr)
     if best.get("inflate_ms"):
         res["inflate_MB_per_s"] = round(best["inflate_inflated_bytes"] / 1e6 / (best["inflate_ms"] / 1e3))
     line = json.dumps(res)

@@ -51,6 +51,16 @@ def warn_no_md(stats, reference) -> None:
                         "reference bases", stats["reads_no_md"], stats["reads"])
 
 
+def report_reads(args, stats) -> None:
+    """The read filter's line and, with --read-stats, the census."""
+    from dl4vc_amd import read_filter
+    flt = read_filter.check(args, sys.exit)
+    if flt is not None:
+        print(read_filter.report_line(stats, flt))
+    if args.read_stats:
+        print(read_filter.census_text(stats))
+
+
 def run_children(args, argv) -> int:
     """--gpus N: a fresh process per GPU (``--shard g/N``, its own HIP_VISIBLE_DEVICES), then the merge of their parts."""
     import subprocess
@@ -70,6 +80,7 @@ def run_children(args, argv) -> int:
         from dl4vc_amd import subsample
         print(subsample.report_line(stats["subsample_records_seen"], stats["subsample_records_kept"],
                                     (args.subsample, args.subsample_seed or 0)))
+    report_reads(args, stats)                                 # (the census of the parts, summed)
     logging.info("Generated final VCF file at %s from %d parts.", args.output, args.gpus)
     print("summary " + json.dumps(stats, sort_keys=True))
     return 0
@@ -89,9 +100,12 @@ def main(argv=None) -> int:
                    "of giving them no alleles; reads with an MD tag are walked by it as before. Each contig touched stays on the GPU "
                    "as 1 byte per base")
     from dl4vc_amd import subsample
+    from dl4vc_amd import read_filter
     subsample.add_flags(p)
+    read_filter.add_flags(p)
     args = p.parse_args(argv)
     rule = subsample.parse(p, args)                           # (before any device work, --gpus children included)
+    flt = read_filter.parse(p, args)
     print(args)
     logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.DEBUG if args.debug else logging.INFO)
     if args.reference is not None and not (os.path.isfile(args.reference) and os.access(args.reference, os.R_OK)):
@@ -110,11 +124,12 @@ def main(argv=None) -> int:
                      chunk_size=args.chunk_size, threads=args.threads, snp_min_freq=args.snp_min_freq,
                      indel_min_freq=args.indel_min_freq, keep_multialleles=args.keep_multialleles,
                      max_len_indel_allele=args.max_len_indel_allele, inflate_device=args.inflate_device, shard=shard,
-                     reference=args.reference, subsample=rule)
+                     reference=args.reference, subsample=rule, read_filter=flt, read_stats=args.read_stats)
     if shard is None:                      # (the parent of shards says it once, of the summed counts)
         warn_no_md(stats, args.reference)
         if rule is not None:
             print(subsample.report_line(stats["subsample_records_seen"], stats["subsample_records_kept"], rule))
+        report_reads(args, stats)
     if shard is not None:
         from dl4vc_amd.shard import part_path
         logging.info("Wrote the records of shard %d/%d to %s.", shard[0], shard[1], part_path(args.output, shard[0]))

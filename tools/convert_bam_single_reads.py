@@ -42,6 +42,7 @@ def _convert_compressed(args, locations, opt, start, step, procs, append):
     n_loc = len(locations)
     dtype = record_dtype(opt.max_reads, 2 * opt.window_size + 1)
     total_errors = written = 0
+    census = {}
     stages = {k: 0.0 for k in ("pack_ms", "deflate_ms", "gather_ms", "compress_copy_back_ms", "raw_bytes", "chunk_bytes_out", "stored_chunks",
                                 "fixed_segments", "dynamic_segments", "stored_segments")}
     t0 = time.time()
@@ -59,6 +60,9 @@ def _convert_compressed(args, locations, opt, start, step, procs, append):
                     writer.write_chunks(b.chunks)
                     for k in stages:
                         stages[k] += b.stats[k]
+                for k, v in b.stats.items():
+                    if k.startswith("read_"):
+                        census[k] = census.get(k, 0) + v
                 writer.append_records(b.tail)
                 total_errors += b.errors
                 written += b.records
@@ -67,8 +71,21 @@ def _convert_compressed(args, locations, opt, start, step, procs, append):
     stages.update(chunk_write_ms=round(writer.write_s * 1e3, 3), chunks_from_device=writer.direct_chunks, chunks_from_host=writer.host_chunks,
                   chunks_unfiltered=writer.stored_chunks, records=written)
     print("compress-device gpu stages: %s" % json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in stages.items()}))
+    report_reads(opt, census)
     print("Parsing errors in %d / %d locations -- saved to: %s" % (total_errors, n_loc, args.output))
     return 0
+
+
+def report_reads(opt, census) -> None:
+    """The read filter's line and, with --read-stats, the census: the counts of the encoder that framed the reads (the GPU
+    encoder's with --pileup-device gpu, else pe_encode's; the Python builder keeps none)."""
+    from dl4vc_amd import read_filter
+    if not census:
+        return
+    if opt.read_filter is not None:
+        print(read_filter.report_line(census, opt.read_filter))
+    if opt.read_stats:
+        print(read_filter.census_text(census))
 
 
 def main(argv=None):
@@ -112,9 +129,12 @@ def main(argv=None):
                     help="with --compress-device gpu: dynamic gives a chunk's segments dynamic Huffman codes where that is smaller "
                          "(a smaller file, the same records; the compressor parses every segment twice); default fixed")
     from dl4vc_amd import subsample
+    from dl4vc_amd import read_filter
     subsample.add_flags(ap)
+    read_filter.add_flags(ap)
     args = ap.parse_args(argv)
     rule = subsample.parse(ap, args)
+    flt = read_filter.parse(ap, args)
     if args.inflate_device and args.pileup_device != "gpu":
         raise SystemExit("--inflate-device gpu is an option of the GPU pileup encoder: give --pileup-device gpu as well")
     if args.compress_device and args.pileup_device != "gpu":
@@ -132,7 +152,7 @@ def main(argv=None):
     assert args.save_strand, "Too many options, need to run with strand save"
     opt = EncoderOptions(window_size=args.window_size, max_reads=args.max_reads, max_insert_length=args.max_insert_length,
                          max_insert_length_variant=args.max_insert_length_variant, min_base_quality=args.min_base_quality,
-                         subsample=rule)
+                         subsample=rule, read_filter=flt, read_stats=args.read_stats)
     if rule is not None:
         # (the host encoders keep no count of the records they drop: tools/subsample_bam.py and the candidate generator print them)
         print("subsample: every encoder keeps the reads of fraction %g, seed %d" % rule)
@@ -167,6 +187,7 @@ def main(argv=None):
         import multiprocessing as mp
         pool = mp.get_context("spawn").Pool(procs)
     total_errors, written, created = 0, 0, append
+    census = {}                                               # the read census of the encode calls (with a filter or --read-stats)
     t0 = time.time()
     if args.compress_device == "gpu":
         return _convert_compressed(args, locations, opt, start, step, procs, append)
@@ -181,7 +202,7 @@ def main(argv=None):
                 errors = sum(p[1] for p in parts)
             else:
                 recs, errors = encode_locations(args.input, args.fasta_input, chunk, opt, native=native, threads=procs,
-                                                device=args.pileup_device, inflate_device=args.inflate_device)
+                                                device=args.pileup_device, inflate_device=args.inflate_device, read_stats=census)
             total_errors += errors
             if not created:
                 hdf5io.write_candidates(args.output, recs, chunk=8)
@@ -195,6 +216,7 @@ def main(argv=None):
         if pool is not None:
             pool.terminate()
             pool.join()
+    report_reads(opt, census)
     print("Parsing errors in %d / %d locations -- saved to: %s" % (total_errors, n_loc, args.output))
     return 0
 

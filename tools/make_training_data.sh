@@ -15,8 +15,10 @@
 # per base) instead of giving them no alleles; reads with an MD tag are walked by it as before.  Not passed by default.
 # -s F [-S SEED]: candidate generation and the converter (with -n: the printed --train_bam flags) keep the fraction F in (0, 1] of
 # the BAM's reads, chosen by a hash of the read name (--subsample / --subsample-seed): training data at F of the coverage.
+# -q Q, -F MASK, -R MASK: candidate generation and the converter (with -n: the printed --train_bam flags) drop the reads with
+# MAPQ < Q, with any flag bit of -F or without a flag bit of -R (--min-mapq / --exclude-flags / --require-flags).
 set -e
-usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c [-y]] [-n] [-f] [-s FRACTION [-S SEED]]"; exit 1; }
+usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c [-y]] [-n] [-f] [-s FRACTION [-S SEED]] [-q MIN_MAPQ] [-F EXCLUDE_FLAGS] [-R REQUIRE_FLAGS]"; exit 1; }
 PROCS=16
 COMPRESS=""
 CODES=""
@@ -24,7 +26,10 @@ NOFILE=""
 FROMREF=""
 SUBSAMPLE=""
 SEED=""
-while getopts "i:r:t:o:b:p:s:S:nfcyh" opt; do
+MINMAPQ=""
+EXCLUDE=""
+REQUIRE=""
+while getopts "i:r:t:o:b:p:s:S:q:F:R:nfcyh" opt; do
   case $opt in
     i) BAM=$OPTARG ;;
     r) REFERENCE=$OPTARG ;;
@@ -38,6 +43,9 @@ while getopts "i:r:t:o:b:p:s:S:nfcyh" opt; do
     f) FROMREF=1 ;;         # candidate generation: reads without MD are walked against REFERENCE
     s) SUBSAMPLE=$OPTARG ;; # every BAM reader keeps this fraction of the reads (--subsample)
     S) SEED=$OPTARG ;;      # with -s: the seed (--subsample-seed)
+    q) MINMAPQ=$OPTARG ;;   # every BAM reader drops the reads below this mapping quality (--min-mapq)
+    F) EXCLUDE=$OPTARG ;;   # ... and the reads with any of these flag bits (--exclude-flags)
+    R) REQUIRE=$OPTARG ;;   # ... and the reads without any of these flag bits (--require-flags)
     *) usage ;;
   esac
 done
@@ -46,7 +54,8 @@ done
 [ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
 [ -n "$NOFILE" ] && [ -n "$COMPRESS" ] && { echo "-n writes no train.hdf, so there is nothing for -c to compress: give one of them"; exit 1; }
 [ -n "$SEED" ] && [ -z "$SUBSAMPLE" ] && { echo "-S is the seed of -s: give -s FRACTION as well"; exit 1; }
-SUBFLAGS=(${SUBSAMPLE:+--subsample "$SUBSAMPLE"} ${SEED:+--subsample-seed "$SEED"})
+SUBFLAGS=(${SUBSAMPLE:+--subsample "$SUBSAMPLE"} ${SEED:+--subsample-seed "$SEED"} ${MINMAPQ:+--min-mapq "$MINMAPQ"} \
+          ${EXCLUDE:+--exclude-flags "$EXCLUDE"} ${REQUIRE:+--require-flags "$REQUIRE"})
 SCRIPTDIR="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 mkdir -p "$OUTDIR"
 if [ ! -f "$OUTDIR/candidates.vcf" ]; then
@@ -63,7 +72,7 @@ if [ -n "$NOFILE" ]; then
   echo "No train.hdf written.  Train straight from the BAM with:"
   echo "  python $SCRIPTDIR/main.py --train_bam $BAM --train_fasta $REFERENCE --train_tp_vcf $OUTDIR/isec/0003.vcf" \
        "--train_tp_full_vcf $OUTDIR/isec/0002.vcf --train_fp_vcf $OUTDIR/isec/0001.vcf --train-loader-device gpu --train-cache-device gpu" \
-       "[--train-cache-format compact]"${SUBSAMPLE:+ "${SUBFLAGS[*]}"} \
+       "[--train-cache-format compact]"${SUBFLAGS:+ "${SUBFLAGS[*]}"} \
        "( --test_file V.hdf | --test_bam Y.bam --test_fasta REF [--test_tp_vcf ... --test_tp_full_vcf ... --test_fp_vcf ...] )" \
        "<flags of train_variant_caller.sh>"
   exit 0

@@ -10,14 +10,16 @@ rounds), each under its own time limit; a child that fails ends the tool, nothin
 the pass.  One JSON record; no number in it is a pass mark.
 
     python tools/pileup_inflate_rate.py --dir /tmp/pir [--rounds 3] [--wg-reads 2000000 --wg-length 10000000] [--out profiles/x.json]
-        [--kernel-trace] [--score-bam] [--subsample F [--subsample-seed S]]
+        [--kernel-trace] [--score-bam] [--subsample F [--subsample-seed S]] [--min-mapq Q] [--exclude-flags F] [--require-flags F]
+        [--read-stats]
 
 ``--kernel-trace``: afterwards, for both shapes and both settings, one more child (one pass) under ``rocprofv3 --kernel-trace
 --stats``; the record gains the total time per kernel, warm-up included.  ``--score-bam``: afterwards, one round each of
 ``tools/score_bam_rate.py`` on the dense BAM at fp32 and bf16x3, without and with ``--inflate-device gpu``; the record gains the
 scoring-loop rates.  Every one of these is again one process at a time under its own time limit, and a failure ends the tool.
 ``--subsample F [--subsample-seed S]`` is passed through to every child's encoder (reads subsampled by name hash where the
-framing runs); the summed stats then carry ``subsample_records_seen`` / ``subsample_records_kept``.
+framing runs); the summed stats then carry ``subsample_records_seen`` / ``subsample_records_kept``.  The read filter flags are
+passed through likewise; the stats then carry the census totals (``read_seen`` ...).
 """
 import argparse
 import glob
@@ -45,6 +47,8 @@ def child(a):
     dev = torch.device("cuda", 0)
     out = [torch.empty((CALL, 200, 201), dtype=torch.uint8, device=dev) for _ in range(3)]
     extra = {"subsample": (a.subsample, a.subsample_seed or 0)} if a.subsample is not None else {}
+    if a.read_filter is not None or a.read_stats:
+        extra.update(read_filter=a.read_filter, read_stats=a.read_stats)
     with pileup_gpu.GpuPileupEncoder(a.bam, a.fasta, 100, 200, 10, 50, inflate_device=a.inflate_device, **extra) as g:
         g.encode_device(contigs[:1000], pos[:1000], out=out)
         torch.cuda.synchronize()
@@ -62,6 +66,9 @@ def child(a):
             if best is None or dt < best["seconds"]:
                 best = {"seconds": round(dt, 4), "locations_per_s": round(len(pos) / dt), "status_0_1_2": status.tolist(),
                         "stats": {k: (round(v, 2) if isinstance(v, float) else int(v)) for k, v in total.items()}}
+    if a.read_filter is not None:
+        from dl4vc_amd import read_filter
+        print(read_filter.report_line(best["stats"], a.read_filter), file=sys.stderr)
     print("RESULT " + json.dumps(best))
     return 0
 
@@ -123,10 +130,14 @@ def main():
         ap.add_argument(name, type=int, default=default)
     ap.add_argument("--inflate-device", default=None, choices=["gpu"])
     from dl4vc_amd import subsample
+    from dl4vc_amd import read_filter
     subsample.add_flags(ap)
+    read_filter.add_flags(ap)
     a = ap.parse_args()
     rule = subsample.parse(ap, a)
+    a.read_filter = read_filter.parse(ap, a)
     sub_flags = ["--subsample", repr(rule[0]), "--subsample-seed", str(rule[1])] if rule is not None else []
+    sub_flags += read_filter.cli_flags(a.read_filter, a.read_stats)
     if a.child:
         return child(a)
     if not a.dir:
@@ -138,7 +149,8 @@ def main():
     shapes = [("dense", dense_bam, dense_fa, "chr20", 300, 10, n_dense),
               ("whole_genome", wg_bam, wg_fa, "chr1", 500, 500, (a.wg_length - 1000) // 500)]
     res = {"tool": "pileup_inflate_rate", "call_locations": CALL, "window_size": 100, "max_reads": 200, "dense_length": a.dense_length,
-           "wg_reads": a.wg_reads, "wg_length": a.wg_length, "subsample": list(rule) if rule is not None else None, "shapes": {}}
+           "wg_reads": a.wg_reads, "wg_length": a.wg_length, "subsample": list(rule) if rule is not None else None,
+           "read_filter": list(a.read_filter) if a.read_filter is not None else None, "shapes": {}}
     for name, bam, fa, contig, first, step, count in shapes:
         rounds = []
         for k in range(a.rounds):

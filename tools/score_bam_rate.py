@@ -94,7 +94,7 @@ def census_arms(a, bam, fa, n_loc, common):
             r = {}
             for arm, flag in (("test_bam", []), ("census", ["--record-census", "gpu"])):
                 dt, out = timed([sys.executable, os.path.join(ROOT, "main.py"), "--test_bam", bam, "--test_fasta", fa,
-                                 "--save_vcf_records_file", os.path.join(a.dir, arm + ".vcf")] + common + extra + flag)
+                                 "--save_vcf_records_file", os.path.join(a.dir, arm + ".vcf")] + common + extra + flag + a.rf_flags)
                 r[arm + "_wall_s"] = round(dt, 3)
                 r[arm + "_loop"] = loop_clock(out)
                 if flag:
@@ -128,7 +128,11 @@ def main():
     ap.add_argument("--record-census", dest="record_census", default=None, choices=["gpu"],
                     help="measure main.py --test_bam --record-census gpu beside --test_bam instead (see above)")
     ap.add_argument("--out", default=None)
+    from dl4vc_amd import read_filter
+    read_filter.add_flags(ap)
     a = ap.parse_args()
+    # the read filter goes to the converter and to main.py --test_bam alike (a --test_file run reads no BAM and gets none)
+    rf_flags = read_filter.cli_flags(read_filter.parse(ap, a), a.read_stats)
     os.makedirs(a.dir, exist_ok=True)
     t = time.time()
     bam, fa, vcf, n_loc = make_inputs(a.dir, a.length)
@@ -140,6 +144,7 @@ def main():
     if not os.path.isfile(ck):
         torch.save({"state_dict": {"module." + k: torch.from_numpy(v) for k, v in random_state_dict(DanConfig(), seed=1).items()}}, ck)
     common = ["--modelload", ck, "--sample_vcf", vcf, "--save_vcf_records", "--sites-per-launch", "4096", "--precision", a.precision] + MODEL
+    a.rf_flags = rf_flags
     if a.record_census:
         line = json.dumps(census_arms(a, bam, fa, n_loc, common))
         print(line)
@@ -155,12 +160,12 @@ def main():
         t_conv, _ = timed([sys.executable, os.path.join(ROOT, "tools", "convert_bam_single_reads.py"), "--input", bam, "--fp_vcf", vcf,
                            "--fasta-input", fa, "--output", hdf, "--max-reads", "200", "--num-processes", str(a.threads),
                            "--locations-process-step", "100000", "--max-insert-length", "10", "--max-insert-length-variant", "50",
-                           "--save-q-scores", "--save-strand"])
+                           "--save-q-scores", "--save-strand"] + [f for f in rf_flags if f != "--read-stats"])
         t_file, out_file = timed([sys.executable, os.path.join(ROOT, "main.py"), "--test_file", hdf, "--save_vcf_records_file",
                                   os.path.join(a.dir, "two_step.vcf")] + common)
         t_bam, out_bam = timed([sys.executable, os.path.join(ROOT, "main.py"), "--test_bam", bam, "--test_fasta", fa,
                                 "--save_vcf_records_file", os.path.join(a.dir, "direct.vcf")] + common +
-                               (["--inflate-device", a.inflate_device] if a.inflate_device else []))
+                               (["--inflate-device", a.inflate_device] if a.inflate_device else []) + rf_flags)
         same = open(os.path.join(a.dir, "epoch1_two_step.vcf"), "rb").read() == open(os.path.join(a.dir, "epoch1_direct.vcf"), "rb").read()
         if not same:
             sys.exit("round %d: the two paths wrote different scored VCFs" % k)
@@ -176,6 +181,7 @@ def main():
     fwd = max(r["test_file_loop"]["sites_per_s"] for r in rounds)
     loop = max(r["test_bam_loop"]["sites_per_s"] for r in rounds)
     res = {"tool": "score_bam_rate", "inflate_device": a.inflate_device, "locations": n_loc, "sites": sites, "precision": a.precision, "rounds": rounds,
+           "read_filter": rf_flags or None,
            "i_test_bam_sites_per_s_whole_process": round(sites / best_bam), "i_test_bam_sites_per_s_scoring_loop": loop,
            "ii_two_step_wall_s": [r["two_step_wall_s"] for r in rounds], "i_test_bam_wall_s": [r["test_bam_wall_s"] for r in rounds],
            "test_bam_faster_in_every_round": all(r["test_bam_wall_s"] < r["two_step_wall_s"] for r in rounds),
