@@ -252,12 +252,21 @@ __device__ __forceinline__ v4f pk_fma(v4f a, v2f k, v4f c) {        // a * k + c
     const v2f hi = __builtin_elementwise_fma((v2f){a[2], a[3]}, k, (v2f){c[2], c[3]});
     return (v4f){lo[0], lo[1], hi[0], hi[1]};
 }
+// The fragment pointers are wave-uniform (wl, wd: this wave's tile of the block) with the lane's byte offset beside them (lo): the
+// loads take the scalar-base form and the k-group's address arithmetic runs on the scalar unit.  The k-group loop is unrolled by two
+// over two fragment sets that swap roles, so that no set is copied into the other at the loop's end: a vector instruction of
+// either wave of a SIMD costs the matrix pipe its issue time, moves and address adds as much as the transform's.
+typedef const __attribute__((address_space(1))) char* gchar_ptr;
+__device__ __forceinline__ v4f frag_at(gv4f_ptr base, unsigned lo) {
+    asm volatile("" : "+s"(base));      // (pinned to scalar registers: left alone, hipcc folds the lane offset in and steps a 64-bit vector pointer)
+    return *(gv4f_ptr)((gchar_ptr)base + lo);
+}
 template <bool REM>
-__device__ __forceinline__ void conv_gemm_wino43(v4f (&acc)[MW43][6], const float* xrow, gv4f_ptr wl, const v4f (&a_first)[6],
+__device__ __forceinline__ void conv_gemm_wino43(v4f (&acc)[MW43][6], const float* xrow, gv4f_ptr wl, unsigned lo, const v4f (&a_first)[6],
                                                  [[maybe_unused]] v4f& racc, [[maybe_unused]] const float* xr, [[maybe_unused]] gv4f_ptr wd) {
-    v4f a_nxt[6], d[6];
+    v4f a0[6], a1[6], d[6];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) a_nxt[k] = a_first[k];
+    for (int k = 0; k < 6; ++k) a0[k] = a_first[k];
 #pragma unroll
     for (int i = 0; i < 6; ++i) d[i] = *(const v4f*)(xrow + 2 * i * LDS_S);
     [[maybe_unused]] v4f rb;
@@ -265,17 +274,15 @@ __device__ __forceinline__ void conv_gemm_wino43(v4f (&acc)[MW43][6], const floa
     float c1 = -1.f, c2 = 2.f, c4 = 4.f, c5 = -5.f;
     asm volatile("" : "+v"(c1), "+v"(c2), "+v"(c4), "+v"(c5));
     const v2f m1 = {c1, c1}, p2 = {c2, c2}, m2 = {-c2, -c2}, p4 = {c4, c4}, m4 = {-c4, -c4}, m5 = {c5, c5};
-    for (int g = 0; g < KGC; ++g) {
-        v4f a[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) a[k] = a_nxt[k];
+    // one k-group: a holds its fragments, a_nxt takes the next one's
+    auto kgroup = [&](int g, const v4f (&a)[6], v4f (&a_nxt)[6]) {
         const int gn = (g + 1 < KGC) ? g + 1 : g;            // last step: harmless re-read
 #pragma unroll
-        for (int k = 0; k < 6; ++k) a_nxt[k] = wl[(size_t)(k * KGC + gn) * (KGC * 64)];
+        for (int k = 0; k < 6; ++k) a_nxt[k] = frag_at(wl + (size_t)(k * KGC + gn) * (KGC * 64), lo);
         [[maybe_unused]] v4f ra[3];
         if constexpr (REM) {
 #pragma unroll
-            for (int t = 0; t < 3; ++t) ra[t] = wd[(size_t)(t * KGC + g) * (KGC * 64)];
+            for (int t = 0; t < 3; ++t) ra[t] = frag_at(wd + (size_t)(t * KGC + g) * (KGC * 64), lo);
         }
         const float* xg = xrow + g * 16;
         const float* xn = xrow + gn * 16;
@@ -310,6 +317,13 @@ __device__ __forceinline__ void conv_gemm_wino43(v4f (&acc)[MW43][6], const floa
             __builtin_amdgcn_s_setprio(0);
             if constexpr (REM) rb = *(const v4f*)(m + 1 < MW43 ? xr + (m + 1) * 2 * LDS_S + g * 16 : xr + gn * 16);
         }
+    };
+    static_assert(KGC % 2 == 0, "the k-group loop is unrolled by two");
+    for (int g = 0; g < KGC; g += 2) {
+        // (opaque once per trip: hipcc otherwise widens the offset to a pair outside the loop and adds it to the base in front of every load)
+        asm volatile("" : "+v"(lo));
+        kgroup(g, a0, a1);
+        kgroup(g + 1, a1, a0);
     }
 }
 

@@ -519,7 +519,8 @@ next_row:                                                   // (PERSIST only: ba
                 gv4f_ptr w0 = (gv4f_ptr)(wblk + W43_OFF) + wave * 64 + lane;
                 constexpr size_t KS = (size_t)KGC * (KGC * 64);
                 const v4f pre_w[6] = {w0[0], w0[KS], w0[2 * KS], w0[3 * KS], w0[4 * KS], w0[5 * KS]};
-                conv_gemm_wino43<REM>(acc, xw - 2 * LDS_S + kk * 4, w0, pre_w, rout, xs + (HALO + rp - 2) * LDS_S + kk * 4, (gv4f_ptr)(wblk + W_OFF) + wave * 64 + lane);
+                conv_gemm_wino43<REM>(acc, xw - 2 * LDS_S + kk * 4, (gv4f_ptr)(wblk + W43_OFF) + wave * 64, (unsigned)lane * 16u, pre_w, rout,
+                                      xs + (HALO + rp - 2) * LDS_S + kk * 4, (gv4f_ptr)(wblk + W_OFF) + wave * 64);
             } else if constexpr (CARRY) {
                 const v4f pre_w[4] = {pc0, pc1, pc2, pc3};
                 conv_gemm_wino(acc, xw - 2 * LDS_S + kk * 4, w_w, pre_w);

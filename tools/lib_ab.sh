@@ -2,9 +2,19 @@
 #   <build> = tree (the tree's library) or NAME for tools/ab/libdl4vc_dan_NAME.so, e.g. built from HEAD's sources with other flags:
 #     git archive HEAD dl4vc_amd/csrc include | tar -x -C /tmp/b && make -C /tmp/b/dl4vc_amd/csrc libdl4vc_dan.so CXXFLAGS='...' && cp ... tools/ab/
 #   every bench runs under its own time limit (BENCH_LIMIT seconds, default 600); the first failure ends the script
+#   TIMING_ONLY="NAME ..." names builds that compute wrong numbers on purpose (a gate: the schedule of a change without its work):
+#   for them alone a bench that ends by failing the parity check, which it does behind its result line, counts as run
 set -e
 PY=$(command -v python)
-python() { if [ "$1" = bench.py ]; then timeout -k 10 ${BENCH_LIMIT:-600} "$PY" "$@"; else "$PY" "$@"; fi; }
+ERRLOG=$(mktemp)
+python() {
+  if [ "$1" != bench.py ]; then "$PY" "$@"; return; fi
+  local rc=0
+  timeout -k 10 ${BENCH_LIMIT:-600} "$PY" "$@" 2> "$ERRLOG" || rc=$?
+  cat "$ERRLOG" >&2
+  case " $TIMING_ONLY " in *" $v "*) if [ $rc -ne 0 ] && grep -q "failed the parity check" "$ERRLOG"; then rc=0; fi ;; esac
+  return $rc
+}
 ARGS="${1:---precision 1 --sites 32768}"
 N=${2:-2}
 TAG=$(echo "$ARGS" | tr -c "a-zA-Z0-9" "_")

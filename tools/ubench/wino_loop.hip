@@ -92,9 +92,9 @@ __global__ __launch_bounds__(SEG_THREADS, 2) void k(const float* wl, float* out,
         for (int q = 0; q < 6; ++q) pre[q] = w_w[(size_t)q * KGC * (KGC * 64)];
         const float* xrow = xs + (HALO + wP0 - 2) * LDS_S + kk * 4;
         const float* xr = xs + (HALO + MPOS_SHORT + (lane & 15) - 2) * LDS_S + kk * 4;
-        gv4f_ptr w_d = (gv4f_ptr)(wl + W_OFF) + wave * 64 + lane;
+        gv4f_ptr w_d = (gv4f_ptr)(wl + W_OFF) + wave * 64;          // (wave-uniform: the lane's byte offset goes beside it)
         t0 = __builtin_amdgcn_s_memtime();
-        for (int it = 0; it < iters; ++it) conv_gemm_wino43<REM>(acc, xrow, w_w, pre, racc, xr, w_d);
+        for (int it = 0; it < iters; ++it) conv_gemm_wino43<REM>(acc, xrow, w_w - lane, (unsigned)lane * 16u, pre, racc, xr, w_d);
         t1 = __builtin_amdgcn_s_memtime();
         for (int m = 0; m < MW43; ++m) for (int q = 0; q < 6; ++q) s += acc[m][q][0] + acc[m][q][1] + acc[m][q][2] + acc[m][q][3];
         s += racc[0] + racc[1] + racc[2] + racc[3];
