@@ -24,6 +24,9 @@
 # -f (needs -r): the candidate generator walks the reads that have no MD tag against REFERENCE (--reference; whole contigs on the
 # GPU, 1 byte per base) instead of giving them no alleles; reads with an MD tag are walked by it as before.  Not passed by
 # default: without -f candidates.vcf is what it was.
+# -L (needs -r; implies -f): the candidate generator moves every insertion and deletion to its left-most placement on REFERENCE
+# before it is counted (--left-align), so that the placements of one event inside a repeat give one candidate.  Reads are not
+# realigned: the pileups show them as they are aligned.  Not passed by default.
 # -s F [-S SEED] (needs -i): every stage that reads the BAM keeps the fraction F in (0, 1] of its reads, chosen by a hash of the
 # read name as `samtools view --subsample F --subsample-seed SEED` chooses them (--subsample / --subsample-seed): candidate
 # generation and the pileup step (the converter, or main.py --test_bam with -d) see the same reads, so the calls are those of the
@@ -34,7 +37,7 @@
 # -f): candidate generation and the pileup step are filtered alike, e.g. -q 20 -F 0x704 counts the candidates over the reads the
 # pileup shows.  As with -s, give a fresh OUTDIR per filter.
 set -e
-usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-f] [-c [-y]] [-l] [-s FRACTION [-S SEED]] [-q MIN_MAPQ] [-F EXCLUDE_FLAGS] [-R REQUIRE_FLAGS]"; exit 1; }
+usage() { echo "Usage: $0 -m MODEL -o OUTDIR [-i BAM -r REFERENCE] [-b BED] [-g GPUS] [-p PROCESSES] [-d] [-z] [-f] [-L] [-c [-y]] [-l] [-s FRACTION [-S SEED]] [-q MIN_MAPQ] [-F EXCLUDE_FLAGS] [-R REQUIRE_FLAGS]"; exit 1; }
 GPUS=1
 PROCS=16
 DIRECT=0
@@ -43,12 +46,13 @@ COMPRESS=""
 CODES=""
 LOADER=""
 FROMREF=""
+LEFTALIGN=""
 SUBSAMPLE=""
 SEED=""
 MINMAPQ=""
 EXCLUDE=""
 REQUIRE=""
-while getopts "m:o:g:i:r:b:p:s:S:q:F:R:fldzcyh" opt; do
+while getopts "m:o:g:i:r:b:p:s:S:q:F:R:fLldzcyh" opt; do
   case $opt in
     m) MODEL=$OPTARG ;;
     o) OUTDIR=$OPTARG ;;
@@ -62,6 +66,7 @@ while getopts "m:o:g:i:r:b:p:s:S:q:F:R:fldzcyh" opt; do
     c) COMPRESS=gpu ;;      # candidates.hdf: pileups, record packing and chunk compression on the GPU
     y) CODES=dynamic ;;     # with -c: dynamic Huffman codes in the compressed chunks
     f) FROMREF=1 ;;         # candidate generation: reads without MD are walked against REFERENCE
+    L) LEFTALIGN=1; FROMREF=1 ;;  # candidate generation: indels are left-aligned on REFERENCE before they are counted
     s) SUBSAMPLE=$OPTARG ;; # every BAM reader keeps this fraction of the reads (--subsample)
     S) SEED=$OPTARG ;;      # with -s: the seed (--subsample-seed)
     q) MINMAPQ=$OPTARG ;;   # every BAM reader drops the reads below this mapping quality (--min-mapq)
@@ -74,6 +79,7 @@ done
 [ -z "$MODEL" ] || [ -z "$OUTDIR" ] && usage
 [ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
 [ -n "$LOADER" ] && [ "$DIRECT" = 1 ] && { echo "-l loads candidates.hdf on the GPU and -d reads no candidates.hdf: give one of them"; exit 1; }
+[ -n "$LEFTALIGN" ] && [ -z "$REFERENCE" ] && { echo "-L left-aligns the indels on the reference: give -r REFERENCE as well"; exit 1; }
 [ -n "$FROMREF" ] && [ -z "$REFERENCE" ] && { echo "-f walks the reads without MD against the reference: give -r REFERENCE as well"; exit 1; }
 [ -n "$SEED" ] && [ -z "$SUBSAMPLE" ] && { echo "-S is the seed of -s: give -s FRACTION as well"; exit 1; }
 [ -n "$SUBSAMPLE" ] && [ -z "$BAM" ] && { echo "-s thins the reads of the BAM: give -i BAM as well (a candidates.hdf holds pileups already encoded)"; exit 1; }
@@ -89,7 +95,7 @@ if [ ! -f "$OUTDIR/candidates.hdf" ] && [ ! -f "$OUTDIR/candidates.vcf" ] && [ -
   python "$SCRIPTDIR/tools/candidate_generator.py" --input "$BAM" --output "$OUTDIR/candidates.vcf" \
       --snp_min_freq 0.075 --indel_min_freq 0.02 ${BED:+--bedfile "$BED"} --keep_multialleles \
       ${INFLATE:+--inflate-device "$INFLATE"} ${MULTI:+--gpus "$GPUS"} ${FROMREF:+--reference "$REFERENCE"} \
-      "${SUBFLAGS[@]}" > "$OUTDIR/candidate_generator.log" 2>&1
+      ${LEFTALIGN:+--left-align} "${SUBFLAGS[@]}" > "$OUTDIR/candidate_generator.log" 2>&1
 fi
 if [ "$DIRECT" = 1 ]; then
   [ -f "$OUTDIR/candidates.vcf" ] && [ -n "$BAM" ] && [ -n "$REFERENCE" ] || { echo "-d needs -i BAM -r REFERENCE (and $OUTDIR/candidates.vcf, made from the BAM when absent)"; exit 1; }

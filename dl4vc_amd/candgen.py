@@ -14,6 +14,7 @@ SYMBOLS = ("cg_open", "cg_run", "cg_last_error", "cg_close", "cg_n_refs", "cg_re
            "cg_set_inflate_device", "cg_get_inflate_stats", "cg_debug_ranges", "cg_set_subsample", "cg_get_subsample_stats",
            "cg_set_read_filter", "cg_set_read_stats", "cg_get_read_stats",
            "cg_set_reference", "cg_get_reference_stats", "cg_reference_codes", "cg_reference_codes_host",
+           "cg_set_left_align", "cg_get_left_align_stats", "cg_left_align_host",
            "bz_inflate", "bz_inflate_host", "bz_status_text", "bz_last_error")
 INFLATE_DEVICES = ("gpu",)
 
@@ -57,6 +58,13 @@ class ReferenceStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class LeftAlignStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("observations", "shifted", "bases_shifted", "clamped", "not_eligible")]
+
+    def as_dict(self) -> Dict[str, int]:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class SubsampleStats(C.Structure):
     _fields_ = [("records_seen", C.c_int64), ("records_kept", C.c_int64)]
 
@@ -95,6 +103,10 @@ def load_library() -> C.CDLL:
         lib.cg_reference_codes.argtypes = [C.c_char_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64),
                                            C.c_int]
         lib.cg_reference_codes_host.argtypes = lib.cg_reference_codes.argtypes[:-1]
+        lib.cg_set_left_align.argtypes = [C.c_void_p, C.c_int]
+        lib.cg_get_left_align_stats.argtypes = [C.c_void_p, C.POINTER(LeftAlignStats)]
+        lib.cg_left_align_host.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int32)]
         lib.bz_inflate.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                    C.c_int]
         lib.bz_inflate_host.argtypes = lib.bz_inflate.argtypes[:-1]
@@ -157,12 +169,36 @@ def reference_codes(raw: bytes, linebases: int, linewidth: int, length: int, dev
     return out[:max(0, length)], other.value
 
 
+LEFT_ALIGN_INS, LEFT_ALIGN_DEL = 1, 2
+LEFT_ALIGN_ELIGIBLE, LEFT_ALIGN_CLAMPED = 1, 2
+
+
+def left_align_host(codes, kind: int, anchor_aligned: bool, anchor_pos: int, anchor_code: int, bases: Sequence[int], floor: int = 0):
+    """The left-alignment rule of ``csrc/cand_left_align.h`` for one observation, on the CPU (``cg_left_align_host``).  ``codes``:
+    the contig as a uint8 numpy array of BAM nibble codes; ``kind``: ``LEFT_ALIGN_INS`` / ``LEFT_ALIGN_DEL``; ``bases``: the
+    inserted or deleted bases as codes.  Returns ``(pos, anchor_code, bases, flags)``."""
+    import numpy as np
+    lib = load_library()
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    b = np.ascontiguousarray(bases, dtype=np.uint8)
+    out = np.zeros(len(b) + 1, np.uint8)
+    pos, flags = C.c_int64(), C.c_int32()
+    rc = lib.cg_left_align_host(codes.ctypes.data, len(codes), kind, int(bool(anchor_aligned)), anchor_pos, anchor_code, b.ctypes.data,
+                                len(b), floor, C.byref(pos), out.ctypes.data, C.byref(flags))
+    if rc != 0:
+        raise RuntimeError(lib.cg_last_error().decode())
+    return pos.value, int(out[0]), [int(v) for v in out[1:]], flags.value
+
+
 class CandidateCounter:
     """One open BAM.  ``run(subregions)`` -> ``[(region_index, tid, pos0, ref, alt, depth, count)]`` (unordered) and stats.
     ``inflate_device="gpu"`` sends each batch's BGZF blocks to the device compressed (inflate, record walk and framing there;
     needs the ``.bai``); the stats then carry ``inflate_*`` entries as well.  ``reference="ref.fa"``: a read without an MD tag is
     walked against the FASTA's bases of its contig (whole contigs, resident on the device, 1 byte per base) instead of giving
     no alleles; reads with MD are walked by their MD as before.  The stats then carry ``reference_*`` entries.
+    ``left_align=True`` (needs ``reference``): every insertion and deletion is moved to its left-most placement on the
+    reference bases before it is counted (``cg_set_left_align``), so the placements of one event in a repeat give one candidate;
+    the stats then carry ``left_align_*`` entries.
     ``subsample=(fraction, seed)``: reads are subsampled by name hash (``bamio.SampleRule``, ``cg_set_subsample``) where a read
     outside the subregion is dropped, on the host or in the device's frame kernel; the stats then carry ``subsample_records_seen``
     and ``subsample_records_kept``.  ``read_filter=(exclude, require, min_mapq)``: reads are dropped by flags and mapping quality
@@ -172,8 +208,10 @@ class CandidateCounter:
     def __init__(self, bam_path: str, bai_path: Optional[str] = None, threads: Optional[int] = None,
                  max_len_indel_allele: int = 60, snp_min_freq: float = 0.01, indel_min_freq: float = 0.01, device: int = 0,
                  inflate_device: Optional[str] = None, reference: Optional[str] = None, subsample=None,
-                 read_filter=None, read_stats: bool = False):
+                 read_filter=None, read_stats: bool = False, left_align: bool = False):
         from .bamio import ReadFilter, SampleRule
+        if left_align and reference is None:
+            raise ValueError("left_align needs reference: left-alignment is defined by the reference bases")
         self.subsample = SampleRule.of(subsample)
         self.read_filter = ReadFilter.of(read_filter)
         self.collects = bool(read_stats) or self.read_filter is not None
@@ -198,6 +236,11 @@ class CandidateCounter:
             msg = self.lib.cg_last_error().decode()
             self.close()
             raise RuntimeError("cg_set_reference: %s" % msg)
+        self.left_align = bool(left_align)
+        if self.left_align and self.lib.cg_set_left_align(h, 1) != 0:
+            msg = self.lib.cg_last_error().decode()
+            self.close()
+            raise RuntimeError("cg_set_left_align: %s" % msg)
         if self.subsample is not None and self.lib.cg_set_subsample(h, self.subsample.fraction, self.subsample.seed) != 0:
             msg = self.lib.cg_last_error().decode()
             self.close()
@@ -229,6 +272,10 @@ class CandidateCounter:
             rst = ReferenceStats()
             self.lib.cg_get_reference_stats(self.h, C.byref(rst))
             stats.update(("reference_" + k, v) for k, v in rst.as_dict().items())
+        if self.left_align:
+            lst = LeftAlignStats()
+            self.lib.cg_get_left_align_stats(self.h, C.byref(lst))
+            stats.update(("left_align_" + k, v) for k, v in lst.as_dict().items())
         if self.subsample is not None:
             sst = SubsampleStats()
             self.lib.cg_get_subsample_stats(self.h, C.byref(sst))

@@ -196,7 +196,8 @@ def generate(bam_path: str, output: str, contigs: Optional[str] = None, bedfile:
              keep_contig_chr: bool = False, chunk_size: int = 1000, threads: Optional[int] = None, snp_min_freq: float = 0.01,
              indel_min_freq: float = 0.01, keep_multialleles: bool = False, max_len_indel_allele: int = 60,
              device: int = 0, inflate_device: Optional[str] = None, shard: Optional[Tuple[int, int]] = None,
-             reference: Optional[str] = None, subsample=None, read_filter=None, read_stats: bool = False) -> dict:
+             reference: Optional[str] = None, subsample=None, read_filter=None, read_stats: bool = False,
+             left_align: bool = False) -> dict:
     """Writes ``output`` and returns the run's summary (counts of reads by kind, candidates, times).  ``read_filter=(exclude,
     require, min_mapq)``: reads are dropped by flags and mapping quality in front of every count (``bamio.ReadFilter``); with it or
     with ``read_stats`` the summary carries the read census (``read_*`` entries, ``read_filter.census_of``).  ``subsample=(fraction,
@@ -204,16 +205,20 @@ def generate(bam_path: str, output: str, contigs: Optional[str] = None, bedfile:
     ``subsample_records_kept`` in the summary).  ``inflate_device="gpu"``
     inflates and frames the BAM's records on the device (needs the ``.bai``) and adds the ``inflate_*`` figures to the summary.
     ``reference="ref.fa"`` walks the reads that have no MD tag against the FASTA's bases (``reference_*`` figures in the summary).
+    ``left_align=True`` (needs ``reference``): insertions and deletions are moved to their left-most placement on the reference
+    bases before they are counted (``left_align_*`` figures in the summary; ``merge_parts`` sums them over shards).
     ``shard=(g, n)``: only the g-th of n contiguous ranges of the groups is counted, and instead of ``output`` the shard's
     unsorted body lines go to ``part_path(output, g)`` with its summary and the header beside them (``merge_parts`` makes
     ``output`` of the n parts)."""
     from .candgen import CandidateCounter, MAX_ALLELE_LEN
+    if left_align and reference is None:
+        raise ValueError("left_align needs reference: left-alignment is defined by the reference bases")
     if max_len_indel_allele > MAX_ALLELE_LEN:
         raise ValueError("--max_len_indel_allele %d exceeds the allele key's limit of %d bases" % (max_len_indel_allele,
                                                                                                   MAX_ALLELE_LEN))
     with CandidateCounter(bam_path, threads=threads, max_len_indel_allele=max_len_indel_allele, snp_min_freq=snp_min_freq,
                           indel_min_freq=indel_min_freq, device=device, inflate_device=inflate_device, reference=reference,
-                          subsample=subsample, read_filter=read_filter, read_stats=read_stats) as cc:
+                          subsample=subsample, read_filter=read_filter, read_stats=read_stats, left_align=left_align) as cc:
         regions = contig_regions(cc.references, cc.lengths, contigs, bedfile, keep_contig_chr)
         logging.info("Examining %d regions in the bamfile", len(regions))
         subregions = split_subregions(regions, chunk_size * 1000)

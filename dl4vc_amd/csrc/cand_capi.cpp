@@ -11,6 +11,9 @@
 // With cg_set_reference() a read without MD is walked against the FASTA's bases of its contig: batch_refs() makes the contigs a
 // batch touches resident (load_contig(): the raw byte range read with fasta_native.h's index, uploaded, and turned into one code
 // per base by reference_codes_kernel) and hands the kernels one RefDesc per subregion, on either record path.
+//
+// With cg_set_left_align() (which needs the reference) the kernels move every insertion and deletion to its left-most placement
+// on those bases before it is counted (cand_left_align.h); finish_batch() sums the counters of the batches.
 #include "../../include/dl4vc_candgen.h"
 #include "bam_frame.h"
 #include "bam_native.h"
@@ -74,6 +77,9 @@ struct cg_handle {   // (members are destroyed last to first: the stream outlive
     std::unique_ptr<fastan::Fasta> fasta;
     std::map<int32_t, dev::Buffer> contigs;     // tid -> exactly header.lengths[tid] bytes
     cg_reference_stats rst{};
+    // left-alignment of indels (cg_set_left_align): needs the reference source
+    bool left_align = false;
+    cg_left_align_stats lst{};
     // read subsampling (cg_set_subsample)
     bamn::frame::SampleRule sample{0, 0};
     cg_subsample_stats sst{};
@@ -220,9 +226,15 @@ int finish_batch(cg_handle* h, const cg_region* regions, int64_t b0, uint64_t n_
     const uint8_t* status = nullptr;
     uint64_t n_out = 0, n_events = 0, n_unique = 0;
     cand::BatchTimes bt{};
+    uint64_t la[cand::LA_COUNTERS];
     if (cand::run_batch(h->ws.get(), n_reads, n_subs, cov, h->opt.max_len_indel_allele, h->opt.snp_min_freq, h->opt.indel_min_freq,
-                        h->stream, &dc, &n_out, &status, &n_events, &n_unique, &bt, &msg))
+                        h->left_align, h->stream, &dc, &n_out, &status, &n_events, &n_unique, la, &bt, &msg))
         return fail(-2, "device: %s", msg);
+    h->lst.observations += (int64_t)la[cand::LA_SEEN];
+    h->lst.shifted += (int64_t)la[cand::LA_SHIFTED];
+    h->lst.bases_shifted += (int64_t)la[cand::LA_BASES];
+    h->lst.clamped += (int64_t)la[cand::LA_CLAMPED];
+    h->lst.not_eligible += (int64_t)la[cand::LA_NOT_ELIGIBLE];
     st.device_ms += bt.device_ms;
     st.reads += (int64_t)n_reads;
     for (uint64_t r = 0; r < n_reads; ++r) {
@@ -436,6 +448,7 @@ int cg_run(cg_handle_t* h, const cg_region* regions, int64_t n_regions, const cg
         cg_stats st{};
         h->ist = cg_inflate_stats{};
         h->rst.reads = 0;
+        h->lst = cg_left_align_stats{};
         h->sst = cg_subsample_stats{};
         h->census = bamn::frame::Census{};
         h->out.clear();
@@ -519,6 +532,9 @@ int cg_set_reference(cg_handle_t* h, const char* fasta_path) {
     return capi::guarded(g_err, "cg_set_reference", [&] {
         if (!h) return fail(-1, "cg_set_reference: null handle");
         std::unique_ptr<fastan::Fasta> fa;
+        if (h->left_align && !(fasta_path && *fasta_path))
+            return fail(-1, "cg_set_reference: left-alignment is on and takes its bases from the reference: switch it off first "
+                        "(cg_set_left_align(h, 0))");
         if (fasta_path && *fasta_path) {
             std::string err;
             fa.reset(new fastan::Fasta());
@@ -535,6 +551,23 @@ int cg_set_reference(cg_handle_t* h, const char* fasta_path) {
 int cg_get_reference_stats(const cg_handle_t* h, cg_reference_stats* out) {
     if (!h || !out) return fail(-1, "cg_get_reference_stats: null argument");
     *out = h->rst;
+    return 0;
+}
+
+int cg_set_left_align(cg_handle_t* h, int on) {
+    return capi::guarded(g_err, "cg_set_left_align", [&] {
+        if (!h) return fail(-1, "cg_set_left_align: null handle");
+        if (on && !h->fasta)
+            return fail(-1, "cg_set_left_align: left-alignment is defined by the reference bases and no reference is set: call "
+                        "cg_set_reference first");
+        h->left_align = on != 0;
+        return 0;
+    });
+}
+
+int cg_get_left_align_stats(const cg_handle_t* h, cg_left_align_stats* out) {
+    if (!h || !out) return fail(-1, "cg_get_left_align_stats: null argument");
+    *out = h->lst;
     return 0;
 }
 

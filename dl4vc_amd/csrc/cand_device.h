@@ -51,6 +51,9 @@ struct DevCand {
     uint64_t w[4];
 };
 
+// left-alignment (cg_set_left_align): what run_batch counts over the indel observations that were counted as alleles
+enum { LA_SEEN = 0, LA_SHIFTED, LA_BASES, LA_CLAMPED, LA_NOT_ELIGIBLE, LA_COUNTERS };
+
 struct Workspace;     // device buffers, grown on demand (cand_kernels.hip)
 
 struct BatchTimes {
@@ -62,6 +65,8 @@ void workspace_destroy(Workspace* ws);
 // Runs one batch whose framed records are already on the device (ws buffers from upload()).  Returns 0 or a negative code
 // with msg set.  out / n_out: survivors in a host array owned by the workspace; status: one byte per read, host.
 // refs: one RefDesc per subregion (reads without MD are walked against them), or nullptr (such reads are ST_NO_MD).
+// left_align (needs refs): insertions and deletions are moved to their left-most placement on those bases before they are
+// counted (cand_left_align.h); la_counts[LA_COUNTERS] receives the batch's counters (zero with the option off).
 int upload(Workspace* ws, const uint8_t* recs, uint64_t rec_bytes, const ReadMeta* meta, uint64_t n_reads,
            const SubDesc* subs, const RefDesc* refs, uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg);
 // The same for records and meta that are already on the device (the BGZF path, bgzf_device.h): they are used in place and must
@@ -69,8 +74,8 @@ int upload(Workspace* ws, const uint8_t* recs, uint64_t rec_bytes, const ReadMet
 int upload_device(Workspace* ws, const uint8_t* recs_dev, const ReadMeta* meta_dev, const SubDesc* subs, const RefDesc* refs,
                   uint32_t n_subs, int64_t cov_len, hipStream_t stream, const char** msg);
 int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len, int max_len, double snp_min, double indel_min,
-              hipStream_t stream, const DevCand** out, uint64_t* n_out, const uint8_t** status, uint64_t* n_events,
-              uint64_t* n_unique, BatchTimes* t, const char** msg);
+              bool left_align, hipStream_t stream, const DevCand** out, uint64_t* n_out, const uint8_t** status, uint64_t* n_events,
+              uint64_t* n_unique, uint64_t* la_counts, BatchTimes* t, const char** msg);
 
 // Reference bases (cand_reference.h has the rule): raw_dev[0, raw_len) -> out_dev[0, length), on the stream.  counts_dev[0]
 // gains the bytes outside the alphabet, counts_dev[1] takes the minimum with the first base that is a line end, '>' or past

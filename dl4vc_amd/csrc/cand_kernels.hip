@@ -18,8 +18,11 @@
 // BAM alphabet) is marked malformed and gives no alleles.  Every byte read is bounded by the read's framed length.
 // A read without MD gives coverage and no alleles, unless the batch carries the reference bases of its contig (cg_set_reference):
 // then the same walk takes them from there (RefSeq below; reference_codes_kernel makes them of the FASTA's bytes).
+// With cg_set_left_align an insertion or deletion is moved to its left-most placement on those bases before its key is made
+// (cand_left_align.h has the rule): close_run applies it in both passes, so the count pass's offsets hold in the emit pass.
 #include "bam_frame.h"
 #include "cand_device.h"
+#include "cand_left_align.h"
 #include "cand_reference.h"
 #include "device_buffer.h"
 
@@ -140,6 +143,7 @@ struct Sink {
     uint64_t* snp;
     IndelKey* indel;
     uint32_t n_snp, n_indel;
+    uint32_t la[LA_COUNTERS];   // left-alignment, of the indels counted (LA_* of cand_device.h)
 };
 
 struct Pair {
@@ -156,12 +160,16 @@ struct Walk {
     uint32_t sub;
     int max_len;
     bool del_dropped;
+    const uint8_t* la_codes;   // the contig's codes when indels are left-aligned, else nullptr
+    int64_t la_length;
 
     __device__ int read_code(int q) const { return (q & 1) ? (seq[q >> 1] & 0xf) : (seq[q >> 1] >> 4); }
 
     // md: the read's reference source at its start (Md or RefSeq), taken by value: each run walks it from the beginning.
     // dry = true: only the walk of the source, returning the last pair (the anchor of a deletion run at the first pair)
-    template <class Ref>
+    // LA: indels are left-aligned on la_codes before they are counted (a kernel instantiation of its own, so that the walk
+    // without the option is the code it was)
+    template <bool LA, class Ref>
     __device__ bool run(Ref md, bool dry, Pair last_pair, Sink& out, Pair* last_out) const {
         int32_t rp = pos;
         int qp = 0;
@@ -169,11 +177,26 @@ struct Walk {
         int run_kind = -1, run_len = 0;
         int32_t run_pos = 0;
         uint64_t run_w[4] = {0, 0, 0, 0};
-        bool first = true;
+        bool first = true, run_aligned = false;
         auto close_run = [&]() {
             if (run_kind < 0) return;
-            const bool keep = run_len <= max_len && run_pos >= lo && run_pos <= hi && !(run_kind == OP_D && del_dropped);
+            bool keep = run_len <= max_len && !(run_kind == OP_D && del_dropped);
+            int la_flags = 0;
+            int64_t la_k = 0;
+            if (LA && keep) {
+                la_k = lal::align(run_kind == OP_I ? lal::INS : lal::DEL, run_aligned, run_w, run_len - 1, la_codes, la_length, run_pos,
+                                  pos, &la_flags);
+                run_pos -= (int32_t)la_k;
+            }
+            keep = keep && run_pos >= lo && run_pos <= hi;
             if (keep) {
+                if (LA) {
+                    ++out.la[LA_SEEN];
+                    out.la[LA_SHIFTED] += la_k > 0;
+                    out.la[LA_BASES] += (uint32_t)la_k;
+                    out.la[LA_CLAMPED] += (la_flags & lal::CLAMPED) != 0;
+                    out.la[LA_NOT_ELIGIBLE] += !(la_flags & lal::ELIGIBLE);
+                }
                 if (out.indel) {
                     IndelKey k;
                     k.w[0] = ((uint64_t)sub << 40) | ((uint64_t)(uint32_t)run_pos << 8) |
@@ -189,8 +212,9 @@ struct Walk {
             if (run_len < KEY_BASES) run_w[run_len >> 4] |= (uint64_t)code << (60 - 4 * (run_len & 15));
             ++run_len;
         };
-        auto start_run = [&](int kind, const Pair& anchor) {
+        auto start_run = [&](int kind, const Pair& anchor, bool stand_in) {
             run_kind = kind;
+            run_aligned = anchor.kind == OP_M && !stand_in;
             run_pos = anchor.pos;
             run_len = 0;
             run_w[0] = run_w[1] = run_w[2] = run_w[3] = 0;
@@ -223,7 +247,7 @@ struct Walk {
                     if (!dry && run_kind == OP_I) close_run();
                     const int code = md.del();
                     if (md.bad) return false;
-                    if (!dry && run_kind != OP_D) start_run(OP_D, first ? last_pair : prev);
+                    if (!dry && run_kind != OP_D) start_run(OP_D, first ? last_pair : prev, first);
                     if (!dry) push_base(code);
                     prev = Pair{OP_D, rp + i, code};
                     first = false;
@@ -234,7 +258,7 @@ struct Walk {
                     md.end_del();
                     if (md.bad) return false;
                     if (!dry && run_kind == OP_D) close_run();
-                    if (!dry && run_kind != OP_I) start_run(OP_I, prev);
+                    if (!dry && run_kind != OP_I) start_run(OP_I, prev, false);
                     if (!dry) push_base(read_code(qp + i));
                     prev = Pair{OP_I, 0, 0};
                 }
@@ -250,19 +274,19 @@ struct Walk {
     }
 
     // the dry run for a deletion run at the first pair, then the run that counts or emits
-    template <class Ref>
+    template <bool LA, class Ref>
     __device__ bool run_read(const Ref& src, Sink& out) const {
         Pair last{-1, 0, 0};
-        Sink dry{nullptr, nullptr, 0, 0};
+        Sink dry{nullptr, nullptr, 0, 0, {}};
         if ((ld32(cig + 4 * k0) & 0xf) == OP_D) {
-            if (!run(src, true, last, dry, &last)) return false;
+            if (!run<false>(src, true, last, dry, &last)) return false;
         }
-        return run(src, false, last, out, nullptr);
+        return run<LA>(src, false, last, out, nullptr);
     }
 };
 
 // Shared by both passes: frames the read (again, on the device), adds its coverage events (count pass), and walks it.
-template <bool EMIT>
+template <bool EMIT, bool LA>
 __device__ void process_read(const uint8_t* __restrict__ buf, const ReadMeta& m, const SubDesc* __restrict__ subs,
                              const RefDesc* __restrict__ refs, int max_len, int* __restrict__ cov, Sink& out, uint8_t& status) {
     const uint8_t* b = buf + m.off;
@@ -329,30 +353,42 @@ __device__ void process_read(const uint8_t* __restrict__ buf, const ReadMeta& m,
     Walk w;
     w.cig = cig; w.seq = b + seq_off; w.n_cig = n_cig; w.k0 = k0; w.k1 = k1; w.pos = pos;
     w.lo = sd.start; w.hi = sd.end; w.sub = m.sub; w.max_len = max_len; w.del_dropped = dd;
+    w.la_codes = nullptr; w.la_length = 0;
+    if (LA) {                      // (run_batch launches this instantiation only with refs)
+        const RefDesc rd = refs[m.sub];
+        w.la_codes = rd.codes; w.la_length = rd.length;
+    }
     bool ok;
     if (from_ref) {
         const RefDesc rd = refs[m.sub];
-        ok = w.run_read(RefSeq{rd.codes, rd.length, (int64_t)pos, false}, out);
+        ok = w.run_read<LA>(RefSeq{rd.codes, rd.length, (int64_t)pos, false}, out);
     } else {
-        ok = w.run_read(Md{b + m.md_off, m.md_len, 0, 0, false, false}, out);
+        ok = w.run_read<LA>(Md{b + m.md_off, m.md_len, 0, 0, false, false}, out);
     }
-    if (!ok) { out.n_snp = out.n_indel = 0; return; }
+    if (!ok) { out = Sink{out.snp, out.indel, 0, 0, {}}; return; }
     status = (uint8_t)((dd ? ST_OK | ST_DEL_DROPPED : ST_OK) | flag);
 }
 
+template <bool LA>
 __global__ void count_kernel(const uint8_t* __restrict__ buf, const ReadMeta* __restrict__ meta, uint64_t n,
-                             const SubDesc* __restrict__ subs, const RefDesc* __restrict__ refs, int max_len, int* __restrict__ cov,
-                             uint32_t* __restrict__ n_snp, uint32_t* __restrict__ n_indel, uint8_t* __restrict__ status) {
+                             const SubDesc* __restrict__ subs, const RefDesc* __restrict__ refs, int max_len,
+                             int* __restrict__ cov, uint32_t* __restrict__ n_snp, uint32_t* __restrict__ n_indel,
+                             uint8_t* __restrict__ status, unsigned long long* __restrict__ la_counts) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
-    Sink s{nullptr, nullptr, 0, 0};
+    Sink s{nullptr, nullptr, 0, 0, {}};
     uint8_t st;
-    process_read<false>(buf, meta[r], subs, refs, max_len, cov, s, st);
+    process_read<false, LA>(buf, meta[r], subs, refs, max_len, cov, s, st);
     n_snp[r] = s.n_snp;
     n_indel[r] = s.n_indel;
     status[r] = st;
+    // (integer adds: exact in any order; only reads with a counted indel get here, and only with the option on)
+    if (LA && s.la[LA_SEEN])
+        for (int j = 0; j < LA_COUNTERS; ++j)
+            if (s.la[j]) atomicAdd(la_counts + j, (unsigned long long)s.la[j]);
 }
 
+template <bool LA>
 __global__ void emit_kernel(const uint8_t* __restrict__ buf, const ReadMeta* __restrict__ meta, uint64_t n,
                             const SubDesc* __restrict__ subs, const RefDesc* __restrict__ refs, int max_len,
                             const uint32_t* __restrict__ snp_off, const uint32_t* __restrict__ indel_off,
@@ -360,9 +396,9 @@ __global__ void emit_kernel(const uint8_t* __restrict__ buf, const ReadMeta* __r
                             IndelKey* __restrict__ indel_keys) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n || (n_snp[r] == 0 && n_indel[r] == 0)) return;
-    Sink s{snp_keys + snp_off[r], indel_keys + indel_off[r], 0, 0};
+    Sink s{snp_keys + snp_off[r], indel_keys + indel_off[r], 0, 0, {}};
     uint8_t st;
-    process_read<true>(buf, meta[r], subs, refs, max_len, nullptr, s, st);
+    process_read<true, LA>(buf, meta[r], subs, refs, max_len, nullptr, s, st);
 }
 
 __device__ inline void keep_if(const SubDesc* subs, const int* depth, uint32_t sub, int32_t pos, uint32_t count, bool snp,
@@ -437,7 +473,7 @@ struct IndelDecomposer {
 
 struct Workspace {
     dev::Buffer recs, meta, subs, refs, cov, depth, n_snp, n_indel, snp_off, indel_off, status, snp_keys, snp_sorted, indel_keys, indel_sorted,
-        snp_unique, snp_counts, indel_unique, indel_counts, scalars, cands, temp;
+        snp_unique, snp_counts, indel_unique, indel_counts, scalars, la_counts, cands, temp;
     std::vector<uint8_t> h_status;
     std::vector<DevCand> h_cands;
     const uint8_t* recs_p = nullptr;      // the batch's records and their meta: ws->recs / ws->meta after upload(), the
@@ -495,10 +531,12 @@ int upload_device(Workspace* ws, const uint8_t* recs_dev, const ReadMeta* meta_d
 }
 
 int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len, int max_len, double snp_min, double indel_min,
-              hipStream_t stream, const DevCand** out, uint64_t* n_out, const uint8_t** status, uint64_t* n_events,
-              uint64_t* n_unique, BatchTimes* t, const char** msg) {
+              bool left_align, hipStream_t stream, const DevCand** out, uint64_t* n_out, const uint8_t** status, uint64_t* n_events,
+              uint64_t* n_unique, uint64_t* la_counts, BatchTimes* t, const char** msg) {
     (void)n_subs;
     *n_out = 0; *n_events = 0; *n_unique = 0;
+    for (int j = 0; j < LA_COUNTERS; ++j) la_counts[j] = 0;
+    if (left_align && !ws->refs_p) { *msg = "left-alignment needs the batch's reference bases"; return -1; }
     ws->h_status.assign(n_reads, 0);
     *status = ws->h_status.data();
     HIP_CHECK_MSG(hipEventRecord(ws->ev0, stream));
@@ -512,12 +550,15 @@ int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len,
     HIP_CHECK_MSG(ws->scalars.ensure(16 * sizeof(uint32_t)));
     uint32_t* sc = ws->scalars.as<uint32_t>();     // [0] snp runs, [1] indel runs, [2] survivors
     HIP_CHECK_MSG(hipMemsetAsync(sc, 0, 16 * sizeof(uint32_t), stream));
+    HIP_CHECK_MSG(ws->la_counts.ensure(LA_COUNTERS * sizeof(unsigned long long)));
+    if (left_align) HIP_CHECK_MSG(hipMemsetAsync(ws->la_counts.p, 0, LA_COUNTERS * sizeof(unsigned long long), stream));
     const int TB = 256;
     const unsigned grid = (unsigned)((n_reads + TB - 1) / TB);
     if (n_reads) {
-        hipLaunchKernelGGL(count_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs_p, ws->meta_p,
-                           n_reads, ws->subs.as<const SubDesc>(), ws->refs_p, max_len, ws->cov.as<int>(), ws->n_snp.as<uint32_t>(),
-                           ws->n_indel.as<uint32_t>(), ws->status.as<uint8_t>());
+        hipLaunchKernelGGL(left_align ? count_kernel<true> : count_kernel<false>, dim3(grid), dim3(TB), 0, stream, ws->recs_p, ws->meta_p,
+                           n_reads, ws->subs.as<const SubDesc>(), ws->refs_p, max_len, ws->cov.as<int>(),
+                           ws->n_snp.as<uint32_t>(), ws->n_indel.as<uint32_t>(), ws->status.as<uint8_t>(),
+                           ws->la_counts.as<unsigned long long>());
         HIP_CHECK_MSG(hipGetLastError());
     }
     // per-read output offsets (exclusive scans; the element past the last read carries the total)
@@ -554,7 +595,7 @@ int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len,
     HIP_CHECK_MSG(ws->indel_counts.ensure((ni + 1) * 4));
     HIP_CHECK_MSG(ws->cands.ensure((ns + ni + 1) * sizeof(DevCand)));
     if (ns + ni > 0) {
-        hipLaunchKernelGGL(emit_kernel, dim3(grid), dim3(TB), 0, stream, ws->recs_p, ws->meta_p,
+        hipLaunchKernelGGL(left_align ? emit_kernel<true> : emit_kernel<false>, dim3(grid), dim3(TB), 0, stream, ws->recs_p, ws->meta_p,
                            n_reads, ws->subs.as<const SubDesc>(), ws->refs_p, max_len, ws->snp_off.as<const uint32_t>(),
                            ws->indel_off.as<const uint32_t>(), ws->n_snp.as<const uint32_t>(), ws->n_indel.as<const uint32_t>(),
                            ws->snp_keys.as<uint64_t>(), ws->indel_keys.as<IndelKey>());
@@ -596,7 +637,10 @@ int run_batch(Workspace* ws, uint64_t n_reads, uint32_t n_subs, int64_t cov_len,
     uint32_t hs[3];
     HIP_CHECK_MSG(hipMemcpyAsync(hs, sc, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     if (n_reads) HIP_CHECK_MSG(hipMemcpyAsync(ws->h_status.data(), ws->status.p, n_reads, hipMemcpyDeviceToHost, stream));
+    unsigned long long la[LA_COUNTERS] = {};
+    if (left_align) HIP_CHECK_MSG(hipMemcpyAsync(la, ws->la_counts.p, sizeof la, hipMemcpyDeviceToHost, stream));
     HIP_CHECK_MSG(hipStreamSynchronize(stream));
+    for (int j = 0; j < LA_COUNTERS; ++j) la_counts[j] = la[j];
     *n_unique = (uint64_t)hs[0] + hs[1];
     ws->h_cands.resize(hs[2]);
     if (hs[2]) {

@@ -1,11 +1,13 @@
 // C ABI of the reference-base conversion (include/dl4vc_candgen.h): the raw bytes of one FASTA contig in host memory, converted
 // by the loop over the rule of cand_reference.h on the CPU (cg_reference_codes_host) or by reference_codes_kernel on the GPU
-// (cg_reference_codes).  Also the library's error text (cg_last_error), which cand_capi.cpp shares.  Every entry catches what it
+// (cg_reference_codes), and of the left-alignment rule of cand_left_align.h for one observation on the CPU
+// (cg_left_align_host).  Also the library's error text (cg_last_error), which cand_capi.cpp shares.  Every entry catches what it
 // throws; an index that does not describe the bytes is an error code.
 //
 // With -DCG_REFERENCE_HOST_ONLY a plain C++ compiler builds the host entry alone (tools/asan_cand_reference.sh runs it under
 // sanitizers).
 #include "../../include/dl4vc_candgen.h"
+#include "cand_left_align.h"
 #include "cand_reference.h"
 #include "capi_shell.h"
 #ifndef CG_REFERENCE_HOST_ONLY
@@ -53,6 +55,32 @@ int cg_reference_codes_host(const uint8_t* raw, uint64_t raw_len, int64_t lineba
         if (const int rc = check_arguments("cg_reference_codes", raw, raw_len, linebases, linewidth, length, out, n_other)) return rc;
         const uint64_t bad = cand::refc::codes_host(raw, raw_len, linebases, linewidth, length, out, n_other);
         return bad == cand::refc::NONE ? 0 : broken("cg_reference_codes", bad, linebases, linewidth);
+    });
+}
+
+int cg_left_align_host(const uint8_t* codes, int64_t length, int32_t kind, int32_t anchor_aligned, int64_t anchor_pos, int32_t anchor_code,
+                       const uint8_t* bases, int32_t n_bases, int64_t floor, int64_t* pos_out, uint8_t* bases_out, int32_t* flags) {
+    return capi::guarded(cand::last_error(), "cg_left_align_host", [&] {
+        namespace L = cand::lal;
+        if (!pos_out || !bases_out || !flags || (length > 0 && !codes) || (n_bases > 0 && !bases))
+            return ref_fail(-1, "cg_left_align_host: null argument");
+        if (length < 0 || n_bases < 0) return ref_fail(-1, "cg_left_align_host: negative length");
+        *pos_out = anchor_pos;
+        *flags = 0;
+        bases_out[0] = (uint8_t)anchor_code;
+        for (int32_t j = 0; j < n_bases; ++j) bases_out[j + 1] = bases[j];
+        bool codes_ok = (anchor_code & ~0xf) == 0;
+        for (int32_t j = 0; j < n_bases; ++j) codes_ok = codes_ok && bases[j] < 16;
+        if (n_bases > L::MAX_L || !codes_ok) return 0;           // no key holds it: not eligible, returned as it came
+        uint64_t w[4] = {0, 0, 0, 0};
+        L::put_code(w, 0, anchor_code);
+        for (int32_t j = 0; j < n_bases; ++j) L::put_code(w, j + 1, bases[j]);
+        int fl = 0;
+        const int64_t k = L::align(kind, anchor_aligned != 0, w, n_bases, codes, length, anchor_pos, floor, &fl);
+        *pos_out = anchor_pos - k;
+        *flags = fl;
+        for (int32_t j = 0; j <= n_bases; ++j) bases_out[j] = (uint8_t)L::code_at(w, j);
+        return 0;
     });
 }
 

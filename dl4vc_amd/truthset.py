@@ -15,6 +15,12 @@ are compatible"), restated from the manual:
 * both inputs must be position-sorted (contig order from ``##contig`` lines, else from first appearance); an unsorted input
   is refused, never paired.
 
+With ``left_align`` (``--left-align REF.fa`` of the tools) the simple indels of BOTH inputs are left-aligned on the FASTA before
+their keys are made (``left_align_record``: the rule of ``csrc/cand_left_align.h`` with floor 0, restated here in Python), so a
+record placed to the right inside a repeat pairs with its left-aligned twin.  Only the keys move: every output line is still its
+input's line, byte for byte.  MNPs, complex alleles and multi-allelic records are compared as they are; this is no
+haplotype-aware comparison.
+
 UNPINNED: there is no bcftools here, so the pairing rule is checked against hand-written cases only.
 The counting, the curve, the F1 search and the printing are pinned to the reference's own code by
 ``tools/gen_golden_evaluation.py``.
@@ -128,20 +134,121 @@ def _key(rec: Record):
     return rec[1], rec[2], rec[3], alts if len(alts) < 2 else tuple(sorted(set(alts)))
 
 
+# --- left-alignment ------------------------------------------------------------------------------------------------------------
+LA_INS, LA_DEL = 1, 2
+
+
+def left_align_letters(ref_at: Callable[[int], str], length: int, kind: int, a: int, anchor: str, bases: str, floor: int = 0,
+                       anchor_aligned: bool = True) -> Tuple[int, str, str, bool, bool]:
+    """The left-alignment rule for one indel observation, on letters: ``ref_at(p)`` is the contig's letter at 0-based ``p`` as
+    the allele walk sees it (upper case, N for a byte outside the alphabet) for ``0 <= p < length``; ``a`` / ``anchor`` the anchor
+    position and base; ``bases`` the inserted read bases (``LA_INS``) or the deleted reference bases (``LA_DEL``); ``floor`` the
+    read's POS.  Returns ``(pos, anchor, bases, eligible, clamped)``: the left-most placement, whether the observation was
+    eligible at all (else it comes back as it went in), and whether the shift stopped at ``floor`` where floor 0 would have let it
+    go on.  The restatement the C++ rule (``csrc/cand_left_align.h``) is held to; it rotates the string where that indexes."""
+    L = len(bases)
+    acgt = set("ACGT")
+    same = (a, anchor, bases, False, False)
+    if not anchor_aligned or L < 1 or kind not in (LA_INS, LA_DEL) or not 0 <= a < length:
+        return same
+    if anchor not in acgt or any(c not in acgt for c in bases) or ref_at(a) != anchor:
+        return same
+    if kind == LA_DEL and (a + L >= length or any(ref_at(a + 1 + j) != bases[j] for j in range(L))):
+        return same
+    floor = max(0, floor)
+    k, s, clamped = 0, bases, False
+    while True:
+        p = a - k
+        if p - 1 < 0 or ref_at(p - 1) not in acgt:
+            break
+        if ref_at(p) != (ref_at(p + L) if kind == LA_DEL else s[-1]):
+            break
+        if p - 1 < floor:
+            clamped = True
+            break
+        k += 1
+        s = s[-1] + s[:-1]
+    p = a - k
+    if kind == LA_DEL:
+        s = "".join(ref_at(p + 1 + j) for j in range(L))
+    return p, ref_at(p), s, True, clamped
+
+
+class _ContigLetters:
+    """``ref_at`` over one contig of a ``bamio.FastaFile``, fetched in blocks."""
+    BLOCK = 1024
+
+    def __init__(self, fasta, chrom: str):
+        self.fasta, self.chrom, self.blocks = fasta, chrom, {}
+        self.length = fasta.get_reference_length(chrom)
+
+    def __call__(self, p: int) -> str:
+        b = p // self.BLOCK
+        if b not in self.blocks:
+            if len(self.blocks) > 64:
+                self.blocks.clear()
+            raw = self.fasta.fetch(self.chrom, b * self.BLOCK, (b + 1) * self.BLOCK).upper()
+            self.blocks[b] = "".join(c if c in "=ACMGRSVTWYHKDBN" else "N" for c in raw)
+        return self.blocks[b][p - b * self.BLOCK]
+
+
+def left_align_record(fasta, chrom: str, pos: int, ref: str, alt):
+    """``(pos, ref, alt)`` of a VCF record (1-based ``pos``) with a simple indel moved to its left-most placement on ``fasta`` (a
+    ``bamio.FastaFile``): the rule of ``left_align_letters`` with floor 0.  Simple means one ALT allele, one of REF / ALT of
+    length 1, and both starting with the same base.  Everything else passes through untouched: SNPs, MNPs, complex alleles,
+    multi-allelic records (``alt`` a tuple of several, or a string with a comma), a contig the FASTA lacks, and an indel whose
+    bases are not ACGT or whose REF differs from the FASTA.  ``alt`` comes back in the form it came in."""
+    one = alt[0] if isinstance(alt, (tuple, list)) and len(alt) == 1 else alt
+    if not isinstance(one, str) or "," in one or not ref or not one or ref[0].upper() != one[0].upper():
+        return pos, ref, alt
+    if not ((len(ref) == 1) != (len(one) == 1)):
+        return pos, ref, alt
+    cache = fasta.__dict__.setdefault("_left_align_contigs", {})
+    if chrom not in cache:
+        try:
+            cache[chrom] = _ContigLetters(fasta, chrom)
+        except KeyError:
+            cache[chrom] = None
+    letters = cache[chrom]
+    if letters is None:
+        return pos, ref, alt
+    kind = LA_INS if len(ref) == 1 else LA_DEL
+    bases = (one if kind == LA_INS else ref)[1:].upper()
+    p, anchor, s, eligible, _ = left_align_letters(letters, letters.length, kind, pos - 1, ref[0].upper(), bases, 0)
+    if not eligible or p == pos - 1:
+        return pos, ref, alt
+    new_ref, new_alt = (anchor, anchor + s) if kind == LA_INS else (anchor + s, anchor)
+    return p + 1, new_ref, (type(alt)([new_alt]) if isinstance(alt, (tuple, list)) else new_alt)
+
+
+def record_left_aligner(fasta_path: str) -> Callable[[Record], Record]:
+    """``normalise`` for ``isec_stream``: a record with its key fields left-aligned on the FASTA, its line unchanged."""
+    from .bamio import FastaFile
+    fasta = FastaFile(fasta_path)
+
+    def normalise(rec: Record) -> Record:
+        pos, ref, alts = left_align_record(fasta, rec[1], rec[2], rec[3], rec[4])
+        return rec[0], rec[1], pos, ref, alts
+    return normalise
+
+
 # output numbers, as bcftools isec -p names them
 PRIVATE_A, PRIVATE_B, SHARED_A, SHARED_B = 0, 1, 2, 3
 
 
 def isec_stream(a: str, b: str, emit: Callable[[int, Record], None],
-                headers: Optional[Callable[[List[str], List[str]], None]] = None) -> Tuple[int, int, int, int]:
+                headers: Optional[Callable[[List[str], List[str]], None]] = None,
+                normalise: Optional[Callable[[Record], Record]] = None) -> Tuple[int, int, int, int]:
     """Pairs the records of VCF ``a`` with those of VCF ``b`` (module docstring) and hands each record to
     ``emit(output, record)``, ``output`` one of PRIVATE_A / PRIVATE_B / SHARED_A / SHARED_B.  Every output receives its
     records in its input's order; all of B's records come before A's.  ``headers(header_a, header_b)`` is called once, before
-    the first ``emit``.  Memory holds A's keys only; A is read twice, B once.  Returns the four record counts."""
+    the first ``emit``.  Memory holds A's keys only; A is read twice, B once.  Returns the four record counts.
+    ``normalise(record)``: the record whose fields make the key (``record_left_aligner``); ``emit`` still gets the input's own."""
+    key = _key if normalise is None else (lambda r: _key(normalise(r)))
     ra = VcfReader(a)
     count_a: Dict[tuple, int] = {}
     for rec in ra:
-        k = _key(rec)
+        k = key(rec)
         count_a[k] = count_a.get(k, 0) + 1
     rb = VcfReader(b)
     seen_b: Dict[tuple, int] = {}
@@ -152,7 +259,7 @@ def isec_stream(a: str, b: str, emit: Callable[[int, Record], None],
             if headers is not None:
                 headers(ra.header, rb.header)
             started = True
-        k = _key(rec)
+        k = key(rec)
         avail = count_a.get(k, 0)
         out = PRIVATE_B
         if avail:
@@ -166,7 +273,7 @@ def isec_stream(a: str, b: str, emit: Callable[[int, Record], None],
         headers(ra.header, rb.header)
     seen_a: Dict[tuple, int] = {}
     for rec in VcfReader(a):
-        k = _key(rec)
+        k = key(rec)
         shared = seen_b.get(k, 0)
         out = PRIVATE_A
         if shared:
@@ -179,16 +286,19 @@ def isec_stream(a: str, b: str, emit: Callable[[int, Record], None],
     return tuple(counts)
 
 
-def isec(a: str, b: str) -> Tuple[List[Record], List[Record], List[Record], List[Record]]:
-    """``(private_a, private_b, shared_a, shared_b)``: bcftools isec -p's 0000 / 0001 / 0002 / 0003 as record lists."""
+def isec(a: str, b: str, left_align: Optional[str] = None) -> Tuple[List[Record], List[Record], List[Record], List[Record]]:
+    """``(private_a, private_b, shared_a, shared_b)``: bcftools isec -p's 0000 / 0001 / 0002 / 0003 as record lists.
+    ``left_align="ref.fa"``: the simple indels of both inputs are left-aligned on it before pairing."""
     outs: Tuple[List[Record], ...] = ([], [], [], [])
-    isec_stream(a, b, lambda o, r: outs[o].append(r))
+    isec_stream(a, b, lambda o, r: outs[o].append(r), normalise=record_left_aligner(left_align) if left_align else None)
     return outs
 
 
-def isec_to_dir(a: str, b: str, outdir: str) -> Tuple[int, int, int, int]:
+def isec_to_dir(a: str, b: str, outdir: str, left_align: Optional[str] = None) -> Tuple[int, int, int, int]:
     """Writes ``outdir/0000.vcf`` .. ``0003.vcf`` (each with its input's header, record lines copied byte for byte) and
-    ``outdir/README.txt``.  On a refused input the four files are removed again."""
+    ``outdir/README.txt``.  On a refused input the four files are removed again.  ``left_align="ref.fa"``: the simple indels of
+    both inputs are left-aligned on it before pairing (the lines written are still the inputs' own)."""
+    normalise = record_left_aligner(left_align) if left_align else None
     os.makedirs(outdir, exist_ok=True)
     paths = [os.path.join(outdir, "%04d.vcf" % i) for i in range(4)]
     files = [open(p, "w", encoding="utf-8", newline="") for p in paths]
@@ -197,7 +307,7 @@ def isec_to_dir(a: str, b: str, outdir: str) -> Tuple[int, int, int, int]:
             for i, h in enumerate((ha, hb, ha, hb)):
                 files[i].writelines(h)
 
-        counts = isec_stream(a, b, lambda o, r: files[o].write(r[0]), headers)
+        counts = isec_stream(a, b, lambda o, r: files[o].write(r[0]), headers, normalise)
     except BaseException:
         for f in files:
             f.close()
@@ -208,13 +318,13 @@ def isec_to_dir(a: str, b: str, outdir: str) -> Tuple[int, int, int, int]:
         f.close()
     with open(os.path.join(outdir, "README.txt"), "w") as f:
         f.write("This file was produced by vcf_isec.py, the bcftools isec -p restatement of this repository.\n"
-                "The command line was:\tvcf_isec.py -p %s %s %s\n\n"
+                "The command line was:\tvcf_isec.py -p %s %s%s %s\n\n"
                 "Using the following file names:\n"
                 "%s\tfor records private to\t%s\n"
                 "%s\tfor records private to\t%s\n"
                 "%s\tfor records from %s shared by both\t%s %s\n"
                 "%s\tfor records from %s shared by both\t%s %s\n"
-                % (outdir, a, b, paths[0], a, paths[1], b, paths[2], a, a, b, paths[3], b, a, b))
+                % (outdir, "--left-align %s " % left_align if left_align else "", a, b, paths[0], a, paths[1], b, paths[2], a, a, b, paths[3], b, a, b))
     return counts
 
 

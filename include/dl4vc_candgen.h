@@ -141,6 +141,35 @@ int cg_reference_codes_host(const uint8_t* raw, uint64_t raw_len, int64_t lineba
                             uint8_t* out, int64_t* n_other);
 int cg_reference_codes(const uint8_t* raw, uint64_t raw_len, int64_t linebases, int64_t linewidth, int64_t length, uint8_t* out,
                        int64_t* n_other, int device);
+/* Left-alignment of insertions and deletions (csrc/cand_left_align.h has the rule).  on != 0: before an indel observation is
+ * counted, the kernels move it to its left-most placement on the reference bases of its contig, so that the placements of one
+ * event inside a homopolymer or tandem repeat give one allele key, one count and one record.  The shift stops at the read's own
+ * POS (the read covers its shifted anchor, so the subregion of the new position fetches it) and at a reference base outside
+ * ACGT.  Not shifted, and counted as before: an indel anchored on a deleted or inserted position or on the stand-in anchor of a
+ * leading deletion, one with a base outside ACGT, and one whose anchor or deleted bases differ from the FASTA (an MD tag that
+ * disagrees with it).  The length limit, the deletion-drop rule and the coverage are those of the option off; the position
+ * tests and the depth are taken at the shifted position.  Needs cg_set_reference: refused with the reason on a handle without
+ * one (the handle stays usable), and while it is on cg_set_reference(h, NULL) is refused.  A consequence of needing the
+ * reference: reads without MD are walked against the FASTA too.  Off by default. */
+int cg_set_left_align(cg_handle_t* h, int on);
+/* Of the last cg_run, over the indel observations that were counted as alleles (all zero with the option off): exact integer
+ * sums, independent of the order the reads ran in. */
+typedef struct {
+    int64_t observations;          /* = the indel share of cg_stats.allele_events */
+    int64_t shifted;               /* moved by at least one base */
+    int64_t bases_shifted;         /* the sum of their shifts */
+    int64_t clamped;               /* stopped at the read's POS where the reference would have let them go on */
+    int64_t not_eligible;          /* left as they were */
+} cg_left_align_stats;
+int cg_get_left_align_stats(const cg_handle_t* h, cg_left_align_stats* out);
+/* For tests and the sanitizer program: the rule for one observation, on the CPU.  codes[0, length): the contig as BAM nibble
+ * codes; kind 1 = insertion, 2 = deletion; anchor_aligned: the anchor is an aligned pair of the read; bases[0, n_bases): the
+ * inserted or deleted bases as codes; floor: the read's POS.  *pos_out = the placement's anchor position, bases_out[0] its
+ * anchor code and bases_out[1 .. n_bases] its bases (n_bases + 1 bytes), *flags = 1 (eligible) | 2 (clamped).  An observation
+ * that is not eligible, n_bases > 63 included, comes back as it went in with *flags = 0.  Reads nothing outside codes[0, length). */
+int cg_left_align_host(const uint8_t* codes, int64_t length, int32_t kind, int32_t anchor_aligned, int64_t anchor_pos,
+                       int32_t anchor_code, const uint8_t* bases, int32_t n_bases, int64_t floor, int64_t* pos_out,
+                       uint8_t* bases_out, int32_t* flags);
 /* For tests: the byte ranges and walk boundaries the device path would use for one region, as BGZF virtual offsets.
  * ranges: n_ranges pairs [begin, end), merged and sorted; bounds: every walk boundary (range ends included), sorted.  At most
  * cap_* entries are written; the counts are always the full ones.  Reads the index only. */

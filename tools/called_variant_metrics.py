@@ -14,7 +14,10 @@ Differences from the reference:
 * where a count is zero and the reference stops with ZeroDivisionError, the ratio is printed as `nan` and all four lines are
   printed;
 * `--regions_bed BED` (an extension) keeps, in every set, only records whose 0-based `POS - 1` lies inside a BED interval;
-* inputs need no index, and may be plain text as well as bgzip / gzip.
+* inputs need no index, and may be plain text as well as bgzip / gzip;
+* `--left-align REF.fa` (an extension) moves the simple indels of both the truth and the calls to their left-most placement on
+  the FASTA before they are paired (dl4vc_amd/truthset.py::left_align_record); MNPs, complex alleles and multi-allelic records
+  are compared as they are.
 """
 from __future__ import annotations
 
@@ -34,7 +37,11 @@ def main(argv=None):
                         help="region in form chrom:start:end. If not set defaults to whole genome")
     parser.add_argument("--regions_bed", type=str, default=None,
                         help="BED file: count only records whose POS-1 lies in one of its intervals (not in the reference)")
+    parser.add_argument("--left-align", dest="left_align", type=str, default=None, metavar="REF.fa",
+                        help="left-align the simple indels of both inputs on this FASTA before pairing (not in the reference)")
     args = parser.parse_args(argv)
+    if args.left_align is not None and not os.path.isfile(args.left_align):
+        parser.error("--left-align %s is not a readable file" % args.left_align)
 
     if args.region is not None:
         chrom, start, end = args.region.split(":")
@@ -51,7 +58,8 @@ def main(argv=None):
             sets[o].append(rec[1:])
 
     try:
-        T.isec_stream(args.truth_variants, args.called_variants, keep)
+        T.isec_stream(args.truth_variants, args.called_variants, keep,
+                      normalise=T.record_left_aligner(args.left_align) if args.left_align else None)
         fn_snps, fn_insertions, fn_deletions = T.count_variant_types(sets[0], chrom, start, end)
         fp_snps, fp_insertions, fp_deletions = T.count_variant_types(sets[1], chrom, start, end)
         tp_snps, tp_insertions, tp_deletions = T.count_variant_types(sets[2], chrom, start, end)

@@ -6,7 +6,7 @@ host's inflate-and-frame time against the device time (per-stage device times co
 
     python tools/candgen_rate.py --bam /tmp/cg_rate.bam [--reads 2000000 --length 10000000] [--out profiles/x.json]
         [--inflate-device gpu] [--chunk_size 1000] [--no-md] [--fasta REF.fa] [--reference REF.fa]
-        [--subsample F [--subsample-seed S]] [--min-mapq Q] [--exclude-flags F] [--require-flags F] [--read-stats]
+        [--left-align] [--subsample F [--subsample-seed S]] [--min-mapq Q] [--exclude-flags F] [--require-flags F] [--read-stats]
 
 ``--inflate-device gpu`` measures the device inflate path (the line then carries its read / inflate / walk-and-frame times);
 ``--chunk_size`` other than 1000 changes the subregions, and with them the candidates at their boundaries: a timing line only.
@@ -15,6 +15,9 @@ The reference arm: ``--no-md`` writes the same reads without aux tags (when ``--
 genome they were drawn from beside it (60 bases a line, with its ``.fai``), and ``--reference REF.fa`` walks the reads that have
 no MD tag against it; the line then carries the ``reference_*`` figures.  Every repeat opens its own handle, so the contig's
 one-time load (read, upload and convert) is inside every repeat's wall time.
+
+``--left-align`` (with ``--reference``) left-aligns the indels before they are counted; the line then carries the
+``left_align_*`` counters.
 
 ``--subsample F [--subsample-seed S]`` is passed through (reads subsampled by name hash in front of every count); the line then
 carries the records seen and kept, and ``reads_per_s`` counts the records SEEN, the work the framing did.  The read filter
@@ -89,6 +92,7 @@ def main():
     ap.add_argument("--no-md", dest="no_md", action="store_true", help="write the BAM without aux tags (when it has to be made)")
     ap.add_argument("--fasta", default=None, help="write the BAM's genome here, with its .fai (when the BAM has to be made)")
     ap.add_argument("--reference", default=None, help="walk the reads that have no MD tag against this FASTA")
+    ap.add_argument("--left-align", dest="left_align", action="store_true", help="left-align the indels on --reference before counting")
     from dl4vc_amd import subsample
     from dl4vc_amd import read_filter
     subsample.add_flags(ap)
@@ -96,6 +100,8 @@ def main():
     a = ap.parse_args()
     rule = subsample.parse(ap, a)
     flt = read_filter.parse(ap, a)
+    if a.left_align and not a.reference:
+        ap.error("--left-align needs --reference REF.fa")
     if not os.path.isfile(a.bam + ".bai"):
         t = time.time()
         make_bam(a.bam, a.reads, a.length, md_tags=not a.no_md, fasta=a.fasta)
@@ -104,6 +110,8 @@ def main():
     extra = {"subsample": rule} if rule is not None else {}
     if flt is not None or a.read_stats:
         extra.update(read_filter=flt, read_stats=a.read_stats)
+    if a.left_align:
+        extra.update(left_align=True)
     runs = []
     for k in range(a.repeats):
         t = time.perf_counter()
@@ -118,10 +126,11 @@ def main():
            "native_total_ms": round(best["total_ms"], 1), "candidates": best["candidates"], "alleles": best["alleles"],
            "allele_events": best["allele_events"], "batches": best["batches"], "threads": a.threads or min(16, len(os.sched_getaffinity(0))),
            "chunk_size": a.chunk_size, "inflate_device": a.inflate_device, "reference": bool(a.reference),
-           "reads_no_md": best["reads_no_md"]}
+           "reads_no_md": best["reads_no_md"], "left_align": bool(a.left_align)}
     for k in ("inflate_blocks", "inflate_compressed_bytes", "inflate_inflated_bytes", "inflate_records", "inflate_read_ms", "inflate_ms",
               "inflate_walk_frame_ms", "reference_reads", "reference_contigs", "reference_bases", "reference_other_bytes",
-              "reference_read_ms", "reference_upload_convert_ms"):
+              "reference_read_ms", "reference_upload_convert_ms", "left_align_observations", "left_align_shifted",
+              "left_align_bases_shifted", "left_align_clamped", "left_align_not_eligible"):
         if k in best:
             res[k] = round(best[k], 1) if isinstance(best[k], float) else best[k]
     if rule is not None:

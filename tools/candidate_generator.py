@@ -51,6 +51,12 @@ def warn_no_md(stats, reference) -> None:
                         "reference bases", stats["reads_no_md"], stats["reads"])
 
 
+def report_left_align(args, stats) -> None:
+    if args.left_align:
+        print("left-align: %d indel observations, %d shifted by %d bases in all, %d clamped by their read's start, %d not eligible"
+              % tuple(stats.get("left_align_" + k, 0) for k in ("observations", "shifted", "bases_shifted", "clamped", "not_eligible")))
+
+
 def report_reads(args, stats) -> None:
     """The read filter's line and, with --read-stats, the census."""
     from dl4vc_amd import read_filter
@@ -81,6 +87,7 @@ def run_children(args, argv) -> int:
         print(subsample.report_line(stats["subsample_records_seen"], stats["subsample_records_kept"],
                                     (args.subsample, args.subsample_seed or 0)))
     report_reads(args, stats)                                 # (the census of the parts, summed)
+    report_left_align(args, stats)
     logging.info("Generated final VCF file at %s from %d parts.", args.output, args.gpus)
     print("summary " + json.dumps(stats, sort_keys=True))
     return 0
@@ -99,6 +106,10 @@ def main(argv=None) -> int:
                    help="Walk the reads that have no MD tag against this FASTA's bases (REF.fa.fai when that file exists) instead "
                    "of giving them no alleles; reads with an MD tag are walked by it as before. Each contig touched stays on the GPU "
                    "as 1 byte per base")
+    p.add_argument("--left-align", dest="left_align", action="store_true", default=False,
+                   help="Move every insertion and deletion to its left-most placement on the reference bases before it is counted, "
+                   "so that the placements of one event inside a repeat give one candidate (needs --reference; with it, reads "
+                   "without an MD tag are walked against the FASTA too)")
     from dl4vc_amd import subsample
     from dl4vc_amd import read_filter
     subsample.add_flags(p)
@@ -108,6 +119,8 @@ def main(argv=None) -> int:
     flt = read_filter.parse(p, args)
     print(args)
     logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.DEBUG if args.debug else logging.INFO)
+    if args.left_align and args.reference is None:
+        p.error("--left-align needs --reference REF.fa: left-alignment is defined by the reference bases")
     if args.reference is not None and not (os.path.isfile(args.reference) and os.access(args.reference, os.R_OK)):
         p.error("--reference %s is not a readable file" % args.reference)      # (before any device work, --gpus children included)
     from dl4vc_amd.candidates import generate
@@ -124,12 +137,14 @@ def main(argv=None) -> int:
                      chunk_size=args.chunk_size, threads=args.threads, snp_min_freq=args.snp_min_freq,
                      indel_min_freq=args.indel_min_freq, keep_multialleles=args.keep_multialleles,
                      max_len_indel_allele=args.max_len_indel_allele, inflate_device=args.inflate_device, shard=shard,
-                     reference=args.reference, subsample=rule, read_filter=flt, read_stats=args.read_stats)
+                     reference=args.reference, subsample=rule, read_filter=flt, read_stats=args.read_stats,
+                     left_align=args.left_align)
     if shard is None:                      # (the parent of shards says it once, of the summed counts)
         warn_no_md(stats, args.reference)
         if rule is not None:
             print(subsample.report_line(stats["subsample_records_seen"], stats["subsample_records_kept"], rule))
         report_reads(args, stats)
+        report_left_align(args, stats)
     if shard is not None:
         from dl4vc_amd.shard import part_path
         logging.info("Wrote the records of shard %d/%d to %s.", shard[0], shard[1], part_path(args.output, shard[0]))

@@ -13,23 +13,28 @@
 # outputs (--train_bam: the pileups are encoded on the GPU into the resident record store, the same records in the same order).
 # -f: the candidate generator walks the reads that have no MD tag against REFERENCE (--reference; whole contigs on the GPU, 1 byte
 # per base) instead of giving them no alleles; reads with an MD tag are walked by it as before.  Not passed by default.
+# -L (implies -f): the candidate generator moves every insertion and deletion to its left-most placement on REFERENCE before it is
+# counted (--left-align), and tools/vcf_isec.py left-aligns the simple indels of both the truth set and the candidates the same
+# way before it pairs them (--left-align REFERENCE): a candidate and a truth record that name one event at two placements of a
+# repeat pair.  Reads are not realigned.  Not passed by default.
 # -s F [-S SEED]: candidate generation and the converter (with -n: the printed --train_bam flags) keep the fraction F in (0, 1] of
 # the BAM's reads, chosen by a hash of the read name (--subsample / --subsample-seed): training data at F of the coverage.
 # -q Q, -F MASK, -R MASK: candidate generation and the converter (with -n: the printed --train_bam flags) drop the reads with
 # MAPQ < Q, with any flag bit of -F or without a flag bit of -R (--min-mapq / --exclude-flags / --require-flags).
 set -e
-usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c [-y]] [-n] [-f] [-s FRACTION [-S SEED]] [-q MIN_MAPQ] [-F EXCLUDE_FLAGS] [-R REQUIRE_FLAGS]"; exit 1; }
+usage() { echo "Usage: $0 -i BAM -r REFERENCE -t TRUTH.vcf[.gz] -o OUTDIR [-b BED] [-p PROCESSES] [-c [-y]] [-n] [-f] [-L] [-s FRACTION [-S SEED]] [-q MIN_MAPQ] [-F EXCLUDE_FLAGS] [-R REQUIRE_FLAGS]"; exit 1; }
 PROCS=16
 COMPRESS=""
 CODES=""
 NOFILE=""
 FROMREF=""
+LEFTALIGN=""
 SUBSAMPLE=""
 SEED=""
 MINMAPQ=""
 EXCLUDE=""
 REQUIRE=""
-while getopts "i:r:t:o:b:p:s:S:q:F:R:nfcyh" opt; do
+while getopts "i:r:t:o:b:p:s:S:q:F:R:nfLcyh" opt; do
   case $opt in
     i) BAM=$OPTARG ;;
     r) REFERENCE=$OPTARG ;;
@@ -41,6 +46,7 @@ while getopts "i:r:t:o:b:p:s:S:q:F:R:nfcyh" opt; do
     y) CODES=dynamic ;;
     n) NOFILE=1 ;;
     f) FROMREF=1 ;;         # candidate generation: reads without MD are walked against REFERENCE
+    L) LEFTALIGN=1; FROMREF=1 ;;  # indels left-aligned on REFERENCE: in candidate generation and on both sides of the pairing
     s) SUBSAMPLE=$OPTARG ;; # every BAM reader keeps this fraction of the reads (--subsample)
     S) SEED=$OPTARG ;;      # with -s: the seed (--subsample-seed)
     q) MINMAPQ=$OPTARG ;;   # every BAM reader drops the reads below this mapping quality (--min-mapq)
@@ -49,6 +55,7 @@ while getopts "i:r:t:o:b:p:s:S:q:F:R:nfcyh" opt; do
     *) usage ;;
   esac
 done
+[ -n "$LEFTALIGN" ] && [ -z "$REFERENCE" ] && { echo "-L left-aligns the indels on the reference: give -r REFERENCE as well"; exit 1; }
 [ -n "$FROMREF" ] && [ -z "$REFERENCE" ] && { echo "-f walks the reads without MD against the reference: give -r REFERENCE as well"; exit 1; }
 [ -z "$BAM" ] || [ -z "$REFERENCE" ] || [ -z "$TRUTH" ] || [ -z "$OUTDIR" ] && usage
 [ -n "$CODES" ] && [ -z "$COMPRESS" ] && { echo "-y chooses the codes of the chunks -c compresses: give -c as well"; exit 1; }
@@ -62,11 +69,11 @@ if [ ! -f "$OUTDIR/candidates.vcf" ]; then
   printf "Generate candidate VCF...\n"
   python "$SCRIPTDIR/tools/candidate_generator.py" --input "$BAM" --output "$OUTDIR/candidates.vcf" \
       --snp_min_freq 0.075 --indel_min_freq 0.02 ${BED:+--bedfile "$BED"} --keep_multialleles \
-      ${FROMREF:+--reference "$REFERENCE"} "${SUBFLAGS[@]}" > "$OUTDIR/candidate_generator.log" 2>&1
+      ${FROMREF:+--reference "$REFERENCE"} ${LEFTALIGN:+--left-align} "${SUBFLAGS[@]}" > "$OUTDIR/candidate_generator.log" 2>&1
 fi
 if [ ! -f "$OUTDIR/isec/0003.vcf" ]; then
   printf "Intersect candidates with the truth set...\n"
-  python "$SCRIPTDIR/tools/vcf_isec.py" -p "$OUTDIR/isec" "$TRUTH" "$OUTDIR/candidates.vcf" > "$OUTDIR/isec.log" 2>&1
+  python "$SCRIPTDIR/tools/vcf_isec.py" -p "$OUTDIR/isec" ${LEFTALIGN:+--left-align "$REFERENCE"} "$TRUTH" "$OUTDIR/candidates.vcf" > "$OUTDIR/isec.log" 2>&1
 fi
 if [ -n "$NOFILE" ]; then
   echo "No train.hdf written.  Train straight from the BAM with:"

@@ -11,6 +11,10 @@ record of the same ALT set, so a truth ``A>G,T`` and a candidate ``A>G`` both st
 
     vcf_isec.py -p isec truth.vcf.gz candidates.vcf
 
+``--left-align REF.fa`` (not a bcftools option): the simple indels of both inputs are moved to their left-most placement on the
+FASTA before they are paired, so that one event named at two placements of a repeat pairs (dl4vc_amd/truthset.py::
+left_align_record).  The lines written are still the inputs' own.
+
 Every other bcftools isec option is refused, never ignored.
 """
 from __future__ import annotations
@@ -21,11 +25,11 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-USAGE = "usage: vcf_isec.py -p DIR A.vcf[.gz] B.vcf[.gz]"
+USAGE = "usage: vcf_isec.py -p DIR [--left-align REF.fa] A.vcf[.gz] B.vcf[.gz]"
 
 
 def parse_args(argv):
-    prefix, files = None, []
+    prefix, files, left_align = None, [], None
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -38,7 +42,15 @@ def parse_args(argv):
             prefix = argv[i + 1]
             i += 2
             continue
-        if a.startswith("--prefix="):
+        if a == "--left-align":
+            if i + 1 >= len(argv):
+                raise SystemExit("vcf_isec.py: --left-align needs the reference FASTA\n%s" % USAGE)
+            left_align = argv[i + 1]
+            i += 2
+            continue
+        if a.startswith("--left-align="):
+            left_align = a[len("--left-align="):]
+        elif a.startswith("--prefix="):
             prefix = a[len("--prefix="):]
         elif a.startswith("-p") and len(a) > 2:
             prefix = a[2:]
@@ -53,15 +65,17 @@ def parse_args(argv):
                          "implemented)\n%s" % USAGE)
     if len(files) != 2:
         raise SystemExit("vcf_isec.py: exactly two VCF files are needed, got %d\n%s" % (len(files), USAGE))
-    return prefix, files[0], files[1]
+    if left_align is not None and not os.path.isfile(left_align):
+        raise SystemExit("vcf_isec.py: --left-align %s is not a readable file" % left_align)
+    return prefix, files[0], files[1], left_align
 
 
 def main(argv=None):
     from dl4vc_amd.truthset import VcfError, isec_to_dir
-    prefix, a, b = parse_args(sys.argv[1:] if argv is None else argv)
+    prefix, a, b, left_align = parse_args(sys.argv[1:] if argv is None else argv)
     t0 = time.time()
     try:
-        counts = isec_to_dir(a, b, prefix)
+        counts = isec_to_dir(a, b, prefix, left_align=left_align)
     except VcfError as e:
         print("vcf_isec.py: %s" % e, file=sys.stderr)
         return 1
