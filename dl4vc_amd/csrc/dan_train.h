@@ -16,6 +16,25 @@ constexpr int WG_S = 144;                 // LDS row stride (floats) of the weig
 constexpr int WG_CH = 104;                // positions per staged chunk (half a read)
 constexpr int TRAIN_PARTIAL_WGS = 256;    // workgroups of a weight-gradient launch = slices of the split-K partial buffer
 
+// ---- what the launchers made of the row count and the CU count ------------------------------------------------------------------
+// Filled by the launchers below when the caller passes one (they read nothing from it: grids and arguments do not depend on it);
+// dan_train_capi.cpp keeps one per step behind dan_train_query's "sched:" keys (include/dl4vc_dan_train.h), so that a test can
+// ASSERT that it crossed a schedule's threshold.  Maxima / minima over the step's launches of a form; 0 = the form did not run.
+struct TrainSched {
+    int rowh_units_per_wg_max = 0, rowh_units_per_wg_min = 0;   // train_rowh_kernel: half-read units a workgroup walks
+    int rowh_stagger = 0;                                       // 1: some half-read launch ran with a non-zero stagger
+    int row_reads_per_wg_max = 0;                               // train_row_kernel (whole reads; the Winograd form)
+    int wgrad3_rows_per_wg_max = 0, wgrad3_rows_per_wg_min = 0; // train_wgrad3_kernel
+    int wgrad1_rows_per_wg_max = 0;                             // train_wgrad1_kernel (both instances)
+    int wgradpool_rows_per_wg_max = 0;                          // train_wgrad_kernel<3, true, 8>
+    int l0_rows_per_wg_max = 0, l0_partials = 0;                // l0_bins_kernel: rows per workgroup, partial slices summed
+    int stats_entries_per_block_max = 0, stats_blocks_max = 0;  // stats_partial_kernel
+    int gemm_tiles_m_max = 0, gemm_tiles_n_max = 0, gemm_k_tiles_max = 0, gemm_splits_max = 0;   // gemm_kernel (k-tiles per split)
+    int fc1_streaming = 0;                                      // 1: an fc_skinny_* form ran
+    static void hi(int& m, int v) { if (v > m) m = v; }
+    static void lo(int& m, int v) { if (m == 0 || v < m) m = v; }
+};
+
 // ---- T1: one layer-shaped step on the LDS-resident read -------------------------------------------------------------------
 //   image  = load                                         rows src1 [affine with src2] [masked by src2 > 0] [+ pool]
 //   acc    = w1 ? GEMM(image; taps, kg, dil) : image
@@ -59,7 +78,7 @@ struct RowArgs {
 // (TRAIN_ROW_ERR_FORM).  train_row_fuses_second_product(a): true when `a` (with or without w3 / src3 / src4 set) selects the one
 // form that honours w3 -- the caller decides the g_{l-1} fusion with it.
 constexpr int TRAIN_ROW_ERR_STATS = -2, TRAIN_ROW_ERR_FORM = -3;
-int launch_train_row(const RowArgs& a, int n_rows, hipStream_t s, int stat_cap = 1 << 30);
+int launch_train_row(const RowArgs& a, int n_rows, hipStream_t s, int stat_cap = 1 << 30, TrainSched* sched = nullptr);
 bool train_row_fuses_second_product(const RowArgs& a);
 
 // ---- T2: weight gradient  dW[t][o][c] = sum over positions of  A[p][o] * B[p + (t - 1) dil][c]   (+ bias grad = sum A) ------
@@ -82,14 +101,14 @@ struct WgradArgs {
 };
 // returns the number of workgroups (partial slices) used; 0, with nothing launched, for a shape no kernel form serves: the forms are
 // 1 tap without a_coef / b_pool (A 128 or 32 wide), and 3 taps on 128 x 128 channels
-int launch_train_wgrad(const WgradArgs& a, hipStream_t s);
+int launch_train_wgrad(const WgradArgs& a, hipStream_t s, TrainSched* sched = nullptr);
 // G[(o * n_in + i) * taps + t] = sum_wg partial[wg][t][o][cmap ? cmap[i] : i];  gb[o] = sum_wg bias_partial[wg][o]
 void launch_wgrad_reduce(const float* partial, const float* bias_partial, int wgs, int taps, int o_pad, int c_pad, int n_out,
                          int n_in, const int* cmap, float* g_w, float* g_b, hipStream_t s);
 
 // ---- per-channel statistics ---------------------------------------------------------------------------------------------------
 // block partials in double: bp[block][2][CPAD] = sum over the block's rows of stats[row][2][CPAD]
-void launch_stats_partial(const float* stats, int n_rows, double* bp, int* n_blocks, hipStream_t s);
+void launch_stats_partial(const float* stats, int n_rows, double* bp, int* n_blocks, hipStream_t s, TrainSched* sched = nullptr);
 // forward BatchNorm (training): mean / biased variance over N = n_rows * L positions -> coef = (scale, 0, shift) with
 // scale = gamma / sqrt(var + eps), shift = beta - mean * scale; saves mean / invstd; running stats += momentum 0.1 (unbiased)
 void launch_bn_forward_finalize(const double* bp, int n_blocks, double n_pos, const float* gamma, const float* beta, int channels,
@@ -134,7 +153,7 @@ void launch_highway_bias_grad_all(const float* dfeat, const float* feat, long lo
 constexpr int L0_BINS_TOTALS = 208 * 128 + 2 * 3 * 10 * 128 + 3 * 5 * 128 + 32;
 int l0_bins_lds_bytes();
 int launch_l0_backward(const WgradArgs& a, int n_sites, double* tot, const float* w1, const int* canon, int n_out, int n_in, float* g_w,
-                        float* g_b, float* g_emb, hipStream_t s);
+                        float* g_b, float* g_emb, hipStream_t s, TrainSched* sched = nullptr);
 // Layer 1's forward by table (the inference walk of dan_kernels.h L0_*, tables rebuilt from the step's weights): tab = l0_tab_floats(L)
 // floats; inv: canonical channel -> reference channel or -1.  The forward writes a_1 = relu(conv1 + bias) [row][L][CPAD] and, if stats,
 // one entry of BatchNorm sums per row; returns the number of entries.
@@ -144,7 +163,8 @@ int launch_l0_train_forward(const RowArgs& enc, const float* tab, const float* b
 // C[m][n] (+)= sum_k opA(m,k) * opB(n,k);  an operand is K-contiguous (X[i*ld + k]) or K-slow (X[k*ld + i])
 // split_ws: workspace for split-K partials (used when the tile grid cannot fill the chip and K is long), or nullptr
 void launch_gemm(const float* A, long long lda, int a_kslow, const float* B, long long ldb, int b_kslow, const float* bias,
-                 float* C, long long ldc, int M, int N, int K, int relu, float* split_ws, long long split_ws_floats, hipStream_t s);
+                 float* C, long long ldc, int M, int N, int K, int relu, float* split_ws, long long split_ws_floats, hipStream_t s,
+                 TrainSched* sched = nullptr);
 // y[i] = x[i] * mask[i] * scale  (mask: one byte per element, row-major [rows][cols]; x, y with row stride ld)
 void launch_dropout(const float* x, const uint8_t* mask, float scale, float* y, int rows, int cols, long long ld, hipStream_t s);
 // dx = dy * mask * scale * (act > 0 || !relu)      (backward of Linear -> ReLU -> Dropout, act = the ReLU output)

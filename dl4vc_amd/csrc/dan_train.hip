@@ -686,7 +686,7 @@ bool train_row_fuses_second_product(const RowArgs& a) {
 
 // Returns the number of `stats` entries the launch writes (reads for the whole-read form, half-read units for the half-read form,
 // 64-position tiles for the pointwise one), or TRAIN_ROW_ERR_* without launching.
-int launch_train_row(const RowArgs& a, int n_rows, hipStream_t s, int stat_cap) {
+int launch_train_row(const RowArgs& a, int n_rows, hipStream_t s, int stat_cap, TrainSched* sched) {
     const bool pointwise = !a.pool_in && !a.wino && (a.w1 == nullptr || a.taps == 1);
     static const int n_cus = [] {
         int dev = 0, n = 0;
@@ -714,12 +714,18 @@ int launch_train_row(const RowArgs& a, int n_rows, hipStream_t s, int stat_cap) 
         // the second workgroup of a CU starts half a unit late (three s_sleep 127: ~10 us) when there is a second one per CU
         const dim3 grid((unsigned)wgs), blk(RH_THREADS);
         const int st = wgs > n_cus ? 3 : 0;
+        if (sched) {
+            sched->hi(sched->rowh_units_per_wg_max, (n_units + wgs - 1) / wgs);
+            sched->lo(sched->rowh_units_per_wg_min, n_units / wgs);
+            if (st) sched->rowh_stagger = 1;
+        }
         if (f2) hipLaunchKernelGGL((train_rowh_kernel<true, false, true>), grid, blk, 0, s, a, n_rows, st);
         else if (src2) hipLaunchKernelGGL((train_rowh_kernel<true, false, false>), grid, blk, 0, s, a, n_rows, st);
         else if (pool) hipLaunchKernelGGL((train_rowh_kernel<false, true, false>), grid, blk, 0, s, a, n_rows, st);
         else hipLaunchKernelGGL((train_rowh_kernel<false, false, false>), grid, blk, 0, s, a, n_rows, st);
         return n_units;
     }
+    if (sched) sched->hi(sched->row_reads_per_wg_max, (n_rows + std::min(n_rows, n_cus) - 1) / std::min(n_rows, n_cus));
     hipLaunchKernelGGL(train_row_kernel, dim3((unsigned)std::min(n_rows, n_cus)), dim3(SEG_THREADS), 0, s, a, n_rows);
     return n_rows;
 }
@@ -1237,23 +1243,29 @@ __global__ __launch_bounds__(SEG_THREADS, NWAVE / 4) void train_wgrad3_kernel(Wg
     }
 }
 
-int launch_train_wgrad(const WgradArgs& a, hipStream_t s) {
+int launch_train_wgrad(const WgradArgs& a, hipStream_t s, TrainSched* sched) {
     // (balanced over the rounds: 1 000 rows at 10 sites are 250 workgroups of 4 rows, not 256 of which 232 run a fourth round)
     auto balanced = [](int n, int cap) { const int rounds = (n + cap - 1) / cap; return (n + rounds - 1) / rounds; };
     const int wgs = balanced(a.n_rows, TRAIN_PARTIAL_WGS);
     const dim3 grid((unsigned)wgs), blk(SEG_THREADS);
     if (a.taps == 1 && !a.b_pool && !a.a_coef) {   // 1x1 forms: two workgroups per CU (train_wgrad1_kernel)
         const int wgs2 = balanced(a.n_rows, 2 * TRAIN_PARTIAL_WGS);
+        if (sched) sched->hi(sched->wgrad1_rows_per_wg_max, (a.n_rows + wgs2 - 1) / wgs2);
         if (a.o_tiles <= 2) hipLaunchKernelGGL((train_wgrad1_kernel<false, 1>), dim3((unsigned)wgs2), blk, 0, s, a);
         else hipLaunchKernelGGL((train_wgrad1_kernel<true, KGC>), dim3((unsigned)wgs2), blk, 0, s, a);
         return wgs2;
     }
     if (a.taps == 3 && !a.b_pool && a.a2 && a.a_stride == CPAD && a.c_tiles == KGC && a.o_tiles == KGC) {
+        if (sched) {
+            sched->hi(sched->wgrad3_rows_per_wg_max, (a.n_rows + wgs - 1) / wgs);
+            sched->lo(sched->wgrad3_rows_per_wg_min, a.n_rows / wgs);
+        }
         hipLaunchKernelGGL((train_wgrad3_kernel<KGC>), grid, blk, 0, s, a);                    // the next chunk in flight under the MFMAs
         return wgs;
     }
     // the generic form is instantiated for the one shape left to it: the 3-tap gradient of a pooled layer, 128 x 128 channels
     if (a.taps != 3 || a.o_tiles != KGC || a.c_tiles != KGC) return 0;
+    if (sched) sched->hi(sched->wgradpool_rows_per_wg_max, (a.n_rows + wgs - 1) / wgs);
     hipLaunchKernelGGL((train_wgrad_kernel<3, true, KGC>), grid, blk, 0, s, a);
     return wgs;
 }
@@ -1336,10 +1348,14 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(const float* __restr
     bp[(size_t)blockIdx.x * 2 * CPAD + threadIdx.x] = sum;
 }
 
-void launch_stats_partial(const float* stats, int n_rows, double* bp, int* n_blocks, hipStream_t s) {
+void launch_stats_partial(const float* stats, int n_rows, double* bp, int* n_blocks, hipStream_t s, TrainSched* sched) {
     const int per_block = std::max(32, (n_rows + 127) / 128);
     const int nb = (n_rows + per_block - 1) / per_block;
     *n_blocks = nb;
+    if (sched) {
+        sched->hi(sched->stats_entries_per_block_max, std::min(per_block, n_rows));
+        sched->hi(sched->stats_blocks_max, nb);
+    }
     hipLaunchKernelGGL(stats_partial_kernel, dim3(nb), dim3(2 * CPAD), 0, s, stats, n_rows, per_block, bp);
 }
 
@@ -1983,10 +1999,14 @@ int l0_bins_lds_bytes() { return ((MPOS + 2) * L0B_DZ_S + 2 * MPOS * L0B_A) * (i
 // The attribute belongs to (function, device): set on every call -- one driver table lookup -- rather than once per process, which
 // would leave a second device of the same process without it.
 int launch_l0_backward(const WgradArgs& a, int n_sites, double* tot, const float* w1, const int* canon, int n_out, int n_in, float* g_w,
-                       float* g_b, float* g_emb, hipStream_t s) {
+                       float* g_b, float* g_emb, hipStream_t s, TrainSched* sched) {
     const hipError_t e = hipFuncSetAttribute((const void*)l0_bins_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, l0_bins_lds_bytes());
     if (e != hipSuccess) return (int)e;
     const int wgs = a.n_rows < TRAIN_PARTIAL_WGS ? a.n_rows : TRAIN_PARTIAL_WGS;
+    if (sched) {
+        sched->hi(sched->l0_rows_per_wg_max, (a.n_rows + wgs - 1) / wgs);
+        sched->l0_partials = wgs;
+    }
     hipLaunchKernelGGL(l0_bins_kernel, dim3(wgs), dim3(512), l0_bins_lds_bytes(), s, a, n_sites);
     hipLaunchKernelGGL(l0_bins_reduce_kernel, dim3((L0B_FLOATS + 255) / 256), dim3(256), 0, s, a.partial, wgs, tot);
     const int total = 3 * n_out * n_in + n_out + VOCAB * EMBED;
@@ -2378,13 +2398,15 @@ __global__ __launch_bounds__(SK_THREADS) void fc_skinny_wgrad_kernel(const float
 }
 
 void launch_gemm(const float* A, long long lda, int a_kslow, const float* B, long long ldb, int b_kslow, const float* bias,
-                 float* C, long long ldc, int M, int N, int K, int relu, float* split_ws, long long split_ws_floats, hipStream_t s) {
+                 float* C, long long ldc, int M, int N, int K, int relu, float* split_ws, long long split_ws_floats, hipStream_t s,
+                 TrainSched* sched) {
     // FC1 at a few sites per GPU: the three weight-streaming forms (fc_skinny_*_kernel); vector accesses need the 16-byte
     // alignment the trainer's padded strides give
     const bool al = ((lda | ldb | ldc) & 3) == 0;
     if (split_ws && al && !a_kslow && !b_kslow && M <= SK_MAXM && K >= 8192 && (long long)((K + SK_SLAB - 1) / SK_SLAB) * M * N <= split_ws_floats) {
         const int slabs = (K + SK_SLAB - 1) / SK_SLAB, groups = std::max(1, std::min(N / 16, (768 + slabs - 1) / slabs));
         const int rows = (N + groups - 1) / groups;
+        if (sched) sched->fc1_streaming = 1;
         hipLaunchKernelGGL(fc_skinny_fwd_kernel, dim3((unsigned)slabs, (unsigned)((N + rows - 1) / rows)), dim3(SK_THREADS), (size_t)M * SK_SLAB * sizeof(float), s, A, lda, B, ldb, split_ws, M, N, K, rows);
         hipLaunchKernelGGL(gemm_split_reduce_kernel, dim3((M * N + 255) / 256), dim3(256), 0, s, split_ws, slabs, bias, C, ldc, M, N, relu);
         return;
@@ -2396,6 +2418,7 @@ void launch_gemm(const float* A, long long lda, int a_kslow, const float* B, lon
         const int rows = ((K + groups - 1) / groups + 3) & ~3;
         groups = (K + rows - 1) / rows;
         if ((long long)groups * M * N <= split_ws_floats && rows <= SK_DROWS) {
+            if (sched) sched->fc1_streaming = 1;
             hipLaunchKernelGGL(fc_skinny_dgrad_kernel, dim3((unsigned)slabs, (unsigned)groups), dim3(SK_THREADS), 0, s, A, lda, B, ldb, split_ws, M, N, K, rows);
             hipLaunchKernelGGL(gemm_split_reduce_kernel, dim3((M * N + 255) / 256), dim3(256), 0, s, split_ws, groups, bias, C, ldc, M, N, relu);
             return;
@@ -2404,6 +2427,7 @@ void launch_gemm(const float* A, long long lda, int a_kslow, const float* B, lon
     if (al && a_kslow && b_kslow && K <= SK_MAXM && N >= 8192 && (N & 3) == 0 && !bias && !relu) {
         const int slabs = (N + SK_SLAB - 1) / SK_SLAB, groups = std::max(1, std::min(M / 16, (768 + slabs - 1) / slabs));
         const int rows = (M + groups - 1) / groups;
+        if (sched) sched->fc1_streaming = 1;
         hipLaunchKernelGGL(fc_skinny_wgrad_kernel, dim3((unsigned)slabs, (unsigned)((M + rows - 1) / rows)), dim3(SK_THREADS), 0, s, A, lda, B, ldb, C, ldc, M, N, K, rows);
         return;
     }
@@ -2423,6 +2447,12 @@ void launch_gemm(const float* A, long long lda, int a_kslow, const float* B, lon
         splits = (K + k_per - 1) / k_per;
     }
     float* so = splits > 1 ? split_ws : nullptr;
+    if (sched) {
+        sched->hi(sched->gemm_tiles_m_max, tiles_m);
+        sched->hi(sched->gemm_tiles_n_max, tiles_n);
+        sched->hi(sched->gemm_k_tiles_max, (std::min(K, k_per) + GK - 1) / GK);
+        sched->hi(sched->gemm_splits_max, splits);
+    }
     const dim3 grid((unsigned)tiles, (unsigned)splits), blk(512);
     if (!a_kslow && !b_kslow) hipLaunchKernelGGL((gemm_kernel<false, false>), grid, blk, 0, s, A, lda, B, ldb, bias, C, ldc, M, N, K, relu, tiles_n, k_per, so);
     else if (!a_kslow && b_kslow) hipLaunchKernelGGL((gemm_kernel<false, true>), grid, blk, 0, s, A, lda, B, ldb, bias, C, ldc, M, N, K, relu, tiles_n, k_per, so);

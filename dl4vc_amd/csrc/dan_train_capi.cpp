@@ -112,6 +112,7 @@ struct dan_trainer {
     bool pending = false;
     dev::Event ev_tail;
     float dp_mean_sites = 0.f, dp_ce_den[2] = {0.f, 0.f};     // dan_train_set_global_batch: for the next backward only
+    TrainSched sched;                                         // what the last step's launchers did (dan_train_query "sched:*")
 };
 
 namespace {
@@ -590,13 +591,13 @@ int forward_layer(dan_trainer* t, Step& st, int l) {
             if (t->wino_layer[l]) { a.w1 = t->pk_wino_f[l]; a.wino = 1; }
             a.bias1 = bias; a.relu_out = 1; a.out1 = t->d_a[l];
             a.stats = c.use_bn ? t->d_stats : nullptr;
-            st.stat_entries = launch_train_row(a, st.n_rows, s, stat_cap);
+            st.stat_entries = launch_train_row(a, st.n_rows, s, stat_cap, &t->sched);
             if ((rc = check_row_launch(t, st.stat_entries, "conv forward", l))) return rc;
         }
     }
     if (c.use_bn) {                                      // batch statistics over (B, R, L) per channel (model.py:750-751, train mode)
         int nb = 0;
-        launch_stats_partial(t->d_stats, st.stat_entries, t->d_bp, &nb, s);
+        launch_stats_partial(t->d_stats, st.stat_entries, t->d_bp, &nb, s, &t->sched);
         launch_bn_forward_finalize(t->d_bp, nb, st.n_pos, pp(t, lp.bn_g), pp(t, lp.bn_b), lp.cout, coef_f(t, l), t->d_smean + (size_t)l * CPAD,
                                    t->d_sinv + (size_t)l * CPAD, t->d_rmean + (size_t)l * CPAD, t->d_rvar + (size_t)l * CPAD, s);
     }
@@ -609,7 +610,7 @@ int forward_layer(dan_trainer* t, Step& st, int l) {
         }
         a.out1 = t->d_x[l];                              // (nullptr for a lazy layer: the launch then only writes h_l)
         if (c.bottleneck > 0) { a.w2 = t->pk_bot_f[l]; a.bias2 = bias + 2 * CPAD; a.out2 = h_of(t, l, st.n_rows); }
-        if ((rc = check_row_launch(t, launch_train_row(a, st.n_rows, s, stat_cap), "BatchNorm-apply / residual / bottleneck", l))) return rc;
+        if ((rc = check_row_launch(t, launch_train_row(a, st.n_rows, s, stat_cap, &t->sched), "BatchNorm-apply / residual / bottleneck", l))) return rc;
     }
     if (pool_after(c, l + 1)) launch_read_mean(t->d_x[l], t->d_pool[l + 1], st.B, c.reads, c.length, nullptr, s);
     return DAN_OK;
@@ -627,9 +628,9 @@ void forward_tail(dan_trainer* t, const Step& st) {
         launch_highway(t->d_h, (long long)st.n_rows * L * HPAD, t->d_wc_pk, (long long)L * 2 * 2 * 256, t->d_bc_pad, t->d_feat, t->F_stride, 2 * c.c_final * L, B, R, L,
                        c.bottleneck, NL, nullptr, s);
     launch_dropout(t->d_feat, st.mk[0], st.dscale, t->d_featd, B, t->F, t->F_stride, s);
-    launch_gemm(t->d_featd, t->F_stride, 0, pp(t, t->p_fc0w), t->F_stride, 0, pp(t, t->p_fc0b), t->d_hid0, t->n0_stride, B, t->n0, (int)t->F_stride, 1, t->d_split_ws, t->split_ws_floats, s);
+    launch_gemm(t->d_featd, t->F_stride, 0, pp(t, t->p_fc0w), t->F_stride, 0, pp(t, t->p_fc0b), t->d_hid0, t->n0_stride, B, t->n0, (int)t->F_stride, 1, t->d_split_ws, t->split_ws_floats, s, &t->sched);
     launch_dropout(t->d_hid0, st.mk[1], st.dscale, t->d_hid0d, B, t->n0, t->n0_stride, s);
-    launch_gemm(t->d_hid0d, t->n0_stride, 0, pp(t, t->p_fc1w), t->n0_stride, 0, pp(t, t->p_fc1b), t->d_hid1, t->n1_stride, B, t->n1, (int)t->n0_stride, 1, t->d_split_ws, t->split_ws_floats, s);
+    launch_gemm(t->d_hid0d, t->n0_stride, 0, pp(t, t->p_fc1w), t->n0_stride, 0, pp(t, t->p_fc1b), t->d_hid1, t->n1_stride, B, t->n1, (int)t->n0_stride, 1, t->d_split_ws, t->split_ws_floats, s, &t->sched);
     launch_dropout(t->d_hid1, st.mk[2], st.dscale, t->d_hid1d, B, t->n1, t->n1_stride, s);
     LossArgs a{};
     a.B = B; a.hid = t->n1; a.hid_stride = (int)t->n1_stride; a.hidden = t->d_hid1d; a.wh = pp(t, t->p_hw); a.bh = pp(t, t->p_hb);
@@ -652,15 +653,15 @@ int backward_fc(dan_trainer* t, const Step& st) {
     launch_heads_bwd(t->d_dlogits, t->d_hid1d, pp(t, t->p_hw), B, t->n1, (int)t->n1_stride, t->d_dhid1d, gp(t, t->p_hw), gp(t, t->p_hb), s);
     launch_dropout_relu_bwd(t->d_dhid1d, st.mk[2], st.dscale, t->d_hid1, 1, t->d_dhid1, B, t->n1, t->n1_stride, s);
     // FC2: gW1[n][k] = sum_b d1[b][n] hid0d[b][k];  d(hid0d) = d1 W1
-    launch_gemm(t->d_dhid1, t->n1_stride, 1, t->d_hid0d, t->n0_stride, 1, nullptr, gp(t, t->p_fc1w), t->n0_stride, t->n1, t->n0, B, 0, t->d_split_ws, t->split_ws_floats, s);
+    launch_gemm(t->d_dhid1, t->n1_stride, 1, t->d_hid0d, t->n0_stride, 1, nullptr, gp(t, t->p_fc1w), t->n0_stride, t->n1, t->n0, B, 0, t->d_split_ws, t->split_ws_floats, s, &t->sched);
     launch_colsum(t->d_dhid1, B, t->n1, t->n1_stride, gp(t, t->p_fc1b), s);
-    launch_gemm(t->d_dhid1, t->n1_stride, 0, pp(t, t->p_fc1w), t->n0_stride, 1, nullptr, t->d_dhid0d, t->n0_stride, B, t->n0, t->n1, 0, t->d_split_ws, t->split_ws_floats, s);
+    launch_gemm(t->d_dhid1, t->n1_stride, 0, pp(t, t->p_fc1w), t->n0_stride, 1, nullptr, t->d_dhid0d, t->n0_stride, B, t->n0, t->n1, 0, t->d_split_ws, t->split_ws_floats, s, &t->sched);
     launch_dropout_relu_bwd(t->d_dhid0d, st.mk[1], st.dscale, t->d_hid0, 1, t->d_dhid0, B, t->n0, t->n0_stride, s);
     // FC1
-    launch_gemm(t->d_dhid0, t->n0_stride, 1, t->d_featd, t->F_stride, 1, nullptr, gp(t, t->p_fc0w), t->F_stride, t->n0, t->F, B, 0, t->d_split_ws, t->split_ws_floats, s);
+    launch_gemm(t->d_dhid0, t->n0_stride, 1, t->d_featd, t->F_stride, 1, nullptr, gp(t, t->p_fc0w), t->F_stride, t->n0, t->F, B, 0, t->d_split_ws, t->split_ws_floats, s, &t->sched);
     launch_colsum(t->d_dhid0, B, t->n0, t->n0_stride, gp(t, t->p_fc0b), s);
     HIPT(t, hipEventRecord(t->ev_tail, s));                  // bucket 0 (FC stack + heads: the tail of the flat buffer) is final
-    launch_gemm(t->d_dhid0, t->n0_stride, 0, pp(t, t->p_fc0w), t->F_stride, 1, nullptr, t->d_dfeatd, t->F_stride, B, t->F, t->n0, 0, t->d_split_ws, t->split_ws_floats, s);
+    launch_gemm(t->d_dhid0, t->n0_stride, 0, pp(t, t->p_fc0w), t->F_stride, 1, nullptr, t->d_dfeatd, t->F_stride, B, t->F, t->n0, 0, t->d_split_ws, t->split_ws_floats, s, &t->sched);
     launch_dropout_relu_bwd(t->d_dfeatd, st.mk[0], st.dscale, nullptr, 0, t->d_dfeat, B, t->F, t->F_stride, s);
     return DAN_OK;
 }
@@ -684,7 +685,7 @@ void backward_highway_pools(dan_trainer* t, const Step& st) {
 // one weight (and bias) gradient of layer l: the partials of launch_train_wgrad, summed into gw / gb
 int wgrad(dan_trainer* t, const Step& st, WgradArgs& w, int l, const char* what, int n_out, int n_in, float* gw, float* gb) {
     w.R = t->cfg.reads; w.L = t->cfg.length; w.n_rows = st.n_rows; w.partial = t->d_partial; w.bias_partial = t->d_bias_partial;
-    const int wgs = launch_train_wgrad(w, st.s);
+    const int wgs = launch_train_wgrad(w, st.s, &t->sched);
     if (wgs < 1) return failt(t, DAN_ERR_STATE, "%s weight gradient of layer %d: no kernel form for its shape", what, l + 1);
     launch_wgrad_reduce(t->d_partial, t->d_bias_partial, wgs, w.taps, w.o_tiles * 16, w.c_tiles * 16, n_out, n_in, nullptr, gw, gb, st.s);
     return DAN_OK;
@@ -706,7 +707,7 @@ int accumulate_g(dan_trainer* t, Step& st, int l) {
     a.addb = pool_after(c, l + 1) ? t->d_dpool : nullptr;
     a.out1 = t->d_g[st.cur];
     if (!residual) { a.stats = t->d_stats; a.stat_aux = t->d_a[l]; }
-    const int e = launch_train_row(a, st.n_rows, st.s, t->stat_entries_max);
+    const int e = launch_train_row(a, st.n_rows, st.s, t->stat_entries_max, &t->sched);
     if (!residual) st.stat_entries = e;
     return check_row_launch(t, e, "g accumulation", l);
 }
@@ -718,7 +719,7 @@ int backward_residual(dan_trainer* t, Step& st, int l, const float* g) {
     a.src1 = g; a.s1_stride = CPAD;
     a.w1 = t->pk_res_d[l]; a.taps = 1; a.kg = KGC; a.dil = 0;
     a.out1 = t->d_dn; a.stats = t->d_stats; a.stat_aux = t->d_a[l];
-    st.stat_entries = launch_train_row(a, st.n_rows, st.s, t->stat_entries_max);
+    st.stat_entries = launch_train_row(a, st.n_rows, st.s, t->stat_entries_max, &t->sched);
     if (int rc = check_row_launch(t, st.stat_entries, "residual data gradient", l)) return rc;
     WgradArgs w{};
     w.a1 = g; w.a_stride = CPAD; w.b1 = t->d_a[l]; w.b_coef = coef_f(t, l);
@@ -734,7 +735,7 @@ int backward_layer1(dan_trainer* t, const Step& st, const float* dn) {
     w.R = t->cfg.reads; w.L = t->cfg.length; w.n_rows = st.n_rows; w.a1 = dn; w.a_stride = CPAD; w.a2 = t->d_a[0]; w.a_coef = t->d_coef_b; w.a_mask = 1;
     fill_encode(w, t, st.B);
     w.partial = t->d_partial;
-    const int e0 = launch_l0_backward(w, st.B, t->d_l0tot, pp(t, lp.conv_w), t->d_canon, lp.cout, lp.cin, gp(t, lp.conv_w), gp(t, lp.conv_b), gp(t, t->p_emb), st.s);
+    const int e0 = launch_l0_backward(w, st.B, t->d_l0tot, pp(t, lp.conv_w), t->d_canon, lp.cout, lp.cin, gp(t, lp.conv_w), gp(t, lp.conv_b), gp(t, t->p_emb), st.s, &t->sched);
     if (e0) return failt(t, DAN_ERR_HIP, "layer 1's backward: the device refuses %d B of dynamic LDS for l0_bins_kernel: %s", l0_bins_lds_bytes(), hipGetErrorString((hipError_t)e0));
     return DAN_OK;
 }
@@ -760,7 +761,7 @@ int backward_conv_data(dan_trainer* t, Step& st, int l, const float* dn, const f
         if (stats_below) { a.stats = t->d_stats; a.stat_aux = t->d_a[l - 1]; }
         st.fused_g = true;
     }
-    const int e = launch_train_row(a, st.n_rows, st.s, t->stat_entries_max);
+    const int e = launch_train_row(a, st.n_rows, st.s, t->stat_entries_max, &t->sched);
     if (int rc = check_row_launch(t, e, "conv data gradient", l)) return rc;
     if (st.fused_g && stats_below) st.stat_entries = e;
     if (pool_after(c, l)) launch_read_mean(t->d_du, t->d_dpool, st.B, c.reads, c.length, nullptr, st.s);     // u_l = x_{l-1} + mean_r x_{l-1}
@@ -782,7 +783,7 @@ int backward_layer(dan_trainer* t, Step& st, int l) {
     }
     {   // BatchNorm backward coefficients from sum(dn), sum(dn * a)  (identity without BatchNorm)
         int nb = 0;
-        launch_stats_partial(t->d_stats, st.stat_entries, t->d_bp, &nb, st.s);
+        launch_stats_partial(t->d_stats, st.stat_entries, t->d_bp, &nb, st.s, &t->sched);
         launch_bn_backward_coef(t->d_bp, nb, st.n_pos, pp(t, lp.bn_g), t->d_smean + (size_t)l * CPAD, t->d_sinv + (size_t)l * CPAD, lp.cout, c.use_bn,
                                 t->d_coef_b, gp(t, lp.bn_g), gp(t, lp.bn_b), st.s);
     }
@@ -824,6 +825,7 @@ int backward_begin(dan_trainer_t* t, bool device_planes, void* ready, const uint
     Step st{};
     st.B = (int)n_sites; st.n_rows = st.B * c.reads; st.n_pos = (double)st.n_rows * c.length; st.s = nullptr;
     t->last_B = st.B;
+    t->sched = TrainSched{};
     const uint8_t* const planes[6] = {reads, qual, strand, ref, ref_mask, var_mask};
     int rc;
     if ((rc = stage_inputs(t, st, device_planes, ready, planes, tg)) || (rc = make_dropout_masks(t, st, dropout_masks, seed))) return rc;
@@ -1077,6 +1079,20 @@ int64_t dan_train_query(const dan_trainer_t* t, const char* what) {
     if (!strcmp(what, "num_param_floats")) return t->n_flat;
     if (!strcmp(what, "feature_stride")) return t->F_stride;
     if (!strcmp(what, "feature_width")) return t->F;
+    if (!strncmp(what, "sched:", 6)) {                       // the last step's launches (dan_train.h TrainSched)
+        const TrainSched& q = t->sched;
+        const struct { const char* key; int v; } facts[] = {
+            {"rowh_units_per_wg_max", q.rowh_units_per_wg_max}, {"rowh_units_per_wg_min", q.rowh_units_per_wg_min},
+            {"rowh_stagger", q.rowh_stagger}, {"row_reads_per_wg_max", q.row_reads_per_wg_max},
+            {"wgrad3_rows_per_wg_max", q.wgrad3_rows_per_wg_max}, {"wgrad3_rows_per_wg_min", q.wgrad3_rows_per_wg_min},
+            {"wgrad1_rows_per_wg_max", q.wgrad1_rows_per_wg_max}, {"wgradpool_rows_per_wg_max", q.wgradpool_rows_per_wg_max},
+            {"l0_rows_per_wg_max", q.l0_rows_per_wg_max}, {"l0_partials", q.l0_partials},
+            {"stats_entries_per_block_max", q.stats_entries_per_block_max}, {"stats_blocks_max", q.stats_blocks_max},
+            {"gemm_tiles_m_max", q.gemm_tiles_m_max}, {"gemm_tiles_n_max", q.gemm_tiles_n_max},
+            {"gemm_k_tiles_max", q.gemm_k_tiles_max}, {"gemm_splits_max", q.gemm_splits_max}, {"fc1_streaming", q.fc1_streaming}};
+        for (const auto& f : facts)
+            if (!strcmp(what + 6, f.key)) return f.v;
+    }
     return failt(t, DAN_ERR_INVALID_ARG, "dan_train_query: unknown key '%s'", what);
 }
 

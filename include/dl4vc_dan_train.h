@@ -128,7 +128,25 @@ void* dan_train_grad_buffer(dan_trainer_t* t, int64_t* n_floats);
 int64_t dan_train_get_tensor(dan_trainer_t* t, const char* name, float* dst, int64_t capacity);
 /* Overwrite a parameter or running statistic after finalize (checkpoint restore). */
 int dan_train_put_tensor(dan_trainer_t* t, const char* name, const float* src, int64_t count);
-int64_t dan_train_query(const dan_trainer_t* t, const char* what);   /* "step", "max_batch", "num_param_floats", "feature_stride" */
+/* "step", "max_batch", "num_param_floats", "feature_stride", "feature_width", and the SCHEDULE FACTS of the last
+ * dan_train_backward[_begin] / dan_train_step under "sched:<fact>": what the step's launchers made of its row count
+ * (sites x reads) and the device's compute-unit count.  Host bookkeeping only -- no launch reads them; tests assert through
+ * them that a batch crossed the threshold it was sized for.  Maxima / minima are over the step's launches of the named
+ * kernel; 0 = that kernel did not run in the step (and every fact is 0 before the first step).
+ *   rowh_units_per_wg_max, rowh_units_per_wg_min   half-read units (2 per row) one train_rowh_kernel workgroup walks
+ *   rowh_stagger                                   1 if a train_rowh_kernel launch delayed its second workgroup per CU
+ *   row_reads_per_wg_max                           rows per train_row_kernel workgroup (whole reads: the Winograd form)
+ *   wgrad3_rows_per_wg_max, wgrad3_rows_per_wg_min rows per train_wgrad3_kernel workgroup (> 1: prefetch across rows)
+ *   wgrad1_rows_per_wg_max                         rows per train_wgrad1_kernel workgroup (the 1x1 weight gradients)
+ *   wgradpool_rows_per_wg_max                      rows per train_wgrad_kernel<3, true, 8> workgroup (the pooled layer)
+ *   l0_rows_per_wg_max, l0_partials                l0_bins_kernel: rows per workgroup; partial slices summed in order
+ *   stats_entries_per_block_max, stats_blocks_max  stats_partial_kernel: entries one block adds; blocks (= the partials
+ *                                                  the single-workgroup BatchNorm kernels add)
+ *   gemm_tiles_m_max, gemm_tiles_n_max,            gemm_kernel (FC stack from 17 sites on): 128 x 128 tiles along M and N,
+ *   gemm_k_tiles_max, gemm_splits_max              32-wide k-tiles per split, K splits
+ *   fc1_streaming                                  1 if an fc_skinny_* form ran (FC1 at up to 16 sites)
+ * Any other key: DAN_ERR_INVALID_ARG, "dan_train_query: unknown key '<what>'". */
+int64_t dan_train_query(const dan_trainer_t* t, const char* what);
 
 #ifdef __cplusplus
 }

@@ -17,12 +17,12 @@ from oracle import dan_train_oracle as O   # noqa: E402
 from dl4vc_amd.train import DanTrainer     # noqa: E402
 
 
-def decision_differences(seed, log=None):
+def decision_differences(seed, log=None, **shape):
     """[(where, count, largest |oracle value| among the differing decisions relative to the tensor's scale)]"""
-    kw, cfg, sd, batch, hp, tg, masks = T.random_train_case(seed)
+    kw, cfg, sd, batch, hp, tg, masks = T.random_train_case(seed, **shape)
     ohp = O.TrainHyper(**{k: getattr(hp, k) for k in O.TrainHyper.__dataclass_fields__})
     w64 = O.train_step_oracle(sd, cfg, batch.arrays(), tg, ohp, dropout_masks=masks, dtype=torch.float64, taps=True)
-    tr = DanTrainer(cfg, hp, max_batch=8).load_state_dict(sd)
+    tr = DanTrainer(cfg, hp, max_batch=max(8, len(batch))).load_state_dict(sd)
     tr.backward(batch.arrays(), tg, dropout_masks=masks)
     B, R, L = len(tg["label"]), cfg.reads, cfg.length
     out = []
