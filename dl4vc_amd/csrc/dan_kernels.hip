@@ -136,6 +136,7 @@ __global__ __launch_bounds__(SEG_THREADS, NWAVE / 4) void segment_kernel(Segment
     // the one-unit six-tile strips are walked in F(4,3) form, three tiles of four outputs (conv_gemm_wino43); the split form's and the
     // seven-tile strips in F(2,3) form
     constexpr bool W43 = WINO && !SPLIT && TW == MW_SHORT;
+    constexpr bool WBOT_EARLY = W43;       // the deferred bottleneck GEMM's fragments requested behind the conv GEMM (Winograd layer body)
     // one allocation, so that the layout the Winograd tiles past the window rely on (constants right after the activation
     // rows) is explicit
     __shared__ __attribute__((aligned(16))) float lds[LDS_ROWS * LDS_S + MAX_LAYERS * CST_FLOATS];
@@ -530,6 +531,16 @@ next_row:                                                   // (PERSIST only: ba
                 conv_gemm_wino(acc, xw - 2 * LDS_S + kk * 4, w_w, pre_w);
             }
             STAMP(sb + 1);
+            // F(4,3) forms, a stage that hosts the previous layer's deferred bottleneck GEMM (below): the waves that will run it request
+            // its eight weight fragments here, behind their last conv MFMA, so that the loaded-L2 latency falls under their own output
+            // transform and not in front of that GEMM's first MFMA -- they are the waves barrier A waits for (HISTORY.md section 41)
+            if constexpr (WBOT_EARLY) {
+                if (a.has_hw && l > a.l_begin && wave < NWAVE / 2) {
+                    gv4f_ptr w_bp = (gv4f_ptr)(wblk - LAYER_STRIDE + WBOT_OFF) + lane;
+#pragma unroll
+                    for (int g = 0; g < KGC; ++g) wbot[g] = w_bp[(g * 2 + (wave & 1)) * 64];
+                }
+            }
             asm volatile("" : "+v"(wp));       // keeps everything derived from it (addresses, masks) out of the GEMM's live set
             if constexpr (REM) asm volatile("" : "+v"(rp));
             xq = xs + (HALO + wp) * LDS_S;
@@ -615,9 +626,12 @@ next_row:                                                   // (PERSIST only: ba
         }
         // the previous layer's bottleneck GEMM (deferred by its layer_tail): the LDS image is still that layer's output
         if (a.has_hw && l > a.l_begin && wave < NWAVE / 2) {
-            gv4f_ptr w_bp = (gv4f_ptr)(wblk - LAYER_STRIDE + WBOT_OFF) + lane;
+            if constexpr (!WBOT_EARLY) {
+                gv4f_ptr w_bp = (gv4f_ptr)(wblk - LAYER_STRIDE + WBOT_OFF) + lane;
 #pragma unroll
-            for (int g = 0; g < KGC; ++g) wbot[g] = w_bp[(g * 2 + (wave & 1)) * 64];
+                for (int g = 0; g < KGC; ++g) wbot[g] = w_bp[(g * 2 + (wave & 1)) * 64];
+            }
+            STAMP(42 + (l - a.l_begin));                    // (stamps 42 ..: waves 0-3 in front of the deferred bottleneck GEMM; behind it: sb + 2)
             bottleneck<NWAVE / 2, SPLIT, TILES>(xs, wbot, lc - CST_FLOATS + CST_BBOT,
                                          a.h + (size_t)(l - 1) * a.h_layer_stride + (read_idx * (size_t)Lw + u_off) * HPAD, own_hi, wave, lane, own_lo);
         }

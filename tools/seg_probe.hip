@@ -3,6 +3,7 @@
 //   hipcc -O3 --offload-arch=gfx950 -DDAN_STAMPS tools/seg_probe.hip -o /tmp/seg_probe && /tmp/seg_probe [l_begin l_end [0 [wino [L [table 0|1 [fold 0|1]]]]]]
 // fold 1: the site-owning form (SegmentArgs::fold) at 256 sites, one per workgroup; its row end has stamps of its own (56 planes
 // requested, 57 last bottleneck GEMM done, 58 planes updated and stored) and every read of a site is a stamp row.
+// Winograd forms: a line per conv stage that hosts the previous layer's deferred bottleneck GEMM (stamp 42 + i on waves 0-3 in front of it).
 #include "../dl4vc_amd/csrc/dan_kernels.hip"
 #include <cstdio>
 #include <cstdlib>
@@ -49,6 +50,9 @@ int main(int argc, char** argv) {
     a.tap = nullptr; a.tap_layer = -1; a.wino = wino;
     // (precision != 0 selected the round-3 bf16 kernel, deleted in round 4: the bf16 families have probes of their own, segx / segp)
     if (precision != 0) { printf("seg_probe covers the fp32 kernel only: use tools/segx_probe.hip / tools/segp_probe.hip\n"); return 1; }
+    // stamp slots: layer i of the segment has 2 + 8 i .. 9 + 8 i, the deferred bottleneck of stage i sits at 42 + i, the row end at 56 .. 58,
+    // 62, 63 -- a sixth layer's slots (42 .. 49) would collide with the bottleneck stamps, a seventh's with the row end's
+    if (l_end - l_begin > 5) { printf("seg_probe stamps segments of up to five layers (the stamp slots of a sixth collide)\n"); return 1; }
     // layer 1 by table (dan_kernels.h L0_*): an all-zero table exercises the walk's instruction stream
     float* d_l0;
     CK(hipMalloc(&d_l0, l0_tab_floats(L) * 4)); CK(hipMemset(d_l0, 0, l0_tab_floats(L) * 4));
@@ -90,6 +94,33 @@ int main(int argc, char** argv) {
                l + 1, med(l == l_begin ? 1 : sb - 1, sb, -1), med(sb, sb + 1, -1), med(sb, sb + 1, 0), med(sb, sb + 1, 3),
                med(sb + 1, sb + 2, -1), med(sb + 2, sb + 3, -1), med(sb + 3, sb + 4, -1), med(sb + 4, sb + 5, -1),
                med(((a.res_mask >> l) & 1) ? sb + 5 : sb + 3, sb + 6, -1), med(sb + 6, sb + 7, -1), med(sb + 6, sb + 7, 0), med(sb + 6, sb + 7, 3));
+    }
+    if (wino) {
+        // conv stages that host the previous layer's deferred bottleneck GEMM: where the older waves (0-3, which run it) and the
+        // younger waves (4-7) stand, in cycles from wave 0's conv start of the same row (medians over rows and the group's waves).
+        // Stamp 42 + i: waves 0-3 in front of the bottleneck GEMM; sb + 1 / sb + 2 / sb + 3: conv GEMM done / in front of barrier A / behind it
+        auto rel = [&](int k, int base, int w_lo, int w_hi) {
+            std::vector<long long> d;
+            for (int wg = 0; wg < nwg; ++wg) {
+                const unsigned long long* s0 = &st[((size_t)wg * NWAVE + 0) * NSTAMP];
+                for (int w = w_lo; w < w_hi; ++w) {
+                    const unsigned long long* s = &st[((size_t)wg * NWAVE + w) * NSTAMP];
+                    if (s0[base] && s[k]) d.push_back((long long)(s[k] - s0[base]));
+                }
+            }
+            if (d.empty()) return -1LL;
+            std::sort(d.begin(), d.end());
+            return d[d.size() / 2];
+        };
+        for (int l = l_begin + 1; l < l_end; ++l) {
+            const int i = l - l_begin, sb = 2 + i * 8, h = NWAVE / 2;
+            const long long o_conv = rel(sb + 1, sb, 0, h), o_pre = rel(42 + i, sb, 0, h), o_bot = rel(sb + 2, sb, 0, h), o_a = rel(sb + 3, sb, 0, h),
+                            y_conv = rel(sb + 1, sb, h, NWAVE), y_epi = rel(sb + 2, sb, h, NWAVE), y_a = rel(sb + 3, sb, h, NWAVE);
+            printf("L%d hosts L%d's bottleneck | older: conv end %6lld, at the bottleneck %6lld, bottleneck done %6lld, barrier A passed %6lld"
+                   " | younger: conv end %6lld, epilogue done %6lld, barrier A passed %6lld"
+                   " | bottleneck span %5lld, older's wait at A %5lld, younger's epilogue %5lld, younger's wait at A %5lld\n",
+                   l + 1, l, o_conv, o_pre, o_bot, o_a, y_conv, y_epi, y_a, o_bot - o_pre, o_a - o_bot, y_epi - y_conv, y_a - y_epi);
+        }
     }
     {   // per-wave view of the second layer of the segment: conv start relative to wave 0's, conv length, barrier wait
         const int l = l_begin + 1 < l_end ? l_begin + 1 : l_begin, sb = 2 + (l - l_begin) * 8;
